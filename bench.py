@@ -23,10 +23,19 @@ on the batch size (tests/test_detector_gpu.py::test_detector_batch_equals_single
           warps the boxes while the GPUs carry on -- all inside the timed region. No other collective.
 
 Weak scaling: per-rank work is fixed, value = N*K frames / max-over-ranks time. ONE JSON line (rank 0).
+
+A plain run does what its headline needs and nothing else: set up, warm up, time the K steps, print the line
+(`value`, `ms_per_step` = milliseconds per timed step). `--full` adds everything else the line can carry: the in-run
+kernel timings (`roofline`, `kernels`), the CPU baseline, and the secondary measurements that child processes of the
+run make (`f16`, `f32_exact`, `nms_load`, `every_row_every_pass`, `botsort`, `host_frames`, `from_file`, `pipelined`,
+the rocprofv3 traffic passes). `--dump-outputs DIR` writes what the timed path returned in its last step as
+DIR/<name>.npy (float32, or float64 where the path computes float64); the inputs are seeded, so two builds run with
+the same arguments can be compared array by array.
 """
 from __future__ import annotations
 
 import argparse
+import collections
 import json
 import os
 
@@ -116,6 +125,12 @@ def parse():
     ap.add_argument("--no-live-traffic", action="store_true", help="roofline.traffic from the committed PMC summary instead of two rocprofv3 --pmc child passes of this run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="--workload extract / detect: also measure what the headline does not need (roofline and per-kernel timings, CPU baseline, "
+                         "the secondary keys measured by child processes); a plain run only times its steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB; a seeded sample of a larger output)")
     ap.add_argument("--launch-check", action="store_true",
                     help="start the ranks, run one all_reduce over the chosen backend and print {launch_check, n_gpus, ranks_seen} -- no GPU work "
                          "(the CPU-side test of the --gpus N self-launch)")
@@ -189,6 +204,47 @@ def launch_check(args) -> int:
     if rank == 0:
         print(json.dumps({"launch_check": True, "n_gpus": world, "ranks_seen": bin(seen).count("1"), "backend": args.backend}), flush=True)
     return 0
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays: dict) -> None:
+    """--dump-outputs: every array as <out_dir>/<name>.npy, float64 where the path computed float64 and float32 otherwise
+    (integer ids and classes are exact in float32); refuses more than DUMP_LIMIT_BYTES in all."""
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in conv.items():
+        np.save(d / f"{name}.npy", a)
+
+
+def seeded_rows(n_rows: int, n_pick: int) -> np.ndarray:
+    """The fixed sample of rows --dump-outputs takes from an output too large to write whole: sorted, seed 0."""
+    return np.sort(np.random.default_rng(0).choice(n_rows, size=min(n_pick, n_rows), replace=False))
+
+
+def frame_outputs(results) -> dict:
+    """The per-frame results the engine returned in one step (geotrax_amd.engine.FrameResult), as --dump-outputs writes them:
+    frame<j>_* for the j-th frame of the step; an empty array where the frame has no boxes, NaN where it has no homography."""
+    out = {}
+    for j, r in enumerate(results):
+        p = f"frame{j}_"
+        out[p + "xyxy"] = np.asarray(r.xyxy).reshape(-1, 4)
+        out[p + "conf"] = np.asarray(r.conf).reshape(-1)
+        out[p + "cls"] = np.asarray(r.cls).reshape(-1)
+        out[p + "ids"] = np.zeros(0, np.float32) if r.ids is None else np.asarray(r.ids).reshape(-1)
+        out[p + "xywh_stab"] = np.zeros((0, 4), np.float32) if r.xywh_stab is None else np.asarray(r.xywh_stab).reshape(-1, 4)
+        out[p + "H"] = np.full((3, 3), np.nan) if r.H is None else np.asarray(r.H)
+        if r.gmc is not None:
+            out[p + "gmc"] = np.asarray(r.gmc)
+    return out
 
 
 def fp32_split(args):
@@ -401,6 +457,8 @@ def bench_register(args):
     for _ in range(steps):
         Hm, stats, tm = register_once(b, a, **kw)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"H": Hm, "stats": stats})
     ys, xs = np.meshgrid(np.linspace(0, H - 1, 9), np.linspace(0, W - 1, 16), indexing="ij")
     P = np.stack([xs.ravel(), ys.ravel(), np.ones(xs.size)])
     pa, pb = Hm @ P, np.linalg.inv(scene.camera(40, 150)) @ P
@@ -471,6 +529,8 @@ def bench_register_ortho(args):
     for _ in range(steps):
         Hm, stats, tm = register_once(frame, ortho, **kw)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"H": np.full((3, 3), np.nan) if Hm is None else Hm, "stats": stats})
     free1, _ = mem()
     ys, xs = np.meshgrid(np.linspace(0, H - 1, 9), np.linspace(0, W - 1, 16), indexing="ij")
     P = np.stack([xs.ravel(), ys.ravel(), np.ones(xs.size)])
@@ -528,6 +588,9 @@ def bench_georef(args):
     for _ in range(steps):
         out = transform_points(x, y, Hm, ortho, "EPSG:4326", "EPSG:5186", ctx=ctx)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:                                         # 2 M rows x 6 float64 columns: a seeded sample of 262 144 rows
+        rows = seeded_rows(n, 1 << 18)
+        dump_outputs(args.dump_outputs, {"row_index": rows.astype(np.float64), **{k: np.asarray(v)[rows] for k, v in out.items()}})
     m = 200_000                                                   # CPU baseline: the host chain (reference-like numpy) on a bounded sample
     t0 = time.perf_counter()
     ox, oy = apply_homography(x[:m], y[:m], Hm)
@@ -569,6 +632,9 @@ def bench_warp(args):
     elapsed = time.perf_counter() - t0
     out_frame = np.empty_like(frame)
     ctx.dev_download(out_frame, wp.dst)
+    if args.dump_outputs:                                         # 8.3 M BGR pixels: a seeded sample of 1 M of them
+        px = seeded_rows(H * W, 1 << 20)
+        dump_outputs(args.dump_outputs, {"pixel_index": px.astype(np.float64), "bgr": out_frame.reshape(-1, 3)[px]})
     nbytes = 2.0 * frame.nbytes
     gbs = nbytes * steps / elapsed / 1e9
     line = {"metric": "4K frames/sec through the perspective frame warp", "value": steps / elapsed, "unit": "frames/s", "n_gpus": 1,
@@ -843,6 +909,9 @@ def bench_cli(args):
 
 def main():
     args = parse()
+    if args.dump_outputs and args.workload in ("cli", "extract+georef"):
+        print(f"bench.py: --dump-outputs is not available for --workload {args.workload}", file=sys.stderr)
+        sys.exit(2)
     rc = self_launch(args)                                  # --gpus N > 1 without a launcher: N ranks as a child process, nothing of HIP touched here
     if rc is not None:
         sys.exit(rc)
@@ -995,6 +1064,7 @@ def main():
     if extract and stab_kw is not None:
         engine.set_reference(ref_frame)                          # every rank registers against frame 0 of the clip
     records = []
+    last_step = collections.deque(maxlen=B) if args.dump_outputs else None   # --dump-outputs: the results of the newest step
 
     def run(k0, n_steps, sharded):
         """n_steps batches through the engine; per-frame results are identical to the frame-at-a-time order."""
@@ -1006,6 +1076,8 @@ def main():
         t_run = time.perf_counter()
         for r in engine.run(src):
             n_rows = len(r.xyxy)
+            if last_step is not None:
+                last_step.append(r)
             if stamps is not None:
                 stamps.append(time.perf_counter() - t_run)
             if sharded and extract:
@@ -1090,7 +1162,8 @@ def main():
             if args.backend == "nccl":
                 torch.cuda.synchronize()
 
-    if rank == 0 and not args.no_profile:
+    profile = args.full and not args.no_profile                  # in-run HIP-event timings (roofline, kernels): --full only
+    if rank == 0 and profile:
         for d in engine.dets:
             d.trace(args.trace_every)
     worker = None
@@ -1131,6 +1204,8 @@ def main():
     barrier()
     if host_feed is not None:
         host_feed.close()
+    if last_step is not None and rank == 0 and failure is None:
+        dump_outputs(args.dump_outputs, frame_outputs(last_step))
 
     if rank == 0:
         dt = "f16" if args.half else ("f32s" if det.fp32_split else "f32")
@@ -1171,7 +1246,8 @@ def main():
         }
         if failure is not None:
             out["error"] = failure + " -- the measurement is void (a rank that fails still joins the gathers, so nobody hangs)"
-        if not args.no_profile:
+        secondary = args.full and world == 1 and dist is None     # the keys measured by child processes of this run: --full only
+        if profile:
             # kernel durations as they were inside the timed region: HIP events in front of every launch of
             # every --trace-every-th pass, on the stream the kernels were launched on (gtx_detector_trace)
             merged = {}
@@ -1251,7 +1327,7 @@ def main():
                                    "tflops": (d["flops"] / (d["total_ms"] * 1e-3) / 1e12) if d["total_ms"] > 0 else 0.0,
                                    "algo_gbs": (d["bytes"] / (d["total_ms"] * 1e-3) / 1e9) if d["total_ms"] > 0 else 0.0}
                                   for d in fam]
-        if world == 1 and dist is None and not args.half and not args.no_f16_line:
+        if secondary and not args.half and not args.no_f16_line:
             # secondary key: the same workload with ultralytics.half = true (a legitimate reference knob, not its default). Run as
             # a child process after this one has released the GPU: a second engine inside this process inherits its hardware-queue
             # mapping from the streams created (and not yet destroyed) above and measures ~25 % low.
@@ -1272,7 +1348,7 @@ def main():
                                       "process of this run after the primary measurement; secondary, not `value`"}
             except Exception as e:                                  # the secondary line must never void the primary one
                 out["f16"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
-        if world == 1 and dist is None and not args.half and det.fp32_split and not args.no_f16_line:
+        if secondary and not args.half and det.fp32_split and not args.no_f16_line:
             # secondary key: the strict fp32 arithmetic (v_mfma_f32_32x32x2_f32, no split) of the same workload, so that the
             # driver's line carries the exact-fp32 number next to the split-f16x3 one
             import subprocess
@@ -1290,7 +1366,7 @@ def main():
                                             "after the primary measurement; secondary, not `value`"}
             except Exception as e:
                 out["f32_exact"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
-        if world == 1 and dist is None and args.model == "yolov8s" and not args.half and args.workload == "extract" and args.tracker == "bytetrack" and not args.no_f16_line \
+        if secondary and args.model == "yolov8s" and not args.half and args.workload == "extract" and args.tracker == "bytetrack" and not args.no_f16_line \
                 and not args.candidates:
             # secondary key: the same pipeline under the post-processing load SURVEY 8d names (1-3 k anchors above conf per frame). The
             # seeded weights cannot cluster them the way a trained model does (their boxes sit on their anchors: neighbours overlap at
@@ -1311,7 +1387,7 @@ def main():
                                            "tracker and box warp at ~8 x the golden clip's box count; measured by a child process, secondary, not `value`"}
             except Exception as e:
                 out["nms_load"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
-        if world == 1 and dist is None and args.model == "yolov8s" and not args.half and args.workload == "extract" and args.tracker == "bytetrack" and not args.no_f16_line \
+        if secondary and args.model == "yolov8s" and not args.half and args.workload == "extract" and args.tracker == "bytetrack" and not args.no_f16_line \
                 and os.environ.get("GTX_PAD_SKIP", "1") != "0":
             # secondary key: the same line with every row of every layer and every pixel of the Detect box branch computed in every pass
             import subprocess
@@ -1331,7 +1407,7 @@ def main():
                 out["every_row_every_pass"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
             if "roofline" in out:                                 # next to executed / nominal: the frame rate when every nominal FLOP is executed
                 out["roofline"]["value_every_row_every_pass"] = out["every_row_every_pass"].get("value")
-        if world == 1 and dist is None and args.model == "yolov8s" and not args.half and args.workload == "extract" and args.tracker == "bytetrack" and not args.no_f16_line:
+        if secondary and args.model == "yolov8s" and not args.half and args.workload == "extract" and args.tracker == "bytetrack" and not args.no_f16_line:
             # secondary key: the N > 1 default workload (BoT-SORT + GPU GMC, BASELINE configs[4]) on this one GPU, so that a scaling
             # series started from this line has its like-for-like single-GPU base in it (the primary line here is configs[2], ByteTrack)
             import subprocess
@@ -1349,7 +1425,7 @@ def main():
                                           "measured by a child process of this run, secondary, not `value`"}
             except Exception as e:
                 out["botsort"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
-        if world == 1 and dist is None and args.model == "yolov8s" and not args.half and args.workload == "extract" and args.tracker == "bytetrack" and not args.no_f16_line \
+        if secondary and args.model == "yolov8s" and not args.half and args.workload == "extract" and args.tracker == "bytetrack" and not args.no_f16_line \
                 and not args.host_frames:
             # secondary keys: what the same pipeline delivers when the frames do not start in HBM. `host_frames`: pageable host arrays,
             # uploaded inside the timed region (PCIe-inclusive); `from_file`: the product's own loop on a clip file on local disk
@@ -1381,7 +1457,7 @@ def main():
                                             "open file to the aggregated tables, read-ahead feeder; measured by a child process, secondary, not `value`"}
             except Exception as e:
                 out["from_file"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
-        if world == 1 and dist is None and args.model == "yolov8s" and not extract and B == 1 and args.det_streams == 1 and not args.no_f16_line:
+        if secondary and args.model == "yolov8s" and not extract and B == 1 and args.det_streams == 1 and not args.no_f16_line:
             # BASELINE configs[1] is "batch=1": one frame per pass. With ONE pass in flight a pass is ~46 short launches and the chip
             # idles between them (latency-bound: `value`); with two or three single-frame passes in flight on streams of their own
             # the same kernels fill each other's gaps. Secondary key, child processes.
@@ -1398,7 +1474,7 @@ def main():
                 except Exception as e:
                     out["pipelined"][f"{ns}_streams"] = None
                     out["pipelined"]["error"] = f"{type(e).__name__}: {e}"
-        if world == 1 and dist is None and "roofline" in out and not args.no_live_traffic and not args.no_f16_line and not args.host_frames:
+        if secondary and "roofline" in out and not args.no_live_traffic and not args.no_f16_line and not args.host_frames:
             # roofline.traffic measured in THIS run: the engine has been closed above, the children run alone
             try:
                 engine.close()
@@ -1415,7 +1491,7 @@ def main():
         out["host"] = {"cores": host_cores(), "threads_per_rank": engine.host_threads + (1 if (sharded and extract and rank == 0) else 0) + 1,
                        "note": "engine stage threads (blocking waits: they sleep while the GPU works) + the main thread" +
                                (" + rank 0's tracker replay thread" if (sharded and extract) else "")}
-        if not args.no_cpu_baseline and world == 1:             # rank 0 at N = 1 only (the other ranks would sit in the barrier below)
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only (the other ranks would sit in the barrier below)
             out["cpu_baseline"] = cpu_baseline(weights, ref_frame, frames[1], args)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -20,7 +20,7 @@ def _last_json(out: str) -> dict:
 
 
 def test_single_gpu_line_has_the_contract_fields():
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "120", "--warmup", "8", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "120", "--warmup", "8", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _last_json(p.stdout)
@@ -53,6 +53,50 @@ def test_single_gpu_line_has_the_contract_fields():
     nl = d["nms_load"]
     assert 1800 <= nl["candidates_per_frame"] <= 2200 and nl["detections_per_frame"] > 400 and nl["value"] > 0.5 * d["value"], nl
     assert "nms_small" in nl["nms_path"] and "nms_small" in d["config"]["nms_path"]
+
+
+def test_plain_line_times_its_steps_and_dumps_the_same_last_step_twice(tmp_path):
+    """A plain run (no --full) carries the headline only, `steps` timed steps at `ms_per_step` each; --dump-outputs writes the
+    last step's per-frame results, and a second run with the same arguments writes the same arrays."""
+    import numpy as np
+
+    dumps = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "4", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
+        d = _last_json(p.stdout)
+        assert d["steps"] == 12 and d["warmup"] == 4 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"].startswith("f32")
+        B = d["config"]["frames_per_step"]
+        assert d["value"] > 100 and abs(d["value"] * d["ms_per_step"] - 1000.0 * B) < 1e-6 * d["value"] * d["ms_per_step"]
+        for k in ("roofline", "kernels", "cpu_baseline", "f16", "f32_exact", "nms_load", "every_row_every_pass", "botsort", "host_frames", "from_file"):
+            assert k not in d, k
+        files = sorted((tmp_path / run).glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        dumps.append({f.stem: np.load(f) for f in files})
+    a, b = dumps
+    assert set(a) == set(b) and {f"frame{j}_{k}" for j in range(B) for k in ("xyxy", "conf", "cls", "ids", "xywh_stab", "H")} <= set(a)
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+    for j in range(B):
+        n = len(a[f"frame{j}_xyxy"])
+        assert n > 50 and a[f"frame{j}_ids"].shape == (n,) and a[f"frame{j}_xywh_stab"].shape == (n, 4)
+        assert a[f"frame{j}_H"].dtype == np.float64 and np.isfinite(a[f"frame{j}_H"]).all()
+
+
+@pytest.mark.parametrize("workload,names", [("warp", {"pixel_index", "bgr"}), ("georef", {"row_index", "x_local", "y_local"}), ("register", {"H", "stats"})],
+                         ids=["warp", "georef", "register"])
+def test_single_gpu_workloads_dump_their_last_step(tmp_path, workload, names):
+    import numpy as np
+
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", workload, "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
+    assert _last_json(p.stdout)["steps"] == 3
+    got = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+    assert names <= set(got) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
 
 
 @pytest.mark.parametrize("mode,tracker", [("frames", "bytetrack"), ("frames", "botsort"), ("videos", "bytetrack")])
@@ -103,7 +147,7 @@ def test_configs1_detector_only_batch1_one_stream():
     """BASELINE configs[1]: YOLOv8s HIP inference only on 3840x2160 frames, batch 1, one stream (`value`: one pass in flight,
     latency-bound); the same single-frame passes with two and three in flight ride along under `pipelined`."""
     p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "detect", "--batch", "1", "--det-streams", "1", "--steps", "60",
-                        "--warmup", "10", "--no-cpu-baseline", "--no-profile"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--warmup", "10", "--no-cpu-baseline", "--no-profile", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     d = _last_json(p.stdout)
     c = d["config"]

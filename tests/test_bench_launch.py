@@ -52,6 +52,36 @@ def test_single_gpu_workloads_refuse_n_ranks():
     assert p.returncode == 2 and "single-GPU" in p.stderr
 
 
+def test_dump_outputs_refuses_workloads_without_a_dump():
+    p = _run(["--workload", "cli", "--dump-outputs", "unused"])
+    assert p.returncode == 2 and "--dump-outputs" in p.stderr and not p.stdout.strip()
+
+
+def test_dump_outputs_writes_float32_or_float64_within_the_limit(tmp_path):
+    """bench.dump_outputs / frame_outputs in a child process (importing bench.py sets process-wide defaults)."""
+    code = f"""
+import numpy as np, types, bench
+r = types.SimpleNamespace(xyxy=np.ones((3, 4), np.float32), conf=np.ones(3, np.float32), cls=np.array([0, 2, 1], np.int32),
+                          ids=np.array([5, 6, 7], np.int64), xywh_stab=None, H=None, gmc=np.eye(2, 3))
+out = bench.frame_outputs([r])
+bench.dump_outputs({str(tmp_path / "d")!r}, dict(out, big=np.zeros(10, np.float64)))
+try:
+    bench.dump_outputs({str(tmp_path / "e")!r}, {{"x": np.zeros((bench.DUMP_LIMIT_BYTES // 4) + 1, np.int32)}})
+except ValueError:
+    print("refused")
+"""
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0 and p.stdout.strip() == "refused", p.stdout + p.stderr
+    import numpy as np
+
+    got = {f.stem: np.load(f) for f in (tmp_path / "d").glob("*.npy")}
+    assert set(got) == {"frame0_xyxy", "frame0_conf", "frame0_cls", "frame0_ids", "frame0_xywh_stab", "frame0_H", "frame0_gmc", "big"}
+    assert got["frame0_cls"].dtype == np.float32 and got["frame0_cls"].tolist() == [0, 2, 1] and got["frame0_ids"].tolist() == [5, 6, 7]
+    assert got["frame0_H"].dtype == np.float64 and np.isnan(got["frame0_H"]).all() and got["frame0_xywh_stab"].shape == (0, 4)
+    assert got["frame0_gmc"].dtype == np.float64 and got["big"].dtype == np.float64
+    assert not (tmp_path / "e").exists()
+
+
 def test_gpus_1_launches_nothing():
     d = _json(_run(["--gpus", "1", "--launch-check"]).stdout)
     assert d["n_gpus"] == 1 and d["ranks_seen"] == 1
