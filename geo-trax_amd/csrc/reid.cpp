@@ -1,0 +1,568 @@
+// Embedder (reid.hpp): YOLOv8-cls backbone over a batch of detection crops, pooled into one vector per crop, and its C ABI.
+//
+// What upstream does per frame (ultralytics >= 8.4.80, trackers/bot_sort.py ReID.__call__), and where it is done here:
+//   crops = [save_one_box(det, img, save=False) for det in xywh2xyxy(dets[:, :4])]   -> reid_crop_box (host)
+//   ClassificationPredictor.preprocess: classify_transforms(imgsz) on each crop         -> reid_resample_coeffs (host) + reid_crop_kernel
+//   model(crops, embed=[len(model) - 2]): adaptive_avg_pool2d(model.8 output)           -> the conv graph below + reid_pool_kernel
+// Choices restated from memory of the pinned upstream rather than pinned by a test against it (the resample is pinned against PIL):
+//   - the box chain: Boxes.xywh in float32, then float64 (BOTSORT.init_track concatenates the boxes with np.arange), save_one_box's
+//     gain 1.02 / pad 10 / .long() truncation and clip to the frame;
+//   - the channel order the network sees (kNetChannelsBgr);
+//   - the embedded layer: model.8, the last backbone layer of yolov8-cls (len(model) - 2 for a .pt checkpoint).
+#include "reid.hpp"
+#include "api_guard.hpp"
+#include "split_format.hpp"
+
+#include <cmath>
+
+namespace gtx {
+
+// save_one_box(..., BGR=False) reverses the crop's channels and ClassificationPredictor.preprocess applies cv2.cvtColor(BGR2RGB)
+// before the PIL transforms: reversed twice, the network's input channel 0 is the frame's B. reid_crop_kernel writes the
+// frame's bytes in their own order into the stem's channel slots, which is that order.
+constexpr bool kNetChannelsBgr = true;
+static_assert(kNetChannelsBgr, "reid_crop_kernel writes slot c = frame byte c");
+
+namespace {
+constexpr int kPrecBits = 22;   // PIL PRECISION_BITS
+
+bool env_on(const char* name, bool dflt) {
+  const char* e = getenv(name);
+  return (e && *e) ? e[0] != '0' : dflt;
+}
+
+// PIL Resample.c precompute_coeffs (bilinear filter, support 1) + normalize_coeffs_8bpc for output indices [first, first + S) of
+// out_size: bounds [S][2] (xmin, count) and int coefficients [S][ksize] appended to pool. Returns ksize. Double arithmetic,
+// one rounding per operation.
+int reid_resample_coeffs(int in_size, int out_size, int first, int S, std::vector<int>& pool, int* boff, int* koff) {
+#pragma clang fp contract(off)
+  const double scale = (double)(float)in_size / out_size;
+  const double filterscale = scale < 1.0 ? 1.0 : scale;
+  const double support = 1.0 * filterscale;
+  const int ksize = (int)std::ceil(support) * 2 + 1;
+  *boff = (int)pool.size();
+  pool.resize(pool.size() + 2 * (size_t)S);
+  *koff = (int)pool.size();
+  pool.resize(pool.size() + (size_t)S * ksize, 0);
+  std::vector<double> k(ksize);
+  for (int i = 0; i < S; ++i) {
+    const int xx = first + i;
+    const double center = 0.0 + (xx + 0.5) * scale;
+    double ww = 0.0;
+    const double ss = 1.0 / filterscale;
+    int xmin = (int)(center - support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + support + 0.5);
+    if (xmax > in_size) xmax = in_size;
+    xmax -= xmin;
+    for (int x = 0; x < xmax; ++x) {
+      double t = (x + xmin - center + 0.5) * ss;
+      if (t < 0.0) t = -t;
+      const double wgt = t < 1.0 ? 1.0 - t : 0.0;
+      k[x] = wgt;
+      ww += wgt;
+    }
+    for (int x = 0; x < xmax; ++x)
+      if (ww != 0.0) k[x] /= ww;
+    for (int x = 0; x < xmax; ++x)
+      pool[*koff + (size_t)i * ksize + x] = k[x] < 0 ? (int)(-0.5 + k[x] * (1 << kPrecBits)) : (int)(0.5 + k[x] * (1 << kPrecBits));
+    pool[*boff + 2 * i] = xmin;
+    pool[*boff + 2 * i + 1] = xmax;
+  }
+  return ksize;
+}
+
+// torchvision CenterCrop: int(round((size - S) / 2.0)), Python's round (ties to even)
+int center_offset(int size, int S) {
+  const int d = size - S, k = d / 2;
+  return (d % 2 == 0) ? k : ((k % 2 == 0) ? k : k + 1);
+}
+
+std::vector<float> to_ohwi(const HostTensor& t) {
+  const int O = (int)t.shape[0], I = (int)t.shape[1], KH = (int)t.shape[2], KW = (int)t.shape[3];
+  std::vector<float> r((size_t)O * I * KH * KW);
+  for (int o = 0; o < O; ++o)
+    for (int i = 0; i < I; ++i)
+      for (int y = 0; y < KH; ++y)
+        for (int x = 0; x < KW; ++x) r[(((size_t)o * KH + y) * KW + x) * I + i] = t.data[(((size_t)o * I + i) * KH + y) * KW + x];
+  return r;
+}
+}  // namespace
+
+void reid_crop_box(const float b[4], int h, int w, int out[4]) {
+#pragma clang fp contract(off)
+  // Boxes.xywh (float32)
+  const float xc = (b[0] + b[2]) / 2.f, yc = (b[1] + b[3]) / 2.f, bw = b[2] - b[0], bh = b[3] - b[1];
+  // ReID.__call__: xywh2xyxy, float64 from here on
+  const double x1 = (double)xc - (double)bw / 2, x2 = (double)xc + (double)bw / 2;
+  const double y1 = (double)yc - (double)bh / 2, y2 = (double)yc + (double)bh / 2;
+  // save_one_box: xyxy2xywh, wh * gain + pad, xywh2xyxy, .long(), clip_boxes
+  const double cx = (x1 + x2) / 2, cy = (y1 + y2) / 2;
+  const double ww = (x2 - x1) * 1.02 + 10, hh = (y2 - y1) * 1.02 + 10;
+  const long long q[4] = {(long long)(cx - ww / 2), (long long)(cy - hh / 2), (long long)(cx + ww / 2), (long long)(cy + hh / 2)};
+  out[0] = (int)std::min<long long>(std::max<long long>(q[0], 0), w);
+  out[1] = (int)std::min<long long>(std::max<long long>(q[1], 0), h);
+  out[2] = (int)std::min<long long>(std::max<long long>(q[2], 0), w);
+  out[3] = (int)std::min<long long>(std::max<long long>(q[3], 0), h);
+}
+
+Embedder::Embedder(gtx_ctx* ctx, int imgsz, int max_crops, bool fp32_split) : ctx_(ctx), S_(imgsz), max_crops_(max_crops) {
+  GTX_CHECK(imgsz >= 32 && imgsz <= 256 && imgsz % 32 == 0, "reid imgsz must be a multiple of 32 in [32, 256] (got %d)", imgsz);
+  GTX_CHECK(max_crops >= 1, "max_crops must be positive");
+  conv_dtype_ = fp32_split ? DT_F32S : DT_F32;
+  GTX_HIP(hipSetDevice(ctx->device));
+  GTX_HIP(hipEventCreateWithFlags(&done_, wait_event_flags(false)));
+}
+
+Embedder::~Embedder() {
+  if (pin_) (void)hipHostFree(pin_);
+  if (h_emb_) (void)hipHostFree(h_emb_);
+  if (h_sat_) (void)hipHostFree(h_sat_);
+  if (done_) (void)hipEventDestroy(done_);
+}
+
+void Embedder::set_tensor(const std::string& name, const float* data, int ndim, const int64_t* shape) {
+  GTX_CHECK(!finalized_, "set_tensor after finalize");
+  HostTensor t;
+  size_t n = 1;
+  for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
+  t.data.assign(data, data + n);
+  tensors_[name] = std::move(t);
+}
+
+const HostTensor& Embedder::tensor(const std::string& name) const {
+  auto it = tensors_.find(name);
+  if (it == tensors_.end()) fail(-1, "missing tensor '%s'", name.c_str());
+  return it->second;
+}
+
+void* Embedder::alloc(size_t bytes) {
+  bufs_.emplace_back(bytes);
+  GTX_HIP(hipMemset(bufs_.back().p, 0, bufs_.back().bytes));
+  return bufs_.back().p;
+}
+
+View Embedder::new_view(int h, int w, int c) {
+  View v;
+  v.n = max_crops_; v.h = h; v.w = w; v.cstride = c; v.coff = 0; v.c = c;
+  v.ptr = alloc((size_t)v.n * h * w * c * 4);
+  return v;
+}
+
+View Embedder::conv(const std::string& name, const View& x, int stride, const View* out_slice, const View* residual) {
+  const HostTensor& w = tensor(name + ".weight");
+  GTX_CHECK(w.shape.size() == 4 && w.shape[2] == w.shape[3], "%s: expected OIHW square kernel", name.c_str());
+  const int cout = (int)w.shape[0], cin = (int)w.shape[1], ks = (int)w.shape[2];
+  GTX_CHECK(cin == x.c, "%s: weight expects %d input channels, input view has %d", name.c_str(), cin, x.c);
+  const int pad = ks / 2;
+  const int ho = (x.h + 2 * pad - ks) / stride + 1, wo = (x.w + 2 * pad - ks) / stride + 1;
+  View out = out_slice ? *out_slice : new_view(ho, wo, cout);
+  GTX_CHECK(out.h == ho && out.w == wo && out.c == cout, "%s: output view mismatch", name.c_str());
+  Op op;
+  op.kind = Op::CONV;
+  op.name = name;
+  op.cfg = conv_pick_config(conv_dtype_, ks, stride, cin, cout, 0, 0, (long)x.n * ho * wo);
+  if (op.cfg.variant == 3 || op.cfg.variant == 4) { op.cfg.variant = 2; op.cfg.th = 8; }   // GTX_WINO: the direct split kernel here (same kc / bn)
+  const std::vector<float> ohwi = to_ohwi(w);
+  float acc_scale = 1.f;
+  const std::vector<uint8_t> packed = pack_conv_weights(ohwi.data(), cout, cin, op.cfg, &acc_scale);
+  void* dw = alloc(packed.size());
+  GTX_HIP(hipMemcpy(dw, packed.data(), packed.size(), hipMemcpyHostToDevice));
+  float* db = (float*)alloc(((cout + 63) / 64 * 64) * sizeof(float));   // zero-filled up to a whole cout tile
+  if (has(name + ".bias")) {
+    const HostTensor& b = tensor(name + ".bias");
+    GTX_CHECK((int)b.data.size() == cout, "%s: bias size", name.c_str());
+    GTX_HIP(hipMemcpy(db, b.data.data(), cout * sizeof(float), hipMemcpyHostToDevice));
+  }
+  ConvProblem& p = op.grp.p[0];
+  p.in = x.ptr; p.out = out.ptr; p.wpack = dw; p.bias = db;
+  p.res = residual ? residual->ptr : nullptr;
+  p.N = x.n; p.H = x.h; p.W = x.w; p.Ho = ho; p.Wo = wo; p.Cin = cin; p.Cout = cout;
+  p.in_cstride = x.cstride; p.in_coff = x.coff;
+  p.out_cstride = out.cstride; p.out_coff = out.coff;
+  p.res_cstride = residual ? residual->cstride : 0;
+  p.res_coff = residual ? residual->coff : 0;
+  p.act = 1;
+  p.acc_scale = acc_scale;
+  p.sat_flag = conv_dtype_ == DT_F32S ? sat_dev_ : nullptr;
+  op.grp.count = 1;
+  op.family = conv_kernel_name(op.cfg);
+  ops_.push_back(op);
+  layer_views_[name] = out;
+  return out;
+}
+
+// C2f(shortcut=True): cv1 -> split -> n bottlenecks (3x3, 3x3, + residual) -> concat -> cv2 (the detector's c2f, without its fusions)
+View Embedder::c2f(const std::string& pfx, const View& x) {
+  const HostTensor& w1 = tensor(pfx + ".cv1.conv.weight");
+  const int c = (int)w1.shape[0] / 2;
+  int n = 0;
+  while (has(pfx + ".m." + std::to_string(n) + ".cv1.conv.weight")) ++n;
+  View cat = new_view(x.h, x.w, (2 + n) * c);
+  View first = cat.slice(0, 2 * c);
+  conv(pfx + ".cv1.conv", x, 1, &first, nullptr);
+  for (int k = 0; k < n; ++k) {
+    View tmp = new_view(x.h, x.w, c);
+    const std::string m = pfx + ".m." + std::to_string(k);
+    View src = cat.slice((1 + k) * c, c);
+    View dst = cat.slice((2 + k) * c, c);
+    conv(m + ".cv1.conv", src, 1, &tmp, nullptr);
+    conv(m + ".cv2.conv", tmp, 1, &dst, &src);
+  }
+  View out = conv(pfx + ".cv2.conv", cat, 1, nullptr, nullptr);
+  layer_views_[pfx] = out;
+  return out;
+}
+
+void Embedder::build_graph() {
+  img_ = new_view(S_, S_, 1);                                  // [N][S][S] uchar4: 4 bytes per pixel
+  img_.plain = true;
+  if (conv_dtype_ == DT_F32S) {
+    sat_dev_ = (int*)alloc(sizeof(int));
+    GTX_HIP(hipHostMalloc((void**)&h_sat_, sizeof(int)));
+    *h_sat_ = 0;
+  }
+  const HostTensor& w0 = tensor("model.0.conv.weight");
+  GTX_CHECK(w0.shape.size() == 4 && w0.shape[1] == 3 && w0.shape[2] == 3 && w0.shape[3] == 3, "model.0 must be a 3x3 conv on 3 channels");
+  const int c0 = (int)w0.shape[0];
+  View a0 = new_view(S_ / 2, S_ / 2, c0);
+  {
+    std::vector<float> w27((size_t)27 * c0);
+    for (int o = 0; o < c0; ++o)
+      for (int i = 0; i < 3; ++i)
+        for (int y = 0; y < 3; ++y)
+          for (int x = 0; x < 3; ++x) w27[(size_t)((y * 3 + x) * 3 + i) * c0 + o] = w0.data[(((size_t)o * 3 + i) * 3 + y) * 3 + x];
+    float* dw = (float*)alloc(w27.size() * sizeof(float));
+    GTX_HIP(hipMemcpy(dw, w27.data(), w27.size() * sizeof(float), hipMemcpyHostToDevice));
+    std::vector<float> b(c0, 0.f);
+    if (has("model.0.conv.bias")) b = tensor("model.0.conv.bias").data;
+    float* db = (float*)alloc((size_t)(c0 + 31) / 32 * 32 * sizeof(float));
+    GTX_HIP(hipMemcpy(db, b.data(), c0 * sizeof(float), hipMemcpyHostToDevice));
+    Op op;
+    op.kind = Op::STEM;
+    op.name = "model.0.conv";
+    op.family = conv_dtype_ == DT_F32S ? "stem_split_kernel" : "stem_kernel";
+    op.in = img_;
+    op.out = a0;
+    op.w27 = dw;
+    op.bias = db;
+    if (conv_dtype_ == DT_F32S) {
+      const std::vector<uint16_t> pk = pack_stem_weights_split(w27.data(), c0, &op.stem_scale);
+      void* dp = alloc(pk.size() * 2);
+      GTX_HIP(hipMemcpy(dp, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
+      op.wpk = dp;
+    }
+    op.flops = 2.0 * 27 * c0 * (S_ / 2) * (S_ / 2);
+    ops_.push_back(op);
+    layer_views_["model.0.conv"] = a0;
+  }
+  View a = conv("model.1.conv", a0, 2, nullptr, nullptr);
+  a = c2f("model.2", a);
+  a = conv("model.3.conv", a, 2, nullptr, nullptr);
+  a = c2f("model.4", a);
+  a = conv("model.5.conv", a, 2, nullptr, nullptr);
+  a = c2f("model.6", a);
+  a = conv("model.7.conv", a, 2, nullptr, nullptr);
+  last_ = c2f("model.8", a);
+  dim_ = last_.c;
+}
+
+void Embedder::finalize() {
+  GTX_CHECK(!finalized_, "finalize called twice");
+  GTX_HIP(hipSetDevice(ctx_->device));
+  build_graph();
+  if (conv_dtype_ != DT_F32S || !env_on("GTX_SAT_FALLBACK", true)) tensors_.clear();   // the split path keeps them for fall_back_to_exact
+  set_batch(1);
+  GTX_HIP(hipStreamSynchronize(ctx_->stream));
+  finalized_ = true;
+}
+
+void Embedder::set_batch(int nb) {
+  if (nb == cur_nb_) return;
+  for (Op& op : ops_) {
+    if (op.kind != Op::CONV) continue;
+    for (int i = 0; i < op.grp.count; ++i) op.grp.p[i].N = nb;
+    conv_group_finalize(op.grp, op.cfg);
+    op.flops = nb ? conv_flops(op.grp.p[0], op.cfg.ks) / nb : 0.0;
+  }
+  cur_nb_ = nb;
+}
+
+void Embedder::run_op(const Op& op, int nb, hipStream_t s) {
+  if (op.kind == Op::STEM)
+    launch_stem(conv_dtype_, op.in.ptr, nb, op.in.h, op.in.w, op.w27, op.bias, op.wpk, op.out.c, op.out.ptr, op.out.h, op.out.w, s, op.stem_scale);
+  else
+    conv_launch(op.grp, op.cfg, s);
+}
+
+void Embedder::fall_back_to_exact() {
+  std::unique_ptr<Embedder> e(new Embedder(ctx_, S_, max_crops_, false));
+  for (const auto& kv : tensors_) e->set_tensor(kv.first, kv.second.data.data(), (int)kv.second.shape.size(), kv.second.shape.data());
+  e->finalize();
+  GTX_HIP(hipStreamSynchronize(ctx_->stream));
+  ops_.clear();
+  layer_views_.clear();
+  bufs_.clear();
+  tensors_.clear();
+  exact_ = std::move(e);
+}
+
+bool Embedder::saturated(bool clear) {
+  const bool r = sat_seen_;
+  if (clear) {
+    sat_seen_ = false;
+    if (sat_dev_ && !exact_) {
+      GTX_HIP(hipSetDevice(ctx_->device));
+      GTX_HIP(hipMemsetAsync(sat_dev_, 0, sizeof(int), ctx_->stream));
+    }
+  }
+  return r;
+}
+
+// Crop table + coefficients of the pass on the host, one copy to the device, then chunk by chunk of max_crops: crop kernel ->
+// backbone -> pool into the vectors' rows. Everything on the context's stream, so the frames are read before anything the
+// caller enqueues behind this call on that stream.
+void Embedder::enqueue(int n) {
+  hipStream_t s = ctx_->stream;
+  const int H = cur_h_, W = cur_w_;
+  h_crops_.clear();
+  h_pool_.clear();
+  int frame = 0, left = cur_counts_.empty() ? 0 : cur_counts_[0];
+  for (int i = 0; i < n; ++i) {
+    while (left == 0) left = cur_counts_[++frame];
+    --left;
+    int q[4];
+    reid_crop_box(&cur_xyxy_[(size_t)i * 4], H, W, q);
+    ReidCrop c{};
+    c.frame = frame;
+    c.x0 = q[0]; c.y0 = q[1]; c.cw = q[2] - q[0]; c.ch = q[3] - q[1];
+    GTX_CHECK(c.cw > 0 && c.ch > 0, "box %d (%.1f %.1f %.1f %.1f) leaves an empty crop in a %dx%d frame", i, cur_xyxy_[i * 4], cur_xyxy_[i * 4 + 1],
+              cur_xyxy_[i * 4 + 2], cur_xyxy_[i * 4 + 3], W, H);
+    // torchvision Resize(S) on the PIL image: short side S, long side int(S * long / short)
+    int rw, rh;
+    if (c.cw <= c.ch) { rw = S_; rh = (int)((double)((long long)S_ * c.ch) / c.cw); }
+    else { rh = S_; rw = (int)((double)((long long)S_ * c.cw) / c.ch); }
+    c.kh = reid_resample_coeffs(c.cw, rw, center_offset(rw, S_), S_, h_pool_, &c.bh, &c.hoff);
+    c.kv = reid_resample_coeffs(c.ch, rh, center_offset(rh, S_), S_, h_pool_, &c.bv, &c.voff);
+    h_crops_.push_back(c);
+  }
+  const size_t crop_bytes = h_crops_.size() * sizeof(ReidCrop), pool_off = (crop_bytes + 255) / 256 * 256;
+  const size_t bytes = pool_off + h_pool_.size() * sizeof(int);
+  if (pin_bytes_ < bytes) {
+    if (pin_) GTX_HIP(hipHostFree(pin_));
+    pin_ = nullptr;
+    GTX_HIP(hipHostMalloc(&pin_, bytes * 2));
+    pin_bytes_ = bytes * 2;
+  }
+  if (d_params_.bytes < bytes) d_params_.alloc(bytes * 2);
+  if (d_emb_.bytes < std::max<size_t>((size_t)n * dim_ * 4, 4)) d_emb_.alloc(std::max<size_t>((size_t)n * dim_ * 4 * 2, 256));
+  if (h_emb_n_ < (size_t)n * dim_) {
+    if (h_emb_) GTX_HIP(hipHostFree(h_emb_));
+    h_emb_ = nullptr;
+    h_emb_n_ = std::max<size_t>((size_t)n * dim_ * 2, 1);
+    GTX_HIP(hipHostMalloc((void**)&h_emb_, h_emb_n_ * 4));
+  }
+  if (n == 0) return;                                         // zero crops: nothing is launched
+  memcpy(pin_, h_crops_.data(), crop_bytes);
+  memcpy((uint8_t*)pin_ + pool_off, h_pool_.data(), h_pool_.size() * sizeof(int));
+  GTX_HIP(hipMemcpyAsync(d_params_.p, pin_, bytes, hipMemcpyHostToDevice, s));
+  const ReidCrop* d_crops = d_params_.as<ReidCrop>();
+  const int* d_pool = (const int*)((const uint8_t*)d_params_.p + pool_off);
+  for (int c0 = 0; c0 < n; c0 += max_crops_) {
+    const int k = std::min(max_crops_, n - c0);
+    set_batch(k);
+    launch_reid_crop((const uint8_t*)cur_frames_, H, W, d_crops + c0, d_pool, k, S_, img_.ptr, s);
+    for (const Op& op : ops_) run_op(op, k, s);
+    launch_reid_pool(last_.ptr, conv_dtype_ == DT_F32S ? 1 : 0, k, last_.h * last_.w, last_.cstride, last_.coff, dim_,
+                     d_emb_.as<float>() + (size_t)c0 * dim_, s);
+    last_chunk_ = c0;
+    last_chunk_n_ = k;
+  }
+  GTX_HIP(hipMemcpyAsync(h_emb_, d_emb_.p, (size_t)n * dim_ * 4, hipMemcpyDeviceToHost, s));
+  if (sat_dev_) GTX_HIP(hipMemcpyAsync(h_sat_, sat_dev_, sizeof(int), hipMemcpyDeviceToHost, s));
+}
+
+void Embedder::submit_dev(const void* frames, int nb, int h, int w, const int* counts, const float* xyxy) {
+  if (exact_) return exact_->submit_dev(frames, nb, h, w, counts, xyxy);
+  GTX_CHECK(finalized_, "embedder not finalized");
+  GTX_CHECK(!in_flight_, "submit while a pass is in flight: call collect first");
+  GTX_CHECK(nb >= 1 && h > 0 && w > 0, "bad frame batch %d x %dx%d", nb, w, h);
+  GTX_HIP(hipSetDevice(ctx_->device));
+  int n = 0;
+  for (int b = 0; b < nb; ++b) {
+    GTX_CHECK(counts[b] >= 0, "negative box count");
+    n += counts[b];
+  }
+  GTX_CHECK(n == 0 || frames, "frames: NULL");
+  cur_frames_ = frames; cur_h_ = h; cur_w_ = w;
+  cur_counts_.assign(counts, counts + nb);
+  cur_xyxy_.assign(xyxy, xyxy + (size_t)n * 4);
+  n_flight_ = n;
+  enqueue(n);
+  GTX_HIP(hipEventRecord(done_, ctx_->stream));
+  in_flight_ = true;
+}
+
+int Embedder::collect(float* out, int cap) {
+  if (exact_) return exact_->collect(out, cap);
+  GTX_CHECK(in_flight_, "collect without a submitted pass");
+  GTX_HIP(hipSetDevice(ctx_->device));
+  GTX_HIP(hipEventSynchronize(done_));
+  in_flight_ = false;
+  const int n = n_flight_;
+  if (n > 0 && h_sat_ && *h_sat_) {
+    sat_seen_ = true;
+    if (conv_dtype_ == DT_F32S && !tensors_.empty()) {          // this pass again at fp32's range, and every later one (Detector::collect's rule)
+      const void* f = cur_frames_;
+      const std::vector<int> counts = cur_counts_;
+      const std::vector<float> xyxy = cur_xyxy_;
+      fall_back_to_exact();
+      exact_->submit_dev(f, (int)counts.size(), cur_h_, cur_w_, counts.data(), xyxy.data());
+      return exact_->collect(out, cap);
+    }
+  }
+  GTX_CHECK(cap >= n, "output holds %d vectors, the pass has %d", cap, n);
+  if (n > 0 && out) memcpy(out, h_emb_, (size_t)n * dim_ * sizeof(float));
+  return n;
+}
+
+void Embedder::crops(int i, uint8_t* out) {
+  if (exact_) return exact_->crops(i, out);
+  GTX_CHECK(!in_flight_, "crops while a pass is in flight: call collect first");
+  GTX_CHECK(i >= last_chunk_ && i < last_chunk_ + last_chunk_n_, "crop %d is not in the last chunk of the last pass", i);
+  GTX_HIP(hipMemcpy(out, (const uint8_t*)img_.ptr + (size_t)(i - last_chunk_) * S_ * S_ * 4, (size_t)S_ * S_ * 4, hipMemcpyDeviceToHost));
+}
+
+void Embedder::layer_output(int i, const std::string& layer, float* out, int* h, int* w, int* c) {
+  if (exact_) return exact_->layer_output(i, layer, out, h, w, c);
+  GTX_CHECK(!(out && in_flight_), "layer_output while a pass is in flight: call collect first");
+  auto it = layer_views_.find(layer);
+  if (it == layer_views_.end()) fail(-1, "unknown layer '%s'", layer.c_str());
+  const View& v = it->second;
+  if (h) *h = v.h;
+  if (w) *w = v.w;
+  if (c) *c = v.c;
+  if (!out) return;
+  GTX_CHECK(i >= last_chunk_ && i < last_chunk_ + last_chunk_n_, "crop %d is not in the last chunk of the last pass", i);
+  const size_t px = (size_t)v.h * v.w;
+  std::vector<uint8_t> host(px * v.cstride * 4);
+  GTX_HIP(hipMemcpy(host.data(), (const uint8_t*)v.ptr + (size_t)(i - last_chunk_) * px * v.cstride * 4, host.size(), hipMemcpyDeviceToHost));
+  for (size_t p = 0; p < px; ++p)
+    for (int k = 0; k < v.c; ++k) {
+      const size_t src = p * v.cstride + v.coff + k;
+      float f;
+      if (conv_dtype_ == DT_F32S) f = pair_element(host.data(), src);
+      else memcpy(&f, host.data() + src * 4, 4);
+      out[p * v.c + k] = f;
+    }
+}
+
+void Embedder::profile(int n, int iters, std::vector<std::string>& names, std::vector<float>& ms, std::vector<double>& flops) {
+  if (exact_) return exact_->profile(n, iters, names, ms, flops);
+  GTX_CHECK(finalized_ && !in_flight_, "profile: embedder not finalized or a pass in flight");
+  GTX_CHECK(n >= 1 && n <= max_crops_ && iters >= 1, "bad profile arguments");
+  hipStream_t s = ctx_->stream;
+  set_batch(n);
+  std::vector<hipEvent_t> ev(ops_.size() + 1);
+  for (auto& e : ev) GTX_HIP(hipEventCreate(&e));
+  names.clear(); ms.assign(ops_.size(), 0.f); flops.assign(ops_.size(), 0.0);
+  for (const Op& op : ops_) names.push_back(op.name + " " + op.family);
+  for (int it = 0; it < iters; ++it) {
+    for (size_t i = 0; i < ops_.size(); ++i) {
+      GTX_HIP(hipEventRecord(ev[i], s));
+      run_op(ops_[i], n, s);
+    }
+    GTX_HIP(hipEventRecord(ev[ops_.size()], s));
+    GTX_HIP(hipStreamSynchronize(s));
+    for (size_t i = 0; i < ops_.size(); ++i) {
+      float t = 0.f;
+      GTX_HIP(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
+      ms[i] += t / iters;
+      flops[i] = ops_[i].flops * n;
+    }
+  }
+  for (auto& e : ev) (void)hipEventDestroy(e);
+}
+
+}  // namespace gtx
+
+// ------------------------------------------------------------------ C ABI (include/gtx.h, "ReID embedder")
+using gtx::guarded;
+
+namespace {
+void need(const void* p, const char* what) {
+  if (!p) gtx::fail(GTX_ERR_INVALID, "%s: NULL", what);
+}
+}  // namespace
+
+int gtx_embedder_create(gtx_ctx* ctx, int imgsz, int max_crops, int fp32_split, gtx_embedder** out) {
+  return guarded([&] {
+    need(ctx, "ctx"); need(out, "out");
+    std::unique_ptr<gtx_embedder> e(new gtx_embedder);
+    e->impl.reset(new gtx::Embedder(ctx, imgsz, max_crops, fp32_split != 0));
+    *out = e.release();
+  });
+}
+void gtx_embedder_destroy(gtx_embedder* e) { delete e; }
+int gtx_embedder_set_tensor(gtx_embedder* e, const char* name, const float* data, int ndim, const int64_t* shape) {
+  return guarded([&] {
+    need(e, "embedder"); need(name, "name"); need(data, "data"); need(shape, "shape");
+    e->impl->set_tensor(name, data, ndim, shape);
+  });
+}
+int gtx_embedder_finalize(gtx_embedder* e) {
+  return guarded([&] { need(e, "embedder"); e->impl->finalize(); });
+}
+int gtx_embedder_dim(gtx_embedder* e, int* dim) {
+  return guarded([&] { need(e, "embedder"); need(dim, "dim"); *dim = e->impl->dim(); });
+}
+int gtx_embedder_submit_dev(gtx_embedder* e, const void* frames_dptr, int nb, int h, int w, const int* counts, const float* xyxy) {
+  return guarded([&] {
+    need(e, "embedder"); need(counts, "counts");
+    int n = 0;
+    for (int b = 0; b < nb; ++b) n += counts[b];
+    if (n > 0) need(xyxy, "xyxy");
+    e->impl->submit_dev(frames_dptr, nb, h, w, counts, xyxy);
+  });
+}
+int gtx_embedder_collect(gtx_embedder* e, float* out, int cap, int* n) {
+  return guarded([&] { need(e, "embedder"); need(n, "n"); *n = e->impl->collect(out, cap); });
+}
+int gtx_embedder_embed_dev(gtx_embedder* e, const void* frames_dptr, int nb, int h, int w, const int* counts, const float* xyxy, float* out,
+                           int cap, int* n) {
+  const int rc = gtx_embedder_submit_dev(e, frames_dptr, nb, h, w, counts, xyxy);
+  return rc != GTX_OK ? rc : gtx_embedder_collect(e, out, cap, n);
+}
+int gtx_embedder_crops(gtx_embedder* e, int i, uint8_t* out) {
+  return guarded([&] { need(e, "embedder"); need(out, "out"); e->impl->crops(i, out); });
+}
+int gtx_embedder_layer_output(gtx_embedder* e, int i, const char* layer, float* out, int* h, int* w, int* c) {
+  return guarded([&] { need(e, "embedder"); need(layer, "layer"); e->impl->layer_output(i, layer, out, h, w, c); });
+}
+int gtx_embedder_saturated(gtx_embedder* e, int clear, int* flag) {
+  return guarded([&] { need(e, "embedder"); need(flag, "flag"); *flag = e->impl->saturated(clear != 0) ? 1 : 0; });
+}
+int gtx_embedder_fell_back(gtx_embedder* e, int* fell_back) {
+  return guarded([&] { need(e, "embedder"); need(fell_back, "fell_back"); *fell_back = e->impl->fell_back() ? 1 : 0; });
+}
+int gtx_embedder_profile(gtx_embedder* e, int n, int iters, int cap, char* names, float* ms, double* flops, int* n_ops) {
+  return guarded([&] {
+    need(e, "embedder"); need(n_ops, "n_ops");
+    std::vector<std::string> nm;
+    std::vector<float> t;
+    std::vector<double> f;
+    e->impl->profile(n, iters, nm, t, f);
+    *n_ops = (int)nm.size();
+    for (int i = 0; i < (int)nm.size() && i < cap; ++i) {
+      if (names) { memset(names + (size_t)i * 128, 0, 128); strncpy(names + (size_t)i * 128, nm[i].c_str(), 127); }
+      if (ms) ms[i] = t[i];
+      if (flops) flops[i] = f[i];
+    }
+  });
+}
+int gtx_reid_crop_boxes(const float* xyxy, int n, int h, int w, int* out) {
+  return guarded([&] {
+    if (n > 0) { need(xyxy, "xyxy"); need(out, "out"); }
+    for (int i = 0; i < n; ++i) gtx::reid_crop_box(xyxy + (size_t)i * 4, h, w, out + (size_t)i * 4);
+  });
+}

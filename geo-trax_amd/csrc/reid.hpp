@@ -1,0 +1,87 @@
+// Separate ReID network: the YOLOv8-cls backbone (model.0 - model.8 of ultralytics' yolov8-cls.yaml) run over one crop per
+// detection, its last map average-pooled into one vector per crop. Stands in for ultralytics' trackers/bot_sort.py ReID
+// (`with_reid: true, model: <cls checkpoint>` of BoT-SORT, Deep OC-SORT and TrackTrack; geotrax/cfg/default.yaml:379, :421, :470):
+// save_one_box per detection -> ClassificationPredictor (classify_transforms(imgsz)) -> model(embed=[len(model) - 2]).
+// The convolutions are the detector's kernels with the batch dimension equal to the number of crops; the Classify head is never run.
+#pragma once
+#include <map>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "detector.hpp"
+#include "reid_kernels.hpp"
+
+namespace gtx {
+
+// save_one_box(xyxy, im, gain=1.02, pad=10, square=False) of one detection: the clipped crop [x1, x2) x [y1, y2) of an h x w frame
+void reid_crop_box(const float xyxy[4], int h, int w, int out[4]);
+
+class Embedder {
+ public:
+  Embedder(gtx_ctx* ctx, int imgsz, int max_crops, bool fp32_split);
+  ~Embedder();
+  void set_tensor(const std::string& name, const float* data, int ndim, const int64_t* shape);
+  void finalize();
+  int dim() const { return exact_ ? exact_->dim() : dim_; }
+  // frames: nb device frames [h][w][3] BGR u8; counts[nb] boxes per frame, xyxy [sum counts][4] host, frame pixels
+  void submit_dev(const void* frames, int nb, int h, int w, const int* counts, const float* xyxy);
+  // waits for the submitted pass; out [n][dim] (n = the pass's box count, <= cap)
+  int collect(float* out, int cap);
+  void crops(int i, uint8_t* out);                                          // [S][S][4] u8 of crop i of the last pass
+  void layer_output(int i, const std::string& layer, float* out, int* h, int* w, int* c);
+  bool saturated(bool clear);
+  bool fell_back() const { return exact_ != nullptr; }
+  // per-op times of `iters` forward passes over the first n crops of the last pass (events around every launch)
+  void profile(int n, int iters, std::vector<std::string>& names, std::vector<float>& ms, std::vector<double>& flops);
+
+ private:
+  void* alloc(size_t bytes);
+  View new_view(int h, int w, int c);
+  const HostTensor& tensor(const std::string& name) const;
+  bool has(const std::string& name) const { return tensors_.count(name) != 0; }
+  View conv(const std::string& name, const View& x, int stride, const View* out_slice, const View* residual);
+  View c2f(const std::string& pfx, const View& x);
+  void build_graph();
+  void set_batch(int nb);
+  void run_op(const Op& op, int nb, hipStream_t s);
+  void fall_back_to_exact();
+  void enqueue(int n_total);
+
+  gtx_ctx* ctx_;
+  int S_, max_crops_;
+  int conv_dtype_;                       // DT_F32S (split-f16x3) or DT_F32
+  std::map<std::string, HostTensor> tensors_;
+  std::vector<DevBuf> bufs_;
+  std::vector<Op> ops_;
+  std::map<std::string, View> layer_views_;
+  View img_, last_;
+  int dim_ = 0;
+  bool finalized_ = false;
+  int cur_nb_ = -1;
+  std::unique_ptr<Embedder> exact_;
+  int* sat_dev_ = nullptr;
+  int* h_sat_ = nullptr;
+  bool sat_seen_ = false;
+  // the pass in flight (kept for the exact re-run of a saturated pass)
+  bool in_flight_ = false;
+  const void* cur_frames_ = nullptr;
+  int cur_h_ = 0, cur_w_ = 0;
+  std::vector<int> cur_counts_;
+  std::vector<float> cur_xyxy_;
+  int n_flight_ = 0, last_chunk_ = 0, last_chunk_n_ = 0;
+  // per-pass crop table + coefficient pool (pinned staging, device copies) and the vectors
+  std::vector<ReidCrop> h_crops_;
+  std::vector<int> h_pool_;
+  void* pin_ = nullptr; size_t pin_bytes_ = 0;
+  DevBuf d_params_;
+  DevBuf d_emb_;
+  float* h_emb_ = nullptr; size_t h_emb_n_ = 0;
+  hipEvent_t done_ = nullptr;
+};
+
+}  // namespace gtx
+
+struct gtx_embedder {
+  std::unique_ptr<gtx::Embedder> impl;
+};

@@ -150,6 +150,20 @@ _SIGNATURES = {
     "gtx_detector_features": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gtx_detector_trace": (C.c_int, [_P, C.c_int]),
     "gtx_detector_profile": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.POINTER(C.c_int)]),
+    "gtx_embedder_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "gtx_embedder_destroy": (None, [_P]),
+    "gtx_embedder_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64)]),
+    "gtx_embedder_finalize": (C.c_int, [_P]),
+    "gtx_embedder_dim": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "gtx_embedder_submit_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "gtx_embedder_collect": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
+    "gtx_embedder_embed_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(C.c_int)]),
+    "gtx_embedder_crops": (C.c_int, [_P, C.c_int, _P]),
+    "gtx_embedder_layer_output": (C.c_int, [_P, C.c_int, C.c_char_p, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gtx_embedder_saturated": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    "gtx_embedder_fell_back": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "gtx_embedder_profile": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
+    "gtx_reid_crop_boxes": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "gtx_tracker_create": (C.c_int, [C.POINTER(TrackerConfig), C.POINTER(_P)]),
     "gtx_tracker_destroy": (None, [_P]),
     "gtx_tracker_reset": (C.c_int, [_P]),

@@ -272,7 +272,9 @@ class ExtractEngine:
         n_dets = max(int(det_streams), len(self.dets), 1)
         n_stab = max(1, min(int(stab_streams), 4 * n_dets * self.B - 2)) if stab_kw is not None else 0   # frames in flight < gray ring lifetime
         self.tracker = tracker
-        if tracker is not None and getattr(tracker, "with_reid", False):   # BoT-SORT `with_reid: true, model: auto`: a vector per box
+        self.reid_tensors = getattr(tracker, "reid_tensors", None) if tracker is not None and getattr(tracker, "with_reid", False) else None
+        self.encoders = {}               # id(detector) -> ReIDEncoder on that detector's context (`model: <cls checkpoint>`)
+        if tracker is not None and getattr(tracker, "with_reid", False) and self.reid_tensors is None:   # `with_reid: true, model: auto`: a vector per box
             det_kw = dict(det_kw, obj_feats=True)
             if any(not getattr(d, "obj_feats", False) for d in self.dets):
                 raise ValueError("the tracker associates on appearance vectors (with_reid): adopted detectors must be built with obj_feats=True")
@@ -293,6 +295,14 @@ class ExtractEngine:
             self.dets.append(Detector(weights, self.frame_hw, max_batch=self.B, ctx=take("d"), **det_kw))   # det_kw carries obj_feats when the tracker asks
         while len(self.stabs) < n_stab:
             self.stabs.append(Stabilizer(self.frame_hw, ctx=take("s"), **stab_kw))
+        if self.reid_tensors is not None:
+            # the separate ReID network runs on each detector's own stream (no stream of its own: the StreamPlan is the one runs
+            # without ReID get), in stream order behind the detector pass that read the same frames
+            from .reid import ReIDEncoder
+
+            for d in self.dets:
+                self.encoders[id(d)] = ReIDEncoder(self.reid_tensors, ctx=d.ctx, max_crops=min(d.max_det * self.B, 256),
+                                                     fp32_split=det_kw.get("fp32_split"))   # `engine: {fp32_split}` as YOLO.track gets it; None: the library default (also under half)
         self.feeder_ctx = take("f") if feeder_stream else None   # the context a read-ahead feeder's transfers run on
         if gmc:                          # True / "sparseOptFlow": the GPU Lucas-Kanade GMC; "orb" / "sift": the feature-based ones (gmc.FeatureGMC); "ecc": gmc.EccGMC
             from .gmc import make_gmc
@@ -301,6 +311,8 @@ class ExtractEngine:
         self.use_dev_gray = bool(self.stabs) and float(stab_kw.get("downsample_ratio", 0.5)) == 0.5
         self._stage = {}                 # per detector: device staging buffer for host frames
         self._host_frames = {}           # frames kept for the host-gray fallback of the stabilizer
+        self._frames_of = {}             # per detector: device pointer of the frames of its batch in flight (the ReID crops read them)
+        self._last_frames = 0
         self._index, self._have_ref = 0, False
         self._last_H = None              # last valid current->reference transform, in frame order
         self._prof = self.prof = None    # GTX_ENGINE_PROF=1: see run()
@@ -348,6 +360,9 @@ class ExtractEngine:
                 if p:
                     d.ctx.dev_free(p)
             d.close()
+        for e in self.encoders.values():
+            e.close()
+        self.encoders = {}
         for s in self.stabs:
             s.close()
         if self.gmc is not None:
@@ -362,6 +377,7 @@ class ExtractEngine:
         if isinstance(batch, (int, np.integer)):                # device pointer to B contiguous frames
             self._gmc_frames(det, int(batch), self.B)
             det.submit_dev(int(batch), self.B)
+            self._last_frames = int(batch)
             return self.B
         from .feeder import DeviceBatch
         from .frames import Yuv420Frame
@@ -374,6 +390,7 @@ class ExtractEngine:
             batch.wait_on(det.ctx)
             self._gmc_frames(det, batch.ptr, batch.n)
             det.submit_dev(batch.ptr, batch.n)
+            self._last_frames = batch.ptr
             return batch.n
 
         frames = [f if isinstance(f, Yuv420Frame) else np.ascontiguousarray(f, dtype=np.uint8) for f in batch]
@@ -397,6 +414,7 @@ class ExtractEngine:
                 det.ctx.dev_upload(self._stage[key] + i * nbytes, f)
         self._gmc_frames(det, self._stage[key], len(frames))
         det.submit_dev(self._stage[key], len(frames))
+        self._last_frames = self._stage[key]
         if self.stabs and not self.use_dev_gray:
             self._host_frames[key] = [f.bgr() if isinstance(f, Yuv420Frame) else f for f in frames]
         return len(frames)
@@ -457,6 +475,7 @@ class ExtractEngine:
             det = self.dets[k % len(self.dets)]
             k += 1
             inflight.append((det, self._submit(det, b), prev))
+            self._frames_of[id(det)] = self._last_frames
 
         host_gray = bool(self.stabs) and not self.use_dev_gray
         try:
@@ -473,6 +492,17 @@ class ExtractEngine:
                 if self._prof is not None:
                     self._prof["det_collect"] += time.perf_counter() - t0
                     self.marks.append(("det", k - len(inflight) - 1, time.perf_counter() - self._t_run))
+                enc = self.encoders.get(id(det))
+                if enc is not None:
+                    # the crops are cut now, before anything can refill this batch's frames: the next batch for this detector
+                    # (its staging buffer), the feeder's slot release and the re-run of a saturated pass all come after this
+                    # collect. The vectors ride on the detections to the tracker stage.
+                    t0 = time.perf_counter() if self._prof is not None else 0.0
+                    enc.submit_dev(self._frames_of.pop(id(det)), self.frame_hw[0], self.frame_hw[1], [d.xyxy for d in dets])
+                    for d, f in zip(dets, enc.collect()):
+                        d.feats = f
+                    if self._prof is not None:
+                        self._prof["reid"] += time.perf_counter() - t0
                 grays = [det.gray_dptr(b) for b in range(nb)]
                 hosts = self._host_frames.pop(id(det), None)
                 det_ms = float(sum(dets[0].speed.values())) / nb if dets else 0.0

@@ -28,7 +28,7 @@ import yaml
 from . import _lib
 from .detector import Detector
 from .tracker import TRACKER_TYPES, Tracker
-from .weights import load_weights
+from .weights import is_yolov8_cls, load_weights
 
 logger = logging.getLogger(__name__)
 
@@ -160,14 +160,22 @@ class YOLO:
         else:
             params = dict(spec or {})
         ttype = params.get("tracker_type", "botsort")
+        reid_tensors = None
         if ttype not in TRACKER_TYPES:
             raise NotImplementedError(f"tracker_type '{ttype}' is not implemented (available: {sorted(TRACKER_TYPES)})")
         if ttype in ("botsort", "deepocsort", "tracktrack"):  # the trackers that take a camera-motion warp per frame
             if params.get("with_reid"):
                 # `model: auto` (default.yaml:379, :421, :470): appearance vectors from the detector's own feature maps
-                # (Detector(obj_feats=True) -> Tracker.update(feats=)); a separate ReID network's weights cannot be read here
-                if str(params.get("model", "auto")) != "auto":
-                    raise NotImplementedError(f"{ttype} with_reid: only `model: auto` (detector-derived features) is implemented, not '{params.get('model')}'")
+                # (Detector(obj_feats=True) -> Tracker.update(feats=)); `model: <file>.safetensors`: a separate YOLOv8-cls network over
+                # the detection crops (reid.ReIDEncoder). Any other name (a .pt pickle, OSNet, ...) is refused before a file is opened.
+                m = str(params.get("model", "auto"))
+                if m != "auto":
+                    if Path(m).suffix != ".safetensors":
+                        raise NotImplementedError(f"{ttype} with_reid: `model: auto` (detector-derived features) or a YOLOv8-cls checkpoint converted "
+                                                  f"to .safetensors (tools/convert_weights.py) are implemented, not '{m}'")
+                    reid_tensors = load_weights(Path(m))           # relative paths: against the working directory, like YOLO(model)
+                    if not is_yolov8_cls(reid_tensors):
+                        raise NotImplementedError(f"{ttype} with_reid: '{m}' is not a classification checkpoint; only the YOLOv8-cls family is implemented")
             gm = params.get("gmc_method", "none")
             if gm in ("none", None):
                 self._gmc_method = None
@@ -198,12 +206,15 @@ class YOLO:
                            "(det_thresh = track_high_thresh, iou_threshold = 1 - match_thresh, max_age = track_buffer, min_hits = 3 unless "
                            f"'min_hits' is given) and 'fuse_score'{' (set in this config)' if params.get('fuse_score') else ''} is ignored: "
                            "tracks may differ from a geo-trax run of the same tracker. Score a reference run with tools/score_run.py to pin it.")
-        return Tracker(ttype, **{k: v for k, v in params.items() if k in (
+        trk = Tracker(ttype, **{k: v for k, v in params.items() if k in (
             "track_high_thresh", "track_low_thresh", "new_track_thresh", "track_buffer", "match_thresh", "fuse_score",
             "delta_t", "inertia", "use_byte", "min_hits", "reset_velocity_offset_occ", "reset_pos_offset_occ", "enlarge_bbox_occ",
             "dampen_motion_occ", "active_occ_to_lost_thresh", "occ_cover_thresh", "occ_reappear_window", "init_iou_suppress",
             "with_reid", "proximity_thresh", "appearance_thresh", "lost_match_thr", "iou_weight", "reid_weight", "conf_weight", "angle_weight",
             "penalty_p", "penalty_q", "reduce_step", "tai_thr", "min_track_len", "alpha_fixed_emb")})
+        trk.reid_tensors = reid_tensors                       # ExtractEngine and track() build the ReID network from these
+        self._reid = None
+        return trk
 
     # ---- ultralytics-style entry points
     def predict(self, source: np.ndarray, **kwargs) -> list[Results]:
@@ -223,7 +234,9 @@ class YOLO:
                 self._gmc.reset_params()
         kwargs = dict(kwargs)
         kwargs["conf"] = kwargs.get("conf") or 0.1      # ultralytics Model.track default
-        self._obj_feats = bool(getattr(self._tracker, "with_reid", False))   # `with_reid: true, model: auto`: the detector keeps a vector per box
+        with_reid = bool(getattr(self._tracker, "with_reid", False))
+        reid_tensors = getattr(self._tracker, "reid_tensors", None)
+        self._obj_feats = with_reid and reid_tensors is None   # `with_reid: true, model: auto`: the detector keeps a vector per box
         if self._obj_feats and self.is_rtdetr:
             raise NotImplementedError("with_reid: true, model: auto needs the YOLOv8 Detect layer's inputs; not implemented for RT-DETR")
         frame = np.ascontiguousarray(source, dtype=np.uint8)
@@ -248,7 +261,14 @@ class YOLO:
                 warp = self._gmc.collect()
             else:
                 warp = self._gmc.apply(frame)
-        xyxy, ids, score, cls, _idx = self._tracker.update(b._xyxy, b._conf, b._cls.astype(np.int32), gmc=warp, feats=d.feats)
+        feats = d.feats
+        if with_reid and reid_tensors is not None:          # BOTSORT.init_track -> ReID(img, dets): a crop per detection through the cls network
+            if getattr(self, "_reid", None) is None:
+                from .reid import ReIDEncoder
+
+                self._reid = ReIDEncoder(reid_tensors, ctx=self.ctx, fp32_split=self.fp32_split)   # fp32 grade even under half: upstream's own predictor
+            feats = self._reid(np.asarray(source), b._xyxy)
+        xyxy, ids, score, cls, _idx = self._tracker.update(b._xyxy, b._conf, b._cls.astype(np.int32), gmc=warp, feats=feats)
         if len(ids) == 0:                                   # the raw detections (or no rows) with id None (extract.py:161-165)
             return [res]
         res.boxes = Boxes(xyxy, score, cls, ids)

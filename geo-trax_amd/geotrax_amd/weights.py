@@ -354,3 +354,98 @@ def calibrate_rtdetr_scores(tensors: dict[str, np.ndarray], raw_logits: np.ndarr
     name = f"model.28.dec_score_head.{last}.bias"
     out[name] = (tensors[name] + np.float32(delta)).astype(np.float32)
     return out
+
+
+# --------------------------------------------------------------------------- YOLOv8-cls (the separate ReID network)
+# `with_reid: true, model: <cls checkpoint>` (default.yaml:379, :421, :470): ultralytics' ReID runs a classification model over the
+# detection crops and keeps the global average pool of its last backbone layer (model.8 of yolov8-cls.yaml). Only the backbone
+# is read; the Classify head (model.9) may be present and is ignored.
+
+CLS_SCALES = {"n": (0.33, 0.25, 1024), "s": (0.33, 0.50, 1024), "m": (0.67, 0.75, 1024),
+              "l": (1.00, 1.00, 1024), "x": (1.00, 1.25, 1024)}    # yolov8-cls.yaml: depth, width, max_channels
+
+
+def _cls_backbone_specs(c1: int, c2: int, c3: int, c4: int, c5: int, reps: tuple[int, int, int, int]) -> list[tuple[str, tuple[int, ...]]]:
+    specs: list[tuple[str, tuple[int, ...]]] = []
+
+    def c2f(pfx, cin, cout, n):
+        c = cout // 2
+        specs.append((f"{pfx}.cv1.conv", (2 * c, cin, 1, 1)))
+        for k in range(n):
+            specs.append((f"{pfx}.m.{k}.cv1.conv", (c, c, 3, 3)))
+            specs.append((f"{pfx}.m.{k}.cv2.conv", (c, c, 3, 3)))
+        specs.append((f"{pfx}.cv2.conv", (cout, (2 + n) * c, 1, 1)))
+
+    specs.append(("model.0.conv", (c1, 3, 3, 3)))
+    specs.append(("model.1.conv", (c2, c1, 3, 3)))
+    c2f("model.2", c2, c2, reps[0])
+    specs.append(("model.3.conv", (c3, c2, 3, 3)))
+    c2f("model.4", c3, c3, reps[1])
+    specs.append(("model.5.conv", (c4, c3, 3, 3)))
+    c2f("model.6", c4, c4, reps[2])
+    specs.append(("model.7.conv", (c5, c4, 3, 3)))
+    c2f("model.8", c5, c5, reps[3])
+    return specs
+
+
+def yolov8_cls_layer_specs(scale: str = "n", nc: int = 1000) -> list[tuple[str, tuple[int, ...], bool]]:
+    """(tensor name, shape, has_act) of a fused YOLOv8-cls model: the backbone convs, then Classify's conv and linear layer."""
+    depth, width, maxc = CLS_SCALES[scale]
+    ch = lambda c: _make_divisible(min(c, maxc) * width)
+    rep = lambda n: max(round(n * depth), 1)
+    c5 = ch(1024)
+    specs = [(n, s, True) for n, s in _cls_backbone_specs(ch(64), ch(128), ch(256), ch(512), c5, (rep(3), rep(6), rep(6), rep(3)))]
+    specs.append(("model.9.conv.conv", (1280, c5, 1, 1), True))
+    specs.append(("model.9.linear", (nc, 1280), False))
+    return specs
+
+
+def synthetic_yolov8_cls(seed: int = 0, scale: str = "n", nc: int = 1000, gain: float = 1.7) -> dict[str, np.ndarray]:
+    """Seeded random fused YOLOv8-cls weights, drawn like synthetic_yolov8's: conv weights ~ N(0, gain^2 / fan_in), biases ~ N(0, 0.05^2)."""
+    rng = np.random.default_rng(seed)
+    t: dict[str, np.ndarray] = {}
+    for name, shape, has_act in yolov8_cls_layer_specs(scale, nc):
+        fan_in = int(np.prod(shape[1:]))
+        g = gain if has_act else 1.0
+        t[name + ".weight"] = (rng.standard_normal(shape) * (g / np.sqrt(fan_in))).astype(np.float32)
+        t[name + ".bias"] = (rng.standard_normal(shape[0]) * 0.05).astype(np.float32)
+    return t
+
+
+def is_yolov8_cls(tensors: dict) -> bool:
+    """True for a YOLOv8-cls checkpoint (fused). A file that is no classification model at all gives False; one that looks like a
+    classifier of another family (YOLO11-cls: C3k2 blocks under C2f's tensor names with other widths, C2PSA attention, Classify at
+    model.10) raises NotImplementedError: every backbone shape is checked against the layout model.0's width and the C2f repeat
+    counts imply, so such a file is never built into the wrong network."""
+    if "model.0.conv.weight" not in tensors or is_rtdetr(tensors) or any(k.startswith("model.22.") for k in tensors):
+        return False
+    unsupported = NotImplementedError("ReID model: only the YOLOv8-cls family (yolov8{n,s,m,l,x}-cls: Conv/C2f backbone model.0-8, "
+                                      "Classify at model.9) is implemented; this file has another topology")
+    if any(".attn." in k or k.startswith("model.10.") for k in tensors):
+        raise unsupported
+    c1 = int(np.shape(tensors["model.0.conv.weight"])[0])
+    reps = []
+    for i in (2, 4, 6, 8):
+        n = 0
+        while f"model.{i}.m.{n}.cv1.conv.weight" in tensors:
+            n += 1
+        reps.append(n)
+    if min(reps) < 1:
+        raise unsupported
+    want = _cls_backbone_specs(c1, 2 * c1, 4 * c1, 8 * c1, 16 * c1, tuple(reps))
+    names = {n for n, _ in want}
+    for name, shape in want:
+        w = tensors.get(name + ".weight")
+        if w is None or tuple(np.shape(w)) != shape:
+            raise unsupported
+    extra = {k.rsplit(".", 1)[0] for k in tensors if k.startswith(("model.1.", "model.2.", "model.3.", "model.4.", "model.5.", "model.6.",
+                                                                  "model.7.", "model.8.")) and k.endswith(".weight")} - names
+    if extra:
+        raise unsupported
+    return True
+
+
+def cls_imgsz(tensors: dict) -> int:
+    """The classifier's input size: the optional ``cls.meta`` tensor ([imgsz], written by tools/convert_weights.py), else 224."""
+    m = tensors.get("cls.meta")
+    return int(np.asarray(m).ravel()[0]) if m is not None and np.size(m) else 224

@@ -329,6 +329,41 @@ int gtx_detector_profile(gtx_detector* det, int nb, int iters, int cap, char* na
                          int* launches, float* total_ms, double* flops, double* bytes,
                          int* n_families);
 
+/* ------------------------------------------------------------------ ReID embedder
+ * A separate appearance network for `with_reid: true, model: <cls checkpoint>` (BoT-SORT, Deep OC-SORT, TrackTrack;
+ * default.yaml:379, :421, :470): ultralytics' trackers/bot_sort.py ReID. Per detection, save_one_box's crop (gain 1.02, pad 10)
+ * resampled as classify_transforms(imgsz) does (PIL bilinear to short side imgsz, center crop), the YOLOv8-cls backbone
+ * (model.0 - model.8, fused tensors by ultralytics state_dict names) and the global average pool of model.8: [n][dim] fp32,
+ * dim = model.8's channels. The Classify head is not run. fp32_split: 1 = split-f16x3 convolutions with the detector's
+ * saturation rule (a pass that clamps is re-run on the exact-fp32 kernels, and every later one; gtx_embedder_fell_back), 0 = exact
+ * fp32. Added in ABI 10 without changing anything before it. */
+typedef struct gtx_embedder gtx_embedder;
+int gtx_embedder_create(gtx_ctx* ctx, int imgsz, int max_crops, int fp32_split, gtx_embedder** out);
+void gtx_embedder_destroy(gtx_embedder* e);
+int gtx_embedder_set_tensor(gtx_embedder* e, const char* name, const float* data, int ndim, const int64_t* shape);
+int gtx_embedder_finalize(gtx_embedder* e);
+int gtx_embedder_dim(gtx_embedder* e, int* dim);
+/* frames_dptr: nb BGR u8 frames [h][w][3] back to back in HBM; counts[nb]: boxes per frame; xyxy: [sum counts][4] host, frame pixels.
+ * _submit_dev enqueues the pass on the context's stream (the frames are read there, in stream order; a pass whose split-f16x3
+ * convolutions saturate is re-run from the same frames inside _collect) and returns; _collect waits and writes out [n][dim]
+ * (cap >= n). One pass in flight per embedder. Passes of more than max_crops boxes run in chunks of max_crops. No boxes: *n = 0,
+ * nothing is launched. _embed_dev = _submit_dev + _collect. */
+int gtx_embedder_submit_dev(gtx_embedder* e, const void* frames_dptr, int nb, int h, int w, const int* counts, const float* xyxy);
+int gtx_embedder_collect(gtx_embedder* e, float* out, int cap, int* n);
+int gtx_embedder_embed_dev(gtx_embedder* e, const void* frames_dptr, int nb, int h, int w, const int* counts, const float* xyxy,
+                           float* out, int cap, int* n);
+/* Debug reads of the last collected pass (crop i must lie in its last chunk): the u8 network input of crop i, out [imgsz][imgsz][4]
+ * (channel slots = the network's input channels, the frame's B, G, R, then 0), and a named layer's output ("model.4",
+ * "model.7.conv", ...), NHWC fp32 (out NULL: shape only). */
+int gtx_embedder_crops(gtx_embedder* e, int i, uint8_t* out);
+int gtx_embedder_layer_output(gtx_embedder* e, int i, const char* layer, float* out, int* h, int* w, int* c);
+int gtx_embedder_saturated(gtx_embedder* e, int clear, int* flag);
+int gtx_embedder_fell_back(gtx_embedder* e, int* fell_back);
+/* Per-launch mean times of `iters` forward passes over n crops (the last pass's network input), names 128 chars each. */
+int gtx_embedder_profile(gtx_embedder* e, int n, int iters, int cap, char* names, float* ms, double* flops, int* n_ops);
+/* Host only: save_one_box's clipped crop [x1, y1, x2, y2) of each of n boxes in an h x w frame (out [n][4]). */
+int gtx_reid_crop_boxes(const float* xyxy, int n, int h, int w, int* out);
+
 /* ------------------------------------------------------------------ tracker (host, C++)
  * Stands in for the tracker callback ultralytics runs inside model.track()
  * (BYTETracker / BOTSORT.update; cfg tracker.* default.yaml:361-389). */

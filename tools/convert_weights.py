@@ -14,6 +14,9 @@ too (`model.0.stem1.conv.weight` ... `model.28.decoder.layers.5.norm3.bias`); wh
 branches where a version does not fuse them, the decoder's Sequential(Conv2d, BatchNorm2d) input projections -- is folded by
 geotrax_amd.weights.load_weights when the file is read. The decoder's head / point / query counts, which no tensor shape carries,
 go into the small `rtdetr.meta` tensor [heads, points, queries, AIFI heads].
+
+A YOLOv8-cls checkpoint (the ReID network of `with_reid: true, model: <file>.safetensors` in a tracker yaml) is written the same
+way, plus `cls.meta` = [imgsz] from the checkpoint's training arguments (geotrax_amd.weights.cls_imgsz; 224 when absent).
 """
 import sys
 from pathlib import Path
@@ -43,6 +46,10 @@ def main():
         aifi = next((m for m in net.model if type(m).__name__ == "AIFI"), None)
         sd["rtdetr.meta"] = torch.tensor([float(layer.cross_attn.n_heads), float(layer.cross_attn.n_points), float(dec.num_queries),
                                           float(aifi.ma.num_heads if aifi is not None else 8)])
+    if type(dec).__name__ == "Classify":              # a ReID network (`with_reid: true, model: <file>`): its input size, default 224
+        import torch
+
+        sd["cls.meta"] = torch.tensor([float(yolo.model.args.get("imgsz", 224) if isinstance(getattr(yolo.model, "args", None), dict) else 224)])
     save_file(sd, str(dst))
     dst.with_suffix(".names.yaml").write_text(yaml.safe_dump({int(k): str(v) for k, v in yolo.names.items()}))
     print(f"wrote {dst} ({len(sd)} tensors) and {dst.with_suffix('.names.yaml')}")
