@@ -1047,10 +1047,12 @@ void launch_head_gate(int dtype, const HeadParams& hp, int n, const NmsBuffers& 
 void launch_head_boxes(int dtype, const HeadParams& hp, int n, const NmsBuffers& nb, hipStream_t s) {
   dim3 grid2(64, n), block(256);
   const size_t lds = (size_t)hp.n_levels * hp.lv[0].cb * 64 * sizeof(float);
+  GTX_CHECK(hp.n_levels <= kMaxLevels && hp.lv[0].cb <= 128, "head: %d levels of %d box channels", hp.n_levels, hp.lv[0].cb);
   static std::once_flag once;     // detectors run on several host threads (engine stage 1, set_reference)
   std::call_once(once, [] {
-    GTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(head_boxes_kernel<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 128 * 64 * 4));
-    GTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(head_boxes_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 128 * 64 * 4));
+    // the cap only: a launch asks for its own levels' bytes (YOLOv8s: 48 KB, P2-s: 64 KB), so its occupancy is what that size allows
+    GTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(head_boxes_kernel<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLevels * 128 * 64 * 4));
+    GTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(head_boxes_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLevels * 128 * 64 * 4));
   });
   if (dtype == DT_F16) hipLaunchKernelGGL(head_boxes_kernel<_Float16>, grid2, block, lds, s, hp, nb);
   else hipLaunchKernelGGL(head_boxes_kernel<float>, grid2, block, lds, s, hp, nb);

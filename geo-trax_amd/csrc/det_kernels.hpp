@@ -40,7 +40,7 @@ void launch_upsample2x(int dtype, const void* x, int n, int h, int w, int c, int
                        int in_coff, void* y, int out_cstride, int out_coff, hipStream_t s);
 
 // ---- head decode + NMS ----
-constexpr int kMaxLevels = 3;
+constexpr int kMaxLevels = 4;   // yolov8.yaml: strides 8 / 16 / 32; yolov8-p2.yaml: 4 / 8 / 16 / 32
 struct HeadLevel {
   const void* feat;     // [N][h][w][cstride] T: channels [0,cb) box branch, [cb, cb+cc) cls branch
   int h, w, cstride;
@@ -49,7 +49,7 @@ struct HeadLevel {
   const float* bb;      // [64]
   const float* wc;      // [nc][cc] fp32  final cls 1x1 conv
   const float* bc;      // [nc]
-  float stride;         // 8 / 16 / 32
+  float stride;         // 4 / 8 / 16 / 32
   int anchor_begin;     // index of this level's first anchor
 };
 struct HeadParams {
@@ -90,7 +90,7 @@ struct NmsBuffers {
 };
 
 // Per-object appearance vectors "from the detector" (ultralytics BoT-SORT `with_reid: true, model: auto`,
-// default.yaml:376-379): the Detect layer's three input maps, every level's channels averaged in consecutive groups down to
+// default.yaml:376-379): the Detect layer's input maps (three, four with P2), every level's channels averaged in consecutive groups down to
 // the narrowest level's width (`dim`), read at the anchor each kept box came from (predictor.get_obj_feats).
 struct FeatLevels {
   const void* feat[kMaxLevels];   // [N][h][w][cstride] activations of the detector's dtype (pair format for DT_F32S)

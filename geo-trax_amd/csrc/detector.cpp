@@ -1,6 +1,6 @@
 // YOLOv8 (detect) graph builder + executor. Layer topology follows ultralytics'
-// cfg/models/v8/yolov8.yaml (backbone 0-9, head 10-22); channel widths and bottleneck counts
-// are read off the tensor shapes, so every v8 scale (n/s/m/l/x) loads unchanged.
+// cfg/models/v8/yolov8.yaml (backbone 0-9, head 10-22) or yolov8-p2.yaml (head 10-28, a fourth Detect level at stride 4);
+// channel widths and bottleneck counts are read off the tensor shapes, so every v8 scale (n/s/m/l/x) loads unchanged.
 #include "detector.hpp"
 #include "split_format.hpp"
 
@@ -297,28 +297,20 @@ void Detector::build_graph() {
   }
 
   auto cout_of = [&](const std::string& n) { return (int)tensor(n + ".weight").shape[0]; };
-
-  // ---- backbone ----
-  View a1 = conv("model.1.conv", a0, 2, true, nullptr, nullptr);
-  View a2 = c2f("model.2", a1, true, nullptr);
-  View a3 = conv("model.3.conv", a2, 2, true, nullptr, nullptr);
-  // model.4 output feeds conv5 and Concat(14) = [up13, model.4]
-  const int c4 = cout_of("model.4.cv2.conv"), c6 = cout_of("model.6.cv2.conv");
-  const int c9 = cout_of("model.9.cv2.conv"), c12 = cout_of("model.12.cv2.conv");
-  const int c16 = cout_of("model.16.conv"), c19 = cout_of("model.19.conv");
-  View cat14 = new_view(H / 8, W / 8, c12 + c4);
-  View s4 = cat14.slice(c12, c4);
-  View a4 = c2f("model.4", a3, true, &s4);
-  View a5 = conv("model.5.conv", a4, 2, true, nullptr, nullptr);
-  View cat11 = new_view(H / 16, W / 16, c9 + c6);
-  View s6 = cat11.slice(c9, c6);
-  View a6 = c2f("model.6", a5, true, &s6);
-  View a7 = conv("model.7.conv", a6, 2, true, nullptr, nullptr);
-  View a8 = c2f("model.8", a7, true, nullptr);
-  // ---- SPPF (model.9): cv1 -> 3 cascaded pools -> cv2; output lives in Concat(20) = [conv19, model.9]
-  View cat20 = new_view(H / 32, W / 32, c19 + c9);
-  View s9 = cat20.slice(c19, c9);
-  {
+  // yolov8.yaml (Detect = model.22 on 15 / 18 / 21) or yolov8-p2.yaml (one more Upsample + Concat + C2f at stride 4 in the neck,
+  // Detect = model.28 on 18 / 21 / 24 / 27): told apart by the tensor names, like the reference's model yaml does
+  const bool p2 = has("model.28.cv2.0.0.conv.weight");
+  auto upsample = [&](const std::string& name, const View& src, const View& dst) {
+    Op op;
+    op.kind = Op::UPSAMPLE;
+    op.name = name;
+    op.family = "upsample2x_kernel";
+    op.in = src;
+    op.out = dst;
+    ops_.push_back(op);
+  };
+  // ---- SPPF (model.9): cv1 -> 3 cascaded pools -> cv2; its output is written into the slice `s9` of the last Concat
+  auto sppf = [&](const View& a8, const View& s9) {
     const int cm = cout_of("model.9.cv1.conv");
     View sp = new_view(a8.h, a8.w, 4 * cm);
     View sp0 = sp.slice(0, cm);
@@ -332,51 +324,116 @@ void Detector::build_graph() {
     ops_.push_back(op);
     conv("model.9.cv2.conv", sp, 1, true, &s9, nullptr);
     layer_views_["model.9"] = s9;
-  }
-  // ---- head ----
-  auto upsample = [&](const std::string& name, const View& src, const View& dst) {
-    Op op;
-    op.kind = Op::UPSAMPLE;
-    op.name = name;
-    op.family = "upsample2x_kernel";
-    op.in = src;
-    op.out = dst;
-    ops_.push_back(op);
   };
-  // torch's Upsample + Concat in front of model.12 / model.15: the split-f16x3 path reads the low-resolution tensor in
-  // place from the C2f's first 1x1 conv (ConvProblem::in2), the other arithmetics write the upsampled copy
-  const bool fuse_up = conv_dtype_ == DT_F32S && c9 % 32 == 0 && c12 % 32 == 0;
-  if (!fuse_up) upsample("model.10", s9, cat11.slice(0, c9));
-  View cat17 = new_view(H / 16, W / 16, c16 + c12);
-  View s12 = cat17.slice(c16, c12);
-  c2f("model.12", cat11, false, &s12, fuse_up ? &s9 : nullptr);
-  if (!fuse_up) upsample("model.13", s12, cat14.slice(0, c12));
-  View a15 = c2f("model.15", cat14, false, nullptr, fuse_up ? &s12 : nullptr);
-  View s16 = cat17.slice(0, c16);
-  conv("model.16.conv", a15, 2, true, &s16, nullptr);
-  View a18 = c2f("model.18", cat17, false, nullptr);
-  View s19 = cat20.slice(0, c19);
-  conv("model.19.conv", a18, 2, true, &s19, nullptr);
-  View a21 = c2f("model.21", cat20, false, nullptr);
+  std::vector<View> lvl_in;       // the Detect layer's inputs, finest level first
+  std::vector<float> strides;
+  if (!p2) {
+    // ---- backbone ----
+    View a1 = conv("model.1.conv", a0, 2, true, nullptr, nullptr);
+    View a2 = c2f("model.2", a1, true, nullptr);
+    View a3 = conv("model.3.conv", a2, 2, true, nullptr, nullptr);
+    // model.4 output feeds conv5 and Concat(14) = [up13, model.4]
+    const int c4 = cout_of("model.4.cv2.conv"), c6 = cout_of("model.6.cv2.conv");
+    const int c9 = cout_of("model.9.cv2.conv"), c12 = cout_of("model.12.cv2.conv");
+    const int c16 = cout_of("model.16.conv"), c19 = cout_of("model.19.conv");
+    View cat14 = new_view(H / 8, W / 8, c12 + c4);
+    View s4 = cat14.slice(c12, c4);
+    View a4 = c2f("model.4", a3, true, &s4);
+    View a5 = conv("model.5.conv", a4, 2, true, nullptr, nullptr);
+    View cat11 = new_view(H / 16, W / 16, c9 + c6);
+    View s6 = cat11.slice(c9, c6);
+    View a6 = c2f("model.6", a5, true, &s6);
+    View a7 = conv("model.7.conv", a6, 2, true, nullptr, nullptr);
+    View a8 = c2f("model.8", a7, true, nullptr);
+    // SPPF output lives in Concat(20) = [conv19, model.9]
+    View cat20 = new_view(H / 32, W / 32, c19 + c9);
+    View s9 = cat20.slice(c19, c9);
+    sppf(a8, s9);
+    // ---- head ----
+    // torch's Upsample + Concat in front of model.12 / model.15: the split-f16x3 path reads the low-resolution tensor in
+    // place from the C2f's first 1x1 conv (ConvProblem::in2), the other arithmetics write the upsampled copy
+    const bool fuse_up = conv_dtype_ == DT_F32S && c9 % 32 == 0 && c12 % 32 == 0;
+    if (!fuse_up) upsample("model.10", s9, cat11.slice(0, c9));
+    View cat17 = new_view(H / 16, W / 16, c16 + c12);
+    View s12 = cat17.slice(c16, c12);
+    c2f("model.12", cat11, false, &s12, fuse_up ? &s9 : nullptr);
+    if (!fuse_up) upsample("model.13", s12, cat14.slice(0, c12));
+    View a15 = c2f("model.15", cat14, false, nullptr, fuse_up ? &s12 : nullptr);
+    View s16 = cat17.slice(0, c16);
+    conv("model.16.conv", a15, 2, true, &s16, nullptr);
+    View a18 = c2f("model.18", cat17, false, nullptr);
+    View s19 = cat20.slice(0, c19);
+    conv("model.19.conv", a18, 2, true, &s19, nullptr);
+    View a21 = c2f("model.21", cat20, false, nullptr);
+    lvl_in = {a15, a18, a21};
+    strides = {8.f, 16.f, 32.f};
+    det_pfx_ = "model.22";
+  } else {
+    // ---- backbone (as yolov8.yaml); model.2's output also feeds Concat(17) = [up16, model.2] ----
+    const int c2 = cout_of("model.2.cv2.conv"), c4 = cout_of("model.4.cv2.conv"), c6 = cout_of("model.6.cv2.conv");
+    const int c9 = cout_of("model.9.cv2.conv"), c12 = cout_of("model.12.cv2.conv"), c15 = cout_of("model.15.cv2.conv");
+    const int c19 = cout_of("model.19.conv"), c22 = cout_of("model.22.conv"), c25 = cout_of("model.25.conv");
+    View a1 = conv("model.1.conv", a0, 2, true, nullptr, nullptr);
+    View cat17 = new_view(H / 4, W / 4, c15 + c2);
+    View s2 = cat17.slice(c15, c2);
+    View a2 = c2f("model.2", a1, true, &s2);
+    View a3 = conv("model.3.conv", a2, 2, true, nullptr, nullptr);
+    View cat14 = new_view(H / 8, W / 8, c12 + c4);           // [up13, model.4]
+    View s4 = cat14.slice(c12, c4);
+    View a4 = c2f("model.4", a3, true, &s4);
+    View a5 = conv("model.5.conv", a4, 2, true, nullptr, nullptr);
+    View cat11 = new_view(H / 16, W / 16, c9 + c6);          // [up10, model.6]
+    View s6 = cat11.slice(c9, c6);
+    View a6 = c2f("model.6", a5, true, &s6);
+    View a7 = conv("model.7.conv", a6, 2, true, nullptr, nullptr);
+    View a8 = c2f("model.8", a7, true, nullptr);
+    View cat26 = new_view(H / 32, W / 32, c25 + c9);         // [conv25, model.9]
+    View s9 = cat26.slice(c25, c9);
+    sppf(a8, s9);
+    // ---- head: three Upsample + Concat + C2f stages down to stride 4, then three stride-2 Conv + Concat + C2f back up ----
+    const bool fuse_up = conv_dtype_ == DT_F32S && c9 % 32 == 0 && c12 % 32 == 0 && c15 % 32 == 0;
+    if (!fuse_up) upsample("model.10", s9, cat11.slice(0, c9));
+    View cat23 = new_view(H / 16, W / 16, c22 + c12);        // [conv22, model.12]
+    View s12 = cat23.slice(c22, c12);
+    c2f("model.12", cat11, false, &s12, fuse_up ? &s9 : nullptr);
+    if (!fuse_up) upsample("model.13", s12, cat14.slice(0, c12));
+    View cat20 = new_view(H / 8, W / 8, c19 + c15);          // [conv19, model.15]
+    View s15 = cat20.slice(c19, c15);
+    c2f("model.15", cat14, false, &s15, fuse_up ? &s12 : nullptr);
+    if (!fuse_up) upsample("model.16", s15, cat17.slice(0, c15));
+    View a18 = c2f("model.18", cat17, false, nullptr, fuse_up ? &s15 : nullptr);
+    View s19 = cat20.slice(0, c19);
+    conv("model.19.conv", a18, 2, true, &s19, nullptr);
+    View a21 = c2f("model.21", cat20, false, nullptr);
+    View s22 = cat23.slice(0, c22);
+    conv("model.22.conv", a21, 2, true, &s22, nullptr);
+    View a24 = c2f("model.24", cat23, false, nullptr);
+    View s25 = cat26.slice(0, c25);
+    conv("model.25.conv", a24, 2, true, &s25, nullptr);
+    View a27 = c2f("model.27", cat26, false, nullptr);
+    lvl_in = {a18, a21, a24, a27};
+    strides = {4.f, 8.f, 16.f, 32.f};
+    det_pfx_ = "model.28";
+  }
+  const int nl = (int)lvl_in.size();
+  GTX_CHECK(nl <= kMaxLevels, "internal: %d Detect levels", nl);
 
-  // ---- Detect (model.22) ----
+  // ---- Detect (model.22, or model.28 of the P2 graph) ----
   // Stage 1 fuses the sibling convs cv2[l][0] and cv3[l][0] (same input) into one conv by
   // stacking their output channels; stage 2 runs cv2[l][1] and cv3[l][1] on channel slices.
-  // The three levels go out as one grouped launch per stage. The final 1x1 convs are folded
+  // The levels (three, four with P2) go out as one grouped launch per stage. The final 1x1 convs are folded
   // into the decode kernels (the box one only runs for anchors that pass the score gate).
-  const View lvl_in[3] = {a15, a18, a21};
-  const float strides[3] = {8.f, 16.f, 32.f};
   std::vector<Op> st1, st2;
   head_ = HeadParams{};
-  head_.n_levels = 3;
+  head_.n_levels = nl;
   head_.nc = cfg_.nc;
   head_.conf = cfg_.conf;
   head_.class_mask[0] = head_.class_mask[1] = cfg_.n_classes == 0 ? ~0ull : 0ull;
   for (int i = 0; i < cfg_.n_classes; ++i)
     if (cfg_.classes[i] >= 0 && cfg_.classes[i] < 128) head_.class_mask[cfg_.classes[i] >> 6] |= 1ull << (cfg_.classes[i] & 63);
   int anchor = 0;
-  for (int l = 0; l < 3; ++l) {
-    const std::string b2 = "model.22.cv2." + std::to_string(l), b3 = "model.22.cv3." + std::to_string(l);
+  for (int l = 0; l < nl; ++l) {
+    const std::string b2 = det_pfx_ + ".cv2." + std::to_string(l), b3 = det_pfx_ + ".cv3." + std::to_string(l);
     const HostTensor &w20 = tensor(b2 + ".0.conv.weight"), &w30 = tensor(b3 + ".0.conv.weight");
     const int cb = (int)w20.shape[0], cc = (int)w30.shape[0], cin = (int)w20.shape[1];
     GTX_CHECK(cin == lvl_in[l].c && (int)w30.shape[1] == cin, "Detect level %d input channels", l);
@@ -393,11 +450,11 @@ void Detector::build_graph() {
     bs.data.insert(bs.data.end(), b30.begin(), b30.end());
     tensors_["__head" + std::to_string(l) + ".s1.bias"] = bs;
     const size_t mark = ops_.size();
-    // The three levels run as grouped launches: one K chunk and one cout tile for all members of a stage. Widths that
+    // The levels run as grouped launches: one K chunk and one cout tile for all members of a stage. Widths that
     // are multiples of 16 only (yolov8 n / m / x) take the 16-channel chunk; a stage with a member whose Cout is not a
     // multiple of 64 takes the 32-cout tile.
     bool k32 = true;
-    for (int q = 0; q < 3; ++q) k32 = k32 && lvl_in[q].c % 32 == 0;
+    for (int q = 0; q < nl; ++q) k32 = k32 && lvl_in[q].c % 32 == 0;
     force_kc_ = conv_dtype_ == DT_F16 ? (k32 ? 32 : 16) : 0;
     force_bn_ = (cb + cc) % 64 == 0 ? 64 : 32;
     View h1 = conv("__head" + std::to_string(l) + ".s1", lvl_in[l], 1, true, nullptr, nullptr);
@@ -451,7 +508,7 @@ void Detector::build_graph() {
     }
     L.bb = upload(tensor(b2 + ".2.bias").data);
     L.wc = upload(wc.data); L.bc = upload(tensor(b3 + ".2.bias").data);
-    layer_views_["model.22.feat" + std::to_string(l)] = h2;
+    layer_views_[det_pfx_ + ".feat" + std::to_string(l)] = h2;
   }
   head_.n_anchors = anchor;
   {
@@ -470,7 +527,7 @@ void Detector::build_graph() {
       stage.push_back(g);
     };
     std::vector<Op> d1, d2;                          // the dense box layers, kept for the debug read-backs and the overflow case
-    for (int l = 0; l < 3; ++l) {
+    for (int l = 0; l < nl; ++l) {
       Op o1 = head_ops_[l][0];
       const Op &o2 = head_ops_[l][1], &o3 = head_ops_[l][2];
       if (sparse_on_) {
@@ -486,32 +543,33 @@ void Detector::build_graph() {
         GTX_CHECK(full.bias && o2.grp.p[0].bias && o2.grp.p[0].Cin == 64 && o2.grp.p[0].Cout == 64, "sparse box branch: unexpected Detect box layers");
         Op box1 = o1;                                // the box tile alone
         box1.grp.p[0].Cout = cb;
-        add(d1, "model.22.box1", box1);
-        add(d2, "model.22.box2", o2);
+        add(d1, (det_pfx_ + ".box1").c_str(), box1);
+        add(d2, (det_pfx_ + ".box2").c_str(), o2);
         ConvProblem& p = o1.grp.p[0];                // the class tiles alone
         p.wpack = static_cast<const char*>(full.wpack) + tile_bytes;
         p.bias = full.bias + 64;
         p.Cout = cc;
         p.out_coff = full.out_coff + cb;
-        add(st1, "model.22.stage1", o1);
-        add(st2, "model.22.stage2", o3);
+        add(st1, (det_pfx_ + ".stage1").c_str(), o1);
+        add(st2, (det_pfx_ + ".stage2").c_str(), o3);
       } else {
-        add(st1, "model.22.stage1", o1);
-        add(st2, "model.22.stage2", o2);
-        add(st2, "model.22.stage2", o3);
+        add(st1, (det_pfx_ + ".stage1").c_str(), o1);
+        add(st2, (det_pfx_ + ".stage2").c_str(), o2);
+        add(st2, (det_pfx_ + ".stage2").c_str(), o3);
       }
     }
     if (sparse_on_) {
-      sparse_.n_levels = 3;
+      sparse_.n_levels = nl;
       for (std::vector<Op>* stage : {&d1, &d2})
         for (Op& g : *stage) { g.family = conv_kernel_name(g.cfg); dense_box_ops_.push_back(g); }
     }
   }
   feat_levels_ = FeatLevels{};
   if (cfg_.obj_feats) {                           // `with_reid: true, model: auto`: the Detect layer's inputs, read after NMS
-    feat_levels_.n_levels = 3;
-    feat_levels_.dim = std::min(lvl_in[0].c, std::min(lvl_in[1].c, lvl_in[2].c));
-    for (int l = 0; l < 3; ++l) {
+    feat_levels_.n_levels = nl;
+    feat_levels_.dim = lvl_in[0].c;
+    for (int l = 1; l < nl; ++l) feat_levels_.dim = std::min(feat_levels_.dim, lvl_in[l].c);
+    for (int l = 0; l < nl; ++l) {
       feat_levels_.feat[l] = lvl_in[l].ptr; feat_levels_.h[l] = lvl_in[l].h; feat_levels_.w[l] = lvl_in[l].w;
       feat_levels_.cstride[l] = lvl_in[l].cstride; feat_levels_.coff[l] = lvl_in[l].coff; feat_levels_.c[l] = lvl_in[l].c;
       feat_levels_.anchor_begin[l] = head_.lv[l].anchor_begin;
@@ -1187,7 +1245,7 @@ void Detector::layer_output(int b, const std::string& layer, float* out, int* h,
   auto it = layer_views_.find(layer);
   if (it == layer_views_.end()) fail(-1, "unknown layer '%s'", layer.c_str());
   const View& v = it->second;
-  if (out && sparse_on_ && cur_nb_ > 0 && (layer.rfind("model.22.", 0) == 0 || layer.rfind("__head", 0) == 0)) {
+  if (out && sparse_on_ && cur_nb_ > 0 && (layer.rfind(det_pfx_ + ".", 0) == 0 || layer.rfind("__head", 0) == 0)) {
     GTX_HIP(hipSetDevice(ctx_->device));
     run_dense_box(ctx_->stream);                   // the head's box layers are not part of the forward in sparse mode
     GTX_HIP(hipStreamSynchronize(ctx_->stream));

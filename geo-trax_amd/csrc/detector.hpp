@@ -203,7 +203,8 @@ class Detector : public DetectorBase {
   static constexpr int kSparseCap = 8192;   // candidates per image its buffer holds
   bool sparse_on_ = false;
   SparseBox sparse_{};
-  Op head_ops_[3][3];
+  Op head_ops_[kMaxLevels][3];
+  std::string det_pfx_ = "model.22";   // the Detect module: model.22 (yolov8.yaml) or model.28 (yolov8-p2.yaml)
   std::vector<Op> dense_box_ops_;
   bool dense_head_valid_ = false;
   int* h_count_ = nullptr;   // pinned: candidates per image of the pass in flight

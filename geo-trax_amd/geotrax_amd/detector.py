@@ -57,12 +57,14 @@ class Detector:
         self.fp32_split = bool(fp32_split) and not half
         self.ctx = ctx or _lib.default_context()
         lib = self.ctx.lib
-        from .weights import is_rtdetr
+        from .weights import is_rtdetr, is_yolov8_p2
 
         self.rtdetr = is_rtdetr(tensors)     # the graph the tensors describe picks the detector family (reference: the model's yaml, extract.py:222-225)
         if self.rtdetr and obj_feats:
             raise NotImplementedError("RT-DETR: obj_feats (ReID `model: auto`) is not implemented")
-        nc = int(tensors["model.28.enc_score_head.weight" if self.rtdetr else "model.22.cv3.0.2.weight"].shape[0])
+        self.p2 = not self.rtdetr and is_yolov8_p2(tensors)   # yolov8-p2.yaml: a fourth Detect level at stride 4, Detect = model.28
+        nc = int(tensors["model.28.enc_score_head.weight" if self.rtdetr else
+                         "model.28.cv3.0.2.weight" if self.p2 else "model.22.cv3.0.2.weight"].shape[0])
         cfg = DetConfig(imgsz=imgsz, conf=conf, iou=iou, max_det=max_det, agnostic_nms=int(agnostic_nms),
                         half=int(half), rect=int(rect), nc=nc, n_classes=0, max_batch=max_batch,
                         frame_h=frame_hw[0], frame_w=frame_hw[1], fp32_split=int(self.fp32_split), obj_feats=int(bool(obj_feats)), arch=int(self.rtdetr))
@@ -204,6 +206,8 @@ class Detector:
         na = C.c_int()
         h, w = self.net_hw
         anchors = (h // 8) * (w // 8) + (h // 16) * (w // 16) + (h // 32) * (w // 32)
+        if self.p2:
+            anchors += (h // 4) * (w // 4)
         if self.rtdetr:                      # [queries, 4 + nc]: xywh normalised to the frame + class scores (or logits)
             anchors = self.n_queries
         out = np.zeros((anchors, 4 + self.nc), np.float32)

@@ -158,6 +158,79 @@ def synthetic_yolov8(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: flo
     return t
 
 
+# --------------------------------------------------------------------------- YOLOv8-P2 (yolov8-p2.yaml)
+# geo-trax's train.sh `-p`: the backbone of yolov8.yaml, a neck that goes one Upsample + Concat(model.2) + C2f further down to
+# stride 4 (model.16-18) and back up (model.19-27), and Detect = model.28 on [18, 21, 24, 27] (strides 4 / 8 / 16 / 32). The Detect
+# widths follow its finest input: cb = max(16, c18 // 4, 64), cc = max(c18, min(nc, 100)).
+
+def is_yolov8_p2(tensors: dict) -> bool:
+    return "model.28.cv2.0.0.conv.weight" in tensors
+
+
+def yolov8_p2_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
+    """(tensor name, OIHW shape, has_act) for every conv of a fused YOLOv8-P2 detect model."""
+    depth, width, maxc = SCALES[scale]
+    ch = lambda c: _make_divisible(min(c, maxc) * width)
+    rep = lambda n: max(round(n * depth), 1)
+    backbone = [s for s in yolov8_layer_specs(scale, nc) if int(s[0].split(".")[1]) <= 9]
+    specs = list(backbone)
+
+    def conv(name, cin, cout, k):
+        specs.append((name, (cout, cin, k, k), True))
+
+    def c2f(pfx, cin, cout, n):
+        c = cout // 2
+        conv(f"{pfx}.cv1.conv", cin, 2 * c, 1)
+        for k in range(n):
+            conv(f"{pfx}.m.{k}.cv1.conv", c, c, 3)
+            conv(f"{pfx}.m.{k}.cv2.conv", c, c, 3)
+        conv(f"{pfx}.cv2.conv", (2 + n) * c, cout, 1)
+
+    c1, c2, c3, c4, c5 = ch(128), ch(256), ch(512), ch(1024), ch(1024)   # c1: model.2's width (yolov8.yaml's 128 x width)
+    c2f("model.12", c5 + c3, c3, rep(3))
+    c2f("model.15", c3 + c2, c2, rep(3))
+    c2f("model.18", c2 + c1, c1, rep(3))
+    conv("model.19.conv", c1, c1, 3)
+    c2f("model.21", c1 + c2, c2, rep(3))
+    conv("model.22.conv", c2, c2, 3)
+    c2f("model.24", c2 + c3, c3, rep(3))
+    conv("model.25.conv", c3, c3, 3)
+    c2f("model.27", c3 + c5, c5, rep(3))
+    cb = max(16, c1 // 4, 64)
+    cc = max(c1, min(nc, 100))
+    for l, cin in enumerate((c1, c2, c3, c5)):
+        conv(f"model.28.cv2.{l}.0.conv", cin, cb, 3)
+        conv(f"model.28.cv2.{l}.1.conv", cb, cb, 3)
+        specs.append((f"model.28.cv2.{l}.2", (64, cb, 1, 1), False))
+        conv(f"model.28.cv3.{l}.0.conv", cin, cc, 3)
+        conv(f"model.28.cv3.{l}.1.conv", cc, cc, 3)
+        specs.append((f"model.28.cv3.{l}.2", (nc, cc, 1, 1), False))
+    return specs
+
+
+def synthetic_yolov8_p2(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0, gain: float = 1.7,
+                        box_decay: float | tuple = 0.3, level_bias: tuple = (0.0, 0.0, -1e4, -1e4),
+                        box_weight_scale: float = 0.3) -> dict[str, np.ndarray]:
+    """Seeded random fused weights of the YOLOv8-P2 architecture, drawn like synthetic_yolov8's (same knobs, same order of draws
+    over yolov8_p2_layer_specs). ``level_bias`` is added to the class logits of the stride-4/8/16/32 heads; the default silences the
+    two coarse heads, whose random logits otherwise dominate, so that the stride-4 and stride-8 anchors are the ones that fire."""
+    rng = np.random.default_rng(seed)
+    decay = np.broadcast_to(np.asarray(box_decay, dtype=np.float64), (4,))
+    t: dict[str, np.ndarray] = {}
+    for name, shape, has_act in yolov8_p2_layer_specs(scale, nc):
+        fan_in = shape[1] * shape[2] * shape[3]
+        g = gain if has_act else 1.0
+        t[name + ".weight"] = (rng.standard_normal(shape) * (g / np.sqrt(fan_in))).astype(np.float32)
+        b = rng.standard_normal(shape[0]) * 0.05
+        if name.startswith("model.28.cv3.") and name.endswith(".2"):
+            b = b + cls_bias + float(level_bias[int(name.split(".")[3])])
+        if name.startswith("model.28.cv2.") and name.endswith(".2"):
+            t[name + ".weight"] *= np.float32(box_weight_scale)
+            b = b - np.repeat(decay, 16) * np.tile(np.arange(16), 4)
+        t[name + ".bias"] = b.astype(np.float32)
+    return t
+
+
 def calibrate_cls_bias(tensors: dict[str, np.ndarray], raw_logits: np.ndarray, conf: float, target: int) -> dict[str, np.ndarray]:
     """Returns a copy of `tensors` whose class-logit biases are shifted by one constant so that
     about `target` anchors of the probed frame clear `conf`. raw_logits: [anchors, nc] class

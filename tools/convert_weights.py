@@ -8,6 +8,8 @@ Run this once on a machine where `ultralytics` is installed (it is not part of t
 
 Conv+BN pairs are fused with ultralytics' own `model.fuse()`; tensor names are the fused model's
 state_dict keys (`model.0.conv.weight`, `model.0.conv.bias`, ... `model.22.cv3.2.2.bias`).
+A YOLOv8-P2 checkpoint (yolov8<scale>-p2.yaml, geo-trax's train.sh `-p`) goes through the same path unchanged: its fused
+state_dict ends in `model.28.cv3.3.2.bias` (Detect on four levels), which is how geotrax_amd.weights.is_yolov8_p2 tells it apart.
 
 An RT-DETR checkpoint (the reference's `RTDETR` branch, geotrax/extract.py:222-225; rtdetr-l topology) keeps its state_dict names
 too (`model.0.stem1.conv.weight` ... `model.28.decoder.layers.5.norm3.bias`); what `fuse()` leaves unfused -- RepConv's two
