@@ -15,6 +15,12 @@
 
 namespace gtx {
 
+// Environment switch: unset or empty -> dflt, else false when it starts with '0'.
+inline bool env_flag(const char* name, bool dflt) {
+  const char* e = getenv(name);
+  return (e && *e) ? e[0] != '0' : dflt;
+}
+
 // Flags for the events host threads wait on (detector / stabilizer / GMC results). Blocking waits let a waiting
 // thread sleep instead of spinning: one process per GPU with three host stages each would otherwise burn 3 cores
 // per rank just waiting (the GPU boxes give a job a CPU quota). GTX_SPIN_WAIT=1 keeps the default spinning waits.

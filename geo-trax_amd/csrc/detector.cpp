@@ -5,153 +5,29 @@
 #include "split_format.hpp"
 
 #include <algorithm>
-#include <array>
 #include <cmath>
-#include <deque>
-#include <functional>
-#include <mutex>
 
 namespace gtx {
 
-Detector::Detector(gtx_ctx* ctx, const gtx_det_config& cfg) : ctx_(ctx), cfg_(cfg) {
-  GTX_CHECK(cfg.imgsz > 0 && cfg.imgsz % 32 == 0, "imgsz must be a positive multiple of 32 (got %d)", cfg.imgsz);
-  GTX_CHECK(cfg.max_det > 0 && cfg.nc > 0 && cfg.nc <= 128, "max_det must be positive and nc in [1, 128] (got %d, %d)", cfg.max_det, cfg.nc);
-  GTX_CHECK(cfg.frame_h > 0 && cfg.frame_w > 0, "frame size must be given");
-  if (cfg_.max_batch < 1) cfg_.max_batch = 1;
+Detector::Detector(gtx_ctx* ctx, const gtx_det_config& cfg)
+    : DetectorBase(ctx, cfg, cfg.half ? DT_F16 : (cfg.fp32_split ? DT_F32S : DT_F32), dtype_size(cfg.half ? DT_F16 : DT_F32),
+                   cfg.half ? DT_F16 : DT_F32) {
   dtype_ = cfg.half ? DT_F16 : DT_F32;
-  conv_dtype_ = (!cfg.half && cfg.fp32_split) ? DT_F32S : dtype_;
   es_ = dtype_size(dtype_);
   lb_ = letterbox_geometry(cfg.frame_h, cfg.frame_w, cfg.imgsz, cfg.rect != 0, 32);
   GTX_CHECK(lb_.net_h % 32 == 0 && lb_.net_w % 32 == 0, "network input %dx%d is not stride aligned", lb_.net_h, lb_.net_w);
-  GTX_HIP(hipSetDevice(ctx->device));
-  for (auto& e : ev_) GTX_HIP(hipEventCreateWithFlags(&e, wait_event_flags(true)));
-  for (auto& e : ev_up_) GTX_HIP(hipEventCreate(&e));
 }
 
 Detector::~Detector() {
-  if (h_out_n_) (void)hipHostFree(h_out_n_);
-  if (h_sat_) (void)hipHostFree(h_sat_);
-  if (h_out_rows_) (void)hipHostFree(h_out_rows_);
   if (h_feats_) (void)hipHostFree(h_feats_);
   if (h_count_) (void)hipHostFree(h_count_);
-  for (auto& e : ev_)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : ev_up_)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : trace_ev_)
-    if (e) (void)hipEventDestroy(e);
-  if (graph_exec_) (void)hipGraphExecDestroy(graph_exec_);
 }
 
-void Detector::set_tensor(const std::string& name, const float* data, int ndim, const int64_t* shape) {
-  GTX_CHECK(!finalized_, "set_tensor after finalize");
-  HostTensor t;
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) {
-    t.shape.push_back(shape[i]);
-    n *= (size_t)shape[i];
-  }
-  t.data.assign(data, data + n);
-  tensors_[name] = std::move(t);
+std::unique_ptr<NetRuntime> Detector::make_exact() const {
+  gtx_det_config c = cfg_;
+  c.fp32_split = 0;
+  return std::unique_ptr<NetRuntime>(new Detector(ctx_, c));
 }
-
-const HostTensor& Detector::tensor(const std::string& name) const {
-  auto it = tensors_.find(name);
-  if (it == tensors_.end()) fail(-1, "missing tensor '%s'", name.c_str());
-  return it->second;
-}
-
-void* Detector::alloc(size_t bytes) {
-  bufs_.emplace_back(bytes);
-  GTX_HIP(hipMemset(bufs_.back().p, 0, bufs_.back().bytes));
-  return bufs_.back().p;
-}
-
-View Detector::new_view(int h, int w, int c) {
-  View v;
-  v.n = cfg_.max_batch;
-  v.h = h;
-  v.w = w;
-  v.cstride = c;
-  v.coff = 0;
-  v.c = c;
-  v.ptr = alloc((size_t)v.n * h * w * c * es_);
-  return v;
-}
-
-namespace {
-bool env_flag(const char* name, bool dflt) {
-  const char* e = getenv(name);
-  return (e && *e) ? e[0] != '0' : dflt;
-}
-
-// Packed weight images are a pure function of (tensor bytes, tile configuration). An engine builds several detectors from
-// the same tensors (one per stream) and a run builds engines video after video: the image is made once per process and
-// shared (packing YOLOv8s takes ~0.15 s of host time per detector, most of what creating one costs).
-struct PackedWeights {
-  std::vector<uint8_t> bytes;
-  float acc_scale = 1.f;
-  std::vector<float> source;      // the tensor the image was packed from: a hit is a hit only when these floats are the caller's
-};
-std::shared_ptr<const PackedWeights> packed_weights(const HostTensor& w, int cout, int cin, const ConvConfig& cfg,
-                                                    const std::function<PackedWeights()>& make) {
-  static std::mutex mu;
-  static std::map<std::array<uint64_t, 4>, std::shared_ptr<const PackedWeights>> cache;
-  uint64_t h = 1469598103934665603ull;                       // FNV-1a over the tensor's bytes, 8 at a time
-  const uint64_t* q = reinterpret_cast<const uint64_t*>(w.data.data());
-  for (size_t i = 0; i < w.data.size() / 2; ++i) h = (h ^ q[i]) * 1099511628211ull;
-  if (w.data.size() & 1) h = (h ^ (uint64_t)__builtin_bit_cast(uint32_t, w.data.back())) * 1099511628211ull;
-  const std::array<uint64_t, 4> key = {h, (uint64_t)w.data.size(), ((uint64_t)cout << 32) | (uint64_t)cin,
-                                       ((uint64_t)cfg.dtype << 40) | ((uint64_t)cfg.ks << 32) | ((uint64_t)cfg.bn << 16) | ((uint64_t)cfg.kc << 4) | (uint64_t)cfg.variant};
-  // The key's 64-bit FNV-1a is a filter, not an identity: a hit must also hold the same floats (a collision between two layers or
-  // checkpoints of one shape would otherwise run the detector on another tensor's weights, silently). Bounded by bytes: the
-  // images + sources of a YOLOv8x are ~1 GB; past 2 GB the oldest entries go.
-  static std::deque<std::array<uint64_t, 4>> order;
-  static size_t held = 0;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find(key);
-    if (it != cache.end() && it->second->source.size() == w.data.size() &&
-        memcmp(it->second->source.data(), w.data.data(), w.data.size() * sizeof(float)) == 0)
-      return it->second;
-  }
-  PackedWeights fresh = make();
-  fresh.source = w.data;
-  auto made = std::make_shared<const PackedWeights>(std::move(fresh));
-  const size_t cost = made->bytes.size() + made->source.size() * sizeof(float);
-  std::lock_guard<std::mutex> lk(mu);
-  auto old = cache.find(key);
-  if (old != cache.end()) {                                    // same key, other floats: the newer tensor takes the slot
-    held -= old->second->bytes.size() + old->second->source.size() * sizeof(float);
-    cache.erase(old);
-    order.erase(std::remove(order.begin(), order.end(), key), order.end());
-  }
-  while (!order.empty() && held + cost > ((size_t)2 << 30)) {
-    auto victim = cache.find(order.front());
-    if (victim != cache.end()) {
-      held -= victim->second->bytes.size() + victim->second->source.size() * sizeof(float);
-      cache.erase(victim);                                     // detectors that use the image keep it alive through their shared_ptr
-    }
-    order.pop_front();
-  }
-  held += cost;
-  order.push_back(key);
-  return cache.emplace(key, std::move(made)).first->second;
-}
-
-// OIHW -> OHWI
-std::vector<float> to_ohwi(const HostTensor& t) {
-  const int O = (int)t.shape[0], I = (int)t.shape[1], KH = (int)t.shape[2], KW = (int)t.shape[3];
-  std::vector<float> r((size_t)O * I * KH * KW);
-  parallel_for(O, [&](int o) {
-    for (int i = 0; i < I; ++i)
-      for (int y = 0; y < KH; ++y)
-        for (int x = 0; x < KW; ++x)
-          r[(((size_t)o * KH + y) * KW + x) * I + i] = t.data[(((size_t)o * I + i) * KH + y) * KW + x];
-  });
-  return r;
-}
-}  // namespace
 
 // Emits one Conv op: weights "<name>.weight" (OIHW) / "<name>.bias" (optional).
 View Detector::conv(const std::string& name, const View& x, int stride, bool act, const View* out_slice,
@@ -159,62 +35,22 @@ View Detector::conv(const std::string& name, const View& x, int stride, bool act
   const HostTensor& w = tensor(name + ".weight");
   GTX_CHECK(w.shape.size() == 4 && w.shape[2] == w.shape[3], "%s: expected OIHW square kernel", name.c_str());
   const int cout = (int)w.shape[0], cin = (int)w.shape[1], ks = (int)w.shape[2];
-  GTX_CHECK(cin == x.c, "%s: weight expects %d input channels, input view has %d", name.c_str(), cin, x.c);
-  const int pad = ks / 2;
-  const int ho = (x.h + 2 * pad - ks) / stride + 1, wo = (x.w + 2 * pad - ks) / stride + 1;
-  View out = out_slice ? *out_slice : new_view(ho, wo, cout);
-  GTX_CHECK(out.h == ho && out.w == wo && out.c == cout, "%s: output view mismatch", name.c_str());
-  if (conv_dtype_ == DT_F32S) {     // pair format: whole 8-channel groups everywhere
-    out.plain = plain_out_;
-    GTX_CHECK(!x.plain && (!residual || !residual->plain) && (!up_src || !up_src->plain), "%s: a plain fp32 tensor cannot feed a split convolution", name.c_str());
-    GTX_CHECK(x.cstride % 8 == 0 && x.coff % 8 == 0 && out.cstride % 8 == 0 && out.coff % 8 == 0 &&
-                  (!residual || (residual->cstride % 8 == 0 && residual->coff % 8 == 0)),
-              "%s: channel strides / offsets of the split-f16x3 path must be multiples of 8", name.c_str());
-  }
-
-  Op op;
-  op.kind = Op::CONV;
-  op.name = name;
-  op.cfg = conv_pick_config(conv_dtype_, ks, stride, cin, cout, force_kc_, force_bn_, (long)x.n * ho * wo);
-  const auto pw = packed_weights(w, cout, cin, op.cfg, [&] {
-    PackedWeights r;
-    const std::vector<float> ohwi = to_ohwi(w);
-    r.bytes = pack_conv_weights(ohwi.data(), cout, cin, op.cfg, &r.acc_scale);
-    return r;
-  });
-  const float acc_scale = pw->acc_scale;
-  const std::vector<uint8_t>& packed = pw->bytes;
-  void* dw = alloc(packed.size());
-  GTX_HIP(hipMemcpy(dw, packed.data(), packed.size(), hipMemcpyHostToDevice));
-  float* db = nullptr;
-  if (has(name + ".bias")) {
-    const HostTensor& b = tensor(name + ".bias");
-    GTX_CHECK((int)b.data.size() == cout, "%s: bias size", name.c_str());
-    db = (float*)alloc(((cout + 63) / 64 * 64) * sizeof(float));      // zero-filled up to a whole cout tile: the kernels load a tile's bias unconditionally
-    GTX_HIP(hipMemcpy(db, b.data.data(), cout * sizeof(float), hipMemcpyHostToDevice));
-  }
-  ConvProblem& p = op.grp.p[0];
-  p.in = x.ptr; p.out = out.ptr; p.wpack = dw; p.bias = db;
-  p.res = residual ? residual->ptr : nullptr;
-  p.N = x.n; p.H = x.h; p.W = x.w; p.Ho = ho; p.Wo = wo; p.Cin = cin; p.Cout = cout;
-  p.in_cstride = x.cstride; p.in_coff = x.coff;
-  p.out_cstride = out.cstride; p.out_coff = out.coff;
-  p.res_cstride = residual ? residual->cstride : 0;
-  p.res_coff = residual ? residual->coff : 0;
-  p.act = act ? 1 : 0;
-  p.acc_scale = acc_scale;
-  p.out_plain = out.plain ? 1 : 0;
-  p.sat_flag = conv_dtype_ == DT_F32S ? sat_dev_ : nullptr;
+  GTX_CHECK(fmt_ != DT_F32S || !up_src || !up_src->plain, "%s: a plain fp32 tensor cannot feed a split convolution", name.c_str());
+  ConvArgs a;
+  a.stride = stride; a.act = act ? 1 : 0; a.out_slice = out_slice; a.residual = residual;
+  a.plain_out = fmt_ == DT_F32S && plain_out_;
+  a.force_kc = force_kc_; a.force_bn = force_bn_;
+  a.out_pixels = (long)x.n * ((x.h + 2 * (ks / 2) - ks) / stride + 1) * ((x.w + 2 * (ks / 2) - ks) / stride + 1);
+  const View out = emit_conv(ops_, name, w.data.data(), cout, cin, ks, bias_of(name, cout), x, a);
   if (up_src) {
+    Op& op = ops_.back();
     if (op.cfg.variant == 6) op.cfg.variant = 2;     // the second source is read by the 32x32x16 kernel only (same weight image)
     GTX_CHECK(ks == 1 && stride == 1 && op.cfg.variant == 2 && up_src->h * 2 == x.h && up_src->w * 2 == x.w && up_src->c < cin,
               "%s: upsampled source does not fit", name.c_str());
+    ConvProblem& p = op.grp.p[0];
     p.in2 = up_src->ptr; p.in2_cstride = up_src->cstride; p.in2_coff = up_src->coff; p.c_split = up_src->c;
+    op.family = conv_kernel_name(op.cfg);
   }
-  op.grp.count = 1;
-  op.family = conv_kernel_name(op.cfg);
-  ops_.push_back(op);
-  layer_views_[name] = out;
   return out;
 }
 
@@ -243,11 +79,7 @@ View Detector::c2f(const std::string& pfx, const View& x, bool shortcut, const V
 void Detector::build_graph() {
   const int H = lb_.net_h, W = lb_.net_w;
   img_ = new_view(H, W, 4);
-  if (conv_dtype_ == DT_F32S) {
-    sat_dev_ = (int*)alloc(sizeof(int));
-    GTX_HIP(hipHostMalloc((void**)&h_sat_, sizeof(int)));
-    *h_sat_ = 0;
-  }
+  alloc_sat_flag();
 
   // ---- layer 0: stem (dedicated 3-channel kernel) ----
   const HostTensor& w0 = tensor("model.0.conv.weight");
@@ -270,7 +102,7 @@ void Detector::build_graph() {
     Op op;
     op.kind = Op::STEM;
     op.name = "model.0.conv";
-    op.family = dtype_ == DT_F16 ? "stem_mfma_kernel" : (conv_dtype_ == DT_F32S ? "stem_split_kernel" : "stem_kernel");
+    op.family = dtype_ == DT_F16 ? "stem_mfma_kernel" : (fmt_ == DT_F32S ? "stem_split_kernel" : "stem_kernel");
     op.in = img_;
     op.out = a0;
     op.w27 = dw;
@@ -280,7 +112,7 @@ void Detector::build_graph() {
       void* dp = alloc(pk.size() * 2);
       GTX_HIP(hipMemcpy(dp, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
       op.wpk = dp;
-    } else if (conv_dtype_ == DT_F32S) {
+    } else if (fmt_ == DT_F32S) {
       const std::vector<uint16_t> pk = pack_stem_weights_split(w27.data(), c0, &op.stem_scale);
       void* dp = alloc(pk.size() * 2);
       GTX_HIP(hipMemcpy(dp, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
@@ -352,7 +184,7 @@ void Detector::build_graph() {
     // ---- head ----
     // torch's Upsample + Concat in front of model.12 / model.15: the split-f16x3 path reads the low-resolution tensor in
     // place from the C2f's first 1x1 conv (ConvProblem::in2), the other arithmetics write the upsampled copy
-    const bool fuse_up = conv_dtype_ == DT_F32S && c9 % 32 == 0 && c12 % 32 == 0;
+    const bool fuse_up = fmt_ == DT_F32S && c9 % 32 == 0 && c12 % 32 == 0;
     if (!fuse_up) upsample("model.10", s9, cat11.slice(0, c9));
     View cat17 = new_view(H / 16, W / 16, c16 + c12);
     View s12 = cat17.slice(c16, c12);
@@ -391,7 +223,7 @@ void Detector::build_graph() {
     View s9 = cat26.slice(c25, c9);
     sppf(a8, s9);
     // ---- head: three Upsample + Concat + C2f stages down to stride 4, then three stride-2 Conv + Concat + C2f back up ----
-    const bool fuse_up = conv_dtype_ == DT_F32S && c9 % 32 == 0 && c12 % 32 == 0 && c15 % 32 == 0;
+    const bool fuse_up = fmt_ == DT_F32S && c9 % 32 == 0 && c12 % 32 == 0 && c15 % 32 == 0;
     if (!fuse_up) upsample("model.10", s9, cat11.slice(0, c9));
     View cat23 = new_view(H / 16, W / 16, c22 + c12);        // [conv22, model.12]
     View s12 = cat23.slice(c22, c12);
@@ -455,18 +287,18 @@ void Detector::build_graph() {
     // multiple of 64 takes the 32-cout tile.
     bool k32 = true;
     for (int q = 0; q < nl; ++q) k32 = k32 && lvl_in[q].c % 32 == 0;
-    force_kc_ = conv_dtype_ == DT_F16 ? (k32 ? 32 : 16) : 0;
+    force_kc_ = fmt_ == DT_F16 ? (k32 ? 32 : 16) : 0;
     force_bn_ = (cb + cc) % 64 == 0 ? 64 : 32;
     View h1 = conv("__head" + std::to_string(l) + ".s1", lvl_in[l], 1, true, nullptr, nullptr);
     View h2 = new_view(h1.h, h1.w, cb + cc);
     View h1b = h1.slice(0, cb), h1c = h1.slice(cb, cc), h2b = h2.slice(0, cb), h2c = h2.slice(cb, cc);
-    force_kc_ = conv_dtype_ == DT_F16 ? ((cb % 32 == 0 && cc % 32 == 0) ? 32 : 16) : 0;
+    force_kc_ = fmt_ == DT_F16 ? ((cb % 32 == 0 && cc % 32 == 0) ? 32 : 16) : 0;
     force_bn_ = (cb % 64 == 0 && cc % 64 == 0) ? 64 : 32;
     plain_out_ = true;            // the decode kernels read these two as plain fp32
     conv(b2 + ".1.conv", h1b, 1, true, &h2b, nullptr);
     conv(b3 + ".1.conv", h1c, 1, true, &h2c, nullptr);
     plain_out_ = false;
-    h2.plain = conv_dtype_ == DT_F32S;
+    h2.plain = fmt_ == DT_F32S;
     force_kc_ = force_bn_ = 0;
     // move the three freshly built single-problem ops into the grouped stage ops: one grouped launch per stage and kernel
     // configuration (the levels of a stage share a launch when they share the kernel; the fp32 default path runs its deep
@@ -478,7 +310,7 @@ void Detector::build_graph() {
     // at the candidate anchors only, after the score gate; stage 1 keeps its class half (cout tiles 1..), same packed image,
     // same scale. Needs the 16x16x32 kernel's image (32-channel chunks, one 64-cout box tile); decided for all levels at once.
     if (l == 0) {
-      sparse_on_ = conv_dtype_ == DT_F32S && env_flag("GTX_SPARSE_BOX", true);
+      sparse_on_ = fmt_ == DT_F32S && env_flag("GTX_SPARSE_BOX", true);
       sparse_ = SparseBox{};
       dense_box_ops_.clear();
     }
@@ -587,8 +419,7 @@ void Detector::build_graph() {
 // consumer) become one launch: ConvProblem::post_w. The 3x3 layer's output is never written; the launch writes the 1x1
 // layer's. GTX_FUSE_FRONT=0 keeps the two launches. YOLOv8 n and s qualify (32 / 64 channels); the wider scales do not.
 void Detector::fuse_front() {
-  const char* e = getenv("GTX_FUSE_FRONT");
-  if (conv_dtype_ != DT_F32S || (e && e[0] == '0')) return;
+  if (fmt_ != DT_F32S || !env_flag("GTX_FUSE_FRONT", true)) return;
   for (size_t i = 0; i + 1 < ops_.size(); ++i) {
     if (ops_[i].name != "model.1.conv" || ops_[i + 1].name != "model.2.cv1.conv") continue;
     const Op &a = ops_[i], &b = ops_[i + 1];
@@ -616,8 +447,7 @@ void Detector::fuse_front() {
 // Built for model.1 in one cout tile and at most two 16-channel K chunks: YOLOv8 n (16 -> 32) and s (32 -> 64).
 // GTX_FUSE_STEM=0 keeps the stem's own launch.
 void Detector::fuse_stem() {
-  const char* e = getenv("GTX_FUSE_STEM");
-  if (conv_dtype_ != DT_F32S || (e && e[0] == '0') || ops_.size() < 2) return;
+  if (fmt_ != DT_F32S || !env_flag("GTX_FUSE_STEM", true) || ops_.size() < 2) return;
   const Op& st = ops_[0];
   Op& cv = ops_[1];
   if (st.kind != Op::STEM || cv.kind != Op::CONV || cv.grp.count != 1 || !st.front_wpk) return;
@@ -696,14 +526,13 @@ void Detector::materialize_hidden_layers() {
   }
 }
 
-void Detector::set_batch(int nb) {
-  if (nb == cur_nb_) return;
-  for (Op& op : ops_) {
+void set_batch_ops(std::vector<Op>& ops, int nb, size_t es, bool pad_skip_on) {
+  for (Op& op : ops) {
     if (op.kind != Op::CONV) continue;
     for (int i = 0; i < op.grp.count; ++i) {
       op.grp.p[i].N = nb;
-      op.grp.p[i].ty_first = pad_skip_on_ ? op.ty_first[i] : 0;
-      op.grp.p[i].ty_count = pad_skip_on_ ? op.ty_count[i] : 0;
+      op.grp.p[i].ty_first = pad_skip_on ? op.ty_first[i] : 0;
+      op.grp.p[i].ty_count = pad_skip_on ? op.ty_count[i] : 0;
     }
     conv_group_finalize(op.grp, op.cfg);
     op.flops = 0;
@@ -713,30 +542,35 @@ void Detector::set_batch(int nb) {
       // the share of the output rows this launch computes (letterbox-padding rows are skipped: plan_pad_skip)
       const double part = std::min(1.0, (double)p.tiles_y * op.cfg.th / p.Ho);
       op.flops += part * conv_flops(p, op.cfg.ks);
-      op.bytes += part * ((double)p.N * p.H * p.W * (p.Cin - 0.75 * p.c_split) + (double)p.N * p.Ho * p.Wo * p.Cout) * es_ +
-                  (double)p.Cout * p.Cin * op.cfg.ks * op.cfg.ks * es_;
+      op.bytes += part * ((double)p.N * p.H * p.W * (p.Cin - 0.75 * p.c_split) + (double)p.N * p.Ho * p.Wo * p.Cout) * es +
+                  (double)p.Cout * p.Cin * op.cfg.ks * op.cfg.ks * es;
       if (p.post_w) {                     // the fused 1x1 layer: its FLOPs and weights; its output replaces the 3x3 layer's (same size)
         op.flops += part * 2.0 * p.N * p.Ho * p.Wo * (double)p.Cout * p.Cout;
-        op.bytes += (double)p.Cout * p.Cout * es_;
+        op.bytes += (double)p.Cout * p.Cout * es;
       }
       if (p.front_img) {                  // the fused stem: its FLOPs; RGB0 bytes are read instead of the stem's output
         op.flops += part * 2.0 * p.N * p.H * p.W * (double)p.Cin * 27;
-        op.bytes += part * ((double)p.N * p.front_h * p.front_w_px * 4 - (double)p.N * p.H * p.W * p.Cin * es_);
+        op.bytes += part * ((double)p.N * p.front_h * p.front_w_px * 4 - (double)p.N * p.H * p.W * p.Cin * es);
       }
     }
   }
-  for (Op& op : ops_) {
+  for (Op& op : ops) {
     if (op.kind == Op::STEM) {
       op.flops = 2.0 * nb * op.out.h * op.out.w * op.out.c * 27;
-      op.bytes = (double)nb * ((double)op.in.h * op.in.w * 4 + (double)op.out.h * op.out.w * op.out.c * es_);   // RGB0 bytes in
+      op.bytes = (double)nb * ((double)op.in.h * op.in.w * 4 + (double)op.out.h * op.out.w * op.out.c * es);   // RGB0 bytes in
     } else if (op.kind == Op::POOL) {
       op.flops = 0;
-      op.bytes = (double)nb * op.in.h * op.in.w * op.in.c * 4 * es_;
+      op.bytes = (double)nb * op.in.h * op.in.w * op.in.c * 4 * es;
     } else if (op.kind == Op::UPSAMPLE) {
       op.flops = 0;
-      op.bytes = (double)nb * op.in.h * op.in.w * op.in.c * 5 * es_;
+      op.bytes = (double)nb * op.in.h * op.in.w * op.in.c * 5 * es;
     }
   }
+}
+
+void Detector::set_batch(int nb) {
+  if (nb == cur_nb_) return;
+  set_batch_ops(ops_, nb, es_, pad_skip_on_);
   cur_nb_ = nb;
 }
 
@@ -843,7 +677,7 @@ void Detector::prime_pad_skip() {
   pad_skip_on_ = false;
   cur_nb_ = 0;
   set_batch(N);
-  launch_preprocess(dtype_, (const uint8_t*)blank.p, N, lb_, img_.ptr, nullptr, gray_h_, gray_w_, s);
+  launch_preprocess(dtype_, (const uint8_t*)blank.p, N, lb_, img_.ptr, nullptr, cfg_.frame_h / 2, cfg_.frame_w / 2, s);
   for (const Op& op : ops_) run_op(op, N, s);
   int sat = 0;
   if (sat_dev_) GTX_HIP(hipMemcpyAsync(&sat, sat_dev_, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -871,9 +705,7 @@ void Detector::finalize() {
   fuse_stem();
   release_hidden_layers();
   const int N = cfg_.max_batch;
-  gray_h_ = cfg_.frame_h / 2;
-  gray_w_ = cfg_.frame_w / 2;
-  gray_.alloc((size_t)kGrayRing * N * gray_h_ * gray_w_);
+  alloc_outputs();
   // NMS workspace. Candidate capacity = every anchor; sort/NMS capacity = ultralytics max_nms.
   nms_ = NmsBuffers{};
   nms_.cap = head_.n_anchors;
@@ -906,9 +738,7 @@ void Detector::finalize() {
     nms_.lvl_list = (int*)alloc(sizeof(int) * N * kMaxLevels * kSparseCap);
   }
   GTX_HIP(hipHostMalloc((void**)&h_count_, sizeof(int) * N));
-  GTX_HIP(hipHostMalloc((void**)&h_out_n_, sizeof(int) * N));
-  GTX_HIP(hipHostMalloc((void**)&h_out_rows_, sizeof(float) * 6 * N * cfg_.max_det));
-  if (conv_dtype_ != DT_F32S) tensors_.clear();  // host copies are no longer needed (the split path keeps them for fall_back_to_exact)
+  drop_tensors_unless_fallback();
   if (env_flag("GTX_PAD_SKIP", true)) {
     plan_pad_skip();
     prime_pad_skip();
@@ -924,89 +754,15 @@ void Detector::run_op(const Op& op, int nb, hipStream_t s) {
       conv_launch(op.grp, op.cfg, s);
       break;
     case Op::STEM:
-      launch_stem(dtype_ == DT_F32 ? conv_dtype_ : dtype_, op.in.ptr, nb, op.in.h, op.in.w, op.w27, op.bias, op.wpk, op.out.c, op.out.ptr, op.out.h,
+      launch_stem(dtype_ == DT_F32 ? fmt_ : dtype_, op.in.ptr, nb, op.in.h, op.in.w, op.w27, op.bias, op.wpk, op.out.c, op.out.ptr, op.out.h,
                   op.out.w, s, op.stem_scale);
       break;
-    case Op::POOL: launch_sppf_pool(conv_dtype_ == DT_F32S ? DT_F32S : dtype_, op.out.ptr, nb, op.in.h, op.in.w, op.in.c, s); break;
+    case Op::POOL: launch_sppf_pool(fmt_ == DT_F32S ? DT_F32S : dtype_, op.out.ptr, nb, op.in.h, op.in.w, op.in.c, s); break;
     case Op::UPSAMPLE:
       launch_upsample2x(dtype_, op.in.ptr, nb, op.in.h, op.in.w, op.in.c, op.in.cstride, op.in.coff, op.out.ptr,
                         op.out.cstride, op.out.coff, s);
       break;
   }
-}
-
-void Detector::run_forward(int nb, hipStream_t s, bool traced) {
-  if (!traced) {
-    // The forward graph is static for a given batch size (every launch has fixed arguments), so it can be
-    // captured once into a hipGraph and replayed as one submission (GTX_GRAPH=1). Measured on MI355X: no
-    // gain (1292 vs 1274 frames/s end to end, 823 vs 832 detector-only at batch 1) -- the ~5 us between
-    // dependent launches is GPU-side dispatch, not host submission -- so plain launches stay the default.
-    static const bool use_graph = [] { const char* e = getenv("GTX_GRAPH"); return e && e[0] == '1'; }();
-    if (use_graph) {
-      if (graph_nb_ != nb) {
-        if (graph_exec_) { (void)hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }
-        hipGraph_t g = nullptr;
-        GTX_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        for (const Op& op : ops_) run_op(op, nb, s);
-        GTX_HIP(hipStreamEndCapture(s, &g));
-        GTX_HIP(hipGraphInstantiate(&graph_exec_, g, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(g);
-        graph_nb_ = nb;
-      }
-      GTX_HIP(hipGraphLaunch(graph_exec_, s));
-      return;
-    }
-    for (const Op& op : ops_) run_op(op, nb, s);
-    return;
-  }
-  for (size_t i = 0; i < ops_.size(); ++i) {
-    GTX_HIP(hipEventRecord(trace_ev_[i], s));
-    run_op(ops_[i], nb, s);
-  }
-  GTX_HIP(hipEventRecord(trace_ev_[ops_.size()], s));
-}
-
-void Detector::set_trace(int every_n) {
-  if (exact_) return exact_->set_trace(every_n);
-  GTX_CHECK(finalized_ && every_n >= 0, "set_trace: detector not finalized or bad period");
-  GTX_CHECK(!in_flight_, "set_trace while a batch is in flight");
-  trace_every_ = every_n;
-  trace_count_ = 0;
-  if (every_n > 0 && trace_ev_.empty()) {
-    trace_ev_.resize(ops_.size() + 1);
-    for (auto& e : trace_ev_) GTX_HIP(hipEventCreate(&e));
-  }
-  trace_ms_.assign(ops_.size(), 0.0);
-  trace_n_.assign(ops_.size(), 0);
-  trace_flops_.assign(ops_.size(), 0.0);
-  trace_bytes_.assign(ops_.size(), 0.0);
-}
-
-void Detector::trace_report(std::vector<std::string>& names, std::vector<int>& launches, std::vector<float>& ms,
-                            std::vector<double>& flops, std::vector<double>& bytes) {
-  if (exact_) return exact_->trace_report(names, launches, ms, flops, bytes);
-  std::map<std::string, size_t> idx;
-  for (size_t i = 0; i < ops_.size() && i < trace_n_.size(); ++i) {
-    if (trace_n_[i] == 0) continue;
-    auto it = idx.find(ops_[i].family);
-    size_t k;
-    if (it == idx.end()) {
-      k = names.size();
-      idx[ops_[i].family] = k;
-      names.push_back(ops_[i].family);
-      launches.push_back(0); ms.push_back(0.f); flops.push_back(0.0); bytes.push_back(0.0);
-    } else {
-      k = it->second;
-    }
-    launches[k] += trace_n_[i];
-    ms[k] += (float)trace_ms_[i];
-    flops[k] += trace_flops_[i];
-    bytes[k] += trace_bytes_[i];
-  }
-  trace_ms_.assign(ops_.size(), 0.0);
-  trace_n_.assign(ops_.size(), 0);
-  trace_flops_.assign(ops_.size(), 0.0);
-  trace_bytes_.assign(ops_.size(), 0.0);
 }
 
 void Detector::run_post(int nb, hipStream_t s) {
@@ -1025,7 +781,7 @@ void Detector::run_post(int nb, hipStream_t s) {
   GTX_HIP(hipMemcpyAsync(h_out_rows_, nms_.out_rows, sizeof(float) * 6 * nb * cfg_.max_det, hipMemcpyDeviceToHost, s));
   if (sat_dev_) GTX_HIP(hipMemcpyAsync(h_sat_, sat_dev_, sizeof(int), hipMemcpyDeviceToHost, s));
   if (cfg_.obj_feats) {
-    launch_obj_feats(conv_dtype_, feat_levels_, nb, nms_, d_feats_, s);
+    launch_obj_feats(fmt_, feat_levels_, nb, nms_, d_feats_, s);
     GTX_HIP(hipMemcpyAsync(h_feats_, d_feats_, sizeof(float) * nb * cfg_.max_det * feat_levels_.dim, hipMemcpyDeviceToHost, s));
   }
 }
@@ -1043,130 +799,33 @@ void Detector::run_dense_box(hipStream_t s) {
   dense_head_valid_ = true;
 }
 
-void Detector::features(int b, float* out, int cap, int* n, int* dim) const {
-  if (exact_) return exact_->features(b, out, cap, n, dim);
-  GTX_CHECK(cfg_.obj_feats && h_feats_, "features: the detector was created without gtx_det_config.obj_feats");
-  GTX_CHECK(b >= 0 && b < cfg_.max_batch, "features: image %d of %d", b, cfg_.max_batch);
-  const int cnt = std::min(b < (int)c_feat_n_.size() ? c_feat_n_[b] : 0, cap);
-  if (n) *n = cnt;
-  if (dim) *dim = feat_levels_.dim;
-  if (out && cnt > 0) memcpy(out, c_feats_.data() + (size_t)b * cfg_.max_det * feat_levels_.dim, sizeof(float) * cnt * feat_levels_.dim);
-}
-
-// A split-f16x3 pass clamped an activation: from here on this object is a shell around an exact-fp32 detector built from
-// the same tensors on the same context. The split graph's device memory (activations, packed weights) is given back.
-void Detector::fall_back_to_exact() {
-  gtx_det_config c = cfg_;
-  c.fp32_split = 0;
-  std::unique_ptr<Detector> d(new Detector(ctx_, c));
-  for (const auto& kv : tensors_) d->set_tensor(kv.first, kv.second.data.data(), (int)kv.second.shape.size(), kv.second.shape.data());
-  d->finalize();
-  if (trace_every_ > 0) d->set_trace(trace_every_);
-  GTX_HIP(hipStreamSynchronize(ctx_->stream));
-  if (graph_exec_) { (void)hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }
-  ops_.clear();
-  unfused_.clear();
-  layer_views_.clear();
-  bufs_.clear();
-  tensors_.clear();
-  exact_ = std::move(d);
-}
-
-bool Detector::saturated(bool clear) {
-  const bool r = sat_seen_;
-  if (clear) {
-    sat_seen_ = false;
-    if (sat_dev_ && !exact_) {
-      GTX_HIP(hipSetDevice(ctx_->device));
-      GTX_HIP(hipMemsetAsync(sat_dev_, 0, sizeof(int), ctx_->stream));
-    }
+// What the pass left out for the common case: the general NMS kernels for > 4096 candidates in an image, the dense box layers and
+// every candidate's box for > kSparseCap; then the appearance vectors out of the pinned buffer before the next pass lands in it.
+void Detector::after_pass(int nb) {
+  bool over = false, big = false;
+  for (int b = 0; b < nb; ++b) {
+    over = over || (sparse_on_ && h_count_[b] > kSparseCap);                 // more candidates than the sparse buffer holds
+    big = big || !nms_small_covers(std::min(h_count_[b], nms_.cap), nms_.max_det);   // ... than the single-workgroup NMS takes
   }
-  return r;
-}
-
-// Asynchronous half: enqueue preprocess -> forward -> decode/NMS -> D2H of the result rows on the
-// context's stream and return. Results are picked up by collect(). The gray image of this batch
-// goes to the next slot of a 16-deep ring so that consumers on other streams (stabilizers) can
-// still read the images of the four batches before the newest collected one.
-void Detector::submit_dev(const void* frames, int nb, int h, int w) {
-  if (exact_) return exact_->submit_dev(frames, nb, h, w);
-  GTX_CHECK(finalized_, "detector not finalized");
-  GTX_CHECK(!in_flight_, "submit while a batch is in flight: call collect first");
-  GTX_CHECK(nb >= 1 && nb <= cfg_.max_batch, "batch %d outside [1,%d]", nb, cfg_.max_batch);
-  GTX_CHECK(h == cfg_.frame_h && w == cfg_.frame_w, "frame is %dx%d, detector was created for %dx%d", w, h, cfg_.frame_w, cfg_.frame_h);
-  GTX_HIP(hipSetDevice(ctx_->device));
-  hipStream_t s = ctx_->stream;
-  set_batch(nb);
-  cur_frames_ = frames;
-  gray_slot_ = (gray_slot_ + 1) % kGrayRing;
-  uint8_t* gray = gray_.as<uint8_t>() + (size_t)gray_slot_ * cfg_.max_batch * gray_h_ * gray_w_;
-  GTX_HIP(hipEventRecord(ev_[0], s));
-  launch_preprocess(dtype_, (const uint8_t*)frames, nb, lb_, img_.ptr, gray, gray_h_, gray_w_, s);
-  GTX_HIP(hipEventRecord(ev_[1], s));
-  flight_traced_ = trace_every_ > 0 && (trace_count_++ % trace_every_) == 0;
-  run_forward(nb, s, flight_traced_);
-  GTX_HIP(hipEventRecord(ev_[2], s));
-  run_post(nb, s);
-  GTX_HIP(hipEventRecord(ev_[3], s));
-  in_flight_ = true;
-  flight_nb_ = nb;
-}
-
-void Detector::collect(int* n_out, float* xyxy, float* conf, int* cls, float speed_ms[3]) {
-  if (exact_) return exact_->collect(n_out, xyxy, conf, cls, speed_ms);
-  GTX_CHECK(in_flight_, "collect without a submitted batch");
-  GTX_HIP(hipSetDevice(ctx_->device));
-  GTX_HIP(hipEventSynchronize(ev_[3]));
-  in_flight_ = false;
-  collected_gray_slot_ = gray_slot_;
-  if (h_sat_ && *h_sat_) {
-    sat_seen_ = true;
-    static const bool fallback = [] { const char* e = getenv("GTX_SAT_FALLBACK"); return !(e && e[0] == '0'); }();
-    if (fallback && conv_dtype_ == DT_F32S && !tensors_.empty()) {
-      // this batch again, at fp32's range: the frames are still where the caller put them (one batch in flight per detector)
-      flight_traced_ = false;
-      fall_back_to_exact();
-      return exact_->detect_dev(cur_frames_, flight_nb_, cfg_.frame_h, cfg_.frame_w, n_out, xyxy, conf, cls, speed_ms);
+  if (over || big) {
+    hipStream_t s = ctx_->stream;
+    NmsBuffers dense = nms_;
+    if (over) {                                      // the dense box layers, then every candidate's box again
+      run_dense_box(s);
+      launch_head_boxes(dtype_, head_, nb, dense, s);
+      ++sparse_overflows_;
     }
+    launch_nms(dense, nb, cfg_.iou, cfg_.agnostic_nms != 0, 30000, lb_, s, over ? 0 : 2);
+    GTX_HIP(hipMemcpyAsync(h_out_n_, nms_.out_n, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
+    GTX_HIP(hipMemcpyAsync(h_out_rows_, nms_.out_rows, sizeof(float) * 6 * nb * cfg_.max_det, hipMemcpyDeviceToHost, s));
+    if (cfg_.obj_feats) {
+      launch_obj_feats(fmt_, feat_levels_, nb, nms_, d_feats_, s);
+      GTX_HIP(hipMemcpyAsync(h_feats_, d_feats_, sizeof(float) * nb * cfg_.max_det * feat_levels_.dim, hipMemcpyDeviceToHost, s));
+    }
+    record_post_end(s);                              // the postprocess figure now includes the re-run
+    GTX_HIP(hipStreamSynchronize(s));
   }
-  if (flight_traced_) {
-    for (size_t i = 0; i < ops_.size(); ++i) {
-      float t = 0.f;
-      GTX_HIP(hipEventElapsedTime(&t, trace_ev_[i], trace_ev_[i + 1]));
-      trace_ms_[i] += t;
-      trace_n_[i] += 1;
-      trace_flops_[i] += ops_[i].flops;          // of THIS pass's batch size (set_batch ran in submit_dev)
-      trace_bytes_[i] += ops_[i].bytes;
-    }
-    flight_traced_ = false;
-  }
-  {                                                  // what the pass left out for the common case
-    bool over = false, big = false;
-    for (int b = 0; b < flight_nb_; ++b) {
-      over = over || (sparse_on_ && h_count_[b] > kSparseCap);                 // more candidates than the sparse buffer holds
-      big = big || !nms_small_covers(std::min(h_count_[b], nms_.cap), nms_.max_det);   // ... than the single-workgroup NMS takes
-    }
-    if (over || big) {
-      hipStream_t s = ctx_->stream;
-      NmsBuffers dense = nms_;
-      if (over) {                                    // the dense box layers, then every candidate's box again
-        run_dense_box(s);
-        launch_head_boxes(dtype_, head_, flight_nb_, dense, s);
-        ++sparse_overflows_;
-      }
-      launch_nms(dense, flight_nb_, cfg_.iou, cfg_.agnostic_nms != 0, 30000, lb_, s, over ? 0 : 2);
-      GTX_HIP(hipMemcpyAsync(h_out_n_, nms_.out_n, sizeof(int) * flight_nb_, hipMemcpyDeviceToHost, s));
-      GTX_HIP(hipMemcpyAsync(h_out_rows_, nms_.out_rows, sizeof(float) * 6 * flight_nb_ * cfg_.max_det, hipMemcpyDeviceToHost, s));
-      if (cfg_.obj_feats) {
-        launch_obj_feats(conv_dtype_, feat_levels_, flight_nb_, nms_, d_feats_, s);
-        GTX_HIP(hipMemcpyAsync(h_feats_, d_feats_, sizeof(float) * flight_nb_ * cfg_.max_det * feat_levels_.dim, hipMemcpyDeviceToHost, s));
-      }
-      GTX_HIP(hipEventRecord(ev_[3], s));            // the postprocess figure (ev_[2] -> ev_[3]) now includes the re-run
-      GTX_HIP(hipStreamSynchronize(s));
-    }
-  }
-  const int nb = flight_nb_;
-  if (cfg_.obj_feats) {                              // out of the pinned buffer before the next pass of this detector lands in it
+  if (cfg_.obj_feats) {
     c_feat_n_.assign(cfg_.max_batch, 0);
     c_feats_.resize((size_t)cfg_.max_batch * cfg_.max_det * feat_levels_.dim);
     for (int b = 0; b < nb; ++b) {
@@ -1175,56 +834,18 @@ void Detector::collect(int* n_out, float* xyxy, float* conf, int* cls, float spe
       memcpy(c_feats_.data() + o, h_feats_ + o, sizeof(float) * h_out_n_[b] * feat_levels_.dim);
     }
   }
-  for (int b = 0; b < nb; ++b) {
-    const int n = h_out_n_[b];
-    n_out[b] = n;
-    const float* rows = h_out_rows_ + (size_t)b * cfg_.max_det * 6;
-    for (int i = 0; i < n; ++i) {
-      float* bx = xyxy + ((size_t)b * cfg_.max_det + i) * 4;
-      bx[0] = rows[i * 6 + 0]; bx[1] = rows[i * 6 + 1]; bx[2] = rows[i * 6 + 2]; bx[3] = rows[i * 6 + 3];
-      conf[(size_t)b * cfg_.max_det + i] = rows[i * 6 + 4];
-      cls[(size_t)b * cfg_.max_det + i] = (int)rows[i * 6 + 5];
-    }
-  }
-  if (speed_ms) {
-    for (int i = 0; i < 3; ++i) GTX_HIP(hipEventElapsedTime(&speed_ms[i], ev_[i], ev_[i + 1]));
-  }
 }
 
-void Detector::detect_dev(const void* frames, int nb, int h, int w, int* n_out, float* xyxy, float* conf,
-                          int* cls, float speed_ms[3]) {
-  submit_dev(frames, nb, h, w);
-  collect(n_out, xyxy, conf, cls, speed_ms);
-}
-
-void Detector::detect_host(const uint8_t* frame, int h, int w, int* n_out, float* xyxy, float* conf, int* cls,
-                           float speed_ms[3]) {
-  GTX_CHECK(finalized_, "detector not finalized");
-  GTX_HIP(hipSetDevice(ctx_->device));
-  const size_t bytes = (size_t)h * w * 3;
-  if (frame_stage_.bytes < bytes) frame_stage_.alloc(bytes);
-  GTX_HIP(hipEventRecord(ev_up_[0], ctx_->stream));
-  GTX_HIP(hipMemcpyAsync(frame_stage_.p, frame, bytes, hipMemcpyHostToDevice, ctx_->stream));
-  GTX_HIP(hipEventRecord(ev_up_[1], ctx_->stream));
-  detect_dev(frame_stage_.p, 1, h, w, n_out, xyxy, conf, cls, speed_ms);
-  if (speed_ms) {
-    float up_ms = 0.f;
-    GTX_HIP(hipEventElapsedTime(&up_ms, ev_up_[0], ev_up_[1]));
-    speed_ms[0] += up_ms;  // the host->device copy is part of "preprocess"
-  }
-}
-
-const void* Detector::gray(int b, int* gh, int* gw) const {
-  if (exact_) return exact_->gray(b, gh, gw);
-  if (gh) *gh = gray_h_;
-  if (gw) *gw = gray_w_;
-  if (b < 0 || b >= cfg_.max_batch) return nullptr;
-  // the image of the most recently *collected* batch (a newer batch may already be in flight)
-  return gray_.as<uint8_t>() + ((size_t)collected_gray_slot_ * cfg_.max_batch + b) * gray_h_ * gray_w_;
+void Detector::features(int b, float* out, int cap, int* n, int* dim) const {
+  GTX_CHECK(cfg_.obj_feats && h_feats_, "features: the detector was created without gtx_det_config.obj_feats");
+  GTX_CHECK(b >= 0 && b < cfg_.max_batch, "features: image %d of %d", b, cfg_.max_batch);
+  const int cnt = std::min(b < (int)c_feat_n_.size() ? c_feat_n_[b] : 0, cap);
+  if (n) *n = cnt;
+  if (dim) *dim = feat_levels_.dim;
+  if (out && cnt > 0) memcpy(out, c_feats_.data() + (size_t)b * cfg_.max_det * feat_levels_.dim, sizeof(float) * cnt * feat_levels_.dim);
 }
 
 void Detector::raw_output(int b, float* out, int* n_anchors, bool logits) {
-  if (exact_) return exact_->raw_output(b, out, n_anchors, logits);
   GTX_CHECK(finalized_ && cur_nb_ > 0 && b >= 0 && b < cur_nb_, "raw_output: no forward pass for slot %d", b);
   const size_t per = (size_t)head_.n_anchors * (4 + head_.nc);
   if (raw_.bytes < per * cur_nb_ * sizeof(float)) raw_.alloc(per * cur_nb_ * sizeof(float));
@@ -1237,7 +858,6 @@ void Detector::raw_output(int b, float* out, int* n_anchors, bool logits) {
 }
 
 void Detector::layer_output(int b, const std::string& layer, float* out, int* h, int* w, int* c) {
-  if (exact_) return exact_->layer_output(b, layer, out, h, w, c);
   // model.0 / model.1 of a fused front launch are RECOMPUTED below by their stand-alone launches (same products, another
   // summation order): what comes back is not what the network consumed. Not while a pass is in flight: the launches
   // would queue behind it and overwrite the buffers it shares with them.
@@ -1280,66 +900,7 @@ void Detector::layer_output(int b, const std::string& layer, float* out, int* h,
   if (!out) return;
   GTX_CHECK(b >= 0 && b < cfg_.max_batch, "bad batch slot");
   GTX_CHECK(reinterpret_cast<uintptr_t>(v.ptr) > 4096, "layer_output('%s'): the layer's buffer was not re-created", layer.c_str());
-  const size_t px = (size_t)v.h * v.w;
-  std::vector<uint8_t> host(px * v.cstride * es_);
-  GTX_HIP(hipMemcpy(host.data(), (const uint8_t*)v.ptr + (size_t)b * px * v.cstride * es_, host.size(), hipMemcpyDeviceToHost));
-  for (size_t p = 0; p < px; ++p)
-    for (int k = 0; k < v.c; ++k) {
-      const size_t src = p * v.cstride + v.coff + k;
-      float f;
-      if (conv_dtype_ == DT_F32S && !v.plain) {
-        f = pair_element(host.data(), src);
-      } else if (dtype_ == DT_F16) {
-        _Float16 hv;
-        memcpy(&hv, host.data() + src * 2, 2);
-        f = (float)hv;
-      } else {
-        memcpy(&f, host.data() + src * 4, 4);
-      }
-      out[p * v.c + k] = f;
-    }
-}
-
-void Detector::profile(int nb, int iters, std::vector<std::string>& names, std::vector<int>& launches,
-                       std::vector<float>& ms, std::vector<double>& flops, std::vector<double>& bytes) {
-  if (exact_) return exact_->profile(nb, iters, names, launches, ms, flops, bytes);
-  GTX_CHECK(finalized_, "detector not finalized");
-  GTX_CHECK(nb >= 1 && nb <= cfg_.max_batch && iters >= 1, "bad profile arguments");
-  hipStream_t s = ctx_->stream;
-  set_batch(nb);
-  std::vector<hipEvent_t> ev(ops_.size() + 1);
-  for (auto& e : ev) GTX_HIP(hipEventCreate(&e));
-  std::map<std::string, size_t> idx;
-  const bool per_op = std::getenv("GTX_PROFILE_PER_OP") != nullptr;   // one line per launch (its module path) instead of per kernel family
-  auto slot = [&](const std::string& fam) {
-    auto it = idx.find(fam);
-    if (it != idx.end()) return it->second;
-    idx[fam] = names.size();
-    names.push_back(fam);
-    launches.push_back(0);
-    ms.push_back(0.f);
-    flops.push_back(0.0);
-    bytes.push_back(0.0);
-    return names.size() - 1;
-  };
-  for (int it = 0; it < iters; ++it) {
-    for (size_t i = 0; i < ops_.size(); ++i) {
-      GTX_HIP(hipEventRecord(ev[i], s));
-      run_op(ops_[i], nb, s);
-    }
-    GTX_HIP(hipEventRecord(ev[ops_.size()], s));
-    GTX_HIP(hipStreamSynchronize(s));
-    for (size_t i = 0; i < ops_.size(); ++i) {
-      float t = 0.f;
-      GTX_HIP(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-      const size_t k = slot(per_op ? (i < 10 ? "0" : "") + std::to_string(i) + " " + ops_[i].name : ops_[i].family);
-      launches[k] += 1;
-      ms[k] += t;
-      flops[k] += ops_[i].flops;
-      bytes[k] += ops_[i].bytes;
-    }
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
+  read_view(v, b, out);
 }
 
 }  // namespace gtx

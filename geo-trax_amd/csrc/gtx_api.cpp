@@ -609,44 +609,44 @@ int gtx_detector_detect(gtx_detector* det, const uint8_t* frame_bgr, int h, int 
                         float* conf, int* cls, float speed_ms[3]) {
   return guarded([&] {
     need(det, "det"); need(frame_bgr, "frame"); need(n_out, "n_out"); need(xyxy, "xyxy"); need(conf, "conf"); need(cls, "cls");
-    det->impl->detect_host(frame_bgr, h, w, n_out, xyxy, conf, cls, speed_ms);
+    det->impl->live()->detect_host(frame_bgr, h, w, n_out, xyxy, conf, cls, speed_ms);
   });
 }
 int gtx_detector_detect_dev(gtx_detector* det, const void* frame_dptr, int h, int w, int* n_out, float* xyxy,
                             float* conf, int* cls, float speed_ms[3]) {
   return guarded([&] {
     need(det, "det"); need(frame_dptr, "frame"); need(n_out, "n_out"); need(xyxy, "xyxy"); need(conf, "conf"); need(cls, "cls");
-    det->impl->detect_dev(frame_dptr, 1, h, w, n_out, xyxy, conf, cls, speed_ms);
+    det->impl->live()->detect_dev(frame_dptr, 1, h, w, n_out, xyxy, conf, cls, speed_ms);
   });
 }
 int gtx_detector_detect_batch_dev(gtx_detector* det, const void* frames_dptr, int nb, int h, int w, int* n_out,
                                   float* xyxy, float* conf, int* cls, float speed_ms[3]) {
   return guarded([&] {
     need(det, "det"); need(frames_dptr, "frames"); need(n_out, "n_out"); need(xyxy, "xyxy"); need(conf, "conf"); need(cls, "cls");
-    det->impl->detect_dev(frames_dptr, nb, h, w, n_out, xyxy, conf, cls, speed_ms);
+    det->impl->live()->detect_dev(frames_dptr, nb, h, w, n_out, xyxy, conf, cls, speed_ms);
   });
 }
 int gtx_detector_submit_dev(gtx_detector* det, const void* frames_dptr, int nb, int h, int w) {
-  return guarded([&] { need(det, "det"); need(frames_dptr, "frames"); det->impl->submit_dev(frames_dptr, nb, h, w); });
+  return guarded([&] { need(det, "det"); need(frames_dptr, "frames"); det->impl->live()->submit_dev(frames_dptr, nb, h, w); });
 }
 int gtx_detector_collect(gtx_detector* det, int* n_out, float* xyxy, float* conf, int* cls, float speed_ms[3]) {
   return guarded([&] {
     need(det, "det"); need(n_out, "n_out"); need(xyxy, "xyxy"); need(conf, "conf"); need(cls, "cls");
-    det->impl->collect(n_out, xyxy, conf, cls, speed_ms);
+    det->impl->live()->collect(n_out, xyxy, conf, cls, speed_ms);
   });
 }
 const void* gtx_detector_gray(gtx_detector* det, int b, int* gray_h, int* gray_w) {
   if (!det) return nullptr;
-  return det->impl->gray(b, gray_h, gray_w);
+  return det->impl->live()->gray(b, gray_h, gray_w);
 }
 int gtx_detector_raw_output(gtx_detector* det, int b, float* out, int* n_anchors) {
-  return guarded([&] { need(det, "det"); need(out, "out"); det->impl->raw_output(b, out, n_anchors); });
+  return guarded([&] { need(det, "det"); need(out, "out"); det->impl->live()->raw_output(b, out, n_anchors); });
 }
 int gtx_detector_raw_logits(gtx_detector* det, int b, float* out, int* n_anchors) {
-  return guarded([&] { need(det, "det"); need(out, "out"); det->impl->raw_output(b, out, n_anchors, true); });
+  return guarded([&] { need(det, "det"); need(out, "out"); det->impl->live()->raw_output(b, out, n_anchors, true); });
 }
 int gtx_detector_layer_output(gtx_detector* det, int b, const char* layer, float* out, int* h, int* w, int* c) {
-  return guarded([&] { need(det, "det"); need(layer, "layer"); det->impl->layer_output(b, layer, out, h, w, c); });
+  return guarded([&] { need(det, "det"); need(layer, "layer"); det->impl->live()->layer_output(b, layer, out, h, w, c); });
 }
 int gtx_detector_saturated(gtx_detector* det, int clear, int* flag) {
   return guarded([&] { need(det, "det"); need(flag, "flag"); *flag = det->impl->saturated(clear != 0) ? 1 : 0; });
@@ -661,10 +661,10 @@ int gtx_detector_sparse_box(gtx_detector* det, int* on, int* overflows) {
   return guarded([&] { need(det, "det"); det->impl->sparse_box(on, overflows); });
 }
 int gtx_detector_features(gtx_detector* det, int b, float* out, int cap, int* n, int* dim) {
-  return guarded([&] { need(det, "det"); det->impl->features(b, out, cap, n, dim); });
+  return guarded([&] { need(det, "det"); det->impl->live()->features(b, out, cap, n, dim); });
 }
 int gtx_detector_trace(gtx_detector* det, int every_n) {
-  return guarded([&] { need(det, "det"); det->impl->set_trace(every_n); });
+  return guarded([&] { need(det, "det"); det->impl->live()->set_trace(every_n); });
 }
 int gtx_detector_profile(gtx_detector* det, int nb, int iters, int cap, char* names, int* launches, float* total_ms,
                          double* flops, double* bytes, int* n_families) {
@@ -675,8 +675,8 @@ int gtx_detector_profile(gtx_detector* det, int nb, int iters, int cap, char* na
     std::vector<int> la;
     std::vector<float> ms;
     std::vector<double> fl, by;
-    if (iters <= 0) det->impl->trace_report(nm, la, ms, fl, by);   // iters = 0: the live trace totals
-    else det->impl->profile(nb, iters, nm, la, ms, fl, by);
+    if (iters <= 0) det->impl->live()->trace_report(nm, la, ms, fl, by);   // iters = 0: the live trace totals
+    else det->impl->live()->profile(nb, iters, nm, la, ms, fl, by);
     const int n = std::min<int>(cap, (int)nm.size());
     for (int i = 0; i < n; ++i) {
       std::strncpy(names + (size_t)i * 96, nm[i].c_str(), 95);

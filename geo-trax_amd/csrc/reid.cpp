@@ -26,11 +26,6 @@ static_assert(kNetChannelsBgr, "reid_crop_kernel writes slot c = frame byte c");
 namespace {
 constexpr int kPrecBits = 22;   // PIL PRECISION_BITS
 
-bool env_on(const char* name, bool dflt) {
-  const char* e = getenv(name);
-  return (e && *e) ? e[0] != '0' : dflt;
-}
-
 // PIL Resample.c precompute_coeffs (bilinear filter, support 1) + normalize_coeffs_8bpc for output indices [first, first + S) of
 // out_size: bounds [S][2] (xmin, count) and int coefficients [S][ksize] appended to pool. Returns ksize. Double arithmetic,
 // one rounding per operation.
@@ -78,15 +73,6 @@ int center_offset(int size, int S) {
   return (d % 2 == 0) ? k : ((k % 2 == 0) ? k : k + 1);
 }
 
-std::vector<float> to_ohwi(const HostTensor& t) {
-  const int O = (int)t.shape[0], I = (int)t.shape[1], KH = (int)t.shape[2], KW = (int)t.shape[3];
-  std::vector<float> r((size_t)O * I * KH * KW);
-  for (int o = 0; o < O; ++o)
-    for (int i = 0; i < I; ++i)
-      for (int y = 0; y < KH; ++y)
-        for (int x = 0; x < KW; ++x) r[(((size_t)o * KH + y) * KW + x) * I + i] = t.data[(((size_t)o * I + i) * KH + y) * KW + x];
-  return r;
-}
 }  // namespace
 
 void reid_crop_box(const float b[4], int h, int w, int out[4]) {
@@ -106,10 +92,10 @@ void reid_crop_box(const float b[4], int h, int w, int out[4]) {
   out[3] = (int)std::min<long long>(std::max<long long>(q[3], 0), h);
 }
 
-Embedder::Embedder(gtx_ctx* ctx, int imgsz, int max_crops, bool fp32_split) : ctx_(ctx), S_(imgsz), max_crops_(max_crops) {
+Embedder::Embedder(gtx_ctx* ctx, int imgsz, int max_crops, bool fp32_split)
+    : NetRuntime(ctx, fp32_split ? DT_F32S : DT_F32, 4, max_crops), S_(imgsz) {
   GTX_CHECK(imgsz >= 32 && imgsz <= 256 && imgsz % 32 == 0, "reid imgsz must be a multiple of 32 in [32, 256] (got %d)", imgsz);
   GTX_CHECK(max_crops >= 1, "max_crops must be positive");
-  conv_dtype_ = fp32_split ? DT_F32S : DT_F32;
   GTX_HIP(hipSetDevice(ctx->device));
   GTX_HIP(hipEventCreateWithFlags(&done_, wait_event_flags(false)));
 }
@@ -117,79 +103,27 @@ Embedder::Embedder(gtx_ctx* ctx, int imgsz, int max_crops, bool fp32_split) : ct
 Embedder::~Embedder() {
   if (pin_) (void)hipHostFree(pin_);
   if (h_emb_) (void)hipHostFree(h_emb_);
-  if (h_sat_) (void)hipHostFree(h_sat_);
   if (done_) (void)hipEventDestroy(done_);
 }
 
-void Embedder::set_tensor(const std::string& name, const float* data, int ndim, const int64_t* shape) {
-  GTX_CHECK(!finalized_, "set_tensor after finalize");
-  HostTensor t;
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
-  t.data.assign(data, data + n);
-  tensors_[name] = std::move(t);
+std::unique_ptr<NetRuntime> Embedder::make_exact() const {
+  return std::unique_ptr<NetRuntime>(new Embedder(ctx_, S_, max_batch_, false));
 }
 
-const HostTensor& Embedder::tensor(const std::string& name) const {
-  auto it = tensors_.find(name);
-  if (it == tensors_.end()) fail(-1, "missing tensor '%s'", name.c_str());
-  return it->second;
-}
-
-void* Embedder::alloc(size_t bytes) {
-  bufs_.emplace_back(bytes);
-  GTX_HIP(hipMemset(bufs_.back().p, 0, bufs_.back().bytes));
-  return bufs_.back().p;
-}
-
-View Embedder::new_view(int h, int w, int c) {
-  View v;
-  v.n = max_crops_; v.h = h; v.w = w; v.cstride = c; v.coff = 0; v.c = c;
-  v.ptr = alloc((size_t)v.n * h * w * c * 4);
-  return v;
+// GTX_WINO: the direct split kernel here (same kc / bn)
+void Embedder::conv_config_rule(const std::string& name, ConvConfig& cfg) const {
+  (void)name;
+  if (cfg.variant == 3 || cfg.variant == 4) { cfg.variant = 2; cfg.th = 8; }
 }
 
 View Embedder::conv(const std::string& name, const View& x, int stride, const View* out_slice, const View* residual) {
   const HostTensor& w = tensor(name + ".weight");
   GTX_CHECK(w.shape.size() == 4 && w.shape[2] == w.shape[3], "%s: expected OIHW square kernel", name.c_str());
-  const int cout = (int)w.shape[0], cin = (int)w.shape[1], ks = (int)w.shape[2];
-  GTX_CHECK(cin == x.c, "%s: weight expects %d input channels, input view has %d", name.c_str(), cin, x.c);
-  const int pad = ks / 2;
-  const int ho = (x.h + 2 * pad - ks) / stride + 1, wo = (x.w + 2 * pad - ks) / stride + 1;
-  View out = out_slice ? *out_slice : new_view(ho, wo, cout);
-  GTX_CHECK(out.h == ho && out.w == wo && out.c == cout, "%s: output view mismatch", name.c_str());
-  Op op;
-  op.kind = Op::CONV;
-  op.name = name;
-  op.cfg = conv_pick_config(conv_dtype_, ks, stride, cin, cout, 0, 0, (long)x.n * ho * wo);
-  if (op.cfg.variant == 3 || op.cfg.variant == 4) { op.cfg.variant = 2; op.cfg.th = 8; }   // GTX_WINO: the direct split kernel here (same kc / bn)
-  const std::vector<float> ohwi = to_ohwi(w);
-  float acc_scale = 1.f;
-  const std::vector<uint8_t> packed = pack_conv_weights(ohwi.data(), cout, cin, op.cfg, &acc_scale);
-  void* dw = alloc(packed.size());
-  GTX_HIP(hipMemcpy(dw, packed.data(), packed.size(), hipMemcpyHostToDevice));
-  float* db = (float*)alloc(((cout + 63) / 64 * 64) * sizeof(float));   // zero-filled up to a whole cout tile
-  if (has(name + ".bias")) {
-    const HostTensor& b = tensor(name + ".bias");
-    GTX_CHECK((int)b.data.size() == cout, "%s: bias size", name.c_str());
-    GTX_HIP(hipMemcpy(db, b.data.data(), cout * sizeof(float), hipMemcpyHostToDevice));
-  }
-  ConvProblem& p = op.grp.p[0];
-  p.in = x.ptr; p.out = out.ptr; p.wpack = dw; p.bias = db;
-  p.res = residual ? residual->ptr : nullptr;
-  p.N = x.n; p.H = x.h; p.W = x.w; p.Ho = ho; p.Wo = wo; p.Cin = cin; p.Cout = cout;
-  p.in_cstride = x.cstride; p.in_coff = x.coff;
-  p.out_cstride = out.cstride; p.out_coff = out.coff;
-  p.res_cstride = residual ? residual->cstride : 0;
-  p.res_coff = residual ? residual->coff : 0;
-  p.act = 1;
-  p.acc_scale = acc_scale;
-  p.sat_flag = conv_dtype_ == DT_F32S ? sat_dev_ : nullptr;
-  op.grp.count = 1;
-  op.family = conv_kernel_name(op.cfg);
-  ops_.push_back(op);
-  layer_views_[name] = out;
-  return out;
+  const int cout = (int)w.shape[0], ks = (int)w.shape[2];
+  ConvArgs a;
+  a.stride = stride; a.out_slice = out_slice; a.residual = residual;
+  a.out_pixels = (long)x.n * ((x.h + 2 * (ks / 2) - ks) / stride + 1) * ((x.w + 2 * (ks / 2) - ks) / stride + 1);
+  return emit_conv(ops_, name, w.data.data(), cout, (int)w.shape[1], ks, bias_of(name, cout), x, a);
 }
 
 // C2f(shortcut=True): cv1 -> split -> n bottlenecks (3x3, 3x3, + residual) -> concat -> cv2 (the detector's c2f, without its fusions)
@@ -217,11 +151,7 @@ View Embedder::c2f(const std::string& pfx, const View& x) {
 void Embedder::build_graph() {
   img_ = new_view(S_, S_, 1);                                  // [N][S][S] uchar4: 4 bytes per pixel
   img_.plain = true;
-  if (conv_dtype_ == DT_F32S) {
-    sat_dev_ = (int*)alloc(sizeof(int));
-    GTX_HIP(hipHostMalloc((void**)&h_sat_, sizeof(int)));
-    *h_sat_ = 0;
-  }
+  alloc_sat_flag();
   const HostTensor& w0 = tensor("model.0.conv.weight");
   GTX_CHECK(w0.shape.size() == 4 && w0.shape[1] == 3 && w0.shape[2] == 3 && w0.shape[3] == 3, "model.0 must be a 3x3 conv on 3 channels");
   const int c0 = (int)w0.shape[0];
@@ -241,18 +171,17 @@ void Embedder::build_graph() {
     Op op;
     op.kind = Op::STEM;
     op.name = "model.0.conv";
-    op.family = conv_dtype_ == DT_F32S ? "stem_split_kernel" : "stem_kernel";
+    op.family = fmt_ == DT_F32S ? "stem_split_kernel" : "stem_kernel";
     op.in = img_;
     op.out = a0;
     op.w27 = dw;
     op.bias = db;
-    if (conv_dtype_ == DT_F32S) {
+    if (fmt_ == DT_F32S) {
       const std::vector<uint16_t> pk = pack_stem_weights_split(w27.data(), c0, &op.stem_scale);
       void* dp = alloc(pk.size() * 2);
       GTX_HIP(hipMemcpy(dp, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
       op.wpk = dp;
     }
-    op.flops = 2.0 * 27 * c0 * (S_ / 2) * (S_ / 2);
     ops_.push_back(op);
     layer_views_["model.0.conv"] = a0;
   }
@@ -271,7 +200,7 @@ void Embedder::finalize() {
   GTX_CHECK(!finalized_, "finalize called twice");
   GTX_HIP(hipSetDevice(ctx_->device));
   build_graph();
-  if (conv_dtype_ != DT_F32S || !env_on("GTX_SAT_FALLBACK", true)) tensors_.clear();   // the split path keeps them for fall_back_to_exact
+  drop_tensors_unless_fallback();
   set_batch(1);
   GTX_HIP(hipStreamSynchronize(ctx_->stream));
   finalized_ = true;
@@ -279,44 +208,16 @@ void Embedder::finalize() {
 
 void Embedder::set_batch(int nb) {
   if (nb == cur_nb_) return;
-  for (Op& op : ops_) {
-    if (op.kind != Op::CONV) continue;
-    for (int i = 0; i < op.grp.count; ++i) op.grp.p[i].N = nb;
-    conv_group_finalize(op.grp, op.cfg);
-    op.flops = nb ? conv_flops(op.grp.p[0], op.cfg.ks) / nb : 0.0;
-  }
+  set_batch_ops(ops_, nb, 4, false);
   cur_nb_ = nb;
 }
 
-void Embedder::run_op(const Op& op, int nb, hipStream_t s) {
+void Embedder::launch_op(size_t i, int nb, hipStream_t s) {
+  const Op& op = ops_[i];
   if (op.kind == Op::STEM)
-    launch_stem(conv_dtype_, op.in.ptr, nb, op.in.h, op.in.w, op.w27, op.bias, op.wpk, op.out.c, op.out.ptr, op.out.h, op.out.w, s, op.stem_scale);
+    launch_stem(fmt_, op.in.ptr, nb, op.in.h, op.in.w, op.w27, op.bias, op.wpk, op.out.c, op.out.ptr, op.out.h, op.out.w, s, op.stem_scale);
   else
     conv_launch(op.grp, op.cfg, s);
-}
-
-void Embedder::fall_back_to_exact() {
-  std::unique_ptr<Embedder> e(new Embedder(ctx_, S_, max_crops_, false));
-  for (const auto& kv : tensors_) e->set_tensor(kv.first, kv.second.data.data(), (int)kv.second.shape.size(), kv.second.shape.data());
-  e->finalize();
-  GTX_HIP(hipStreamSynchronize(ctx_->stream));
-  ops_.clear();
-  layer_views_.clear();
-  bufs_.clear();
-  tensors_.clear();
-  exact_ = std::move(e);
-}
-
-bool Embedder::saturated(bool clear) {
-  const bool r = sat_seen_;
-  if (clear) {
-    sat_seen_ = false;
-    if (sat_dev_ && !exact_) {
-      GTX_HIP(hipSetDevice(ctx_->device));
-      GTX_HIP(hipMemsetAsync(sat_dev_, 0, sizeof(int), ctx_->stream));
-    }
-  }
-  return r;
 }
 
 // Crop table + coefficients of the pass on the host, one copy to the device, then chunk by chunk of max_crops: crop kernel ->
@@ -368,12 +269,12 @@ void Embedder::enqueue(int n) {
   GTX_HIP(hipMemcpyAsync(d_params_.p, pin_, bytes, hipMemcpyHostToDevice, s));
   const ReidCrop* d_crops = d_params_.as<ReidCrop>();
   const int* d_pool = (const int*)((const uint8_t*)d_params_.p + pool_off);
-  for (int c0 = 0; c0 < n; c0 += max_crops_) {
-    const int k = std::min(max_crops_, n - c0);
+  for (int c0 = 0; c0 < n; c0 += max_batch_) {
+    const int k = std::min(max_batch_, n - c0);
     set_batch(k);
     launch_reid_crop((const uint8_t*)cur_frames_, H, W, d_crops + c0, d_pool, k, S_, img_.ptr, s);
-    for (const Op& op : ops_) run_op(op, k, s);
-    launch_reid_pool(last_.ptr, conv_dtype_ == DT_F32S ? 1 : 0, k, last_.h * last_.w, last_.cstride, last_.coff, dim_,
+    run_ops(k, s, nullptr);
+    launch_reid_pool(last_.ptr, fmt_ == DT_F32S ? 1 : 0, k, last_.h * last_.w, last_.cstride, last_.coff, dim_,
                      d_emb_.as<float>() + (size_t)c0 * dim_, s);
     last_chunk_ = c0;
     last_chunk_n_ = k;
@@ -383,7 +284,6 @@ void Embedder::enqueue(int n) {
 }
 
 void Embedder::submit_dev(const void* frames, int nb, int h, int w, const int* counts, const float* xyxy) {
-  if (exact_) return exact_->submit_dev(frames, nb, h, w, counts, xyxy);
   GTX_CHECK(finalized_, "embedder not finalized");
   GTX_CHECK(!in_flight_, "submit while a pass is in flight: call collect first");
   GTX_CHECK(nb >= 1 && h > 0 && w > 0, "bad frame batch %d x %dx%d", nb, w, h);
@@ -404,7 +304,6 @@ void Embedder::submit_dev(const void* frames, int nb, int h, int w, const int* c
 }
 
 int Embedder::collect(float* out, int cap) {
-  if (exact_) return exact_->collect(out, cap);
   GTX_CHECK(in_flight_, "collect without a submitted pass");
   GTX_HIP(hipSetDevice(ctx_->device));
   GTX_HIP(hipEventSynchronize(done_));
@@ -412,13 +311,13 @@ int Embedder::collect(float* out, int cap) {
   const int n = n_flight_;
   if (n > 0 && h_sat_ && *h_sat_) {
     sat_seen_ = true;
-    if (conv_dtype_ == DT_F32S && !tensors_.empty()) {          // this pass again at fp32's range, and every later one (Detector::collect's rule)
+    if (can_fall_back()) {                                      // this pass again at fp32's range, and every later one
       const void* f = cur_frames_;
       const std::vector<int> counts = cur_counts_;
       const std::vector<float> xyxy = cur_xyxy_;
       fall_back_to_exact();
-      exact_->submit_dev(f, (int)counts.size(), cur_h_, cur_w_, counts.data(), xyxy.data());
-      return exact_->collect(out, cap);
+      live()->submit_dev(f, (int)counts.size(), cur_h_, cur_w_, counts.data(), xyxy.data());
+      return live()->collect(out, cap);
     }
   }
   GTX_CHECK(cap >= n, "output holds %d vectors, the pass has %d", cap, n);
@@ -427,14 +326,12 @@ int Embedder::collect(float* out, int cap) {
 }
 
 void Embedder::crops(int i, uint8_t* out) {
-  if (exact_) return exact_->crops(i, out);
   GTX_CHECK(!in_flight_, "crops while a pass is in flight: call collect first");
   GTX_CHECK(i >= last_chunk_ && i < last_chunk_ + last_chunk_n_, "crop %d is not in the last chunk of the last pass", i);
   GTX_HIP(hipMemcpy(out, (const uint8_t*)img_.ptr + (size_t)(i - last_chunk_) * S_ * S_ * 4, (size_t)S_ * S_ * 4, hipMemcpyDeviceToHost));
 }
 
 void Embedder::layer_output(int i, const std::string& layer, float* out, int* h, int* w, int* c) {
-  if (exact_) return exact_->layer_output(i, layer, out, h, w, c);
   GTX_CHECK(!(out && in_flight_), "layer_output while a pass is in flight: call collect first");
   auto it = layer_views_.find(layer);
   if (it == layer_views_.end()) fail(-1, "unknown layer '%s'", layer.c_str());
@@ -444,44 +341,18 @@ void Embedder::layer_output(int i, const std::string& layer, float* out, int* h,
   if (c) *c = v.c;
   if (!out) return;
   GTX_CHECK(i >= last_chunk_ && i < last_chunk_ + last_chunk_n_, "crop %d is not in the last chunk of the last pass", i);
-  const size_t px = (size_t)v.h * v.w;
-  std::vector<uint8_t> host(px * v.cstride * 4);
-  GTX_HIP(hipMemcpy(host.data(), (const uint8_t*)v.ptr + (size_t)(i - last_chunk_) * px * v.cstride * 4, host.size(), hipMemcpyDeviceToHost));
-  for (size_t p = 0; p < px; ++p)
-    for (int k = 0; k < v.c; ++k) {
-      const size_t src = p * v.cstride + v.coff + k;
-      float f;
-      if (conv_dtype_ == DT_F32S) f = pair_element(host.data(), src);
-      else memcpy(&f, host.data() + src * 4, 4);
-      out[p * v.c + k] = f;
-    }
+  read_view(v, i - last_chunk_, out);
 }
 
 void Embedder::profile(int n, int iters, std::vector<std::string>& names, std::vector<float>& ms, std::vector<double>& flops) {
-  if (exact_) return exact_->profile(n, iters, names, ms, flops);
   GTX_CHECK(finalized_ && !in_flight_, "profile: embedder not finalized or a pass in flight");
-  GTX_CHECK(n >= 1 && n <= max_crops_ && iters >= 1, "bad profile arguments");
-  hipStream_t s = ctx_->stream;
-  set_batch(n);
-  std::vector<hipEvent_t> ev(ops_.size() + 1);
-  for (auto& e : ev) GTX_HIP(hipEventCreate(&e));
+  GTX_CHECK(n >= 1 && n <= max_batch_ && iters >= 1, "bad profile arguments");
   names.clear(); ms.assign(ops_.size(), 0.f); flops.assign(ops_.size(), 0.0);
   for (const Op& op : ops_) names.push_back(op.name + " " + op.family);
-  for (int it = 0; it < iters; ++it) {
-    for (size_t i = 0; i < ops_.size(); ++i) {
-      GTX_HIP(hipEventRecord(ev[i], s));
-      run_op(ops_[i], n, s);
-    }
-    GTX_HIP(hipEventRecord(ev[ops_.size()], s));
-    GTX_HIP(hipStreamSynchronize(s));
-    for (size_t i = 0; i < ops_.size(); ++i) {
-      float t = 0.f;
-      GTX_HIP(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-      ms[i] += t / iters;
-      flops[i] = ops_[i].flops * n;
-    }
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
+  time_ops(n, iters, [&](size_t i, float t) {
+    ms[i] += t / iters;
+    flops[i] = ops_[i].flops;
+  });
 }
 
 }  // namespace gtx
@@ -514,7 +385,7 @@ int gtx_embedder_finalize(gtx_embedder* e) {
   return guarded([&] { need(e, "embedder"); e->impl->finalize(); });
 }
 int gtx_embedder_dim(gtx_embedder* e, int* dim) {
-  return guarded([&] { need(e, "embedder"); need(dim, "dim"); *dim = e->impl->dim(); });
+  return guarded([&] { need(e, "embedder"); need(dim, "dim"); *dim = e->impl->live()->dim(); });
 }
 int gtx_embedder_submit_dev(gtx_embedder* e, const void* frames_dptr, int nb, int h, int w, const int* counts, const float* xyxy) {
   return guarded([&] {
@@ -522,11 +393,11 @@ int gtx_embedder_submit_dev(gtx_embedder* e, const void* frames_dptr, int nb, in
     int n = 0;
     for (int b = 0; b < nb; ++b) n += counts[b];
     if (n > 0) need(xyxy, "xyxy");
-    e->impl->submit_dev(frames_dptr, nb, h, w, counts, xyxy);
+    e->impl->live()->submit_dev(frames_dptr, nb, h, w, counts, xyxy);
   });
 }
 int gtx_embedder_collect(gtx_embedder* e, float* out, int cap, int* n) {
-  return guarded([&] { need(e, "embedder"); need(n, "n"); *n = e->impl->collect(out, cap); });
+  return guarded([&] { need(e, "embedder"); need(n, "n"); *n = e->impl->live()->collect(out, cap); });
 }
 int gtx_embedder_embed_dev(gtx_embedder* e, const void* frames_dptr, int nb, int h, int w, const int* counts, const float* xyxy, float* out,
                            int cap, int* n) {
@@ -534,10 +405,10 @@ int gtx_embedder_embed_dev(gtx_embedder* e, const void* frames_dptr, int nb, int
   return rc != GTX_OK ? rc : gtx_embedder_collect(e, out, cap, n);
 }
 int gtx_embedder_crops(gtx_embedder* e, int i, uint8_t* out) {
-  return guarded([&] { need(e, "embedder"); need(out, "out"); e->impl->crops(i, out); });
+  return guarded([&] { need(e, "embedder"); need(out, "out"); e->impl->live()->crops(i, out); });
 }
 int gtx_embedder_layer_output(gtx_embedder* e, int i, const char* layer, float* out, int* h, int* w, int* c) {
-  return guarded([&] { need(e, "embedder"); need(layer, "layer"); e->impl->layer_output(i, layer, out, h, w, c); });
+  return guarded([&] { need(e, "embedder"); need(layer, "layer"); e->impl->live()->layer_output(i, layer, out, h, w, c); });
 }
 int gtx_embedder_saturated(gtx_embedder* e, int clear, int* flag) {
   return guarded([&] { need(e, "embedder"); need(flag, "flag"); *flag = e->impl->saturated(clear != 0) ? 1 : 0; });
@@ -551,7 +422,7 @@ int gtx_embedder_profile(gtx_embedder* e, int n, int iters, int cap, char* names
     std::vector<std::string> nm;
     std::vector<float> t;
     std::vector<double> f;
-    e->impl->profile(n, iters, nm, t, f);
+    e->impl->live()->profile(n, iters, nm, t, f);
     *n_ops = (int)nm.size();
     for (int i = 0; i < (int)nm.size() && i < cap; ++i) {
       if (names) { memset(names + (size_t)i * 128, 0, 128); strncpy(names + (size_t)i * 128, nm[i].c_str(), 127); }

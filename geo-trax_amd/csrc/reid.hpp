@@ -17,52 +17,40 @@ namespace gtx {
 // save_one_box(xyxy, im, gain=1.02, pad=10, square=False) of one detection: the clipped crop [x1, x2) x [y1, y2) of an h x w frame
 void reid_crop_box(const float xyxy[4], int h, int w, int out[4]);
 
-class Embedder {
+class Embedder : public NetRuntime {
  public:
   Embedder(gtx_ctx* ctx, int imgsz, int max_crops, bool fp32_split);
-  ~Embedder();
-  void set_tensor(const std::string& name, const float* data, int ndim, const int64_t* shape);
-  void finalize();
-  int dim() const { return exact_ ? exact_->dim() : dim_; }
+  ~Embedder() override;
+  // the calls that run or read a pass go here: the exact-fp32 twin once a split-f16x3 pass has saturated
+  Embedder* live() { return live_as<Embedder>(); }
+  void finalize() override;
+  int dim() const { return dim_; }
   // frames: nb device frames [h][w][3] BGR u8; counts[nb] boxes per frame, xyxy [sum counts][4] host, frame pixels
   void submit_dev(const void* frames, int nb, int h, int w, const int* counts, const float* xyxy);
   // waits for the submitted pass; out [n][dim] (n = the pass's box count, <= cap)
   int collect(float* out, int cap);
   void crops(int i, uint8_t* out);                                          // [S][S][4] u8 of crop i of the last pass
   void layer_output(int i, const std::string& layer, float* out, int* h, int* w, int* c);
-  bool saturated(bool clear);
-  bool fell_back() const { return exact_ != nullptr; }
   // per-op times of `iters` forward passes over the first n crops of the last pass (events around every launch)
   void profile(int n, int iters, std::vector<std::string>& names, std::vector<float>& ms, std::vector<double>& flops);
 
  private:
-  void* alloc(size_t bytes);
-  View new_view(int h, int w, int c);
-  const HostTensor& tensor(const std::string& name) const;
-  bool has(const std::string& name) const { return tensors_.count(name) != 0; }
+  size_t op_count() const override { return ops_.size(); }
+  const OpInfo& op_info(size_t i) const override { return ops_[i]; }
+  void launch_op(size_t i, int nb, hipStream_t s) override;
+  std::unique_ptr<NetRuntime> make_exact() const override;
+  void release_graph() override { ops_.clear(); }
+  void conv_config_rule(const std::string& name, ConvConfig& cfg) const override;
   View conv(const std::string& name, const View& x, int stride, const View* out_slice, const View* residual);
   View c2f(const std::string& pfx, const View& x);
   void build_graph();
-  void set_batch(int nb);
-  void run_op(const Op& op, int nb, hipStream_t s);
-  void fall_back_to_exact();
+  void set_batch(int nb) override;
   void enqueue(int n_total);
 
-  gtx_ctx* ctx_;
-  int S_, max_crops_;
-  int conv_dtype_;                       // DT_F32S (split-f16x3) or DT_F32
-  std::map<std::string, HostTensor> tensors_;
-  std::vector<DevBuf> bufs_;
+  int S_;
   std::vector<Op> ops_;
-  std::map<std::string, View> layer_views_;
   View img_, last_;
   int dim_ = 0;
-  bool finalized_ = false;
-  int cur_nb_ = -1;
-  std::unique_ptr<Embedder> exact_;
-  int* sat_dev_ = nullptr;
-  int* h_sat_ = nullptr;
-  bool sat_seen_ = false;
   // the pass in flight (kept for the exact re-run of a saturated pass)
   bool in_flight_ = false;
   const void* cur_frames_ = nullptr;

@@ -9,72 +9,31 @@
 namespace gtx {
 
 namespace {
-bool env_on(const char* name, bool dflt) {
-  const char* e = getenv(name);
-  return (e && *e) ? e[0] != '0' : dflt;
-}
+RtMap rt_map(const View& v) { return RtMap{v.ptr, v.h, v.w, v.cstride, v.coff, v.c}; }
 }  // namespace
 
-RtDetr::RtDetr(gtx_ctx* ctx, const gtx_det_config& cfg) : ctx_(ctx), cfg_(cfg) {
-  GTX_CHECK(cfg.imgsz > 0 && cfg.imgsz % 32 == 0, "imgsz must be a positive multiple of 32 (got %d)", cfg.imgsz);
-  GTX_CHECK(cfg.max_det > 0 && cfg.nc > 0 && cfg.nc <= 128, "max_det must be positive and nc in [1, 128] (got %d, %d)", cfg.max_det, cfg.nc);
-  GTX_CHECK(cfg.frame_h > 0 && cfg.frame_w > 0, "frame size must be given");
+// half: fp16 maps and weights on the fp16 MFMA convolutions (fp32 accumulate); the token side (AIFI, the decoder's queries) stays fp32.
+// Every map is allocated at 4 bytes per element.
+RtDetr::RtDetr(gtx_ctx* ctx, const gtx_det_config& cfg)
+    : DetectorBase(ctx, cfg, cfg.half ? DT_F16 : (cfg.fp32_split ? DT_F32S : DT_F32), 4, DT_F32) {
   GTX_CHECK(!cfg.obj_feats, "RT-DETR: appearance vectors (obj_feats) are not implemented");
-  if (cfg_.max_batch < 1) cfg_.max_batch = 1;
-  // half: fp16 maps and weights on the fp16 MFMA convolutions (fp32 accumulate); the token side (AIFI, the decoder's queries) stays fp32
-  fmt_ = cfg.half ? DT_F16 : (cfg.fp32_split ? DT_F32S : DT_F32);
   // RTDETRPredictor.pre_transform: LetterBox(imgsz, auto=False, scale_fill=True) -- the frame is stretched to the square, no padding
   lb_ = Letterbox{};
   lb_.src_h = cfg.frame_h; lb_.src_w = cfg.frame_w;
   lb_.net_h = lb_.net_w = lb_.new_h = lb_.new_w = cfg.imgsz;
   lb_.top = lb_.left = 0;
   lb_.gain = 1.0;
-  GTX_HIP(hipSetDevice(ctx->device));
-  for (auto& e : ev_) GTX_HIP(hipEventCreateWithFlags(&e, wait_event_flags(true)));
-  for (auto& e : ev_up_) GTX_HIP(hipEventCreate(&e));
 }
 
-RtDetr::~RtDetr() {
-  if (h_out_n_) (void)hipHostFree(h_out_n_);
-  if (h_out_rows_) (void)hipHostFree(h_out_rows_);
-  if (h_sat_) (void)hipHostFree(h_sat_);
-  for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
-  for (auto& e : ev_up_) if (e) (void)hipEventDestroy(e);
-  for (auto& e : trace_ev_) if (e) (void)hipEventDestroy(e);
+std::unique_ptr<NetRuntime> RtDetr::make_exact() const {
+  gtx_det_config c = cfg_;
+  c.fp32_split = 0;
+  return std::unique_ptr<NetRuntime>(new RtDetr(ctx_, c));
 }
 
-void RtDetr::set_tensor(const std::string& name, const float* data, int ndim, const int64_t* shape) {
-  GTX_CHECK(!finalized_, "set_tensor after finalize");
-  HostTensor t;
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
-  t.data.assign(data, data + n);
-  tensors_[name] = std::move(t);
-}
-
-const HostTensor& RtDetr::tensor(const std::string& name) const {
-  auto it = tensors_.find(name);
-  if (it == tensors_.end()) fail(-1, "missing tensor '%s'", name.c_str());
-  return it->second;
-}
-
-void* RtDetr::alloc(size_t bytes) {
-  bufs_.emplace_back(bytes);
-  GTX_HIP(hipMemset(bufs_.back().p, 0, bufs_.back().bytes));
-  return bufs_.back().p;
-}
-
-float* RtDetr::upload(const std::vector<float>& v) {
-  float* d = (float*)alloc(std::max<size_t>(v.size(), 1) * sizeof(float));
-  if (!v.empty()) GTX_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-  return d;
-}
-
-RtDetr::View RtDetr::new_view(int h, int w, int c, bool plain) {
-  View v;
-  v.n = cfg_.max_batch; v.h = h; v.w = w; v.cstride = c; v.coff = 0; v.c = c; v.plain = plain;
-  v.ptr = alloc((size_t)v.n * h * w * c * 4);
-  return v;
+void RtDetr::conv_config_rule(const std::string& name, ConvConfig& cfg) const {
+  (void)name;
+  GTX_CHECK(cfg.variant != 3 && cfg.variant != 4, "RT-DETR does not run on the Winograd kernels (unset GTX_WINO)");
 }
 
 float* RtDetr::new_tokens(int rows_per_image, int ld, const std::string& name) {
@@ -84,65 +43,24 @@ float* RtDetr::new_tokens(int rows_per_image, int ld, const std::string& name) {
 }
 
 // ---------------------------------------------------------------------------- graph pieces
-RtDetr::View RtDetr::conv_raw(const std::string& name, const std::vector<float>& w, int cout, int cin, int ks, const float* bias_host, const View& x,
-                              int stride, int act, const View* out_slice, const View* residual, bool plain_out) {
-  GTX_CHECK(cin == x.c, "%s: weight expects %d input channels, input view has %d", name.c_str(), cin, x.c);
+View RtDetr::conv_raw(const std::string& name, const std::vector<float>& w, int cout, int cin, int ks, const float* bias_host, const View& x,
+                      int stride, int act, const View* out_slice, const View* residual, bool plain_out) {
   GTX_CHECK((int)w.size() == cout * cin * ks * ks, "%s: weight size", name.c_str());
-  const int pad = ks / 2;
-  const int ho = (x.h + 2 * pad - ks) / stride + 1, wo = (x.w + 2 * pad - ks) / stride + 1;
-  View out = out_slice ? *out_slice : new_view(ho, wo, cout, plain_out);
-  GTX_CHECK(out.h == ho && out.w == wo && out.c == cout, "%s: output view mismatch", name.c_str());
-  if (fmt_ == DT_F16) out.plain = false;                       // fp16 maps everywhere, the score maps included (rt_topk reads them as such)
-  GTX_CHECK(!x.plain || fmt_ == DT_F32, "%s: a plain fp32 tensor cannot feed this convolution", name.c_str());
-  if (fmt_ == DT_F32S)
-    GTX_CHECK(x.cstride % 8 == 0 && x.coff % 8 == 0 && out.cstride % 8 == 0 && out.coff % 8 == 0 && (!residual || (residual->cstride % 8 == 0 && residual->coff % 8 == 0)),
-              "%s: channel strides / offsets of the split-f16x3 path must be multiples of 8", name.c_str());
-  Op op;
-  op.kind = Op::CONV;
-  op.name = name;
-  op.cfg = conv_pick_config(fmt_, ks, stride, cin, cout);
-  GTX_CHECK(op.cfg.variant != 3 && op.cfg.variant != 4, "RT-DETR does not run on the Winograd kernels (unset GTX_WINO)");
-  std::vector<float> ohwi((size_t)cout * cin * ks * ks);       // OIHW -> OHWI
-  parallel_for(cout, [&](int o) {
-    for (int i = 0; i < cin; ++i)
-      for (int t = 0; t < ks * ks; ++t) ohwi[((size_t)o * ks * ks + t) * cin + i] = w[((size_t)o * cin + i) * ks * ks + t];
-  });
-  float acc_scale = 1.f;
-  const std::vector<uint8_t> packed = pack_conv_weights(ohwi.data(), cout, cin, op.cfg, &acc_scale);
-  void* dw = alloc(packed.size());
-  GTX_HIP(hipMemcpy(dw, packed.data(), packed.size(), hipMemcpyHostToDevice));
-  float* db = (float*)alloc(((cout + 63) / 64 * 64) * sizeof(float));   // zero-filled up to a whole cout tile
-  if (bias_host) GTX_HIP(hipMemcpy(db, bias_host, cout * sizeof(float), hipMemcpyHostToDevice));
-  ConvProblem& p = op.grp.p[0];
-  p.in = x.ptr; p.out = out.ptr; p.wpack = dw; p.bias = db;
-  p.res = residual ? residual->ptr : nullptr;
-  p.N = x.n; p.H = x.h; p.W = x.w; p.Ho = ho; p.Wo = wo; p.Cin = cin; p.Cout = cout;
-  p.in_cstride = x.cstride; p.in_coff = x.coff;
-  p.out_cstride = out.cstride; p.out_coff = out.coff;
-  p.res_cstride = residual ? residual->cstride : 0;
-  p.res_coff = residual ? residual->coff : 0;
-  p.act = act;
-  p.acc_scale = acc_scale;
-  p.out_plain = (fmt_ == DT_F32S && out.plain) ? 1 : 0;
-  p.sat_flag = fmt_ == DT_F32S ? sat_dev_ : nullptr;
-  op.grp.count = 1;
-  op.family = conv_kernel_name(op.cfg);
-  ops_.push_back(op);
-  layer_views_[name] = out;
-  return out;
+  ConvArgs a;
+  a.stride = stride; a.act = act; a.out_slice = out_slice; a.residual = residual; a.plain_out = plain_out;
+  return emit_conv(ops_, name, w.data(), cout, cin, ks, bias_host, x, a);
 }
 
-RtDetr::View RtDetr::conv(const std::string& name, const View& x, int stride, int act, const View* out_slice, const View* residual) {
+View RtDetr::conv(const std::string& name, const View& x, int stride, int act, const View* out_slice, const View* residual) {
   const HostTensor& w = tensor(name + ".weight");
   GTX_CHECK(w.shape.size() == 4 && w.shape[2] == w.shape[3], "%s: expected OIHW square kernel", name.c_str());
-  const float* b = has(name + ".bias") ? tensor(name + ".bias").data.data() : nullptr;
-  return conv_raw(name, w.data, (int)w.shape[0], (int)w.shape[1], (int)w.shape[2], b, x, stride, act, out_slice, residual);
+  return conv_raw(name, w.data, (int)w.shape[0], (int)w.shape[1], (int)w.shape[2], bias_of(name, (int)w.shape[0]), x, stride, act, out_slice, residual);
 }
 
 // HGStem.stem2a / stem2b: a 2x2 convolution on F.pad(x, [0, 1, 0, 1]) is the 3x3 convolution (pad 1) whose kernel holds the
 // four taps at rows / columns 1..2 and zeros in row 0 and column 0: the zero taps meet the left / top padding, the others
 // the right / bottom one. Runs on the MFMA convolution as it stands (2.25 x the products of a 27 KFLOP-per-pixel layer).
-RtDetr::View RtDetr::conv2x2(const std::string& name, const View& x, const View* out_slice) {
+View RtDetr::conv2x2(const std::string& name, const View& x, const View* out_slice) {
   const HostTensor& w = tensor(name + ".weight");
   GTX_CHECK(w.shape.size() == 4 && w.shape[2] == 2 && w.shape[3] == 2, "%s: expected a 2x2 kernel", name.c_str());
   const int cout = (int)w.shape[0], cin = (int)w.shape[1];
@@ -151,8 +69,7 @@ RtDetr::View RtDetr::conv2x2(const std::string& name, const View& x, const View*
     for (int i = 0; i < cin; ++i)
       for (int dy = 0; dy < 2; ++dy)
         for (int dx = 0; dx < 2; ++dx) w3[(((size_t)o * cin + i) * 3 + 1 + dy) * 3 + 1 + dx] = w.data[(((size_t)o * cin + i) * 2 + dy) * 2 + dx];
-  const float* b = has(name + ".bias") ? tensor(name + ".bias").data.data() : nullptr;
-  return conv_raw(name, w3, cout, cin, 3, b, x, 1, 2, out_slice, nullptr);
+  return conv_raw(name, w3, cout, cin, 3, bias_of(name, cout), x, 1, 2, out_slice, nullptr);
 }
 
 void RtDetr::dwconv(const std::string& name, const View& x, const View& out, int stride, int act) {
@@ -167,12 +84,12 @@ void RtDetr::dwconv(const std::string& name, const View& x, const View& out, int
   op.name = name;
   const bool tiled = stride == 1 && C % 32 == 0;               // launch_rt_dwconv's rule (GTX_RT_DW_TILE=0 aside)
   op.family = std::string(tiled ? "rt_dwconv_tile_kernel<" : "rt_dwconv_kernel<") + (k == 3 ? "3>" : "5>");
-  op.a = x.map(); op.b = out.map();
+  op.a = rt_map(x); op.b = rt_map(out);
   op.w = upload(wt);
   op.bias = has(name + ".bias") ? upload(tensor(name + ".bias").data) : nullptr;
   op.k = k; op.stride = stride; op.act = act;
-  op.flops = 2.0 * out.h * out.w * C * k * k;
-  op.bytes = ((double)x.h * x.w + (double)out.h * out.w) * C * 4;
+  op.img_flops = 2.0 * out.h * out.w * C * k * k;
+  op.img_bytes = ((double)x.h * x.w + (double)out.h * out.w) * C * 4;
   ops_.push_back(op);
   layer_views_[name] = out;
 }
@@ -182,13 +99,13 @@ void RtDetr::upsample(const std::string& name, const View& src, const View& dst)
   op.kind = Op::UPSAMPLE;
   op.name = name;
   op.family = "rt_upsample2x_kernel";
-  op.a = src.map(); op.b = dst.map();
-  op.bytes = (double)src.h * src.w * src.c * 4 * 5;
+  op.a = rt_map(src); op.b = rt_map(dst);
+  op.img_bytes = (double)src.h * src.w * src.c * 4 * 5;
   ops_.push_back(op);
 }
 
 // The HGBlock's concat buffer [x | m.0 .. m.(n-1)]: allocated before x's producer so that x is written in place.
-RtDetr::View RtDetr::hg_cat(const std::string& pfx, int h, int w, int* c1) {
+View RtDetr::hg_cat(const std::string& pfx, int h, int w, int* c1) {
   const bool light = has(pfx + ".m.0.conv1.conv.weight");
   const HostTensor& w0 = tensor(pfx + (light ? ".m.0.conv1.conv.weight" : ".m.0.conv.weight"));
   const int cm = (int)w0.shape[0];
@@ -198,7 +115,7 @@ RtDetr::View RtDetr::hg_cat(const std::string& pfx, int h, int w, int* c1) {
   return new_view(h, w, *c1 + n * cm);
 }
 
-RtDetr::View RtDetr::hgblock(const std::string& pfx, const View& cat, int c1, bool shortcut, const View* out_slice) {
+View RtDetr::hgblock(const std::string& pfx, const View& cat, int c1, bool shortcut, const View* out_slice) {
   const bool light = has(pfx + ".m.0.conv1.conv.weight");
   const int cm = (int)tensor(pfx + (light ? ".m.0.conv1.conv.weight" : ".m.0.conv.weight")).shape[0];
   const int n = (cat.c - c1) / cm;
@@ -223,7 +140,7 @@ RtDetr::View RtDetr::hgblock(const std::string& pfx, const View& cat, int c1, bo
   return out;
 }
 
-RtDetr::View RtDetr::repc3(const std::string& pfx, const View& x) {
+View RtDetr::repc3(const std::string& pfx, const View& x) {
   View a = conv(pfx + ".cv1.conv", x, 1, 1);
   View side = conv(pfx + ".cv2.conv", x, 1, 1);
   int n = 0;
@@ -257,8 +174,8 @@ float* RtDetr::linear(const std::string& name, const std::vector<float>& w, cons
   L.res = res; L.ldr = ldr;
   L.y = y; L.ldy = ldy;
   L.M = rows; L.K = kp; L.Nout = np; L.act = act;
-  op.flops = 2.0 * rows * (double)k * nout;
-  op.bytes = ((double)rows * (k + nout) + (double)k * nout) * 4;
+  op.img_flops = 2.0 * rows * (double)k * nout;
+  op.img_bytes = ((double)rows * (k + nout) + (double)k * nout) * 4;
   ops_.push_back(op);
   return y;
 }
@@ -279,7 +196,7 @@ float* RtDetr::layernorm_tokens(const std::string& name, const float* x, int row
   op.rows = rows; op.C = C;
   op.w = upload(tensor(name + ".weight").data);
   op.bias = upload(tensor(name + ".bias").data);
-  op.bytes = (double)rows * C * 8;
+  op.img_bytes = (double)rows * C * 8;
   ops_.push_back(op);
   return y;
 }
@@ -296,11 +213,7 @@ void RtDetr::build_graph() {
   const int S = lb_.net_h;
   img_ = new_view(S, S, 4);
   img_.plain = true;                                        // RGB0 bytes, really: [N][S][S][4] u8 in a buffer sized for fp32 (kept simple)
-  if (fmt_ == DT_F32S) {
-    sat_dev_ = (int*)alloc(sizeof(int));
-    GTX_HIP(hipHostMalloc((void**)&h_sat_, sizeof(int)));
-    *h_sat_ = 0;
-  }
+  alloc_sat_flag();
   if (has("rtdetr.meta")) {
     const auto& m = tensor("rtdetr.meta").data;
     GTX_CHECK(m.size() >= 4, "rtdetr.meta: [heads, points, queries, encoder heads] expected");
@@ -331,11 +244,11 @@ void RtDetr::build_graph() {
     op.kind = Op::STEM1;
     op.name = "model.0.stem1.conv";
     op.family = "rt_stem1_kernel";
-    op.a = img_.map(); op.b = s1.map();
+    op.a = rt_map(img_); op.b = rt_map(s1);
     op.w = upload(w27);
     op.bias = upload(has("model.0.stem1.conv.bias") ? tensor("model.0.stem1.conv.bias").data : std::vector<float>(cm0, 0.f));
-    op.flops = 2.0 * s1.h * s1.w * cm0 * 27;
-    op.bytes = (double)S * S * 4 + (double)s1.h * s1.w * cm0 * 4;
+    op.img_flops = 2.0 * s1.h * s1.w * cm0 * 27;
+    op.img_bytes = (double)S * S * 4 + (double)s1.h * s1.w * cm0 * 4;
     ops_.push_back(op);
     layer_views_[op.name] = s1;
   }
@@ -347,8 +260,8 @@ void RtDetr::build_graph() {
     op.name = "model.0.pool";
     op.family = "rt_pool2_kernel";
     View dst = cat_s.slice(0, cm0);
-    op.a = s1.map(); op.b = dst.map();
-    op.bytes = (double)s1.h * s1.w * cm0 * 8;
+    op.a = rt_map(s1); op.b = rt_map(dst);
+    op.img_bytes = (double)s1.h * s1.w * cm0 * 8;
     ops_.push_back(op);
   }
   {
@@ -411,12 +324,12 @@ void RtDetr::build_graph() {
     op.kind = Op::TOKENS_IN;
     op.name = A + ".tokens";
     op.family = "rt_tokens_in_kernel";
-    op.a = x10.map();
+    op.a = rt_map(x10);
     op.p0 = upload(pos);
     float* src = new_tokens(T5, E, A + ".src");
     float* q = new_tokens(T5, E, A + ".q");
     op.p1 = src; op.p2 = q;
-    op.bytes = (double)T5 * E * 12;
+    op.img_bytes = (double)T5 * E * 12;
     ops_.push_back(op);
     const HostTensor &ipw = tensor(A + ".ma.in_proj_weight"), &ipb = tensor(A + ".ma.in_proj_bias");
     GTX_CHECK((int)ipw.shape[0] == 3 * E && (int)ipw.shape[1] == E, "AIFI in_proj shape");
@@ -431,8 +344,8 @@ void RtDetr::build_graph() {
       m.family = E / enc_heads_ == 32 ? "rt_mha32_kernel" : "rt_mha_kernel";
       m.p0 = qkv; m.ld0 = 3 * E; m.p1 = attn; m.ld1 = E;
       m.T = T5; m.C = E; m.heads = enc_heads_;
-      m.flops = 4.0 * T5 * (double)T5 * E;
-      m.bytes = (double)T5 * E * 16;
+      m.img_flops = 4.0 * T5 * (double)T5 * E;
+      m.img_bytes = (double)T5 * E * 16;
       ops_.push_back(m);
     }
     float* t1 = linear(A + ".ma.out_proj", tensor(A + ".ma.out_proj.weight").data, tensor(A + ".ma.out_proj.bias").data, E, E, attn, E, nullptr, T5, 0, src, E, nullptr, 0, A + ".t1");
@@ -504,7 +417,7 @@ void RtDetr::build_graph() {
     op.kind = Op::MASK;
     op.name = D + ".valid_mask." + std::to_string(l);
     op.family = "rt_mask_invalid_kernel";
-    op.a = proj[l].map();
+    op.a = rt_map(proj[l]);
     op.level = l;
     ops_.push_back(op);
   }
@@ -521,7 +434,7 @@ void RtDetr::build_graph() {
       op.r_in = op.r_out = RtRows{enc[l].ptr, enc[l].cstride, enc[l].coff, fmt_};
       op.rows = (long)enc[l].h * enc[l].w; op.C = hd_;
       op.w = g; op.bias = be;
-      op.bytes = (double)op.rows * hd_ * 8;
+      op.img_bytes = (double)op.rows * hd_ * 8;
       ops_.push_back(op);
       layer_views_[D + ".enc_output." + std::to_string(l)] = enc[l];
     }
@@ -547,7 +460,7 @@ void RtDetr::build_graph() {
     op.lv.n_levels = 3;
     op.p1 = (float*)alloc(sizeof(unsigned) * cfg_.max_batch * (size_t)S_total);   // key scratch
     op.p2 = (float*)topk_idx;
-    op.bytes = (double)S_total * ncp_ * 4;
+    op.img_bytes = (double)S_total * ncp_ * 4;
     ops_.push_back(op);
   }
   float* embed = new_tokens(nq_, hd_, D + ".embed");
@@ -607,7 +520,7 @@ void RtDetr::build_graph() {
       m.family = hd_ / nh_ == 32 ? "rt_mha32_kernel" : "rt_mha_kernel";
       m.p0 = qkv; m.ld0 = 3 * hd_; m.p1 = attn; m.ld1 = hd_;
       m.T = nq_; m.C = hd_; m.heads = nh_;
-      m.flops = 4.0 * nq_ * (double)nq_ * hd_;
+      m.img_flops = 4.0 * nq_ * (double)nq_ * hd_;
       ops_.push_back(m);
     }
     float* t1 = lin_named(lp + ".self_attn.out_proj", attn, hd_, nullptr, 0, out, hd_, "");
@@ -629,7 +542,7 @@ void RtDetr::build_graph() {
       d.lv = vlv;
       for (int l = 0; l < 3; ++l) d.lv.coff[l] = val[l].coff + i * hd_;
       d.p0 = offaw; d.p1 = samp; d.p2 = refer_;
-      d.bytes = (double)nq_ * hd_ * LP * 4 * 4;
+      d.img_bytes = (double)nq_ * hd_ * LP * 4 * 4;
       ops_.push_back(d);
     }
     float* t2 = lin_named(lp + ".cross_attn.output_proj", samp, hd_, nullptr, 0, o1, hd_, "");
@@ -652,12 +565,16 @@ void RtDetr::build_graph() {
 void RtDetr::set_batch(int nb) {
   if (nb == cur_nb_) return;
   for (Op& op : ops_) {
-    if (op.kind != Op::CONV) continue;
+    if (op.kind != Op::CONV) {
+      op.flops = op.img_flops * nb;
+      op.bytes = op.img_bytes * nb;
+      continue;
+    }
     for (int i = 0; i < op.grp.count; ++i) op.grp.p[i].N = nb;
     conv_group_finalize(op.grp, op.cfg);
     const ConvProblem& p = op.grp.p[0];
-    op.flops = conv_flops(p, op.cfg.ks) / nb;
-    op.bytes = ((double)p.H * p.W * p.Cin + (double)p.Ho * p.Wo * p.Cout) * 4 + (double)p.Cout * p.Cin * op.cfg.ks * op.cfg.ks * 4 / nb;
+    op.flops = conv_flops(p, op.cfg.ks);
+    op.bytes = ((double)p.H * p.W * p.Cin + (double)p.Ho * p.Wo * p.Cout) * 4 * nb + (double)p.Cout * p.Cin * op.cfg.ks * op.cfg.ks * 4;
   }
   cur_nb_ = nb;
 }
@@ -667,18 +584,14 @@ void RtDetr::finalize() {
   GTX_HIP(hipSetDevice(ctx_->device));
   build_graph();
   const int N = cfg_.max_batch;
-  gray_h_ = cfg_.frame_h / 2;
-  gray_w_ = cfg_.frame_w / 2;
-  gray_.alloc((size_t)kGrayRing * N * gray_h_ * gray_w_);
+  alloc_outputs();
   class_mask_[0] = class_mask_[1] = cfg_.n_classes == 0 ? ~0ull : 0ull;
   for (int i = 0; i < cfg_.n_classes; ++i)
     if (cfg_.classes[i] >= 0 && cfg_.classes[i] < 128) class_mask_[cfg_.classes[i] >> 6] |= 1ull << (cfg_.classes[i] & 63);
   raw_ = (float*)alloc(sizeof(float) * N * nq_ * (4 + nc_));
   out_rows_ = (float*)alloc(sizeof(float) * 6 * N * cfg_.max_det);
   out_n_ = (int*)alloc(sizeof(int) * N);
-  GTX_HIP(hipHostMalloc((void**)&h_out_n_, sizeof(int) * N));
-  GTX_HIP(hipHostMalloc((void**)&h_out_rows_, sizeof(float) * 6 * N * cfg_.max_det));
-  if (fmt_ != DT_F32S || !env_on("GTX_SAT_FALLBACK", true)) tensors_.clear();   // the split path keeps the host copies for fall_back_to_exact
+  drop_tensors_unless_fallback();
   set_batch(1);
   GTX_HIP(hipStreamSynchronize(ctx_->stream));
   finalized_ = true;
@@ -708,187 +621,14 @@ void RtDetr::run_op(const Op& op, int nb, hipStream_t s) {
   }
 }
 
-void RtDetr::run_forward(int nb, hipStream_t s, bool traced) {
-  if (!traced) {
-    for (const Op& op : ops_) run_op(op, nb, s);
-    return;
-  }
-  for (size_t i = 0; i < ops_.size(); ++i) {
-    GTX_HIP(hipEventRecord(trace_ev_[i], s));
-    run_op(ops_[i], nb, s);
-  }
-  GTX_HIP(hipEventRecord(trace_ev_[ops_.size()], s));
-}
-
-void RtDetr::set_trace(int every_n) {
-  if (exact_) return exact_->set_trace(every_n);
-  GTX_CHECK(finalized_ && every_n >= 0, "set_trace: detector not finalized or bad period");
-  GTX_CHECK(!in_flight_, "set_trace while a batch is in flight");
-  trace_every_ = every_n;
-  trace_count_ = 0;
-  if (every_n > 0 && trace_ev_.empty()) {
-    trace_ev_.resize(ops_.size() + 1);
-    for (auto& e : trace_ev_) GTX_HIP(hipEventCreate(&e));
-  }
-  trace_ms_.assign(ops_.size(), 0.0);
-  trace_n_.assign(ops_.size(), 0);
-  trace_flops_.assign(ops_.size(), 0.0);
-  trace_bytes_.assign(ops_.size(), 0.0);
-}
-
-void RtDetr::trace_report(std::vector<std::string>& names, std::vector<int>& launches, std::vector<float>& ms, std::vector<double>& flops,
-                          std::vector<double>& bytes) {
-  if (exact_) return exact_->trace_report(names, launches, ms, flops, bytes);
-  std::map<std::string, size_t> idx;
-  for (size_t i = 0; i < ops_.size() && i < trace_n_.size(); ++i) {
-    if (trace_n_[i] == 0) continue;
-    auto it = idx.find(ops_[i].family);
-    size_t k;
-    if (it == idx.end()) {
-      k = names.size();
-      idx[ops_[i].family] = k;
-      names.push_back(ops_[i].family);
-      launches.push_back(0); ms.push_back(0.f); flops.push_back(0.0); bytes.push_back(0.0);
-    } else {
-      k = it->second;
-    }
-    launches[k] += trace_n_[i];
-    ms[k] += (float)trace_ms_[i];
-    flops[k] += trace_flops_[i];
-    bytes[k] += trace_bytes_[i];
-  }
-  trace_ms_.assign(ops_.size(), 0.0);
-  trace_n_.assign(ops_.size(), 0);
-  trace_flops_.assign(ops_.size(), 0.0);
-  trace_bytes_.assign(ops_.size(), 0.0);
-}
-
-void RtDetr::fall_back_to_exact() {
-  gtx_det_config c = cfg_;
-  c.fp32_split = 0;
-  std::unique_ptr<RtDetr> d(new RtDetr(ctx_, c));
-  for (const auto& kv : tensors_) d->set_tensor(kv.first, kv.second.data.data(), (int)kv.second.shape.size(), kv.second.shape.data());
-  d->finalize();
-  if (trace_every_ > 0) d->set_trace(trace_every_);
-  GTX_HIP(hipStreamSynchronize(ctx_->stream));
-  ops_.clear();
-  layer_views_.clear();
-  bufs_.clear();
-  tensors_.clear();
-  exact_ = std::move(d);
-}
-
-bool RtDetr::saturated(bool clear) {
-  const bool r = sat_seen_;
-  if (clear) {
-    sat_seen_ = false;
-    if (sat_dev_ && !exact_) {
-      GTX_HIP(hipSetDevice(ctx_->device));
-      GTX_HIP(hipMemsetAsync(sat_dev_, 0, sizeof(int), ctx_->stream));
-    }
-  }
-  return r;
-}
-
-void RtDetr::submit_dev(const void* frames, int nb, int h, int w) {
-  if (exact_) return exact_->submit_dev(frames, nb, h, w);
-  GTX_CHECK(finalized_, "detector not finalized");
-  GTX_CHECK(!in_flight_, "submit while a batch is in flight: call collect first");
-  GTX_CHECK(nb >= 1 && nb <= cfg_.max_batch, "batch %d outside [1,%d]", nb, cfg_.max_batch);
-  GTX_CHECK(h == cfg_.frame_h && w == cfg_.frame_w, "frame is %dx%d, detector was created for %dx%d", w, h, cfg_.frame_w, cfg_.frame_h);
-  GTX_HIP(hipSetDevice(ctx_->device));
-  hipStream_t s = ctx_->stream;
-  set_batch(nb);
-  cur_frames_ = frames;
-  gray_slot_ = (gray_slot_ + 1) % kGrayRing;
-  uint8_t* gray = gray_.as<uint8_t>() + (size_t)gray_slot_ * cfg_.max_batch * gray_h_ * gray_w_;
-  GTX_HIP(hipEventRecord(ev_[0], s));
-  launch_preprocess(DT_F32, (const uint8_t*)frames, nb, lb_, img_.ptr, gray, gray_h_, gray_w_, s);
-  GTX_HIP(hipEventRecord(ev_[1], s));
-  flight_traced_ = trace_every_ > 0 && (trace_count_++ % trace_every_) == 0;
-  run_forward(nb, s, flight_traced_);
-  GTX_HIP(hipEventRecord(ev_[2], s));
+void RtDetr::run_post(int nb, hipStream_t s) {
   launch_rt_post(logits_, ncp_, refer_, nb, nq_, nc_, cfg_.conf, class_mask_, cfg_.frame_w, cfg_.frame_h, cfg_.max_det, out_rows_, out_n_, raw_, s);
   GTX_HIP(hipMemcpyAsync(h_out_n_, out_n_, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
   GTX_HIP(hipMemcpyAsync(h_out_rows_, out_rows_, sizeof(float) * 6 * nb * cfg_.max_det, hipMemcpyDeviceToHost, s));
   if (sat_dev_) GTX_HIP(hipMemcpyAsync(h_sat_, sat_dev_, sizeof(int), hipMemcpyDeviceToHost, s));
-  GTX_HIP(hipEventRecord(ev_[3], s));
-  in_flight_ = true;
-  flight_nb_ = nb;
-}
-
-void RtDetr::collect(int* n_out, float* xyxy, float* conf, int* cls, float speed_ms[3]) {
-  if (exact_) return exact_->collect(n_out, xyxy, conf, cls, speed_ms);
-  GTX_CHECK(in_flight_, "collect without a submitted batch");
-  GTX_HIP(hipSetDevice(ctx_->device));
-  GTX_HIP(hipEventSynchronize(ev_[3]));
-  in_flight_ = false;
-  collected_gray_slot_ = gray_slot_;
-  if (h_sat_ && *h_sat_) {
-    sat_seen_ = true;
-    if (fmt_ == DT_F32S && !tensors_.empty()) {        // this batch again at fp32's range, and every later one (Detector::collect's rule)
-      flight_traced_ = false;
-      fall_back_to_exact();
-      return exact_->detect_dev(cur_frames_, flight_nb_, cfg_.frame_h, cfg_.frame_w, n_out, xyxy, conf, cls, speed_ms);
-    }
-  }
-  if (flight_traced_) {
-    for (size_t i = 0; i < ops_.size(); ++i) {
-      float t = 0.f;
-      GTX_HIP(hipEventElapsedTime(&t, trace_ev_[i], trace_ev_[i + 1]));
-      trace_ms_[i] += t;
-      trace_n_[i] += 1;
-      trace_flops_[i] += ops_[i].flops * flight_nb_;
-      trace_bytes_[i] += ops_[i].bytes * flight_nb_;
-    }
-    flight_traced_ = false;
-  }
-  for (int b = 0; b < flight_nb_; ++b) {
-    const int n = h_out_n_[b];
-    n_out[b] = n;
-    const float* rows = h_out_rows_ + (size_t)b * cfg_.max_det * 6;
-    for (int i = 0; i < n; ++i) {
-      float* bx = xyxy + ((size_t)b * cfg_.max_det + i) * 4;
-      bx[0] = rows[i * 6 + 0]; bx[1] = rows[i * 6 + 1]; bx[2] = rows[i * 6 + 2]; bx[3] = rows[i * 6 + 3];
-      conf[(size_t)b * cfg_.max_det + i] = rows[i * 6 + 4];
-      cls[(size_t)b * cfg_.max_det + i] = (int)rows[i * 6 + 5];
-    }
-  }
-  if (speed_ms)
-    for (int i = 0; i < 3; ++i) GTX_HIP(hipEventElapsedTime(&speed_ms[i], ev_[i], ev_[i + 1]));
-}
-
-void RtDetr::detect_dev(const void* frames, int nb, int h, int w, int* n_out, float* xyxy, float* conf, int* cls, float speed_ms[3]) {
-  submit_dev(frames, nb, h, w);
-  collect(n_out, xyxy, conf, cls, speed_ms);
-}
-
-void RtDetr::detect_host(const uint8_t* frame, int h, int w, int* n_out, float* xyxy, float* conf, int* cls, float speed_ms[3]) {
-  GTX_CHECK(finalized_, "detector not finalized");
-  GTX_HIP(hipSetDevice(ctx_->device));
-  const size_t bytes = (size_t)h * w * 3;
-  if (frame_stage_.bytes < bytes) frame_stage_.alloc(bytes);
-  GTX_HIP(hipEventRecord(ev_up_[0], ctx_->stream));
-  GTX_HIP(hipMemcpyAsync(frame_stage_.p, frame, bytes, hipMemcpyHostToDevice, ctx_->stream));
-  GTX_HIP(hipEventRecord(ev_up_[1], ctx_->stream));
-  detect_dev(frame_stage_.p, 1, h, w, n_out, xyxy, conf, cls, speed_ms);
-  if (speed_ms) {
-    float up_ms = 0.f;
-    GTX_HIP(hipEventElapsedTime(&up_ms, ev_up_[0], ev_up_[1]));
-    speed_ms[0] += up_ms;
-  }
-}
-
-const void* RtDetr::gray(int b, int* gh, int* gw) const {
-  if (exact_) return exact_->gray(b, gh, gw);
-  if (gh) *gh = gray_h_;
-  if (gw) *gw = gray_w_;
-  if (b < 0 || b >= cfg_.max_batch) return nullptr;
-  return gray_.as<uint8_t>() + ((size_t)collected_gray_slot_ * cfg_.max_batch + b) * gray_h_ * gray_w_;
 }
 
 void RtDetr::raw_output(int b, float* out, int* n_anchors, bool logits) {
-  if (exact_) return exact_->raw_output(b, out, n_anchors, logits);
   GTX_CHECK(finalized_ && cur_nb_ > 0 && b >= 0 && b < cur_nb_, "raw_output: no forward pass for slot %d", b);
   GTX_CHECK(!in_flight_, "raw_output while a batch is in flight: call collect first");
   const size_t per = (size_t)nq_ * (4 + nc_);
@@ -903,7 +643,6 @@ void RtDetr::raw_output(int b, float* out, int* n_anchors, bool logits) {
 }
 
 void RtDetr::layer_output(int b, const std::string& layer, float* out, int* h, int* w, int* c) {
-  if (exact_) return exact_->layer_output(b, layer, out, h, w, c);
   GTX_CHECK(!(out && in_flight_), "layer_output while a batch is in flight: call collect first");
   auto it = layer_views_.find(layer);
   if (it == layer_views_.end()) fail(-1, "unknown layer '%s'", layer.c_str());
@@ -913,58 +652,7 @@ void RtDetr::layer_output(int b, const std::string& layer, float* out, int* h, i
   if (c) *c = v.c;
   if (!out) return;
   GTX_CHECK(b >= 0 && b < cfg_.max_batch, "bad batch slot");
-  const size_t px = (size_t)v.h * v.w;
-  const size_t es = (fmt_ == DT_F16 && !v.plain) ? 2 : 4;
-  std::vector<uint8_t> host(px * v.cstride * es);
-  GTX_HIP(hipMemcpy(host.data(), (const uint8_t*)v.ptr + (size_t)b * px * v.cstride * es, host.size(), hipMemcpyDeviceToHost));
-  for (size_t p = 0; p < px; ++p)
-    for (int k = 0; k < v.c; ++k) {
-      const size_t src = p * v.cstride + v.coff + k;
-      float f;
-      if (fmt_ == DT_F32S && !v.plain) f = pair_element(host.data(), src);
-      else if (es == 2) { _Float16 hv; memcpy(&hv, host.data() + src * 2, 2); f = (float)hv; }
-      else memcpy(&f, host.data() + src * 4, 4);
-      out[p * v.c + k] = f;
-    }
-}
-
-void RtDetr::profile(int nb, int iters, std::vector<std::string>& names, std::vector<int>& launches, std::vector<float>& ms,
-                     std::vector<double>& flops, std::vector<double>& bytes) {
-  if (exact_) return exact_->profile(nb, iters, names, launches, ms, flops, bytes);
-  GTX_CHECK(finalized_, "detector not finalized");
-  GTX_CHECK(nb >= 1 && nb <= cfg_.max_batch && iters >= 1, "bad profile arguments");
-  hipStream_t s = ctx_->stream;
-  set_batch(nb);
-  std::vector<hipEvent_t> ev(ops_.size() + 1);
-  for (auto& e : ev) GTX_HIP(hipEventCreate(&e));
-  std::map<std::string, size_t> idx;
-  const bool per_op = std::getenv("GTX_PROFILE_PER_OP") != nullptr;
-  auto slot = [&](const std::string& fam) {
-    auto it = idx.find(fam);
-    if (it != idx.end()) return it->second;
-    idx[fam] = names.size();
-    names.push_back(fam);
-    launches.push_back(0); ms.push_back(0.f); flops.push_back(0.0); bytes.push_back(0.0);
-    return names.size() - 1;
-  };
-  for (int it = 0; it < iters; ++it) {
-    for (size_t i = 0; i < ops_.size(); ++i) {
-      GTX_HIP(hipEventRecord(ev[i], s));
-      run_op(ops_[i], nb, s);
-    }
-    GTX_HIP(hipEventRecord(ev[ops_.size()], s));
-    GTX_HIP(hipStreamSynchronize(s));
-    for (size_t i = 0; i < ops_.size(); ++i) {
-      float t = 0.f;
-      GTX_HIP(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-      const size_t k = slot(per_op ? (i < 10 ? "00" : i < 100 ? "0" : "") + std::to_string(i) + " " + ops_[i].name : ops_[i].family);
-      launches[k] += 1;
-      ms[k] += t;
-      flops[k] += ops_[i].flops * nb;
-      bytes[k] += ops_[i].bytes * nb;
-    }
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
+  read_view(v, b, out);
 }
 
 }  // namespace gtx

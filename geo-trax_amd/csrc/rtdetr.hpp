@@ -15,33 +15,17 @@ namespace gtx {
 class RtDetr : public DetectorBase {
  public:
   RtDetr(gtx_ctx* ctx, const gtx_det_config& cfg);
-  ~RtDetr() override;
-  void set_tensor(const std::string& name, const float* data, int ndim, const int64_t* shape) override;
   void finalize() override;
-  void input_size(int* h, int* w) const override { *h = lb_.net_h; *w = lb_.net_w; }
-  void detect_dev(const void* frames, int nb, int h, int w, int* n_out, float* xyxy, float* conf, int* cls, float speed_ms[3]) override;
-  void submit_dev(const void* frames, int nb, int h, int w) override;
-  void collect(int* n_out, float* xyxy, float* conf, int* cls, float speed_ms[3]) override;
-  void detect_host(const uint8_t* frame, int h, int w, int* n_out, float* xyxy, float* conf, int* cls, float speed_ms[3]) override;
-  const void* gray(int b, int* gh, int* gw) const override;
   // [nq][4 + nc]: xywh normalised to the frame + class scores of every query of image b (logits: the pre-sigmoid class logits)
   void raw_output(int b, float* out, int* n_anchors, bool logits = false) override;
   void layer_output(int b, const std::string& layer, float* out, int* h, int* w, int* c) override;
-  void profile(int nb, int iters, std::vector<std::string>& names, std::vector<int>& launches, std::vector<float>& ms,
-               std::vector<double>& flops, std::vector<double>& bytes) override;
-  void set_trace(int every_n) override;
-  void trace_report(std::vector<std::string>& names, std::vector<int>& launches, std::vector<float>& ms, std::vector<double>& flops,
-                    std::vector<double>& bytes) override;
   void features(int, float*, int, int*, int*) const override { fail(-3, "RT-DETR: appearance vectors (obj_feats) are not implemented"); }
-  bool saturated(bool clear) override;
-  bool fell_back() const override { return exact_ != nullptr; }
   void pad_skip(int* on, int* skipped, int* total) const override { if (on) *on = 0; if (skipped) *skipped = 0; if (total) *total = 0; }
   void sparse_box(int* on, int* overflows) const override { if (on) *on = 0; if (overflows) *overflows = 0; }
 
  private:
-  struct Op {
+  struct Op : OpInfo {
     enum Kind { CONV, STEM1, POOL2, DWCONV, UPSAMPLE, TOKENS_IN, LINEAR, LAYERNORM, MHA, MASK, TOPK, GATHER, REFER, DEFORM } kind = CONV;
-    std::string name, family;
     ConvGroup grp{};
     ConvConfig cfg{};
     RtMap a{}, b{};                  // map in / out
@@ -57,22 +41,16 @@ class RtDetr : public DetectorBase {
     float* p2 = nullptr;             // TOKENS_IN q; REFER refer; DEFORM refer; GATHER anchors
     int ld0 = 0, ld1 = 0;
     RtLevels lv{};                   // TOPK scores / GATHER enc / DEFORM values
-    double flops = 0, bytes = 0;     // per image
-  };
-  struct View {
-    void* ptr = nullptr;
-    int n = 0, h = 0, w = 0, cstride = 0, coff = 0, c = 0;
-    bool plain = false;              // plain fp32 whatever the activation format (token rows, score maps)
-    View slice(int off, int cnt) const { View v = *this; v.coff = coff + off; v.c = cnt; return v; }
-    RtMap map() const { return RtMap{ptr, h, w, cstride, coff, c}; }
+    double img_flops = 0, img_bytes = 0;   // ops other than CONV: per image (set_batch scales them to the pass)
   };
 
-  void* alloc(size_t bytes);
-  float* upload(const std::vector<float>& v);
-  View new_view(int h, int w, int c, bool plain = false);
+  size_t op_count() const override { return ops_.size(); }
+  const OpInfo& op_info(size_t i) const override { return ops_[i]; }
+  void launch_op(size_t i, int nb, hipStream_t s) override { run_op(ops_[i], nb, s); }
+  std::unique_ptr<NetRuntime> make_exact() const override;
+  void release_graph() override { ops_.clear(); }
+  void conv_config_rule(const std::string& name, ConvConfig& cfg) const override;
   float* new_tokens(int rows_per_image, int ld, const std::string& name);
-  const HostTensor& tensor(const std::string& name) const;
-  bool has(const std::string& name) const { return tensors_.count(name) != 0; }
   // graph building
   View conv_raw(const std::string& name, const std::vector<float>& w_oihw, int cout, int cin, int ks, const float* bias_host, const View& x, int stride,
                 int act, const View* out_slice, const View* residual, bool plain_out = false);
@@ -88,34 +66,12 @@ class RtDetr : public DetectorBase {
   float* layernorm_tokens(const std::string& name, const float* x, int rows, int C, const std::string& out_name, const View* map_out = nullptr);
   void build_graph();
   void run_op(const Op& op, int nb, hipStream_t s);
-  void run_forward(int nb, hipStream_t s, bool traced);
-  void set_batch(int nb);
-  void fall_back_to_exact();
+  void run_post(int nb, hipStream_t s) override;
+  void set_batch(int nb) override;
 
-  gtx_ctx* ctx_;
-  gtx_det_config cfg_;
-  std::unique_ptr<RtDetr> exact_;
-  int fmt_;                          // activation format of the map tensors: DT_F32 or DT_F32S
-  Letterbox lb_{};
-  std::map<std::string, HostTensor> tensors_;
-  std::vector<DevBuf> bufs_;
   std::vector<Op> ops_;
-  std::map<std::string, View> layer_views_;
-  bool finalized_ = false;
-  int cur_nb_ = 0;
   int nh_ = 8, npts_ = 4, nq_ = 300, enc_heads_ = 8, hd_ = 256, nc_ = 0, ncp_ = 0, ndl_ = 0;
 
-  View img_;
-  DevBuf frame_stage_, gray_;
-  int gray_h_ = 0, gray_w_ = 0;
-  const void* cur_frames_ = nullptr;
-  static constexpr int kGrayRing = 16;
-  int gray_slot_ = 0, collected_gray_slot_ = 0;
-  bool in_flight_ = false;
-  int flight_nb_ = 0;
-  int* sat_dev_ = nullptr;
-  int* h_sat_ = nullptr;
-  bool sat_seen_ = false;
   // post stage
   const float* logits_ = nullptr;    // [N * nq][ncp]
   float* refer_ = nullptr;           // [N * nq][16]
@@ -123,15 +79,6 @@ class RtDetr : public DetectorBase {
   unsigned long long class_mask_[2] = {~0ull, ~0ull};
   float* out_rows_ = nullptr;
   int* out_n_ = nullptr;
-  int* h_out_n_ = nullptr;
-  float* h_out_rows_ = nullptr;
-  hipEvent_t ev_[4]{};
-  hipEvent_t ev_up_[2]{};
-  int trace_every_ = 0, trace_count_ = 0;
-  bool flight_traced_ = false;
-  std::vector<hipEvent_t> trace_ev_;
-  std::vector<double> trace_ms_, trace_flops_, trace_bytes_;
-  std::vector<int> trace_n_;
 };
 
 }  // namespace gtx

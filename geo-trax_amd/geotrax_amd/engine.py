@@ -569,7 +569,7 @@ class ExtractEngine:
             yield from self._track_batch(*item)
 
     def _tracked_frames_threaded(self, batches):
-        # Queue depths. A frame's gray image lives in its detector's 16-deep ring (detector.hpp kGrayRing) until that
+        # Queue depths. A frame's gray image lives in its detector's 16-deep ring (net_runtime.hpp DetectorBase::kGrayRing) until that
         # detector has started 15 more passes; by then stage 1 has handed on at least 14 * n_dets * B later frames, so
         # the frames between stage 1 and the stabilizer's collect must stay below that.
         n_batches = 2
