@@ -1,5 +1,5 @@
-// YOLOv8 (detect) graph builder + executor. Layer topology follows ultralytics'
-// cfg/models/v8/yolov8.yaml (backbone 0-9, head 10-22) or yolov8-p2.yaml (head 10-28, a fourth Detect level at stride 4);
+// YOLOv8 (detect) graph builder + executor: the trunk (yolo_trunk.cpp: backbone + neck of ultralytics' cfg/models/v8/yolov8.yaml or
+// yolov8-p2.yaml) and the Detect layer on its outputs (model.22, or model.28 of the P2 graph: a fourth level at stride 4);
 // channel widths and bottleneck counts are read off the tensor shapes, so every v8 scale (n/s/m/l/x) loads unchanged.
 #include "detector.hpp"
 #include "split_format.hpp"
@@ -11,7 +11,8 @@ namespace gtx {
 
 Detector::Detector(gtx_ctx* ctx, const gtx_det_config& cfg)
     : DetectorBase(ctx, cfg, cfg.half ? DT_F16 : (cfg.fp32_split ? DT_F32S : DT_F32), dtype_size(cfg.half ? DT_F16 : DT_F32),
-                   cfg.half ? DT_F16 : DT_F32) {
+                   cfg.half ? DT_F16 : DT_F32),
+      trunk_(*this, ops_, cfg.half ? DT_F16 : DT_F32) {
   dtype_ = cfg.half ? DT_F16 : DT_F32;
   es_ = dtype_size(dtype_);
   lb_ = letterbox_geometry(cfg.frame_h, cfg.frame_w, cfg.imgsz, cfg.rect != 0, 32);
@@ -29,224 +30,23 @@ std::unique_ptr<NetRuntime> Detector::make_exact() const {
   return std::unique_ptr<NetRuntime>(new Detector(ctx_, c));
 }
 
-// Emits one Conv op: weights "<name>.weight" (OIHW) / "<name>.bias" (optional).
-View Detector::conv(const std::string& name, const View& x, int stride, bool act, const View* out_slice,
-                    const View* residual, const View* up_src) {
-  const HostTensor& w = tensor(name + ".weight");
-  GTX_CHECK(w.shape.size() == 4 && w.shape[2] == w.shape[3], "%s: expected OIHW square kernel", name.c_str());
-  const int cout = (int)w.shape[0], cin = (int)w.shape[1], ks = (int)w.shape[2];
-  GTX_CHECK(fmt_ != DT_F32S || !up_src || !up_src->plain, "%s: a plain fp32 tensor cannot feed a split convolution", name.c_str());
+// One Conv op of the Detect head, with the grouped stages' K chunk / cout tile / plain output in force
+View Detector::head_conv(const std::string& name, const View& x, const View* out_slice) {
   ConvArgs a;
-  a.stride = stride; a.act = act ? 1 : 0; a.out_slice = out_slice; a.residual = residual;
+  a.out_slice = out_slice;
   a.plain_out = fmt_ == DT_F32S && plain_out_;
   a.force_kc = force_kc_; a.force_bn = force_bn_;
-  a.out_pixels = (long)x.n * ((x.h + 2 * (ks / 2) - ks) / stride + 1) * ((x.w + 2 * (ks / 2) - ks) / stride + 1);
-  const View out = emit_conv(ops_, name, w.data.data(), cout, cin, ks, bias_of(name, cout), x, a);
-  if (up_src) {
-    Op& op = ops_.back();
-    if (op.cfg.variant == 6) op.cfg.variant = 2;     // the second source is read by the 32x32x16 kernel only (same weight image)
-    GTX_CHECK(ks == 1 && stride == 1 && op.cfg.variant == 2 && up_src->h * 2 == x.h && up_src->w * 2 == x.w && up_src->c < cin,
-              "%s: upsampled source does not fit", name.c_str());
-    ConvProblem& p = op.grp.p[0];
-    p.in2 = up_src->ptr; p.in2_cstride = up_src->cstride; p.in2_coff = up_src->coff; p.c_split = up_src->c;
-    op.family = conv_kernel_name(op.cfg);
-  }
-  return out;
-}
-
-View Detector::c2f(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src) {
-  const HostTensor& w1 = tensor(pfx + ".cv1.conv.weight");
-  const int c = (int)w1.shape[0] / 2;
-  int n = 0;
-  while (has(pfx + ".m." + std::to_string(n) + ".cv1.conv.weight")) ++n;
-  View cat = new_view(x.h, x.w, (2 + n) * c);
-  View first = cat.slice(0, 2 * c);
-  conv(pfx + ".cv1.conv", x, 1, true, &first, nullptr, up_src);
-  for (int k = 0; k < n; ++k) {
-    // a buffer of its own per bottleneck: rows that no launch rewrites (plan_pad_skip) must keep ONE producer's values
-    View tmp = new_view(x.h, x.w, c);
-    const std::string m = pfx + ".m." + std::to_string(k);
-    View src = cat.slice((1 + k) * c, c);
-    View dst = cat.slice((2 + k) * c, c);
-    conv(m + ".cv1.conv", src, 1, true, &tmp, nullptr);
-    conv(m + ".cv2.conv", tmp, 1, true, &dst, shortcut ? &src : nullptr);
-  }
-  View out = conv(pfx + ".cv2.conv", cat, 1, true, out_slice, nullptr);
-  layer_views_[pfx] = out;
-  return out;
+  return emit_named_conv(ops_, name, x, a);
 }
 
 void Detector::build_graph() {
   const int H = lb_.net_h, W = lb_.net_w;
   img_ = new_view(H, W, 4);
   alloc_sat_flag();
-
-  // ---- layer 0: stem (dedicated 3-channel kernel) ----
-  const HostTensor& w0 = tensor("model.0.conv.weight");
-  GTX_CHECK(w0.shape.size() == 4 && w0.shape[1] == 3 && w0.shape[2] == 3, "model.0 must be a 3x3 conv on 3 channels");
-  const int c0 = (int)w0.shape[0];
-  View a0 = new_view(H / 2, W / 2, c0);
-  {
-    std::vector<float> w27((size_t)27 * c0);
-    for (int o = 0; o < c0; ++o)
-      for (int i = 0; i < 3; ++i)
-        for (int y = 0; y < 3; ++y)
-          for (int x = 0; x < 3; ++x)
-            w27[(size_t)((y * 3 + x) * 3 + i) * c0 + o] = w0.data[(((size_t)o * 3 + i) * 3 + y) * 3 + x];
-    float* dw = (float*)alloc(w27.size() * sizeof(float));
-    GTX_HIP(hipMemcpy(dw, w27.data(), w27.size() * sizeof(float), hipMemcpyHostToDevice));
-    std::vector<float> b(c0, 0.f);
-    if (has("model.0.conv.bias")) b = tensor("model.0.conv.bias").data;
-    float* db = (float*)alloc((size_t)(c0 + 31) / 32 * 32 * sizeof(float));   // zero-filled up to whole 32-channel groups (the MFMA stems read a group's bias unconditionally)
-    GTX_HIP(hipMemcpy(db, b.data(), c0 * sizeof(float), hipMemcpyHostToDevice));
-    Op op;
-    op.kind = Op::STEM;
-    op.name = "model.0.conv";
-    op.family = dtype_ == DT_F16 ? "stem_mfma_kernel" : (fmt_ == DT_F32S ? "stem_split_kernel" : "stem_kernel");
-    op.in = img_;
-    op.out = a0;
-    op.w27 = dw;
-    op.bias = db;
-    if (dtype_ == DT_F16) {
-      const std::vector<uint16_t> pk = pack_stem_weights_f16(w27.data(), c0);
-      void* dp = alloc(pk.size() * 2);
-      GTX_HIP(hipMemcpy(dp, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
-      op.wpk = dp;
-    } else if (fmt_ == DT_F32S) {
-      const std::vector<uint16_t> pk = pack_stem_weights_split(w27.data(), c0, &op.stem_scale);
-      void* dp = alloc(pk.size() * 2);
-      GTX_HIP(hipMemcpy(dp, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
-      op.wpk = dp;
-      if (c0 % 16 == 0) {                       // fuse_stem(): whole 16-channel K chunks of model.1
-        const std::vector<uint16_t> fk = pack_front_weights_split(w27.data(), c0, &op.front_scale);
-        void* fp = alloc(fk.size() * 2);
-        GTX_HIP(hipMemcpy(fp, fk.data(), fk.size() * 2, hipMemcpyHostToDevice));
-        op.front_wpk = fp;
-      }
-    }
-    ops_.push_back(op);
-    layer_views_["model.0.conv"] = a0;
-  }
-
-  auto cout_of = [&](const std::string& n) { return (int)tensor(n + ".weight").shape[0]; };
-  // yolov8.yaml (Detect = model.22 on 15 / 18 / 21) or yolov8-p2.yaml (one more Upsample + Concat + C2f at stride 4 in the neck,
-  // Detect = model.28 on 18 / 21 / 24 / 27): told apart by the tensor names, like the reference's model yaml does
-  const bool p2 = has("model.28.cv2.0.0.conv.weight");
-  auto upsample = [&](const std::string& name, const View& src, const View& dst) {
-    Op op;
-    op.kind = Op::UPSAMPLE;
-    op.name = name;
-    op.family = "upsample2x_kernel";
-    op.in = src;
-    op.out = dst;
-    ops_.push_back(op);
-  };
-  // ---- SPPF (model.9): cv1 -> 3 cascaded pools -> cv2; its output is written into the slice `s9` of the last Concat
-  auto sppf = [&](const View& a8, const View& s9) {
-    const int cm = cout_of("model.9.cv1.conv");
-    View sp = new_view(a8.h, a8.w, 4 * cm);
-    View sp0 = sp.slice(0, cm);
-    conv("model.9.cv1.conv", a8, 1, true, &sp0, nullptr);
-    Op op;
-    op.kind = Op::POOL;
-    op.name = "model.9.m";
-    op.family = "sppf_pool_kernel";
-    op.in = sp0;
-    op.out = sp;
-    ops_.push_back(op);
-    conv("model.9.cv2.conv", sp, 1, true, &s9, nullptr);
-    layer_views_["model.9"] = s9;
-  };
-  std::vector<View> lvl_in;       // the Detect layer's inputs, finest level first
-  std::vector<float> strides;
-  if (!p2) {
-    // ---- backbone ----
-    View a1 = conv("model.1.conv", a0, 2, true, nullptr, nullptr);
-    View a2 = c2f("model.2", a1, true, nullptr);
-    View a3 = conv("model.3.conv", a2, 2, true, nullptr, nullptr);
-    // model.4 output feeds conv5 and Concat(14) = [up13, model.4]
-    const int c4 = cout_of("model.4.cv2.conv"), c6 = cout_of("model.6.cv2.conv");
-    const int c9 = cout_of("model.9.cv2.conv"), c12 = cout_of("model.12.cv2.conv");
-    const int c16 = cout_of("model.16.conv"), c19 = cout_of("model.19.conv");
-    View cat14 = new_view(H / 8, W / 8, c12 + c4);
-    View s4 = cat14.slice(c12, c4);
-    View a4 = c2f("model.4", a3, true, &s4);
-    View a5 = conv("model.5.conv", a4, 2, true, nullptr, nullptr);
-    View cat11 = new_view(H / 16, W / 16, c9 + c6);
-    View s6 = cat11.slice(c9, c6);
-    View a6 = c2f("model.6", a5, true, &s6);
-    View a7 = conv("model.7.conv", a6, 2, true, nullptr, nullptr);
-    View a8 = c2f("model.8", a7, true, nullptr);
-    // SPPF output lives in Concat(20) = [conv19, model.9]
-    View cat20 = new_view(H / 32, W / 32, c19 + c9);
-    View s9 = cat20.slice(c19, c9);
-    sppf(a8, s9);
-    // ---- head ----
-    // torch's Upsample + Concat in front of model.12 / model.15: the split-f16x3 path reads the low-resolution tensor in
-    // place from the C2f's first 1x1 conv (ConvProblem::in2), the other arithmetics write the upsampled copy
-    const bool fuse_up = fmt_ == DT_F32S && c9 % 32 == 0 && c12 % 32 == 0;
-    if (!fuse_up) upsample("model.10", s9, cat11.slice(0, c9));
-    View cat17 = new_view(H / 16, W / 16, c16 + c12);
-    View s12 = cat17.slice(c16, c12);
-    c2f("model.12", cat11, false, &s12, fuse_up ? &s9 : nullptr);
-    if (!fuse_up) upsample("model.13", s12, cat14.slice(0, c12));
-    View a15 = c2f("model.15", cat14, false, nullptr, fuse_up ? &s12 : nullptr);
-    View s16 = cat17.slice(0, c16);
-    conv("model.16.conv", a15, 2, true, &s16, nullptr);
-    View a18 = c2f("model.18", cat17, false, nullptr);
-    View s19 = cat20.slice(0, c19);
-    conv("model.19.conv", a18, 2, true, &s19, nullptr);
-    View a21 = c2f("model.21", cat20, false, nullptr);
-    lvl_in = {a15, a18, a21};
-    strides = {8.f, 16.f, 32.f};
-    det_pfx_ = "model.22";
-  } else {
-    // ---- backbone (as yolov8.yaml); model.2's output also feeds Concat(17) = [up16, model.2] ----
-    const int c2 = cout_of("model.2.cv2.conv"), c4 = cout_of("model.4.cv2.conv"), c6 = cout_of("model.6.cv2.conv");
-    const int c9 = cout_of("model.9.cv2.conv"), c12 = cout_of("model.12.cv2.conv"), c15 = cout_of("model.15.cv2.conv");
-    const int c19 = cout_of("model.19.conv"), c22 = cout_of("model.22.conv"), c25 = cout_of("model.25.conv");
-    View a1 = conv("model.1.conv", a0, 2, true, nullptr, nullptr);
-    View cat17 = new_view(H / 4, W / 4, c15 + c2);
-    View s2 = cat17.slice(c15, c2);
-    View a2 = c2f("model.2", a1, true, &s2);
-    View a3 = conv("model.3.conv", a2, 2, true, nullptr, nullptr);
-    View cat14 = new_view(H / 8, W / 8, c12 + c4);           // [up13, model.4]
-    View s4 = cat14.slice(c12, c4);
-    View a4 = c2f("model.4", a3, true, &s4);
-    View a5 = conv("model.5.conv", a4, 2, true, nullptr, nullptr);
-    View cat11 = new_view(H / 16, W / 16, c9 + c6);          // [up10, model.6]
-    View s6 = cat11.slice(c9, c6);
-    View a6 = c2f("model.6", a5, true, &s6);
-    View a7 = conv("model.7.conv", a6, 2, true, nullptr, nullptr);
-    View a8 = c2f("model.8", a7, true, nullptr);
-    View cat26 = new_view(H / 32, W / 32, c25 + c9);         // [conv25, model.9]
-    View s9 = cat26.slice(c25, c9);
-    sppf(a8, s9);
-    // ---- head: three Upsample + Concat + C2f stages down to stride 4, then three stride-2 Conv + Concat + C2f back up ----
-    const bool fuse_up = fmt_ == DT_F32S && c9 % 32 == 0 && c12 % 32 == 0 && c15 % 32 == 0;
-    if (!fuse_up) upsample("model.10", s9, cat11.slice(0, c9));
-    View cat23 = new_view(H / 16, W / 16, c22 + c12);        // [conv22, model.12]
-    View s12 = cat23.slice(c22, c12);
-    c2f("model.12", cat11, false, &s12, fuse_up ? &s9 : nullptr);
-    if (!fuse_up) upsample("model.13", s12, cat14.slice(0, c12));
-    View cat20 = new_view(H / 8, W / 8, c19 + c15);          // [conv19, model.15]
-    View s15 = cat20.slice(c19, c15);
-    c2f("model.15", cat14, false, &s15, fuse_up ? &s12 : nullptr);
-    if (!fuse_up) upsample("model.16", s15, cat17.slice(0, c15));
-    View a18 = c2f("model.18", cat17, false, nullptr, fuse_up ? &s15 : nullptr);
-    View s19 = cat20.slice(0, c19);
-    conv("model.19.conv", a18, 2, true, &s19, nullptr);
-    View a21 = c2f("model.21", cat20, false, nullptr);
-    View s22 = cat23.slice(0, c22);
-    conv("model.22.conv", a21, 2, true, &s22, nullptr);
-    View a24 = c2f("model.24", cat23, false, nullptr);
-    View s25 = cat26.slice(0, c25);
-    conv("model.25.conv", a24, 2, true, &s25, nullptr);
-    View a27 = c2f("model.27", cat26, false, nullptr);
-    lvl_in = {a18, a21, a24, a27};
-    strides = {4.f, 8.f, 16.f, 32.f};
-    det_pfx_ = "model.28";
-  }
+  const YoloTrunk::Levels trunk = trunk_.build(img_);
+  const std::vector<View>& lvl_in = trunk.in;     // the Detect layer's inputs, finest level first
+  const std::vector<float>& strides = trunk.strides;
+  det_pfx_ = trunk.det_pfx;
   const int nl = (int)lvl_in.size();
   GTX_CHECK(nl <= kMaxLevels, "internal: %d Detect levels", nl);
 
@@ -289,14 +89,14 @@ void Detector::build_graph() {
     for (int q = 0; q < nl; ++q) k32 = k32 && lvl_in[q].c % 32 == 0;
     force_kc_ = fmt_ == DT_F16 ? (k32 ? 32 : 16) : 0;
     force_bn_ = (cb + cc) % 64 == 0 ? 64 : 32;
-    View h1 = conv("__head" + std::to_string(l) + ".s1", lvl_in[l], 1, true, nullptr, nullptr);
+    View h1 = head_conv("__head" + std::to_string(l) + ".s1", lvl_in[l], nullptr);
     View h2 = new_view(h1.h, h1.w, cb + cc);
     View h1b = h1.slice(0, cb), h1c = h1.slice(cb, cc), h2b = h2.slice(0, cb), h2c = h2.slice(cb, cc);
     force_kc_ = fmt_ == DT_F16 ? ((cb % 32 == 0 && cc % 32 == 0) ? 32 : 16) : 0;
     force_bn_ = (cb % 64 == 0 && cc % 64 == 0) ? 64 : 32;
     plain_out_ = true;            // the decode kernels read these two as plain fp32
-    conv(b2 + ".1.conv", h1b, 1, true, &h2b, nullptr);
-    conv(b3 + ".1.conv", h1c, 1, true, &h2c, nullptr);
+    head_conv(b2 + ".1.conv", h1b, &h2b);
+    head_conv(b3 + ".1.conv", h1c, &h2c);
     plain_out_ = false;
     h2.plain = fmt_ == DT_F32S;
     force_kc_ = force_bn_ = 0;
@@ -413,159 +213,6 @@ void Detector::build_graph() {
       g.family = conv_kernel_name(g.cfg);
       ops_.push_back(g);
     }
-}
-
-// model.1.conv (3x3 stride 2, all of its output channels in one cout tile) and model.2.cv1.conv (the 1x1 that is its only
-// consumer) become one launch: ConvProblem::post_w. The 3x3 layer's output is never written; the launch writes the 1x1
-// layer's. GTX_FUSE_FRONT=0 keeps the two launches. YOLOv8 n and s qualify (32 / 64 channels); the wider scales do not.
-void Detector::fuse_front() {
-  if (fmt_ != DT_F32S || !env_flag("GTX_FUSE_FRONT", true)) return;
-  for (size_t i = 0; i + 1 < ops_.size(); ++i) {
-    if (ops_[i].name != "model.1.conv" || ops_[i + 1].name != "model.2.cv1.conv") continue;
-    const Op &a = ops_[i], &b = ops_[i + 1];
-    if (a.kind != Op::CONV || b.kind != Op::CONV || a.grp.count != 1 || b.grp.count != 1) return;
-    const ConvProblem &pa = a.grp.p[0], &pb = b.grp.p[0];
-    const bool ok = a.cfg.variant == 2 && a.cfg.ks == 3 && a.cfg.stride == 2 && pa.Cout == a.cfg.bn && !pa.res &&
-                    (b.cfg.variant == 2 || b.cfg.variant == 6) && b.cfg.ks == 1 && b.cfg.kc == 32 && b.cfg.bn == pb.Cout && pb.Cin == pa.Cout && pb.Cout == pa.Cout &&
-                    pb.in == pa.out && pb.in_cstride == pa.out_cstride && pb.in_coff == pa.out_coff && !pb.res && !pb.in2;
-    if (!ok) return;
-    unfused_ = {a, b};
-    Op f = a;
-    f.name = "model.1.conv+model.2.cv1.conv";
-    ConvProblem& p = f.grp.p[0];
-    p.post_w = pb.wpack; p.post_bias = pb.bias; p.post_scale = pb.acc_scale; p.post_act = pb.act;
-    p.out = pb.out; p.out_cstride = pb.out_cstride; p.out_coff = pb.out_coff; p.out_plain = pb.out_plain;
-    ops_[i] = f;
-    ops_.erase(ops_.begin() + (long)i + 1);
-    return;
-  }
-}
-
-// model.0.conv (the stem) moves into the launch of its only consumer, model.1.conv (already carrying model.2.cv1 when
-// fuse_front() applied): ConvProblem::front_img. The stem's output -- the largest tensor of the network, 236 MB per two
-// 1920 x 1920 frames -- is neither written nor read back; the workgroup recomputes the one-pixel halo of its patch (9.6 %).
-// Built for model.1 in one cout tile and at most two 16-channel K chunks: YOLOv8 n (16 -> 32) and s (32 -> 64).
-// GTX_FUSE_STEM=0 keeps the stem's own launch.
-void Detector::fuse_stem() {
-  if (fmt_ != DT_F32S || !env_flag("GTX_FUSE_STEM", true) || ops_.size() < 2) return;
-  const Op& st = ops_[0];
-  Op& cv = ops_[1];
-  if (st.kind != Op::STEM || cv.kind != Op::CONV || cv.grp.count != 1 || !st.front_wpk) return;
-  ConvProblem& p = cv.grp.p[0];
-  const bool ok = cv.cfg.variant == 2 && cv.cfg.ks == 3 && cv.cfg.stride == 2 && cv.cfg.kc == 16 && cv.cfg.th == 8 && ((cv.cfg.bn == 32 && p.Cin == 16) || (cv.cfg.bn == 64 && p.Cin == 32)) &&
-                  p.Cout <= cv.cfg.bn && !p.res && p.in == st.out.ptr && p.in_cstride == st.out.c && p.in_coff == 0 && p.Cin == st.out.c &&
-                  st.in.h == 2 * st.out.h && st.in.w == 2 * st.out.w && p.H == st.out.h && p.W == st.out.w;
-  if (!ok) return;
-  unfused_.insert(unfused_.begin(), st);
-  p.front_img = st.in.ptr;
-  p.front_w = st.front_wpk;
-  p.front_bias = st.bias;
-  p.front_scale = st.front_scale;
-  p.front_h = st.in.h;
-  p.front_w_px = st.in.w;
-  cv.name = "model.0.conv+" + cv.name;
-  cv.family = "conv_front_split_kernel";
-  ops_.erase(ops_.begin());
-}
-
-// The stem's output and model.1's are written by no launch of the fused forward pass (354 MB per two 1920 x 1920 frames and
-// detector): their buffers are given back here. layer_output() of one of them re-creates them and runs the stand-alone
-// launches (unfused_). Until then every reference to them holds a token that is no device address.
-namespace {
-void swap_ptr(Op& o, const void* from, void* to) {
-  if (o.in.ptr == from) o.in.ptr = to;
-  if (o.out.ptr == from) o.out.ptr = to;
-  for (int i = 0; i < o.grp.count; ++i) {
-    ConvProblem& p = o.grp.p[i];
-    if (p.in == from) p.in = to;
-    if (p.out == from) p.out = to;
-    if (p.res == from) p.res = to;
-    if (p.in2 == from) p.in2 = to;
-  }
-}
-}  // namespace
-
-void Detector::release_hidden_layers() {
-  std::vector<void*> ptrs;
-  for (size_t i = 0; i + 1 < unfused_.size() || (i < unfused_.size() && unfused_[i].kind == Op::STEM); ++i) {
-    const Op& o = unfused_[i];                       // every stand-alone op but the last conv writes a hidden tensor
-    void* out = o.kind == Op::STEM ? o.out.ptr : (o.grp.count == 1 ? o.grp.p[0].out : nullptr);
-    if (out) ptrs.push_back(out);
-  }
-  for (void* ptr : ptrs) {
-    bool live = false;                               // still written or read by a launch of the forward pass?
-    for (const Op& o : ops_) {
-      if (o.kind != Op::CONV && (o.in.ptr == ptr || o.out.ptr == ptr)) live = true;
-      for (int i = 0; i < o.grp.count; ++i) {
-        const ConvProblem& q = o.grp.p[i];
-        const bool reads_in = !q.front_img;          // a front stage computes its input patch from the image instead of loading it
-        if ((reads_in && q.in == ptr) || q.out == ptr || q.res == ptr || q.in2 == ptr) live = true;
-      }
-    }
-    if (live) continue;
-    for (size_t b = 0; b < bufs_.size(); ++b) {
-      if (bufs_[b].p != ptr) continue;
-      void* token = reinterpret_cast<void*>(static_cast<uintptr_t>(16 * (hidden_.size() + 1)));
-      hidden_.push_back({token, bufs_[b].bytes, nullptr});
-      bufs_.erase(bufs_.begin() + (long)b);
-      for (Op& o : unfused_) swap_ptr(o, ptr, token);
-      for (auto& kv : layer_views_)
-        if (kv.second.ptr == ptr) kv.second.ptr = token;
-      break;
-    }
-  }
-}
-
-void Detector::materialize_hidden_layers() {
-  for (Hidden& h : hidden_) {
-    if (h.real) continue;
-    h.real = alloc(h.bytes);
-    for (Op& o : unfused_) swap_ptr(o, h.token, h.real);
-    for (auto& kv : layer_views_)
-      if (kv.second.ptr == h.token) kv.second.ptr = h.real;
-  }
-}
-
-void set_batch_ops(std::vector<Op>& ops, int nb, size_t es, bool pad_skip_on) {
-  for (Op& op : ops) {
-    if (op.kind != Op::CONV) continue;
-    for (int i = 0; i < op.grp.count; ++i) {
-      op.grp.p[i].N = nb;
-      op.grp.p[i].ty_first = pad_skip_on ? op.ty_first[i] : 0;
-      op.grp.p[i].ty_count = pad_skip_on ? op.ty_count[i] : 0;
-    }
-    conv_group_finalize(op.grp, op.cfg);
-    op.flops = 0;
-    op.bytes = 0;
-    for (int i = 0; i < op.grp.count; ++i) {
-      const ConvProblem& p = op.grp.p[i];
-      // the share of the output rows this launch computes (letterbox-padding rows are skipped: plan_pad_skip)
-      const double part = std::min(1.0, (double)p.tiles_y * op.cfg.th / p.Ho);
-      op.flops += part * conv_flops(p, op.cfg.ks);
-      op.bytes += part * ((double)p.N * p.H * p.W * (p.Cin - 0.75 * p.c_split) + (double)p.N * p.Ho * p.Wo * p.Cout) * es +
-                  (double)p.Cout * p.Cin * op.cfg.ks * op.cfg.ks * es;
-      if (p.post_w) {                     // the fused 1x1 layer: its FLOPs and weights; its output replaces the 3x3 layer's (same size)
-        op.flops += part * 2.0 * p.N * p.Ho * p.Wo * (double)p.Cout * p.Cout;
-        op.bytes += (double)p.Cout * p.Cout * es;
-      }
-      if (p.front_img) {                  // the fused stem: its FLOPs; RGB0 bytes are read instead of the stem's output
-        op.flops += part * 2.0 * p.N * p.H * p.W * (double)p.Cin * 27;
-        op.bytes += part * ((double)p.N * p.front_h * p.front_w_px * 4 - (double)p.N * p.H * p.W * p.Cin * es);
-      }
-    }
-  }
-  for (Op& op : ops) {
-    if (op.kind == Op::STEM) {
-      op.flops = 2.0 * nb * op.out.h * op.out.w * op.out.c * 27;
-      op.bytes = (double)nb * ((double)op.in.h * op.in.w * 4 + (double)op.out.h * op.out.w * op.out.c * es);   // RGB0 bytes in
-    } else if (op.kind == Op::POOL) {
-      op.flops = 0;
-      op.bytes = (double)nb * op.in.h * op.in.w * op.in.c * 4 * es;
-    } else if (op.kind == Op::UPSAMPLE) {
-      op.flops = 0;
-      op.bytes = (double)nb * op.in.h * op.in.w * op.in.c * 5 * es;
-    }
-  }
 }
 
 void Detector::set_batch(int nb) {
@@ -701,9 +348,7 @@ void Detector::finalize() {
   GTX_CHECK(!finalized_, "finalize called twice");
   GTX_HIP(hipSetDevice(ctx_->device));
   build_graph();
-  fuse_front();
-  fuse_stem();
-  release_hidden_layers();
+  trunk_.fuse();
   const int N = cfg_.max_batch;
   alloc_outputs();
   // NMS workspace. Candidate capacity = every anchor; sort/NMS capacity = ultralytics max_nms.
@@ -748,22 +393,7 @@ void Detector::finalize() {
   finalized_ = true;
 }
 
-void Detector::run_op(const Op& op, int nb, hipStream_t s) {
-  switch (op.kind) {
-    case Op::CONV:
-      conv_launch(op.grp, op.cfg, s);
-      break;
-    case Op::STEM:
-      launch_stem(dtype_ == DT_F32 ? fmt_ : dtype_, op.in.ptr, nb, op.in.h, op.in.w, op.w27, op.bias, op.wpk, op.out.c, op.out.ptr, op.out.h,
-                  op.out.w, s, op.stem_scale);
-      break;
-    case Op::POOL: launch_sppf_pool(fmt_ == DT_F32S ? DT_F32S : dtype_, op.out.ptr, nb, op.in.h, op.in.w, op.in.c, s); break;
-    case Op::UPSAMPLE:
-      launch_upsample2x(dtype_, op.in.ptr, nb, op.in.h, op.in.w, op.in.c, op.in.cstride, op.in.coff, op.out.ptr,
-                        op.out.cstride, op.out.coff, s);
-      break;
-  }
-}
+void Detector::run_op(const Op& op, int nb, hipStream_t s) { trunk_.run_op(op, nb, s); }
 
 void Detector::run_post(int nb, hipStream_t s) {
   if (sparse_on_) {                                // score gate -> the box branch at the candidates -> their boxes
@@ -858,9 +488,8 @@ void Detector::raw_output(int b, float* out, int* n_anchors, bool logits) {
 }
 
 void Detector::layer_output(int b, const std::string& layer, float* out, int* h, int* w, int* c) {
-  // model.0 / model.1 of a fused front launch are RECOMPUTED below by their stand-alone launches (same products, another
-  // summation order): what comes back is not what the network consumed. Not while a pass is in flight: the launches
-  // would queue behind it and overwrite the buffers it shares with them.
+  // Not while a pass is in flight: the stand-alone launches of the hidden layers would queue behind it and overwrite the
+  // buffers it shares with them.
   GTX_CHECK(!(out && in_flight_), "layer_output while a batch is in flight: call collect first");
   auto it = layer_views_.find(layer);
   if (it == layer_views_.end()) fail(-1, "unknown layer '%s'", layer.c_str());
@@ -870,36 +499,13 @@ void Detector::layer_output(int b, const std::string& layer, float* out, int* h,
     run_dense_box(ctx_->stream);                   // the head's box layers are not part of the forward in sparse mode
     GTX_HIP(hipStreamSynchronize(ctx_->stream));
   }
-  if (out) {
-    // an intermediate the fused launches no longer write (the stem's output, model.1's): run the stand-alone launches up to
-    // it now -- the network input of the last pass is still in HBM. The last entry of unfused_ is a layer the fused launch
-    // does write.
-    int k = -1;
-    for (size_t i = 0; i < unfused_.size(); ++i) {
-      const bool still_written = i + 1 == unfused_.size() && unfused_[i].kind != Op::STEM;   // the fused launch's own output layer
-      if (!still_written && unfused_[i].name == layer) k = (int)i;
-    }
-    if (k >= 0) GTX_CHECK(cur_nb_ > 0, "layer_output('%s'): no forward pass has run yet", layer.c_str());
-    if (k >= 0 && cur_nb_ > 0) {
-      GTX_HIP(hipSetDevice(ctx_->device));
-      materialize_hidden_layers();
-      for (int j = 0; j <= k; ++j) {
-        Op o = unfused_[(size_t)j];
-        if (o.kind == Op::CONV) {
-          for (int i = 0; i < o.grp.count; ++i) o.grp.p[i].N = cur_nb_;
-          conv_group_finalize(o.grp, o.cfg);
-        }
-        run_op(o, cur_nb_, ctx_->stream);
-      }
-      GTX_HIP(hipStreamSynchronize(ctx_->stream));
-    }
-  }
+  if (out) trunk_.recompute_hidden(layer, cur_nb_, ctx_->stream);   // the stem's output, model.1's: not written by the fused front
   if (h) *h = v.h;
   if (w) *w = v.w;
   if (c) *c = v.c;
   if (!out) return;
   GTX_CHECK(b >= 0 && b < cfg_.max_batch, "bad batch slot");
-  GTX_CHECK(reinterpret_cast<uintptr_t>(v.ptr) > 4096, "layer_output('%s'): the layer's buffer was not re-created", layer.c_str());
+  GTX_CHECK(!trunk_.hidden(v.ptr), "layer_output('%s'): the layer's buffer was not re-created", layer.c_str());
   read_view(v, b, out);
 }
 

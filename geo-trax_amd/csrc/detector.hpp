@@ -9,28 +9,9 @@
 #include <string>
 #include <vector>
 
-#include "net_runtime.hpp"
+#include "yolo_trunk.hpp"
 
 namespace gtx {
-
-struct Op : OpInfo {
-  enum Kind { CONV, STEM, POOL, UPSAMPLE } kind = CONV;
-  ConvGroup grp{};       // CONV
-  ConvConfig cfg{};
-  // STEM / POOL / UPSAMPLE parameters
-  View in, out;
-  const float* w27 = nullptr;
-  const float* bias = nullptr;
-  const void* wpk = nullptr;   // fp16 MFMA / split-f16x3 stem weights
-  float stem_scale = 1.f;      // split-f16x3 stem: inverse of the weights' power-of-two scaling
-  const void* front_wpk = nullptr;   // the same weights packed for the front stage of model.1 (ConvProblem::front_w)
-  float front_scale = 1.f;
-  // rows of the output that depend on the frame (Detector::plan_pad_skip), as tile rows per group member; count 0 = all
-  int ty_first[kMaxGroup] = {0}, ty_count[kMaxGroup] = {0};
-};
-
-// N of every conv op (and the rows it computes) and every op's flops / bytes for a pass at batch nb (es: bytes per activation)
-void set_batch_ops(std::vector<Op>& ops, int nb, size_t es, bool pad_skip_on);
 
 class Detector : public DetectorBase {
  public:
@@ -56,29 +37,19 @@ class Detector : public DetectorBase {
   const OpInfo& op_info(size_t i) const override { return ops_[i]; }
   void launch_op(size_t i, int nb, hipStream_t s) override { run_op(ops_[i], nb, s); }
   std::unique_ptr<NetRuntime> make_exact() const override;
-  void release_graph() override { ops_.clear(); unfused_.clear(); }
-  // graph building
-  // up_src: the leading up_src->c channels of x are the 2x nearest upsampling of *up_src and are read from there
-  // (split-f16x3 1x1 convs; ConvProblem::in2) -- the slice of x they would occupy is never written
-  View conv(const std::string& name, const View& x, int stride, bool act, const View* out_slice,
-            const View* residual, const View* up_src = nullptr);
-  View c2f(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src = nullptr);
+  void release_graph() override { ops_.clear(); trunk_.clear(); }
+  // graph building: the trunk (yolo_trunk.hpp), then the Detect head on its outputs
+  View head_conv(const std::string& name, const View& x, const View* out_slice);
   void build_graph();
-  void fuse_front();         // model.1 (3x3 stride 2) + model.2.cv1 (1x1) as one launch on the split-f16x3 path
-  void fuse_stem();          // model.0 (the stem) computed inside model.1's launch: its output never reaches HBM
   void run_op(const Op& op, int nb, hipStream_t s);
   void run_post(int nb, hipStream_t s) override;
   void after_pass(int nb) override;   // the overflow / large-NMS re-run and the appearance vectors' copy
   void set_batch(int nb) override;
 
-  void release_hidden_layers();     // after the fusions: buffers only the stand-alone forms of fused layers write
-  void materialize_hidden_layers(); // ... come back on the first layer_output() that asks for one of them
-  struct Hidden { void* token; size_t bytes; void* real; };
-  std::vector<Hidden> hidden_;
-
   int dtype_;                // activation type in HBM (DT_F16 / DT_F32); fmt_: what the conv kernels compute in (dtype_, or DT_F32S)
   size_t es_;
   std::vector<Op> ops_;
+  YoloTrunk trunk_;          // emits the backbone + neck into ops_ and launches its ops
   int force_kc_ = 0;         // K chunk forced on the convs being built (grouped head stages)
   int force_bn_ = 0;         // cout tile forced on them
 
@@ -86,7 +57,6 @@ class Detector : public DetectorBase {
   NmsBuffers nms_{};
   DevBuf raw_;               // debug raw output
   bool plain_out_ = false;   // convs being built write plain fp32 (head stage 2)
-  std::vector<Op> unfused_;  // the stand-alone forms of fused ops (layer_output of an intermediate runs them on demand)
   FeatLevels feat_levels_{};
   // sparse box branch (head_sparse.hip): on for the split-f16x3 path when the head's layers have the 16x16x32 kernel's weight images
   static constexpr int kSparseCap = 8192;   // candidates per image its buffer holds

@@ -61,6 +61,21 @@ void* NetRuntime::alloc(size_t bytes) {
   return bufs_.back().p;
 }
 
+void NetRuntime::repoint_layer_views(const void* from, void* to) {
+  for (auto& kv : layer_views_)
+    if (kv.second.ptr == from) kv.second.ptr = to;
+}
+
+size_t NetRuntime::release_buffer(const void* p) {
+  for (size_t b = 0; b < bufs_.size(); ++b) {
+    if (bufs_[b].p != p) continue;
+    const size_t bytes = bufs_[b].bytes;
+    bufs_.erase(bufs_.begin() + (long)b);
+    return bytes;
+  }
+  return 0;
+}
+
 float* NetRuntime::upload(const std::vector<float>& v) {
   float* d = (float*)alloc(std::max<size_t>(v.size(), 1) * sizeof(float));
   if (!v.empty()) GTX_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));

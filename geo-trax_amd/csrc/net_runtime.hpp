@@ -63,12 +63,18 @@ struct KernelTable {
   void add(const std::string& label, int n, float t, double f, double b);
 };
 
+class YoloTrunk;
+
 class NetRuntime {
  public:
   NetRuntime(gtx_ctx* ctx, int fmt, size_t view_es, int max_batch) : ctx_(ctx), fmt_(fmt), view_es_(view_es), max_batch_(max_batch) {}
   virtual ~NetRuntime();
   NetRuntime(const NetRuntime&) = delete;
   NetRuntime& operator=(const NetRuntime&) = delete;
+  // The YOLOv8 trunk (yolo_trunk.hpp) is a part of the net that holds it, not a family: it builds through the protected calls
+  // below (tensor / has, alloc / new_view, emit_named_conv, set_layer_view, repoint_layer_views, release_buffer, format, device)
+  // and touches no data member.
+  friend class YoloTrunk;
   void set_tensor(const std::string& name, const float* data, int ndim, const int64_t* shape);
   // split-f16x3 path: true when some activation of a collected pass (since the last call with clear) had to be clamped to fp16's
   // range on its way into the pair format. The pass is then re-run on an exact-fp32 twin built from the same tensors and every
@@ -120,8 +126,24 @@ class NetRuntime {
     layer_views_[name] = out;
     return out;
   }
+  // The same from the tensors "<name>.weight" (OIHW, square kernel) and "<name>.bias" (optional); fills a.out_pixels.
+  template <class OpT>
+  View emit_named_conv(std::vector<OpT>& ops, const std::string& name, const View& x, ConvArgs a) {
+    const HostTensor& w = tensor(name + ".weight");
+    GTX_CHECK(w.shape.size() == 4 && w.shape[2] == w.shape[3], "%s: expected OIHW square kernel", name.c_str());
+    const int cout = (int)w.shape[0], cin = (int)w.shape[1], ks = (int)w.shape[2];
+    a.out_pixels = (long)x.n * ((x.h + 2 * (ks / 2) - ks) / a.stride + 1) * ((x.w + 2 * (ks / 2) - ks) / a.stride + 1);
+    return emit_conv(ops, name, w.data.data(), cout, cin, ks, bias_of(name, cout), x, a);
+  }
   // a family's rule on the configuration conv_pick_config chose, applied before the weights are packed
   virtual void conv_config_rule(const std::string& name, ConvConfig& cfg) const { (void)name; (void)cfg; }
+
+  // ---- the layers layer_output() can read, by module path
+  void set_layer_view(const std::string& name, const View& v) { layer_views_[name] = v; }
+  void repoint_layer_views(const void* from, void* to);   // every layer on buffer `from` now points at `to`
+  size_t release_buffer(const void* p);                    // gives arena buffer p back early: its size (0: p is none of them)
+  int format() const { return fmt_; }
+  int device() const { return ctx_->device; }
 
   // ---- layer v of batch slot `slot` as fp32 [h][w][c] (pair format, fp16 or fp32 per the net's format and v.plain)
   void read_view(const View& v, int slot, float* out) const;

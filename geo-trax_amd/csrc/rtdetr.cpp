@@ -1,6 +1,6 @@
-// RT-DETR graph builder + executor. Layer topology follows ultralytics' cfg/models/rt-detr/rtdetr-l.yaml (backbone 0-9:
-// HGStem, HGBlock x 6 with DWConv downsampling; head 10-27: AIFI on P5, CCFM with RepC3; 28: RTDETRDecoder); channel widths,
-// class count, decoder depth and block lengths are read off the tensor shapes.
+// RT-DETR graph builder + executor (rtdetr.hpp). rtdetr-l.yaml: backbone 0-9 (HGStem, HGBlock x 6 with DWConv downsampling), head
+// 10-27 (AIFI on P5, CCFM with RepC3), 28: RTDETRDecoder. yolov8-rtdetr.yaml: the YOLOv8 trunk 0-21 (yolo_trunk.cpp), 22:
+// RTDETRDecoder. Channel widths, class count, decoder depth and block lengths are read off the tensor shapes.
 #include "rtdetr.hpp"
 #include "split_format.hpp"
 
@@ -13,9 +13,10 @@ RtMap rt_map(const View& v) { return RtMap{v.ptr, v.h, v.w, v.cstride, v.coff, v
 }  // namespace
 
 // half: fp16 maps and weights on the fp16 MFMA convolutions (fp32 accumulate); the token side (AIFI, the decoder's queries) stays fp32.
-// Every map is allocated at 4 bytes per element.
+// rtdetr-l allocates every map at 4 bytes per element; the YOLOv8 trunk's maps take its activation type's size (build_graph).
 RtDetr::RtDetr(gtx_ctx* ctx, const gtx_det_config& cfg)
-    : DetectorBase(ctx, cfg, cfg.half ? DT_F16 : (cfg.fp32_split ? DT_F32S : DT_F32), 4, DT_F32) {
+    : DetectorBase(ctx, cfg, cfg.half ? DT_F16 : (cfg.fp32_split ? DT_F32S : DT_F32), 4, DT_F32),
+      trunk_(*this, trunk_ops_, cfg.half ? DT_F16 : DT_F32) {
   GTX_CHECK(!cfg.obj_feats, "RT-DETR: appearance vectors (obj_feats) are not implemented");
   // RTDETRPredictor.pre_transform: LetterBox(imgsz, auto=False, scale_fill=True) -- the frame is stretched to the square, no padding
   lb_ = Letterbox{};
@@ -36,8 +37,9 @@ void RtDetr::conv_config_rule(const std::string& name, ConvConfig& cfg) const {
   GTX_CHECK(cfg.variant != 3 && cfg.variant != 4, "RT-DETR does not run on the Winograd kernels (unset GTX_WINO)");
 }
 
+// Token rows are fp32 on every path, whatever a map element takes (2 bytes under half for the YOLOv8 trunk's maps).
 float* RtDetr::new_tokens(int rows_per_image, int ld, const std::string& name) {
-  View v = new_view(1, rows_per_image, ld, true);
+  View v{alloc((size_t)max_batch_ * rows_per_image * ld * sizeof(float)), max_batch_, 1, rows_per_image, ld, 0, ld, true};
   if (!name.empty()) layer_views_[name] = v;
   return (float*)v.ptr;
 }
@@ -211,24 +213,33 @@ std::vector<float> part_of(const std::vector<float>& v, int a, int b) { return s
 
 void RtDetr::build_graph() {
   const int S = lb_.net_h;
-  img_ = new_view(S, S, 4);
-  img_.plain = true;                                        // RGB0 bytes, really: [N][S][S][4] u8 in a buffer sized for fp32 (kept simple)
-  alloc_sat_flag();
   if (has("rtdetr.meta")) {
     const auto& m = tensor("rtdetr.meta").data;
     GTX_CHECK(m.size() >= 4, "rtdetr.meta: [heads, points, queries, encoder heads] expected");
     nh_ = (int)m[0]; npts_ = (int)m[1]; nq_ = (int)m[2]; enc_heads_ = (int)m[3];
   }
-  const std::string D = "model.28";
-  nc_ = (int)tensor(D + ".enc_score_head.weight").shape[0];
-  hd_ = (int)tensor(D + ".enc_score_head.weight").shape[1];
-  ncp_ = (nc_ + 15) / 16 * 16;
-  GTX_CHECK(nc_ == cfg_.nc, "RT-DETR score head has %d classes, the configuration says %d", nc_, cfg_.nc);
-  GTX_CHECK(nq_ >= 1 && nq_ <= 512 && hd_ % nh_ == 0 && hd_ % 16 == 0, "RT-DETR decoder: %d queries, width %d, %d heads", nq_, hd_, nh_);
-  ndl_ = 0;
-  while (has(D + ".decoder.layers." + std::to_string(ndl_) + ".linear1.weight")) ++ndl_;
-  GTX_CHECK(ndl_ >= 1, "RT-DETR: no decoder layers among the tensors");
+  // yolov8-rtdetr.yaml: the YOLOv8 detector's trunk under its storage conventions (maps of its activation type, fp16 under half,
+  // where rtdetr-l allocates 4 bytes per element), so that model.15 / 18 / 21 are that detector's bit for bit
+  yolo_ = has("model.0.conv.weight");
+  if (yolo_) view_es_ = dtype_size(cfg_.half ? DT_F16 : DT_F32);
+  img_ = new_view(S, S, 4);
+  img_.plain = !yolo_;                                      // HGStem: RGB0 bytes, really: [N][S][S][4] u8 in a buffer sized for fp32 (kept simple)
+  alloc_sat_flag();
+  View feats[3];
+  if (yolo_) {
+    const YoloTrunk::Levels lv = trunk_.build(img_);
+    GTX_CHECK(lv.in.size() == 3 && lv.det_pfx == "model.22" && has("model.22.enc_score_head.weight"),
+              "YOLOv8-RTDETR: the decoder must be model.22 on model.15 / 18 / 21 (yolov8-rtdetr.yaml)");
+    for (int l = 0; l < 3; ++l) feats[l] = lv.in[l];
+    build_decoder("model.22", feats);
+  } else {
+    build_hgnet(feats);
+    build_decoder("model.28", feats);
+  }
+}
 
+void RtDetr::build_hgnet(View feats[3]) {
+  const int S = lb_.net_h;
   // ---- HGStem (model.0)
   const HostTensor& w1 = tensor("model.0.stem1.conv.weight");
   GTX_CHECK(w1.shape.size() == 4 && w1.shape[1] == 3 && w1.shape[2] == 3, "model.0.stem1 must be a 3x3 conv on 3 channels");
@@ -392,9 +403,21 @@ void RtDetr::build_graph() {
     conv("model.25.conv", x24, 2, 1, &d);
   }
   View x27 = repc3("model.27", cat27);
+  feats[0] = x21; feats[1] = x24; feats[2] = x27;
+}
 
-  // ---- RTDETRDecoder (model.28)
-  const View feat[3] = {x21, x24, x27};
+void RtDetr::build_decoder(const std::string& D, const View feats[3]) {
+  nc_ = (int)tensor(D + ".enc_score_head.weight").shape[0];
+  hd_ = (int)tensor(D + ".enc_score_head.weight").shape[1];
+  ncp_ = (nc_ + 15) / 16 * 16;
+  GTX_CHECK(nc_ == cfg_.nc, "RT-DETR score head has %d classes, the configuration says %d", nc_, cfg_.nc);
+  GTX_CHECK(nq_ >= 1 && nq_ <= 512 && hd_ % nh_ == 0 && hd_ % 16 == 0, "RT-DETR decoder: %d queries, width %d, %d heads", nq_, hd_, nh_);
+  ndl_ = 0;
+  while (has(D + ".decoder.layers." + std::to_string(ndl_) + ".linear1.weight")) ++ndl_;
+  GTX_CHECK(ndl_ >= 1, "RT-DETR: no decoder layers among the tensors");
+
+  // ---- RTDETRDecoder: input_proj.l reads level l at its own width (model.21 / 24 / 27 of rtdetr-l, model.15 / 18 / 21 of YOLOv8-RTDETR)
+  const View* feat = feats;
   const int LP = 3 * npts_;
   View proj[3], val[3], enc[3], score[3];
   std::vector<float> wv((size_t)ndl_ * hd_ * hd_), bv((size_t)ndl_ * hd_);     // the six layers' value_proj stacked: one conv per level
@@ -564,6 +587,7 @@ void RtDetr::build_graph() {
 
 void RtDetr::set_batch(int nb) {
   if (nb == cur_nb_) return;
+  set_batch_ops(trunk_ops_, nb, view_es_, false);
   for (Op& op : ops_) {
     if (op.kind != Op::CONV) {
       op.flops = op.img_flops * nb;
@@ -583,6 +607,7 @@ void RtDetr::finalize() {
   GTX_CHECK(!finalized_, "finalize called twice");
   GTX_HIP(hipSetDevice(ctx_->device));
   build_graph();
+  if (yolo_) trunk_.fuse();
   const int N = cfg_.max_batch;
   alloc_outputs();
   class_mask_[0] = class_mask_[1] = cfg_.n_classes == 0 ? ~0ull : 0ull;
@@ -647,11 +672,13 @@ void RtDetr::layer_output(int b, const std::string& layer, float* out, int* h, i
   auto it = layer_views_.find(layer);
   if (it == layer_views_.end()) fail(-1, "unknown layer '%s'", layer.c_str());
   const View& v = it->second;
+  if (out && yolo_) trunk_.recompute_hidden(layer, cur_nb_, ctx_->stream);   // the stem's output, model.1's: not written by the fused front
   if (h) *h = v.h;
   if (w) *w = v.w;
   if (c) *c = v.c;
   if (!out) return;
   GTX_CHECK(b >= 0 && b < cfg_.max_batch, "bad batch slot");
+  GTX_CHECK(!trunk_.hidden(v.ptr), "layer_output('%s'): the layer's buffer was not re-created", layer.c_str());
   read_view(v, b, out);
 }
 

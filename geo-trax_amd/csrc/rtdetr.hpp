@@ -1,7 +1,11 @@
-// RT-DETR detector runtime (rtdetr-l topology; widths, class count and layer counts read off the tensors): builds the layer
-// graph from ultralytics-named fused tensors and runs preprocess -> HGNetv2 backbone -> AIFI + CCFM encoder -> query
-// selection -> deformable-attention decoder -> score / box stage on a HIP stream. Stands in for what ultralytics' RTDETR
-// predictor does underneath model.track() when the model's yaml names RT-DETR (geotrax/extract.py:222-225, :153).
+// RT-DETR detector runtime: builds the layer graph from ultralytics-named fused tensors and runs preprocess -> trunk -> query
+// selection -> deformable-attention decoder -> score / box stage on a HIP stream. Stands in for what ultralytics' RTDETR predictor
+// does underneath model.track() when the model's yaml names RT-DETR (geotrax/extract.py:222-225, :153). Two topologies, told apart
+// by the tensor names:
+//   rtdetr-l.yaml       HGNetv2 backbone, AIFI + CCFM encoder (model.0-27), RTDETRDecoder = model.28
+//   yolov8-rtdetr.yaml  the YOLOv8 backbone + neck (model.0-21, yolo_trunk.hpp: the YOLOv8 detector's own trunk, under its storage
+//                       conventions), RTDETRDecoder = model.22 on model.15 / 18 / 21
+// Widths, class count and layer counts are read off the tensors.
 //
 // Convolutions (and the per-anchor linear layers, which are 1x1 convolutions on the three feature levels) run on the
 // detector's MFMA kernels in the activation format of the run (split-f16x3 pair format by default, exact fp32 with
@@ -44,11 +48,14 @@ class RtDetr : public DetectorBase {
     double img_flops = 0, img_bytes = 0;   // ops other than CONV: per image (set_batch scales them to the pass)
   };
 
-  size_t op_count() const override { return ops_.size(); }
-  const OpInfo& op_info(size_t i) const override { return ops_[i]; }
-  void launch_op(size_t i, int nb, hipStream_t s) override { run_op(ops_[i], nb, s); }
+  // the YOLOv8 trunk's launches (yolov8-rtdetr) come first, then the family's own
+  size_t op_count() const override { return trunk_ops_.size() + ops_.size(); }
+  const OpInfo& op_info(size_t i) const override { return i < trunk_ops_.size() ? (const OpInfo&)trunk_ops_[i] : ops_[i - trunk_ops_.size()]; }
+  void launch_op(size_t i, int nb, hipStream_t s) override {
+    if (i < trunk_ops_.size()) trunk_.run_op(trunk_ops_[i], nb, s); else run_op(ops_[i - trunk_ops_.size()], nb, s);
+  }
   std::unique_ptr<NetRuntime> make_exact() const override;
-  void release_graph() override { ops_.clear(); }
+  void release_graph() override { ops_.clear(); trunk_ops_.clear(); trunk_.clear(); }
   void conv_config_rule(const std::string& name, ConvConfig& cfg) const override;
   float* new_tokens(int rows_per_image, int ld, const std::string& name);
   // graph building
@@ -65,11 +72,16 @@ class RtDetr : public DetectorBase {
                 int rows, int act, const float* res, int ldr, float* y, int ldy, const std::string& out_name);
   float* layernorm_tokens(const std::string& name, const float* x, int rows, int C, const std::string& out_name, const View* map_out = nullptr);
   void build_graph();
+  void build_hgnet(View feats[3]);                  // rtdetr-l: HGStem .. CCFM; feats = model.21 / 24 / 27
+  void build_decoder(const std::string& D, const View feats[3]);   // the RTDETRDecoder at prefix D on three maps, finest first
   void run_op(const Op& op, int nb, hipStream_t s);
   void run_post(int nb, hipStream_t s) override;
   void set_batch(int nb) override;
 
   std::vector<Op> ops_;
+  bool yolo_ = false;                // yolov8-rtdetr.yaml: the YOLOv8 trunk
+  std::vector<gtx::Op> trunk_ops_;
+  YoloTrunk trunk_;
   int nh_ = 8, npts_ = 4, nq_ = 300, enc_heads_ = 8, hd_ = 256, nc_ = 0, ncp_ = 0, ndl_ = 0;
 
   // post stage

@@ -1,0 +1,74 @@
+// The YOLOv8 trunk: ultralytics' yolov8.yaml backbone + neck (model.0-21) or yolov8-p2.yaml's (model.0-27), everything in front of
+// the Detect layer. One builder for every family that runs it: the YOLOv8 / P2 detector (Detect on its outputs, detector.cpp)
+// and YOLOv8-RTDETR (an RTDETRDecoder on model.15 / 18 / 21, rtdetr.cpp). It emits the trunk's launches into the caller's op
+// list, owns the fused front (stem + model.1 + model.2.cv1 in one launch on the split-f16x3 path) and the stand-alone forms it
+// hides, and launches its four op kinds.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "net_runtime.hpp"
+
+namespace gtx {
+
+struct Op : OpInfo {
+  enum Kind { CONV, STEM, POOL, UPSAMPLE } kind = CONV;
+  ConvGroup grp{};       // CONV
+  ConvConfig cfg{};
+  // STEM / POOL / UPSAMPLE parameters
+  View in, out;
+  const float* w27 = nullptr;
+  const float* bias = nullptr;
+  const void* wpk = nullptr;   // fp16 MFMA / split-f16x3 stem weights
+  float stem_scale = 1.f;      // split-f16x3 stem: inverse of the weights' power-of-two scaling
+  const void* front_wpk = nullptr;   // the same weights packed for the front stage of model.1 (ConvProblem::front_w)
+  float front_scale = 1.f;
+  // rows of the output that depend on the frame (Detector::plan_pad_skip), as tile rows per group member; count 0 = all
+  int ty_first[kMaxGroup] = {0}, ty_count[kMaxGroup] = {0};
+};
+
+// N of every conv op (and the rows it computes) and every op's flops / bytes for a pass at batch nb (es: bytes per activation)
+void set_batch_ops(std::vector<Op>& ops, int nb, size_t es, bool pad_skip_on);
+
+class YoloTrunk {
+ public:
+  // dtype: the activation type in HBM (DT_F16 / DT_F32); the net's format (DT_F32S on the split path) is what the convs compute in
+  YoloTrunk(NetRuntime& net, std::vector<Op>& ops, int dtype) : net_(net), ops_(ops), dtype_(dtype) {}
+
+  struct Levels {
+    std::vector<View> in;        // the Detect layer's inputs, finest level first
+    std::vector<float> strides;
+    std::string det_pfx;         // where the yaml puts Detect: model.22 (yolov8.yaml) or model.28 (yolov8-p2.yaml)
+  };
+  // Emits model.0 .. the last neck C2f on img ([N][H][W][4] RGB0 bytes). The P2 graph is chosen when the tensors hold its Detect.
+  Levels build(const View& img);
+  // One Conv op (SiLU). up_src: the leading up_src->c channels of x are the 2x nearest upsampling of *up_src and are read from
+  // there (split-f16x3 1x1 convs; ConvProblem::in2) -- the slice of x they would occupy is never written.
+  View conv(const std::string& name, const View& x, int stride, const View* out_slice, const View* residual = nullptr,
+            const View* up_src = nullptr);
+  // After the whole graph is built: fuse_front, fuse_stem, then the buffers only the stand-alone forms of fused layers write go back.
+  void fuse();
+  void run_op(const Op& op, int nb, hipStream_t s) const;
+  // layer_output of a layer the fused launches do not write (the stem's output, model.1's): its buffer is re-created and the
+  // stand-alone launches run up to it on the input of the last pass (nb images). False for every other layer.
+  bool recompute_hidden(const std::string& layer, int nb, hipStream_t s);
+  // p is the placeholder of a released buffer that no layer_output() has re-created yet (no device address)
+  bool hidden(const void* p) const;
+  void clear() { unfused_.clear(); hidden_.clear(); }
+
+ private:
+  View c2f(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src = nullptr);
+  void fuse_front();         // model.1 (3x3 stride 2) + model.2.cv1 (1x1) as one launch on the split-f16x3 path
+  void fuse_stem();          // model.0 (the stem) computed inside model.1's launch: its output never reaches HBM
+  void release_hidden_layers();
+  void materialize_hidden_layers();
+
+  NetRuntime& net_;
+  std::vector<Op>& ops_;
+  int dtype_;
+  std::vector<Op> unfused_;  // the stand-alone forms of fused ops (layer_output of an intermediate runs them on demand)
+  struct Hidden { void* token; size_t bytes; void* real; };
+  std::vector<Hidden> hidden_;
+};
+
+}  // namespace gtx

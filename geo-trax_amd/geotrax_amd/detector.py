@@ -55,16 +55,18 @@ class Detector:
         if fp32_split is None:
             fp32_split = os.environ.get("GTX_FP32_SPLIT", "1" if FP32_SPLIT_DEFAULT else "0") == "1"
         self.fp32_split = bool(fp32_split) and not half
-        self.ctx = ctx or _lib.default_context()
-        lib = self.ctx.lib
-        from .weights import is_rtdetr, is_yolov8_p2
+        from .weights import detector_topology
 
-        self.rtdetr = is_rtdetr(tensors)     # the graph the tensors describe picks the detector family (reference: the model's yaml, extract.py:222-225)
+        # the graph the tensors describe picks the detector family (reference: the model's yaml, extract.py:222-225): the RTDETR
+        # predictor for rtdetr-l and yolov8-rtdetr (gtx_det_config.arch = 1; the library tells the two trunks apart by the names)
+        self.graph, head = detector_topology(tensors)
+        self.rtdetr = self.graph in ("rtdetr-l", "yolov8-rtdetr")
         if self.rtdetr and obj_feats:
             raise NotImplementedError("RT-DETR: obj_feats (ReID `model: auto`) is not implemented")
-        self.p2 = not self.rtdetr and is_yolov8_p2(tensors)   # yolov8-p2.yaml: a fourth Detect level at stride 4, Detect = model.28
-        nc = int(tensors["model.28.enc_score_head.weight" if self.rtdetr else
-                         "model.28.cv3.0.2.weight" if self.p2 else "model.22.cv3.0.2.weight"].shape[0])
+        self.p2 = self.graph == "yolov8-p2"   # yolov8-p2.yaml: a fourth Detect level at stride 4, Detect = model.28
+        nc = int(tensors[head + (".enc_score_head.weight" if self.rtdetr else ".cv3.0.2.weight")].shape[0])
+        self.ctx = ctx or _lib.default_context()
+        lib = self.ctx.lib
         cfg = DetConfig(imgsz=imgsz, conf=conf, iou=iou, max_det=max_det, agnostic_nms=int(agnostic_nms),
                         half=int(half), rect=int(rect), nc=nc, n_classes=0, max_batch=max_batch,
                         frame_h=frame_hw[0], frame_w=frame_hw[1], fp32_split=int(self.fp32_split), obj_feats=int(bool(obj_feats)), arch=int(self.rtdetr))
@@ -217,7 +219,7 @@ class Detector:
         return out
 
     def layer_output_int(self, layer: str, b: int = 0) -> np.ndarray:
-        """An integer read-back (RT-DETR's selected anchor indices, layer 'model.28.topk')."""
+        """An integer read-back (RT-DETR's selected anchor indices, layer 'model.28.topk'; 'model.22.topk' for YOLOv8-RTDETR)."""
         return self.layer_output(layer, b).view(np.int32)
 
     def layer_output(self, layer: str, b: int = 0) -> np.ndarray:
@@ -236,8 +238,9 @@ class Detector:
         return self.profile(nb=0, iters=0)
 
     def profile(self, nb: int = 1, iters: int = 5) -> list[dict]:
-        """Per-kernel-family totals of `iters` forward passes (HIP events around every launch)."""
-        cap = 64
+        """Per-kernel-family totals of `iters` forward passes (HIP events around every launch); with GTX_PROFILE_PER_OP set, one
+        row per launch. The C call fills at most `cap` rows: a table that reaches it is refused rather than returned cut off."""
+        cap = 4096                            # per launch: 171 rows for YOLOv8s-RTDETR, a few hundred for rtdetr-l
         names = C.create_string_buffer(cap * 96)
         launches = np.zeros(cap, np.int32)
         ms = np.zeros(cap, np.float32)
@@ -246,6 +249,8 @@ class Detector:
         n = C.c_int()
         check(self.ctx.lib.gtx_detector_profile(self.handle, nb, iters, cap, names, ptr(launches), ptr(ms), ptr(flops),
                                                 ptr(nbytes), C.byref(n)))
+        if n.value >= cap:
+            raise RuntimeError(f"profile: the table fills all {cap} rows and may be cut off")
         out = []
         for i in range(n.value):
             nm = names.raw[i * 96:(i + 1) * 96].split(b"\0")[0].decode()

@@ -119,17 +119,17 @@ class YOLO:
             side = p.with_suffix(".names.yaml")
             if side.is_file():
                 self.names = {int(k): str(v) for k, v in yaml.safe_load(side.read_text()).items()}
-        from .weights import is_rtdetr, is_yolov8_p2
+        from .weights import detector_topology
 
-        self.is_rtdetr = is_rtdetr(self.tensors)
-        self.is_p2 = not self.is_rtdetr and is_yolov8_p2(self.tensors)
-        nc = int(self.tensors["model.28.enc_score_head.weight" if self.is_rtdetr else
-                              "model.28.cv3.0.2.weight" if self.is_p2 else "model.22.cv3.0.2.weight"].shape[0])
+        graph, head = detector_topology(self.tensors)     # refuses an RT-DETR layout this build does not run
+        self.is_rtdetr = graph in ("rtdetr-l", "yolov8-rtdetr")
+        self.is_p2 = graph == "yolov8-p2"
+        nc = int(self.tensors[head + (".enc_score_head.weight" if self.is_rtdetr else ".cv3.0.2.weight")].shape[0])
         if not self.names:
             self.names = {i: str(i) for i in range(nc)}
         self.model = self            # ultralytics exposes .model.yaml_file; keep attribute access harmless
         # the reference reads this attribute to swap YOLO for RTDETR (extract.py:223-225); here one class serves both graphs
-        self.yaml_file = "rtdetr-l.yaml" if self.is_rtdetr else "yolov8-p2.yaml" if self.is_p2 else "yolov8.yaml"
+        self.yaml_file = graph + ".yaml"
         self._det: Detector | None = None
         self._det_key = None
         self._tracker: Tracker | None = None

@@ -137,10 +137,16 @@ def synthetic_yolov8(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: flo
     then vary smoothly over neighbouring anchors, so the
     anchors that clear the confidence threshold come in clusters of several per object and NMS has boxes to
     suppress -- the load SURVEY.md 8d.2 asks for (1-3 k candidates in ~132 clusters) instead of isolated ones."""
-    rng = np.random.default_rng(seed)
+    return _draw_yolov8(np.random.default_rng(seed), yolov8_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias,
+                        box_weight_scale, smooth_cls)
+
+
+def _draw_yolov8(rng, specs, cls_bias: float = -4.0, gain: float = 1.7, box_decay: float | tuple = 0.3, level_bias: tuple = (0.0, 0.0, 0.0),
+                 box_weight_scale: float = 0.3, smooth_cls: bool | int = False) -> dict[str, np.ndarray]:
+    """synthetic_yolov8's draws, layer by layer in spec order from `rng` (synthetic_yolov8_rtdetr draws its trunk with it)."""
     decay = np.broadcast_to(np.asarray(box_decay, dtype=np.float64), (4,))
     t: dict[str, np.ndarray] = {}
-    for name, shape, has_act in yolov8_layer_specs(scale, nc):
+    for name, shape, has_act in specs:
         fan_in = shape[1] * shape[2] * shape[3]
         g = gain if has_act else 1.0
         t[name + ".weight"] = (rng.standard_normal(shape) * (g / np.sqrt(fan_in))).astype(np.float32)
@@ -245,14 +251,41 @@ def calibrate_cls_bias(tensors: dict[str, np.ndarray], raw_logits: np.ndarray, c
     return out
 
 
-# --------------------------------------------------------------------------- RT-DETR (rtdetr-l topology)
+# --------------------------------------------------------------------------- RT-DETR (rtdetr-l and yolov8-rtdetr topologies)
 # The reference swaps YOLO for RTDETR when the model's yaml says so (geotrax/extract.py:222-225). Tensor names are ultralytics'
 # state_dict names of cfg/models/rt-detr/rtdetr-l.yaml; load_weights() brings a checkpoint to the fused form the library and the
 # oracle read: Conv+BN folded (fold_bn), RepConv's 3x3 + 1x1 pair fused into `.conv` (fuse_repconv), the decoder's
 # Sequential(Conv2d, BatchNorm2d) input projections folded into `.0.weight` / `.0.bias` (fold_input_proj).
 
 def is_rtdetr(tensors: dict) -> bool:
-    return any(k.startswith("model.28.decoder.layers.") for k in tensors)
+    """True when the tensors hold an RTDETRDecoder (`model.<k>.decoder.layers.*`, whatever k): the RTDETR predictor family
+    (stretch to the square, no NMS, the 300-query score stage). Which RT-DETR graph it is: detector_topology()."""
+    for k in tensors:
+        parts = k.split(".", 4)
+        if len(parts) == 5 and parts[0] == "model" and parts[1].isdigit() and parts[2:4] == ["decoder", "layers"]:
+            return True
+    return False
+
+
+RTDETR_TOPOLOGIES = ("rtdetr-l (HGNetv2 + AIFI + CCFM, RTDETRDecoder = model.28)",
+                     "yolov8-rtdetr (the YOLOv8 backbone + neck model.0-21, RTDETRDecoder = model.22)")
+
+
+def detector_topology(tensors: dict) -> tuple[str, str]:
+    """(graph, head prefix) of a detector checkpoint, read off the tensor names the way the reference reads its model yaml:
+    ("yolov8", "model.22"), ("yolov8-p2", "model.28"), ("rtdetr-l", "model.28") or ("yolov8-rtdetr", "model.22"). An RT-DETR
+    layout other than those two (rtdetr-x with its decoder at model.32, ResNet backbones, ...) raises NotImplementedError."""
+    if not is_rtdetr(tensors):
+        return ("yolov8-p2", "model.28") if is_yolov8_p2(tensors) else ("yolov8", "model.22")
+    decs = sorted({k.split(".")[1] for k in tensors if k.startswith("model.") and ".decoder.layers." in k and k.split(".")[2] == "decoder"})
+    has = lambda pfx: any(k.startswith(pfx) for k in tensors)
+    if decs == ["28"] and has("model.0.stem1."):
+        return "rtdetr-l", "model.28"
+    if decs == ["22"] and "model.0.conv.weight" in tensors and has("model.9.cv1.") and has("model.21.cv2."):
+        return "yolov8-rtdetr", "model.22"
+    where = ", ".join(f"model.{d}" for d in decs)
+    raise NotImplementedError(f"RT-DETR checkpoint with its decoder at {where}: only {RTDETR_TOPOLOGIES[0]} and "
+                              f"{RTDETR_TOPOLOGIES[1]} are implemented")
 
 
 def fuse_repconv(t: dict[str, np.ndarray]) -> dict[str, np.ndarray]:
@@ -268,7 +301,8 @@ def fuse_repconv(t: dict[str, np.ndarray]) -> dict[str, np.ndarray]:
             continue
         w = w3.astype(np.float64).copy()
         w[:, :, 1, 1] += w1[:, :, 0, 0].astype(np.float64)
-        b = t.get(p + ".conv1.conv.bias", 0).astype(np.float64) + t.get(p + ".conv2.conv.bias", 0).astype(np.float64)
+        zero = np.zeros(w3.shape[0], np.float32)
+        b = t.get(p + ".conv1.conv.bias", zero).astype(np.float64) + t.get(p + ".conv2.conv.bias", zero).astype(np.float64)
         for s in (".conv1.conv.weight", ".conv1.conv.bias", ".conv2.conv.weight", ".conv2.conv.bias"):
             out.pop(p + s, None)
         out[p + ".conv.weight"], out[p + ".conv.bias"] = w.astype(np.float32), b.astype(np.float32)
@@ -357,9 +391,26 @@ def rtdetr_layer_specs(nc: int = 80, width: float = 1.0, hd: int = 256, ndl: int
     repc3("model.24", 2 * e, e)
     conv("model.25.conv", e, e, 3, "silu")
     repc3("model.27", 2 * e, e)
-    d = "model.28"
+    specs += rtdetr_decoder_specs("model.28", (e, e, e), nc, hd, ndl, nh, npts, d_ffn)
+    return specs
+
+
+def rtdetr_decoder_specs(d: str, ch: tuple[int, int, int], nc: int = 80, hd: int = 256, ndl: int = 6, nh: int = 8, npts: int = 4,
+                         d_ffn: int = 1024):
+    """(name, shape, kind) of a fused RTDETRDecoder at prefix d on three maps of ch channels (finest first)."""
+    specs = []
+
+    def conv(name, cin, cout, k, kind):
+        specs.append((name, (cout, cin, k, k), kind))
+
+    def lin(name, cin, cout):
+        specs.append((name, (cout, cin), "lin"))
+
+    def ln(name, c):
+        specs.append((name, (c,), "ln"))
+
     for i in range(3):
-        conv(f"{d}.input_proj.{i}.0", e, hd, 1, "lin")
+        conv(f"{d}.input_proj.{i}.0", ch[i], hd, 1, "lin")
     for i in range(ndl):
         lp = f"{d}.decoder.layers.{i}"
         lin(lp + ".self_attn.in_proj", hd, 3 * hd)
@@ -393,8 +444,14 @@ def synthetic_rtdetr(seed: int = 0, nc: int = 80, width: float = 1.0, hd: int = 
     LayerNorm weights 1 + N(0, 0.1^2). The box heads' last layers are damped (box_scale) so that refined boxes stay near their
     anchors; the score heads' biases are shifted (score_bias) so that a minority of the queries clears conf = 0.25."""
     rng = np.random.default_rng(seed)
+    t = _draw_rtdetr(rng, rtdetr_layer_specs(nc, width, hd, ndl, nh, npts, d_ffn), score_bias, box_scale)
+    t["rtdetr.meta"] = np.asarray([nh, npts, nq, 8], np.float32)
+    return t
+
+
+def _draw_rtdetr(rng, specs, score_bias: float, box_scale: float) -> dict[str, np.ndarray]:
     t: dict[str, np.ndarray] = {}
-    for name, shape, kind in rtdetr_layer_specs(nc, width, hd, ndl, nh, npts, d_ffn):
+    for name, shape, kind in specs:
         if kind == "ln":
             t[name + ".weight"] = (1 + 0.1 * rng.standard_normal(shape)).astype(np.float32)
             t[name + ".bias"] = (0.05 * rng.standard_normal(shape)).astype(np.float32)
@@ -411,7 +468,24 @@ def synthetic_rtdetr(seed: int = 0, nc: int = 80, width: float = 1.0, hd: int = 
             t[name + "_weight"], t[name + "_bias"] = w.astype(np.float32), b.astype(np.float32)
         else:
             t[name + ".weight"], t[name + ".bias"] = w.astype(np.float32), b.astype(np.float32)
-    t["rtdetr.meta"] = np.asarray([nh, npts, nq, 8], np.float32)
+    return t
+
+
+# --------------------------------------------------------------------------- YOLOv8-RTDETR (yolov8-rtdetr.yaml)
+# geo-trax's train.sh `-rt`: the backbone and neck of yolov8.yaml (model.0-21, Concat orders and shortcut flags unchanged) with an
+# RTDETRDecoder(nc) on [15, 18, 21] as model.22 in place of Detect (hd 256, 300 queries, 8 heads, 4 points, 6 layers, d_ffn 1024).
+# Its name contains "rtdetr", so the reference runs it through RTDETR (extract.py:222-225): stretched input, no NMS.
+
+def synthetic_yolov8_rtdetr(seed: int = 0, nc: int = 4, scale: str = "s", hd: int = 256, ndl: int = 6, nh: int = 8, npts: int = 4,
+                            nq: int = 300, d_ffn: int = 1024, score_bias: float = -1.5, box_scale: float = 0.3) -> dict[str, np.ndarray]:
+    """Seeded random fused YOLOv8-RTDETR weights. The trunk comes first from the generator, drawn exactly as synthetic_yolov8 draws
+    it (its Detect specs come last there), so model.0-21 equal synthetic_yolov8(seed, scale=scale)'s tensors; then the decoder,
+    drawn like synthetic_rtdetr's, at model.22 with input_proj widths taken from the trunk (model.15 / 18 / 21)."""
+    rng = np.random.default_rng(seed)
+    t = _draw_yolov8(rng, [s for s in yolov8_layer_specs(scale, nc) if not s[0].startswith("model.22.")])
+    ch = tuple(int(t[f"model.{i}.cv2.conv.weight"].shape[0]) for i in (15, 18, 21))
+    t.update(_draw_rtdetr(rng, rtdetr_decoder_specs("model.22", ch, nc, hd, ndl, nh, npts, d_ffn), score_bias, box_scale))
+    t["rtdetr.meta"] = np.asarray([nh, npts, nq, 8], np.float32)   # no AIFI: the encoder-heads entry is unused
     return t
 
 
@@ -422,9 +496,10 @@ def calibrate_rtdetr_scores(tensors: dict[str, np.ndarray], raw_logits: np.ndarr
     logit = np.sort(raw_logits.max(1).astype(np.float64))[::-1]
     k = min(max(int(target), 1), len(logit) - 1)
     delta = np.log(conf / (1 - conf)) - 0.5 * (logit[k - 1] + logit[k])
-    last = max(int(n.split(".")[3]) for n in tensors if n.startswith("model.28.dec_score_head.") and n.endswith(".bias"))
+    d = detector_topology(tensors)[1]
+    last = max(int(n.split(".")[3]) for n in tensors if n.startswith(d + ".dec_score_head.") and n.endswith(".bias"))
     out = dict(tensors)
-    name = f"model.28.dec_score_head.{last}.bias"
+    name = f"{d}.dec_score_head.{last}.bias"
     out[name] = (tensors[name] + np.float32(delta)).astype(np.float32)
     return out
 

@@ -238,8 +238,10 @@ typedef struct gtx_det_config {
                      * `with_reid: true, model: auto` (default.yaml:376-379; engine/predictor.py get_obj_feats): the Detect layer's
                      * three input maps, each level's channels averaged in consecutive groups down to the narrowest level's width
                      * (128 for YOLOv8s), read at the anchor the box came from */
-  int arch;         /* 0: YOLOv8 (Detect head + NMS). 1: RT-DETR (rtdetr-l topology: HGNetv2, AIFI + CCFM, deformable-attention
-                     * decoder, no NMS; ultralytics RTDETR, extract.py:222-225). The frame is then stretched to imgsz x imgsz
+  int arch;         /* 0: YOLOv8 (Detect head + NMS). 1: the RTDETR predictor (deformable-attention decoder, no NMS; ultralytics
+                     * RTDETR, extract.py:222-225) on one of two trunks, read off the tensor names like YOLOv8-P2 is:
+                     * rtdetr-l (HGNetv2, AIFI + CCFM; `model.0.stem1.*`, decoder = model.28) or yolov8-rtdetr (the YOLOv8
+                     * backbone + neck, `model.0.conv.*`, decoder = model.22 on model.15 / 18 / 21). The frame is then stretched to imgsz x imgsz
                      * (RTDETRPredictor.pre_transform: scale_fill), iou / agnostic_nms / rect are not read, obj_feats must be 0; half = 1: fp16 maps and
                      * weights on the fp16 MFMA convolutions, the token side (AIFI, the decoder's queries) stays fp32;
                      * gtx_detector_raw_output returns [queries][4 + nc] = xywh normalised to the frame + class scores */
