@@ -534,7 +534,7 @@ void launch_stem(int dtype, const void* img, int n, int h, int w, const float* w
     GTX_HIP(hipGetLastError());                                                                  \
     return;                                                                                      \
   }
-  GTX_STEM(16) GTX_STEM(32) GTX_STEM(48) GTX_STEM(64) GTX_STEM(80)
+  GTX_STEM(16) GTX_STEM(32) GTX_STEM(48) GTX_STEM(64) GTX_STEM(80) GTX_STEM(96)
 #undef GTX_STEM
   fail(-3, "stem: unsupported channel count %d", c0);
 }

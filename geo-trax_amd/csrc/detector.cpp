@@ -1,5 +1,6 @@
-// YOLOv8 (detect) graph builder + executor: the trunk (yolo_trunk.cpp: backbone + neck of ultralytics' cfg/models/v8/yolov8.yaml or
-// yolov8-p2.yaml) and the Detect layer on its outputs (model.22, or model.28 of the P2 graph: a fourth level at stride 4);
+// YOLOv8 / YOLO11 (detect) graph builder + executor: the trunk (yolo_trunk.cpp: backbone + neck of ultralytics' cfg/models/v8/yolov8.yaml,
+// yolov8-p2.yaml or cfg/models/11/yolo11.yaml) and the Detect layer on its outputs (model.22, model.28 of the P2 graph: a fourth level
+// at stride 4, or model.23 of YOLO11: a class branch of depthwise + pointwise pairs);
 // channel widths and bottleneck counts are read off the tensor shapes, so every v8 scale (n/s/m/l/x) loads unchanged.
 #include "detector.hpp"
 #include "split_format.hpp"
@@ -56,6 +57,8 @@ void Detector::build_graph() {
   // The levels (three, four with P2) go out as one grouped launch per stage. The final 1x1 convs are folded
   // into the decode kernels (the box one only runs for anchors that pass the score gate).
   std::vector<Op> st1, st2;
+  const bool dw_cls = trunk.dw_cls;
+  std::vector<Op> dw_a, pw_a, dw_b;                // yolo11.yaml: per level, the class branch's DWConv / 1x1 Conv / DWConv in front of its last 1x1
   head_ = HeadParams{};
   head_.n_levels = nl;
   head_.nc = cfg_.nc;
@@ -66,9 +69,42 @@ void Detector::build_graph() {
   int anchor = 0;
   for (int l = 0; l < nl; ++l) {
     const std::string b2 = det_pfx_ + ".cv2." + std::to_string(l), b3 = det_pfx_ + ".cv3." + std::to_string(l);
-    const HostTensor &w20 = tensor(b2 + ".0.conv.weight"), &w30 = tensor(b3 + ".0.conv.weight");
+    const HostTensor &w20 = tensor(b2 + ".0.conv.weight"), &w30 = tensor(b3 + (dw_cls ? ".1.1.conv.weight" : ".0.conv.weight"));
     const int cb = (int)w20.shape[0], cc = (int)w30.shape[0], cin = (int)w20.shape[1];
-    GTX_CHECK(cin == lvl_in[l].c && (int)w30.shape[1] == cin, "Detect level %d input channels", l);
+    GTX_CHECK(cin == lvl_in[l].c && (dw_cls || (int)w30.shape[1] == cin), "Detect level %d input channels", l);
+    Op o1, o2, o3;
+    View h2;
+    if (dw_cls) {
+      // yolo11.yaml's Detect: the box branch as above on its own (cv2[l][0] is a launch of one 64-cout tile, the sparse box branch's
+      // image); the class branch is DWConv 3x3 + Conv 1x1 twice. Six ops per level, regrouped by stage below.
+      const size_t mark = ops_.size();
+      bool k32 = true;
+      for (int q = 0; q < nl; ++q) k32 = k32 && lvl_in[q].c % 32 == 0;
+      h2 = new_view(lvl_in[l].h, lvl_in[l].w, cb + cc);
+      View h2b = h2.slice(0, cb), h2c = h2.slice(cb, cc);
+      force_kc_ = fmt_ == DT_F16 ? (k32 ? 32 : 16) : 0;
+      force_bn_ = cb % 64 == 0 ? 64 : 32;
+      const View h1b = head_conv(b2 + ".0.conv", lvl_in[l], nullptr);
+      force_kc_ = fmt_ == DT_F16 ? (cb % 32 == 0 ? 32 : 16) : 0;
+      plain_out_ = true;
+      head_conv(b2 + ".1.conv", h1b, &h2b);
+      plain_out_ = false;
+      const View d0 = trunk_.dwconv(b3 + ".0.0.conv", lvl_in[l], 1);
+      force_kc_ = fmt_ == DT_F16 ? (k32 ? 32 : 16) : 0;
+      force_bn_ = cc % 64 == 0 ? 64 : 32;
+      const View p0 = head_conv(b3 + ".0.1.conv", d0, nullptr);
+      const View d1v = trunk_.dwconv(b3 + ".1.0.conv", p0, 1);
+      force_kc_ = fmt_ == DT_F16 ? (cc % 32 == 0 ? 32 : 16) : 0;
+      plain_out_ = true;
+      head_conv(b3 + ".1.1.conv", d1v, &h2c);
+      plain_out_ = false;
+      h2.plain = fmt_ == DT_F32S;
+      force_kc_ = force_bn_ = 0;
+      GTX_CHECK(ops_.size() == mark + 6, "internal: head op count");
+      o1 = ops_[mark]; o2 = ops_[mark + 1]; o3 = ops_[mark + 5];
+      dw_a.push_back(ops_[mark + 2]); pw_a.push_back(ops_[mark + 3]); dw_b.push_back(ops_[mark + 4]);
+      ops_.resize(mark);
+    } else {
     // stacked stage-1 weights / bias
     HostTensor ws;
     ws.shape = {cb + cc, cin, 3, 3};
@@ -90,22 +126,24 @@ void Detector::build_graph() {
     force_kc_ = fmt_ == DT_F16 ? (k32 ? 32 : 16) : 0;
     force_bn_ = (cb + cc) % 64 == 0 ? 64 : 32;
     View h1 = head_conv("__head" + std::to_string(l) + ".s1", lvl_in[l], nullptr);
-    View h2 = new_view(h1.h, h1.w, cb + cc);
-    View h1b = h1.slice(0, cb), h1c = h1.slice(cb, cc), h2b = h2.slice(0, cb), h2c = h2.slice(cb, cc);
+    View h2v = new_view(h1.h, h1.w, cb + cc);
+    View h1b = h1.slice(0, cb), h1c = h1.slice(cb, cc), h2b = h2v.slice(0, cb), h2c = h2v.slice(cb, cc);
     force_kc_ = fmt_ == DT_F16 ? ((cb % 32 == 0 && cc % 32 == 0) ? 32 : 16) : 0;
     force_bn_ = (cb % 64 == 0 && cc % 64 == 0) ? 64 : 32;
     plain_out_ = true;            // the decode kernels read these two as plain fp32
     head_conv(b2 + ".1.conv", h1b, &h2b);
     head_conv(b3 + ".1.conv", h1c, &h2c);
     plain_out_ = false;
-    h2.plain = fmt_ == DT_F32S;
+    h2v.plain = fmt_ == DT_F32S;
     force_kc_ = force_bn_ = 0;
     // move the three freshly built single-problem ops into the grouped stage ops: one grouped launch per stage and kernel
     // configuration (the levels of a stage share a launch when they share the kernel; the fp32 default path runs its deep
     // levels -- Cin >= 256 -- on the Winograd kernel and the 240 x 240 level on the direct one: two launches for a stage)
     GTX_CHECK(ops_.size() == mark + 3, "internal: head op count");
-    Op o1 = ops_[mark], o2 = ops_[mark + 1], o3 = ops_[mark + 2];
+    o1 = ops_[mark]; o2 = ops_[mark + 1]; o3 = ops_[mark + 2];
     ops_.resize(mark);
+    h2 = h2v;
+    }
     // Sparse box branch (head_sparse.hip): the box half of stage 1 (cout tile 0 of the stacked image) and cv2[l][1] are evaluated
     // at the candidate anchors only, after the score gate; stage 1 keeps its class half (cout tiles 1..), same packed image,
     // same scale. Needs the 16x16x32 kernel's image (32-channel chunks, one 64-cout box tile); decided for all levels at once.
@@ -177,6 +215,11 @@ void Detector::build_graph() {
         box1.grp.p[0].Cout = cb;
         add(d1, (det_pfx_ + ".box1").c_str(), box1);
         add(d2, (det_pfx_ + ".box2").c_str(), o2);
+        if (dw_cls) {                                // stage 1 holds no class tile: the class branch's own 1x1 layers
+          add(st1, (det_pfx_ + ".stage1").c_str(), pw_a[l]);
+          add(st2, (det_pfx_ + ".stage2").c_str(), o3);
+          continue;
+        }
         ConvProblem& p = o1.grp.p[0];                // the class tiles alone
         p.wpack = static_cast<const char*>(full.wpack) + tile_bytes;
         p.bias = full.bias + 64;
@@ -185,6 +228,7 @@ void Detector::build_graph() {
         add(st1, (det_pfx_ + ".stage1").c_str(), o1);
         add(st2, (det_pfx_ + ".stage2").c_str(), o3);
       } else {
+        if (dw_cls) add(st1, (det_pfx_ + ".stage1").c_str(), pw_a[l]);
         add(st1, (det_pfx_ + ".stage1").c_str(), o1);
         add(st2, (det_pfx_ + ".stage2").c_str(), o2);
         add(st2, (det_pfx_ + ".stage2").c_str(), o3);
@@ -208,11 +252,13 @@ void Detector::build_graph() {
       GTX_CHECK(lvl_in[l].c % feat_levels_.dim == 0, "obj_feats: Detect input %d has %d channels, not a multiple of %d", l, lvl_in[l].c, feat_levels_.dim);
     }
   }
-  for (std::vector<Op>* stage : {&st1, &st2})
+  for (std::vector<Op>* stage : {&st1, &st2}) {
+    for (const Op& d : stage == &st1 ? dw_a : dw_b) ops_.push_back(d);   // the depthwise layers a stage's 1x1 launches read
     for (Op& g : *stage) {
       g.family = conv_kernel_name(g.cfg);
       ops_.push_back(g);
     }
+  }
 }
 
 void Detector::set_batch(int nb) {

@@ -72,7 +72,7 @@ class NetRuntime {
   NetRuntime(const NetRuntime&) = delete;
   NetRuntime& operator=(const NetRuntime&) = delete;
   // The YOLOv8 trunk (yolo_trunk.hpp) is a part of the net that holds it, not a family: it builds through the protected calls
-  // below (tensor / has, alloc / new_view, emit_named_conv, set_layer_view, repoint_layer_views, release_buffer, format, device)
+  // below (tensor / has, alloc / new_view, emit_conv / emit_named_conv, bias_of, upload, set_layer_view, repoint_layer_views, release_buffer, format, device, sat_flag)
   // and touches no data member.
   friend class YoloTrunk;
   void set_tensor(const std::string& name, const float* data, int ndim, const int64_t* shape);
@@ -144,6 +144,7 @@ class NetRuntime {
   size_t release_buffer(const void* p);                    // gives arena buffer p back early: its size (0: p is none of them)
   int format() const { return fmt_; }
   int device() const { return ctx_->device; }
+  int* sat_flag() const { return sat_dev_; }                // null off the split-f16x3 path
 
   // ---- layer v of batch slot `slot` as fp32 [h][w][c] (pair format, fp16 or fp32 per the net's format and v.plain)
   void read_view(const View& v, int slot, float* out) const;

@@ -13,6 +13,7 @@ namespace gtx {
 namespace {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 // ---- 8-channel groups in the three activation formats; e = element index of the group's first channel (a multiple of 8)
@@ -211,6 +212,9 @@ __global__ __launch_bounds__(256) void rt_dwconv_kernel(RtMap in, RtMap out, int
   if (act == 2) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = fmaxf(acc[j], 0.f);
+  } else if (act == 1) {                              // SiLU, as the convolutions' epilogue computes it (YOLO11's DWConv)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = acc[j] * __builtin_amdgcn_rcpf(1.f + __expf(-acc[j]));
   }
   bool s = false;
   store8<FMT>(out.ptr, pix * out.cstride + out.coff + g * 8, acc, s);
@@ -261,6 +265,9 @@ __global__ __launch_bounds__(256) void rt_dwconv_tile_kernel(RtMap in, RtMap out
   if (act == 2) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = fmaxf(acc[j], 0.f);
+  } else if (act == 1) {                              // SiLU, as the convolutions' epilogue computes it (YOLO11's DWConv)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = acc[j] * __builtin_amdgcn_rcpf(1.f + __expf(-acc[j]));
   }
   bool s = false;
   store8<FMT>(out.ptr, (((size_t)n * out.h + oy) * out.w + ox) * out.cstride + out.coff + c0 + g * 8, acc, s);
@@ -647,6 +654,170 @@ __global__ __launch_bounds__(256) void rt_mha32_kernel(const float* __restrict__
   }
 }
 
+// ============================================================================ position-sensitive attention on a qkv map (YOLO11's C2PSA)
+// Four consecutive channels (e a multiple of 4) in the three activation formats: half a group of the pair format
+template <int FMT> __device__ __forceinline__ void load4(const void* base, size_t e, float v[4]) {
+  const char* b = static_cast<const char*>(base);
+  if constexpr (FMT == DT_F16) {
+    const half4 h = *reinterpret_cast<const half4*>(b + e * 2);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = (float)h[i];
+  } else if constexpr (FMT == DT_F32) {
+    const float4 a = *reinterpret_cast<const float4*>(b + e * 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  } else {
+    const char* g = b + (e & ~(size_t)7) * 4 + 2 * (e & 7);
+    const half4 hi = *reinterpret_cast<const half4*>(g), lo = *reinterpret_cast<const half4*>(g + 16);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = (float)hi[i] + (float)lo[i];
+  }
+}
+template <int FMT> __device__ __forceinline__ void store4(void* base, size_t e, const float v[4], bool& sat) {
+  char* b = static_cast<char*>(base);
+  if constexpr (FMT == DT_F16) {
+    half4 h;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) h[i] = (_Float16)v[i];
+    *reinterpret_cast<half4*>(b + e * 2) = h;
+  } else if constexpr (FMT == DT_F32) {
+    *reinterpret_cast<float4*>(b + e * 4) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    half4 hi, lo;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float x = __builtin_amdgcn_fmed3f(v[i], -65504.f, 65504.f);
+      sat |= x != v[i];
+      hi[i] = (_Float16)x;
+      lo[i] = (_Float16)(x - (float)hi[i]);
+    }
+    char* g = b + (e & ~(size_t)7) * 4 + 2 * (e & 7);
+    *reinterpret_cast<half4*>(g) = hi;
+    *reinterpret_cast<half4*>(g + 16) = lo;
+  }
+}
+
+// rt_mha32_kernel's scheme (a wave owns 16 queries, walks the keys 16 at a time on v_mfma_f32_16x16x4_f32, the probabilities stay
+// in the lanes that computed them, K / V tiles of 64 keys shared through LDS with the next stage prefetched into registers) for
+// ultralytics' Attention block: the positions of a map are the tokens, a head's 128 channels of the qkv map are [q 32 | k 32 | v 64],
+//   S^T[key][query]  = sum_32 K Q * 32^-0.5        8 MFMAs per 16 x 16 tile
+//   O^T[dim][query] += sum_key V[key][dim] P^T     16 MFMAs (four 16-dim tiles x four key groups)
+// read in the path's activation format, scores and softmax in fp32. The epilogue adds the positional term -- the depthwise 3x3
+// convolution `pe` of v as a map, no activation -- for the lane's 16 output channels and writes the map `proj` reads: the
+// h w x h w score matrix (207 MB per head set at 60 x 60) never exists.
+template <int FMT>
+__global__ __launch_bounds__(256) void psa_attn_kernel(RtMap qkv, RtMap out, const float* __restrict__ pe_w, const float* __restrict__ pe_b, int* sat) {
+  constexpr int KS = 64, PK = 36, PV = 68;
+  __shared__ float s_k[KS * PK];
+  __shared__ float s_v[KS * PV];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lc = lane & 15, kk = lane >> 4;
+  const int head = blockIdx.y, n = blockIdx.z, T = qkv.h * qkv.w;
+  const int q0 = blockIdx.x * 64 + wave * 16;
+  const size_t img = (size_t)n * T;
+  const int ch = qkv.coff + head * 128;
+  const float scale = 0.17677669529663687f;      // key_dim^-0.5, key_dim = 32
+  float qf[8];                                     // B operand of the first product: Q[query lc][4 i + kk], scaled
+  {
+    const int qi = q0 + lc;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) qf[i] = qi < T ? load1<FMT>(qkv.ptr, (img + qi) * qkv.cstride + ch + 4 * i + kk) * scale : 0.f;
+  }
+  floatx4 o[4];                                    // O^T[dim 16 t + 4 kk + r][query lc]
+#pragma unroll
+  for (int t = 0; t < 4; ++t) o[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+  float m = -FLT_MAX, l = 0.f;
+  float pk[8], pv[2][8];                           // the next stage's rows: one 8-channel group of K and two of V per thread
+  auto fetch = [&](int k0) {
+    {
+      const int kr = threadIdx.x >> 2, g = threadIdx.x & 3;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) pk[e] = 0.f;
+      if (k0 + kr < T) load8<FMT>(qkv.ptr, (img + k0 + kr) * qkv.cstride + ch + 32 + g * 8, pk);
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int i = threadIdx.x + 256 * j, kr = i >> 3, g = i & 7;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) pv[j][e] = 0.f;
+      if (k0 + kr < T) load8<FMT>(qkv.ptr, (img + k0 + kr) * qkv.cstride + ch + 64 + g * 8, pv[j]);
+    }
+  };
+  fetch(0);
+  for (int k0 = 0; k0 < T; k0 += KS) {
+    __syncthreads();
+    {
+      float* d = &s_k[(threadIdx.x >> 2) * PK + (threadIdx.x & 3) * 8];
+      *reinterpret_cast<float4*>(d) = make_float4(pk[0], pk[1], pk[2], pk[3]);
+      *reinterpret_cast<float4*>(d + 4) = make_float4(pk[4], pk[5], pk[6], pk[7]);
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int i = threadIdx.x + 256 * j;
+      float* d = &s_v[(i >> 3) * PV + (i & 7) * 8];
+      *reinterpret_cast<float4*>(d) = make_float4(pv[j][0], pv[j][1], pv[j][2], pv[j][3]);
+      *reinterpret_cast<float4*>(d + 4) = make_float4(pv[j][4], pv[j][5], pv[j][6], pv[j][7]);
+    }
+    if (k0 + KS < T) fetch(k0 + KS);
+    __syncthreads();
+    const int nk = min(KS, T - k0);
+    for (int t0 = 0; t0 < nk; t0 += 16) {
+      floatx4 sc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int i = 0; i < 8; ++i) sc = __builtin_amdgcn_mfma_f32_16x16x4f32(s_k[(t0 + lc) * PK + 4 * i + kk], qf[i], sc, 0, 0, 0);
+      float mx = -FLT_MAX;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (t0 + 4 * kk + r >= nk) sc[r] = -FLT_MAX;          // keys past the end
+        mx = fmaxf(mx, sc[r]);
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 16));
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      const float mn = fmaxf(m, mx), resc = __expf(m - mn);
+      float p[4], ps = 0.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { p[r] = sc[r] > -FLT_MAX ? __expf(sc[r] - mn) : 0.f; ps += p[r]; }
+      ps += __shfl_xor(ps, 16);
+      ps += __shfl_xor(ps, 32);
+      l = l * resc + ps;
+      m = mn;
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[t][r] *= resc;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float* vr = &s_v[(t0 + 4 * kk + r) * PV];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) o[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(vr[16 * t + lc], p[r], o[t], 0, 0, 0);
+      }
+    }
+  }
+  const int qi = q0 + lc;
+  if (qi >= T) return;
+  const float inv = 1.f / l;
+  const int y = qi / qkv.w, x = qi % qkv.w, C = out.c;
+  bool s = false;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int d = 16 * t + 4 * kk;                 // the lane's four channels of this tile
+    const float4 b4 = *reinterpret_cast<const float4*>(pe_b + head * 64 + d);
+    float pe[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const int yy = y + ky - 1, xx = x + kx - 1;
+        if (yy < 0 || yy >= qkv.h || xx < 0 || xx >= qkv.w) continue;
+        float v[4];
+        load4<FMT>(qkv.ptr, (img + (size_t)yy * qkv.w + xx) * qkv.cstride + ch + 64 + d, v);
+        const float4 w4 = *reinterpret_cast<const float4*>(pe_w + (size_t)(ky * 3 + kx) * C + head * 64 + d);
+        pe[0] = fmaf(v[0], w4.x, pe[0]); pe[1] = fmaf(v[1], w4.y, pe[1]); pe[2] = fmaf(v[2], w4.z, pe[2]); pe[3] = fmaf(v[3], w4.w, pe[3]);
+      }
+    const float r4[4] = {o[t][0] * inv + pe[0], o[t][1] * inv + pe[1], o[t][2] * inv + pe[2], o[t][3] * inv + pe[3]};
+    store4<FMT>(out.ptr, (img + qi) * out.cstride + out.coff + head * 64 + d, r4, s);
+  }
+  flag_sat(sat, s);
+}
+
 // ============================================================================ query selection (top-k anchors per image)
 __device__ __forceinline__ unsigned sortable(float f) {
   const unsigned u = __float_as_uint(f);
@@ -992,6 +1163,13 @@ void launch_rt_mha(const float* qkv, int ld, int n, int T, int C, int heads, flo
   else if (d == 8) hipLaunchKernelGGL(rt_mha_kernel<8>, grid, block, 0, s, qkv, ld, T, C, out, ldo);
   else fail(-3, "rt_mha: head dimension %d is not built (8, 16, 32)", d);
   GTX_HIP(hipGetLastError());
+}
+
+void launch_psa_attention(int fmt, const RtMap& qkv, const RtMap& out, int n, int heads, const float* pe_w, const float* pe_b, int* sat, hipStream_t s) {
+  GTX_CHECK(heads > 0 && qkv.c == heads * 128 && out.c == heads * 64 && qkv.h == out.h && qkv.w == out.w, "psa_attention: %d heads on %d -> %d channels", heads, qkv.c, out.c);
+  GTX_CHECK(qkv.cstride % 8 == 0 && qkv.coff % 8 == 0 && out.cstride % 8 == 0 && out.coff % 8 == 0, "psa_attention: channel strides / offsets must be multiples of 8");
+  const dim3 grid(cdiv(qkv.h * qkv.w, 64), heads, n), block(256);
+  RT_FMT(fmt, hipLaunchKernelGGL(psa_attn_kernel<F>, grid, block, 0, s, qkv, out, pe_w, pe_b, sat));
 }
 
 void launch_rt_topk(int fmt, const RtLevels& scores, int nc, int n, int nq, unsigned* keys_scratch, int* out_idx, hipStream_t s) {

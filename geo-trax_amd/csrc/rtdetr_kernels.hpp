@@ -24,7 +24,7 @@ struct RtMap {            // one NHWC map tensor (or a channel slice of one)
 void launch_rt_stem1(int fmt, const void* img, int n, int H, int W, const float* w27, const float* bias, const RtMap& out, int* sat, hipStream_t s);
 // MaxPool2d(2, 1, ceil_mode) on F.pad(x, [0, 1, 0, 1]): out(y, x) = max over the 2 x 2 window at (y, x), zeros past the border
 void launch_rt_pool2(int fmt, const RtMap& in, const RtMap& out, int n, int* sat, hipStream_t s);
-// depthwise k x k (3 or 5), stride 1 or 2, pad k / 2; w [k * k][C] tap-major, bias [C]; act: 0 none, 2 ReLU
+// depthwise k x k (3 or 5), stride 1 or 2, pad k / 2; w [k * k][C] tap-major, bias [C]; act: 0 none, 1 SiLU (YOLO11's DWConv), 2 ReLU
 void launch_rt_dwconv(int fmt, const RtMap& in, const RtMap& out, int n, int k, int stride, const float* w, const float* bias, int act, int* sat, hipStream_t s);
 // nearest 2x upsampling into a channel slice (raw copy of 8-channel groups)
 void launch_rt_upsample2x(int fmt, const RtMap& in, const RtMap& out, int n, hipStream_t s);
@@ -51,6 +51,11 @@ void launch_rt_layernorm(const RtRows& in, const RtRows& out, long rows, int C, 
 
 // softmax(Q K^T / sqrt(d)) V per image and head on token rows: qkv [N * T][ld] with q at column 0, k at C, v at 2C
 void launch_rt_mha(const float* qkv, int ld, int n, int T, int C, int heads, float* out, int ldo, hipStream_t s);
+
+// ultralytics' Attention block (YOLO11's C2PSA) on maps in the path's activation format: qkv [N][h][w] with heads x [q 32 | k 32 | v 64]
+// channels, out [N][h][w][heads * 64] = softmax(q^T k * 32^-0.5) v over the h w positions + pe(v), pe a depthwise 3x3
+// convolution without activation (pe_w [9][heads * 64] tap-major, pe_b [heads * 64]). Scores and softmax in fp32.
+void launch_psa_attention(int fmt, const RtMap& qkv, const RtMap& out, int n, int heads, const float* pe_w, const float* pe_b, int* sat, hipStream_t s);
 
 // query selection: per image, the nq anchors with the largest max-over-classes score, descending (ties: lower anchor index
 // first). scores: per level maps [N][h][w][cs] with the classes in channels [0, nc): plain fp32 (fmt DT_F32, both fp32-grade

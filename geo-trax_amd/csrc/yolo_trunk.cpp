@@ -2,6 +2,7 @@
 // topology follows ultralytics' cfg/models/v8/yolov8.yaml (backbone 0-9, head 10-21) or yolov8-p2.yaml (head 10-27, one more
 // stage at stride 4); channel widths and bottleneck counts are read off the tensor shapes, so every v8 scale (n/s/m/l/x) loads unchanged.
 #include "yolo_trunk.hpp"
+#include "rtdetr_kernels.hpp"
 #include "split_format.hpp"
 
 #include <algorithm>
@@ -45,6 +46,217 @@ View YoloTrunk::c2f(const std::string& pfx, const View& x, bool shortcut, const 
   View out = conv(pfx + ".cv2.conv", cat, 1, out_slice, nullptr);
   net_.set_layer_view(pfx, out);
   return out;
+}
+
+void YoloTrunk::upsample(const std::string& name, const View& src, const View& dst) {
+  Op op;
+  op.kind = Op::UPSAMPLE;
+  op.name = name;
+  op.family = "upsample2x_kernel";
+  op.in = src;
+  op.out = dst;
+  ops_.push_back(op);
+}
+
+// ---- SPPF (model.9): cv1 -> 3 cascaded pools -> cv2; its output is written into the slice `s9` of the last Concat
+void YoloTrunk::sppf(const View& a8, const View& s9) {
+  const int cm = (int)net_.tensor("model.9.cv1.conv.weight").shape[0];
+  View sp = net_.new_view(a8.h, a8.w, 4 * cm);
+  View sp0 = sp.slice(0, cm);
+  conv("model.9.cv1.conv", a8, 1, &sp0, nullptr);
+  Op op;
+  op.kind = Op::POOL;
+  op.name = "model.9.m";
+  op.family = "sppf_pool_kernel";
+  op.in = sp0;
+  op.out = sp;
+  ops_.push_back(op);
+  conv("model.9.cv2.conv", sp, 1, &s9, nullptr);
+  net_.set_layer_view("model.9", s9);
+}
+
+// ============================================================================ YOLO11 (ultralytics cfg/models/11/yolo11.yaml)
+// One stride-1 Conv op with the given activation (0 none, 1 SiLU). The convolution kernels take channel counts that are
+// multiples of 16: a narrower layer (the 8-channel hidden layer of scale n's model.2 bottleneck) gets zero output channels
+// appended -- SiLU(0) = 0 -- and its consumer zero input weights for them, which changes no sum.
+View YoloTrunk::conv_act(const std::string& name, const View& x, int act, const View* out_slice, const View* residual) {
+  const HostTensor& w = net_.tensor(name + ".weight");
+  GTX_CHECK(w.shape.size() == 4 && w.shape[2] == w.shape[3], "%s: expected OIHW square kernel", name.c_str());
+  const int cout = (int)w.shape[0], cin = (int)w.shape[1], ks = (int)w.shape[2], taps = ks * ks;
+  const int cout_p = (cout + 15) / 16 * 16, cin_p = x.c;
+  NetRuntime::ConvArgs a;
+  a.act = act; a.out_slice = out_slice; a.residual = residual;
+  if (cout_p == cout && cin_p == cin) return net_.emit_named_conv(ops_, name, x, a);
+  GTX_CHECK(cin_p >= cin && (cout_p == cout || (!out_slice && !residual)), "%s: %d -> %d channels cannot be padded here", name.c_str(), cin, cout);
+  std::vector<float> wp((size_t)cout_p * cin_p * taps, 0.f), bp(cout_p, 0.f);
+  for (int o = 0; o < cout; ++o)
+    for (int i = 0; i < cin; ++i)
+      for (int t = 0; t < taps; ++t) wp[((size_t)o * cin_p + i) * taps + t] = w.data[((size_t)o * cin + i) * taps + t];
+  if (const float* b = net_.bias_of(name, cout)) std::copy(b, b + cout, bp.begin());
+  a.out_pixels = (long)x.n * x.h * x.w;
+  return net_.emit_conv(ops_, name, wp.data(), cout_p, cin_p, ks, bp.data(), x, a);
+}
+
+// Bottleneck(c, c, shortcut, k = (3, 3), e): src -> dst (+ src); the hidden width is read off cv1 (c / 2 in C3k2, c in C3k)
+View YoloTrunk::bottleneck_half(const std::string& m, const View& src, const View& dst, bool shortcut) {
+  const View tmp = conv_act(m + ".cv1.conv", src, 1, nullptr, nullptr);   // a buffer of its own, as in c2f()
+  return conv_act(m + ".cv2.conv", tmp, 1, &dst, shortcut ? &src : nullptr);
+}
+
+// C3k: cv3(cat(m(cv1(x)), cv2(x))), m = Bottlenecks of full hidden width
+View YoloTrunk::c3k(const std::string& m, const View& src, const View& dst, bool shortcut) {
+  const int ch = (int)net_.tensor(m + ".cv1.conv.weight").shape[0];
+  int n = 0;
+  while (net_.has(m + ".m." + std::to_string(n) + ".cv1.conv.weight")) ++n;
+  View cat = net_.new_view(src.h, src.w, 2 * ch);
+  View left = cat.slice(0, ch), right = cat.slice(ch, ch);
+  View y = n == 0 ? left : net_.new_view(src.h, src.w, ch);
+  conv_act(m + ".cv1.conv", src, 1, &y, nullptr);
+  for (int j = 0; j < n; ++j) {
+    View nxt = j + 1 == n ? left : net_.new_view(src.h, src.w, ch);
+    bottleneck_half(m + ".m." + std::to_string(j), y, nxt, shortcut);
+    y = nxt;
+  }
+  conv_act(m + ".cv2.conv", src, 1, &right, nullptr);
+  return conv_act(m + ".cv3.conv", cat, 1, &dst, nullptr);
+}
+
+// C3k2 = C2f whose m.{k} is a half-width Bottleneck (c3k = False) or a C3k (c3k = True: the block has a cv3)
+View YoloTrunk::c3k2(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src) {
+  const int c = (int)net_.tensor(pfx + ".cv1.conv.weight").shape[0] / 2;
+  int n = 0;
+  while (net_.has(pfx + ".m." + std::to_string(n) + ".cv1.conv.weight")) ++n;
+  View cat = net_.new_view(x.h, x.w, (2 + n) * c);
+  View first = cat.slice(0, 2 * c);
+  conv(pfx + ".cv1.conv", x, 1, &first, nullptr, up_src);
+  for (int k = 0; k < n; ++k) {
+    const std::string m = pfx + ".m." + std::to_string(k);
+    View src = cat.slice((1 + k) * c, c), dst = cat.slice((2 + k) * c, c);
+    if (net_.has(m + ".cv3.conv.weight")) c3k(m, src, dst, shortcut); else bottleneck_half(m, src, dst, shortcut);
+  }
+  View out = conv(pfx + ".cv2.conv", cat, 1, out_slice, nullptr);
+  net_.set_layer_view(pfx, out);
+  return out;
+}
+
+// C2PSA: cv1 -> a | b; per PSABlock b += proj(attention(qkv(b)) + pe(v)), b += ffn.1(ffn.0(b)); cv2 on cat(a, b). The convolutions
+// without activation take the residual in their epilogue (activation first, then the residual: x + conv(x)). The last block
+// writes b back into cv1's buffer, which cv2 then reads whole.
+View YoloTrunk::c2psa(const std::string& pfx, const View& x, const View* out_slice) {
+  const int c = (int)net_.tensor(pfx + ".cv1.conv.weight").shape[0] / 2;
+  GTX_CHECK(c % 64 == 0, "%s: %d hidden channels are not whole 64-wide attention heads", pfx.c_str(), c);
+  const int heads = c / 64;
+  int n = 0;
+  while (net_.has(pfx + ".m." + std::to_string(n) + ".attn.qkv.conv.weight")) ++n;
+  GTX_CHECK(n > 0, "%s: no PSABlock", pfx.c_str());
+  View ab = conv(pfx + ".cv1.conv", x, 1, nullptr, nullptr);
+  View b = ab.slice(c, c);
+  for (int k = 0; k < n; ++k) {
+    const std::string m = pfx + ".m." + std::to_string(k);
+    const HostTensor &wq = net_.tensor(m + ".attn.qkv.conv.weight"), &wp = net_.tensor(m + ".attn.pe.conv.weight");
+    GTX_CHECK((int)wq.shape[0] == heads * 128 && wp.shape.size() == 4 && (int)wp.shape[0] == c && wp.shape[1] == 1 && wp.shape[2] == 3,
+              "%s: attention of %d heads with key_dim 32 / head_dim 64 expected", m.c_str(), heads);
+    const View qkv = conv_act(m + ".attn.qkv.conv", b, 0, nullptr, nullptr);
+    View att = net_.new_view(x.h, x.w, c);
+    {
+      std::vector<float> wt((size_t)9 * c);
+      for (int ch = 0; ch < c; ++ch)
+        for (int t = 0; t < 9; ++t) wt[(size_t)t * c + ch] = wp.data[(size_t)ch * 9 + t];
+      std::vector<float> bias(c, 0.f);
+      if (const float* pb = net_.bias_of(m + ".attn.pe.conv", c)) std::copy(pb, pb + c, bias.begin());
+      Op op;
+      op.kind = Op::ATTN;
+      op.name = m + ".attn";
+      op.family = "psa_attn_kernel";
+      op.in = qkv; op.out = att;
+      op.heads = heads;
+      op.dw_w = net_.upload(wt); op.dw_bias = net_.upload(bias);
+      op.sat = net_.sat_flag();
+      ops_.push_back(op);
+      net_.set_layer_view(m + ".attn.out", att);       // softmax(q^T k) v + pe(v): what proj reads
+    }
+    View b1 = net_.new_view(x.h, x.w, c);
+    conv_act(m + ".attn.proj.conv", att, 0, &b1, &b);
+    const View f0 = conv_act(m + ".ffn.0.conv", b1, 1, nullptr, nullptr);
+    View b2 = k + 1 == n ? ab.slice(c, c) : net_.new_view(x.h, x.w, c);
+    conv_act(m + ".ffn.1.conv", f0, 0, &b2, &b1);
+    b = b2;
+  }
+  View out = conv(pfx + ".cv2.conv", ab, 1, out_slice, nullptr);
+  net_.set_layer_view(pfx, out);
+  return out;
+}
+
+View YoloTrunk::dwconv(const std::string& name, const View& x, int act) {
+  const HostTensor& w = net_.tensor(name + ".weight");
+  const int c = x.c;
+  GTX_CHECK(w.shape.size() == 4 && (int)w.shape[0] == c && w.shape[1] == 1 && w.shape[2] == 3 && w.shape[3] == 3 && c % 8 == 0,
+            "%s: expected a depthwise 3x3 convolution on %d channels", name.c_str(), c);
+  std::vector<float> wt((size_t)9 * c), bias(c, 0.f);
+  for (int ch = 0; ch < c; ++ch)
+    for (int t = 0; t < 9; ++t) wt[(size_t)t * c + ch] = w.data[(size_t)ch * 9 + t];
+  if (const float* pb = net_.bias_of(name, c)) std::copy(pb, pb + c, bias.begin());
+  Op op;
+  op.kind = Op::DWCONV;
+  op.name = name;
+  op.family = c % 32 == 0 ? "rt_dwconv_tile_kernel<3>" : "rt_dwconv_kernel<3>";     // launch_rt_dwconv's rule
+  op.in = x;
+  op.out = net_.new_view(x.h, x.w, c);
+  op.dw_w = net_.upload(wt); op.dw_bias = net_.upload(bias);
+  op.dw_act = act;
+  op.sat = net_.sat_flag();
+  ops_.push_back(op);
+  net_.set_layer_view(name, op.out);
+  return op.out;
+}
+
+// Backbone 0-10 (C3k2 stages, SPPF, C2PSA), neck 11-22, Detect = model.23 on 16 / 19 / 22. Widths, repeats and c3k-or-not are read
+// off the tensors, so every scale (n / s / m / l / x) loads unchanged. Shortcuts: on in the backbone; in the neck kNeckShortcut, which
+// no tensor tells (taken as off, as in yolov8.yaml's neck; tests/yolo11_ref.py names the doubt).
+YoloTrunk::Levels YoloTrunk::build_yolo11(const View& a0) {
+  constexpr bool kNeckShortcut = false;
+  const int H = a0.h * 2, W = a0.w * 2, fmt = net_.format();
+  auto cout_of = [&](const std::string& n) { return (int)net_.tensor(n + ".weight").shape[0]; };
+  const int c4 = cout_of("model.4.cv2.conv"), c6 = cout_of("model.6.cv2.conv"), c9 = cout_of("model.9.cv2.conv");
+  const int c10 = cout_of("model.10.cv2.conv"), c13 = cout_of("model.13.cv2.conv");
+  const int c17 = cout_of("model.17.conv"), c20 = cout_of("model.20.conv");
+  View a1 = conv("model.1.conv", a0, 2, nullptr, nullptr);
+  View a2 = c3k2("model.2", a1, true, nullptr);
+  View a3 = conv("model.3.conv", a2, 2, nullptr, nullptr);
+  View cat15 = net_.new_view(H / 8, W / 8, c13 + c4);             // [up14, model.4]
+  View s4 = cat15.slice(c13, c4);
+  View a4 = c3k2("model.4", a3, true, &s4);
+  View a5 = conv("model.5.conv", a4, 2, nullptr, nullptr);
+  View cat12 = net_.new_view(H / 16, W / 16, c10 + c6);           // [up11, model.6]
+  View s6 = cat12.slice(c10, c6);
+  View a6 = c3k2("model.6", a5, true, &s6);
+  View a7 = conv("model.7.conv", a6, 2, nullptr, nullptr);
+  View a8 = c3k2("model.8", a7, true, nullptr);
+  View s9 = net_.new_view(H / 32, W / 32, c9);
+  sppf(a8, s9);
+  View cat21 = net_.new_view(H / 32, W / 32, c20 + c10);          // [conv20, model.10]
+  View s10 = cat21.slice(c20, c10);
+  c2psa("model.10", s9, &s10);
+  // Upsample + Concat in front of model.13 / model.16: read in place by the C3k2's first 1x1 on the split-f16x3 path (as in yolov8.yaml)
+  const bool fuse_up = fmt == DT_F32S && c10 % 32 == 0 && c13 % 32 == 0;
+  if (!fuse_up) upsample("model.11", s10, cat12.slice(0, c10));
+  View cat18 = net_.new_view(H / 16, W / 16, c17 + c13);          // [conv17, model.13]
+  View s13 = cat18.slice(c17, c13);
+  c3k2("model.13", cat12, kNeckShortcut, &s13, fuse_up ? &s10 : nullptr);
+  if (!fuse_up) upsample("model.14", s13, cat15.slice(0, c13));
+  View a16 = c3k2("model.16", cat15, kNeckShortcut, nullptr, fuse_up ? &s13 : nullptr);
+  View s17 = cat18.slice(0, c17);
+  conv("model.17.conv", a16, 2, &s17, nullptr);
+  View a19 = c3k2("model.19", cat18, kNeckShortcut, nullptr);
+  View s20 = cat21.slice(0, c20);
+  conv("model.20.conv", a19, 2, &s20, nullptr);
+  View a22 = c3k2("model.22", cat21, kNeckShortcut, nullptr);
+  Levels lv;
+  lv.in = {a16, a19, a22};
+  lv.strides = {8.f, 16.f, 32.f};
+  lv.det_pfx = "model.23";
+  lv.dw_cls = true;
+  return lv;
 }
 
 YoloTrunk::Levels YoloTrunk::build(const View& img) {
@@ -102,31 +314,8 @@ YoloTrunk::Levels YoloTrunk::build(const View& img) {
   // yolov8.yaml (Detect = model.22 on 15 / 18 / 21) or yolov8-p2.yaml (one more Upsample + Concat + C2f at stride 4 in the neck,
   // Detect = model.28 on 18 / 21 / 24 / 27): told apart by the tensor names, like the reference's model yaml does
   const bool p2 = net_.has("model.28.cv2.0.0.conv.weight");
-  auto upsample = [&](const std::string& name, const View& src, const View& dst) {
-    Op op;
-    op.kind = Op::UPSAMPLE;
-    op.name = name;
-    op.family = "upsample2x_kernel";
-    op.in = src;
-    op.out = dst;
-    ops_.push_back(op);
-  };
-  // ---- SPPF (model.9): cv1 -> 3 cascaded pools -> cv2; its output is written into the slice `s9` of the last Concat
-  auto sppf = [&](const View& a8, const View& s9) {
-    const int cm = cout_of("model.9.cv1.conv");
-    View sp = net_.new_view(a8.h, a8.w, 4 * cm);
-    View sp0 = sp.slice(0, cm);
-    conv("model.9.cv1.conv", a8, 1, &sp0, nullptr);
-    Op op;
-    op.kind = Op::POOL;
-    op.name = "model.9.m";
-    op.family = "sppf_pool_kernel";
-    op.in = sp0;
-    op.out = sp;
-    ops_.push_back(op);
-    conv("model.9.cv2.conv", sp, 1, &s9, nullptr);
-    net_.set_layer_view("model.9", s9);
-  };
+  // yolo11.yaml: C2PSA at model.10 and Detect (depthwise class branch) at model.23 -- names no YOLOv8 file has
+  if (net_.has("model.10.m.0.attn.qkv.conv.weight") && net_.has("model.23.cv3.0.0.0.conv.weight")) return build_yolo11(a0);
   Levels lv;
   if (!p2) {
     // ---- backbone ----
@@ -378,6 +567,14 @@ void YoloTrunk::run_op(const Op& op, int nb, hipStream_t s) const {
       launch_upsample2x(dtype_, op.in.ptr, nb, op.in.h, op.in.w, op.in.c, op.in.cstride, op.in.coff, op.out.ptr,
                         op.out.cstride, op.out.coff, s);
       break;
+    case Op::DWCONV:
+      launch_rt_dwconv(fmt, RtMap{op.in.ptr, op.in.h, op.in.w, op.in.cstride, op.in.coff, op.in.c},
+                       RtMap{op.out.ptr, op.out.h, op.out.w, op.out.cstride, op.out.coff, op.out.c}, nb, 3, 1, op.dw_w, op.dw_bias, op.dw_act, op.sat, s);
+      break;
+    case Op::ATTN:
+      launch_psa_attention(fmt, RtMap{op.in.ptr, op.in.h, op.in.w, op.in.cstride, op.in.coff, op.in.c},
+                           RtMap{op.out.ptr, op.out.h, op.out.w, op.out.cstride, op.out.coff, op.out.c}, nb, op.heads, op.dw_w, op.dw_bias, op.sat, s);
+      break;
   }
 }
 
@@ -419,6 +616,13 @@ void set_batch_ops(std::vector<Op>& ops, int nb, size_t es, bool pad_skip_on) {
     } else if (op.kind == Op::UPSAMPLE) {
       op.flops = 0;
       op.bytes = (double)nb * op.in.h * op.in.w * op.in.c * 5 * es;
+    } else if (op.kind == Op::DWCONV) {
+      op.flops = 2.0 * 9 * nb * op.in.h * op.in.w * op.in.c;
+      op.bytes = 2.0 * nb * op.in.h * op.in.w * op.in.c * es;
+    } else if (op.kind == Op::ATTN) {               // q.k (depth 32) + p.v (width 64) per query-key pair and head, + pe; the qkv map in, the output map out
+      const double T = (double)op.in.h * op.in.w;
+      op.flops = nb * (op.heads * T * T * 2.0 * (32 + 64) + 2.0 * 9 * T * op.out.c);
+      op.bytes = nb * T * (op.in.c + op.out.c) * es;
     }
   }
 }

@@ -2,7 +2,8 @@
 // the Detect layer. One builder for every family that runs it: the YOLOv8 / P2 detector (Detect on its outputs, detector.cpp)
 // and YOLOv8-RTDETR (an RTDETRDecoder on model.15 / 18 / 21, rtdetr.cpp). It emits the trunk's launches into the caller's op
 // list, owns the fused front (stem + model.1 + model.2.cv1 in one launch on the split-f16x3 path) and the stand-alone forms it
-// hides, and launches its four op kinds.
+// hides, and launches its op kinds. YOLO11's trunk (yolo11.yaml: C3k2 blocks, C2PSA attention at model.10, Detect at model.23) is the
+// third graph it builds, on the same convolution kernels plus a depthwise 3x3 and the attention kernel.
 #pragma once
 #include <string>
 #include <vector>
@@ -12,7 +13,7 @@
 namespace gtx {
 
 struct Op : OpInfo {
-  enum Kind { CONV, STEM, POOL, UPSAMPLE } kind = CONV;
+  enum Kind { CONV, STEM, POOL, UPSAMPLE, DWCONV, ATTN } kind = CONV;
   ConvGroup grp{};       // CONV
   ConvConfig cfg{};
   // STEM / POOL / UPSAMPLE parameters
@@ -23,6 +24,11 @@ struct Op : OpInfo {
   float stem_scale = 1.f;      // split-f16x3 stem: inverse of the weights' power-of-two scaling
   const void* front_wpk = nullptr;   // the same weights packed for the front stage of model.1 (ConvProblem::front_w)
   float front_scale = 1.f;
+  // DWCONV (depthwise 3x3 on `in` -> `out`; act 0 none, 1 SiLU) / ATTN (C2PSA's attention on the qkv map `in`, dw_w / dw_bias = its pe)
+  const float* dw_w = nullptr;       // [9][C] tap-major
+  const float* dw_bias = nullptr;
+  int dw_act = 0, heads = 0;
+  int* sat = nullptr;                // the net's saturation flag (split-f16x3 path)
   // rows of the output that depend on the frame (Detector::plan_pad_skip), as tile rows per group member; count 0 = all
   int ty_first[kMaxGroup] = {0}, ty_count[kMaxGroup] = {0};
 };
@@ -38,7 +44,8 @@ class YoloTrunk {
   struct Levels {
     std::vector<View> in;        // the Detect layer's inputs, finest level first
     std::vector<float> strides;
-    std::string det_pfx;         // where the yaml puts Detect: model.22 (yolov8.yaml) or model.28 (yolov8-p2.yaml)
+    std::string det_pfx;         // where the yaml puts Detect: model.22 (yolov8.yaml), model.28 (yolov8-p2.yaml) or model.23 (yolo11.yaml)
+    bool dw_cls = false;         // yolo11.yaml's Detect: the class branch is DWConv + 1x1 Conv twice
   };
   // Emits model.0 .. the last neck C2f on img ([N][H][W][4] RGB0 bytes). The P2 graph is chosen when the tensors hold its Detect.
   Levels build(const View& img);
@@ -55,9 +62,20 @@ class YoloTrunk {
   // p is the placeholder of a released buffer that no layer_output() has re-created yet (no device address)
   bool hidden(const void* p) const;
   void clear() { unfused_.clear(); hidden_.clear(); }
+  // Depthwise 3x3 convolution "<name>.weight" [C][1][3][3] (+ bias), stride 1, SiLU or no activation (YOLO11's DWConv, used by its Detect)
+  View dwconv(const std::string& name, const View& x, int act);
 
  private:
   View c2f(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src = nullptr);
+  // ---- YOLO11 (yolo11.yaml): the graph of build() when the tensors hold its C2PSA and its Detect at model.23
+  Levels build_yolo11(const View& a0);
+  View conv_act(const std::string& name, const View& x, int act, const View* out_slice, const View* residual);
+  View bottleneck_half(const std::string& m, const View& src, const View& dst, bool shortcut);
+  View c3k(const std::string& m, const View& src, const View& dst, bool shortcut);
+  View c3k2(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src = nullptr);
+  View c2psa(const std::string& pfx, const View& x, const View* out_slice);
+  void upsample(const std::string& name, const View& src, const View& dst);
+  void sppf(const View& a8, const View& s9);
   void fuse_front();         // model.1 (3x3 stride 2) + model.2.cv1 (1x1) as one launch on the split-f16x3 path
   void fuse_stem();          // model.0 (the stem) computed inside model.1's launch: its output never reaches HBM
   void release_hidden_layers();

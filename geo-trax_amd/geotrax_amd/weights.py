@@ -237,6 +237,147 @@ def synthetic_yolov8_p2(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: 
     return t
 
 
+# --------------------------------------------------------------------------- YOLO11 (cfg/models/11/yolo11.yaml)
+# What `YOLO("yolo11s.pt")` fine-tunes to under the reference's ultralytics: Conv / C3k2 backbone (model.0-8), SPPF (9), C2PSA (10:
+# position-sensitive attention), a neck of C3k2 blocks (13 / 16 / 19 / 22) and Detect = model.23 on [16, 19, 22] whose class branch
+# is DWConv + Conv(1x1) twice. C3k2 is C2f with half-width Bottlenecks (c3k=False) or C3k blocks (c3k=True: 6 / 8 / 22 for n and s,
+# everywhere for m / l / x) as m.{k}. Restated from ultralytics' public source; not checked against the package (it is not installed).
+
+YOLO11_SCALES = {"n": (0.50, 0.25, 1024), "s": (0.50, 0.50, 1024), "m": (0.50, 1.00, 512),
+                 "l": (1.00, 1.00, 512), "x": (1.00, 1.50, 512)}   # yolo11.yaml: depth, width, max_channels
+
+YOLO11_TOPOLOGY = "yolo11 detect (yolo11{n,s,m,l,x}: C3k2 backbone + neck, C2PSA = model.10, Detect = model.23 on model.16 / 19 / 22)"
+
+
+def has_yolo11_blocks(tensors: dict) -> bool:
+    """True when the names hold what no YOLOv8 file has: an attention block (`.attn.`) or a Detect class branch that starts with a
+    DWConv + Conv pair (`model.<k>.cv3.0.0.0.conv`). Which graph it is, and whether this build runs it: check_yolo11()."""
+    for k in tensors:
+        if ".attn." in k:
+            return True
+        p = k.split(".")
+        if len(p) >= 8 and p[0] == "model" and p[2] == "cv3" and p[4:7] == ["0", "0", "conv"]:
+            return True
+    return False
+
+
+def check_yolo11(tensors: dict) -> None:
+    """Raises NotImplementedError unless the names and shapes are those of a fused yolo11.yaml detect model. Other graphs built from
+    the same blocks (YOLO12's A2C2f, YOLO26's end-to-end Detect, yolo11-cls with C2PSA at model.9, -seg / -obb / -pose heads with a
+    cv4 or proto branch) are never built into the wrong network."""
+    no = NotImplementedError(f"checkpoint with attention / depthwise-Detect blocks in another arrangement than yolo11.yaml's: of that "
+                             f"family only {YOLO11_TOPOLOGY} is implemented")
+    shape = lambda n: tuple(np.shape(tensors[n])) if n in tensors else None
+    need = [f"model.{i}.conv.weight" for i in (0, 1, 3, 5, 7, 17, 20)]
+    need += [f"model.{i}.{c}.conv.weight" for i in (2, 4, 6, 8, 13, 16, 19, 22) for c in ("cv1", "cv2", "m.0.cv1", "m.0.cv2")]
+    need += ["model.9.cv1.conv.weight", "model.9.cv2.conv.weight", "model.10.cv1.conv.weight", "model.10.cv2.conv.weight"]
+    need += [f"model.10.m.0.{c}.conv.weight" for c in ("attn.qkv", "attn.proj", "attn.pe", "ffn.0", "ffn.1")]
+    for l in range(3):
+        need += [f"model.23.cv2.{l}.0.conv.weight", f"model.23.cv2.{l}.1.conv.weight", f"model.23.cv2.{l}.2.weight",
+                 f"model.23.cv3.{l}.0.0.conv.weight", f"model.23.cv3.{l}.0.1.conv.weight", f"model.23.cv3.{l}.1.0.conv.weight",
+                 f"model.23.cv3.{l}.1.1.conv.weight", f"model.23.cv3.{l}.2.weight"]
+    if any(n not in tensors for n in need):
+        raise no
+    for k in tensors:
+        p = k.split(".")
+        if p[0] != "model" or len(p) < 3 or not p[1].isdigit():
+            continue
+        i = int(p[1])
+        if i > 23 or (".attn." in k and i != 10) or (i == 23 and (p[2] not in ("cv2", "cv3", "dfl") or (p[2] in ("cv2", "cv3") and p[3] not in "012"))):
+            raise no
+        if i in (11, 12, 14, 15, 18, 21):                  # Upsample / Concat: no tensors
+            raise no
+    c = shape("model.10.cv1.conv.weight")[0] // 2
+    if c % 64 or shape("model.10.m.0.attn.qkv.conv.weight") != (2 * c, c, 1, 1) or shape("model.10.m.0.attn.pe.conv.weight") != (c, 1, 3, 3):
+        raise no                                           # heads = c / 64, key_dim 32 (attn_ratio 0.5), head_dim 64
+    if shape("model.23.cv2.0.2.weight")[0] != 64 or shape("model.23.cv3.0.0.0.conv.weight")[1] != 1 or shape("model.23.cv3.0.1.0.conv.weight")[1] != 1:
+        raise no
+
+
+def yolo11_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
+    """(tensor name, OIHW shape, has_act) for every conv of a fused YOLO11 detect model (depthwise convs: (C, 1, 3, 3))."""
+    depth, width, maxc = YOLO11_SCALES[scale]
+    ch = lambda c: _make_divisible(min(c, maxc) * width)
+    n = max(round(2 * depth), 1)                           # every C3k2 and the C2PSA have 2 repeats in the yaml
+    force_c3k = scale in "mlx"                             # parse_model: c3k=True in every C3k2 of the larger scales
+    specs: list[tuple[str, tuple[int, ...], bool]] = []
+
+    def conv(name, cin, cout, k, act=True):
+        specs.append((name, (cout, cin, k, k), act))
+
+    def dwconv(name, c, act):
+        specs.append((name, (c, 1, 3, 3), act))
+
+    def bottleneck(p, c, e):
+        conv(p + ".cv1.conv", c, int(c * e), 3)
+        conv(p + ".cv2.conv", int(c * e), c, 3)
+
+    def c3k2(pfx, cin, cout, c3k, e=0.5):
+        c = int(cout * e)
+        conv(f"{pfx}.cv1.conv", cin, 2 * c, 1)
+        for k in range(n):
+            m = f"{pfx}.m.{k}"
+            if c3k or force_c3k:
+                h = int(c * 0.5)
+                conv(m + ".cv1.conv", c, h, 1)
+                conv(m + ".cv2.conv", c, h, 1)
+                conv(m + ".cv3.conv", 2 * h, c, 1)
+                for j in range(2):
+                    bottleneck(f"{m}.m.{j}", h, 1.0)
+            else:
+                bottleneck(m, c, 0.5)
+        conv(f"{pfx}.cv2.conv", (2 + n) * c, cout, 1)
+
+    c1, c2, c3, c4, c5 = ch(64), ch(128), ch(256), ch(512), ch(1024)
+    conv("model.0.conv", 3, c1, 3)
+    conv("model.1.conv", c1, c2, 3)
+    c3k2("model.2", c2, c3, False, 0.25)
+    conv("model.3.conv", c3, c3, 3)
+    c3k2("model.4", c3, c4, False, 0.25)
+    conv("model.5.conv", c4, c4, 3)
+    c3k2("model.6", c4, c4, True)
+    conv("model.7.conv", c4, c5, 3)
+    c3k2("model.8", c5, c5, True)
+    conv("model.9.cv1.conv", c5, c5 // 2, 1)
+    conv("model.9.cv2.conv", c5 * 2, c5, 1)
+    c = c5 // 2                                            # C2PSA: heads = c / 64, key_dim 32, head_dim 64
+    conv("model.10.cv1.conv", c5, 2 * c, 1)
+    for k in range(n):
+        m = f"model.10.m.{k}"
+        conv(m + ".attn.qkv.conv", c, c + 2 * (c // 64) * 32, 1, act=False)
+        conv(m + ".attn.proj.conv", c, c, 1, act=False)
+        dwconv(m + ".attn.pe.conv", c, False)
+        conv(m + ".ffn.0.conv", c, 2 * c, 1)
+        conv(m + ".ffn.1.conv", 2 * c, c, 1, act=False)
+    conv("model.10.cv2.conv", 2 * c, c5, 1)
+    c3k2("model.13", c5 + c4, c4, False)
+    c3k2("model.16", c4 + c4, c3, False)
+    conv("model.17.conv", c3, c3, 3)
+    c3k2("model.19", c3 + c4, c4, False)
+    conv("model.20.conv", c4, c4, 3)
+    c3k2("model.22", c4 + c5, c5, True)
+    cb = max(16, c3 // 4, 64)
+    cc = max(c3, min(nc, 100))
+    for l, cin in enumerate((c3, c4, c5)):
+        conv(f"model.23.cv2.{l}.0.conv", cin, cb, 3)
+        conv(f"model.23.cv2.{l}.1.conv", cb, cb, 3)
+        specs.append((f"model.23.cv2.{l}.2", (64, cb, 1, 1), False))
+        dwconv(f"model.23.cv3.{l}.0.0.conv", cin, True)
+        conv(f"model.23.cv3.{l}.0.1.conv", cin, cc, 1)
+        dwconv(f"model.23.cv3.{l}.1.0.conv", cc, True)
+        conv(f"model.23.cv3.{l}.1.1.conv", cc, cc, 1)
+        specs.append((f"model.23.cv3.{l}.2", (nc, cc, 1, 1), False))
+    return specs
+
+
+def synthetic_yolo11(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0, gain: float = 1.7,
+                     box_decay: float | tuple = 0.3, level_bias: tuple = (0.0, 0.0, 0.0), box_weight_scale: float = 0.3) -> dict[str, np.ndarray]:
+    """Seeded random fused weights of the YOLO11 architecture, drawn like synthetic_yolov8's (same knobs, the draws in the order of
+    yolo11_layer_specs): weights ~ N(0, g^2 / fan_in) with g = gain in front of a SiLU and 1 for the activation-free layers (qkv,
+    proj, pe, ffn.1, Detect's last 1x1s); a depthwise layer's fan-in is its 9 taps."""
+    return _draw_yolov8(np.random.default_rng(seed), yolo11_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias, box_weight_scale)
+
+
 def calibrate_cls_bias(tensors: dict[str, np.ndarray], raw_logits: np.ndarray, conf: float, target: int) -> dict[str, np.ndarray]:
     """Returns a copy of `tensors` whose class-logit biases are shifted by one constant so that
     about `target` anchors of the probed frame clear `conf`. raw_logits: [anchors, nc] class
@@ -273,9 +414,13 @@ RTDETR_TOPOLOGIES = ("rtdetr-l (HGNetv2 + AIFI + CCFM, RTDETRDecoder = model.28)
 
 def detector_topology(tensors: dict) -> tuple[str, str]:
     """(graph, head prefix) of a detector checkpoint, read off the tensor names the way the reference reads its model yaml:
-    ("yolov8", "model.22"), ("yolov8-p2", "model.28"), ("rtdetr-l", "model.28") or ("yolov8-rtdetr", "model.22"). An RT-DETR
-    layout other than those two (rtdetr-x with its decoder at model.32, ResNet backbones, ...) raises NotImplementedError."""
+    ("yolov8", "model.22"), ("yolov8-p2", "model.28"), ("yolo11", "model.23"), ("rtdetr-l", "model.28") or ("yolov8-rtdetr", "model.22").
+    An RT-DETR layout other than those two (rtdetr-x with its decoder at model.32, ResNet backbones, ...) raises NotImplementedError,
+    and so does a file with YOLO11's blocks (attention, a depthwise Detect class branch) in another arrangement than yolo11.yaml's."""
     if not is_rtdetr(tensors):
+        if has_yolo11_blocks(tensors):
+            check_yolo11(tensors)                          # raises for YOLO12 / YOLO26 / yolo11-cls, -seg, -obb, -pose ...
+            return "yolo11", "model.23"
         return ("yolov8-p2", "model.28") if is_yolov8_p2(tensors) else ("yolov8", "model.22")
     decs = sorted({k.split(".")[1] for k in tensors if k.startswith("model.") and ".decoder.layers." in k and k.split(".")[2] == "decoder"})
     has = lambda pfx: any(k.startswith(pfx) for k in tensors)

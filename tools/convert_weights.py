@@ -10,6 +10,8 @@ Conv+BN pairs are fused with ultralytics' own `model.fuse()`; tensor names are t
 state_dict keys (`model.0.conv.weight`, `model.0.conv.bias`, ... `model.22.cv3.2.2.bias`).
 A YOLOv8-P2 checkpoint (yolov8<scale>-p2.yaml, geo-trax's train.sh `-p`) goes through the same path unchanged: its fused
 state_dict ends in `model.28.cv3.3.2.bias` (Detect on four levels), which is how geotrax_amd.weights.is_yolov8_p2 tells it apart.
+A YOLO11 detect checkpoint (yolo11<scale>.yaml) goes through unchanged as well: its fused state_dict has `model.10.m.0.attn.qkv.conv.*`
+and ends in `model.23.cv3.2.2.bias`; DWConv and the activation-free Convs (qkv, proj, pe, ffn.1) fold their BN like any Conv.
 
 An RT-DETR checkpoint (the reference's `RTDETR` branch, geotrax/extract.py:222-225; rtdetr-l topology) keeps its state_dict names
 too (`model.0.stem1.conv.weight` ... `model.28.decoder.layers.5.norm3.bias`); what `fuse()` leaves unfused -- RepConv's two
