@@ -1,7 +1,7 @@
-// YOLOv8 / YOLO11 (detect) graph builder + executor: the trunk (yolo_trunk.cpp: backbone + neck of ultralytics' cfg/models/v8/yolov8.yaml,
-// yolov8-p2.yaml or cfg/models/11/yolo11.yaml) and the Detect layer on its outputs (model.22, model.28 of the P2 graph: a fourth level
-// at stride 4, or model.23 of YOLO11: a class branch of depthwise + pointwise pairs);
-// channel widths and bottleneck counts are read off the tensor shapes, so every v8 scale (n/s/m/l/x) loads unchanged.
+// YOLOv8 / YOLO11 (detect) graph builder + executor: the trunk (yolo_trunk.cpp walks the layer table of ultralytics' cfg/models/v8/yolov8.yaml,
+// yolov8-p2.yaml or cfg/models/11/yolo11.yaml, whichever the tensor names tell) and the Detect layer on the levels, strides and prefix the
+// table's Detect row gives (model.22, model.28 of the P2 graph: a fourth level at stride 4, or model.23 of YOLO11: a class branch of
+// depthwise + pointwise pairs); channel widths and bottleneck counts are read off the tensor shapes, so every scale (n/s/m/l/x) loads unchanged.
 #include "detector.hpp"
 #include "split_format.hpp"
 

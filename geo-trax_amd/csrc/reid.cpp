@@ -3,7 +3,7 @@
 // What upstream does per frame (ultralytics >= 8.4.80, trackers/bot_sort.py ReID.__call__), and where it is done here:
 //   crops = [save_one_box(det, img, save=False) for det in xywh2xyxy(dets[:, :4])]   -> reid_crop_box (host)
 //   ClassificationPredictor.preprocess: classify_transforms(imgsz) on each crop         -> reid_resample_coeffs (host) + reid_crop_kernel
-//   model(crops, embed=[len(model) - 2]): adaptive_avg_pool2d(model.8 output)           -> the conv graph below + reid_pool_kernel
+//   model(crops, embed=[len(model) - 2]): adaptive_avg_pool2d(model.8 output)           -> YoloTrunk's backbone rows + reid_pool_kernel
 // Choices restated from memory of the pinned upstream rather than pinned by a test against it (the resample is pinned against PIL):
 //   - the box chain: Boxes.xywh in float32, then float64 (BOTSORT.init_track concatenates the boxes with np.arange), save_one_box's
 //     gain 1.02 / pad 10 / .long() truncation and clip to the frame;
@@ -93,7 +93,7 @@ void reid_crop_box(const float b[4], int h, int w, int out[4]) {
 }
 
 Embedder::Embedder(gtx_ctx* ctx, int imgsz, int max_crops, bool fp32_split)
-    : NetRuntime(ctx, fp32_split ? DT_F32S : DT_F32, 4, max_crops), S_(imgsz) {
+    : NetRuntime(ctx, fp32_split ? DT_F32S : DT_F32, 4, max_crops), S_(imgsz), trunk_(*this, ops_, DT_F32) {
   GTX_CHECK(imgsz >= 32 && imgsz <= 256 && imgsz % 32 == 0, "reid imgsz must be a multiple of 32 in [32, 256] (got %d)", imgsz);
   GTX_CHECK(max_crops >= 1, "max_crops must be positive");
   GTX_HIP(hipSetDevice(ctx->device));
@@ -116,83 +116,12 @@ void Embedder::conv_config_rule(const std::string& name, ConvConfig& cfg) const 
   if (cfg.variant == 3 || cfg.variant == 4) { cfg.variant = 2; cfg.th = 8; }
 }
 
-View Embedder::conv(const std::string& name, const View& x, int stride, const View* out_slice, const View* residual) {
-  const HostTensor& w = tensor(name + ".weight");
-  GTX_CHECK(w.shape.size() == 4 && w.shape[2] == w.shape[3], "%s: expected OIHW square kernel", name.c_str());
-  const int cout = (int)w.shape[0], ks = (int)w.shape[2];
-  ConvArgs a;
-  a.stride = stride; a.out_slice = out_slice; a.residual = residual;
-  a.out_pixels = (long)x.n * ((x.h + 2 * (ks / 2) - ks) / stride + 1) * ((x.w + 2 * (ks / 2) - ks) / stride + 1);
-  return emit_conv(ops_, name, w.data.data(), cout, (int)w.shape[1], ks, bias_of(name, cout), x, a);
-}
-
-// C2f(shortcut=True): cv1 -> split -> n bottlenecks (3x3, 3x3, + residual) -> concat -> cv2 (the detector's c2f, without its fusions)
-View Embedder::c2f(const std::string& pfx, const View& x) {
-  const HostTensor& w1 = tensor(pfx + ".cv1.conv.weight");
-  const int c = (int)w1.shape[0] / 2;
-  int n = 0;
-  while (has(pfx + ".m." + std::to_string(n) + ".cv1.conv.weight")) ++n;
-  View cat = new_view(x.h, x.w, (2 + n) * c);
-  View first = cat.slice(0, 2 * c);
-  conv(pfx + ".cv1.conv", x, 1, &first, nullptr);
-  for (int k = 0; k < n; ++k) {
-    View tmp = new_view(x.h, x.w, c);
-    const std::string m = pfx + ".m." + std::to_string(k);
-    View src = cat.slice((1 + k) * c, c);
-    View dst = cat.slice((2 + k) * c, c);
-    conv(m + ".cv1.conv", src, 1, &tmp, nullptr);
-    conv(m + ".cv2.conv", tmp, 1, &dst, &src);
-  }
-  View out = conv(pfx + ".cv2.conv", cat, 1, nullptr, nullptr);
-  layer_views_[pfx] = out;
-  return out;
-}
-
+// model.0-8 through the trunk's walk (no fusion: fuse() is never called, so the stem gets no front-packed weights)
 void Embedder::build_graph() {
   img_ = new_view(S_, S_, 1);                                  // [N][S][S] uchar4: 4 bytes per pixel
   img_.plain = true;
   alloc_sat_flag();
-  const HostTensor& w0 = tensor("model.0.conv.weight");
-  GTX_CHECK(w0.shape.size() == 4 && w0.shape[1] == 3 && w0.shape[2] == 3 && w0.shape[3] == 3, "model.0 must be a 3x3 conv on 3 channels");
-  const int c0 = (int)w0.shape[0];
-  View a0 = new_view(S_ / 2, S_ / 2, c0);
-  {
-    std::vector<float> w27((size_t)27 * c0);
-    for (int o = 0; o < c0; ++o)
-      for (int i = 0; i < 3; ++i)
-        for (int y = 0; y < 3; ++y)
-          for (int x = 0; x < 3; ++x) w27[(size_t)((y * 3 + x) * 3 + i) * c0 + o] = w0.data[(((size_t)o * 3 + i) * 3 + y) * 3 + x];
-    float* dw = (float*)alloc(w27.size() * sizeof(float));
-    GTX_HIP(hipMemcpy(dw, w27.data(), w27.size() * sizeof(float), hipMemcpyHostToDevice));
-    std::vector<float> b(c0, 0.f);
-    if (has("model.0.conv.bias")) b = tensor("model.0.conv.bias").data;
-    float* db = (float*)alloc((size_t)(c0 + 31) / 32 * 32 * sizeof(float));
-    GTX_HIP(hipMemcpy(db, b.data(), c0 * sizeof(float), hipMemcpyHostToDevice));
-    Op op;
-    op.kind = Op::STEM;
-    op.name = "model.0.conv";
-    op.family = fmt_ == DT_F32S ? "stem_split_kernel" : "stem_kernel";
-    op.in = img_;
-    op.out = a0;
-    op.w27 = dw;
-    op.bias = db;
-    if (fmt_ == DT_F32S) {
-      const std::vector<uint16_t> pk = pack_stem_weights_split(w27.data(), c0, &op.stem_scale);
-      void* dp = alloc(pk.size() * 2);
-      GTX_HIP(hipMemcpy(dp, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
-      op.wpk = dp;
-    }
-    ops_.push_back(op);
-    layer_views_["model.0.conv"] = a0;
-  }
-  View a = conv("model.1.conv", a0, 2, nullptr, nullptr);
-  a = c2f("model.2", a);
-  a = conv("model.3.conv", a, 2, nullptr, nullptr);
-  a = c2f("model.4", a);
-  a = conv("model.5.conv", a, 2, nullptr, nullptr);
-  a = c2f("model.6", a);
-  a = conv("model.7.conv", a, 2, nullptr, nullptr);
-  last_ = c2f("model.8", a);
+  last_ = trunk_.build(img_, YoloTrunk::cls_backbone(), false).in[0];
   dim_ = last_.c;
 }
 
@@ -210,14 +139,6 @@ void Embedder::set_batch(int nb) {
   if (nb == cur_nb_) return;
   set_batch_ops(ops_, nb, 4, false);
   cur_nb_ = nb;
-}
-
-void Embedder::launch_op(size_t i, int nb, hipStream_t s) {
-  const Op& op = ops_[i];
-  if (op.kind == Op::STEM)
-    launch_stem(fmt_, op.in.ptr, nb, op.in.h, op.in.w, op.w27, op.bias, op.wpk, op.out.c, op.out.ptr, op.out.h, op.out.w, s, op.stem_scale);
-  else
-    conv_launch(op.grp, op.cfg, s);
 }
 
 // Crop table + coefficients of the pass on the host, one copy to the device, then chunk by chunk of max_crops: crop kernel ->

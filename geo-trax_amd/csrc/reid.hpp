@@ -2,7 +2,8 @@
 // detection, its last map average-pooled into one vector per crop. Stands in for ultralytics' trackers/bot_sort.py ReID
 // (`with_reid: true, model: <cls checkpoint>` of BoT-SORT, Deep OC-SORT and TrackTrack; geotrax/cfg/default.yaml:379, :421, :470):
 // save_one_box per detection -> ClassificationPredictor (classify_transforms(imgsz)) -> model(embed=[len(model) - 2]).
-// The convolutions are the detector's kernels with the batch dimension equal to the number of crops; the Classify head is never run.
+// The graph is the YOLO trunk's (yolo_trunk.hpp: the backbone rows of its yolov8.yaml table) with the batch dimension equal to the
+// number of crops; the Classify head is never run.
 #pragma once
 #include <map>
 #include <memory>
@@ -37,18 +38,17 @@ class Embedder : public NetRuntime {
  private:
   size_t op_count() const override { return ops_.size(); }
   const OpInfo& op_info(size_t i) const override { return ops_[i]; }
-  void launch_op(size_t i, int nb, hipStream_t s) override;
+  void launch_op(size_t i, int nb, hipStream_t s) override { trunk_.run_op(ops_[i], nb, s); }
   std::unique_ptr<NetRuntime> make_exact() const override;
   void release_graph() override { ops_.clear(); }
   void conv_config_rule(const std::string& name, ConvConfig& cfg) const override;
-  View conv(const std::string& name, const View& x, int stride, const View* out_slice, const View* residual);
-  View c2f(const std::string& pfx, const View& x);
   void build_graph();
   void set_batch(int nb) override;
   void enqueue(int n_total);
 
   int S_;
   std::vector<Op> ops_;
+  YoloTrunk trunk_;          // builds model.0-8 (the first rows of yolov8.yaml's table) into ops_ and launches them
   View img_, last_;
   int dim_ = 0;
   // the pass in flight (kept for the exact re-run of a saturated pass)

@@ -1,6 +1,9 @@
-// YoloTrunk (yolo_trunk.hpp): the YOLOv8 / YOLOv8-P2 backbone + neck, shared by the YOLOv8 detector and YOLOv8-RTDETR. Layer
-// topology follows ultralytics' cfg/models/v8/yolov8.yaml (backbone 0-9, head 10-21) or yolov8-p2.yaml (head 10-27, one more
-// stage at stride 4); channel widths and bottleneck counts are read off the tensor shapes, so every v8 scale (n/s/m/l/x) loads unchanged.
+// YoloTrunk (yolo_trunk.hpp): the backbone + neck of the YOLO detectors, built by one walk (build()) over a layer table that restates
+// the family's model yaml row by row: ultralytics' cfg/models/v8/yolov8.yaml (kYolov8: Detect = model.22; YOLOv8-RTDETR puts its
+// decoder there; rows 0-8 are the YOLOv8-cls backbone of the ReID embedder), v8/yolov8-p2.yaml (kYolov8P2: one more stage at stride 4,
+// Detect = model.28) and 11/yolo11.yaml (kYolo11: C3k2 blocks, C2PSA = model.10, Detect = model.23). Channel widths, bottleneck counts
+// and c3k-or-not are read off the tensor shapes, so every scale (n/s/m/l/x) loads unchanged. A new family is one more table and one
+// more rule in choose_graph(); a new module is one more case in build().
 #include "yolo_trunk.hpp"
 #include "rtdetr_kernels.hpp"
 #include "split_format.hpp"
@@ -8,6 +11,48 @@
 #include <algorithm>
 
 namespace gtx {
+
+namespace {
+using R = TrunkRow;
+constexpr R kYolov8[] = {
+    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},
+    {4, R::BLOCK, {-1}, true},      {5, R::CONV, {-1}, false},        {6, R::BLOCK, {-1}, true},       {7, R::CONV, {-1}, false},
+    {8, R::BLOCK, {-1}, true},      {9, R::SPPF, {-1}, false},        {10, R::UPSAMPLE, {-1}, false},  {11, R::CONCAT, {-1, 6}, false},
+    {12, R::BLOCK, {-1}, false},    {13, R::UPSAMPLE, {-1}, false},   {14, R::CONCAT, {-1, 4}, false}, {15, R::BLOCK, {-1}, false},
+    {16, R::CONV, {-1}, false},     {17, R::CONCAT, {-1, 12}, false}, {18, R::BLOCK, {-1}, false},     {19, R::CONV, {-1}, false},
+    {20, R::CONCAT, {-1, 9}, false}, {21, R::BLOCK, {-1}, false},     {22, R::DETECT, {15, 18, 21}, false}};
+constexpr int kClsBackboneRows = 9;   // yolov8-cls.yaml: model.0-8 are yolov8.yaml's
+constexpr R kYolov8P2[] = {
+    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},
+    {4, R::BLOCK, {-1}, true},      {5, R::CONV, {-1}, false},        {6, R::BLOCK, {-1}, true},       {7, R::CONV, {-1}, false},
+    {8, R::BLOCK, {-1}, true},      {9, R::SPPF, {-1}, false},        {10, R::UPSAMPLE, {-1}, false},  {11, R::CONCAT, {-1, 6}, false},
+    {12, R::BLOCK, {-1}, false},    {13, R::UPSAMPLE, {-1}, false},   {14, R::CONCAT, {-1, 4}, false}, {15, R::BLOCK, {-1}, false},
+    {16, R::UPSAMPLE, {-1}, false}, {17, R::CONCAT, {-1, 2}, false},  {18, R::BLOCK, {-1}, false},     {19, R::CONV, {-1}, false},
+    {20, R::CONCAT, {-1, 15}, false}, {21, R::BLOCK, {-1}, false},    {22, R::CONV, {-1}, false},      {23, R::CONCAT, {-1, 12}, false},
+    {24, R::BLOCK, {-1}, false},    {25, R::CONV, {-1}, false},       {26, R::CONCAT, {-1, 9}, false}, {27, R::BLOCK, {-1}, false},
+    {28, R::DETECT, {18, 21, 24, 27}, false}};
+// YOLO11's shortcuts: on in the backbone; in the neck kNeckShortcut, which no tensor tells (taken as off, as in yolov8.yaml's neck;
+// tests/yolo11_ref.py names the doubt).
+constexpr bool kNeckShortcut = false;
+constexpr R kYolo11[] = {
+    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},
+    {4, R::BLOCK, {-1}, true},      {5, R::CONV, {-1}, false},        {6, R::BLOCK, {-1}, true},       {7, R::CONV, {-1}, false},
+    {8, R::BLOCK, {-1}, true},      {9, R::SPPF, {-1}, false},        {10, R::C2PSA, {-1}, false},     {11, R::UPSAMPLE, {-1}, false},
+    {12, R::CONCAT, {-1, 6}, false}, {13, R::BLOCK, {-1}, kNeckShortcut}, {14, R::UPSAMPLE, {-1}, false}, {15, R::CONCAT, {-1, 4}, false},
+    {16, R::BLOCK, {-1}, kNeckShortcut}, {17, R::CONV, {-1}, false},  {18, R::CONCAT, {-1, 13}, false}, {19, R::BLOCK, {-1}, kNeckShortcut},
+    {20, R::CONV, {-1}, false},     {21, R::CONCAT, {-1, 10}, false}, {22, R::BLOCK, {-1}, kNeckShortcut}, {23, R::DETECT, {16, 19, 22}, false}};
+template <int N> constexpr TrunkGraph graph_of(const R (&rows)[N], bool dw_cls) { return TrunkGraph{rows, N, dw_cls}; }
+}  // namespace
+
+TrunkGraph YoloTrunk::cls_backbone() { return TrunkGraph{kYolov8, kClsBackboneRows, false}; }
+
+// Which yaml the tensors were built from, told apart by their names like the reference's model yaml does
+TrunkGraph YoloTrunk::choose_graph() const {
+  // yolo11.yaml: C2PSA at model.10 and Detect (depthwise class branch) at model.23 -- names no YOLOv8 file has
+  if (net_.has("model.10.m.0.attn.qkv.conv.weight") && net_.has("model.23.cv3.0.0.0.conv.weight")) return graph_of(kYolo11, true);
+  // yolov8-p2.yaml: Detect = model.28 on four levels; else yolov8.yaml (Detect, or YOLOv8-RTDETR's decoder, = model.22)
+  return net_.has("model.28.cv2.0.0.conv.weight") ? graph_of(kYolov8P2, false) : graph_of(kYolov8, false);
+}
 
 View YoloTrunk::conv(const std::string& name, const View& x, int stride, const View* out_slice, const View* residual, const View* up_src) {
   GTX_CHECK(net_.format() != DT_F32S || !up_src || !up_src->plain, "%s: a plain fp32 tensor cannot feed a split convolution", name.c_str());
@@ -26,28 +71,6 @@ View YoloTrunk::conv(const std::string& name, const View& x, int stride, const V
   return out;
 }
 
-View YoloTrunk::c2f(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src) {
-  const HostTensor& w1 = net_.tensor(pfx + ".cv1.conv.weight");
-  const int c = (int)w1.shape[0] / 2;
-  int n = 0;
-  while (net_.has(pfx + ".m." + std::to_string(n) + ".cv1.conv.weight")) ++n;
-  View cat = net_.new_view(x.h, x.w, (2 + n) * c);
-  View first = cat.slice(0, 2 * c);
-  conv(pfx + ".cv1.conv", x, 1, &first, nullptr, up_src);
-  for (int k = 0; k < n; ++k) {
-    // a buffer of its own per bottleneck: rows that no launch rewrites (plan_pad_skip) must keep ONE producer's values
-    View tmp = net_.new_view(x.h, x.w, c);
-    const std::string m = pfx + ".m." + std::to_string(k);
-    View src = cat.slice((1 + k) * c, c);
-    View dst = cat.slice((2 + k) * c, c);
-    conv(m + ".cv1.conv", src, 1, &tmp, nullptr);
-    conv(m + ".cv2.conv", tmp, 1, &dst, shortcut ? &src : nullptr);
-  }
-  View out = conv(pfx + ".cv2.conv", cat, 1, out_slice, nullptr);
-  net_.set_layer_view(pfx, out);
-  return out;
-}
-
 void YoloTrunk::upsample(const std::string& name, const View& src, const View& dst) {
   Op op;
   op.kind = Op::UPSAMPLE;
@@ -58,24 +81,23 @@ void YoloTrunk::upsample(const std::string& name, const View& src, const View& d
   ops_.push_back(op);
 }
 
-// ---- SPPF (model.9): cv1 -> 3 cascaded pools -> cv2; its output is written into the slice `s9` of the last Concat
-void YoloTrunk::sppf(const View& a8, const View& s9) {
-  const int cm = (int)net_.tensor("model.9.cv1.conv.weight").shape[0];
-  View sp = net_.new_view(a8.h, a8.w, 4 * cm);
+// ---- SPPF: cv1 -> 3 cascaded pools -> cv2, written into `out` (its slice of the Concat that lists it, or a view of its own)
+void YoloTrunk::sppf(const std::string& pfx, const View& x, const View& out) {
+  const int cm = (int)net_.tensor(pfx + ".cv1.conv.weight").shape[0];
+  View sp = net_.new_view(x.h, x.w, 4 * cm);
   View sp0 = sp.slice(0, cm);
-  conv("model.9.cv1.conv", a8, 1, &sp0, nullptr);
+  conv(pfx + ".cv1.conv", x, 1, &sp0, nullptr);
   Op op;
   op.kind = Op::POOL;
-  op.name = "model.9.m";
+  op.name = pfx + ".m";
   op.family = "sppf_pool_kernel";
   op.in = sp0;
   op.out = sp;
   ops_.push_back(op);
-  conv("model.9.cv2.conv", sp, 1, &s9, nullptr);
-  net_.set_layer_view("model.9", s9);
+  conv(pfx + ".cv2.conv", sp, 1, &out, nullptr);
+  net_.set_layer_view(pfx, out);
 }
 
-// ============================================================================ YOLO11 (ultralytics cfg/models/11/yolo11.yaml)
 // One stride-1 Conv op with the given activation (0 none, 1 SiLU). The convolution kernels take channel counts that are
 // multiples of 16: a narrower layer (the 8-channel hidden layer of scale n's model.2 bottleneck) gets zero output channels
 // appended -- SiLU(0) = 0 -- and its consumer zero input weights for them, which changes no sum.
@@ -97,9 +119,10 @@ View YoloTrunk::conv_act(const std::string& name, const View& x, int act, const 
   return net_.emit_conv(ops_, name, wp.data(), cout_p, cin_p, ks, bp.data(), x, a);
 }
 
-// Bottleneck(c, c, shortcut, k = (3, 3), e): src -> dst (+ src); the hidden width is read off cv1 (c / 2 in C3k2, c in C3k)
-View YoloTrunk::bottleneck_half(const std::string& m, const View& src, const View& dst, bool shortcut) {
-  const View tmp = conv_act(m + ".cv1.conv", src, 1, nullptr, nullptr);   // a buffer of its own, as in c2f()
+// Bottleneck(c, c, shortcut, k = (3, 3), e): src -> dst (+ src); the hidden width is read off cv1 (c in C2f and C3k, c / 2 in C3k2)
+View YoloTrunk::bottleneck(const std::string& m, const View& src, const View& dst, bool shortcut) {
+  // a buffer of its own per bottleneck: rows that no launch rewrites (plan_pad_skip) must keep ONE producer's values
+  const View tmp = conv_act(m + ".cv1.conv", src, 1, nullptr, nullptr);
   return conv_act(m + ".cv2.conv", tmp, 1, &dst, shortcut ? &src : nullptr);
 }
 
@@ -114,15 +137,16 @@ View YoloTrunk::c3k(const std::string& m, const View& src, const View& dst, bool
   conv_act(m + ".cv1.conv", src, 1, &y, nullptr);
   for (int j = 0; j < n; ++j) {
     View nxt = j + 1 == n ? left : net_.new_view(src.h, src.w, ch);
-    bottleneck_half(m + ".m." + std::to_string(j), y, nxt, shortcut);
+    bottleneck(m + ".m." + std::to_string(j), y, nxt, shortcut);
     y = nxt;
   }
   conv_act(m + ".cv2.conv", src, 1, &right, nullptr);
   return conv_act(m + ".cv3.conv", cat, 1, &dst, nullptr);
 }
 
-// C3k2 = C2f whose m.{k} is a half-width Bottleneck (c3k = False) or a C3k (c3k = True: the block has a cv3)
-View YoloTrunk::c3k2(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src) {
+// C2f / C3k2: cv1 -> a | b, n blocks m.{k} chained from b with every output appended, cv2 on the concatenation. m.{k} is a Bottleneck
+// (C2f: full hidden width; C3k2 with c3k = False: half of it) or a C3k (C3k2 with c3k = True: the block has a cv3).
+View YoloTrunk::c2f(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src) {
   const int c = (int)net_.tensor(pfx + ".cv1.conv.weight").shape[0] / 2;
   int n = 0;
   while (net_.has(pfx + ".m." + std::to_string(n) + ".cv1.conv.weight")) ++n;
@@ -132,7 +156,7 @@ View YoloTrunk::c3k2(const std::string& pfx, const View& x, bool shortcut, const
   for (int k = 0; k < n; ++k) {
     const std::string m = pfx + ".m." + std::to_string(k);
     View src = cat.slice((1 + k) * c, c), dst = cat.slice((2 + k) * c, c);
-    if (net_.has(m + ".cv3.conv.weight")) c3k(m, src, dst, shortcut); else bottleneck_half(m, src, dst, shortcut);
+    if (net_.has(m + ".cv3.conv.weight")) c3k(m, src, dst, shortcut); else bottleneck(m, src, dst, shortcut);
   }
   View out = conv(pfx + ".cv2.conv", cat, 1, out_slice, nullptr);
   net_.set_layer_view(pfx, out);
@@ -210,201 +234,143 @@ View YoloTrunk::dwconv(const std::string& name, const View& x, int act) {
   return op.out;
 }
 
-// Backbone 0-10 (C3k2 stages, SPPF, C2PSA), neck 11-22, Detect = model.23 on 16 / 19 / 22. Widths, repeats and c3k-or-not are read
-// off the tensors, so every scale (n / s / m / l / x) loads unchanged. Shortcuts: on in the backbone; in the neck kNeckShortcut, which
-// no tensor tells (taken as off, as in yolov8.yaml's neck; tests/yolo11_ref.py names the doubt).
-YoloTrunk::Levels YoloTrunk::build_yolo11(const View& a0) {
-  constexpr bool kNeckShortcut = false;
-  const int H = a0.h * 2, W = a0.w * 2, fmt = net_.format();
-  auto cout_of = [&](const std::string& n) { return (int)net_.tensor(n + ".weight").shape[0]; };
-  const int c4 = cout_of("model.4.cv2.conv"), c6 = cout_of("model.6.cv2.conv"), c9 = cout_of("model.9.cv2.conv");
-  const int c10 = cout_of("model.10.cv2.conv"), c13 = cout_of("model.13.cv2.conv");
-  const int c17 = cout_of("model.17.conv"), c20 = cout_of("model.20.conv");
-  View a1 = conv("model.1.conv", a0, 2, nullptr, nullptr);
-  View a2 = c3k2("model.2", a1, true, nullptr);
-  View a3 = conv("model.3.conv", a2, 2, nullptr, nullptr);
-  View cat15 = net_.new_view(H / 8, W / 8, c13 + c4);             // [up14, model.4]
-  View s4 = cat15.slice(c13, c4);
-  View a4 = c3k2("model.4", a3, true, &s4);
-  View a5 = conv("model.5.conv", a4, 2, nullptr, nullptr);
-  View cat12 = net_.new_view(H / 16, W / 16, c10 + c6);           // [up11, model.6]
-  View s6 = cat12.slice(c10, c6);
-  View a6 = c3k2("model.6", a5, true, &s6);
-  View a7 = conv("model.7.conv", a6, 2, nullptr, nullptr);
-  View a8 = c3k2("model.8", a7, true, nullptr);
-  View s9 = net_.new_view(H / 32, W / 32, c9);
-  sppf(a8, s9);
-  View cat21 = net_.new_view(H / 32, W / 32, c20 + c10);          // [conv20, model.10]
-  View s10 = cat21.slice(c20, c10);
-  c2psa("model.10", s9, &s10);
-  // Upsample + Concat in front of model.13 / model.16: read in place by the C3k2's first 1x1 on the split-f16x3 path (as in yolov8.yaml)
-  const bool fuse_up = fmt == DT_F32S && c10 % 32 == 0 && c13 % 32 == 0;
-  if (!fuse_up) upsample("model.11", s10, cat12.slice(0, c10));
-  View cat18 = net_.new_view(H / 16, W / 16, c17 + c13);          // [conv17, model.13]
-  View s13 = cat18.slice(c17, c13);
-  c3k2("model.13", cat12, kNeckShortcut, &s13, fuse_up ? &s10 : nullptr);
-  if (!fuse_up) upsample("model.14", s13, cat15.slice(0, c13));
-  View a16 = c3k2("model.16", cat15, kNeckShortcut, nullptr, fuse_up ? &s13 : nullptr);
-  View s17 = cat18.slice(0, c17);
-  conv("model.17.conv", a16, 2, &s17, nullptr);
-  View a19 = c3k2("model.19", cat18, kNeckShortcut, nullptr);
-  View s20 = cat21.slice(0, c20);
-  conv("model.20.conv", a19, 2, &s20, nullptr);
-  View a22 = c3k2("model.22", cat21, kNeckShortcut, nullptr);
-  Levels lv;
-  lv.in = {a16, a19, a22};
-  lv.strides = {8.f, 16.f, 32.f};
-  lv.det_pfx = "model.23";
-  lv.dw_cls = true;
-  return lv;
+// ---- layer 0: the stem (dedicated 3-channel kernel). front: also the weights packed for fuse_stem()
+View YoloTrunk::stem(const View& img, bool front) {
+  const int fmt = net_.format();
+  const HostTensor& w0 = net_.tensor("model.0.conv.weight");
+  GTX_CHECK(w0.shape.size() == 4 && w0.shape[1] == 3 && w0.shape[2] == 3 && w0.shape[3] == 3, "model.0 must be a 3x3 conv on 3 channels");
+  const int c0 = (int)w0.shape[0];
+  View a0 = net_.new_view(img.h / 2, img.w / 2, c0);
+  std::vector<float> w27((size_t)27 * c0);
+  for (int o = 0; o < c0; ++o)
+    for (int i = 0; i < 3; ++i)
+      for (int y = 0; y < 3; ++y)
+        for (int x = 0; x < 3; ++x)
+          w27[(size_t)((y * 3 + x) * 3 + i) * c0 + o] = w0.data[(((size_t)o * 3 + i) * 3 + y) * 3 + x];
+  float* dw = (float*)net_.alloc(w27.size() * sizeof(float));
+  GTX_HIP(hipMemcpy(dw, w27.data(), w27.size() * sizeof(float), hipMemcpyHostToDevice));
+  std::vector<float> b(c0, 0.f);
+  if (net_.has("model.0.conv.bias")) b = net_.tensor("model.0.conv.bias").data;
+  float* db = (float*)net_.alloc((size_t)(c0 + 31) / 32 * 32 * sizeof(float));   // zero-filled up to whole 32-channel groups (the MFMA stems read a group's bias unconditionally)
+  GTX_HIP(hipMemcpy(db, b.data(), c0 * sizeof(float), hipMemcpyHostToDevice));
+  auto upload_u16 = [&](const std::vector<uint16_t>& pk) {
+    void* dp = net_.alloc(pk.size() * 2);
+    GTX_HIP(hipMemcpy(dp, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
+    return dp;
+  };
+  Op op;
+  op.kind = Op::STEM;
+  op.name = "model.0.conv";
+  op.family = dtype_ == DT_F16 ? "stem_mfma_kernel" : (fmt == DT_F32S ? "stem_split_kernel" : "stem_kernel");
+  op.in = img;
+  op.out = a0;
+  op.w27 = dw;
+  op.bias = db;
+  if (dtype_ == DT_F16) {
+    op.wpk = upload_u16(pack_stem_weights_f16(w27.data(), c0));
+  } else if (fmt == DT_F32S) {
+    op.wpk = upload_u16(pack_stem_weights_split(w27.data(), c0, &op.stem_scale));
+    if (front && c0 % 16 == 0) op.front_wpk = upload_u16(pack_front_weights_split(w27.data(), c0, &op.front_scale));   // fuse_stem(): whole 16-channel K chunks of model.1
+  }
+  ops_.push_back(op);
+  net_.set_layer_view("model.0.conv", a0);
+  return a0;
 }
 
-YoloTrunk::Levels YoloTrunk::build(const View& img) {
-  const int H = img.h, W = img.w;
-  const int fmt = net_.format();
+// The walk over a layer table, in yaml order. No Concat op exists: a row that a Concat lists writes straight into its slice of that
+// Concat's buffer (members in the yaml's `from` order, widths off the tensor shapes), which the Concat's consumer reads whole.
+YoloTrunk::Levels YoloTrunk::build(const View& img, const TrunkGraph& g, bool front) {
+  const int n = g.n;
+  auto name = [](int i) { return "model." + std::to_string(i); };
+  auto cout_of = [&](const std::string& t) { return (int)net_.tensor(t + ".weight").shape[0]; };
+  auto from = [&](const TrunkRow& r, int k) { return r.from[k] < 0 ? r.i + r.from[k] : r.from[k]; };   // row 0: -1, the image
+  auto n_from = [](const TrunkRow& r) { int k = 0; while (k < 4 && r.from[k] != 0) ++k; return k; };
 
-  // ---- layer 0: stem (dedicated 3-channel kernel) ----
-  const HostTensor& w0 = net_.tensor("model.0.conv.weight");
-  GTX_CHECK(w0.shape.size() == 4 && w0.shape[1] == 3 && w0.shape[2] == 3, "model.0 must be a 3x3 conv on 3 channels");
-  const int c0 = (int)w0.shape[0];
-  View a0 = net_.new_view(H / 2, W / 2, c0);
-  {
-    std::vector<float> w27((size_t)27 * c0);
-    for (int o = 0; o < c0; ++o)
-      for (int i = 0; i < 3; ++i)
-        for (int y = 0; y < 3; ++y)
-          for (int x = 0; x < 3; ++x)
-            w27[(size_t)((y * 3 + x) * 3 + i) * c0 + o] = w0.data[(((size_t)o * 3 + i) * 3 + y) * 3 + x];
-    float* dw = (float*)net_.alloc(w27.size() * sizeof(float));
-    GTX_HIP(hipMemcpy(dw, w27.data(), w27.size() * sizeof(float), hipMemcpyHostToDevice));
-    std::vector<float> b(c0, 0.f);
-    if (net_.has("model.0.conv.bias")) b = net_.tensor("model.0.conv.bias").data;
-    float* db = (float*)net_.alloc((size_t)(c0 + 31) / 32 * 32 * sizeof(float));   // zero-filled up to whole 32-channel groups (the MFMA stems read a group's bias unconditionally)
-    GTX_HIP(hipMemcpy(db, b.data(), c0 * sizeof(float), hipMemcpyHostToDevice));
-    Op op;
-    op.kind = Op::STEM;
-    op.name = "model.0.conv";
-    op.family = dtype_ == DT_F16 ? "stem_mfma_kernel" : (fmt == DT_F32S ? "stem_split_kernel" : "stem_kernel");
-    op.in = img;
-    op.out = a0;
-    op.w27 = dw;
-    op.bias = db;
-    if (dtype_ == DT_F16) {
-      const std::vector<uint16_t> pk = pack_stem_weights_f16(w27.data(), c0);
-      void* dp = net_.alloc(pk.size() * 2);
-      GTX_HIP(hipMemcpy(dp, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
-      op.wpk = dp;
-    } else if (fmt == DT_F32S) {
-      const std::vector<uint16_t> pk = pack_stem_weights_split(w27.data(), c0, &op.stem_scale);
-      void* dp = net_.alloc(pk.size() * 2);
-      GTX_HIP(hipMemcpy(dp, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
-      op.wpk = dp;
-      if (c0 % 16 == 0) {                       // fuse_stem(): whole 16-channel K chunks of model.1
-        const std::vector<uint16_t> fk = pack_front_weights_split(w27.data(), c0, &op.front_scale);
-        void* fp = net_.alloc(fk.size() * 2);
-        GTX_HIP(hipMemcpy(fp, fk.data(), fk.size() * 2, hipMemcpyHostToDevice));
-        op.front_wpk = fp;
-      }
+  // ---- output width of every row; the Concat (at most one) that lists it and its channel offset there
+  std::vector<int> width(n, 0), cat_of(n, -1), cat_off(n, 0);
+  bool fuse_up = net_.format() == DT_F32S;
+  for (int i = 0; i < n; ++i) {
+    const TrunkRow& r = g.rows[i];
+    GTX_CHECK(r.i == i && n_from(r) >= 1, "internal: layer table row %d", i);
+    for (int k = 0; k < n_from(r); ++k) GTX_CHECK(from(r, k) < i && (from(r, k) >= 0 || i == 0), "internal: model.%d reads a later layer", i);
+    switch (r.mod) {
+      case TrunkRow::CONV: width[i] = cout_of(name(i) + ".conv"); break;
+      case TrunkRow::BLOCK: case TrunkRow::SPPF: case TrunkRow::C2PSA: width[i] = cout_of(name(i) + ".cv2.conv"); break;
+      case TrunkRow::UPSAMPLE:
+        // torch's Upsample + Concat in front of a block: the split-f16x3 path reads the low-resolution tensor in place from the
+        // block's first 1x1 conv (ConvProblem::in2) when every such tensor of the graph is whole 32-channel groups (all or nothing),
+        // the other arithmetics write the upsampled copy
+        width[i] = width[from(r, 0)];
+        fuse_up = fuse_up && width[i] % 32 == 0;
+        break;
+      case TrunkRow::CONCAT:
+        for (int k = 0; k < n_from(r); ++k) {
+          const int m = from(r, k);
+          GTX_CHECK(cat_of[m] < 0, "internal: model.%d feeds two Concats (model.%d and model.%d)", m, cat_of[m], i);
+          cat_of[m] = i;
+          cat_off[m] = width[i];
+          width[i] += width[m];
+        }
+        break;
+      case TrunkRow::DETECT: break;
     }
-    ops_.push_back(op);
-    net_.set_layer_view("model.0.conv", a0);
   }
 
-  auto cout_of = [&](const std::string& n) { return (int)net_.tensor(n + ".weight").shape[0]; };
-  // yolov8.yaml (Detect = model.22 on 15 / 18 / 21) or yolov8-p2.yaml (one more Upsample + Concat + C2f at stride 4 in the neck,
-  // Detect = model.28 on 18 / 21 / 24 / 27): told apart by the tensor names, like the reference's model yaml does
-  const bool p2 = net_.has("model.28.cv2.0.0.conv.weight");
-  // yolo11.yaml: C2PSA at model.10 and Detect (depthwise class branch) at model.23 -- names no YOLOv8 file has
-  if (net_.has("model.10.m.0.attn.qkv.conv.weight") && net_.has("model.23.cv3.0.0.0.conv.weight")) return build_yolo11(a0);
+  // ---- the ops
+  std::vector<View> out(n);         // per row; a Concat's: its whole buffer, allocated when its first member is placed
+  std::vector<int> up_src(n, -1);   // per Concat under fuse_up: the row whose 2x upsampling its leading slice would hold (never written)
+  View slot;
+  auto place = [&](int i, int h, int w) -> const View* {   // where row i writes: null = a view of its own
+    if (cat_of[i] < 0) return nullptr;
+    View& c = out[cat_of[i]];
+    if (!c.ptr) c = net_.new_view(h, w, width[cat_of[i]]);
+    GTX_CHECK(c.h == h && c.w == w, "model.%d: %dx%d does not fit Concat model.%d (%dx%d)", i, w, h, cat_of[i], c.w, c.h);
+    slot = c.slice(cat_off[i], width[i]);
+    return &slot;
+  };
   Levels lv;
-  if (!p2) {
-    // ---- backbone ----
-    View a1 = conv("model.1.conv", a0, 2, nullptr, nullptr);
-    View a2 = c2f("model.2", a1, true, nullptr);
-    View a3 = conv("model.3.conv", a2, 2, nullptr, nullptr);
-    // model.4 output feeds conv5 and Concat(14) = [up13, model.4]
-    const int c4 = cout_of("model.4.cv2.conv"), c6 = cout_of("model.6.cv2.conv");
-    const int c9 = cout_of("model.9.cv2.conv"), c12 = cout_of("model.12.cv2.conv");
-    const int c16 = cout_of("model.16.conv"), c19 = cout_of("model.19.conv");
-    View cat14 = net_.new_view(H / 8, W / 8, c12 + c4);
-    View s4 = cat14.slice(c12, c4);
-    View a4 = c2f("model.4", a3, true, &s4);
-    View a5 = conv("model.5.conv", a4, 2, nullptr, nullptr);
-    View cat11 = net_.new_view(H / 16, W / 16, c9 + c6);
-    View s6 = cat11.slice(c9, c6);
-    View a6 = c2f("model.6", a5, true, &s6);
-    View a7 = conv("model.7.conv", a6, 2, nullptr, nullptr);
-    View a8 = c2f("model.8", a7, true, nullptr);
-    // SPPF output lives in Concat(20) = [conv19, model.9]
-    View cat20 = net_.new_view(H / 32, W / 32, c19 + c9);
-    View s9 = cat20.slice(c19, c9);
-    sppf(a8, s9);
-    // ---- head ----
-    // torch's Upsample + Concat in front of model.12 / model.15: the split-f16x3 path reads the low-resolution tensor in
-    // place from the C2f's first 1x1 conv (ConvProblem::in2), the other arithmetics write the upsampled copy
-    const bool fuse_up = fmt == DT_F32S && c9 % 32 == 0 && c12 % 32 == 0;
-    if (!fuse_up) upsample("model.10", s9, cat11.slice(0, c9));
-    View cat17 = net_.new_view(H / 16, W / 16, c16 + c12);
-    View s12 = cat17.slice(c16, c12);
-    c2f("model.12", cat11, false, &s12, fuse_up ? &s9 : nullptr);
-    if (!fuse_up) upsample("model.13", s12, cat14.slice(0, c12));
-    View a15 = c2f("model.15", cat14, false, nullptr, fuse_up ? &s12 : nullptr);
-    View s16 = cat17.slice(0, c16);
-    conv("model.16.conv", a15, 2, &s16, nullptr);
-    View a18 = c2f("model.18", cat17, false, nullptr);
-    View s19 = cat20.slice(0, c19);
-    conv("model.19.conv", a18, 2, &s19, nullptr);
-    View a21 = c2f("model.21", cat20, false, nullptr);
-    lv.in = {a15, a18, a21};
-    lv.strides = {8.f, 16.f, 32.f};
-    lv.det_pfx = "model.22";
-  } else {
-    // ---- backbone (as yolov8.yaml); model.2's output also feeds Concat(17) = [up16, model.2] ----
-    const int c2 = cout_of("model.2.cv2.conv"), c4 = cout_of("model.4.cv2.conv"), c6 = cout_of("model.6.cv2.conv");
-    const int c9 = cout_of("model.9.cv2.conv"), c12 = cout_of("model.12.cv2.conv"), c15 = cout_of("model.15.cv2.conv");
-    const int c19 = cout_of("model.19.conv"), c22 = cout_of("model.22.conv"), c25 = cout_of("model.25.conv");
-    View a1 = conv("model.1.conv", a0, 2, nullptr, nullptr);
-    View cat17 = net_.new_view(H / 4, W / 4, c15 + c2);
-    View s2 = cat17.slice(c15, c2);
-    View a2 = c2f("model.2", a1, true, &s2);
-    View a3 = conv("model.3.conv", a2, 2, nullptr, nullptr);
-    View cat14 = net_.new_view(H / 8, W / 8, c12 + c4);           // [up13, model.4]
-    View s4 = cat14.slice(c12, c4);
-    View a4 = c2f("model.4", a3, true, &s4);
-    View a5 = conv("model.5.conv", a4, 2, nullptr, nullptr);
-    View cat11 = net_.new_view(H / 16, W / 16, c9 + c6);          // [up10, model.6]
-    View s6 = cat11.slice(c9, c6);
-    View a6 = c2f("model.6", a5, true, &s6);
-    View a7 = conv("model.7.conv", a6, 2, nullptr, nullptr);
-    View a8 = c2f("model.8", a7, true, nullptr);
-    View cat26 = net_.new_view(H / 32, W / 32, c25 + c9);         // [conv25, model.9]
-    View s9 = cat26.slice(c25, c9);
-    sppf(a8, s9);
-    // ---- head: three Upsample + Concat + C2f stages down to stride 4, then three stride-2 Conv + Concat + C2f back up ----
-    const bool fuse_up = fmt == DT_F32S && c9 % 32 == 0 && c12 % 32 == 0 && c15 % 32 == 0;
-    if (!fuse_up) upsample("model.10", s9, cat11.slice(0, c9));
-    View cat23 = net_.new_view(H / 16, W / 16, c22 + c12);        // [conv22, model.12]
-    View s12 = cat23.slice(c22, c12);
-    c2f("model.12", cat11, false, &s12, fuse_up ? &s9 : nullptr);
-    if (!fuse_up) upsample("model.13", s12, cat14.slice(0, c12));
-    View cat20 = net_.new_view(H / 8, W / 8, c19 + c15);          // [conv19, model.15]
-    View s15 = cat20.slice(c19, c15);
-    c2f("model.15", cat14, false, &s15, fuse_up ? &s12 : nullptr);
-    if (!fuse_up) upsample("model.16", s15, cat17.slice(0, c15));
-    View a18 = c2f("model.18", cat17, false, nullptr, fuse_up ? &s15 : nullptr);
-    View s19 = cat20.slice(0, c19);
-    conv("model.19.conv", a18, 2, &s19, nullptr);
-    View a21 = c2f("model.21", cat20, false, nullptr);
-    View s22 = cat23.slice(0, c22);
-    conv("model.22.conv", a21, 2, &s22, nullptr);
-    View a24 = c2f("model.24", cat23, false, nullptr);
-    View s25 = cat26.slice(0, c25);
-    conv("model.25.conv", a24, 2, &s25, nullptr);
-    View a27 = c2f("model.27", cat26, false, nullptr);
-    lv.in = {a18, a21, a24, a27};
-    lv.strides = {4.f, 8.f, 16.f, 32.f};
-    lv.det_pfx = "model.28";
+  lv.dw_cls = g.dw_cls;
+  for (int i = 0; i < n; ++i) {
+    const TrunkRow& r = g.rows[i];
+    const int f = from(r, 0);
+    const View& x = i == 0 ? img : out[f];
+    GTX_CHECK(i == 0 || r.mod == TrunkRow::DETECT || r.mod == TrunkRow::CONCAT || x.ptr, "internal: model.%d reads model.%d, which has no output", i, f);
+    GTX_CHECK(i == 0 || up_src[f] < 0 || r.mod == TrunkRow::BLOCK, "internal: only a C2f / C3k2 reads an upsampled source in place (model.%d)", i);
+    switch (r.mod) {
+      case TrunkRow::CONV:
+        if (i == 0) { out[i] = stem(img, front); break; }
+        out[i] = conv(name(i) + ".conv", x, 2, place(i, (x.h - 1) / 2 + 1, (x.w - 1) / 2 + 1), nullptr);
+        break;
+      case TrunkRow::BLOCK:
+        out[i] = c2f(name(i), x, r.shortcut, place(i, x.h, x.w), up_src[f] >= 0 ? &out[up_src[f]] : nullptr);
+        break;
+      case TrunkRow::SPPF: {
+        const View* s = place(i, x.h, x.w);
+        out[i] = s ? *s : net_.new_view(x.h, x.w, width[i]);
+        sppf(name(i), x, out[i]);
+        break;
+      }
+      case TrunkRow::C2PSA: out[i] = c2psa(name(i), x, place(i, x.h, x.w)); break;
+      case TrunkRow::UPSAMPLE: {
+        const View* s = place(i, 2 * x.h, 2 * x.w);
+        GTX_CHECK(s && cat_off[i] == 0, "internal: Upsample model.%d must lead a Concat", i);
+        if (!fuse_up) upsample(name(i), x, *s);
+        break;
+      }
+      case TrunkRow::CONCAT:
+        GTX_CHECK(out[i].ptr, "internal: Concat model.%d has no member in front of it", i);
+        if (fuse_up && g.rows[f].mod == TrunkRow::UPSAMPLE) up_src[i] = from(g.rows[f], 0);
+        break;
+      case TrunkRow::DETECT:
+        for (int k = 0; k < n_from(r); ++k) {
+          lv.in.push_back(out[from(r, k)]);
+          lv.strides.push_back((float)(img.h / lv.in.back().h));
+        }
+        lv.det_pfx = name(i);
+        break;
+    }
   }
+  if (lv.in.empty()) lv.in.push_back(out[n - 1]);   // a table without a Detect row (the cls backbone): its last layer
   return lv;
 }
 

@@ -1,9 +1,9 @@
-// The YOLOv8 trunk: ultralytics' yolov8.yaml backbone + neck (model.0-21) or yolov8-p2.yaml's (model.0-27), everything in front of
-// the Detect layer. One builder for every family that runs it: the YOLOv8 / P2 detector (Detect on its outputs, detector.cpp)
-// and YOLOv8-RTDETR (an RTDETRDecoder on model.15 / 18 / 21, rtdetr.cpp). It emits the trunk's launches into the caller's op
-// list, owns the fused front (stem + model.1 + model.2.cv1 in one launch on the split-f16x3 path) and the stand-alone forms it
-// hides, and launches its op kinds. YOLO11's trunk (yolo11.yaml: C3k2 blocks, C2PSA attention at model.10, Detect at model.23) is the
-// third graph it builds, on the same convolution kernels plus a depthwise 3x3 and the attention kernel.
+// The YOLO trunk: everything in front of the Detect layer of ultralytics' yolov8.yaml (model.0-21), yolov8-p2.yaml (model.0-27) and
+// yolo11.yaml (model.0-22), and the YOLOv8-cls backbone (model.0-8). Each graph is a constant table with one row per yaml layer
+// (yolo_trunk.cpp); one walk over a table emits its launches into the caller's op list. Every family that runs a trunk builds
+// through it: the YOLOv8 / P2 / YOLO11 detector (Detect on its outputs, detector.cpp), YOLOv8-RTDETR (an RTDETRDecoder on model.15 /
+// 18 / 21, rtdetr.cpp) and the ReID embedder (reid.cpp). It also owns the fused front (stem + model.1 + model.2.cv1 in one launch on
+// the split-f16x3 path) with the stand-alone forms it hides, and launches its op kinds.
 #pragma once
 #include <string>
 #include <vector>
@@ -33,6 +33,20 @@ struct Op : OpInfo {
   int ty_first[kMaxGroup] = {0}, ty_count[kMaxGroup] = {0};
 };
 
+// One row of a trunk's layer table: a layer of the model yaml, as the yaml writes it
+struct TrunkRow {
+  enum Module { CONV, BLOCK, SPPF, C2PSA, UPSAMPLE, CONCAT, DETECT };
+  int i;            // the layer index: its tensors are "model.<i>.*"
+  Module mod;       // CONV: Conv 3x3 stride 2 (row 0: the stem); BLOCK: C2f / C3k2 (which one, the tensors tell)
+  int from[4];      // the yaml's `from`: -1 = the row above (row 0: the image), else a layer index; 0 ends the list
+  bool shortcut;    // BLOCK: the bottlenecks add their input
+};
+struct TrunkGraph {
+  const TrunkRow* rows;
+  int n;
+  bool dw_cls;      // yolo11.yaml's Detect: the class branch is DWConv + 1x1 Conv twice
+};
+
 // N of every conv op (and the rows it computes) and every op's flops / bytes for a pass at batch nb (es: bytes per activation)
 void set_batch_ops(std::vector<Op>& ops, int nb, size_t es, bool pad_skip_on);
 
@@ -42,13 +56,18 @@ class YoloTrunk {
   YoloTrunk(NetRuntime& net, std::vector<Op>& ops, int dtype) : net_(net), ops_(ops), dtype_(dtype) {}
 
   struct Levels {
-    std::vector<View> in;        // the Detect layer's inputs, finest level first
-    std::vector<float> strides;
-    std::string det_pfx;         // where the yaml puts Detect: model.22 (yolov8.yaml), model.28 (yolov8-p2.yaml) or model.23 (yolo11.yaml)
-    bool dw_cls = false;         // yolo11.yaml's Detect: the class branch is DWConv + 1x1 Conv twice
+    std::vector<View> in;        // the Detect row's inputs, finest level first (a table without one: its last layer's output)
+    std::vector<float> strides;  // net height / level height
+    std::string det_pfx;         // the Detect row: model.22 (yolov8.yaml), model.28 (yolov8-p2.yaml) or model.23 (yolo11.yaml)
+    bool dw_cls = false;         // TrunkGraph::dw_cls
   };
-  // Emits model.0 .. the last neck C2f on img ([N][H][W][4] RGB0 bytes). The P2 graph is chosen when the tensors hold its Detect.
-  Levels build(const View& img);
+  // The graph the tensors were built from, by their names: yolo11.yaml, yolov8-p2.yaml, else yolov8.yaml
+  TrunkGraph choose_graph() const;
+  static TrunkGraph cls_backbone();   // model.0-8 of yolov8.yaml = yolov8-cls.yaml's backbone
+  // Emits every row of g in front of its Detect on img ([N][H][W][4] RGB0 bytes). front: the stem also gets its weights packed for
+  // fuse() (a net that never calls fuse() passes false).
+  Levels build(const View& img, const TrunkGraph& g, bool front = true);
+  Levels build(const View& img) { return build(img, choose_graph()); }
   // One Conv op (SiLU). up_src: the leading up_src->c channels of x are the 2x nearest upsampling of *up_src and are read from
   // there (split-f16x3 1x1 convs; ConvProblem::in2) -- the slice of x they would occupy is never written.
   View conv(const std::string& name, const View& x, int stride, const View* out_slice, const View* residual = nullptr,
@@ -66,16 +85,15 @@ class YoloTrunk {
   View dwconv(const std::string& name, const View& x, int act);
 
  private:
-  View c2f(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src = nullptr);
-  // ---- YOLO11 (yolo11.yaml): the graph of build() when the tensors hold its C2PSA and its Detect at model.23
-  Levels build_yolo11(const View& a0);
+  View stem(const View& img, bool front);
+  View c2f(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src);   // C2f and C3k2
+  // one stride-1 Conv op with activation `act`; channel counts that are no multiple of 16 are zero-padded (YOLO11-n's 8-channel hidden layer)
   View conv_act(const std::string& name, const View& x, int act, const View* out_slice, const View* residual);
-  View bottleneck_half(const std::string& m, const View& src, const View& dst, bool shortcut);
+  View bottleneck(const std::string& m, const View& src, const View& dst, bool shortcut);
   View c3k(const std::string& m, const View& src, const View& dst, bool shortcut);
-  View c3k2(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src = nullptr);
   View c2psa(const std::string& pfx, const View& x, const View* out_slice);
   void upsample(const std::string& name, const View& src, const View& dst);
-  void sppf(const View& a8, const View& s9);
+  void sppf(const std::string& pfx, const View& x, const View& out);
   void fuse_front();         // model.1 (3x3 stride 2) + model.2.cv1 (1x1) as one launch on the split-f16x3 path
   void fuse_stem();          // model.0 (the stem) computed inside model.1's launch: its output never reaches HBM
   void release_hidden_layers();

@@ -10,6 +10,7 @@ ultralytics' ``fuse_conv_and_bn``.
 """
 from __future__ import annotations
 
+import re
 from pathlib import Path
 
 import numpy as np
@@ -66,52 +67,197 @@ def _make_divisible(x: float, d: int = 8) -> int:
     return int(np.ceil(x / d) * d)
 
 
-def yolov8_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
-    """(tensor name, OIHW shape, has_act) for every conv of a fused YOLOv8 detect model."""
-    depth, width, maxc = SCALES[scale]
-    ch = lambda c: _make_divisible(min(c, maxc) * width)
-    rep = lambda n: max(round(n * depth), 1)
+# --------------------------------------------------------------------------- the model yamls, as tables
+# One row per yaml layer, written as the yaml writes it: (from, repeats, module, args). A new family is one more table here (and
+# one in csrc/yolo_trunk.cpp); _parse_model() turns a table into the spec list every function below returns.
+_UP = (-1, 1, "Upsample", (None, 2, "nearest"))
+_V8_BACKBONE = [                                           # model.0-8 of yolov8.yaml, yolov8-p2.yaml and yolov8-cls.yaml
+    (-1, 1, "Conv", (64, 3, 2)),
+    (-1, 1, "Conv", (128, 3, 2)),
+    (-1, 3, "C2f", (128, True)),
+    (-1, 1, "Conv", (256, 3, 2)),
+    (-1, 6, "C2f", (256, True)),
+    (-1, 1, "Conv", (512, 3, 2)),
+    (-1, 6, "C2f", (512, True)),
+    (-1, 1, "Conv", (1024, 3, 2)),
+    (-1, 3, "C2f", (1024, True)),
+]
+YOLOV8_YAML = _V8_BACKBONE + [
+    (-1, 1, "SPPF", (1024, 5)),                            # 9
+    _UP,
+    ((-1, 6), 1, "Concat", (1,)),
+    (-1, 3, "C2f", (512,)),                                # 12
+    _UP,
+    ((-1, 4), 1, "Concat", (1,)),
+    (-1, 3, "C2f", (256,)),                                # 15
+    (-1, 1, "Conv", (256, 3, 2)),
+    ((-1, 12), 1, "Concat", (1,)),
+    (-1, 3, "C2f", (512,)),                                # 18
+    (-1, 1, "Conv", (512, 3, 2)),
+    ((-1, 9), 1, "Concat", (1,)),
+    (-1, 3, "C2f", (1024,)),                               # 21
+    ((15, 18, 21), 1, "Detect", ("nc",)),                  # 22
+]
+YOLOV8_P2_YAML = _V8_BACKBONE + [
+    (-1, 1, "SPPF", (1024, 5)),                            # 9
+    _UP,
+    ((-1, 6), 1, "Concat", (1,)),
+    (-1, 3, "C2f", (512,)),                                # 12
+    _UP,
+    ((-1, 4), 1, "Concat", (1,)),
+    (-1, 3, "C2f", (256,)),                                # 15
+    _UP,
+    ((-1, 2), 1, "Concat", (1,)),
+    (-1, 3, "C2f", (128,)),                                # 18
+    (-1, 1, "Conv", (128, 3, 2)),
+    ((-1, 15), 1, "Concat", (1,)),
+    (-1, 3, "C2f", (256,)),                                # 21
+    (-1, 1, "Conv", (256, 3, 2)),
+    ((-1, 12), 1, "Concat", (1,)),
+    (-1, 3, "C2f", (512,)),                                # 24
+    (-1, 1, "Conv", (512, 3, 2)),
+    ((-1, 9), 1, "Concat", (1,)),
+    (-1, 3, "C2f", (1024,)),                               # 27
+    ((18, 21, 24, 27), 1, "Detect", ("nc",)),              # 28
+]
+YOLO11_YAML = [
+    (-1, 1, "Conv", (64, 3, 2)),
+    (-1, 1, "Conv", (128, 3, 2)),
+    (-1, 2, "C3k2", (256, False, 0.25)),
+    (-1, 1, "Conv", (256, 3, 2)),
+    (-1, 2, "C3k2", (512, False, 0.25)),
+    (-1, 1, "Conv", (512, 3, 2)),
+    (-1, 2, "C3k2", (512, True)),
+    (-1, 1, "Conv", (1024, 3, 2)),
+    (-1, 2, "C3k2", (1024, True)),
+    (-1, 1, "SPPF", (1024, 5)),                            # 9
+    (-1, 2, "C2PSA", (1024,)),                             # 10
+    _UP,
+    ((-1, 6), 1, "Concat", (1,)),
+    (-1, 2, "C3k2", (512, False)),                         # 13
+    _UP,
+    ((-1, 4), 1, "Concat", (1,)),
+    (-1, 2, "C3k2", (256, False)),                         # 16
+    (-1, 1, "Conv", (256, 3, 2)),
+    ((-1, 13), 1, "Concat", (1,)),
+    (-1, 2, "C3k2", (512, False)),                         # 19
+    (-1, 1, "Conv", (512, 3, 2)),
+    ((-1, 10), 1, "Concat", (1,)),
+    (-1, 2, "C3k2", (1024, True)),                         # 22
+    ((16, 19, 22), 1, "Detect", ("nc",)),                  # 23: the class branch is DWConv + Conv(1x1) twice
+]
+YOLOV8_CLS_YAML = _V8_BACKBONE + [(-1, 1, "Classify", ("nc",))]
+
+
+def _rows(table, *modules) -> tuple[int, ...]:
+    """The layer indices of a table's rows of the given modules."""
+    return tuple(i for i, r in enumerate(table) if r[2] in modules)
+
+
+def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False) -> list[tuple[str, tuple[int, ...], bool]]:
+    """ultralytics' parse_model over one table: (tensor name, shape, has_act) of every conv of the fused model, in module order.
+    ch(c): a yaml width as built; rep(i, n): the repeats of layer i as built; c3k_all: every C3k2 holds C3k blocks (yolo11 m / l / x);
+    dw_cls: Detect's class branch is DWConv + Conv(1x1) twice (yolo11.yaml)."""
     specs: list[tuple[str, tuple[int, ...], bool]] = []
+    out: list[int] = []                                    # output channels per layer
 
-    def conv(name, cin, cout, k):
-        specs.append((name, (cout, cin, k, k), True))
+    def conv(name, cin, cout, k, act=True):
+        specs.append((name, (cout, cin, k, k), act))
 
-    def c2f(pfx, cin, cout, n):
-        c = cout // 2
+    def dwconv(name, c, act):
+        specs.append((name, (c, 1, 3, 3), act))
+
+    def bottleneck(p, c, e):
+        conv(p + ".cv1.conv", c, int(c * e), 3)
+        conv(p + ".cv2.conv", int(c * e), c, 3)
+
+    def c2f(pfx, cin, cout, n, c3k=None, e=0.5):
+        """C2f (c3k None: full-width Bottlenecks) or C3k2 (half-width Bottlenecks, or C3k blocks of two Bottlenecks when c3k)."""
+        c = int(cout * e)
         conv(f"{pfx}.cv1.conv", cin, 2 * c, 1)
         for k in range(n):
-            conv(f"{pfx}.m.{k}.cv1.conv", c, c, 3)
-            conv(f"{pfx}.m.{k}.cv2.conv", c, c, 3)
+            m = f"{pfx}.m.{k}"
+            if c3k:
+                h = int(c * 0.5)
+                conv(m + ".cv1.conv", c, h, 1)
+                conv(m + ".cv2.conv", c, h, 1)
+                conv(m + ".cv3.conv", 2 * h, c, 1)
+                for j in range(2):
+                    bottleneck(f"{m}.m.{j}", h, 1.0)
+            else:
+                bottleneck(m, c, 1.0 if c3k is None else 0.5)
         conv(f"{pfx}.cv2.conv", (2 + n) * c, cout, 1)
 
-    c1, c2, c3, c4, c5 = ch(64), ch(128), ch(256), ch(512), ch(1024)
-    conv("model.0.conv", 3, c1, 3)
-    conv("model.1.conv", c1, c2, 3)
-    c2f("model.2", c2, c2, rep(3))
-    conv("model.3.conv", c2, c3, 3)
-    c2f("model.4", c3, c3, rep(6))
-    conv("model.5.conv", c3, c4, 3)
-    c2f("model.6", c4, c4, rep(6))
-    conv("model.7.conv", c4, c5, 3)
-    c2f("model.8", c5, c5, rep(3))
-    conv("model.9.cv1.conv", c5, c5 // 2, 1)
-    conv("model.9.cv2.conv", c5 * 2, c5, 1)
-    c2f("model.12", c5 + c4, c4, rep(3))
-    c2f("model.15", c4 + c3, c3, rep(3))
-    conv("model.16.conv", c3, c3, 3)
-    c2f("model.18", c3 + c4, c4, rep(3))
-    conv("model.19.conv", c4, c4, 3)
-    c2f("model.21", c4 + c5, c5, rep(3))
-    cb = max(16, c3 // 4, 64)
-    cc = max(c3, min(nc, 100))
-    for l, cin in enumerate((c3, c4, c5)):
-        conv(f"model.22.cv2.{l}.0.conv", cin, cb, 3)
-        conv(f"model.22.cv2.{l}.1.conv", cb, cb, 3)
-        specs.append((f"model.22.cv2.{l}.2", (64, cb, 1, 1), False))
-        conv(f"model.22.cv3.{l}.0.conv", cin, cc, 3)
-        conv(f"model.22.cv3.{l}.1.conv", cc, cc, 3)
-        specs.append((f"model.22.cv3.{l}.2", (nc, cc, 1, 1), False))
+    def detect(d, chans):
+        cb = max(16, chans[0] // 4, 64)
+        cc = max(chans[0], min(nc, 100))
+        for l, cin in enumerate(chans):
+            conv(f"{d}.cv2.{l}.0.conv", cin, cb, 3)
+            conv(f"{d}.cv2.{l}.1.conv", cb, cb, 3)
+            specs.append((f"{d}.cv2.{l}.2", (64, cb, 1, 1), False))
+            if dw_cls:
+                dwconv(f"{d}.cv3.{l}.0.0.conv", cin, True)
+                conv(f"{d}.cv3.{l}.0.1.conv", cin, cc, 1)
+                dwconv(f"{d}.cv3.{l}.1.0.conv", cc, True)
+                conv(f"{d}.cv3.{l}.1.1.conv", cc, cc, 1)
+            else:
+                conv(f"{d}.cv3.{l}.0.conv", cin, cc, 3)
+                conv(f"{d}.cv3.{l}.1.conv", cc, cc, 3)
+            specs.append((f"{d}.cv3.{l}.2", (nc, cc, 1, 1), False))
+
+    for i, (frm, n, mod, args) in enumerate(table):
+        src = [out[f if f >= 0 else i + f] for f in ((frm,) if isinstance(frm, int) else frm)] if i else [3]
+        pfx, cin, n = f"model.{i}", src[0], rep(i, n)
+        if mod == "Conv":
+            out.append(ch(args[0]))
+            conv(pfx + ".conv", cin, out[i], args[1])
+        elif mod == "C2f":
+            out.append(ch(args[0]))
+            c2f(pfx, cin, out[i], n)
+        elif mod == "C3k2":
+            out.append(ch(args[0]))
+            c2f(pfx, cin, out[i], n, c3k_all or args[1], *args[2:])
+        elif mod == "SPPF":
+            out.append(ch(args[0]))
+            conv(pfx + ".cv1.conv", cin, cin // 2, 1)
+            conv(pfx + ".cv2.conv", cin // 2 * 4, out[i], 1)
+        elif mod == "C2PSA":                               # heads = c / 64, key_dim 32, head_dim 64
+            out.append(ch(args[0]))
+            c = cin // 2
+            conv(pfx + ".cv1.conv", cin, 2 * c, 1)
+            for k in range(n):
+                m = f"{pfx}.m.{k}"
+                conv(m + ".attn.qkv.conv", c, c + 2 * (c // 64) * 32, 1, act=False)
+                conv(m + ".attn.proj.conv", c, c, 1, act=False)
+                dwconv(m + ".attn.pe.conv", c, False)
+                conv(m + ".ffn.0.conv", c, 2 * c, 1)
+                conv(m + ".ffn.1.conv", 2 * c, c, 1, act=False)
+            conv(pfx + ".cv2.conv", 2 * c, out[i], 1)
+        elif mod == "Upsample":
+            out.append(cin)
+        elif mod == "Concat":
+            out.append(sum(src))
+        elif mod == "Detect":
+            out.append(0)
+            detect(pfx, src)
+        elif mod == "Classify":
+            out.append(nc)
+            conv(pfx + ".conv.conv", cin, 1280, 1)
+            specs.append((pfx + ".linear", (nc, 1280), False))
+        else:
+            raise ValueError(f"model.{i}: module {mod}")
     return specs
+
+
+def _scaled_specs(table, scales, scale, nc, **kw):
+    """_parse_model at one of the yaml's scales (depth, width, max_channels)."""
+    depth, width, maxc = scales[scale]
+    return _parse_model(table, nc, lambda c: _make_divisible(min(c, maxc) * width), lambda i, n: max(round(n * depth), 1) if n > 1 else n, **kw)
+
+
+def yolov8_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
+    """(tensor name, OIHW shape, has_act) for every conv of a fused YOLOv8 detect model."""
+    return _scaled_specs(YOLOV8_YAML, SCALES, scale, nc)
 
 
 def synthetic_yolov8(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0,
@@ -147,7 +293,7 @@ def _draw_yolov8(rng, specs, cls_bias: float = -4.0, gain: float = 1.7, box_deca
     decay = np.broadcast_to(np.asarray(box_decay, dtype=np.float64), (4,))
     t: dict[str, np.ndarray] = {}
     for name, shape, has_act in specs:
-        fan_in = shape[1] * shape[2] * shape[3]
+        fan_in = int(np.prod(shape[1:]))
         g = gain if has_act else 1.0
         t[name + ".weight"] = (rng.standard_normal(shape) * (g / np.sqrt(fan_in))).astype(np.float32)
         if smooth_cls and shape[2] == 3 and (".cv3." in name or name.startswith("model.15.m.") or
@@ -155,9 +301,10 @@ def _draw_yolov8(rng, specs, cls_bias: float = -4.0, gain: float = 1.7, box_deca
             mix = t[name + ".weight"][:, :, 1:2, 1:2] * np.float32(np.sqrt(shape[2] * shape[3]))   # keeps the output variance for smooth inputs
             t[name + ".weight"] = np.broadcast_to(mix / np.float32(shape[2] * shape[3]), shape).astype(np.float32).copy()
         b = rng.standard_normal(shape[0]) * 0.05
-        if name.endswith("cv3.0.2") or name.endswith("cv3.1.2") or name.endswith("cv3.2.2"):
-            b = b + cls_bias + float(level_bias[int(name.split(".")[3])])
-        if ".cv2." in name and name.endswith(".2"):
+        last = re.fullmatch(r"model\.\d+\.cv([23])\.(\d+)\.2", name)   # Detect's closing 1x1 of the box (cv2) / class (cv3) branch of level l
+        if last and last.group(1) == "3":
+            b = b + cls_bias + float(level_bias[int(last.group(2))])
+        if last and last.group(1) == "2":
             t[name + ".weight"] *= np.float32(box_weight_scale)
             b = b - np.repeat(decay, 16) * np.tile(np.arange(16), 4)
         t[name + ".bias"] = b.astype(np.float32)
@@ -175,43 +322,7 @@ def is_yolov8_p2(tensors: dict) -> bool:
 
 def yolov8_p2_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
     """(tensor name, OIHW shape, has_act) for every conv of a fused YOLOv8-P2 detect model."""
-    depth, width, maxc = SCALES[scale]
-    ch = lambda c: _make_divisible(min(c, maxc) * width)
-    rep = lambda n: max(round(n * depth), 1)
-    backbone = [s for s in yolov8_layer_specs(scale, nc) if int(s[0].split(".")[1]) <= 9]
-    specs = list(backbone)
-
-    def conv(name, cin, cout, k):
-        specs.append((name, (cout, cin, k, k), True))
-
-    def c2f(pfx, cin, cout, n):
-        c = cout // 2
-        conv(f"{pfx}.cv1.conv", cin, 2 * c, 1)
-        for k in range(n):
-            conv(f"{pfx}.m.{k}.cv1.conv", c, c, 3)
-            conv(f"{pfx}.m.{k}.cv2.conv", c, c, 3)
-        conv(f"{pfx}.cv2.conv", (2 + n) * c, cout, 1)
-
-    c1, c2, c3, c4, c5 = ch(128), ch(256), ch(512), ch(1024), ch(1024)   # c1: model.2's width (yolov8.yaml's 128 x width)
-    c2f("model.12", c5 + c3, c3, rep(3))
-    c2f("model.15", c3 + c2, c2, rep(3))
-    c2f("model.18", c2 + c1, c1, rep(3))
-    conv("model.19.conv", c1, c1, 3)
-    c2f("model.21", c1 + c2, c2, rep(3))
-    conv("model.22.conv", c2, c2, 3)
-    c2f("model.24", c2 + c3, c3, rep(3))
-    conv("model.25.conv", c3, c3, 3)
-    c2f("model.27", c3 + c5, c5, rep(3))
-    cb = max(16, c1 // 4, 64)
-    cc = max(c1, min(nc, 100))
-    for l, cin in enumerate((c1, c2, c3, c5)):
-        conv(f"model.28.cv2.{l}.0.conv", cin, cb, 3)
-        conv(f"model.28.cv2.{l}.1.conv", cb, cb, 3)
-        specs.append((f"model.28.cv2.{l}.2", (64, cb, 1, 1), False))
-        conv(f"model.28.cv3.{l}.0.conv", cin, cc, 3)
-        conv(f"model.28.cv3.{l}.1.conv", cc, cc, 3)
-        specs.append((f"model.28.cv3.{l}.2", (nc, cc, 1, 1), False))
-    return specs
+    return _scaled_specs(YOLOV8_P2_YAML, SCALES, scale, nc)
 
 
 def synthetic_yolov8_p2(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0, gain: float = 1.7,
@@ -220,21 +331,7 @@ def synthetic_yolov8_p2(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: 
     """Seeded random fused weights of the YOLOv8-P2 architecture, drawn like synthetic_yolov8's (same knobs, same order of draws
     over yolov8_p2_layer_specs). ``level_bias`` is added to the class logits of the stride-4/8/16/32 heads; the default silences the
     two coarse heads, whose random logits otherwise dominate, so that the stride-4 and stride-8 anchors are the ones that fire."""
-    rng = np.random.default_rng(seed)
-    decay = np.broadcast_to(np.asarray(box_decay, dtype=np.float64), (4,))
-    t: dict[str, np.ndarray] = {}
-    for name, shape, has_act in yolov8_p2_layer_specs(scale, nc):
-        fan_in = shape[1] * shape[2] * shape[3]
-        g = gain if has_act else 1.0
-        t[name + ".weight"] = (rng.standard_normal(shape) * (g / np.sqrt(fan_in))).astype(np.float32)
-        b = rng.standard_normal(shape[0]) * 0.05
-        if name.startswith("model.28.cv3.") and name.endswith(".2"):
-            b = b + cls_bias + float(level_bias[int(name.split(".")[3])])
-        if name.startswith("model.28.cv2.") and name.endswith(".2"):
-            t[name + ".weight"] *= np.float32(box_weight_scale)
-            b = b - np.repeat(decay, 16) * np.tile(np.arange(16), 4)
-        t[name + ".bias"] = b.astype(np.float32)
-    return t
+    return _draw_yolov8(np.random.default_rng(seed), yolov8_p2_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias, box_weight_scale)
 
 
 # --------------------------------------------------------------------------- YOLO11 (cfg/models/11/yolo11.yaml)
@@ -268,8 +365,8 @@ def check_yolo11(tensors: dict) -> None:
     no = NotImplementedError(f"checkpoint with attention / depthwise-Detect blocks in another arrangement than yolo11.yaml's: of that "
                              f"family only {YOLO11_TOPOLOGY} is implemented")
     shape = lambda n: tuple(np.shape(tensors[n])) if n in tensors else None
-    need = [f"model.{i}.conv.weight" for i in (0, 1, 3, 5, 7, 17, 20)]
-    need += [f"model.{i}.{c}.conv.weight" for i in (2, 4, 6, 8, 13, 16, 19, 22) for c in ("cv1", "cv2", "m.0.cv1", "m.0.cv2")]
+    need = [f"model.{i}.conv.weight" for i in _rows(YOLO11_YAML, "Conv")]
+    need += [f"model.{i}.{c}.conv.weight" for i in _rows(YOLO11_YAML, "C3k2") for c in ("cv1", "cv2", "m.0.cv1", "m.0.cv2")]
     need += ["model.9.cv1.conv.weight", "model.9.cv2.conv.weight", "model.10.cv1.conv.weight", "model.10.cv2.conv.weight"]
     need += [f"model.10.m.0.{c}.conv.weight" for c in ("attn.qkv", "attn.proj", "attn.pe", "ffn.0", "ffn.1")]
     for l in range(3):
@@ -285,7 +382,7 @@ def check_yolo11(tensors: dict) -> None:
         i = int(p[1])
         if i > 23 or (".attn." in k and i != 10) or (i == 23 and (p[2] not in ("cv2", "cv3", "dfl") or (p[2] in ("cv2", "cv3") and p[3] not in "012"))):
             raise no
-        if i in (11, 12, 14, 15, 18, 21):                  # Upsample / Concat: no tensors
+        if i in _rows(YOLO11_YAML, "Upsample", "Concat"):  # no tensors
             raise no
     c = shape("model.10.cv1.conv.weight")[0] // 2
     if c % 64 or shape("model.10.m.0.attn.qkv.conv.weight") != (2 * c, c, 1, 1) or shape("model.10.m.0.attn.pe.conv.weight") != (c, 1, 3, 3):
@@ -296,78 +393,7 @@ def check_yolo11(tensors: dict) -> None:
 
 def yolo11_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
     """(tensor name, OIHW shape, has_act) for every conv of a fused YOLO11 detect model (depthwise convs: (C, 1, 3, 3))."""
-    depth, width, maxc = YOLO11_SCALES[scale]
-    ch = lambda c: _make_divisible(min(c, maxc) * width)
-    n = max(round(2 * depth), 1)                           # every C3k2 and the C2PSA have 2 repeats in the yaml
-    force_c3k = scale in "mlx"                             # parse_model: c3k=True in every C3k2 of the larger scales
-    specs: list[tuple[str, tuple[int, ...], bool]] = []
-
-    def conv(name, cin, cout, k, act=True):
-        specs.append((name, (cout, cin, k, k), act))
-
-    def dwconv(name, c, act):
-        specs.append((name, (c, 1, 3, 3), act))
-
-    def bottleneck(p, c, e):
-        conv(p + ".cv1.conv", c, int(c * e), 3)
-        conv(p + ".cv2.conv", int(c * e), c, 3)
-
-    def c3k2(pfx, cin, cout, c3k, e=0.5):
-        c = int(cout * e)
-        conv(f"{pfx}.cv1.conv", cin, 2 * c, 1)
-        for k in range(n):
-            m = f"{pfx}.m.{k}"
-            if c3k or force_c3k:
-                h = int(c * 0.5)
-                conv(m + ".cv1.conv", c, h, 1)
-                conv(m + ".cv2.conv", c, h, 1)
-                conv(m + ".cv3.conv", 2 * h, c, 1)
-                for j in range(2):
-                    bottleneck(f"{m}.m.{j}", h, 1.0)
-            else:
-                bottleneck(m, c, 0.5)
-        conv(f"{pfx}.cv2.conv", (2 + n) * c, cout, 1)
-
-    c1, c2, c3, c4, c5 = ch(64), ch(128), ch(256), ch(512), ch(1024)
-    conv("model.0.conv", 3, c1, 3)
-    conv("model.1.conv", c1, c2, 3)
-    c3k2("model.2", c2, c3, False, 0.25)
-    conv("model.3.conv", c3, c3, 3)
-    c3k2("model.4", c3, c4, False, 0.25)
-    conv("model.5.conv", c4, c4, 3)
-    c3k2("model.6", c4, c4, True)
-    conv("model.7.conv", c4, c5, 3)
-    c3k2("model.8", c5, c5, True)
-    conv("model.9.cv1.conv", c5, c5 // 2, 1)
-    conv("model.9.cv2.conv", c5 * 2, c5, 1)
-    c = c5 // 2                                            # C2PSA: heads = c / 64, key_dim 32, head_dim 64
-    conv("model.10.cv1.conv", c5, 2 * c, 1)
-    for k in range(n):
-        m = f"model.10.m.{k}"
-        conv(m + ".attn.qkv.conv", c, c + 2 * (c // 64) * 32, 1, act=False)
-        conv(m + ".attn.proj.conv", c, c, 1, act=False)
-        dwconv(m + ".attn.pe.conv", c, False)
-        conv(m + ".ffn.0.conv", c, 2 * c, 1)
-        conv(m + ".ffn.1.conv", 2 * c, c, 1, act=False)
-    conv("model.10.cv2.conv", 2 * c, c5, 1)
-    c3k2("model.13", c5 + c4, c4, False)
-    c3k2("model.16", c4 + c4, c3, False)
-    conv("model.17.conv", c3, c3, 3)
-    c3k2("model.19", c3 + c4, c4, False)
-    conv("model.20.conv", c4, c4, 3)
-    c3k2("model.22", c4 + c5, c5, True)
-    cb = max(16, c3 // 4, 64)
-    cc = max(c3, min(nc, 100))
-    for l, cin in enumerate((c3, c4, c5)):
-        conv(f"model.23.cv2.{l}.0.conv", cin, cb, 3)
-        conv(f"model.23.cv2.{l}.1.conv", cb, cb, 3)
-        specs.append((f"model.23.cv2.{l}.2", (64, cb, 1, 1), False))
-        dwconv(f"model.23.cv3.{l}.0.0.conv", cin, True)
-        conv(f"model.23.cv3.{l}.0.1.conv", cin, cc, 1)
-        dwconv(f"model.23.cv3.{l}.1.0.conv", cc, True)
-        conv(f"model.23.cv3.{l}.1.1.conv", cc, cc, 1)
-        specs.append((f"model.23.cv3.{l}.2", (nc, cc, 1, 1), False))
-    return specs
+    return _scaled_specs(YOLO11_YAML, YOLO11_SCALES, scale, nc, c3k_all=scale in "mlx", dw_cls=True)   # parse_model: c3k=True in every C3k2 of the larger scales
 
 
 def synthetic_yolo11(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0, gain: float = 1.7,
@@ -659,50 +685,20 @@ CLS_SCALES = {"n": (0.33, 0.25, 1024), "s": (0.33, 0.50, 1024), "m": (0.67, 0.75
 
 
 def _cls_backbone_specs(c1: int, c2: int, c3: int, c4: int, c5: int, reps: tuple[int, int, int, int]) -> list[tuple[str, tuple[int, ...]]]:
-    specs: list[tuple[str, tuple[int, ...]]] = []
-
-    def c2f(pfx, cin, cout, n):
-        c = cout // 2
-        specs.append((f"{pfx}.cv1.conv", (2 * c, cin, 1, 1)))
-        for k in range(n):
-            specs.append((f"{pfx}.m.{k}.cv1.conv", (c, c, 3, 3)))
-            specs.append((f"{pfx}.m.{k}.cv2.conv", (c, c, 3, 3)))
-        specs.append((f"{pfx}.cv2.conv", (cout, (2 + n) * c, 1, 1)))
-
-    specs.append(("model.0.conv", (c1, 3, 3, 3)))
-    specs.append(("model.1.conv", (c2, c1, 3, 3)))
-    c2f("model.2", c2, c2, reps[0])
-    specs.append(("model.3.conv", (c3, c2, 3, 3)))
-    c2f("model.4", c3, c3, reps[1])
-    specs.append(("model.5.conv", (c4, c3, 3, 3)))
-    c2f("model.6", c4, c4, reps[2])
-    specs.append(("model.7.conv", (c5, c4, 3, 3)))
-    c2f("model.8", c5, c5, reps[3])
-    return specs
+    """(name, shape) of model.0-8 with the given widths and C2f repeats (is_yolov8_cls reads them off a file)."""
+    widths = {64: c1, 128: c2, 256: c3, 512: c4, 1024: c5}
+    specs = _parse_model(_V8_BACKBONE, 0, widths.get, lambda i, n: reps[i // 2 - 1] if i in (2, 4, 6, 8) else n)
+    return [(n, s) for n, s, _ in specs]
 
 
 def yolov8_cls_layer_specs(scale: str = "n", nc: int = 1000) -> list[tuple[str, tuple[int, ...], bool]]:
     """(tensor name, shape, has_act) of a fused YOLOv8-cls model: the backbone convs, then Classify's conv and linear layer."""
-    depth, width, maxc = CLS_SCALES[scale]
-    ch = lambda c: _make_divisible(min(c, maxc) * width)
-    rep = lambda n: max(round(n * depth), 1)
-    c5 = ch(1024)
-    specs = [(n, s, True) for n, s in _cls_backbone_specs(ch(64), ch(128), ch(256), ch(512), c5, (rep(3), rep(6), rep(6), rep(3)))]
-    specs.append(("model.9.conv.conv", (1280, c5, 1, 1), True))
-    specs.append(("model.9.linear", (nc, 1280), False))
-    return specs
+    return _scaled_specs(YOLOV8_CLS_YAML, CLS_SCALES, scale, nc)
 
 
 def synthetic_yolov8_cls(seed: int = 0, scale: str = "n", nc: int = 1000, gain: float = 1.7) -> dict[str, np.ndarray]:
     """Seeded random fused YOLOv8-cls weights, drawn like synthetic_yolov8's: conv weights ~ N(0, gain^2 / fan_in), biases ~ N(0, 0.05^2)."""
-    rng = np.random.default_rng(seed)
-    t: dict[str, np.ndarray] = {}
-    for name, shape, has_act in yolov8_cls_layer_specs(scale, nc):
-        fan_in = int(np.prod(shape[1:]))
-        g = gain if has_act else 1.0
-        t[name + ".weight"] = (rng.standard_normal(shape) * (g / np.sqrt(fan_in))).astype(np.float32)
-        t[name + ".bias"] = (rng.standard_normal(shape[0]) * 0.05).astype(np.float32)
-    return t
+    return _draw_yolov8(np.random.default_rng(seed), yolov8_cls_layer_specs(scale, nc), gain=gain)
 
 
 def is_yolov8_cls(tensors: dict) -> bool:
