@@ -24,22 +24,19 @@
 // Work decomposition and LDS staging are those of conv_igemm.hip (8x16 output pixels x 32*WN couts per
 // 4-wave workgroup, per K chunk the input patch and the KS*KS weight taps staged once, taps read shifted
 // fragments); an LDS row holds the CPR hi chunks of its 8*CPR channels followed by the CPR lo chunks.
+// The arithmetic helpers, the block decode, the epilogue pieces and the launcher are conv_split_device.hpp's, shared with the
+// other split-f16x3 kernels (conv_k32_split.hip, conv_k32p_split.hip, conv_wino_split.hip, head_sparse.hip).
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
 #include <cmath>
-#include <mutex>
 
-#include "conv_igemm.hpp"
+#include "conv_split_device.hpp"
 
 namespace gtx {
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 #define GTXS_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
 
 // Diagnostic builds (`make stamp`) force-include csrc/diag/conv_split_diag.hpp, which defines these two hooks as clock
@@ -69,41 +66,17 @@ struct SplitTile {
   static constexpr int W_SLOTS = (W_CHUNKS + 255) / 256;
   static constexpr int PATCH_BYTES = NPIX * RB;
   static constexpr int STAGE_BYTES = PATCH_BYTES + KS * KS * BN * RB;
-  static constexpr int EPI_PITCH = BN * 4 + 16;      // fp32 epilogue transpose: bytes per staged pixel row
-  static constexpr int EPI_BYTES = 4 * 32 * EPI_PITCH;   // one 32-pixel sub-tile per wave at a time
+  static constexpr int EPI_PITCH = epi_pitch(BN), EPI_BYTES = epi_bytes(BN);   // fp32 epilogue transpose, one 32-pixel sub-tile per wave at a time
   static constexpr int LDS_BYTES = STAGE_BYTES > EPI_BYTES ? STAGE_BYTES : EPI_BYTES;
   static constexpr int ROWS_PER_BANKROW = 256 / RB;  // 4 (RB=64) or 2 (RB=128)
   static __host__ __device__ constexpr int swz(int row) { return (row / ROWS_PER_BANKROW) & (NCH - 1); }
 };
 
-// x * sigmoid(x) with v_exp_f32 and v_rcp_f32 (1 ulp each); hipcc expands __fdividef to a full IEEE division (10 instructions)
-__device__ __forceinline__ float silu_f(float v) { return v * __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
-
-// The epilogues work on PAIRS of values: gfx950 has packed fp32 multiply / add / fma (v_pk_mul_f32, v_pk_add_f32,
-// v_pk_fma_f32: two values per lane and issue slot) and a packed fp32 -> fp16 conversion, so SiLU + the hi / lo split cost
-// 8.5 vector instructions per value instead of 12.5 -- the epilogue is the VALU-bound part of a workgroup's life. Same
-// operations in the same order as the scalar forms (silu_f; hi = fp16(x), lo = fp16(x - hi)): the results are theirs bit for bit.
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float2v relu2(const float2v v) { return float2v{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f)}; }   // ConvProblem::act == 2 (RT-DETR's HGNetv2 blocks)
-__device__ __forceinline__ float2v silu2(const float2v v) {
-  const float2v t = v * -1.44269504088896341f;                      // exp(-v) = exp2(-v log2 e): what __expf compiles to
-  const float2v d = float2v{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)} + 1.f;
-  return v * float2v{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-}
-// 2 fp32 values -> their two hi halves and two lo halves (one register each); sat becomes true when a value had to be clamped
-__device__ __forceinline__ void split2(const float2v v, unsigned& hi, unsigned& lo, bool& sat) {
-  const float2v x = {__builtin_amdgcn_fmed3f(v.x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v.y, -65504.f, 65504.f)};
-  sat |= x.x != v.x || x.y != v.y;                                  // also true for a NaN (it is clamped to -65504 by v_med3)
-  const half2v h = __builtin_convertvector(x, half2v);
-  const half2v l = __builtin_convertvector(x - __builtin_convertvector(h, float2v), half2v);   // x - hi is exact in fp32
-  hi = __builtin_bit_cast(unsigned, h);
-  lo = __builtin_bit_cast(unsigned, l);
-}
-// 4 fp32 values -> their 4 hi halves and 4 lo halves (8 bytes each)
-__device__ __forceinline__ void split4(const float2v (&v)[2], uint2& hi, uint2& lo, bool& sat) {
-  split2(v[0], hi.x, lo.x, sat);
-  split2(v[1], hi.y, lo.y, sat);
+// accumulator group g4 of a 32x32x16 accumulator: the lane's 4 consecutive channels 8 g4 + 4 h + 0..3 of its pixel
+__device__ __forceinline__ floatx4 acc_group(const floatx16 a, const int g4) { return floatx4{a[4 * g4], a[4 * g4 + 1], a[4 * g4 + 2], a[4 * g4 + 3]}; }
+__device__ __forceinline__ void set_acc_group(floatx16& a, const int g4, const floatx4 v) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) a[4 * g4 + k] = v[k];
 }
 
 // Front stage (ConvProblem::front_img, 3x3 stride-2 launches): the layer's input is YOLOv8's stem, SiLU(conv 3x3 stride 2 of
@@ -155,32 +128,9 @@ __device__ __forceinline__ void conv_split_body(const ConvGroup& g) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  // launch header first, as one burst of scalar loads: group size and every member's first block
-  const int cnt = g.count;
-  int bb[kMaxGroup];
-#pragma unroll
-  for (int i = 0; i < kMaxGroup; ++i) bb[i] = g.p[i].block_begin;
-  // XCD-aware logical block id: blocks b and b+8 share an XCD (speed only, never correctness); every XCD works through one
-  // contiguous range of logical blocks -- the cout tiles of one pixel tile (same input patch) and neighbouring pixel tiles
-  // (shared halo) meet in one L2 -- and the ranges hold equal work (ConvGroup::xcd_begin). Surplus blocks of the shorter
-  // ranges leave here.
-  const int xcd = blockIdx.x & 7;
-  const int L = g.xcd_begin[xcd] + (int)(blockIdx.x >> 3);
-  if (L >= g.xcd_begin[xcd + 1]) return;
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < kMaxGroup; ++i)
-    if (i < cnt && L >= bb[i]) pi = i;
-  const ConvProblem P = g.p[pi];            // by value: one burst of wide scalar loads instead of a load (and a wait) per field
-
-  const int lb = L - P.block_begin;
-  const int ct = lb % P.n_ct;
-  const int pt = lb / P.n_ct;
-  const int tx = pt % P.tiles_x;
-  const int t2 = pt / P.tiles_x;
-  const int ty = t2 % P.tiles_y + P.ty_first;
-  const int n = t2 / P.tiles_y;
-  const int oy0 = ty * TH, ox0 = tx * TW;
+  ConvProblem P;                                   // launch header: conv_split_device.hpp
+  int ct, n, oy0, ox0;
+  if (!conv_block_decode<TH, TW>(g, P, ct, n, oy0, ox0)) return;
   const int iy0 = oy0 * STRIDE - Tile::PAD, ix0 = ox0 * STRIDE - Tile::PAD;
 
   const float* __restrict__ in = static_cast<const float*>(P.in);
@@ -393,9 +343,7 @@ __device__ __forceinline__ void conv_split_body(const ConvGroup& g) {
     }                                                                                        \
   }
 
-  // The accumulators start at bias / acc_scale (acc_scale is a power of two: exact), so the epilogue is one multiply and
-  // has no loads of its own: the bias fetch overlaps the first global -> LDS round trip instead of opening the epilogue.
-  float4 b4[WN][4];
+  float4 b4[WN][4];                                 // the accumulators start at bias / acc_scale (acc_start)
 #define GTXS_LOAD_BIAS()                                                                     \
   {                                                                                          \
     _Pragma("unroll") for (int j = 0; j < WN; ++j)                                           \
@@ -429,10 +377,7 @@ __device__ __forceinline__ void conv_split_body(const ConvGroup& g) {
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4)
 #pragma unroll
-        for (int m = 0; m < WM; ++m) {
-          acc[m][j][4 * g4 + 0] = b4[j][g4].x * inv_sc; acc[m][j][4 * g4 + 1] = b4[j][g4].y * inv_sc;
-          acc[m][j][4 * g4 + 2] = b4[j][g4].z * inv_sc; acc[m][j][4 * g4 + 3] = b4[j][g4].w * inv_sc;
-        }
+        for (int m = 0; m < WM; ++m) set_acc_group(acc[m][j], g4, acc_start(b4[j][g4], inv_sc));
   }
 
   constexpr int NSTEP = KS * KS * (CPR / 2);
@@ -537,19 +482,9 @@ __device__ __forceinline__ void conv_split_body(const ConvGroup& g) {
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
           const int cl = 32 * j + 8 * g4 + 4 * h;
-          float2v v[2];
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            v[q] = float2v{acc[0][j][4 * g4 + 2 * q], acc[0][j][4 * g4 + 2 * q + 1]} * P.acc_scale;
-            if (P.act == 1) v[q] = silu2(v[q]); else if (P.act == 2) v[q] = relu2(v[q]);
-          }
-          uint2 hi, lo;
-          split4(v, hi, lo, sat_y);
-          const auto sx = __builtin_amdgcn_permlane32_swap(hi.x, lo.x, false, false);
-          const auto sy = __builtin_amdgcn_permlane32_swap(hi.y, lo.y, false, false);
-          *reinterpret_cast<uint4*>(stg + prow * PITCH + cl * 4) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
+          epilogue_fragment<32>(acc_group(acc[0][j], g4), P.acc_scale, P.act, false, nullptr, false, stg + prow * PITCH + cl * 4, sat_y);
         }
-      if (P.sat_flag && __builtin_amdgcn_ballot_w64(sat_y) != 0 && lane == 0) atomicOr(P.sat_flag, 1);
+      flag_saturation(P.sat_flag, sat_y, lane);
 #pragma unroll
       for (int i = 0; i < W2_SLOTS; ++i)
         if (tid + 256 * i < W2_CHUNKS) *reinterpret_cast<uint4*>(smem + W2_OFF + (tid + 256 * i) * 16) = w2r[i];
@@ -558,10 +493,7 @@ __device__ __forceinline__ void conv_split_body(const ConvGroup& g) {
 #pragma unroll
       for (int j = 0; j < WN; ++j)
 #pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          acc[0][j][4 * g4 + 0] = b2[j][g4].x * inv2; acc[0][j][4 * g4 + 1] = b2[j][g4].y * inv2;
-          acc[0][j][4 * g4 + 2] = b2[j][g4].z * inv2; acc[0][j][4 * g4 + 3] = b2[j][g4].w * inv2;
-        }
+        for (int g4 = 0; g4 < 4; ++g4) set_acc_group(acc[0][j], g4, acc_start(b2[j][g4], inv2));
       constexpr int K2 = BN / 32;                 // 32-channel chunks of the 1x1 layer's K = BN
 #pragma unroll
       for (int k2 = 0; k2 < K2; ++k2)
@@ -572,7 +504,7 @@ __device__ __forceinline__ void conv_split_body(const ConvGroup& g) {
           const half8 yl = *reinterpret_cast<const half8*>(stg + prow * PITCH + grp * 32 + 16);
 #pragma unroll
           for (int j = 0; j < WN; ++j) {
-            const int nrow = 32 * j + prow, sw = (nrow >> 1) & 7, ci = 2 * ks + h;
+            const int nrow = 32 * j + prow, sw = swz128(nrow), ci = 2 * ks + h;
             const char* wr = smem + W2_OFF + (k2 * BN + nrow) * 128;
             const half8 wh = *reinterpret_cast<const half8*>(wr + ((ci ^ sw) << 4));
             const half8 wl = *reinterpret_cast<const half8*>(wr + (((4 + ci) ^ sw) << 4));
@@ -584,78 +516,32 @@ __device__ __forceinline__ void conv_split_body(const ConvGroup& g) {
     }
   }
 
-  // ---- epilogue: acc * 2^-shift (bias is already in) -> SiLU (+ residual) -> split into hi / lo -> NHWC pair format ----
-  // After the MFMAs a lane holds 4 consecutive channels of one pixel; lanes l and l + 32 hold the two halves of one
-  // 8-channel group. Two v_permlane32_swap turn that into the group's 16-byte hi chunk (lane l) and 16-byte lo chunk
-  // (lane l + 32), which land in the LDS staging row at the byte offset the fp32 float4 would have had; the wave then
-  // stores whole BN*4-byte runs per pixel. ConvProblem::out_plain keeps plain fp32 (the Detect head's last stage, read by
-  // the decode kernels).
+  // ---- epilogue: acc * 2^-shift (bias is already in) -> activation (+ residual) -> split into hi / lo -> NHWC pair format ----
+  // The pieces are conv_split_device.hpp's (swap width 32): the lane's fragments go into the wave's LDS staging rows, the
+  // wave then stores whole BN*4-byte runs per pixel.
   const float sc = post ? P.post_scale : P.acc_scale;
   const int cvalid = P.Cout - ct * BN;          // < BN in a last cout tile that is half empty (Cout = 16, 48, 80 ...)
-  const bool plain = P.out_plain != 0;
-  const int act = post ? P.post_act : P.act;      // 0 none, 1 SiLU, 2 ReLU
-  const void* const res_p = P.res;
-  const int o_cstride = P.out_cstride, o_coff = P.out_coff;
-  float* const o_base = static_cast<float*>(P.out);
+  const bool plain = P.out_plain != 0, has_res = P.res != nullptr;
+  const int act = post ? P.post_act : P.act;
   bool sat = false;
   __syncthreads();                              // every wave is done with the staging buffers
 #pragma unroll
   for (int m = 0; m < WM; ++m) {
-    const int trow = trow0 + 2 * m;
-    const int oy = oy0 + trow, ox = ox0 + tcol;
     constexpr int PITCH = Tile::EPI_PITCH;
     char* stg = smem + wave * (32 * PITCH);     // wave-private: its own LDS writes are ordered before its reads
-    const bool inside = oy < P.Ho && ox < P.Wo;
-    const size_t pix = inside ? ((size_t)n * P.Ho + oy) * P.Wo + ox : 0;
-    const float* __restrict__ res =
-        (res_p && inside) ? static_cast<const float*>(res_p) + pix * P.res_cstride + P.res_coff + ct * BN : nullptr;
+    const float* __restrict__ res = residual_row(P, n, oy0 + trow0 + 2 * m, ox0 + tcol, ct * BN);
 #pragma unroll
     for (int j = 0; j < WN; ++j) {
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const int cl = 32 * j + 8 * g4 + 4 * h;
-        float2v v[2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          v[q] = float2v{acc[m][j][4 * g4 + 2 * q], acc[m][j][4 * g4 + 2 * q + 1]} * sc;
-          if (act == 1) v[q] = silu2(v[q]); else if (act == 2) v[q] = relu2(v[q]);
-        }
-        if (res_p) {                               // uniform; the swaps below need every lane
-          uint4 rc = make_uint4(0, 0, 0, 0);       // lane l: the group's hi chunk, lane l + 32: its lo chunk
-          if (res && cl < cvalid) rc = *reinterpret_cast<const uint4*>(res + cl);
-          const auto sx = __builtin_amdgcn_permlane32_swap(rc.x, rc.z, false, false);   // -> (hi, lo) of this lane's channels 0, 1
-          const auto sy = __builtin_amdgcn_permlane32_swap(rc.y, rc.w, false, false);   // ... and 2, 3
-          const unsigned hw[2] = {sx[0], sy[0]}, lw[2] = {sx[1], sy[1]};
-          const half4 rh = *reinterpret_cast<const half4*>(hw), rl = *reinterpret_cast<const half4*>(lw);
-#pragma unroll
-          for (int q = 0; q < 2; ++q)                                                   // hi + lo is exact in fp32
-            v[q] += float2v{(float)rh[2 * q], (float)rh[2 * q + 1]} + float2v{(float)rl[2 * q], (float)rl[2 * q + 1]};
-        }
-        if (plain) {
-          *reinterpret_cast<float4*>(stg + prow * PITCH + cl * 4) = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
-        } else {
-          uint2 hi, lo;
-          split4(v, hi, lo, sat);
-          const auto sx = __builtin_amdgcn_permlane32_swap(hi.x, lo.x, false, false);
-          const auto sy = __builtin_amdgcn_permlane32_swap(hi.y, lo.y, false, false);
-          *reinterpret_cast<uint4*>(stg + prow * PITCH + cl * 4) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-        }
+        epilogue_fragment<32>(acc_group(acc[m][j], g4), sc, act, has_res, (res && cl < cvalid) ? res + cl : nullptr, plain,
+                              stg + prow * PITCH + cl * 4, sat);
       }
     }
-    constexpr int LPP = BN / 4;                 // lanes per pixel (16 B each)
-    constexpr int PPI = 64 / LPP;               // pixels per store instruction
-#pragma unroll
-    for (int it = 0; it < 32 / PPI; ++it) {
-      const int p = it * PPI + lane / LPP, q = lane % LPP;
-      const int py = oy0 + 2 * (WM * wave + m) + (p >> 4), px = ox0 + (p & 15);
-      const uint4 val = *reinterpret_cast<const uint4*>(stg + p * PITCH + q * 16);
-      if (py < P.Ho && px < P.Wo && (q >> 1) * 8 < cvalid) {     // cvalid is a multiple of 16: whole groups
-        float* dst = o_base + (((size_t)n * P.Ho + py) * P.Wo + px) * o_cstride + o_coff + ct * BN + q * 4;
-        *reinterpret_cast<uint4*>(dst) = val;
-      }
-    }
+    store_runs<BN>(stg, P, n, ct, oy0 + 2 * (WM * wave + m), ox0, cvalid, lane);
   }
-  if (P.sat_flag && __builtin_amdgcn_ballot_w64(sat) != 0 && lane == 0) atomicOr(P.sat_flag, 1);
+  flag_saturation(P.sat_flag, sat, lane);
   GTXS_DIAG_EXIT()
 }
 
@@ -675,29 +561,17 @@ void conv_front_split_kernel(const ConvGroup g) {
 template <int KS, int STRIDE, int WN, int CPR, int WM>
 void launch_t(const ConvGroup& g, hipStream_t stream) {
   using Tile = SplitTile<KS, STRIDE, WN, CPR, WM>;
-  auto kern = conv_igemm_split_kernel<KS, STRIDE, WN, CPR, WM>;
-  static std::once_flag once;
-  std::call_once(once, [&] {
-    GTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Tile::LDS_BYTES));
-  });
-  hipLaunchKernelGGL(kern, dim3(g.grid_blocks), dim3(256), Tile::LDS_BYTES, stream, g);
-  GTX_HIP(hipGetLastError());
+  launch_conv_group<conv_igemm_split_kernel<KS, STRIDE, WN, CPR, WM>>(g, 256, Tile::LDS_BYTES, stream);
 }
 
 template <int WN, int NCH>
 void launch_front_t(const ConvGroup& g, hipStream_t stream) {
   constexpr int lds = split_lds_bytes<3, 2, WN, 2, 1, NCH>();
   static_assert(FrontTile::TILES % 4 == 0 && 2 * lds <= 160 * 1024, "front stage: 9 patch tiles per wave, two workgroups per CU");
-  auto kern = conv_front_split_kernel<WN, NCH>;
   // GTX_FRONT_LDS_PAD=bytes: measurement hook (round 6): requests that much LDS on top of what the kernel uses, to price what its
   // 74 KB footprint costs beside the other detector stream's workgroups (profiles/r06_front_lds.txt)
   static const int pad = [] { const char* e = getenv("GTX_FRONT_LDS_PAD"); return e ? std::max(0, std::min(atoi(e), 160 * 1024 - lds)) : 0; }();
-  static std::once_flag once;
-  std::call_once(once, [&] {
-    GTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds + pad));
-  });
-  hipLaunchKernelGGL(kern, dim3(g.grid_blocks), dim3(256), lds + pad, stream, g);
-  GTX_HIP(hipGetLastError());
+  launch_conv_group<conv_front_split_kernel<WN, NCH>>(g, 256, lds + pad, stream);
 }
 
 }  // namespace

@@ -1,7 +1,7 @@
 // 1x1 (pointwise) split-f16x3 convolution on v_mfma_f32_16x16x32_f16 ("K32 pointwise forms", ConvConfig::variant 6). gfx950 only.
 // EXPERIMENT, closed with numbers: built by `make K32P=1` only, selected with GTX_K32P=1 / 2, never by default.
 //
-// The arithmetic contract, the packed weight image (pack_conv_weights_split, 32-channel chunks, one tap) and the output tile
+// The arithmetic contract (conv_split_device.hpp), the packed weight image (pack_conv_weights_split, 32-channel chunks, one tap) and the output tile
 // (8 x 16 pixels x 64 couts per 4-wave workgroup, wave w owning tile rows 2w and 2w + 1) are conv_k32_split.hip's; what differs
 // is the K loop. A 1x1 layer has no taps to reuse a staged patch over, so a stage here is TWO 32-channel chunks: 128 pixels x
 // 256 B of activations (32 KB: every pixel's 256-byte run of the pair format is one coalesced read) beside 2 x 64 couts x 128 B
@@ -19,19 +19,13 @@
 #include <hip/hip_fp16.h>
 
 #include <cstdlib>
-#include <mutex>
 
-#include "conv_igemm.hpp"
+#include "conv_split_device.hpp"
 
 namespace gtx {
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 #define GTXP_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
 
 struct K32PTile {
@@ -45,30 +39,11 @@ struct K32PTile {
   static constexpr int W_SLOTS = CS * W_CHUNK_U4 / 256;               // 4
   static constexpr int W_BYTES = CS * W_CHUNK_U4 * 16;
   static constexpr int STAGE_BYTES = PATCH_BYTES + W_BYTES;
-  static constexpr int EPI_PITCH = BN * 4 + 16;
-  static constexpr int EPI_BYTES = 4 * 32 * EPI_PITCH;
-  static constexpr int LDS_BYTES = STAGE_BYTES > EPI_BYTES ? STAGE_BYTES : EPI_BYTES;
-  static constexpr int LDS_DIRECT_BYTES = W_BYTES > EPI_BYTES ? W_BYTES : EPI_BYTES;     // direct form: only the weights are staged
-  static __host__ __device__ constexpr int swz(int row) { return (row >> 1) & 7; }
+  static constexpr int LDS_BYTES = STAGE_BYTES > epi_bytes(BN) ? STAGE_BYTES : epi_bytes(BN);
+  static constexpr int LDS_DIRECT_BYTES = W_BYTES > epi_bytes(BN) ? W_BYTES : epi_bytes(BN);     // direct form: only the weights are staged
 };
 static_assert(3 * K32PTile::LDS_BYTES <= 160 * 1024, "three workgroups per CU");
 static_assert(K32PTile::PATCH_SLOTS == 4 && K32PTile::W_SLOTS == 4, "four slots each");
-
-// conv_igemm_split.hip's epilogue arithmetic (same operations in the same order)
-__device__ __forceinline__ float2v relu2(const float2v v) { return float2v{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f)}; }
-__device__ __forceinline__ float2v silu2(const float2v v) {
-  const float2v t = v * -1.44269504088896341f;
-  const float2v d = float2v{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)} + 1.f;
-  return v * float2v{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-}
-__device__ __forceinline__ void split2(const float2v v, unsigned& hi, unsigned& lo, bool& sat) {
-  const float2v x = {__builtin_amdgcn_fmed3f(v.x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v.y, -65504.f, 65504.f)};
-  sat |= x.x != v.x || x.y != v.y;
-  const half2v h = __builtin_convertvector(x, half2v);
-  const half2v l = __builtin_convertvector(x - __builtin_convertvector(h, float2v), half2v);
-  hi = __builtin_bit_cast(unsigned, h);
-  lo = __builtin_bit_cast(unsigned, l);
-}
 
 // DIRECT: the pixels' fragments never pass through LDS. A wave's pixels are its own (rows 2w, 2w + 1 of the tile), and lane (col, kg)'s
 // operand of chunk ch is exactly the 32-byte unit 4 ch + kg of pixel (row, col) in the pair format: the four (row, chunk) units a
@@ -86,28 +61,9 @@ void conv_k32p_split_kernel(const ConvGroup g) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  // launch header and XCD-aware logical block id: conv_igemm_split.hip
-  const int cnt = g.count;
-  int bb[kMaxGroup];
-#pragma unroll
-  for (int i = 0; i < kMaxGroup; ++i) bb[i] = g.p[i].block_begin;
-  const int xcd = blockIdx.x & 7;
-  const int L = g.xcd_begin[xcd] + (int)(blockIdx.x >> 3);
-  if (L >= g.xcd_begin[xcd + 1]) return;
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < kMaxGroup; ++i)
-    if (i < cnt && L >= bb[i]) pi = i;
-  const ConvProblem P = g.p[pi];
-
-  const int lb = L - P.block_begin;
-  const int ct = lb % P.n_ct;
-  const int pt = lb / P.n_ct;
-  const int tx = pt % P.tiles_x;
-  const int t2 = pt / P.tiles_x;
-  const int ty = t2 % P.tiles_y + P.ty_first;
-  const int n = t2 / P.tiles_y;
-  const int oy0 = ty * Tile::TH, ox0 = tx * Tile::TW;
+  ConvProblem P;                                   // launch header: conv_split_device.hpp
+  int ct, n, oy0, ox0;
+  if (!conv_block_decode<Tile::TH, Tile::TW>(g, P, ct, n, oy0, ox0)) return;
 
   const float* __restrict__ in = static_cast<const float*>(P.in);
   const int nchunks = P.Cin / Tile::KC;
@@ -132,7 +88,7 @@ void conv_k32p_split_kernel(const ConvGroup g) {
       const int oy = oy0 + (p >> 4), ox = ox0 + (p & 15);
       const bool inb = oy < P.H && ox < P.W;
       goff[s] = inb ? ((n * P.H + oy) * P.W + ox) * P.in_cstride + P.in_coff + c * 8 : -1;
-      loff[s] = (c >> 2) * Tile::PATCH_CHUNK_BYTES + p * RB + (((c & 3) ^ Tile::swz(p)) << 4);
+      loff[s] = (c >> 2) * Tile::PATCH_CHUNK_BYTES + p * RB + (((c & 3) ^ swz128(p)) << 4);
     }
   }
   // packed image: [cout tile][chunk][n][8 swizzled 16-byte pieces]: a stage's two chunks are 1024 contiguous uint4
@@ -175,8 +131,10 @@ void conv_k32p_split_kernel(const ConvGroup g) {
   pw2 = pw3 = make_uint4(0, 0, 0, 0);
   GTXP_PREFETCH(0)
 
-  // accumulators start at bias / acc_scale (conv_igemm_split.hip): lane (col, kg) of block a holds couts 16 a + 4 kg + 0..3
-  floatx4 acc[4][2];
+  // accumulators start at bias / acc_scale: conv_k32_split.hip's loop, lane (col, kg) of block a holds couts 16 a + 4 kg + 0..3.
+  // (This kernel has no spills either way -- 159 / 150 registers with a shared function that fills the array, 151 / 142 with
+  // the loop -- the loop is here because conv_k32_split_kernel cannot take the function, see there.)
+  floatx4 acc[4][2];                             // [cout block a][pixel block m]
   {
     const float inv_sc = __builtin_amdgcn_rcpf(P.acc_scale);
 #pragma unroll
@@ -184,7 +142,7 @@ void conv_k32p_split_kernel(const ConvGroup g) {
       float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
       if (P.bias) b = *reinterpret_cast<const float4*>(P.bias + ct * BN + 16 * a + 4 * kg);
 #pragma unroll
-      for (int m = 0; m < 2; ++m) acc[a][m] = floatx4{b.x * inv_sc, b.y * inv_sc, b.z * inv_sc, b.w * inv_sc};
+      for (int m = 0; m < 2; ++m) acc[a][m] = acc_start(b, inv_sc);
     }
   }
 
@@ -195,16 +153,16 @@ void conv_k32p_split_kernel(const ConvGroup g) {
     {                                                                                          \
       const int p__ = p0 + ((Q) >> 1) * 16;                                                    \
       const char* pr__ = lds_patch + (CH) * Tile::PATCH_CHUNK_BYTES + p__ * RB;                \
-      if (((Q) & 1) == 0) bh[CH][(Q) >> 1] = *reinterpret_cast<const half8*>(pr__ + ((kg ^ Tile::swz(p__)) << 4)); \
-      else bl[CH][(Q) >> 1] = *reinterpret_cast<const half8*>(pr__ + (((CPR + kg) ^ Tile::swz(p__)) << 4)); \
+      if (((Q) & 1) == 0) bh[CH][(Q) >> 1] = *reinterpret_cast<const half8*>(pr__ + ((kg ^ swz128(p__)) << 4)); \
+      else bl[CH][(Q) >> 1] = *reinterpret_cast<const half8*>(pr__ + (((CPR + kg) ^ swz128(p__)) << 4)); \
     }
   // weights' fragments of (chunk CH, cout block A) -> slot
 #define GTXP_LOAD_A(CH, A, SLOT)                                                               \
     {                                                                                          \
       const int nrow__ = 16 * (A) + col;                                                       \
       const char* wr__ = lds_w + ((CH) * BN + nrow__) * RB;                                    \
-      ah[SLOT] = *reinterpret_cast<const half8*>(wr__ + ((kg ^ Tile::swz(nrow__)) << 4));     \
-      al[SLOT] = *reinterpret_cast<const half8*>(wr__ + (((CPR + kg) ^ Tile::swz(nrow__)) << 4)); \
+      ah[SLOT] = *reinterpret_cast<const half8*>(wr__ + ((kg ^ swz128(nrow__)) << 4));     \
+      al[SLOT] = *reinterpret_cast<const half8*>(wr__ + (((CPR + kg) ^ swz128(nrow__)) << 4)); \
     }
   // unit U = 4 CH + a: 6 MFMAs; reads the weights of unit U + 1 and, during the first chunk, one piece of the second chunk's pixels
 #define GTXP_UNIT(U)                                                                           \
@@ -249,69 +207,8 @@ void conv_k32p_split_kernel(const ConvGroup g) {
 #undef GTXP_LOAD_A
 #undef GTXP_LOAD_B
 
-  // ---- epilogue: conv_k32_split.hip's (acc * 2^-shift -> activation (+ residual) -> split -> NHWC pair format) ----
-  const float sc = P.acc_scale;
-  const int cvalid = P.Cout - ct * BN;
-  const bool plain = P.out_plain != 0;
-  const int act = P.act;                          // 0 none, 1 SiLU, 2 ReLU
-  const void* const res_p = P.res;
-  float* const o_base = static_cast<float*>(P.out);
-  bool sat = false;
-  constexpr int PITCH = Tile::EPI_PITCH;
-  __syncthreads();                                // every wave is done with the staging buffers
-  char* stg = smem + wave * (32 * PITCH);
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    const int oy = oy0 + 2 * wave + m, ox = ox0 + col;
-    const bool inside = oy < P.Ho && ox < P.Wo;
-    const size_t pix = inside ? ((size_t)n * P.Ho + oy) * P.Wo + ox : 0;
-    const float* __restrict__ res =
-        (res_p && inside) ? static_cast<const float*>(res_p) + pix * P.res_cstride + P.res_coff + ct * BN : nullptr;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int cl = 16 * a + 4 * kg;
-      float2v v[2];
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        v[q] = float2v{acc[a][m][2 * q], acc[a][m][2 * q + 1]} * sc;
-        if (act == 1) v[q] = silu2(v[q]); else if (act == 2) v[q] = relu2(v[q]);
-      }
-      if (res_p) {                                 // uniform; the swaps need every lane
-        uint4 rc = make_uint4(0, 0, 0, 0);         // even kg: the group's hi chunk, odd kg: its lo chunk
-        if (res && cl < cvalid) rc = *reinterpret_cast<const uint4*>(res + cl);
-        const auto sx = __builtin_amdgcn_permlane16_swap(rc.x, rc.z, false, false);
-        const auto sy = __builtin_amdgcn_permlane16_swap(rc.y, rc.w, false, false);
-        const unsigned hw[2] = {sx[0], sy[0]}, lw[2] = {sx[1], sy[1]};
-        const half4 rh = *reinterpret_cast<const half4*>(hw), rl = *reinterpret_cast<const half4*>(lw);
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-          v[q] += float2v{(float)rh[2 * q], (float)rh[2 * q + 1]} + float2v{(float)rl[2 * q], (float)rl[2 * q + 1]};
-      }
-      char* dst = stg + (16 * m + col) * PITCH + cl * 4;
-      if (plain) {
-        *reinterpret_cast<float4*>(dst) = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
-      } else {
-        uint2 hi, lo;
-        split2(v[0], hi.x, lo.x, sat);
-        split2(v[1], hi.y, lo.y, sat);
-        const auto sx = __builtin_amdgcn_permlane16_swap(hi.x, lo.x, false, false);
-        const auto sy = __builtin_amdgcn_permlane16_swap(hi.y, lo.y, false, false);
-        *reinterpret_cast<uint4*>(dst) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-      }
-    }
-  }
-  constexpr int LPP = BN / 4, PPI = 64 / LPP;     // 16 lanes of 16 B per pixel, 4 pixels per store instruction
-#pragma unroll
-  for (int it = 0; it < 32 / PPI; ++it) {
-    const int p = it * PPI + lane / LPP, q = lane % LPP;
-    const int py = oy0 + 2 * wave + (p >> 4), px = ox0 + (p & 15);
-    const uint4 val = *reinterpret_cast<const uint4*>(stg + p * PITCH + q * 16);
-    if (py < P.Ho && px < P.Wo && (q >> 1) * 8 < cvalid) {
-      float* dst = o_base + (((size_t)n * P.Ho + py) * P.Wo + px) * P.out_cstride + P.out_coff + ct * BN + q * 4;
-      *reinterpret_cast<uint4*>(dst) = val;
-    }
-  }
-  if (P.sat_flag && __builtin_amdgcn_ballot_w64(sat) != 0 && lane == 0) atomicOr(P.sat_flag, 1);
+  // ---- epilogue: conv_k32_split.hip's (conv_split_device.hpp) ----
+  epilogue_k32(acc, P, smem, ct, n, oy0, ox0, wave, lane);
 }
 
 }  // namespace
@@ -324,14 +221,8 @@ void conv_k32p_launch(const ConvGroup& g, const ConvConfig& c, hipStream_t strea
               "conv (K32 pointwise form): Cin %d must be a multiple of 32 and the launch a plain 1x1 layer", g.p[i].Cin);
   const char* e = getenv("GTX_K32P");               // 1: the form that stages the pixels in LDS too (A/B; read per launch so that one process can compare)
   const bool direct = !(e && e[0] == '1');
-  static std::once_flag once;
-  std::call_once(once, [&] {
-    GTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_k32p_split_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, K32PTile::LDS_BYTES));
-    GTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_k32p_split_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, K32PTile::LDS_DIRECT_BYTES));
-  });
-  if (direct) hipLaunchKernelGGL(conv_k32p_split_kernel<true>, dim3(g.grid_blocks), dim3(256), K32PTile::LDS_DIRECT_BYTES, stream, g);
-  else hipLaunchKernelGGL(conv_k32p_split_kernel<false>, dim3(g.grid_blocks), dim3(256), K32PTile::LDS_BYTES, stream, g);
-  GTX_HIP(hipGetLastError());
+  if (direct) launch_conv_group<conv_k32p_split_kernel<true>>(g, 256, K32PTile::LDS_DIRECT_BYTES, stream);
+  else launch_conv_group<conv_k32p_split_kernel<false>>(g, 256, K32PTile::LDS_BYTES, stream);
 }
 
 }  // namespace gtx

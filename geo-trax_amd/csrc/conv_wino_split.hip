@@ -1,6 +1,6 @@
 // Winograd F(2x2, 3x3) form of the fp32-grade ("split-f16x3") 3x3 stride-1 convolution. gfx950 only.
 //
-// Same arithmetic contract as conv_igemm_split.hip (activations in pair format, every product as three fp16 MFMAs with fp32
+// Same arithmetic contract as conv_igemm_split.hip, kept in conv_split_device.hpp (activations in pair format, every product as three fp16 MFMAs with fp32
 // accumulation, weights scaled by an exact power of two), 2.25 x fewer matrix instructions: a 4x4 input tile d and the 3x3
 // weights g of a (cin, cout) pair give the 2x2 output tile
 //     Y = At [ (G g Gt) (.) (Bt d B) ] A            ((.) = element by element, summed over cin)
@@ -25,19 +25,13 @@
 #include <hip/hip_fp16.h>
 
 #include <cmath>
-#include <mutex>
 
-#include "conv_igemm.hpp"
+#include "conv_split_device.hpp"
 
 namespace gtx {
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 #define GTXW_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
 // Timing-only builds (`make winoprobe`, wrong results): GTXW_PROBE bit 0 = no transform arithmetic (the values read are
 // written back unchanged), bit 1 = no MFMAs, bit 2 = no transform at all (no LDS reads / writes of it either), bit 3 = no weight
@@ -66,21 +60,25 @@ struct WinoTile {
   static __host__ __device__ constexpr int v_swz(int t) { return (2 * ((t >> 1) & 1)) ^ ((t >> 2) & 1); }
 };
 
-__device__ __forceinline__ float2v silu2(const float2v v) {
-  const float2v t = v * -1.44269504088896341f;
-  const float2v d = float2v{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)} + 1.f;
-  return v * float2v{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+// The lane's output pixel (oy, ox) of image n: y (4 channels from c0 of the transformed accumulators) * 2^-shift + bias ->
+// activation (+ residual) -> pair format or plain fp32 -> global memory. The value pieces of conv_split_device.hpp (swap width
+// 32: lanes l and l + 32 hold the two halves of an 8-channel group) without the LDS pass. Every lane must come here.
+__device__ __forceinline__ void wino_store_pixel(const float4 y, const float4 bias, const ConvProblem& P, const int n, const int oy, const int ox,
+                                                 const int c0, bool& sat) {
+  const float sc = P.acc_scale;
+  const bool inside = oy < P.Ho && ox < P.Wo;
+  float2v v[2] = {act2(__builtin_elementwise_fma(float2v{y.x, y.y}, float2v{sc, sc}, float2v{bias.x, bias.y}), P.act),
+                  act2(__builtin_elementwise_fma(float2v{y.z, y.w}, float2v{sc, sc}, float2v{bias.z, bias.w}), P.act)};
+  if (P.res) add_residual<32>(v, residual_row(P, n, oy, ox, c0));   // uniform
+  float* dst = static_cast<float*>(P.out) + (inside ? ((size_t)n * P.Ho + oy) * P.Wo + ox : 0) * P.out_cstride + P.out_coff + c0;
+  if (P.out_plain) {
+    if (inside) *reinterpret_cast<float4*>(dst) = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
+  } else {
+    const uint4 chunk = pair_chunk<32>(v, sat);                     // lane l: hi chunk at +0, lane l + 32: lo chunk at +16 bytes
+    if (inside) *reinterpret_cast<uint4*>(dst) = chunk;
+  }
 }
-// 2 fp32 values -> hi halves, lo halves (conv_igemm_split.hip's split2: clamp to +-65504, flag what was clamped, NaN included)
-__device__ __forceinline__ void split2(const float2v v, unsigned& hi, unsigned& lo, bool& sat) {
-  const float2v x = {__builtin_amdgcn_fmed3f(v.x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v.y, -65504.f, 65504.f)};
-  sat |= x.x != v.x || x.y != v.y;
-  const half2v h = __builtin_convertvector(x, half2v);
-  const half2v l = __builtin_convertvector(x - __builtin_convertvector(h, float2v), half2v);
-  hi = __builtin_bit_cast(unsigned, h);
-  lo = __builtin_bit_cast(unsigned, l);
-}
-// ... without the clamp, for the transformed inputs: a V beyond fp16's range becomes inf, its lo half -inf or NaN, the
+// split2 (conv_split_device.hpp) without the clamp, for the transformed inputs: a V beyond fp16's range becomes inf, its lo half -inf or NaN, the
 // products NaN, and the epilogue's split2 flags the NaN (ConvProblem::sat_flag -> the detector falls back to exact fp32)
 __device__ __forceinline__ void split2_raw(const float2v x, unsigned& hi, unsigned& lo) {
   const half2v h = __builtin_convertvector(x, half2v);
@@ -122,27 +120,9 @@ void conv_wino_split_kernel(const ConvGroup g) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = wave >> 1, j = wave & 1;             // transform row of this wave, its 32-cout block
 
-  const int cnt = g.count;
-  int bb[kMaxGroup];
-#pragma unroll
-  for (int i = 0; i < kMaxGroup; ++i) bb[i] = g.p[i].block_begin;
-  const int xcd = blockIdx.x & 7;
-  const int L = g.xcd_begin[xcd] + (int)(blockIdx.x >> 3);
-  if (L >= g.xcd_begin[xcd + 1]) return;
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < kMaxGroup; ++i)
-    if (i < cnt && L >= bb[i]) pi = i;
-  const ConvProblem P = g.p[pi];
-
-  const int lb = L - P.block_begin;
-  const int ct = lb % P.n_ct;
-  const int pt = lb / P.n_ct;
-  const int tx0 = pt % P.tiles_x;
-  const int t2 = pt / P.tiles_x;
-  const int ty0 = t2 % P.tiles_y + P.ty_first;
-  const int n = t2 / P.tiles_y;
-  const int oy0 = ty0 * T::TH, ox0 = tx0 * T::TW;
+  ConvProblem P;                                     // launch header: conv_split_device.hpp
+  int ct, n, oy0, ox0;
+  if (!conv_block_decode<T::TH, T::TW>(g, P, ct, n, oy0, ox0)) return;
   const int nchunks = P.Cin / T::KC;
   const float* __restrict__ in = static_cast<const float*>(P.in);
 
@@ -376,48 +356,16 @@ void conv_wino_split_kernel(const ConvGroup g) {
     }
   }
 
-  // ---- bias, SiLU, residual, split, store: the lane's 2 x 2 pixels of tile mt, four channels each; lanes l and l + 32 hold
-  // the two halves of the 8-channel group 4 j + r of the cout tile (conv_igemm_split.hip's epilogue, without its LDS pass) ----
-  const float sc = P.acc_scale;
-  const bool plain = P.out_plain != 0, act = P.act != 0;
-  const void* const res_p = P.res;
-  const int cg = ct * T::BN + 32 * j + 8 * r;         // first channel of the group
+  // ---- bias, activation, residual, split, store: the lane's 2 x 2 pixels of tile mt, four channels each; lanes l and l + 32 hold
+  // the two halves of the 8-channel group 4 j + r of the cout tile ----
   const int mty = mt >> 3, mtx = mt & 7;
   bool sat = false;
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
-    for (int bq = 0; bq < 2; ++bq) {
-      const int oy = oy0 + 2 * mty + a, ox = ox0 + 2 * mtx + bq;
-      const bool inside = oy < P.Ho && ox < P.Wo;
-      const size_t pix = inside ? ((size_t)n * P.Ho + oy) * P.Wo + ox : 0;
-      float2v v[2] = {__builtin_elementwise_fma(float2v{y[a][bq].x, y[a][bq].y}, float2v{sc, sc}, float2v{bias4.x, bias4.y}),
-                      __builtin_elementwise_fma(float2v{y[a][bq].z, y[a][bq].w}, float2v{sc, sc}, float2v{bias4.z, bias4.w})};
-      if (act) { v[0] = silu2(v[0]); v[1] = silu2(v[1]); }
-      if (res_p) {                                   // uniform; the swaps need every lane
-        uint4 rc = make_uint4(0, 0, 0, 0);           // lane l: the group's hi chunk, lane l + 32: its lo chunk
-        if (inside) rc = *reinterpret_cast<const uint4*>(static_cast<const float*>(res_p) + pix * P.res_cstride + P.res_coff + cg + 4 * h);
-        const auto sx = __builtin_amdgcn_permlane32_swap(rc.x, rc.z, false, false);
-        const auto sy = __builtin_amdgcn_permlane32_swap(rc.y, rc.w, false, false);
-        const unsigned hw[2] = {sx[0], sy[0]}, lw[2] = {sx[1], sy[1]};
-        const half4 rh = *reinterpret_cast<const half4*>(hw), rl = *reinterpret_cast<const half4*>(lw);
-#pragma unroll
-        for (int k = 0; k < 2; ++k)
-          v[k] += float2v{(float)rh[2 * k], (float)rh[2 * k + 1]} + float2v{(float)rl[2 * k], (float)rl[2 * k + 1]};
-      }
-      float* dst = static_cast<float*>(P.out) + pix * P.out_cstride + P.out_coff + cg + 4 * h;
-      if (plain) {
-        if (inside) *reinterpret_cast<float4*>(dst) = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
-      } else {
-        uint2 hi, lo;
-        split2(v[0], hi.x, lo.x, sat);
-        split2(v[1], hi.y, lo.y, sat);
-        const auto sx = __builtin_amdgcn_permlane32_swap(hi.x, lo.x, false, false);
-        const auto sy = __builtin_amdgcn_permlane32_swap(hi.y, lo.y, false, false);
-        if (inside) *reinterpret_cast<uint4*>(dst) = make_uint4(sx[0], sy[0], sx[1], sy[1]);   // lane l: hi chunk at +0, lane l + 32: lo chunk at +16 bytes
-      }
-    }
-  if (P.sat_flag && __builtin_amdgcn_ballot_w64(sat) != 0 && lane == 0) atomicOr(P.sat_flag, 1);
+    for (int bq = 0; bq < 2; ++bq)
+      wino_store_pixel(y[a][bq], bias4, P, n, oy0 + 2 * mty + a, ox0 + 2 * mtx + bq, ct * T::BN + 32 * j + 8 * r + 4 * h, sat);
+  flag_saturation(P.sat_flag, sat, lane);
 }
 
 
@@ -456,27 +404,9 @@ void conv_wino2_split_kernel(const ConvGroup g) {
   const int lane = tid & 63;
   const int r = __builtin_amdgcn_readfirstlane(tid >> 6);   // the wave = the transform row its MFMAs work on
 
-  const int cnt = g.count;
-  int bb[kMaxGroup];
-#pragma unroll
-  for (int i = 0; i < kMaxGroup; ++i) bb[i] = g.p[i].block_begin;
-  const int xcd = blockIdx.x & 7;
-  const int L = g.xcd_begin[xcd] + (int)(blockIdx.x >> 3);
-  if (L >= g.xcd_begin[xcd + 1]) return;
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < kMaxGroup; ++i)
-    if (i < cnt && L >= bb[i]) pi = i;
-  const ConvProblem P = g.p[pi];
-
-  const int lb = L - P.block_begin;
-  const int ct = lb % P.n_ct;
-  const int pt = lb / P.n_ct;
-  const int tx0 = pt % P.tiles_x;
-  const int t2 = pt / P.tiles_x;
-  const int ty0 = t2 % P.tiles_y + P.ty_first;
-  const int n = t2 / P.tiles_y;
-  const int oy0 = ty0 * T::TH, ox0 = tx0 * T::TW;
+  ConvProblem P;                                     // launch header: conv_split_device.hpp
+  int ct, n, oy0, ox0;
+  if (!conv_block_decode<T::TH, T::TW>(g, P, ct, n, oy0, ox0)) return;
   const int nchunks = P.Cin / T::KC;
   const float* __restrict__ in = static_cast<const float*>(P.in);
 
@@ -736,9 +666,6 @@ void conv_wino2_split_kernel(const ConvGroup g) {
         }
   }
   __syncthreads();
-  const float sc = P.acc_scale;
-  const bool plain = P.out_plain != 0, act = P.act != 0;
-  const void* const res_p = P.res;
   bool sat = false;
 #pragma unroll
   for (int tb = 0; tb < 2; ++tb)
@@ -753,43 +680,14 @@ void conv_wino2_split_kernel(const ConvGroup g) {
         y[0][bq] = make_float4(s0.x + s1.x + s2.x, s0.y + s1.y + s2.y, s0.z + s1.z + s2.z, s0.w + s1.w + s2.w);
         y[1][bq] = make_float4(s1.x - s2.x - s3.x, s1.y - s2.y - s3.y, s1.z - s2.z - s3.z, s1.w - s2.w - s3.w);
       }
-      const int cg = ct * T::BN + 32 * j + 8 * r;     // first channel of the lane pair's 8-channel group
       const int tile = tb * 32 + mt, mty = tile >> 3, mtx = tile & 7;
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int bq = 0; bq < 2; ++bq) {
-          const int oy = oy0 + 2 * mty + a, ox = ox0 + 2 * mtx + bq;
-          const bool inside = oy < P.Ho && ox < P.Wo;
-          const size_t pix = inside ? ((size_t)n * P.Ho + oy) * P.Wo + ox : 0;
-          float2v v[2] = {__builtin_elementwise_fma(float2v{y[a][bq].x, y[a][bq].y}, float2v{sc, sc}, float2v{bias4[j].x, bias4[j].y}),
-                          __builtin_elementwise_fma(float2v{y[a][bq].z, y[a][bq].w}, float2v{sc, sc}, float2v{bias4[j].z, bias4[j].w})};
-          if (act) { v[0] = silu2(v[0]); v[1] = silu2(v[1]); }
-          if (res_p) {
-            uint4 rc = make_uint4(0, 0, 0, 0);
-            if (inside) rc = *reinterpret_cast<const uint4*>(static_cast<const float*>(res_p) + pix * P.res_cstride + P.res_coff + cg + 4 * h);
-            const auto sx = __builtin_amdgcn_permlane32_swap(rc.x, rc.z, false, false);
-            const auto sy = __builtin_amdgcn_permlane32_swap(rc.y, rc.w, false, false);
-            const unsigned hw[2] = {sx[0], sy[0]}, lw[2] = {sx[1], sy[1]};
-            const half4 rh = *reinterpret_cast<const half4*>(hw), rl = *reinterpret_cast<const half4*>(lw);
-#pragma unroll
-            for (int k = 0; k < 2; ++k)
-              v[k] += float2v{(float)rh[2 * k], (float)rh[2 * k + 1]} + float2v{(float)rl[2 * k], (float)rl[2 * k + 1]};
-          }
-          float* dst = static_cast<float*>(P.out) + pix * P.out_cstride + P.out_coff + cg + 4 * h;
-          if (plain) {
-            if (inside) *reinterpret_cast<float4*>(dst) = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
-          } else {
-            uint2 hi, lo;
-            split2(v[0], hi.x, lo.x, sat);
-            split2(v[1], hi.y, lo.y, sat);
-            const auto sx = __builtin_amdgcn_permlane32_swap(hi.x, lo.x, false, false);
-            const auto sy = __builtin_amdgcn_permlane32_swap(hi.y, lo.y, false, false);
-            if (inside) *reinterpret_cast<uint4*>(dst) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-          }
-        }
+        for (int bq = 0; bq < 2; ++bq)
+          wino_store_pixel(y[a][bq], bias4[j], P, n, oy0 + 2 * mty + a, ox0 + 2 * mtx + bq, ct * T::BN + 32 * j + 8 * r + 4 * h, sat);
     }
-  if (P.sat_flag && __builtin_amdgcn_ballot_w64(sat) != 0 && lane == 0) atomicOr(P.sat_flag, 1);
+  flag_saturation(P.sat_flag, sat, lane);
 }
 
 }  // namespace
@@ -855,23 +753,8 @@ void conv_wino_launch(const ConvGroup& g, const ConvConfig& c, hipStream_t strea
                   !p.post_w && !p.front_img && p.c_split == 0,
               "conv (Winograd): 3x3 stride 1, pad 1, Cout %% 64 == 0, Cin %% 16 == 0 only (Cin %d, Cout %d)", p.Cin, p.Cout);
   }
-  if (c.th == 16) {                                   // variant 4: 16 x 16 pixels, 4 waves, one per SIMD
-    auto kern2 = conv_wino2_split_kernel;
-    static std::once_flag once2;
-    std::call_once(once2, [&] {
-      GTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern2), hipFuncAttributeMaxDynamicSharedMemorySize, Wino2Tile::LDS_BYTES));
-    });
-    hipLaunchKernelGGL(kern2, dim3(g.grid_blocks), dim3(256), Wino2Tile::LDS_BYTES, stream, g);
-    GTX_HIP(hipGetLastError());
-    return;
-  }
-  auto kern = conv_wino_split_kernel;
-  static std::once_flag once;
-  std::call_once(once, [&] {
-    GTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, WinoTile::LDS_BYTES));
-  });
-  hipLaunchKernelGGL(kern, dim3(g.grid_blocks), dim3(512), WinoTile::LDS_BYTES, stream, g);
-  GTX_HIP(hipGetLastError());
+  if (c.th == 16) launch_conv_group<conv_wino2_split_kernel>(g, 256, Wino2Tile::LDS_BYTES, stream);   // variant 4: 16 x 16 pixels, 4 waves, one per SIMD
+  else launch_conv_group<conv_wino_split_kernel>(g, 512, WinoTile::LDS_BYTES, stream);
 }
 
 }  // namespace gtx

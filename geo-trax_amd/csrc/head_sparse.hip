@@ -5,7 +5,7 @@
 // input. This kernel evaluates the two layers for those anchors alone -- a wave takes four candidates of one level: the 3 x 3
 // neighbourhood of cv2[l][0] outputs the second layer needs (nine MFMA columns per candidate), then cv2[l][1] at the anchors --
 // with the arithmetic of the dense
-// kernels it replaces (conv_k32_split.hip: same packed weight images and power-of-two scales, same v_mfma_f32_16x16x32_f16
+// kernels it replaces (conv_k32_split.hip, through conv_split_device.hpp: same packed weight images and power-of-two scales, same v_mfma_f32_16x16x32_f16
 // sequence per output pixel -- chunk, kernel row, kernel column, small terms first -- same bias start, SiLU and hi / lo split,
 // zero padding at the image border for both layers), so a candidate's 64 box features are the dense path's bit for bit.
 // The wave then decodes its candidates' boxes (the final 1x1 convolution + DFL of head_boxes_kernel, same operations in the same
@@ -14,32 +14,14 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
+#include "conv_split_device.hpp"
 #include "det_kernels.hpp"
 
 namespace gtx {
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 #define GTXH_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
-
-// conv_k32_split.hip's epilogue arithmetic (same operations in the same order)
-__device__ __forceinline__ float2v silu2(const float2v v) {
-  const float2v t = v * -1.44269504088896341f;
-  const float2v d = float2v{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)} + 1.f;
-  return v * float2v{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-}
-__device__ __forceinline__ void split2(const float2v v, unsigned& hi, unsigned& lo, bool& sat) {
-  const float2v x = {__builtin_amdgcn_fmed3f(v.x, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v.y, -65504.f, 65504.f)};
-  sat |= x.x != v.x || x.y != v.y;
-  const half2v h = __builtin_convertvector(x, half2v);
-  const half2v l = __builtin_convertvector(x - __builtin_convertvector(h, float2v), half2v);
-  hi = __builtin_bit_cast(unsigned, h);
-  lo = __builtin_bit_cast(unsigned, l);
-}
 
 constexpr int kRowBytes = 256;                    // 64 channels in pair format
 constexpr int kCandPerWave = 4;                   // candidates of one level a wave works on: they share every weight fragment
@@ -89,7 +71,7 @@ __global__ __launch_bounds__(256) void head_sparse_box_kernel(const SparseBox sb
     for (int q = 0; q < 4; ++q) {
       const float4 b = *reinterpret_cast<const float4*>(L.b1 + 16 * q + 4 * kg);
 #pragma unroll
-      for (int c = 0; c < kCandPerWave; ++c) acc[c][q] = floatx4{b.x * inv_sc, b.y * inv_sc, b.z * inv_sc, b.w * inv_sc};
+      for (int c = 0; c < kCandPerWave; ++c) acc[c][q] = acc_start(b, inv_sc);
     }
   }
   const int nsteps = (L.cin / 32) * 9;
@@ -113,8 +95,8 @@ __global__ __launch_bounds__(256) void head_sparse_box_kernel(const SparseBox sb
     _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                             \
       const int row__ = 16 * q + col;                                                           \
       const char* w__ = wrow(L.w1, STEP, row__);                                                \
-      ah[R][q] = *reinterpret_cast<const half8*>(w__ + ((kg ^ ((row__ >> 1) & 7)) << 4));       \
-      al[R][q] = *reinterpret_cast<const half8*>(w__ + (((4 + kg) ^ ((row__ >> 1) & 7)) << 4)); \
+      ah[R][q] = *reinterpret_cast<const half8*>(w__ + ((kg ^ swz128(row__)) << 4));       \
+      al[R][q] = *reinterpret_cast<const half8*>(w__ + (((4 + kg) ^ swz128(row__)) << 4)); \
     }                                                                                           \
   }
 #define GTXH_STEP1(S, R)                                                                        \
@@ -136,8 +118,8 @@ __global__ __launch_bounds__(256) void head_sparse_box_kernel(const SparseBox sb
   }
 #undef GTXH_STEP1
 #undef GTXH_LOAD1
-  // SiLU, hi / lo split, pair rows in LDS: lane (col, kg) of block q holds channels 16 q + 4 kg + 0..3 of pixel col; two
-  // v_permlane16_swap make the 8-channel group's hi chunk (even kg) and lo chunk (odd kg): byte 64 q + 16 kg of the row
+  // SiLU, hi / lo split, pair rows in LDS: lane (col, kg) of block q holds channels 16 q + 4 kg + 0..3 of pixel col; pair_chunk<16>
+  // makes the 8-channel group's hi chunk (even kg) and lo chunk (odd kg): byte 64 q + 16 kg of the row
   bool sat = false;
 #pragma unroll
   for (int c = 0; c < kCandPerWave; ++c)
@@ -149,14 +131,10 @@ __global__ __launch_bounds__(256) void head_sparse_box_kernel(const SparseBox sb
         v[e] = silu2(float2v{acc[c][q][2 * e], acc[c][q][2 * e + 1]} * L.sc1);
         if (!valid1[c]) v[e] = float2v{0.f, 0.f};
       }
-      uint2 hi, lo;
       bool s1 = false;
-      split2(v[0], hi.x, lo.x, s1);
-      split2(v[1], hi.y, lo.y, s1);
+      const uint4 chunk = pair_chunk<16>(v, s1);
       sat |= s1 && col < 9;
-      const auto sx = __builtin_amdgcn_permlane16_swap(hi.x, lo.x, false, false);
-      const auto sy = __builtin_amdgcn_permlane16_swap(hi.y, lo.y, false, false);
-      if (col < 9) *reinterpret_cast<uint4*>(lds + (c * 9 + col) * kRowBytes + 64 * q + 16 * kg) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
+      if (col < 9) *reinterpret_cast<uint4*>(lds + (c * 9 + col) * kRowBytes + 64 * q + 16 * kg) = chunk;
     }
 
   // ---- second layer at the anchors: K = 64 x 9 over each candidate's nine staged pixels; MFMA column j works for candidate j & 3 ----
@@ -166,7 +144,7 @@ __global__ __launch_bounds__(256) void head_sparse_box_kernel(const SparseBox sb
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float4 b = *reinterpret_cast<const float4*>(L.b2 + 16 * q + 4 * kg);
-      acc2[q] = floatx4{b.x * inv_sc, b.y * inv_sc, b.z * inv_sc, b.w * inv_sc};
+      acc2[q] = acc_start(b, inv_sc);
     }
   }
   const char* mine = lds + (col & 3) * 9 * kRowBytes;
@@ -175,8 +153,8 @@ __global__ __launch_bounds__(256) void head_sparse_box_kernel(const SparseBox sb
   _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                               \
     const int row__ = 16 * q + col;                                                             \
     const char* w__ = wrow(L.w2, STEP, row__);                                                  \
-    wh[R][q] = *reinterpret_cast<const half8*>(w__ + ((kg ^ ((row__ >> 1) & 7)) << 4));         \
-    wl[R][q] = *reinterpret_cast<const half8*>(w__ + (((4 + kg) ^ ((row__ >> 1) & 7)) << 4));   \
+    wh[R][q] = *reinterpret_cast<const half8*>(w__ + ((kg ^ swz128(row__)) << 4));         \
+    wl[R][q] = *reinterpret_cast<const half8*>(w__ + (((4 + kg) ^ swz128(row__)) << 4));   \
   }
 #define GTXH_STEP2(S, R)                                                                        \
   {                                                                                             \
@@ -242,7 +220,7 @@ __global__ __launch_bounds__(256) void head_sparse_box_kernel(const SparseBox sb
       reinterpret_cast<float4*>(nb.cand_box)[(size_t)n * nb.cap + ci[c]] = make_float4(b.x - hw, b.y - hh, b.x + hw, b.y + hh);
     }
   }
-  if (sb.sat_flag && __builtin_amdgcn_ballot_w64(sat) != 0 && lane == 0) atomicOr(sb.sat_flag, 1);
+  flag_saturation(sb.sat_flag, sat, lane);
 }
 
 }  // namespace
