@@ -428,6 +428,12 @@ ConvConfig conv_pick_config(int dtype, int ks, int stride, int cin, int cout, in
       c.variant = 5;
       c.kc = 32;
     }
+    // 3x3 stride 2, whole 64-cout tiles, Cin a multiple of 32: the same instruction shape (conv_k32s2_split.hip). A caller that pins
+    // the K chunk keeps the 32x32x16 kernel (YOLOv8's model.1, which carries the fused front / post stages). GTX_K32S2=0: off
+    if (ks == 3 && stride == 2 && c.bn == 64 && c.variant == 2 && force_kc == 0 && cin % 32 == 0 && cout % 64 == 0 && env_int("GTX_K32S2", 1) != 0) {
+      c.variant = 7;
+      c.kc = 32;
+    }
     // 1x1 with whole 64-cout tiles and 32-channel chunks: the pointwise v_mfma_f32_16x16x32_f16 forms (conv_k32p_split.hip) are built
     // by `make K32P=1`, bit-comparison-tested and OFF: 0.97 x / 0.81 x of the 32x32x16 kernel on RT-DETR's 1x1 layers
     // (profiles/r06_k32p_probe.txt). GTX_K32P=1: pixels staged in LDS, 2: pixels straight into the operand registers. Same weight
@@ -478,7 +484,7 @@ std::vector<uint8_t> pack_conv_weights_wino(const float*, int, int, const ConvCo
 
 std::vector<uint8_t> pack_conv_weights(const float* w, int cout, int cin, const ConvConfig& cfg, float* acc_scale) {
   if (acc_scale) *acc_scale = 1.f;
-  if (cfg.variant >= 2 && cfg.variant <= 6) {
+  if (cfg.variant >= 2 && cfg.variant <= 7) {
     float sc = 1.f;
     std::vector<uint8_t> r = (cfg.variant == 3 || cfg.variant == 4) ? pack_conv_weights_wino(w, cout, cin, cfg, &sc) : pack_conv_weights_split(w, cout, cin, cfg, &sc);
     if (acc_scale) *acc_scale = sc;
@@ -604,6 +610,7 @@ void conv_launch(const ConvGroup& g, const ConvConfig& cfg, hipStream_t stream) 
   if (cfg.variant == 3 || cfg.variant == 4) return conv_wino_launch(g, cfg, stream);
   if (cfg.variant == 5) return conv_k32_launch(g, cfg, stream);
   if (cfg.variant == 6) return conv_k32p_launch(g, cfg, stream);
+  if (cfg.variant == 7) return conv_k32s2_launch(g, cfg, stream);
   if (cfg.variant == 2) return conv_split_launch(g, cfg, stream);
   if (cfg.dtype == DT_F16) launch_dt<_Float16>(g, cfg, stream);
   else launch_dt<float>(g, cfg, stream);
@@ -615,6 +622,7 @@ const char* conv_kernel_name(const ConvConfig& c) {
   if (c.variant == 4) return "conv_wino2_split_kernel";
   if (c.variant == 5) return "conv_k32_split_kernel";
   if (c.variant == 6) return "conv_k32p_split_kernel";
+  if (c.variant == 7) return "conv_k32s2_split_kernel";
   if (c.variant == 2) {
     snprintf(buf, sizeof buf, "conv_igemm_split_kernel<%d, %d, %d, %d, %d>", c.ks, c.stride, c.bn / 32, c.kc / 8, c.th / 8);
     return buf;

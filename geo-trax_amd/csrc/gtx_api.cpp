@@ -290,6 +290,41 @@ int gtx_op_conv2d(gtx_ctx* ctx, const gtx_conv_desc* d, const void* x, const flo
   });
 }
 
+int gtx_op_conv2d_group(gtx_ctx* ctx, int n_members, const gtx_conv_desc* descs, const void* const* xs, const float* const* ws,
+                        const float* const* biases, void* const* ys, const int* ty_first, const int* ty_count) {
+  return guarded([&] {
+    need(descs, "descs"); need(xs, "xs"); need(ws, "ws"); need(ys, "ys");
+    if (n_members < 1 || n_members > gtx::kMaxGroup) gtx::fail(GTX_ERR_INVALID, "1..%d members", gtx::kMaxGroup);
+    std::vector<ConvOpState> st(n_members);
+    gtx::ConvGroup g{};
+    for (int i = 0; i < n_members; ++i) {
+      need(xs[i], "x"); need(ws[i], "w"); need(ys[i], "y");
+      if (descs[i].has_residual) gtx::fail(GTX_ERR_INVALID, "grouped op: no residual");
+      conv_setup(ctx, &descs[i], xs[i], ws[i], biases ? biases[i] : nullptr, nullptr, ys[i], st[i]);
+      const gtx::ConvConfig &a = st[0].cfg, &b = st[i].cfg;
+      if (a.dtype != b.dtype || a.ks != b.ks || a.stride != b.stride || a.bn != b.bn || a.kc != b.kc || a.variant != b.variant || a.th != b.th)
+        gtx::fail(GTX_ERR_INVALID, "grouped op: member %d picks another kernel than member 0", i);
+      g.p[i] = st[i].g.p[0];
+      g.p[i].ty_first = ty_first ? ty_first[i] : 0;
+      g.p[i].ty_count = ty_count ? ty_count[i] : 0;
+    }
+    g.count = n_members;
+    gtx::conv_group_finalize(g, st[0].cfg);
+    gtx::conv_launch(g, st[0].cfg, ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < n_members; ++i) {
+      const size_t yb = (size_t)descs[i].n * st[i].ho * st[i].wo * descs[i].out_cstride * gtx::dtype_size(descs[i].dtype);
+      if (descs[i].dtype == GTX_F32S) {                 // pair format -> the caller's plain fp32 array
+        std::vector<uint8_t> tmp(yb);
+        GTX_HIP(hipMemcpy(tmp.data(), st[i].y.p, yb, hipMemcpyDeviceToHost));
+        gtx::pairs_to_f32(tmp.data(), static_cast<float*>(ys[i]), yb / 4);
+      } else {
+        GTX_HIP(hipMemcpy(ys[i], st[i].y.p, yb, hipMemcpyDeviceToHost));
+      }
+    }
+  });
+}
+
 int gtx_op_conv_xcd_ranges(int n_members, const int* blocks, const int* cin, int xcd_begin[9], int* grid_blocks) {
   return guarded([&] {
     need(blocks, "blocks"); need(cin, "cin"); need(xcd_begin, "xcd_begin");

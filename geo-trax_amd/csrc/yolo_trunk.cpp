@@ -58,6 +58,12 @@ View YoloTrunk::conv(const std::string& name, const View& x, int stride, const V
   GTX_CHECK(net_.format() != DT_F32S || !up_src || !up_src->plain, "%s: a plain fp32 tensor cannot feed a split convolution", name.c_str());
   NetRuntime::ConvArgs a;
   a.stride = stride; a.act = 1; a.out_slice = out_slice; a.residual = residual;
+  // The fused post / front stages (fuse_front, fuse_stem) are stages of the 32x32x16 kernel and read its 16-channel-chunk weight
+  // image. The one layer they can attach to -- model.1 with all its couts in one tile, YOLOv8 n / s -- keeps that kernel while
+  // either fusion is enabled; conv_pick_config leaves a pinned K chunk alone.
+  if (net_.format() == DT_F32S && stride == 2 && name == "model.1.conv" && net_.tensor(name + ".weight").shape[0] <= 64 &&
+      (env_flag("GTX_FUSE_FRONT", true) || env_flag("GTX_FUSE_STEM", true)))
+    a.force_kc = 16;
   const View out = net_.emit_named_conv(ops_, name, x, a);
   if (up_src) {
     Op& op = ops_.back();

@@ -53,6 +53,37 @@ def conv2d(x: np.ndarray, w_ohwi: np.ndarray, bias: np.ndarray | None = None, *,
     return out
 
 
+def conv2d_group(members, *, stride: int = 1, act: bool = True, split: bool = False, ctx: _lib.Context | None = None):
+    """One grouped launch (the Detect stages' form). members: dicts with x [n,h,w,cs], w [cout,k,k,cin] and optionally bias,
+    in_coff, out (the output buffer as it is before the launch), out_coff, ty_first, ty_count (compute only these 8-row output
+    tile rows; the others keep what `out` holds). Returns the members' outputs."""
+    ctx = ctx or _lib.default_context()
+    m = len(members)
+    descs = (ConvDesc * m)()
+    keep, outs = [], []
+    xs, ws, bs, ys = (C.c_void_p * m)(), (C.c_void_p * m)(), (C.c_void_p * m)(), (C.c_void_p * m)()
+    tf, tc = (C.c_int * m)(), (C.c_int * m)()
+    for i, mem in enumerate(members):
+        x = np.ascontiguousarray(mem["x"])
+        w = np.ascontiguousarray(mem["w"], dtype=np.float32)
+        cout, k, _, cin = w.shape
+        n, h, wd, cs = x.shape
+        pad = k // 2
+        ho, wo = (h + 2 * pad - k) // stride + 1, (wd + 2 * pad - k) // stride + 1
+        out = mem.get("out")
+        out = np.zeros((n, ho, wo, cout), dtype=x.dtype) if out is None else np.array(out, dtype=x.dtype, order="C")
+        assert out.shape[:3] == (n, ho, wo)
+        b = None if mem.get("bias") is None else np.ascontiguousarray(mem["bias"], dtype=np.float32)
+        descs[i] = ConvDesc(dtype=GTX_F32S if split else _dt(x), n=n, h=h, w=wd, cin=cin, cout=cout, ksize=k, stride=stride, act=int(act),
+                            in_cstride=cs, in_coff=mem.get("in_coff", 0), out_cstride=out.shape[3], out_coff=mem.get("out_coff", 0), has_residual=0)
+        xs[i], ws[i], bs[i], ys[i] = x.ctypes.data, w.ctypes.data, (b.ctypes.data if b is not None else None), out.ctypes.data
+        tf[i], tc[i] = mem.get("ty_first", 0), mem.get("ty_count", 0)
+        keep += [x, w, b]
+        outs.append(out)
+    check(ctx.lib.gtx_op_conv2d_group(ctx.handle, m, descs, xs, ws, bs, ys, tf, tc))
+    return outs
+
+
 def conv2d_time(dtype, n, h, w, cin, cout, ksize, stride, iters=20, ctx=None):
     """Mean kernel time (ms) and algorithmic FLOPs of one conv launch on zero-filled data."""
     ctx = ctx or _lib.default_context()

@@ -183,6 +183,13 @@ int gtx_op_conv2d(gtx_ctx* ctx, const gtx_conv_desc* d, const void* x, const flo
  * HIP events on the launch stream, plus the algorithmic FLOPs of one launch. */
 int gtx_op_conv2d_time(gtx_ctx* ctx, const gtx_conv_desc* d, int iters, float* ms_per_launch,
                        double* flops);
+/* One GROUPED launch of n_members convolutions (the Detect stages' form: members of different Cin and map size share one
+ * kernel configuration and one grid). Arrays of n_members entries: descs, xs, ws, biases (entries or the array may be NULL)
+ * and ys as in gtx_op_conv2d (no residual). ty_first / ty_count (arrays or NULL): ty_count[i] > 0 computes only the
+ * 8-row output tile rows [ty_first[i], ty_first[i] + ty_count[i]) of member i; the other rows of ys[i] come back as given.
+ * Fails when the members do not pick the same kernel. */
+int gtx_op_conv2d_group(gtx_ctx* ctx, int n_members, const gtx_conv_desc* descs, const void* const* xs, const float* const* ws,
+                        const float* const* biases, void* const* ys, const int* ty_first, const int* ty_count);
 /* Host only (no GPU call): how a grouped convolution launch is cut over the 8 XCDs. n_members problems of
  * blocks[i] workgroups with cin[i] input channels each, in launch order. xcd_begin[0..8]: hardware block b takes
  * logical block xcd_begin[b & 7] + (b >> 3) and exits when that reaches xcd_begin[(b & 7) + 1]; the ranges hold equal
