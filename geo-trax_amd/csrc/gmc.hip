@@ -43,11 +43,6 @@ struct Pyr {
   int w[kMaxLevel + 1], h[kMaxLevel + 1];
 };
 
-struct GmcResult {
-  int n_prev, n_valid, best_count, pad;
-  double a, b, tx, ty;
-};
-
 __device__ __forceinline__ int refl101(int i, int n) {
   const int p = 2 * (n - 1);
   i = (i < 0 ? -i : i) % p;
@@ -543,6 +538,40 @@ bool similarity_from(const std::vector<float4>& pr, const std::vector<char>& inl
 
 }  // namespace
 
+void gmc_launch_gray_half(const uint8_t* bgr, int w, uint8_t* out, int oh, int ow, hipStream_t s) {
+  hipLaunchKernelGGL(gray_half_kernel, dim3(cdiv(ow, 256), oh), dim3(256), 0, s, bgr, w, out, oh, ow);
+}
+
+void gmc_launch_ransac(const float4* pairs, GmcResult* res, unsigned seed, double4* model, int* count, hipStream_t s) {
+  static_assert(kGmcHypotheses == kHyp, "one hypothesis count");
+  hipLaunchKernelGGL(ransac_kernel, dim3(kHyp / 4), dim3(256), 0, s, pairs, res, seed, model, count);
+  hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(kHyp), 0, s, model, count, res);
+}
+
+bool gmc_refit(const GmcResult& R, const float4* pairs, double scale, double A[6], int* n_inliers) {
+  if (!(R.n_valid > 4 && R.best_count >= 0)) return false;
+  std::vector<float4> pr(pairs, pairs + R.n_valid);
+  double M[6] = {R.a, -R.b, R.tx, R.b, R.a, R.ty};
+  std::vector<char> inl(pr.size());
+  int n_inl = 0;
+  for (int it = 0; it < 3; ++it) {
+    n_inl = 0;
+    for (size_t i = 0; i < pr.size(); ++i) {
+      const double ex = M[0] * pr[i].x + M[1] * pr[i].y + M[2] - pr[i].z, ey = M[3] * pr[i].x + M[4] * pr[i].y + M[5] - pr[i].w;
+      inl[i] = (ex * ex + ey * ey < kRansacThr * kRansacThr) ? 1 : 0;
+      n_inl += inl[i];
+    }
+    if (n_inl < 2) break;
+    double M2[6];
+    if (!similarity_from(pr, inl, M2)) break;
+    std::memcpy(M, M2, sizeof M);
+  }
+  M[2] *= scale; M[5] *= scale;
+  std::memcpy(A, M, sizeof M);
+  *n_inliers = n_inl;
+  return true;
+}
+
 struct Gmc::Impl {
   int device;
   // Two streams: frame t works on st[t & 1]. Pyramid + corner detection of a frame need nothing from other
@@ -666,9 +695,7 @@ void Gmc::submit_gray_dev(const void* gray, int gh, int gw) {
                        S.next[c].as<float2>(), S.status[c].as<int>());
     hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(1024), 0, s, S.pts[p].as<float2>(), S.next[c].as<float2>(), S.status[c].as<int>(),
                        S.npts[p].as<int>(), S.pairs[c].as<float4>(), S.res[c].as<GmcResult>());
-    hipLaunchKernelGGL(ransac_kernel, dim3(kHyp / 4), dim3(256), 0, s, S.pairs[c].as<float4>(), S.res[c].as<GmcResult>(), S.seed,
-                       S.model[c].as<double4>(), S.count[c].as<int>());
-    hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(kHyp), 0, s, S.model[c].as<double4>(), S.count[c].as<int>(), S.res[c].as<GmcResult>());
+    gmc_launch_ransac(S.pairs[c].as<float4>(), S.res[c].as<GmcResult>(), S.seed, S.model[c].as<double4>(), S.count[c].as<int>(), s);
     GTX_HIP(hipMemcpyAsync(S.h_res + slot, S.res[c].p, sizeof(GmcResult), hipMemcpyDeviceToHost, s));
     GTX_HIP(hipMemcpyAsync(S.h_pairs + (size_t)slot * 1024, S.pairs[c].p, sizeof(float4) * 1024, hipMemcpyDeviceToHost, s));
   }
@@ -691,7 +718,7 @@ void Gmc::submit_frame(const uint8_t* frame_bgr, int h, int w) {
   hipStream_t s = S.st[S.cur];
   if (gray.bytes < (size_t)S.w * S.h) gray.alloc((size_t)S.w * S.h);
   GTX_HIP(hipMemcpyAsync(S.frame.p, frame_bgr, bytes, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(gray_half_kernel, dim3(cdiv(S.w, 256), S.h), dim3(256), 0, s, S.frame.as<uint8_t>(), w, gray.as<uint8_t>(), S.h, S.w);
+  gmc_launch_gray_half(S.frame.as<uint8_t>(), w, gray.as<uint8_t>(), S.h, S.w, s);
   submit_gray_dev(gray.p, S.h, S.w);
 }
 
@@ -704,7 +731,7 @@ void Gmc::submit_frame_dev(const void* frame_bgr_dptr, int h, int w, bool restar
   DevBuf& gbuf = S.gray[S.cur];
   if (gbuf.bytes < (size_t)S.w * S.h) gbuf.alloc((size_t)S.w * S.h);
   uint8_t* gray = gbuf.as<uint8_t>();
-  hipLaunchKernelGGL(gray_half_kernel, dim3(cdiv(S.w, 256), S.h), dim3(256), 0, S.st[S.cur], static_cast<const uint8_t*>(frame_bgr_dptr), w, gray, S.h, S.w);
+  gmc_launch_gray_half(static_cast<const uint8_t*>(frame_bgr_dptr), w, gray, S.h, S.w, S.st[S.cur]);
   if (restart) S.have_prev = false;
   submit_gray_dev(gray, S.h, S.w);
 }
@@ -722,26 +749,8 @@ void Gmc::collect(double A[6], int* valid, int stats[3]) {
   if (!S.first[slot]) {
     const GmcResult& R = S.h_res[slot];
     S.stats[0] = R.n_prev; S.stats[1] = R.n_valid;
-    if (R.n_valid > 4 && R.best_count >= 0) {
-      const float4* hp = S.h_pairs + (size_t)slot * 1024;
-      std::vector<float4> pr(hp, hp + R.n_valid);
-      double M[6] = {R.a, -R.b, R.tx, R.b, R.a, R.ty};
-      std::vector<char> inl(pr.size());
-      int n_inl = 0;
-      for (int it = 0; it < 3; ++it) {
-        n_inl = 0;
-        for (size_t i = 0; i < pr.size(); ++i) {
-          const double ex = M[0] * pr[i].x + M[1] * pr[i].y + M[2] - pr[i].z, ey = M[3] * pr[i].x + M[4] * pr[i].y + M[5] - pr[i].w;
-          inl[i] = (ex * ex + ey * ey < kRansacThr * kRansacThr) ? 1 : 0;
-          n_inl += inl[i];
-        }
-        if (n_inl < 2) break;
-        double M2[6];
-        if (!similarity_from(pr, inl, M2)) break;
-        std::memcpy(M, M2, sizeof M);
-      }
-      M[2] *= 2.0; M[5] *= 2.0;       // back to full-resolution pixels (downscale 2)
-      std::memcpy(A, M, sizeof M);
+    int n_inl = 0;
+    if (gmc_refit(R, S.h_pairs + (size_t)slot * 1024, 2.0, A, &n_inl)) {   // x 2: back to full-resolution pixels (downscale 2)
       S.stats[2] = n_inl;
       if (valid) *valid = 1;
     }

@@ -9,6 +9,23 @@
 
 namespace gtx {
 
+// Device-side record of one frame's fit: filled by the compaction step (counts, identity model), then by the RANSAC winner.
+struct GmcResult {
+  int n_prev, n_valid, best_count, pad;
+  double a, b, tx, ty;
+};
+
+// ---- steps shared with the feature-based methods (gmc_feat.hip), each one enqueued on `s`
+constexpr int kGmcHypotheses = 512;
+// BGR u8 [2 * oh][w][3] -> gray (cv2 fixed point) -> exact 2x2 mean [oh][ow], as the detector's preprocess pass writes it
+void gmc_launch_gray_half(const uint8_t* bgr, int w, uint8_t* out, int oh, int ow, hipStream_t s);
+// 512 two-point similarity hypotheses over pairs[0 .. res->n_valid) = (p.x, p.y, q.x, q.y), 3 px threshold, first best wins ->
+// res->{best_count, a, b, tx, ty}. model / count: scratch of kGmcHypotheses entries. The procedure gtx_op_estimate_affine_partial states.
+void gmc_launch_ransac(const float4* pairs, GmcResult* res, unsigned seed, double4* model, int* count, hipStream_t s);
+// Host half of the fit: three rounds of least squares on the inliers of the RANSAC winner, translation x `scale`.
+// false (A untouched): fewer than 5 pairs or no hypothesis.
+bool gmc_refit(const GmcResult& R, const float4* pairs, double scale, double A[6], int* n_inliers);
+
 class Gmc {
  public:
   // gray_h x gray_w: the half-resolution gray image the method works on (frame size / 2).

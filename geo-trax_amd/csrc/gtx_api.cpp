@@ -17,6 +17,7 @@
 #include "geometry.hpp"
 #include "ecc.hpp"
 #include "gmc.hpp"
+#include "gmc_feat.hpp"
 #include "match_l2.hpp"
 #include "register.hpp"
 #include "sift.hpp"
@@ -445,6 +446,56 @@ int gtx_gmc_collect(gtx_gmc* g, double A[6], int* valid, int stats[3]) {
 }
 int gtx_gmc_points(gtx_gmc* g, int which, int cap, int* n, float* xy, int* status) {
   return guarded([&] { need(g, "gmc"); need(n, "n"); g->impl->debug_points(which, cap, n, xy, status); });
+}
+
+struct gtx_fgmc {
+  gtx_ctx* ctx;
+  std::unique_ptr<gtx::FeatGmc> impl;
+};
+
+int gtx_fgmc_create(gtx_ctx* ctx, int frame_h, int frame_w, int max_features, int seed, gtx_fgmc** out) {
+  return guarded([&] {
+    need(ctx, "ctx"); need(out, "out");
+    GTX_HIP(hipSetDevice(ctx->device));
+    std::unique_ptr<gtx_fgmc> g(new gtx_fgmc);
+    g->ctx = ctx;
+    g->impl.reset(new gtx::FeatGmc(ctx, frame_h, frame_w, max_features, seed));
+    *out = g.release();
+  });
+}
+void gtx_fgmc_destroy(gtx_fgmc* g) { delete g; }
+int gtx_fgmc_reset(gtx_fgmc* g) {
+  return guarded([&] { need(g, "gmc"); g->impl->reset(); });
+}
+int gtx_fgmc_restart(gtx_fgmc* g) {
+  return guarded([&] { need(g, "gmc"); g->impl->restart(); });
+}
+int gtx_fgmc_submit_gray_dev(gtx_fgmc* g, const void* gray_dptr, int gh, int gw) {
+  return guarded([&] { need(g, "gmc"); need(gray_dptr, "gray"); g->impl->submit_gray_dev(gray_dptr, gh, gw); });
+}
+int gtx_fgmc_submit_gray(gtx_fgmc* g, const uint8_t* gray, int gh, int gw) {
+  return guarded([&] { need(g, "gmc"); need(gray, "gray"); g->impl->submit_gray(gray, gh, gw); });
+}
+int gtx_fgmc_submit_frame_dev(gtx_fgmc* g, const void* frame_bgr_dptr, int h, int w, int restart) {
+  return guarded([&] { need(g, "gmc"); need(frame_bgr_dptr, "frame"); g->impl->submit_frame_dev(frame_bgr_dptr, h, w, restart != 0); });
+}
+int gtx_fgmc_collect(gtx_fgmc* g, double A[6], int* valid, int stats[3]) {
+  return guarded([&] { need(g, "gmc"); need(A, "A"); g->impl->collect(A, valid, stats); });
+}
+int gtx_fgmc_pairs(gtx_fgmc* g, int cap, int* n, float* pairs4) {
+  return guarded([&] { need(g, "gmc"); need(n, "n"); g->impl->debug_pairs(cap, n, pairs4); });
+}
+int gtx_fgmc_matches(gtx_fgmc* g, int cap, int* n_q, int* n_t, int* best_idx, int* best_d, int* second_d, float* q_xy, float* t_xy) {
+  return guarded([&] { need(g, "gmc"); need(n_q, "n_q"); need(n_t, "n_t"); g->impl->debug_matches(cap, n_q, n_t, best_idx, best_d, second_d, q_xy, t_xy); });
+}
+int gtx_gray_half_dev(gtx_ctx* ctx, const void* frame_bgr_dptr, int h, int w, void* gray_dptr) {
+  return guarded([&] {
+    need(ctx, "ctx"); need(frame_bgr_dptr, "frame"); need(gray_dptr, "gray");
+    if (h < 2 || w < 2) gtx::fail(GTX_ERR_INVALID, "gtx_gray_half_dev: frame %dx%d", w, h);
+    GTX_HIP(hipSetDevice(ctx->device));
+    gtx::gmc_launch_gray_half(static_cast<const uint8_t*>(frame_bgr_dptr), w, static_cast<uint8_t*>(gray_dptr), h / 2, w / 2, ctx->stream);
+    GTX_HIP(hipGetLastError());
+  });
 }
 
 struct gtx_ecc {

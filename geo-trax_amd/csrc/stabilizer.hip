@@ -1153,6 +1153,7 @@ struct Stabilizer::Impl {
   void build_rects(const float* boxes, int n, std::vector<int4>& rects) const;
   void extract(const uint8_t* gray_dev, const float* boxes, int n, const Levels& L, int slots, Feat& out);
   void gray_from_frame(const uint8_t* frame, int h, int w);
+  void launch_match();
   void submit_match();
   void collect(double Hout[9], int* valid_out, int st[4]);
 };
@@ -1546,7 +1547,7 @@ bool refine_homography(const std::vector<float4>& pts, double cx, double cy, dou
 
 // Asynchronous half of a stabilize pass: match -> ratio -> RANSAC on the stream, then two D2H
 // copies (result record, match points) into pinned memory and an event.
-void Stabilizer::Impl::submit_match() {
+void Stabilizer::Impl::launch_match() {
   hipStream_t s = ctx->stream;
   const int max_q = slots_cur, n_chunks = cdiv(slots_ref, kMatchChunk);
   hipLaunchKernelGGL(match_kernel, dim3(cdiv(slots_cur, 256), n_chunks), dim3(256), 0, s, cur.desc.as<unsigned long long>(),
@@ -1554,6 +1555,11 @@ void Stabilizer::Impl::submit_match() {
                      d_pd2.as<int>(), d_mticket.as<unsigned>(), cfg.filter_ratio, cfg.filter_type == 1 ? 1 : 0, cur.xy.as<float2>(), ref.xy.as<float2>(),
                      d_bidx.as<int>(), d_bd.as<int>(), d_sd.as<int>(), d_mq.as<int>(), d_mt.as<int>(), d_md.as<int>(), d_mpts(),
                      d_nmatch.as<int>());
+}
+
+void Stabilizer::Impl::submit_match() {
+  hipStream_t s = ctx->stream;
+  launch_match();
   const double cx = fw / 2.0, cy = fh / 2.0, sc = 2.0 / fw;
   const float thr2 = cfg.ransac_threshold * cfg.ransac_threshold;
   hipLaunchKernelGGL(ransac_kernel, dim3(cdiv(n_hyp, 8)), dim3(512), 0, s, d_mpts(), d_nmatch.as<int>(), cur.n.as<int>(), cfg.seed, n_hyp,
@@ -1649,6 +1655,28 @@ void Stabilizer::promote_cur_to_ref() {
 }
 
 float Stabilizer::last_ms() const { return impl_->last_ms; }
+
+void Stabilizer::extract_cur_async(const void* gray) {
+  Impl& S = *impl_;
+  GTX_CHECK(S.slots_ref == S.slots_cur, "stabilizer: the reference holds %d keypoint slots, a frame %d (ref_multiplier must be 1)", S.slots_ref, S.slots_cur);
+  S.extract(static_cast<const uint8_t*>(gray), nullptr, 0, S.lev_cur, S.slots_cur, S.cur);
+}
+
+void Stabilizer::match_cur_async() {
+  impl_->launch_match();
+  GTX_HIP(hipGetLastError());
+}
+
+void Stabilizer::swap_sets() { std::swap(impl_->ref, impl_->cur); }
+
+Stabilizer::FeatureSet Stabilizer::feature_set(int which) const {
+  const Impl::Feat& f = which == 0 ? impl_->ref : impl_->cur;
+  return {f.xy.as<float2>(), f.n.as<int>()};
+}
+
+Stabilizer::RawMatches Stabilizer::raw_matches() const { return {impl_->d_bidx.as<int>(), impl_->d_bd.as<int>(), impl_->d_sd.as<int>()}; }
+
+int Stabilizer::slots() const { return impl_->slots_cur; }
 
 void Stabilizer::collect(double H[9], int* valid, int stats[4]) {
   GTX_HIP(hipSetDevice(impl_->ctx->device));

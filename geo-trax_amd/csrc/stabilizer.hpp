@@ -30,6 +30,18 @@ class Stabilizer {
   // GPU time (ms, stream-ordered events) of the last collected submit_gray_dev pass: keypoints -> matching -> RANSAC
   float last_ms() const;
 
+  // ---- the stages on their own, for a caller that chains them on the context's stream itself (gmc_feat.hip: every frame is
+  // matched against the one before it). Nothing here waits for the device or touches the object's host-side results; the two
+  // feature sets must have the same plan (ref_multiplier 1).
+  struct FeatureSet { const float2* xy; const int* n; };          // full-resolution keypoint positions and their count, in HBM
+  struct RawMatches { const int *best_idx, *best_d, *second_d; };  // per query keypoint: nearest reference keypoint (-1: none), its and the second nearest's Hamming distance
+  void extract_cur_async(const void* gray);     // keypoints + descriptors of a gray image in HBM (read in place) -> the current set
+  void match_cur_async();                       // Hamming 2-NN of the current set (query) against the reference set
+  void swap_sets();                             // current <-> reference: later launches see the swapped sets (host-side handles only)
+  FeatureSet feature_set(int which) const;      // 0 = reference, 1 = current
+  RawMatches raw_matches() const;
+  int slots() const;                            // keypoint slots per set
+
  private:
   struct Impl;
   std::unique_ptr<Impl> impl_;

@@ -113,6 +113,17 @@ _SIGNATURES = {
     "gtx_gmc_submit_frame_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
     "gtx_gmc_collect": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
     "gtx_gmc_points": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P]),
+    "gtx_fgmc_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "gtx_fgmc_destroy": (None, [_P]),
+    "gtx_fgmc_reset": (C.c_int, [_P]),
+    "gtx_fgmc_restart": (C.c_int, [_P]),
+    "gtx_fgmc_submit_gray_dev": (C.c_int, [_P, _P, C.c_int, C.c_int]),
+    "gtx_fgmc_submit_gray": (C.c_int, [_P, _P, C.c_int, C.c_int]),
+    "gtx_fgmc_submit_frame_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
+    "gtx_fgmc_collect": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
+    "gtx_fgmc_pairs": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), _P]),
+    "gtx_fgmc_matches": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _P, _P, _P, _P, _P]),
+    "gtx_gray_half_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "gtx_ecc_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(_P)]),
     "gtx_ecc_destroy": (None, [_P]),
     "gtx_ecc_reset": (C.c_int, [_P]),

@@ -259,7 +259,7 @@ class StreamPlan:
 class ExtractEngine:
     def __init__(self, weights: dict, frame_hw: tuple[int, int], det_kw: dict, tracker: Tracker | None, stab_kw: dict | None, *,
                  device: int | None = None, batch: int = 2, det_streams: int = 2, stab_streams: int = 4, gmc: bool | str = False,
-                 detectors: list[Detector] | None = None, feeder_stream: bool = False):
+                 detectors: list[Detector] | None = None, feeder_stream: bool = False, gmc_kw: dict | None = None):
         """det_kw: Detector keywords (imgsz, conf, iou, max_det, classes, agnostic_nms, half, rect). tracker None: raw
         detections pass through (ids None; the frame-sharded bench tracks later on rank 0). stab_kw None: no
         stabilization. `detectors`: already-built Detector objects to adopt (same weights, own contexts). `feeder_stream`: also
@@ -307,7 +307,8 @@ class ExtractEngine:
         if gmc:                          # True / "sparseOptFlow": the GPU Lucas-Kanade GMC; "orb" / "sift": the feature-based ones (gmc.FeatureGMC); "ecc": gmc.EccGMC
             from .gmc import make_gmc
 
-            self.gmc = make_gmc(self.frame_hw, method=gmc if isinstance(gmc, str) else "sparseOptFlow", ctx=take("g"))
+            self.gmc = make_gmc(self.frame_hw, method=gmc if isinstance(gmc, str) else "sparseOptFlow", ctx=take("g"),
+                                **(gmc_kw or {}))    # gmc_kw: the GMC object's own keywords (`engine: {gmc: {...}}`, e.g. ecc's max_iters)
         self.use_dev_gray = bool(self.stabs) and float(stab_kw.get("downsample_ratio", 0.5)) == 0.5
         self._stage = {}                 # per detector: device staging buffer for host frames
         self._host_frames = {}           # frames kept for the host-gray fallback of the stabilizer
@@ -474,7 +475,13 @@ class ExtractEngine:
                 prev = False if prev is None else prev          # None: the batch opens the clip -> restart without a frame
             det = self.dets[k % len(self.dets)]
             k += 1
-            inflight.append((det, self._submit(det, b), prev))
+            n_skip = 0
+            if prev is not None and prev is not False and self.gmc is not None and getattr(self.gmc, "wants_frames", False):
+                # gmc_method ecc registers every frame against the clip's FIRST frame: a shard rank that does not hold that frame
+                # hands it over here (`prev`), once, ahead of its first batch -- it becomes the template, its identity warp is dropped
+                n_skip = self.gmc.submit_frame_dev(int(prev), self.frame_hw[0], self.frame_hw[1])
+                self._gmc_sub += n_skip
+            inflight.append((det, self._submit(det, b), prev, n_skip))
             self._frames_of[id(det)] = self._last_frames
 
         host_gray = bool(self.stabs) and not self.use_dev_gray
@@ -486,7 +493,7 @@ class ExtractEngine:
             submit_next()
             fill()
             while inflight:
-                det, nb, prev = inflight.popleft()
+                det, nb, prev, n_skip = inflight.popleft()
                 t0 = time.perf_counter() if self._prof is not None else 0.0
                 dets = det.collect()
                 if self._prof is not None:
@@ -509,11 +516,7 @@ class ExtractEngine:
                 late = host_gray or paced                           # paced source: the batch's results leave before the stage blocks on the next one
                 if not late:
                     fill()                                      # keep the detectors busy while the host works on the batch
-                n_skip = 0
-                if self.gmc is not None and getattr(self.gmc, "wants_frames", False):
-                    if prev is not None:
-                        raise NotImplementedError("gmc_method ecc registers every frame against the first frame of the clip: not available to a frame-sharded run")
-                elif self.gmc is not None:                      # the batch queues on the GMC stream now, results in order
+                if self.gmc is not None and not getattr(self.gmc, "wants_frames", False):   # the batch queues on the GMC stream now, results in order
                     restart = prev is not None                  # a shard rank's batch: it does not continue the previous one
                     if restart and prev is not False:           # the frame that precedes the batch in the clip, from HBM
                         self.gmc.submit_frame_dev(int(prev), self.frame_hw[0], self.frame_hw[1], restart=True)
@@ -577,7 +580,9 @@ class ExtractEngine:
         in_flight = (n_batches + 1) * self.B + n_frames + len(self.stabs) + 1
         assert in_flight <= 14 * len(self.dets) * self.B, "engine queues outlive the detector's gray ring"
         assert self.gmc is None or (n_batches + 2) * self.B <= 63, "engine queues outrun the GMC's 64-deep result ring"
-        assert self.gmc is None or not getattr(self.gmc, "wants_frames", False) or (len(self.dets) + n_batches + 1) * self.B <= 31, \
+        # ECC frames are queued when a batch goes to its detector: one batch in flight per detector stream, the batches of the stage
+        # queue, the one the detector stage holds and the one the tracker stage holds, plus a shard rank's template frame
+        assert self.gmc is None or not getattr(self.gmc, "wants_frames", False) or (len(self.dets) + n_batches + 2) * self.B + 1 <= 31, \
             "engine queues outrun the ECC GMC's 32-deep frame ring"
         q_det = queue.Queue(maxsize=n_batches)                  # detected batches
         q_trk = queue.Queue(maxsize=n_frames)                   # tracked frames

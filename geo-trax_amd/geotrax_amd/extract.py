@@ -193,9 +193,9 @@ def track_with_model_sharded(model: YOLO, config: dict, logger: logging.Logger) 
         raise NotImplementedError("the frame-sharded run carries boxes and warps between ranks, not appearance vectors: "
                                   "`with_reid: true` needs the single-process run (one GPU per video)")
     with_gmc = model._gmc_method is not None
-    if model._gmc_method in ('orb', 'sift', 'ecc'):
-        raise NotImplementedError(f"gmc_method '{model._gmc_method}': the frame-sharded run primes every rank's GMC with the frame before its batch, which only 'sparseOptFlow' takes "
-                                  "('ecc' registers every frame against the first frame of the clip); run unsharded")
+    # sparseOptFlow / orb / sift compare a frame with the one before it: a run is primed with the clip's frame before it.
+    # ecc registers every frame against the clip's FIRST frame: a rank hands its GMC that frame once, ahead of its first run.
+    ecc = model._gmc_method == 'ecc'
     max_det = det_kw['max_det']
     state = {}
 
@@ -207,7 +207,8 @@ def track_with_model_sharded(model: YOLO, config: dict, logger: logging.Logger) 
         n_total = reader.frame_count if last is None else min(reader.frame_count, last + 1)
         assert n_total == state['n_frames']
         engine = ExtractEngine(model.tensors, reader.frame_hw, det_kw, None, stab_kw, device=local, batch=int(eng_cfg.get('batch', 2)),
-                               det_streams=int(eng_cfg.get('det_streams', 2)), stab_streams=int(eng_cfg.get('stab_streams', 4)), gmc=with_gmc,
+                               det_streams=int(eng_cfg.get('det_streams', 2)), stab_streams=int(eng_cfg.get('stab_streams', 4)),
+                               gmc=model._gmc_method or False, gmc_kw=eng_cfg.get('gmc'),
                                feeder_stream=os.environ.get("GTX_FEEDER", "1") != "0" and eng_cfg.get('read_ahead', True) is not False)
         state['engine'] = engine
         seekable = hasattr(reader, 'seek')
@@ -252,14 +253,22 @@ def track_with_model_sharded(model: YOLO, config: dict, logger: logging.Logger) 
             pctx.dev_upload(p, np.ascontiguousarray(frame.bgr() if hasattr(frame, "bgr") else frame, np.uint8))
             return p
 
+        def prime_frame(i, start):
+            """The clip frame run i of this rank is primed with, or None (the run opens the clip / ecc after the rank's first run)."""
+            if not with_gmc or start <= first:
+                return None
+            if ecc:
+                return first if i == 0 else None
+            return start - 1
+
         def batches():
-            for start, stop in runs:
+            for i, (start, stop) in enumerate(runs):
                 prev_ptr = None
                 if do_stab and not state.get('have_ref'):
                     engine.set_reference(frame_at(first))    # every rank registers against the clip's reference frame
                     state['have_ref'] = True
-                if with_gmc and start > first:
-                    prev_ptr = prime_ptr(frame_at(start - 1))
+                if prime_frame(i, start) is not None:
+                    prev_ptr = prime_ptr(frame_at(prime_frame(i, start)))
                 group, opened = [], False
                 for f in range(start, stop):
                     group.append(frame_at(f))
@@ -276,7 +285,7 @@ def track_with_model_sharded(model: YOLO, config: dict, logger: logging.Logger) 
             path, kind, offsets = reader.raw_layout()
             B, n_dets = engine.B, len(engine.dets)
             mine = [f for start, stop in runs for f in range(start, stop)]
-            primes = [start - 1 for start, stop in runs if with_gmc and start > first]
+            primes = [prime_frame(i, start) for i, (start, stop) in enumerate(runs) if prime_frame(i, start) is not None]
             fd = FrameFeeder(reader.frame_hw, kind=kind, batch=B, ring=max(int(eng_cfg.get('read_ahead_batches', 3)), 1) + n_dets + 1, device=local,
                              ctx=engine.feeder_ctx)
             state['feeders'] = [fd]
@@ -288,12 +297,12 @@ def track_with_model_sharded(model: YOLO, config: dict, logger: logging.Logger) 
                 state['feeders'].append(pf)
                 pf.open_file(path, offsets[primes], n_threads=1)
                 prime_it = pf.batches(n_prime)              # a slot is written again n_prime runs later, as with the ring above
-            for start, stop in runs:
+            for i, (start, stop) in enumerate(runs):
                 prev_ptr = None
                 if do_stab and not state.get('have_ref'):
                     engine.set_reference(frame_at(first))
                     state['have_ref'] = True
-                if with_gmc and start > first:
+                if prime_frame(i, start) is not None:
                     pb = next(prime_it)
                     pb.wait_on(None)                        # long since resident: it was requested when the feeder opened
                     prev_ptr = pb.ptr
@@ -415,7 +424,8 @@ def track_with_model(model: YOLO, config: dict, logger: logging.Logger) -> tuple
         tracker = model._make_tracker(ul.get('tracker', {'tracker_type': 'botsort'}))
         engine = ExtractEngine(model.tensors, reader.frame_hw, det_kw, tracker, stab_kw, batch=int(eng_cfg.get('batch', 2)),
                                det_streams=int(eng_cfg.get('det_streams', 2)), stab_streams=int(eng_cfg.get('stab_streams', 4)),
-                               gmc=model._gmc_method or False,          # the method's name: sparseOptFlow (GPU LK), orb / sift (gmc.FeatureGMC)
+                               gmc=model._gmc_method or False,          # the method's name: sparseOptFlow (GPU LK), orb / sift (gmc.FeatureGMC), ecc (gmc.EccGMC)
+                               gmc_kw=eng_cfg.get('gmc'),
                                feeder_stream=os.environ.get("GTX_FEEDER", "1") != "0" and eng_cfg.get('read_ahead', True) is not False)
         model._det = engine.dets[0]                        # introspection (names, gray) keeps working on the model object
         t_engine = time.time()

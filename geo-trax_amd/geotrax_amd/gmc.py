@@ -6,6 +6,7 @@ as BOTSORT.update calls it once per frame inside model.track(..., persist=True)
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import numpy as np
@@ -108,14 +109,17 @@ class FeatureGMC:
     descriptors of the half-resolution gray image, brute-force 2-NN matching against the previous frame's with Lowe's ratio 0.9,
     the two spatial filters of apply_features, then the RANSAC partial-affine fit. Built from what the path already has:
 
-    * orb: the stabilizer's detector / descriptor / Hamming matcher kernels (csrc/stabilizer.hip: FAST 20 on an 8-level pyramid,
-      Harris ranking, 256-bit rotated BRIEF; 1000 keypoints per frame), the previous frame set as its reference each step;
-    * sift: csrc/sift.hip's SIFT (plain, not RootSIFT) + the L2 2-NN kernel (csrc/match_l2.hip);
-    * the fit: gtx_op_estimate_affine_partial (the sparseOptFlow fit's procedure on the host).
+    * orb: gtx_fgmc_* (csrc/gmc_feat.hip) -- the stabilizer's detector / descriptor / Hamming matcher kernels (csrc/stabilizer.hip:
+      FAST 20 on an 8-level pyramid, Harris ranking, 256-bit rotated BRIEF; 1000 keypoints per frame), the filters and the RANSAC
+      hypotheses as one chain on the object's stream per submitted frame. submit_gray_dev / submit_gray / submit_frame_dev only
+      enqueue (frames may be submitted ahead, as with GMC); collect() waits for the oldest frame and refits on the host;
+    * sift: csrc/sift.hip's SIFT (plain, not RootSIFT) + the L2 2-NN kernel (csrc/match_l2.hip), the filters in numpy and the fit
+      by gtx_op_estimate_affine_partial. SYNCHRONOUS: sift.hip's detect reads its candidate counters back on the host between
+      its stages, so a frame's warp is computed when it is collected; the submit calls only queue the image.
 
     Stated differences from the OpenCV calls upstream makes: the matcher's query is the CURRENT frame (stabilo's rule; upstream
     queries with the previous one), no detection-box mask, SIFT with OpenCV's default thresholds (upstream: contrast 0.02, edge 20).
-    Synchronous: a frame's warp is computed when it is collected. Interface of GMC above."""
+    Interface of GMC above."""
 
     def __init__(self, frame_hw: tuple[int, int], method: str = "orb", downscale: int = 2, seed: int = 0, ctx: _lib.Context | None = None,
                  max_features: int = 1000):
@@ -130,30 +134,31 @@ class FeatureGMC:
         self.max_features = int(max_features)
         self.stats = np.zeros(3, np.int32)              # keypoints of the previous frame, matches kept, inliers
         self.valid = False
-        self._pending = []                               # gray images submitted and not yet collected (device pointers or host arrays)
+        self.handle = None
+        self._pending = collections.deque()              # orb: host images in flight (kept alive); sift: (kind, image, restart) not yet collected
         self._prev = None
+        self._restart_next = False                       # sift: the next submitted frame opens a new sequence
         if method == "orb":
-            from .stabilizer import Stabilizer
-
-            self._st = Stabilizer(self.frame_hw, max_features=self.max_features, ref_multiplier=1.0, filter_ratio=0.9, mask_use=False,
-                                  downsample_ratio=0.5, seed=seed, ctx=self.ctx)
-            self._dev = None                             # device copies of (previous, current) gray for host-side submissions
+            h = C.c_void_p()
+            check(self.ctx.lib.gtx_fgmc_create(self.ctx.handle, self.frame_hw[0], self.frame_hw[1], self.max_features, int(seed), C.byref(h)))
+            self.handle = h
+            self._n_sub = self._n_col = 0                # frames submitted / collected (one writer each)
         else:
             from .registration import Sift
 
             self._sift = Sift((self.gh, self.gw), ctx=self.ctx)
 
     def close(self):
-        if getattr(self, "_st", None) is not None:
-            self._st.close()
-            self._st = None
+        if getattr(self, "handle", None):
+            self.ctx.lib.gtx_fgmc_destroy(self.handle)
+            self.handle = None
         if getattr(self, "_sift", None) is not None:
             self._sift.close()
             self._sift = None
-        if getattr(self, "_dev", None):
-            for d in self._dev:
-                self.ctx.dev_free(d)
-            self._dev = None
+            for kind, cur, _ in self._pending:
+                if kind == "own":
+                    self.ctx.dev_free(cur)
+            self._pending.clear()
 
     def __del__(self):
         try:
@@ -162,25 +167,69 @@ class FeatureGMC:
             pass
 
     def reset_params(self):
-        self._prev = None
+        """Forget the previous frame; frames submitted and not collected are dropped. The blocking variant, used between clips."""
+        if self.method == "orb":
+            A, valid = np.zeros(6, np.float64), C.c_int()
+            while self._n_col < self._n_sub:
+                check(self.ctx.lib.gtx_fgmc_collect(self.handle, ptr(A), C.byref(valid), None))
+                self._n_col += 1
+            self._pending.clear()
+            check(self.ctx.lib.gtx_fgmc_reset(self.handle))
+            return
+        self._prev, self._restart_next = None, False
+        for kind, cur, _ in self._pending:
+            if kind == "own":
+                self.ctx.dev_free(cur)
         self._pending.clear()
 
-    reset_sequence = reset_params
+    def reset_sequence(self) -> None:
+        """The next submitted frame opens a new sequence (identity warp), with frames still in flight."""
+        if self.method == "orb":
+            check(self.ctx.lib.gtx_fgmc_restart(self.handle))
+        else:
+            self._restart_next = True
 
-    # ---- submission: half-resolution gray images, resident in HBM (the detector's) or on the host
+    # ---- submission: half-resolution gray images, resident in HBM (the detector's) or on the host, or a BGR frame in HBM
     def submit_gray_dev(self, gray_dptr: int, gh: int, gw: int) -> None:
         if (gh, gw) != (self.gh, self.gw):
             raise ValueError(f"gray image is {gw}x{gh}, the GMC was made for {self.gw}x{self.gh}")
-        self._pending.append(("dev", int(gray_dptr)))
+        if self.method == "orb":
+            check(self.ctx.lib.gtx_fgmc_submit_gray_dev(self.handle, C.c_void_p(int(gray_dptr)), gh, gw))
+            self._pending.append(None)
+            self._n_sub += 1
+        else:
+            self._pending.append(("dev", int(gray_dptr), self._take_restart()))
 
     def submit_gray(self, gray: np.ndarray) -> None:
         g = np.ascontiguousarray(gray, np.uint8)
         if g.shape != (self.gh, self.gw):
             raise ValueError(f"gray image is {g.shape[1]}x{g.shape[0]}, the GMC was made for {self.gw}x{self.gh}")
-        self._pending.append(("host", g))
+        if self.method == "orb":
+            check(self.ctx.lib.gtx_fgmc_submit_gray(self.handle, ptr(g), self.gh, self.gw))
+            self._pending.append(g)                      # the upload is queued: the image stays alive until its frame is collected
+            self._n_sub += 1
+        else:
+            self._pending.append(("host", g, self._take_restart()))
 
     def submit_frame_dev(self, frame_dptr: int, h: int, w: int, restart: bool = False) -> None:
-        raise NotImplementedError("gmc_method orb / sift: a frame-sharded run primes its GMC with a BGR frame in HBM, which only 'sparseOptFlow' takes")
+        """A BGR frame in HBM (gray + 2x2 mean on the device, the kernel gtx_gmc_submit_frame_dev uses); restart=True opens a new
+        sequence with it (identity warp, the next frame is compared with it): how a shard rank primes its GMC."""
+        if (int(h), int(w)) != self.frame_hw:
+            raise ValueError(f"frame is {w}x{h}, the GMC was made for {self.frame_hw[1]}x{self.frame_hw[0]}")
+        if self.method == "orb":
+            check(self.ctx.lib.gtx_fgmc_submit_frame_dev(self.handle, C.c_void_p(int(frame_dptr)), int(h), int(w), int(restart)))
+            self._pending.append(None)
+            self._n_sub += 1
+            return
+        g = self.ctx.dev_alloc(self.gh * self.gw)        # the frame's buffer may be recycled before the frame is collected: an image of its own
+        check(self.ctx.lib.gtx_gray_half_dev(self.ctx.handle, C.c_void_p(int(frame_dptr)), int(h), int(w), C.c_void_p(g)))
+        if restart:
+            self._restart_next = True
+        self._pending.append(("own", g, self._take_restart()))
+
+    def _take_restart(self) -> bool:
+        r, self._restart_next = self._restart_next, False
+        return r
 
     def apply(self, raw_frame: np.ndarray, detections=None) -> np.ndarray:
         """2x3 float64 warp previous -> current frame (identity for the first frame). raw_frame: BGR [h, w, 3] uint8."""
@@ -191,33 +240,14 @@ class FeatureGMC:
         return self.collect()
 
     # ---- one step
-    def _pairs_orb(self, kind, cur):
-        n = self.gh * self.gw
-        if kind == "host":                               # the stabilizer's gray entry points take device images
-            if self._dev is None:
-                self._dev = [self.ctx.dev_alloc(n), self.ctx.dev_alloc(n)]
-            self._dev.reverse()                          # [previous, current]
-            self.ctx.dev_upload(self._dev[1], cur)
-            cur_ptr = self._dev[1]
-        else:
-            cur_ptr = cur
-        prev_ptr, self._prev = self._prev, cur_ptr
-        if prev_ptr is None:
-            self._st.set_ref_gray_dev(cur_ptr, self.gh, self.gw)     # the sequence's first frame: its features wait as the reference
-            return None
-        self._st.stabilize_gray_dev(cur_ptr, self.gh, self.gw)      # features of this frame + matches against the previous frame's
-        qi, ti, _ = self._st.matches()
-        ref, cur_k = self._st.keypoints("ref")["xy"], self._st.keypoints("cur")["xy"]
-        self._st.promote_cur()                                      # ... which now become the reference of the next frame (no second extraction)
-        self.stats[0] = len(ref)
-        return ref[ti], cur_k[qi]                        # previous-frame points, current-frame points (full-resolution pixels)
-
     def _pairs_sift(self, kind, cur):
         from .ops import match_2nn
 
-        if kind == "dev":
+        if kind in ("dev", "own"):
             g = np.zeros((self.gh, self.gw), np.uint8)
-            self.ctx.dev_download(g, cur)
+            self.ctx.dev_download(g, cur)                # waits for the context's stream: the gray pass queued at submit is behind it
+            if kind == "own":
+                self.ctx.dev_free(cur)
         else:
             g = cur
         k = self._sift.detect_and_compute(np.repeat(g[:, :, None], 3, 2), max_features=self.max_features, root=False)
@@ -231,13 +261,22 @@ class FeatureGMC:
         return prev_f[0][i1[good]], cur_f[0][good]
 
     def collect(self) -> np.ndarray:
+        if self.method == "orb":
+            A, valid = np.zeros(6, np.float64), C.c_int()
+            check(self.ctx.lib.gtx_fgmc_collect(self.handle, ptr(A), C.byref(valid), ptr(self.stats)))
+            self._n_col += 1
+            self._pending.popleft()
+            self.valid = bool(valid.value)
+            return A.reshape(2, 3)
         if not self._pending:
             raise RuntimeError("GMC.collect without a submitted frame")
-        kind, cur = self._pending.pop(0)
+        kind, cur, restart = self._pending.popleft()
+        if restart:
+            self._prev = None
         H = np.eye(2, 3)
         self.valid = False
         self.stats[:] = 0
-        pairs = self._pairs_orb(kind, cur) if self.method == "orb" else self._pairs_sift(kind, cur)
+        pairs = self._pairs_sift(kind, cur)
         if pairs is None or len(pairs[0]) == 0:
             return H
         prev_xy, cur_xy = pairs
@@ -249,6 +288,22 @@ class FeatureGMC:
                 H, self.valid = M, True
                 self.stats[2] = inl
         return H
+
+    # ---- parity hooks (orb; nothing may be in flight)
+    def kept_pairs(self):
+        """(previous-frame points, current-frame points) the filters kept for the frame collected last, full-resolution pixels."""
+        n, out = C.c_int(), np.zeros((1024, 4), np.float32)
+        check(self.ctx.lib.gtx_fgmc_pairs(self.handle, 1024, C.byref(n), ptr(out)))
+        return out[:n.value, :2].copy(), out[:n.value, 2:].copy()
+
+    def raw_matches(self):
+        """The matcher's output for the frame submitted last: dict(best_idx, best_d, second_d [n_q], cur_xy [n_q, 2], prev_xy [n_t, 2])."""
+        nq, nt = C.c_int(), C.c_int()
+        bi, b1, b2 = (np.zeros(1024, np.int32) for _ in range(3))
+        q, t = np.zeros((1024, 2), np.float32), np.zeros((1024, 2), np.float32)
+        check(self.ctx.lib.gtx_fgmc_matches(self.handle, 1024, C.byref(nq), C.byref(nt), ptr(bi), ptr(b1), ptr(b2), ptr(q), ptr(t)))
+        return dict(best_idx=bi[:nq.value].copy(), best_d=b1[:nq.value].copy(), second_d=b2[:nq.value].copy(), cur_xy=q[:nq.value].copy(),
+                    prev_xy=t[:nt.value].copy())
 
 
 class EccGMC:
@@ -308,10 +363,15 @@ class EccGMC:
 
     reset_sequence = reset_params
 
-    def submit_frame_dev(self, frame_dptr: int, h: int, w: int, restart: bool = False, producer: _lib.Context | None = None) -> None:
+    def submit_frame_dev(self, frame_dptr: int, h: int, w: int, restart: bool = False, producer: _lib.Context | None = None) -> int:
+        """-> the number of warps the call queued. restart=True marks the frame a shard rank primes the other methods with (the one
+        before its run): this method registers every frame against the clip's FIRST frame, so it ignores that frame -- nothing is
+        queued and there is no warp to collect. What a rank needs instead is the clip's first frame as its template: it submits
+        that one like any other frame, once, before its first run, and discards its identity warp."""
         if restart:
-            raise NotImplementedError("gmc_method ecc registers against the first frame of the sequence: a frame-sharded run cannot prime it with another frame")
+            return 0
         check(self.ctx.lib.gtx_ecc_submit_dev(self.handle, producer.handle if producer is not None else None, C.c_void_p(int(frame_dptr)), int(h), int(w)))
+        return 1
 
     def submit_gray_dev(self, gray_dptr: int, gh: int, gw: int) -> None:
         raise NotImplementedError("gmc_method ecc blurs the full-resolution gray image before reducing it: it takes BGR frames (submit_frame_dev / apply)")

@@ -49,7 +49,8 @@ extern "C" {
  * 9: gtx_det_config.arch appended: 1 = RT-DETR (the reference swaps YOLO for RTDETR on the model's yaml, extract.py:222-225);
  *    gtx_tracker_config.alpha_fixed_emb appended, with_reid also read by types 3 (deepocsort) and 5 (tracktrack);
  *    gtx_op_estimate_affine_partial added (GMC methods orb / sift).
- * 10: gtx_ecc_* added (GMC method ecc). */
+ * 10: gtx_ecc_* added (GMC method ecc); gtx_fgmc_* (GMC method orb, stream-ordered) and gtx_gray_half_dev added: new entry
+ *     points only, no struct or existing signature changed, so the number stays. */
 #define GTX_ABI_VERSION 10
 
 typedef enum gtx_status {
@@ -559,6 +560,33 @@ int gtx_gmc_collect(gtx_gmc* g, double A[6], int* valid, int stats[3]);
 /* Parity hook: which 0 = corners of the last frame, 1 = corners of the frame before, 2 = where LK put
  * those in the last frame (+ status). xy in half-resolution pixels. */
 int gtx_gmc_points(gtx_gmc* g, int which, int cap, int* n, float* xy, int* status);
+
+/* ------------------------------------------------------------------ global motion compensation, method 'orb'
+ * `gmc_method: orb` (geotrax/cfg/default.yaml:374,419,467): ultralytics' GMC.apply_features on ORB keypoints of the half-resolution
+ * gray image -- the stabilizer's FAST / Harris / steered-BRIEF kernels (max_features <= 1024 per frame), Hamming 2-NN of the current
+ * frame's descriptors (query) against the previous frame's, Lowe ratio 0.9, apply_features' two spatial filters, then the
+ * partial-affine RANSAC of gtx_op_estimate_affine_partial -- as ONE chain on the context's stream per submitted frame, like
+ * gtx_gmc_*: up to 64 frames may be submitted ahead (the image is copied at submit), _collect waits for the oldest, refits on the
+ * host and returns the warps in submission order. A, valid as gtx_gmc_*; stats = {keypoints of the previous frame, pairs kept,
+ * inliers}. _reset / _restart / _submit_frame_dev(restart) follow gtx_gmc_*. _submit_gray takes the gray image from host memory. */
+typedef struct gtx_fgmc gtx_fgmc;
+int gtx_fgmc_create(gtx_ctx* ctx, int frame_h, int frame_w, int max_features, int seed, gtx_fgmc** out);
+void gtx_fgmc_destroy(gtx_fgmc* g);
+int gtx_fgmc_reset(gtx_fgmc* g);
+int gtx_fgmc_restart(gtx_fgmc* g);
+int gtx_fgmc_submit_gray_dev(gtx_fgmc* g, const void* gray_dptr, int gray_h, int gray_w);
+int gtx_fgmc_submit_gray(gtx_fgmc* g, const uint8_t* gray, int gray_h, int gray_w);
+int gtx_fgmc_submit_frame_dev(gtx_fgmc* g, const void* frame_bgr_dptr, int h, int w, int restart);
+int gtx_fgmc_collect(gtx_fgmc* g, double A[6], int* valid, int stats[3]);
+/* Parity hooks (nothing may be in flight). _pairs: the pairs the filters kept for the frame collected last, rows (prev.x, prev.y,
+ * cur.x, cur.y) in full-resolution pixels, in match order. _matches: what the filters were given for the frame submitted last --
+ * per keypoint of that frame the index of the nearest keypoint of the frame before (-1: none) and the two smallest Hamming
+ * distances, plus both frames' keypoint positions; *n_q = *n_t = 0 when the frame opened a sequence. */
+int gtx_fgmc_pairs(gtx_fgmc* g, int cap, int* n, float* pairs4);
+int gtx_fgmc_matches(gtx_fgmc* g, int cap, int* n_q, int* n_t, int* best_idx, int* best_d, int* second_d, float* q_xy, float* t_xy);
+/* The gray + 2x2-mean pass of gtx_gmc_submit_frame_dev on its own: BGR u8 [h][w][3] in HBM -> u8 [h / 2][w / 2] in HBM (the bytes
+ * the detector's gray image holds), enqueued on the context's stream. */
+int gtx_gray_half_dev(gtx_ctx* ctx, const void* frame_bgr_dptr, int h, int w, void* gray_dptr);
 
 /* ------------------------------------------------------------------ camera-motion compensation, method 'ecc'
  * `gmc_method: ecc` (geotrax/cfg/default.yaml:374,419,467): ultralytics' GMC.apply_ecc, i.e. cv2.findTransformECC(first frame,
