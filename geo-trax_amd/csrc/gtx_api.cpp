@@ -406,6 +406,54 @@ int gtx_op_upsample2x(gtx_ctx* ctx, int dtype, int n, int h, int w, int c, const
   });
 }
 
+int gtx_op_psa_attention(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int heads, const void* qkv, int in_cstride, int in_coff,
+                         const float* pe_w, const float* pe_b, void* out, int out_cstride, int out_coff, int form, int iters, float* ms_per_launch,
+                         int* saturated) {
+  return guarded([&] {
+    need(ctx, "ctx"); need(qkv, "qkv"); need(pe_w, "pe_w"); need(pe_b, "pe_b"); need(out, "out");
+    if (n < 1 || n_alloc < n || h < 1 || w < 1 || heads < 1 || iters < 0) gtx::fail(GTX_ERR_INVALID, "psa_attention: bad sizes");
+    if (in_coff < 0 || in_coff + heads * 128 > in_cstride || out_coff < 0 || out_coff + heads * 64 > out_cstride)
+      gtx::fail(GTX_ERR_INVALID, "psa_attention: the channel slices do not fit their strides");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t es = gtx::dtype_size(dtype), C = (size_t)heads * 64;
+    const size_t xb = (size_t)n_alloc * h * w * in_cstride * es, yb = (size_t)n * h * w * out_cstride * es;
+    gtx::DevBuf dx(xb), dy(yb), dw(9 * C * 4), db(C * 4), ds(4);
+    std::vector<uint8_t> tx, ty;
+    if (dtype == GTX_F32S) {                          // plain fp32 host arrays <-> pair format on the device
+      tx.resize(xb); ty.resize(yb);
+      gtx::f32_to_pairs(static_cast<const float*>(qkv), tx.data(), xb / 4);
+      gtx::f32_to_pairs(static_cast<const float*>(out), ty.data(), yb / 4);
+    }
+    GTX_HIP(hipMemcpy(dx.p, dtype == GTX_F32S ? tx.data() : qkv, xb, hipMemcpyHostToDevice));
+    GTX_HIP(hipMemcpy(dy.p, dtype == GTX_F32S ? ty.data() : out, yb, hipMemcpyHostToDevice));
+    GTX_HIP(hipMemcpy(dw.p, pe_w, 9 * C * 4, hipMemcpyHostToDevice));
+    GTX_HIP(hipMemcpy(db.p, pe_b, C * 4, hipMemcpyHostToDevice));
+    GTX_HIP(hipMemset(ds.p, 0, 4));
+    const gtx::RtMap in{dx.p, h, w, in_cstride, in_coff, heads * 128}, o{dy.p, h, w, out_cstride, out_coff, heads * 64};
+    auto once = [&] { gtx::launch_psa_attention(dtype, in, o, n, heads, dw.as<float>(), db.as<float>(), ds.as<int>(), ctx->stream, form); };
+    once();
+    if (iters > 0 && ms_per_launch) {
+      hipEvent_t e0, e1;
+      GTX_HIP(hipEventCreate(&e0));
+      GTX_HIP(hipEventCreate(&e1));
+      for (int i = 0; i < 3; ++i) once();
+      GTX_HIP(hipEventRecord(e0, ctx->stream));
+      for (int i = 0; i < iters; ++i) once();
+      GTX_HIP(hipEventRecord(e1, ctx->stream));
+      GTX_HIP(hipStreamSynchronize(ctx->stream));
+      float ms = 0.f;
+      GTX_HIP(hipEventElapsedTime(&ms, e0, e1));
+      (void)hipEventDestroy(e0);
+      (void)hipEventDestroy(e1);
+      *ms_per_launch = ms / iters;
+    }
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    GTX_HIP(hipMemcpy(dtype == GTX_F32S ? ty.data() : out, dy.p, yb, hipMemcpyDeviceToHost));
+    if (dtype == GTX_F32S) gtx::pairs_to_f32(ty.data(), static_cast<float*>(out), yb / 4);
+    if (saturated) GTX_HIP(hipMemcpy(saturated, ds.p, 4, hipMemcpyDeviceToHost));
+  });
+}
+
 struct gtx_gmc {
   gtx_ctx* ctx;
   std::unique_ptr<gtx::Gmc> impl;

@@ -1,14 +1,15 @@
-// Embedder (reid.hpp): YOLOv8-cls backbone over a batch of detection crops, pooled into one vector per crop, and its C ABI.
+// Embedder (reid.hpp): YOLOv8-cls or YOLO11-cls backbone over a batch of detection crops, pooled into one vector per crop, and its C ABI.
 //
 // What upstream does per frame (ultralytics >= 8.4.80, trackers/bot_sort.py ReID.__call__), and where it is done here:
 //   crops = [save_one_box(det, img, save=False) for det in xywh2xyxy(dets[:, :4])]   -> reid_crop_box (host)
 //   ClassificationPredictor.preprocess: classify_transforms(imgsz) on each crop         -> reid_resample_coeffs (host) + reid_crop_kernel
 //   model(crops, embed=[len(model) - 2]): adaptive_avg_pool2d(model.8 output)           -> YoloTrunk's backbone rows + reid_pool_kernel
+//     (yolo11-cls: model.9, the C2PSA output; its attention runs psa_attn_small_kernel on the crops' 2 x 2 to 8 x 8 maps)
 // Choices restated from memory of the pinned upstream rather than pinned by a test against it (the resample is pinned against PIL):
 //   - the box chain: Boxes.xywh in float32, then float64 (BOTSORT.init_track concatenates the boxes with np.arange), save_one_box's
 //     gain 1.02 / pad 10 / .long() truncation and clip to the frame;
 //   - the channel order the network sees (kNetChannelsBgr);
-//   - the embedded layer: model.8, the last backbone layer of yolov8-cls (len(model) - 2 for a .pt checkpoint).
+//   - the embedded layer: model.8, the last backbone layer of yolov8-cls (len(model) - 2 for a .pt checkpoint); model.9 of yolo11-cls.
 #include "reid.hpp"
 #include "api_guard.hpp"
 #include "split_format.hpp"
@@ -94,7 +95,7 @@ void reid_crop_box(const float b[4], int h, int w, int out[4]) {
 
 Embedder::Embedder(gtx_ctx* ctx, int imgsz, int max_crops, bool fp32_split)
     : NetRuntime(ctx, fp32_split ? DT_F32S : DT_F32, 4, max_crops), S_(imgsz), trunk_(*this, ops_, DT_F32) {
-  GTX_CHECK(imgsz >= 32 && imgsz <= 256 && imgsz % 32 == 0, "reid imgsz must be a multiple of 32 in [32, 256] (got %d)", imgsz);
+  GTX_CHECK(imgsz >= 32 && imgsz <= 320 && imgsz % 32 == 0, "reid imgsz must be a multiple of 32 in [32, 320] (got %d)", imgsz);
   GTX_CHECK(max_crops >= 1, "max_crops must be positive");
   GTX_HIP(hipSetDevice(ctx->device));
   GTX_HIP(hipEventCreateWithFlags(&done_, wait_event_flags(false)));
@@ -116,12 +117,13 @@ void Embedder::conv_config_rule(const std::string& name, ConvConfig& cfg) const 
   if (cfg.variant == 3 || cfg.variant == 4) { cfg.variant = 2; cfg.th = 8; }
 }
 
-// model.0-8 through the trunk's walk (no fusion: fuse() is never called, so the stem gets no front-packed weights)
+// model.0-8 (yolov8-cls) or model.0-9 (yolo11-cls) through the trunk's walk (no fusion: fuse() is never called, so the stem gets no
+// front-packed weights)
 void Embedder::build_graph() {
   img_ = new_view(S_, S_, 1);                                  // [N][S][S] uchar4: 4 bytes per pixel
   img_.plain = true;
   alloc_sat_flag();
-  last_ = trunk_.build(img_, YoloTrunk::cls_backbone(), false).in[0];
+  last_ = trunk_.build(img_, trunk_.choose_cls_graph(), false).in[0];
   dim_ = last_.c;
 }
 

@@ -1,5 +1,5 @@
-// Separate ReID network: the YOLOv8-cls backbone (model.0 - model.8 of ultralytics' yolov8-cls.yaml) run over one crop per
-// detection, its last map average-pooled into one vector per crop. Stands in for ultralytics' trackers/bot_sort.py ReID
+// Separate ReID network: the YOLOv8-cls backbone (model.0 - model.8 of ultralytics' yolov8-cls.yaml) or the YOLO11-cls one (model.0 -
+// model.9 of yolo11-cls.yaml: C3k2 blocks, then C2PSA) run over one crop per detection, its last map average-pooled into one vector per crop. Stands in for ultralytics' trackers/bot_sort.py ReID
 // (`with_reid: true, model: <cls checkpoint>` of BoT-SORT, Deep OC-SORT and TrackTrack; geotrax/cfg/default.yaml:379, :421, :470):
 // save_one_box per detection -> ClassificationPredictor (classify_transforms(imgsz)) -> model(embed=[len(model) - 2]).
 // The graph is the YOLO trunk's (yolo_trunk.hpp: the backbone rows of its yolov8.yaml table) with the batch dimension equal to the
@@ -48,7 +48,7 @@ class Embedder : public NetRuntime {
 
   int S_;
   std::vector<Op> ops_;
-  YoloTrunk trunk_;          // builds model.0-8 (the first rows of yolov8.yaml's table) into ops_ and launches them
+  YoloTrunk trunk_;          // builds the classifier's rows (YoloTrunk::choose_cls_graph) into ops_ and launches them
   View img_, last_;
   int dim_ = 0;
   // the pass in flight (kept for the exact re-run of a saturated pass)

@@ -10,17 +10,15 @@
 // and adds each chunk's rows that fall in their windows (integer sums: the chunking does not change a bit). A crop's short side
 // runs from ~10 px to the frame's height (downscale factor short / S: up to 2160 / 224 = 9.6, support +-9.6 source rows), so an
 // 8-row band reads from 2 source rows up to 8 * 9.6 + 2 * 9.6 = ~96 (~45 for a 1000-px short side); chunking keeps the LDS at a
-// fixed 32 KB (S <= 256) whatever the band reads. Neighbouring bands recompute the few source rows their windows share.
+// fixed 32 KB (S <= 256; 30 KB in chunks of 24 rows for S up to 320) whatever the band reads. Neighbouring bands recompute the few
+// source rows their windows share.
 #include "reid_kernels.hpp"
 
 namespace gtx {
 
 namespace {
 constexpr int kBand = 8;                // output rows per workgroup
-constexpr int kChunk = 32;              // intermediate rows per LDS chunk
-constexpr int kMaxS = 256;
 constexpr int kThreads = 256;
-constexpr int kPix = kBand * kMaxS / kThreads;   // output pixels per thread (8)
 constexpr int kPrec = 22;               // PIL PRECISION_BITS (32 - 8 - 2)
 
 __device__ __forceinline__ uint32_t clip8(int v) {
@@ -30,9 +28,12 @@ __device__ __forceinline__ uint32_t clip8(int v) {
 }
 }  // namespace
 
+// kMaxS: the largest S of this instance; kChunk: intermediate rows per LDS chunk
+template <int kMaxS, int kChunk>
 __global__ __launch_bounds__(kThreads) void reid_crop_kernel(const uint8_t* __restrict__ frames, int H, int W,
                                                              const ReidCrop* __restrict__ crops, const int* __restrict__ pool, int S,
                                                              uchar4* __restrict__ out) {
+  constexpr int kPix = kBand * kMaxS / kThreads;   // output pixels per thread (8 / 10)
   __shared__ uint32_t tile[kChunk * kMaxS];
   const ReidCrop c = crops[blockIdx.y];
   const int r0 = blockIdx.x * kBand;
@@ -95,9 +96,11 @@ __global__ __launch_bounds__(kThreads) void reid_crop_kernel(const uint8_t* __re
 }
 
 void launch_reid_crop(const uint8_t* frames, int h, int w, const ReidCrop* crops, const int* pool, int n, int S, void* out, hipStream_t s) {
-  GTX_CHECK(S >= 32 && S <= kMaxS, "reid crop: size %d outside [32, %d]", S, kMaxS);
+  GTX_CHECK(S >= 32 && S <= 320, "reid crop: size %d outside [32, %d]", S, 320);
   if (n == 0) return;
-  hipLaunchKernelGGL(reid_crop_kernel, dim3(cdiv(S, kBand), n), dim3(kThreads), 0, s, frames, h, w, crops, pool, S, (uchar4*)out);
+  const dim3 grid(cdiv(S, kBand), n), block(kThreads);
+  if (S <= 256) hipLaunchKernelGGL((reid_crop_kernel<256, 32>), grid, block, 0, s, frames, h, w, crops, pool, S, (uchar4*)out);
+  else hipLaunchKernelGGL((reid_crop_kernel<320, 24>), grid, block, 0, s, frames, h, w, crops, pool, S, (uchar4*)out);
   GTX_HIP(hipGetLastError());
 }
 

@@ -818,6 +818,107 @@ __global__ __launch_bounds__(256) void psa_attn_kernel(RtMap qkv, RtMap out, con
   flag_sat(sat, s);
 }
 
+// The same attention for many small maps (the ReID embedder's C2PSA: hundreds of crops of 2 x 2 to 8 x 8 positions, T = h w <= 64).
+// A (crop, head) pair's whole K and V fit one LDS stage, so the parent's prefetch registers, second barrier per stage and online
+// rescale have nothing to do: one workgroup per pair stages them once (rows T and up zero-filled: a zero probability times
+// whatever LDS held before would not be zero), then each wave takes a 16-query group -- groups past row T do not exist, so no
+// wave runs one --, computes every score tile, takes the row maximum in one sweep and runs P V with the probabilities in the
+// lanes that computed them. Key slots >= T are masked by index before the maximum and get probability zero; query rows >= T are
+// neither read nor stored. pe(v) reads the staged V: at these sizes most of its 3 x 3 window is padding.
+// LDS: 64 * (36 + 68) floats = 26 624 bytes, six workgroups per CU. (Two pairs per workgroup measured slower at every crop count
+// from 100 to 600: DESIGN section 7a.)
+constexpr int kPsaSmallT = 64;
+template <int FMT>
+__global__ __launch_bounds__(256) void psa_attn_small_kernel(RtMap qkv, RtMap out, int heads, const float* __restrict__ pe_w,
+                                                             const float* __restrict__ pe_b, int* sat) {
+  constexpr int KS = kPsaSmallT, PK = 36, PV = 68;
+  __shared__ float s_k[KS * PK];
+  __shared__ float s_v[KS * PV];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lc = lane & 15, kk = lane >> 4;
+  const int T = qkv.h * qkv.w, QG = (T + 15) >> 4, TP = QG * 16;      // query groups = key tiles; TP: T rounded up to whole tiles
+  const int n = blockIdx.x / heads, head = blockIdx.x - n * heads;
+  const size_t img = (size_t)n * T;
+  const int ch = qkv.coff + head * 128;
+  // ---- stage: 12 eight-channel groups per key row (4 of K, 8 of V)
+  for (int i = threadIdx.x; i < TP * 12; i += 256) {
+    const int g = i % 12, row = i / 12;
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (row < T) load8<FMT>(qkv.ptr, (img + row) * qkv.cstride + ch + 32 + g * 8, v);
+    float* d = g < 4 ? &s_k[row * PK + g * 8] : &s_v[row * PV + (g - 4) * 8];
+    *reinterpret_cast<float4*>(d) = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>(d + 4) = make_float4(v[4], v[5], v[6], v[7]);
+  }
+  __syncthreads();
+  const float scale = 0.17677669529663687f;      // key_dim^-0.5, key_dim = 32
+  bool s = false;
+  const float *sk = s_k, *sv = s_v;
+  if (wave < QG) {                                 // wave-uniform
+    const int qi = wave * 16 + lc;
+    float qf[8];                                   // B operand of the first product: Q[query lc][4 i + kk], scaled
+#pragma unroll
+    for (int i = 0; i < 8; ++i) qf[i] = qi < T ? load1<FMT>(qkv.ptr, (img + qi) * qkv.cstride + ch + 4 * i + kk) * scale : 0.f;
+    floatx4 sc[4];                                 // S^T[key 16 t + 4 kk + r][query lc]
+    float mx = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      sc[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+      if (16 * t < TP) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(sk[(16 * t + lc) * PK + 4 * i + kk], qf[i], sc[t], 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (16 * t + 4 * kk + r >= T) sc[t][r] = -INFINITY;      // key slots past the end, before the maximum
+          mx = fmaxf(mx, sc[t][r]);
+        }
+      }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));            // key 0 is never masked: finite for every query column
+    floatx4 o[4];                                  // O^T[dim 16 t + 4 kk + r][query lc]
+#pragma unroll
+    for (int t = 0; t < 4; ++t) o[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+    float l = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (16 * t < TP) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = 16 * t + 4 * kk + r;
+          const float p = key < T ? __expf(sc[t][r] - mx) : 0.f;
+          l += p;
+          const float* vr = &sv[key * PV];
+#pragma unroll
+          for (int d = 0; d < 4; ++d) o[d] = __builtin_amdgcn_mfma_f32_16x16x4f32(vr[16 * d + lc], p, o[d], 0, 0, 0);
+        }
+      }
+    }
+    l += __shfl_xor(l, 16);
+    l += __shfl_xor(l, 32);
+    if (qi >= T) return;
+    const float inv = 1.f / l;
+    const int y = qi / qkv.w, x = qi - y * qkv.w, C = out.c;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int d = 16 * t + 4 * kk;               // the lane's four channels of this tile
+      const float4 b4 = *reinterpret_cast<const float4*>(pe_b + head * 64 + d);
+      float pe[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+          const int yy = y + ky - 1, xx = x + kx - 1;
+          if (yy < 0 || yy >= qkv.h || xx < 0 || xx >= qkv.w) continue;
+          const float4 v4 = *reinterpret_cast<const float4*>(&sv[(yy * qkv.w + xx) * PV + d]);
+          const float4 w4 = *reinterpret_cast<const float4*>(pe_w + (size_t)(ky * 3 + kx) * C + head * 64 + d);
+          pe[0] = fmaf(v4.x, w4.x, pe[0]); pe[1] = fmaf(v4.y, w4.y, pe[1]); pe[2] = fmaf(v4.z, w4.z, pe[2]); pe[3] = fmaf(v4.w, w4.w, pe[3]);
+        }
+      const float r4[4] = {o[t][0] * inv + pe[0], o[t][1] * inv + pe[1], o[t][2] * inv + pe[2], o[t][3] * inv + pe[3]};
+      store4<FMT>(out.ptr, (img + qi) * out.cstride + out.coff + head * 64 + d, r4, s);
+    }
+  }
+  flag_sat(sat, s);
+}
+
 // ============================================================================ query selection (top-k anchors per image)
 __device__ __forceinline__ unsigned sortable(float f) {
   const unsigned u = __float_as_uint(f);
@@ -1165,9 +1266,17 @@ void launch_rt_mha(const float* qkv, int ld, int n, int T, int C, int heads, flo
   GTX_HIP(hipGetLastError());
 }
 
-void launch_psa_attention(int fmt, const RtMap& qkv, const RtMap& out, int n, int heads, const float* pe_w, const float* pe_b, int* sat, hipStream_t s) {
+bool psa_attention_small(int h, int w) { return h * w <= kPsaSmallT; }
+
+void launch_psa_attention(int fmt, const RtMap& qkv, const RtMap& out, int n, int heads, const float* pe_w, const float* pe_b, int* sat, hipStream_t s,
+                          int form) {
   GTX_CHECK(heads > 0 && qkv.c == heads * 128 && out.c == heads * 64 && qkv.h == out.h && qkv.w == out.w, "psa_attention: %d heads on %d -> %d channels", heads, qkv.c, out.c);
   GTX_CHECK(qkv.cstride % 8 == 0 && qkv.coff % 8 == 0 && out.cstride % 8 == 0 && out.coff % 8 == 0, "psa_attention: channel strides / offsets must be multiples of 8");
+  GTX_CHECK(form >= 0 && form <= 2 && (form != 2 || psa_attention_small(qkv.h, qkv.w)), "psa_attention: form %d on a %d x %d map", form, qkv.w, qkv.h);
+  if (form == 2 || (form == 0 && psa_attention_small(qkv.h, qkv.w))) {
+    RT_FMT(fmt, hipLaunchKernelGGL(psa_attn_small_kernel<F>, dim3(n * heads), dim3(256), 0, s, qkv, out, heads, pe_w, pe_b, sat));
+    return;
+  }
   const dim3 grid(cdiv(qkv.h * qkv.w, 64), heads, n), block(256);
   RT_FMT(fmt, hipLaunchKernelGGL(psa_attn_kernel<F>, grid, block, 0, s, qkv, out, pe_w, pe_b, sat));
 }

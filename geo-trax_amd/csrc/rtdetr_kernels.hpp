@@ -55,7 +55,12 @@ void launch_rt_mha(const float* qkv, int ld, int n, int T, int C, int heads, flo
 // ultralytics' Attention block (YOLO11's C2PSA) on maps in the path's activation format: qkv [N][h][w] with heads x [q 32 | k 32 | v 64]
 // channels, out [N][h][w][heads * 64] = softmax(q^T k * 32^-0.5) v over the h w positions + pe(v), pe a depthwise 3x3
 // convolution without activation (pe_w [9][heads * 64] tap-major, pe_b [heads * 64]). Scores and softmax in fp32.
-void launch_psa_attention(int fmt, const RtMap& qkv, const RtMap& out, int n, int heads, const float* pe_w, const float* pe_b, int* sat, hipStream_t s);
+// Maps of at most 64 positions (the ReID embedder's crops) run psa_attn_small_kernel: one workgroup per (crop, head) pair, its K
+// and V staged once; larger ones psa_attn_kernel. form: 0 = that rule, 1 / 2 = the large- / small-map kernel whatever the size (the
+// operator-level hook's, for tests and timing; 2 needs h w <= 64).
+void launch_psa_attention(int fmt, const RtMap& qkv, const RtMap& out, int n, int heads, const float* pe_w, const float* pe_b, int* sat, hipStream_t s,
+                          int form = 0);
+bool psa_attention_small(int h, int w);   // the rule of form 0
 
 // query selection: per image, the nq anchors with the largest max-over-classes score, descending (ties: lower anchor index
 // first). scores: per level maps [N][h][w][cs] with the classes in channels [0, nc): plain fp32 (fmt DT_F32, both fp32-grade

@@ -3,7 +3,8 @@
 // decoder there; rows 0-8 are the YOLOv8-cls backbone of the ReID embedder), v8/yolov8-p2.yaml (kYolov8P2: one more stage at stride 4,
 // Detect = model.28) and 11/yolo11.yaml (kYolo11: C3k2 blocks, C2PSA = model.10, Detect = model.23). Channel widths, bottleneck counts
 // and c3k-or-not are read off the tensor shapes, so every scale (n/s/m/l/x) loads unchanged. A new family is one more table and one
-// more rule in choose_graph(); a new module is one more case in build().
+// more rule in choose_graph(); a new module is one more case in build(). The two classification graphs of the ReID embedder are
+// prefixes of these tables: yolov8-cls.yaml = kYolov8's rows 0-8, 11/yolo11-cls.yaml = kYolo11's rows 0-8 + C2PSA as model.9 (kYolo11Cls).
 #include "yolo_trunk.hpp"
 #include "rtdetr_kernels.hpp"
 #include "split_format.hpp"
@@ -41,10 +42,21 @@ constexpr R kYolo11[] = {
     {12, R::CONCAT, {-1, 6}, false}, {13, R::BLOCK, {-1}, kNeckShortcut}, {14, R::UPSAMPLE, {-1}, false}, {15, R::CONCAT, {-1, 4}, false},
     {16, R::BLOCK, {-1}, kNeckShortcut}, {17, R::CONV, {-1}, false},  {18, R::CONCAT, {-1, 13}, false}, {19, R::BLOCK, {-1}, kNeckShortcut},
     {20, R::CONV, {-1}, false},     {21, R::CONCAT, {-1, 10}, false}, {22, R::BLOCK, {-1}, kNeckShortcut}, {23, R::DETECT, {16, 19, 22}, false}};
+// yolo11-cls.yaml: model.0-8 are yolo11.yaml's, C2PSA follows them directly (no SPPF) and is the embedded layer; Classify = model.10
+constexpr R kYolo11Cls[] = {
+    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},
+    {4, R::BLOCK, {-1}, true},      {5, R::CONV, {-1}, false},        {6, R::BLOCK, {-1}, true},       {7, R::CONV, {-1}, false},
+    {8, R::BLOCK, {-1}, true},      {9, R::C2PSA, {-1}, false}};
 template <int N> constexpr TrunkGraph graph_of(const R (&rows)[N], bool dw_cls) { return TrunkGraph{rows, N, dw_cls}; }
 }  // namespace
 
 TrunkGraph YoloTrunk::cls_backbone() { return TrunkGraph{kYolov8, kClsBackboneRows, false}; }
+
+// The classifier's yaml by its tensor names: an attention block at model.9 and no Detect at model.23 is yolo11-cls.yaml
+TrunkGraph YoloTrunk::choose_cls_graph() const {
+  if (net_.has("model.9.m.0.attn.qkv.conv.weight") && !net_.has("model.23.cv2.0.0.conv.weight")) return graph_of(kYolo11Cls, false);
+  return cls_backbone();
+}
 
 // Which yaml the tensors were built from, told apart by their names like the reference's model yaml does
 TrunkGraph YoloTrunk::choose_graph() const {
@@ -197,7 +209,7 @@ View YoloTrunk::c2psa(const std::string& pfx, const View& x, const View* out_sli
       Op op;
       op.kind = Op::ATTN;
       op.name = m + ".attn";
-      op.family = "psa_attn_kernel";
+      op.family = psa_attention_small(x.h, x.w) ? "psa_attn_small_kernel" : "psa_attn_kernel";     // launch_psa_attention's rule
       op.in = qkv; op.out = att;
       op.heads = heads;
       op.dw_w = net_.upload(wt); op.dw_bias = net_.upload(bias);

@@ -1,5 +1,5 @@
 // The YOLO trunk: everything in front of the Detect layer of ultralytics' yolov8.yaml (model.0-21), yolov8-p2.yaml (model.0-27) and
-// yolo11.yaml (model.0-22), and the YOLOv8-cls backbone (model.0-8). Each graph is a constant table with one row per yaml layer
+// yolo11.yaml (model.0-22), and the YOLOv8-cls (model.0-8) and YOLO11-cls (model.0-9) backbones. Each graph is a constant table with one row per yaml layer
 // (yolo_trunk.cpp); one walk over a table emits its launches into the caller's op list. Every family that runs a trunk builds
 // through it: the YOLOv8 / P2 / YOLO11 detector (Detect on its outputs, detector.cpp), YOLOv8-RTDETR (an RTDETRDecoder on model.15 /
 // 18 / 21, rtdetr.cpp) and the ReID embedder (reid.cpp). It also owns the fused front (stem + model.1 + model.2.cv1 in one launch on
@@ -64,6 +64,8 @@ class YoloTrunk {
   // The graph the tensors were built from, by their names: yolo11.yaml, yolov8-p2.yaml, else yolov8.yaml
   TrunkGraph choose_graph() const;
   static TrunkGraph cls_backbone();   // model.0-8 of yolov8.yaml = yolov8-cls.yaml's backbone
+  // The classification graph the tensors were built from: yolo11-cls.yaml (model.0-8 of yolo11.yaml + C2PSA = model.9), else cls_backbone()
+  TrunkGraph choose_cls_graph() const;
   // Emits every row of g in front of its Detect on img ([N][H][W][4] RGB0 bytes). front: the stem also gets its weights packed for
   // fuse() (a net that never calls fuse() passes false).
   Levels build(const View& img, const TrunkGraph& g, bool front = true);

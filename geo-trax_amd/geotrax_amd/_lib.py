@@ -104,6 +104,8 @@ _SIGNATURES = {
     "gtx_op_conv_xcd_ranges": (C.c_int, [C.c_int, _P, _P, _P, _P]),
     "gtx_op_sppf_pool": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gtx_op_upsample2x": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
+    "gtx_op_psa_attention": (C.c_int, [_P] + [C.c_int] * 6 + [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "gtx_gmc_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "gtx_gmc_destroy": (None, [_P]),
     "gtx_gmc_reset": (C.c_int, [_P]),

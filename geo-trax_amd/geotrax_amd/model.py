@@ -28,7 +28,7 @@ import yaml
 from . import _lib
 from .detector import Detector
 from .tracker import TRACKER_TYPES, Tracker
-from .weights import is_yolov8_cls, load_weights
+from .weights import cls_family, load_weights
 
 logger = logging.getLogger(__name__)
 
@@ -168,16 +168,16 @@ class YOLO:
         if ttype in ("botsort", "deepocsort", "tracktrack"):  # the trackers that take a camera-motion warp per frame
             if params.get("with_reid"):
                 # `model: auto` (default.yaml:379, :421, :470): appearance vectors from the detector's own feature maps
-                # (Detector(obj_feats=True) -> Tracker.update(feats=)); `model: <file>.safetensors`: a separate YOLOv8-cls network over
+                # (Detector(obj_feats=True) -> Tracker.update(feats=)); `model: <file>.safetensors`: a separate YOLO11-cls or YOLOv8-cls network over
                 # the detection crops (reid.ReIDEncoder). Any other name (a .pt pickle, OSNet, ...) is refused before a file is opened.
                 m = str(params.get("model", "auto"))
                 if m != "auto":
                     if Path(m).suffix != ".safetensors":
-                        raise NotImplementedError(f"{ttype} with_reid: `model: auto` (detector-derived features) or a YOLOv8-cls checkpoint converted "
+                        raise NotImplementedError(f"{ttype} with_reid: `model: auto` (detector-derived features) or a YOLO11-cls / YOLOv8-cls checkpoint converted "
                                                   f"to .safetensors (tools/convert_weights.py) are implemented, not '{m}'")
                     reid_tensors = load_weights(Path(m))           # relative paths: against the working directory, like YOLO(model)
-                    if not is_yolov8_cls(reid_tensors):
-                        raise NotImplementedError(f"{ttype} with_reid: '{m}' is not a classification checkpoint; only the YOLOv8-cls family is implemented")
+                    if cls_family(reid_tensors) is None:
+                        raise NotImplementedError(f"{ttype} with_reid: '{m}' is not a classification checkpoint; only the YOLO11-cls and YOLOv8-cls families are implemented")
             gm = params.get("gmc_method", "none")
             if gm in ("none", None):
                 self._gmc_method = None
@@ -240,7 +240,8 @@ class YOLO:
         reid_tensors = getattr(self._tracker, "reid_tensors", None)
         self._obj_feats = with_reid and reid_tensors is None   # `with_reid: true, model: auto`: the detector keeps a vector per box
         if self._obj_feats and self.is_rtdetr:
-            raise NotImplementedError("with_reid: true, model: auto needs the YOLOv8 Detect layer's inputs; not implemented for RT-DETR")
+            raise NotImplementedError("with_reid: true, model: auto needs the YOLOv8 Detect layer's inputs; not implemented for RT-DETR "
+                                      "(a separate network works: `model: yolo11n-cls.safetensors`)")
         frame = np.ascontiguousarray(source, dtype=np.uint8)
         d = self._detector(frame.shape[:2], kwargs).detect(frame)
         res = Results(Boxes(d.xyxy, d.conf, d.cls, None), d.speed, frame.shape[:2], self.names)

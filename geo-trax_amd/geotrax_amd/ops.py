@@ -114,6 +114,28 @@ def upsample2x(x: np.ndarray, c: int, in_coff: int, out: np.ndarray, out_coff: i
     return out
 
 
+def psa_attention(qkv: np.ndarray, pe_w: np.ndarray, pe_b: np.ndarray, heads: int, *, n: int | None = None, in_coff: int = 0,
+                  out: np.ndarray | None = None, out_coff: int = 0, split: bool = False, form: int = 0, iters: int = 0, ctx=None):
+    """C2PSA's attention on maps: qkv [n_alloc, h, w, cs] with heads x [q 32 | k 32 | v 64] channels from in_coff; pe_w [64 heads, 1, 3, 3]
+    (the depthwise conv's own layout), pe_b [64 heads]. The first n maps run (default all). form: 0 the library's choice, 1 / 2 the
+    large- / small-map kernel. Returns (out [n, h, w, cs_out], saturated, ms per launch or None)."""
+    ctx = ctx or _lib.default_context()
+    qkv = np.ascontiguousarray(qkv)
+    na, h, w, cs = qkv.shape
+    n = na if n is None else n
+    c = heads * 64
+    if out is None:
+        out = np.zeros((n, h, w, c), qkv.dtype)
+    out = np.ascontiguousarray(out).copy()
+    assert out.shape[:3] == (n, h, w) and out.dtype == qkv.dtype and (not split or qkv.dtype == np.float32)
+    wt = np.ascontiguousarray(np.asarray(pe_w, np.float32).reshape(c, 9).T)     # tap-major
+    b = np.ascontiguousarray(pe_b, dtype=np.float32)
+    ms, sat = C.c_float(), C.c_int()
+    check(ctx.lib.gtx_op_psa_attention(ctx.handle, GTX_F32S if split else _dt(qkv), n, na, h, w, heads, ptr(qkv), cs, in_coff, ptr(wt), ptr(b),
+                                       ptr(out), out.shape[3], out_coff, form, iters, C.byref(ms), C.byref(sat)))
+    return out, bool(sat.value), (ms.value if iters > 0 else None)
+
+
 def preprocess(frame_bgr: np.ndarray, net_h: int, net_w: int, dtype=np.float32, want_gray: bool = True, ctx=None):
     """Letterbox + BGR->RGB + /255 into [net_h,net_w,4] (RGB0) and the half-res gray image."""
     ctx = ctx or _lib.default_context()

@@ -6,9 +6,10 @@ when the tracker yaml names a model; geotrax/cfg/default.yaml:379, :421, :470)::
     feats = self.model.predictor([save_one_box(det, img, save=False) for det in xywh2xyxy(torch.from_numpy(dets[:, :4]))])
 
 i.e. one crop per detection (gain 1.02, pad 10), ``classify_transforms(imgsz)`` (PIL bilinear to short side imgsz, center crop,
-/255), the classification model's backbone and the global average pool of its last backbone layer. The YOLOv8-cls family is
-implemented (weights.is_yolov8_cls); the network runs at fp32 grade whatever the detector's ``half`` says, as upstream's own
-predictor does.
+/255), the classification model's backbone and the global average pool of the layer in front of its Classify head. Two families are
+implemented: YOLO11-cls (weights.is_yolo11_cls: the vector is the pool of model.9, the C2PSA output) and YOLOv8-cls
+(weights.is_yolov8_cls: model.8). The network runs at fp32 grade whatever the detector's ``half`` says, as upstream's own predictor
+does.
 """
 from __future__ import annotations
 
@@ -24,13 +25,15 @@ from ._lib import check, ptr
 class ReIDEncoder:
     def __init__(self, tensors: dict[str, np.ndarray], ctx: _lib.Context | None = None, fp32_split: bool | None = None,
                  imgsz: int | None = None, max_crops: int = 300):
-        """tensors: a fused YOLOv8-cls checkpoint (weights.load_weights). fp32_split: split-f16x3 convolutions (default, the detector's
+        """tensors: a fused YOLO11-cls or YOLOv8-cls checkpoint (weights.load_weights). fp32_split: split-f16x3 convolutions (default, the detector's
         GTX_FP32_SPLIT rule) or exact fp32. imgsz: the classifier's input size (default: the file's ``cls.meta``, else 224).
         max_crops: crops per backbone launch the buffers hold (more run in chunks)."""
-        from .weights import cls_imgsz, is_yolov8_cls
+        from .weights import cls_family, cls_imgsz
 
-        if not is_yolov8_cls(tensors):
-            raise NotImplementedError("ReID model: the tensors are not a YOLOv8-cls checkpoint (only that family is implemented)")
+        self.family = cls_family(tensors)                     # raises for a classifier of another topology
+        if self.family is None:
+            raise NotImplementedError("ReID model: the tensors are not a YOLO11-cls or YOLOv8-cls checkpoint (only those families are implemented)")
+        head = {"yolo11-cls": "model.10.", "yolov8-cls": "model.9."}[self.family]   # Classify: never loaded
         if fp32_split is None:
             from .detector import FP32_SPLIT_DEFAULT
 
@@ -44,7 +47,7 @@ class ReIDEncoder:
         check(lib.gtx_embedder_create(self.ctx.handle, self.imgsz, self.max_crops, int(self.fp32_split), C.byref(h)))
         self.handle = h
         for name, arr in tensors.items():
-            if not name.startswith("model.") or name.startswith("model.9."):
+            if not name.startswith("model.") or name.startswith(head):
                 continue
             a = np.ascontiguousarray(arr, dtype=np.float32)
             shape = (C.c_int64 * a.ndim)(*a.shape)

@@ -147,6 +147,10 @@ YOLO11_YAML = [
     ((16, 19, 22), 1, "Detect", ("nc",)),                  # 23: the class branch is DWConv + Conv(1x1) twice
 ]
 YOLOV8_CLS_YAML = _V8_BACKBONE + [(-1, 1, "Classify", ("nc",))]
+YOLO11_CLS_YAML = YOLO11_YAML[:9] + [                      # model.0-8 of yolo11.yaml; no SPPF
+    (-1, 2, "C2PSA", (1024,)),                             # 9
+    (-1, 1, "Classify", ("nc",)),                          # 10
+]
 
 
 def _rows(table, *modules) -> tuple[int, ...]:
@@ -360,7 +364,7 @@ def has_yolo11_blocks(tensors: dict) -> bool:
 
 def check_yolo11(tensors: dict) -> None:
     """Raises NotImplementedError unless the names and shapes are those of a fused yolo11.yaml detect model. Other graphs built from
-    the same blocks (YOLO12's A2C2f, YOLO26's end-to-end Detect, yolo11-cls with C2PSA at model.9, -seg / -obb / -pose heads with a
+    the same blocks (YOLO12's A2C2f, YOLO26's end-to-end Detect, yolo11-cls with C2PSA at model.9 -- the ReID embedder's, is_yolo11_cls --, -seg / -obb / -pose heads with a
     cv4 or proto branch) are never built into the wrong network."""
     no = NotImplementedError(f"checkpoint with attention / depthwise-Detect blocks in another arrangement than yolo11.yaml's: of that "
                              f"family only {YOLO11_TOPOLOGY} is implemented")
@@ -732,6 +736,85 @@ def is_yolov8_cls(tensors: dict) -> bool:
     if extra:
         raise unsupported
     return True
+
+
+# --------------------------------------------------------------------------- YOLO11-cls (cfg/models/11/yolo11-cls.yaml)
+# The family the pinned ultralytics names as the trackers' embedder: model.0-8 of yolo11.yaml, C2PSA = model.9 (no SPPF), Classify =
+# model.10. ReID embeds layer len(model) - 2 = model.9: the vector is the global average pool of the C2PSA output (YOLOv8-cls pools
+# model.8). Restated from ultralytics' public source; not checked against the package (it is not installed).
+
+YOLO11_CLS_SCALES = {"n": (0.50, 0.25, 1024), "s": (0.50, 0.50, 1024), "m": (0.50, 1.00, 512),
+                     "l": (1.00, 1.00, 512), "x": (1.00, 1.50, 512)}   # yolo11-cls.yaml: depth, width, max_channels (yolo11.yaml's)
+
+YOLO11_CLS_TOPOLOGY = "yolo11-cls (yolo11{n,s,m,l,x}-cls: Conv/C3k2 backbone model.0-8, C2PSA = model.9, Classify at model.10)"
+
+
+def yolo11_cls_layer_specs(scale: str = "n", nc: int = 1000) -> list[tuple[str, tuple[int, ...], bool]]:
+    """(tensor name, shape, has_act) of a fused YOLO11-cls model: the backbone and C2PSA convs, then Classify's conv and linear layer."""
+    return _scaled_specs(YOLO11_CLS_YAML, YOLO11_CLS_SCALES, scale, nc, c3k_all=scale in "mlx")
+
+
+def synthetic_yolo11_cls(seed: int = 0, scale: str = "n", nc: int = 1000, gain: float = 1.7) -> dict[str, np.ndarray]:
+    """Seeded random fused YOLO11-cls weights, drawn like synthetic_yolov8_cls's (the draws in the order of yolo11_cls_layer_specs)."""
+    return _draw_yolov8(np.random.default_rng(seed), yolo11_cls_layer_specs(scale, nc), gain=gain)
+
+
+def is_yolo11_cls(tensors: dict) -> bool:
+    """True for a complete fused YOLO11-cls checkpoint. A file that is no classifier of this family (a detect file with its Detect
+    head, RT-DETR, a YOLOv8-cls file: no attention block at model.9) gives False; a near miss (C2PSA at model.9 with a width or a
+    block that yolo11-cls.yaml does not give, a yolo11 detect file cut to its first rows: SPPF at model.9, C2PSA at model.10)
+    raises NotImplementedError. Strict like check_yolo11(): every backbone and C2PSA shape is checked against what model.0's width,
+    the repeat counts and c3k-or-not imply, so such a file is never built into the wrong network."""
+    if "model.0.conv.weight" not in tensors or is_rtdetr(tensors):
+        return False
+    layer = lambda k: int(k.split(".")[1]) if k.startswith("model.") and k.split(".")[1].isdigit() else -1
+    if any(layer(k) > 10 for k in tensors):                # a neck or a Detect head: no classifier
+        return False
+    if not any(".attn." in k for k in tensors):            # no attention anywhere: YOLOv8-cls or something else, not ours to judge
+        return False
+    unsupported = NotImplementedError(f"ReID model: of the classifiers with attention blocks only {YOLO11_CLS_TOPOLOGY} is implemented "
+                                      f"(next to YOLOv8-cls); this file has another topology")
+    shape = lambda n: tuple(np.shape(tensors[n + ".weight"])) if n + ".weight" in tensors else None
+    c0 = int(np.shape(tensors["model.0.conv.weight"])[0])
+    if c0 % 16 or any(".attn." in k and layer(k) != 9 for k in tensors):
+        raise unsupported
+    width = 4 * c0 / 64                                    # model.0 is ch(64): the scale's width factor, max_channels aside
+    c8 = shape("model.8.cv2.conv")
+    if c8 is None:
+        raise unsupported
+    maxc = {0.25: 1024, 0.5: 1024, 1.0: 512, 1.5: 512}.get(width / 4)
+    if maxc is None:
+        raise unsupported
+    reps, c3k = {}, {}
+    for i in (2, 4, 6, 8):
+        n = 0
+        while f"model.{i}.m.{n}.cv1.conv.weight" in tensors:
+            n += 1
+        reps[i], c3k[i] = n, f"model.{i}.m.0.cv3.conv.weight" in tensors
+    n9 = 0
+    while f"model.9.m.{n9}.attn.qkv.conv.weight" in tensors:
+        n9 += 1
+    reps[9] = n9
+    if min(reps.values()) < 1 or len(set(reps.values())) != 1 or not (c3k[6] and c3k[8]) or c3k[2] != c3k[4] or c3k[2] != (width / 4 >= 1.0):
+        raise unsupported
+    table = [(f, n, m, (a[0], c3k[i]) + tuple(a[2:]) if m == "C3k2" else a) for i, (f, n, m, a) in enumerate(YOLO11_CLS_YAML[:10])]
+    want = _parse_model(table, 0, lambda c: _make_divisible(min(c, maxc) * width / 4), lambda i, n: reps[i] if n > 1 else n)
+    names = {n for n, _, _ in want}
+    for name, shp, _ in want:
+        if shape(name) != shp:
+            raise unsupported
+    extra = {k.rsplit(".", 1)[0] for k in tensors if 0 <= layer(k) <= 9 and k.endswith(".weight")} - names
+    if extra:
+        raise unsupported
+    return True
+
+
+def cls_family(tensors: dict) -> str | None:
+    """"yolo11-cls" / "yolov8-cls" for a checkpoint the ReID embedder runs, None for a file that is no classifier; a classifier of
+    another topology raises NotImplementedError (is_yolo11_cls is asked first, then is_yolov8_cls)."""
+    if is_yolo11_cls(tensors):
+        return "yolo11-cls"
+    return "yolov8-cls" if is_yolov8_cls(tensors) else None
 
 
 def cls_imgsz(tensors: dict) -> int:

@@ -50,7 +50,8 @@ extern "C" {
  *    gtx_tracker_config.alpha_fixed_emb appended, with_reid also read by types 3 (deepocsort) and 5 (tracktrack);
  *    gtx_op_estimate_affine_partial added (GMC methods orb / sift).
  * 10: gtx_ecc_* added (GMC method ecc); gtx_fgmc_* (GMC method orb, stream-ordered) and gtx_gray_half_dev added: new entry
- *     points only, no struct or existing signature changed, so the number stays. */
+ *     points only, no struct or existing signature changed, so the number stays. gtx_op_psa_attention added and the embedder takes
+ *     YOLO11-cls tensors (C2PSA = model.9): the same, the number stays. */
 #define GTX_ABI_VERSION 10
 
 typedef enum gtx_status {
@@ -204,6 +205,15 @@ int gtx_op_sppf_pool(gtx_ctx* ctx, int dtype, int n, int h, int w, int c, void* 
 /* nn.Upsample(scale_factor=2, mode="nearest") writing into a channel slice. */
 int gtx_op_upsample2x(gtx_ctx* ctx, int dtype, int n, int h, int w, int c, const void* x,
                       int in_cstride, int in_coff, void* y, int out_cstride, int out_coff);
+/* ultralytics' Attention block (YOLO11's C2PSA) on the first n of n_alloc maps: qkv [n_alloc][h][w][in_cstride] holds heads x
+ * [q 32 | k 32 | v 64] channels from in_coff; out [n][h][w][out_cstride] gets softmax(q^T k * 32^-0.5) v + pe(v) in its channels
+ * [out_coff, out_coff + 64 heads) and keeps the rest. pe_w [9][64 heads] tap-major, pe_b [64 heads]. Host arrays: fp16 (GTX_F16)
+ * or plain fp32 (GTX_F32; GTX_F32S: converted to the pair format on the way). form: 0 = the library's rule (the small-map kernel
+ * for h w <= 64), 1 / 2 = the large- / small-map kernel whatever the size. iters > 0: *ms_per_launch = mean time of that many
+ * further launches. *saturated: the launch clamped a value to fp16's range (GTX_F32S). */
+int gtx_op_psa_attention(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int heads, const void* qkv, int in_cstride,
+                         int in_coff, const float* pe_w, const float* pe_b, void* out, int out_cstride, int out_coff, int form,
+                         int iters, float* ms_per_launch, int* saturated);
 
 /* Brute-force L2 2-nearest-neighbour search of unit-norm 128-d float descriptors (RootSIFT): what
  * cv2.BFMatcher(NORM_L2).knnMatch(query, train, k=2) returns inside stabilo for the orthophoto
@@ -342,7 +352,7 @@ int gtx_detector_profile(gtx_detector* det, int nb, int iters, int cap, char* na
 /* ------------------------------------------------------------------ ReID embedder
  * A separate appearance network for `with_reid: true, model: <cls checkpoint>` (BoT-SORT, Deep OC-SORT, TrackTrack;
  * default.yaml:379, :421, :470): ultralytics' trackers/bot_sort.py ReID. Per detection, save_one_box's crop (gain 1.02, pad 10)
- * resampled as classify_transforms(imgsz) does (PIL bilinear to short side imgsz, center crop), the YOLOv8-cls backbone
+ * resampled as classify_transforms(imgsz) does (PIL bilinear to short side imgsz, center crop), the YOLOv8-cls or YOLO11-cls backbone
  * (model.0 - model.8, fused tensors by ultralytics state_dict names) and the global average pool of model.8: [n][dim] fp32,
  * dim = model.8's channels. The Classify head is not run. fp32_split: 1 = split-f16x3 convolutions with the detector's
  * saturation rule (a pass that clamps is re-run on the exact-fp32 kernels, and every later one; gtx_embedder_fell_back), 0 = exact

@@ -21,7 +21,7 @@ go into the small `rtdetr.meta` tensor [heads, points, queries, AIFI heads].
 A YOLOv8-RTDETR checkpoint (yolov8<scale>-rtdetr.yaml, geo-trax's train.sh `-rt`: the YOLOv8 backbone and neck, RTDETRDecoder =
 model.22) takes the same branch ("rtdetr" is in its yaml name); with no AIFI its last `rtdetr.meta` entry falls back to 8 and is unused.
 
-A YOLOv8-cls checkpoint (the ReID network of `with_reid: true, model: <file>.safetensors` in a tracker yaml) is written the same
+A YOLOv8-cls or YOLO11-cls checkpoint (the ReID network of `with_reid: true, model: <file>.safetensors` in a tracker yaml) is written the same
 way, plus `cls.meta` = [imgsz] from the checkpoint's training arguments (geotrax_amd.weights.cls_imgsz; 224 when absent).
 """
 import sys
