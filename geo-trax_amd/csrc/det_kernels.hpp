@@ -126,6 +126,16 @@ struct SparseBox {
   int* sat_flag;
 };
 void launch_head_sparse_box(const SparseBox& sb, int n, const NmsBuffers& nb, hipStream_t s);
+// ---- the YOLOv10 tail (v10_select.hip): v10Detect's one-to-one head needs no NMS
+constexpr int kV10Keep = 300;   // ultralytics Detect.max_det: the rows v10Detect.postprocess keeps per image, whatever the predictor's max_det
+// cand: the score gate's candidates (launch_head_gate with every class kept: one per anchor whose best score clears conf). sel (cap in
+// [kV10Keep, 512], its own count / cand_* arrays; lvl_* optional): the at most kV10Keep (anchor, class) entries the two-stage cut keeps,
+// sorted by score (ties: the lower flat index anchor * nc + class first), filed by level for launch_head_sparse_box. scores: scratch
+// [N][kV10Keep][nc] fp32.
+void launch_v10_select(int dtype, const HeadParams& hp, int n, const NmsBuffers& cand, const NmsBuffers& sel, float* scores, hipStream_t s);
+// sel's entries with their boxes (cand_box: launch_head_sparse_box or launch_head_boxes on sel) -> out_rows / out_n (/ out_anchor):
+// `classes`, the max_det cut, scale_boxes + clip to the frame
+void launch_v10_rows(const NmsBuffers& sel, const unsigned long long class_mask[2], int n, const Letterbox& lb, hipStream_t s);
 // Decode every anchor (debug / parity): out [N][A][4+nc] fp32 = xywh (network px) + class scores
 // (or class logits).
 void launch_head_raw(int dtype, const HeadParams& hp, int n, float* out, bool logits, hipStream_t s);

@@ -1,7 +1,7 @@
-// YOLOv8 / YOLO11 (detect) graph builder + executor: the trunk (yolo_trunk.cpp walks the layer table of ultralytics' cfg/models/v8/yolov8.yaml,
+// YOLOv8 / YOLO11 / YOLOv10 (detect) graph builder + executor: the trunk (yolo_trunk.cpp walks the layer table of ultralytics' cfg/models/v8/yolov8.yaml,
 // yolov8-p2.yaml or cfg/models/11/yolo11.yaml, whichever the tensor names tell) and the Detect layer on the levels, strides and prefix the
-// table's Detect row gives (model.22, model.28 of the P2 graph: a fourth level at stride 4, or model.23 of YOLO11: a class branch of
-// depthwise + pointwise pairs); channel widths and bottleneck counts are read off the tensor shapes, so every scale (n/s/m/l/x) loads unchanged.
+// table's Detect row gives (model.22, model.28 of the P2 graph: a fourth level at stride 4, or model.23 of YOLO11 and YOLOv10: a class branch of
+// depthwise + pointwise pairs; YOLOv10's one-to-one pair of branches ends in the top-300 cut of v10_select.hip instead of the NMS); channel widths and bottleneck counts are read off the tensor shapes, so every scale (n/s/m/l/x) loads unchanged.
 #include "detector.hpp"
 #include "split_format.hpp"
 
@@ -50,6 +50,16 @@ void Detector::build_graph() {
   det_pfx_ = trunk.det_pfx;
   const int nl = (int)lvl_in.size();
   GTX_CHECK(nl <= kMaxLevels, "internal: %d Detect levels", nl);
+  // v10Detect holds Detect's layers twice: cv2 / cv3 (one-to-many, followed by NMS) and one2one_cv2 / one2one_cv3 (followed by the
+  // top-300 cut, v10_select.hip). gtx_det_config.end2end picks the pair; the other pair's tensors are not read.
+  const bool has_o2o = has(det_pfx_ + ".one2one_cv2.0.0.conv.weight");
+  end2end_ = cfg_.end2end != 0;
+  GTX_CHECK(!end2end_ || has_o2o, "end2end: the checkpoint has no one-to-one head (%s.one2one_cv2 / one2one_cv3): only a YOLOv10 file has", det_pfx_.c_str());
+  GTX_CHECK(!end2end_ || !cfg_.obj_feats, "end2end: obj_feats (ReID `model: auto`) is not implemented for the one-to-one head");
+  const std::string box_br = end2end_ ? ".one2one_cv2." : ".cv2.", cls_br = end2end_ ? ".one2one_cv3." : ".cv3.";
+  GTX_CHECK(has(det_pfx_ + box_br + "0.0.conv.weight") && has(det_pfx_ + cls_br + "0.2.weight"),
+            "%s: the checkpoint holds no %s / %s tensors (a fused YOLOv10 export keeps the one-to-one head only: run it with end2end)", det_pfx_.c_str(),
+            box_br.substr(1, box_br.size() - 2).c_str(), cls_br.substr(1, cls_br.size() - 2).c_str());
 
   // ---- Detect (model.22, or model.28 of the P2 graph) ----
   // Stage 1 fuses the sibling convs cv2[l][0] and cv3[l][0] (same input) into one conv by
@@ -68,7 +78,7 @@ void Detector::build_graph() {
     if (cfg_.classes[i] >= 0 && cfg_.classes[i] < 128) head_.class_mask[cfg_.classes[i] >> 6] |= 1ull << (cfg_.classes[i] & 63);
   int anchor = 0;
   for (int l = 0; l < nl; ++l) {
-    const std::string b2 = det_pfx_ + ".cv2." + std::to_string(l), b3 = det_pfx_ + ".cv3." + std::to_string(l);
+    const std::string b2 = det_pfx_ + box_br + std::to_string(l), b3 = det_pfx_ + cls_br + std::to_string(l);
     const HostTensor &w20 = tensor(b2 + ".0.conv.weight"), &w30 = tensor(b3 + (dw_cls ? ".1.1.conv.weight" : ".0.conv.weight"));
     const int cb = (int)w20.shape[0], cc = (int)w30.shape[0], cin = (int)w20.shape[1];
     GTX_CHECK(cin == lvl_in[l].c && (dw_cls || (int)w30.shape[1] == cin), "Detect level %d input channels", l);
@@ -407,11 +417,13 @@ void Detector::finalize() {
   nms_.cand_anchor = (int*)alloc(sizeof(int) * N * nms_.cap);
   nms_.cand_cls = (int*)alloc(sizeof(int) * N * nms_.cap);
   nms_.cand_box = (float*)alloc(sizeof(float) * 4 * N * nms_.cap);
-  nms_.sorted_n = (int*)alloc(sizeof(int) * N);
-  nms_.s_box = (float*)alloc(sizeof(float) * 4 * N * nms_.nms_cap);
-  nms_.s_score = (float*)alloc(sizeof(float) * N * nms_.nms_cap);
-  nms_.s_cls = (int*)alloc(sizeof(int) * N * nms_.nms_cap);
-  nms_.mask = (unsigned long long*)alloc(sizeof(unsigned long long) * N * (size_t)nms_.nms_cap * (nms_.nms_cap / 64));
+  if (!end2end_) {                                   // the sort / mask workspace of the NMS kernels (113 MB per batch slot): the one-to-one head runs none of them
+    nms_.sorted_n = (int*)alloc(sizeof(int) * N);
+    nms_.s_box = (float*)alloc(sizeof(float) * 4 * N * nms_.nms_cap);
+    nms_.s_score = (float*)alloc(sizeof(float) * N * nms_.nms_cap);
+    nms_.s_cls = (int*)alloc(sizeof(int) * N * nms_.nms_cap);
+    nms_.mask = (unsigned long long*)alloc(sizeof(unsigned long long) * N * (size_t)nms_.nms_cap * (nms_.nms_cap / 64));
+  }
   nms_.out_n = (int*)alloc(sizeof(int) * N);
   nms_.out_rows = (float*)alloc(sizeof(float) * 6 * N * cfg_.max_det);
   nms_.s_anchor = nms_.out_anchor = nullptr;
@@ -421,12 +433,33 @@ void Detector::finalize() {
     d_feats_ = (float*)alloc(sizeof(float) * N * cfg_.max_det * feat_levels_.dim);
     GTX_HIP(hipHostMalloc((void**)&h_feats_, sizeof(float) * N * cfg_.max_det * feat_levels_.dim));
   }
-  if (sparse_on_) {
+  if (sparse_on_ && !end2end_) {
     sparse_.cap = kSparseCap;
     sparse_.sat_flag = sat_dev_;
     nms_.lvl_cap = kSparseCap;
     nms_.lvl_count = (int*)alloc(sizeof(int) * N * kMaxLevels);
     nms_.lvl_list = (int*)alloc(sizeof(int) * N * kMaxLevels * kSparseCap);
+  }
+  if (end2end_) {
+    // the one-to-one head: nms_ holds the gate's candidates (one per anchor at most); sel_ the entries v10_select keeps, with the
+    // result buffers; the box branch runs on sel_'s entries only
+    sel_ = nms_;
+    sel_.cap = kSelCap;
+    sel_.count = (int*)alloc(sizeof(int) * N);
+    sel_.cand_score = (float*)alloc(sizeof(float) * N * kSelCap);
+    sel_.cand_anchor = (int*)alloc(sizeof(int) * N * kSelCap);
+    sel_.cand_cls = (int*)alloc(sizeof(int) * N * kSelCap);
+    sel_.cand_box = (float*)alloc(sizeof(float) * 4 * N * kSelCap);
+    sel_.lvl_count = sel_.lvl_list = nullptr;
+    sel_.lvl_cap = 0;
+    if (sparse_on_) {
+      sparse_.cap = kSelCap;
+      sparse_.sat_flag = sat_dev_;
+      sel_.lvl_cap = kSelCap;
+      sel_.lvl_count = (int*)alloc(sizeof(int) * N * kMaxLevels);
+      sel_.lvl_list = (int*)alloc(sizeof(int) * N * kMaxLevels * kSelCap);
+    }
+    v10_scores_ = (float*)alloc(sizeof(float) * N * kV10Keep * cfg_.nc);
   }
   GTX_HIP(hipHostMalloc((void**)&h_count_, sizeof(int) * N));
   drop_tensors_unless_fallback();
@@ -442,6 +475,24 @@ void Detector::finalize() {
 void Detector::run_op(const Op& op, int nb, hipStream_t s) { trunk_.run_op(op, nb, s); }
 
 void Detector::run_post(int nb, hipStream_t s) {
+  if (end2end_) {                                  // no NMS: gate -> the two-stage top-300 cut -> the box branch at the entries kept -> rows
+    HeadParams gate = head_;
+    gate.class_mask[0] = gate.class_mask[1] = ~0ull;   // `classes` is applied to the rows the cut keeps, not in front of it
+    launch_head_gate(dtype_, gate, nb, nms_, s);
+    launch_v10_select(dtype_, head_, nb, nms_, sel_, v10_scores_, s);
+    if (sparse_on_) {
+      launch_head_sparse_box(sparse_, nb, sel_, s);
+      dense_head_valid_ = false;
+    } else {
+      launch_head_boxes(dtype_, head_, nb, sel_, s);
+    }
+    launch_v10_rows(sel_, head_.class_mask, nb, lb_, s);
+    GTX_HIP(hipMemcpyAsync(h_count_, nms_.count, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
+    GTX_HIP(hipMemcpyAsync(h_out_n_, sel_.out_n, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
+    GTX_HIP(hipMemcpyAsync(h_out_rows_, sel_.out_rows, sizeof(float) * 6 * nb * cfg_.max_det, hipMemcpyDeviceToHost, s));
+    if (sat_dev_) GTX_HIP(hipMemcpyAsync(h_sat_, sat_dev_, sizeof(int), hipMemcpyDeviceToHost, s));
+    return;
+  }
   if (sparse_on_) {                                // score gate -> the box branch at the candidates -> their boxes
     launch_head_gate(dtype_, head_, nb, nms_, s);
     launch_head_sparse_box(sparse_, nb, nms_, s);    // the box branch at the candidates and their boxes
@@ -478,6 +529,11 @@ void Detector::run_dense_box(hipStream_t s) {
 // What the pass left out for the common case: the general NMS kernels for > 4096 candidates in an image, the dense box layers and
 // every candidate's box for > kSparseCap; then the appearance vectors out of the pinned buffer before the next pass lands in it.
 void Detector::after_pass(int nb) {
+  // The one-to-one head leaves nothing out of its pass, so there is no overflow case to finish here: the gate's buffer (nms_.cap =
+  // n_anchors) takes one candidate per anchor at most, head_candidates_kernel writes no more, and v10_select hands the box branch at
+  // most kV10Keep = 300 entries of sel_'s 304 (cap and lvl_cap) -- the sparse buffer cannot fill, whatever conf is
+  // (tests/test_yolov10_gpu.py::test_every_anchor_a_candidate). No NMS runs either, so there is no large-NMS re-run.
+  if (end2end_) return;
   bool over = false, big = false;
   for (int b = 0; b < nb; ++b) {
     over = over || (sparse_on_ && h_count_[b] > kSparseCap);                 // more candidates than the sparse buffer holds

@@ -55,6 +55,11 @@ class Detector : public DetectorBase {
 
   HeadParams head_{};
   NmsBuffers nms_{};
+  // gtx_det_config.end2end (yolov10.yaml's one-to-one head): the entries v10_select keeps (v10_select.hip) and its score scratch
+  bool end2end_ = false;
+  NmsBuffers sel_{};
+  float* v10_scores_ = nullptr;
+  static constexpr int kSelCap = 304;       // >= kV10Keep, whole groups of 16 for the sparse box branch
   DevBuf raw_;               // debug raw output
   bool plain_out_ = false;   // convs being built write plain fp32 (head stage 2)
   FeatLevels feat_levels_{};

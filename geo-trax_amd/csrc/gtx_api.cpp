@@ -14,6 +14,7 @@
 #include "det_kernels.hpp"
 #include "detector.hpp"
 #include "rtdetr.hpp"
+#include "rtdetr_kernels.hpp"
 #include "geometry.hpp"
 #include "ecc.hpp"
 #include "gmc.hpp"
@@ -454,6 +455,45 @@ int gtx_op_psa_attention(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int
   });
 }
 
+int gtx_op_dwconv(gtx_ctx* ctx, int dtype, int n, int h, int w, int c, int k, int stride, const void* x, const float* wt, const float* bias,
+                  int act, const void* res, void* out, int* saturated) {
+  return guarded([&] {
+    need(ctx, "ctx"); need(x, "x"); need(wt, "w"); need(bias, "bias"); need(out, "out");
+    if (n < 1 || h < 1 || w < 1 || c < 8 || c % 8 || (k != 3 && k != 5 && k != 7) || (stride != 1 && stride != 2)) gtx::fail(GTX_ERR_INVALID, "dwconv: bad sizes");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const int ho = (h - 1) / stride + 1, wo = (w - 1) / stride + 1;
+    const size_t es = gtx::dtype_size(dtype);
+    const size_t xb = (size_t)n * h * w * c * es, yb = (size_t)n * ho * wo * c * es, wb = (size_t)k * k * c * 4;
+    gtx::DevBuf dx(xb), dy(yb), dr(res ? yb : 16), dw(wb), db((size_t)c * 4), ds(4);
+    std::vector<uint8_t> tx, ty;
+    auto up = [&](gtx::DevBuf& d, const void* src, size_t bytes) {
+      if (dtype == GTX_F32S) {                        // plain fp32 host arrays <-> pair format on the device
+        tx.resize(bytes);
+        gtx::f32_to_pairs(static_cast<const float*>(src), tx.data(), bytes / 4);
+        src = tx.data();
+      }
+      GTX_HIP(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+    };
+    up(dx, x, xb);
+    if (res) up(dr, res, yb);
+    GTX_HIP(hipMemcpy(dw.p, wt, wb, hipMemcpyHostToDevice));
+    GTX_HIP(hipMemcpy(db.p, bias, (size_t)c * 4, hipMemcpyHostToDevice));
+    GTX_HIP(hipMemset(ds.p, 0, 4));
+    GTX_HIP(hipMemset(dy.p, 0, yb));
+    const gtx::RtMap in{dx.p, h, w, c, 0, c}, o{dy.p, ho, wo, c, 0, c}, r{dr.p, ho, wo, c, 0, c};
+    gtx::launch_rt_dwconv(dtype, in, o, n, k, stride, dw.as<float>(), db.as<float>(), act, ds.as<int>(), ctx->stream, res ? &r : nullptr);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    if (dtype == GTX_F32S) {
+      ty.resize(yb);
+      GTX_HIP(hipMemcpy(ty.data(), dy.p, yb, hipMemcpyDeviceToHost));
+      gtx::pairs_to_f32(ty.data(), static_cast<float*>(out), yb / 4);
+    } else {
+      GTX_HIP(hipMemcpy(out, dy.p, yb, hipMemcpyDeviceToHost));
+    }
+    if (saturated) GTX_HIP(hipMemcpy(saturated, ds.p, 4, hipMemcpyDeviceToHost));
+  });
+}
+
 struct gtx_gmc {
   gtx_ctx* ctx;
   std::unique_ptr<gtx::Gmc> impl;
@@ -719,6 +759,7 @@ int gtx_detector_create(gtx_ctx* ctx, const gtx_det_config* cfg, gtx_detector** 
   return guarded([&] {
     need(ctx, "ctx"); need(cfg, "cfg"); need(out, "out");
     std::unique_ptr<gtx_detector> d(new gtx_detector);
+    if (cfg->arch == 1 && cfg->end2end) gtx::fail(-3, "gtx_det_config.end2end: the one-to-one head belongs to YOLOv10 (arch 0); RT-DETR has no NMS to leave out");
     if (cfg->arch == 1) d->impl.reset(new gtx::RtDetr(ctx, *cfg));
     else if (cfg->arch == 0) d->impl.reset(new gtx::Detector(ctx, *cfg));
     else gtx::fail(-3, "gtx_det_config.arch %d: 0 (YOLOv8) or 1 (RT-DETR)", cfg->arch);

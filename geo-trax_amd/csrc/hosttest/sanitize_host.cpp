@@ -20,6 +20,7 @@
 #include "../geometry.hpp"
 #include "../tracker.hpp"
 #include "../vec_acos.hpp"
+#include "../yolo_tables.hpp"
 
 namespace {
 struct Frame { std::vector<float> xyxy, conf; std::vector<int> cls; };
@@ -171,10 +172,44 @@ bool run_writers(unsigned seed) {
   return anchor[0] == 0 && anchor[1] <= 1;
 }
 
+// The YOLO trunks' layer tables are walkable (yolov10.yaml's among them), a broken one is caught at its row, and the depthwise
+// weight transposition touches exactly its taps x channels values (odd sizes: 7x7 on 24 channels, 3x3 on 8)
+static bool run_trunk_tables() {
+  using namespace gtx;
+  using namespace gtx::tables;
+  const struct { const TrunkRow* rows; int n; } all[] = {{kYolov8, (int)(sizeof(kYolov8) / sizeof(TrunkRow))}, {kYolov8P2, (int)(sizeof(kYolov8P2) / sizeof(TrunkRow))},
+                                                          {kYolo11, (int)(sizeof(kYolo11) / sizeof(TrunkRow))}, {kYolo10, (int)(sizeof(kYolo10) / sizeof(TrunkRow))},
+                                                          {kYolo11Cls, (int)(sizeof(kYolo11Cls) / sizeof(TrunkRow))}, {kYolov8, kClsBackboneRows}};
+  for (const auto& t : all)
+    if (trunk_table_error(t.rows, t.n) >= 0) return false;
+  int scdown = 0, psa = 0;
+  for (const TrunkRow& r : kYolo10) { scdown += r.mod == TrunkRow::SCDOWN; psa += r.mod == TrunkRow::PSA; }
+  if (scdown != 3 || psa != 1 || kYolo10[23].mod != TrunkRow::DETECT) return false;
+  std::vector<TrunkRow> bad(kYolo10, kYolo10 + 24);
+  bad[12].from[1] = 13;                               // a Concat that reads a later layer
+  if (trunk_table_error(bad.data(), 24) != 12) return false;
+  bad.assign(kYolo10, kYolo10 + 24);
+  bad[21].from[1] = 6;                                // model.6 in two Concats
+  if (trunk_table_error(bad.data(), 24) != 21) return false;
+  const int sizes[2][2] = {{24, 49}, {8, 9}};
+  for (const auto& ck : sizes) {
+    const int c = ck[0], taps = ck[1];
+    std::vector<float> w((size_t)c * taps);
+    for (size_t i = 0; i < w.size(); ++i) w[i] = (float)i;
+    const std::vector<float> wt = dw_tap_major(w.data(), c, taps);
+    if (wt.size() != w.size()) return false;
+    for (int ch = 0; ch < c; ++ch)
+      for (int t = 0; t < taps; ++t)
+        if (wt[(size_t)t * c + ch] != (float)(ch * taps + t)) return false;
+  }
+  return true;
+}
+
 int main(int argc, char** argv) {
   const bool threads = argc > 1 && argv[1][0] == 't';
   long rows = 0;
   if (!run_writers(threads ? 2 : 1)) { std::fprintf(stderr, "result-file writers failed\n"); return 3; }
+  if (!run_trunk_tables()) { std::fprintf(stderr, "trunk layer tables / depthwise packing wrong\n"); return 6; }
   if (threads) {
     std::vector<long> r(6);
     std::vector<std::thread> th;

@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void rt_pool2_kernel(RtMap in, RtMap out, int 
 // ============================================================================ depthwise convolution
 template <int FMT, int K>
 __global__ __launch_bounds__(256) void rt_dwconv_kernel(RtMap in, RtMap out, int N, int stride, const float* __restrict__ w,
-                                                        const float* __restrict__ bias, int act, int* sat) {
+                                                        const float* __restrict__ bias, int act, int* sat, RtMap res) {
   const int groups = in.c / 8, C = in.c;
   const size_t total = (size_t)N * out.h * out.w * groups;
   const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -216,6 +216,12 @@ __global__ __launch_bounds__(256) void rt_dwconv_kernel(RtMap in, RtMap out, int
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = acc[j] * __builtin_amdgcn_rcpf(1.f + __expf(-acc[j]));
   }
+  if (res.ptr) {                                      // x + act(conv(x)): the residual after the activation, like the convolutions' epilogue (YOLOv10's CIB)
+    float r[8];
+    load8<FMT>(res.ptr, pix * res.cstride + res.coff + g * 8, r);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] += r[j];
+  }
   bool s = false;
   store8<FMT>(out.ptr, pix * out.cstride + out.coff + g * 8, acc, s);
   flag_sat(sat, s);
@@ -225,10 +231,11 @@ __global__ __launch_bounds__(256) void rt_dwconv_kernel(RtMap in, RtMap out, int
 // takes an 8 x 8 pixel tile x 32 channels, stages the (8 + K - 1)^2 input patch ONCE in LDS as fp32 (the per-thread form read and
 // converted every input pixel K^2 times: 25 small loads per thread made it latency-bound at 0.7 TB/s) and its K^2 x 32 weights,
 // then every thread runs the same K^2 fused multiply-adds in the same order: the results are the per-thread kernel's bit for bit.
+// K = 7 (YOLOv10's fused RepVGGDW, a 3-pixel halo): the same tiling with a 14 x 14 patch, 25 KB + 6 KB of LDS.
 // (A 16 x 16-pixel tile with four pixels of a row per thread -- 26 LDS reads per 160 multiply-adds instead of 80, 1.56 x instead of 2.25 x
 // halo -- was measured at the end of round 6: 0.609 against 0.59-0.60 ms for the 24 launches. Not LDS reads; the staging's round trip per workgroup.)
 template <int FMT, int K>
-__global__ __launch_bounds__(256) void rt_dwconv_tile_kernel(RtMap in, RtMap out, const float* __restrict__ w, const float* __restrict__ bias, int act, int* sat) {
+__global__ __launch_bounds__(256) void rt_dwconv_tile_kernel(RtMap in, RtMap out, const float* __restrict__ w, const float* __restrict__ bias, int act, int* sat, RtMap res) {
   constexpr int T = 8, P = T + K - 1, R = K / 2;
   __shared__ float s_in[P * P][32];
   __shared__ float s_w[K * K][32];
@@ -268,6 +275,12 @@ __global__ __launch_bounds__(256) void rt_dwconv_tile_kernel(RtMap in, RtMap out
   } else if (act == 1) {                              // SiLU, as the convolutions' epilogue computes it (YOLO11's DWConv)
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = acc[j] * __builtin_amdgcn_rcpf(1.f + __expf(-acc[j]));
+  }
+  if (res.ptr) {                                      // x + act(conv(x)), as in rt_dwconv_kernel
+    float r[8];
+    load8<FMT>(res.ptr, (((size_t)n * out.h + oy) * out.w + ox) * res.cstride + res.coff + c0 + g * 8, r);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] += r[j];
   }
   bool s = false;
   store8<FMT>(out.ptr, (((size_t)n * out.h + oy) * out.w + ox) * out.cstride + out.coff + c0 + g * 8, acc, s);
@@ -1198,19 +1211,24 @@ void launch_rt_pool2(int fmt, const RtMap& in, const RtMap& out, int n, int* sat
   RT_FMT(fmt, hipLaunchKernelGGL(rt_pool2_kernel<F>, dim3(blocks_for(total)), dim3(256), 0, s, in, out, n, sat));
 }
 
-void launch_rt_dwconv(int fmt, const RtMap& in, const RtMap& out, int n, int k, int stride, const float* w, const float* bias, int act, int* sat, hipStream_t s) {
-  GTX_CHECK(in.c % 8 == 0 && in.c == out.c && (k == 3 || k == 5) && (stride == 1 || stride == 2), "rt_dwconv: unsupported %dx%d stride %d on %d channels", k, k, stride, in.c);
+void launch_rt_dwconv(int fmt, const RtMap& in, const RtMap& out, int n, int k, int stride, const float* w, const float* bias, int act, int* sat, hipStream_t s,
+                      const RtMap* residual) {
+  GTX_CHECK(in.c % 8 == 0 && in.c == out.c && (k == 3 || k == 5 || k == 7) && (stride == 1 || stride == 2), "rt_dwconv: unsupported %dx%d stride %d on %d channels", k, k, stride, in.c);
   GTX_CHECK(out.h == (in.h + 2 * (k / 2) - k) / stride + 1 && out.w == (in.w + 2 * (k / 2) - k) / stride + 1, "rt_dwconv: output size");
+  const RtMap res = residual ? *residual : RtMap{nullptr, 0, 0, 0, 0, 0};
+  GTX_CHECK(!res.ptr || (res.h == out.h && res.w == out.w && res.c == out.c && res.coff % 8 == 0 && res.cstride % 8 == 0), "rt_dwconv: the residual does not have the output's shape");
   const size_t total = (size_t)n * out.h * out.w * (in.c / 8);
   static const bool tiled = [] { const char* e = getenv("GTX_RT_DW_TILE"); return !(e && e[0] == '0'); }();
   if (stride == 1 && in.c % 32 == 0 && tiled) {
     const dim3 grid(cdiv(out.w, 8) * cdiv(out.h, 8), in.c / 32, n);
-    if (k == 3) RT_FMT(fmt, hipLaunchKernelGGL((rt_dwconv_tile_kernel<F, 3>), grid, dim3(256), 0, s, in, out, w, bias, act, sat));
-    else RT_FMT(fmt, hipLaunchKernelGGL((rt_dwconv_tile_kernel<F, 5>), grid, dim3(256), 0, s, in, out, w, bias, act, sat));
+    if (k == 3) RT_FMT(fmt, hipLaunchKernelGGL((rt_dwconv_tile_kernel<F, 3>), grid, dim3(256), 0, s, in, out, w, bias, act, sat, res));
+    else if (k == 5) RT_FMT(fmt, hipLaunchKernelGGL((rt_dwconv_tile_kernel<F, 5>), grid, dim3(256), 0, s, in, out, w, bias, act, sat, res));
+    else RT_FMT(fmt, hipLaunchKernelGGL((rt_dwconv_tile_kernel<F, 7>), grid, dim3(256), 0, s, in, out, w, bias, act, sat, res));
     return;
   }
-  if (k == 3) RT_FMT(fmt, hipLaunchKernelGGL((rt_dwconv_kernel<F, 3>), dim3(blocks_for(total)), dim3(256), 0, s, in, out, n, stride, w, bias, act, sat));
-  else RT_FMT(fmt, hipLaunchKernelGGL((rt_dwconv_kernel<F, 5>), dim3(blocks_for(total)), dim3(256), 0, s, in, out, n, stride, w, bias, act, sat));
+  if (k == 3) RT_FMT(fmt, hipLaunchKernelGGL((rt_dwconv_kernel<F, 3>), dim3(blocks_for(total)), dim3(256), 0, s, in, out, n, stride, w, bias, act, sat, res));
+  else if (k == 5) RT_FMT(fmt, hipLaunchKernelGGL((rt_dwconv_kernel<F, 5>), dim3(blocks_for(total)), dim3(256), 0, s, in, out, n, stride, w, bias, act, sat, res));
+  else RT_FMT(fmt, hipLaunchKernelGGL((rt_dwconv_kernel<F, 7>), dim3(blocks_for(total)), dim3(256), 0, s, in, out, n, stride, w, bias, act, sat, res));
 }
 
 void launch_rt_upsample2x(int fmt, const RtMap& in, const RtMap& out, int n, hipStream_t s) {

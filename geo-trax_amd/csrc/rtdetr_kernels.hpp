@@ -24,8 +24,10 @@ struct RtMap {            // one NHWC map tensor (or a channel slice of one)
 void launch_rt_stem1(int fmt, const void* img, int n, int H, int W, const float* w27, const float* bias, const RtMap& out, int* sat, hipStream_t s);
 // MaxPool2d(2, 1, ceil_mode) on F.pad(x, [0, 1, 0, 1]): out(y, x) = max over the 2 x 2 window at (y, x), zeros past the border
 void launch_rt_pool2(int fmt, const RtMap& in, const RtMap& out, int n, int* sat, hipStream_t s);
-// depthwise k x k (3 or 5), stride 1 or 2, pad k / 2; w [k * k][C] tap-major, bias [C]; act: 0 none, 1 SiLU (YOLO11's DWConv), 2 ReLU
-void launch_rt_dwconv(int fmt, const RtMap& in, const RtMap& out, int n, int k, int stride, const float* w, const float* bias, int act, int* sat, hipStream_t s);
+// depthwise k x k (3, 5 or 7), stride 1 or 2, pad k / 2; w [k * k][C] tap-major, bias [C]; act: 0 none, 1 SiLU (YOLO11's DWConv), 2 ReLU;
+// residual (optional, the output's shape): added after the activation (YOLOv10's CIB: x + cv1(x))
+void launch_rt_dwconv(int fmt, const RtMap& in, const RtMap& out, int n, int k, int stride, const float* w, const float* bias, int act, int* sat, hipStream_t s,
+                      const RtMap* residual = nullptr);
 // nearest 2x upsampling into a channel slice (raw copy of 8-channel groups)
 void launch_rt_upsample2x(int fmt, const RtMap& in, const RtMap& out, int n, hipStream_t s);
 // map -> tokens: src [N * h * w][C] plain fp32 and, when q != null, q = src + pos (pos [h * w][C])

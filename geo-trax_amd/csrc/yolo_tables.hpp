@@ -1,0 +1,101 @@
+// The YOLO trunks' layer tables and the pure host arithmetic around them: no HIP, no device memory, so that the host sanitizer
+// builds (make asan tsan, csrc/hosttest/sanitize_host.cpp) cover them. yolo_trunk.cpp walks the tables.
+#pragma once
+#include <cstddef>
+#include <vector>
+
+namespace gtx {
+
+// One row of a trunk's layer table: a layer of the model yaml, as the yaml writes it
+struct TrunkRow {
+  enum Module { CONV, BLOCK, SPPF, C2PSA, UPSAMPLE, CONCAT, DETECT, SCDOWN, PSA };
+  int i;            // the layer index: its tensors are "model.<i>.*"
+  Module mod;       // CONV: Conv 3x3 stride 2 (row 0: the stem); BLOCK: C2f / C3k2 / C2fCIB (which one, the tensors tell);
+                    // SCDOWN: 1x1 Conv + depthwise 3x3 stride 2 without activation; PSA: C2PSA's one block directly under the layer (yolov10.yaml)
+  int from[4];      // the yaml's `from`: -1 = the row above (row 0: the image), else a layer index; 0 ends the list
+  bool shortcut;    // BLOCK: the bottlenecks add their input
+};
+struct TrunkGraph {
+  const TrunkRow* rows;
+  int n;
+  bool dw_cls;      // yolo11.yaml's Detect: the class branch is DWConv + 1x1 Conv twice
+};
+
+// The first row of a table that build() cannot walk, -1 when there is none: row i is layer i, it reads at least one layer, only
+// earlier ones (row 0: the image), a Concat's members feed one Concat only, an Upsample leads its Concat, the Detect row comes last.
+inline int trunk_table_error(const TrunkRow* rows, int n) {
+  std::vector<int> cat_of(n > 0 ? n : 0, -1);
+  for (int i = 0; i < n; ++i) {
+    const TrunkRow& r = rows[i];
+    int nf = 0;
+    while (nf < 4 && r.from[nf] != 0) ++nf;
+    if (r.i != i || nf < 1) return i;
+    for (int k = 0; k < nf; ++k) {
+      const int f = r.from[k] < 0 ? i + r.from[k] : r.from[k];
+      if (f >= i || (f < 0 && i != 0)) return i;
+      if (r.mod == TrunkRow::CONCAT) {
+        if (cat_of[f] >= 0 || (rows[f].mod == TrunkRow::UPSAMPLE && k != 0)) return i;
+        cat_of[f] = i;
+      }
+    }
+    if (r.mod == TrunkRow::DETECT && i != n - 1) return i;
+    if (r.mod != TrunkRow::CONCAT && r.mod != TrunkRow::DETECT && nf != 1) return i;
+  }
+  return -1;
+}
+
+// Depthwise weights [C][1][k][k] (taps = k * k values per channel) -> tap-major [taps][C], what rt_dwconv_* read
+inline std::vector<float> dw_tap_major(const float* w, int c, int taps) {
+  std::vector<float> wt((size_t)taps * c);
+  for (int ch = 0; ch < c; ++ch)
+    for (int t = 0; t < taps; ++t) wt[(size_t)t * c + ch] = w[(size_t)ch * taps + t];
+  return wt;
+}
+
+namespace tables {
+using R = TrunkRow;
+inline constexpr R kYolov8[] = {
+    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},
+    {4, R::BLOCK, {-1}, true},      {5, R::CONV, {-1}, false},        {6, R::BLOCK, {-1}, true},       {7, R::CONV, {-1}, false},
+    {8, R::BLOCK, {-1}, true},      {9, R::SPPF, {-1}, false},        {10, R::UPSAMPLE, {-1}, false},  {11, R::CONCAT, {-1, 6}, false},
+    {12, R::BLOCK, {-1}, false},    {13, R::UPSAMPLE, {-1}, false},   {14, R::CONCAT, {-1, 4}, false}, {15, R::BLOCK, {-1}, false},
+    {16, R::CONV, {-1}, false},     {17, R::CONCAT, {-1, 12}, false}, {18, R::BLOCK, {-1}, false},     {19, R::CONV, {-1}, false},
+    {20, R::CONCAT, {-1, 9}, false}, {21, R::BLOCK, {-1}, false},     {22, R::DETECT, {15, 18, 21}, false}};
+inline constexpr int kClsBackboneRows = 9;   // yolov8-cls.yaml: model.0-8 are yolov8.yaml's
+inline constexpr R kYolov8P2[] = {
+    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},
+    {4, R::BLOCK, {-1}, true},      {5, R::CONV, {-1}, false},        {6, R::BLOCK, {-1}, true},       {7, R::CONV, {-1}, false},
+    {8, R::BLOCK, {-1}, true},      {9, R::SPPF, {-1}, false},        {10, R::UPSAMPLE, {-1}, false},  {11, R::CONCAT, {-1, 6}, false},
+    {12, R::BLOCK, {-1}, false},    {13, R::UPSAMPLE, {-1}, false},   {14, R::CONCAT, {-1, 4}, false}, {15, R::BLOCK, {-1}, false},
+    {16, R::UPSAMPLE, {-1}, false}, {17, R::CONCAT, {-1, 2}, false},  {18, R::BLOCK, {-1}, false},     {19, R::CONV, {-1}, false},
+    {20, R::CONCAT, {-1, 15}, false}, {21, R::BLOCK, {-1}, false},    {22, R::CONV, {-1}, false},      {23, R::CONCAT, {-1, 12}, false},
+    {24, R::BLOCK, {-1}, false},    {25, R::CONV, {-1}, false},       {26, R::CONCAT, {-1, 9}, false}, {27, R::BLOCK, {-1}, false},
+    {28, R::DETECT, {18, 21, 24, 27}, false}};
+// YOLO11's shortcuts: on in the backbone; in the neck kNeckShortcut, which no tensor tells (taken as off, as in yolov8.yaml's neck;
+// tests/yolo11_ref.py names the doubt).
+inline constexpr bool kNeckShortcut = false;
+inline constexpr R kYolo11[] = {
+    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},
+    {4, R::BLOCK, {-1}, true},      {5, R::CONV, {-1}, false},        {6, R::BLOCK, {-1}, true},       {7, R::CONV, {-1}, false},
+    {8, R::BLOCK, {-1}, true},      {9, R::SPPF, {-1}, false},        {10, R::C2PSA, {-1}, false},     {11, R::UPSAMPLE, {-1}, false},
+    {12, R::CONCAT, {-1, 6}, false}, {13, R::BLOCK, {-1}, kNeckShortcut}, {14, R::UPSAMPLE, {-1}, false}, {15, R::CONCAT, {-1, 4}, false},
+    {16, R::BLOCK, {-1}, kNeckShortcut}, {17, R::CONV, {-1}, false},  {18, R::CONCAT, {-1, 13}, false}, {19, R::BLOCK, {-1}, kNeckShortcut},
+    {20, R::CONV, {-1}, false},     {21, R::CONCAT, {-1, 10}, false}, {22, R::BLOCK, {-1}, kNeckShortcut}, {23, R::DETECT, {16, 19, 22}, false}};
+// v10/yolov10{n,s}.yaml: SCDown in place of the stride-2 Convs at 5 / 7 / 20, PSA = model.10, C2fCIB where the tensors say so (model.8
+// of scale s, model.22), v10Detect = model.23: YOLO11's Detect layers twice (cv2 / cv3 and one2one_cv2 / one2one_cv3)
+inline constexpr R kYolo10[] = {
+    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},
+    {4, R::BLOCK, {-1}, true},      {5, R::SCDOWN, {-1}, false},      {6, R::BLOCK, {-1}, true},       {7, R::SCDOWN, {-1}, false},
+    {8, R::BLOCK, {-1}, true},      {9, R::SPPF, {-1}, false},        {10, R::PSA, {-1}, false},       {11, R::UPSAMPLE, {-1}, false},
+    {12, R::CONCAT, {-1, 6}, false}, {13, R::BLOCK, {-1}, false},     {14, R::UPSAMPLE, {-1}, false},  {15, R::CONCAT, {-1, 4}, false},
+    {16, R::BLOCK, {-1}, false},    {17, R::CONV, {-1}, false},       {18, R::CONCAT, {-1, 13}, false}, {19, R::BLOCK, {-1}, false},
+    {20, R::SCDOWN, {-1}, false},   {21, R::CONCAT, {-1, 10}, false}, {22, R::BLOCK, {-1}, true},      {23, R::DETECT, {16, 19, 22}, false}};
+// yolo11-cls.yaml: model.0-8 are yolo11.yaml's, C2PSA follows them directly (no SPPF) and is the embedded layer; Classify = model.10
+inline constexpr R kYolo11Cls[] = {
+    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},
+    {4, R::BLOCK, {-1}, true},      {5, R::CONV, {-1}, false},        {6, R::BLOCK, {-1}, true},       {7, R::CONV, {-1}, false},
+    {8, R::BLOCK, {-1}, true},      {9, R::C2PSA, {-1}, false}};
+template <int N> constexpr TrunkGraph graph_of(const R (&rows)[N], bool dw_cls) { return TrunkGraph{rows, N, dw_cls}; }
+}  // namespace tables
+
+}  // namespace gtx

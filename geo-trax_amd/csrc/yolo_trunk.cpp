@@ -3,7 +3,7 @@
 // decoder there; rows 0-8 are the YOLOv8-cls backbone of the ReID embedder), v8/yolov8-p2.yaml (kYolov8P2: one more stage at stride 4,
 // Detect = model.28) and 11/yolo11.yaml (kYolo11: C3k2 blocks, C2PSA = model.10, Detect = model.23). Channel widths, bottleneck counts
 // and c3k-or-not are read off the tensor shapes, so every scale (n/s/m/l/x) loads unchanged. A new family is one more table and one
-// more rule in choose_graph(); a new module is one more case in build(). The two classification graphs of the ReID embedder are
+// more rule in choose_graph(); a new module is one more case in build(). v10/yolov10.yaml is kYolo10 (SCDown, PSA = model.10, C2fCIB, v10Detect = model.23). The two classification graphs of the ReID embedder are
 // prefixes of these tables: yolov8-cls.yaml = kYolov8's rows 0-8, 11/yolo11-cls.yaml = kYolo11's rows 0-8 + C2PSA as model.9 (kYolo11Cls).
 #include "yolo_trunk.hpp"
 #include "rtdetr_kernels.hpp"
@@ -14,40 +14,7 @@
 namespace gtx {
 
 namespace {
-using R = TrunkRow;
-constexpr R kYolov8[] = {
-    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},
-    {4, R::BLOCK, {-1}, true},      {5, R::CONV, {-1}, false},        {6, R::BLOCK, {-1}, true},       {7, R::CONV, {-1}, false},
-    {8, R::BLOCK, {-1}, true},      {9, R::SPPF, {-1}, false},        {10, R::UPSAMPLE, {-1}, false},  {11, R::CONCAT, {-1, 6}, false},
-    {12, R::BLOCK, {-1}, false},    {13, R::UPSAMPLE, {-1}, false},   {14, R::CONCAT, {-1, 4}, false}, {15, R::BLOCK, {-1}, false},
-    {16, R::CONV, {-1}, false},     {17, R::CONCAT, {-1, 12}, false}, {18, R::BLOCK, {-1}, false},     {19, R::CONV, {-1}, false},
-    {20, R::CONCAT, {-1, 9}, false}, {21, R::BLOCK, {-1}, false},     {22, R::DETECT, {15, 18, 21}, false}};
-constexpr int kClsBackboneRows = 9;   // yolov8-cls.yaml: model.0-8 are yolov8.yaml's
-constexpr R kYolov8P2[] = {
-    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},
-    {4, R::BLOCK, {-1}, true},      {5, R::CONV, {-1}, false},        {6, R::BLOCK, {-1}, true},       {7, R::CONV, {-1}, false},
-    {8, R::BLOCK, {-1}, true},      {9, R::SPPF, {-1}, false},        {10, R::UPSAMPLE, {-1}, false},  {11, R::CONCAT, {-1, 6}, false},
-    {12, R::BLOCK, {-1}, false},    {13, R::UPSAMPLE, {-1}, false},   {14, R::CONCAT, {-1, 4}, false}, {15, R::BLOCK, {-1}, false},
-    {16, R::UPSAMPLE, {-1}, false}, {17, R::CONCAT, {-1, 2}, false},  {18, R::BLOCK, {-1}, false},     {19, R::CONV, {-1}, false},
-    {20, R::CONCAT, {-1, 15}, false}, {21, R::BLOCK, {-1}, false},    {22, R::CONV, {-1}, false},      {23, R::CONCAT, {-1, 12}, false},
-    {24, R::BLOCK, {-1}, false},    {25, R::CONV, {-1}, false},       {26, R::CONCAT, {-1, 9}, false}, {27, R::BLOCK, {-1}, false},
-    {28, R::DETECT, {18, 21, 24, 27}, false}};
-// YOLO11's shortcuts: on in the backbone; in the neck kNeckShortcut, which no tensor tells (taken as off, as in yolov8.yaml's neck;
-// tests/yolo11_ref.py names the doubt).
-constexpr bool kNeckShortcut = false;
-constexpr R kYolo11[] = {
-    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},
-    {4, R::BLOCK, {-1}, true},      {5, R::CONV, {-1}, false},        {6, R::BLOCK, {-1}, true},       {7, R::CONV, {-1}, false},
-    {8, R::BLOCK, {-1}, true},      {9, R::SPPF, {-1}, false},        {10, R::C2PSA, {-1}, false},     {11, R::UPSAMPLE, {-1}, false},
-    {12, R::CONCAT, {-1, 6}, false}, {13, R::BLOCK, {-1}, kNeckShortcut}, {14, R::UPSAMPLE, {-1}, false}, {15, R::CONCAT, {-1, 4}, false},
-    {16, R::BLOCK, {-1}, kNeckShortcut}, {17, R::CONV, {-1}, false},  {18, R::CONCAT, {-1, 13}, false}, {19, R::BLOCK, {-1}, kNeckShortcut},
-    {20, R::CONV, {-1}, false},     {21, R::CONCAT, {-1, 10}, false}, {22, R::BLOCK, {-1}, kNeckShortcut}, {23, R::DETECT, {16, 19, 22}, false}};
-// yolo11-cls.yaml: model.0-8 are yolo11.yaml's, C2PSA follows them directly (no SPPF) and is the embedded layer; Classify = model.10
-constexpr R kYolo11Cls[] = {
-    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},
-    {4, R::BLOCK, {-1}, true},      {5, R::CONV, {-1}, false},        {6, R::BLOCK, {-1}, true},       {7, R::CONV, {-1}, false},
-    {8, R::BLOCK, {-1}, true},      {9, R::C2PSA, {-1}, false}};
-template <int N> constexpr TrunkGraph graph_of(const R (&rows)[N], bool dw_cls) { return TrunkGraph{rows, N, dw_cls}; }
+using namespace tables;
 }  // namespace
 
 TrunkGraph YoloTrunk::cls_backbone() { return TrunkGraph{kYolov8, kClsBackboneRows, false}; }
@@ -60,6 +27,9 @@ TrunkGraph YoloTrunk::choose_cls_graph() const {
 
 // Which yaml the tensors were built from, told apart by their names like the reference's model yaml does
 TrunkGraph YoloTrunk::choose_graph() const {
+  // yolov10.yaml: PSA's attention directly under model.10, SCDown's depthwise model.5.cv2 and a one-to-one head at model.23
+  if (net_.has("model.10.attn.qkv.conv.weight") && net_.has("model.5.cv2.conv.weight") && net_.has("model.23.one2one_cv2.0.0.conv.weight"))
+    return graph_of(kYolo10, true);
   // yolo11.yaml: C2PSA at model.10 and Detect (depthwise class branch) at model.23 -- names no YOLOv8 file has
   if (net_.has("model.10.m.0.attn.qkv.conv.weight") && net_.has("model.23.cv3.0.0.0.conv.weight")) return graph_of(kYolo11, true);
   // yolov8-p2.yaml: Detect = model.28 on four levels; else yolov8.yaml (Detect, or YOLOv8-RTDETR's decoder, = model.22)
@@ -167,14 +137,16 @@ View YoloTrunk::c3k(const std::string& m, const View& src, const View& dst, bool
 View YoloTrunk::c2f(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src) {
   const int c = (int)net_.tensor(pfx + ".cv1.conv.weight").shape[0] / 2;
   int n = 0;
-  while (net_.has(pfx + ".m." + std::to_string(n) + ".cv1.conv.weight")) ++n;
+  while (net_.has(pfx + ".m." + std::to_string(n) + ".cv1.conv.weight") || net_.has(pfx + ".m." + std::to_string(n) + ".cv1.0.conv.weight")) ++n;
   View cat = net_.new_view(x.h, x.w, (2 + n) * c);
   View first = cat.slice(0, 2 * c);
   conv(pfx + ".cv1.conv", x, 1, &first, nullptr, up_src);
   for (int k = 0; k < n; ++k) {
     const std::string m = pfx + ".m." + std::to_string(k);
     View src = cat.slice((1 + k) * c, c), dst = cat.slice((2 + k) * c, c);
-    if (net_.has(m + ".cv3.conv.weight")) c3k(m, src, dst, shortcut); else bottleneck(m, src, dst, shortcut);
+    if (net_.has(m + ".cv1.0.conv.weight")) cib(m, src, dst, shortcut);                       // C2fCIB (yolov10.yaml)
+    else if (net_.has(m + ".cv3.conv.weight")) c3k(m, src, dst, shortcut);
+    else bottleneck(m, src, dst, shortcut);
   }
   View out = conv(pfx + ".cv2.conv", cat, 1, out_slice, nullptr);
   net_.set_layer_view(pfx, out);
@@ -184,17 +156,17 @@ View YoloTrunk::c2f(const std::string& pfx, const View& x, bool shortcut, const 
 // C2PSA: cv1 -> a | b; per PSABlock b += proj(attention(qkv(b)) + pe(v)), b += ffn.1(ffn.0(b)); cv2 on cat(a, b). The convolutions
 // without activation take the residual in their epilogue (activation first, then the residual: x + conv(x)). The last block
 // writes b back into cv1's buffer, which cv2 then reads whole.
-View YoloTrunk::c2psa(const std::string& pfx, const View& x, const View* out_slice) {
+View YoloTrunk::c2psa(const std::string& pfx, const View& x, const View* out_slice, bool bare) {
   const int c = (int)net_.tensor(pfx + ".cv1.conv.weight").shape[0] / 2;
   GTX_CHECK(c % 64 == 0, "%s: %d hidden channels are not whole 64-wide attention heads", pfx.c_str(), c);
   const int heads = c / 64;
-  int n = 0;
-  while (net_.has(pfx + ".m." + std::to_string(n) + ".attn.qkv.conv.weight")) ++n;
+  int n = bare ? 1 : 0;
+  while (!bare && net_.has(pfx + ".m." + std::to_string(n) + ".attn.qkv.conv.weight")) ++n;
   GTX_CHECK(n > 0, "%s: no PSABlock", pfx.c_str());
   View ab = conv(pfx + ".cv1.conv", x, 1, nullptr, nullptr);
   View b = ab.slice(c, c);
   for (int k = 0; k < n; ++k) {
-    const std::string m = pfx + ".m." + std::to_string(k);
+    const std::string m = bare ? pfx : pfx + ".m." + std::to_string(k);
     const HostTensor &wq = net_.tensor(m + ".attn.qkv.conv.weight"), &wp = net_.tensor(m + ".attn.pe.conv.weight");
     GTX_CHECK((int)wq.shape[0] == heads * 128 && wp.shape.size() == 4 && (int)wp.shape[0] == c && wp.shape[1] == 1 && wp.shape[2] == 3,
               "%s: attention of %d heads with key_dim 32 / head_dim 64 expected", m.c_str(), heads);
@@ -229,27 +201,51 @@ View YoloTrunk::c2psa(const std::string& pfx, const View& x, const View* out_sli
   return out;
 }
 
-View YoloTrunk::dwconv(const std::string& name, const View& x, int act) {
+View YoloTrunk::dwconv(const std::string& name, const View& x, int act, int stride, const View* out_slice, const View* residual) {
   const HostTensor& w = net_.tensor(name + ".weight");
   const int c = x.c;
-  GTX_CHECK(w.shape.size() == 4 && (int)w.shape[0] == c && w.shape[1] == 1 && w.shape[2] == 3 && w.shape[3] == 3 && c % 8 == 0,
-            "%s: expected a depthwise 3x3 convolution on %d channels", name.c_str(), c);
-  std::vector<float> wt((size_t)9 * c), bias(c, 0.f);
-  for (int ch = 0; ch < c; ++ch)
-    for (int t = 0; t < 9; ++t) wt[(size_t)t * c + ch] = w.data[(size_t)ch * 9 + t];
+  GTX_CHECK(w.shape.size() == 4 && (int)w.shape[0] == c && w.shape[1] == 1 && (w.shape[2] == 3 || w.shape[2] == 7) && w.shape[3] == w.shape[2] && c % 8 == 0,
+            "%s: expected a depthwise 3x3 or 7x7 convolution on %d channels", name.c_str(), c);
+  const int k = (int)w.shape[2], taps = k * k;
+  GTX_CHECK(stride == 1 || (stride == 2 && k == 3), "%s: stride %d", name.c_str(), stride);
+  std::vector<float> wt = dw_tap_major(w.data.data(), c, taps), bias(c, 0.f);
   if (const float* pb = net_.bias_of(name, c)) std::copy(pb, pb + c, bias.begin());
+  const int ho = (x.h - 1) / stride + 1, wo = (x.w - 1) / stride + 1;
   Op op;
   op.kind = Op::DWCONV;
   op.name = name;
-  op.family = c % 32 == 0 ? "rt_dwconv_tile_kernel<3>" : "rt_dwconv_kernel<3>";     // launch_rt_dwconv's rule
+  op.family = std::string(stride == 1 && c % 32 == 0 ? "rt_dwconv_tile_kernel<" : "rt_dwconv_kernel<") + (k == 3 ? "3>" : "7>");     // launch_rt_dwconv's rule
   op.in = x;
-  op.out = net_.new_view(x.h, x.w, c);
+  op.out = out_slice ? *out_slice : net_.new_view(ho, wo, c);
+  GTX_CHECK(op.out.h == ho && op.out.w == wo && op.out.c == c, "%s: the output slice does not fit", name.c_str());
+  if (residual) {
+    GTX_CHECK(residual->h == ho && residual->w == wo && residual->c == c, "%s: the residual does not fit", name.c_str());
+    op.dw_res = *residual;
+  }
   op.dw_w = net_.upload(wt); op.dw_bias = net_.upload(bias);
-  op.dw_act = act;
+  op.dw_act = act; op.dw_k = k; op.dw_stride = stride;
   op.sat = net_.sat_flag();
   ops_.push_back(op);
   net_.set_layer_view(name, op.out);
   return op.out;
+}
+
+// CIB(c, c, shortcut, e = 1.0, lk): dw3x3 -> 1x1 c -> 2c -> dw3x3 (lk: the fused RepVGGDW, one dw7x7) -> 1x1 2c -> c -> dw3x3, SiLU after
+// each; src -> dst (+ src, in the last depthwise layer's epilogue after its activation)
+View YoloTrunk::cib(const std::string& m, const View& src, const View& dst, bool shortcut) {
+  const View d0 = dwconv(m + ".cv1.0.conv", src, 1);
+  const View p1 = conv_act(m + ".cv1.1.conv", d0, 1, nullptr, nullptr);
+  const View d2 = dwconv(m + ".cv1.2.conv", p1, 1);
+  const View p3 = conv_act(m + ".cv1.3.conv", d2, 1, nullptr, nullptr);
+  return dwconv(m + ".cv1.4.conv", p3, 1, 1, &dst, shortcut ? &src : nullptr);
+}
+
+// SCDown(c1, c2, 3, 2): cv2(cv1(x)), cv1 = 1x1 Conv + SiLU, cv2 = depthwise 3x3 stride 2 without activation
+View YoloTrunk::scdown(const std::string& pfx, const View& x, const View* out_slice) {
+  const View a = conv(pfx + ".cv1.conv", x, 1, nullptr, nullptr);
+  const View out = dwconv(pfx + ".cv2.conv", a, 0, 2, out_slice);
+  net_.set_layer_view(pfx, out);
+  return out;
 }
 
 // ---- layer 0: the stem (dedicated 3-channel kernel). front: also the weights packed for fuse_stem()
@@ -304,16 +300,15 @@ YoloTrunk::Levels YoloTrunk::build(const View& img, const TrunkGraph& g, bool fr
   auto from = [&](const TrunkRow& r, int k) { return r.from[k] < 0 ? r.i + r.from[k] : r.from[k]; };   // row 0: -1, the image
   auto n_from = [](const TrunkRow& r) { int k = 0; while (k < 4 && r.from[k] != 0) ++k; return k; };
 
+  GTX_CHECK(trunk_table_error(g.rows, n) < 0, "internal: layer table row %d", trunk_table_error(g.rows, n));
   // ---- output width of every row; the Concat (at most one) that lists it and its channel offset there
   std::vector<int> width(n, 0), cat_of(n, -1), cat_off(n, 0);
   bool fuse_up = net_.format() == DT_F32S;
   for (int i = 0; i < n; ++i) {
     const TrunkRow& r = g.rows[i];
-    GTX_CHECK(r.i == i && n_from(r) >= 1, "internal: layer table row %d", i);
-    for (int k = 0; k < n_from(r); ++k) GTX_CHECK(from(r, k) < i && (from(r, k) >= 0 || i == 0), "internal: model.%d reads a later layer", i);
     switch (r.mod) {
       case TrunkRow::CONV: width[i] = cout_of(name(i) + ".conv"); break;
-      case TrunkRow::BLOCK: case TrunkRow::SPPF: case TrunkRow::C2PSA: width[i] = cout_of(name(i) + ".cv2.conv"); break;
+      case TrunkRow::BLOCK: case TrunkRow::SPPF: case TrunkRow::C2PSA: case TrunkRow::SCDOWN: case TrunkRow::PSA: width[i] = cout_of(name(i) + ".cv2.conv"); break;
       case TrunkRow::UPSAMPLE:
         // torch's Upsample + Concat in front of a block: the split-f16x3 path reads the low-resolution tensor in place from the
         // block's first 1x1 conv (ConvProblem::in2) when every such tensor of the graph is whole 32-channel groups (all or nothing),
@@ -369,6 +364,8 @@ YoloTrunk::Levels YoloTrunk::build(const View& img, const TrunkGraph& g, bool fr
         break;
       }
       case TrunkRow::C2PSA: out[i] = c2psa(name(i), x, place(i, x.h, x.w)); break;
+      case TrunkRow::PSA: out[i] = c2psa(name(i), x, place(i, x.h, x.w), true); break;
+      case TrunkRow::SCDOWN: out[i] = scdown(name(i), x, place(i, (x.h - 1) / 2 + 1, (x.w - 1) / 2 + 1)); break;
       case TrunkRow::UPSAMPLE: {
         const View* s = place(i, 2 * x.h, 2 * x.w);
         GTX_CHECK(s && cat_off[i] == 0, "internal: Upsample model.%d must lead a Concat", i);
@@ -551,10 +548,13 @@ void YoloTrunk::run_op(const Op& op, int nb, hipStream_t s) const {
       launch_upsample2x(dtype_, op.in.ptr, nb, op.in.h, op.in.w, op.in.c, op.in.cstride, op.in.coff, op.out.ptr,
                         op.out.cstride, op.out.coff, s);
       break;
-    case Op::DWCONV:
+    case Op::DWCONV: {
+      const RtMap res{op.dw_res.ptr, op.dw_res.h, op.dw_res.w, op.dw_res.cstride, op.dw_res.coff, op.dw_res.c};
       launch_rt_dwconv(fmt, RtMap{op.in.ptr, op.in.h, op.in.w, op.in.cstride, op.in.coff, op.in.c},
-                       RtMap{op.out.ptr, op.out.h, op.out.w, op.out.cstride, op.out.coff, op.out.c}, nb, 3, 1, op.dw_w, op.dw_bias, op.dw_act, op.sat, s);
+                       RtMap{op.out.ptr, op.out.h, op.out.w, op.out.cstride, op.out.coff, op.out.c}, nb, op.dw_k, op.dw_stride, op.dw_w, op.dw_bias, op.dw_act,
+                       op.sat, s, op.dw_res.ptr ? &res : nullptr);
       break;
+    }
     case Op::ATTN:
       launch_psa_attention(fmt, RtMap{op.in.ptr, op.in.h, op.in.w, op.in.cstride, op.in.coff, op.in.c},
                            RtMap{op.out.ptr, op.out.h, op.out.w, op.out.cstride, op.out.coff, op.out.c}, nb, op.heads, op.dw_w, op.dw_bias, op.sat, s);
@@ -601,8 +601,8 @@ void set_batch_ops(std::vector<Op>& ops, int nb, size_t es, bool pad_skip_on) {
       op.flops = 0;
       op.bytes = (double)nb * op.in.h * op.in.w * op.in.c * 5 * es;
     } else if (op.kind == Op::DWCONV) {
-      op.flops = 2.0 * 9 * nb * op.in.h * op.in.w * op.in.c;
-      op.bytes = 2.0 * nb * op.in.h * op.in.w * op.in.c * es;
+      op.flops = 2.0 * op.dw_k * op.dw_k * nb * op.out.h * op.out.w * op.in.c;
+      op.bytes = (double)nb * ((double)op.in.h * op.in.w + (double)op.out.h * op.out.w * (op.dw_res.ptr ? 2 : 1)) * op.in.c * es;
     } else if (op.kind == Op::ATTN) {               // q.k (depth 32) + p.v (width 64) per query-key pair and head, + pe; the qkv map in, the output map out
       const double T = (double)op.in.h * op.in.w;
       op.flops = nb * (op.heads * T * T * 2.0 * (32 + 64) + 2.0 * 9 * T * op.out.c);

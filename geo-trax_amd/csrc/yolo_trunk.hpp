@@ -1,5 +1,5 @@
 // The YOLO trunk: everything in front of the Detect layer of ultralytics' yolov8.yaml (model.0-21), yolov8-p2.yaml (model.0-27) and
-// yolo11.yaml (model.0-22), and the YOLOv8-cls (model.0-8) and YOLO11-cls (model.0-9) backbones. Each graph is a constant table with one row per yaml layer
+// yolo11.yaml / yolov10.yaml (model.0-22), and the YOLOv8-cls (model.0-8) and YOLO11-cls (model.0-9) backbones. Each graph is a constant table with one row per yaml layer
 // (yolo_trunk.cpp); one walk over a table emits its launches into the caller's op list. Every family that runs a trunk builds
 // through it: the YOLOv8 / P2 / YOLO11 detector (Detect on its outputs, detector.cpp), YOLOv8-RTDETR (an RTDETRDecoder on model.15 /
 // 18 / 21, rtdetr.cpp) and the ReID embedder (reid.cpp). It also owns the fused front (stem + model.1 + model.2.cv1 in one launch on
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "net_runtime.hpp"
+#include "yolo_tables.hpp"
 
 namespace gtx {
 
@@ -24,27 +25,16 @@ struct Op : OpInfo {
   float stem_scale = 1.f;      // split-f16x3 stem: inverse of the weights' power-of-two scaling
   const void* front_wpk = nullptr;   // the same weights packed for the front stage of model.1 (ConvProblem::front_w)
   float front_scale = 1.f;
-  // DWCONV (depthwise 3x3 on `in` -> `out`; act 0 none, 1 SiLU) / ATTN (C2PSA's attention on the qkv map `in`, dw_w / dw_bias = its pe)
-  const float* dw_w = nullptr;       // [9][C] tap-major
+  // DWCONV (depthwise dw_k x dw_k, stride dw_stride, on `in` -> `out`; act 0 none, 1 SiLU; dw_res: added after the activation when it
+  // has a buffer) / ATTN (C2PSA's attention on the qkv map `in`, dw_w / dw_bias = its pe)
+  const float* dw_w = nullptr;       // [k * k][C] tap-major
   const float* dw_bias = nullptr;
   int dw_act = 0, heads = 0;
+  int dw_k = 3, dw_stride = 1;
+  View dw_res;
   int* sat = nullptr;                // the net's saturation flag (split-f16x3 path)
   // rows of the output that depend on the frame (Detector::plan_pad_skip), as tile rows per group member; count 0 = all
   int ty_first[kMaxGroup] = {0}, ty_count[kMaxGroup] = {0};
-};
-
-// One row of a trunk's layer table: a layer of the model yaml, as the yaml writes it
-struct TrunkRow {
-  enum Module { CONV, BLOCK, SPPF, C2PSA, UPSAMPLE, CONCAT, DETECT };
-  int i;            // the layer index: its tensors are "model.<i>.*"
-  Module mod;       // CONV: Conv 3x3 stride 2 (row 0: the stem); BLOCK: C2f / C3k2 (which one, the tensors tell)
-  int from[4];      // the yaml's `from`: -1 = the row above (row 0: the image), else a layer index; 0 ends the list
-  bool shortcut;    // BLOCK: the bottlenecks add their input
-};
-struct TrunkGraph {
-  const TrunkRow* rows;
-  int n;
-  bool dw_cls;      // yolo11.yaml's Detect: the class branch is DWConv + 1x1 Conv twice
 };
 
 // N of every conv op (and the rows it computes) and every op's flops / bytes for a pass at batch nb (es: bytes per activation)
@@ -58,10 +48,10 @@ class YoloTrunk {
   struct Levels {
     std::vector<View> in;        // the Detect row's inputs, finest level first (a table without one: its last layer's output)
     std::vector<float> strides;  // net height / level height
-    std::string det_pfx;         // the Detect row: model.22 (yolov8.yaml), model.28 (yolov8-p2.yaml) or model.23 (yolo11.yaml)
+    std::string det_pfx;         // the Detect row: model.22 (yolov8.yaml), model.28 (yolov8-p2.yaml) or model.23 (yolo11.yaml, yolov10.yaml)
     bool dw_cls = false;         // TrunkGraph::dw_cls
   };
-  // The graph the tensors were built from, by their names: yolo11.yaml, yolov8-p2.yaml, else yolov8.yaml
+  // The graph the tensors were built from, by their names: yolov10.yaml, yolo11.yaml, yolov8-p2.yaml, else yolov8.yaml
   TrunkGraph choose_graph() const;
   static TrunkGraph cls_backbone();   // model.0-8 of yolov8.yaml = yolov8-cls.yaml's backbone
   // The classification graph the tensors were built from: yolo11-cls.yaml (model.0-8 of yolo11.yaml + C2PSA = model.9), else cls_backbone()
@@ -83,8 +73,10 @@ class YoloTrunk {
   // p is the placeholder of a released buffer that no layer_output() has re-created yet (no device address)
   bool hidden(const void* p) const;
   void clear() { unfused_.clear(); hidden_.clear(); }
-  // Depthwise 3x3 convolution "<name>.weight" [C][1][3][3] (+ bias), stride 1, SiLU or no activation (YOLO11's DWConv, used by its Detect)
-  View dwconv(const std::string& name, const View& x, int act);
+  // Depthwise convolution "<name>.weight" [C][1][k][k] (+ bias), k = 3 or 7 read off the tensor, stride 1 or 2, SiLU or no activation
+  // (YOLO11's DWConv, used by its Detect; YOLOv10's SCDown and CIB). out_slice: where it writes (null: a view of its own);
+  // residual: added after the activation
+  View dwconv(const std::string& name, const View& x, int act, int stride = 1, const View* out_slice = nullptr, const View* residual = nullptr);
 
  private:
   View stem(const View& img, bool front);
@@ -93,7 +85,9 @@ class YoloTrunk {
   View conv_act(const std::string& name, const View& x, int act, const View* out_slice, const View* residual);
   View bottleneck(const std::string& m, const View& src, const View& dst, bool shortcut);
   View c3k(const std::string& m, const View& src, const View& dst, bool shortcut);
-  View c2psa(const std::string& pfx, const View& x, const View* out_slice);
+  View c2psa(const std::string& pfx, const View& x, const View* out_slice, bool bare = false);   // bare: PSA, the one block's tensors directly under pfx
+  View cib(const std::string& m, const View& src, const View& dst, bool shortcut);
+  View scdown(const std::string& pfx, const View& x, const View* out_slice);
   void upsample(const std::string& name, const View& src, const View& dst);
   void sppf(const std::string& pfx, const View& x, const View& out);
   void fuse_front();         // model.1 (3x3 stride 2) + model.2.cv1 (1x1) as one launch on the split-f16x3 path

@@ -33,6 +33,7 @@ class DetConfig(C.Structure):
         ("agnostic_nms", C.c_int), ("half", C.c_int), ("rect", C.c_int), ("nc", C.c_int),
         ("n_classes", C.c_int), ("classes", C.c_int * 80), ("max_batch", C.c_int),
         ("frame_h", C.c_int), ("frame_w", C.c_int), ("fp32_split", C.c_int), ("obj_feats", C.c_int), ("arch", C.c_int),
+        ("end2end", C.c_int),
     ]
 
 
@@ -104,6 +105,7 @@ _SIGNATURES = {
     "gtx_op_conv_xcd_ranges": (C.c_int, [C.c_int, _P, _P, _P, _P]),
     "gtx_op_sppf_pool": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gtx_op_upsample2x": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
+    "gtx_op_dwconv": (C.c_int, [_P] + [C.c_int] * 7 + [_P, _P, _P, C.c_int, _P, _P, _P]),
     "gtx_op_psa_attention": (C.c_int, [_P] + [C.c_int] * 6 + [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "gtx_gmc_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),

@@ -42,12 +42,34 @@ class Detections:
             if len(b) else np.zeros((0, 4), np.float32)
 
 
+def resolve_end2end(graph: str, tensors: dict, end2end: bool | None) -> bool:
+    """Which head a detector of `graph` runs under `ultralytics.end2end` (null = the checkpoint's own): True = YOLOv10's one-to-one
+    head + top-300 cut, False = Detect + NMS. Raises for end2end: true with a family that has no such head, and for end2end: false
+    with a YOLOv10 file that no longer holds its one-to-many branches."""
+    from .weights import yolov10_has_one2many
+
+    if graph != "yolov10":
+        if end2end:
+            raise ValueError(f"end2end: true needs a checkpoint with an end-to-end (one-to-one) head; this one is {graph}, of the implemented "
+                             f"families only YOLOv10 has one (leave end2end empty)")
+        return False
+    if end2end is None or end2end:
+        return True
+    if not yolov10_has_one2many(tensors):
+        raise ValueError("end2end: false runs YOLOv10's one-to-many branches (model.23.cv2 / cv3) through NMS, but this file holds only the "
+                         "one-to-one head (a fused ultralytics export drops them; tools/convert_weights.py keeps them)")
+    return False
+
+
 class Detector:
     def __init__(self, tensors: dict[str, np.ndarray], frame_hw: tuple[int, int], *, imgsz: int = 1920,
                  conf: float = 0.25, iou: float = 0.7, max_det: int = 1000, classes=None,
                  agnostic_nms: bool = True, half: bool = False, rect: bool = False, max_batch: int = 1,
-                 fp32_split: bool | None = None, obj_feats: bool = False, ctx: _lib.Context | None = None):
-        """obj_feats: keep one appearance vector per box (Detections.feats; include/gtx.h gtx_det_config.obj_feats).
+                 fp32_split: bool | None = None, obj_feats: bool = False, end2end: bool | None = None, ctx: _lib.Context | None = None):
+        """end2end (ultralytics.end2end, default.yaml:250): None = the checkpoint's own head -- YOLOv10's one-to-one head without NMS
+        (the 300 best (anchor, class) scores; iou / agnostic_nms are not read), Detect + NMS for every other family; False runs a
+        YOLOv10 file's one-to-many branches (cv2 / cv3) through Detect + NMS; True with another family raises.
+        obj_feats: keep one appearance vector per box (Detections.feats; include/gtx.h gtx_det_config.obj_feats).
         half=False (the reference default, default.yaml:245) computes at fp32 grade: fp32 activations in HBM and
         either the exact-fp32 MFMA (fp32_split=False) or the split-f16x3 convolutions (fp32_split=True: hi + lo fp16
         operands, three fp16 MFMAs per product, fp32 accumulate; csrc/conv_igemm_split.hip). fp32_split=None takes
@@ -64,12 +86,17 @@ class Detector:
         if self.rtdetr and obj_feats:
             raise NotImplementedError("RT-DETR: obj_feats (ReID `model: auto`) is not implemented")
         self.p2 = self.graph == "yolov8-p2"   # yolov8-p2.yaml: a fourth Detect level at stride 4, Detect = model.28
-        nc = int(tensors[head + (".enc_score_head.weight" if self.rtdetr else ".cv3.0.2.weight")].shape[0])
+        self.end2end = resolve_end2end(self.graph, tensors, end2end)
+        if self.end2end and obj_feats:
+            raise NotImplementedError("with_reid: true, model: auto reads the Detect layer's inputs at the boxes NMS keeps; not implemented for YOLOv10's "
+                                      "end-to-end head (a separate network works: `model: yolo11n-cls.safetensors`, or run the file with end2end: false)")
+        nc = int(tensors[head + (".enc_score_head.weight" if self.rtdetr else ".one2one_cv3.0.2.weight" if self.end2end else ".cv3.0.2.weight")].shape[0])
         self.ctx = ctx or _lib.default_context()
         lib = self.ctx.lib
         cfg = DetConfig(imgsz=imgsz, conf=conf, iou=iou, max_det=max_det, agnostic_nms=int(agnostic_nms),
                         half=int(half), rect=int(rect), nc=nc, n_classes=0, max_batch=max_batch,
-                        frame_h=frame_hw[0], frame_w=frame_hw[1], fp32_split=int(self.fp32_split), obj_feats=int(bool(obj_feats)), arch=int(self.rtdetr))
+                        frame_h=frame_hw[0], frame_w=frame_hw[1], fp32_split=int(self.fp32_split), obj_feats=int(bool(obj_feats)), arch=int(self.rtdetr),
+                        end2end=int(self.end2end))
         self.obj_feats = bool(obj_feats)
         if classes is not None:
             classes = list(classes)
@@ -81,7 +108,7 @@ class Detector:
         check(lib.gtx_detector_create(self.ctx.handle, C.byref(cfg), C.byref(h)))
         self.handle = h
         for name, arr in tensors.items():
-            if name.endswith("dfl.conv.weight") or ".bn." in name:
+            if name.endswith("dfl.conv.weight") or ".bn." in name or name == "detector.meta":
                 continue
             a = np.ascontiguousarray(arr, dtype=np.float32)
             shape = (C.c_int64 * a.ndim)(*a.shape)

@@ -122,6 +122,8 @@ def _engine_kwargs(config: dict) -> tuple[dict, dict | None, dict]:
     det_kw = dict(imgsz=int(max(imgsz) if isinstance(imgsz, (list, tuple)) else imgsz), conf=float(ul.get('conf') or 0.1),
                   iou=float(ul.get('iou', 0.7)), max_det=int(ul.get('max_det', 300)), classes=ul.get('classes'),
                   agnostic_nms=bool(ul.get('agnostic_nms', False)), half=bool(ul.get('half', False)), rect=bool(ul.get('rect', False)))   # absent -> the reference config's value (default.yaml:300)
+    if ul.get('end2end') is not None:                     # ultralytics.end2end (default.yaml:250): null = the checkpoint's own head (Detector)
+        det_kw['end2end'] = bool(ul['end2end'])
     eng_cfg = config['main'].get('engine') or {}
     if eng_cfg.get('fp32_split') is not None:             # `engine: {fp32_split: false}` in the config: the exact-fp32 MFMA convolutions
         det_kw['fp32_split'] = bool(eng_cfg['fp32_split'])   # instead of split-f16x3 (half: false only; default: GTX_FP32_SPLIT or on)

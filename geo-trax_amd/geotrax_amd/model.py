@@ -95,7 +95,7 @@ class Results:
         return len(self.boxes)
 
 
-_PREDICT_KEYS = ("imgsz", "conf", "iou", "max_det", "classes", "agnostic_nms", "half", "rect")
+_PREDICT_KEYS = ("imgsz", "conf", "iou", "max_det", "classes", "agnostic_nms", "half", "rect", "end2end")
 
 
 class YOLO:
@@ -124,7 +124,12 @@ class YOLO:
         graph, head = detector_topology(self.tensors)     # refuses an RT-DETR layout this build does not run
         self.is_rtdetr = graph in ("rtdetr-l", "yolov8-rtdetr")
         self.is_p2 = graph == "yolov8-p2"
-        nc = int(self.tensors[head + (".enc_score_head.weight" if self.is_rtdetr else ".cv3.0.2.weight")].shape[0])
+        self.is_yolov10 = graph == "yolov10"
+        nc = int(self.tensors[head + (".enc_score_head.weight" if self.is_rtdetr else ".one2one_cv3.0.2.weight" if self.is_yolov10 else ".cv3.0.2.weight")].shape[0])
+        if self.is_yolov10:                               # ultralytics names the file by its scale: yolov10n.yaml / yolov10s.yaml
+            from .weights import check_yolov10
+
+            graph += check_yolov10(self.tensors)
         if not self.names:
             self.names = {i: str(i) for i in range(nc)}
         self.model = self            # ultralytics exposes .model.yaml_file; keep attribute access harmless
@@ -152,7 +157,8 @@ class YOLO:
             self._det = Detector(self.tensors, frame_hw, imgsz=int(imgsz), conf=float(kw.get("conf") or 0.1),
                                  iou=float(kw.get("iou", 0.7)), max_det=int(kw.get("max_det", 300)), classes=kw.get("classes"),
                                  agnostic_nms=bool(kw.get("agnostic_nms", False)), half=bool(kw.get("half", False)),
-                                 rect=bool(kw.get("rect", False)), fp32_split=self.fp32_split, obj_feats=bool(getattr(self, "_obj_feats", False)), ctx=self.ctx)   # absent -> the reference config's value (default.yaml:300)
+                                 rect=bool(kw.get("rect", False)), fp32_split=self.fp32_split, obj_feats=bool(getattr(self, "_obj_feats", False)),
+                                 end2end=kw.get("end2end"), ctx=self.ctx)   # absent -> the reference config's value (default.yaml:300)
             self._det_key = key
         return self._det
 
@@ -242,6 +248,9 @@ class YOLO:
         if self._obj_feats and self.is_rtdetr:
             raise NotImplementedError("with_reid: true, model: auto needs the YOLOv8 Detect layer's inputs; not implemented for RT-DETR "
                                       "(a separate network works: `model: yolo11n-cls.safetensors`)")
+        if self._obj_feats and self.is_yolov10 and kwargs.get("end2end") in (None, True):
+            raise NotImplementedError("with_reid: true, model: auto needs the boxes NMS keeps and the Detect layer's inputs; not implemented for YOLOv10's "
+                                      "end-to-end head (a separate network works: `model: yolo11n-cls.safetensors`)")
         frame = np.ascontiguousarray(source, dtype=np.uint8)
         d = self._detector(frame.shape[:2], kwargs).detect(frame)
         res = Results(Boxes(d.xyxy, d.conf, d.cls, None), d.speed, frame.shape[:2], self.names)

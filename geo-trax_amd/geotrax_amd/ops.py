@@ -136,6 +136,26 @@ def psa_attention(qkv: np.ndarray, pe_w: np.ndarray, pe_b: np.ndarray, heads: in
     return out, bool(sat.value), (ms.value if iters > 0 else None)
 
 
+def dwconv(x: np.ndarray, w: np.ndarray, bias: np.ndarray, *, stride: int = 1, act: int = 1, residual: np.ndarray | None = None,
+           split: bool = False, ctx=None):
+    """Depthwise k x k convolution (k = 3, 5, 7; pad k / 2) + bias + activation (0 none, 1 SiLU, 2 ReLU) + residual after the
+    activation. x [n, h, w, c]; w [c, 1, k, k] (the conv's own layout); residual [n, ho, wo, c]. split=True (float32 arrays): the
+    pair format on the device (GTX_F32S). Returns (out, saturated)."""
+    ctx = ctx or _lib.default_context()
+    x = np.ascontiguousarray(x)
+    n, h, wd, c = x.shape
+    k = int(w.shape[-1])
+    wt = np.ascontiguousarray(np.asarray(w, np.float32).reshape(c, k * k).T)     # tap-major
+    b = np.ascontiguousarray(bias, dtype=np.float32)
+    out = np.zeros((n, (h - 1) // stride + 1, (wd - 1) // stride + 1, c), x.dtype)
+    r = None if residual is None else np.ascontiguousarray(residual, dtype=x.dtype)
+    assert r is None or r.shape == out.shape
+    sat = C.c_int()
+    check(ctx.lib.gtx_op_dwconv(ctx.handle, GTX_F32S if split else _dt(x), n, h, wd, c, k, stride, ptr(x), ptr(wt), ptr(b), int(act), ptr(r), ptr(out),
+                                C.byref(sat)))
+    return out, bool(sat.value)
+
+
 def preprocess(frame_bgr: np.ndarray, net_h: int, net_w: int, dtype=np.float32, want_gray: bool = True, ctx=None):
     """Letterbox + BGR->RGB + /255 into [net_h,net_w,4] (RGB0) and the half-res gray image."""
     ctx = ctx or _lib.default_context()

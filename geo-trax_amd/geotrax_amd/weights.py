@@ -52,6 +52,8 @@ def load_weights(path: str | Path) -> dict[str, np.ndarray]:
     t = load_file(str(path))
     t = {k: np.asarray(v, dtype=np.float32) for k, v in t.items()}
     t = fold_bn(t)
+    if any(".one2one_cv2." in k for k in t):               # a YOLOv10 file stored unfused: its RepVGGDW pairs become the fused model's one 7x7
+        t = fold_repvggdw(t)
     if is_rtdetr(t):
         t = fold_input_proj(fuse_repconv(t))
     return t
@@ -146,6 +148,32 @@ YOLO11_YAML = [
     (-1, 2, "C3k2", (1024, True)),                         # 22
     ((16, 19, 22), 1, "Detect", ("nc",)),                  # 23: the class branch is DWConv + Conv(1x1) twice
 ]
+YOLOV10_YAML = [                                           # v10/yolov10s.yaml; yolov10n.yaml has a C2f at row 8 (_yolov10_table)
+    (-1, 1, "Conv", (64, 3, 2)),
+    (-1, 1, "Conv", (128, 3, 2)),
+    (-1, 3, "C2f", (128, True)),
+    (-1, 1, "Conv", (256, 3, 2)),
+    (-1, 6, "C2f", (256, True)),
+    (-1, 1, "SCDown", (512, 3, 2)),
+    (-1, 6, "C2f", (512, True)),
+    (-1, 1, "SCDown", (1024, 3, 2)),
+    (-1, 3, "C2fCIB", (1024, True, True)),                 # 8: (c2, shortcut, lk)
+    (-1, 1, "SPPF", (1024, 5)),                            # 9
+    (-1, 1, "PSA", (1024,)),                               # 10
+    _UP,
+    ((-1, 6), 1, "Concat", (1,)),
+    (-1, 3, "C2f", (512,)),                                # 13
+    _UP,
+    ((-1, 4), 1, "Concat", (1,)),
+    (-1, 3, "C2f", (256,)),                                # 16
+    (-1, 1, "Conv", (256, 3, 2)),
+    ((-1, 13), 1, "Concat", (1,)),
+    (-1, 3, "C2f", (512,)),                                # 19
+    (-1, 1, "SCDown", (512, 3, 2)),
+    ((-1, 10), 1, "Concat", (1,)),
+    (-1, 3, "C2fCIB", (1024, True, True)),                 # 22
+    ((16, 19, 22), 1, "v10Detect", ("nc",)),               # 23: YOLO11's Detect layers twice (cv2 / cv3, one2one_cv2 / one2one_cv3)
+]
 YOLOV8_CLS_YAML = _V8_BACKBONE + [(-1, 1, "Classify", ("nc",))]
 YOLO11_CLS_YAML = YOLO11_YAML[:9] + [                      # model.0-8 of yolo11.yaml; no SPPF
     (-1, 2, "C2PSA", (1024,)),                             # 9
@@ -168,20 +196,27 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False) -> list[tuple[
     def conv(name, cin, cout, k, act=True):
         specs.append((name, (cout, cin, k, k), act))
 
-    def dwconv(name, c, act):
-        specs.append((name, (c, 1, 3, 3), act))
+    def dwconv(name, c, act, k=3):
+        specs.append((name, (c, 1, k, k), act))
 
     def bottleneck(p, c, e):
         conv(p + ".cv1.conv", c, int(c * e), 3)
         conv(p + ".cv2.conv", int(c * e), c, 3)
 
-    def c2f(pfx, cin, cout, n, c3k=None, e=0.5):
-        """C2f (c3k None: full-width Bottlenecks) or C3k2 (half-width Bottlenecks, or C3k blocks of two Bottlenecks when c3k)."""
+    def c2f(pfx, cin, cout, n, c3k=None, e=0.5, cib=None):
+        """C2f (c3k None: full-width Bottlenecks) or C3k2 (half-width Bottlenecks, or C3k blocks of two Bottlenecks when c3k) or
+        C2fCIB (cib = lk: CIB blocks of full hidden width; lk: the middle depthwise layer is the fused RepVGGDW, one 7x7)."""
         c = int(cout * e)
         conv(f"{pfx}.cv1.conv", cin, 2 * c, 1)
         for k in range(n):
             m = f"{pfx}.m.{k}"
-            if c3k:
+            if cib is not None:                            # CIB(c, c, shortcut, e=1.0, lk): dw3 -> 1x1 c->2c -> dw3 / dw7 -> 1x1 2c->c -> dw3, SiLU after each
+                dwconv(m + ".cv1.0.conv", c, True)
+                conv(m + ".cv1.1.conv", c, 2 * c, 1)
+                dwconv(m + ".cv1.2.conv", 2 * c, True, 7 if cib else 3)
+                conv(m + ".cv1.3.conv", 2 * c, c, 1)
+                dwconv(m + ".cv1.4.conv", c, True)
+            elif c3k:
                 h = int(c * 0.5)
                 conv(m + ".cv1.conv", c, h, 1)
                 conv(m + ".cv2.conv", c, h, 1)
@@ -192,22 +227,22 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False) -> list[tuple[
                 bottleneck(m, c, 1.0 if c3k is None else 0.5)
         conv(f"{pfx}.cv2.conv", (2 + n) * c, cout, 1)
 
-    def detect(d, chans):
+    def detect(d, chans, box="cv2", cls="cv3"):
         cb = max(16, chans[0] // 4, 64)
         cc = max(chans[0], min(nc, 100))
         for l, cin in enumerate(chans):
-            conv(f"{d}.cv2.{l}.0.conv", cin, cb, 3)
-            conv(f"{d}.cv2.{l}.1.conv", cb, cb, 3)
-            specs.append((f"{d}.cv2.{l}.2", (64, cb, 1, 1), False))
+            conv(f"{d}.{box}.{l}.0.conv", cin, cb, 3)
+            conv(f"{d}.{box}.{l}.1.conv", cb, cb, 3)
+            specs.append((f"{d}.{box}.{l}.2", (64, cb, 1, 1), False))
             if dw_cls:
-                dwconv(f"{d}.cv3.{l}.0.0.conv", cin, True)
-                conv(f"{d}.cv3.{l}.0.1.conv", cin, cc, 1)
-                dwconv(f"{d}.cv3.{l}.1.0.conv", cc, True)
-                conv(f"{d}.cv3.{l}.1.1.conv", cc, cc, 1)
+                dwconv(f"{d}.{cls}.{l}.0.0.conv", cin, True)
+                conv(f"{d}.{cls}.{l}.0.1.conv", cin, cc, 1)
+                dwconv(f"{d}.{cls}.{l}.1.0.conv", cc, True)
+                conv(f"{d}.{cls}.{l}.1.1.conv", cc, cc, 1)
             else:
-                conv(f"{d}.cv3.{l}.0.conv", cin, cc, 3)
-                conv(f"{d}.cv3.{l}.1.conv", cc, cc, 3)
-            specs.append((f"{d}.cv3.{l}.2", (nc, cc, 1, 1), False))
+                conv(f"{d}.{cls}.{l}.0.conv", cin, cc, 3)
+                conv(f"{d}.{cls}.{l}.1.conv", cc, cc, 3)
+            specs.append((f"{d}.{cls}.{l}.2", (nc, cc, 1, 1), False))
 
     for i, (frm, n, mod, args) in enumerate(table):
         src = [out[f if f >= 0 else i + f] for f in ((frm,) if isinstance(frm, int) else frm)] if i else [3]
@@ -237,6 +272,23 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False) -> list[tuple[
                 conv(m + ".ffn.0.conv", c, 2 * c, 1)
                 conv(m + ".ffn.1.conv", 2 * c, c, 1, act=False)
             conv(pfx + ".cv2.conv", 2 * c, out[i], 1)
+        elif mod == "C2fCIB":
+            out.append(ch(args[0]))
+            c2f(pfx, cin, out[i], n, cib=bool(args[2]) if len(args) > 2 else False)
+        elif mod == "SCDown":                              # cv1: 1x1 Conv + SiLU; cv2: depthwise 3x3 stride 2, no activation
+            out.append(ch(args[0]))
+            conv(pfx + ".cv1.conv", cin, out[i], 1)
+            dwconv(pfx + ".cv2.conv", out[i], False)
+        elif mod == "PSA":                                 # C2PSA's one block directly under the layer: heads = c / 64, key_dim 32
+            out.append(ch(args[0]))
+            c = cin // 2
+            conv(pfx + ".cv1.conv", cin, 2 * c, 1)
+            conv(pfx + ".attn.qkv.conv", c, c + 2 * (c // 64) * 32, 1, act=False)
+            conv(pfx + ".attn.proj.conv", c, c, 1, act=False)
+            dwconv(pfx + ".attn.pe.conv", c, False)
+            conv(pfx + ".ffn.0.conv", c, 2 * c, 1)
+            conv(pfx + ".ffn.1.conv", 2 * c, c, 1, act=False)
+            conv(pfx + ".cv2.conv", 2 * c, out[i], 1)
         elif mod == "Upsample":
             out.append(cin)
         elif mod == "Concat":
@@ -244,6 +296,10 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False) -> list[tuple[
         elif mod == "Detect":
             out.append(0)
             detect(pfx, src)
+        elif mod == "v10Detect":                           # the one-to-many pair, then its copy with weights of its own
+            out.append(0)
+            detect(pfx, src)
+            detect(pfx, src, "one2one_cv2", "one2one_cv3")
         elif mod == "Classify":
             out.append(nc)
             conv(pfx + ".conv.conv", cin, 1280, 1)
@@ -305,7 +361,7 @@ def _draw_yolov8(rng, specs, cls_bias: float = -4.0, gain: float = 1.7, box_deca
             mix = t[name + ".weight"][:, :, 1:2, 1:2] * np.float32(np.sqrt(shape[2] * shape[3]))   # keeps the output variance for smooth inputs
             t[name + ".weight"] = np.broadcast_to(mix / np.float32(shape[2] * shape[3]), shape).astype(np.float32).copy()
         b = rng.standard_normal(shape[0]) * 0.05
-        last = re.fullmatch(r"model\.\d+\.cv([23])\.(\d+)\.2", name)   # Detect's closing 1x1 of the box (cv2) / class (cv3) branch of level l
+        last = re.fullmatch(r"model\.\d+\.(?:one2one_)?cv([23])\.(\d+)\.2", name)   # Detect's closing 1x1 of the box (cv2) / class (cv3) branch of level l (v10Detect: of either pair)
         if last and last.group(1) == "3":
             b = b + cls_bias + float(level_bias[int(last.group(2))])
         if last and last.group(1) == "2":
@@ -407,6 +463,146 @@ def synthetic_yolo11(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: flo
     proj, pe, ffn.1, Detect's last 1x1s); a depthwise layer's fan-in is its 9 taps."""
     return _draw_yolov8(np.random.default_rng(seed), yolo11_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias, box_weight_scale)
 
+# --------------------------------------------------------------------------- YOLOv10 (cfg/models/v10/yolov10{n,s}.yaml)
+# What `YOLO("yolov10s.pt")` fine-tunes to: the YOLOv8 backbone and neck with SCDown (1x1 Conv, then a depthwise 3x3 stride 2 without
+# activation) in place of the stride-2 Convs at 5 / 7 / 20, PSA (C2PSA's one block directly under the layer) = model.10, C2fCIB (C2f whose
+# m.{k} are CIBs: dw3 -> 1x1 -> dw3 or the fused RepVGGDW's dw7 -> 1x1 -> dw3) at model.22 and, from scale s on, model.8, and v10Detect =
+# model.23 on [16, 19, 22]: YOLO11's Detect layers twice, cv2 / cv3 (one-to-many, trained with NMS in mind) and one2one_cv2 / one2one_cv3
+# (the NMS-free head inference uses: the 300 best (anchor, class) scores, V10_MAX_DET). Restated from ultralytics' public source; not
+# checked against the package (it is not installed).
+
+YOLOV10_SCALES = {"n": (0.33, 0.25, 1024), "s": (0.33, 0.50, 1024)}   # yolov10{n,s}.yaml: depth, width, max_channels
+
+YOLOV10_TOPOLOGY = ("yolov10 detect (yolov10{n,s}: SCDown = model.5 / 7 / 20, PSA = model.10, C2fCIB where the tensors say so, "
+                    "v10Detect = model.23 on model.16 / 19 / 22 with its one2one_cv2 / one2one_cv3 head)")
+
+V10_MAX_DET = 300   # Detect.max_det: the rows v10Detect.postprocess keeps, whatever the predictor's max_det (csrc: kV10Keep)
+
+_V10_BIGGER = {48: "yolov10m", 64: "yolov10b / yolov10l", 80: "yolov10x"}   # model.0's width of the scales that are not implemented
+
+
+def _yolov10_table(scale: str):
+    """yolov10<scale>.yaml as a table: scale n keeps a plain C2f at model.8."""
+    t = list(YOLOV10_YAML)
+    if scale == "n":
+        t[8] = (-1, 3, "C2f", (1024, True))
+    return t
+
+
+def is_yolov10(tensors: dict) -> bool:
+    """True when the names hold what only a YOLOv10 file has: attention directly under model.10 (`model.10.attn.qkv`: PSA; C2PSA has
+    `model.10.m.0.attn`), SCDown's depthwise `model.5.cv2.conv` and a one-to-one head (`.one2one_cv2.`). Which graph it is, and
+    whether this build runs it: check_yolov10()."""
+    w = tensors.get("model.5.cv2.conv.weight")
+    return ("model.10.attn.qkv.conv.weight" in tensors and w is not None and np.ndim(w) == 4 and np.shape(w)[1] == 1
+            and any(".one2one_cv2." in k for k in tensors))
+
+
+def check_yolov10(tensors: dict) -> str:
+    """The scale ("n" / "s") of a fused yolov10.yaml detect model; raises NotImplementedError for every other arrangement of its blocks
+    (a cv4 / proto branch, attention elsewhere, Detect elsewhere, anything past model.23, another width). Strict like check_yolo11():
+    the table is rebuilt from what the tensors tell (repeats, C2f or C2fCIB per block row, large-kernel or not) and every shape is
+    compared. The one-to-many pair cv2 / cv3 may be missing as a whole (ultralytics' fuse() drops it)."""
+    no = NotImplementedError(f"checkpoint with YOLOv10's blocks (PSA, SCDown, a one-to-one head) in another arrangement than yolov10.yaml's: of that "
+                             f"family only {YOLOV10_TOPOLOGY} is implemented")
+    shape = lambda n: tuple(np.shape(tensors[n])) if n in tensors else None
+    c0 = shape("model.0.conv.weight")
+    if c0 is None:
+        raise no
+    if c0[0] in _V10_BIGGER:
+        raise NotImplementedError(f"{_V10_BIGGER[c0[0]]} (model.0 has {c0[0]} channels): of the YOLOv10 scales only n and s are implemented ({YOLOV10_TOPOLOGY})")
+    scale = {16: "n", 32: "s"}.get(c0[0])
+    if scale is None:
+        raise no
+    layer = lambda k: int(k.split(".")[1]) if k.startswith("model.") and k.split(".")[1].isdigit() else -1
+    table = []
+    for i, (frm, n, mod, args) in enumerate(YOLOV10_YAML):
+        if mod in ("C2f", "C2fCIB"):
+            cib = f"model.{i}.m.0.cv1.0.conv.weight" in tensors
+            first = f"model.{i}.m.0." + ("cv1.0.conv.weight" if cib else "cv1.conv.weight")
+            if first not in tensors:
+                raise no
+            lk = cib and (shape(f"model.{i}.m.0.cv1.2.conv.weight") or (0, 0, 0))[2] == 7
+            table.append((frm, n, "C2fCIB", (args[0], args[1] if len(args) > 1 else False, lk)) if cib else (frm, n, "C2f", args[:2]))
+        else:
+            table.append((frm, n, mod, args))
+    nc_w = shape("model.23.one2one_cv3.0.2.weight")
+    if nc_w is None:
+        raise no
+    want = _scaled_specs(table, YOLOV10_SCALES, scale, nc_w[0], dw_cls=True)
+    many = [n for n, _, _ in want if n.startswith(("model.23.cv2.", "model.23.cv3."))]
+    have_many = [n + ".weight" in tensors for n in many]
+    if any(have_many) and not all(have_many):
+        raise no
+    names = set()
+    for name, shp, _ in want:
+        if name in many and not have_many[0]:
+            continue
+        names.add(name)
+        if shape(name + ".weight") != shp:
+            raise no
+    for k in tensors:
+        i = layer(k)
+        if i < 0:
+            continue
+        if i > 23 or (".attn." in k and i != 10):
+            raise no
+        if i == 23 and k.split(".")[2] == "dfl":
+            continue
+        if k.endswith(".weight") and k[: -len(".weight")] not in names:
+            raise no
+    return scale
+
+
+def yolov10_has_one2many(tensors: dict) -> bool:
+    """True when the file kept v10Detect's one-to-many pair (cv2 / cv3), which `end2end: false` runs through Detect + NMS."""
+    return "model.23.cv2.0.0.conv.weight" in tensors and "model.23.cv3.0.2.weight" in tensors
+
+
+def yolov10_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
+    """(tensor name, OIHW shape, has_act) for every conv of a fused YOLOv10 detect model (depthwise convs: (C, 1, k, k); the fused
+    RepVGGDW of a large-kernel CIB: (C, 1, 7, 7) at m.{k}.cv1.2.conv), both head pairs included."""
+    return _scaled_specs(_yolov10_table(scale), YOLOV10_SCALES, scale, nc, dw_cls=True)
+
+
+def synthetic_yolov10(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0, gain: float = 1.7,
+                      box_decay: float | tuple = 0.3, level_bias: tuple = (0.0, 0.0, 0.0), box_weight_scale: float = 0.3) -> dict[str, np.ndarray]:
+    """Seeded random fused weights of the YOLOv10 architecture, drawn like synthetic_yolo11's (same knobs, the draws in the order of
+    yolov10_layer_specs). Both head pairs are emitted, cv2 / cv3 first, each with draws of its own, so the two heads detect
+    different things; the knobs shape both alike."""
+    return _draw_yolov8(np.random.default_rng(seed), yolov10_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias, box_weight_scale)
+
+
+def detector_meta(tensors: dict) -> dict | None:
+    """The optional `detector.meta` tensor tools/convert_weights.py writes for a YOLOv10 file: [family 10, one-to-many pair kept,
+    end-to-end head, the head's row count]; None when the file has none."""
+    m = tensors.get("detector.meta")
+    if m is None or np.size(m) < 4:
+        return None
+    m = np.asarray(m).ravel()
+    return dict(family={10: "yolov10"}.get(int(m[0]), str(int(m[0]))), one2many=bool(m[1]), end2end=bool(m[2]), max_det=int(m[3]))
+
+
+def fold_repvggdw(t: dict[str, np.ndarray]) -> dict[str, np.ndarray]:
+    """RepVGGDW.fuse on BN-folded tensors: `X.conv.conv` (depthwise 7x7) + `X.conv1.conv` (depthwise 3x3, zero-padded to 7x7) ->
+    `X.conv` (one depthwise 7x7; biases summed), the fused model's name for it. fp64 sums, fp32 result."""
+    out = dict(t)
+    for k in list(t):
+        if not k.endswith(".conv1.conv.weight"):
+            continue
+        p = k[: -len(".conv1.conv.weight")]
+        w3, w7 = t[k], t.get(p + ".conv.conv.weight")
+        if w7 is None or w3.shape[1:] != (1, 3, 3) or w7.shape[1:] != (1, 7, 7) or w3.shape[0] != w7.shape[0]:
+            continue
+        w = w7.astype(np.float64).copy()
+        w[:, :, 2:5, 2:5] += w3.astype(np.float64)
+        zero = np.zeros(w3.shape[0], np.float32)
+        b = t.get(p + ".conv.conv.bias", zero).astype(np.float64) + t.get(p + ".conv1.conv.bias", zero).astype(np.float64)
+        for q in (".conv.conv.weight", ".conv.conv.bias", ".conv1.conv.weight", ".conv1.conv.bias"):
+            out.pop(p + q, None)
+        out[p + ".conv.weight"], out[p + ".conv.bias"] = w.astype(np.float32), b.astype(np.float32)
+    return out
+
 
 def calibrate_cls_bias(tensors: dict[str, np.ndarray], raw_logits: np.ndarray, conf: float, target: int) -> dict[str, np.ndarray]:
     """Returns a copy of `tensors` whose class-logit biases are shifted by one constant so that
@@ -444,10 +640,15 @@ RTDETR_TOPOLOGIES = ("rtdetr-l (HGNetv2 + AIFI + CCFM, RTDETRDecoder = model.28)
 
 def detector_topology(tensors: dict) -> tuple[str, str]:
     """(graph, head prefix) of a detector checkpoint, read off the tensor names the way the reference reads its model yaml:
-    ("yolov8", "model.22"), ("yolov8-p2", "model.28"), ("yolo11", "model.23"), ("rtdetr-l", "model.28") or ("yolov8-rtdetr", "model.22").
+    ("yolov8", "model.22"), ("yolov8-p2", "model.28"), ("yolo11", "model.23"), ("yolov10", "model.23"), ("rtdetr-l", "model.28") or
+    ("yolov8-rtdetr", "model.22").
     An RT-DETR layout other than those two (rtdetr-x with its decoder at model.32, ResNet backbones, ...) raises NotImplementedError,
-    and so does a file with YOLO11's blocks (attention, a depthwise Detect class branch) in another arrangement than yolo11.yaml's."""
+    and so does a file with YOLO11's or YOLOv10's blocks (attention, a depthwise Detect class branch, SCDown + a one-to-one head) in
+    another arrangement than their yaml's."""
     if not is_rtdetr(tensors):
+        if is_yolov10(tensors):
+            check_yolov10(tensors)                         # raises for another arrangement, and for the scales that are not implemented
+            return "yolov10", "model.23"
         if has_yolo11_blocks(tensors):
             check_yolo11(tensors)                          # raises for YOLO12 / YOLO26 / yolo11-cls, -seg, -obb, -pose ...
             return "yolo11", "model.23"

@@ -51,7 +51,8 @@ extern "C" {
  *    gtx_op_estimate_affine_partial added (GMC methods orb / sift).
  * 10: gtx_ecc_* added (GMC method ecc); gtx_fgmc_* (GMC method orb, stream-ordered) and gtx_gray_half_dev added: new entry
  *     points only, no struct or existing signature changed, so the number stays. gtx_op_psa_attention added and the embedder takes
- *     YOLO11-cls tensors (C2PSA = model.9): the same, the number stays. */
+ *     YOLO11-cls tensors (C2PSA = model.9): the same, the number stays. gtx_det_config.end2end appended at the struct's end (YOLOv10's
+ *     one-to-one head; 0 = every earlier behaviour) and gtx_op_dwconv added: the number stays. */
 #define GTX_ABI_VERSION 10
 
 typedef enum gtx_status {
@@ -215,6 +216,13 @@ int gtx_op_psa_attention(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int
                          int in_coff, const float* pe_w, const float* pe_b, void* out, int out_cstride, int out_coff, int form,
                          int iters, float* ms_per_launch, int* saturated);
 
+/* Depthwise k x k convolution (k = 3, 5 or 7; stride 1 or 2; pad k / 2) + bias + activation (0 none, 1 SiLU, 2 ReLU) + optional residual
+ * added after the activation: x [n][h][w][c], w [k * k][c] tap-major, bias [c], res (or NULL) and out [n][ho][wo][c], c % 8 == 0. Host
+ * arrays: fp16 (GTX_F16) or plain fp32 (GTX_F32; GTX_F32S: converted to the pair format on the way). *saturated: the launch clamped a
+ * value to fp16's range (GTX_F32S). Channel counts that are multiples of 32 take the LDS-tiled kernel at stride 1. */
+int gtx_op_dwconv(gtx_ctx* ctx, int dtype, int n, int h, int w, int c, int k, int stride, const void* x, const float* wt, const float* bias,
+                  int act, const void* res, void* out, int* saturated);
+
 /* Brute-force L2 2-nearest-neighbour search of unit-norm 128-d float descriptors (RootSIFT): what
  * cv2.BFMatcher(NORM_L2).knnMatch(query, train, k=2) returns inside stabilo for the orthophoto
  * registration (geotrax/utils/registration.py:59-85, matcher_name='bf'). query [nq][128], train
@@ -263,6 +271,11 @@ typedef struct gtx_det_config {
                      * (RTDETRPredictor.pre_transform: scale_fill), iou / agnostic_nms / rect are not read, obj_feats must be 0; half = 1: fp16 maps and
                      * weights on the fp16 MFMA convolutions, the token side (AIFI, the decoder's queries) stays fp32;
                      * gtx_detector_raw_output returns [queries][4 + nc] = xywh normalised to the frame + class scores */
+  int end2end;      /* arch 0 only. 0: Detect's cv2 / cv3 branches + NMS. 1: YOLOv10's one-to-one head (`model.23.one2one_cv2 / one2one_cv3`,
+                     * ultralytics.end2end, default.yaml:250) and no NMS: per image the 300 (Detect.max_det) best (anchor, class) scores --
+                     * ties: the lower flat index anchor * nc + class first --, then score > conf, classes, the max_det cut, the scale to
+                     * the frame; iou / agnostic_nms are not read, obj_feats must be 0. The tensors tell the graph (yolov10.yaml: SCDown, PSA =
+                     * model.10, C2fCIB, v10Detect = model.23); gtx_detector_raw_output / _raw_logits return the branch that ran */
 } gtx_det_config;
 
 int gtx_detector_create(gtx_ctx* ctx, const gtx_det_config* cfg, gtx_detector** out);
@@ -323,7 +336,7 @@ int gtx_detector_fell_back(gtx_detector* det, int* fell_back);
 /* Default fp32 path: the Detect box branch (cv2[l][0], cv2[l][1]) is evaluated at the anchors that pass the score gate only, bit
  * for bit what the dense layers give there (csrc/head_sparse.hip; GTX_SPARSE_BOX=0 builds detectors without it). on = 1 when this
  * detector does so; overflows = collected batches with more candidates per image than its buffer holds (8192), which were
- * finished by the dense layers instead. */
+ * finished by the dense layers instead (end2end = 1: the branch is evaluated at the at most 300 entries the cut keeps, so none can). */
 int gtx_detector_sparse_box(gtx_detector* det, int* on, int* overflows);
 /* Letterbox-padding rows (ultralytics LetterBox with `rect: false`: 420 + 420 of 1920 input rows for a 16:9 frame): an activation row
  * out of reach of the frame's rows sees the same inputs for every frame, so its value is a constant of the checkpoint. The detector

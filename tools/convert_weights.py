@@ -21,6 +21,12 @@ go into the small `rtdetr.meta` tensor [heads, points, queries, AIFI heads].
 A YOLOv8-RTDETR checkpoint (yolov8<scale>-rtdetr.yaml, geo-trax's train.sh `-rt`: the YOLOv8 backbone and neck, RTDETRDecoder =
 model.22) takes the same branch ("rtdetr" is in its yaml name); with no AIFI its last `rtdetr.meta` entry falls back to 8 and is unused.
 
+A YOLOv10 detect checkpoint (yolov10{n,s}.yaml) is folded here and not by `model.fuse()`, which would drop v10Detect's one-to-many
+branches (`model.23.cv2 / cv3`): convert_state_dict() folds every Conv + BN pair, sums each RepVGGDW's 7x7 and zero-padded 3x3 branch
+(weights and BN-folded biases) into the single 7x7 of the fused model (`...cv1.2.conv.weight`), keeps cv2 / cv3 next to one2one_cv2 /
+one2one_cv3 -- `end2end: false` runs them through NMS -- and writes `detector.meta` = [family 10, one-to-many kept, end-to-end head,
+the head's 300].
+
 A YOLOv8-cls or YOLO11-cls checkpoint (the ReID network of `with_reid: true, model: <file>.safetensors` in a tracker yaml) is written the same
 way, plus `cls.meta` = [imgsz] from the checkpoint's training arguments (geotrax_amd.weights.cls_imgsz; 224 when absent).
 """
@@ -28,6 +34,25 @@ import sys
 from pathlib import Path
 
 import yaml
+
+
+def convert_state_dict(sd: dict) -> dict:
+    """An unfused YOLOv10 state_dict (numpy arrays under ultralytics' names) -> the flat fused tensors the library reads, plus
+    `detector.meta` (geotrax_amd.weights.detector_meta). Needs no ultralytics."""
+    import numpy as np
+
+    root = Path(__file__).resolve().parent.parent / "geo-trax_amd"
+    if str(root) not in sys.path:
+        sys.path.insert(0, str(root))
+    from geotrax_amd.weights import V10_MAX_DET, detector_topology, fold_bn, fold_repvggdw, yolov10_has_one2many
+
+    t = {k: np.asarray(v, np.float32) for k, v in sd.items() if "dfl" not in k and "num_batches_tracked" not in k}
+    t = fold_repvggdw(fold_bn(t))
+    graph, _ = detector_topology(t)
+    if graph != "yolov10":
+        raise ValueError(f"convert_state_dict folds YOLOv10 checkpoints; this one is {graph}")
+    t["detector.meta"] = np.asarray([10, float(yolov10_has_one2many(t)), 1, V10_MAX_DET], np.float32)
+    return t
 
 
 def main():
@@ -41,6 +66,14 @@ def main():
         from ultralytics import RTDETR
 
         yolo = RTDETR(str(src))                       # what the reference itself does (extract.py:223-225)
+    if any(".one2one_cv2." in k for k in yolo.model.state_dict()):   # YOLOv10: folded here, so that cv2 / cv3 survive
+        from safetensors.numpy import save_file as save_np
+
+        sd = convert_state_dict({k: v.detach().float().numpy() for k, v in yolo.model.float().eval().state_dict().items() if v.dtype.is_floating_point})
+        save_np(sd, str(dst))
+        dst.with_suffix(".names.yaml").write_text(yaml.safe_dump({int(k): str(v) for k, v in yolo.names.items()}))
+        print(f"wrote {dst} ({len(sd)} tensors, YOLOv10 with both head pairs) and {dst.with_suffix('.names.yaml')}")
+        return
     net = yolo.model.float().fuse().eval()
     sd = {k: v.detach().float().contiguous() for k, v in net.state_dict().items()
           if v.dtype.is_floating_point and "dfl" not in k and "num_batches_tracked" not in k}
