@@ -494,6 +494,251 @@ int gtx_op_dwconv(gtx_ctx* ctx, int dtype, int n, int h, int w, int c, int k, in
   });
 }
 
+// ---- RT-DETR's token-side kernels, one hook per launcher (tests/test_rtdetr_ops_gpu.py). Every size is checked here, before
+// anything touches the GPU: whatever a launcher's own GTX_CHECK would refuse, and whatever would let a kernel read or write
+// outside the arrays it is given.
+namespace {
+void rt_bad(const char* op, const char* what) { gtx::fail(GTX_ERR_INVALID, "%s: %s", op, what); }
+
+// Up to three levels of NHWC maps [n][h][w][cstride] with `c` channels read from coff
+struct RtLevelSet {
+  gtx::RtLevels L{};
+  gtx::DevBuf buf[3];
+  int S = 0;
+};
+void rt_levels_check(const char* op, int fmt, int n, int n_levels, const void* const* maps, const int* h, const int* w, const int* cstride,
+                     const int* coff, int c, bool allow_split) {
+  need(maps, "maps"); need(h, "h"); need(w, "w"); need(cstride, "cstride"); need(coff, "coff");
+  if (!(fmt == GTX_F16 || fmt == GTX_F32 || (allow_split && fmt == GTX_F32S))) rt_bad(op, "unsupported map format");
+  if (n < 1 || n_levels < 1 || n_levels > 3 || c < 1) rt_bad(op, "bad sizes");
+  long S = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    need(maps[l], "maps[l]");
+    if (h[l] < 1 || w[l] < 1 || coff[l] < 0 || (long)coff[l] + c > cstride[l]) rt_bad(op, "a level's channel slice does not fit its stride");
+    if (fmt == GTX_F32S && (cstride[l] % 8 || coff[l] % 8)) rt_bad(op, "pair-format maps need channel strides and offsets that are multiples of 8");
+    S += (long)h[l] * w[l];
+    if (S > (1l << 24) || (double)n * h[l] * w[l] * cstride[l] > 1e9) rt_bad(op, "maps too large");
+  }
+}
+void rt_levels_upload(RtLevelSet& s, int fmt, int n, int n_levels, const void* const* maps, const int* h, const int* w, const int* cstride,
+                      const int* coff) {
+  s.L.n_levels = n_levels;
+  std::vector<uint8_t> tmp;
+  for (int l = 0; l < n_levels; ++l) {
+    const size_t bytes = (size_t)n * h[l] * w[l] * cstride[l] * gtx::dtype_size(fmt);
+    s.buf[l].alloc(bytes);
+    const void* src = maps[l];
+    if (fmt == GTX_F32S) {                            // plain fp32 host arrays -> pair format on the device
+      tmp.resize(bytes);
+      gtx::f32_to_pairs(static_cast<const float*>(src), tmp.data(), bytes / 4);
+      src = tmp.data();
+    }
+    GTX_HIP(hipMemcpy(s.buf[l].p, src, bytes, hipMemcpyHostToDevice));
+    s.L.ptr[l] = s.buf[l].p; s.L.h[l] = h[l]; s.L.w[l] = w[l]; s.L.cstride[l] = cstride[l]; s.L.coff[l] = coff[l];
+    s.S += h[l] * w[l];
+  }
+}
+void rt_upload(gtx::DevBuf& d, const void* src, size_t bytes) {
+  d.alloc(bytes);
+  GTX_HIP(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+}
+}  // namespace
+
+int gtx_op_rt_linear(gtx_ctx* ctx, int M, int K, int Nout, const float* x, int ldx, const float* x2, int ldx2, int x2_cols, const float* w,
+                     const float* bias, const float* res, int ldr, float* y, int ldy, int ycol, int act) {
+  return guarded([&] {
+    const char* op = "rt_linear";
+    if (M < 1 || M > (1 << 20) || K < 16 || K % 16 || K > (1 << 16) || Nout < 16 || Nout % 16 || Nout > (1 << 16)) rt_bad(op, "M >= 1, K and Nout positive multiples of 16");
+    if (ldx < K || ldx % 4 || ldx > (1 << 20)) rt_bad(op, "ldx must hold K values and be a multiple of 4");
+    if (x2 && (ldx2 < K || ldx2 % 4 || ldx2 > (1 << 20) || x2_cols < 0 || (x2_cols % 64 && x2_cols < Nout)))
+      rt_bad(op, "the second addend needs ldx2 >= K, a multiple of 4, and x2_cols a multiple of 64 or all of Nout");
+    if (res && (ldr < Nout || ldr > (1 << 20))) rt_bad(op, "ldr must hold Nout values");
+    if (ycol < 0 || ldy > (1 << 20) || (long)ycol + Nout > ldy) rt_bad(op, "the output columns do not fit ldy");
+    if (act != 0 && act != 2 && act != 3) rt_bad(op, "act: 0 none, 2 ReLU, 3 GELU");
+    need(ctx, "ctx"); need(x, "x"); need(w, "w"); need(y, "y");
+    GTX_HIP(hipSetDevice(ctx->device));
+    gtx::DevBuf dx, dx2, dw, db, dr, dy;
+    rt_upload(dx, x, (size_t)M * ldx * 4);
+    if (x2) rt_upload(dx2, x2, (size_t)M * ldx2 * 4);
+    rt_upload(dw, w, (size_t)Nout * K * 4);
+    if (bias) rt_upload(db, bias, (size_t)Nout * 4);
+    if (res) rt_upload(dr, res, (size_t)M * ldr * 4);
+    rt_upload(dy, y, (size_t)M * ldy * 4);
+    gtx::RtLinear p{};
+    p.x = dx.as<float>(); p.ldx = ldx;
+    p.x2 = x2 ? dx2.as<float>() : nullptr; p.ldx2 = ldx2; p.x2_cols = x2_cols;
+    p.w = dw.as<float>(); p.bias = bias ? db.as<float>() : nullptr;
+    p.res = res ? dr.as<float>() : nullptr; p.ldr = ldr;
+    p.y = dy.as<float>() + ycol; p.ldy = ldy;
+    p.M = M; p.K = K; p.Nout = Nout; p.act = act;
+    gtx::launch_rt_linear(p, ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    GTX_HIP(hipMemcpy(y, dy.p, (size_t)M * ldy * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int gtx_op_rt_layernorm(gtx_ctx* ctx, int rows, int C, int in_fmt, const void* in, int in_cstride, int in_coff, int out_fmt, void* out,
+                        int out_cstride, int out_coff, const float* gamma, const float* beta, int* saturated) {
+  return guarded([&] {
+    const char* op = "rt_layernorm";
+    if (rows < 1 || rows > (1 << 22) || C < 8 || C % 8 || C > 1024) rt_bad(op, "rows >= 1, C a multiple of 8 up to 1024");
+    const bool pair_ok = (in_fmt == GTX_F32 && (out_fmt == GTX_F32 || out_fmt == GTX_F32S || out_fmt == GTX_F16)) ||
+                         (in_fmt == GTX_F32S && out_fmt == GTX_F32S) || (in_fmt == GTX_F16 && out_fmt == GTX_F16);
+    if (!pair_ok) rt_bad(op, "formats: F32 -> F32 / F32S / F16, F32S -> F32S, F16 -> F16");
+    if (in_coff < 0 || in_coff % 8 || in_cstride % 8 || in_cstride > (1 << 16) || (long)in_coff + C > in_cstride || out_coff < 0 || out_coff % 8 ||
+        out_cstride % 8 || out_cstride > (1 << 16) || (long)out_coff + C > out_cstride)
+      rt_bad(op, "channel strides / offsets must be multiples of 8 and hold C channels");
+    need(ctx, "ctx"); need(in, "in"); need(out, "out"); need(gamma, "gamma"); need(beta, "beta");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t xb = (size_t)rows * in_cstride * gtx::dtype_size(in_fmt), yb = (size_t)rows * out_cstride * gtx::dtype_size(out_fmt);
+    gtx::DevBuf dx(xb), dy(yb), dg, dbt, ds(4);
+    std::vector<uint8_t> tx, ty;
+    if (in_fmt == GTX_F32S) {                         // plain fp32 host arrays <-> pair format on the device
+      tx.resize(xb);
+      gtx::f32_to_pairs(static_cast<const float*>(in), tx.data(), xb / 4);
+    }
+    if (out_fmt == GTX_F32S) {
+      ty.resize(yb);
+      gtx::f32_to_pairs(static_cast<const float*>(out), ty.data(), yb / 4);
+    }
+    GTX_HIP(hipMemcpy(dx.p, in_fmt == GTX_F32S ? tx.data() : in, xb, hipMemcpyHostToDevice));
+    GTX_HIP(hipMemcpy(dy.p, out_fmt == GTX_F32S ? ty.data() : out, yb, hipMemcpyHostToDevice));
+    rt_upload(dg, gamma, (size_t)C * 4);
+    rt_upload(dbt, beta, (size_t)C * 4);
+    GTX_HIP(hipMemset(ds.p, 0, 4));
+    const gtx::RtRows ri{dx.p, in_cstride, in_coff, in_fmt}, ro{dy.p, out_cstride, out_coff, out_fmt};
+    gtx::launch_rt_layernorm(ri, ro, rows, C, dg.as<float>(), dbt.as<float>(), ds.as<int>(), ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    GTX_HIP(hipMemcpy(out_fmt == GTX_F32S ? ty.data() : out, dy.p, yb, hipMemcpyDeviceToHost));
+    if (out_fmt == GTX_F32S) gtx::pairs_to_f32(ty.data(), static_cast<float*>(out), yb / 4);
+    if (saturated) GTX_HIP(hipMemcpy(saturated, ds.p, 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int gtx_op_rt_mha(gtx_ctx* ctx, int n, int T, int C, int heads, const float* qkv, int ld, float* out, int ldo, int form) {
+  return guarded([&] {
+    const char* op = "rt_mha";
+    if (n < 1 || n > 1024 || T < 1 || T > (1 << 20) || heads < 1 || C < 1 || C % heads) rt_bad(op, "bad sizes");
+    const int d = C / heads;
+    if (d != 8 && d != 16 && d != 32) rt_bad(op, "head dimension 8, 16 or 32");
+    if (ld < 3 * C || ld % 4 || ld > (1 << 16) || ldo < C || ldo % 4 || ldo > (1 << 16)) rt_bad(op, "ld >= 3 C, ldo >= C, both multiples of 4");
+    if (form != 0 && form != 1) rt_bad(op, "form: 0 the library's rule, 1 the generic kernel");
+    need(ctx, "ctx"); need(qkv, "qkv"); need(out, "out");
+    GTX_HIP(hipSetDevice(ctx->device));
+    gtx::DevBuf dq, dout;
+    rt_upload(dq, qkv, (size_t)n * T * ld * 4);
+    rt_upload(dout, out, (size_t)n * T * ldo * 4);
+    gtx::launch_rt_mha(dq.as<float>(), ld, n, T, C, heads, dout.as<float>(), ldo, ctx->stream, form);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    GTX_HIP(hipMemcpy(out, dout.p, (size_t)n * T * ldo * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int gtx_op_rt_topk(gtx_ctx* ctx, int fmt, int n, int n_levels, const void* const* scores, const int* h, const int* w, const int* cstride,
+                   const int* coff, int nc, int nq, int* idx) {
+  return guarded([&] {
+    const char* op = "rt_topk";
+    rt_levels_check(op, fmt, n, n_levels, scores, h, w, cstride, coff, nc, false);
+    long S = 0;
+    for (int l = 0; l < n_levels; ++l) S += (long)h[l] * w[l];
+    if (nq < 1 || nq > 1024 || S < nq) rt_bad(op, "1..1024 queries, no more than there are anchors");
+    need(ctx, "ctx"); need(idx, "idx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    RtLevelSet lv;
+    rt_levels_upload(lv, fmt, n, n_levels, scores, h, w, cstride, coff);
+    gtx::DevBuf keys((size_t)n * lv.S * 4), di((size_t)n * nq * 4);
+    gtx::launch_rt_topk(fmt, lv.L, nc, n, nq, keys.as<unsigned>(), di.as<int>(), ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    GTX_HIP(hipMemcpy(idx, di.p, (size_t)n * nq * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int gtx_op_rt_gather_refer(gtx_ctx* ctx, int fmt, int n, int n_levels, const void* const* enc, const int* h, const int* w, const int* cstride,
+                           const int* coff, int C, int nq, const int* idx, const float* delta, int ldd, int mode, float* embed, float* anchors,
+                           float* refer) {
+  return guarded([&] {
+    const char* op = "rt_gather_refer";
+    if (mode != 0 && mode != 1) rt_bad(op, "mode 0 (gather + anchors) or 1 (inverse sigmoid of refer)");
+    if (n < 1 || nq < 1 || (long)n * nq > (1 << 20) || ldd < 4 || ldd > (1 << 16)) rt_bad(op, "bad sizes");
+    need(delta, "delta"); need(refer, "refer");
+    const int M = n * nq;
+    if (mode == 0) {
+      rt_levels_check(op, fmt, n, n_levels, enc, h, w, cstride, coff, C, true);
+      need(idx, "idx"); need(embed, "embed"); need(anchors, "anchors");
+      long S = 0;
+      for (int l = 0; l < n_levels; ++l) S += (long)h[l] * w[l];
+      for (int m = 0; m < M; ++m)
+        if (idx[m] < 0 || idx[m] >= S) rt_bad(op, "an anchor index is outside the level set");
+    }
+    need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    gtx::DevBuf dd, dr((size_t)M * 16 * 4);
+    rt_upload(dd, delta, (size_t)M * ldd * 4);
+    if (mode == 1) {
+      GTX_HIP(hipMemcpy(dr.p, refer, (size_t)M * 16 * 4, hipMemcpyHostToDevice));
+      gtx::launch_rt_refer(dd.as<float>(), ldd, nullptr, dr.as<float>(), M, 1, ctx->stream);
+    } else {
+      RtLevelSet lv;
+      rt_levels_upload(lv, fmt, n, n_levels, enc, h, w, cstride, coff);
+      gtx::DevBuf di, de((size_t)M * C * 4), da((size_t)M * 4 * 4);
+      rt_upload(di, idx, (size_t)M * 4);
+      GTX_HIP(hipMemset(dr.p, 0, (size_t)M * 16 * 4));
+      gtx::launch_rt_gather(fmt, lv.L, C, n, nq, di.as<int>(), de.as<float>(), da.as<float>(), ctx->stream);
+      gtx::launch_rt_refer(dd.as<float>(), ldd, da.as<float>(), dr.as<float>(), M, 0, ctx->stream);
+      GTX_HIP(hipStreamSynchronize(ctx->stream));
+      GTX_HIP(hipMemcpy(embed, de.p, (size_t)M * C * 4, hipMemcpyDeviceToHost));
+      GTX_HIP(hipMemcpy(anchors, da.p, (size_t)M * 4 * 4, hipMemcpyDeviceToHost));
+    }
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    GTX_HIP(hipMemcpy(refer, dr.p, (size_t)M * 16 * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int gtx_op_rt_deform(gtx_ctx* ctx, int fmt, int n, int n_levels, const void* const* value, const int* h, const int* w, const int* cstride,
+                     const int* coff, int hd, int nh, int npts, int nq, const float* offaw, const float* refer, float* out) {
+  return guarded([&] {
+    const char* op = "rt_deform";
+    if (hd < 1 || hd > 1024 || nh < 1 || hd % nh || npts < 1 || npts > 64 || nq < 1 || n < 1 || (long)n * nq > (1 << 20)) rt_bad(op, "bad sizes");
+    rt_levels_check(op, fmt, n, n_levels, value, h, w, cstride, coff, hd, true);
+    need(ctx, "ctx"); need(offaw, "offaw"); need(refer, "refer"); need(out, "out");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const int M = n * nq;
+    RtLevelSet lv;
+    rt_levels_upload(lv, fmt, n, n_levels, value, h, w, cstride, coff);
+    gtx::DevBuf dof, dr, dout((size_t)M * hd * 4);
+    rt_upload(dof, offaw, (size_t)M * nh * n_levels * npts * 3 * 4);
+    rt_upload(dr, refer, (size_t)M * 16 * 4);
+    gtx::launch_rt_deform(fmt, lv.L, hd, nh, npts, dof.as<float>(), dr.as<float>(), n, nq, dout.as<float>(), ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    GTX_HIP(hipMemcpy(out, dout.p, (size_t)M * hd * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int gtx_op_rt_post(gtx_ctx* ctx, int n, int nq, int nc, const float* logits, int ldl, const float* refer, float conf, uint64_t class_mask0,
+                   uint64_t class_mask1, int frame_w, int frame_h, int max_det, float* out_rows, int* out_n, float* raw) {
+  return guarded([&] {
+    const char* op = "rt_post";
+    if (nq < 1 || nq > 512) rt_bad(op, "1..512 queries");
+    if (nc < 1 || nc > 128) rt_bad(op, "1..128 classes (the class mask has two 64-bit words)");
+    if (n < 1 || n > 4096 || ldl < nc || ldl > (1 << 16) || max_det < 1 || max_det > (1 << 16) || frame_w < 1 || frame_h < 1) rt_bad(op, "bad sizes");
+    need(ctx, "ctx"); need(logits, "logits"); need(refer, "refer"); need(out_rows, "out_rows"); need(out_n, "out_n");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t M = (size_t)n * nq, rawb = M * (4 + nc) * 4, rowb = (size_t)n * max_det * 6 * 4;
+    gtx::DevBuf dl, dr, drows, dn((size_t)n * 4), draw(raw ? rawb : 16);
+    rt_upload(dl, logits, M * ldl * 4);
+    rt_upload(dr, refer, M * 16 * 4);
+    rt_upload(drows, out_rows, rowb);
+    GTX_HIP(hipMemset(dn.p, 0, (size_t)n * 4));
+    const unsigned long long mask[2] = {class_mask0, class_mask1};
+    gtx::launch_rt_post(dl.as<float>(), ldl, dr.as<float>(), n, nq, nc, conf, mask, frame_w, frame_h, max_det, drows.as<float>(), dn.as<int>(),
+                        raw ? draw.as<float>() : nullptr, ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    GTX_HIP(hipMemcpy(out_rows, drows.p, rowb, hipMemcpyDeviceToHost));
+    GTX_HIP(hipMemcpy(out_n, dn.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (raw) GTX_HIP(hipMemcpy(raw, draw.p, rawb, hipMemcpyDeviceToHost));
+  });
+}
+
 struct gtx_gmc {
   gtx_ctx* ctx;
   std::unique_ptr<gtx::Gmc> impl;
@@ -757,7 +1002,11 @@ int gtx_op_preprocess(gtx_ctx* ctx, int dtype, const uint8_t* frame, int h, int 
 
 int gtx_detector_create(gtx_ctx* ctx, const gtx_det_config* cfg, gtx_detector** out) {
   return guarded([&] {
-    need(ctx, "ctx"); need(cfg, "cfg"); need(out, "out");
+    need(cfg, "cfg"); need(out, "out");
+    // the class filter is a two-word mask: class 128 would shift past it. The YOLO path already refuses nc > 128 when it builds its
+    // head (net_runtime.cpp); RT-DETR had no such check, so for it this one is new
+    if (cfg->nc < 1 || cfg->nc > 128) gtx::fail(GTX_ERR_UNSUPPORTED, "gtx_det_config.nc %d: 1..128 classes", cfg->nc);
+    need(ctx, "ctx");
     std::unique_ptr<gtx_detector> d(new gtx_detector);
     if (cfg->arch == 1 && cfg->end2end) gtx::fail(-3, "gtx_det_config.end2end: the one-to-one head belongs to YOLOv10 (arch 0); RT-DETR has no NMS to leave out");
     if (cfg->arch == 1) d->impl.reset(new gtx::RtDetr(ctx, *cfg));

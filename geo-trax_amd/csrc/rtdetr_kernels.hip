@@ -1271,12 +1271,13 @@ void launch_rt_layernorm(const RtRows& in, const RtRows& out, long rows, int C, 
   GTX_HIP(hipGetLastError());
 }
 
-void launch_rt_mha(const float* qkv, int ld, int n, int T, int C, int heads, float* out, int ldo, hipStream_t s) {
+void launch_rt_mha(const float* qkv, int ld, int n, int T, int C, int heads, float* out, int ldo, hipStream_t s, int form) {
   const int d = C / heads;
   GTX_CHECK(C % heads == 0 && ld % 4 == 0 && ldo % 4 == 0, "rt_mha: C=%d heads=%d", C, heads);
+  GTX_CHECK(form == 0 || form == 1, "rt_mha: form %d", form);
   const dim3 grid(cdiv(T, 64), heads, n), block(256);
   static const bool mfma = [] { const char* e = getenv("GTX_RT_MHA_MFMA"); return !(e && e[0] == '0'); }();
-  if (d == 32 && mfma) hipLaunchKernelGGL(rt_mha32_kernel, grid, block, 0, s, qkv, ld, T, C, out, ldo);
+  if (d == 32 && mfma && form == 0) hipLaunchKernelGGL(rt_mha32_kernel, grid, block, 0, s, qkv, ld, T, C, out, ldo);
   else if (d == 32) hipLaunchKernelGGL(rt_mha_kernel<32>, grid, block, 0, s, qkv, ld, T, C, out, ldo);
   else if (d == 16) hipLaunchKernelGGL(rt_mha_kernel<16>, grid, block, 0, s, qkv, ld, T, C, out, ldo);
   else if (d == 8) hipLaunchKernelGGL(rt_mha_kernel<8>, grid, block, 0, s, qkv, ld, T, C, out, ldo);
@@ -1326,6 +1327,7 @@ void launch_rt_deform(int fmt, const RtLevels& value, int hd, int nh, int npts, 
 void launch_rt_post(const float* logits, int ldl, const float* refer, int n, int nq, int nc, float conf, const unsigned long long class_mask[2],
                     int frame_w, int frame_h, int max_det, float* out_rows, int* out_n, float* raw, hipStream_t s) {
   GTX_CHECK(nq <= 512, "rt_post: %d queries (at most 512)", nq);
+  GTX_CHECK(nc >= 1 && nc <= 128, "rt_post: %d classes (the class mask has two 64-bit words: 1..128)", nc);
   hipLaunchKernelGGL(rt_post_kernel, dim3(n), dim3(512), 0, s, logits, ldl, refer, nq, nc, conf, class_mask[0], class_mask[1], (float)frame_w, (float)frame_h,
                      max_det, out_rows, out_n, raw);
   GTX_HIP(hipGetLastError());

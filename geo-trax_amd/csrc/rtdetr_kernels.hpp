@@ -51,8 +51,10 @@ void launch_rt_linear(const RtLinear& p, hipStream_t s);
 struct RtRows { void* ptr; int cstride, coff; int fmt; };
 void launch_rt_layernorm(const RtRows& in, const RtRows& out, long rows, int C, const float* gamma, const float* beta, int* sat, hipStream_t s);
 
-// softmax(Q K^T / sqrt(d)) V per image and head on token rows: qkv [N * T][ld] with q at column 0, k at C, v at 2C
-void launch_rt_mha(const float* qkv, int ld, int n, int T, int C, int heads, float* out, int ldo, hipStream_t s);
+// softmax(Q K^T / sqrt(d)) V per image and head on token rows: qkv [N * T][ld] with q at column 0, k at C, v at 2C.
+// Head dimension 32 runs rt_mha32_kernel (the fp32 matrix pipe; GTX_RT_MHA_MFMA=0 turns it off), 16 and 8 the generic rt_mha_kernel<D>.
+// form: 0 = that rule, 1 = the generic kernel whatever D is (the operator-level hook's, for tests).
+void launch_rt_mha(const float* qkv, int ld, int n, int T, int C, int heads, float* out, int ldo, hipStream_t s, int form = 0);
 
 // ultralytics' Attention block (YOLO11's C2PSA) on maps in the path's activation format: qkv [N][h][w] with heads x [q 32 | k 32 | v 64]
 // channels, out [N][h][w][heads * 64] = softmax(q^T k * 32^-0.5) v over the h w positions + pe(v), pe a depthwise 3x3

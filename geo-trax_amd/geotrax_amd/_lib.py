@@ -78,7 +78,7 @@ class StabConfig(C.Structure):
 
 # name -> (restype, argtypes); kept in one table so tests can check the export list against
 # include/gtx.h.
-ABI_VERSION = 10       # GTX_ABI_VERSION of include/gtx.h
+ABI_VERSION = 11       # GTX_ABI_VERSION of include/gtx.h
 _P = C.c_void_p
 _SIGNATURES = {
     "gtx_abi_version": (C.c_int, []),
@@ -108,6 +108,13 @@ _SIGNATURES = {
     "gtx_op_dwconv": (C.c_int, [_P] + [C.c_int] * 7 + [_P, _P, _P, C.c_int, _P, _P, _P]),
     "gtx_op_psa_attention": (C.c_int, [_P] + [C.c_int] * 6 + [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "gtx_op_rt_linear": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int]),
+    "gtx_op_rt_layernorm": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_int)]),
+    "gtx_op_rt_mha": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int]),
+    "gtx_op_rt_topk": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "gtx_op_rt_gather_refer": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "gtx_op_rt_deform": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "gtx_op_rt_post": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_float, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "gtx_gmc_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "gtx_gmc_destroy": (None, [_P]),
     "gtx_gmc_reset": (C.c_int, [_P]),

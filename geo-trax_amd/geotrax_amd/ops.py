@@ -202,3 +202,141 @@ def conv_xcd_ranges(blocks, cin):
     grid = C.c_int()
     check(lib.gtx_op_conv_xcd_ranges(len(b), b.ctypes.data, c.ctypes.data, out.ctypes.data, C.addressof(grid)))
     return out, grid.value
+
+
+# ---------------------------------------------------------------------------- RT-DETR's token-side kernels (gtx_op_rt_*)
+def _f32(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _map_fmt(a: np.ndarray, split: bool) -> int:
+    if split and a.dtype != np.float32:
+        raise TypeError("split=True needs float32 maps")
+    return GTX_F32S if split else _dt(a)
+
+
+def _levels(maps, coff, split):
+    """Level maps [n, h, w, cstride] -> the hooks' per-level arrays. Returns (kept arrays, fmt, n, L, ptrs, h, w, cstride, coff)."""
+    maps = [np.ascontiguousarray(m) for m in maps]
+    L = len(maps)
+    coff = [coff] * L if np.isscalar(coff) else list(coff)
+    assert 1 <= L <= 3 and len(coff) == L and all(m.ndim == 4 and m.dtype == maps[0].dtype and m.shape[0] == maps[0].shape[0] for m in maps)
+    ptrs = (C.c_void_p * L)(*[m.ctypes.data for m in maps])
+    ints = lambda v: (C.c_int * L)(*[int(i) for i in v])
+    return (maps, _map_fmt(maps[0], split), maps[0].shape[0], L, ptrs, ints(m.shape[1] for m in maps), ints(m.shape[2] for m in maps),
+            ints(m.shape[3] for m in maps), ints(coff))
+
+
+def rt_linear(x: np.ndarray, w: np.ndarray, bias=None, *, k: int | None = None, x2=None, x2_cols: int = 0, res=None, act: int = 0,
+              y: np.ndarray | None = None, ycol: int = 0, ctx=None) -> np.ndarray:
+    """y[:, ycol:ycol + Nout] = act(x[:, :K] (+ x2[:, :K] for the output columns [0, x2_cols)) @ w.T + bias) (+ res[:, :Nout]).
+    x [M, ldx >= K], w [Nout, K], res [M, ldr >= Nout]; y (optional) [M, ldy]: a copy comes back with only that block written.
+    act: 0 none, 2 ReLU, 3 GELU."""
+    ctx = ctx or _lib.default_context()
+    x, w, x2, res, b = _f32(x), _f32(w), _f32(x2), _f32(res), _f32(bias)
+    nout, kk = w.shape
+    k = kk if k is None else k
+    assert k == kk and x.ndim == 2
+    m = x.shape[0]
+    y = np.zeros((m, nout), np.float32) if y is None else np.array(y, dtype=np.float32, order="C")
+    assert y.shape[0] == m and (x2 is None or x2.shape[0] == m) and (res is None or res.shape[0] == m)
+    check(ctx.lib.gtx_op_rt_linear(ctx.handle, m, k, nout, ptr(x), x.shape[1], ptr(x2), 0 if x2 is None else x2.shape[1], int(x2_cols), ptr(w), ptr(b),
+                                   ptr(res), 0 if res is None else res.shape[1], ptr(y), y.shape[1], int(ycol), int(act)))
+    return y
+
+
+def rt_layernorm(x: np.ndarray, gamma, beta, *, c: int | None = None, in_coff: int = 0, in_split: bool = False, out: np.ndarray | None = None,
+                 out_coff: int = 0, out_dtype=None, out_split: bool = False, ctx=None):
+    """LayerNorm (eps 1e-5) of x[:, in_coff:in_coff + c] into out[:, out_coff:out_coff + c] (a copy of `out` otherwise). Formats
+    are the arrays' dtypes; *_split=True (float32 arrays): the pair format on the device. Returns (out, saturated)."""
+    ctx = ctx or _lib.default_context()
+    x = np.ascontiguousarray(x)
+    rows, cs = x.shape
+    c = cs if c is None else c
+    if out is None:
+        out = np.zeros((rows, c), out_dtype or x.dtype)
+    out = np.array(out, order="C")
+    assert out.shape[0] == rows
+    sat = C.c_int()
+    check(ctx.lib.gtx_op_rt_layernorm(ctx.handle, rows, c, _map_fmt(x, in_split), ptr(x), cs, in_coff, _map_fmt(out, out_split), ptr(out), out.shape[1],
+                                      out_coff, ptr(_f32(gamma)), ptr(_f32(beta)), C.byref(sat)))
+    return out, bool(sat.value)
+
+
+def rt_mha(qkv: np.ndarray, c: int, heads: int, *, out: np.ndarray | None = None, form: int = 0, ctx=None) -> np.ndarray:
+    """Multi-head attention on token rows: qkv [n, T, ld >= 3 c] (q | k | v at columns 0, c, 2 c) -> out [n, T, ldo >= c] (a copy of
+    `out` with columns [0, c) written). form: 0 the library's rule, 1 the generic kernel."""
+    ctx = ctx or _lib.default_context()
+    qkv = _f32(qkv)
+    n, t, ld = qkv.shape
+    out = np.zeros((n, t, c), np.float32) if out is None else np.array(out, dtype=np.float32, order="C")
+    assert out.shape[:2] == (n, t)
+    check(ctx.lib.gtx_op_rt_mha(ctx.handle, n, t, c, heads, ptr(qkv), ld, ptr(out), out.shape[2], form))
+    return out
+
+
+def rt_topk(scores, nc: int, nq: int, *, coff=0, ctx=None) -> np.ndarray:
+    """Query selection over up to three score maps [n, h, w, cstride] (float32 or float16; classes at [coff, coff + nc)) -> idx [n, nq]."""
+    ctx = ctx or _lib.default_context()
+    keep, fmt, n, L, ptrs, h, w, cs, co = _levels(scores, coff, False)
+    idx = np.full((n, nq), -1, np.int32)
+    check(ctx.lib.gtx_op_rt_topk(ctx.handle, fmt, n, L, ptrs, h, w, cs, co, nc, nq, ptr(idx)))
+    return idx
+
+
+def rt_gather_refer(enc, c: int, idx: np.ndarray, delta: np.ndarray, *, coff=0, split: bool = False, ctx=None):
+    """The selected anchors' rows, anchor logits and first reference boxes: enc = level maps [n, h, w, cstride], idx [n, nq],
+    delta [n * nq, ldd >= 4] -> (embed [n * nq, c], anchors [n * nq, 4], refer [n * nq, 16])."""
+    ctx = ctx or _lib.default_context()
+    keep, fmt, n, L, ptrs, h, w, cs, co = _levels(enc, coff, split)
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    delta = _f32(delta)
+    nq = idx.shape[1]
+    m = n * nq
+    assert idx.shape[0] == n and delta.shape[0] == m
+    embed, anchors, refer = np.zeros((m, c), np.float32), np.zeros((m, 4), np.float32), np.zeros((m, 16), np.float32)
+    check(ctx.lib.gtx_op_rt_gather_refer(ctx.handle, fmt, n, L, ptrs, h, w, cs, co, c, nq, ptr(idx), ptr(delta), delta.shape[1], 0, ptr(embed),
+                                         ptr(anchors), ptr(refer)))
+    return embed, anchors, refer
+
+
+def rt_refer_update(refer: np.ndarray, delta: np.ndarray, ctx=None) -> np.ndarray:
+    """refer[:, :4] = sigmoid(delta[:, :4] + inverse_sigmoid(refer[:, :4])) (rt_refer mode 1); refer [M, 16] comes back as a copy."""
+    ctx = ctx or _lib.default_context()
+    refer = np.array(refer, dtype=np.float32, order="C")
+    delta = _f32(delta)
+    m = refer.shape[0]
+    assert refer.shape == (m, 16) and delta.shape[0] == m
+    check(ctx.lib.gtx_op_rt_gather_refer(ctx.handle, GTX_F32, 1, 0, None, None, None, None, None, 0, m, None, ptr(delta), delta.shape[1], 1, None, None,
+                                         ptr(refer)))
+    return refer
+
+
+def rt_deform(value, hd: int, nh: int, npts: int, offaw: np.ndarray, refer: np.ndarray, *, coff=0, split: bool = False, ctx=None) -> np.ndarray:
+    """Multi-scale deformable attention sampling: value = level maps [n, h, w, cstride] (hd channels from coff), offaw
+    [n, nq, nh * L * npts * 3], refer [n, nq, 16] -> out [n, nq, hd]."""
+    ctx = ctx or _lib.default_context()
+    keep, fmt, n, L, ptrs, h, w, cs, co = _levels(value, coff, split)
+    offaw, refer = _f32(offaw), _f32(refer)
+    nq = offaw.shape[1]
+    assert offaw.shape == (n, nq, nh * L * npts * 3) and refer.shape == (n, nq, 16)
+    out = np.zeros((n, nq, hd), np.float32)
+    check(ctx.lib.gtx_op_rt_deform(ctx.handle, fmt, n, L, ptrs, h, w, cs, co, hd, nh, npts, nq, ptr(offaw), ptr(refer), ptr(out)))
+    return out
+
+
+def rt_post(logits: np.ndarray, nc: int, refer: np.ndarray, conf: float, frame_wh, max_det: int, *, class_mask=(2**64 - 1, 2**64 - 1),
+            out_rows: np.ndarray | None = None, want_raw: bool = True, ctx=None):
+    """RT-DETR's score / box stage: logits [n, nq, ldl >= nc], refer [n, nq, 16] -> (rows [n, max_det, 6] -- a copy of `out_rows`
+    with the first out_n rows of each image written --, out_n [n], raw [n, nq, 4 + nc] or None). class_mask: two 64-bit words."""
+    ctx = ctx or _lib.default_context()
+    logits, refer = _f32(logits), _f32(refer)
+    n, nq, ldl = logits.shape
+    assert refer.shape == (n, nq, 16)
+    rows = np.zeros((n, max_det, 6), np.float32) if out_rows is None else np.array(out_rows, dtype=np.float32, order="C")
+    assert rows.shape == (n, max_det, 6)
+    out_n = np.full(n, -1, np.int32)
+    raw = np.zeros((n, nq, 4 + nc), np.float32) if want_raw else None
+    check(ctx.lib.gtx_op_rt_post(ctx.handle, n, nq, nc, ptr(logits), ldl, ptr(refer), float(conf), int(class_mask[0]), int(class_mask[1]),
+                                 int(frame_wh[0]), int(frame_wh[1]), max_det, ptr(rows), ptr(out_n), ptr(raw)))
+    return rows, out_n, raw

@@ -52,8 +52,9 @@ extern "C" {
  * 10: gtx_ecc_* added (GMC method ecc); gtx_fgmc_* (GMC method orb, stream-ordered) and gtx_gray_half_dev added: new entry
  *     points only, no struct or existing signature changed, so the number stays. gtx_op_psa_attention added and the embedder takes
  *     YOLO11-cls tensors (C2PSA = model.9): the same, the number stays. gtx_det_config.end2end appended at the struct's end (YOLOv10's
- *     one-to-one head; 0 = every earlier behaviour) and gtx_op_dwconv added: the number stays. */
-#define GTX_ABI_VERSION 10
+ *     one-to-one head; 0 = every earlier behaviour) and gtx_op_dwconv added: the number stays.
+ * 11: gtx_op_rt_{linear, layernorm, mha, topk, gather_refer, deform, post} added: RT-DETR's token-side kernels one launcher at a time. */
+#define GTX_ABI_VERSION 11
 
 typedef enum gtx_status {
   GTX_OK = 0,
@@ -222,6 +223,43 @@ int gtx_op_psa_attention(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int
  * value to fp16's range (GTX_F32S). Channel counts that are multiples of 32 take the LDS-tiled kernel at stride 1. */
 int gtx_op_dwconv(gtx_ctx* ctx, int dtype, int n, int h, int w, int c, int k, int stride, const void* x, const float* wt, const float* bias,
                   int act, const void* res, void* out, int* saturated);
+
+/* RT-DETR's token-side kernels (csrc/rtdetr_kernels.hpp), one launcher per call, for the operator-level tests. Token tensors are plain
+ * fp32 rows; map tensors are NHWC host arrays of fp16 (GTX_F16) or plain fp32 (GTX_F32; GTX_F32S: converted to the pair format on the
+ * way). Every size is checked before the GPU is touched: what a launcher would refuse comes back as GTX_ERR_INVALID.
+ *
+ * y[M][ldy], columns [ycol, ycol + Nout) = act(x[M][K] (+ x2 for the output columns [0, x2_cols)) . w[Nout][K]^T + bias) (+ res[M][ldr]);
+ * the other columns of y come back as given. x2, bias, res may be NULL. K, Nout multiples of 16; act 0 none, 2 ReLU, 3 GELU (erf);
+ * x2_cols a multiple of 64, or >= Nout. */
+int gtx_op_rt_linear(gtx_ctx* ctx, int M, int K, int Nout, const float* x, int ldx, const float* x2, int ldx2, int x2_cols, const float* w,
+                     const float* bias, const float* res, int ldr, float* y, int ldy, int ycol, int act);
+/* LayerNorm (eps 1e-5) over C channels at in_coff of rows [rows][in_cstride] into channels [out_coff, out_coff + C) of out
+ * [rows][out_cstride] (the rest comes back as given). Formats: F32 -> F32 / F32S / F16, F32S -> F32S, F16 -> F16. C a multiple of 8 up
+ * to 1024; strides and offsets multiples of 8. *saturated: an output was clamped to fp16's range (F32S). */
+int gtx_op_rt_layernorm(gtx_ctx* ctx, int rows, int C, int in_fmt, const void* in, int in_cstride, int in_coff, int out_fmt, void* out,
+                        int out_cstride, int out_coff, const float* gamma, const float* beta, int* saturated);
+/* softmax(q k^T / sqrt(d)) v per image and head: qkv [n * T][ld] with q at column 0, k at C, v at 2 C; out [n * T][ldo], columns
+ * [0, C) written. d = C / heads in {8, 16, 32}. form: 0 = the library's rule (d = 32 on the matrix pipe), 1 = the generic kernel. */
+int gtx_op_rt_mha(gtx_ctx* ctx, int n, int T, int C, int heads, const float* qkv, int ld, float* out, int ldo, int form);
+/* Query selection: idx [n][nq] = the nq anchors with the largest max-over-classes score per image, descending, ties: lower anchor
+ * index first. scores: n_levels (1..3) maps [n][h][w][cstride] with the nc classes from coff; fmt GTX_F32 or GTX_F16. nq <= 1024. */
+int gtx_op_rt_topk(gtx_ctx* ctx, int fmt, int n, int n_levels, const void* const* scores, const int* h, const int* w, const int* cstride,
+                   const int* coff, int nc, int nq, int* idx);
+/* mode 0: embed [n * nq][C] = the rows of the anchors idx [n][nq] in the level maps enc, anchors [n * nq][4] their logits (+inf
+ * outside (0.01, 0.99)), refer [n * nq][16] = sigmoid(delta[:, :4] + anchors) in columns 0..3, zero elsewhere. mode 1: refer (given,
+ * in place) = sigmoid(delta + inverse_sigmoid(refer)); enc, idx, embed and anchors are not read. delta [n * nq][ldd]. */
+int gtx_op_rt_gather_refer(gtx_ctx* ctx, int fmt, int n, int n_levels, const void* const* enc, const int* h, const int* w, const int* cstride,
+                           const int* coff, int C, int nq, const int* idx, const float* delta, int ldd, int mode, float* embed, float* anchors,
+                           float* refer);
+/* Multi-scale deformable attention sampling: value levels [n][h][w][cstride] with the layer's hd channels from coff, offaw
+ * [n * nq][nh * L * npts * 3] (sampling offsets, then attention logits), refer [n * nq][16]; out [n * nq][hd]. */
+int gtx_op_rt_deform(gtx_ctx* ctx, int fmt, int n, int n_levels, const void* const* value, const int* h, const int* w, const int* cstride,
+                     const int* coff, int hd, int nh, int npts, int nq, const float* offaw, const float* refer, float* out);
+/* RTDETRPredictor.postprocess: logits [n * nq][ldl], refer [n * nq][16]; out_rows [n][max_det][6] (xyxy in frame pixels, score,
+ * class; rows past out_n come back as given), out_n [n], raw [n * nq][4 + nc] or NULL. class_mask0 / 1: bit c of word c / 64 keeps
+ * class c. nq <= 512, nc <= 128. */
+int gtx_op_rt_post(gtx_ctx* ctx, int n, int nq, int nc, const float* logits, int ldl, const float* refer, float conf, uint64_t class_mask0,
+                   uint64_t class_mask1, int frame_w, int frame_h, int max_det, float* out_rows, int* out_n, float* raw);
 
 /* Brute-force L2 2-nearest-neighbour search of unit-norm 128-d float descriptors (RootSIFT): what
  * cv2.BFMatcher(NORM_L2).knnMatch(query, train, k=2) returns inside stabilo for the orthophoto

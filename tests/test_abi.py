@@ -25,7 +25,7 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/gtx.h but not exported by libgtx.so"
     assert declared == set(_lib._SIGNATURES), declared ^ set(_lib._SIGNATURES)
-    assert lib.gtx_abi_version() == _lib.ABI_VERSION == 10
+    assert lib.gtx_abi_version() == _lib.ABI_VERSION == 11
 
 
 def test_errors_are_codes_with_messages_not_exceptions():
@@ -42,6 +42,46 @@ def test_errors_are_codes_with_messages_not_exceptions():
     assert rc < 0 and b"tracker type" in lib.gtx_last_error()
     with pytest.raises(_lib.GtxError):
         _lib.check(rc)
+
+
+def test_rtdetr_hooks_refuse_bad_sizes_before_any_launch():
+    """Host only: what a launcher's own checks would refuse comes back as an error code from the operator hooks (no context is
+    even given), and more than 128 classes -- the class mask of the score stage has two 64-bit words -- never reaches a detector."""
+    from geotrax_amd import _lib
+
+    lib = _lib.load()
+    f = np.zeros(4096, np.float32)
+    i = np.zeros(64, np.int32)
+    p = _lib.ptr
+    full = 2**64 - 1
+    assert lib.gtx_op_rt_post(None, 1, 4, 129, p(f), 132, p(f), 0.5, full, full, 64, 64, 4, p(f), p(i), None) == -1
+    assert b"128 classes" in lib.gtx_last_error()
+    assert lib.gtx_op_rt_post(None, 1, 513, 4, p(f), 4, p(f), 0.5, full, full, 64, 64, 4, p(f), p(i), None) == -1
+    assert b"512 queries" in lib.gtx_last_error()
+    assert lib.gtx_op_rt_post(None, 1, 4, 128, p(f), 128, p(f), 0.5, full, full, 64, 64, 4, p(f), p(i), None) == -1
+    assert b"ctx is NULL" in lib.gtx_last_error()                                   # the sizes were fine
+    assert lib.gtx_op_rt_linear(None, 4, 24, 16, p(f), 24, None, 0, 0, p(f), None, None, 0, p(f), 16, 0, 0) == -1      # K % 16
+    assert b"rt_linear" in lib.gtx_last_error()
+    assert lib.gtx_op_rt_linear(None, 4, 16, 128, p(f), 16, p(f), 16, 32, p(f), None, None, 0, p(f), 128, 0, 0) == -1  # x2_cols % 64
+    assert lib.gtx_op_rt_linear(None, 4, 16, 16, p(f), 16, None, 0, 0, p(f), None, None, 0, p(f), 24, 16, 0) == -1     # past ldy
+    assert lib.gtx_op_rt_layernorm(None, 2, 1032, 1, p(f), 1032, 0, 1, p(f), 1032, 0, p(f), p(f), None) == -1          # C > 1024
+    assert lib.gtx_op_rt_layernorm(None, 2, 64, 2, p(f), 64, 0, 1, p(f), 64, 0, p(f), p(f), None) == -1                # F32S -> F32
+    assert lib.gtx_op_rt_mha(None, 1, 4, 48, 4, p(f), 144, p(f), 48, 0) == -1                                          # head dimension 12
+    assert lib.gtx_op_rt_mha(None, 1, 4, 32, 1, p(f), 96, p(f), 32, 2) == -1                                           # form
+    maps = (C.c_void_p * 1)(f.ctypes.data)
+    one = lambda v: (C.c_int * 1)(v)
+    assert lib.gtx_op_rt_topk(None, 1, 1, 1, maps, one(3), one(4), one(4), one(0), 4, 13, p(i)) == -1                  # 13 queries of 12 anchors
+    assert b"rt_topk" in lib.gtx_last_error()
+    assert lib.gtx_op_rt_topk(None, 2, 1, 1, maps, one(3), one(4), one(4), one(0), 4, 4, p(i)) == -1                   # pair-format scores
+    i[:4] = [0, 5, 12, 3]
+    assert lib.gtx_op_rt_gather_refer(None, 1, 1, 1, maps, one(3), one(4), one(8), one(0), 8, 4, p(i), p(f), 4, 0, p(f), p(f), p(f)) == -1
+    assert b"outside the level set" in lib.gtx_last_error()
+    assert lib.gtx_op_rt_deform(None, 1, 1, 1, maps, one(3), one(4), one(8), one(0), 8, 3, 4, 2, p(f), p(f), p(f)) == -1   # hd % nh
+    h = C.c_void_p()
+    cfg = _lib.DetConfig(imgsz=640, conf=0.25, iou=0.7, max_det=300, nc=129, frame_h=64, frame_w=64, arch=1)
+    assert lib.gtx_detector_create(None, C.byref(cfg), C.byref(h)) == -3 and b"128 classes" in lib.gtx_last_error() and not h.value
+    cfg.arch = 0
+    assert lib.gtx_detector_create(None, C.byref(cfg), C.byref(h)) == -3 and not h.value
 
 
 def test_no_gpu_means_loud_failure_not_fallback():

@@ -225,6 +225,21 @@ def test_rtdetr_other_head_sizes_match_the_oracle(gtx_ctx):
     det.close()
 
 
+def test_rtdetr_class_filter_reaches_the_second_mask_word(gtx_ctx):
+    """`classes=[2, 70]` on the 80-class head: class 70 lives in the second 64-bit word of the mask the score stage reads. The boxes,
+    scores and classes that come out are oracle.rtdetr_ref.postprocess's with the same filter."""
+    from geotrax_amd.detector import Detector
+    from geotrax_amd.weights import synthetic_rtdetr
+    from oracle.rtdetr_ref import RtDetrRef
+
+    w = synthetic_rtdetr(seed=11, nc=80, nq=100, ndl=3, score_bias=-0.5)
+    frame = _frame(3)
+    det = Detector(w, FRAME_HW, imgsz=384, conf=0.05, max_det=100, classes=[2, 70], ctx=gtx_ctx)
+    got, pred, _ = _check_against_oracle(det, RtDetrRef(w), frame, 384, 0.05, [2, 70], layers=["model.27"])
+    assert 0 < len(got) < 100 and set(got.cls.tolist()) <= {2, 70} and 70 in got.cls      # the filter cut, and class 70 came through
+    det.close()
+
+
 def test_rtdetr_half_precision_maps(gtx_ctx, weights):
     """`ultralytics.half: true` (default.yaml:245) for RT-DETR: fp16 maps and weights on the fp16 MFMA convolutions (fp32 accumulate),
     the token side stays fp32 -- so this path is MORE exact than a half() model upstream, and it is held against the fp32 oracle at
