@@ -1048,6 +1048,8 @@ void launch_head_boxes(int dtype, const HeadParams& hp, int n, const NmsBuffers&
   dim3 grid2(64, n), block(256);
   const size_t lds = (size_t)hp.n_levels * hp.lv[0].cb * 64 * sizeof(float);
   GTX_CHECK(hp.n_levels <= kMaxLevels && hp.lv[0].cb <= 128, "head: %d levels of %d box channels", hp.n_levels, hp.lv[0].cb);
+  for (int l = 1; l < hp.n_levels; ++l)            // the kernel lays its LDS out in slices of level 0's width
+    GTX_CHECK(hp.lv[l].cb <= hp.lv[0].cb, "head: level %d has %d box channels, more than level 0's %d", l, hp.lv[l].cb, hp.lv[0].cb);
   static std::once_flag once;     // detectors run on several host threads (engine stage 1, set_reference)
   std::call_once(once, [] {
     // the cap only: a launch asks for its own levels' bytes (YOLOv8s: 48 KB, P2-s: 64 KB), so its occupancy is what that size allows
@@ -1069,6 +1071,7 @@ void launch_head_raw(int dtype, const HeadParams& hp, int n, float* out, bool lo
 // ============================================================================ NMS
 constexpr int kSmallNms = 4096;    // candidates the single-workgroup path handles
 constexpr int kSmallKeep = 2048;   // max_det it handles
+constexpr unsigned kSmallAnchors = 1u << 20;   // anchor indices it orders: its sort key has 20 bits for them (launch_nms, Detector)
 
 // (1) rank: position of each candidate in (score desc, anchor asc) order = stable descending
 //     sort of the anchor-ordered candidate list, which is what torchvision.ops.nms applies to
@@ -1291,7 +1294,7 @@ __global__ __launch_bounds__(1024) void nms_small_kernel(const NmsBuffers nb, fl
     unsigned long long k = 0ull;
     if (i < cnt) {
       const unsigned sb = __float_as_uint(nb.cand_score[base + i]);            // scores are positive: bits are monotone
-      k = ((unsigned long long)sb << 32) | ((unsigned long long)(0x7FFFFu - (unsigned)nb.cand_anchor[base + i]) << 12) | (unsigned)i;
+      k = ((unsigned long long)sb << 32) | ((unsigned long long)(kSmallAnchors - 1u - (unsigned)nb.cand_anchor[base + i]) << 12) | (unsigned)i;   // anchor: bits 12..31
     }
     s_key[i] = k;
   }
@@ -1427,6 +1430,8 @@ void launch_obj_feats(int dtype, const FeatLevels& fl, int n, const NmsBuffers& 
 void launch_nms(const NmsBuffers& nb, int n, float iou_thr, bool agnostic, int max_nms,
                 const Letterbox& lb, hipStream_t s, int which) {
   GTX_CHECK(nb.nms_cap <= kNmsWords * 64, "nms: capacity %d too large", nb.nms_cap);
+  // Detector's candidate capacity is its anchor count; the operator hook checks the anchors it is given
+  GTX_CHECK(which == 2 || (unsigned)nb.cap <= kSmallAnchors, "nms: %d anchors, the single-workgroup kernel orders at most %u", nb.cap, kSmallAnchors);
   const int limit = std::min(max_nms, nb.nms_cap);
   const float cls_offset = agnostic ? 0.f : 7680.f;  // ultralytics max_wh
   // ultralytics scale_boxes: gain = min ratio, pad = round((net - src*gain)/2 - 0.1)
@@ -1449,5 +1454,6 @@ void launch_nms(const NmsBuffers& nb, int n, float iou_thr, bool agnostic, int m
 }
 
 bool nms_small_covers(int candidates, int max_det) { return candidates <= kSmallNms && max_det <= kSmallKeep; }
+int nms_max_anchors() { return (int)kSmallAnchors; }
 
 }  // namespace gtx

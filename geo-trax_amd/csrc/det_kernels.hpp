@@ -131,8 +131,9 @@ constexpr int kV10Keep = 300;   // ultralytics Detect.max_det: the rows v10Detec
 // cand: the score gate's candidates (launch_head_gate with every class kept: one per anchor whose best score clears conf). sel (cap in
 // [kV10Keep, 512], its own count / cand_* arrays; lvl_* optional): the at most kV10Keep (anchor, class) entries the two-stage cut keeps,
 // sorted by score (ties: the lower flat index anchor * nc + class first), filed by level for launch_head_sparse_box. scores: scratch
-// [N][kV10Keep][nc] fp32.
-void launch_v10_select(int dtype, const HeadParams& hp, int n, const NmsBuffers& cand, const NmsBuffers& sel, float* scores, hipStream_t s);
+// [N][kV10Keep][nc] fp32, one row per anchor stage 1 kept, in the order they arrived; kept_anchor (optional, [N][kV10Keep]): those anchors.
+void launch_v10_select(int dtype, const HeadParams& hp, int n, const NmsBuffers& cand, const NmsBuffers& sel, float* scores, hipStream_t s,
+                       int* kept_anchor = nullptr);
 // sel's entries with their boxes (cand_box: launch_head_sparse_box or launch_head_boxes on sel) -> out_rows / out_n (/ out_anchor):
 // `classes`, the max_det cut, scale_boxes + clip to the frame
 void launch_v10_rows(const NmsBuffers& sel, const unsigned long long class_mask[2], int n, const Letterbox& lb, hipStream_t s);
@@ -143,5 +144,7 @@ void launch_nms(const NmsBuffers& nb, int n, float iou_thr, bool agnostic, int m
                 const Letterbox& lb, hipStream_t s, int which = 0);
 // true when the single-workgroup kernel handles an image with that many candidates (the general kernels then have nothing to do)
 bool nms_small_covers(int candidates, int max_det);
+// anchors per image the NMS kernels order correctly (the single-workgroup kernel's sort key keeps 20 bits of the anchor index)
+int nms_max_anchors();
 
 }  // namespace gtx

@@ -191,6 +191,8 @@ void Detector::build_graph() {
     layer_views_[det_pfx_ + ".feat" + std::to_string(l)] = h2;
   }
   head_.n_anchors = anchor;
+  GTX_CHECK(end2end_ || anchor <= nms_max_anchors(), "%d anchors per image: the NMS kernels order at most %d (ties between candidates go to the lower anchor)", anchor,
+            nms_max_anchors());
   {
     auto same = [](const ConvConfig& a, const ConvConfig& b) {
       return a.dtype == b.dtype && a.ks == b.ks && a.stride == b.stride && a.bn == b.bn && a.kc == b.kc &&

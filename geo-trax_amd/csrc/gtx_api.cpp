@@ -739,6 +739,314 @@ int gtx_op_rt_post(gtx_ctx* ctx, int n, int nq, int nc, const float* logits, int
   });
 }
 
+// ---- the detector's post-pass kernels, one hook per launcher (tests/test_head_ops_gpu.py). As above: every size, and every index a
+// kernel would follow, is checked before anything touches the GPU.
+namespace {
+struct HeadSet {
+  gtx::HeadParams hp{};
+  gtx::DevBuf feat[gtx::kMaxLevels], wb[gtx::kMaxLevels], bb[gtx::kMaxLevels], wc[gtx::kMaxLevels], bc[gtx::kMaxLevels];
+};
+// gate: the class branch is read (16-byte loads); boxes: the box branch is
+long head_check(const char* op, int dtype, int n, int n_levels, const gtx_head_level* lv, int nc, bool gate, bool boxes) {
+  if (dtype != GTX_F16 && dtype != GTX_F32) rt_bad(op, "maps are GTX_F16 or GTX_F32");
+  if (n_levels > gtx::kMaxLevels) rt_bad(op, "at most 4 levels");
+  if (n < 1 || n > 64 || n_levels < 1) rt_bad(op, "bad sizes");
+  if (gate && (nc < 1 || nc > 128)) rt_bad(op, "1..128 classes (the class mask has two 64-bit words)");
+  need(lv, "lv");
+  const int al = dtype == GTX_F16 ? 8 : 4;          // elements in 16 bytes
+  long A = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    const gtx_head_level& L = lv[l];
+    need(L.feat, "lv[l].feat");
+    if (L.h < 1 || L.w < 1 || L.cb < 0 || L.cc < 0 || L.cstride < 1 || L.cstride > (1 << 16) || (long)L.cb + L.cc > L.cstride)
+      rt_bad(op, "a level's channels do not fit its stride");
+    if ((double)n * L.h * L.w * L.cstride > 2.5e8) rt_bad(op, "maps too large");
+    A += (long)L.h * L.w;
+    if (gate) {
+      need(L.wc, "lv[l].wc"); need(L.bc, "lv[l].bc");
+      if (L.cc < 8 || L.cc % 8) rt_bad(op, "cc must be a positive multiple of 8 (the kernel reads 8-channel chunks)");
+      if (L.cb % al || L.cstride % al) rt_bad(op, "cb and cstride must keep the class features 16-byte aligned");
+    }
+    if (boxes) {
+      need(L.wb, "lv[l].wb"); need(L.bb, "lv[l].bb");
+      if (L.cb < 1 || L.cb > 128) rt_bad(op, "1..128 box channels");
+      if (L.cb > lv[0].cb) rt_bad(op, "no level's cb may exceed level 0's (the kernel's LDS layout)");
+    }
+  }
+  if (A > (1l << 22)) rt_bad(op, "too many anchors");
+  return A;
+}
+void head_upload(HeadSet& s, int dtype, int n, int n_levels, const gtx_head_level* lv, int nc, bool gate, bool boxes) {
+  s.hp.n_levels = n_levels;
+  s.hp.nc = nc;
+  int anchor = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    const gtx_head_level& L = lv[l];
+    gtx::HeadLevel& H = s.hp.lv[l];
+    rt_upload(s.feat[l], L.feat, (size_t)n * L.h * L.w * L.cstride * gtx::dtype_size(dtype));
+    H.feat = s.feat[l].p; H.h = L.h; H.w = L.w; H.cstride = L.cstride; H.cb = L.cb; H.cc = L.cc; H.stride = L.stride;
+    H.anchor_begin = anchor;
+    anchor += L.h * L.w;
+    if (gate) {
+      rt_upload(s.wc[l], L.wc, (size_t)nc * L.cc * 4);
+      rt_upload(s.bc[l], L.bc, (size_t)nc * 4);
+      H.wc = s.wc[l].as<float>(); H.bc = s.bc[l].as<float>();
+    }
+    if (boxes) {
+      rt_upload(s.wb[l], L.wb, (size_t)L.cb * 64 * 4);
+      rt_upload(s.bb[l], L.bb, 64 * 4);
+      H.wb = s.wb[l].as<float>(); H.bb = s.bb[l].as<float>();
+    }
+  }
+  s.hp.n_anchors = anchor;
+}
+// the first min(count, cap) entries of every image index an anchor below `anchors`
+void cand_check(const char* op, int n, int cap, const int* count, const int* anchor, long anchors) {
+  need(count, "count"); need(anchor, "anchor");
+  for (int b = 0; b < n; ++b) {
+    if (count[b] < 0) rt_bad(op, "a negative count");
+    const int m = std::min(count[b], cap);
+    for (int i = 0; i < m; ++i)
+      if (anchor[(size_t)b * cap + i] < 0 || anchor[(size_t)b * cap + i] >= anchors) rt_bad(op, "an anchor index is outside the level set");
+  }
+}
+void geometry_check(const char* op, int src_h, int src_w, int net_h, int net_w, double gain) {
+  if (src_h < 1 || src_w < 1 || net_h < 1 || net_w < 1 || src_h > (1 << 16) || src_w > (1 << 16) || net_h > (1 << 16) || net_w > (1 << 16) || !(gain > 0.0))
+    rt_bad(op, "bad letterbox geometry");
+}
+gtx::Letterbox geometry(int src_h, int src_w, int net_h, int net_w, double gain) {
+  gtx::Letterbox lb{};
+  lb.src_h = src_h; lb.src_w = src_w; lb.net_h = net_h; lb.net_w = net_w; lb.gain = gain;
+  return lb;
+}
+void fill_ff(gtx::DevBuf& d, size_t bytes) {
+  d.alloc(bytes);
+  GTX_HIP(hipMemset(d.p, 0xFF, bytes));
+}
+void download(void* host, const gtx::DevBuf& d, size_t bytes) { GTX_HIP(hipMemcpy(host, d.p, bytes, hipMemcpyDeviceToHost)); }
+}  // namespace
+
+int gtx_op_head_gate(gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx_head_level* lv, int nc, float conf, uint64_t class_mask0,
+                     uint64_t class_mask1, int cap, int lvl_cap, int* count, float* cand_score, int* cand_anchor, int* cand_cls, int* lvl_count,
+                     int* lvl_list) {
+  return guarded([&] {
+    const char* op = "head_gate";
+    head_check(op, dtype, n, n_levels, lv, nc, true, false);
+    if (cap < 1 || cap > (1 << 22) || lvl_cap < 0 || lvl_cap > (1 << 22)) rt_bad(op, "cap >= 1, lvl_cap >= 0");
+    need(count, "count"); need(cand_score, "cand_score"); need(cand_anchor, "cand_anchor"); need(cand_cls, "cand_cls");
+    if (lvl_cap) { need(lvl_count, "lvl_count"); need(lvl_list, "lvl_list"); }
+    need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    HeadSet hs;
+    head_upload(hs, dtype, n, n_levels, lv, nc, true, false);
+    hs.hp.conf = conf;
+    hs.hp.class_mask[0] = class_mask0; hs.hp.class_mask[1] = class_mask1;
+    const size_t m = (size_t)n * cap, lb = (size_t)n * gtx::kMaxLevels * (size_t)std::max(lvl_cap, 1) * 4;
+    gtx::DevBuf dc, ds, da, dk, dlc, dll;
+    fill_ff(dc, (size_t)n * 4); fill_ff(ds, m * 4); fill_ff(da, m * 4); fill_ff(dk, m * 4);
+    gtx::NmsBuffers nb{};
+    nb.cap = cap;
+    nb.count = dc.as<int>(); nb.cand_score = ds.as<float>(); nb.cand_anchor = da.as<int>(); nb.cand_cls = dk.as<int>();
+    if (lvl_cap) {
+      fill_ff(dlc, (size_t)n * gtx::kMaxLevels * 4); fill_ff(dll, lb);
+      nb.lvl_count = dlc.as<int>(); nb.lvl_list = dll.as<int>(); nb.lvl_cap = lvl_cap;
+    }
+    gtx::launch_head_gate(dtype, hs.hp, n, nb, ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download(count, dc, (size_t)n * 4); download(cand_score, ds, m * 4); download(cand_anchor, da, m * 4); download(cand_cls, dk, m * 4);
+    if (lvl_cap) { download(lvl_count, dlc, (size_t)n * gtx::kMaxLevels * 4); download(lvl_list, dll, lb); }
+  });
+}
+
+int gtx_op_head_boxes(gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx_head_level* lv, int cap, const int* count, const int* cand_anchor,
+                      float* cand_box) {
+  return guarded([&] {
+    const char* op = "head_boxes";
+    const long A = head_check(op, dtype, n, n_levels, lv, 0, false, true);
+    if (cap < 1 || cap > (1 << 22)) rt_bad(op, "cap >= 1");
+    cand_check(op, n, cap, count, cand_anchor, A);
+    need(cand_box, "cand_box"); need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    HeadSet hs;
+    head_upload(hs, dtype, n, n_levels, lv, 0, false, true);
+    const size_t m = (size_t)n * cap;
+    gtx::DevBuf dc, da, db;
+    rt_upload(dc, count, (size_t)n * 4); rt_upload(da, cand_anchor, m * 4); fill_ff(db, m * 16);
+    gtx::NmsBuffers nb{};
+    nb.cap = cap;
+    nb.count = dc.as<int>(); nb.cand_anchor = da.as<int>(); nb.cand_box = db.as<float>();
+    gtx::launch_head_boxes(dtype, hs.hp, n, nb, ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download(cand_box, db, m * 16);
+  });
+}
+
+int gtx_op_nms(gtx_ctx* ctx, int n, int cap, const int* count, const float* cand_score, const int* cand_anchor, const int* cand_cls,
+               const float* cand_box, float iou_thr, int agnostic, int max_nms, int nms_cap, int max_det, int src_h, int src_w, int net_h, int net_w,
+               double gain, int which, float* out_rows, int* out_n, int* out_anchor) {
+  return guarded([&] {
+    const char* op = "nms";
+    if (n < 1 || n > 64 || cap < 1 || cap > (1 << 20) || max_det < 1 || max_det > (1 << 16) || max_nms < 1) rt_bad(op, "bad sizes");
+    if (nms_cap < 64 || nms_cap % 64 || nms_cap > 32768 || (double)n * nms_cap * (nms_cap / 64) * 8 > 3e8) rt_bad(op, "nms_cap: a multiple of 64, the mask within 300 MB");
+    if (which < 0 || which > 2) rt_bad(op, "which: 0 both paths, 1 the single-workgroup kernel, 2 the general kernels");
+    geometry_check(op, src_h, src_w, net_h, net_w, gain);
+    cand_check(op, n, cap, count, cand_anchor, gtx::nms_max_anchors());
+    need(cand_score, "cand_score"); need(cand_cls, "cand_cls"); need(cand_box, "cand_box"); need(out_rows, "out_rows"); need(out_n, "out_n");
+    need(out_anchor, "out_anchor");
+    for (int b = 0; b < n; ++b)
+      for (int i = 0; i < std::min(count[b], cap); ++i) {
+        if (!(cand_score[(size_t)b * cap + i] > 0.f)) rt_bad(op, "scores must be positive (the sort key is their bit pattern)");
+        if (cand_cls[(size_t)b * cap + i] < 0 || cand_cls[(size_t)b * cap + i] > 127) rt_bad(op, "classes 0..127");
+      }
+    need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t m = (size_t)n * cap, sm = (size_t)n * nms_cap, rows = (size_t)n * max_det;
+    gtx::DevBuf dc, ds, da, dk, db, dsn((size_t)n * 4), sb(sm * 16), ss(sm * 4), sc(sm * 4), sa(sm * 4), dm(sm * (nms_cap / 64) * 8), dn, dr, doa;
+    rt_upload(dc, count, (size_t)n * 4); rt_upload(ds, cand_score, m * 4); rt_upload(da, cand_anchor, m * 4); rt_upload(dk, cand_cls, m * 4);
+    rt_upload(db, cand_box, m * 16);
+    rt_upload(dn, out_n, (size_t)n * 4); rt_upload(dr, out_rows, rows * 24); rt_upload(doa, out_anchor, rows * 4);
+    GTX_HIP(hipMemset(dsn.p, 0, (size_t)n * 4));       // which == 2 alone: an image left to the other path has nothing sorted
+    gtx::NmsBuffers nb{};
+    nb.cap = cap;
+    nb.count = dc.as<int>(); nb.cand_score = ds.as<float>(); nb.cand_anchor = da.as<int>(); nb.cand_cls = dk.as<int>(); nb.cand_box = db.as<float>();
+    nb.nms_cap = nms_cap;
+    nb.sorted_n = dsn.as<int>(); nb.s_box = sb.as<float>(); nb.s_score = ss.as<float>(); nb.s_cls = sc.as<int>(); nb.s_anchor = sa.as<int>();
+    nb.mask = dm.as<unsigned long long>();
+    nb.max_det = max_det;
+    nb.out_n = dn.as<int>(); nb.out_rows = dr.as<float>(); nb.out_anchor = doa.as<int>();
+    gtx::launch_nms(nb, n, iou_thr, agnostic != 0, max_nms, geometry(src_h, src_w, net_h, net_w, gain), ctx->stream, which);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download(out_n, dn, (size_t)n * 4); download(out_rows, dr, rows * 24); download(out_anchor, doa, rows * 4);
+  });
+}
+
+int gtx_op_v10_select(gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx_head_level* lv, int nc, float conf, int cap, const int* count,
+                      const float* cand_score, const int* cand_anchor, int sel_cap, int lvl_cap, int* sel_count, float* sel_score, int* sel_anchor,
+                      int* sel_cls, int* lvl_count, int* lvl_list, float* scores, int* score_anchor) {
+  return guarded([&] {
+    const char* op = "v10_select";
+    const long A = head_check(op, dtype, n, n_levels, lv, nc, true, false);
+    if (cap < 1 || cap > (1 << 22)) rt_bad(op, "cap >= 1");
+    if (sel_cap < gtx::kV10Keep || sel_cap > 512) rt_bad(op, "sel_cap in [300, 512]");
+    if (lvl_cap != 0 && (lvl_cap < gtx::kV10Keep || lvl_cap > (1 << 16))) rt_bad(op, "lvl_cap: 0 (not kept) or >= 300");
+    cand_check(op, n, cap, count, cand_anchor, A);
+    need(cand_score, "cand_score");
+    for (int b = 0; b < n; ++b)
+      for (int i = 0; i < std::min(count[b], cap); ++i)
+        if (!(cand_score[(size_t)b * cap + i] > 0.f)) rt_bad(op, "scores must be positive (the select key is their bit pattern)");
+    need(sel_count, "sel_count"); need(sel_score, "sel_score"); need(sel_anchor, "sel_anchor"); need(sel_cls, "sel_cls"); need(scores, "scores");
+    need(score_anchor, "score_anchor");
+    if (lvl_cap) { need(lvl_count, "lvl_count"); need(lvl_list, "lvl_list"); }
+    need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    HeadSet hs;
+    head_upload(hs, dtype, n, n_levels, lv, nc, true, false);
+    hs.hp.conf = conf;
+    hs.hp.class_mask[0] = hs.hp.class_mask[1] = ~0ull;
+    const size_t m = (size_t)n * cap, sm = (size_t)n * sel_cap, scb = (size_t)n * gtx::kV10Keep * nc * 4,
+                 lb = (size_t)n * gtx::kMaxLevels * (size_t)std::max(lvl_cap, 1) * 4;
+    gtx::DevBuf dc, ds, da, qc, qs, qa, qk, dlc, dll, dsc, dka;
+    fill_ff(dka, (size_t)n * gtx::kV10Keep * 4);
+    rt_upload(dc, count, (size_t)n * 4); rt_upload(ds, cand_score, m * 4); rt_upload(da, cand_anchor, m * 4);
+    fill_ff(qc, (size_t)n * 4); fill_ff(qs, sm * 4); fill_ff(qa, sm * 4); fill_ff(qk, sm * 4); fill_ff(dsc, scb);
+    gtx::NmsBuffers cand{}, sel{};
+    cand.cap = cap;
+    cand.count = dc.as<int>(); cand.cand_score = ds.as<float>(); cand.cand_anchor = da.as<int>();
+    sel.cap = sel_cap;
+    sel.count = qc.as<int>(); sel.cand_score = qs.as<float>(); sel.cand_anchor = qa.as<int>(); sel.cand_cls = qk.as<int>();
+    if (lvl_cap) {
+      fill_ff(dlc, (size_t)n * gtx::kMaxLevels * 4); fill_ff(dll, lb);
+      sel.lvl_count = dlc.as<int>(); sel.lvl_list = dll.as<int>(); sel.lvl_cap = lvl_cap;
+    }
+    gtx::launch_v10_select(dtype, hs.hp, n, cand, sel, dsc.as<float>(), ctx->stream, dka.as<int>());
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download(sel_count, qc, (size_t)n * 4); download(sel_score, qs, sm * 4); download(sel_anchor, qa, sm * 4); download(sel_cls, qk, sm * 4);
+    download(scores, dsc, scb); download(score_anchor, dka, (size_t)n * gtx::kV10Keep * 4);
+    if (lvl_cap) { download(lvl_count, dlc, (size_t)n * gtx::kMaxLevels * 4); download(lvl_list, dll, lb); }
+  });
+}
+
+int gtx_op_v10_rows(gtx_ctx* ctx, int n, int sel_cap, const int* sel_count, const float* sel_score, const int* sel_anchor, const int* sel_cls,
+                    const float* sel_box, uint64_t class_mask0, uint64_t class_mask1, int max_det, int src_h, int src_w, int net_h, int net_w,
+                    double gain, float* out_rows, int* out_n, int* out_anchor) {
+  return guarded([&] {
+    const char* op = "v10_rows";
+    if (n < 1 || n > 64 || sel_cap < 1 || sel_cap > 512 || max_det < 1 || max_det > (1 << 16)) rt_bad(op, "sel_cap in [1, 512], max_det >= 1");
+    geometry_check(op, src_h, src_w, net_h, net_w, gain);
+    need(sel_count, "sel_count"); need(sel_score, "sel_score"); need(sel_anchor, "sel_anchor"); need(sel_cls, "sel_cls"); need(sel_box, "sel_box");
+    need(out_rows, "out_rows"); need(out_n, "out_n"); need(out_anchor, "out_anchor");
+    for (int b = 0; b < n; ++b)
+      if (sel_count[b] < 0) rt_bad(op, "a negative count");
+    need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t sm = (size_t)n * sel_cap, rows = (size_t)n * max_det;
+    gtx::DevBuf qc, qs, qa, qk, qb, dn, dr, doa;
+    rt_upload(qc, sel_count, (size_t)n * 4); rt_upload(qs, sel_score, sm * 4); rt_upload(qa, sel_anchor, sm * 4); rt_upload(qk, sel_cls, sm * 4);
+    rt_upload(qb, sel_box, sm * 16);
+    rt_upload(dn, out_n, (size_t)n * 4); rt_upload(dr, out_rows, rows * 24); rt_upload(doa, out_anchor, rows * 4);
+    gtx::NmsBuffers sel{};
+    sel.cap = sel_cap;
+    sel.count = qc.as<int>(); sel.cand_score = qs.as<float>(); sel.cand_anchor = qa.as<int>(); sel.cand_cls = qk.as<int>(); sel.cand_box = qb.as<float>();
+    sel.max_det = max_det;
+    sel.out_n = dn.as<int>(); sel.out_rows = dr.as<float>(); sel.out_anchor = doa.as<int>();
+    const unsigned long long mask[2] = {class_mask0, class_mask1};
+    gtx::launch_v10_rows(sel, mask, n, geometry(src_h, src_w, net_h, net_w, gain), ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download(out_n, dn, (size_t)n * 4); download(out_rows, dr, rows * 24); download(out_anchor, doa, rows * 4);
+  });
+}
+
+int gtx_op_obj_feats(gtx_ctx* ctx, int dtype, int n, int n_levels, const void* const* maps, const int* h, const int* w, const int* cstride,
+                     const int* coff, const int* c, int dim, int max_det, const int* out_n, const int* out_anchor, float* out) {
+  return guarded([&] {
+    const char* op = "obj_feats";
+    if (dtype != GTX_F16 && dtype != GTX_F32 && dtype != GTX_F32S) rt_bad(op, "unsupported map format");
+    if (n_levels > gtx::kMaxLevels) rt_bad(op, "at most 4 levels");
+    if (n < 1 || n > 64 || n_levels < 1 || dim < 1 || dim > (1 << 12) || max_det < 1 || max_det > (1 << 16)) rt_bad(op, "bad sizes");
+    need(maps, "maps"); need(h, "h"); need(w, "w"); need(cstride, "cstride"); need(coff, "coff"); need(c, "c");
+    long A = 0;
+    for (int l = 0; l < n_levels; ++l) {
+      need(maps[l], "maps[l]");
+      if (h[l] < 1 || w[l] < 1 || coff[l] < 0 || c[l] < 1 || cstride[l] > (1 << 16) || (long)coff[l] + c[l] > cstride[l]) rt_bad(op, "a level's channel slice does not fit its stride");
+      if (c[l] % dim) rt_bad(op, "every level's channel count must be a multiple of dim");
+      if (dtype == GTX_F32S && cstride[l] % 8) rt_bad(op, "pair-format maps need channel strides that are multiples of 8");
+      if ((double)n * h[l] * w[l] * cstride[l] > 2.5e8) rt_bad(op, "maps too large");
+      A += (long)h[l] * w[l];
+    }
+    if (A > (1l << 22)) rt_bad(op, "too many anchors");
+    cand_check(op, n, max_det, out_n, out_anchor, A);
+    need(out, "out"); need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    gtx::FeatLevels fl{};
+    gtx::DevBuf buf[gtx::kMaxLevels], dn, doa, dout;
+    std::vector<uint8_t> tmp;
+    int anchor = 0;
+    for (int l = 0; l < n_levels; ++l) {
+      const size_t bytes = (size_t)n * h[l] * w[l] * cstride[l] * gtx::dtype_size(dtype);
+      const void* src = maps[l];
+      if (dtype == GTX_F32S) {                          // plain fp32 host arrays -> pair format on the device
+        tmp.resize(bytes);
+        gtx::f32_to_pairs(static_cast<const float*>(src), tmp.data(), bytes / 4);
+        src = tmp.data();
+      }
+      rt_upload(buf[l], src, bytes);
+      fl.feat[l] = buf[l].p; fl.h[l] = h[l]; fl.w[l] = w[l]; fl.cstride[l] = cstride[l]; fl.coff[l] = coff[l]; fl.c[l] = c[l];
+      fl.anchor_begin[l] = anchor;
+      anchor += h[l] * w[l];
+    }
+    fl.n_levels = n_levels;
+    fl.dim = dim;
+    const size_t rows = (size_t)n * max_det;
+    rt_upload(dn, out_n, (size_t)n * 4); rt_upload(doa, out_anchor, rows * 4); rt_upload(dout, out, rows * dim * 4);
+    gtx::NmsBuffers nb{};
+    nb.max_det = max_det;
+    nb.out_n = dn.as<int>(); nb.out_anchor = doa.as<int>();
+    gtx::launch_obj_feats(dtype, fl, n, nb, dout.as<float>(), ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download(out, dout, rows * dim * 4);
+  });
+}
+
 struct gtx_gmc {
   gtx_ctx* ctx;
   std::unique_ptr<gtx::Gmc> impl;

@@ -120,7 +120,8 @@ constexpr int kSelThreads = 1024;
 constexpr int kSortCap = 512;        // >= kV10Keep, a power of two
 
 template <typename T>
-__global__ __launch_bounds__(kSelThreads) void v10_select_kernel(const HeadParams hp, const NmsBuffers cand, const NmsBuffers sel, float* __restrict__ scores_all) {
+__global__ __launch_bounds__(kSelThreads) void v10_select_kernel(const HeadParams hp, const NmsBuffers cand, const NmsBuffers sel, float* __restrict__ scores_all,
+                                                                    int* __restrict__ kept_anchor) {
   __shared__ unsigned hist[256];
   __shared__ unsigned long long s_prefix;
   __shared__ unsigned s_need, s_n;
@@ -150,6 +151,7 @@ __global__ __launch_bounds__(kSelThreads) void v10_select_kernel(const HeadParam
     if (tid == 0) sel.count[n] = 0;
     return;
   }
+  if (kept_anchor && tid < K) kept_anchor[(size_t)n * kV10Keep + tid] = s_anchor[tid];   // which anchor each row of `scores` belongs to (operator tests)
 
   // ---- every class score of the anchors kept: 16 lanes per anchor, 64 anchors per round (whole waves: the shuffles need all lanes)
   float* scores = scores_all + (size_t)n * kV10Keep * nc;
@@ -259,11 +261,11 @@ __global__ __launch_bounds__(kSortCap) void v10_rows_kernel(const NmsBuffers sel
 
 }  // namespace
 
-void launch_v10_select(int dtype, const HeadParams& hp, int n, const NmsBuffers& cand, const NmsBuffers& sel, float* scores, hipStream_t s) {
+void launch_v10_select(int dtype, const HeadParams& hp, int n, const NmsBuffers& cand, const NmsBuffers& sel, float* scores, hipStream_t s, int* kept_anchor) {
   GTX_CHECK(sel.cap >= kV10Keep && sel.cap <= kSortCap && (!sel.lvl_count || sel.lvl_cap >= kV10Keep), "v10_select: the selection buffers hold %d entries", sel.cap);
   GTX_CHECK((long long)hp.n_anchors * hp.nc < (1ll << 32), "v10_select: %d anchors x %d classes do not fit a 32-bit flat index", hp.n_anchors, hp.nc);
-  if (dtype == DT_F16) hipLaunchKernelGGL(v10_select_kernel<_Float16>, dim3(n), dim3(kSelThreads), 0, s, hp, cand, sel, scores);
-  else hipLaunchKernelGGL(v10_select_kernel<float>, dim3(n), dim3(kSelThreads), 0, s, hp, cand, sel, scores);
+  if (dtype == DT_F16) hipLaunchKernelGGL(v10_select_kernel<_Float16>, dim3(n), dim3(kSelThreads), 0, s, hp, cand, sel, scores, kept_anchor);
+  else hipLaunchKernelGGL(v10_select_kernel<float>, dim3(n), dim3(kSelThreads), 0, s, hp, cand, sel, scores, kept_anchor);
   GTX_HIP(hipGetLastError());
 }
 

@@ -76,9 +76,15 @@ class StabConfig(C.Structure):
     ]
 
 
+class HeadLevel(C.Structure):
+    """gtx_head_level: one Detect level of the post-pass operator hooks."""
+    _fields_ = [("feat", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("cstride", C.c_int), ("cb", C.c_int), ("cc", C.c_int),
+                ("wb", C.c_void_p), ("bb", C.c_void_p), ("wc", C.c_void_p), ("bc", C.c_void_p), ("stride", C.c_float)]
+
+
 # name -> (restype, argtypes); kept in one table so tests can check the export list against
 # include/gtx.h.
-ABI_VERSION = 11       # GTX_ABI_VERSION of include/gtx.h
+ABI_VERSION = 12       # GTX_ABI_VERSION of include/gtx.h
 _P = C.c_void_p
 _SIGNATURES = {
     "gtx_abi_version": (C.c_int, []),
@@ -115,6 +121,14 @@ _SIGNATURES = {
     "gtx_op_rt_gather_refer": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "gtx_op_rt_deform": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "gtx_op_rt_post": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_float, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "gtx_op_head_gate": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "gtx_op_head_boxes": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "gtx_op_nms": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                             C.c_double, C.c_int, _P, _P, _P]),
+    "gtx_op_v10_select": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gtx_op_v10_rows": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                  _P, _P, _P]),
+    "gtx_op_obj_feats": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "gtx_gmc_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "gtx_gmc_destroy": (None, [_P]),
     "gtx_gmc_reset": (C.c_int, [_P]),

@@ -340,3 +340,133 @@ def rt_post(logits: np.ndarray, nc: int, refer: np.ndarray, conf: float, frame_w
     check(ctx.lib.gtx_op_rt_post(ctx.handle, n, nq, nc, ptr(logits), ldl, ptr(refer), float(conf), int(class_mask[0]), int(class_mask[1]),
                                  int(frame_wh[0]), int(frame_wh[1]), max_det, ptr(rows), ptr(out_n), ptr(raw)))
     return rows, out_n, raw
+
+
+# ---------------------------------------------------------------------------- the detector's post-pass kernels
+def head_levels(levels):
+    """Detect levels for the post-pass hooks. levels: dicts with feat [n, h, w, cstride] (float16 / float32), cb, cc, stride and, as
+    the hook needs them, wb [cb, 64], bb [64], wc [nc, cc], bc [nc]. -> (kept arrays, dtype, n, L, gtx_head_level array)."""
+    L = len(levels)
+    arr = (_lib.HeadLevel * max(L, 1))()
+    keep = []
+    feat0 = np.ascontiguousarray(levels[0]["feat"])
+    for i, lv in enumerate(levels):
+        f = np.ascontiguousarray(lv["feat"])
+        assert f.ndim == 4 and f.dtype == feat0.dtype and f.shape[0] == feat0.shape[0]
+        w = {k: _f32(lv.get(k)) for k in ("wb", "bb", "wc", "bc")}
+        keep += [f, w]
+        adr = lambda a: None if a is None else a.ctypes.data
+        arr[i] = _lib.HeadLevel(f.ctypes.data, f.shape[1], f.shape[2], f.shape[3], int(lv["cb"]), int(lv["cc"]), adr(w["wb"]), adr(w["bb"]), adr(w["wc"]),
+                                adr(w["bc"]), float(lv.get("stride", 8.0)))
+    return keep, _dt(feat0), feat0.shape[0], L, arr
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def head_gate(levels, nc: int, conf: float, cap: int, *, class_mask=(2**64 - 1, 2**64 - 1), lvl_cap: int = 0, ctx=None):
+    """The score gate. -> dict: count [n] (the true number that passed), score / anchor / cls [n, cap] (unwritten entries: NaN / -1),
+    lvl_count [n, 4] and lvl_list [n, 4, lvl_cap] when lvl_cap > 0."""
+    ctx = ctx or _lib.default_context()
+    keep, dt, n, L, arr = head_levels(levels)
+    count = np.full(n, -1, np.int32)
+    score, anchor, cls = np.zeros((n, cap), np.float32), np.zeros((n, cap), np.int32), np.zeros((n, cap), np.int32)
+    lc = np.zeros((n, 4), np.int32) if lvl_cap else None
+    ll = np.zeros((n, 4, lvl_cap), np.int32) if lvl_cap else None
+    check(ctx.lib.gtx_op_head_gate(ctx.handle, dt, n, L, arr, nc, float(conf), int(class_mask[0]), int(class_mask[1]), cap, lvl_cap, ptr(count),
+                                   ptr(score), ptr(anchor), ptr(cls), ptr(lc), ptr(ll)))
+    return dict(count=count, score=score, anchor=anchor, cls=cls, lvl_count=lc, lvl_list=ll)
+
+
+def head_boxes(levels, count, cand_anchor, ctx=None) -> np.ndarray:
+    """DFL decode of the first min(count, cap) candidates per image: cand_anchor [n, cap] -> boxes [n, cap, 4] (xyxy, network pixels;
+    NaN where nothing was decoded)."""
+    ctx = ctx or _lib.default_context()
+    keep, dt, n, L, arr = head_levels(levels)
+    count, cand_anchor = _i32(count), _i32(cand_anchor)
+    cap = cand_anchor.shape[1]
+    assert count.shape == (n,) and cand_anchor.shape == (n, cap)
+    box = np.zeros((n, cap, 4), np.float32)
+    check(ctx.lib.gtx_op_head_boxes(ctx.handle, dt, n, L, arr, cap, ptr(count), ptr(cand_anchor), ptr(box)))
+    return box
+
+
+def _rows_io(n, max_det, out_rows, out_n, out_anchor):
+    rows = np.zeros((n, max_det, 6), np.float32) if out_rows is None else np.array(out_rows, dtype=np.float32, order="C")
+    on = np.full(n, -1, np.int32) if out_n is None else np.array(out_n, dtype=np.int32, order="C")
+    oa = np.full((n, max_det), -1, np.int32) if out_anchor is None else np.array(out_anchor, dtype=np.int32, order="C")
+    assert rows.shape == (n, max_det, 6) and on.shape == (n,) and oa.shape == (n, max_det)
+    return rows, on, oa
+
+
+def nms(count, score, anchor, cls, box, *, iou_thr: float, max_det: int, src_hw, net_hw, gain: float, agnostic: bool = False, max_nms: int = 30000,
+        nms_cap: int = 4160, which: int = 0, out_rows=None, out_n=None, out_anchor=None, ctx=None):
+    """launch_nms on given candidates (count [n], score / anchor / cls [n, cap], box [n, cap, 4]). which: 0 both paths, 1 the
+    single-workgroup kernel, 2 the general kernels. -> (rows [n, max_det, 6], out_n [n], out_anchor [n, max_det]): copies of what is
+    given (zeros / -1 / -1 otherwise) with only what the kernels wrote changed."""
+    ctx = ctx or _lib.default_context()
+    count, score, anchor, cls, box = _i32(count), _f32(score), _i32(anchor), _i32(cls), _f32(box)
+    n, cap = score.shape
+    assert count.shape == (n,) and anchor.shape == (n, cap) and cls.shape == (n, cap) and box.shape == (n, cap, 4)
+    rows, on, oa = _rows_io(n, max_det, out_rows, out_n, out_anchor)
+    check(ctx.lib.gtx_op_nms(ctx.handle, n, cap, ptr(count), ptr(score), ptr(anchor), ptr(cls), ptr(box), float(iou_thr), int(agnostic), max_nms, nms_cap,
+                             max_det, int(src_hw[0]), int(src_hw[1]), int(net_hw[0]), int(net_hw[1]), float(gain), which, ptr(rows), ptr(on), ptr(oa)))
+    return rows, on, oa
+
+
+def v10_select(levels, nc: int, conf: float, count, cand_score, cand_anchor, *, sel_cap: int = 304, lvl_cap: int = 0, ctx=None):
+    """YOLOv10's two-stage top-300 cut over the gate's candidates. -> dict: count [n], score / anchor / cls [n, sel_cap], lvl_count /
+    lvl_list when lvl_cap > 0, scores [n, 300, nc] (the kernel's scratch: one row per anchor stage 1 kept, NaN rows past them) and
+    score_anchor [n, 300] (the anchor of each row, -1 past them)."""
+    ctx = ctx or _lib.default_context()
+    keep, dt, n, L, arr = head_levels(levels)
+    count, cand_score, cand_anchor = _i32(count), _f32(cand_score), _i32(cand_anchor)
+    cap = cand_score.shape[1]
+    assert count.shape == (n,) and cand_score.shape == (n, cap) and cand_anchor.shape == (n, cap)
+    sc = np.full(n, -1, np.int32)
+    ss, sa, sk = np.zeros((n, sel_cap), np.float32), np.zeros((n, sel_cap), np.int32), np.zeros((n, sel_cap), np.int32)
+    lc = np.zeros((n, 4), np.int32) if lvl_cap else None
+    ll = np.zeros((n, 4, lvl_cap), np.int32) if lvl_cap else None
+    scores = np.zeros((n, 300, nc), np.float32)
+    score_anchor = np.zeros((n, 300), np.int32)
+    check(ctx.lib.gtx_op_v10_select(ctx.handle, dt, n, L, arr, nc, float(conf), cap, ptr(count), ptr(cand_score), ptr(cand_anchor), sel_cap, lvl_cap,
+                                    ptr(sc), ptr(ss), ptr(sa), ptr(sk), ptr(lc), ptr(ll), ptr(scores), ptr(score_anchor)))
+    return dict(count=sc, score=ss, anchor=sa, cls=sk, lvl_count=lc, lvl_list=ll, scores=scores, score_anchor=score_anchor)
+
+
+def v10_rows(sel_count, sel_score, sel_anchor, sel_cls, sel_box, *, max_det: int, src_hw, net_hw, gain: float, class_mask=(2**64 - 1, 2**64 - 1),
+             out_rows=None, out_n=None, out_anchor=None, ctx=None):
+    """The rows of given selected entries (sel_* [n, sel_cap], sel_box [n, sel_cap, 4]): class mask, max_det cut, scale_boxes + clip.
+    -> (rows, out_n, out_anchor) as nms()."""
+    ctx = ctx or _lib.default_context()
+    sel_count, sel_score, sel_anchor, sel_cls, sel_box = _i32(sel_count), _f32(sel_score), _i32(sel_anchor), _i32(sel_cls), _f32(sel_box)
+    n, cap = sel_score.shape
+    assert sel_count.shape == (n,) and sel_anchor.shape == (n, cap) and sel_cls.shape == (n, cap) and sel_box.shape == (n, cap, 4)
+    rows, on, oa = _rows_io(n, max_det, out_rows, out_n, out_anchor)
+    check(ctx.lib.gtx_op_v10_rows(ctx.handle, n, cap, ptr(sel_count), ptr(sel_score), ptr(sel_anchor), ptr(sel_cls), ptr(sel_box), int(class_mask[0]),
+                                  int(class_mask[1]), max_det, int(src_hw[0]), int(src_hw[1]), int(net_hw[0]), int(net_hw[1]), float(gain), ptr(rows), ptr(on),
+                                  ptr(oa)))
+    return rows, on, oa
+
+
+def obj_feats(maps, c, dim: int, out_n, out_anchor, *, coff=0, split: bool = False, out=None, ctx=None) -> np.ndarray:
+    """Appearance vectors: maps = level maps [n, h, w, cstride] (c[l] channels from coff[l]; split=True: float32 arrays in the pair
+    format on the device), out_n [n], out_anchor [n, max_det] -> out [n, max_det, dim] (a copy of `out` with rows [0, out_n) written)."""
+    ctx = ctx or _lib.default_context()
+    maps = [np.ascontiguousarray(m) for m in maps]
+    L = len(maps)
+    coff = [coff] * L if np.isscalar(coff) else list(coff)
+    c = [c] * L if np.isscalar(c) else list(c)
+    assert len(coff) == L and len(c) == L and all(m.ndim == 4 and m.dtype == maps[0].dtype and m.shape[0] == maps[0].shape[0] for m in maps)
+    n = maps[0].shape[0]
+    out_n, out_anchor = _i32(out_n), _i32(out_anchor)
+    max_det = out_anchor.shape[1]
+    assert out_n.shape == (n,) and out_anchor.shape == (n, max_det)
+    out = np.zeros((n, max_det, dim), np.float32) if out is None else np.array(out, dtype=np.float32, order="C")
+    assert out.shape == (n, max_det, dim)
+    ptrs = (C.c_void_p * max(L, 1))(*[m.ctypes.data for m in maps])
+    ints = lambda v: (C.c_int * max(L, 1))(*[int(i) for i in v])
+    check(ctx.lib.gtx_op_obj_feats(ctx.handle, _map_fmt(maps[0], split), n, L, ptrs, ints(m.shape[1] for m in maps), ints(m.shape[2] for m in maps),
+                                   ints(m.shape[3] for m in maps), ints(coff), ints(c), dim, max_det, ptr(out_n), ptr(out_anchor), ptr(out)))
+    return out

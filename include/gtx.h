@@ -53,8 +53,10 @@ extern "C" {
  *     points only, no struct or existing signature changed, so the number stays. gtx_op_psa_attention added and the embedder takes
  *     YOLO11-cls tensors (C2PSA = model.9): the same, the number stays. gtx_det_config.end2end appended at the struct's end (YOLOv10's
  *     one-to-one head; 0 = every earlier behaviour) and gtx_op_dwconv added: the number stays.
- * 11: gtx_op_rt_{linear, layernorm, mha, topk, gather_refer, deform, post} added: RT-DETR's token-side kernels one launcher at a time. */
-#define GTX_ABI_VERSION 11
+ * 11: gtx_op_rt_{linear, layernorm, mha, topk, gather_refer, deform, post} added: RT-DETR's token-side kernels one launcher at a time.
+ * 12: gtx_op_{head_gate, head_boxes, nms, v10_select, v10_rows, obj_feats} and gtx_head_level added: the detector's post-pass kernels
+ *     one launcher at a time. A detector with more than 2^20 anchors per image is refused (the NMS sort key's anchor field). */
+#define GTX_ABI_VERSION 12
 
 typedef enum gtx_status {
   GTX_OK = 0,
@@ -260,6 +262,62 @@ int gtx_op_rt_deform(gtx_ctx* ctx, int fmt, int n, int n_levels, const void* con
  * class c. nq <= 512, nc <= 128. */
 int gtx_op_rt_post(gtx_ctx* ctx, int n, int nq, int nc, const float* logits, int ldl, const float* refer, float conf, uint64_t class_mask0,
                    uint64_t class_mask1, int frame_w, int frame_h, int max_det, float* out_rows, int* out_n, float* raw);
+
+/* The detector's post-pass kernels (csrc/det_kernels.hpp, csrc/v10_select.hip), one launcher per call, for the operator-level tests
+ * (tests/test_head_ops_gpu.py). Host arrays in, host arrays out; every size and every index is checked before the GPU is touched: what
+ * a launcher would refuse, or a kernel would silently mishandle, comes back as GTX_ERR_INVALID.
+ *
+ * One Detect level: feat [n][h][w][cstride] (GTX_F16 or GTX_F32) with the box branch's cb channels at 0 and the class branch's cc
+ * channels at cb; wb [cb][64] (the final box 1x1 convolution, transposed) and bb [64]; wc [nc][cc] and bc [nc]. The gate reads
+ * wc / bc, the box decode wb / bb; what a hook does not read may be NULL. Anchors are numbered level by level, row-major. */
+typedef struct gtx_head_level {
+  const void* feat;
+  int h, w, cstride, cb, cc;
+  const float* wb;
+  const float* bb;
+  const float* wc;
+  const float* bc;
+  float stride;
+} gtx_head_level;
+/* The score gate: per anchor the best class (ties: the lower class) of sigmoid(wc . f + bc); kept when its score > conf and the
+ * class mask has its bit. count [n]: how many passed, also above cap; cand_score / cand_anchor / cand_cls [n][cap]: the first cap
+ * of them in arrival order (unwritten entries: all bits set). lvl_cap > 0: lvl_count [n][4] and lvl_list [n][4][lvl_cap] file the
+ * stored entries with an index below lvl_cap under their level. cc a multiple of 8; cb and cstride multiples of 8 (F16) or 4 (F32):
+ * the kernel's 16-byte loads; nc in [1, 128]; at most 4 levels. */
+int gtx_op_head_gate(gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx_head_level* lv, int nc, float conf, uint64_t class_mask0,
+                     uint64_t class_mask1, int cap, int lvl_cap, int* count, float* cand_score, int* cand_anchor, int* cand_cls, int* lvl_count,
+                     int* lvl_list);
+/* DFL decode of the first min(count, cap) candidates of every image: cand_box [n][cap][4] xyxy in network pixels (entries past
+ * them: all bits set). cb <= 128 and no level's cb above level 0's. */
+int gtx_op_head_boxes(gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx_head_level* lv, int cap, const int* count, const int* cand_anchor,
+                      float* cand_box);
+/* NMS of given candidates (count [n], cand_* [n][cap]; anchors in [0, 2^20)): order score descending then anchor ascending, greedy
+ * suppression at IoU > iou_thr (boxes offset by 7680 * class unless agnostic), the max_nms best only, max_det rows, scale_boxes +
+ * clip to the frame. which: 0 both paths, 1 the single-workgroup kernel only (an image beyond 4096 candidates or max_det beyond 2048
+ * gets out_n = 0), 2 the general kernels only (an image the single-workgroup kernel covers is left alone). nms_cap: the general
+ * path's sort capacity, a multiple of 64 up to 32768. out_rows [n][max_det][6], out_n [n], out_anchor [n][max_det] are read as they
+ * are before the launch and come back with only what the kernels wrote changed. */
+int gtx_op_nms(gtx_ctx* ctx, int n, int cap, const int* count, const float* cand_score, const int* cand_anchor, const int* cand_cls,
+               const float* cand_box, float iou_thr, int agnostic, int max_nms, int nms_cap, int max_det, int src_h, int src_w, int net_h, int net_w,
+               double gain, int which, float* out_rows, int* out_n, int* out_anchor);
+/* YOLOv10's two-stage top-300 cut over the gate's candidates (count [n], cand_score / cand_anchor [n][cap]): sel_count [n], sel_score /
+ * sel_anchor / sel_cls [n][sel_cap] in score order (ties: the lower anchor * nc + class), lvl_count / lvl_list as the gate's when
+ * lvl_cap > 0 (then >= 300); scores [n][300][nc]: the kernel's scratch, one row per anchor stage 1 kept, in no particular order, and
+ * score_anchor [n][300]: the anchor of each row. sel_cap in [300, 512]. Unwritten entries: all bits set. */
+int gtx_op_v10_select(gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx_head_level* lv, int nc, float conf, int cap, const int* count,
+                      const float* cand_score, const int* cand_anchor, int sel_cap, int lvl_cap, int* sel_count, float* sel_score, int* sel_anchor,
+                      int* sel_cls, int* lvl_count, int* lvl_list, float* scores, int* score_anchor);
+/* The rows of given selected entries (sel_* [n][sel_cap], sel_box [n][sel_cap][4], sel_cap <= 512): the class mask, the max_det
+ * cut, scale_boxes + clip. out_rows / out_n / out_anchor as gtx_op_nms. */
+int gtx_op_v10_rows(gtx_ctx* ctx, int n, int sel_cap, const int* sel_count, const float* sel_score, const int* sel_anchor, const int* sel_cls,
+                    const float* sel_box, uint64_t class_mask0, uint64_t class_mask1, int max_det, int src_h, int src_w, int net_h, int net_w,
+                    double gain, float* out_rows, int* out_n, int* out_anchor);
+/* Appearance vectors: per image the rows [0, min(out_n, max_det)) of out [n][max_det][dim] = the c[l] channels from coff[l] at anchor
+ * out_anchor [n][max_det] of its level's map [n][h][w][cstride], averaged in consecutive groups of c[l] / dim; the other rows come
+ * back as given. Maps: GTX_F16, GTX_F32 or GTX_F32S (plain fp32 arrays, converted to the pair format on the way; cstride a multiple
+ * of 8). At most 4 levels. */
+int gtx_op_obj_feats(gtx_ctx* ctx, int dtype, int n, int n_levels, const void* const* maps, const int* h, const int* w, const int* cstride,
+                     const int* coff, const int* c, int dim, int max_det, const int* out_n, const int* out_anchor, float* out);
 
 /* Brute-force L2 2-nearest-neighbour search of unit-norm 128-d float descriptors (RootSIFT): what
  * cv2.BFMatcher(NORM_L2).knnMatch(query, train, k=2) returns inside stabilo for the orthophoto

@@ -25,7 +25,7 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/gtx.h but not exported by libgtx.so"
     assert declared == set(_lib._SIGNATURES), declared ^ set(_lib._SIGNATURES)
-    assert lib.gtx_abi_version() == _lib.ABI_VERSION == 11
+    assert lib.gtx_abi_version() == _lib.ABI_VERSION == 12
 
 
 def test_errors_are_codes_with_messages_not_exceptions():
@@ -82,6 +82,97 @@ def test_rtdetr_hooks_refuse_bad_sizes_before_any_launch():
     assert lib.gtx_detector_create(None, C.byref(cfg), C.byref(h)) == -3 and b"128 classes" in lib.gtx_last_error() and not h.value
     cfg.arch = 0
     assert lib.gtx_detector_create(None, C.byref(cfg), C.byref(h)) == -3 and not h.value
+
+
+def test_head_hooks_refuse_bad_sizes_before_any_launch():
+    """Host only: what the post-pass launchers would refuse, or their kernels would mishandle in silence, comes back as an error code
+    from the operator hooks with no context given."""
+    from geotrax_amd import _lib
+
+    lib = _lib.load()
+    f = np.zeros(8192, np.float32)
+    i = np.zeros(4096, np.int32)
+    p = _lib.ptr
+    full = 2**64 - 1
+
+    def levels(n_levels=1, h=2, w=2, cstride=32, cb=16, cc=16, cbs=None):
+        arr = (_lib.HeadLevel * n_levels)()
+        for l in range(n_levels):
+            arr[l] = _lib.HeadLevel(f.ctypes.data, h, w, cstride, cb if cbs is None else cbs[l], cc, f.ctypes.data, f.ctypes.data, f.ctypes.data,
+                                    f.ctypes.data, 8.0)
+        return arr
+
+    def gate(lv, n_levels=1, dtype=1, nc=4):
+        return lib.gtx_op_head_gate(None, dtype, 1, n_levels, lv, nc, 0.25, full, full, 16, 0, p(i), p(f), p(i), p(i), None, None)
+
+    assert gate(levels()) == -1 and b"ctx is NULL" in lib.gtx_last_error()                                # the sizes were fine
+    assert gate(levels(cc=12)) == -1 and b"multiple of 8" in lib.gtx_last_error()                         # cc >> 3 chunks would drop channels
+    assert gate(levels(cb=2, cstride=36)) == -1 and b"16-byte" in lib.gtx_last_error()                    # cb breaks load8's alignment (fp32)
+    assert gate(levels(cb=4, cstride=36), dtype=0) == -1 and b"16-byte" in lib.gtx_last_error()           # fine in fp32, not in fp16
+    assert gate(levels(cb=4, cstride=36)) == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert gate(levels(cstride=34)) == -1 and b"16-byte" in lib.gtx_last_error()                          # cstride does
+    assert gate(levels(), nc=0) == -1 and b"128 classes" in lib.gtx_last_error()
+    assert gate(levels(), nc=129) == -1 and b"128 classes" in lib.gtx_last_error()
+    assert gate(levels(5), n_levels=5) == -1 and b"4 levels" in lib.gtx_last_error()
+    assert gate(levels(cstride=24)) == -1 and b"do not fit" in lib.gtx_last_error()                       # cb + cc > cstride
+
+    def boxes(lv, n_levels=1, anchor=0):
+        i[:] = 0
+        i[0] = 1                                                                                          # count = 1
+        a = np.full(16, anchor, np.int32)
+        return lib.gtx_op_head_boxes(None, 1, 1, n_levels, lv, 16, p(i), p(a), p(f))
+
+    assert boxes(levels()) == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert boxes(levels(2, cstride=64, cbs=[16, 32]), 2) == -1 and b"level 0" in lib.gtx_last_error()                  # the LDS slices would overlap
+    assert boxes(levels(cb=136, cstride=160)) == -1 and b"128 box channels" in lib.gtx_last_error()
+    assert boxes(levels(), anchor=4) == -1 and b"outside the level set" in lib.gtx_last_error()           # 2 x 2 anchors
+
+    def nms(anchor=0, nms_cap=64, which=0, score=0.5, count=1, max_det=4):
+        c = np.array([count], np.int32)
+        s = np.full(16, score, np.float32)
+        a = np.full(16, anchor, np.int32)
+        return lib.gtx_op_nms(None, 1, 16, p(c), p(s), p(a), p(i), p(f), 0.5, 0, 30000, nms_cap, max_det, 64, 64, 64, 64, 1.0, which, p(f), p(i), p(i))
+
+    assert nms() == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert nms(anchor=2**20 - 1) == -1 and b"ctx is NULL" in lib.gtx_last_error()                         # the sort key's 20 anchor bits
+    assert nms(anchor=2**20) == -1 and b"outside the level set" in lib.gtx_last_error()
+    assert nms(nms_cap=100) == -1 and b"nms_cap" in lib.gtx_last_error()
+    assert nms(nms_cap=32832) == -1 and b"nms_cap" in lib.gtx_last_error()
+    assert nms(which=3) == -1 and b"which" in lib.gtx_last_error()
+    assert nms(score=0.0) == -1 and b"positive" in lib.gtx_last_error()
+    assert nms(count=-1) == -1 and b"negative count" in lib.gtx_last_error()
+    assert nms(max_det=0) == -1
+
+    def select(sel_cap=304, lvl_cap=0, anchor=0):
+        c = np.array([1], np.int32)
+        s = np.full(16, 0.5, np.float32)
+        a = np.full(16, anchor, np.int32)
+        return lib.gtx_op_v10_select(None, 1, 1, 1, levels(), 4, 0.25, 16, p(c), p(s), p(a), sel_cap, lvl_cap, p(i), p(f), p(i), p(i), p(i), p(i), p(f), p(i))
+
+    assert select() == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert select(sel_cap=299) == -1 and b"sel_cap" in lib.gtx_last_error()
+    assert select(sel_cap=513) == -1 and b"sel_cap" in lib.gtx_last_error()
+    assert select(lvl_cap=299) == -1 and b"lvl_cap" in lib.gtx_last_error()
+    assert select(anchor=4) == -1 and b"outside the level set" in lib.gtx_last_error()
+    assert lib.gtx_op_v10_rows(None, 1, 513, p(i), p(f), p(i), p(i), p(f), full, full, 4, 64, 64, 64, 64, 1.0, p(f), p(i), p(i)) == -1
+    assert b"sel_cap" in lib.gtx_last_error()
+    assert lib.gtx_op_v10_rows(None, 1, 304, p(i), p(f), p(i), p(i), p(f), full, full, 4, 64, 64, 64, 64, 0.0, p(f), p(i), p(i)) == -1
+    assert b"geometry" in lib.gtx_last_error()
+
+    maps = (C.c_void_p * 1)(f.ctypes.data)
+    one = lambda v: (C.c_int * 1)(v)
+
+    def feats(dtype=1, cstride=32, coff=0, c=16, dim=8, anchor=0):
+        n_out = np.array([1], np.int32)
+        a = np.full(4, anchor, np.int32)
+        return lib.gtx_op_obj_feats(None, dtype, 1, 1, maps, one(2), one(2), one(cstride), one(coff), one(c), dim, 4, p(n_out), p(a), p(f))
+
+    assert feats() == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert feats(dim=12) == -1 and b"multiple of dim" in lib.gtx_last_error()
+    assert feats(coff=24) == -1 and b"does not fit" in lib.gtx_last_error()
+    assert feats(dtype=2, cstride=36) == -1 and b"multiples of 8" in lib.gtx_last_error()
+    assert feats(dtype=3) == -1 and b"format" in lib.gtx_last_error()
+    assert feats(anchor=4) == -1 and b"outside the level set" in lib.gtx_last_error()
 
 
 def test_no_gpu_means_loud_failure_not_fallback():
