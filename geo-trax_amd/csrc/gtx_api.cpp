@@ -1575,6 +1575,56 @@ int gtx_stabilizer_last_ms(gtx_stabilizer* st, float* ms) {
   return guarded([&] { need(st, "st"); need(ms, "ms"); *ms = st->impl->last_ms(); });
 }
 
+int gtx_stabilizer_keep_pass(gtx_stabilizer* st, int on) {
+  return guarded([&] { need(st, "st"); st->impl->keep_pass(on != 0); });
+}
+int gtx_stabilizer_level(gtx_stabilizer* st, int which, int i, int* h, int* w, uint8_t* out, int64_t cap) {
+  return guarded([&] {
+    need(st, "st"); need(h, "h"); need(w, "w");
+    if (cap < 0) gtx::fail(GTX_ERR_INVALID, "stabilizer level: negative cap");
+    st->impl->level(which, i, h, w, out, (size_t)cap);
+  });
+}
+int gtx_stabilizer_candidates(gtx_stabilizer* st, int which, int i, int cap, int* n, int* pix, int* score, int* n_elig, int* n_kp, int* n_dropped) {
+  return guarded([&] { need(st, "st"); need(n, "n"); st->impl->candidates(which, i, cap, n, pix, score, n_elig, n_kp, n_dropped); });
+}
+
+// ---- the stabilizer's matcher and RANSAC kernel, one launch each (tests/test_orb_ops_gpu.py). As for the hooks above: sizes are
+// checked before anything touches the GPU.
+int gtx_op_orb_match(gtx_ctx* ctx, const uint8_t* desc_q, int nq, int slots_q, const uint8_t* desc_t, int nt, int slots_t, float ratio, int keep_all,
+                     const float* xy_q, const float* xy_t, int* best_idx, int* best_d, int* second_d, int* m_q, int* m_t, int* m_d, float* m_pts,
+                     int* n_match) {
+  return guarded([&] {
+    const char* op = "orb_match";
+    if (nq < 1 || nt < 0 || slots_q < nq || slots_t < std::max(nt, 1) || slots_q > (1 << 16) || slots_t > (1 << 20)) rt_bad(op, "1 <= nq <= slots_q <= 65536, 0 <= nt <= slots_t <= 2^20, slots_t >= 1");
+    if ((double)gtx::cdiv(slots_t, 256) * slots_q > 6.4e7) rt_bad(op, "the per-chunk partials would pass 768 MB");
+    if (!(ratio >= 0.f && ratio <= 4.f)) rt_bad(op, "ratio in [0, 4]");
+    need(desc_q, "desc_q"); need(xy_q, "xy_q");
+    if (nt > 0) { need(desc_t, "desc_t"); need(xy_t, "xy_t"); }
+    need(best_idx, "best_idx"); need(best_d, "best_d"); need(second_d, "second_d"); need(m_q, "m_q"); need(m_t, "m_t"); need(m_d, "m_d");
+    need(m_pts, "m_pts"); need(n_match, "n_match"); need(ctx, "ctx");
+    gtx::op_orb_match(ctx, desc_q, nq, slots_q, desc_t, nt, slots_t, ratio, keep_all != 0, xy_q, xy_t, best_idx, best_d, second_d, m_q, m_t, m_d, m_pts,
+                      n_match);
+  });
+}
+
+int gtx_op_orb_ransac(gtx_ctx* ctx, const float* pts, int n, uint32_t seed, int n_hyp, int frame_w, int frame_h, float thr, int affine, int* best,
+                      int64_t* cost, double H[9]) {
+  return guarded([&] {
+    const char* op = "orb_ransac";
+    if (n < 0 || n > (1 << 20)) rt_bad(op, "0 <= n <= 2^20 point pairs");
+    if (n_hyp < 1 || n_hyp > 65536) rt_bad(op, "1..65536 hypotheses (the winner's index has 16 bits of the key)");
+    if (frame_w < 1 || frame_h < 1 || frame_w > (1 << 16) || frame_h > (1 << 16)) rt_bad(op, "bad frame size");
+    if (!(thr > 0.f && thr <= 64.f)) rt_bad(op, "threshold in (0, 64] px (a match costs at most thr^2 * 1024, the sum has 47 bits)");
+    if (affine != 0 && affine != 1) rt_bad(op, "affine is 0 or 1");
+    if (n > 0) need(pts, "pts");
+    need(best, "best"); need(cost, "cost"); need(H, "H"); need(ctx, "ctx");
+    long long c = 0;
+    gtx::op_orb_ransac(ctx, pts, n, seed, n_hyp, frame_w, frame_h, thr, affine, best, &c, H);
+    *cost = c;
+  });
+}
+
 int gtx_stabilizer_pattern(gtx_stabilizer* st, int8_t* out) {
   return guarded([&] {
     need(out, "out");

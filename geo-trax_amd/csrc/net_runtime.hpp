@@ -17,7 +17,9 @@ struct gtx_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   hipDeviceProp_t prop{};
+  void* orb_op_state = nullptr;      // device words of gtx_op_orb_match / gtx_op_orb_ransac (stabilizer.hip), allocated by their first call
   ~gtx_ctx() {
+    if (orb_op_state) (void)hipFree(orb_op_state);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };

@@ -473,7 +473,8 @@ struct KeyPoint {
 __device__ __forceinline__ unsigned long long flip_key(long k) { return (unsigned long long)k ^ 0x8000000000000000ull; }
 
 constexpr int kSortCap = 8192;   // eligible candidates the in-LDS sort handles (more: radix-select path)
-constexpr int kTopCap = 2048;    // keypoints per level the radix-select path keeps (level 0 takes ~22 % of max_features)
+constexpr int kTopCap = kSortCap; // keypoints per level the radix-select path keeps: whatever the sort path can deliver (plan() refuses a level that wants more)
+constexpr int kSelectLds = kSortCap * 12 + 256 * 4 + 16;   // select_kernel's dynamic LDS: the sort's {key, pix} pairs; the radix path's kept set + histogram + 3 scalars
 
 // Stage 2 of the selection, one workgroup per level: the n_want best Harris keys of the eligible set, ordered by
 // (key desc, pix asc). Usual case (n <= 8192): one bitonic sort of {key, pix} pairs in LDS (select_by_sort). More eligible
@@ -617,7 +618,7 @@ __device__ void select_by_radix(unsigned char* s_raw, const Cand* __restrict__ c
 
 __global__ __launch_bounds__(1024) void select_kernel(const Cand* __restrict__ cand, const int* __restrict__ cand_n,
                                                       const Levels L, KeyPoint* __restrict__ kps, int* __restrict__ kp_n) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];            // kSortCap * 12 bytes
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];            // kSelectLds bytes
   const int li = blockIdx.x;
   const Level lv = L.l[li];
   const int n = min(cand_n[li], lv.cand_cap);
@@ -981,6 +982,7 @@ __device__ __forceinline__ bool make_hypothesis(const float4* __restrict__ pts, 
 struct StabResult {
   int n_match, best, n_cur, pad;
   double H[9];
+  long cost;        // the winner's MSAC cost in 1/1024 px^2 (0 when there is none); the record stays 96 bytes with its padding
 };
 
 // Hypothesise, score and pick the winner in ONE launch (round 4; three launches before: solve, score, argmin).
@@ -1057,6 +1059,7 @@ __global__ __launch_bounds__(512) void ransac_kernel(const float4* __restrict__ 
     res->n_cur = *n_cur_p;
     res->best = b;
     for (int k = 0; k < 9; ++k) res->H[k] = H[k];
+    res->cost = b >= 0 ? (long)(best_key >> 16) : 0;
     atomicExch(&state[0], kNoHyp);                                         // re-arm for the next pass on this stream
     atomicExch(&state[1], 0ull);
   }
@@ -1149,6 +1152,15 @@ struct Stabilizer::Impl {
   bool valid = false;
   int stats[4] = {0, 0, 0, 0};
 
+  // Debug read-backs of the last extract pass (keep_pass): the plan it ran with and a copy of the candidate / eligible counters
+  // taken in front of describe_kernel, which clears them. Nothing is copied unless asked for.
+  static constexpr int kSnapInts = kPyrLevels * kCandSub + kPyrLevels;
+  bool keep = false;
+  int last_which = -1;           // 0 = the reference set's pass, 1 = the current set's, -1 = none kept yet
+  Levels last_L{};
+  DevBuf d_snap;
+  const Levels& kept(int which, int i) const;
+
   void plan(Levels& L, int max_features, int& slots);
   void build_rects(const float* boxes, int n, std::vector<int4>& rects) const;
   void extract(const uint8_t* gray_dev, const float* boxes, int n, const Levels& L, int slots, Feat& out);
@@ -1172,9 +1184,14 @@ void Stabilizer::Impl::plan(Levels& L, int max_features, int& slots) {
     lv.off = off;
     off += lv.w * lv.h;
     lv.cand_off = coff;
-    lv.sub_cap = cdiv(std::max(4096, lv.w * lv.h / 16), kCandSub);
+    lv.tiles_x = cdiv(lv.w, kTileW);
+    // Nothing may be dropped (a dropped candidate changes the keypoint set, and which one is dropped depends on the order the
+    // atomics arrive in): two pixels of one 2x2 block are neighbours, so the strict 3x3 maximum test lets at most one of them
+    // through, a 64x16 tile holds 256 such blocks, and sub-list s takes the tiles t with t % kCandSub == s.
+    lv.sub_cap = cdiv(lv.tiles_x * cdiv(lv.h, kTileH), kCandSub) * (kTileW / 2) * (kTileH / 2);
     lv.cand_cap = lv.sub_cap * kCandSub;
     coff += lv.cand_cap;
+    GTX_CHECK(coff < (1 << 28), "stabilizer: %dx%d working image needs too many candidate slots", gw, gh);
     if (i < L.n - 1) {
       lv.n_want = (int)std::lround(want);
       sum += lv.n_want;
@@ -1184,7 +1201,6 @@ void Stabilizer::Impl::plan(Levels& L, int max_features, int& slots) {
     }
     lv.kp_off = koff;
     koff += lv.n_want;
-    lv.tiles_x = cdiv(lv.w, 64);
     lv.tile_begin = i == 0 ? 0 : L.l[i - 1].tile_begin + L.l[i - 1].tiles_x * cdiv(L.l[i - 1].h, 16);
   }
   L.n_tiles = L.l[L.n - 1].tile_begin + L.l[L.n - 1].tiles_x * cdiv(L.l[L.n - 1].h, 16);
@@ -1230,7 +1246,9 @@ void Stabilizer::Impl::plan(Levels& L, int max_features, int& slots) {
       first += n;
     }
   }
-  GTX_CHECK(max_features * 0.25 < kTopCap, "stabilizer: at most ~8000 features per image are supported");
+  for (int i = 0; i < L.n; ++i)
+    GTX_CHECK(L.l[i].n_want <= kTopCap, "stabilizer: level %d would keep %d of %d features, at most %d per level are supported", i, L.l[i].n_want,
+              max_features, kTopCap);
   pyr_bytes = off;
   cand_total = coff;
   slots = koff;
@@ -1266,6 +1284,8 @@ Stabilizer::Stabilizer(gtx_ctx* ctx, const gtx_stab_config& cfg) : impl_(new Imp
   S.d_counters.alloc(sizeof(int) * (kCounterInts));
   GTX_HIP(hipMemset(S.d_counters.p, 0, sizeof(int) * (kCounterInts)));
   S.d_kp_n.alloc(sizeof(int) * kPyrLevels);
+  GTX_HIP(hipMemset(S.d_kp_n.p, 0, sizeof(int) * kPyrLevels));
+  S.d_snap.alloc(sizeof(int) * Impl::kSnapInts);
   S.d_kps.alloc(sizeof(KeyPoint) * slots);
   for (Impl::Feat* f : {&S.ref, &S.cur}) {
     f->kps.alloc(sizeof(KeyPoint) * slots);
@@ -1300,7 +1320,7 @@ Stabilizer::Stabilizer(gtx_ctx* ctx, const gtx_stab_config& cfg) : impl_(new Imp
   stabilizer_pattern_table(S.pattern);   // rotated sampling patterns
   S.d_pattern.alloc(S.pattern.size());
   GTX_HIP(hipMemcpy(S.d_pattern.p, S.pattern.data(), S.pattern.size(), hipMemcpyHostToDevice));
-  GTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kSortCap * 12));
+  GTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kSelectLds));
   {
     const Levels& L = S.lev_cur;
     std::vector<unsigned> tab;
@@ -1397,8 +1417,13 @@ void Stabilizer::Impl::extract(const uint8_t* gray_dev, const float* boxes, int 
   hipLaunchKernelGGL(fast_detect_kernel, dim3(L.n_tiles), dim3(256), 0, s, d_rects.as<int4>(), n_rects, gw, gh, L, cfg.fast_threshold,
                      d_cand.as<Cand>(), cand_n, hist);
   hipLaunchKernelGGL(harris_kernel, dim3(512), dim3(256), 0, s, L, d_cand.as<Cand>(), cand_n, hist, d_elig.as<Cand>(), elig_n);
-  hipLaunchKernelGGL(select_kernel, dim3(L.n), dim3(1024), kSortCap * 12, s, d_elig.as<Cand>(), elig_n, L, d_kps.as<KeyPoint>(),
+  hipLaunchKernelGGL(select_kernel, dim3(L.n), dim3(1024), kSelectLds, s, d_elig.as<Cand>(), elig_n, L, d_kps.as<KeyPoint>(),
                      d_kp_n.as<int>());
+  if (keep) {
+    GTX_HIP(hipMemcpyAsync(d_snap.p, d_counters.p, sizeof(int) * kSnapInts, hipMemcpyDeviceToDevice, s));
+    last_L = L;
+    last_which = &out == &ref ? 0 : 1;
+  }
   hipLaunchKernelGGL(describe_kernel, dim3(cdiv(slots, 4)), dim3(256), 0, s, L, d_kps.as<KeyPoint>(), d_kp_n.as<int>(),
                      d_pattern.as<int8_t>(), out.kps.as<KeyPoint>(), out.desc.as<unsigned long long>(), out.xy.as<float2>(), out.n.as<int>(),
                      1.0f / cfg.downsample_ratio, slots, d_counters.as<int>(), kCounterInts);
@@ -1545,25 +1570,46 @@ bool refine_homography(const std::vector<float4>& pts, double cx, double cy, dou
 
 }  // namespace
 
-// Asynchronous half of a stabilize pass: match -> ratio -> RANSAC on the stream, then two D2H
-// copies (result record, match points) into pinned memory and an event.
+namespace {
+// The match launch: a grid over the keypoint SLOTS of both sets (their counts are read on the device). Buffers: query / train
+// descriptors and counts, the per-chunk partials [cdiv(slots_t, 256)][slots_q], the ticket (0 between launches), the outputs.
+struct MatchBufs {
+  const unsigned long long *q, *t;
+  const int *nq, *nt;
+  const float2 *q_xy, *t_xy;
+  int *part_idx, *part_d1, *part_d2;
+  unsigned* ticket;
+  int *best_idx, *best_d, *second_d, *m_q, *m_t, *m_d;
+  float4* m_pts;
+  int* n_match;
+};
+void launch_match_kernel(hipStream_t s, int slots_q, int slots_t, const MatchBufs& B, float ratio, int keep_all) {
+  hipLaunchKernelGGL(match_kernel, dim3(cdiv(slots_q, 256), cdiv(slots_t, kMatchChunk)), dim3(256), 0, s, B.q, B.nq, B.t, B.nt, slots_q, B.part_idx,
+                     B.part_d1, B.part_d2, B.ticket, ratio, keep_all, B.q_xy, B.t_xy, B.best_idx, B.best_d, B.second_d, B.m_q, B.m_t, B.m_d, B.m_pts,
+                     B.n_match);
+}
+// The RANSAC launch: n_hyp hypotheses, 8 per workgroup, on a state that is armed ({all ones, 0}) between launches.
+void launch_ransac_kernel(hipStream_t s, const float4* pts, const int* n_p, const int* n_cur_p, unsigned seed, int n_hyp, int frame_w, int frame_h,
+                          int affine, float thr, unsigned long long* state, StabResult* res) {
+  const double cx = frame_w / 2.0, cy = frame_h / 2.0, sc = 2.0 / frame_w;
+  hipLaunchKernelGGL(ransac_kernel, dim3(cdiv(n_hyp, 8)), dim3(512), 0, s, pts, n_p, n_cur_p, seed, n_hyp, cx, cy, sc, affine, thr * thr, state, res);
+}
+}  // namespace
+
 void Stabilizer::Impl::launch_match() {
-  hipStream_t s = ctx->stream;
-  const int max_q = slots_cur, n_chunks = cdiv(slots_ref, kMatchChunk);
-  hipLaunchKernelGGL(match_kernel, dim3(cdiv(slots_cur, 256), n_chunks), dim3(256), 0, s, cur.desc.as<unsigned long long>(),
-                     cur.n.as<int>(), ref.desc.as<unsigned long long>(), ref.n.as<int>(), max_q, d_pidx.as<int>(), d_pd1.as<int>(),
-                     d_pd2.as<int>(), d_mticket.as<unsigned>(), cfg.filter_ratio, cfg.filter_type == 1 ? 1 : 0, cur.xy.as<float2>(), ref.xy.as<float2>(),
-                     d_bidx.as<int>(), d_bd.as<int>(), d_sd.as<int>(), d_mq.as<int>(), d_mt.as<int>(), d_md.as<int>(), d_mpts(),
-                     d_nmatch.as<int>());
+  MatchBufs B{cur.desc.as<unsigned long long>(), ref.desc.as<unsigned long long>(), cur.n.as<int>(), ref.n.as<int>(), cur.xy.as<float2>(),
+              ref.xy.as<float2>(), d_pidx.as<int>(), d_pd1.as<int>(), d_pd2.as<int>(), d_mticket.as<unsigned>(), d_bidx.as<int>(), d_bd.as<int>(),
+              d_sd.as<int>(), d_mq.as<int>(), d_mt.as<int>(), d_md.as<int>(), d_mpts(), d_nmatch.as<int>()};
+  launch_match_kernel(ctx->stream, slots_cur, slots_ref, B, cfg.filter_ratio, cfg.filter_type == 1 ? 1 : 0);
 }
 
+// Asynchronous half of a stabilize pass: match -> ratio -> RANSAC on the stream, then two D2H
+// copies (result record, match points) into pinned memory and an event.
 void Stabilizer::Impl::submit_match() {
   hipStream_t s = ctx->stream;
   launch_match();
-  const double cx = fw / 2.0, cy = fh / 2.0, sc = 2.0 / fw;
-  const float thr2 = cfg.ransac_threshold * cfg.ransac_threshold;
-  hipLaunchKernelGGL(ransac_kernel, dim3(cdiv(n_hyp, 8)), dim3(512), 0, s, d_mpts(), d_nmatch.as<int>(), cur.n.as<int>(), cfg.seed, n_hyp,
-                     cx, cy, sc, cfg.affine ? 1 : 0, thr2, d_rstate.as<unsigned long long>(), d_res());
+  launch_ransac_kernel(s, d_mpts(), d_nmatch.as<int>(), cur.n.as<int>(), cfg.seed, n_hyp, fw, fh, cfg.affine ? 1 : 0, cfg.ransac_threshold,
+                       d_rstate.as<unsigned long long>(), d_res());
   GTX_HIP(hipGetLastError());
   GTX_HIP(hipMemcpyAsync(h_out, d_out.p, kOutPts + sizeof(float4) * slots_cur, hipMemcpyDeviceToHost, s));
   GTX_HIP(hipEventRecord(t1_ev, s));
@@ -1718,6 +1764,62 @@ void Stabilizer::matches(int cap, int* n, int* cur_idx, int* ref_idx, int* dist)
   if (dist) GTX_HIP(hipMemcpy(dist, S.d_md.p, 4 * (size_t)k, hipMemcpyDeviceToHost));
 }
 
+// ---- read-backs of the last extract pass (debug accessors for the per-kernel tests)
+void Stabilizer::keep_pass(bool on) { impl_->keep = on; }
+
+const Levels& Stabilizer::Impl::kept(int which, int i) const {
+  GTX_CHECK(which == 0 || which == 1, "stabilizer: which must be 0 (reference) or 1 (current)");
+  if (last_which < 0) fail(GTX_ERR_STATE, "stabilizer: no pass was kept (keep_pass before the frame)");
+  if (which != last_which) fail(GTX_ERR_STATE, "stabilizer: only the last extract pass is kept, and that was the %s set's", last_which == 0 ? "reference" : "current");
+  GTX_CHECK(i >= 0 && i < last_L.n, "stabilizer: level %d of %d", i, last_L.n);
+  return last_L;
+}
+
+void Stabilizer::level(int which, int i, int* h, int* w, uint8_t* out, size_t cap) {
+  Impl& S = *impl_;
+  const Level& lv = S.kept(which, i).l[i];
+  *h = lv.h;
+  *w = lv.w;
+  if (!out) return;
+  GTX_CHECK(cap >= (size_t)lv.w * lv.h, "stabilizer: level %d holds %d x %d bytes", i, lv.w, lv.h);
+  GTX_HIP(hipSetDevice(S.ctx->device));
+  GTX_HIP(hipStreamSynchronize(S.ctx->stream));
+  GTX_HIP(hipMemcpy(out, lv.img, (size_t)lv.w * lv.h, hipMemcpyDeviceToHost));
+}
+
+void Stabilizer::candidates(int which, int i, int cap, int* n, int* pix, int* score, int* n_elig, int* n_kp, int* n_dropped) {
+  Impl& S = *impl_;
+  const Level& lv = S.kept(which, i).l[i];
+  GTX_HIP(hipSetDevice(S.ctx->device));
+  GTX_HIP(hipStreamSynchronize(S.ctx->stream));
+  int snap[Impl::kSnapInts], kp_n[kPyrLevels];
+  GTX_HIP(hipMemcpy(snap, S.d_snap.p, sizeof snap, hipMemcpyDeviceToHost));
+  GTX_HIP(hipMemcpy(kp_n, S.d_kp_n.p, sizeof kp_n, hipMemcpyDeviceToHost));
+  int total = 0, dropped = 0;
+  for (int sb = 0; sb < kCandSub; ++sb) {
+    const int cnt = snap[i * kCandSub + sb];
+    total += std::min(cnt, lv.sub_cap);
+    dropped += std::max(cnt - lv.sub_cap, 0);
+  }
+  *n = total;
+  if (n_elig) *n_elig = snap[kPyrLevels * kCandSub + i];
+  if (n_kp) *n_kp = kp_n[i];
+  if (n_dropped) *n_dropped = dropped;
+  if (!pix && !score) return;
+  GTX_CHECK(cap >= total, "stabilizer: level %d holds %d candidates, room for %d", i, total, cap);
+  std::vector<Cand> buf;
+  for (int sb = 0, o = 0; sb < kCandSub; ++sb) {
+    const int cnt = std::min(snap[i * kCandSub + sb], lv.sub_cap);
+    if (cnt == 0) continue;
+    buf.resize(cnt);
+    GTX_HIP(hipMemcpy(buf.data(), S.d_cand.as<Cand>() + lv.cand_off + (size_t)sb * lv.sub_cap, sizeof(Cand) * cnt, hipMemcpyDeviceToHost));
+    for (int k = 0; k < cnt; ++k, ++o) {
+      if (pix) pix[o] = buf[k].pix;
+      if (score) score[o] = buf[k].score;
+    }
+  }
+}
+
 void Stabilizer::pattern(int8_t* out) const { std::memcpy(out, impl_->pattern.data(), impl_->pattern.size()); }
 
 // Blocking robust homography from matched point pairs already in HBM (registration path): the same
@@ -1748,8 +1850,8 @@ bool ransac_homography(int device, hipStream_t s, const float4* d_pts, int n_mat
   GTX_HIP(hipMemcpyAsync(d_state.p, armed, sizeof armed, hipMemcpyHostToDevice, s));
   const double cx = frame_w / 2.0, cy = frame_h / 2.0, sc = 2.0 / frame_w;
   GTX_CHECK(n_hyp <= 65536, "ransac: at most 65536 hypotheses (got %d)", n_hyp);
-  hipLaunchKernelGGL(ransac_kernel, dim3(cdiv(n_hyp, 8)), dim3(512), 0, s, d_pts, d_n.as<int>(), d_n.as<int>() + 1, seed, n_hyp, cx, cy, sc, 0,
-                     threshold * threshold, d_state.as<unsigned long long>(), d_res.as<StabResult>());
+  launch_ransac_kernel(s, d_pts, d_n.as<int>(), d_n.as<int>() + 1, seed, n_hyp, frame_w, frame_h, 0, threshold, d_state.as<unsigned long long>(),
+                       d_res.as<StabResult>());
   GTX_HIP(hipGetLastError());
   StabResult R;
   std::vector<float4> pts(n_match);
@@ -1764,6 +1866,86 @@ bool ransac_homography(int device, hipStream_t s, const float4* d_pts, int n_mat
   if (!refine_homography(pts, cx, cy, sc, (double)threshold, Hc, n_inliers)) return false;
   std::memcpy(H, Hc, sizeof Hc);
   return true;
+}
+
+// ---- operator hooks (gtx_op_orb_match / gtx_op_orb_ransac): one launch of match_kernel / ransac_kernel on host arrays. The ticket
+// and the RANSAC state live with the context and are initialised once, when the first hook call allocates them: every later call
+// finds them as the launch before it left them, which is how the kernels' re-arming is exercised. The caller has validated all sizes.
+namespace {
+struct OrbOpState {
+  unsigned long long ransac[2];
+  unsigned ticket, pad;
+};
+OrbOpState* orb_op_state(gtx_ctx* ctx) {
+  if (!ctx->orb_op_state) {
+    const OrbOpState armed{{kNoHyp, 0ull}, 0u, 0u};
+    GTX_HIP(hipMalloc(&ctx->orb_op_state, sizeof armed));
+    GTX_HIP(hipMemcpy(ctx->orb_op_state, &armed, sizeof armed, hipMemcpyHostToDevice));
+  }
+  return static_cast<OrbOpState*>(ctx->orb_op_state);
+}
+void upload(DevBuf& d, const void* src, size_t bytes, size_t room) {
+  d.alloc(std::max(room, bytes));
+  if (bytes) GTX_HIP(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+}
+void fill_ff(DevBuf& d, size_t bytes) {
+  d.alloc(bytes);
+  GTX_HIP(hipMemset(d.p, 0xFF, d.bytes));
+}
+}  // namespace
+
+void op_orb_match(gtx_ctx* ctx, const uint8_t* desc_q, int nq, int slots_q, const uint8_t* desc_t, int nt, int slots_t, float ratio, int keep_all,
+                  const float* xy_q, const float* xy_t, int* best_idx, int* best_d, int* second_d, int* m_q, int* m_t, int* m_d, float* m_pts,
+                  int* n_match) {
+  GTX_HIP(hipSetDevice(ctx->device));
+  OrbOpState* st = orb_op_state(ctx);
+  DevBuf dq, dt, dqxy, dtxy, dn, pi, p1, p2, bi, bd, sd, mq, mt, md, mp, nm;
+  upload(dq, desc_q, 32 * (size_t)nq, 32 * (size_t)slots_q);
+  upload(dt, desc_t, 32 * (size_t)nt, 32 * (size_t)slots_t);
+  upload(dqxy, xy_q, 8 * (size_t)nq, 8 * (size_t)slots_q);
+  upload(dtxy, xy_t, 8 * (size_t)nt, 8 * (size_t)slots_t);
+  const int counts[2] = {nq, nt};
+  upload(dn, counts, sizeof counts, sizeof counts);
+  const size_t parts = 4 * (size_t)cdiv(slots_t, kMatchChunk) * slots_q, per_q = 4 * (size_t)slots_q;
+  fill_ff(pi, parts); fill_ff(p1, parts); fill_ff(p2, parts);
+  fill_ff(bi, per_q); fill_ff(bd, per_q); fill_ff(sd, per_q); fill_ff(mq, per_q); fill_ff(mt, per_q); fill_ff(md, per_q); fill_ff(mp, 4 * per_q);
+  fill_ff(nm, sizeof(int));
+  MatchBufs B{dq.as<unsigned long long>(), dt.as<unsigned long long>(), dn.as<int>(), dn.as<int>() + 1, dqxy.as<float2>(), dtxy.as<float2>(),
+              pi.as<int>(), p1.as<int>(), p2.as<int>(), &st->ticket, bi.as<int>(), bd.as<int>(), sd.as<int>(), mq.as<int>(), mt.as<int>(), md.as<int>(),
+              mp.as<float4>(), nm.as<int>()};
+  launch_match_kernel(ctx->stream, slots_q, slots_t, B, ratio, keep_all);
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipStreamSynchronize(ctx->stream));
+  const size_t out_q = 4 * (size_t)nq;
+  GTX_HIP(hipMemcpy(n_match, nm.p, sizeof(int), hipMemcpyDeviceToHost));
+  if (nq == 0) return;
+  GTX_HIP(hipMemcpy(best_idx, bi.p, out_q, hipMemcpyDeviceToHost));
+  GTX_HIP(hipMemcpy(best_d, bd.p, out_q, hipMemcpyDeviceToHost));
+  GTX_HIP(hipMemcpy(second_d, sd.p, out_q, hipMemcpyDeviceToHost));
+  GTX_HIP(hipMemcpy(m_q, mq.p, out_q, hipMemcpyDeviceToHost));
+  GTX_HIP(hipMemcpy(m_t, mt.p, out_q, hipMemcpyDeviceToHost));
+  GTX_HIP(hipMemcpy(m_d, md.p, out_q, hipMemcpyDeviceToHost));
+  GTX_HIP(hipMemcpy(m_pts, mp.p, 4 * out_q, hipMemcpyDeviceToHost));
+}
+
+void op_orb_ransac(gtx_ctx* ctx, const float* pts, int n, unsigned seed, int n_hyp, int frame_w, int frame_h, float thr, int affine, int* best,
+                   long long* cost, double H[9]) {
+  GTX_HIP(hipSetDevice(ctx->device));
+  OrbOpState* st = orb_op_state(ctx);
+  DevBuf dp, dn, dr;
+  upload(dp, pts, sizeof(float4) * (size_t)n, sizeof(float4));
+  const int counts[2] = {n, n};
+  upload(dn, counts, sizeof counts, sizeof counts);
+  fill_ff(dr, sizeof(StabResult));
+  launch_ransac_kernel(ctx->stream, dp.as<float4>(), dn.as<int>(), dn.as<int>() + 1, seed, n_hyp, frame_w, frame_h, affine, thr, st->ransac,
+                       dr.as<StabResult>());
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipStreamSynchronize(ctx->stream));
+  StabResult R;
+  GTX_HIP(hipMemcpy(&R, dr.p, sizeof R, hipMemcpyDeviceToHost));
+  *best = R.best;
+  *cost = R.cost;
+  std::memcpy(H, R.H, sizeof R.H);
 }
 
 }  // namespace gtx

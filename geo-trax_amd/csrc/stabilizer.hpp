@@ -27,6 +27,13 @@ class Stabilizer {
   void matches(int cap, int* n, int* cur_idx, int* ref_idx, int* dist);
   // rotated sampling pattern table [256 bins][256 tests][ax, ay, bx, by] int8 (data, for the oracle)
   void pattern(int8_t* out) const;
+  // Debug read-backs of the LAST extract pass (like Sift::pyramid): keep_pass(true) makes every later pass keep its plan and a
+  // copy of its candidate counters (one small device copy per pass; nothing when off). `which` must name the set that pass filled.
+  void keep_pass(bool on);
+  void level(int which, int i, int* h, int* w, uint8_t* out, size_t cap);           // pyramid level i: h x w bytes (out may be null: sizes only)
+  // level i after FAST + 3x3 NMS + mask: n (pix, score) pairs in no particular order; the count stage 1 passed on to the Harris
+  // ranking, the keypoints kept, and the candidates that found their sub-list full (the lists are sized so that this is 0)
+  void candidates(int which, int i, int cap, int* n, int* pix, int* score, int* n_elig, int* n_kp, int* n_dropped);
   // GPU time (ms, stream-ordered events) of the last collected submit_gray_dev pass: keypoints -> matching -> RANSAC
   float last_ms() const;
 
@@ -60,6 +67,14 @@ void clahe_image(gtx_ctx* ctx, const uint8_t* gray, int h, int w, uint8_t* out);
 // (x, y) -> (z, w) in HBM; threshold in pixels of the destination. false: no model.
 bool ransac_homography(int device, hipStream_t s, const float4* d_pts, int n_match, unsigned seed, int n_hyp, int frame_w, int frame_h,
                        float threshold, double H[9], int* n_inliers);
+
+// Operator hooks: one launch of the matcher / of the RANSAC kernel on host arrays, exactly as the stabilizer launches them (sizes are
+// validated by the caller, gtx_api.cpp). Their ticket / state words live with the context and are never re-initialised by the host.
+void op_orb_match(gtx_ctx* ctx, const uint8_t* desc_q, int nq, int slots_q, const uint8_t* desc_t, int nt, int slots_t, float ratio, int keep_all,
+                  const float* xy_q, const float* xy_t, int* best_idx, int* best_d, int* second_d, int* m_q, int* m_t, int* m_d, float* m_pts,
+                  int* n_match);
+void op_orb_ransac(gtx_ctx* ctx, const float* pts, int n, unsigned seed, int n_hyp, int frame_w, int frame_h, float thr, int affine, int* best,
+                   long long* cost, double H[9]);
 }  // namespace gtx
 
 struct gtx_stabilizer {

@@ -84,7 +84,7 @@ class HeadLevel(C.Structure):
 
 # name -> (restype, argtypes); kept in one table so tests can check the export list against
 # include/gtx.h.
-ABI_VERSION = 12       # GTX_ABI_VERSION of include/gtx.h
+ABI_VERSION = 13       # GTX_ABI_VERSION of include/gtx.h
 _P = C.c_void_p
 _SIGNATURES = {
     "gtx_abi_version": (C.c_int, []),
@@ -222,6 +222,13 @@ _SIGNATURES = {
     "gtx_stabilizer_matches": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), _P, _P, _P]),
     "gtx_stabilizer_pattern": (C.c_int, [_P, _P]),
     "gtx_stabilizer_last_ms": (C.c_int, [_P, _P]),
+    "gtx_stabilizer_keep_pass": (C.c_int, [_P, C.c_int]),
+    "gtx_stabilizer_level": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _P, C.c_int64]),
+    "gtx_stabilizer_candidates": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                            C.POINTER(C.c_int)]),
+    "gtx_op_orb_match": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gtx_op_orb_ransac": (C.c_int, [_P, _P, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int),
+                                    C.POINTER(C.c_int64), _P]),
     "gtx_warp_boxes": (C.c_int, [_P, _P, C.c_int, _P]),
     "gtx_perspective_points": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
     "gtx_op_estimate_affine_partial": (C.c_int, [_P, _P, C.c_int, C.c_uint, _P, _P, _P]),

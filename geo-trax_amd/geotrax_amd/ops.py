@@ -470,3 +470,39 @@ def obj_feats(maps, c, dim: int, out_n, out_anchor, *, coff=0, split: bool = Fal
     check(ctx.lib.gtx_op_obj_feats(ctx.handle, _map_fmt(maps[0], split), n, L, ptrs, ints(m.shape[1] for m in maps), ints(m.shape[2] for m in maps),
                                    ints(m.shape[3] for m in maps), ints(coff), ints(c), dim, max_det, ptr(out_n), ptr(out_anchor), ptr(out)))
     return out
+
+
+def orb_match(desc_q, desc_t, ratio: float, *, keep_all: bool = False, xy_q=None, xy_t=None, slots_q: int | None = None, slots_t: int | None = None,
+              ctx=None):
+    """One launch of the stabilizer's matcher: desc_q [nq, 32], desc_t [nt, 32] u8 (xy_* [n, 2] f32, zeros when not given); slots_*: the
+    keypoint slots the grid covers (default: the counts). -> dict: best_idx / best_d / second_d [nq], and the compacted q / t / d [m],
+    pts [m, 4] of the queries that pass the ratio test (keep_all: that have a neighbour)."""
+    ctx = ctx or _lib.default_context()
+    dq = np.ascontiguousarray(desc_q, dtype=np.uint8).reshape(-1, 32)
+    dt = np.ascontiguousarray(desc_t, dtype=np.uint8).reshape(-1, 32)
+    nq, nt = len(dq), len(dt)
+    xq = np.zeros((nq, 2), np.float32) if xy_q is None else _f32(xy_q)
+    xt = np.zeros((max(nt, 1), 2), np.float32) if xy_t is None else _f32(xy_t)
+    assert xq.shape == (nq, 2) and (xy_t is None or xt.shape == (nt, 2))
+    if nt == 0:
+        dt = np.zeros((1, 32), np.uint8)
+    bi, bd, sd, mq, mt, md = (np.zeros(nq, np.int32) for _ in range(6))
+    mp = np.zeros((nq, 4), np.float32)
+    m = C.c_int(-1)
+    check(ctx.lib.gtx_op_orb_match(ctx.handle, ptr(dq), nq, nq if slots_q is None else slots_q, ptr(dt), nt, max(nt, 1) if slots_t is None else slots_t,
+                                   float(ratio), int(keep_all), ptr(xq), ptr(xt), ptr(bi), ptr(bd), ptr(sd), ptr(mq), ptr(mt), ptr(md), ptr(mp),
+                                   C.byref(m)))
+    k = m.value
+    return dict(best_idx=bi, best_d=bd, second_d=sd, q=mq[:k].copy(), t=mt[:k].copy(), d=md[:k].copy(), pts=mp[:k].copy(), n=k,
+                tail=(mq[k:], mt[k:], md[k:]))
+
+
+def orb_ransac(pts, seed: int, n_hyp: int, frame_wh, thr: float, *, affine: bool = False, ctx=None):
+    """One launch of the stabilizer's RANSAC kernel on pts [n, 4] f32 = (x, y) -> (z, w), no refit. -> (winner index or -1, its integer
+    MSAC cost in 1/1024 px^2, its H [3, 3] f64 as sampled: all zero when there is no winner)."""
+    ctx = ctx or _lib.default_context()
+    p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 4)
+    best, cost, H = C.c_int(-2), C.c_int64(-1), np.full(9, np.nan, np.float64)
+    check(ctx.lib.gtx_op_orb_ransac(ctx.handle, ptr(p) if len(p) else None, len(p), int(seed) & 0xFFFFFFFF, int(n_hyp), int(frame_wh[0]), int(frame_wh[1]),
+                                    float(thr), int(affine), C.byref(best), C.byref(cost), ptr(H)))
+    return best.value, cost.value, H.reshape(3, 3)

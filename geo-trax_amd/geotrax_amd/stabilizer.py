@@ -256,6 +256,30 @@ class Stabilizer:
         k = n.value
         return q[:k].copy(), t[:k].copy(), d[:k].copy()
 
+    def keep_pass(self, on: bool = True) -> None:
+        """Every later extract pass keeps what level() and candidates() read back (off by default: nothing is kept)."""
+        check(self.ctx.lib.gtx_stabilizer_keep_pass(self.handle, int(on)))
+
+    def level(self, which: str, i: int) -> np.ndarray:
+        """Pyramid level i of the last extract pass [h, w] u8; `which` ('ref' / 'cur') must name the set that pass filled."""
+        w_ = 0 if which == "ref" else 1
+        h, w = C.c_int(), C.c_int()
+        check(self.ctx.lib.gtx_stabilizer_level(self.handle, w_, i, C.byref(h), C.byref(w), None, 0))
+        out = np.zeros((h.value, w.value), np.uint8)
+        check(self.ctx.lib.gtx_stabilizer_level(self.handle, w_, i, C.byref(h), C.byref(w), ptr(out), out.size))
+        return out
+
+    def candidates(self, which: str, i: int) -> dict:
+        """Level i of the last extract pass after FAST, NMS and the mask: pix (y * w + x) and score in no particular order, n_elig
+        (what stage 1 handed to the Harris ranking), n_kp (keypoints kept), dropped (candidates that found their sub-list full)."""
+        w_ = 0 if which == "ref" else 1
+        n, ne, nk, nd = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(self.ctx.lib.gtx_stabilizer_candidates(self.handle, w_, i, 0, C.byref(n), None, None, C.byref(ne), C.byref(nk), C.byref(nd)))
+        pix, score = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32)
+        if n.value:
+            check(self.ctx.lib.gtx_stabilizer_candidates(self.handle, w_, i, n.value, C.byref(n), ptr(pix), ptr(score), None, None, None))
+        return dict(pix=pix, score=score, n_elig=ne.value, n_kp=nk.value, dropped=nd.value)
+
     def pattern(self) -> np.ndarray:
         out = np.zeros((256, 256, 4), np.int8)
         check(self.ctx.lib.gtx_stabilizer_pattern(self.handle, ptr(out)))

@@ -55,8 +55,11 @@ extern "C" {
  *     one-to-one head; 0 = every earlier behaviour) and gtx_op_dwconv added: the number stays.
  * 11: gtx_op_rt_{linear, layernorm, mha, topk, gather_refer, deform, post} added: RT-DETR's token-side kernels one launcher at a time.
  * 12: gtx_op_{head_gate, head_boxes, nms, v10_select, v10_rows, obj_feats} and gtx_head_level added: the detector's post-pass kernels
- *     one launcher at a time. A detector with more than 2^20 anchors per image is refused (the NMS sort key's anchor field). */
-#define GTX_ABI_VERSION 12
+ *     one launcher at a time. A detector with more than 2^20 anchors per image is refused (the NMS sort key's anchor field).
+ * 13: gtx_stabilizer_{keep_pass, level, candidates} (read-backs of the last extract pass) and gtx_op_orb_{match, ransac} (the
+ *     stabilizer's matcher and RANSAC kernel one launch at a time) added. A stabilizer plan is refused per level (more than 8192
+ *     keypoints on one level) instead of by max_features; the candidate lists are sized so that no FAST corner can be dropped. */
+#define GTX_ABI_VERSION 13
 
 typedef enum gtx_status {
   GTX_OK = 0,
@@ -646,6 +649,35 @@ int gtx_stabilizer_keypoints(gtx_stabilizer* st, int which /*0 ref, 1 cur*/, int
 /* Good matches of the last stabilize call: pairs (cur index, ref index) and Hamming distance. */
 int gtx_stabilizer_matches(gtx_stabilizer* st, int cap, int* n, int* cur_idx, int* ref_idx,
                            int* dist);
+
+/* Read-backs of the LAST extract pass, for the per-kernel tests. _keep_pass(st, 1) makes every later pass keep its level plan and a
+ * copy of its candidate counters (one small device copy per pass; off by default, and then nothing is kept). `which` (0 ref, 1 cur)
+ * must name the set the last pass filled: the pyramid and the candidate lists are shared by both.
+ * _level: pyramid level i as h x w bytes (out may be NULL: sizes only; cap = room in out).
+ * _candidates: level i after FAST, 3x3 non-maximum suppression and the mask: n (pix = y * w + x, FAST score) pairs in no particular
+ * order (pix / score may be NULL: counts only; cap = room in each); n_elig = how many of them stage 1 handed to the Harris ranking,
+ * n_kp = keypoints kept on the level, n_dropped = candidates that found their sub-list full (0: the lists hold every possible corner). */
+int gtx_stabilizer_keep_pass(gtx_stabilizer* st, int on);
+int gtx_stabilizer_level(gtx_stabilizer* st, int which, int i, int* h, int* w, uint8_t* out, int64_t cap);
+int gtx_stabilizer_candidates(gtx_stabilizer* st, int which, int i, int cap, int* n, int* pix, int* score, int* n_elig, int* n_kp,
+                              int* n_dropped);
+
+/* The stabilizer's matcher on its own: ONE launch of its kernel, shaped as the stabilizer shapes it (a grid over slots_q x slots_t
+ * keypoint slots, slots_* >= n*, of which nq / nt are filled). desc_q [nq][32], desc_t [nt][32] u8, xy_q [nq][2], xy_t [nt][2] f32.
+ * Per query: best_idx (lowest index among equals; -1 when nt = 0), best_d, second_d (2^30 where there is none). Then the Lowe test
+ * best_d < ratio * second_d in fp32 (keep_all: every query with a neighbour), survivors compacted in query order: m_q, m_t, m_d
+ * [nq], m_pts [nq][4] = (xy_q, xy_t), n_match. Entries past n_match: all bits set. The kernel's ticket word lives with the context
+ * and is written by the host once, before the first call: every later call relies on the launch before it having re-armed it. */
+int gtx_op_orb_match(gtx_ctx* ctx, const uint8_t* desc_q, int nq, int slots_q, const uint8_t* desc_t, int nt, int slots_t, float ratio,
+                     int keep_all, const float* xy_q, const float* xy_t, int* best_idx, int* best_d, int* second_d, int* m_q, int* m_t,
+                     int* m_d, float* m_pts, int* n_match);
+/* The stabilizer's RANSAC kernel on its own, without the host refit: n_hyp <= 65536 hypotheses (4-point homographies, or 3-point
+ * affine maps) sampled by the counter hash of (seed, hypothesis, draw) from pts [n][4] = (x, y) -> (z, w), scored by the truncated
+ * squared error in units of 1/1024 px^2. best = the winner's index (lowest cost, then lowest index; -1: no hypothesis could be
+ * made), cost = its integer cost, H = its matrix as sampled (all zero when best = -1). The state words live with the context like
+ * the matcher's ticket. */
+int gtx_op_orb_ransac(gtx_ctx* ctx, const float* pts, int n, uint32_t seed, int n_hyp, int frame_w, int frame_h, float thr, int affine,
+                      int* best, int64_t* cost, double H[9]);
 
 /* The steered-BRIEF sampling table the descriptor kernel uses: [256 orientation bins][256
  * tests][ax, ay, bx, by] int8 = 262144 bytes. `st` may be NULL (the table does not depend on the

@@ -194,9 +194,11 @@ def mask_rects(boxes_xywh, ratio: float, margin: float, gw: int, gh: int):
     return rects
 
 
-def extract(gray: np.ndarray, boxes_xywh, cfg: dict, max_features: int, pattern: np.ndarray):
+def extract(gray: np.ndarray, boxes_xywh, cfg: dict, max_features: int, pattern: np.ndarray, stages: list | None = None):
     """gray: level-0 image (already downsampled). Returns dict(xy [K,2] f32 full-res, level, bin,
-    desc [K,32] u8, px [K,2] level pixels), ordered level by level, rank order inside a level."""
+    desc [K,32] u8, px [K,2] level pixels), ordered level by level, rank order inside a level.
+    stages: a list that receives one dict per level -- img, pix / score of the corners left by FAST, the 3x3 maximum test and
+    the mask (pixel order), n_want, n_elig (what stage 1 hands to the Harris ranking) and n_kp (keypoints kept)."""
     gh, gw = gray.shape
     plan = level_plan(gw, gh, cfg["n_levels"], cfg["scale_factor"], max_features)
     mask = None
@@ -224,6 +226,9 @@ def extract(gray: np.ndarray, boxes_xywh, cfg: dict, max_features: int, pattern:
             y0 = np.minimum((ys.astype(np.int64) * gh + h // 2) // h, gh - 1)
             ok = mask[y0, x0] != 0
             ys, xs = ys[ok], xs[ok]
+        if stages is not None:
+            stages.append(dict(img=img, pix=(ys.astype(np.int64) * w + xs).astype(np.int32), score=score[ys, xs].astype(np.int32),
+                               n_want=n_want, n_elig=0, n_kp=0))
         if len(xs) == 0 or n_want == 0:
             continue
         # stage 1 (as OpenCV's ORB): the 2*n_want best FAST scores, everything tied with the last kept
@@ -233,6 +238,8 @@ def extract(gray: np.ndarray, boxes_xywh, cfg: dict, max_features: int, pattern:
             sel = fs >= cut
             ys, xs = ys[sel], xs[sel]
         # stage 2: the n_want best Harris responses, ties to the smaller pixel index
+        if stages is not None:
+            stages[-1].update(n_elig=len(xs), n_kp=min(n_want, len(xs)))
         keys = harris_keys(img, ys, xs)
         pix = ys.astype(np.int64) * w + xs
         order = np.lexsort((pix, -keys))[:n_want]
@@ -357,17 +364,30 @@ def _errors(H, p, q):
     return dx * dx + dy * dy
 
 
-def ransac_homography(pts_q: np.ndarray, pts_t: np.ndarray, frame_wh, thr: float, n_hyp: int, seed: int, affine: bool = False):
-    """pts_*: [n,2] float32 full-res pixels (query -> train). Returns (H 3x3 f64 or None, n_inliers).
-    affine: 3-point samples and an affine minimal solve instead of 4-point homographies; same scoring."""
+def _basis_ok(x, y):
+    """The kernel's test of a 4-point sample (csrc/stabilizer.hip basis_matrix): the first three points are not collinear, and the
+    fourth is on none of the lines through two of them -- |det| and the three barycentric-like weights above 1e-9 in normalised units."""
+    det = x[0] * (y[1] - y[2]) - x[1] * (y[0] - y[2]) + x[2] * (y[0] - y[1])
+    if not abs(det) > 1e-9:
+        return False
+    l0 = (x[3] * (y[1] - y[2]) - x[1] * (y[3] - y[2]) + x[2] * (y[3] - y[1])) / det
+    l1 = (x[0] * (y[3] - y[2]) - x[3] * (y[0] - y[2]) + x[2] * (y[0] - y[3])) / det
+    l2 = (x[0] * (y[1] - y[3]) - x[1] * (y[0] - y[3]) + x[3] * (y[0] - y[1])) / det
+    return abs(l0) > 1e-9 and abs(l1) > 1e-9 and abs(l2) > 1e-9
+
+
+def ransac_hypotheses(pts_q: np.ndarray, pts_t: np.ndarray, frame_wh, thr: float, n_hyp: int, seed: int, affine: bool = False):
+    """The hypothesis stage of ransac_homography on its own: (winner index or -1, its MSAC cost quantised to 1/1024 px^2, its H 3x3 f64
+    as sampled -- not normalised, not refined -- or None). The winner is the lowest cost, then the lowest hypothesis index. A sample
+    with three collinear points, in either image, makes no hypothesis (the kernel's test, _basis_ok)."""
     n = len(pts_q)
     ns = 3 if affine else 4
     if n < ns:
-        return None, 0
+        return -1, 0, None
     p, q = pts_q.astype(np.float64), pts_t.astype(np.float64)
     cx, cy, sc = frame_wh[0] / 2.0, frame_wh[1] / 2.0, 2.0 / frame_wh[0]
     thr2 = float(np.float32(thr) * np.float32(thr))
-    best_cost, best_H = None, None
+    best, best_cost, best_H = -1, 0, None
     for hyp in range(n_hyp):
         idx, ctr = [], 0
         while len(idx) < ns:
@@ -383,6 +403,8 @@ def ransac_homography(pts_q: np.ndarray, pts_t: np.ndarray, frame_wh, thr: float
                 continue
             hvec = np.concatenate([np.linalg.solve(M, u), np.linalg.solve(M, v), [0.0, 0.0]])
         else:
+            if not (_basis_ok(x, y) and _basis_ok(u, v)):
+                continue
             A = np.zeros((8, 8))
             rhs = np.zeros(8)
             for i in range(4):
@@ -401,10 +423,20 @@ def ransac_homography(pts_q: np.ndarray, pts_t: np.ndarray, frame_wh, thr: float
         with np.errstate(all="ignore"):
             e = np.where(ok, np.minimum(_errors(H, p, q), thr2), thr2)
         cost = int(np.floor(e * 1024.0 + 0.5).sum())
-        if best_cost is None or cost < best_cost:
-            best_cost, best_H = cost, H
+        if best_H is None or cost < best_cost:
+            best, best_cost, best_H = hyp, cost, H
+    return best, best_cost, best_H
+
+
+def ransac_homography(pts_q: np.ndarray, pts_t: np.ndarray, frame_wh, thr: float, n_hyp: int, seed: int, affine: bool = False):
+    """pts_*: [n,2] float32 full-res pixels (query -> train). Returns (H 3x3 f64 or None, n_inliers).
+    affine: 3-point samples and an affine minimal solve instead of 4-point homographies; same scoring.
+    ransac_hypotheses picks the winner, refine_homography refits it."""
+    _, _, best_H = ransac_hypotheses(pts_q, pts_t, frame_wh, thr, n_hyp, seed, affine)
     if best_H is None:
         return None, 0
+    p, q = pts_q.astype(np.float64), pts_t.astype(np.float64)
+    cx, cy, sc = frame_wh[0] / 2.0, frame_wh[1] / 2.0, 2.0 / frame_wh[0]
     return refine_homography(best_H / best_H[2, 2], p, q, cx, cy, sc, float(np.float32(thr)), affine)
 
 

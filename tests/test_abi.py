@@ -25,7 +25,7 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/gtx.h but not exported by libgtx.so"
     assert declared == set(_lib._SIGNATURES), declared ^ set(_lib._SIGNATURES)
-    assert lib.gtx_abi_version() == _lib.ABI_VERSION == 12
+    assert lib.gtx_abi_version() == _lib.ABI_VERSION == 13
 
 
 def test_errors_are_codes_with_messages_not_exceptions():
@@ -173,6 +173,51 @@ def test_head_hooks_refuse_bad_sizes_before_any_launch():
     assert feats(dtype=2, cstride=36) == -1 and b"multiples of 8" in lib.gtx_last_error()
     assert feats(dtype=3) == -1 and b"format" in lib.gtx_last_error()
     assert feats(anchor=4) == -1 and b"outside the level set" in lib.gtx_last_error()
+
+
+def test_orb_hooks_refuse_bad_sizes_before_any_launch():
+    """Host only: the matcher and RANSAC hooks and the stabilizer's read-backs answer bad sizes and missing arrays with an error
+    code, with no context or object given."""
+    from geotrax_amd import _lib
+
+    lib = _lib.load()
+    d = np.zeros((64, 32), np.uint8)
+    f = np.zeros(4096, np.float32)
+    i = np.zeros(4096, np.int32)
+    p = _lib.ptr
+    n = C.c_int()
+
+    def match(nq=8, slots_q=8, nt=8, slots_t=8, ratio=0.9, dt=d, xt=f):
+        return lib.gtx_op_orb_match(None, p(d), nq, slots_q, p(dt), nt, slots_t, ratio, 0, p(f), p(xt), p(i), p(i), p(i), p(i), p(i), p(i), p(f), C.byref(n))
+
+    assert match() == -1 and b"ctx is NULL" in lib.gtx_last_error()                                     # the sizes were fine
+    assert match(nt=0, slots_t=1, dt=None, xt=None) == -1 and b"ctx is NULL" in lib.gtx_last_error()    # no train keypoint is a case
+    assert match(nq=0) == -1 and b"orb_match" in lib.gtx_last_error()
+    assert match(slots_q=7) == -1 and b"orb_match" in lib.gtx_last_error()                              # fewer slots than keypoints
+    assert match(nt=9) == -1 and b"orb_match" in lib.gtx_last_error()
+    assert match(nt=0, slots_t=0) == -1 and b"orb_match" in lib.gtx_last_error()                        # an empty grid
+    assert match(slots_q=(1 << 16) + 1) == -1 and b"orb_match" in lib.gtx_last_error()
+    assert match(slots_q=1 << 16, slots_t=1 << 20) == -1 and b"partials" in lib.gtx_last_error()
+    assert match(ratio=float("nan")) == -1 and b"ratio" in lib.gtx_last_error()
+    assert match(dt=None) == -1 and b"desc_t is NULL" in lib.gtx_last_error()
+    best, cost = C.c_int(), C.c_int64()
+    H = np.zeros(9, np.float64)
+
+    def ransac(n_pts=8, n_hyp=64, w=640, h=480, thr=2.0, affine=0, pts=f):
+        return lib.gtx_op_orb_ransac(None, p(pts), n_pts, 0, n_hyp, w, h, thr, affine, C.byref(best), C.byref(cost), p(H))
+
+    assert ransac() == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert ransac(n_pts=0, pts=None) == -1 and b"ctx is NULL" in lib.gtx_last_error()                   # no pair at all: no winner, not an error
+    assert ransac(n_pts=-1) == -1 and b"orb_ransac" in lib.gtx_last_error()
+    assert ransac(n_hyp=65537) == -1 and b"65536" in lib.gtx_last_error()                               # the key's 16 index bits
+    assert ransac(n_hyp=0) == -1 and b"65536" in lib.gtx_last_error()
+    assert ransac(w=0) == -1 and b"frame" in lib.gtx_last_error()
+    assert ransac(thr=0.0) == -1 and b"threshold" in lib.gtx_last_error()
+    assert ransac(affine=2) == -1 and b"affine" in lib.gtx_last_error()
+    assert ransac(pts=None) == -1 and b"pts is NULL" in lib.gtx_last_error()
+    assert lib.gtx_stabilizer_keep_pass(None, 1) == -1 and b"st is NULL" in lib.gtx_last_error()
+    assert lib.gtx_stabilizer_level(None, 0, 0, C.byref(n), C.byref(n), None, 0) == -1 and b"st is NULL" in lib.gtx_last_error()
+    assert lib.gtx_stabilizer_candidates(None, 0, 0, 0, C.byref(n), None, None, None, None, None) == -1 and b"st is NULL" in lib.gtx_last_error()
 
 
 def test_no_gpu_means_loud_failure_not_fallback():
