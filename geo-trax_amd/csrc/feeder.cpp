@@ -22,6 +22,7 @@
 #include <atomic>
 #include <cerrno>
 #include <condition_variable>
+#include <map>
 #include <mutex>
 #include <thread>
 
@@ -30,18 +31,28 @@
 #include "common.hpp"
 #include "detector.hpp"
 #include "geometry.hpp"
+#include "jpeg.hpp"
 
 struct gtx_feeder {
   gtx_ctx ctx;                       // device + the copy stream
   bool own_stream = true;            // false: the stream belongs to the context the feeder was created on
-  int h = 0, w = 0, kind = 0;        // kind 0: BGR u8 frames, 1: I420 planes
+  int h = 0, w = 0, kind = 0;        // kind 0: BGR u8 frames, 1: I420 planes, 2: compressed JPEG frames (the slot holds the decoded record)
   int B = 1, ring = 4;
   size_t src_bytes = 0, bgr_bytes = 0;
   uint8_t* pinned = nullptr;         // [ring][B][src_bytes], hipHostMalloc
   gtx::DevBuf dev, dev_yuv;          // [ring][B][bgr_bytes]; [ring][B][src_bytes] (I420 only)
+  gtx::DevBuf dev_rec, dev_planes;   // JPEG only: one record and its sample planes (the copy stream runs the frames in order)
   std::vector<hipEvent_t> ev;        // per ring slot: the batch's uploads (and conversions) are complete
 
   int fd = -1;
+  std::vector<std::string> paths;    // JPEG file mode: the files frames are read from ...
+  int one_fd = -1;                   // ... one file (a clip): opened once; several (a file per frame): each reader thread opens the
+                                     //     file of the frame it took, reads it and closes it again, so a folder of any length
+                                     //     costs one descriptor per thread, never one per frame
+  std::vector<int32_t> file_index;   // ... which of them holds frame i ...
+  std::vector<int64_t> lengths;      // ... and how many compressed bytes it has there (at offsets[i])
+  std::vector<uint32_t> slot_len;    // [ring*B] JPEG only: bytes of the record in the pinned slot
+  std::map<int64_t, std::string> bad;   // JPEG only: frames that could not be decoded; the uploader reports one when it reaches it
   std::vector<int64_t> offsets;      // file mode: payload offset of every frame to deliver, in delivery order
   std::vector<const uint8_t*> mem;   // memory mode: the frames as host pointers (the caller keeps them alive), in delivery order
   std::vector<std::thread> readers;
@@ -74,6 +85,7 @@ struct gtx_feeder {
     for (auto e : ev) (void)hipEventDestroy(e);
     if (pinned) (void)hipHostFree(pinned);
     if (fd >= 0) ::close(fd);
+    if (one_fd >= 0) ::close(one_fd);
     if (!own_stream) ctx.stream = nullptr;   // ~gtx_ctx must not destroy a borrowed stream
   }
 
@@ -82,6 +94,79 @@ struct gtx_feeder {
     if (error.empty()) error = what;
     stop = true;
     cv.notify_all();
+  }
+
+  // JPEG: entropy-decodes one compressed frame into frame i's pinned slot and checks the record the kernels will index by.
+  // false: `why` says what is wrong with the frame (nothing of it is delivered).
+  bool decode_into_slot(int64_t i, const uint8_t* data, size_t len, std::string& why) {
+    const size_t s = slot_of(i);
+    uint8_t* dst = pinned + s * src_bytes;
+    gtx::jpeg::Info info;
+    size_t needed = 0;
+    char msg[512];
+    const int rc = gtx::jpeg::parse(data, len, (long long)i, &info, dst, src_bytes, &needed, msg, sizeof msg);
+    if (rc < 0) {
+      why = msg;
+      return false;
+    }
+    if (info.height != h || info.width != w) {
+      why = "JPEG frame " + std::to_string(i) + ": its size " + std::to_string(info.width) + " x " + std::to_string(info.height) + " differs from the feeder's " +
+            std::to_string(w) + " x " + std::to_string(h);
+      return false;
+    }
+    if (rc != 0 || gtx::jpeg::check_record(dst, needed, h, w, msg, sizeof msg) != 0) {
+      why = rc != 0 ? "JPEG frame " + std::to_string(i) + ": the record does not fit the slot" : std::string(msg);
+      return false;
+    }
+    slot_len[s] = (uint32_t)needed;
+    return true;
+  }
+
+  // Frame i is in its slot (why empty) or can never be (the uploader reports it after the batches before it).
+  void publish(int64_t i, const std::string& why) {
+    {
+      std::lock_guard<std::mutex> lk(m);
+      if (!why.empty()) bad[i] = why;
+      slot_frame[slot_of(i)] = i;
+    }
+    cv.notify_all();
+  }
+
+  // reader thread of a JPEG source: pread the compressed bytes, entropy-decode into the pinned slot
+  void read_jpeg_loop() {
+    std::vector<uint8_t> buf;
+    for (;;) {
+      int64_t i;
+      {
+        std::unique_lock<std::mutex> lk(m);
+        if (stop || next_read >= n_frames) return;
+        i = next_read++;
+        cv.wait(lk, [&] { return stop || i / B < released + ring; });
+        if (stop) return;
+      }
+      const size_t len = (size_t)lengths[(size_t)i];
+      buf.resize(len);
+      std::string why;
+      size_t got = 0;
+      int d = one_fd;
+      if (d < 0) {
+        const std::string& p = paths[(size_t)file_index[(size_t)i]];
+        d = ::open(p.c_str(), O_RDONLY | O_CLOEXEC);
+        if (d < 0) why = "frame " + std::to_string(i) + ": cannot open '" + p + "': " + strerror(errno);
+      }
+      while (why.empty() && got < len) {
+        const ssize_t r = ::pread(d, buf.data() + got, len - got, (off_t)(offsets[(size_t)i] + (int64_t)got));
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) {
+          why = "frame " + std::to_string(i) + " could not be read (" + (r == 0 ? std::string("file ends early") : std::string(strerror(errno))) + ")";
+          break;
+        }
+        got += (size_t)r;
+      }
+      if (d >= 0 && d != one_fd) ::close(d);
+      if (why.empty()) decode_into_slot(i, buf.data(), len, why);
+      publish(i, why);
+    }
   }
 
   // reader thread: frames in file order, each into the pinned slot of its (batch, position)
@@ -132,10 +217,24 @@ struct gtx_feeder {
           end = n_frames >= 0 && i >= n_frames;
         }
         if (end && i % B == 0) return;
+        if (!end && kind == 2) {
+          std::string why;
+          {
+            std::lock_guard<std::mutex> lk(m);
+            auto it = bad.find(i);
+            if (it != bad.end()) why = it->second;
+          }
+          if (!why.empty()) return set_error(why);            // every batch before this frame's has its event already
+        }
         if (!end) {
           const size_t s = slot_of(i);
           uint8_t* bgr = dev.as<uint8_t>() + s * bgr_bytes;
-          if (kind == 1) {
+          if (kind == 2) {
+            gtx::jpeg::RecordHeader hd;
+            memcpy(&hd, pinned + s * src_bytes, sizeof hd);
+            GTX_HIP(hipMemcpyAsync(dev_rec.p, pinned + s * src_bytes, slot_len[s], hipMemcpyHostToDevice, ctx.stream));
+            gtx::jpeg_decode_launch(&ctx, dev_rec.p, hd, dev_planes.p, bgr);
+          } else if (kind == 1) {
             uint8_t* yuv = dev_yuv.as<uint8_t>() + s * src_bytes;
             GTX_HIP(hipMemcpyAsync(yuv, pinned + s * src_bytes, src_bytes, hipMemcpyHostToDevice, ctx.stream));
             gtx::yuv420_to_bgr_dev(&ctx, yuv, h, w, bgr);
@@ -167,7 +266,7 @@ extern "C" {
 namespace {
 void feeder_create(int device, hipStream_t borrowed, int h, int w, int kind, int batch, int ring, gtx_feeder** out) {
   if (!out) gtx::fail(GTX_ERR_INVALID, "out is NULL");
-  if (h <= 0 || w <= 0 || (kind != 0 && kind != 1) || batch < 1 || ring < 2)
+  if (h <= 0 || w <= 0 || kind < 0 || kind > 2 || batch < 1 || ring < 2)
     gtx::fail(GTX_ERR_INVALID, "feeder: bad geometry (h %d, w %d, kind %d, batch %d, ring %d)", h, w, kind, batch, ring);
   GTX_HIP(hipSetDevice(device));
   std::unique_ptr<gtx_feeder> f(new gtx_feeder);
@@ -175,6 +274,10 @@ void feeder_create(int device, hipStream_t borrowed, int h, int w, int kind, int
   f->h = h, f->w = w, f->kind = kind, f->B = batch, f->ring = ring;
   f->bgr_bytes = (size_t)h * w * 3;
   f->src_bytes = kind == 1 ? (size_t)h * w + 2 * (size_t)((h + 1) / 2) * ((w + 1) / 2) : f->bgr_bytes;
+  if (kind == 2) {
+    if (h > gtx::jpeg::kMaxDim || w > gtx::jpeg::kMaxDim) gtx::fail(GTX_ERR_UNSUPPORTED, "feeder: JPEG frames larger than %d are not decoded", gtx::jpeg::kMaxDim);
+    f->src_bytes = (gtx::jpeg::record_bound(h, w) + 63) / 64 * 64;     // the worst-case record: every block 64 coefficients long
+  }
   if (borrowed) {
     f->ctx.stream = borrowed;
     f->own_stream = false;
@@ -185,6 +288,11 @@ void feeder_create(int device, hipStream_t borrowed, int h, int w, int kind, int
   GTX_HIP(hipHostMalloc((void**)&f->pinned, slots * f->src_bytes, hipHostMallocDefault));
   f->dev.alloc(slots * f->bgr_bytes);
   if (kind == 1) f->dev_yuv.alloc(slots * f->src_bytes);
+  if (kind == 2) {
+    f->dev_rec.alloc(f->src_bytes);
+    f->dev_planes.alloc(64 * gtx::jpeg::max_blocks(h, w));
+    f->slot_len.assign(slots, 0);
+  }
   f->ev.resize((size_t)ring);
   for (auto& e : f->ev) GTX_HIP(hipEventCreateWithFlags(&e, gtx::wait_event_flags(false)));
   f->slot_frame.assign(slots, -1);
@@ -209,6 +317,7 @@ int gtx_feeder_open_file(gtx_feeder* f, const char* path, const int64_t* offsets
   return guarded([&] {
     if (!f || !path || (n_frames > 0 && !offsets)) gtx::fail(GTX_ERR_INVALID, "feeder_open_file: NULL argument");
     if (f->fd >= 0 || f->uploader.joinable()) gtx::fail(GTX_ERR_STATE, "feeder already has a source");
+    if (f->kind == 2) gtx::fail(GTX_ERR_INVALID, "feeder_open_file: a JPEG feeder is opened with gtx_feeder_open_jpeg");
     f->fd = ::open(path, O_RDONLY | O_CLOEXEC);
     if (f->fd < 0) gtx::fail(GTX_ERR_INVALID, "feeder: cannot open '%s': %s", path, strerror(errno));
     f->offsets.assign(offsets, offsets + n_frames);
@@ -222,6 +331,7 @@ int gtx_feeder_open_memory(gtx_feeder* f, const void* const* frames, int64_t n_f
   return guarded([&] {
     if (!f || (n_frames > 0 && !frames)) gtx::fail(GTX_ERR_INVALID, "feeder_open_memory: NULL argument");
     if (f->fd >= 0 || f->uploader.joinable()) gtx::fail(GTX_ERR_STATE, "feeder already has a source");
+    if (f->kind == 2) gtx::fail(GTX_ERR_INVALID, "feeder_open_memory: a JPEG feeder is opened with gtx_feeder_open_jpeg or fed by gtx_feeder_push");
     for (int64_t i = 0; i < n_frames; ++i) {
       if (!frames[i]) gtx::fail(GTX_ERR_INVALID, "feeder_open_memory: frame %lld is NULL", (long long)i);
       f->mem.push_back(static_cast<const uint8_t*>(frames[i]));
@@ -229,6 +339,44 @@ int gtx_feeder_open_memory(gtx_feeder* f, const void* const* frames, int64_t n_f
     f->n_frames = n_frames;
     f->uploader = std::thread([f] { f->upload_loop(); });
     for (int t = 0; t < std::max(1, std::min(n_threads, 16)); ++t) f->readers.emplace_back([f] { f->read_loop(); });
+  });
+}
+
+int gtx_feeder_open_jpeg(gtx_feeder* f, const char* const* paths, int n_paths, const int32_t* file_index, const int64_t* offsets,
+                         const int64_t* lengths, int64_t n_frames, int n_threads) {
+  return guarded([&] {
+    if (!f || n_frames < 0 || n_paths < 0 || (n_frames > 0 && (!paths || !file_index || !offsets || !lengths)))
+      gtx::fail(GTX_ERR_INVALID, "feeder_open_jpeg: NULL argument");
+    if (f->kind != 2) gtx::fail(GTX_ERR_INVALID, "feeder_open_jpeg: the feeder was created with kind %d, not 2", f->kind);
+    if (f->fd >= 0 || f->one_fd >= 0 || !f->paths.empty() || f->uploader.joinable()) gtx::fail(GTX_ERR_STATE, "feeder already has a source");
+    for (int64_t i = 0; i < n_frames; ++i) {
+      if (file_index[i] < 0 || file_index[i] >= n_paths) gtx::fail(GTX_ERR_INVALID, "feeder_open_jpeg: frame %lld names file %d of %d", (long long)i, file_index[i], n_paths);
+      if (offsets[i] < 0 || lengths[i] < 4 || lengths[i] > (int64_t)1 << 30)
+        gtx::fail(GTX_ERR_INVALID, "feeder_open_jpeg: frame %lld has %lld bytes at offset %lld", (long long)i, (long long)lengths[i], (long long)offsets[i]);
+    }
+    std::vector<char> named((size_t)n_paths, 0);                // only the files the (possibly sliced) index names are touched
+    for (int64_t i = 0; i < n_frames; ++i) named[(size_t)file_index[i]] = 1;
+    f->paths.assign((size_t)n_paths, std::string());
+    int n_named = 0, only = -1;
+    for (int k = 0; k < n_paths; ++k) {
+      if (!named[(size_t)k]) continue;
+      if (!paths[k]) gtx::fail(GTX_ERR_INVALID, "feeder_open_jpeg: path %d is NULL", k);
+      f->paths[(size_t)k] = paths[k];
+      ++n_named, only = k;
+    }
+    if (n_named == 1) {                                          // a clip: one descriptor for the feeder's lifetime
+      f->one_fd = ::open(f->paths[(size_t)only].c_str(), O_RDONLY | O_CLOEXEC);
+      if (f->one_fd < 0) gtx::fail(GTX_ERR_INVALID, "feeder: cannot open '%s': %s", f->paths[(size_t)only].c_str(), strerror(errno));
+    } else if (n_frames > 0) {                                   // a file per frame: a missing first file is reported here, like a missing clip
+      const std::string& p = f->paths[(size_t)file_index[0]];
+      if (::access(p.c_str(), R_OK) != 0) gtx::fail(GTX_ERR_INVALID, "feeder: cannot open '%s': %s", p.c_str(), strerror(errno));
+    }
+    f->file_index.assign(file_index, file_index + n_frames);
+    f->offsets.assign(offsets, offsets + n_frames);
+    f->lengths.assign(lengths, lengths + n_frames);
+    f->n_frames = n_frames;
+    f->uploader = std::thread([f] { f->upload_loop(); });
+    for (int t = 0; t < std::max(1, std::min(n_threads, 16)); ++t) f->readers.emplace_back([f] { f->read_jpeg_loop(); });
   });
 }
 
@@ -243,7 +391,7 @@ int gtx_feeder_open_push(gtx_feeder* f) {
 int gtx_feeder_push(gtx_feeder* f, const void* frame, size_t bytes) {
   return guarded([&] {
     if (!f || !frame) gtx::fail(GTX_ERR_INVALID, "feeder_push: NULL argument");
-    if (bytes != f->src_bytes) gtx::fail(GTX_ERR_INVALID, "feeder_push: frame has %zu bytes, the feeder was built for %zu", bytes, f->src_bytes);
+    if (f->kind != 2 && bytes != f->src_bytes) gtx::fail(GTX_ERR_INVALID, "feeder_push: frame has %zu bytes, the feeder was built for %zu", bytes, f->src_bytes);
     int64_t i;
     {
       std::unique_lock<std::mutex> lk(f->m);
@@ -252,6 +400,13 @@ int gtx_feeder_push(gtx_feeder* f, const void* frame, size_t bytes) {
       f->cv.wait(lk, [&] { return f->stop || i / f->B < f->released + f->ring; });
       if (f->stop) gtx::fail(GTX_ERR_STATE, "feeder stopped: %s", f->error.c_str());
       f->next_read = i + 1;
+    }
+    if (f->kind == 2) {                                  // a compressed frame: decoded here, on the producer's thread
+      std::string why;
+      f->decode_into_slot(i, static_cast<const uint8_t*>(frame), bytes, why);
+      f->publish(i, why);
+      if (!why.empty()) gtx::fail(GTX_ERR_INVALID, "%s", why.c_str());
+      return;
     }
     memcpy(f->pinned + f->slot_of(i) * f->src_bytes, frame, bytes);
     {
@@ -265,13 +420,24 @@ int gtx_feeder_push(gtx_feeder* f, const void* frame, size_t bytes) {
 int gtx_feeder_push_at(gtx_feeder* f, int64_t i, const void* frame, size_t bytes) {
   return guarded([&] {
     if (!f || !frame || i < 0) gtx::fail(GTX_ERR_INVALID, "feeder_push_at: bad argument");
-    if (bytes != f->src_bytes) gtx::fail(GTX_ERR_INVALID, "feeder_push_at: frame has %zu bytes, the feeder was built for %zu", bytes, f->src_bytes);
+    if (f->kind != 2 && bytes != f->src_bytes) gtx::fail(GTX_ERR_INVALID, "feeder_push_at: frame has %zu bytes, the feeder was built for %zu", bytes, f->src_bytes);
     {
       std::unique_lock<std::mutex> lk(f->m);
       if (f->n_frames >= 0) gtx::fail(GTX_ERR_STATE, "feeder_push_at after feeder_finish");
       f->cv.wait(lk, [&] { return f->stop || i / f->B < f->released + f->ring; });
       if (f->stop) gtx::fail(GTX_ERR_STATE, "feeder stopped: %s", f->error.c_str());
       if (i / f->B < f->released) gtx::fail(GTX_ERR_STATE, "feeder_push_at: frame %lld belongs to a batch that was already consumed", (long long)i);
+    }
+    if (f->kind == 2) {
+      std::string why;
+      f->decode_into_slot(i, static_cast<const uint8_t*>(frame), bytes, why);
+      {
+        std::lock_guard<std::mutex> lk(f->m);
+        if (i + 1 > f->next_read) f->next_read = i + 1;
+      }
+      f->publish(i, why);
+      if (!why.empty()) gtx::fail(GTX_ERR_INVALID, "%s", why.c_str());
+      return;
     }
     memcpy(f->pinned + f->slot_of(i) * f->src_bytes, frame, bytes);
     {

@@ -19,6 +19,7 @@
 #include "ecc.hpp"
 #include "gmc.hpp"
 #include "gmc_feat.hpp"
+#include "jpeg.hpp"
 #include "match_l2.hpp"
 #include "register.hpp"
 #include "sift.hpp"
@@ -1672,6 +1673,100 @@ int gtx_yuv420_to_bgr_dev(gtx_ctx* ctx, const void* yuv_dptr, int h, int w, void
   return guarded([&] {
     need(ctx, "ctx"); need(yuv_dptr, "yuv"); need(bgr_dptr, "bgr");
     gtx::yuv420_to_bgr_dev(ctx, yuv_dptr, h, w, bgr_dptr);
+  });
+}
+
+size_t gtx_jpeg_record_bound(int h, int w) {
+  return (h <= 0 || w <= 0 || h > gtx::jpeg::kMaxDim || w > gtx::jpeg::kMaxDim) ? 0 : gtx::jpeg::record_bound(h, w);
+}
+
+int gtx_jpeg_parse(const void* bytes, size_t n, int64_t frame, int* h, int* w, int* ncomp, int* hs, int* vs, void* record, size_t capacity,
+                   size_t* needed) {
+  int rc = 0;
+  const int st = guarded([&] {
+    need(bytes, "bytes"); need(needed, "needed");
+    if (!record && capacity) gtx::fail(GTX_ERR_INVALID, "jpeg_parse: record is NULL with a capacity of %zu", capacity);
+    gtx::jpeg::Info info;
+    char msg[512];
+    rc = gtx::jpeg::parse(static_cast<const uint8_t*>(bytes), n, (long long)frame, &info, record, capacity, needed, msg, sizeof msg);
+    if (h) *h = info.height;
+    if (w) *w = info.width;
+    if (ncomp) *ncomp = info.ncomp;
+    if (hs) *hs = info.hs;
+    if (vs) *vs = info.vs;
+    if (rc < 0) gtx::fail(rc, "%s", msg);
+  });
+  return st != GTX_OK ? st : rc;
+}
+
+int gtx_jpeg_probe(const void* bytes, size_t n, int64_t frame, int* h, int* w, int* ncomp, int* hs, int* vs) {
+  return guarded([&] {
+    need(bytes, "bytes");
+    gtx::jpeg::Info info;
+    char msg[512];
+    const int rc = gtx::jpeg::probe(static_cast<const uint8_t*>(bytes), n, (long long)frame, &info, msg, sizeof msg);
+    if (h) *h = info.height;
+    if (w) *w = info.width;
+    if (ncomp) *ncomp = info.ncomp;
+    if (hs) *hs = info.hs;
+    if (vs) *vs = info.vs;
+    if (rc < 0) gtx::fail(rc, "%s", msg);
+  });
+}
+
+int gtx_jpeg_decode_dev(gtx_ctx* ctx, const void* record, size_t bytes, int h, int w, void* bgr_dptr) {
+  return guarded([&] {
+    need(record, "record");
+    char msg[256];
+    if (gtx::jpeg::check_record(record, bytes, h, w, msg, sizeof msg) != 0) gtx::fail(GTX_ERR_INVALID, "%s", msg);
+    need(ctx, "ctx"); need(bgr_dptr, "bgr");
+    gtx::jpeg::RecordHeader hd;
+    memcpy(&hd, record, sizeof hd);
+    GTX_HIP(hipSetDevice(ctx->device));
+    gtx::DevBuf d_rec(bytes), d_planes(gtx::jpeg::planes_bytes(hd));
+    GTX_HIP(hipMemcpyAsync(d_rec.p, record, bytes, hipMemcpyHostToDevice, ctx->stream));
+    gtx::jpeg_decode_launch(ctx, d_rec.p, hd, d_planes.p, bgr_dptr);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));                 // the scratch buffers go out of scope here
+  });
+}
+
+int gtx_jpeg_kernel_ms(gtx_ctx* ctx, const void* record, size_t bytes, int h, int w, void* bgr_dptr, const void* yuv_dptr, int reps, float ms[3]) {
+  return guarded([&] {
+    need(record, "record"); need(ms, "ms");
+    char msg[256];
+    if (gtx::jpeg::check_record(record, bytes, h, w, msg, sizeof msg) != 0) gtx::fail(GTX_ERR_INVALID, "%s", msg);
+    if (reps < 1 || reps > 10000) gtx::fail(GTX_ERR_INVALID, "jpeg_kernel_ms: %d repetitions", reps);
+    need(ctx, "ctx"); need(bgr_dptr, "bgr");
+    gtx::jpeg::RecordHeader hd;
+    memcpy(&hd, record, sizeof hd);
+    GTX_HIP(hipSetDevice(ctx->device));
+    gtx::DevBuf d_rec(bytes), d_planes(gtx::jpeg::planes_bytes(hd));
+    GTX_HIP(hipMemcpyAsync(d_rec.p, record, bytes, hipMemcpyHostToDevice, ctx->stream));
+    hipEvent_t e[4];
+    for (auto& x : e) GTX_HIP(hipEventCreate(&x));
+    double sum[3] = {0, 0, 0};
+    try {
+      for (int r = -1; r < reps; ++r) {                          // one untimed pass first
+        GTX_HIP(hipEventRecord(e[0], ctx->stream));
+        gtx::jpeg_decode_launch(ctx, d_rec.p, hd, d_planes.p, bgr_dptr, e[1]);
+        GTX_HIP(hipEventRecord(e[2], ctx->stream));
+        if (yuv_dptr) gtx::yuv420_to_bgr_dev(ctx, yuv_dptr, h, w, bgr_dptr);
+        GTX_HIP(hipEventRecord(e[3], ctx->stream));
+        GTX_HIP(hipEventSynchronize(e[3]));
+        if (r < 0) continue;
+        for (int k = 0; k < 3; ++k) {
+          float t = 0;
+          GTX_HIP(hipEventElapsedTime(&t, e[k], e[k + 1]));
+          sum[k] += t;
+        }
+      }
+    } catch (...) {
+      for (auto x : e) (void)hipEventDestroy(x);
+      throw;
+    }
+    for (auto x : e) (void)hipEventDestroy(x);
+    for (int k = 0; k < 3; ++k) ms[k] = (float)(sum[k] / reps);
+    if (!yuv_dptr) ms[2] = 0.f;
   });
 }
 

@@ -249,6 +249,12 @@ _SIGNATURES = {
     "gtx_feeder_next": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "gtx_feeder_wait": (C.c_int, [_P, C.c_int64, _P]),
     "gtx_feeder_release": (C.c_int, [_P, C.c_int64]),
+    "gtx_jpeg_record_bound": (C.c_size_t, [C.c_int, C.c_int]),
+    "gtx_jpeg_parse": (C.c_int, [_P, C.c_size_t, C.c_int64] + [C.POINTER(C.c_int)] * 5 + [_P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gtx_jpeg_decode_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_int, _P]),
+    "gtx_jpeg_probe": (C.c_int, [_P, C.c_size_t, C.c_int64] + [C.POINTER(C.c_int)] * 5),
+    "gtx_jpeg_kernel_ms": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_float)]),
+    "gtx_feeder_open_jpeg": (C.c_int, [_P, C.POINTER(C.c_char_p), C.c_int, _P, _P, _P, C.c_int64, C.c_int]),
 }
 
 _lib = None

@@ -284,20 +284,31 @@ def track_with_model_sharded(model: YOLO, config: dict, logger: logging.Logger) 
             frame before each run) come through a second, one-frame feeder whose ring replaces the explicit one above."""
             from .feeder import FrameFeeder
 
-            path, kind, offsets = reader.raw_layout()
+            raw = reader.raw_layout() if hasattr(reader, 'raw_layout') else None
+            if raw is not None:
+                path, kind, offsets = raw
+
+                def open_on(fd_, frames, threads):
+                    fd_.open_file(path, offsets[frames], n_threads=threads or int(eng_cfg.get('reader_threads', 3)))
+            else:                                            # compressed JPEG frames: the feeder's threads entropy-decode them
+                kind = "jpeg"
+                paths, findex, offsets, lengths = reader.jpeg_layout()
+
+                def open_on(fd_, frames, threads):
+                    fd_.open_jpeg((paths, findex[frames], offsets[frames], lengths[frames]), n_threads=threads or int(eng_cfg.get('decode_threads', 8)))
             B, n_dets = engine.B, len(engine.dets)
             mine = [f for start, stop in runs for f in range(start, stop)]
             primes = [prime_frame(i, start) for i, (start, stop) in enumerate(runs) if prime_frame(i, start) is not None]
             fd = FrameFeeder(reader.frame_hw, kind=kind, batch=B, ring=max(int(eng_cfg.get('read_ahead_batches', 3)), 1) + n_dets + 1, device=local,
                              ctx=engine.feeder_ctx)
             state['feeders'] = [fd]
-            fd.open_file(path, offsets[mine], n_threads=int(eng_cfg.get('reader_threads', 3)))
+            open_on(fd, mine, 0)
             main_it = fd.batches(n_dets)
             prime_it = None
             if primes:
                 pf = FrameFeeder(reader.frame_hw, kind=kind, batch=1, ring=n_prime + 1, device=local)
                 state['feeders'].append(pf)
-                pf.open_file(path, offsets[primes], n_threads=1)
+                open_on(pf, primes, 1)
                 prime_it = pf.batches(n_prime)              # a slot is written again n_prime runs later, as with the ring above
             for i, (start, stop) in enumerate(runs):
                 prev_ptr = None
@@ -312,7 +323,8 @@ def track_with_model_sharded(model: YOLO, config: dict, logger: logging.Logger) 
                     b = next(main_it)
                     yield b if k else (b, prev_ptr)
 
-        layout_ok = hasattr(reader, 'raw_layout') and reader.raw_layout() is not None
+        layout_ok = ((hasattr(reader, 'raw_layout') and reader.raw_layout() is not None)
+                     or (hasattr(reader, 'jpeg_layout') and reader.jpeg_layout() is not None))
         lengths_ok = all((stop - start) % engine.B == 0 for start, stop in runs[:-1])       # batches must not span two runs
         use_feeder = (layout_ok and lengths_ok and fail_at is None and os.environ.get("GTX_FEEDER", "1") != "0" and eng_cfg.get('read_ahead', True) is not False
                       and (not engine.stabs or engine.use_dev_gray))
@@ -389,6 +401,12 @@ def _read_ahead_batches(reader, engine, eng_cfg: dict, first: int, last, frame_n
         path, kind, offsets = layout
         feeder = FrameFeeder(reader.frame_hw, kind=kind, batch=engine.B, ring=ring, device=engine.device, ctx=engine.feeder_ctx)
         feeder.open_file(path, offsets[first:stop], n_threads=int(eng_cfg.get('reader_threads', 3)))
+        frame_nums.extend(range(first, max(stop, first)))
+    elif hasattr(reader, 'jpeg_layout') and reader.jpeg_layout() is not None:
+        # compressed JPEG frames (.mjpeg, MJPG .avi, a folder of .jpg): read and entropy-decoded by the feeder's threads
+        paths, findex, offsets, lengths = reader.jpeg_layout()
+        feeder = FrameFeeder(reader.frame_hw, kind="jpeg", batch=engine.B, ring=ring, device=engine.device, ctx=engine.feeder_ctx)
+        feeder.open_jpeg((paths, findex[first:stop], offsets[first:stop], lengths[first:stop]), n_threads=int(eng_cfg.get('decode_threads', 8)))
         frame_nums.extend(range(first, max(stop, first)))
     else:
         from .frames import Y4mReader

@@ -3,6 +3,8 @@
 
 A source that exposes ``raw_layout()`` (frames.Y4mReader, the memory-mapped .npy reader) is read by the
 library's own threads (pread into pinned slots, async upload on a copy stream, I420 -> BGR on the GPU);
+one that exposes ``jpeg_layout()`` (Motion-JPEG clips, folders of .jpg files) likewise, the threads
+entropy-decoding each frame into its slot and the GPU finishing the decode (csrc/jpeg.hip);
 any other reader is drained by one host thread here that pushes its frames into the same pinned ring.
 Either way the engine receives `DeviceBatch` objects: frames already on their way into HBM, ordered
 against the consuming detector's stream by an event -- the detector stage thread never touches the file.
@@ -41,9 +43,11 @@ class FrameFeeder:
         self.ctx = ctx
         self.device = ctx.device if ctx is not None else (_lib.default_device() if device is None else device)
         self.h, self.w = int(frame_hw[0]), int(frame_hw[1])
-        self.kind = {"bgr": 0, "i420": 1}[kind]
+        self.kind = {"bgr": 0, "i420": 1, "jpeg": 2}[kind]
         self.batch, self.ring = int(batch), int(ring)
         self.src_bytes = self.h * self.w * 3 if self.kind == 0 else self.h * self.w + 2 * ((self.h + 1) // 2) * ((self.w + 1) // 2)
+        if self.kind == 2:
+            self.src_bytes = None                               # compressed frames: any length
         h = C.c_void_p()
         if ctx is not None:
             check(self.lib.gtx_feeder_create_on(ctx.handle, self.h, self.w, self.kind, self.batch, self.ring, C.byref(h)))
@@ -57,6 +61,19 @@ class FrameFeeder:
     def open_file(self, path, offsets, n_threads: int = 3) -> None:
         off = np.ascontiguousarray(offsets, dtype=np.int64)
         check(self.lib.gtx_feeder_open_file(self.handle, str(path).encode(), _lib.ptr(off), len(off), int(n_threads)))
+
+    def open_jpeg(self, layout, n_threads: int = 8) -> None:
+        """`layout`: (paths, file_index, offsets, lengths) of a reader's jpeg_layout(), or a slice of it: frame i is lengths[i]
+        bytes at offsets[i] of paths[file_index[i]]. `n_threads` library threads read and entropy-decode the frames (a
+        parameter, never the machine's CPU count: the engine has threads of its own)."""
+        paths, file_index, offsets, lengths = layout
+        idx = np.ascontiguousarray(file_index, dtype=np.int32)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        ln = np.ascontiguousarray(lengths, dtype=np.int64)
+        if not (len(idx) == len(off) == len(ln)):
+            raise ValueError("jpeg layout: file_index, offsets and lengths differ in length")
+        arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
+        check(self.lib.gtx_feeder_open_jpeg(self.handle, arr, len(paths), _lib.ptr(idx), _lib.ptr(off), _lib.ptr(ln), len(off), int(n_threads)))
 
     def open_memory(self, frames, n_threads: int = 3) -> None:
         """`frames`: a sequence of host arrays (BGR ndarrays, or the I420 `data` of Yuv420Frame objects) delivered in order; the
@@ -77,6 +94,8 @@ class FrameFeeder:
         def run():
             try:
                 for f in frames:
+                    if isinstance(f, (bytes, bytearray, memoryview)):       # a compressed frame for a "jpeg" feeder
+                        f = np.frombuffer(f, dtype=np.uint8)
                     a = f.data if hasattr(f, "data") and hasattr(f, "bgr") else np.ascontiguousarray(f, dtype=np.uint8)
                     a = np.ascontiguousarray(a, dtype=np.uint8)
                     if self.lib.gtx_feeder_push(self.handle, _lib.ptr(a), a.nbytes) != 0:
@@ -98,6 +117,8 @@ class FrameFeeder:
             try:
                 for i in range(t, n_frames, threads):
                     f = frame_at(i)
+                    if isinstance(f, (bytes, bytearray, memoryview)):       # a compressed frame for a "jpeg" feeder
+                        f = np.frombuffer(f, dtype=np.uint8)
                     a = f.data if hasattr(f, "data") and hasattr(f, "bgr") else f
                     a = np.ascontiguousarray(a, dtype=np.uint8)
                     if self.lib.gtx_feeder_push_at(self.handle, i, _lib.ptr(a), a.nbytes) != 0:

@@ -58,7 +58,9 @@ extern "C" {
  *     one launcher at a time. A detector with more than 2^20 anchors per image is refused (the NMS sort key's anchor field).
  * 13: gtx_stabilizer_{keep_pass, level, candidates} (read-backs of the last extract pass) and gtx_op_orb_{match, ransac} (the
  *     stabilizer's matcher and RANSAC kernel one launch at a time) added. A stabilizer plan is refused per level (more than 8192
- *     keypoints on one level) instead of by max_features; the candidate lists are sized so that no FAST corner can be dropped. */
+ *     keypoints on one level) instead of by max_features; the candidate lists are sized so that no FAST corner can be dropped.
+ *     gtx_jpeg_{record_bound, probe, parse, decode_dev, kernel_ms}, gtx_feeder_open_jpeg and feeder kind 2 (compressed JPEG frames) added: new entry
+ *     points only, no struct or existing signature changed, so the number stays. */
 #define GTX_ABI_VERSION 13
 
 typedef enum gtx_status {
@@ -127,7 +129,8 @@ int gtx_yuv420_to_bgr_dev(gtx_ctx* ctx, const void* yuv_dptr, int h, int w, void
  * read by the feeder's own threads with pread() straight into a ring of pinned host slots, copied to a ring of
  * device batches on the feeder's own stream (I420 frames converted to BGR there, as gtx_yuv420_to_bgr_dev does) and
  * handed out in clip order as device pointers of `batch` contiguous BGR frames.
- *   kind: 0 = frames are BGR u8 [h][w][3]; 1 = I420 planes (h*w + 2*((h+1)/2)*((w+1)/2) bytes).
+ *   kind: 0 = frames are BGR u8 [h][w][3]; 1 = I420 planes (h*w + 2*((h+1)/2)*((w+1)/2) bytes); 2 = compressed JPEG frames
+ *   (gtx_feeder_open_jpeg below).
  *   ring: device batches (and pinned slots x batch) the feeder owns; it reads ahead until all of them are full.
  * gtx_feeder_open_file: deliver the n_frames frames whose payloads start at offsets[i] (delivery order = array order),
  *   read by n_threads reader threads. gtx_feeder_open_push / _push / _finish: the caller's thread supplies host frames
@@ -164,6 +167,46 @@ int gtx_feeder_stop(gtx_feeder* f);
 int gtx_feeder_next(gtx_feeder* f, void** dptr, int* n, int64_t* batch_index);
 int gtx_feeder_wait(gtx_feeder* f, int64_t batch_index, gtx_ctx* consumer);
 int gtx_feeder_release(gtx_feeder* f, int64_t n_batches);
+
+/* JPEG frame source: cv2.VideoCapture.read() (geotrax/extract.py:146) for Motion-JPEG clips (.mjpeg, MJPG .avi) and folders of
+ * .jpg frames. Baseline (SOF0) 8-bit Huffman JPEG, grayscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0 in one interleaved scan, with or
+ * without DHT (ITU T.81 Annex K.3 tables) and restart intervals; everything else (progressive, arithmetic, 12-bit, CMYK, Adobe
+ * RGB / YCCK, other samplings, multi-scan colour, 16-bit DQT) is GTX_ERR_UNSUPPORTED with the marker and the frame number in the
+ * message, damaged data GTX_ERR_INVALID: a frame decodes whole or not at all. The host decodes the entropy-coded data into a
+ * packed record (csrc/jpeg_parse.hpp: header, one quantisation table per component, a uint32 offset per 8x8 block, one int16
+ * stream of zigzag runs); the GPU dequantises, inverts the DCT, upsamples the chroma and converts to BGR with libjpeg's default
+ * integer arithmetic (slow-integer IDCT, fancy upsampling, 16-bit YCbCr tables): the bytes of cv2.imread / Pillow. */
+/* Replaces cv2.VideoCapture.read(), extract.py:146 (its worst-case record size for an h x w frame; 0 for a bad size). */
+size_t gtx_jpeg_record_bound(int h, int w);
+/* Replaces cv2.VideoCapture.read(), extract.py:146 (the entropy-decoding half; host only, no context). Decodes bytes[0, n) into
+ * record[0, capacity) (4-byte aligned; NULL with capacity 0 asks for the size). *h, *w, *ncomp (1 or 3), *hs, *vs (luma sampling
+ * factors) are set once the frame header is read, *needed when the frame decodes. Returns 0 (record filled, *needed bytes),
+ * 1 (capacity < *needed: nothing usable was written) or a negative status. `frame` numbers the frame in messages. Output
+ * pointers other than `needed` may be NULL. */
+int gtx_jpeg_parse(const void* bytes, size_t n, int64_t frame, int* h, int* w, int* ncomp, int* hs, int* vs, void* record, size_t capacity,
+                   size_t* needed);
+/* Replaces cv2.VideoCapture.read(), extract.py:146 (its decision whether it can play a picture): the header half of gtx_jpeg_parse
+ * alone. bytes[0, n) need only reach the SOS header; 0 when gtx_jpeg_parse would decode this variant, else its negative status
+ * and message. A folder of .jpg frames is routed by it (geotrax_amd.frames.DirReader). */
+int gtx_jpeg_probe(const void* bytes, size_t n, int64_t frame, int* h, int* w, int* ncomp, int* hs, int* vs);
+/* Replaces cv2.VideoCapture.read(), extract.py:146 (the pixel half): one record (host memory, `bytes` long, as gtx_jpeg_parse
+ * filled it) of an h x w frame -> packed BGR u8 [h][w][3] at bgr_dptr, on the context's stream; the sibling of
+ * gtx_yuv420_to_bgr_dev. The record is checked on the host first (sizes, monotone offsets, closing offset): a damaged one is
+ * GTX_ERR_INVALID before any launch. Returns when the frame is complete. */
+int gtx_jpeg_decode_dev(gtx_ctx* ctx, const void* record, size_t bytes, int h, int w, void* bgr_dptr);
+/* Timing of what replaces cv2.VideoCapture.read(), extract.py:146: the two kernels of gtx_jpeg_decode_dev `reps` times on the
+ * context's stream with events around each (after one untimed pass), and, when yuv_dptr is not NULL (an I420 frame of the same
+ * h x w in HBM), gtx_yuv420_to_bgr_dev in the same loop: ms[0] = inverse DCT launch, ms[1] = upsampling + colour launch,
+ * ms[2] = the I420 conversion (0 without yuv_dptr), mean milliseconds per launch. tools/jpeg_time.py. */
+int gtx_jpeg_kernel_ms(gtx_ctx* ctx, const void* record, size_t bytes, int h, int w, void* bgr_dptr, const void* yuv_dptr, int reps, float ms[3]);
+/* Replaces cv2.VideoCapture.read(), extract.py:146, for a feeder of kind 2 (compressed JPEG frames): frame i is lengths[i] bytes
+ * at offsets[i] of paths[file_index[i]] (one .mjpeg / .avi file, or one file per frame). n_threads reader threads pread() the
+ * compressed bytes and entropy-decode them into the pinned slot (sized for the worst-case record); the copy stream uploads the
+ * record's real length and launches the two kernels into the batch slot. A frame that cannot be decoded, or whose size is not
+ * the feeder's h x w, surfaces at gtx_feeder_next after the batches before it. With kind 2, gtx_feeder_push / _push_at take one
+ * compressed frame of any length. */
+int gtx_feeder_open_jpeg(gtx_feeder* f, const char* const* paths, int n_paths, const int32_t* file_index, const int64_t* offsets,
+                         const int64_t* lengths, int64_t n_frames, int n_threads);
 
 /* ------------------------------------------------------------------ operator level
  * Single operators of the detector, exposed so the parity tests can check every kernel

@@ -1,0 +1,182 @@
+"""Figures of the JPEG frame source at 4K ("JPEG frame source"); raw output: profiles/jpeg_time.txt.
+
+    python tools/jpeg_time.py [--frames 150] [--distinct 6] [--out DIR]
+
+  * host entropy decode (gtx_jpeg_parse): ms per 4K frame on one thread, Pillow quality 90, 4:2:0, the synthetic scene
+  * bytes per frame: the .jpg, the packed record, I420
+  * the two kernels' GPU time per frame (events around each launch, gtx_jpeg_kernel_ms) next to gtx_yuv420_to_bgr_dev's on the
+    same frame in the same loop
+  * the feeder alone (read -> decode / convert -> BGR batches in HBM, a consumer that only waits): frames/s of a .mjpeg clip at
+    4, 8 and 12 decode threads and of the same frames as .y4m (page cache), in one process, three passes each
+  * the product's loop (geotrax_amd.extract.track_with_model: reader -> engine -> tables) on the 150-frame clip as .y4m and as
+    .mjpeg at 4, 8 and 12 decode threads, in one process: `bench.py --workload cli` writes the weights, the config and the .y4m,
+    this script adds the .mjpeg of the same frames (--no-loop skips it)
+
+Needs Pillow (the encoder) and a GPU for the feeder part (--no-gpu skips it)."""
+import argparse
+import io
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT / "geo-trax_amd"))
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=150)
+    ap.add_argument("--distinct", type=int, default=6)
+    ap.add_argument("--h", type=int, default=2160)
+    ap.add_argument("--w", type=int, default=3840)
+    ap.add_argument("--no-gpu", action="store_true")
+    ap.add_argument("--no-loop", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    from PIL import Image
+
+    from geotrax_amd import _lib, jpeg
+    from geotrax_amd.frames import bgr_to_i420, open_source, write_y4m
+    from geotrax_amd.synth import make_scene
+
+    h, w = a.h, a.w
+    sc = make_scene(seed=0, h=h, w=w)
+    frames = [sc.render(5 * t, 150) for t in range(a.distinct)]
+    blobs = []
+    for f in frames:
+        buf = io.BytesIO()
+        Image.fromarray(np.ascontiguousarray(f[..., ::-1]), "RGB").save(buf, "JPEG", quality=90, subsampling=2)
+        blobs.append(buf.getvalue())
+    i420 = h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)
+    recs = [jpeg.parse(b)[0] for b in blobs]
+    print(f"frame {w} x {h}, Pillow quality 90, 4:2:0, {a.distinct} distinct frames of the synthetic scene")
+    print(f"bytes per frame: jpg {np.mean([len(b) for b in blobs]):.0f}, record {np.mean([r.nbytes for r in recs]):.0f}, "
+          f"record bound {_lib.load().gtx_jpeg_record_bound(h, w)}, I420 {i420}, BGR {h * w * 3}")
+    t = []
+    for _ in range(3):
+        for b in blobs:
+            t0 = time.perf_counter()
+            jpeg.parse(b)                                          # two passes: the size query and the fill
+            t.append((time.perf_counter() - t0) / 2)
+    print(f"host entropy decode: {1e3 * np.median(t):.2f} ms per frame on one thread (median of {len(t)}, min {1e3 * min(t):.2f})")
+    if a.no_gpu:
+        return
+    import ctypes as C
+
+    from geotrax_amd.feeder import FrameFeeder
+
+    ctx = _lib.default_context(0)
+    yuv = np.frombuffer(bgr_to_i420(frames[0]), np.uint8)
+    d_yuv, d_bgr = ctx.dev_alloc(yuv.nbytes), ctx.dev_alloc(h * w * 3)
+    ctx.dev_upload(d_yuv, yuv)
+    for rep in range(3):
+        ms = (C.c_float * 3)()
+        _lib.check(ctx.lib.gtx_jpeg_kernel_ms(ctx.handle, _lib.ptr(recs[0]), recs[0].nbytes, h, w, C.c_void_p(d_bgr), C.c_void_p(d_yuv), 50, ms))
+        print(f"GPU time per frame, pass {rep} (mean of 50, events): jpeg_idct_kernel {ms[0]:.4f} ms, jpeg_colour_kernel {ms[1]:.4f} ms, "
+              f"both {ms[0] + ms[1]:.4f} ms; yuv420_to_bgr_kernel {ms[2]:.4f} ms")
+    ctx.dev_free(d_yuv)
+    ctx.dev_free(d_bgr)
+    out = Path(a.out) if a.out else Path(tempfile.mkdtemp())
+    out.mkdir(parents=True, exist_ok=True)
+    n = a.frames
+    clip = out / "clip.mjpeg"
+    clip.write_bytes(b"".join(blobs[k % a.distinct] for k in range(n)))
+    y4m = out / "clip.y4m"
+    planes = [bgr_to_i420(f) for f in frames]
+    write_y4m(y4m, [planes[k % a.distinct] if k else frames[0] for k in range(n)])
+
+    def drain(fd):
+        t0 = time.perf_counter()
+        k = 0
+        for b in fd.batches(in_flight=2):
+            b.wait_on(None)                                        # the calling thread waits for the batch to be resident
+            k += b.n
+        dt = time.perf_counter() - t0
+        fd.close()
+        return k, dt
+
+    r = open_source(y4m)
+    path, kind, off = r.raw_layout()
+    r.release()
+    for rep in range(3):
+        fd = FrameFeeder((h, w), kind=kind, batch=2, ring=6, ctx=None, device=ctx.device)
+        fd.open_file(path, off, n_threads=3)
+        k, dt = drain(fd)
+        print(f"feeder alone, .y4m (page cache), 3 reader threads, pass {rep}: {k} frames in {dt:.3f} s = {k / dt:.0f} frames/s")
+    r = open_source(clip)
+    layout = r.jpeg_layout()
+    r.release()
+    for threads in (4, 8, 12):
+        for rep in range(3):
+            fd = FrameFeeder((h, w), kind="jpeg", batch=2, ring=6, device=ctx.device)
+            fd.open_jpeg(layout, n_threads=threads)
+            k, dt = drain(fd)
+            print(f"feeder alone, .mjpeg, {threads} decode threads, pass {rep}: {k} frames in {dt:.3f} s = {k / dt:.0f} frames/s")
+    print(f"files: .mjpeg {clip.stat().st_size} bytes, .y4m {y4m.stat().st_size} bytes")
+    clip.unlink()
+    y4m.unlink()
+    if not a.no_loop:
+        product_loop(out / "loop", n)
+
+
+def product_loop(root: Path, n: int) -> None:
+    """The product's loop on the same 150 frames as .y4m and as .mjpeg, one process, warm-up run + two timed runs each."""
+    import argparse as ap_
+    import io
+    import logging
+    import subprocess
+
+    import yaml
+    from PIL import Image
+
+    from geotrax_amd import extract as ex
+    from geotrax_amd.config_utils import load_config_all
+    from geotrax_amd.synth import make_scene
+
+    root.mkdir(parents=True, exist_ok=True)
+    # weights calibrated to the golden clip's box count, the config and clip.y4m: written by the benchmark's own cli workload
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "cli", "--cli-dir", str(root), "--cli-formats", "y4m", "--cli-compare-sync", "0",
+                        "--cli-frames", str(n)], capture_output=True, text=True)
+    if r.returncode != 0:
+        raise SystemExit("bench.py --workload cli failed:\n" + r.stdout[-2000:] + r.stderr[-2000:])
+    h, w, pool = 2160, 3840, 6                                   # bench.py's clip: 6 renders of scene 0 played ping-pong
+    sc = make_scene(seed=0, h=h, w=w)
+    blobs = []
+    for t in range(pool):
+        buf = io.BytesIO()
+        Image.fromarray(np.ascontiguousarray(sc.render(t, 150)[..., ::-1]), "RGB").save(buf, "JPEG", quality=90, subsampling=2)
+        blobs.append(buf.getvalue())
+    order = list(range(pool)) + list(range(pool - 2, 0, -1))
+    (root / "clip.mjpeg").write_bytes(b"".join(blobs[order[i % len(order)]] for i in range(n)))
+    cfg = yaml.safe_load((root / "cfg.yaml").read_text())
+    logger = logging.getLogger("jpeg_time")
+    logger.setLevel(logging.ERROR)
+
+    def one_run(path, cfg_path):
+        a = ap_.Namespace(source=str(path), cfg=cfg_path, output_folder=None, log_path=None, verbose=False, model=None, class_names=None, conf=None,
+                          classes=None, cut_frame_left=None, cut_frame_right=None, interpolate=None)
+        model = ex.load_detector(a, logger)
+        config = load_config_all(a, logger, model_names=model.names)
+        tracks, _ = ex.track_with_model(model, config, logger)
+        lr = model.last_run
+        assert len(tracks) and lr["frames"] == n, (len(tracks), lr)
+        return lr["loop_fps"], len(tracks)
+
+    cases = [("clip.y4m", None)] + [("clip.mjpeg", t) for t in (4, 8, 12)]
+    for name, threads in cases:
+        c = dict(cfg)
+        c["engine"] = dict(cfg.get("engine") or {})
+        if threads:
+            c["engine"]["decode_threads"] = threads
+        cfg_path = root / f"cfg_{threads or 'y4m'}.yaml"
+        cfg_path.write_text(yaml.safe_dump(c))
+        runs = [one_run(root / name, cfg_path) for _ in range(3)]
+        what = f"{name}, {threads} decode threads" if threads else f"{name} (page cache), 3 reader threads"
+        print(f"product loop, {what}: {runs[1][0]:.0f} and {runs[2][0]:.0f} frames/s (warm-up run {runs[0][0]:.0f}); {runs[1][1]} track rows")
+
+
+if __name__ == "__main__":
+    main()
