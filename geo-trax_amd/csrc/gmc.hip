@@ -26,6 +26,7 @@
 #include <cstring>
 #include <vector>
 
+#include "net_runtime.hpp"   // gtx_ctx
 #include "gmc.hpp"
 
 namespace gtx {
@@ -211,19 +212,28 @@ __global__ __launch_bounds__(256) void nms_kernel(const double* __restrict__ lam
 // The candidates' histogram over the top 16 key bits (filled by nms_kernel) gives the bucket the 1000th
 // strongest falls into; one sweep then gathers everything above that bucket plus the bucket itself
 // (a 6 %-wide value range: a few hundred candidates) into LDS, where a bitonic sort of (key, pix)
-// finishes the job. A bucket too full for LDS is narrowed by further 8-bit radix passes first.
+// finishes the job. A bucket too full for LDS is narrowed by further 8-bit radix passes first: over the
+// remaining 48 value bits and, when those are used up and the bucket is one group of EQUAL responses that
+// still does not fit (a periodic texture: thousands of exactly equal maxima), over the pixel index, the
+// second half of the order. What is gathered is then always the top of the (val, pix) order, whatever the
+// sizes of the tie groups, and never more than kSelCap - 64 entries.
+// record[4] = {maxima found (the raw counter), stored (<= cap), gathered into LDS, narrowing passes} of this
+// frame, written before the counters are cleared (gtx_gmc_counts, gtx_op_gmc_corners).
 constexpr int kSelCap = 4096;
 __global__ __launch_bounds__(1024) void select_kernel(const Cand* __restrict__ cand, int* __restrict__ n_cand, int cap, int w,
                                                       int* __restrict__ hist16, unsigned long long* __restrict__ max_bits_p,
-                                                      float2* __restrict__ pts, int* __restrict__ n_pts) {
+                                                      float2* __restrict__ pts, int* __restrict__ n_pts, int* __restrict__ record) {
   __shared__ unsigned long long s_key[kSelCap];
   __shared__ int s_pix[kSelCap];
   __shared__ int s_hist[256];
   __shared__ unsigned long long s_lo;       // keys >= s_lo are gathered
   __shared__ int s_cnt, s_bucket, s_above, s_need;
   const int tid = threadIdx.x;
-  const int n = min(*n_cand, cap);
+  const int found = *n_cand;
+  const int n = min(found, cap);
   const int want = min(n, kMaxCorners);
+  unsigned plo = 0;                         // within the tie group at s_lo, pixel indices >= plo are gathered
+  int passes = 0;
   if (tid == 0) { s_lo = 0; s_cnt = 0; }
   __syncthreads();
   if (n > kSelCap) {
@@ -256,6 +266,30 @@ __global__ __launch_bounds__(1024) void select_kernel(const Cand* __restrict__ c
       __syncthreads();
       lo |= (unsigned long long)s_bucket << shift;
       population = s_cnt;
+      ++passes;
+      __syncthreads();
+    }
+    // still too full with every value bit fixed: `lo` is one response shared by the whole bucket. The order among equals is
+    // the pixel index, larger first: the same narrowing over its 32 bits.
+    for (int shift = 24; population + s_above > kSelCap - 64 && shift >= 0; shift -= 8) {
+      if (tid < 256) s_hist[tid] = 0;
+      __syncthreads();
+      const unsigned mask = shift == 24 ? 0u : ~0u << (shift + 8);
+      for (int i = tid; i < n; i += 1024) {
+        const unsigned long long k = (unsigned long long)__double_as_longlong(cand[i].val);
+        const unsigned px = (unsigned)cand[i].pix;
+        if (k == lo && (px & mask) == plo) atomicAdd(&s_hist[(px >> shift) & 255], 1);
+      }
+      __syncthreads();
+      if (tid == 0) {
+        int need = s_need, b2 = 255;
+        for (; b2 > 0; --b2) { if (s_hist[b2] >= need) break; need -= s_hist[b2]; s_above += s_hist[b2]; }
+        s_need = need; s_bucket = b2; s_cnt = s_hist[b2];
+      }
+      __syncthreads();
+      plo |= (unsigned)s_bucket << shift;
+      population = s_cnt;
+      ++passes;
       __syncthreads();
     }
     if (tid == 0) { s_lo = lo; s_cnt = 0; }
@@ -266,7 +300,7 @@ __global__ __launch_bounds__(1024) void select_kernel(const Cand* __restrict__ c
   const unsigned long long lo = s_lo;
   for (int i = tid; i < n; i += 1024) {
     const unsigned long long k = (unsigned long long)__double_as_longlong(cand[i].val);
-    if (k >= lo) {
+    if (k > lo || (k == lo && (unsigned)cand[i].pix >= plo)) {
       const int slot = atomicAdd(&s_cnt, 1);
       if (slot < kSelCap) { s_key[slot] = k; s_pix[slot] = cand[i].pix; }
     }
@@ -295,7 +329,10 @@ __global__ __launch_bounds__(1024) void select_kernel(const Cand* __restrict__ c
   // last reader of the frame's counters: clear them for the next frame of this parity (two memset launches less per
   // frame on the tracker's critical path; they start out zero)
   if (tid < 256) hist16[tid] = 0;
-  if (tid == 0) { *max_bits_p = 0ull; *n_cand = 0; }
+  if (tid == 0) {
+    *reinterpret_cast<int4*>(record) = make_int4(found, n, s_cnt, passes);
+    *max_bits_p = 0ull; *n_cand = 0;
+  }
 }
 
 // ---- pyramid
@@ -460,7 +497,7 @@ __global__ __launch_bounds__(1024) void compact_kernel(const float2* __restrict_
     __syncthreads();
   }
   if (flag) pairs[s_scan[tid] - 1] = make_float4(prev[tid].x, prev[tid].y, next[tid].x, next[tid].y);
-  if (tid == 1023) { res->n_prev = n; res->n_valid = s_scan[1023]; res->best_count = -1; res->a = 1; res->b = 0; res->tx = 0; res->ty = 0; }
+  if (tid == 1023) { res->n_prev = n; res->n_valid = s_scan[1023]; res->best_count = -1; res->winner = -1; res->a = 1; res->b = 0; res->tx = 0; res->ty = 0; }
 }
 
 __device__ __forceinline__ unsigned hash_u32(unsigned x) {
@@ -512,7 +549,7 @@ __global__ __launch_bounds__(kHyp) void argmax_kernel(const double4* __restrict_
   }
   if (tid == 0 && s_c[0] >= 0) {
     const double4 m = model[s_i[0]];
-    res->best_count = s_c[0]; res->a = m.x; res->b = m.y; res->tx = m.z; res->ty = m.w;
+    res->best_count = s_c[0]; res->winner = s_i[0]; res->a = m.x; res->b = m.y; res->tx = m.z; res->ty = m.w;
   }
 }
 
@@ -572,6 +609,111 @@ bool gmc_refit(const GmcResult& R, const float4* pairs, double scale, double A[6
   return true;
 }
 
+// one frame's counter block: [0] the response maximum's bit pattern (8 bytes), [8] the candidate counter, [12] unused,
+// [16] select_kernel's record of four ints
+constexpr size_t kCounterBytes = 32;
+
+namespace {
+
+void upload(DevBuf& d, const void* src, size_t bytes) {
+  d.alloc(bytes);
+  if (bytes) GTX_HIP(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+}
+
+void zeros(DevBuf& d, size_t bytes) {
+  d.alloc(bytes);
+  GTX_HIP(hipMemset(d.p, 0, d.bytes));
+}
+
+void fill_ff(DevBuf& d, size_t bytes) {
+  d.alloc(bytes);
+  GTX_HIP(hipMemset(d.p, 0xff, d.bytes));
+}
+
+// a 4-level pyramid of an h x w host image in one allocation, built by pyrdown_kernel on `s`
+void make_pyramid(DevBuf& buf, Pyr& P, const uint8_t* img, int h, int w, hipStream_t s) {
+  size_t total = 0;
+  for (int l = 0, lw = w, lh = h; l <= kMaxLevel; ++l) { total += (size_t)lw * lh; lw = (lw + 1) / 2; lh = (lh + 1) / 2; }
+  buf.alloc(total);
+  uint8_t* p = buf.as<uint8_t>();
+  for (int l = 0, lw = w, lh = h; l <= kMaxLevel; ++l) { P.img[l] = p; P.w[l] = lw; P.h[l] = lh; p += (size_t)lw * lh; lw = (lw + 1) / 2; lh = (lh + 1) / 2; }
+  GTX_HIP(hipMemcpyAsync(buf.p, img, (size_t)w * h, hipMemcpyHostToDevice, s));
+  for (int l = 1; l <= kMaxLevel; ++l)
+    hipLaunchKernelGGL(pyrdown_kernel, dim3(cdiv(P.w[l], 256), P.h[l]), dim3(256), 0, s, P.img[l - 1], P.w[l - 1], P.h[l - 1], const_cast<uint8_t*>(P.img[l]),
+                       P.w[l], P.h[l]);
+}
+
+}  // namespace
+
+// ---- the kernels one launcher at a time, on host arrays (gtx_op_gmc_*; tests/test_gmc_ops_gpu.py). Sizes and coordinates are
+// checked by the callers in gtx_api.cpp before anything here touches the GPU. Each launch is shaped as submit_gray_dev shapes it.
+void op_gmc_corners(gtx_ctx* ctx, const uint8_t* gray, int h, int w, int* n, float* xy, int counts[4]) {
+  GTX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int cap = (w - 2) * (h - 2);
+  DevBuf dg, lam(sizeof(double) * (size_t)w * h), cand(sizeof(Cand) * (size_t)cap), counters, hist, pts, npts;
+  upload(dg, gray, (size_t)w * h);
+  zeros(counters, kCounterBytes);
+  zeros(hist, sizeof(int) * 256);
+  fill_ff(pts, sizeof(float2) * 1024);
+  fill_ff(npts, sizeof(int));
+  unsigned long long* max_bits = counters.as<unsigned long long>();
+  int* n_cand = reinterpret_cast<int*>(max_bits + 1);
+  hipLaunchKernelGGL(response_kernel, dim3(cdiv(w, kRT_W), cdiv(h, kRT_H)), dim3(256), 0, s, dg.as<uint8_t>(), w, h, lam.as<double>(), max_bits);
+  hipLaunchKernelGGL(nms_kernel, dim3(cdiv(w - 2, 256), cdiv(h - 2, kNmsRows)), dim3(256), 0, s, lam.as<double>(), w, h, max_bits, cand.as<Cand>(), n_cand, cap,
+                     hist.as<int>());
+  hipLaunchKernelGGL(select_kernel, dim3(1), dim3(1024), 0, s, cand.as<Cand>(), n_cand, cap, w, hist.as<int>(), max_bits, pts.as<float2>(), npts.as<int>(),
+                     n_cand + 2);
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipStreamSynchronize(s));
+  int block[kCounterBytes / sizeof(int)];
+  GTX_HIP(hipMemcpy(block, counters.p, kCounterBytes, hipMemcpyDeviceToHost));
+  GTX_CHECK(block[0] == 0 && block[1] == 0 && block[2] == 0, "gmc_corners: select_kernel left the frame's counters set");   // the next frame of the parity starts from them
+  std::memcpy(counts, block + 4, 4 * sizeof(int));
+  GTX_HIP(hipMemcpy(n, npts.p, sizeof(int), hipMemcpyDeviceToHost));
+  GTX_CHECK(*n >= 0 && *n <= kMaxCorners, "gmc_corners: %d corners", *n);
+  if (*n > 0) GTX_HIP(hipMemcpy(xy, pts.p, sizeof(float2) * *n, hipMemcpyDeviceToHost));
+}
+
+void op_gmc_lk(gtx_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int h, int w, const float* pts, int n, float* next, int* status) {
+  GTX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  DevBuf bp, bc, dp, dn, dnext, dst;
+  Pyr P{}, C{};
+  make_pyramid(bp, P, prev, h, w, s);
+  make_pyramid(bc, C, cur, h, w, s);
+  upload(dp, pts, sizeof(float2) * (size_t)n);
+  upload(dn, &n, sizeof(int));
+  fill_ff(dnext, sizeof(float2) * 1024);
+  fill_ff(dst, sizeof(int) * 1024);
+  hipLaunchKernelGGL(lk_kernel, dim3(cdiv(kMaxCorners, 4)), dim3(256), 0, s, P, C, dp.as<float2>(), dn.as<int>(), dnext.as<float2>(), dst.as<int>());
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipStreamSynchronize(s));
+  if (n > 0) {
+    GTX_HIP(hipMemcpy(next, dnext.p, sizeof(float2) * n, hipMemcpyDeviceToHost));
+    GTX_HIP(hipMemcpy(status, dst.p, sizeof(int) * n, hipMemcpyDeviceToHost));
+  }
+}
+
+void op_gmc_ransac(gtx_ctx* ctx, const float* pairs, int n, unsigned seed, int* best_count, int* winner, double model4[4], int* count) {
+  GTX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  DevBuf dp, dr, dm, dc;
+  upload(dp, pairs, sizeof(float4) * (size_t)n);
+  const GmcResult R0{n, n, -1, -1, 1.0, 0.0, 0.0, 0.0};        // as compact_kernel leaves it
+  upload(dr, &R0, sizeof R0);
+  fill_ff(dm, sizeof(double4) * kHyp);
+  fill_ff(dc, sizeof(int) * kHyp);
+  gmc_launch_ransac(dp.as<float4>(), dr.as<GmcResult>(), seed, dm.as<double4>(), dc.as<int>(), s);
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipStreamSynchronize(s));
+  GmcResult R;
+  GTX_HIP(hipMemcpy(&R, dr.p, sizeof R, hipMemcpyDeviceToHost));
+  GTX_HIP(hipMemcpy(count, dc.p, sizeof(int) * kHyp, hipMemcpyDeviceToHost));
+  *best_count = R.best_count; *winner = R.winner;
+  model4[0] = R.a; model4[1] = R.b; model4[2] = R.tx; model4[3] = R.ty;
+}
+
 struct Gmc::Impl {
   int device;
   // Two streams: frame t works on st[t & 1]. Pyramid + corner detection of a frame need nothing from other
@@ -625,13 +767,15 @@ Gmc::Gmc(int device, hipStream_t stream, int gray_h, int gray_w, int seed) : imp
     S.npts[k].alloc(sizeof(int));
     GTX_HIP(hipMemset(S.npts[k].p, 0, sizeof(int)));
   }
-  S.cand_cap = gray_w * gray_h / 4;
+  // every pixel inside the 1-pixel border can be a candidate: equal neighbours all count as maxima (goodFeaturesToTrack's rule),
+  // and a texture of period 3 makes the whole response map one plateau. 16 B each: 8.2 MB per parity for a 960 x 540 gray image.
+  S.cand_cap = (gray_w - 2) * (gray_h - 2);
   for (int k = 0; k < 2; ++k) {
     S.lam[k].alloc(sizeof(double) * gray_w * gray_h);
     S.cand[k].alloc(sizeof(Cand) * S.cand_cap);
-    S.counters[k].alloc(16);
+    S.counters[k].alloc(kCounterBytes);
     S.hist16[k].alloc(sizeof(int) * 256);
-    GTX_HIP(hipMemset(S.counters[k].p, 0, 16));
+    GTX_HIP(hipMemset(S.counters[k].p, 0, kCounterBytes));
     GTX_HIP(hipMemset(S.hist16[k].p, 0, sizeof(int) * 256));
     S.next[k].alloc(sizeof(float2) * 1024); S.status[k].alloc(sizeof(int) * 1024); S.pairs[k].alloc(sizeof(float4) * 1024);
     S.res[k].alloc(sizeof(GmcResult)); S.model[k].alloc(sizeof(double4) * kHyp); S.count[k].alloc(sizeof(int) * kHyp);
@@ -686,7 +830,7 @@ void Gmc::submit_gray_dev(const void* gray, int gh, int gw) {
   hipLaunchKernelGGL(nms_kernel, dim3(cdiv(S.w - 2, 256), cdiv(S.h - 2, kNmsRows)), dim3(256), 0, s, S.lam[c].as<double>(), S.w, S.h, max_bits, S.cand[c].as<Cand>(),
                      n_cand, S.cand_cap, S.hist16[c].as<int>());
   hipLaunchKernelGGL(select_kernel, dim3(1), dim3(1024), 0, s, S.cand[c].as<Cand>(), n_cand, S.cand_cap, S.w, S.hist16[c].as<int>(), max_bits,
-                     S.pts[c].as<float2>(), S.npts[c].as<int>());
+                     S.pts[c].as<float2>(), S.npts[c].as<int>(), n_cand + 2);
   GTX_HIP(hipEventRecord(S.front_ev[c], s));
   S.first[slot] = !S.have_prev;
   if (S.have_prev) {
@@ -757,6 +901,15 @@ void Gmc::collect(double A[6], int* valid, int stats[3]) {
   }
   if (stats) std::memcpy(stats, S.stats, sizeof S.stats);
   S.collected.fetch_add(1, std::memory_order_release);   // the slot's pinned records are free for the producer again
+}
+
+void Gmc::debug_counts(int counts[4]) const {
+  const Impl& S = *impl_;
+  GTX_CHECK(S.pending() == 0, "gmc: debug read while a frame is in flight");
+  GTX_HIP(hipSetDevice(S.device));
+  GTX_HIP(hipStreamSynchronize(S.st[0]));
+  GTX_HIP(hipStreamSynchronize(S.st[1]));
+  GTX_HIP(hipMemcpy(counts, S.counters[S.cur ^ 1].as<int>() + 4, 4 * sizeof(int), hipMemcpyDeviceToHost));   // zero until a frame of that parity ran
 }
 
 void Gmc::debug_points(int which, int cap, int* n, float* xy, int* status) const {

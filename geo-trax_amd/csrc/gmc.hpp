@@ -7,11 +7,13 @@
 
 #include "common.hpp"
 
+struct gtx_ctx;
+
 namespace gtx {
 
 // Device-side record of one frame's fit: filled by the compaction step (counts, identity model), then by the RANSAC winner.
 struct GmcResult {
-  int n_prev, n_valid, best_count, pad;
+  int n_prev, n_valid, best_count, winner;   // winner: index of the winning hypothesis (-1: none)
   double a, b, tx, ty;
 };
 
@@ -48,10 +50,20 @@ class Gmc {
   void collect(double A[6], int* valid, int stats[3]);
   // test hook: which 0 = corners of the last frame, 1 = corners of the frame before, 2 = their LK positions
   void debug_points(int which, int cap, int* n, float* xy, int* status) const;
+  // test hook: the corner step's record of the last submitted frame = {maxima found, stored, gathered into LDS, narrowing passes}
+  void debug_counts(int counts[4]) const;
 
  private:
   struct Impl;
   std::unique_ptr<Impl> impl_;
 };
+
+// ---- gtx_op_gmc_*: one launcher each on host arrays (arguments checked by the caller, gtx_api.cpp)
+// response + nms + select on a gray image: corners strongest first (n <= 1000) and the corner step's record (debug_counts)
+void op_gmc_corners(gtx_ctx* ctx, const uint8_t* gray, int h, int w, int* n, float* xy, int counts[4]);
+// pyrdown x 3 on both images + lk_kernel on n <= 1000 given points
+void op_gmc_lk(gtx_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int h, int w, const float* pts, int n, float* next, int* status);
+// ransac_kernel + argmax_kernel on n <= 1024 pairs: the winner's inlier count, index and (a, b, tx, ty), and every hypothesis' count
+void op_gmc_ransac(gtx_ctx* ctx, const float* pairs, int n, unsigned seed, int* best_count, int* winner, double model4[4], int* count);
 
 }  // namespace gtx

@@ -84,7 +84,7 @@ __global__ __launch_bounds__(kMaxFeat) void feat_filter_kernel(const int* __rest
     __syncthreads();
   }
   if (keep) pairs[s_scan[tid] - 1] = make_float4(p.x, p.y, q.x, q.y);
-  if (tid == kMaxFeat - 1) { res->n_prev = nt; res->n_valid = s_scan[tid]; res->best_count = -1; res->pad = 0; res->a = 1; res->b = 0; res->tx = 0; res->ty = 0; }
+  if (tid == kMaxFeat - 1) { res->n_prev = nt; res->n_valid = s_scan[tid]; res->best_count = -1; res->winner = -1; res->a = 1; res->b = 0; res->tx = 0; res->ty = 0; }
 }
 
 }  // namespace

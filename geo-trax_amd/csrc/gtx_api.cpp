@@ -1089,6 +1089,49 @@ int gtx_gmc_collect(gtx_gmc* g, double A[6], int* valid, int stats[3]) {
 int gtx_gmc_points(gtx_gmc* g, int which, int cap, int* n, float* xy, int* status) {
   return guarded([&] { need(g, "gmc"); need(n, "n"); g->impl->debug_points(which, cap, n, xy, status); });
 }
+int gtx_gmc_counts(gtx_gmc* g, int counts[4]) {
+  return guarded([&] { need(g, "gmc"); need(counts, "counts"); g->impl->debug_counts(counts); });
+}
+
+// ---- the sparse-optical-flow GMC's kernels one launcher at a time (tests/test_gmc_ops_gpu.py). Sizes, and every coordinate a
+// kernel would turn into an address, are checked before anything touches the GPU.
+int gtx_op_gmc_corners(gtx_ctx* ctx, const uint8_t* gray, int h, int w, int cap, int* n, float* xy, int counts[4]) {
+  return guarded([&] {
+    const char* op = "gmc_corners";
+    if (h < 16 || w < 16 || h > 8192 || w > 8192) rt_bad(op, "a gray image of 16..8192 pixels a side");
+    if (cap < 1000) rt_bad(op, "room for 1000 corners");
+    need(gray, "gray"); need(n, "n"); need(xy, "xy"); need(counts, "counts"); need(ctx, "ctx");
+    gtx::op_gmc_corners(ctx, gray, h, w, n, xy, counts);
+  });
+}
+
+int gtx_op_gmc_lk(gtx_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int h, int w, const float* pts, int n, float* next, int* status) {
+  return guarded([&] {
+    const char* op = "gmc_lk";
+    if (h < 16 || w < 16 || h > 8192 || w > 8192) rt_bad(op, "gray images of 16..8192 pixels a side (every pyramid level at least two wide)");
+    if (n < 0 || n > 1000) rt_bad(op, "0 <= n <= 1000 points");
+    need(prev, "prev"); need(cur, "cur");
+    if (n > 0) { need(pts, "pts"); need(next, "next"); need(status, "status"); }
+    for (int i = 0; i < n; ++i) {
+      const float x = pts[2 * i], y = pts[2 * i + 1];
+      if (!(x >= 0.f && x <= (float)(w - 1) && y >= 0.f && y <= (float)(h - 1))) rt_bad(op, "a point outside the image (or not a number)");
+    }
+    need(ctx, "ctx");
+    gtx::op_gmc_lk(ctx, prev, cur, h, w, pts, n, next, status);
+  });
+}
+
+int gtx_op_gmc_ransac(gtx_ctx* ctx, const float* pairs, int n, uint32_t seed, int* best_count, int* winner, double model[4], int* count) {
+  return guarded([&] {
+    const char* op = "gmc_ransac";
+    if (n < 0 || n > 1024) rt_bad(op, "0 <= n <= 1024 pairs (the compaction step's list)");
+    if (n > 0) need(pairs, "pairs");
+    for (int i = 0; i < 4 * n; ++i)
+      if (!std::isfinite(pairs[i])) rt_bad(op, "a coordinate that is not a finite number");
+    need(best_count, "best_count"); need(winner, "winner"); need(model, "model"); need(count, "count"); need(ctx, "ctx");
+    gtx::op_gmc_ransac(ctx, pairs, n, seed, best_count, winner, model, count);
+  });
+}
 
 struct gtx_fgmc {
   gtx_ctx* ctx;

@@ -138,6 +138,10 @@ _SIGNATURES = {
     "gtx_gmc_submit_frame_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
     "gtx_gmc_collect": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
     "gtx_gmc_points": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P]),
+    "gtx_gmc_counts": (C.c_int, [_P, _P]),
+    "gtx_op_gmc_corners": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P]),
+    "gtx_op_gmc_lk": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
+    "gtx_op_gmc_ransac": (C.c_int, [_P, _P, C.c_int, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int), _P, _P]),
     "gtx_fgmc_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "gtx_fgmc_destroy": (None, [_P]),
     "gtx_fgmc_reset": (C.c_int, [_P]),

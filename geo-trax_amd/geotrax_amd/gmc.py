@@ -80,6 +80,12 @@ class GMC:
         check(self.ctx.lib.gtx_gmc_points(self.handle, which, 1024, C.byref(n), ptr(xy), ptr(st)))
         return xy[:n.value].copy(), st[:n.value].astype(bool)
 
+    def counts(self) -> dict:
+        """The corner step's record of the last submitted frame: dict(found, stored, gathered, passes) (gtx_gmc_counts)."""
+        c = np.zeros(4, np.int32)
+        check(self.ctx.lib.gtx_gmc_counts(self.handle, ptr(c)))
+        return dict(zip(("found", "stored", "gathered", "passes"), (int(v) for v in c)))
+
 
 def estimate_affine_partial(p_xy: np.ndarray, q_xy: np.ndarray, seed: int = 0):
     """cv2.estimateAffinePartial2D(p, q, RANSAC) stand-in (gtx_op_estimate_affine_partial, host C++): 2x3 float64 or None."""

@@ -506,3 +506,39 @@ def orb_ransac(pts, seed: int, n_hyp: int, frame_wh, thr: float, *, affine: bool
     check(ctx.lib.gtx_op_orb_ransac(ctx.handle, ptr(p) if len(p) else None, len(p), int(seed) & 0xFFFFFFFF, int(n_hyp), int(frame_wh[0]), int(frame_wh[1]),
                                     float(thr), int(affine), C.byref(best), C.byref(cost), ptr(H)))
     return best.value, cost.value, H.reshape(3, 3)
+
+
+def gmc_corners(gray, *, ctx=None):
+    """The sparse-optical-flow GMC's corner step (response + nms + select kernels, one launch each) on a gray image [h, w] u8.
+    -> (corners [n, 2] f32 (x, y), n <= 1000, strongest first, equal responses by larger pixel index first;
+    dict(found, stored, gathered, passes): the step's record, see gtx_gmc_counts)."""
+    ctx = ctx or _lib.default_context()
+    g = np.ascontiguousarray(gray, dtype=np.uint8)
+    assert g.ndim == 2
+    n, xy, c = C.c_int(-1), np.full((1000, 2), np.nan, np.float32), np.full(4, -1, np.int32)
+    check(ctx.lib.gtx_op_gmc_corners(ctx.handle, ptr(g), g.shape[0], g.shape[1], 1000, C.byref(n), ptr(xy), ptr(c)))
+    return xy[:n.value].copy(), dict(zip(("found", "stored", "gathered", "passes"), (int(v) for v in c)))
+
+
+def gmc_lk(prev, cur, pts, *, ctx=None):
+    """The GMC's pyramid reductions on both gray images [h, w] u8 and its Lucas-Kanade kernel on pts [n, 2] f32 (n <= 1000,
+    fractional, anywhere inside the image). -> (next [n, 2] f32, status [n] bool)."""
+    ctx = ctx or _lib.default_context()
+    a, b = np.ascontiguousarray(prev, dtype=np.uint8), np.ascontiguousarray(cur, dtype=np.uint8)
+    assert a.ndim == 2 and a.shape == b.shape
+    p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 2)
+    n = len(p)
+    nxt, st = np.full((max(n, 1), 2), np.nan, np.float32), np.full(max(n, 1), -1, np.int32)
+    check(ctx.lib.gtx_op_gmc_lk(ctx.handle, ptr(a), ptr(b), a.shape[0], a.shape[1], ptr(p) if n else None, n, ptr(nxt), ptr(st)))
+    assert n == 0 or set(np.unique(st[:n])) <= {0, 1}
+    return nxt[:n], st[:n].astype(bool)
+
+
+def gmc_ransac(pairs, seed: int = 0, *, ctx=None):
+    """The GMC's hypothesis kernel and its arg-max on pairs [n, 4] f32 = (p.x, p.y, q.x, q.y), n <= 1024, no refit.
+    -> dict(best_count, winner, model [4] f64 = (a, b, tx, ty), count [512] int32)."""
+    ctx = ctx or _lib.default_context()
+    p = np.ascontiguousarray(pairs, dtype=np.float32).reshape(-1, 4)
+    best, win, model, count = C.c_int(-2), C.c_int(-2), np.full(4, np.nan, np.float64), np.full(512, -2, np.int32)
+    check(ctx.lib.gtx_op_gmc_ransac(ctx.handle, ptr(p) if len(p) else None, len(p), int(seed) & 0xFFFFFFFF, C.byref(best), C.byref(win), ptr(model), ptr(count)))
+    return dict(best_count=best.value, winner=win.value, model=model, count=count)

@@ -60,7 +60,8 @@ extern "C" {
  *     stabilizer's matcher and RANSAC kernel one launch at a time) added. A stabilizer plan is refused per level (more than 8192
  *     keypoints on one level) instead of by max_features; the candidate lists are sized so that no FAST corner can be dropped.
  *     gtx_jpeg_{record_bound, probe, parse, decode_dev, kernel_ms}, gtx_feeder_open_jpeg and feeder kind 2 (compressed JPEG frames) added: new entry
- *     points only, no struct or existing signature changed, so the number stays. */
+ *     points only, no struct or existing signature changed, so the number stays. gtx_gmc_counts and gtx_op_gmc_{corners, lk, ransac} (the
+ *     sparse-optical-flow GMC's kernels one launcher at a time) added: the same, the number stays. */
 #define GTX_ABI_VERSION 13
 
 typedef enum gtx_status {
@@ -754,6 +755,23 @@ int gtx_gmc_collect(gtx_gmc* g, double A[6], int* valid, int stats[3]);
 /* Parity hook: which 0 = corners of the last frame, 1 = corners of the frame before, 2 = where LK put
  * those in the last frame (+ status). xy in half-resolution pixels. */
 int gtx_gmc_points(gtx_gmc* g, int which, int cap, int* n, float* xy, int* status);
+/* The corner step's record of the last submitted frame: counts = {3x3 local maxima found (equal neighbours all count), stored in
+ * the candidate list (the list holds every pixel inside the border, so: the same number), gathered into LDS for the final sort (at
+ * most 4032 once the list is longer than 4096), radix passes that narrowed the gather (0 on ordinary frames)}. */
+int gtx_gmc_counts(gtx_gmc* g, int counts[4]);
+
+/* The method's kernels one launcher at a time on host arrays, each launch shaped as gtx_gmc_submit_* shapes it; sizes and
+ * coordinates are checked before the GPU is touched.
+ * _corners: response + nms + select on a gray image [h][w] u8 (16..8192 a side) -> n <= 1000 corners, strongest first, equal
+ * responses by larger pixel index first, xy [n][2] f32 (cap = room in xy, at least 1000), counts as gtx_gmc_counts.
+ * _lk: the three pyramid reductions of both images, then the Lucas-Kanade kernel on n <= 1000 caller-given points pts [n][2] f32
+ * (fractional, anywhere inside the image) -> next [n][2] f32, status [n] (1 = tracked).
+ * _ransac: the hypothesis kernel and its arg-max on pairs [n][4] f32 = (p.x, p.y, q.x, q.y), n <= 1024 -> count [512] per hypothesis
+ * (-1: none could be made), the winner's index (most inliers, lowest index among equals; -1: none), best_count (-1: none) and
+ * model = (a, b, tx, ty) of [a -b tx; b a ty] as sampled (the identity when there is no winner). No host refit. */
+int gtx_op_gmc_corners(gtx_ctx* ctx, const uint8_t* gray, int h, int w, int cap, int* n, float* xy, int counts[4]);
+int gtx_op_gmc_lk(gtx_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int h, int w, const float* pts, int n, float* next, int* status);
+int gtx_op_gmc_ransac(gtx_ctx* ctx, const float* pairs, int n, uint32_t seed, int* best_count, int* winner, double model[4], int* count);
 
 /* ------------------------------------------------------------------ global motion compensation, method 'orb'
  * `gmc_method: orb` (geotrax/cfg/default.yaml:374,419,467): ultralytics' GMC.apply_features on ORB keypoints of the half-resolution

@@ -55,9 +55,9 @@ def corner_response(gray: np.ndarray) -> np.ndarray:
     return 0.5 * (a + c).astype(np.float64) - np.sqrt(0.25 * ((a - c).astype(np.float64) ** 2) + b.astype(np.float64) ** 2)
 
 
-def good_features(gray: np.ndarray) -> np.ndarray:
-    """[n,2] float32 (x, y): 3x3 local maxima above 0.01 * max, strongest first (ties: larger pixel
-    index first), at most 1000, the 1-pixel border excluded."""
+def local_maxima(gray: np.ndarray):
+    """Every 3x3 local maximum above 0.01 * max, the 1-pixel border excluded (equal neighbours all count, as in
+    cv2.goodFeaturesToTrack): (pixel index y * w + x [n] int64, response [n] float64), in raster order."""
     lam = corner_response(gray)
     h, w = lam.shape
     thr = lam.max() * QUALITY
@@ -71,9 +71,16 @@ def good_features(gray: np.ndarray) -> np.ndarray:
     ok[0, :] = ok[-1, :] = False
     ok[:, 0] = ok[:, -1] = False
     ys, xs = np.nonzero(ok)
-    pix = ys * w + xs
-    order = np.lexsort((-pix, -v[ys, xs]))[:MAX_CORNERS]
-    return np.stack([xs[order], ys[order]], 1).astype(np.float32)
+    return ys * w + xs, v[ys, xs]
+
+
+def good_features(gray: np.ndarray) -> np.ndarray:
+    """[n,2] float32 (x, y): 3x3 local maxima above 0.01 * max, strongest first (ties: larger pixel
+    index first), at most 1000, the 1-pixel border excluded."""
+    pix, val = local_maxima(gray)
+    w = gray.shape[1]
+    order = np.lexsort((-pix, -val))[:MAX_CORNERS]
+    return np.stack([pix[order] % w, pix[order] // w], 1).astype(np.float32)
 
 
 def pyr_down(img: np.ndarray) -> np.ndarray:
@@ -107,8 +114,15 @@ def _bilinear(img, x0, y0, fx, fy):
     return (p[:-1, :-1] * (1 - fx) * (1 - fy) + p[:-1, 1:] * fx * (1 - fy) + p[1:, :-1] * (1 - fx) * fy + p[1:, 1:] * fx * fy)
 
 
-def lk_track(prev_pyr, cur_pyr, pts: np.ndarray):
-    """Pyramidal Lucas-Kanade, one point at a time. -> (next points [n,2] f32, status [n] bool)."""
+LK_EXITS = ("skipped", "min-eig", "eps", "oscillation", "cap of 30", "left the image")
+
+
+def lk_track(prev_pyr, cur_pyr, pts: np.ndarray, trace: list | None = None):
+    """Pyramidal Lucas-Kanade, one point at a time. -> (next points [n,2] f32, status [n] bool).
+    trace (optional list): gains one entry per point, a list indexed by pyramid level with the way that level ended, one of
+    LK_EXITS: 'skipped' (the 22-sample window of the previous image does not fit), 'min-eig' (the structure tensor is rejected),
+    'eps' (a step of at most 0.01 px), 'oscillation' (two steps that cancel), 'cap of 30' (the iteration limit), 'left the image'
+    (the window around the moving estimate no longer fits). It records; it does not change what is computed."""
     grads = [_scharr(p) for p in prev_pyr]
     prevf = [p.astype(np.float64) for p in prev_pyr]
     curf = [p.astype(np.float64) for p in cur_pyr]
@@ -117,6 +131,7 @@ def lk_track(prev_pyr, cur_pyr, pts: np.ndarray):
     for n, (px, py) in enumerate(pts.astype(np.float64)):
         nx = ny = 0.0
         ok = True
+        why = [None] * (MAX_LEVEL + 1)
         for L in range(MAX_LEVEL, -1, -1):
             sc = 1.0 / (1 << L)
             qx, qy = px * sc, py * sc
@@ -129,6 +144,7 @@ def lk_track(prev_pyr, cur_pyr, pts: np.ndarray):
             tx, ty = qx - HALF, qy - HALF
             x0, y0 = int(np.floor(tx)), int(np.floor(ty))
             if x0 < 0 or y0 < 0 or x0 + WIN + 1 > w or y0 + WIN + 1 > h:
+                why[L] = "skipped"
                 if L == 0:
                     ok = False
                 continue
@@ -138,15 +154,18 @@ def lk_track(prev_pyr, cur_pyr, pts: np.ndarray):
             D = A11 * A22 - A12 * A12
             min_eig = (A22 + A11 - np.sqrt((A11 - A22) ** 2 + 4.0 * A12 * A12)) / (2.0 * WIN * WIN)
             if min_eig < MIN_EIG_THR or D < 1.1920929e-7:
+                why[L] = "min-eig"
                 if L == 0:
                     ok = False
                 continue
             D = 1.0 / D
             pdx = pdy = 0.0
+            why[L] = "cap of 30"
             for j in range(MAX_ITERS):
                 ux, uy = nx - HALF, ny - HALF
                 jx0, jy0 = int(np.floor(ux)), int(np.floor(uy))
                 if jx0 < 0 or jy0 < 0 or jx0 + WIN + 1 > w or jy0 + WIN + 1 > h:
+                    why[L] = "left the image"
                     if L == 0:
                         ok = False
                     break
@@ -156,13 +175,17 @@ def lk_track(prev_pyr, cur_pyr, pts: np.ndarray):
                 dx, dy = (A12 * b2 - A22 * b1) * D, (A12 * b1 - A11 * b2) * D
                 nx, ny = nx + dx, ny + dy
                 if dx * dx + dy * dy <= EPS * EPS:
+                    why[L] = "eps"
                     break
                 if j > 0 and abs(dx + pdx) < 0.01 and abs(dy + pdy) < 0.01:
                     nx, ny = nx - dx * 0.5, ny - dy * 0.5
+                    why[L] = "oscillation"
                     break
                 pdx, pdy = dx, dy
         out[n] = (nx, ny)
         status[n] = ok
+        if trace is not None:
+            trace.append(why)
     return out.astype(np.float32), status
 
 
@@ -186,9 +209,44 @@ def _similarity_from(p, q):
     return np.array([[a, -b, mq[0] - (a * mp[0] - b * mp[1])], [b, a, mq[1] - (b * mp[0] + a * mp[1])]])
 
 
-def estimate_affine_partial(p: np.ndarray, q: np.ndarray, seed: int = 0):
+def ransac_hypotheses(p: np.ndarray, q: np.ndarray, seed: int = 0) -> dict:
+    """The 512 two-point hypotheses of estimate_affine_partial one by one, for the per-kernel tests. -> dict: count [512] (inliers
+    within 3 px; -1 where no hypothesis is made: fewer than two pairs, the same pair drawn twice, or two pairs whose first points
+    coincide), model [512, 4] = (a, b, tx, ty) (identity where count is -1), winner (most inliers, the lowest index among equals;
+    -1: none), best_count (-1: none), best_model [4], margin = the smallest | |err| - 3 | over all hypotheses and pairs (inf when
+    there is nothing to measure): counts are exact for any evaluation order whose rounding stays below it."""
+    n = len(p)
+    p, q = np.asarray(p, np.float64).reshape(-1, 2), np.asarray(q, np.float64).reshape(-1, 2)
+    count = np.full(N_HYP, -1, np.int64)
+    model = np.tile(np.array([1.0, 0.0, 0.0, 0.0]), (N_HYP, 1))
+    margin = np.inf
+    for hyp in range(N_HYP if n >= 2 else 0):
+        i = _hash(seed ^ _hash(2 * hyp)) % n
+        j = _hash(seed ^ _hash(2 * hyp + 1)) % n
+        if i == j:
+            continue
+        dpx, dpy = p[j, 0] - p[i, 0], p[j, 1] - p[i, 1]
+        den = dpx * dpx + dpy * dpy
+        if den < 1e-12:
+            continue
+        dqx, dqy = q[j, 0] - q[i, 0], q[j, 1] - q[i, 1]
+        a, b = (dpx * dqx + dpy * dqy) / den, (dpx * dqy - dpy * dqx) / den
+        tx, ty = q[i, 0] - (a * p[i, 0] - b * p[i, 1]), q[i, 1] - (b * p[i, 0] + a * p[i, 1])
+        ex = a * p[:, 0] - b * p[:, 1] + tx - q[:, 0]
+        ey = b * p[:, 0] + a * p[:, 1] + ty - q[:, 1]
+        err2 = ex * ex + ey * ey
+        count[hyp] = int((err2 < RANSAC_THR * RANSAC_THR).sum())
+        model[hyp] = (a, b, tx, ty)
+        margin = min(margin, float(np.abs(np.sqrt(err2) - RANSAC_THR).min()))
+    winner = int(np.argmax(count)) if count.max() >= 0 else -1        # argmax: the first of equals
+    return dict(count=count, model=model, winner=winner, best_count=int(count[winner]) if winner >= 0 else -1,
+                best_model=model[winner] if winner >= 0 else np.array([1.0, 0.0, 0.0, 0.0]), margin=margin)
+
+
+def estimate_affine_partial(p: np.ndarray, q: np.ndarray, seed: int = 0, info: dict | None = None):
     """RANSAC similarity p -> q: 512 two-point hypotheses (counter-hash sampling), most inliers within
-    3 px wins (first on ties), then three rounds of least squares on the inliers. -> 2x3 f64 or None."""
+    3 px wins (first on ties), then three rounds of least squares on the inliers. -> 2x3 f64 or None.
+    info (optional dict): gains 'inliers', the size of the last inlier set a round counted (the set the returned fit was made from)."""
     n = len(p)
     if n < 2:
         return None
@@ -217,6 +275,8 @@ def estimate_affine_partial(p: np.ndarray, q: np.ndarray, seed: int = 0):
     for _ in range(3):
         e = p @ M[:, :2].T + M[:, 2] - q
         inl = (e * e).sum(1) < RANSAC_THR * RANSAC_THR
+        if info is not None:
+            info["inliers"] = int(inl.sum())
         if inl.sum() < 2:
             break
         M2 = _similarity_from(p[inl], q[inl])
@@ -242,9 +302,9 @@ class GmcRef:
         if self.prev_pyr is not None and self.prev_pts is not None and len(self.prev_pts):
             nxt, st = lk_track(self.prev_pyr, pyr, self.prev_pts)
             p, q = self.prev_pts[st], nxt[st]
-            self.last = dict(prev=self.prev_pts, next=nxt, status=st)
+            self.last = dict(prev=self.prev_pts, next=nxt, status=st, inliers=0)
             if len(p) > 4:
-                M = estimate_affine_partial(p, q, self.seed)
+                M = estimate_affine_partial(p, q, self.seed, self.last)
                 if M is not None:
                     H = M.copy()
                     H[:, 2] *= 2.0

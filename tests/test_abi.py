@@ -220,6 +220,56 @@ def test_orb_hooks_refuse_bad_sizes_before_any_launch():
     assert lib.gtx_stabilizer_candidates(None, 0, 0, 0, C.byref(n), None, None, None, None, None) == -1 and b"st is NULL" in lib.gtx_last_error()
 
 
+def test_gmc_hooks_refuse_bad_sizes_before_any_launch():
+    """Host only: the sparse-optical-flow GMC's operator hooks and its counts read-back answer bad sizes, points outside the image
+    and missing arrays with an error code, with no context or object given."""
+    from geotrax_amd import _lib
+
+    lib = _lib.load()
+    g = np.zeros((64, 64), np.uint8)
+    f = np.zeros(4096, np.float32)
+    i = np.zeros(1024, np.int32)
+    p = _lib.ptr
+    n, w = C.c_int(), C.c_int()
+
+    def corners(h=64, wd=64, cap=1000, gray=g):
+        return lib.gtx_op_gmc_corners(None, p(gray), h, wd, cap, C.byref(n), p(f), p(i))
+
+    assert corners() == -1 and b"ctx is NULL" in lib.gtx_last_error()                                   # the sizes were fine
+    assert corners(h=15) == -1 and b"gmc_corners" in lib.gtx_last_error()
+    assert corners(wd=8193) == -1 and b"gmc_corners" in lib.gtx_last_error()
+    assert corners(cap=999) == -1 and b"1000 corners" in lib.gtx_last_error()
+    assert corners(gray=None) == -1 and b"gray is NULL" in lib.gtx_last_error()
+
+    def lk(h=64, wd=64, n_pts=2, pts=(10.0, 10.0, 63.0, 63.0), cur=g):
+        xy = np.array(pts, np.float32)
+        return lib.gtx_op_gmc_lk(None, p(g), p(cur), h, wd, p(xy), n_pts, p(f), p(i))
+
+    assert lk() == -1 and b"ctx is NULL" in lib.gtx_last_error()                                        # the border pixel is inside
+    assert lk(n_pts=0) == -1 and b"ctx is NULL" in lib.gtx_last_error()                                 # no point is a case
+    assert lk(pts=(10.0, 10.0, 63.5, 10.0)) == -1 and b"outside the image" in lib.gtx_last_error()
+    assert lk(pts=(10.0, 10.0, 10.0, -0.5)) == -1 and b"outside the image" in lib.gtx_last_error()
+    assert lk(pts=(10.0, 10.0, float("nan"), 1.0)) == -1 and b"outside the image" in lib.gtx_last_error()
+    assert lk(n_pts=1001) == -1 and b"1000 points" in lib.gtx_last_error()
+    assert lk(n_pts=-1) == -1 and b"1000 points" in lib.gtx_last_error()
+    assert lk(h=15) == -1 and b"gmc_lk" in lib.gtx_last_error()                                         # level 3 would be one pixel high
+    assert lk(cur=None) == -1 and b"cur is NULL" in lib.gtx_last_error()
+    model = np.zeros(4, np.float64)
+
+    def ransac(n_pairs=8, pairs=f):
+        return lib.gtx_op_gmc_ransac(None, p(pairs), n_pairs, 0, C.byref(n), C.byref(w), p(model), p(i))
+
+    assert ransac() == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert ransac(n_pairs=0, pairs=None) == -1 and b"ctx is NULL" in lib.gtx_last_error()               # no pair: no winner, not an error
+    assert ransac(n_pairs=1025) == -1 and b"1024 pairs" in lib.gtx_last_error()
+    assert ransac(n_pairs=-1) == -1 and b"1024 pairs" in lib.gtx_last_error()
+    assert ransac(pairs=None) == -1 and b"pairs is NULL" in lib.gtx_last_error()
+    bad = np.zeros(32, np.float32)
+    bad[5] = np.inf
+    assert ransac(pairs=bad) == -1 and b"finite" in lib.gtx_last_error()
+    assert lib.gtx_gmc_counts(None, p(i)) == -1 and b"gmc is NULL" in lib.gtx_last_error()
+
+
 def test_no_gpu_means_loud_failure_not_fallback():
     """Without a GPU the compute entry points must fail with a message; nothing falls back to CPU."""
     from geotrax_amd import _lib
