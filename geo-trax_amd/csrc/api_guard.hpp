@@ -9,6 +9,10 @@
 namespace gtx {
 inline thread_local std::string g_last_error;
 
+inline void need(const void* p, const char* what) {
+  if (!p) fail(GTX_ERR_INVALID, "%s is NULL", what);
+}
+
 template <typename F>
 int guarded(F&& f) {
   try {

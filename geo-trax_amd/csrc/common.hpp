@@ -30,7 +30,7 @@ inline unsigned wait_event_flags(bool timing) {
 }
 
 
-// Error transport: C++ exceptions never cross the C ABI; gtx_api.cpp catches
+// Error transport: C++ exceptions never cross the C ABI; guarded() (api_guard.hpp) catches
 // them, stores the text in a thread-local buffer and returns a negative code.
 struct Error : std::runtime_error {
   int code;

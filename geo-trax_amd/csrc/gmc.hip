@@ -28,6 +28,7 @@
 
 #include "net_runtime.hpp"   // gtx_ctx
 #include "gmc.hpp"
+#include "op_staging.hpp"
 
 namespace gtx {
 
@@ -615,21 +616,6 @@ constexpr size_t kCounterBytes = 32;
 
 namespace {
 
-void upload(DevBuf& d, const void* src, size_t bytes) {
-  d.alloc(bytes);
-  if (bytes) GTX_HIP(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-}
-
-void zeros(DevBuf& d, size_t bytes) {
-  d.alloc(bytes);
-  GTX_HIP(hipMemset(d.p, 0, d.bytes));
-}
-
-void fill_ff(DevBuf& d, size_t bytes) {
-  d.alloc(bytes);
-  GTX_HIP(hipMemset(d.p, 0xff, d.bytes));
-}
-
 // a 4-level pyramid of an h x w host image in one allocation, built by pyrdown_kernel on `s`
 void make_pyramid(DevBuf& buf, Pyr& P, const uint8_t* img, int h, int w, hipStream_t s) {
   size_t total = 0;
@@ -646,7 +632,7 @@ void make_pyramid(DevBuf& buf, Pyr& P, const uint8_t* img, int h, int w, hipStre
 }  // namespace
 
 // ---- the kernels one launcher at a time, on host arrays (gtx_op_gmc_*; tests/test_gmc_ops_gpu.py). Sizes and coordinates are
-// checked by the callers in gtx_api.cpp before anything here touches the GPU. Each launch is shaped as submit_gray_dev shapes it.
+// checked by the callers in gtx_ops.cpp before anything here touches the GPU. Each launch is shaped as submit_gray_dev shapes it.
 void op_gmc_corners(gtx_ctx* ctx, const uint8_t* gray, int h, int w, int* n, float* xy, int counts[4]) {
   GTX_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
@@ -667,12 +653,12 @@ void op_gmc_corners(gtx_ctx* ctx, const uint8_t* gray, int h, int w, int* n, flo
   GTX_HIP(hipGetLastError());
   GTX_HIP(hipStreamSynchronize(s));
   int block[kCounterBytes / sizeof(int)];
-  GTX_HIP(hipMemcpy(block, counters.p, kCounterBytes, hipMemcpyDeviceToHost));
+  download(block, counters, kCounterBytes);
   GTX_CHECK(block[0] == 0 && block[1] == 0 && block[2] == 0, "gmc_corners: select_kernel left the frame's counters set");   // the next frame of the parity starts from them
   std::memcpy(counts, block + 4, 4 * sizeof(int));
-  GTX_HIP(hipMemcpy(n, npts.p, sizeof(int), hipMemcpyDeviceToHost));
+  download(n, npts, sizeof(int));
   GTX_CHECK(*n >= 0 && *n <= kMaxCorners, "gmc_corners: %d corners", *n);
-  if (*n > 0) GTX_HIP(hipMemcpy(xy, pts.p, sizeof(float2) * *n, hipMemcpyDeviceToHost));
+  if (*n > 0) download(xy, pts, sizeof(float2) * *n);
 }
 
 void op_gmc_lk(gtx_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int h, int w, const float* pts, int n, float* next, int* status) {
@@ -690,8 +676,8 @@ void op_gmc_lk(gtx_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int h, int
   GTX_HIP(hipGetLastError());
   GTX_HIP(hipStreamSynchronize(s));
   if (n > 0) {
-    GTX_HIP(hipMemcpy(next, dnext.p, sizeof(float2) * n, hipMemcpyDeviceToHost));
-    GTX_HIP(hipMemcpy(status, dst.p, sizeof(int) * n, hipMemcpyDeviceToHost));
+    download(next, dnext, sizeof(float2) * n);
+    download(status, dst, sizeof(int) * n);
   }
 }
 
@@ -708,8 +694,8 @@ void op_gmc_ransac(gtx_ctx* ctx, const float* pairs, int n, unsigned seed, int* 
   GTX_HIP(hipGetLastError());
   GTX_HIP(hipStreamSynchronize(s));
   GmcResult R;
-  GTX_HIP(hipMemcpy(&R, dr.p, sizeof R, hipMemcpyDeviceToHost));
-  GTX_HIP(hipMemcpy(count, dc.p, sizeof(int) * kHyp, hipMemcpyDeviceToHost));
+  download(&R, dr, sizeof R);
+  download(count, dc, sizeof(int) * kHyp);
   *best_count = R.best_count; *winner = R.winner;
   model4[0] = R.a; model4[1] = R.b; model4[2] = R.tx; model4[3] = R.ty;
 }

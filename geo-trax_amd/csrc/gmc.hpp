@@ -58,7 +58,7 @@ class Gmc {
   std::unique_ptr<Impl> impl_;
 };
 
-// ---- gtx_op_gmc_*: one launcher each on host arrays (arguments checked by the caller, gtx_api.cpp)
+// ---- gtx_op_gmc_*: one launcher each on host arrays (arguments checked by the caller, gtx_ops.cpp)
 // response + nms + select on a gray image: corners strongest first (n <= 1000) and the corner step's record (debug_counts)
 void op_gmc_corners(gtx_ctx* ctx, const uint8_t* gray, int h, int w, int* n, float* xy, int counts[4]);
 // pyrdown x 3 on both images + lk_kernel on n <= 1000 given points

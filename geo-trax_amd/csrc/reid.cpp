@@ -282,12 +282,7 @@ void Embedder::profile(int n, int iters, std::vector<std::string>& names, std::v
 
 // ------------------------------------------------------------------ C ABI (include/gtx.h, "ReID embedder")
 using gtx::guarded;
-
-namespace {
-void need(const void* p, const char* what) {
-  if (!p) gtx::fail(GTX_ERR_INVALID, "%s: NULL", what);
-}
-}  // namespace
+using gtx::need;
 
 int gtx_embedder_create(gtx_ctx* ctx, int imgsz, int max_crops, int fp32_split, gtx_embedder** out) {
   return guarded([&] {

@@ -13,7 +13,7 @@
 namespace gtx {
 
 // Host-side conversion of whole buffers (n a multiple of 8), used where plain fp32 host arrays meet the library
-// (gtx_op_conv2d, gtx_op_sppf_pool, gtx_detector_layer_output). Returns true when a value was clamped.
+// (the operator hooks through op_staging.hpp's upload_fmt / download_fmt, gtx_detector_layer_output). Returns true when a value was clamped.
 inline bool f32_to_pairs(const float* src, void* dst, size_t n) {
   bool sat = false;
   uint8_t* d = static_cast<uint8_t*>(dst);

@@ -21,6 +21,7 @@
 
 #include "detector.hpp"   // gtx_ctx
 #include "geometry.hpp"
+#include "op_staging.hpp"
 #include "stabilizer.hpp"
 
 namespace gtx {
@@ -1884,14 +1885,6 @@ OrbOpState* orb_op_state(gtx_ctx* ctx) {
   }
   return static_cast<OrbOpState*>(ctx->orb_op_state);
 }
-void upload(DevBuf& d, const void* src, size_t bytes, size_t room) {
-  d.alloc(std::max(room, bytes));
-  if (bytes) GTX_HIP(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-}
-void fill_ff(DevBuf& d, size_t bytes) {
-  d.alloc(bytes);
-  GTX_HIP(hipMemset(d.p, 0xFF, d.bytes));
-}
 }  // namespace
 
 void op_orb_match(gtx_ctx* ctx, const uint8_t* desc_q, int nq, int slots_q, const uint8_t* desc_t, int nt, int slots_t, float ratio, int keep_all,
@@ -1917,15 +1910,15 @@ void op_orb_match(gtx_ctx* ctx, const uint8_t* desc_q, int nq, int slots_q, cons
   GTX_HIP(hipGetLastError());
   GTX_HIP(hipStreamSynchronize(ctx->stream));
   const size_t out_q = 4 * (size_t)nq;
-  GTX_HIP(hipMemcpy(n_match, nm.p, sizeof(int), hipMemcpyDeviceToHost));
+  download(n_match, nm, sizeof(int));
   if (nq == 0) return;
-  GTX_HIP(hipMemcpy(best_idx, bi.p, out_q, hipMemcpyDeviceToHost));
-  GTX_HIP(hipMemcpy(best_d, bd.p, out_q, hipMemcpyDeviceToHost));
-  GTX_HIP(hipMemcpy(second_d, sd.p, out_q, hipMemcpyDeviceToHost));
-  GTX_HIP(hipMemcpy(m_q, mq.p, out_q, hipMemcpyDeviceToHost));
-  GTX_HIP(hipMemcpy(m_t, mt.p, out_q, hipMemcpyDeviceToHost));
-  GTX_HIP(hipMemcpy(m_d, md.p, out_q, hipMemcpyDeviceToHost));
-  GTX_HIP(hipMemcpy(m_pts, mp.p, 4 * out_q, hipMemcpyDeviceToHost));
+  download(best_idx, bi, out_q);
+  download(best_d, bd, out_q);
+  download(second_d, sd, out_q);
+  download(m_q, mq, out_q);
+  download(m_t, mt, out_q);
+  download(m_d, md, out_q);
+  download(m_pts, mp, 4 * out_q);
 }
 
 void op_orb_ransac(gtx_ctx* ctx, const float* pts, int n, unsigned seed, int n_hyp, int frame_w, int frame_h, float thr, int affine, int* best,
@@ -1942,7 +1935,7 @@ void op_orb_ransac(gtx_ctx* ctx, const float* pts, int n, unsigned seed, int n_h
   GTX_HIP(hipGetLastError());
   GTX_HIP(hipStreamSynchronize(ctx->stream));
   StabResult R;
-  GTX_HIP(hipMemcpy(&R, dr.p, sizeof R, hipMemcpyDeviceToHost));
+  download(&R, dr, sizeof R);
   *best = R.best;
   *cost = R.cost;
   std::memcpy(H, R.H, sizeof R.H);

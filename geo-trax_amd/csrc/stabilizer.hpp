@@ -69,7 +69,7 @@ bool ransac_homography(int device, hipStream_t s, const float4* d_pts, int n_mat
                        float threshold, double H[9], int* n_inliers);
 
 // Operator hooks: one launch of the matcher / of the RANSAC kernel on host arrays, exactly as the stabilizer launches them (sizes are
-// validated by the caller, gtx_api.cpp). Their ticket / state words live with the context and are never re-initialised by the host.
+// validated by the caller, gtx_ops.cpp). Their ticket / state words live with the context and are never re-initialised by the host.
 void op_orb_match(gtx_ctx* ctx, const uint8_t* desc_q, int nq, int slots_q, const uint8_t* desc_t, int nt, int slots_t, float ratio, int keep_all,
                   const float* xy_q, const float* xy_t, int* best_idx, int* best_d, int* second_d, int* m_q, int* m_t, int* m_d, float* m_pts,
                   int* n_match);
