@@ -2,9 +2,10 @@
 // The float64 tests drive them, and the package calls a few itself (the registration matcher, the georeference chain, CLAHE).
 // A hook checks every size, and every index a kernel would turn into an address, before it touches the GPU; then it stages its
 // arrays with op_staging.hpp, launches as the product launches, and copies the results back. The hooks of file-local kernels
-// (op_gmc_* in gmc.hip, op_orb_* in stabilizer.hip) keep their staging beside the kernels and have only their checks here.
+// (op_gmc_* in gmc.hip, op_orb_* in stabilizer.hip, op_sift_* in sift.hip) keep their staging beside the kernels and have only their checks here.
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -20,6 +21,7 @@
 #include "op_staging.hpp"
 #include "register.hpp"
 #include "rtdetr_kernels.hpp"
+#include "sift.hpp"
 #include "stabilizer.hpp"
 #include "tracker.hpp"
 
@@ -860,6 +862,104 @@ int gtx_op_orb_ransac(gtx_ctx* ctx, const float* pts, int n, uint32_t seed, int 
     long long c = 0;
     gtx::op_orb_ransac(ctx, pts, n, seed, n_hyp, frame_w, frame_h, thr, affine, best, &c, H);
     *cost = c;
+  });
+}
+
+// ---- the SIFT kernels one stage at a time (tests/test_sift_ops_gpu.py). Sizes, and every record field a kernel turns into an address
+// or a loop bound, are checked before anything touches the GPU.
+namespace {
+void sift_image_ok(const char* op, int h, int w, int octave) {
+  if (h < 1 || w < 1 || h > 4096 || w > 4096) op_bad(op, "images of 1..4096 pixels a side");
+  if (octave < 0 || octave > 15) op_bad(op, "octave 0..15");
+}
+}  // namespace
+
+int gtx_op_sift_blur(gtx_ctx* ctx, const float* src, int h, int w, double sigma, int form, float* dst, float* dog) {
+  return guarded([&] {
+    const char* op = "sift_blur";
+    sift_image_ok(op, h, w, 0);
+    if (!(sigma > 0.0 && sigma <= 64.0)) op_bad(op, "sigma in (0, 64]");
+    if (form < 0 || form > 2) op_bad(op, "form: 0 the pyramid's dispatch, 1 the generic tile kernel, 2 the row / column / subtraction passes");
+    (void)gtx::sift_blur_radius(sigma);                    // a radius above 16 is refused here, before any launch
+    need(src, "src"); need(dst, "dst"); need(ctx, "ctx");
+    gtx::op_sift_blur(ctx, src, h, w, sigma, form, dst, dog);
+  });
+}
+
+int gtx_op_sift_extrema(gtx_ctx* ctx, const float* dog5, int h, int w, int octave, int cap, int* count, int* cand) {
+  return guarded([&] {
+    const char* op = "sift_extrema";
+    sift_image_ok(op, h, w, octave);
+    if (cap < 1 || cap > (1 << 24)) op_bad(op, "cap in [1, 2^24]");
+    need(dog5, "dog5"); need(count, "count"); need(cand, "cand"); need(ctx, "ctx");
+    gtx::op_sift_extrema(ctx, dog5, h, w, octave, cap, count, cand);
+  });
+}
+
+int gtx_op_sift_refine(gtx_ctx* ctx, const float* dog5, int h, int w, int octave, const int* cand, int n, int* count, void* out) {
+  return guarded([&] {
+    const char* op = "sift_refine";
+    sift_image_ok(op, h, w, octave);
+    if (n < 0 || n > (1 << 24)) op_bad(op, "0 <= n <= 2^24 candidates");
+    need(dog5, "dog5"); need(count, "count");
+    if (n > 0) { need(cand, "cand"); need(out, "out"); }
+    for (int i = 0; i < n; ++i) {
+      const int* c = cand + 4 * (size_t)i;
+      if (c[0] != octave) op_bad(op, "a candidate of another octave");
+      if (c[1] < 1 || c[1] > 3 || c[2] < 5 || c[2] >= h - 5 || c[3] < 5 || c[3] >= w - 5) op_bad(op, "a candidate outside layers 1..3 or inside the border of 5");
+    }
+    need(ctx, "ctx");
+    gtx::op_sift_refine(ctx, dog5, h, w, octave, cand, n, count, out);
+  });
+}
+
+int gtx_op_sift_orient(gtx_ctx* ctx, const float* gauss_layer, int h, int w, int octave, const void* refined, int n, int cap, int* count, void* out,
+                       float* hist) {
+  return guarded([&] {
+    const char* op = "sift_orient";
+    sift_image_ok(op, h, w, octave);
+    if (n < 0 || n > (1 << 20)) op_bad(op, "0 <= n <= 2^20 keypoints");
+    if (cap < 1 || cap > (1 << 24)) op_bad(op, "cap in [1, 2^24]");
+    need(gauss_layer, "gauss_layer"); need(count, "count"); need(out, "out");
+    if (n > 0) { need(refined, "refined"); need(hist, "hist"); }
+    for (int i = 0; i < n; ++i) {
+      float f[4];
+      int k[5];
+      std::memcpy(f, static_cast<const char*>(refined) + 52 * (size_t)i, sizeof f);
+      std::memcpy(k, static_cast<const char*>(refined) + 52 * (size_t)i + 16, sizeof k);
+      if (k[1] != octave) op_bad(op, "a keypoint of another octave");
+      if (k[2] < 0 || k[2] > 5 || k[3] < 0 || k[3] >= h || k[4] < 0 || k[4] >= w) op_bad(op, "a keypoint outside layers 0..5 or outside the image");
+      // the window's radius is rint(4.5 * size / 2 / 2^octave) pixels; the kernel walks (2 radius + 1)^2 of them
+      if (!(f[2] > 0.f && 4.5 * 0.5 * (double)f[2] / (double)(1 << octave) <= 2048.0)) op_bad(op, "a keypoint size that is not positive, or a window radius above 2048");
+    }
+    need(ctx, "ctx");
+    gtx::op_sift_orient(ctx, gauss_layer, h, w, octave, refined, n, cap, count, out, hist);
+  });
+}
+
+int gtx_op_sift_describe(gtx_ctx* ctx, const float* gauss_layer, int h, int w, const void* finals, int n, int root, float root_eps, float* desc) {
+  return guarded([&] {
+    const char* op = "sift_describe";
+    sift_image_ok(op, h, w, 0);
+    if (n < 0 || n > (1 << 20)) op_bad(op, "0 <= n <= 2^20 keypoints");
+    if (root != 0 && root != 1) op_bad(op, "root is 0 or 1");
+    need(gauss_layer, "gauss_layer");
+    if (n > 0) { need(finals, "finals"); need(desc, "desc"); }
+    for (int i = 0; i < n; ++i) {
+      double ori;
+      float f[3];
+      int k[2];
+      const char* rec = static_cast<const char*>(finals) + 32 * (size_t)i;
+      std::memcpy(&ori, rec, sizeof ori);
+      std::memcpy(f, rec + 8, sizeof f);
+      std::memcpy(k, rec + 20, sizeof k);
+      if (k[0] != 0 || k[1] < 0 || k[1] > 5) op_bad(op, "records name octave 0 and a layer 0..5 (the one image given)");
+      if (!(ori >= 0.0 && ori <= 360.0)) op_bad(op, "ori in [0, 360] degrees");
+      if (!(std::fabs(f[0]) <= 1e6f && std::fabs(f[1]) <= 1e6f)) op_bad(op, "a position that is not a number, or beyond 1e6 pixels");
+      if (!(f[2] > 0.f && f[2] <= 1e6f)) op_bad(op, "scl in (0, 1e6] (the window's radius is clamped by the image diagonal)");
+    }
+    need(ctx, "ctx");
+    gtx::op_sift_describe(ctx, gauss_layer, h, w, finals, n, root, root_eps, desc);
   });
 }
 

@@ -22,6 +22,8 @@
 #include <cmath>
 #include <cstring>
 
+#include "net_runtime.hpp"   // gtx_ctx
+#include "op_staging.hpp"
 #include "sift.hpp"
 
 namespace gtx {
@@ -334,8 +336,9 @@ __global__ __launch_bounds__(256) void refine_kernel(const OctaveTable T, const 
 }
 
 // calcOrientationHist + peak picking: one wave per refined keypoint
+// hist_out (null on the product path): the smoothed histogram of every input keypoint, [n][kOriBins]
 __global__ __launch_bounds__(256) void orient_kernel(const OctaveTable T, const Refined* __restrict__ in, int n, Oriented* __restrict__ out,
-                                                     int* __restrict__ n_out, int cap) {
+                                                     int* __restrict__ n_out, int cap, float* __restrict__ hist_out) {
   __shared__ double s_hist[4][kOriBins];
   __shared__ float s_tmp[4][kOriBins + 4], s_h[4][kOriBins];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -381,6 +384,7 @@ __global__ __launch_bounds__(256) void orient_kernel(const OctaveTable T, const 
     const float* t = s_tmp[wave] + lane;   // t[0..4] = tmp[lane-2 .. lane+2]
     hv = ((t[0] + t[4]) * (1.f / 16.f) + (t[1] + t[3]) * (4.f / 16.f)) + t[2] * (6.f / 16.f);
     s_h[wave][lane] = hv;
+    if (hist_out) hist_out[(size_t)i * kOriBins + lane] = hv;
   }
   float mx = hv;
 #pragma unroll
@@ -508,7 +512,143 @@ Taps make_taps(double sigma) {
   return t;
 }
 
+// dst = Gaussian(src), dog (may be null) = dst - src, in one of three forms that give the same bits (tests/test_sift_ops_gpu.py,
+// test_blur_forms_equal_the_oracle): 0 = the tile kernel, with the radius at compile time where there is an instance; 1 = the generic
+// tile kernel whatever the radius; 2 = the row and column passes through the scratch image `tmp` and a subtraction pass.
+void launch_blur(const float* src, float* dst, float* dog, float* tmp, int w, int h, const Taps& t, int form, hipStream_t s) {
+  if (form == 2) {
+    hipLaunchKernelGGL(blur_h_kernel, dim3(cdiv(w, 256), h), dim3(256), 0, s, src, tmp, w, h, t);
+    hipLaunchKernelGGL(blur_v_kernel, dim3(cdiv(w, 256), h), dim3(256), 0, s, tmp, dst, w, h, t);
+    const size_t np = (size_t)w * h;
+    if (dog) hipLaunchKernelGGL(sub_kernel, dim3((unsigned)cdiv((long)np, 256L)), dim3(256), 0, s, dst, src, dog, np);
+    return;
+  }
+  const dim3 grid(cdiv(w, kBlurTW), cdiv(h, kBlurTH));
+  switch (form == 1 ? 0 : t.r) {                           // the default scale space's radii at compile time; anything else: the generic tile
+    case 5: hipLaunchKernelGGL(blur_tile_kernel_r<5>, grid, dim3(256), 0, s, src, dst, dog, w, h, t); break;
+    case 6: hipLaunchKernelGGL(blur_tile_kernel_r<6>, grid, dim3(256), 0, s, src, dst, dog, w, h, t); break;
+    case 8: hipLaunchKernelGGL(blur_tile_kernel_r<8>, grid, dim3(256), 0, s, src, dst, dog, w, h, t); break;
+    case 10: hipLaunchKernelGGL(blur_tile_kernel_r<10>, grid, dim3(256), 0, s, src, dst, dog, w, h, t); break;
+    case 13: hipLaunchKernelGGL(blur_tile_kernel_r<13>, grid, dim3(256), 0, s, src, dst, dog, w, h, t); break;
+    default: hipLaunchKernelGGL(blur_tile_kernel, grid, dim3(256), 0, s, src, dst, dog, w, h, t);
+  }
+}
+
+// The three layer passes of octave o: candidates are appended to cand (at most cap are stored), *cnt counts every one of them.
+// An octave without an interior (a side of 2 * kBorder or less) launches nothing.
+void launch_extrema(const OctaveTable& T, int o, Cand* cand, int* cnt, int cap, hipStream_t s) {
+  const int ww = T.w[o], hh = T.h[o];
+  if (ww <= 2 * kBorder || hh <= 2 * kBorder) return;
+  const float thr = (float)std::floor(0.5 * kContrastThr / kLayers * 255);
+  for (int i = 1; i <= kLayers; ++i)
+    hipLaunchKernelGGL(extrema_kernel, dim3(cdiv(ww - 2 * kBorder, 256), hh - 2 * kBorder), dim3(256), 0, s, T.d[o][i - 1], T.d[o][i], T.d[o][i + 1],
+                       ww, hh, thr, o, i, cand, cnt, cap);
+}
+
+static_assert(sizeof(Cand) == 16 && sizeof(Refined) == 52 && sizeof(Oriented) == 52 && sizeof(Final) == 32,
+              "the record layouts include/gtx.h documents for gtx_op_sift_*");
+
 }  // namespace
+
+// ---- the kernels one stage at a time, on host arrays (gtx_op_sift_*; tests/test_sift_ops_gpu.py). Sizes, and every record field a
+// kernel would turn into an address, are checked by the callers in gtx_ops.cpp before anything here touches the GPU. Each hook
+// builds a one-octave OctaveTable over fresh device buffers and launches as detect_and_compute launches.
+int sift_blur_radius(double sigma) { return make_taps(sigma).r; }
+
+void op_sift_blur(gtx_ctx* ctx, const float* src, int h, int w, double sigma, int form, float* dst, float* dog) {
+  const Taps t = make_taps(sigma);
+  GTX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const size_t bytes = sizeof(float) * (size_t)w * h;
+  DevBuf ds, dd, dg, tmp;
+  upload(ds, src, bytes);
+  fill_ff(dd, bytes);
+  fill_ff(dg, bytes);
+  fill_ff(tmp, bytes);
+  launch_blur(ds.as<float>(), dd.as<float>(), dog ? dg.as<float>() : nullptr, tmp.as<float>(), w, h, t, form, s);
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipStreamSynchronize(s));
+  download(dst, dd, bytes);
+  if (dog) download(dog, dg, bytes);
+}
+
+void op_sift_extrema(gtx_ctx* ctx, const float* dog5, int h, int w, int octave, int cap, int* count, int* cand) {
+  GTX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const size_t np = (size_t)w * h;
+  DevBuf dd, dc, dn;
+  upload(dd, dog5, sizeof(float) * np * kDog);
+  fill_ff(dc, sizeof(Cand) * (size_t)cap);
+  zeros(dn, sizeof(int));
+  OctaveTable T{};
+  T.n = octave + 1; T.w[octave] = w; T.h[octave] = h;
+  for (int i = 0; i < kDog; ++i) T.d[octave][i] = dd.as<float>() + np * i;
+  launch_extrema(T, octave, dc.as<Cand>(), dn.as<int>(), cap, s);
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipStreamSynchronize(s));
+  download(count, dn, sizeof(int));
+  const int stored = std::min(*count, cap);
+  if (stored > 0) download(cand, dc, sizeof(Cand) * (size_t)stored);
+}
+
+void op_sift_refine(gtx_ctx* ctx, const float* dog5, int h, int w, int octave, const int* cand, int n, int* count, void* out) {
+  GTX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const size_t np = (size_t)w * h;
+  DevBuf dd, dc, dr, dn;
+  upload(dd, dog5, sizeof(float) * np * kDog);
+  upload(dc, cand, sizeof(Cand) * (size_t)n);
+  fill_ff(dr, sizeof(Refined) * (size_t)n);
+  zeros(dn, sizeof(int));
+  OctaveTable T{};
+  T.n = octave + 1; T.w[octave] = w; T.h[octave] = h;
+  for (int i = 0; i < kDog; ++i) T.d[octave][i] = dd.as<float>() + np * i;
+  if (n > 0) hipLaunchKernelGGL(refine_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, T, dc.as<Cand>(), n, dr.as<Refined>(), dn.as<int>());
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipStreamSynchronize(s));
+  download(count, dn, sizeof(int));
+  GTX_CHECK(*count >= 0 && *count <= n, "sift_refine: %d keypoints of %d candidates", *count, n);
+  if (*count > 0) download(out, dr, sizeof(Refined) * (size_t)*count);
+}
+
+void op_sift_orient(gtx_ctx* ctx, const float* gauss_layer, int h, int w, int octave, const void* refined, int n, int cap, int* count, void* out,
+                    float* hist) {
+  GTX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  DevBuf dg, dr, dout, dn, dh;
+  upload(dg, gauss_layer, sizeof(float) * (size_t)w * h);
+  upload(dr, refined, sizeof(Refined) * (size_t)n);
+  fill_ff(dout, sizeof(Oriented) * (size_t)cap);
+  fill_ff(dh, sizeof(float) * kOriBins * (size_t)n);
+  zeros(dn, sizeof(int));
+  OctaveTable T{};
+  T.n = octave + 1; T.w[octave] = w; T.h[octave] = h;
+  for (int i = 0; i < kGauss; ++i) T.g[octave][i] = dg.as<float>();       // whichever layer a record names: the one image
+  if (n > 0)
+    hipLaunchKernelGGL(orient_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, T, dr.as<Refined>(), n, dout.as<Oriented>(), dn.as<int>(), cap, dh.as<float>());
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipStreamSynchronize(s));
+  download(count, dn, sizeof(int));
+  const int stored = std::min(*count, cap);
+  if (stored > 0) download(out, dout, sizeof(Oriented) * (size_t)stored);
+  if (n > 0) download(hist, dh, sizeof(float) * kOriBins * (size_t)n);
+}
+
+void op_sift_describe(gtx_ctx* ctx, const float* gauss_layer, int h, int w, const void* finals, int n, int root, float root_eps, float* desc) {
+  GTX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  DevBuf dg, df, dd;
+  upload(dg, gauss_layer, sizeof(float) * (size_t)w * h);
+  upload(df, finals, sizeof(Final) * (size_t)n);
+  fill_ff(dd, sizeof(float) * 128 * (size_t)n);
+  OctaveTable T{};
+  T.n = 1; T.w[0] = w; T.h[0] = h;
+  for (int i = 0; i < kGauss; ++i) T.g[0][i] = dg.as<float>();
+  if (n > 0) hipLaunchKernelGGL(describe_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, T, df.as<Final>(), n, dd.as<float>(), root ? 1 : 0, root_eps);
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipStreamSynchronize(s));
+  if (n > 0) download(desc, dd, sizeof(float) * 128 * (size_t)n);
+}
 
 struct Sift::Impl {
   int device;
@@ -529,26 +669,11 @@ struct Sift::Impl {
   }
 
   // dst = Gaussian(src, sigma); dog (may be null) = dst - src. GTX_SIFT_TWO_PASS=1: the two row / column passes through the scratch
-  // image and a subtraction pass (the round-1 form, kept for the A/B and the bit-identity test between the two)
+  // image and a subtraction pass (the round-1 form, kept for the A/B; tests/test_sift_ops_gpu.py::test_blur_forms_equal_the_oracle
+  // holds the two forms, and the generic tile, to the same bits through gtx_op_sift_blur)
   void blur(const float* src, float* dst, float* dog, int w, int h, double sigma) {
-    const Taps t = make_taps(sigma);
     static const bool two_pass = [] { const char* e = getenv("GTX_SIFT_TWO_PASS"); return e && e[0] == '1'; }();
-    if (two_pass) {
-      hipLaunchKernelGGL(blur_h_kernel, dim3(cdiv(w, 256), h), dim3(256), 0, s, src, tmp.as<float>(), w, h, t);
-      hipLaunchKernelGGL(blur_v_kernel, dim3(cdiv(w, 256), h), dim3(256), 0, s, tmp.as<float>(), dst, w, h, t);
-      const size_t np = (size_t)w * h;
-      if (dog) hipLaunchKernelGGL(sub_kernel, dim3((unsigned)cdiv((long)np, 256L)), dim3(256), 0, s, dst, src, dog, np);
-      return;
-    }
-    const dim3 grid(cdiv(w, kBlurTW), cdiv(h, kBlurTH));
-    switch (t.r) {                                           // the default scale space's radii at compile time; anything else: the generic tile
-      case 5: hipLaunchKernelGGL(blur_tile_kernel_r<5>, grid, dim3(256), 0, s, src, dst, dog, w, h, t); break;
-      case 6: hipLaunchKernelGGL(blur_tile_kernel_r<6>, grid, dim3(256), 0, s, src, dst, dog, w, h, t); break;
-      case 8: hipLaunchKernelGGL(blur_tile_kernel_r<8>, grid, dim3(256), 0, s, src, dst, dog, w, h, t); break;
-      case 10: hipLaunchKernelGGL(blur_tile_kernel_r<10>, grid, dim3(256), 0, s, src, dst, dog, w, h, t); break;
-      case 13: hipLaunchKernelGGL(blur_tile_kernel_r<13>, grid, dim3(256), 0, s, src, dst, dog, w, h, t); break;
-      default: hipLaunchKernelGGL(blur_tile_kernel, grid, dim3(256), 0, s, src, dst, dog, w, h, t);
-    }
+    launch_blur(src, dst, dog, tmp.as<float>(), w, h, make_taps(sigma), two_pass ? 2 : 0, s);
   }
 };
 
@@ -637,29 +762,27 @@ void Sift::detect_and_compute(const uint8_t* image, int h, int w, int max_featur
   // ---- extrema -> refine -> orientation
   int* cnt = S.counters.as<int>();
   GTX_HIP(hipMemsetAsync(cnt, 0, 4 * sizeof(int), s));
-  const float thr = (float)std::floor(0.5 * kContrastThr / kLayers * 255);
-  for (int o = 0; o < T.n; ++o) {
-    const int ww = T.w[o], hh = T.h[o];
-    if (ww <= 2 * kBorder || hh <= 2 * kBorder) continue;
-    for (int i = 1; i <= kLayers; ++i)
-      hipLaunchKernelGGL(extrema_kernel, dim3(cdiv(ww - 2 * kBorder, 256), hh - 2 * kBorder), dim3(256), 0, s, T.d[o][i - 1], T.d[o][i],
-                         T.d[o][i + 1], ww, hh, thr, o, i, S.cand.as<Cand>(), cnt, (int)S.cand_cap);
-  }
+  for (int o = 0; o < T.n; ++o) launch_extrema(T, o, S.cand.as<Cand>(), cnt, (int)S.cand_cap, s);
   int hc[4];
   GTX_HIP(hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, s));
   GTX_HIP(hipStreamSynchronize(s));
-  const int n_cand = std::min<long>(hc[0], (long)S.cand_cap);
+  // A full list has dropped whatever found no room, and which entries those were depends on the order of the atomics: the keypoints
+  // would differ from run to run. The reference has no cap at all, so an overflow is an error, not a smaller answer.
+  GTX_CHECK(hc[0] >= 0 && (size_t)hc[0] <= S.cand_cap, "sift: extrema stage found %d candidates, the list holds %zu", hc[0], S.cand_cap);
+  const int n_cand = hc[0];
   if (n_cand > 0) hipLaunchKernelGGL(refine_kernel, dim3(cdiv(n_cand, 256)), dim3(256), 0, s, T, S.cand.as<Cand>(), n_cand, S.refined.as<Refined>(), cnt + 1);
   GTX_HIP(hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, s));
   GTX_HIP(hipStreamSynchronize(s));
   const int n_ref = hc[1];
+  GTX_CHECK(n_ref >= 0 && (size_t)n_ref <= S.cand_cap, "sift: refine stage kept %d keypoints, the list holds %zu", n_ref, S.cand_cap);
   if (n_ref > 0)
     hipLaunchKernelGGL(orient_kernel, dim3(cdiv(n_ref, 4)), dim3(256), 0, s, T, S.refined.as<Refined>(), n_ref, S.oriented.as<Oriented>(), cnt + 2,
-                       (int)S.kp_cap);
+                       (int)S.kp_cap, (float*)nullptr);
   GTX_HIP(hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, s));
   GTX_HIP(hipStreamSynchronize(s));
   GTX_HIP(hipEventRecord(S.ev[2], s));
-  const int n_ori = std::min<long>(hc[2], (long)S.kp_cap);
+  GTX_CHECK(hc[2] >= 0 && (size_t)hc[2] <= S.kp_cap, "sift: orientation stage made %d keypoints, the list holds %zu", hc[2], S.kp_cap);
+  const int n_ori = hc[2];
   std::vector<Oriented> ori(n_ori);
   if (n_ori) GTX_HIP(hipMemcpy(ori.data(), S.oriented.p, sizeof(Oriented) * n_ori, hipMemcpyDeviceToHost));
   // OpenCV order: octave, layer, row, column of the scale-space extremum, then orientation bin -- one 64-bit key per keypoint.

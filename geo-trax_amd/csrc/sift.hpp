@@ -10,6 +10,8 @@
 
 #include "common.hpp"
 
+struct gtx_ctx;
+
 namespace gtx {
 
 struct SiftKeypoint {
@@ -46,5 +48,20 @@ class Sift {
   struct Impl;
   std::unique_ptr<Impl> impl_;
 };
+
+// ---- gtx_op_sift_*: one stage each on host arrays (arguments checked by the caller, gtx_ops.cpp; record layouts: include/gtx.h)
+// radius of the Gaussian the scale space would use for sigma; fails above the kernels' largest (16), as every blur does
+int sift_blur_radius(double sigma);
+// one Gaussian blur (+ DoG layer when dog is given): form 0 as the pyramid dispatches it, 1 the generic tile kernel, 2 row / column / subtraction passes
+void op_sift_blur(gtx_ctx* ctx, const float* src, int h, int w, double sigma, int form, float* dst, float* dog);
+// the three extrema passes over the five DoG layers of one octave: every candidate counted, at most cap stored
+void op_sift_extrema(gtx_ctx* ctx, const float* dog5, int h, int w, int octave, int cap, int* count, int* cand);
+// refine_kernel on n candidates of that octave: the accepted ones, in no particular order, each with the candidate it came from
+void op_sift_refine(gtx_ctx* ctx, const float* dog5, int h, int w, int octave, const int* cand, int n, int* count, void* out);
+// orient_kernel on n refined records over one Gaussian layer: every peak counted, at most cap stored; hist [n][36] smoothed histograms
+void op_sift_orient(gtx_ctx* ctx, const float* gauss_layer, int h, int w, int octave, const void* refined, int n, int cap, int* count, void* out,
+                    float* hist);
+// describe_kernel on n final records over one Gaussian layer: desc [n][128]
+void op_sift_describe(gtx_ctx* ctx, const float* gauss_layer, int h, int w, const void* finals, int n, int root, float root_eps, float* desc);
 
 }  // namespace gtx

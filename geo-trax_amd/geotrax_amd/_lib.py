@@ -84,7 +84,7 @@ class HeadLevel(C.Structure):
 
 # name -> (restype, argtypes); kept in one table so tests can check the export list against
 # include/gtx.h.
-ABI_VERSION = 13       # GTX_ABI_VERSION of include/gtx.h
+ABI_VERSION = 14       # GTX_ABI_VERSION of include/gtx.h
 _P = C.c_void_p
 _SIGNATURES = {
     "gtx_abi_version": (C.c_int, []),
@@ -168,6 +168,11 @@ _SIGNATURES = {
     "gtx_sift_detect": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), _P, _P, _P]),
     "gtx_sift_stage_ms": (C.c_int, [_P, _P]),
     "gtx_sift_pyramid": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gtx_op_sift_blur": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, C.c_int, _P, _P]),
+    "gtx_op_sift_extrema": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _P]),
+    "gtx_op_sift_refine": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int), _P]),
+    "gtx_op_sift_orient": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P]),
+    "gtx_op_sift_describe": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, _P]),
     "gtx_op_match_2nn": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
     "gtx_op_preprocess": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int]),
     "gtx_detector_create": (C.c_int, [_P, C.POINTER(DetConfig), C.POINTER(_P)]),

@@ -542,3 +542,76 @@ def gmc_ransac(pairs, seed: int = 0, *, ctx=None):
     best, win, model, count = C.c_int(-2), C.c_int(-2), np.full(4, np.nan, np.float64), np.full(512, -2, np.int32)
     check(ctx.lib.gtx_op_gmc_ransac(ctx.handle, ptr(p) if len(p) else None, len(p), int(seed) & 0xFFFFFFFF, C.byref(best), C.byref(win), ptr(model), ptr(count)))
     return dict(best_count=best.value, winner=win.value, model=model, count=count)
+
+
+# ---- the SIFT kernels one stage at a time (csrc/sift.hip; record layouts: include/gtx.h)
+_KEY = [("key_o", "<i4"), ("key_layer", "<i4"), ("key_r", "<i4"), ("key_c", "<i4")]
+SIFT_REFINED = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("response", "<f4"), ("word", "<i4"), ("o", "<i4"), ("layer", "<i4"),
+                         ("r", "<i4"), ("c", "<i4")] + _KEY)
+SIFT_ORIENTED = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("word", "<i4"), ("o", "<i4"),
+                          ("layer", "<i4")] + _KEY + [("bin", "<i4")])
+SIFT_FINAL = np.dtype([("ori", "<f8"), ("px", "<f4"), ("py", "<f4"), ("scl", "<f4"), ("o", "<i4"), ("layer", "<i4"), ("pad", "<i4")])
+assert SIFT_REFINED.itemsize == 52 and SIFT_ORIENTED.itemsize == 52 and SIFT_FINAL.itemsize == 32
+
+
+def sift_blur(src, sigma: float, form: int = 0, *, dog: bool = True, ctx=None):
+    """One Gaussian blur of the SIFT scale space on src [h, w] f32 -> (dst, dst - src or None). form 0: as the pyramid dispatches
+    it, 1: the generic tile kernel, 2: the row / column / subtraction passes. A radius above 16 raises."""
+    ctx = ctx or _lib.default_context()
+    a = np.ascontiguousarray(src, dtype=np.float32)
+    assert a.ndim == 2
+    dst = np.full(a.shape, np.nan, np.float32)
+    d = np.full(a.shape, np.nan, np.float32) if dog else None
+    check(ctx.lib.gtx_op_sift_blur(ctx.handle, ptr(a), a.shape[0], a.shape[1], float(sigma), int(form), ptr(dst), ptr(d)))
+    return dst, d
+
+
+def sift_extrema(dog5, octave: int = 0, cap: int | None = None, *, ctx=None):
+    """The three extrema passes over the five DoG layers [5, h, w] f32 of one octave -> (true count, stored candidates
+    [min(count, cap), 4] i32 = (octave, layer, row, column), in no particular order). cap defaults to every interior pixel."""
+    ctx = ctx or _lib.default_context()
+    d = np.ascontiguousarray(dog5, dtype=np.float32)
+    assert d.ndim == 3 and d.shape[0] == 5
+    h, w = d.shape[1:]
+    cap = max(1, 3 * h * w) if cap is None else int(cap)
+    n, cand = C.c_int(-1), np.full((cap, 4), -1, np.int32)
+    check(ctx.lib.gtx_op_sift_extrema(ctx.handle, ptr(d), h, w, int(octave), cap, C.byref(n), ptr(cand)))
+    return n.value, cand[:min(n.value, cap)].copy()
+
+
+def sift_refine(dog5, cand, octave: int = 0, *, ctx=None):
+    """refine_kernel on candidates [n, 4] i32 of one octave -> the accepted records (SIFT_REFINED), in no particular order."""
+    ctx = ctx or _lib.default_context()
+    d = np.ascontiguousarray(dog5, dtype=np.float32)
+    assert d.ndim == 3 and d.shape[0] == 5
+    c = np.ascontiguousarray(cand, dtype=np.int32).reshape(-1, 4)
+    n, out = C.c_int(-1), np.zeros(max(len(c), 1), SIFT_REFINED)
+    check(ctx.lib.gtx_op_sift_refine(ctx.handle, ptr(d), d.shape[1], d.shape[2], int(octave), ptr(c) if len(c) else None, len(c), C.byref(n), ptr(out)))
+    return out[:n.value].copy()
+
+
+def sift_orient(gauss_layer, refined, octave: int = 0, cap: int | None = None, *, ctx=None):
+    """orient_kernel on refined records (SIFT_REFINED) over one Gaussian layer [h, w] f32 -> (true count of peaks, the stored
+    records (SIFT_ORIENTED) in no particular order, hist [n, 36] f32: the smoothed histogram of every input record)."""
+    ctx = ctx or _lib.default_context()
+    g = np.ascontiguousarray(gauss_layer, dtype=np.float32)
+    assert g.ndim == 2
+    r = np.ascontiguousarray(refined, dtype=SIFT_REFINED).reshape(-1)
+    cap = max(1, 36 * len(r)) if cap is None else int(cap)
+    n, out, hist = C.c_int(-1), np.zeros(cap, SIFT_ORIENTED), np.full((max(len(r), 1), 36), np.nan, np.float32)
+    check(ctx.lib.gtx_op_sift_orient(ctx.handle, ptr(g), g.shape[0], g.shape[1], int(octave), ptr(r) if len(r) else None, len(r), cap, C.byref(n), ptr(out),
+                                     ptr(hist)))
+    return n.value, out[:min(n.value, cap)].copy(), hist[:len(r)]
+
+
+def sift_describe(gauss_layer, px, py, ori, scl, *, root: bool = False, eps: float = 1e-8, ctx=None):
+    """describe_kernel over one Gaussian layer [h, w] f32 for keypoints at octave-local (px, py) with orientation ori (degrees,
+    360 - angle) and scale scl -> desc [n, 128] f32 (0..255 integers; RootSIFT rows when root)."""
+    ctx = ctx or _lib.default_context()
+    g = np.ascontiguousarray(gauss_layer, dtype=np.float32)
+    assert g.ndim == 2
+    f = np.zeros(len(np.atleast_1d(px)), SIFT_FINAL)
+    f["px"], f["py"], f["ori"], f["scl"] = px, py, ori, scl
+    desc = np.full((max(len(f), 1), 128), np.nan, np.float32)
+    check(ctx.lib.gtx_op_sift_describe(ctx.handle, ptr(g), g.shape[0], g.shape[1], ptr(f) if len(f) else None, len(f), int(root), float(eps), ptr(desc)))
+    return desc[:len(f)]

@@ -61,8 +61,11 @@ extern "C" {
  *     keypoints on one level) instead of by max_features; the candidate lists are sized so that no FAST corner can be dropped.
  *     gtx_jpeg_{record_bound, probe, parse, decode_dev, kernel_ms}, gtx_feeder_open_jpeg and feeder kind 2 (compressed JPEG frames) added: new entry
  *     points only, no struct or existing signature changed, so the number stays. gtx_gmc_counts and gtx_op_gmc_{corners, lk, ransac} (the
- *     sparse-optical-flow GMC's kernels one launcher at a time) added: the same, the number stays. */
-#define GTX_ABI_VERSION 13
+ *     sparse-optical-flow GMC's kernels one launcher at a time) added: the same, the number stays.
+ * 14: gtx_op_sift_{blur, extrema, refine, orient, describe} added: the SIFT kernels one stage at a time. gtx_sift_detect and
+ *     gtx_register_images fail (GTX_ERR_UNSUPPORTED) when a stage finds more candidates or keypoints than its list holds, instead of
+ *     going on with whichever of them found room. */
+#define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
   GTX_OK = 0,
@@ -861,6 +864,31 @@ int gtx_sift_stage_ms(gtx_sift* s, float out[4]);
 /* Gaussian (kind 0) or DoG (kind 1) image of the last detect call, [h][w] fp32. */
 int gtx_sift_pyramid(gtx_sift* s, int kind, int octave, int layer, int cap, float* out, int* h, int* w,
                      int* n_octaves);
+
+/* The SIFT kernels one stage at a time on host arrays (images [h][w] fp32, 1..4096 a side), each launched as gtx_sift_detect
+ * launches it over a one-octave pyramid table; sizes, and every record field a kernel turns into an address, are checked before the
+ * GPU is touched. `octave` (0..15) is the octave the images belong to: records carry it, and positions and sizes scale with 2^octave.
+ * Records are rows of 32-bit words:
+ *   candidate [4] i32 = (octave, layer, row, column);
+ *   refined  [13]     = f32 (x, y, size, response), i32 (octave word, octave, layer, row, column), the candidate it came from;
+ *   oriented [13]     = f32 (x, y, size, angle, response), i32 (octave word, octave, layer), the candidate, i32 orientation bin;
+ *   final    [8]      = f64 ori (360 - angle, degrees), f32 (px, py: octave-local position; scl), i32 (octave = 0, layer, 0).
+ * _blur: dst = Gaussian(src, sigma) with radius ((int)rint(8 sigma + 1) | 1) / 2 <= 16 (a larger one is an error), dog (may be NULL) =
+ *   dst - src. form 0: as the pyramid dispatches it (a compile-time instance for radii 5, 6, 8, 10, 13, else the generic tile kernel),
+ *   1: the generic tile kernel, 2: row pass, column pass and subtraction pass. All three give the same bits.
+ * _extrema: dog5 = the octave's five DoG layers [5][h][w]; the three layer passes. *count = every candidate, the first min(count, cap)
+ *   entries of cand are stored candidates in no particular order (which ones, when count > cap, depends on the run).
+ * _refine: n candidates of layers 1..3 inside the border of 5 -> *count accepted records in out [n][13], in no particular order.
+ * _orient: n refined records (layer 0..5 all read gauss_layer) -> *count peaks, the first min(count, cap) stored in out [cap][13];
+ *   hist [n][36] = the smoothed orientation histogram of every input record.
+ * _describe: n final records -> desc [n][128]: 0..255 integers, or their RootSIFT form sqrt(d / (sum(d) + root_eps)) when root != 0. */
+int gtx_op_sift_blur(gtx_ctx* ctx, const float* src, int h, int w, double sigma, int form, float* dst, float* dog);
+int gtx_op_sift_extrema(gtx_ctx* ctx, const float* dog5, int h, int w, int octave, int cap, int* count, int* cand);
+int gtx_op_sift_refine(gtx_ctx* ctx, const float* dog5, int h, int w, int octave, const int* cand, int n, int* count, void* out);
+int gtx_op_sift_orient(gtx_ctx* ctx, const float* gauss_layer, int h, int w, int octave, const void* refined, int n, int cap, int* count,
+                       void* out, float* hist);
+int gtx_op_sift_describe(gtx_ctx* ctx, const float* gauss_layer, int h, int w, const void* finals, int n, int root, float root_eps,
+                         float* desc);
 
 /* Stabilizer.transform_cur_boxes(): maps the 4 corners of each xywh box through H and
  * returns the axis-aligned bounding rectangle as xywh (rule pinned on the reference's golden

@@ -188,8 +188,10 @@ def _solve3(Hm, b):
     return x
 
 
-def refine(dog_o, octv: int, layer: int, r: int, c: int):
-    """adjustLocalExtrema -> (x, y, octave word, size, response, layer, r, c) or None."""
+def refine(dog_o, octv: int, layer: int, r: int, c: int, trace: list | None = None):
+    """adjustLocalExtrema -> (x, y, octave word, size, response, layer, r, c) or None. trace (a list) receives what happened:
+    ("move", d layer, d r, d c) per step taken, then the name of the exit taken, or "accept"."""
+    note = (lambda *a: trace.append(a if len(a) > 1 else a[0])) if trace is not None else (lambda *a: None)
     img_scale = F(1.0 / 255.0)
     ds, sds, cds = F(img_scale * F(0.5)), img_scale, F(img_scale * F(0.25))
     h, w = dog_o[0].shape
@@ -207,23 +209,32 @@ def refine(dog_o, octv: int, layer: int, r: int, c: int):
         dys = (nxt[r + 1, c] - nxt[r - 1, c] - prv[r + 1, c] + prv[r - 1, c]) * cds
         X = _solve3([[dxx, dxy, dxs], [dxy, dyy, dys], [dxs, dys, dss]], dD)
         if X is None:
+            note("singular")
             return None
         xi, xr, xc = F(-X[2]), F(-X[1]), F(-X[0])
         if abs(xi) < 0.5 and abs(xr) < 0.5 and abs(xc) < 0.5:
             break
         if abs(xi) > 2 ** 30 or abs(xr) > 2 ** 30 or abs(xc) > 2 ** 30:
+            note("offset")
             return None
         c += cv_round(xc); r += cv_round(xr); layer += cv_round(xi)
-        if layer < 1 or layer > N_LAYERS or c < BORDER or c >= w - BORDER or r < BORDER or r >= h - BORDER:
+        note("move", cv_round(xi), cv_round(xr), cv_round(xc))
+        if layer < 1 or layer > N_LAYERS:
+            note("layer")
+            return None
+        if c < BORDER or c >= w - BORDER or r < BORDER or r >= h - BORDER:
+            note("border")
             return None
         i += 1
     if i >= MAX_INTERP:
+        note("steps")
         return None
     img, prv, nxt = dog_o[layer], dog_o[layer - 1], dog_o[layer + 1]
     dD = np.array([(img[r, c + 1] - img[r, c - 1]) * ds, (img[r + 1, c] - img[r - 1, c]) * ds, (nxt[r, c] - prv[r, c]) * ds], F)
     t = F(F(dD[0] * xc) + F(dD[1] * xr)) + F(dD[2] * xi)
     contr = F(img[r, c] * img_scale + F(t * F(0.5)))
     if abs(contr) * N_LAYERS < CONTRAST_THR:
+        note("contrast")
         return None
     v2 = F(img[r, c] * F(2))
     dxx = (img[r, c + 1] + img[r, c - 1] - v2) * sds
@@ -232,7 +243,9 @@ def refine(dog_o, octv: int, layer: int, r: int, c: int):
     tr = F(dxx + dyy)
     det = F(F(dxx * dyy) - F(dxy * dxy))
     if det <= 0 or F(tr * tr) * F(EDGE_THR) >= F((EDGE_THR + 1) ** 2) * det:
+        note("det" if det <= 0 else "edge")
         return None
+    note("accept")
     scale = float(1 << octv)
     x = F((c + xc) * F(scale)); y = F((r + xr) * F(scale))
     octave_word = octv + (layer << 8) + (cv_round((float(xi) + 0.5) * 255) << 16)
@@ -260,6 +273,41 @@ def orientation_hist(img: np.ndarray, r: int, c: int, radius: int, sigma: float)
     return ((t[:-4] + t[4:]) * F(1 / 16) + (t[1:-3] + t[3:-1]) * F(4 / 16) + t[2:-2] * F(6 / 16)).astype(F)
 
 
+def orientation_hist64(img: np.ndarray, r: int, c: int, radius: int, sigma: float, ambiguous: float | None = None):
+    """orientation_hist with every intermediate in float64 and math-precision atan2 / exp: the high-precision reference of
+    the histogram (float64 [36]). ambiguous = a tolerance in bin units: also returns, per bin, the 1-4-6-4-1 smoothed sum of
+    weight * magnitude of the pixels whose ori * 36 / 360 lies within that tolerance of a half-integer -- the pixels a last-bit
+    difference in atan2 can move to the neighbouring bin, each counted in both bins it may fall into."""
+    h, w = img.shape
+    ii, jj = np.mgrid[-radius:radius + 1, -radius:radius + 1]
+    y, x = r + ii, c + jj
+    ok = (y > 0) & (y < h - 1) & (x > 0) & (x < w - 1)
+    y, x, ii, jj = y[ok], x[ok], ii[ok], jj[ok]
+    g = img.astype(np.float64)
+    dx = g[y, x + 1] - g[y, x - 1]
+    dy = g[y - 1, x] - g[y + 1, x]
+    wgt = np.exp((ii * ii + jj * jj).astype(np.float64) * (-1.0 / (2.0 * sigma * sigma)))
+    ori = np.degrees(np.arctan2(dy, dx))
+    ori = np.where(ori < 0, ori + 360.0, ori)
+    mag = np.sqrt(dx * dx + dy * dy)
+    t = ori * (ORI_BINS / 360.0)
+    tmp = np.zeros(ORI_BINS, np.float64)
+    np.add.at(tmp, np.rint(t).astype(np.int64) % ORI_BINS, wgt * mag)
+
+    def smooth(v):
+        e = np.concatenate([v[-2:], v, v[:2]])
+        return (e[:-4] + e[4:]) * (1 / 16) + (e[1:-3] + e[3:-1]) * (4 / 16) + e[2:-2] * (6 / 16)
+
+    if ambiguous is None:
+        return smooth(tmp)
+    lo = np.floor(t)
+    near = np.abs(t - lo - 0.5) <= ambiguous
+    amb = np.zeros(ORI_BINS, np.float64)
+    np.add.at(amb, lo[near].astype(np.int64) % ORI_BINS, (wgt * mag)[near])
+    np.add.at(amb, (lo[near].astype(np.int64) + 1) % ORI_BINS, (wgt * mag)[near])
+    return smooth(tmp), smooth(amb)
+
+
 def keypoint_angles(hist: np.ndarray) -> list[float]:
     n = ORI_BINS
     thr = hist.max() * F(ORI_PEAK_RATIO)
@@ -276,6 +324,11 @@ def keypoint_angles(hist: np.ndarray) -> list[float]:
 
 def descriptor(img: np.ndarray, x: float, y: float, ori: float, scl: float) -> np.ndarray:
     """calcSIFTDescriptor: 4x4x8 histogram with trilinear interpolation, 0.2 clamp, x512 -> u8."""
+    return np.clip(np.rint(descriptor_unrounded(img, x, y, ori, scl)), 0, 255).astype(F)
+
+
+def descriptor_unrounded(img: np.ndarray, x: float, y: float, ori: float, scl: float) -> np.ndarray:
+    """The 128 values of `descriptor` before they are rounded and clipped to 0..255 (float32)."""
     d, n = DESCR_WIDTH, DESCR_BINS
     h, w = img.shape
     px, py = cv_round(x), cv_round(y)
@@ -319,7 +372,53 @@ def descriptor(img: np.ndarray, x: float, y: float, ori: float, scl: float) -> n
     thr = F(F(np.sqrt((dst.astype(np.float64) ** 2).sum())) * F(DESCR_MAG_THR))
     dst = np.minimum(dst, thr)
     nrm = F(INT_DESCR_FCTR) / max(F(np.sqrt((dst.astype(np.float64) ** 2).sum())), F(1.19e-7))
-    return np.clip(np.rint(dst * nrm), 0, 255).astype(F)
+    return (dst * nrm).astype(F)
+
+
+def descriptor_unrounded64(img: np.ndarray, x: float, y: float, ori: float, scl: float) -> np.ndarray:
+    """descriptor_unrounded with every intermediate in float64 and math-precision atan2 / exp / cos / sin: the high-precision
+    reference of the 128 values (float64). Clamped bins all hold the same value, the largest: the clamp's knee."""
+    d, n = DESCR_WIDTH, DESCR_BINS
+    h, w = img.shape
+    px, py = cv_round(x), cv_round(y)
+    hist_width = DESCR_SCL_FCTR * scl
+    radius = cv_round(hist_width * 1.4142135623730951 * (d + 1) * 0.5)
+    radius = min(radius, int(math.sqrt(h * h + w * w)))
+    cos_t, sin_t = math.cos(math.radians(ori)) / hist_width, math.sin(math.radians(ori)) / hist_width
+    ii, jj = np.mgrid[-radius:radius + 1, -radius:radius + 1]
+    ii, jj = ii.ravel().astype(np.float64), jj.ravel().astype(np.float64)
+    c_rot = jj * cos_t - ii * sin_t
+    r_rot = jj * sin_t + ii * cos_t
+    rbin = r_rot + (d / 2 - 0.5)
+    cbin = c_rot + (d / 2 - 0.5)
+    r, c = py + ii.astype(np.int64), px + jj.astype(np.int64)
+    ok = (rbin > -1) & (rbin < d) & (cbin > -1) & (cbin < d) & (r > 0) & (r < h - 1) & (c > 0) & (c < w - 1)
+    r, c, rbin, cbin, c_rot, r_rot = r[ok], c[ok], rbin[ok], cbin[ok], c_rot[ok], r_rot[ok]
+    g = img.astype(np.float64)
+    dx = g[r, c + 1] - g[r, c - 1]
+    dy = g[r - 1, c] - g[r + 1, c]
+    wgt = np.exp((c_rot * c_rot + r_rot * r_rot) * (-1.0 / (d * d * 0.5)))
+    o = np.degrees(np.arctan2(dy, dx))
+    o = np.where(o < 0, o + 360.0, o)
+    mag = np.sqrt(dx * dx + dy * dy) * wgt
+    obin = (o - ori) * (n / 360.0)
+    r0, c0, o0 = np.floor(rbin).astype(np.int64), np.floor(cbin).astype(np.int64), np.floor(obin).astype(np.int64)
+    rbin, cbin, obin = rbin - r0, cbin - c0, obin - o0
+    o0 = np.where(o0 < 0, o0 + n, o0)
+    o0 = np.where(o0 >= n, o0 - n, o0)
+    hist = np.zeros(((d + 2), (d + 2), (n + 2)), np.float64)
+    v_r1 = mag * rbin; v_r0 = mag - v_r1
+    v_rc11 = v_r1 * cbin; v_rc10 = v_r1 - v_rc11
+    v_rc01 = v_r0 * cbin; v_rc00 = v_r0 - v_rc01
+    for dr, dc, v in ((0, 0, v_rc00), (0, 1, v_rc01), (1, 0, v_rc10), (1, 1, v_rc11)):
+        v1 = v * obin; v0 = v - v1
+        np.add.at(hist, (r0 + 1 + dr, c0 + 1 + dc, o0), v0)
+        np.add.at(hist, (r0 + 1 + dr, c0 + 1 + dc, o0 + 1), v1)
+    hist[:, :, 0] += hist[:, :, n]
+    hist[:, :, 1] += hist[:, :, n + 1]
+    dst = hist[1:d + 1, 1:d + 1, :n].reshape(-1)
+    dst = np.minimum(dst, math.sqrt((dst ** 2).sum()) * DESCR_MAG_THR)
+    return dst * (INT_DESCR_FCTR / max(math.sqrt((dst ** 2).sum()), 1.19e-7))
 
 
 def detect_and_compute(img_bgr: np.ndarray, max_features: int = 250000, root: bool = True, eps: float = 1e-8):

@@ -25,7 +25,7 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/gtx.h but not exported by libgtx.so"
     assert declared == set(_lib._SIGNATURES), declared ^ set(_lib._SIGNATURES)
-    assert lib.gtx_abi_version() == _lib.ABI_VERSION == 13
+    assert lib.gtx_abi_version() == _lib.ABI_VERSION == 14
 
 
 def test_errors_are_codes_with_messages_not_exceptions():
@@ -268,6 +268,90 @@ def test_gmc_hooks_refuse_bad_sizes_before_any_launch():
     bad[5] = np.inf
     assert ransac(pairs=bad) == -1 and b"finite" in lib.gtx_last_error()
     assert lib.gtx_gmc_counts(None, p(i)) == -1 and b"gmc is NULL" in lib.gtx_last_error()
+
+
+def test_sift_hooks_refuse_bad_sizes_before_any_launch():
+    """Host only: the SIFT operator hooks answer bad sizes, a Gaussian wider than the kernels' 16-pixel radius, and records that
+    would index outside their image with an error code, with no context given."""
+    from geotrax_amd import _lib, ops
+
+    lib = _lib.load()
+    f = np.zeros(5 * 32 * 32, np.float32)
+    i = np.zeros(4096, np.int32)
+    p = _lib.ptr
+    n = C.c_int()
+
+    def blur(h=32, w=32, sigma=1.6, form=0, src=f):
+        return lib.gtx_op_sift_blur(None, p(src), h, w, sigma, form, p(f), None)
+
+    assert blur() == -1 and b"ctx is NULL" in lib.gtx_last_error()                                      # the sizes were fine
+    assert blur(sigma=4.0) == -1 and b"ctx is NULL" in lib.gtx_last_error()                             # radius 16: the largest
+    assert blur(sigma=4.25) == -3 and b"radius 17 exceeds 16" in lib.gtx_last_error()                   # make_taps, not a launch
+    assert blur(sigma=0.0) == -1 and b"sigma" in lib.gtx_last_error()
+    assert blur(sigma=float("nan")) == -1 and b"sigma" in lib.gtx_last_error()
+    assert blur(form=3) == -1 and b"form" in lib.gtx_last_error()
+    assert blur(h=0) == -1 and b"sift_blur" in lib.gtx_last_error()
+    assert blur(w=4097) == -1 and b"sift_blur" in lib.gtx_last_error()
+    assert blur(src=None) == -1 and b"src is NULL" in lib.gtx_last_error()
+
+    def extrema(h=32, w=32, octave=0, cap=16, dog=f):
+        return lib.gtx_op_sift_extrema(None, p(dog), h, w, octave, cap, C.byref(n), p(i))
+
+    assert extrema() == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert extrema(h=10, w=30) == -1 and b"ctx is NULL" in lib.gtx_last_error()                         # no interior is a case, not an error
+    assert extrema(cap=0) == -1 and b"cap" in lib.gtx_last_error()
+    assert extrema(octave=16) == -1 and b"octave" in lib.gtx_last_error()
+    assert extrema(dog=None) == -1 and b"dog5 is NULL" in lib.gtx_last_error()
+
+    def refine(cand=(0, 1, 5, 5), n_cand=1, octave=0, h=32, w=32):
+        c = np.array(cand, np.int32)
+        return lib.gtx_op_sift_refine(None, p(f), h, w, octave, p(c), n_cand, C.byref(n), p(i))
+
+    assert refine() == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert refine(n_cand=0) == -1 and b"ctx is NULL" in lib.gtx_last_error()                            # no candidate is a case
+    assert refine(cand=(0, 3, 26, 26)) == -1 and b"ctx is NULL" in lib.gtx_last_error()                 # the last interior pixel and layer
+    assert refine(cand=(0, 0, 5, 5)) == -1 and b"border" in lib.gtx_last_error()                        # layer 0 has no layer below
+    assert refine(cand=(0, 4, 5, 5)) == -1 and b"border" in lib.gtx_last_error()
+    assert refine(cand=(0, 1, 4, 5)) == -1 and b"border" in lib.gtx_last_error()
+    assert refine(cand=(0, 1, 5, 27)) == -1 and b"border" in lib.gtx_last_error()
+    assert refine(cand=(1, 1, 5, 5)) == -1 and b"another octave" in lib.gtx_last_error()
+    assert refine(h=10) == -1 and b"border" in lib.gtx_last_error()                                     # an image without interior has no candidate
+    assert refine(n_cand=-1) == -1 and b"sift_refine" in lib.gtx_last_error()
+
+    def orient(octave=0, cap=36, **fields):
+        r = np.zeros(1, ops.SIFT_REFINED)
+        r["size"], r["layer"], r["r"], r["c"] = 4.0, 1, 5, 5
+        for k, v in fields.items():
+            r[k] = v
+        return lib.gtx_op_sift_orient(None, p(f), 32, 32, octave, p(r), 1, cap, C.byref(n), p(i), p(f))
+
+    assert orient() == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert orient(r=32) == -1 and b"outside the image" in lib.gtx_last_error()
+    assert orient(c=-1) == -1 and b"outside the image" in lib.gtx_last_error()
+    assert orient(layer=6) == -1 and b"outside the image" in lib.gtx_last_error()
+    assert orient(o=1) == -1 and b"another octave" in lib.gtx_last_error()
+    assert orient(size=0.0) == -1 and b"size" in lib.gtx_last_error()
+    assert orient(size=float("nan")) == -1 and b"size" in lib.gtx_last_error()
+    assert orient(size=1000.0) == -1 and b"radius" in lib.gtx_last_error()                              # a 2251-pixel radius
+    assert orient(size=1000.0, octave=1, o=1) == -1 and b"ctx is NULL" in lib.gtx_last_error()          # half that in octave 1
+    assert orient(cap=0) == -1 and b"cap" in lib.gtx_last_error()
+
+    def describe(root=0, **fields):
+        k = np.zeros(1, ops.SIFT_FINAL)
+        k["px"], k["py"], k["scl"], k["ori"] = 5.0, 5.0, 2.0, 45.0
+        for name, v in fields.items():
+            k[name] = v
+        return lib.gtx_op_sift_describe(None, p(f), 32, 32, p(k), 1, root, 1e-8, p(f))
+
+    assert describe() == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert describe(px=-3.0, py=40.0, scl=1e6, ori=360.0) == -1 and b"ctx is NULL" in lib.gtx_last_error()   # the kernel clips the window itself
+    assert describe(o=1) == -1 and b"octave 0" in lib.gtx_last_error()
+    assert describe(layer=6) == -1 and b"octave 0" in lib.gtx_last_error()
+    assert describe(ori=360.5) == -1 and b"ori" in lib.gtx_last_error()
+    assert describe(ori=float("nan")) == -1 and b"ori" in lib.gtx_last_error()
+    assert describe(px=float("inf")) == -1 and b"position" in lib.gtx_last_error()
+    assert describe(scl=0.0) == -1 and b"scl" in lib.gtx_last_error()
+    assert describe(root=2) == -1 and b"root" in lib.gtx_last_error()
 
 
 def test_no_gpu_means_loud_failure_not_fallback():

@@ -119,7 +119,7 @@ def test_embedder_abi_symbols():
     lib = _lib.load()
     for s in EMBEDDER_SYMBOLS:
         assert hasattr(lib, s), s
-    assert lib.gtx_abi_version() == 13
+    assert lib.gtx_abi_version() == 14
 
 
 def test_reference_crop_geometry_hand_cases():
