@@ -16,7 +16,9 @@
 #include <cmath>
 #include <mutex>
 
+#include "net_runtime.hpp"   // gtx_ctx
 #include "ecc.hpp"
+#include "op_staging.hpp"
 
 namespace gtx {
 
@@ -266,6 +268,61 @@ __global__ __launch_bounds__(kThreads) void ecc_update_kernel(EccState* __restri
 }
 
 }  // namespace
+
+// ---- the kernels on host arrays (gtx_op_ecc_*; tests/test_ecc_ops_gpu.py). Sizes and pointers are checked by the callers in
+// gtx_ops.cpp before anything here touches the GPU. Each launch is shaped as submit_frame_dev / collect shape it.
+void op_ecc_prepare(gtx_ctx* ctx, const uint8_t* frame_bgr, int H, int W, float* out) {
+  GTX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int h2 = H / 2, w2 = W / 2;
+  DevBuf df, dout;
+  upload(df, frame_bgr, (size_t)H * W * 3);
+  fill_ff(dout, (size_t)h2 * w2 * 4);
+  hipLaunchKernelGGL(ecc_prepare_kernel, dim3(cdiv(w2, 64), cdiv(h2, 4)), dim3(256), 0, s, df.as<uint8_t>(), H, W, dout.as<float>(), h2, w2);
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipStreamSynchronize(s));
+  download(out, dout, (size_t)h2 * w2 * 4);
+}
+
+void op_ecc_iterate(gtx_ctx* ctx, const float* tmpl, const float* img, int h, int w, bool exact, double eps, int max_iters, EccOpState* io, float* gx,
+                    float* gy, double* partial_stats, double* partial_accum) {
+  GTX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const size_t px = (size_t)h * w, pbytes = (size_t)kBlocks * kSums * 8;
+  DevBuf dt, di, dgx, dgy, part, state;
+  upload(dt, tmpl, px * 4);
+  upload(di, img, px * 4);
+  fill_ff(dgx, px * 4);
+  fill_ff(dgy, px * 4);
+  fill_ff(part, pbytes);
+  EccState init{};
+  for (int k = 0; k < 6; ++k) init.map[k] = io->map[k];
+  init.iter = io->iter; init.status = io->status; init.done = io->done; init.max_iters = max_iters;
+  init.exact = exact ? 1 : 0; init.eps = eps; init.rho = io->rho; init.last_rho = io->last_rho;
+  upload(state, &init, sizeof init);
+  EccState* st = state.as<EccState>();
+  hipLaunchKernelGGL(ecc_gradient_kernel, dim3(cdiv(w, 64), cdiv(h, 4)), dim3(256), 0, s, di.as<float>(), h, w, dgx.as<float>(), dgy.as<float>());
+  hipLaunchKernelGGL(ecc_stats_kernel, dim3(kBlocks), dim3(kThreads), 0, s, st, di.as<float>(), dt.as<float>(), h, w, part.as<double>());
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipStreamSynchronize(s));
+  download(partial_stats, part, pbytes);
+  hipLaunchKernelGGL(ecc_stats_finish_kernel, dim3(1), dim3(kThreads), 0, s, st, part.as<double>());
+  hipLaunchKernelGGL(ecc_accum_kernel, dim3(kBlocks), dim3(kThreads), 0, s, st, di.as<float>(), dgx.as<float>(), dgy.as<float>(), dt.as<float>(), h, w, part.as<double>());
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipStreamSynchronize(s));
+  download(partial_accum, part, pbytes);
+  hipLaunchKernelGGL(ecc_update_kernel, dim3(1), dim3(kThreads), 0, s, st, part.as<double>());
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipStreamSynchronize(s));
+  EccState fin;
+  download(&fin, state, sizeof fin);
+  download(gx, dgx, px * 4);
+  download(gy, dgy, px * 4);
+  for (int k = 0; k < 6; ++k) io->map[k] = fin.map[k];
+  io->iter = fin.iter; io->status = fin.status; io->done = fin.done;
+  io->rho = fin.rho; io->last_rho = fin.last_rho; io->n = fin.n; io->img_norm = fin.img_norm; io->tmp_norm = fin.tmp_norm;
+  io->img_mean = fin.img_mean; io->tmp_mean = fin.tmp_mean;
+}
 
 struct Ecc::Impl {
   int device;

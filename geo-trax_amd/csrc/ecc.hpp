@@ -7,6 +7,8 @@
 
 #include "common.hpp"
 
+struct gtx_ctx;
+
 namespace gtx {
 
 class Ecc {
@@ -36,5 +38,21 @@ class Ecc {
   struct Impl;
   std::unique_ptr<Impl> impl_;
 };
+
+// ---- gtx_op_ecc_*: the kernels on host arrays (arguments checked by the caller, gtx_ops.cpp)
+// the prepare kernel on a BGR u8 frame [H][W][3] -> out [H / 2][W / 2] f32, launched as submit_frame_dev launches it
+void op_ecc_prepare(gtx_ctx* ctx, const uint8_t* frame_bgr, int H, int W, float* out);
+// The fields of the device state a caller sets (map, iter, status, done, rho, last_rho) and reads back (all of them).
+struct EccOpState {
+  float map[6];
+  int iter, status, done;
+  double rho, last_rho, n, img_norm, tmp_norm;
+  float img_mean, tmp_mean;
+};
+// The gradient kernel on img, then ONE round of stats, stats-finish, accum and update on (tmpl, img) [h][w] f32 from the state
+// given, grids and blocks as collect() launches them. partial_stats / partial_accum [512][13] f64: the partial-sum buffer as it
+// stands after the stats kernel (5 columns written) and after the accum kernel; every byte of it is 0xFF before the stats launch.
+void op_ecc_iterate(gtx_ctx* ctx, const float* tmpl, const float* img, int h, int w, bool exact, double eps, int max_iters, EccOpState* st, float* gx,
+                    float* gy, double* partial_stats, double* partial_accum);
 
 }  // namespace gtx

@@ -2,7 +2,7 @@
 // The float64 tests drive them, and the package calls a few itself (the registration matcher, the georeference chain, CLAHE).
 // A hook checks every size, and every index a kernel would turn into an address, before it touches the GPU; then it stages its
 // arrays with op_staging.hpp, launches as the product launches, and copies the results back. The hooks of file-local kernels
-// (op_gmc_* in gmc.hip, op_orb_* in stabilizer.hip, op_sift_* in sift.hip) keep their staging beside the kernels and have only their checks here.
+// (op_gmc_* in gmc.hip, op_ecc_* in ecc.hip, op_orb_* in stabilizer.hip, op_sift_* in sift.hip) keep their staging beside the kernels and have only their checks here.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -15,6 +15,7 @@
 #include "conv_igemm.hpp"
 #include "det_kernels.hpp"
 #include "detector.hpp"
+#include "ecc.hpp"
 #include "geometry.hpp"
 #include "gmc.hpp"
 #include "match_l2.hpp"
@@ -826,6 +827,43 @@ int gtx_op_gmc_ransac(gtx_ctx* ctx, const float* pairs, int n, uint32_t seed, in
       if (!std::isfinite(pairs[i])) op_bad(op, "a coordinate that is not a finite number");
     need(best_count, "best_count"); need(winner, "winner"); need(model, "model"); need(count, "count"); need(ctx, "ctx");
     gtx::op_gmc_ransac(ctx, pairs, n, seed, best_count, winner, model, count);
+  });
+}
+
+// ---- GMC method ecc: the prepare kernel, and the gradient kernel with one round of the fit's four launches (tests/test_ecc_ops_gpu.py).
+// Sizes, the map and the state a kernel branches on are checked before anything touches the GPU.
+int gtx_op_ecc_prepare(gtx_ctx* ctx, const uint8_t* frame_bgr, int H, int W, float* out) {
+  return guarded([&] {
+    const char* op = "ecc_prepare";
+    if (H < 8 || W < 8 || H > 16384 || W > 16384) op_bad(op, "a frame of 8..16384 pixels a side");
+    need(frame_bgr, "frame_bgr"); need(out, "out"); need(ctx, "ctx");
+    gtx::op_ecc_prepare(ctx, frame_bgr, H, W, out);
+  });
+}
+
+int gtx_op_ecc_iterate(gtx_ctx* ctx, const float* tmpl, const float* img, int h, int w, const float map[6], int exact, double rho_in,
+                       double last_rho_in, double eps, int iter_in, int max_iters, int status_in, int done_in, float* gx, float* gy,
+                       double* partial_stats, double* partial_accum, float map_out[6], int state_i[3], double state_d[5], float means[2]) {
+  return guarded([&] {
+    const char* op = "ecc_iterate";
+    if (h < 2 || w < 2 || h > 8192 || w > 8192) op_bad(op, "images of 2..8192 pixels a side (REFLECT_101 needs two)");
+    need(map, "map");
+    for (int k = 0; k < 6; ++k)
+      if (!(std::fabs(map[k]) <= 1e6f)) op_bad(op, "a map entry that is not a number, or beyond 1e6");
+    if (exact != 0 && exact != 1) op_bad(op, "exact is 0 or 1");
+    if (!(eps > 0.0)) op_bad(op, "eps > 0");
+    if (max_iters < 1 || iter_in < 0 || iter_in >= max_iters) op_bad(op, "0 <= iter_in < max_iters");
+    if (status_in < 0 || status_in > 2 || (done_in != 0 && done_in != 1)) op_bad(op, "status_in 0..2, done_in 0 or 1");
+    need(tmpl, "tmpl"); need(img, "img"); need(gx, "gx"); need(gy, "gy"); need(partial_stats, "partial_stats"); need(partial_accum, "partial_accum");
+    need(map_out, "map_out"); need(state_i, "state_i"); need(state_d, "state_d"); need(means, "means"); need(ctx, "ctx");
+    gtx::EccOpState st{};
+    for (int k = 0; k < 6; ++k) st.map[k] = map[k];
+    st.iter = iter_in; st.status = status_in; st.done = done_in; st.rho = rho_in; st.last_rho = last_rho_in;
+    gtx::op_ecc_iterate(ctx, tmpl, img, h, w, exact != 0, eps, max_iters, &st, gx, gy, partial_stats, partial_accum);
+    for (int k = 0; k < 6; ++k) map_out[k] = st.map[k];
+    state_i[0] = st.iter; state_i[1] = st.status; state_i[2] = st.done;
+    state_d[0] = st.rho; state_d[1] = st.last_rho; state_d[2] = st.n; state_d[3] = st.img_norm; state_d[4] = st.tmp_norm;
+    means[0] = st.img_mean; means[1] = st.tmp_mean;
   });
 }
 

@@ -162,6 +162,9 @@ _SIGNATURES = {
     "gtx_ecc_submit_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
     "gtx_ecc_collect": (C.c_int, [_P, _P, _P, C.POINTER(C.c_double)]),
     "gtx_ecc_image": (C.c_int, [_P, C.c_int, _P]),
+    "gtx_op_ecc_prepare": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "gtx_op_ecc_iterate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     _P, _P, _P, _P, _P, _P, _P, _P]),
     "gtx_register_images": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.POINTER(C.c_int), _P, _P]),
     "gtx_sift_create": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
     "gtx_sift_destroy": (None, [_P]),

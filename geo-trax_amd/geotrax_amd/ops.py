@@ -544,6 +544,38 @@ def gmc_ransac(pairs, seed: int = 0, *, ctx=None):
     return dict(best_count=best.value, winner=win.value, model=model, count=count)
 
 
+# ---- GMC method ecc (csrc/ecc.hip): the prepare kernel, and the gradient kernel with one round of the fit's four launches
+def ecc_prepare(frame_bgr, *, ctx=None):
+    """cvtColor -> GaussianBlur(3x3, 1.5) -> resize(1/2) of a BGR u8 frame [H, W, 3] (H, W >= 8) -> [H // 2, W // 2] f32."""
+    ctx = ctx or _lib.default_context()
+    f = np.ascontiguousarray(frame_bgr, dtype=np.uint8)
+    assert f.ndim == 3 and f.shape[2] == 3
+    out = np.full((f.shape[0] // 2, f.shape[1] // 2), np.nan, np.float32)
+    check(ctx.lib.gtx_op_ecc_prepare(ctx.handle, ptr(f), f.shape[0], f.shape[1], ptr(out)))
+    return out
+
+
+def ecc_iterate(tmpl, img, M, *, exact: bool = True, rho: float = -1.0, last_rho: float | None = None, eps: float = 1e-6, iter_in: int = 0,
+                max_iters: int = 5000, status_in: int = 0, done_in: int = 0, ctx=None):
+    """The gradient kernel on img, then exactly one round of stats, stats-finish, accum and update on template and image [h, w] f32
+    from the state given (M [2, 3] f32; the defaults are the state a fit starts from). -> dict(gx, gy [h, w] f32; partial_stats,
+    partial_accum [512, 13] f64: the partial-sum buffer after the stats kernel (columns 0..4 written, the rest still the 0xFF fill:
+    NaN) and after the accum kernel; map [2, 3] f32, iter, status, done, rho, last_rho, n, img_norm, tmp_norm, img_mean, tmp_mean)."""
+    ctx = ctx or _lib.default_context()
+    t, i = np.ascontiguousarray(tmpl, dtype=np.float32), np.ascontiguousarray(img, dtype=np.float32)
+    assert t.ndim == 2 and t.shape == i.shape
+    m = np.ascontiguousarray(M, dtype=np.float32).reshape(6)
+    h, w = t.shape
+    gx, gy = np.full((h, w), np.nan, np.float32), np.full((h, w), np.nan, np.float32)
+    ps, pa = np.zeros((512, 13), np.float64), np.zeros((512, 13), np.float64)
+    mo, si, sd, me = np.full(6, np.nan, np.float32), np.full(3, -9, np.int32), np.full(5, np.nan, np.float64), np.full(2, np.nan, np.float32)
+    check(ctx.lib.gtx_op_ecc_iterate(ctx.handle, ptr(t), ptr(i), h, w, ptr(m), int(bool(exact)), float(rho), float(-eps if last_rho is None else last_rho),
+                                     float(eps), int(iter_in), int(max_iters), int(status_in), int(done_in), ptr(gx), ptr(gy), ptr(ps), ptr(pa), ptr(mo),
+                                     ptr(si), ptr(sd), ptr(me)))
+    return dict(gx=gx, gy=gy, partial_stats=ps, partial_accum=pa, map=mo.reshape(2, 3), iter=int(si[0]), status=int(si[1]), done=int(si[2]),
+                rho=float(sd[0]), last_rho=float(sd[1]), n=float(sd[2]), img_norm=float(sd[3]), tmp_norm=float(sd[4]), img_mean=me[0], tmp_mean=me[1])
+
+
 # ---- the SIFT kernels one stage at a time (csrc/sift.hip; record layouts: include/gtx.h)
 _KEY = [("key_o", "<i4"), ("key_layer", "<i4"), ("key_r", "<i4"), ("key_c", "<i4")]
 SIFT_REFINED = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("response", "<f4"), ("word", "<i4"), ("o", "<i4"), ("layer", "<i4"),

@@ -826,6 +826,21 @@ int gtx_ecc_submit_dev(gtx_ecc* e, gtx_ctx* producer, const void* frame_bgr_dptr
 int gtx_ecc_collect(gtx_ecc* e, double A[6], int info[2], double* rho);
 /* Parity hook: which 0 = the prepared image of the frame collected last, 1 = the template; out [h / 2][w / 2] float32 */
 int gtx_ecc_image(gtx_ecc* e, int which, float* out);
+/* The method's kernels on host arrays, each launch shaped as gtx_ecc_submit / _collect shape it; sizes and pointers are checked
+ * before the GPU is touched.
+ * _prepare: the prepare kernel on a BGR u8 frame [H][W][3], H, W >= 8 (as gtx_ecc_create) -> out [H / 2][W / 2] f32.
+ * _iterate: the gradient kernel on img, then exactly ONE round of stats, stats-finish, accum and update on template and image
+ * [h][w] f32 (2..8192 a side), starting from the state given: map [6] (row-major 2x3, finite, entries within 1e6), exact (0 / 1),
+ * rho_in, last_rho_in, eps > 0, 0 <= iter_in < max_iters, status_in (0..2) and done_in (0 / 1; 1: every kernel of the round
+ * returns at once). Out: gx, gy [h][w] f32; partial_stats, partial_accum [512][13] f64 -- the partial-sum buffer as it stands after
+ * the stats kernel (columns 0..4 of each block's row: count, sum and sum of squares of the sample, the same of the template; the
+ * other columns still hold the 0xFF bytes the whole buffer is filled with before that launch) and after the accum kernel (Hessian 6,
+ * image projection 3, template projection 3, correlation); map_out [6]; state_i = {iter, status, done}; state_d = {rho, last_rho,
+ * n, img_norm, tmp_norm}; means = {img_mean, tmp_mean}, the float32 values the masked subtraction uses. */
+int gtx_op_ecc_prepare(gtx_ctx* ctx, const uint8_t* frame_bgr, int H, int W, float* out);
+int gtx_op_ecc_iterate(gtx_ctx* ctx, const float* tmpl, const float* img, int h, int w, const float map[6], int exact, double rho_in,
+                       double last_rho_in, double eps, int iter_in, int max_iters, int status_in, int done_in, float* gx, float* gy,
+                       double* partial_stats, double* partial_accum, float map_out[6], int state_i[3], double state_d[5], float means[2]);
 
 /* ------------------------------------------------------------------ registration (once per video)
  * Replaces estimate_homography() of geotrax/utils/registration.py:21-95 -- stabilo.Stabilizer with

@@ -180,70 +180,134 @@ def _inv3(hm: np.ndarray):
     return t.astype(np.float32)
 
 
+SUM_NAMES = ("j0j0", "j0j1", "j0j2", "j1j1", "j1j2", "j2j2", "j0i", "j1i", "j2i", "j0t", "j1t", "j2t", "ti")   # csrc/ecc.hip's 13 sums, in its order
+
+
+def iteration(tmpl_f32: np.ndarray, img_f32: np.ndarray, M: np.ndarray, rho: float, last_rho: float, warp: str = "exact", grads=None, trace: bool = True):
+    """Everything one iteration of the loop sums, from the map M (2x3 float32) as it stands: the warp, the mask, the masked means and
+    norms, the Jacobian and the 13 sums (SUM_NAMES). rho and last_rho are only carried into the state update_from_sums takes.
+    Returns a dict: n (mask count), img_mean / tmp_mean (the float32 values the subtraction uses), img_norm / tmp_norm, sums13
+    (float64 [13]), state (for update_from_sums) and, with trace, stats_terms [5] and terms [13]: the per-pixel float64 arrays
+    (count, a, a a, t, t t under the mask; the 13 products) whose sums these are, for a caller that wants to sum them otherwise.
+    grads: gradients(img_f32), when the caller has them."""
+    tmpl, img = tmpl_f32, img_f32
+    hs, ws = tmpl.shape
+    gx, gy = gradients(img) if grads is None else grads
+    X = np.broadcast_to(np.arange(ws, dtype=np.float32)[None, :], (hs, ws))
+    Y = np.broadcast_to(np.arange(hs, dtype=np.float32)[:, None], (hs, ws))
+    ones = np.ones(img.shape, np.float32)
+    lin, (nx, ny) = warp_coords(M, hs, ws)
+    if warp == "exact":
+        ex = warp_coords_exact(M, hs, ws)
+        iw, gxw, gyw = warp_linear_exact(img, ex), warp_linear_exact(gx, ex), warp_linear_exact(gy, ex)
+    else:
+        iw, gxw, gyw = warp_linear(img, lin), warp_linear(gx, lin), warp_linear(gy, lin)
+    mask = _fetch(ones, ny, nx) > 0
+    n = int(mask.sum())
+    out = {}
+    if trace:
+        a, t = np.where(mask, iw, np.float32(0.0)).astype(np.float64), np.where(mask, tmpl, np.float32(0.0)).astype(np.float64)
+        out["stats_terms"] = [mask.astype(np.float64), a, a * a, t, t * t]
+    img_mean, img_std = _masked_mean_std(iw, mask, n) if n else (0.0, 0.0)
+    tmp_mean, tmp_std = _masked_mean_std(tmpl, mask, n) if n else (0.0, 0.0)
+    iw = np.where(mask, iw - np.float32(img_mean), iw).astype(np.float32)
+    tz = np.where(mask, tmpl - np.float32(tmp_mean), np.float32(0.0)).astype(np.float32)
+    tmp_norm = np.sqrt(n * tmp_std * tmp_std)
+    img_norm = np.sqrt(n * img_std * img_std)
+    h0, h1 = M[0, 0], M[1, 0]                                         # cos(theta), sin(theta), float32
+    hat_x = -(X * h1) - (Y * h0)
+    hat_y = (X * h0) - (Y * h1)
+    J = [(gxw * hat_x) + (gyw * hat_y), gxw, gyw]                     # float32
+    Jd = [j.astype(np.float64) for j in J]
+    iwd, tzd = iw.astype(np.float64), tz.astype(np.float64)
+    pairs = [(Jd[0], Jd[0]), (Jd[0], Jd[1]), (Jd[0], Jd[2]), (Jd[1], Jd[1]), (Jd[1], Jd[2]), (Jd[2], Jd[2]), (Jd[0], iwd), (Jd[1], iwd), (Jd[2], iwd),
+             (Jd[0], tzd), (Jd[1], tzd), (Jd[2], tzd), (tzd, iwd)]
+    sums, terms = np.empty(13), []
+    for k, (p, q) in enumerate(pairs):
+        pq = p * q
+        sums[k] = np.sum(pq)
+        if trace:
+            terms.append(pq)
+    if trace:
+        out["terms"] = terms
+    out.update(n=n, img_mean=np.float32(img_mean), tmp_mean=np.float32(tmp_mean), img_norm=float(img_norm), tmp_norm=float(tmp_norm), sums13=sums,
+               state=dict(M=M.copy(), rho=rho, last_rho=last_rho, img_norm=float(img_norm), tmp_norm=float(tmp_norm)))
+    return out
+
+
+def update_from_sums(sums13, state: dict) -> dict:
+    """csrc/ecc.hip's ecc_update_kernel, operation by operation, on the 13 totals: the float32 Hessian and projections, the cofactor
+    inverse, rho, lambda, the parameter step and the new map, status and done. state: M (2x3 float32), rho, last_rho, img_norm,
+    tmp_norm, and optionally iter (0), max_iters (MAX_ITERS), eps (EPS), status (0), done (0). Returns a new state (M a new array) that
+    also carries what the step went through: det (the Hessian's determinant in float64), lam, dp (None where the step was not taken)."""
+    st = dict(iter=0, max_iters=MAX_ITERS, eps=EPS, status=0, done=0)
+    st.update(state)
+    st["M"] = np.array(st["M"], np.float32)
+    st.update(det=None, lam=None, dp=None)
+    if st["done"]:
+        return st
+    s = np.asarray(sums13, np.float64)
+    f64 = lambda v: np.asarray(v, np.float64)
+    st["iter"] += 1
+    hs = s[:6].astype(np.float32)
+    hess = np.array([[hs[0], hs[1], hs[2]], [hs[1], hs[3], hs[4]], [hs[2], hs[4], hs[5]]], np.float32)
+    a = hess.astype(np.float64)
+    st["det"] = float(a[0, 0] * (a[1, 1] * a[2, 2] - a[1, 2] * a[2, 1]) - a[0, 1] * (a[1, 0] * a[2, 2] - a[1, 2] * a[2, 0])
+                      + a[0, 2] * (a[1, 0] * a[2, 1] - a[1, 1] * a[2, 0]))
+    hinv = _inv3(hess)
+    if hinv is None:                                                  # a singular Hessian inverts to zeros in OpenCV: no update, rho repeats
+        hinv = np.zeros((3, 3), np.float32)
+    hinv = f64(hinv)
+    correlation = float(s[12])
+    img_norm, tmp_norm = float(st["img_norm"]), float(st["tmp_norm"])
+    st["last_rho"] = st["rho"]
+    den = img_norm * tmp_norm
+    with np.errstate(all="ignore"):
+        rho = correlation / den if den != 0 else float("nan")
+    st["rho"] = rho
+    if np.isnan(rho):
+        st.update(status=1, done=1)
+        return st
+    img_proj, tmp_proj = f64(s[6:9].astype(np.float32)), f64(s[9:12].astype(np.float32))
+    mv = lambda m, v: np.array([(m[i, 0] * v[0] + m[i, 1] * v[1]) + m[i, 2] * v[2] for i in range(3)]).astype(np.float32)
+    dot = lambda u, v: float((u[0] * v[0] + u[1] * v[1]) + u[2] * v[2])
+    iph = f64(mv(hinv, img_proj))
+    lambda_n = img_norm * img_norm - dot(img_proj, iph)
+    lambda_d = correlation - dot(tmp_proj, iph)
+    if lambda_d <= 0.0:
+        st.update(rho=-1.0, status=2, done=1)
+        return st
+    lam = lambda_n / lambda_d
+    # error = lambda * templateZM - imageWarped projected onto the Jacobian; the projection is linear in its argument. The
+    # float32 image `error` upstream forms first costs one rounding per pixel, which the float64 sums of 10^5+ terms absorb.
+    err_proj = f64((lam * tmp_proj - img_proj).astype(np.float32))
+    dp = mv(hinv, err_proj)
+    M = st["M"]
+    theta = np.arcsin(np.float64(M[1, 0])) + np.float64(dp[0])
+    M[0, 2] = np.float32(np.float64(M[0, 2]) + np.float64(dp[1]))
+    M[1, 2] = np.float32(np.float64(M[1, 2]) + np.float64(dp[2]))
+    M[0, 0] = M[1, 1] = np.float32(np.cos(theta))
+    M[1, 0] = np.float32(np.sin(theta))
+    M[0, 1] = -M[1, 0]
+    st.update(lam=lam, dp=dp)
+    if st["iter"] >= st["max_iters"] or abs(st["rho"] - st["last_rho"]) < st["eps"]:
+        st["done"] = 1
+    return st
+
+
 def find_transform_ecc(template_u8: np.ndarray, image_u8: np.ndarray, M: np.ndarray, max_iters: int = MAX_ITERS, eps: float = EPS, warp: str = "exact"):
     """cv2.findTransformECC(template, image, M, MOTION_EUCLIDEAN, (EPS | COUNT, max_iters, eps), None, 1). M (2x3 float32) is
     updated in place. Returns (rho, iterations run, status): status 0 = finished, 1 = NaN correlation, 2 = the correlation
     would be minimised (both are cv2.error upstream)."""
     tmpl = template_u8.astype(np.float32)
     img = image_u8.astype(np.float32)
-    hs, ws = tmpl.shape
-    gx, gy = gradients(img)
-    X = np.broadcast_to(np.arange(ws, dtype=np.float32)[None, :], (hs, ws))
-    Y = np.broadcast_to(np.arange(hs, dtype=np.float32)[:, None], (hs, ws))
-    ones = np.ones(img.shape, np.float32)
-    rho, last_rho = -1.0, -eps
-    it = 0
-    while it < max_iters and abs(rho - last_rho) >= eps:
-        it += 1
-        lin, (nx, ny) = warp_coords(M, hs, ws)
-        if warp == "exact":
-            ex = warp_coords_exact(M, hs, ws)
-            iw, gxw, gyw = warp_linear_exact(img, ex), warp_linear_exact(gx, ex), warp_linear_exact(gy, ex)
-        else:
-            iw, gxw, gyw = warp_linear(img, lin), warp_linear(gx, lin), warp_linear(gy, lin)
-        mask = _fetch(ones, ny, nx) > 0
-        n = int(mask.sum())
-        img_mean, img_std = _masked_mean_std(iw, mask, n) if n else (0.0, 0.0)
-        tmp_mean, tmp_std = _masked_mean_std(tmpl, mask, n) if n else (0.0, 0.0)
-        iw = np.where(mask, iw - np.float32(img_mean), iw).astype(np.float32)
-        tz = np.where(mask, tmpl - np.float32(tmp_mean), np.float32(0.0)).astype(np.float32)
-        tmp_norm = np.sqrt(n * tmp_std * tmp_std)
-        img_norm = np.sqrt(n * img_std * img_std)
-        h0, h1 = M[0, 0], M[1, 0]                                         # cos(theta), sin(theta), float32
-        hat_x = -(X * h1) - (Y * h0)
-        hat_y = (X * h0) - (Y * h1)
-        J = [(gxw * hat_x) + (gyw * hat_y), gxw, gyw]                     # float32
-        Jd = [j.astype(np.float64) for j in J]
-        hess = np.array([[np.sum(Jd[i] * Jd[j]) for j in range(3)] for i in range(3)]).astype(np.float32)
-        hinv = _inv3(hess)
-        iwd, tzd = iw.astype(np.float64), tz.astype(np.float64)
-        correlation = float(np.sum(tzd * iwd))
-        last_rho = rho
-        with np.errstate(all="ignore"):
-            rho = correlation / (img_norm * tmp_norm) if img_norm * tmp_norm != 0 else float("nan")
-        if np.isnan(rho):
-            return rho, it, 1
-        if hinv is None:                                                  # a singular Hessian inverts to zeros in OpenCV: no update, rho repeats
-            hinv = np.zeros((3, 3), np.float32)
-        img_proj = np.array([np.sum(Jd[i] * iwd) for i in range(3)]).astype(np.float32)
-        tmp_proj = np.array([np.sum(Jd[i] * tzd) for i in range(3)]).astype(np.float32)
-        iph = (hinv.astype(np.float64) @ img_proj.astype(np.float64)).astype(np.float32)
-        lambda_n = img_norm * img_norm - float(np.dot(img_proj.astype(np.float64), iph.astype(np.float64)))
-        lambda_d = correlation - float(np.dot(tmp_proj.astype(np.float64), iph.astype(np.float64)))
-        if lambda_d <= 0.0:
-            return -1.0, it, 2
-        lam = lambda_n / lambda_d
-        # error = lambda * templateZM - imageWarped projected onto the Jacobian; the projection is linear in its argument. The
-        # float32 image `error` upstream forms first costs one rounding per pixel, which the float64 sums of 10^5+ terms absorb.
-        err_proj = (lam * tmp_proj.astype(np.float64) - img_proj.astype(np.float64)).astype(np.float32)
-        dp = (hinv.astype(np.float64) @ err_proj.astype(np.float64)).astype(np.float32)
-        theta = np.arcsin(np.float64(M[1, 0])) + np.float64(dp[0])
-        M[0, 2] = np.float32(np.float64(M[0, 2]) + np.float64(dp[1]))
-        M[1, 2] = np.float32(np.float64(M[1, 2]) + np.float64(dp[2]))
-        M[0, 0] = M[1, 1] = np.float32(np.cos(theta))
-        M[1, 0] = np.float32(np.sin(theta))
-        M[0, 1] = -M[1, 0]
-    return rho, it, 0
+    grads = gradients(img)
+    st = dict(M=M, rho=-1.0, last_rho=-eps, iter=0, max_iters=max_iters, eps=eps, status=0, done=0 if max_iters > 0 else 1)
+    while not st["done"]:
+        it = iteration(tmpl, img, st["M"], st["rho"], st["last_rho"], warp, grads=grads, trace=False)
+        st = update_from_sums(it["sums13"], dict(st, img_norm=it["img_norm"], tmp_norm=it["tmp_norm"]))
+    M[...] = st["M"]
+    return st["rho"], st["iter"], st["status"]
 
 
 class EccRef:

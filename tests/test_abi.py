@@ -270,6 +270,57 @@ def test_gmc_hooks_refuse_bad_sizes_before_any_launch():
     assert lib.gtx_gmc_counts(None, p(i)) == -1 and b"gmc is NULL" in lib.gtx_last_error()
 
 
+def test_ecc_hooks_refuse_bad_sizes_before_any_launch():
+    """Host only: the two operator hooks of GMC method ecc answer bad sizes, a map or a state the kernels must not be started from and
+    missing arrays with an error code, with no context given."""
+    from geotrax_amd import _lib
+
+    lib = _lib.load()
+    fr = np.zeros((16, 16, 3), np.uint8)
+    f = np.zeros(512 * 13 * 2, np.float32)
+    d = np.zeros(512 * 13, np.float64)
+    i = np.zeros(8, np.int32)
+    p = _lib.ptr
+
+    def prepare(H=16, W=16, frame=fr, out=f):
+        return lib.gtx_op_ecc_prepare(None, p(frame), H, W, p(out))
+
+    assert prepare() == -1 and b"ctx is NULL" in lib.gtx_last_error()                                   # the sizes were fine
+    assert prepare(H=8, W=8) == -1 and b"ctx is NULL" in lib.gtx_last_error()                           # the object's own lower bound
+    assert prepare(H=7) == -1 and b"ecc_prepare" in lib.gtx_last_error()
+    assert prepare(W=7) == -1 and b"ecc_prepare" in lib.gtx_last_error()
+    assert prepare(W=16385) == -1 and b"ecc_prepare" in lib.gtx_last_error()
+    assert prepare(frame=None) == -1 and b"frame_bgr is NULL" in lib.gtx_last_error()
+    assert prepare(out=None) == -1 and b"out is NULL" in lib.gtx_last_error()
+
+    def iterate(h=8, w=8, m=(1, 0, 0, 0, 1, 0), exact=1, eps=1e-6, iter_in=0, max_iters=5, status_in=0, done_in=0, tmpl=f, img=f, ps=d, mo=f, none_map=False):
+        mm = np.array(m, np.float32)
+        return lib.gtx_op_ecc_iterate(None, p(tmpl), p(img), h, w, None if none_map else p(mm), exact, -1.0, -eps, eps, iter_in, max_iters, status_in, done_in,
+                                      p(f), p(f), p(ps), p(d), p(mo), p(i), p(d), p(f))
+
+    assert iterate() == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert iterate(h=2, w=2) == -1 and b"ctx is NULL" in lib.gtx_last_error()                           # the smallest REFLECT_101 can mirror
+    assert iterate(iter_in=4, done_in=1, status_in=2, exact=0) == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert iterate(h=1) == -1 and b"ecc_iterate" in lib.gtx_last_error()
+    assert iterate(w=8193) == -1 and b"ecc_iterate" in lib.gtx_last_error()
+    assert iterate(m=(1, 0, float("nan"), 0, 1, 0)) == -1 and b"map entry" in lib.gtx_last_error()
+    assert iterate(m=(1, 0, 0, 0, 1, float("inf"))) == -1 and b"map entry" in lib.gtx_last_error()
+    assert iterate(m=(1, 0, 2e6, 0, 1, 0)) == -1 and b"map entry" in lib.gtx_last_error()
+    assert iterate(none_map=True) == -1 and b"map is NULL" in lib.gtx_last_error()
+    assert iterate(exact=2) == -1 and b"exact" in lib.gtx_last_error()
+    assert iterate(eps=0.0) == -1 and b"eps" in lib.gtx_last_error()
+    assert iterate(eps=float("nan")) == -1 and b"eps" in lib.gtx_last_error()
+    assert iterate(iter_in=5) == -1 and b"iter_in" in lib.gtx_last_error()                              # the cap is already reached
+    assert iterate(iter_in=-1) == -1 and b"iter_in" in lib.gtx_last_error()
+    assert iterate(max_iters=0) == -1 and b"iter_in" in lib.gtx_last_error()
+    assert iterate(status_in=3) == -1 and b"status_in" in lib.gtx_last_error()
+    assert iterate(done_in=2) == -1 and b"status_in" in lib.gtx_last_error()
+    assert iterate(tmpl=None) == -1 and b"tmpl is NULL" in lib.gtx_last_error()
+    assert iterate(img=None) == -1 and b"img is NULL" in lib.gtx_last_error()
+    assert iterate(ps=None) == -1 and b"partial_stats is NULL" in lib.gtx_last_error()
+    assert iterate(mo=None) == -1 and b"map_out is NULL" in lib.gtx_last_error()
+
+
 def test_sift_hooks_refuse_bad_sizes_before_any_launch():
     """Host only: the SIFT operator hooks answer bad sizes, a Gaussian wider than the kernels' 16-pixel radius, and records that
     would index outside their image with an error code, with no context given."""

@@ -127,3 +127,46 @@ def test_error_conditions_keep_the_matrix_as_the_failed_call_left_it():
     ref.apply(a)
     H = ref.apply(255 - a)                                               # anti-correlated: lambda's denominator is not positive
     assert ref.last["status"] == 2 and np.isfinite(H).all()
+
+
+def _recorded_cases():
+    """Every fit of this file, both warp forms: (name, first frame, second frame, max_iters)."""
+    import sys
+    from pathlib import Path
+
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "geo-trax_amd"))
+    from geotrax_amd.synth import make_scene
+
+    h, w = 216, 384
+    big = _texture(h + 40, w + 40, seed=3)
+    for tx, ty, th in [(3.0, -1.5, 0.0), (-4.25, 2.0, 0.004), (0.0, 0.0, -0.01), (7.5, 5.0, 0.002)]:
+        yield f"motion_{tx}_{ty}_{th}", _view(big, h, w, 0, 0, 0), _view(big, h, w, tx, ty, th), 100
+    sc = make_scene(seed=3, h=270, w=480)
+    yield "scene_0_30", sc.render(0), sc.render(30), 150
+    flat = np.full((64, 96, 3), 100, np.uint8)
+    yield "flat", flat, flat, 5000
+    a = np.random.default_rng(5).integers(0, 256, (64, 96, 3), dtype=np.uint8)
+    yield "anticorrelated", a, 255 - a, 50
+
+
+def test_the_loop_over_iteration_and_update_from_sums_gives_what_the_single_loop_gave():
+    """find_transform_ecc is a loop over iteration() and update_from_sums() since the kernels are tested one by one
+    (tests/test_ecc_ops_gpu.py). tests/golden/ecc_oracle_fits.json holds what the undivided loop returned on every fit of this
+    file in both warp forms -- the map's six float32 and rho as hex strings, the iteration count and the status: all must be
+    reproduced exactly."""
+    import json
+    from pathlib import Path
+
+    want = json.loads((Path(__file__).resolve().parent / "golden" / "ecc_oracle_fits.json").read_text())
+    seen = 0
+    for name, f0, f1, cap in _recorded_cases():
+        for warp in ("exact", "fixed"):
+            e = ecc_ref.EccRef(max_iters=cap, warp=warp)
+            e.apply(f0)
+            H = e.apply(f1)
+            rec = want[f"{name}/{warp}"]
+            assert [float(v).hex() for v in H.ravel()] == rec["map"], (name, warp)
+            assert (e.last["iters"], e.last["status"]) == (rec["iters"], rec["status"]), (name, warp)
+            assert (float(e.last["rho"]).hex() if not np.isnan(e.last["rho"]) else "nan") == rec["rho"], (name, warp)
+            seen += 1
+    assert seen == len(want) == 14
