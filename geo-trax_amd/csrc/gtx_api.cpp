@@ -19,6 +19,7 @@
 #include "jpeg.hpp"
 #include "register.hpp"
 #include "sift.hpp"
+#include "sift_stab.hpp"
 #include "stabilizer.hpp"
 #include "tracker.hpp"
 
@@ -604,6 +605,45 @@ int gtx_stabilizer_keypoints(gtx_stabilizer* st, int which, int cap, int* n, flo
 }
 int gtx_stabilizer_matches(gtx_stabilizer* st, int cap, int* n, int* cur_idx, int* ref_idx, int* dist) {
   return guarded([&] { need(st, "st"); need(n, "n"); st->impl->matches(cap, n, cur_idx, ref_idx, dist); });
+}
+
+int gtx_sift_stab_create(gtx_ctx* ctx, const gtx_sift_stab_config* cfg, gtx_sift_stab** out) {
+  return guarded([&] {
+    need(ctx, "ctx"); need(cfg, "cfg"); need(out, "out");
+    std::unique_ptr<gtx_sift_stab> s(new gtx_sift_stab);
+    s->impl.reset(new gtx::SiftStab(ctx, *cfg));
+    *out = s.release();
+  });
+}
+void gtx_sift_stab_destroy(gtx_sift_stab* st) { delete st; }
+int gtx_sift_stab_set_ref_gray_dev(gtx_sift_stab* st, const void* gray_dptr, int gh, int gw, const float* boxes_xywh, int n) {
+  return guarded([&] { need(st, "st"); need(gray_dptr, "gray"); st->impl->set_ref_gray_dev(gray_dptr, gh, gw, boxes_xywh, n); });
+}
+int gtx_sift_stab_submit_gray_dev(gtx_sift_stab* st, const void* gray_dptr, int gh, int gw, const float* boxes_xywh, int n) {
+  return guarded([&] { need(st, "st"); need(gray_dptr, "gray"); st->impl->submit_gray_dev(gray_dptr, gh, gw, boxes_xywh, n); });
+}
+int gtx_sift_stab_collect(gtx_sift_stab* st, double H[9], int* valid, int stats[4]) {
+  return guarded([&] { need(st, "st"); need(H, "H"); need(valid, "valid"); st->impl->collect(H, valid, stats); });
+}
+int gtx_sift_stab_stabilize_gray_dev(gtx_sift_stab* st, const void* gray_dptr, int gh, int gw, const float* boxes_xywh, int n, double H[9],
+                                     int* valid, int stats[4]) {
+  return guarded([&] {
+    need(st, "st"); need(gray_dptr, "gray"); need(H, "H"); need(valid, "valid");
+    st->impl->submit_gray_dev(gray_dptr, gh, gw, boxes_xywh, n);
+    st->impl->collect(H, valid, stats);
+  });
+}
+int gtx_sift_stab_last_ms(gtx_sift_stab* st, float* ms) {
+  return guarded([&] { need(st, "st"); need(ms, "ms"); *ms = st->impl->last_ms(); });
+}
+int gtx_sift_stab_keypoints(gtx_sift_stab* st, int which, int cap, int* n, float* kp5, int* octave, float* desc) {
+  return guarded([&] { need(st, "st"); need(n, "n"); st->impl->keypoints(which, cap, n, kp5, octave, desc); });
+}
+int gtx_sift_stab_pairs(gtx_sift_stab* st, int cap, int* n, float* pts) {
+  return guarded([&] { need(st, "st"); need(n, "n"); st->impl->pairs(cap, n, pts); });
+}
+int gtx_sift_stab_counters(gtx_sift_stab* st, int out[4]) {
+  return guarded([&] { need(st, "st"); need(out, "out"); st->impl->counters(out); });
 }
 
 int gtx_stabilizer_last_ms(gtx_stabilizer* st, float* ms) {

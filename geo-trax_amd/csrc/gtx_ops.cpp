@@ -1001,6 +1001,36 @@ int gtx_op_sift_describe(gtx_ctx* ctx, const float* gauss_layer, int h, int w, c
   });
 }
 
+int gtx_op_sift_select(gtx_ctx* ctx, const void* oriented, int n, int max_features, const int* rects, int n_rects, int* count, void* finals,
+                       float* xy, float* kp5, int* octave) {
+  return guarded([&] {
+    const char* op = "sift_select";
+    if (n < 0 || n > (1 << 20)) op_bad(op, "0 <= n <= 2^20 records");
+    if (max_features < 1 || max_features > gtx::sift_select_max_features()) op_bad(op, "max_features in [1, 65536]");
+    if (n_rects < 0 || n_rects > gtx::sift_select_max_rects()) op_bad(op, "0 <= n_rects <= 1024 rectangles");
+    need(count, "count");
+    if (n > 0) need(oriented, "oriented");
+    if (n_rects > 0) need(rects, "rects");
+    std::vector<uint64_t> keys((size_t)n);
+    for (int i = 0; i < n; ++i) {
+      float f[5];
+      int k[8];
+      std::memcpy(f, static_cast<const char*>(oriented) + 52 * (size_t)i, sizeof f);
+      std::memcpy(k, static_cast<const char*>(oriented) + 52 * (size_t)i + 20, sizeof k);     // word, o, layer, key (o, layer, r, c), bin
+      if (!(std::isfinite(f[4]) && f[4] >= 0.f)) op_bad(op, "a response that is not finite, or negative");
+      if (k[1] < 0 || k[1] > 15 || k[3] < 0 || k[3] > 15) op_bad(op, "an octave outside 0..15");
+      if (k[4] < 0 || k[4] > 7) op_bad(op, "a key layer outside 0..7");
+      if (k[5] < 0 || k[5] >= (1 << 20) || k[6] < 0 || k[6] >= (1 << 20)) op_bad(op, "a key row or column outside [0, 2^20)");
+      if (k[7] < 0 || k[7] > 255) op_bad(op, "an orientation bin outside 0..255");
+      keys[(size_t)i] = ((uint64_t)k[3] << 56) | ((uint64_t)k[4] << 48) | ((uint64_t)k[5] << 28) | ((uint64_t)k[6] << 8) | (uint64_t)k[7];
+    }
+    std::sort(keys.begin(), keys.end());
+    if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) op_bad(op, "two records with one key (octave, layer, row, column, bin)");
+    need(ctx, "ctx");
+    gtx::op_sift_select(ctx, oriented, n, max_features, rects, n_rects, count, finals, xy, kp5, octave);
+  });
+}
+
 // ---- single routines on host arrays: the registration matcher, the detector's preprocess pass, the trackers' assignment solver,
 // the host-side affine fit, the georeference chain and CLAHE
 int gtx_op_match_2nn(gtx_ctx* ctx, const float* query, int nq, const float* train, int nt, int* idx1, int* idx2, float* d1,

@@ -161,7 +161,51 @@ __global__ void to_half_kernel(const float* __restrict__ src, _Float16* __restri
   if (i < n) dst[i] = (_Float16)src[i];
 }
 
+// Lowe's ratio test and the matched point pairs, in query order: one workgroup walks the queries 1024 at a time, a block-wide prefix
+// sum of the pass flags gives every passing query its row. No atomics: the list is the one a host loop over the queries builds.
+__global__ __launch_bounds__(1024) void ratio_pairs_kernel(const int* __restrict__ idx1, const int* __restrict__ idx2, const float* __restrict__ d1,
+                                                           const float* __restrict__ d2, const int* __restrict__ nq_dev, int cap, int nt, float ratio,
+                                                           const float2* __restrict__ xy_q, const float2* __restrict__ xy_t, float4* __restrict__ pts,
+                                                           int* __restrict__ n_pairs) {
+  __shared__ int s_wave[16];
+  __shared__ int s_total;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nq = min(max(*nq_dev, 0), cap);          // rows past the count hold anything and are not read
+  int base = 0;
+  for (int q0 = 0; q0 < nq; q0 += 1024) {
+    const int i = q0 + tid;
+    bool pass = false;
+    int j = -1;
+    if (i < nq) {
+      j = idx1[i];
+      pass = j >= 0 && j < nt && idx2[i] >= 0 && d1[i] < ratio * d2[i];
+    }
+    const unsigned long long m = __ballot(pass);
+    if (lane == 0) s_wave[wave] = __popcll(m);
+    __syncthreads();
+    if (tid == 0) {
+      int acc = 0;
+      for (int k = 0; k < 16; ++k) { const int c = s_wave[k]; s_wave[k] = acc; acc += c; }
+      s_total = acc;
+    }
+    __syncthreads();
+    if (pass) {
+      const float2 a = xy_q[i], b = xy_t[j];
+      pts[base + s_wave[wave] + __popcll(m & ((1ull << lane) - 1ull))] = make_float4(a.x, a.y, b.x, b.y);
+    }
+    base += s_total;
+    __syncthreads();
+  }
+  if (tid == 0) *n_pairs = base;
+}
+
 }  // namespace
+
+void ratio_pairs(const int* idx1, const int* idx2, const float* d1, const float* d2, const int* nq_dev, int cap, int nt, float ratio,
+                 const float2* xy_q, const float2* xy_t, float4* pts, int* n_pairs, hipStream_t s) {
+  hipLaunchKernelGGL(ratio_pairs_kernel, dim3(1), dim3(1024), 0, s, idx1, idx2, d1, d2, nq_dev, cap, nt, ratio, xy_q, xy_t, pts, n_pairs);
+  GTX_HIP(hipGetLastError());
+}
 
 int match2nn_splits(int nq, int nt) {
   // enough workgroups to fill 256 CUs a few times over, but splits of at least 8 tiles

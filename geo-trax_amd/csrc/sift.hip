@@ -76,6 +76,12 @@ __global__ void gray_kernel(const uint8_t* __restrict__ bgr, float* __restrict__
   out[i] = (float)((b * 1868 + g * 9617 + r * 4899 + 8192) >> 14);
 }
 
+// a u8 gray image in HBM, read in place: the value gray_kernel gives a pixel with B = G = R = g (g * 16384 + 8192 >> 14 = g)
+__global__ void gray_u8_kernel(const uint8_t* __restrict__ gray, float* __restrict__ out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (float)gray[i];
+}
+
 // dst(x, y) = bilinear(src, x / 2, y / 2), replicate past the last row / column
 __global__ void upscale_kernel(const float* __restrict__ g, int h, int w, float* __restrict__ out) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
@@ -271,11 +277,16 @@ __device__ bool solve3(float A[3][3], float x[3]) {
   return true;
 }
 
+// The element count of a stage that is launched before the host knows it (extract_async): n_dev names the counter word the stage
+// before left in HBM, and `cap` is what the list holds -- the count is clamped to it before anything is indexed (a count above the
+// capacity is reported as an error when the counters reach the host). n_dev == nullptr: the count is `cap` itself, by value.
+__device__ __forceinline__ int list_count(const int* __restrict__ n_dev, int cap) { return n_dev ? min(max(*n_dev, 0), cap) : cap; }
+
 // adjustLocalExtrema: thread per candidate
 __global__ __launch_bounds__(256) void refine_kernel(const OctaveTable T, const Cand* __restrict__ cand, int n_cand, Refined* __restrict__ out,
-                                                     int* __restrict__ n_out) {
+                                                     int* __restrict__ n_out, const int* __restrict__ n_dev) {
   const int i0 = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i0 >= n_cand) return;
+  if (i0 >= list_count(n_dev, n_cand)) return;
   const Cand cd = cand[i0];
   const int o = cd.o, w = T.w[o], h = T.h[o];
   int layer = cd.layer, r = cd.r, c = cd.c;
@@ -338,12 +349,12 @@ __global__ __launch_bounds__(256) void refine_kernel(const OctaveTable T, const 
 // calcOrientationHist + peak picking: one wave per refined keypoint
 // hist_out (null on the product path): the smoothed histogram of every input keypoint, [n][kOriBins]
 __global__ __launch_bounds__(256) void orient_kernel(const OctaveTable T, const Refined* __restrict__ in, int n, Oriented* __restrict__ out,
-                                                     int* __restrict__ n_out, int cap, float* __restrict__ hist_out) {
+                                                     int* __restrict__ n_out, int cap, float* __restrict__ hist_out, const int* __restrict__ n_dev) {
   __shared__ double s_hist[4][kOriBins];
   __shared__ float s_tmp[4][kOriBins + 4], s_h[4][kOriBins];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + wave;
-  if (i >= n) return;                       // whole wave exits together (i is wave-uniform)
+  if (i >= list_count(n_dev, n)) return;    // whole wave exits together (i is wave-uniform)
   const Refined R = in[i];
   const int w = T.w[R.o], h = T.h[R.o];
   const float* img = T.g[R.o][R.layer];
@@ -413,12 +424,12 @@ __global__ __launch_bounds__(256) void orient_kernel(const OctaveTable T, const 
 // calcSIFTDescriptor (+ RootSIFT): one wave per keypoint
 constexpr int kD = 4, kN = 8, kHist = (kD + 2) * (kD + 2) * (kN + 2);
 __global__ __launch_bounds__(256) void describe_kernel(const OctaveTable T, const Final* __restrict__ kps, int n, float* __restrict__ desc, int root,
-                                                       float root_eps) {
+                                                       float root_eps, const int* __restrict__ n_dev) {
   __shared__ double s_hist[4][kHist];
   __shared__ float s_dst[4][128];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + wave;
-  if (i >= n) return;
+  if (i >= list_count(n_dev, n)) return;
   const Final K = kps[i];
   const int w = T.w[K.o], h = T.h[K.o];
   const float* img = T.g[K.o][K.layer];
@@ -497,6 +508,180 @@ __global__ __launch_bounds__(256) void describe_kernel(const OctaveTable T, cons
   (void)s_dst;
   desc[(size_t)i * 128 + lane] = v[0];
   desc[(size_t)i * 128 + 64 + lane] = v[1];
+}
+
+// ---- retainBest, the keypoint order and the final records on the device (extract_async; detect_and_compute does the same on the host).
+// Every oriented record has a 96-bit rank (a, b): a = the complement of its response's order-preserving integer image (ascending a =
+// descending response), b = its 64-bit key (octave, layer, row, column, orientation bin: unique per record). The max_features records
+// with the smallest rank stay: a radix select finds the rank of the last of them, 8 bits a pass, twelve passes of one workgroup over
+// the compact (a, b) arrays with an LDS histogram each. Integer counts only, so nothing depends on the order of the list or of the
+// atomics. The kept records are then gathered (in any order), masked, and each one's output row is the number of unmasked kept
+// records with a smaller key: rows come out in key order without a sort.
+struct Kept {
+  unsigned long long key;
+  int src, masked;
+};
+constexpr int kSelThreads = 1024;
+constexpr int kMaxSelect = 1 << 16;         // max_features of extract_async: the ranking is quadratic in it
+constexpr int kMaxMaskRects = 1024;
+// counter words of a pass: candidates, refined, oriented, keypoints kept (after the mask); records selected (before the mask), the
+// threshold rank (a, b low, b high)
+constexpr int kCntSel = 4, kCntThr = 5, kCntWords = 8;
+
+__device__ __forceinline__ unsigned long long oriented_key(const Oriented& a) {
+  return ((unsigned long long)a.key.o << 56) | ((unsigned long long)a.key.layer << 48) | ((unsigned long long)(unsigned)a.key.r << 28) |
+         ((unsigned long long)(unsigned)a.key.c << 8) | (unsigned long long)(unsigned)a.bin;
+}
+
+__global__ __launch_bounds__(256) void select_rank_words_kernel(const Oriented* __restrict__ ori, const int* __restrict__ n_dev, int cap,
+                                                                unsigned* __restrict__ ra, unsigned long long* __restrict__ rb) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= list_count(n_dev, cap)) return;
+  const Oriented O = ori[i];
+  unsigned u = O.response == 0.f ? 0u : __float_as_uint(O.response);     // -0 and +0 compare equal
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);                         // ascending u = ascending float
+  ra[i] = ~u;
+  rb[i] = oriented_key(O);
+}
+
+__global__ __launch_bounds__(kSelThreads) void select_threshold_kernel(const unsigned* __restrict__ ra, const unsigned long long* __restrict__ rb,
+                                                                       const int* __restrict__ n_dev, int cap, int keep, unsigned* __restrict__ thr) {
+  __shared__ int s_hist[256], s_scan[256];
+  __shared__ int s_digit, s_rem;
+  const int tid = threadIdx.x;
+  const int n = list_count(n_dev, cap);
+  unsigned pa = ~0u;
+  unsigned long long pb = ~0ull;                // n <= keep: every record is at or below the threshold
+  if (n > keep) {
+    pa = 0u; pb = 0ull;
+    int rem = keep;                             // the threshold is the rem-th smallest rank among those that share the prefix (pa, pb)
+    for (int p = 0; p < 12; ++p) {
+      if (tid < 256) s_hist[tid] = 0;
+      __syncthreads();
+      const int q = p - 4;
+      const unsigned ma = p == 0 ? 0u : (p >= 4 ? ~0u : ~0u << (32 - 8 * p));
+      const unsigned long long mb = q <= 0 ? 0ull : ~0ull << (64 - 8 * q);
+      for (int i = tid; i < n; i += kSelThreads) {
+        const unsigned a = ra[i];
+        if ((a & ma) != pa) continue;
+        if (p < 4) { atomicAdd(&s_hist[(a >> (24 - 8 * p)) & 255u], 1); continue; }
+        const unsigned long long b = rb[i];
+        if ((b & mb) == pb) atomicAdd(&s_hist[(int)((b >> (56 - 8 * q)) & 255ull)], 1);
+      }
+      __syncthreads();
+      if (tid < 256) s_scan[tid] = s_hist[tid];
+      __syncthreads();
+      for (int off = 1; off < 256; off <<= 1) {
+        int v = 0;
+        if (tid < 256 && tid >= off) v = s_scan[tid - off];
+        __syncthreads();
+        if (tid < 256) s_scan[tid] += v;
+        __syncthreads();
+      }
+      if (tid < 256) {
+        const int incl = s_scan[tid], excl = incl - s_hist[tid];
+        if (excl < rem && rem <= incl) { s_digit = tid; s_rem = rem - excl; }      // one bin: 1 <= rem <= the records that share the prefix
+      }
+      __syncthreads();
+      const int d = s_digit;
+      rem = s_rem;
+      if (p < 4) pa |= (unsigned)d << (24 - 8 * p);
+      else pb |= (unsigned long long)d << (56 - 8 * q);
+      __syncthreads();
+    }
+  }
+  if (tid == 0) { thr[0] = pa; thr[1] = (unsigned)pb; thr[2] = (unsigned)(pb >> 32); }
+}
+
+// OpenCV's KeyPointsFilter::runByPixelsMask on rectangles: the keypoint's working-resolution position, rounded as (int)(v + 0.5f),
+// inside one of the inclusive rectangles (x1, y1, x2, y2)
+__device__ __forceinline__ bool in_mask_rects(float x, float y, const int4* __restrict__ rects, int n_rects) {
+  const int ix = (int)(x + 0.5f), iy = (int)(y + 0.5f);
+  bool hit = false;
+  for (int r = 0; r < n_rects; ++r) {
+    const int4 q = rects[r];
+    hit |= ix >= q.x && ix <= q.z && iy >= q.y && iy <= q.w;
+  }
+  return hit;
+}
+
+__global__ __launch_bounds__(256) void select_gather_kernel(const Oriented* __restrict__ ori, const unsigned* __restrict__ ra,
+                                                            const unsigned long long* __restrict__ rb, const int* __restrict__ n_dev, int cap, int keep,
+                                                            const unsigned* __restrict__ thr, const int4* __restrict__ rects, int n_rects,
+                                                            Kept* __restrict__ kept, int* __restrict__ n_sel, int* __restrict__ n_kept) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  bool in = i < list_count(n_dev, cap);
+  unsigned long long b = 0;
+  if (in) {
+    const unsigned a = ra[i], ta = thr[0];
+    const unsigned long long tb = (unsigned long long)thr[1] | ((unsigned long long)thr[2] << 32);
+    b = rb[i];
+    in = a < ta || (a == ta && b <= tb);
+  }
+  const int slot = gtx_wave_append(n_sel, in);
+  in = in && slot < keep;                     // keys are unique, so the threshold admits exactly min(n, keep) records
+  bool masked = false;
+  if (in) {
+    const Oriented O = ori[i];
+    masked = n_rects > 0 && in_mask_rects((float)((double)O.x * 0.5), (float)((double)O.y * 0.5), rects, n_rects);
+    kept[slot] = Kept{b, i, masked ? 1 : 0};
+  }
+  (void)gtx_wave_append(n_kept, in && !masked);
+}
+
+// One thread per selected record: its row among the unmasked ones in key order, and the three records of that row -- the descriptor
+// kernel's Final, the position, the keypoint as gtx_sift_detect reports it -- with detect_and_compute's double-precision scaling.
+__global__ __launch_bounds__(256) void select_finalize_kernel(const Oriented* __restrict__ ori, const Kept* __restrict__ kept, const int* __restrict__ n_sel,
+                                                              int keep, Final* __restrict__ fin, float2* __restrict__ xy, SiftKeypoint* __restrict__ kps) {
+  __shared__ unsigned long long s_key[256];
+  const int n = list_count(n_sel, keep);
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  Kept mine{~0ull, 0, 1};
+  if (j < n) mine = kept[j];
+  int row = 0;
+  for (int t0 = 0; t0 < n; t0 += 256) {
+    unsigned long long k = ~0ull;             // a masked record, and the tile's tail: above every key
+    if (t0 + (int)threadIdx.x < n) { const Kept o = kept[t0 + threadIdx.x]; if (!o.masked) k = o.key; }
+    s_key[threadIdx.x] = k;
+    __syncthreads();
+    const int m = min(256, n - t0);
+    for (int u = 0; u < m; ++u) row += s_key[u] < mine.key ? 1 : 0;
+    __syncthreads();
+  }
+  if (j >= n || mine.masked) return;
+  const Oriented O = ori[mine.src];
+  const double scale = 1.0 / (double)(1 << O.o);
+  Final f;
+  f.px = (float)((double)O.x * scale); f.py = (float)((double)O.y * scale);
+  double a = 360.0 - (double)O.angle;
+  if (fabs(a - 360.0) < 1.19e-7) a = 0.0;
+  f.ori = a;
+  f.scl = (float)((double)O.size * scale * 0.5);
+  f.o = O.o; f.layer = O.layer; f.pad = 0;
+  fin[row] = f;
+  SiftKeypoint k;
+  k.x = (float)((double)O.x * 0.5); k.y = (float)((double)O.y * 0.5); k.size = (float)((double)O.size * 0.5);
+  k.angle = O.angle; k.response = O.response;
+  k.octave = (O.word & ~255) | ((O.o - 1) & 255);
+  kps[row] = k;
+  xy[row] = make_float2(k.x, k.y);
+}
+
+struct SelectBufs {
+  unsigned* ra;
+  unsigned long long* rb;
+  Kept* kept;
+};
+// The four selection launches: ori [cap] with its count in cnt[2]; the kept count lands in cnt[3]; cnt[4..7] are scratch words the
+// caller zeroed with the counters.
+void launch_select(const Oriented* ori, int cap, int* cnt, int keep, const int4* rects, int n_rects, const SelectBufs& B, Final* fin, float2* xy,
+                   SiftKeypoint* kps, hipStream_t s) {
+  unsigned* thr = reinterpret_cast<unsigned*>(cnt + kCntThr);
+  hipLaunchKernelGGL(select_rank_words_kernel, dim3(cdiv(cap, 256)), dim3(256), 0, s, ori, cnt + 2, cap, B.ra, B.rb);
+  hipLaunchKernelGGL(select_threshold_kernel, dim3(1), dim3(kSelThreads), 0, s, B.ra, B.rb, cnt + 2, cap, keep, thr);
+  hipLaunchKernelGGL(select_gather_kernel, dim3(cdiv(cap, 256)), dim3(256), 0, s, ori, B.ra, B.rb, cnt + 2, cap, keep, thr, rects, n_rects, B.kept,
+                     cnt + kCntSel, cnt + 3);
+  hipLaunchKernelGGL(select_finalize_kernel, dim3(cdiv(keep, 256)), dim3(256), 0, s, ori, B.kept, cnt + kCntSel, keep, fin, xy, kps);
 }
 
 Taps make_taps(double sigma) {
@@ -603,7 +788,7 @@ void op_sift_refine(gtx_ctx* ctx, const float* dog5, int h, int w, int octave, c
   OctaveTable T{};
   T.n = octave + 1; T.w[octave] = w; T.h[octave] = h;
   for (int i = 0; i < kDog; ++i) T.d[octave][i] = dd.as<float>() + np * i;
-  if (n > 0) hipLaunchKernelGGL(refine_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, T, dc.as<Cand>(), n, dr.as<Refined>(), dn.as<int>());
+  if (n > 0) hipLaunchKernelGGL(refine_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, T, dc.as<Cand>(), n, dr.as<Refined>(), dn.as<int>(), (const int*)nullptr);
   GTX_HIP(hipGetLastError());
   GTX_HIP(hipStreamSynchronize(s));
   download(count, dn, sizeof(int));
@@ -625,7 +810,7 @@ void op_sift_orient(gtx_ctx* ctx, const float* gauss_layer, int h, int w, int oc
   T.n = octave + 1; T.w[octave] = w; T.h[octave] = h;
   for (int i = 0; i < kGauss; ++i) T.g[octave][i] = dg.as<float>();       // whichever layer a record names: the one image
   if (n > 0)
-    hipLaunchKernelGGL(orient_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, T, dr.as<Refined>(), n, dout.as<Oriented>(), dn.as<int>(), cap, dh.as<float>());
+    hipLaunchKernelGGL(orient_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, T, dr.as<Refined>(), n, dout.as<Oriented>(), dn.as<int>(), cap, dh.as<float>(), (const int*)nullptr);
   GTX_HIP(hipGetLastError());
   GTX_HIP(hipStreamSynchronize(s));
   download(count, dn, sizeof(int));
@@ -644,10 +829,48 @@ void op_sift_describe(gtx_ctx* ctx, const float* gauss_layer, int h, int w, cons
   OctaveTable T{};
   T.n = 1; T.w[0] = w; T.h[0] = h;
   for (int i = 0; i < kGauss; ++i) T.g[0][i] = dg.as<float>();
-  if (n > 0) hipLaunchKernelGGL(describe_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, T, df.as<Final>(), n, dd.as<float>(), root ? 1 : 0, root_eps);
+  if (n > 0) hipLaunchKernelGGL(describe_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, T, df.as<Final>(), n, dd.as<float>(), root ? 1 : 0, root_eps, (const int*)nullptr);
   GTX_HIP(hipGetLastError());
   GTX_HIP(hipStreamSynchronize(s));
   if (n > 0) download(desc, dd, sizeof(float) * 128 * (size_t)n);
+}
+
+int sift_select_max_features() { return kMaxSelect; }
+int sift_select_max_rects() { return kMaxMaskRects; }
+
+void op_sift_select(gtx_ctx* ctx, const void* oriented, int n, int max_features, const int* rects, int n_rects, int* count, void* finals, float* xy,
+                    float* kp5, int* octave) {
+  GTX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int cap = std::max(n, 1);
+  DevBuf dori, dcnt, drect, dra, drb, dkept, dfin, dxy, dkp;
+  upload(dori, oriented, sizeof(Oriented) * (size_t)n, sizeof(Oriented) * (size_t)cap);
+  int hc[kCntWords] = {0, 0, n, 0, 0, 0, 0, 0};
+  upload(dcnt, hc, sizeof hc);
+  upload(drect, rects, sizeof(int4) * (size_t)n_rects, sizeof(int4));
+  fill_ff(dra, sizeof(unsigned) * (size_t)cap);
+  fill_ff(drb, sizeof(unsigned long long) * (size_t)cap);
+  fill_ff(dkept, sizeof(Kept) * (size_t)max_features);
+  fill_ff(dfin, sizeof(Final) * (size_t)max_features);
+  fill_ff(dxy, sizeof(float2) * (size_t)max_features);
+  fill_ff(dkp, sizeof(SiftKeypoint) * (size_t)max_features);
+  const SelectBufs B{dra.as<unsigned>(), drb.as<unsigned long long>(), dkept.as<Kept>()};
+  launch_select(dori.as<Oriented>(), cap, dcnt.as<int>(), max_features, drect.as<int4>(), n_rects, B, dfin.as<Final>(), dxy.as<float2>(),
+                dkp.as<SiftKeypoint>(), s);
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipStreamSynchronize(s));
+  download(hc, dcnt, sizeof hc);
+  *count = hc[3];
+  GTX_CHECK(*count >= 0 && *count <= std::min(n, max_features), "sift_select: %d keypoints kept of %d (max_features %d)", *count, n, max_features);
+  if (*count == 0) return;
+  if (finals) download(finals, dfin, sizeof(Final) * (size_t)*count);
+  if (xy) download(xy, dxy, sizeof(float2) * (size_t)*count);
+  std::vector<SiftKeypoint> k(*count);
+  download(k.data(), dkp, sizeof(SiftKeypoint) * (size_t)*count);
+  for (int i = 0; i < *count; ++i) {
+    if (kp5) { kp5[5 * i] = k[i].x; kp5[5 * i + 1] = k[i].y; kp5[5 * i + 2] = k[i].size; kp5[5 * i + 3] = k[i].angle; kp5[5 * i + 4] = k[i].response; }
+    if (octave) octave[i] = k[i].octave;
+  }
 }
 
 struct Sift::Impl {
@@ -658,6 +881,12 @@ struct Sift::Impl {
   DevBuf pyr, tmp, frame, gray, cand, refined, oriented, counters, finals, desc, xy;
   size_t cand_cap = 0, kp_cap = 0;
   int n = 0;
+  // extract_async: the selection's rank words and kept list, the keypoint rows in HBM, how many keypoints the buffers hold
+  DevBuf sel_a, sel_b, sel_kept, kps_dev;
+  int async_cap = 0;
+
+  void layout(int h, int w);
+  void pyramid_from_gray(int h, int w);
   std::vector<SiftKeypoint> host_kps;
   // GPU time of the stages of the last detect_and_compute (HIP events on the stream): 0 upload + gray + upscale + Gaussian / DoG pyramid,
   // 1 extrema + refine + orientation (with their host round trips for the counters), 2 descriptors; 3 = doubled-base pixels
@@ -676,6 +905,49 @@ struct Sift::Impl {
     launch_blur(src, dst, dog, tmp.as<float>(), w, h, make_taps(sigma), two_pass ? 2 : 0, s);
   }
 };
+
+void Sift::Impl::layout(int h, int w) {
+  // ---- pyramid layout for this image
+  const int bw = 2 * w, bh = 2 * h;
+  T.n = std::min(kMaxOct, (int)std::nearbyint(std::log((double)std::min(bw, bh)) / std::log(2.0) - 2) + 1);
+  GTX_CHECK(T.n >= 1, "sift: image too small for one octave");
+  float* p = pyr.as<float>();
+  int ow = bw, oh = bh, n_oct = 0;
+  for (int o = 0; o < T.n; ++o) {
+    T.w[o] = ow; T.h[o] = oh;
+    for (int i = 0; i < kGauss; ++i) { T.g[o][i] = p; p += (size_t)ow * oh; }
+    for (int i = 0; i < kDog; ++i) { T.d[o][i] = p; p += (size_t)ow * oh; }
+    n_oct = o + 1;
+    if (std::min(ow, oh) / 2 < 1) break;
+    ow /= 2; oh /= 2;
+  }
+  T.n = n_oct;
+}
+
+// Gaussian and DoG pyramids from the float gray image in `gray`
+void Sift::Impl::pyramid_from_gray(int h, int w) {
+  const int bw = 2 * w, bh = 2 * h;
+  hipLaunchKernelGGL(upscale_kernel, dim3(cdiv(bw, 256), bh), dim3(256), 0, s, gray.as<float>(), h, w, T.g[0][1]);  // scratch: layer 1
+  blur(T.g[0][1], T.g[0][0], nullptr, bw, bh, std::sqrt(std::max(kSigma * kSigma - 4 * 0.5 * 0.5, 0.01)));
+  double sig[kGauss];
+  {
+    const double k = std::pow(2.0, 1.0 / kLayers);
+    sig[0] = kSigma;
+    for (int i = 1; i < kGauss; ++i) {
+      const double prev = kSigma * std::pow(k, i - 1);
+      sig[i] = std::sqrt((prev * k) * (prev * k) - prev * prev);
+    }
+  }
+  for (int o = 0; o < T.n; ++o) {
+    const int ww = T.w[o], hh = T.h[o];
+    if (o > 0) {
+      const int sw = T.w[o - 1], sh = T.h[o - 1];
+      hipLaunchKernelGGL(down_kernel, dim3(cdiv(ww, 256), hh), dim3(256), 0, s, T.g[o - 1][kLayers], sh, sw, T.g[o][0], hh, ww,
+                         (double)sh / hh, (double)sw / ww);
+    }
+    for (int i = 1; i < kGauss; ++i) blur(T.g[o][i - 1], T.g[o][i], T.d[o][i - 1], ww, hh, sig[i]);   // DoG layer i - 1 = g[i] - g[i - 1], written by the blur
+  }
+}
 
 Sift::Sift(int device, hipStream_t stream, int max_h, int max_w) : impl_(new Impl) {
   Impl& S = *impl_;
@@ -696,7 +968,7 @@ Sift::Sift(int device, hipStream_t stream, int max_h, int max_w) : impl_(new Imp
   S.cand.alloc(S.cand_cap * sizeof(Cand));
   S.refined.alloc(S.cand_cap * sizeof(Refined));
   S.oriented.alloc(S.kp_cap * sizeof(Oriented));
-  S.counters.alloc(4 * sizeof(int));
+  S.counters.alloc(kCntWords * sizeof(int));
   for (hipEvent_t& e : S.ev) GTX_HIP(hipEventCreate(&e));
 }
 
@@ -717,47 +989,15 @@ void Sift::detect_and_compute(const uint8_t* image, int h, int w, int max_featur
   GTX_CHECK(max_features >= 1, "sift: max_features must be positive");
   GTX_HIP(hipSetDevice(S.device));
   hipStream_t s = S.s;
-  // ---- pyramid layout for this image
+  S.layout(h, w);
   const int bw = 2 * w, bh = 2 * h;
   OctaveTable& T = S.T;
-  T.n = std::min(kMaxOct, (int)std::nearbyint(std::log((double)std::min(bw, bh)) / std::log(2.0) - 2) + 1);
-  GTX_CHECK(T.n >= 1, "sift: image too small for one octave");
-  float* p = S.pyr.as<float>();
-  int ow = bw, oh = bh, n_oct = 0;
-  for (int o = 0; o < T.n; ++o) {
-    T.w[o] = ow; T.h[o] = oh;
-    for (int i = 0; i < kGauss; ++i) { T.g[o][i] = p; p += (size_t)ow * oh; }
-    for (int i = 0; i < kDog; ++i) { T.d[o][i] = p; p += (size_t)ow * oh; }
-    n_oct = o + 1;
-    if (std::min(ow, oh) / 2 < 1) break;
-    ow /= 2; oh /= 2;
-  }
-  T.n = n_oct;
   // ---- base image
   GTX_HIP(hipEventRecord(S.ev[0], s));
   GTX_HIP(hipMemcpyAsync(S.frame.p, image, (size_t)h * w * 3, hipMemcpyHostToDevice, s));
   const size_t npx = (size_t)h * w;
   hipLaunchKernelGGL(gray_kernel, dim3((unsigned)cdiv((long)npx, 256L)), dim3(256), 0, s, S.frame.as<uint8_t>(), S.gray.as<float>(), npx);
-  hipLaunchKernelGGL(upscale_kernel, dim3(cdiv(bw, 256), bh), dim3(256), 0, s, S.gray.as<float>(), h, w, T.g[0][1]);  // scratch: layer 1
-  S.blur(T.g[0][1], T.g[0][0], nullptr, bw, bh, std::sqrt(std::max(kSigma * kSigma - 4 * 0.5 * 0.5, 0.01)));
-  double sig[kGauss];
-  {
-    const double k = std::pow(2.0, 1.0 / kLayers);
-    sig[0] = kSigma;
-    for (int i = 1; i < kGauss; ++i) {
-      const double prev = kSigma * std::pow(k, i - 1);
-      sig[i] = std::sqrt((prev * k) * (prev * k) - prev * prev);
-    }
-  }
-  for (int o = 0; o < T.n; ++o) {
-    const int ww = T.w[o], hh = T.h[o];
-    if (o > 0) {
-      const int sw = T.w[o - 1], sh = T.h[o - 1];
-      hipLaunchKernelGGL(down_kernel, dim3(cdiv(ww, 256), hh), dim3(256), 0, s, T.g[o - 1][kLayers], sh, sw, T.g[o][0], hh, ww,
-                         (double)sh / hh, (double)sw / ww);
-    }
-    for (int i = 1; i < kGauss; ++i) S.blur(T.g[o][i - 1], T.g[o][i], T.d[o][i - 1], ww, hh, sig[i]);   // DoG layer i - 1 = g[i] - g[i - 1], written by the blur
-  }
+  S.pyramid_from_gray(h, w);
   GTX_HIP(hipEventRecord(S.ev[1], s));
   // ---- extrema -> refine -> orientation
   int* cnt = S.counters.as<int>();
@@ -770,14 +1010,14 @@ void Sift::detect_and_compute(const uint8_t* image, int h, int w, int max_featur
   // would differ from run to run. The reference has no cap at all, so an overflow is an error, not a smaller answer.
   GTX_CHECK(hc[0] >= 0 && (size_t)hc[0] <= S.cand_cap, "sift: extrema stage found %d candidates, the list holds %zu", hc[0], S.cand_cap);
   const int n_cand = hc[0];
-  if (n_cand > 0) hipLaunchKernelGGL(refine_kernel, dim3(cdiv(n_cand, 256)), dim3(256), 0, s, T, S.cand.as<Cand>(), n_cand, S.refined.as<Refined>(), cnt + 1);
+  if (n_cand > 0) hipLaunchKernelGGL(refine_kernel, dim3(cdiv(n_cand, 256)), dim3(256), 0, s, T, S.cand.as<Cand>(), n_cand, S.refined.as<Refined>(), cnt + 1, (const int*)nullptr);
   GTX_HIP(hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, s));
   GTX_HIP(hipStreamSynchronize(s));
   const int n_ref = hc[1];
   GTX_CHECK(n_ref >= 0 && (size_t)n_ref <= S.cand_cap, "sift: refine stage kept %d keypoints, the list holds %zu", n_ref, S.cand_cap);
   if (n_ref > 0)
     hipLaunchKernelGGL(orient_kernel, dim3(cdiv(n_ref, 4)), dim3(256), 0, s, T, S.refined.as<Refined>(), n_ref, S.oriented.as<Oriented>(), cnt + 2,
-                       (int)S.kp_cap, (float*)nullptr);
+                       (int)S.kp_cap, (float*)nullptr, (const int*)nullptr);
   GTX_HIP(hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, s));
   GTX_HIP(hipStreamSynchronize(s));
   GTX_HIP(hipEventRecord(S.ev[2], s));
@@ -845,13 +1085,84 @@ void Sift::detect_and_compute(const uint8_t* image, int h, int w, int max_featur
   if (n > 0) {
     GTX_HIP(hipMemcpyAsync(S.finals.p, fin.data(), sizeof(Final) * n, hipMemcpyHostToDevice, s));
     GTX_HIP(hipMemcpyAsync(S.xy.p, xy.data(), sizeof(float2) * n, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(describe_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, T, S.finals.as<Final>(), n, S.desc.as<float>(), root ? 1 : 0, root_eps);
+    hipLaunchKernelGGL(describe_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, T, S.finals.as<Final>(), n, S.desc.as<float>(), root ? 1 : 0, root_eps, (const int*)nullptr);
     GTX_HIP(hipGetLastError());
   }
   GTX_HIP(hipEventRecord(S.ev[3], s));
   GTX_HIP(hipStreamSynchronize(s));     // fin / xy are stack-owned host buffers
   for (int i = 0; i < 3; ++i) GTX_HIP(hipEventElapsedTime(&S.stage_ms[i], S.ev[i], S.ev[i + 1]));
   S.stage_ms[3] = (float)((double)bw * bh);
+}
+
+// ---- the same passes with nothing between them but the stream: every count stays in HBM (counters_dev), every list is launched at
+// its capacity, and retainBest, the order and the final records are the select_* kernels. Nothing here waits for the device.
+void Sift::reserve_async(int max_features) {
+  Impl& S = *impl_;
+  GTX_CHECK(max_features >= 1 && max_features <= kMaxSelect, "sift: max_features=%d outside [1, %d] on the stream-ordered path", max_features, kMaxSelect);
+  if (max_features <= S.async_cap) return;
+  GTX_HIP(hipSetDevice(S.device));
+  GTX_HIP(hipStreamSynchronize(S.s));
+  const size_t k = (size_t)max_features;
+  S.sel_a.alloc(sizeof(unsigned) * S.kp_cap);
+  S.sel_b.alloc(sizeof(unsigned long long) * S.kp_cap);
+  S.sel_kept.alloc(sizeof(Kept) * k);
+  S.kps_dev.alloc(sizeof(SiftKeypoint) * k);
+  S.finals.alloc(sizeof(Final) * k);
+  S.desc.alloc(sizeof(float) * 128 * k);
+  S.xy.alloc(sizeof(float2) * k);
+  GTX_HIP(hipMemset(S.desc.p, 0, S.desc.bytes));       // rows past the count are read by the matcher's launch at capacity
+  GTX_HIP(hipMemset(S.xy.p, 0, S.xy.bytes));
+  S.async_cap = max_features;
+}
+
+void Sift::extract_async(const uint8_t* gray_dev, int h, int w, int max_features, bool root, float root_eps, const int4* mask_rects_dev, int n_rects) {
+  Impl& S = *impl_;
+  GTX_CHECK(gray_dev && h >= 8 && w >= 8 && h <= S.max_h && w <= S.max_w, "sift: image %dx%d outside [8, %dx%d]", w, h, S.max_w, S.max_h);
+  GTX_CHECK(max_features >= 1 && max_features <= S.async_cap, "sift: max_features=%d, buffers reserved for %d", max_features, S.async_cap);
+  GTX_CHECK(n_rects >= 0 && n_rects <= kMaxMaskRects && (n_rects == 0 || mask_rects_dev), "sift: %d mask rectangles (at most %d)", n_rects, kMaxMaskRects);
+  GTX_HIP(hipSetDevice(S.device));
+  hipStream_t s = S.s;
+  S.layout(h, w);
+  const OctaveTable& T = S.T;
+  const size_t npx = (size_t)h * w;
+  hipLaunchKernelGGL(gray_u8_kernel, dim3((unsigned)cdiv((long)npx, 256L)), dim3(256), 0, s, gray_dev, S.gray.as<float>(), npx);
+  S.pyramid_from_gray(h, w);
+  int* cnt = S.counters.as<int>();
+  GTX_HIP(hipMemsetAsync(cnt, 0, kCntWords * sizeof(int), s));
+  const int cand_cap = (int)S.cand_cap, kp_cap = (int)S.kp_cap;
+  for (int o = 0; o < T.n; ++o) launch_extrema(T, o, S.cand.as<Cand>(), cnt, cand_cap, s);
+  hipLaunchKernelGGL(refine_kernel, dim3(cdiv(cand_cap, 256)), dim3(256), 0, s, T, S.cand.as<Cand>(), cand_cap, S.refined.as<Refined>(), cnt + 1,
+                     (const int*)cnt);
+  hipLaunchKernelGGL(orient_kernel, dim3(cdiv(cand_cap, 4)), dim3(256), 0, s, T, S.refined.as<Refined>(), cand_cap, S.oriented.as<Oriented>(), cnt + 2,
+                     kp_cap, (float*)nullptr, (const int*)(cnt + 1));
+  const SelectBufs B{S.sel_a.as<unsigned>(), S.sel_b.as<unsigned long long>(), S.sel_kept.as<Kept>()};
+  launch_select(S.oriented.as<Oriented>(), kp_cap, cnt, max_features, mask_rects_dev, n_rects, B, S.finals.as<Final>(), S.xy.as<float2>(),
+                S.kps_dev.as<SiftKeypoint>(), s);
+  hipLaunchKernelGGL(describe_kernel, dim3(cdiv(max_features, 4)), dim3(256), 0, s, T, S.finals.as<Final>(), max_features, S.desc.as<float>(),
+                     root ? 1 : 0, root_eps, (const int*)(cnt + 3));
+  GTX_HIP(hipGetLastError());
+  S.n = 0;
+  S.host_kps.clear();
+}
+
+const int* Sift::counters_dev() const { return impl_->counters.as<int>(); }
+const SiftKeypoint* Sift::keypoints_dev() const { return impl_->kps_dev.as<SiftKeypoint>(); }
+
+void Sift::check_counters(const int c[4], int max_features) const {
+  const Impl& S = *impl_;
+  GTX_CHECK(c[0] >= 0 && (size_t)c[0] <= S.cand_cap, "sift: extrema stage found %d candidates, the list holds %zu", c[0], S.cand_cap);
+  GTX_CHECK(c[1] >= 0 && (size_t)c[1] <= S.cand_cap, "sift: refine stage kept %d keypoints, the list holds %zu", c[1], S.cand_cap);
+  GTX_CHECK(c[2] >= 0 && (size_t)c[2] <= S.kp_cap, "sift: orientation stage made %d keypoints, the list holds %zu", c[2], S.kp_cap);
+  GTX_CHECK(c[3] >= 0 && c[3] <= max_features, "sift: selection kept %d keypoints of at most %d", c[3], max_features);
+}
+
+size_t Sift::resident_bytes(int max_h, int max_w) {
+  const size_t base = (size_t)(2 * max_h) * (2 * max_w);
+  size_t total = 0;
+  int w = 2 * max_w, h = 2 * max_h;
+  for (int o = 0; o < kMaxOct && w >= 1 && h >= 1; ++o) { total += (size_t)w * h * (kGauss + kDog); w /= 2; h /= 2; }
+  const size_t cap = std::max<size_t>(1 << 16, base / 16);
+  return total * sizeof(float) + base * sizeof(float) + (size_t)max_h * max_w * 7 + cap * (sizeof(Cand) + sizeof(Refined) + sizeof(Oriented) + 12);
 }
 
 const std::vector<SiftKeypoint>& Sift::keypoints_host() const { return impl_->host_kps; }

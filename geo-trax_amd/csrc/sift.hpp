@@ -32,6 +32,18 @@ class Sift {
   // orientation bin) with their descriptors (128 floats each; RootSIFT when root) are left on the
   // device; n = number of keypoints (<= max_features, the strongest responses are retained).
   void detect_and_compute(const uint8_t* image_bgr, int h, int w, int max_features, bool root, float root_eps);
+  // The same result from a u8 gray image [h][w] in HBM, read in place, with nothing but launches on the object's stream: no host
+  // wait and no host work. The counts stay in HBM (counters_dev: candidates, refined, oriented, keypoints kept); the strongest
+  // max_features are selected, ordered and finalised by kernels, and the kept keypoints whose rounded position lies inside one of
+  // the inclusive rectangles (x1, y1, x2, y2; pixels of the image; device memory) are then dropped, as cv2's detectAndCompute does
+  // with a mask. count() and keypoints_host() do not cover this path. reserve_async sizes its buffers and may wait for the device;
+  // check_counters fails (as detect_and_compute does) when a stage counted more than its list holds.
+  void reserve_async(int max_features);
+  void extract_async(const uint8_t* gray_dev, int h, int w, int max_features, bool root, float root_eps, const int4* mask_rects_dev, int n_rects);
+  const int* counters_dev() const;               // [4]
+  const SiftKeypoint* keypoints_dev() const;     // [kept] rows as gtx_sift_detect reports them
+  void check_counters(const int counters[4], int max_features) const;
+  static size_t resident_bytes(int max_h, int max_w);     // what an object for images up to max_h x max_w keeps in HBM
   int count() const;
   const float* descriptors_dev() const;         // [n][128] fp32
   const float2* positions_dev() const;          // [n] (x, y)
@@ -63,5 +75,11 @@ void op_sift_orient(gtx_ctx* ctx, const float* gauss_layer, int h, int w, int oc
                     float* hist);
 // describe_kernel on n final records over one Gaussian layer: desc [n][128]
 void op_sift_describe(gtx_ctx* ctx, const float* gauss_layer, int h, int w, const void* finals, int n, int root, float root_eps, float* desc);
+// the selection / finalisation / mask launches of extract_async on n oriented records: count kept, then their final records [count][8],
+// positions [count][2], keypoint rows [count][5] and octave words [count]; rects [n_rects][4] inclusive (x1, y1, x2, y2)
+void op_sift_select(gtx_ctx* ctx, const void* oriented, int n, int max_features, const int* rects, int n_rects, int* count, void* finals, float* xy,
+                    float* kp5, int* octave);
+int sift_select_max_features();
+int sift_select_max_rects();
 
 }  // namespace gtx

@@ -1869,6 +1869,45 @@ bool ransac_homography(int device, hipStream_t s, const float4* d_pts, int n_mat
   return true;
 }
 
+// The two halves of ransac_homography for a chain that keeps the pair count in HBM and must not wait (sift_stab.cpp): ransac_submit
+// enqueues the one launch on a state that ransac_arm initialised once (the kernel re-arms it), ransac_finish is the host half on the
+// record and the pairs the caller copied back.
+size_t ransac_record_bytes() { return sizeof(StabResult); }
+
+void ransac_arm(unsigned long long* state_dev, hipStream_t s) {
+  const unsigned long long armed[2] = {kNoHyp, 0ull};
+  GTX_HIP(hipMemcpyAsync(state_dev, armed, sizeof armed, hipMemcpyHostToDevice, s));
+  GTX_HIP(hipStreamSynchronize(s));
+}
+
+void ransac_submit(hipStream_t s, const float4* d_pts, const int* n_pairs_dev, const int* n_cur_dev, unsigned seed, int n_hyp, int frame_w, int frame_h,
+                   float threshold, unsigned long long* state_dev, void* record_dev) {
+  GTX_CHECK(n_hyp <= 65536, "ransac: at most 65536 hypotheses (got %d)", n_hyp);
+  launch_ransac_kernel(s, d_pts, n_pairs_dev, n_cur_dev, seed, n_hyp, frame_w, frame_h, 0, threshold, state_dev, static_cast<StabResult*>(record_dev));
+  GTX_HIP(hipGetLastError());
+}
+
+void ransac_record_counts(const void* record_host, int* n_pairs, int* n_cur) {
+  const StabResult& R = *static_cast<const StabResult*>(record_host);
+  *n_pairs = R.n_match;
+  *n_cur = R.n_cur;
+}
+
+bool ransac_finish(const void* record_host, const float4* pts_host, int frame_w, int frame_h, float threshold, double H[9], int* n_inliers) {
+  const StabResult& R = *static_cast<const StabResult*>(record_host);
+  *n_inliers = 0;
+  if (R.n_match < 4 || R.best < 0) return false;
+  const double cx = frame_w / 2.0, cy = frame_h / 2.0, sc = 2.0 / frame_w;
+  std::vector<float4> pts(pts_host, pts_host + R.n_match);
+  double Hc[9];
+  std::memcpy(Hc, R.H, sizeof Hc);
+  const double inv = 1.0 / Hc[8];
+  for (double& v : Hc) v *= inv;
+  if (!refine_homography(pts, cx, cy, sc, (double)threshold, Hc, n_inliers)) return false;
+  std::memcpy(H, Hc, sizeof Hc);
+  return true;
+}
+
 // ---- operator hooks (gtx_op_orb_match / gtx_op_orb_ransac): one launch of match_kernel / ransac_kernel on host arrays. The ticket
 // and the RANSAC state live with the context and are initialised once, when the first hook call allocates them: every later call
 // finds them as the launch before it left them, which is how the kernels' re-arming is exercised. The caller has validated all sizes.

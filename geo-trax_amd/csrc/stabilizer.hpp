@@ -68,6 +68,16 @@ void clahe_image(gtx_ctx* ctx, const uint8_t* gray, int h, int w, uint8_t* out);
 bool ransac_homography(int device, hipStream_t s, const float4* d_pts, int n_match, unsigned seed, int n_hyp, int frame_w, int frame_h,
                        float threshold, double H[9], int* n_inliers);
 
+// The same in two halves, for a caller whose pair count is in HBM and who must not wait between them: state_dev is two words that
+// ransac_arm sets once (the kernel leaves them armed), record_dev ransac_record_bytes() of HBM. n_cur_dev is copied into the record.
+// After the stream has run: copy the record and the pairs to the host, read the counts, and ransac_finish does the refit.
+size_t ransac_record_bytes();
+void ransac_arm(unsigned long long* state_dev, hipStream_t s);
+void ransac_submit(hipStream_t s, const float4* d_pts, const int* n_pairs_dev, const int* n_cur_dev, unsigned seed, int n_hyp, int frame_w, int frame_h,
+                   float threshold, unsigned long long* state_dev, void* record_dev);
+void ransac_record_counts(const void* record_host, int* n_pairs, int* n_cur);
+bool ransac_finish(const void* record_host, const float4* pts_host, int frame_w, int frame_h, float threshold, double H[9], int* n_inliers);
+
 // Operator hooks: one launch of the matcher / of the RANSAC kernel on host arrays, exactly as the stabilizer launches them (sizes are
 // validated by the caller, gtx_ops.cpp). Their ticket / state words live with the context and are never re-initialised by the host.
 void op_orb_match(gtx_ctx* ctx, const uint8_t* desc_q, int nq, int slots_q, const uint8_t* desc_t, int nt, int slots_t, float ratio, int keep_all,

@@ -66,6 +66,14 @@ class GeorefChain(C.Structure):
                 ("false_northing", C.c_double)]
 
 
+class SiftStabConfig(C.Structure):
+    """gtx_sift_stab_config (include/gtx.h)."""
+    _fields_ = [("work_h", C.c_int), ("work_w", C.c_int), ("max_features", C.c_int), ("ref_multiplier", C.c_float), ("root", C.c_int),
+                ("rsift_eps", C.c_float), ("filter_ratio", C.c_float), ("ransac_threshold", C.c_float), ("ransac_max_iter", C.c_int),
+                ("ransac_confidence", C.c_float), ("mask_use", C.c_int), ("mask_margin_ratio", C.c_float), ("downsample_ratio", C.c_float),
+                ("seed", C.c_uint32)]
+
+
 class StabConfig(C.Structure):
     _fields_ = [
         ("downsample_ratio", C.c_float), ("max_features", C.c_int), ("ref_multiplier", C.c_float),
@@ -176,6 +184,17 @@ _SIGNATURES = {
     "gtx_op_sift_refine": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int), _P]),
     "gtx_op_sift_orient": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P]),
     "gtx_op_sift_describe": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, _P]),
+    "gtx_op_sift_select": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int), _P, _P, _P, _P]),
+    "gtx_sift_stab_create": (C.c_int, [_P, C.POINTER(SiftStabConfig), C.POINTER(_P)]),
+    "gtx_sift_stab_destroy": (None, [_P]),
+    "gtx_sift_stab_set_ref_gray_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int]),
+    "gtx_sift_stab_submit_gray_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int]),
+    "gtx_sift_stab_collect": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
+    "gtx_sift_stab_stabilize_gray_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.POINTER(C.c_int), _P]),
+    "gtx_sift_stab_last_ms": (C.c_int, [_P, _P]),
+    "gtx_sift_stab_keypoints": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P, _P]),
+    "gtx_sift_stab_pairs": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), _P]),
+    "gtx_sift_stab_counters": (C.c_int, [_P, _P]),
     "gtx_op_match_2nn": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
     "gtx_op_preprocess": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int]),
     "gtx_detector_create": (C.c_int, [_P, C.POINTER(DetConfig), C.POINTER(_P)]),

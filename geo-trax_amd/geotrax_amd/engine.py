@@ -35,6 +35,7 @@ import numpy as np
 from . import _lib
 from .detector import Detector
 from .geometry import warp_boxes
+from .sift_stabilizer import SiftStabilizer, resident
 from .stabilizer import Stabilizer
 from .tracker import Tracker
 
@@ -256,15 +257,24 @@ class StreamPlan:
                     ent[2] = None
 
 
+def stabilizer_class(stab_kw: dict | None):
+    """The class an engine builds its stabilizers from: SiftStabilizer for exactly the `stabilo:` blocks it runs (sift / rsift at
+    downsample_ratio 0.5, ratio filter, projective, CLAHE off: sift_stabilizer.resident, the predicate extract.pipelined() uses),
+    Stabilizer for everything else -- sift / rsift at other ratios included, which it serves on host frames, and the combinations it
+    refuses."""
+    return SiftStabilizer if resident(stab_kw) else Stabilizer
+
+
 class ExtractEngine:
     def __init__(self, weights: dict, frame_hw: tuple[int, int], det_kw: dict, tracker: Tracker | None, stab_kw: dict | None, *,
                  device: int | None = None, batch: int = 2, det_streams: int = 2, stab_streams: int = 4, gmc: bool | str = False,
-                 detectors: list[Detector] | None = None, feeder_stream: bool = False, gmc_kw: dict | None = None):
+                 detectors: list[Detector] | None = None, feeder_stream: bool = False, gmc_kw: dict | None = None, stab_cls=None):
         """det_kw: Detector keywords (imgsz, conf, iou, max_det, classes, agnostic_nms, half, rect). tracker None: raw
         detections pass through (ids None; the frame-sharded bench tracks later on rank 0). stab_kw None: no
         stabilization. `detectors`: already-built Detector objects to adopt (same weights, own contexts). `feeder_stream`: also
         take `self.feeder_ctx`, the context a read-ahead feeder's transfers run on (geotrax_amd.feeder.FrameFeeder(ctx=...)),
-        from the stream plan."""
+        from the stream plan. `stab_cls`: the stabilizer class, instead of stabilizer_class(stab_kw) (the frame-sharded run keeps
+        Stabilizer for every detector)."""
         self.device = _lib.default_device() if device is None else device
         self.frame_hw = (int(frame_hw[0]), int(frame_hw[1]))
         self.B = max(int(batch), 1)
@@ -293,8 +303,11 @@ class ExtractEngine:
 
         while len(self.dets) < n_dets:
             self.dets.append(Detector(weights, self.frame_hw, max_batch=self.B, ctx=take("d"), **det_kw))   # det_kw carries obj_feats when the tracker asks
+        # sift / rsift blocks SiftStabilizer runs: the stream-ordered chain on the gray image (each object keeps a SIFT pyramid in HBM
+        # and checks at creation that it fits); everything else: Stabilizer, as before
+        stab_cls = stab_cls or stabilizer_class(stab_kw)
         while len(self.stabs) < n_stab:
-            self.stabs.append(Stabilizer(self.frame_hw, ctx=take("s"), **stab_kw))
+            self.stabs.append(stab_cls(self.frame_hw, ctx=take("s"), **stab_kw))
         if self.reid_tensors is not None:
             # the separate ReID network runs on each detector's own stream (no stream of its own: the StreamPlan is the one runs
             # without ReID get), in stream order behind the detector pass that read the same frames

@@ -172,6 +172,15 @@ def load_detector_sharded(args: argparse.Namespace, logger: logging.Logger) -> Y
     return model
 
 
+def sharded_engine_kwargs() -> dict:
+    """What the frame-sharded run fixes about its engines. Its stabilizers are Stabilizer objects whatever the detector: sift /
+    rsift stabilization is served there as before (host frames at downsample_ratio 1.0) or refused as before (Stabilizer.
+    set_ref_gray_dev raises at 0.5); the resident SiftStabilizer chain is the single-process engine's."""
+    from .stabilizer import Stabilizer
+
+    return dict(stab_cls=Stabilizer)
+
+
 def track_with_model_sharded(model: YOLO, config: dict, logger: logging.Logger) -> tuple[np.ndarray, np.ndarray] | None:
     """The hot loop with the frames of the video sharded over the ranks of the launcher (one process per GPU):
     runs of consecutive frames dealt round-robin (distributed.shard_runs), every rank registers against the same reference
@@ -211,7 +220,8 @@ def track_with_model_sharded(model: YOLO, config: dict, logger: logging.Logger) 
         engine = ExtractEngine(model.tensors, reader.frame_hw, det_kw, None, stab_kw, device=local, batch=int(eng_cfg.get('batch', 2)),
                                det_streams=int(eng_cfg.get('det_streams', 2)), stab_streams=int(eng_cfg.get('stab_streams', 4)),
                                gmc=model._gmc_method or False, gmc_kw=eng_cfg.get('gmc'),
-                               feeder_stream=os.environ.get("GTX_FEEDER", "1") != "0" and eng_cfg.get('read_ahead', True) is not False)
+                               feeder_stream=os.environ.get("GTX_FEEDER", "1") != "0" and eng_cfg.get('read_ahead', True) is not False,
+                               **sharded_engine_kwargs())
         state['engine'] = engine
         seekable = hasattr(reader, 'seek')
         cursor = {'pos': 0, 'last': None}                    # sequential sources: next frame read() returns, and the one before it
@@ -564,8 +574,12 @@ def track_with_model_blocking(model: YOLO, config: dict, logger: logging.Logger)
 def pipelined(config: dict) -> bool:
     """`engine: {pipelined: false}` / GTX_ENGINE=blocking: the frame-at-a-time loop instead of the engine."""
     eng_cfg = config['main'].get('engine') or {}
-    if str((config.get('stabilo') or {}).get('detector_name', 'orb')) in ('sift', 'rsift') and config['main']['extraction'].get('stabilize', True):
-        return False                        # those detectors register host frames one at a time (stabilizer.py): the blocking loop
+    stab = config.get('stabilo') or {}
+    if str(stab.get('detector_name', 'orb')) in ('sift', 'rsift') and config['main']['extraction'].get('stabilize', True):
+        from .sift_stabilizer import resident
+
+        if not resident(stab):              # what SiftStabilizer does not run (other downsample ratios, affine, filter_type none, clahe)
+            return False                    # registers host frames one at a time (stabilizer.py): the blocking loop
     return eng_cfg.get('pipelined', True) is not False and os.environ.get("GTX_ENGINE", "") != "blocking"
 
 

@@ -647,3 +647,20 @@ def sift_describe(gauss_layer, px, py, ori, scl, *, root: bool = False, eps: flo
     desc = np.full((max(len(f), 1), 128), np.nan, np.float32)
     check(ctx.lib.gtx_op_sift_describe(ctx.handle, ptr(g), g.shape[0], g.shape[1], ptr(f) if len(f) else None, len(f), int(root), float(eps), ptr(desc)))
     return desc[:len(f)]
+
+
+def sift_select(oriented, max_features: int, rects=None, *, ctx=None):
+    """The selection / finalisation / mask launches of the stream-ordered extraction on oriented records (SIFT_ORIENTED, any
+    order): the max_features strongest (response descending, equal responses by key ascending), in key order, minus those whose
+    rounded working-resolution position lies in one of rects [m, 4] i32 (x1, y1, x2, y2, inclusive).
+    -> dict(n, final (SIFT_FINAL), xy [n, 2], kp5 [n, 5], octave [n])."""
+    ctx = ctx or _lib.default_context()
+    o = np.ascontiguousarray(oriented, dtype=SIFT_ORIENTED).reshape(-1)
+    r = np.zeros((0, 4), np.int32) if rects is None else np.ascontiguousarray(rects, dtype=np.int32).reshape(-1, 4)
+    room = max(min(len(o), int(max_features)), 1)
+    n = C.c_int(-1)
+    fin, xy, kp5, octv = np.zeros(room, SIFT_FINAL), np.zeros((room, 2), np.float32), np.zeros((room, 5), np.float32), np.zeros(room, np.int32)
+    check(ctx.lib.gtx_op_sift_select(ctx.handle, ptr(o) if len(o) else None, len(o), int(max_features), ptr(r) if len(r) else None, len(r), C.byref(n),
+                                     ptr(fin), ptr(xy), ptr(kp5), ptr(octv)))
+    k = n.value
+    return dict(n=k, final=fin[:k].copy(), xy=xy[:k].copy(), kp5=kp5[:k].copy(), octave=octv[:k].copy())

@@ -64,7 +64,9 @@ extern "C" {
  *     sparse-optical-flow GMC's kernels one launcher at a time) added: the same, the number stays.
  * 14: gtx_op_sift_{blur, extrema, refine, orient, describe} added: the SIFT kernels one stage at a time. gtx_sift_detect and
  *     gtx_register_images fail (GTX_ERR_UNSUPPORTED) when a stage finds more candidates or keypoints than its list holds, instead of
- *     going on with whichever of them found room. */
+ *     going on with whichever of them found room. gtx_sift_stab_* (stabilo's sift / rsift stabilizer as a stream-ordered chain on the
+ *     detector's gray image) and gtx_op_sift_select (its selection / finalisation / mask kernels on host arrays) added: new entry points
+ *     and a struct of their own only, no existing struct or signature changed, so the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -904,6 +906,67 @@ int gtx_op_sift_orient(gtx_ctx* ctx, const float* gauss_layer, int h, int w, int
                        void* out, float* hist);
 int gtx_op_sift_describe(gtx_ctx* ctx, const float* gauss_layer, int h, int w, const void* finals, int n, int root, float root_eps,
                          float* desc);
+
+/* The selection stage of the stream-ordered extraction on host arrays: of n oriented records (rows of 13 words, above; any order) the
+ * max_features strongest stay -- response descending, equal responses by key (octave, layer, row, column, orientation bin)
+ * ascending; fewer than max_features: all of them -- and come out in ascending key order with the kept keypoints whose
+ * working-resolution position, rounded as (int)(v + 0.5f), lies inside one of the n_rects inclusive rectangles rects [n_rects][4] i32
+ * (x1, y1, x2, y2) dropped (cv2: the mask is applied after retainBest). *count = keypoints left; finals [count][8] words (the final
+ * record above), xy [count][2], kp5 [count][5] and octave [count] as gtx_sift_detect reports them (each may be NULL). The result
+ * depends on the set of records only. Refused before the GPU is touched: n outside [0, 2^20], max_features outside [1, 65536], more
+ * than 1024 rectangles, a response that is not finite or is negative, an octave outside 0..15, a layer outside 0..7, a row or column
+ * outside [0, 2^20), a bin outside 0..255, two records with one key. */
+int gtx_op_sift_select(gtx_ctx* ctx, const void* oriented, int n, int max_features, const int* rects, int n_rects, int* count, void* finals,
+                       float* xy, float* kp5, int* octave);
+
+/* ------------------------------------------------------------------ stabilizer, detector_name sift / rsift
+ * stabilo.Stabilizer with `detector_name: sift | rsift`, matcher bf, filter_type ratio, projective model, on the detector's
+ * half-resolution gray image in HBM: the kernels of gtx_register_images as one stream-ordered chain. The reference frame's features
+ * are extracted once (_set_ref_gray_dev; lround(max_features * ref_multiplier) of them, as the ORB stabilizer plans its reference
+ * set). _submit_gray_dev enqueues extraction (every count stays in HBM), fp16 descriptors, the L2 2-NN search, Lowe's ratio with the
+ * pair list, and the RANSAC launch on the context's stream and returns without waiting; _collect waits, checks the counters (a stage
+ * that counted more than its list holds: GTX_ERR_UNSUPPORTED, as gtx_sift_detect) and runs the robust refit on the host.
+ * H maps current to reference pixels OF THE WORKING IMAGE (row-major 3x3 f64); the caller conjugates it with the downsample
+ * ratio. stats[4] = keypoints ref, keypoints cur, pairs after the ratio test, inliers; valid = 0 (not an error) with fewer than 1
+ * current keypoint, 2 reference keypoints or 4 pairs, or when no model is found. The vehicle mask (boxes xywh [n][4] in frame pixels
+ * grown by mask_margin_ratio, scaled by downsample_ratio, floor / ceil, clipped, inclusive -- the ORB path's rule) drops kept
+ * keypoints after the strongest max_features were chosen, as cv2's detectAndCompute(image, mask) does. For the same images, seed,
+ * threshold and max_iter the pairs, stats and H are those of gtx_register_images, provided the matcher splits the reference set alike
+ * for max_features query rows (this chain) and for the frame's own keypoint count (gtx_register_images): always so below 2048
+ * reference keypoints. At most 1024 rectangles are masked; boxes beyond them are ignored. Each object keeps one Gaussian / DoG pyramid in
+ * HBM (about 59 bytes per pixel of the doubled working image); _create fails with the sizes when that does not fit. */
+typedef struct gtx_sift_stab_config {
+  int work_h, work_w;          /* the working (gray) image */
+  int max_features;            /* per frame; the reference frame gets lround(max_features * ref_multiplier) */
+  float ref_multiplier;
+  int root;                    /* 1: RootSIFT descriptors (rsift), 0: plain SIFT */
+  float rsift_eps;             /* RootSIFT L1-normalisation epsilon (1e-8) */
+  float filter_ratio;          /* Lowe ratio */
+  float ransac_threshold;      /* px of the working image */
+  int ransac_max_iter;         /* hypotheses, clamped to [256, 16384] */
+  float ransac_confidence;     /* accepted for interface parity; the hypothesis count is fixed */
+  int mask_use;
+  float mask_margin_ratio;
+  float downsample_ratio;      /* frame pixels -> working pixels (scales the boxes of the mask) */
+  uint32_t seed;               /* RANSAC sampling seed */
+} gtx_sift_stab_config;
+typedef struct gtx_sift_stab gtx_sift_stab;
+int gtx_sift_stab_create(gtx_ctx* ctx, const gtx_sift_stab_config* cfg, gtx_sift_stab** out);
+void gtx_sift_stab_destroy(gtx_sift_stab* st);
+int gtx_sift_stab_set_ref_gray_dev(gtx_sift_stab* st, const void* gray_dptr, int gh, int gw, const float* boxes_xywh, int n);
+int gtx_sift_stab_submit_gray_dev(gtx_sift_stab* st, const void* gray_dptr, int gh, int gw, const float* boxes_xywh, int n);
+int gtx_sift_stab_collect(gtx_sift_stab* st, double H[9], int* valid, int stats[4]);
+/* _submit_gray_dev + _collect */
+int gtx_sift_stab_stabilize_gray_dev(gtx_sift_stab* st, const void* gray_dptr, int gh, int gw, const float* boxes_xywh, int n, double H[9],
+                                     int* valid, int stats[4]);
+/* GPU time (ms, stream-ordered events) of the last collected pass: extraction -> matching -> RANSAC */
+int gtx_sift_stab_last_ms(gtx_sift_stab* st, float* ms);
+/* Keypoints of the reference (which 0) or of the last collected frame (1, until the next submit), rows as gtx_sift_detect's. */
+int gtx_sift_stab_keypoints(gtx_sift_stab* st, int which, int cap, int* n, float* kp5, int* octave, float* desc);
+/* The pair list of the last collected frame: pts [n][4] = (x_cur, y_cur, x_ref, y_ref) in query order. */
+int gtx_sift_stab_pairs(gtx_sift_stab* st, int cap, int* n, float* pts);
+/* The extraction's counters of the last collected frame: extrema candidates, refined, oriented, keypoints kept. */
+int gtx_sift_stab_counters(gtx_sift_stab* st, int out[4]);
 
 /* Stabilizer.transform_cur_boxes(): maps the 4 corners of each xywh box through H and
  * returns the axis-aligned bounding rectangle as xywh (rule pinned on the reference's golden
