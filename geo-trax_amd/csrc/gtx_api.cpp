@@ -17,6 +17,7 @@
 #include "gmc.hpp"
 #include "gmc_feat.hpp"
 #include "jpeg.hpp"
+#include "jpeg_enc.hpp"
 #include "register.hpp"
 #include "sift.hpp"
 #include "sift_stab.hpp"
@@ -791,6 +792,56 @@ int gtx_jpeg_kernel_ms(gtx_ctx* ctx, const void* record, size_t bytes, int h, in
     for (int k = 0; k < 3; ++k) ms[k] = (float)(sum[k] / reps);
     if (!yuv_dptr) ms[2] = 0.f;
   });
+}
+
+int gtx_jpeg_enc_create(gtx_ctx* ctx, int h, int w, int quality, int subsampling, gtx_jpeg_enc** out) {
+  return guarded([&] {
+    need(out, "out");
+    *out = nullptr;
+    gtx::JpegEncoder::check_args(h, w, quality, subsampling);
+    need(ctx, "ctx");
+    std::unique_ptr<gtx_jpeg_enc> e(new gtx_jpeg_enc);
+    e->impl.reset(new gtx::JpegEncoder(ctx, h, w, quality, subsampling));
+    *out = e.release();
+  });
+}
+
+void gtx_jpeg_enc_destroy(gtx_jpeg_enc* enc) { delete enc; }
+
+int gtx_jpeg_enc_submit_dev(gtx_jpeg_enc* enc, const void* bgr_dptr) {
+  return guarded([&] {
+    need(enc, "enc"); need(bgr_dptr, "bgr");
+    enc->impl->submit(bgr_dptr);
+  });
+}
+
+int gtx_jpeg_enc_collect(gtx_jpeg_enc* enc, void* record, size_t capacity, size_t* bytes) {
+  bool fits = true;
+  const int st = guarded([&] {
+    need(enc, "enc"); need(bytes, "bytes");
+    fits = enc->impl->collect(record, capacity, bytes);
+  });
+  return st != GTX_OK ? st : fits ? 0 : 1;
+}
+
+int gtx_jpeg_enc_last_ms(gtx_jpeg_enc* enc, float* ms) {
+  return guarded([&] {
+    need(enc, "enc"); need(ms, "ms");
+    *ms = enc->impl->last_ms();
+  });
+}
+
+int gtx_jpeg_emit(const void* record, size_t bytes, void* out, size_t capacity, size_t* n) {
+  int rc = 0;
+  const int st = guarded([&] {
+    need(record, "record"); need(n, "n");
+    if (!out && capacity) gtx::fail(GTX_ERR_INVALID, "jpeg_emit: out is NULL with a capacity of %zu", capacity);
+    if (reinterpret_cast<uintptr_t>(record) & 3) gtx::fail(GTX_ERR_INVALID, "jpeg_emit: the record is not 4-byte aligned");
+    char msg[256];
+    rc = gtx::jpeg::emit(record, bytes, static_cast<uint8_t*>(out), capacity, n, msg, sizeof msg);
+    if (rc < 0) gtx::fail(rc, "%s", msg);
+  });
+  return st != GTX_OK ? st : rc;
 }
 
 int gtx_warp_frame_dev(gtx_ctx* ctx, const void* src_dptr, int h, int w, const double H[9], void* dst_dptr) {

@@ -18,6 +18,7 @@
 #include "ecc.hpp"
 #include "geometry.hpp"
 #include "gmc.hpp"
+#include "jpeg_enc.hpp"
 #include "match_l2.hpp"
 #include "op_staging.hpp"
 #include "register.hpp"
@@ -1137,6 +1138,30 @@ int gtx_op_clahe(gtx_ctx* ctx, const uint8_t* gray, int h, int w, uint8_t* out) 
     need(ctx, "ctx"); need(gray, "gray"); need(out, "out");
     gtx::clahe_image(ctx, gray, h, w, out);
   });
+}
+
+// ---- the JPEG encoder's chain on a host frame (tests/test_jpeg_encode_gpu.py)
+
+int gtx_op_jpeg_encode(gtx_ctx* ctx, const uint8_t* bgr, int h, int w, int quality, int subsampling, void* record, size_t capacity, size_t* bytes) {
+  bool fits = true;
+  const int st = guarded([&] {
+    gtx::JpegEncoder::check_args(h, w, quality, subsampling);
+    need(bgr, "bgr"); need(bytes, "bytes");
+    if (!record && capacity) op_bad("jpeg_encode", "record is NULL with a capacity");
+    if (record && (reinterpret_cast<uintptr_t>(record) & 3)) op_bad("jpeg_encode", "the record buffer is not 4-byte aligned");
+    need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    gtx::DevBuf d_bgr;
+    upload(d_bgr, bgr, (size_t)h * w * 3);
+    gtx::JpegEncoder enc(ctx, h, w, quality, subsampling);
+    enc.submit(d_bgr.p);
+    fits = enc.collect(record, capacity, bytes);
+    if (!fits) {                                                  // the caller asks again with *bytes; nothing stays in flight here
+      std::vector<uint32_t> tmp((*bytes + 3) / 4);
+      (void)enc.collect(tmp.data(), tmp.size() * 4, bytes);
+    }
+  });
+  return st != GTX_OK ? st : fits ? 0 : 1;
 }
 
 }  // extern "C"

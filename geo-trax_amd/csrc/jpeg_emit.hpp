@@ -1,0 +1,31 @@
+// Host half of the JPEG frame sink: the packed record of jpeg_parse.hpp (from the GPU encoder, csrc/jpeg_enc.hip, or from the
+// parser) -> one baseline JFIF JPEG. It replaces the entropy-coding half of cv2.VideoWriter.write() (geotrax/visualize.py:298);
+// colour conversion, chroma downsampling, the forward DCT and quantisation are csrc/jpeg_enc.hip's. Plain C++, no HIP: it
+// compiles alone (csrc/diag/jpeg_emit_check.cpp runs it under the sanitizers).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "jpeg_parse.hpp"
+
+namespace gtx {
+namespace jpeg {
+
+// jpeg_set_quality(quality, force_baseline = TRUE): jpeg_quality_scaling applied to the ITU T.81 Annex K.1 / K.2 tables, clamped
+// to 1..255; natural (row-major) order. quality outside 1..100: false, nothing written.
+bool quality_tables(int quality, uint16_t luma[64], uint16_t chroma[64]);
+
+// The header of the record a w x h frame of `ncomp` components with luma sampling hs x vs has (everything but n_coef and bytes,
+// which depend on the data). false: a size or a sampling outside the accepted set.
+bool make_header(int h, int w, int ncomp, int hs, int vs, RecordHeader* hd);
+
+// Writes the record (`bytes` long, 4-byte aligned; check_record runs first) as a baseline JFIF file into out[0, capacity):
+// SOI, APP0, DQT, SOF0, DHT (the Annex K.3 tables), SOS, the Huffman-coded scan with FF bytes stuffed, EOI. *n receives the
+// file's size whenever the record can be coded. Returns kOk (written), kTooSmall (capacity < *n: call again with *n bytes;
+// nothing outside out[0, capacity) was touched) or kInvalid with a message: a damaged record, a quantiser above 255, or a
+// coefficient the Annex K.3 tables have no code for (a DC difference beyond 11 bits, an AC value beyond 10: no 8-bit picture
+// yields one). Every record the parser produces from 8-bit pictures is accepted: grayscale, 4:4:4, 4:2:2, 4:2:0.
+int emit(const void* record, size_t bytes, uint8_t* out, size_t capacity, size_t* n, char* msg, size_t msg_cap);
+
+}  // namespace jpeg
+}  // namespace gtx

@@ -174,3 +174,185 @@ def decode_dev(ctx: _lib.Context, rec: np.ndarray, h: int, w: int) -> np.ndarray
     finally:
         ctx.dev_free(dst)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- encode
+# The decode run backwards: BGR frame -> the same packed record (host twin of csrc/jpeg_enc.hip), libjpeg's integer definition
+# step by step (jccolor.c, jcsample.c, jcprepct.c, jfdctint.c, jcdctmgr.c, jccoefct.c), so that the record equals the one the
+# parser reads out of the file Pillow / libjpeg-turbo writes for the same pixels. record_to_bytes() is the host emitter
+# (csrc/jpeg_emit.cpp): record -> baseline JFIF bytes.
+
+SUBSAMPLINGS = {"4:4:4": (1, 1, 0), "4:2:0": (2, 2, 2)}            # name -> (hs, vs, the C ABI's number: libjpeg-turbo's TJSAMP)
+# ITU T.81 Annex K.1 / K.2, natural (row-major) order
+STD_LUMA_QUANT = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+                           18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99])
+STD_CHROMA_QUANT = np.array([17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99]
+                            + [99] * 32)
+
+
+def quality_tables(quality: int) -> np.ndarray:
+    """jpeg_set_quality(quality, force_baseline): jpeg_quality_scaling applied to the Annex K tables, clamped to 1..255.
+    uint16 [2][64] (luma, chroma), natural order."""
+    q = int(quality)
+    if not 1 <= q <= 100:
+        raise ValueError(f"JPEG quality {quality} is outside 1..100")
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return np.stack([np.clip((t * scale + 50) // 100, 1, 255) for t in (STD_LUMA_QUANT, STD_CHROMA_QUANT)]).astype(np.uint16)
+
+
+def bgr_to_planes(bgr: np.ndarray, subsampling: str = "4:2:0") -> tuple[dict, list[np.ndarray]]:
+    """Stage 1 (jpeg_planes_kernel): jccolor.c's RGB -> YCbCr at 16 fixed-point bits, edge replication, jcsample.c's h2v2
+    downsampling. Returns the record's geometry and the u8 planes Y, Cb, Cr at their padded block-grid sizes.
+
+    Edges as libjpeg pads them: columns repeat the last pixel (expand_right_edge) and input rows repeat the last row up to an
+    even count before the chroma is formed; the rows below that repeat the last *downsampled* row (jcprepct.c pads its output)."""
+    if subsampling not in SUBSAMPLINGS:
+        raise ValueError(f"JPEG subsampling {subsampling!r}: one of {sorted(SUBSAMPLINGS)}")
+    a = np.asarray(bgr)
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+        raise ValueError(f"expected an [h, w, 3] uint8 frame, got {a.dtype} {a.shape}")
+    h, w = a.shape[:2]
+    if not (1 <= h <= 16384 and 1 <= w <= 16384):
+        raise ValueError(f"a {w} x {h} frame is outside 1..16384")
+    hs, vs, _ = SUBSAMPLINGS[subsampling]
+    mcus_x, mcus_y = -(-w // (8 * hs)), -(-h // (8 * vs))
+    f = dict(w=w, h=h, ncomp=3, hs=hs, vs=vs, mcus_x=mcus_x, mcus_y=mcus_y, n_blocks=mcus_x * mcus_y * (hs * vs + 2),
+             bw=[mcus_x * hs, mcus_x, mcus_x], bh=[mcus_y * vs, mcus_y, mcus_y])
+    b, g, r = (a[..., k].astype(np.int32) for k in range(3))
+    half = 1 << 15
+    y = (19595 * r + 38470 * g + 7471 * b + half) >> 16
+    off = (128 << 16) + half - 1                                   # CBCR_OFFSET + ONE_HALF - 1
+    cb = (-11059 * r - 21709 * g + 32768 * b + off) >> 16
+    cr = (32768 * r - 27439 * g - 5329 * b + off) >> 16
+
+    def pad(p, ph, pw):                                            # replicate the last column, then the last row
+        return np.pad(p, ((0, ph - p.shape[0]), (0, pw - p.shape[1])), mode="edge")
+
+    planes = [pad(y, 8 * f["bh"][0], 8 * f["bw"][0])]
+    for c in (cb, cr):
+        if hs == 2:                                                # h2v2_downsample: 2x2 box, bias 1, 2, 1, 2, ... along a row
+            c = pad(c, h + (h & 1), 16 * mcus_x)
+            bias = 1 + (np.arange(c.shape[1] // 2) & 1)
+            c = (c[0::2, 0::2] + c[0::2, 1::2] + c[1::2, 0::2] + c[1::2, 1::2] + bias[None, :]) >> 2
+        planes.append(pad(c, 8 * mcus_y, 8 * mcus_x))
+    return f, [p.astype(np.uint8) for p in planes]
+
+
+def _fdct8(x: np.ndarray, first: bool) -> np.ndarray:
+    """jfdctint.c's 1-D pass over the last axis (8 long) of an int32 array. first: the row pass (results scaled up by
+    2^PASS1_BITS), else the column pass (PASS1_BITS removed again; the output stays scaled by 8)."""
+    d = [x[..., k] for k in range(8)]
+    tmp0, tmp7, tmp1, tmp6 = d[0] + d[7], d[0] - d[7], d[1] + d[6], d[1] - d[6]
+    tmp2, tmp5, tmp3, tmp4 = d[2] + d[5], d[2] - d[5], d[3] + d[4], d[3] - d[4]
+    tmp10, tmp13, tmp11, tmp12 = tmp0 + tmp3, tmp0 - tmp3, tmp1 + tmp2, tmp1 - tmp2
+    sh = 11 if first else 15                                       # CONST_BITS -/+ PASS1_BITS
+    rnd = np.int32(1 << (sh - 1))
+    o = [None] * 8
+    if first:
+        o[0], o[4] = (tmp10 + tmp11) << 2, (tmp10 - tmp11) << 2
+    else:
+        o[0], o[4] = (tmp10 + tmp11 + 2) >> 2, (tmp10 - tmp11 + 2) >> 2
+    z1 = (tmp12 + tmp13) * np.int32(4433)
+    o[2] = (z1 + tmp13 * np.int32(6270) + rnd) >> sh
+    o[6] = (z1 + tmp12 * np.int32(-15137) + rnd) >> sh
+    z1, z2, z3, z4 = tmp4 + tmp7, tmp5 + tmp6, tmp4 + tmp6, tmp5 + tmp7
+    z5 = (z3 + z4) * np.int32(9633)
+    tmp4, tmp5, tmp6, tmp7 = tmp4 * np.int32(2446), tmp5 * np.int32(16819), tmp6 * np.int32(25172), tmp7 * np.int32(12299)
+    z1, z2, z3, z4 = z1 * np.int32(-7373), z2 * np.int32(-20995), z3 * np.int32(-16069), z4 * np.int32(-3196)
+    z3, z4 = z3 + z5, z4 + z5
+    o[7], o[5] = (tmp4 + z1 + z3 + rnd) >> sh, (tmp5 + z2 + z4 + rnd) >> sh
+    o[3], o[1] = (tmp6 + z2 + z3 + rnd) >> sh, (tmp7 + z1 + z4 + rnd) >> sh
+    return np.stack(o, -1)
+
+
+def _quantised_blocks(plane: np.ndarray, quant: np.ndarray) -> np.ndarray:
+    """Every 8x8 block of a padded plane: -128, forward DCT, jcdctmgr.c's quantisation -> int32 [bh][bw][64], natural order."""
+    bh, bw = plane.shape[0] // 8, plane.shape[1] // 8
+    x = plane.reshape(bh, 8, bw, 8).transpose(0, 2, 1, 3).astype(np.int32) - 128
+    x = _fdct8(x, True)                                            # rows
+    x = _fdct8(x.transpose(0, 1, 3, 2), False).transpose(0, 1, 3, 2)   # columns
+    x = x.reshape(bh, bw, 64)
+    div = quant.astype(np.int32)[None, None, :] << 3              # the DCT's output is scaled by 8
+    mag = (np.abs(x) + (div >> 1)) // div                          # truncating division of the magnitude: rounds half away from zero
+    return np.where(x < 0, -mag, mag).astype(np.int32)
+
+
+def planes_to_record(f: dict, planes: list[np.ndarray], quality: int = 90) -> np.ndarray:
+    """Stages 2-4 (jpeg_fdct_kernel, the prefix sum, the compaction): planes -> record. Blocks past a component's own block grid
+    (ceil(w / 8) x ceil(h / 8) of its samples) that only fill up an MCU are jccoefct.c's dummy blocks: no AC, the DC of the
+    block before them in the MCU (right edge: the last real block of the row; bottom row: the last block of the MCU's row above)."""
+    qt = quality_tables(quality)
+    quant = np.stack([qt[0], qt[1], qt[1]])
+    hs, vs, mcus_x, mcus_y = f["hs"], f["vs"], f["mcus_x"], f["mcus_y"]
+    comps = [_quantised_blocks(planes[c], quant[c]) for c in range(3)]
+    rbw, rbh = -(-f["w"] // 8), -(-f["h"] // 8)                    # luma's own block grid
+    lum = comps[0]
+    if rbw < f["bw"][0]:                                           # hs == 2 and an odd count: the MCU's second column is dummy
+        lum[:, rbw:, :] = 0
+        lum[:, rbw:, 0] = lum[:, rbw - 1:rbw, 0]
+    if rbh < f["bh"][0]:                                           # the MCU's second row is dummy: DC of the last block of its first row
+        lum[rbh:, :, :] = 0
+        src = lum[rbh - 1, :, 0].reshape(mcus_x, hs)[:, hs - 1]
+        lum[rbh, :, 0] = np.repeat(src, hs)
+    # scan order: MCU by MCU, hs x vs luma blocks row by row, Cb, Cr
+    mcu_l = lum.reshape(mcus_y, vs, mcus_x, hs, 64).transpose(0, 2, 1, 3, 4).reshape(mcus_y, mcus_x, hs * vs, 64)
+    blocks = np.concatenate([mcu_l, comps[1][:, :, None, :], comps[2][:, :, None, :]], 2).reshape(-1, 64)
+    zz = blocks[:, NATURAL]
+    nz = zz != 0
+    lens = np.where(nz.any(1), 64 - np.argmax(nz[:, ::-1], 1), 0)
+    nb = len(lens)
+    offsets = np.zeros(nb + 1, np.uint32)
+    np.cumsum(lens, out=offsets[1:])
+    n_coef = int(offsets[-1])
+    total = OFFSETS_OFFSET + 4 * (nb + 1) + 2 * n_coef
+    rec = np.zeros((total + 3) // 4, np.uint32).view(np.uint8)[:total]
+    rec[:HEADER_BYTES].view(np.uint32)[:17] = [MAGIC, total, f["w"], f["h"], 3, hs, vs, mcus_x, mcus_y, nb, n_coef, *f["bw"], *f["bh"]]
+    rec[QUANT_OFFSET:OFFSETS_OFFSET].view(np.uint16)[:] = quant.ravel()
+    end = OFFSETS_OFFSET + 4 * (nb + 1)
+    rec[OFFSETS_OFFSET:end].view(np.uint32)[:] = offsets
+    rec[end:].view(np.int16)[:] = zz[np.arange(64)[None, :] < lens[:, None]]
+    return rec
+
+
+def bgr_to_record(bgr: np.ndarray, quality: int = 90, subsampling: str = "4:2:0") -> np.ndarray:
+    """One BGR u8 [h][w][3] frame -> the record libjpeg writes for it at this quality (its default tables and integer DCT),
+    the bytes the GPU encoder produces (gtx_jpeg_enc_*)."""
+    quality_tables(quality)                                        # refuses the quality before any work
+    return planes_to_record(*bgr_to_planes(bgr, subsampling), quality)
+
+
+def record_to_bytes(rec: np.ndarray) -> bytes:
+    """Record -> baseline JFIF JPEG (gtx_jpeg_emit: SOI, APP0, DQT, SOF0, the Annex K.3 DHT, SOS, the Huffman-coded scan, EOI).
+    Host only; the call releases the GIL."""
+    lib = _lib.load()
+    r = np.ascontiguousarray(rec, dtype=np.uint8)
+    if r.ctypes.data & 3:
+        r = np.concatenate([r, np.zeros(3, np.uint8)]).view(np.uint8)      # (a fresh allocation is aligned)
+        r = r[:len(rec)]
+    n = C.c_size_t()
+    out = np.empty(r.nbytes + 1024, np.uint8)
+    rc = lib.gtx_jpeg_emit(_lib.ptr(r), r.nbytes, _lib.ptr(out), out.nbytes, C.byref(n))
+    if rc == 1:
+        out = np.empty(n.value, np.uint8)
+        rc = lib.gtx_jpeg_emit(_lib.ptr(r), r.nbytes, _lib.ptr(out), out.nbytes, C.byref(n))
+    if rc != 0:
+        raise JpegError(rc, lib.gtx_last_error().decode("utf-8", "replace"))
+    return out[:n.value].tobytes()
+
+
+def encode_dev(ctx: _lib.Context, bgr: np.ndarray, quality: int = 90, subsampling: str = "4:2:0") -> np.ndarray:
+    """One host frame through gtx_op_jpeg_encode (upload, the encoder's launches, the record at its real length): tests, tools."""
+    a = np.ascontiguousarray(bgr, dtype=np.uint8)
+    h, w = a.shape[:2]
+    if subsampling not in SUBSAMPLINGS:
+        raise ValueError(f"JPEG subsampling {subsampling!r}: one of {sorted(SUBSAMPLINGS)}")
+    lib = ctx.lib
+    n = C.c_size_t()
+    rec = np.zeros(1 << 16, np.uint32).view(np.uint8)
+    for _ in range(2):
+        rc = lib.gtx_op_jpeg_encode(ctx.handle, _lib.ptr(a), h, w, int(quality), SUBSAMPLINGS[subsampling][2], _lib.ptr(rec), rec.nbytes, C.byref(n))
+        if rc != 1:
+            break
+        rec = np.zeros((n.value + 3) // 4, np.uint32).view(np.uint8)
+    _lib.check(rc)
+    return rec[:n.value]

@@ -66,7 +66,9 @@ extern "C" {
  *     gtx_register_images fail (GTX_ERR_UNSUPPORTED) when a stage finds more candidates or keypoints than its list holds, instead of
  *     going on with whichever of them found room. gtx_sift_stab_* (stabilo's sift / rsift stabilizer as a stream-ordered chain on the
  *     detector's gray image) and gtx_op_sift_select (its selection / finalisation / mask kernels on host arrays) added: new entry points
- *     and a struct of their own only, no existing struct or signature changed, so the number stays. */
+ *     and a struct of their own only, no existing struct or signature changed, so the number stays. gtx_jpeg_enc_{create, destroy,
+ *     submit_dev, collect, last_ms}, gtx_jpeg_emit and gtx_op_jpeg_encode (the JPEG frame sink: BGR in HBM -> record -> baseline JPEG)
+ *     added: new entry points and an opaque handle only, so the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -213,6 +215,40 @@ int gtx_jpeg_kernel_ms(gtx_ctx* ctx, const void* record, size_t bytes, int h, in
  * compressed frame of any length. */
 int gtx_feeder_open_jpeg(gtx_feeder* f, const char* const* paths, int n_paths, const int32_t* file_index, const int64_t* offsets,
                          const int64_t* lengths, int64_t n_frames, int n_threads);
+
+/* JPEG frame sink: cv2.VideoWriter.write() (geotrax/visualize.py:298) for Motion-JPEG output, the decode above run backwards.
+ * The GPU turns a packed BGR frame in HBM into the same packed record (csrc/jpeg_parse.hpp) with libjpeg's default integer
+ * arithmetic (jccolor.c's 16-bit tables, h2v2 downsampling with its alternating bias, the slow-integer forward DCT, jcdctmgr.c's
+ * divide, the Annex K quantisation tables scaled by jpeg_quality_scaling): the coefficients Pillow / cv2.imwrite write for the
+ * same pixels. The host Huffman-codes the record with the Annex K.3 tables into a baseline JFIF file. */
+typedef struct gtx_jpeg_enc gtx_jpeg_enc;
+/* Replaces cv2.VideoWriter(...), visualize.py:131 (its encoder state): one encoder for h x w frames at `quality` (1..100, libjpeg's
+ * scale) and `subsampling` (0 = 4:4:4, 2 = 4:2:0: libjpeg-turbo's numbers). A size outside 1..16384, another quality or
+ * subsampling is GTX_ERR_INVALID before anything is allocated or launched. */
+int gtx_jpeg_enc_create(gtx_ctx* ctx, int h, int w, int quality, int subsampling, gtx_jpeg_enc** out);
+void gtx_jpeg_enc_destroy(gtx_jpeg_enc* enc);
+/* Replaces cv2.VideoWriter.write(), visualize.py:298 (the pixel half): enqueues colour conversion + downsampling, forward DCT +
+ * quantisation, the prefix sum of the block lengths and the compaction for the BGR u8 [h][w][3] frame at bgr_dptr on the
+ * context's stream and returns without waiting. The frame is read on that stream: whatever overwrites it must be ordered behind
+ * this call there. One frame per encoder may be in flight (GTX_ERR_INVALID otherwise): keep a ring of encoders to overlap. */
+int gtx_jpeg_enc_submit_dev(gtx_jpeg_enc* enc, const void* bgr_dptr);
+/* Replaces cv2.VideoWriter.write(), visualize.py:298 (the hand-over to the host): waits for the submitted frame, reads the closing
+ * offset and copies the record at its real length into record[0, capacity) (4-byte aligned). *bytes receives that length.
+ * Returns 0 (record filled), 1 (capacity < *bytes: nothing was copied, the frame stays collectable) or a negative status. */
+int gtx_jpeg_enc_collect(gtx_jpeg_enc* enc, void* record, size_t capacity, size_t* bytes);
+/* Timing of what replaces cv2.VideoWriter.write(), visualize.py:298: milliseconds of the launches of the frame collected last
+ * (two events around the chain). tools/jpeg_encode_time.py. */
+int gtx_jpeg_enc_last_ms(gtx_jpeg_enc* enc, float* ms);
+/* Replaces cv2.VideoWriter.write(), visualize.py:298 (the entropy-coding half; host only, no context): record[0, bytes) (4-byte
+ * aligned, from gtx_jpeg_enc_collect or gtx_jpeg_parse: grayscale, 4:4:4, 4:2:2 or 4:2:0) -> a baseline JFIF file in
+ * out[0, capacity): SOI, APP0, DQT, SOF0, DHT (Annex K.3), SOS, the scan, EOI. The record is checked first (a damaged one, a
+ * quantiser above 255 or a coefficient the Annex K.3 tables cannot code is GTX_ERR_INVALID). *n receives the file's size.
+ * Returns 0 (written), 1 (capacity < *n: nothing outside out[0, capacity) was touched) or a negative status. */
+int gtx_jpeg_emit(const void* record, size_t bytes, void* out, size_t capacity, size_t* n);
+/* Replaces cv2.VideoWriter.write(), visualize.py:298, on host arrays (the operator hook the kernel tests use): uploads the BGR
+ * frame, runs one encoder's chain and returns the record as gtx_jpeg_enc_collect does (0, 1 or a negative status). Sizes,
+ * quality and subsampling are checked before the GPU is touched. */
+int gtx_op_jpeg_encode(gtx_ctx* ctx, const uint8_t* bgr, int h, int w, int quality, int subsampling, void* record, size_t capacity, size_t* bytes);
 
 /* ------------------------------------------------------------------ operator level
  * Single operators of the detector, exposed so the parity tests can check every kernel
