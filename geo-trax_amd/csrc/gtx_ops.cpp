@@ -1124,6 +1124,15 @@ int gtx_op_estimate_affine_partial(const float* p_xy, const float* q_xy, int n, 
     *valid = gtx::estimate_affine_partial(p_xy, q_xy, n, seed, A, n_inliers) ? 1 : 0;
   });
 }
+
+// The inverse gtx_warp_frame[_dev] hands its kernel (tests/test_warp_ops_gpu.py feeds the oracle the same matrix). Host only.
+int gtx_op_invert3x3(const double H[9], double inv[9]) {
+  return guarded([&] {
+    need(H, "H"); need(inv, "inv");
+    if (!gtx::invert3x3(H, inv)) gtx::fail(GTX_ERR_INVALID, "invert3x3: the matrix is singular or not finite");
+  });
+}
+
 int gtx_op_georef_points(gtx_ctx* ctx, const gtx_georef_chain* chain, const double* x, const double* y, int n,
                          double* ortho_x, double* ortho_y, double* lat, double* lon, double* east, double* north) {
   return guarded([&] {

@@ -26,6 +26,15 @@ def warp_perspective(frame: np.ndarray, H: np.ndarray, ctx: _lib.Context | None 
     return out
 
 
+def inverse_homography(H: np.ndarray) -> np.ndarray:
+    """The destination -> source matrix the warp kernel is given for H (gtx_op_invert3x3: host arithmetic, no context);
+    GtxError for a singular or non-finite H."""
+    Hm = np.ascontiguousarray(H, dtype=np.float64).reshape(9)
+    inv = np.empty(9, np.float64)
+    check(_lib.load().gtx_op_invert3x3(ptr(Hm), ptr(inv)))
+    return inv.reshape(3, 3)
+
+
 class FrameWarper:
     """Warps a stream of equally sized frames through two persistent HBM buffers (one upload, one kernel, one
     download per frame; the visualisation loop's shape). `warp_dev` works on device pointers only."""

@@ -68,7 +68,8 @@ extern "C" {
  *     detector's gray image) and gtx_op_sift_select (its selection / finalisation / mask kernels on host arrays) added: new entry points
  *     and a struct of their own only, no existing struct or signature changed, so the number stays. gtx_jpeg_enc_{create, destroy,
  *     submit_dev, collect, last_ms}, gtx_jpeg_emit and gtx_op_jpeg_encode (the JPEG frame sink: BGR in HBM -> record -> baseline JPEG)
- *     added: new entry points and an opaque handle only, so the number stays. */
+ *     added: new entry points and an opaque handle only, so the number stays. gtx_op_invert3x3 (the inverse the frame warp uses, on
+ *     the host) added: the same, the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -1040,6 +1041,10 @@ int gtx_warp_frame(gtx_ctx* ctx, const uint8_t* src_bgr, int h, int w, const dou
 /* Same, both images resident in HBM (dptrs from gtx_dev_alloc, distinct buffers); enqueued on the
  * context's stream, returns without waiting (gtx_ctx_synchronize / a later call on the stream orders it). */
 int gtx_warp_frame_dev(gtx_ctx* ctx, const void* src_dptr, int h, int w, const double H[9], void* dst_dptr);
+/* The inverse of H that the two calls above hand their kernel (the adjugate over the determinant, f64), row-major. Host arithmetic,
+ * no context and no device. GTX_ERR_INVALID, with inv left as it was, when the determinant is zero or not finite -- the
+ * matrices gtx_warp_frame refuses as singular. */
+int gtx_op_invert3x3(const double H[9], double inv[9]);
 
 /* ------------------------------------------------------------------ result files (host code, no GPU work)
  *

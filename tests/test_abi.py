@@ -405,6 +405,19 @@ def test_sift_hooks_refuse_bad_sizes_before_any_launch():
     assert describe(root=2) == -1 and b"root" in lib.gtx_last_error()
 
 
+def test_invert3x3_hook_needs_no_context_and_refuses_null_and_singular():
+    """Host only: gtx_op_invert3x3 takes no context; NULL arrays and a singular matrix come back as -1 with a message."""
+    from geotrax_amd import _lib
+
+    lib = _lib.load()
+    H, inv = np.array([1.0, 0, 5, 0, 2, -3, 0, 0, 1]), np.zeros(9)
+    assert lib.gtx_op_invert3x3(_lib.ptr(H), _lib.ptr(inv)) == 0
+    np.testing.assert_array_equal(inv, [1, 0, -5, 0, 0.5, 1.5, 0, 0, 1])
+    assert lib.gtx_op_invert3x3(None, _lib.ptr(inv)) == -1 and b"H is NULL" in lib.gtx_last_error()
+    assert lib.gtx_op_invert3x3(_lib.ptr(H), None) == -1 and b"inv is NULL" in lib.gtx_last_error()
+    assert lib.gtx_op_invert3x3(_lib.ptr(np.zeros(9)), _lib.ptr(inv)) == -1 and b"singular" in lib.gtx_last_error()
+
+
 def test_no_gpu_means_loud_failure_not_fallback():
     """Without a GPU the compute entry points must fail with a message; nothing falls back to CPU."""
     from geotrax_amd import _lib

@@ -103,3 +103,71 @@ def test_estimate_affine_partial_equals_the_oracle_and_recovers_a_similarity():
             assert np.abs(got - M).max() < 0.2 and inl > 0.6 * n
     got, inl = estimate_affine_partial(np.zeros((1, 2), np.float32), np.zeros((1, 2), np.float32))
     assert got is None and inl == 0
+
+
+def _adjugate_inverse_longdouble(H):
+    m = np.asarray(H, np.longdouble).ravel()
+    a, b, c, d, e, f, g, h, i = m
+    adj = np.array([e * i - f * h, -(b * i - c * h), b * f - c * e,
+                    -(d * i - f * g), a * i - c * g, -(a * f - c * d),
+                    d * h - e * g, -(a * h - b * g), a * e - b * d], np.longdouble)
+    return (adj / (a * adj[0] + b * adj[3] + c * adj[6])).reshape(3, 3)
+
+
+def _camera_like(rng):
+    """Rotation up to half a radian, zoom 0.5 .. 2 with 5 % anisotropy, a shift of up to 2000 px, perspective terms up to 1e-4."""
+    a, s = rng.uniform(-0.5, 0.5), np.exp(rng.uniform(-0.7, 0.7))
+    return np.array([[s * np.cos(a) * rng.uniform(0.95, 1.05), -s * np.sin(a), rng.uniform(-2000, 2000)],
+                     [s * np.sin(a), s * np.cos(a) * rng.uniform(0.95, 1.05), rng.uniform(-2000, 2000)],
+                     [rng.uniform(-1e-4, 1e-4), rng.uniform(-1e-4, 1e-4), 1.0]])
+
+
+def test_invert3x3_hook_against_a_longdouble_adjugate():
+    """gtx_op_invert3x3 (the inverse gtx_warp_frame hands its kernel) over every matrix of tests/test_warp_ops_gpu.py and 200 seeded
+    camera-like ones, against the adjugate formula evaluated in np.longdouble: |inv - ref| <= 16 eps cond_inf(H) max|ref|, elementwise.
+    A matrix is kept only if the reference itself is known to sit well inside that bound: its error is at most
+    |ref|_inf |I - H ref|_inf (from H^-1 - ref = H^-1 (I - H ref)), the residual taken in longdouble; where that estimate exceeds
+    1/8 of the bound (a platform whose longdouble is float64) the matrix is dropped and named in the output."""
+    import warp_cases as wc
+
+    eps = np.finfo(np.float64).eps
+    rng = np.random.default_rng(2024)
+    mats = dict(wc.issue_matrices())
+    mats.update({f"camera-like-{k}": _camera_like(rng) for k in range(200)})
+    worst, worst_name, dropped = 0.0, None, []
+    for name, H in mats.items():
+        ref = _adjugate_inverse_longdouble(H)
+        Hl = np.asarray(H, np.longdouble)
+        norm = lambda m: np.abs(m).sum(1).max()
+        bound = 16 * eps * float(norm(Hl) * norm(ref)) * float(np.abs(ref).max())
+        ref_err = float(norm(ref) * norm(np.eye(3, dtype=np.longdouble) - Hl @ ref))
+        if not ref_err <= bound / 8:
+            dropped.append(name)
+            continue
+        got = wc.hook_inverse(H)
+        ratio = float(np.abs(got.astype(np.longdouble) - ref).max()) / bound
+        if ratio > worst:
+            worst, worst_name = ratio, name
+        assert ratio <= 1.0, (name, ratio)
+    print(f"gtx_op_invert3x3: {len(mats) - len(dropped)} matrices, largest |inv - ref| / bound = {worst:.3g} ({worst_name}); "
+          f"dropped because the reference could not be held: {dropped or 'none'}")
+    assert len(dropped) == 0 or np.finfo(np.longdouble).eps >= eps / 2
+
+
+def test_invert3x3_hook_refuses_singular_and_non_finite_matrices():
+    """Singular, NaN and Inf matrices: -1, and the output array is left as it was."""
+    from geotrax_amd import _lib
+
+    lib = _lib.load()
+    bad = {"zero": np.zeros((3, 3)), "equal rows": np.array([[1.0, 2, 3], [1, 2, 3], [4, 5, 6]]),
+           "rank 2": np.array([[1.0, 2, 3], [4, 5, 6], [7, 8, 9]]), "zero column": np.array([[1.0, 0, 3], [4, 0, 6], [7, 0, 10]]),
+           "nan": np.array([[1.0, 0, 0], [0, np.nan, 0], [0, 0, 1]]), "inf": np.array([[1.0, 0, np.inf], [0, 1, 0], [0, 0, 1]]),
+           "-inf": np.array([[-np.inf, 0, 0], [0, 1, 0], [0, 0, 1]]), "overflowing determinant": np.diag([1e200, 1e200, 1e200])}
+    for name, H in bad.items():
+        inv = np.full(9, 7.0)
+        assert lib.gtx_op_invert3x3(_lib.ptr(np.ascontiguousarray(H.ravel())), _lib.ptr(inv)) == -1, name
+        assert b"singular" in lib.gtx_last_error(), name
+        np.testing.assert_array_equal(inv, np.full(9, 7.0), err_msg=name)
+    inv = np.full(9, 7.0)
+    assert lib.gtx_op_invert3x3(_lib.ptr(np.diag([2.0, 4.0, 8.0]).ravel()), _lib.ptr(inv)) == 0
+    np.testing.assert_array_equal(inv.reshape(3, 3), np.diag([0.5, 0.25, 0.125]))

@@ -131,11 +131,13 @@ def test_writer_keeps_the_order_through_its_ring_and_pool(gtx_ctx, tmp_path):
 
 def test_stabilized_video_stage(gtx_ctx, tmp_path):
     """An 8-frame 256x144 .y4m and a transforms file that leaves frame 3 out: every picture of the output is the emitter's bytes for
-    the twin's record of the warped frame, frame 3's of the frame as it is."""
+    the twin's record of the warped frame, frame 3's of the frame as it is. The warped frame is the oracle's (oracle/warp_ref.py on
+    the matrix as the transforms file holds it, with the library's own inverse), not the warp kernel's."""
     from geotrax_amd import jpeg, stabilized_video
     from geotrax_amd.frames import AviMjpegReader, Y4mReader, write_y4m
     from geotrax_amd.synth import make_scene
-    from geotrax_amd.warp import warp_perspective
+    from geotrax_amd.warp import inverse_homography, warp_perspective
+    from oracle.warp_ref import warp_perspective as warp_ref
 
     w, h = 256, 144
     scene = make_scene(seed=1, h=h, w=w)
@@ -148,12 +150,18 @@ def test_stabilized_video_stage(gtx_ctx, tmp_path):
     Hs = {i: np.array([[1 + 0.004 * i, 0.002 * i, 1.5 * i], [-0.003 * i, 1 - 0.002 * i, -0.75 * i], [1e-6 * i, -2e-6 * i, 1.0]]) for i in range(8) if i != 3}
     (tmp_path / "results").mkdir()
     np.savetxt(tmp_path / "results" / "clip_vid_transf.txt", np.array([[i, *H.ravel()] for i, H in Hs.items()]), fmt="%.16g", delimiter=",")
+    on_file = {int(r[0]): r[1:].reshape(3, 3) for r in np.loadtxt(tmp_path / "results" / "clip_vid_transf.txt", delimiter=",")}
+    assert sorted(on_file) == sorted(Hs) and all(np.allclose(on_file[i], Hs[i], rtol=1e-15, atol=0) for i in Hs)
+    warped = {i: warp_ref(frames[i], on_file[i], M_inv=inverse_homography(on_file[i])) for i in Hs}
+    for i in (1, 7):                                                 # (and the kernel on its own agrees, so a difference below is the stage's)
+        np.testing.assert_array_equal(warp_perspective(frames[i], on_file[i], gtx_ctx), warped[i])
+        assert (warped[i] != frames[i]).any()
     assert stabilized_video.main([str(clip), "--quality", "85"]) == 0
     out = tmp_path / "results" / "clip_mode_1.avi"
     got = AviMjpegReader(out)
     assert got.frame_count == 8 and got.frame_hw == (h, w)
     for i, f in enumerate(frames):
-        src = warp_perspective(f, Hs[i], gtx_ctx) if i in Hs else f
+        src = warped[i] if i in Hs else f
         assert got._bytes(i) == jpeg.record_to_bytes(jpeg.bgr_to_record(src, 85)), f"frame {i}"
     got.release()
     # the frame range: cut_frame_left .. cut_frame_right - 1, numbered as in the clip
@@ -163,6 +171,6 @@ def test_stabilized_video_stage(gtx_ctx, tmp_path):
     cut = MjpegReader(tmp_path / "cut.mjpeg")
     assert cut.frame_count == 3
     for k, i in enumerate((2, 3, 4)):
-        src = warp_perspective(frames[i], Hs[i], gtx_ctx) if i in Hs else frames[i]
+        src = warped[i] if i in Hs else frames[i]
         assert cut._bytes(k) == jpeg.record_to_bytes(jpeg.bgr_to_record(src, 90)), f"frame {i}"
     cut.release()

@@ -26,7 +26,7 @@ def _camera(seed, w, h, strength=1.0):
 
 @pytest.mark.parametrize("case", ["golden-envelope", "strong", "zoom-out-rotate"])
 def test_warp_4k_matches_oracle(gtx_ctx, case):
-    from geotrax_amd.warp import warp_perspective
+    from geotrax_amd.warp import inverse_homography, warp_perspective
     from oracle.warp_ref import warp_perspective as ref
 
     rng = np.random.default_rng(3)
@@ -40,6 +40,7 @@ def test_warp_4k_matches_oracle(gtx_ctx, case):
         T = np.array([[1, 0, W4 / 2], [0, 1, H4 / 2], [0, 0, 1.0]])
         Hm = T @ np.array([[z * c, -z * s, 0], [z * s, z * c, 0], [2e-6, -1e-6, 1.0]]) @ np.linalg.inv(T)
     got = warp_perspective(f, Hm, ctx=gtx_ctx)
+    np.testing.assert_array_equal(got, ref(f, Hm, M_inv=inverse_homography(Hm)))     # the oracle on the library's own inverse: every pixel
     want = ref(f, Hm)
     diff = got.astype(np.int16) - want.astype(np.int16)
     # the two inverses of H (library: adjugate; oracle: LAPACK) agree to ~1e-16: a handful of coordinates in 16.6 M may fall on the other side of a 1/32 px rounding boundary
