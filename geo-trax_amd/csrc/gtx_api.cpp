@@ -11,6 +11,7 @@
 #include "api_guard.hpp"
 #include "common.hpp"
 #include "detector.hpp"
+#include "draw.hpp"
 #include "rtdetr.hpp"
 #include "geometry.hpp"
 #include "ecc.hpp"
@@ -160,6 +161,13 @@ int gtx_dev_upload(gtx_ctx* ctx, void* dptr, const void* host, size_t bytes) {
     GTX_HIP(hipSetDevice(ctx->device));
     GTX_HIP(hipMemcpyAsync(dptr, host, bytes, hipMemcpyHostToDevice, ctx->stream));
     GTX_HIP(hipStreamSynchronize(ctx->stream));
+  });
+}
+int gtx_dev_copy(gtx_ctx* ctx, void* dst_dptr, const void* src_dptr, size_t bytes) {
+  return guarded([&] {
+    need(ctx, "ctx"); need(dst_dptr, "dst"); need(src_dptr, "src");
+    GTX_HIP(hipSetDevice(ctx->device));
+    if (bytes) GTX_HIP(hipMemcpyAsync(dst_dptr, src_dptr, bytes, hipMemcpyDeviceToDevice, ctx->stream));
   });
 }
 int gtx_dev_download(gtx_ctx* ctx, void* host, const void* dptr, size_t bytes) {
@@ -842,6 +850,34 @@ int gtx_jpeg_emit(const void* record, size_t bytes, void* out, size_t capacity, 
     if (rc < 0) gtx::fail(rc, "%s", msg);
   });
   return st != GTX_OK ? st : rc;
+}
+
+int gtx_drawer_create(gtx_ctx* ctx, int h, int w, int max_prims, const void* atlas, size_t atlas_bytes, gtx_drawer** out) {
+  return guarded([&] {
+    need(out, "out");
+    *out = nullptr;
+    gtx::Drawer::check_args(h, w, max_prims, atlas, atlas_bytes);
+    need(ctx, "ctx");
+    std::unique_ptr<gtx_drawer> d(new gtx_drawer);
+    d->impl.reset(new gtx::Drawer(ctx, h, w, max_prims, atlas, atlas_bytes));
+    *out = d.release();
+  });
+}
+
+void gtx_drawer_destroy(gtx_drawer* drawer) { delete drawer; }
+
+int gtx_drawer_draw_dev(gtx_drawer* drawer, void* frame_dptr, const int32_t* prims, int n) {
+  return guarded([&] {
+    need(drawer, "drawer");
+    drawer->impl->draw(frame_dptr, prims, n);
+  });
+}
+
+int gtx_drawer_last_ms(gtx_drawer* drawer, float* ms) {
+  return guarded([&] {
+    need(drawer, "drawer"); need(ms, "ms");
+    *ms = drawer->impl->last_ms();
+  });
 }
 
 int gtx_warp_frame_dev(gtx_ctx* ctx, const void* src_dptr, int h, int w, const double H[9], void* dst_dptr) {

@@ -15,6 +15,7 @@
 #include "conv_igemm.hpp"
 #include "det_kernels.hpp"
 #include "detector.hpp"
+#include "draw.hpp"
 #include "ecc.hpp"
 #include "geometry.hpp"
 #include "gmc.hpp"
@@ -1171,6 +1172,26 @@ int gtx_op_jpeg_encode(gtx_ctx* ctx, const uint8_t* bgr, int h, int w, int quali
     }
   });
   return st != GTX_OK ? st : fits ? 0 : 1;
+}
+
+// ---- the drawing kernel on a host frame (tests/test_draw_ops_gpu.py)
+
+int gtx_op_draw(gtx_ctx* ctx, uint8_t* bgr, int h, int w, const int32_t* prims, int n, const void* atlas, size_t atlas_bytes) {
+  return guarded([&] {
+    gtx::draw_check_frame(h, w);
+    need(bgr, "bgr");
+    if (!atlas && atlas_bytes) op_bad("draw", "atlas is NULL with a size");
+    gtx::draw_check_prims(prims, n, gtx::kDrawMaxPrims, atlas_bytes);
+    gtx::Drawer::check_args(h, w, n > 0 ? n : 1, atlas, atlas_bytes);
+    need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    gtx::DevBuf d_bgr;
+    upload(d_bgr, bgr, (size_t)h * w * 3);
+    gtx::Drawer drawer(ctx, h, w, n > 0 ? n : 1, atlas, atlas_bytes);
+    drawer.draw(d_bgr.p, prims, n);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download(bgr, d_bgr, (size_t)h * w * 3);
+  });
 }
 
 }  // extern "C"

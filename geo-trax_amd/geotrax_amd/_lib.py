@@ -294,6 +294,12 @@ _SIGNATURES = {
     "gtx_jpeg_enc_last_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "gtx_jpeg_emit": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "gtx_op_jpeg_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gtx_dev_copy": (C.c_int, [_P, _P, _P, C.c_size_t]),
+    "gtx_drawer_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(_P)]),
+    "gtx_drawer_destroy": (None, [_P]),
+    "gtx_drawer_draw_dev": (C.c_int, [_P, _P, _P, C.c_int]),
+    "gtx_drawer_last_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "gtx_op_draw": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_size_t]),
 }
 
 _lib = None
@@ -368,6 +374,10 @@ class Context:
 
     def dev_upload(self, dptr: int, a: np.ndarray):
         check(self.lib.gtx_dev_upload(self.handle, C.c_void_p(dptr), ptr(a), a.nbytes))
+
+    def dev_copy(self, dst: int, src: int, nbytes: int):
+        """Device to device on the context's stream; does not wait."""
+        check(self.lib.gtx_dev_copy(self.handle, C.c_void_p(dst), C.c_void_p(src), nbytes))
 
     def dev_download(self, a: np.ndarray, dptr: int):
         check(self.lib.gtx_dev_download(self.handle, ptr(a), C.c_void_p(dptr), a.nbytes))

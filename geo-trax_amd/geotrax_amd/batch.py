@@ -147,7 +147,7 @@ def process_file(file: Path, args, logger, out_cfg: dict, run=detect_track_stabi
 
     geo_only, no_geo = bool(getattr(args, "geo_only", False)), bool(getattr(args, "no_geo", False))
     if getattr(args, "viz_only", False) or getattr(args, "plot_only", False):
-        logger.warning(f"'{file}': --viz-only / --plot-only: visualisation and plots are not part of this build; nothing to do.")
+        logger.warning(f"'{file}': --viz-only / --plot-only: visualisation and plots are not part of this build's batch; nothing to do (one clip at a time: python -m geotrax_amd.visualize <clip>).")
         return 'skipped'
     stages = ([] if geo_only else [("extract", ACTION_EXTRACT, run)]) + ([] if no_geo else [("georef", ACTION_GEOREF, run_geo)])
     ran = dry = False

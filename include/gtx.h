@@ -69,7 +69,9 @@ extern "C" {
  *     and a struct of their own only, no existing struct or signature changed, so the number stays. gtx_jpeg_enc_{create, destroy,
  *     submit_dev, collect, last_ms}, gtx_jpeg_emit and gtx_op_jpeg_encode (the JPEG frame sink: BGR in HBM -> record -> baseline JPEG)
  *     added: new entry points and an opaque handle only, so the number stays. gtx_op_invert3x3 (the inverse the frame warp uses, on
- *     the host) added: the same, the number stays. */
+ *     the host) added: the same, the number stays. gtx_drawer_{create, destroy, draw_dev, last_ms}, gtx_op_draw (the visualize stage's
+ *     drawing: a primitive list painted into a frame in HBM) and gtx_dev_copy added: new entry points and an opaque handle only, so the
+ *     number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -126,6 +128,10 @@ int gtx_dev_alloc(gtx_ctx* ctx, size_t bytes, void** dptr);
 int gtx_dev_free(gtx_ctx* ctx, void* dptr);
 int gtx_dev_upload(gtx_ctx* ctx, void* dptr, const void* host, size_t bytes);
 int gtx_dev_download(gtx_ctx* ctx, void* host, const void* dptr, size_t bytes);
+/* Device-to-device copy of `bytes` bytes (both dptrs from gtx_dev_alloc, not overlapping), enqueued on the context's stream; returns
+ * without waiting. Replaces ref_frame.copy() of visualisation mode 2 (visualize.py:277, :292): every frame is drawn on a fresh
+ * copy of the kept reference frame. */
+int gtx_dev_copy(gtx_ctx* ctx, void* dst_dptr, const void* src_dptr, size_t bytes);
 
 /* One planar YUV 4:2:0 (I420) frame in HBM -> packed BGR u8 in HBM: the colour conversion a video decoder applies
  * before extract.py:146 sees the frame (cv2.VideoCapture.read() returns BGR). BT.601 limited range, the fixed-point
@@ -1045,6 +1051,36 @@ int gtx_warp_frame_dev(gtx_ctx* ctx, const void* src_dptr, int h, int w, const d
  * no context and no device. GTX_ERR_INVALID, with inv left as it was, when the determinant is zero or not finite -- the
  * matrices gtx_warp_frame refuses as singular. */
 int gtx_op_invert3x3(const double H[9], double inv[9]);
+
+/* ------------------------------------------------------------------ drawing (for the visualize stage)
+ *
+ * Replaces the cv2 drawing calls of annotate_frame / draw_oriented_box / _draw_dashed_poly (visualize.py:747-783, :807, :934-939):
+ * cv2.rectangle (outline and filled), cv2.line, cv2.polylines, cv2.circle and cv2.putText become one list of primitives that one
+ * kernel paints into the BGR u8 frame [h][w][3] where it lies in HBM. A primitive is eight int32 -- kind, x0, y0, x1, y1, p0, p1,
+ * bgr (b | g << 8 | r << 16) -- kind 0 FILL (corners inclusive), 1 SEGMENT (endpoints, p0 = thickness, anti-aliased, round caps),
+ * 2 RING (centre, x1 = radius, p0 = thickness), 3 GLYPH (cell top-left, x1 y1 = cell size, p0 = byte offset into the coverage
+ * atlas, p1 = row pitch); applied in index order. The pixel rule is specified in geotrax_amd/draw.py, whose numpy twin the kernel
+ * equals byte for byte; its differences from OpenCV's rasteriser are listed in DESIGN.md.
+ *
+ * Every record is checked before anything is launched: kind in 0..3; x0, y0, x1, y1 in [-32768, 32767]; thickness >= 1 (SEGMENT,
+ * RING); radius >= 0; a GLYPH with x1, y1, p1 > 0, p0 >= 0 and p0 + (y1 - 1) p1 + x1 <= atlas_bytes; n <= max_prims. A violation is
+ * GTX_ERR_INVALID with the record's index in the message, and nothing is drawn: no record is ever dropped. */
+typedef struct gtx_drawer gtx_drawer;
+/* A drawer for h x w frames (1..16384 each side) and lists of up to max_prims (1..2^20) primitives. The atlas (atlas_bytes bytes of
+ * coverage, 0..255; NULL with 0 bytes when no GLYPH is drawn) is uploaded once, here. */
+int gtx_drawer_create(gtx_ctx* ctx, int h, int w, int max_prims, const void* atlas, size_t atlas_bytes, gtx_drawer** out);
+/* Waits for the context's stream (a queued upload may still read the pinned ring): destroy a drawer before its context. */
+void gtx_drawer_destroy(gtx_drawer* drawer);
+/* Validates the list, stages it (a ring of four pinned buffers: the call returns before the launch before it has read its list),
+ * enqueues upload and kernel on the context's stream and returns without waiting. prims may be reused at once. n = 0 launches
+ * nothing. frame_dptr: h * w * 3 bytes in HBM, painted in place. */
+int gtx_drawer_draw_dev(gtx_drawer* drawer, void* frame_dptr, const int32_t* prims, int n);
+/* Milliseconds of the last gtx_drawer_draw_dev's launch, between two events (waits for it); 0 when that call launched nothing.
+ * The list's upload, enqueued ahead of the launch on the same stream, is outside the two events. tools/visualize_time.py. */
+int gtx_drawer_last_ms(gtx_drawer* drawer, float* ms);
+/* Operator hook (tests/test_draw_ops_gpu.py): a host frame, painted in place through one drawer. Sizes and records are checked
+ * before the GPU is touched. */
+int gtx_op_draw(gtx_ctx* ctx, uint8_t* bgr, int h, int w, const int32_t* prims, int n, const void* atlas, size_t atlas_bytes);
 
 /* ------------------------------------------------------------------ result files (host code, no GPU work)
  *
