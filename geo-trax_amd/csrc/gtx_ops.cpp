@@ -22,6 +22,7 @@
 #include "jpeg_enc.hpp"
 #include "match_l2.hpp"
 #include "op_staging.hpp"
+#include "pool_down.hpp"
 #include "register.hpp"
 #include "rtdetr_kernels.hpp"
 #include "sift.hpp"
@@ -275,6 +276,37 @@ int gtx_op_dwconv(gtx_ctx* ctx, int dtype, int n, int h, int w, int c, int k, in
     GTX_HIP(hipStreamSynchronize(ctx->stream));
     download_fmt(out, dtype, dy, yb);
     if (saturated) download(saturated, ds, 4);
+  });
+}
+
+int gtx_op_pool_down(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int c_avg, int c_max, const void* x, int in_cstride, int in_coff,
+                     void* avg, int avg_cstride, int avg_coff, void* mx, int max_cstride, int max_coff, int iters, float* ms_per_launch) {
+  return guarded([&] {
+    // every size first: a kernel turns them into addresses
+    if (n_alloc < n || iters < 0) op_bad("pool_down", "bad sizes");
+    if (c_avg % 8 || c_max % 8 || c_avg < 8 || c_max < 0) op_bad("pool_down", "channel counts must be multiples of 8 (c_avg > 0)");
+    char stub = 0;                                      // the shape check wants non-null buffers; none is touched
+    const gtx::RtMap in0{&stub, h, w, in_cstride, in_coff, c_avg + c_max}, avg0{&stub, h, w, avg_cstride, avg_coff, c_avg},
+        mx0{c_max ? &stub : nullptr, h / 2, w / 2, c_max ? max_cstride : 0, c_max ? max_coff : 0, c_max};
+    if (const char* why = gtx::pool_down_refusal(dtype, in0, avg0, mx0, n)) op_bad("pool_down", why);
+    need(x, "x"); need(avg, "avg");
+    if (c_max) need(mx, "max");
+    need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t es = gtx::dtype_size(dtype);
+    const size_t xb = (size_t)n_alloc * h * w * in_cstride * es, ab = (size_t)n_alloc * h * w * avg_cstride * es,
+                 mb = c_max ? (size_t)n_alloc * (h / 2) * (w / 2) * max_cstride * es : 0;
+    gtx::DevBuf dx, da, dm;
+    upload_fmt(dx, dtype, x, xb); upload_fmt(da, dtype, avg, ab);
+    if (c_max) upload_fmt(dm, dtype, mx, mb);
+    const gtx::RtMap in{dx.p, h, w, in_cstride, in_coff, c_avg + c_max}, a{da.p, h, w, avg_cstride, avg_coff, c_avg},
+        m{c_max ? dm.p : nullptr, h / 2, w / 2, c_max ? max_cstride : 0, c_max ? max_coff : 0, c_max};
+    auto once = [&] { gtx::launch_pool_down(dtype, in, a, m, n, ctx->stream); };
+    once();
+    if (iters > 0 && ms_per_launch) *ms_per_launch = time_launches(ctx->stream, iters, once);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download_fmt(avg, dtype, da, ab);
+    if (c_max) download_fmt(mx, dtype, dm, mb);
   });
 }
 

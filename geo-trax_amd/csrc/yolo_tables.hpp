@@ -8,10 +8,11 @@ namespace gtx {
 
 // One row of a trunk's layer table: a layer of the model yaml, as the yaml writes it
 struct TrunkRow {
-  enum Module { CONV, BLOCK, SPPF, C2PSA, UPSAMPLE, CONCAT, DETECT, SCDOWN, PSA };
+  enum Module { CONV, BLOCK, SPPF, C2PSA, UPSAMPLE, CONCAT, DETECT, SCDOWN, PSA, ELAN, ADOWN, SPPELAN };
   int i;            // the layer index: its tensors are "model.<i>.*"
   Module mod;       // CONV: Conv 3x3 stride 2 (row 0: the stem); BLOCK: C2f / C3k2 / C2fCIB (which one, the tensors tell);
-                    // SCDOWN: 1x1 Conv + depthwise 3x3 stride 2 without activation; PSA: C2PSA's one block directly under the layer (yolov10.yaml)
+                    // SCDOWN: 1x1 Conv + depthwise 3x3 stride 2 without activation; PSA: C2PSA's one block directly under the layer (yolov10.yaml);
+                    // ELAN: ELAN1 / RepNCSPELAN4, ADOWN: AConv / ADown (which one, the tensors tell), SPPELAN: SPPF's pools closed by cv5 (yolov9.yaml)
   int from[4];      // the yaml's `from`: -1 = the row above (row 0: the image), else a layer index; 0 ends the list
   bool shortcut;    // BLOCK: the bottlenecks add their input
 };
@@ -90,6 +91,15 @@ inline constexpr R kYolo10[] = {
     {12, R::CONCAT, {-1, 6}, false}, {13, R::BLOCK, {-1}, false},     {14, R::UPSAMPLE, {-1}, false},  {15, R::CONCAT, {-1, 4}, false},
     {16, R::BLOCK, {-1}, false},    {17, R::CONV, {-1}, false},       {18, R::CONCAT, {-1, 13}, false}, {19, R::BLOCK, {-1}, false},
     {20, R::SCDOWN, {-1}, false},   {21, R::CONCAT, {-1, 10}, false}, {22, R::BLOCK, {-1}, true},      {23, R::DETECT, {16, 19, 22}, false}};
+// v9/yolov9{t,s,m,c}.yaml: ELAN1 or RepNCSPELAN4 where the others have C2f, AConv (t / s / m) or ADown (c) where they have the
+// stride-2 Convs, SPPELAN = model.9, YOLOv8's Detect = model.22
+inline constexpr R kYolo9[] = {
+    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::ELAN, {-1}, true},        {3, R::ADOWN, {-1}, false},
+    {4, R::ELAN, {-1}, true},       {5, R::ADOWN, {-1}, false},       {6, R::ELAN, {-1}, true},        {7, R::ADOWN, {-1}, false},
+    {8, R::ELAN, {-1}, true},       {9, R::SPPELAN, {-1}, false},     {10, R::UPSAMPLE, {-1}, false},  {11, R::CONCAT, {-1, 6}, false},
+    {12, R::ELAN, {-1}, true},      {13, R::UPSAMPLE, {-1}, false},   {14, R::CONCAT, {-1, 4}, false}, {15, R::ELAN, {-1}, true},
+    {16, R::ADOWN, {-1}, false},    {17, R::CONCAT, {-1, 12}, false}, {18, R::ELAN, {-1}, true},       {19, R::ADOWN, {-1}, false},
+    {20, R::CONCAT, {-1, 9}, false}, {21, R::ELAN, {-1}, true},       {22, R::DETECT, {15, 18, 21}, false}};
 // yolo11-cls.yaml: model.0-8 are yolo11.yaml's, C2PSA follows them directly (no SPPF) and is the embedded layer; Classify = model.10
 inline constexpr R kYolo11Cls[] = {
     {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},

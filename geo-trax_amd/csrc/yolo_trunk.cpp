@@ -3,9 +3,11 @@
 // decoder there; rows 0-8 are the YOLOv8-cls backbone of the ReID embedder), v8/yolov8-p2.yaml (kYolov8P2: one more stage at stride 4,
 // Detect = model.28) and 11/yolo11.yaml (kYolo11: C3k2 blocks, C2PSA = model.10, Detect = model.23). Channel widths, bottleneck counts
 // and c3k-or-not are read off the tensor shapes, so every scale (n/s/m/l/x) loads unchanged. A new family is one more table and one
-// more rule in choose_graph(); a new module is one more case in build(). v10/yolov10.yaml is kYolo10 (SCDown, PSA = model.10, C2fCIB, v10Detect = model.23). The two classification graphs of the ReID embedder are
+// more rule in choose_graph(); a new module is one more case in build(). v10/yolov10.yaml is kYolo10 (SCDown, PSA = model.10, C2fCIB, v10Detect = model.23),
+// v9/yolov9{t,s,m,c}.yaml kYolo9 (ELAN1 / RepNCSPELAN4, AConv / ADown behind pool_down.hip's launch, SPPELAN = model.9, Detect = model.22). The two classification graphs of the ReID embedder are
 // prefixes of these tables: yolov8-cls.yaml = kYolov8's rows 0-8, 11/yolo11-cls.yaml = kYolo11's rows 0-8 + C2PSA as model.9 (kYolo11Cls).
 #include "yolo_trunk.hpp"
+#include "pool_down.hpp"
 #include "rtdetr_kernels.hpp"
 #include "split_format.hpp"
 
@@ -32,6 +34,8 @@ TrunkGraph YoloTrunk::choose_graph() const {
     return graph_of(kYolo10, true);
   // yolo11.yaml: C2PSA at model.10 and Detect (depthwise class branch) at model.23 -- names no YOLOv8 file has
   if (net_.has("model.10.m.0.attn.qkv.conv.weight") && net_.has("model.23.cv3.0.0.0.conv.weight")) return graph_of(kYolo11, true);
+  // yolov9.yaml: a RepNCSPELAN4's RepCSP (a Sequential inside the block) and SPPELAN's cv5 at model.9, Detect = model.22
+  if (net_.has("model.9.cv5.conv.weight") && net_.has("model.4.cv2.0.cv1.conv.weight") && net_.has("model.22.cv2.0.0.conv.weight")) return graph_of(kYolo9, false);
   // yolov8-p2.yaml: Detect = model.28 on four levels; else yolov8.yaml (Detect, or YOLOv8-RTDETR's decoder, = model.22)
   return net_.has("model.28.cv2.0.0.conv.weight") ? graph_of(kYolov8P2, false) : graph_of(kYolov8, false);
 }
@@ -70,7 +74,7 @@ void YoloTrunk::upsample(const std::string& name, const View& src, const View& d
 }
 
 // ---- SPPF: cv1 -> 3 cascaded pools -> cv2, written into `out` (its slice of the Concat that lists it, or a view of its own)
-void YoloTrunk::sppf(const std::string& pfx, const View& x, const View& out) {
+void YoloTrunk::sppf(const std::string& pfx, const View& x, const View& out, const char* last) {
   const int cm = (int)net_.tensor(pfx + ".cv1.conv.weight").shape[0];
   View sp = net_.new_view(x.h, x.w, 4 * cm);
   View sp0 = sp.slice(0, cm);
@@ -82,14 +86,16 @@ void YoloTrunk::sppf(const std::string& pfx, const View& x, const View& out) {
   op.in = sp0;
   op.out = sp;
   ops_.push_back(op);
-  conv(pfx + ".cv2.conv", sp, 1, &out, nullptr);
+  conv(pfx + last, sp, 1, &out, nullptr);
   net_.set_layer_view(pfx, out);
 }
 
 // One stride-1 Conv op with the given activation (0 none, 1 SiLU). The convolution kernels take channel counts that are
 // multiples of 16: a narrower layer (the 8-channel hidden layer of scale n's model.2 bottleneck) gets zero output channels
-// appended -- SiLU(0) = 0 -- and its consumer zero input weights for them, which changes no sum.
-View YoloTrunk::conv_act(const std::string& name, const View& x, int act, const View* out_slice, const View* residual) {
+// appended -- SiLU(0) = 0 -- and its consumer zero input weights for them, which changes no sum. A padded layer may write a slice and
+// take a residual of its padded width (the residual's padding channels hold zeros, so the output's do); in_seg: the input is a concat
+// of such padded maps, in_seg real channels in each (YOLOv9-t's 24-channel RepCSP hidden maps).
+View YoloTrunk::conv_act(const std::string& name, const View& x, int act, const View* out_slice, const View* residual, int in_seg) {
   const HostTensor& w = net_.tensor(name + ".weight");
   GTX_CHECK(w.shape.size() == 4 && w.shape[2] == w.shape[3], "%s: expected OIHW square kernel", name.c_str());
   const int cout = (int)w.shape[0], cin = (int)w.shape[1], ks = (int)w.shape[2], taps = ks * ks;
@@ -97,11 +103,16 @@ View YoloTrunk::conv_act(const std::string& name, const View& x, int act, const 
   NetRuntime::ConvArgs a;
   a.act = act; a.out_slice = out_slice; a.residual = residual;
   if (cout_p == cout && cin_p == cin) return net_.emit_named_conv(ops_, name, x, a);
-  GTX_CHECK(cin_p >= cin && (cout_p == cout || (!out_slice && !residual)), "%s: %d -> %d channels cannot be padded here", name.c_str(), cin, cout);
+  GTX_CHECK(cin_p >= cin && (cout_p == cout || ((!out_slice || out_slice->c == cout_p) && (!residual || residual->c == cout_p))),
+            "%s: %d -> %d channels cannot be padded here", name.c_str(), cin, cout);
+  const int seg_p = in_seg > 0 ? (in_seg + 15) / 16 * 16 : 0;
+  GTX_CHECK(in_seg <= 0 || (cin % in_seg == 0 && cin_p == cin / in_seg * seg_p), "%s: %d input channels are not padded segments of %d", name.c_str(), cin_p, in_seg);
   std::vector<float> wp((size_t)cout_p * cin_p * taps, 0.f), bp(cout_p, 0.f);
   for (int o = 0; o < cout; ++o)
-    for (int i = 0; i < cin; ++i)
-      for (int t = 0; t < taps; ++t) wp[((size_t)o * cin_p + i) * taps + t] = w.data[((size_t)o * cin + i) * taps + t];
+    for (int i = 0; i < cin; ++i) {
+      const int ip = in_seg > 0 ? i / in_seg * seg_p + i % in_seg : i;
+      for (int t = 0; t < taps; ++t) wp[((size_t)o * cin_p + ip) * taps + t] = w.data[((size_t)o * cin + i) * taps + t];
+    }
   if (const float* b = net_.bias_of(name, cout)) std::copy(b, b + cout, bp.begin());
   a.out_pixels = (long)x.n * x.h * x.w;
   return net_.emit_conv(ops_, name, wp.data(), cout_p, cin_p, ks, bp.data(), x, a);
@@ -114,22 +125,85 @@ View YoloTrunk::bottleneck(const std::string& m, const View& src, const View& ds
   return conv_act(m + ".cv2.conv", tmp, 1, &dst, shortcut ? &src : nullptr);
 }
 
-// C3k: cv3(cat(m(cv1(x)), cv2(x))), m = Bottlenecks of full hidden width
+// C3k: cv3(cat(m(cv1(x)), cv2(x))), m = Bottlenecks of full hidden width. YOLOv9's RepCSP is the same block (its RepConv arrives fused:
+// one 3x3). A hidden width that is no multiple of 16 (RepCSP's 24 channels in yolov9t) is carried zero-padded: chp channels per map.
 View YoloTrunk::c3k(const std::string& m, const View& src, const View& dst, bool shortcut) {
-  const int ch = (int)net_.tensor(m + ".cv1.conv.weight").shape[0];
+  const int ch = (int)net_.tensor(m + ".cv1.conv.weight").shape[0], chp = (ch + 15) / 16 * 16;
   int n = 0;
   while (net_.has(m + ".m." + std::to_string(n) + ".cv1.conv.weight")) ++n;
-  View cat = net_.new_view(src.h, src.w, 2 * ch);
-  View left = cat.slice(0, ch), right = cat.slice(ch, ch);
-  View y = n == 0 ? left : net_.new_view(src.h, src.w, ch);
+  View cat = net_.new_view(src.h, src.w, 2 * chp);
+  View left = cat.slice(0, chp), right = cat.slice(chp, chp);
+  View y = n == 0 ? left : net_.new_view(src.h, src.w, chp);
   conv_act(m + ".cv1.conv", src, 1, &y, nullptr);
   for (int j = 0; j < n; ++j) {
-    View nxt = j + 1 == n ? left : net_.new_view(src.h, src.w, ch);
+    View nxt = j + 1 == n ? left : net_.new_view(src.h, src.w, chp);
     bottleneck(m + ".m." + std::to_string(j), y, nxt, shortcut);
     y = nxt;
   }
   conv_act(m + ".cv2.conv", src, 1, &right, nullptr);
-  return conv_act(m + ".cv3.conv", cat, 1, &dst, nullptr);
+  return conv_act(m + ".cv3.conv", cat, 1, &dst, nullptr, chp != ch ? ch : 0);
+}
+
+// ELAN1 / RepNCSPELAN4(c1, c2, c3, c4, n): cv1 -> two chunks of c3 / 2; cv2 on the second chunk, cv3 on cv2's output, each a
+// Sequential(RepCSP, Conv3x3) (ELAN1: a plain Conv3x3); cv4 on the concatenation of the four. Chunks and concat are channel offsets
+// into one buffer, as in C2f.
+View YoloTrunk::elan(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src) {
+  const bool rep = net_.has(pfx + ".cv2.0.cv1.conv.weight");
+  const int c3 = (int)net_.tensor(pfx + ".cv1.conv.weight").shape[0], half = c3 / 2;
+  const int c4 = (int)net_.tensor(pfx + (rep ? ".cv2.1.conv.weight" : ".cv2.conv.weight")).shape[0];
+  GTX_CHECK(c3 % 16 == 0 && c4 % 8 == 0, "%s: chunks of %d and branches of %d channels", pfx.c_str(), half, c4);
+  View cat = net_.new_view(x.h, x.w, c3 + 2 * c4);
+  View first = cat.slice(0, c3);
+  conv(pfx + ".cv1.conv", x, 1, &first, nullptr, up_src);
+  View src = cat.slice(half, half);
+  for (int k = 0; k < 2; ++k) {
+    const std::string b = pfx + (k == 0 ? ".cv2" : ".cv3");
+    View dst = cat.slice(c3 + k * c4, c4);
+    if (rep) {
+      const View mid = net_.new_view(x.h, x.w, c4);
+      c3k(b + ".0", src, mid, shortcut);
+      conv_act(b + ".1.conv", mid, 1, &dst, nullptr);
+    } else {
+      conv_act(b + ".conv", src, 1, &dst, nullptr);
+    }
+    src = dst;
+  }
+  View out = conv(pfx + ".cv4.conv", cat, 1, out_slice, nullptr);
+  net_.set_layer_view(pfx, out);
+  return out;
+}
+
+// AConv(c1, c2): cv1(avg_pool2d(x, 2, 1)), cv1 = Conv 3x3 stride 2. ADown(c1, c2), told by its cv2: the same average, then cv1 on the
+// first half of the channels and cv2 = Conv 1x1 on max_pool2d(3, 2, 1) of the second half, concatenated. One pool_down launch writes
+// what the convolutions read: the average at x's size with a zero last row and column (the even-sized stride-2 kernels then form
+// Conv2d(3, 2, 1)'s sums on the odd-sized map), the maximum at half of it.
+View YoloTrunk::adown(const std::string& pfx, const View& x, const View* out_slice) {
+  const bool two = net_.has(pfx + ".cv2.conv.weight");
+  GTX_CHECK(x.h % 2 == 0 && x.w % 2 == 0 && x.c % 16 == 0, "%s: a %dx%d map of %d channels", pfx.c_str(), x.w, x.h, x.c);
+  const int ca = two ? x.c / 2 : x.c;
+  const View avg = net_.new_view(x.h, x.w, ca);
+  View mx;
+  if (two) mx = net_.new_view(x.h / 2, x.w / 2, x.c - ca);
+  Op op;
+  op.kind = Op::POOLDOWN;
+  op.name = pfx + ".pool";
+  op.family = "pool_down_kernel";
+  op.in = x; op.out = avg; op.out2 = mx;
+  ops_.push_back(op);
+  net_.set_layer_view(pfx + ".pool", avg);
+  if (!two) {
+    const View out = conv(pfx + ".cv1.conv", avg, 2, out_slice, nullptr);
+    net_.set_layer_view(pfx, out);
+    return out;
+  }
+  net_.set_layer_view(pfx + ".maxpool", mx);
+  const int c = (int)net_.tensor(pfx + ".cv1.conv.weight").shape[0];
+  const View out = out_slice ? *out_slice : net_.new_view(x.h / 2, x.w / 2, 2 * c);
+  const View a = out.slice(0, c), b = out.slice(c, c);
+  conv(pfx + ".cv1.conv", avg, 2, &a, nullptr);
+  conv(pfx + ".cv2.conv", mx, 1, &b, nullptr);
+  net_.set_layer_view(pfx, out);
+  return out;
 }
 
 // C2f / C3k2: cv1 -> a | b, n blocks m.{k} chained from b with every output appended, cv2 on the concatenation. m.{k} is a Bottleneck
@@ -309,6 +383,9 @@ YoloTrunk::Levels YoloTrunk::build(const View& img, const TrunkGraph& g, bool fr
     switch (r.mod) {
       case TrunkRow::CONV: width[i] = cout_of(name(i) + ".conv"); break;
       case TrunkRow::BLOCK: case TrunkRow::SPPF: case TrunkRow::C2PSA: case TrunkRow::SCDOWN: case TrunkRow::PSA: width[i] = cout_of(name(i) + ".cv2.conv"); break;
+      case TrunkRow::ELAN: width[i] = cout_of(name(i) + ".cv4.conv"); break;
+      case TrunkRow::ADOWN: width[i] = cout_of(name(i) + ".cv1.conv") + (net_.has(name(i) + ".cv2.conv.weight") ? cout_of(name(i) + ".cv2.conv") : 0); break;
+      case TrunkRow::SPPELAN: width[i] = cout_of(name(i) + ".cv5.conv"); break;
       case TrunkRow::UPSAMPLE:
         // torch's Upsample + Concat in front of a block: the split-f16x3 path reads the low-resolution tensor in place from the
         // block's first 1x1 conv (ConvProblem::in2) when every such tensor of the graph is whole 32-channel groups (all or nothing),
@@ -348,7 +425,7 @@ YoloTrunk::Levels YoloTrunk::build(const View& img, const TrunkGraph& g, bool fr
     const int f = from(r, 0);
     const View& x = i == 0 ? img : out[f];
     GTX_CHECK(i == 0 || r.mod == TrunkRow::DETECT || r.mod == TrunkRow::CONCAT || x.ptr, "internal: model.%d reads model.%d, which has no output", i, f);
-    GTX_CHECK(i == 0 || up_src[f] < 0 || r.mod == TrunkRow::BLOCK, "internal: only a C2f / C3k2 reads an upsampled source in place (model.%d)", i);
+    GTX_CHECK(i == 0 || up_src[f] < 0 || r.mod == TrunkRow::BLOCK || r.mod == TrunkRow::ELAN, "internal: only a C2f / C3k2 / ELAN block reads an upsampled source in place (model.%d)", i);
     switch (r.mod) {
       case TrunkRow::CONV:
         if (i == 0) { out[i] = stem(img, front); break; }
@@ -365,6 +442,16 @@ YoloTrunk::Levels YoloTrunk::build(const View& img, const TrunkGraph& g, bool fr
       }
       case TrunkRow::C2PSA: out[i] = c2psa(name(i), x, place(i, x.h, x.w)); break;
       case TrunkRow::PSA: out[i] = c2psa(name(i), x, place(i, x.h, x.w), true); break;
+      case TrunkRow::ELAN:
+        out[i] = elan(name(i), x, r.shortcut, place(i, x.h, x.w), up_src[f] >= 0 ? &out[up_src[f]] : nullptr);
+        break;
+      case TrunkRow::ADOWN: out[i] = adown(name(i), x, place(i, x.h / 2, x.w / 2)); break;
+      case TrunkRow::SPPELAN: {
+        const View* s = place(i, x.h, x.w);
+        out[i] = s ? *s : net_.new_view(x.h, x.w, width[i]);
+        sppf(name(i), x, out[i], ".cv5.conv");
+        break;
+      }
       case TrunkRow::SCDOWN: out[i] = scdown(name(i), x, place(i, (x.h - 1) / 2 + 1, (x.w - 1) / 2 + 1)); break;
       case TrunkRow::UPSAMPLE: {
         const View* s = place(i, 2 * x.h, 2 * x.w);
@@ -555,6 +642,11 @@ void YoloTrunk::run_op(const Op& op, int nb, hipStream_t s) const {
                        op.sat, s, op.dw_res.ptr ? &res : nullptr);
       break;
     }
+    case Op::POOLDOWN:
+      launch_pool_down(fmt, RtMap{op.in.ptr, op.in.h, op.in.w, op.in.cstride, op.in.coff, op.in.c},
+                       RtMap{op.out.ptr, op.out.h, op.out.w, op.out.cstride, op.out.coff, op.out.c},
+                       RtMap{op.out2.ptr, op.out2.h, op.out2.w, op.out2.cstride, op.out2.coff, op.out2.c}, nb, s);
+      break;
     case Op::ATTN:
       launch_psa_attention(fmt, RtMap{op.in.ptr, op.in.h, op.in.w, op.in.cstride, op.in.coff, op.in.c},
                            RtMap{op.out.ptr, op.out.h, op.out.w, op.out.cstride, op.out.coff, op.out.c}, nb, op.heads, op.dw_w, op.dw_bias, op.sat, s);
@@ -603,6 +695,9 @@ void set_batch_ops(std::vector<Op>& ops, int nb, size_t es, bool pad_skip_on) {
     } else if (op.kind == Op::DWCONV) {
       op.flops = 2.0 * op.dw_k * op.dw_k * nb * op.out.h * op.out.w * op.in.c;
       op.bytes = (double)nb * ((double)op.in.h * op.in.w + (double)op.out.h * op.out.w * (op.dw_res.ptr ? 2 : 1)) * op.in.c * es;
+    } else if (op.kind == Op::POOLDOWN) {           // three additions per averaged element, eight maxima per maximum; every map once
+      op.flops = (double)nb * op.in.h * op.in.w * (3.0 * op.out.c + 3.0 * op.out2.c) + 8.0 * nb * op.out2.h * op.out2.w * op.out2.c;
+      op.bytes = (double)nb * ((double)op.in.h * op.in.w * (op.in.c + op.out.c) + (double)op.out2.h * op.out2.w * op.out2.c) * es;
     } else if (op.kind == Op::ATTN) {               // q.k (depth 32) + p.v (width 64) per query-key pair and head, + pe; the qkv map in, the output map out
       const double T = (double)op.in.h * op.in.w;
       op.flops = nb * (op.heads * T * T * 2.0 * (32 + 64) + 2.0 * 9 * T * op.out.c);

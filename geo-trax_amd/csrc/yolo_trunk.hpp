@@ -14,7 +14,7 @@
 namespace gtx {
 
 struct Op : OpInfo {
-  enum Kind { CONV, STEM, POOL, UPSAMPLE, DWCONV, ATTN } kind = CONV;
+  enum Kind { CONV, STEM, POOL, UPSAMPLE, DWCONV, ATTN, POOLDOWN } kind = CONV;
   ConvGroup grp{};       // CONV
   ConvConfig cfg{};
   // STEM / POOL / UPSAMPLE parameters
@@ -32,6 +32,7 @@ struct Op : OpInfo {
   int dw_act = 0, heads = 0;
   int dw_k = 3, dw_stride = 1;
   View dw_res;
+  View out2;                         // POOLDOWN (pool_down.hpp): `in` -> `out` (the 2x2 average) and, ADown, out2 (its 3x3 stride-2 maximum)
   int* sat = nullptr;                // the net's saturation flag (split-f16x3 path)
   // rows of the output that depend on the frame (Detector::plan_pad_skip), as tile rows per group member; count 0 = all
   int ty_first[kMaxGroup] = {0}, ty_count[kMaxGroup] = {0};
@@ -51,7 +52,7 @@ class YoloTrunk {
     std::string det_pfx;         // the Detect row: model.22 (yolov8.yaml), model.28 (yolov8-p2.yaml) or model.23 (yolo11.yaml, yolov10.yaml)
     bool dw_cls = false;         // TrunkGraph::dw_cls
   };
-  // The graph the tensors were built from, by their names: yolov10.yaml, yolo11.yaml, yolov8-p2.yaml, else yolov8.yaml
+  // The graph the tensors were built from, by their names: yolov10.yaml, yolo11.yaml, yolov9.yaml, yolov8-p2.yaml, else yolov8.yaml
   TrunkGraph choose_graph() const;
   static TrunkGraph cls_backbone();   // model.0-8 of yolov8.yaml = yolov8-cls.yaml's backbone
   // The classification graph the tensors were built from: yolo11-cls.yaml (model.0-8 of yolo11.yaml + C2PSA = model.9), else cls_backbone()
@@ -81,15 +82,18 @@ class YoloTrunk {
  private:
   View stem(const View& img, bool front);
   View c2f(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src);   // C2f and C3k2
-  // one stride-1 Conv op with activation `act`; channel counts that are no multiple of 16 are zero-padded (YOLO11-n's 8-channel hidden layer)
-  View conv_act(const std::string& name, const View& x, int act, const View* out_slice, const View* residual);
+  // one stride-1 Conv op with activation `act`; channel counts that are no multiple of 16 are zero-padded (YOLO11-n's 8-channel hidden layer).
+  // in_seg > 0: x is segments of in_seg channels, each followed by its zero padding up to a multiple of 16 (a concat of padded maps)
+  View conv_act(const std::string& name, const View& x, int act, const View* out_slice, const View* residual, int in_seg = 0);
   View bottleneck(const std::string& m, const View& src, const View& dst, bool shortcut);
   View c3k(const std::string& m, const View& src, const View& dst, bool shortcut);
   View c2psa(const std::string& pfx, const View& x, const View* out_slice, bool bare = false);   // bare: PSA, the one block's tensors directly under pfx
   View cib(const std::string& m, const View& src, const View& dst, bool shortcut);
   View scdown(const std::string& pfx, const View& x, const View* out_slice);
+  View elan(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src);   // ELAN1 and RepNCSPELAN4
+  View adown(const std::string& pfx, const View& x, const View* out_slice);                                     // AConv and ADown
   void upsample(const std::string& name, const View& src, const View& dst);
-  void sppf(const std::string& pfx, const View& x, const View& out);
+  void sppf(const std::string& pfx, const View& x, const View& out, const char* last = ".cv2.conv");   // SPPELAN: last = ".cv5.conv"
   void fuse_front();         // model.1 (3x3 stride 2) + model.2.cv1 (1x1) as one launch on the split-f16x3 path
   void fuse_stem();          // model.0 (the stem) computed inside model.1's launch: its output never reaches HBM
   void release_hidden_layers();

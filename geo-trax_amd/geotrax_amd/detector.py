@@ -86,6 +86,17 @@ class Detector:
         if self.rtdetr and obj_feats:
             raise NotImplementedError("RT-DETR: obj_feats (ReID `model: auto`) is not implemented")
         self.p2 = self.graph == "yolov8-p2"   # yolov8-p2.yaml: a fourth Detect level at stride 4, Detect = model.28
+        self._layout: dict[str, np.ndarray] = {}
+        if self.graph == "yolov9":
+            from .weights import check_yolov9, pad_yolov9_channels
+
+            scale = check_yolov9(tensors)
+            if obj_feats and scale != "c":                # ultralytics' own reshape of the Detect inputs fails on these widths too
+                raise NotImplementedError(f"yolov9{scale}: with_reid: true, model: auto needs Detect inputs whose channel counts are multiples of the "
+                                          f"narrowest (yolov9t 64 / 96 / 128, yolov9s 128 / 192 / 256, yolov9m 240 / 360 / 480 are not); of the YOLOv9 "
+                                          f"scales only c qualifies (a separate network works: `model: yolo11n-cls.safetensors`)")
+            # yolov9m: 360 / 184 / 180-channel maps are carried zero-padded to the convolution kernels' 16-channel chunk (same sums)
+            tensors, self._layout = pad_yolov9_channels(tensors, scale)
         self.end2end = resolve_end2end(self.graph, tensors, end2end)
         if self.end2end and obj_feats:
             raise NotImplementedError("with_reid: true, model: auto reads the Detect layer's inputs at the boxes NMS keeps; not implemented for YOLOv10's "
@@ -254,7 +265,8 @@ class Detector:
         check(self.ctx.lib.gtx_detector_layer_output(self.handle, b, layer.encode(), None, C.byref(h), C.byref(w), C.byref(c)))
         out = np.zeros((h.value, w.value, c.value), np.float32)
         check(self.ctx.lib.gtx_detector_layer_output(self.handle, b, layer.encode(), ptr(out), C.byref(h), C.byref(w), C.byref(c)))
-        return out
+        pos = getattr(self, "_layout", {}).get(layer)     # a zero-padded map (yolov9m): its real channels
+        return out if pos is None else np.ascontiguousarray(out[..., pos])
 
     def trace(self, every_n: int) -> None:
         """Time every launch of every `every_n`-th submitted pass with HIP events (0 = off)."""

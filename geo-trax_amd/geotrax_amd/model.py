@@ -130,6 +130,10 @@ class YOLO:
             from .weights import check_yolov10
 
             graph += check_yolov10(self.tensors)
+        if graph == "yolov9":                             # yolov9t.yaml / yolov9s.yaml / yolov9m.yaml / yolov9c.yaml
+            from .weights import check_yolov9
+
+            graph += check_yolov9(self.tensors)
         if not self.names:
             self.names = {i: str(i) for i in range(nc)}
         self.model = self            # ultralytics exposes .model.yaml_file; keep attribute access harmless

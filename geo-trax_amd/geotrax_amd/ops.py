@@ -156,6 +156,30 @@ def dwconv(x: np.ndarray, w: np.ndarray, bias: np.ndarray, *, stride: int = 1, a
     return out, bool(sat.value)
 
 
+def pool_down(x: np.ndarray, c_avg: int, c_max: int = 0, *, n: int | None = None, in_coff: int = 0, avg: np.ndarray | None = None, avg_coff: int = 0,
+              mx: np.ndarray | None = None, max_coff: int = 0, split: bool = False, iters: int = 0, ctx=None):
+    """YOLOv9's AConv / ADown pools in one launch. x [n_alloc, h, w, cs] holds c_avg + c_max channels from in_coff. Returns (avg, max, ms):
+    avg [n_alloc, h, w, .] = avg_pool2d(2, 1) of the first c_avg channels with a zero last row and column, max [n_alloc, h/2, w/2, .] =
+    max_pool2d(3, 2, 1) of that average of the other c_max channels (None when c_max = 0). avg / mx given: the buffers as they are
+    before the launch (written at avg_coff / max_coff; the first n images run, everything else comes back unchanged). split=True
+    (float32 arrays): the pair format on the device (GTX_F32S)."""
+    ctx = ctx or _lib.default_context()
+    x = np.ascontiguousarray(x)
+    na, h, w, cs = x.shape
+    n = na if n is None else n
+    avg = np.zeros((na, h, w, c_avg), x.dtype) if avg is None else np.array(avg, dtype=x.dtype, order="C")
+    if c_max:
+        mx = np.zeros((na, h // 2, w // 2, c_max), x.dtype) if mx is None else np.array(mx, dtype=x.dtype, order="C")
+        assert mx.shape[:3] == (na, h // 2, w // 2)
+    else:
+        mx = None
+    assert avg.shape[:3] == (na, h, w) and (not split or x.dtype == np.float32)
+    ms = C.c_float()
+    check(ctx.lib.gtx_op_pool_down(ctx.handle, GTX_F32S if split else _dt(x), n, na, h, w, c_avg, c_max, ptr(x), cs, in_coff, ptr(avg), avg.shape[3], avg_coff,
+                                   ptr(mx), mx.shape[3] if c_max else 0, max_coff, iters, C.byref(ms)))
+    return avg, mx, (ms.value if iters > 0 else None)
+
+
 def preprocess(frame_bgr: np.ndarray, net_h: int, net_w: int, dtype=np.float32, want_gray: bool = True, ctx=None):
     """Letterbox + BGR->RGB + /255 into [net_h,net_w,4] (RGB0) and the half-res gray image."""
     ctx = ctx or _lib.default_context()

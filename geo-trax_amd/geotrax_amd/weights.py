@@ -56,7 +56,12 @@ def load_weights(path: str | Path) -> dict[str, np.ndarray]:
         t = fold_repvggdw(t)
     if is_rtdetr(t):
         t = fold_input_proj(fuse_repconv(t))
+    elif any(_V9_REPCONV.fullmatch(k) for k in t):         # a YOLOv9 file stored unfused: RepBottleneck's RepConv pairs, BN already folded per branch
+        t = fuse_repconv(t)
     return t
+
+
+_V9_REPCONV = re.compile(r"model\.\d+\.cv[23]\.0\.m\.\d+\.cv1\.conv1\.conv\.weight")   # RepNCSPELAN4 -> RepCSP -> RepBottleneck -> RepConv's 3x3 branch
 
 
 def save_weights(tensors: dict[str, np.ndarray], path: str | Path) -> None:
@@ -227,6 +232,15 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False) -> list[tuple[
                 bottleneck(m, c, 1.0 if c3k is None else 0.5)
         conv(f"{pfx}.cv2.conv", (2 + n) * c, cout, 1)
 
+    def repcsp(p, c1, c2, n):
+        """RepCSP(c1, c2, n) = C3 whose m.{k} are RepBottlenecks of e = 1.0: the fused RepConv (one 3x3) then a Conv3x3"""
+        h = int(c2 * 0.5)
+        conv(p + ".cv1.conv", c1, h, 1)
+        conv(p + ".cv2.conv", c1, h, 1)
+        conv(p + ".cv3.conv", 2 * h, c2, 1)
+        for k in range(n):
+            bottleneck(f"{p}.m.{k}", h, 1.0)
+
     def detect(d, chans, box="cv2", cls="cv3"):
         cb = max(16, chans[0] // 4, 64)
         cc = max(chans[0], min(nc, 100))
@@ -289,6 +303,30 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False) -> list[tuple[
             conv(pfx + ".ffn.0.conv", c, 2 * c, 1)
             conv(pfx + ".ffn.1.conv", 2 * c, c, 1, act=False)
             conv(pfx + ".cv2.conv", 2 * c, out[i], 1)
+        elif mod in ("ELAN1", "RepNCSPELAN4"):            # (c2, c3, c4[, n]): cv1 -> two chunks; cv2 on the second, cv3 on cv2's; cv4 on all four
+            c2, c3, c4 = args[:3]
+            out.append(c2)
+            conv(pfx + ".cv1.conv", cin, c3, 1)
+            if mod == "ELAN1":
+                conv(pfx + ".cv2.conv", c3 // 2, c4, 3)
+                conv(pfx + ".cv3.conv", c4, c4, 3)
+            else:
+                repcsp(pfx + ".cv2.0", c3 // 2, c4, args[3])
+                conv(pfx + ".cv2.1.conv", c4, c4, 3)
+                repcsp(pfx + ".cv3.0", c4, c4, args[3])
+                conv(pfx + ".cv3.1.conv", c4, c4, 3)
+            conv(pfx + ".cv4.conv", c3 + 2 * c4, c2, 1)
+        elif mod == "AConv":                               # avg_pool2d(2, 1), then Conv 3x3 stride 2
+            out.append(args[0])
+            conv(pfx + ".cv1.conv", cin, out[i], 3)
+        elif mod == "ADown":                               # avg_pool2d(2, 1), chunk: Conv 3x3 stride 2 | max_pool2d(3, 2, 1) + Conv 1x1
+            out.append(args[0])
+            conv(pfx + ".cv1.conv", cin // 2, out[i] // 2, 3)
+            conv(pfx + ".cv2.conv", cin // 2, out[i] // 2, 1)
+        elif mod == "SPPELAN":                             # (c2, c3): cv1 1x1, three chained 5x5 max-pools, cv5 1x1 on the four
+            out.append(args[0])
+            conv(pfx + ".cv1.conv", cin, args[1], 1)
+            conv(pfx + ".cv5.conv", 4 * args[1], out[i], 1)
         elif mod == "Upsample":
             out.append(cin)
         elif mod == "Concat":
@@ -572,6 +610,192 @@ def synthetic_yolov10(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: fl
     different things; the knobs shape both alike."""
     return _draw_yolov8(np.random.default_rng(seed), yolov10_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias, box_weight_scale)
 
+# --------------------------------------------------------------------------- YOLOv9 (cfg/models/v9/yolov9{t,s,m,c}.yaml)
+# The GELAN networks: ELAN1 / RepNCSPELAN4 blocks (cv1 1x1 -> two chunks; cv2 and cv3 are Sequential(RepCSP, Conv3x3) -- plain Conv3x3
+# in ELAN1 -- each on the output before it; cv4 1x1 on the four pieces), AConv (avg_pool2d(2, 1) then a 3x3 stride-2 Conv; scales t / s /
+# m) or ADown (the same pool, then one channel half through a 3x3 stride-2 Conv and the other through max_pool2d(3, 2, 1) + a 1x1 Conv;
+# scale c) for downsampling, SPPELAN = model.9 and YOLOv8's legacy Detect = model.22 on [15, 18, 21]. The yamls carry no `scales`: every
+# file writes its widths out, so each scale is a table of its own (_yolov9_table). Restated from ultralytics' public source; not checked
+# against the package (it is not installed). yolov9e (two backbones joined by CBLinear / CBFuse) is not implemented.
+
+YOLOV9_TOPOLOGY = ("yolov9 detect (yolov9{t,s,m,c}: ELAN1 / RepNCSPELAN4 blocks, AConv or ADown = model.3 / 5 / 7 / 16 / 19, SPPELAN = model.9, "
+                   "Detect = model.22 on model.15 / 18 / 21)")
+
+# per scale: model.0, model.1, the block rows 2 / 4 / 6 / 8 / 15 as (c2, c3, c4, n) (n = 0: ELAN1), the widths of the downsampling rows
+# 3 / 5 / 7 / 16 / 19, SPPELAN's c3, and the downsampling module
+_YOLOV9_WIDTHS = {
+    "t": (16, 32, ((32, 32, 16, 0), (64, 64, 32, 3), (96, 96, 48, 3), (128, 128, 64, 3), (64, 64, 32, 3)), (64, 96, 128, 48, 64), 64, "AConv"),
+    "s": (32, 64, ((64, 64, 32, 0), (128, 128, 64, 3), (192, 192, 96, 3), (256, 256, 128, 3), (128, 128, 64, 3)), (128, 192, 256, 96, 128), 128, "AConv"),
+    "m": (32, 64, ((128, 128, 64, 1), (240, 240, 120, 1), (360, 360, 180, 1), (480, 480, 240, 1), (240, 240, 120, 1)), (240, 360, 480, 184, 240), 240, "AConv"),
+    "c": (64, 128, ((256, 128, 64, 1), (512, 256, 128, 1), (512, 512, 256, 1), (512, 512, 256, 1), (256, 256, 128, 1)), (256, 512, 512, 256, 512), 256, "ADown"),
+}
+
+
+def _yolov9_table(scale: str):
+    """yolov9<scale>.yaml as a table. The neck's blocks 12 / 18 / 21 repeat the backbone's 6 / 6 / 8; 15 is row 4 again except in scale c."""
+    c0, c1, blocks, down, spp, dmod = _YOLOV9_WIDTHS[scale]
+    blk = lambda b: (-1, 1, "RepNCSPELAN4", b) if b[3] else (-1, 1, "ELAN1", b[:3])
+    dn = lambda k: (-1, 1, dmod, (down[k],))
+    return [
+        (-1, 1, "Conv", (c0, 3, 2)),
+        (-1, 1, "Conv", (c1, 3, 2)),
+        blk(blocks[0]),                                    # 2
+        dn(0), blk(blocks[1]),                             # 3, 4
+        dn(1), blk(blocks[2]),                             # 5, 6
+        dn(2), blk(blocks[3]),                             # 7, 8
+        (-1, 1, "SPPELAN", (blocks[3][0], spp)),           # 9
+        _UP,
+        ((-1, 6), 1, "Concat", (1,)),
+        blk(blocks[2]),                                    # 12
+        _UP,
+        ((-1, 4), 1, "Concat", (1,)),
+        blk(blocks[4]),                                    # 15
+        dn(3),
+        ((-1, 12), 1, "Concat", (1,)),
+        blk(blocks[2]),                                    # 18
+        dn(4),
+        ((-1, 9), 1, "Concat", (1,)),
+        blk(blocks[3]),                                    # 21
+        ((15, 18, 21), 1, "Detect", ("nc",)),              # 22: the legacy head, cv3 = Conv3x3, Conv3x3, Conv2d
+    ]
+
+
+YOLOV9_YAML = _yolov9_table("s")                           # v9/yolov9s.yaml; the other scales: _yolov9_table
+
+
+def _has_gelan(tensors: dict) -> bool:
+    """A Sequential inside an ELAN block (`model.<N>.cv2.0.cv1.conv.weight`: RepNCSPELAN4.cv2[0] is a RepCSP): no other supported family has it"""
+    for k in tensors:
+        p = k.split(".")
+        if len(p) == 7 and p[0] == "model" and p[1].isdigit() and p[2:] == ["cv2", "0", "cv1", "conv", "weight"]:
+            return True
+    return False
+
+
+def is_yolov9(tensors: dict) -> bool:
+    """True when the names hold what only a YOLOv9 t / s / m / c file has: a RepNCSPELAN4's RepCSP (`model.<N>.cv2.0.cv1.conv`) and
+    SPPELAN's closing conv `model.9.cv5.conv`. Which graph it is, and whether this build runs it: check_yolov9()."""
+    return "model.9.cv5.conv.weight" in tensors and _has_gelan(tensors)
+
+
+def check_yolov9(tensors: dict) -> str:
+    """The scale ("t" / "s" / "m" / "c") of a fused yolov9.yaml detect model; raises NotImplementedError for every other arrangement of
+    its blocks (yolov9e's second backbone, anything past model.22, Detect elsewhere, another width or repeat count). Strict like
+    check_yolov10(): model.0's width names the candidate scales, and every tensor name and shape must be the candidate table's."""
+    no = NotImplementedError(f"checkpoint with YOLOv9's blocks (RepNCSPELAN4, ADown / AConv, SPPELAN) in another arrangement than yolov9{{t,s,m,c}}.yaml's "
+                             f"(yolov9e with its CBLinear / CBFuse second backbone included): of that family only {YOLOV9_TOPOLOGY} is implemented")
+    shape = lambda n: tuple(np.shape(tensors[n])) if n in tensors else None
+    c0, nc_w = shape("model.0.conv.weight"), shape("model.22.cv3.0.2.weight")
+    if c0 is None or nc_w is None:
+        raise no
+    have = {k[: -len(".weight")]: tuple(np.shape(v)) for k, v in tensors.items()
+            if k.startswith("model.") and k.endswith(".weight") and ".dfl." not in k}
+    for scale, w in _YOLOV9_WIDTHS.items():
+        if w[0] != c0[0]:
+            continue
+        want = {n: s for n, s, _ in yolov9_layer_specs(scale, nc_w[0])}
+        if want == have:
+            return scale
+    raise no
+
+
+def yolov9_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
+    """(tensor name, OIHW shape, has_act) for every conv of a fused YOLOv9 detect model (RepConv fused: `...m.{k}.cv1.conv` is one 3x3)"""
+    return _parse_model(_yolov9_table(scale), nc, lambda c: c, lambda i, n: n)
+
+
+def synthetic_yolov9(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0, gain: float = 1.7,
+                     box_decay: float | tuple = 0.3, level_bias: tuple = (0.0, 0.0, 0.0), box_weight_scale: float = 0.3) -> dict[str, np.ndarray]:
+    """Seeded random fused weights of the YOLOv9 architecture, drawn like synthetic_yolov8's (same knobs, the draws in the order of
+    yolov9_layer_specs)."""
+    return _draw_yolov8(np.random.default_rng(seed), yolov9_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias, box_weight_scale)
+
+
+def pad_yolov9_channels(tensors: dict, scale: str) -> tuple[dict, dict]:
+    """A fused yolov9<scale> file as an equal network whose maps all have multiples of 16 channels, the convolution kernels' K chunk:
+    (tensors, layout). yolov9m's widths are not (360, 184, chunks of 180): every such map gets zero channels appended -- zero
+    output weights and biases for them (SiLU(0) = 0; an average, a maximum, an upsampling and a residual of zeros are zero) and zero
+    input weights in every layer that reads them -- which changes no sum. An ELAN block's cv1 is padded per chunk, so chunk(2) still
+    halves it. RepCSP's hidden maps (60 / 90 channels) stay as they are: the trunk builder pads them inside the block, as for
+    yolov9t. layout: layer name -> the positions of its real channels in the padded map (Detector.layer_output reads through it).
+    A scale whose widths are multiples of 16 already (t, s, c) comes back unchanged with an empty layout."""
+    p16 = lambda c: -(-c // 16) * 16
+    ident = lambda c: (np.arange(c), p16(c))                # c real channels, padding behind them
+    plain = lambda c: (np.arange(c), c)                     # left as it is
+    cat = lambda *ls: (np.concatenate([pos + off for (pos, _), off in zip(ls, np.cumsum([0] + [cp for _, cp in ls[:-1]]))]), sum(cp for _, cp in ls))
+    out = {k: np.asarray(v, np.float32) for k, v in tensors.items()}
+
+    def put(name, lin, lout):
+        w, b = out[name + ".weight"], out.get(name + ".bias")
+        wp = np.zeros((lout[1], lin[1]) + w.shape[2:], np.float32)
+        wp[np.ix_(lout[0], lin[0])] = w
+        out[name + ".weight"] = wp
+        bp = np.zeros(lout[1], np.float32)
+        if b is not None:
+            bp[lout[0]] = b
+        out[name + ".bias"] = bp
+
+    def repcsp(p, lin, lout):
+        h = out[p + ".cv1.conv.weight"].shape[0]
+        put(p + ".cv1.conv", lin, plain(h))
+        put(p + ".cv2.conv", lin, plain(h))
+        put(p + ".cv3.conv", plain(2 * h), lout)
+
+    L: list[tuple[np.ndarray, int]] = []
+    table = _yolov9_table(scale)
+    for i, (frm, _, mod, args) in enumerate(table):
+        src = [L[f if f >= 0 else i + f] for f in ((frm,) if isinstance(frm, int) else frm)] if i else [plain(3)]
+        pfx, lx = f"model.{i}", src[0]
+        if mod == "Conv":
+            L.append(ident(args[0]))
+            put(pfx + ".conv", lx, L[i])
+        elif mod in ("ELAN1", "RepNCSPELAN4"):
+            c2, c3, c4 = args[:3]
+            h = c3 // 2
+            l1 = cat(ident(h), ident(h))
+            put(pfx + ".cv1.conv", lx, l1)
+            if mod == "ELAN1":
+                put(pfx + ".cv2.conv", ident(h), ident(c4))
+                put(pfx + ".cv3.conv", ident(c4), ident(c4))
+            else:
+                repcsp(pfx + ".cv2.0", ident(h), ident(c4))
+                put(pfx + ".cv2.1.conv", ident(c4), ident(c4))
+                repcsp(pfx + ".cv3.0", ident(c4), ident(c4))
+                put(pfx + ".cv3.1.conv", ident(c4), ident(c4))
+            L.append(ident(c2))
+            put(pfx + ".cv4.conv", cat(l1, ident(c4), ident(c4)), L[i])
+        elif mod == "AConv":
+            L.append(ident(args[0]))
+            put(pfx + ".cv1.conv", lx, L[i])
+        elif mod == "ADown":                                # each half of the input and of the output padded on its own
+            hi, ho = len(lx[0]) // 2, args[0] // 2
+            if lx[1] != len(lx[0]) or hi % 16 or ho % 16:
+                raise NotImplementedError(f"model.{i}: an ADown on {len(lx[0])} -> {args[0]} channels cannot be padded ({YOLOV9_TOPOLOGY})")
+            L.append(ident(args[0]))
+        elif mod == "SPPELAN":
+            L.append(ident(args[0]))
+            put(pfx + ".cv1.conv", lx, ident(args[1]))
+            put(pfx + ".cv5.conv", cat(*[ident(args[1])] * 4), L[i])
+        elif mod == "Upsample":
+            L.append(lx)
+        elif mod == "Concat":
+            L.append(cat(*src))
+        elif mod == "Detect":
+            for l, lin in enumerate(src):
+                for br in ("cv2", "cv3"):
+                    name = f"{pfx}.{br}.{l}.0.conv"
+                    put(name, lin, plain(out[name + ".weight"].shape[0]))
+    layout = {}
+    for i, (pos, cp) in enumerate(L):
+        if cp != len(pos):
+            layout[f"model.{i}"] = pos
+    for i, row in enumerate(table):                          # a pool's own map is its input row's
+        if row[2] in ("AConv", "ADown") and L[i - 1][1] != len(L[i - 1][0]):
+            layout[f"model.{i}.pool"] = L[i - 1][0]
+    if not layout and all(out[k].shape == np.shape(tensors[k]) for k in tensors):
+        return dict(tensors), {}
+    return out, layout
+
 
 def detector_meta(tensors: dict) -> dict | None:
     """The optional `detector.meta` tensor tools/convert_weights.py writes for a YOLOv10 file: [family 10, one-to-many pair kept,
@@ -640,7 +864,7 @@ RTDETR_TOPOLOGIES = ("rtdetr-l (HGNetv2 + AIFI + CCFM, RTDETRDecoder = model.28)
 
 def detector_topology(tensors: dict) -> tuple[str, str]:
     """(graph, head prefix) of a detector checkpoint, read off the tensor names the way the reference reads its model yaml:
-    ("yolov8", "model.22"), ("yolov8-p2", "model.28"), ("yolo11", "model.23"), ("yolov10", "model.23"), ("rtdetr-l", "model.28") or
+    ("yolov8", "model.22"), ("yolov8-p2", "model.28"), ("yolo11", "model.23"), ("yolov10", "model.23"), ("yolov9", "model.22"), ("rtdetr-l", "model.28") or
     ("yolov8-rtdetr", "model.22").
     An RT-DETR layout other than those two (rtdetr-x with its decoder at model.32, ResNet backbones, ...) raises NotImplementedError,
     and so does a file with YOLO11's or YOLOv10's blocks (attention, a depthwise Detect class branch, SCDown + a one-to-one head) in
@@ -652,6 +876,9 @@ def detector_topology(tensors: dict) -> tuple[str, str]:
         if has_yolo11_blocks(tensors):
             check_yolo11(tensors)                          # raises for YOLO12 / YOLO26 / yolo11-cls, -seg, -obb, -pose ...
             return "yolo11", "model.23"
+        if _has_gelan(tensors):                            # is_yolov9, or GELAN blocks without model.9.cv5: yolov9e, which check_yolov9 refuses by name
+            check_yolov9(tensors)
+            return "yolov9", "model.22"
         return ("yolov8-p2", "model.28") if is_yolov8_p2(tensors) else ("yolov8", "model.22")
     decs = sorted({k.split(".")[1] for k in tensors if k.startswith("model.") and ".decoder.layers." in k and k.split(".")[2] == "decoder"})
     has = lambda pfx: any(k.startswith(pfx) for k in tensors)

@@ -71,7 +71,8 @@ extern "C" {
  *     added: new entry points and an opaque handle only, so the number stays. gtx_op_invert3x3 (the inverse the frame warp uses, on
  *     the host) added: the same, the number stays. gtx_drawer_{create, destroy, draw_dev, last_ms}, gtx_op_draw (the visualize stage's
  *     drawing: a primitive list painted into a frame in HBM) and gtx_dev_copy added: new entry points and an opaque handle only, so the
- *     number stays. */
+ *     number stays. gtx_op_pool_down added and arch 0 also takes YOLOv9 t / s / m / c tensors (yolov9.yaml: ELAN1 / RepNCSPELAN4, AConv / ADown,
+ *     SPPELAN = model.9, Detect = model.22; told by their names like the other families): the same, the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -320,6 +321,16 @@ int gtx_op_psa_attention(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int
  * value to fp16's range (GTX_F32S). Channel counts that are multiples of 32 take the LDS-tiled kernel at stride 1. */
 int gtx_op_dwconv(gtx_ctx* ctx, int dtype, int n, int h, int w, int c, int k, int stride, const void* x, const float* wt, const float* bias,
                   int act, const void* res, void* out, int* saturated);
+
+/* YOLOv9's downsampling pools in one launch (csrc/pool_down.hpp; AConv: c_max = 0, ADown: c_avg = c_max). x [n_alloc][h][w][in_cstride] holds
+ * c_avg + c_max channels from in_coff. avg [n_alloc][h][w][avg_cstride], channels [avg_coff, avg_coff + c_avg): avg_pool2d(2, 1) of the first
+ * c_avg channels, stored h x w with its last row and column zero (what the stride-2 3x3 convolution behind it reads as its pad). max
+ * [n_alloc][h / 2][w / 2][max_cstride], channels [max_coff, max_coff + c_max): max_pool2d(3, 2, 1) of the same average of the other c_max
+ * channels (NULL when c_max = 0). The first n images run; everything else in avg and max comes back as given. h, w even and >= 2; channel
+ * counts, strides and offsets multiples of 8: anything else is refused before the GPU is touched. Host arrays: fp16 (GTX_F16) or plain
+ * fp32 (GTX_F32; GTX_F32S: converted to the pair format on the way). iters > 0: *ms_per_launch = mean time of that many further launches. */
+int gtx_op_pool_down(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int c_avg, int c_max, const void* x, int in_cstride, int in_coff,
+                     void* avg, int avg_cstride, int avg_coff, void* max, int max_cstride, int max_coff, int iters, float* ms_per_launch);
 
 /* RT-DETR's token-side kernels (csrc/rtdetr_kernels.hpp), one launcher per call, for the operator-level tests. Token tensors are plain
  * fp32 rows; map tensors are NHWC host arrays of fp16 (GTX_F16) or plain fp32 (GTX_F32; GTX_F32S: converted to the pair format on the

@@ -27,6 +27,11 @@ branches (`model.23.cv2 / cv3`): convert_state_dict() folds every Conv + BN pair
 one2one_cv3 -- `end2end: false` runs them through NMS -- and writes `detector.meta` = [family 10, one-to-many kept, end-to-end head,
 the head's 300].
 
+A YOLOv9 detect checkpoint (yolov9{t,s,m,c}.yaml) goes through `model.fuse()` like YOLOv8: RepConv.fuse_convs leaves one 3x3 under
+`...cv2.0.m.<k>.cv1.conv.*`, and the fused state_dict ends in `model.22.cv3.2.2.bias`. Where a version leaves a RepConv's two branches
+(`...m.<k>.cv1.conv1` / `conv2`) unfused, geotrax_amd.weights.load_weights folds each branch's BN first and then sums the 1x1 into the
+3x3's centre tap (fold_bn, then fuse_repconv). yolov9e (two backbones, CBLinear / CBFuse) is refused when the file is loaded.
+
 A YOLOv8-cls or YOLO11-cls checkpoint (the ReID network of `with_reid: true, model: <file>.safetensors` in a tracker yaml) is written the same
 way, plus `cls.meta` = [imgsz] from the checkpoint's training arguments (geotrax_amd.weights.cls_imgsz; 224 when absent).
 """
