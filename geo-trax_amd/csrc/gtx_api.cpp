@@ -839,6 +839,64 @@ int gtx_jpeg_enc_last_ms(gtx_jpeg_enc* enc, float* ms) {
   });
 }
 
+int gtx_jpeg_enc_set_entropy(gtx_jpeg_enc* enc, int gpu) {
+  return guarded([&] {
+    need(enc, "enc");
+    if (gpu) {
+      enc->impl->use_gpu_entropy();
+    } else if (enc->impl->gpu_entropy()) {
+      gtx::fail(GTX_ERR_INVALID, "jpeg_enc_set_entropy: the encoder is on the GPU entropy route already");
+    }
+  });
+}
+
+int gtx_jpeg_enc_collect_jpeg(gtx_jpeg_enc* enc, void* out, size_t capacity, size_t* n) {
+  bool fits = true;
+  const int st = guarded([&] {
+    need(enc, "enc"); need(n, "n");
+    fits = enc->impl->collect_jpeg(out, capacity, n);
+  });
+  return st != GTX_OK ? st : fits ? 0 : 1;
+}
+
+int gtx_jpeg_enc_entropy_ms(gtx_jpeg_enc* enc, float* ms) {
+  return guarded([&] {
+    need(enc, "enc"); need(ms, "ms");
+    *ms = enc->impl->entropy_ms();
+  });
+}
+
+size_t gtx_jpeg_picture_bound(int h, int w) {
+  return (h <= 0 || w <= 0 || h > gtx::jpeg::kMaxDim || w > gtx::jpeg::kMaxDim) ? 0 : gtx::jpeg_picture_bound(gtx::jpeg::max_blocks(h, w));
+}
+
+int gtx_jpeg_header(const void* record, size_t bytes, void* out, size_t capacity, size_t* n) {
+  int rc = 0;
+  const int st = guarded([&] {
+    need(record, "record"); need(n, "n");
+    *n = 0;
+    if (!out && capacity) gtx::fail(GTX_ERR_INVALID, "jpeg_header: out is NULL with a capacity of %zu", capacity);
+    if (reinterpret_cast<uintptr_t>(record) & 3) gtx::fail(GTX_ERR_INVALID, "jpeg_header: the record is not 4-byte aligned");
+    if (bytes < gtx::jpeg::kOffsetsOffset) gtx::fail(GTX_ERR_INVALID, "JPEG record: too short for its header and quantisers");
+    gtx::jpeg::RecordHeader hd, want;
+    memcpy(&hd, record, sizeof hd);
+    if (hd.magic != gtx::jpeg::kMagic || !gtx::jpeg::make_header((int)hd.height, (int)hd.width, (int)hd.ncomp, (int)hd.hs, (int)hd.vs, &want))
+      gtx::fail(GTX_ERR_INVALID, "JPEG record: not a record, or a size or sampling outside the accepted set");
+    const uint16_t* quant = reinterpret_cast<const uint16_t*>(static_cast<const uint8_t*>(record) + gtx::jpeg::kQuantOffset);
+    for (uint32_t i = 0; i < 64 * hd.ncomp; ++i)
+      if (quant[i] > 255) gtx::fail(GTX_ERR_INVALID, "JPEG record: a quantiser above 255 (baseline tables have 8-bit entries)");
+    uint8_t tmp[gtx::jpeg::kMaxHeaderBytes];
+    *n = gtx::jpeg::header(hd, quant, tmp, sizeof tmp);
+    if (*n > sizeof tmp) gtx::fail(GTX_ERR_INTERNAL, "jpeg_header: a header of %zu bytes", *n);
+    if (capacity < *n) {
+      rc = 1;
+      return;
+    }
+    memcpy(out, tmp, *n);
+  });
+  return st != GTX_OK ? st : rc;
+}
+
 int gtx_jpeg_emit(const void* record, size_t bytes, void* out, size_t capacity, size_t* n) {
   int rc = 0;
   const int st = guarded([&] {

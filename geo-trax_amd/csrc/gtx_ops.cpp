@@ -1206,6 +1206,46 @@ int gtx_op_jpeg_encode(gtx_ctx* ctx, const uint8_t* bgr, int h, int w, int quali
   return st != GTX_OK ? st : fits ? 0 : 1;
 }
 
+// ---- the GPU entropy coder on a host record (tests/test_jpeg_huff_ops_gpu.py)
+
+int gtx_op_jpeg_huff(gtx_ctx* ctx, const void* record, size_t bytes, void* out, size_t capacity, size_t* n, uint32_t* block_bits) {
+  bool fits = true;
+  const int st = guarded([&] {
+    need(record, "record"); need(n, "n");
+    *n = 0;
+    if (!out && capacity) op_bad("jpeg_huff", "out is NULL with a capacity");
+    if (reinterpret_cast<uintptr_t>(record) & 3) op_bad("jpeg_huff", "the record is not 4-byte aligned");
+    if (bytes < sizeof(gtx::jpeg::RecordHeader)) gtx::fail(GTX_ERR_INVALID, "JPEG record: too short or misaligned");
+    gtx::jpeg::RecordHeader hd;
+    memcpy(&hd, record, sizeof hd);
+    if (hd.width > (uint32_t)gtx::jpeg::kMaxDim || hd.height > (uint32_t)gtx::jpeg::kMaxDim) gtx::fail(GTX_ERR_INVALID, "JPEG record: its frame size differs from h x w");
+    char msg[256];
+    if (gtx::jpeg::check_record(record, bytes, (int)hd.height, (int)hd.width, msg, sizeof msg) != 0) gtx::fail(GTX_ERR_INVALID, "%s", msg);
+    const uint8_t* rec = static_cast<const uint8_t*>(record);
+    const uint16_t* quant = reinterpret_cast<const uint16_t*>(rec + gtx::jpeg::kQuantOffset);
+    for (uint32_t i = 0; i < 64 * hd.ncomp; ++i)
+      if (quant[i] > 255) gtx::fail(GTX_ERR_INVALID, "JPEG record: a quantiser above 255 (baseline tables have 8-bit entries)");
+    need(ctx, "ctx");
+    // the record expanded to what jpeg_fdct_kernel leaves behind: dense runs [n_blocks][64] (zeros past a block's length) + lengths
+    const uint32_t* off = reinterpret_cast<const uint32_t*>(rec + gtx::jpeg::kOffsetsOffset);
+    const int16_t* coef = reinterpret_cast<const int16_t*>(rec + gtx::jpeg::kOffsetsOffset + 4 * ((size_t)hd.n_blocks + 1));
+    std::vector<int16_t> dense((size_t)hd.n_blocks * 64, 0);
+    std::vector<uint32_t> lens(hd.n_blocks);
+    for (uint32_t b = 0; b < hd.n_blocks; ++b) {
+      lens[b] = off[b + 1] - off[b];                              // 0..64, inside the stream: check_record
+      memcpy(dense.data() + (size_t)b * 64, coef + off[b], lens[b] * sizeof(int16_t));
+    }
+    GTX_HIP(hipSetDevice(ctx->device));
+    gtx::DevBuf d_dense, d_lens;
+    upload(d_dense, dense.data(), dense.size() * sizeof(int16_t));
+    upload(d_lens, lens.data(), lens.size() * sizeof(uint32_t));
+    gtx::JpegHuff huff(ctx, hd, quant);
+    huff.enqueue(d_dense.as<const int16_t>(), d_lens.as<const uint32_t>());
+    fits = huff.finish(out, capacity, n, block_bits);
+  });
+  return st != GTX_OK ? st : fits ? 0 : 1;
+}
+
 // ---- the drawing kernel on a host frame (tests/test_draw_ops_gpu.py)
 
 int gtx_op_draw(gtx_ctx* ctx, uint8_t* bgr, int h, int w, const int32_t* prims, int n, const void* atlas, size_t atlas_bytes) {

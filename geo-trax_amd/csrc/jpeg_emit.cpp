@@ -89,6 +89,39 @@ void dht(Writer& w, int cls_id, const uint8_t bits[16], const uint8_t* vals, int
   w.raw(vals, (size_t)nvals);
 }
 
+// SOI, APP0, DQT, SOF0, DHT, SOS: everything in front of the scan (jpeg_emit.hpp: header())
+void write_header(Writer& w, const RecordHeader& hd, const uint16_t* quant) {
+  const int ncomp = (int)hd.ncomp;
+  // Cr shares Cb's table when the two are equal (what libjpeg writes), else it gets a third
+  const bool third = ncomp == 3 && memcmp(quant + 64, quant + 128, 128) != 0;
+  const int n_tables = ncomp == 1 ? 1 : third ? 3 : 2;
+  w.u16(0xFFD8);
+  static const uint8_t app0[] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+  w.raw(app0, sizeof app0);
+  for (int t = 0; t < n_tables; ++t) {
+    w.u16(0xFFDB), w.u16(67), w.byte((unsigned)t);
+    for (int z = 0; z < 64; ++z) w.byte(quant[64 * t + kNatural[z]]);
+  }
+  w.u16(0xFFC0), w.u16(8 + 3 * (unsigned)ncomp), w.byte(8), w.u16(hd.height), w.u16(hd.width), w.byte((unsigned)ncomp);
+  for (int c = 0; c < ncomp; ++c) {
+    w.byte((unsigned)c + 1);
+    w.byte(c == 0 ? (hd.hs << 4 | hd.vs) : 0x11);
+    w.byte(c == 0 ? 0u : (c == 2 && third) ? 2u : 1u);
+  }
+  const int n_huff = ncomp == 1 ? 1 : 2;
+  w.u16(0xFFC4);
+  w.u16(2 + (unsigned)n_huff * (17 + 12) + 17 + 162 + (n_huff == 2 ? 17 + 162 : 0));
+  dht(w, 0x00, kStdDcLumaBits, kStdDcLumaVals, 12);
+  dht(w, 0x10, kStdAcLumaBits, kStdAcLumaVals, 162);
+  if (n_huff == 2) {
+    dht(w, 0x01, kStdDcChromaBits, kStdDcChromaVals, 12);
+    dht(w, 0x11, kStdAcChromaBits, kStdAcChromaVals, 162);
+  }
+  w.u16(0xFFDA), w.u16(6 + 2 * (unsigned)ncomp), w.byte((unsigned)ncomp);
+  for (int c = 0; c < ncomp; ++c) w.byte((unsigned)c + 1), w.byte(c == 0 ? 0x00 : 0x11);
+  w.byte(0), w.byte(63), w.byte(0);
+}
+
 }  // namespace
 
 bool quality_tables(int quality, uint16_t luma[64], uint16_t chroma[64]) {
@@ -116,6 +149,20 @@ bool make_header(int h, int w, int ncomp, int hs, int vs, RecordHeader* hd) {
   return true;
 }
 
+size_t header(const RecordHeader& hd, const uint16_t* quant, uint8_t* out, size_t capacity) {
+  Writer w{out, out ? capacity : 0};
+  write_header(w, hd, quant);
+  return w.n;
+}
+
+void std_huff_codes(HuffCodes* out) {
+  const Tables t;
+  for (int k = 0; k < 2; ++k) {
+    for (int s = 0; s < 12; ++s) out->dc[k][s] = (uint32_t)t.dc[k].code[s] | (uint32_t)t.dc[k].size[s] << 16;
+    for (int s = 0; s < 256; ++s) out->ac[k][s] = (uint32_t)t.ac[k].code[s] | (uint32_t)t.ac[k].size[s] << 16;
+  }
+}
+
 int emit(const void* record, size_t bytes, uint8_t* out, size_t capacity, size_t* n, char* msg, size_t msg_cap) {
   static const Tables tables;
   if (msg && msg_cap) msg[0] = 0;
@@ -137,36 +184,9 @@ int emit(const void* record, size_t bytes, uint8_t* out, size_t capacity, size_t
   const int ncomp = (int)hd.ncomp;
   for (int i = 0; i < 64 * ncomp; ++i)
     if (quant[i] > 255) return bad("a quantiser above 255 (baseline tables have 8-bit entries)");
-  // Cr shares Cb's table when the two are equal (what libjpeg writes), else it gets a third
-  const bool third = ncomp == 3 && memcmp(quant + 64, quant + 128, 128) != 0;
-  const int n_tables = ncomp == 1 ? 1 : third ? 3 : 2;
 
   Writer w{out, out ? capacity : 0};
-  w.u16(0xFFD8);
-  static const uint8_t app0[] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
-  w.raw(app0, sizeof app0);
-  for (int t = 0; t < n_tables; ++t) {
-    w.u16(0xFFDB), w.u16(67), w.byte((unsigned)t);
-    for (int z = 0; z < 64; ++z) w.byte(quant[64 * t + kNatural[z]]);
-  }
-  w.u16(0xFFC0), w.u16(8 + 3 * (unsigned)ncomp), w.byte(8), w.u16(hd.height), w.u16(hd.width), w.byte((unsigned)ncomp);
-  for (int c = 0; c < ncomp; ++c) {
-    w.byte((unsigned)c + 1);
-    w.byte(c == 0 ? (hd.hs << 4 | hd.vs) : 0x11);
-    w.byte(c == 0 ? 0u : (c == 2 && third) ? 2u : 1u);
-  }
-  const int n_huff = ncomp == 1 ? 1 : 2;
-  w.u16(0xFFC4);
-  w.u16(2 + (unsigned)n_huff * (17 + 12) + 17 + 162 + (n_huff == 2 ? 17 + 162 : 0));
-  dht(w, 0x00, kStdDcLumaBits, kStdDcLumaVals, 12);
-  dht(w, 0x10, kStdAcLumaBits, kStdAcLumaVals, 162);
-  if (n_huff == 2) {
-    dht(w, 0x01, kStdDcChromaBits, kStdDcChromaVals, 12);
-    dht(w, 0x11, kStdAcChromaBits, kStdAcChromaVals, 162);
-  }
-  w.u16(0xFFDA), w.u16(6 + 2 * (unsigned)ncomp), w.byte((unsigned)ncomp);
-  for (int c = 0; c < ncomp; ++c) w.byte((unsigned)c + 1), w.byte(c == 0 ? 0x00 : 0x11);
-  w.byte(0), w.byte(63), w.byte(0);
+  write_header(w, hd, quant);
 
   const uint32_t luma = hd.hs * hd.vs, bpm = ncomp == 1 ? 1u : luma + 2u;
   int pred[3] = {0, 0, 0};

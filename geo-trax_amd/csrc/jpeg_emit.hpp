@@ -27,5 +27,20 @@ bool make_header(int h, int w, int ncomp, int hs, int vs, RecordHeader* hd);
 // yields one). Every record the parser produces from 8-bit pictures is accepted: grayscale, 4:4:4, 4:2:2, 4:2:0.
 int emit(const void* record, size_t bytes, uint8_t* out, size_t capacity, size_t* n, char* msg, size_t msg_cap);
 
+// The picture's header alone, the bytes emit() writes in front of the scan: SOI, APP0, DQT (one table per component; Cr shares
+// Cb's when the two are equal), SOF0, DHT, SOS. It depends on the frame's size, sampling and quantisers only (hd's width, height,
+// ncomp, hs, vs; quant[3][64] in natural order), so both entropy routes call it: emit() per picture, the GPU coder
+// (csrc/jpeg_huff.hip) once per encoder. Returns the header's length and stores the bytes below `capacity`.
+constexpr size_t kMaxHeaderBytes = 704;       // 2 + 18 + 3 * 69 + 19 + 420 + 14 = 680 for three components and three tables
+size_t header(const RecordHeader& hd, const uint16_t* quant, uint8_t* out, size_t capacity);
+
+// The Annex K.3 tables as the encoder reads them: entry = code | length << 16. dc[t][category 0..11], ac[t][run << 4 | size];
+// t = 0 luma, 1 chroma. An entry of 0: the table has no code for the symbol.
+struct HuffCodes {
+  uint32_t dc[2][12];
+  uint32_t ac[2][256];
+};
+void std_huff_codes(HuffCodes* out);
+
 }  // namespace jpeg
 }  // namespace gtx

@@ -4,8 +4,11 @@
 //
 //   jpeg_planes_kernel    BGR -> YCbCr, edges replicated, chroma 2x2-averaged -> u8 planes (Y, Cb, Cr at block-grid size)
 //   jpeg_fdct_kernel      planes -> -128 -> 8x8 forward DCT -> quantise -> zigzag -> dense runs [n_blocks][64] + block lengths
-//   jpeg_scan_*           exclusive prefix sum of the lengths -> the record's offset[] (tile sums, scan of the sums, apply)
+//   jpegscan::scan_*      exclusive prefix sum of the lengths -> the record's offset[] (tile sums, scan of the sums, apply;
+//                         csrc/jpeg_scan.hpp, shared with the entropy coder)
 //   jpeg_compact_kernel   dense runs -> coef[] at the offsets
+//
+// On the GPU entropy route (use_gpu_entropy) the last four are replaced by csrc/jpeg_huff.hip's launches: dense runs -> picture.
 //
 // The arithmetic is libjpeg's default encode, integer throughout (what Pillow and cv2.imwrite produce): the 16-bit fixed-point
 // tables of jccolor.c, h2v2_downsample of jcsample.c with its alternating bias, the slow-integer DCT of jfdctint.c (13-bit
@@ -15,6 +18,7 @@
 
 #include "detector.hpp"
 #include "jpeg_enc.hpp"
+#include "jpeg_scan.hpp"
 
 namespace gtx {
 namespace {
@@ -185,73 +189,6 @@ __global__ __launch_bounds__(kFdctLanes) void jpeg_fdct_kernel(const uint8_t* __
   lens[b] = len;
 }
 
-// ---- exclusive prefix sum of lens[0, n) into offsets[0, n], over tiles of kJpegScanTile lengths
-constexpr int kScanLanes = 256, kScanPer = kJpegScanTile / kScanLanes;
-static_assert(kScanPer * kScanLanes == kJpegScanTile, "a tile is a whole number of lengths per lane");
-
-// the workgroup's inclusive scan of one value per lane; *total: the sum over the workgroup. Every lane must call it.
-__device__ __forceinline__ uint32_t block_scan_inclusive(uint32_t v, uint32_t* s /* [kScanLanes] */, uint32_t* total) {
-  const int t = (int)threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (int off = 1; off < kScanLanes; off <<= 1) {
-    const uint32_t add = t >= off ? s[t - off] : 0u;
-    __syncthreads();
-    s[t] += add;
-    __syncthreads();
-  }
-  const uint32_t incl = s[t];
-  *total = s[kScanLanes - 1];
-  __syncthreads();                                                // s may be written again by the caller's next round
-  return incl;
-}
-
-__global__ __launch_bounds__(kScanLanes) void jpeg_scan_sums_kernel(const uint32_t* __restrict__ lens, uint32_t n, uint32_t* __restrict__ tile_sum) {
-  __shared__ uint32_t s[kScanLanes];
-  const size_t base = (size_t)blockIdx.x * kJpegScanTile + (size_t)threadIdx.x * kScanPer;
-  uint32_t v = 0;
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j)
-    if (base + j < n) v += min(lens[base + j], 64u);
-  uint32_t total;
-  block_scan_inclusive(v, s, &total);
-  if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
-}
-
-// One workgroup: tile_sum[0, n_tiles) -> its exclusive prefix sum in place; the grand total goes to offsets[n] and *total_out.
-__global__ __launch_bounds__(kScanLanes) void jpeg_scan_tiles_kernel(uint32_t* __restrict__ tile_sum, uint32_t n_tiles, uint32_t* __restrict__ closing) {
-  __shared__ uint32_t s[kScanLanes];
-  uint32_t carry = 0;
-  for (uint32_t first = 0; first < n_tiles; first += kScanLanes) {
-    const uint32_t i = first + threadIdx.x;
-    const uint32_t v = i < n_tiles ? tile_sum[i] : 0u;
-    uint32_t total;
-    const uint32_t incl = block_scan_inclusive(v, s, &total);
-    if (i < n_tiles) tile_sum[i] = carry + incl - v;
-    carry += total;
-  }
-  if (threadIdx.x == 0) *closing = carry;
-}
-
-__global__ __launch_bounds__(kScanLanes) void jpeg_scan_apply_kernel(const uint32_t* __restrict__ lens, uint32_t n, const uint32_t* __restrict__ tile_off,
-                                                                     uint32_t* __restrict__ offsets) {
-  __shared__ uint32_t s[kScanLanes];
-  const size_t base = (size_t)blockIdx.x * kJpegScanTile + (size_t)threadIdx.x * kScanPer;
-  uint32_t l[kScanPer], v = 0;
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j) {
-    l[j] = base + j < n ? min(lens[base + j], 64u) : 0u;
-    v += l[j];
-  }
-  uint32_t total;
-  uint32_t run = tile_off[blockIdx.x] + block_scan_inclusive(v, s, &total) - v;
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j) {
-    if (base + j < n) offsets[base + j] = run;
-    run += l[j];
-  }
-}
-
 // One lane per (block, position): coefficient z of block b goes to coef[offset[b] + z] when z is inside the block's run.
 // cap: coefficients the stream has room for (64 per block: never exceeded by offsets the scan made from lengths <= 64).
 __global__ __launch_bounds__(256) void jpeg_compact_kernel(const int16_t* __restrict__ dense, const uint32_t* __restrict__ offsets, uint32_t n_blocks,
@@ -290,12 +227,14 @@ JpegEncoder::JpegEncoder(gtx_ctx* ctx, int h, int w, int quality, int subsamplin
   GTX_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_total_), sizeof(uint32_t), hipHostMallocDefault));
   GTX_HIP(hipEventCreateWithFlags(&e0_, wait_event_flags(true)));
   GTX_HIP(hipEventCreateWithFlags(&e1_, wait_event_flags(true)));
+  GTX_HIP(hipEventCreateWithFlags(&eh_, wait_event_flags(true)));
 }
 
 JpegEncoder::~JpegEncoder() {
   if (in_flight_) (void)hipEventSynchronize(e1_);
   if (e0_) (void)hipEventDestroy(e0_);
   if (e1_) (void)hipEventDestroy(e1_);
+  if (eh_) (void)hipEventDestroy(eh_);
   if (h_total_) (void)hipHostFree(h_total_);
 }
 
@@ -304,7 +243,7 @@ void JpegEncoder::submit(const void* bgr) {
   if (in_flight_) fail(GTX_ERR_INVALID, "jpeg_enc_submit: the frame submitted before has not been collected");
   GTX_HIP(hipSetDevice(ctx_->device));
   hipStream_t s = ctx_->stream;
-  const uint32_t nb = hd_.n_blocks, n_tiles = (nb + kJpegScanTile - 1) / kJpegScanTile;
+  const uint32_t nb = hd_.n_blocks;
   uint32_t* offsets = d_rec_.as<uint32_t>();
   int16_t* coef = reinterpret_cast<int16_t*>(d_rec_.as<uint8_t>() + 4 * ((size_t)nb + 1));
   GTX_HIP(hipEventRecord(e0_, s));
@@ -312,18 +251,54 @@ void JpegEncoder::submit(const void* bgr) {
                      d_planes_.as<uint8_t>());
   hipLaunchKernelGGL(jpeg_fdct_kernel, dim3(cdiv((int)nb, kFdctLanes)), dim3(kFdctLanes), 0, s, d_planes_.as<const uint8_t>(), hd_,
                      d_quant_.as<const uint16_t>(), d_dense_.as<int16_t>(), d_lens_.as<uint32_t>());
-  hipLaunchKernelGGL(jpeg_scan_sums_kernel, dim3(n_tiles), dim3(kScanLanes), 0, s, d_lens_.as<const uint32_t>(), nb, d_tiles_.as<uint32_t>());
-  hipLaunchKernelGGL(jpeg_scan_tiles_kernel, dim3(1), dim3(kScanLanes), 0, s, d_tiles_.as<uint32_t>(), n_tiles, offsets + nb);
-  hipLaunchKernelGGL(jpeg_scan_apply_kernel, dim3(n_tiles), dim3(kScanLanes), 0, s, d_lens_.as<const uint32_t>(), nb, d_tiles_.as<const uint32_t>(), offsets);
+  if (huff_) {                                                    // the GPU entropy route: no record, the picture instead
+    GTX_HIP(hipGetLastError());
+    GTX_HIP(hipEventRecord(eh_, s));
+    huff_->enqueue(d_dense_.as<const int16_t>(), d_lens_.as<const uint32_t>());
+    GTX_HIP(hipEventRecord(e1_, s));
+    in_flight_ = submitted_ = true;
+    return;
+  }
+  jpegscan::scan_launch<uint32_t>(s, d_lens_.as<const uint32_t>(), nb, nullptr, 64u, d_tiles_.as<uint32_t>(), offsets, offsets + nb);
   hipLaunchKernelGGL(jpeg_compact_kernel, dim3((unsigned)(((size_t)nb * 64 + 255) / 256)), dim3(256), 0, s, d_dense_.as<const int16_t>(), offsets, nb,
                      (size_t)64 * nb, coef);
   GTX_HIP(hipGetLastError());
   GTX_HIP(hipEventRecord(e1_, s));
   GTX_HIP(hipMemcpyAsync(h_total_, offsets + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  in_flight_ = true;
+  in_flight_ = submitted_ = true;
+}
+
+void JpegEncoder::use_gpu_entropy() {
+  if (huff_) return;
+  if (submitted_) fail(GTX_ERR_INVALID, "jpeg_enc_set_entropy: the encoder has already been given a frame");
+  GTX_HIP(hipSetDevice(ctx_->device));
+  huff_.reset(new JpegHuff(ctx_, hd_, &quant_[0][0]));
+  d_rec_.release();                                               // no record is made on this route
+  d_tiles_.release();
+}
+
+bool JpegEncoder::collect_jpeg(void* out, size_t capacity, size_t* bytes) {
+  if (!huff_) fail(GTX_ERR_INVALID, "jpeg_enc_collect_jpeg: the encoder is on the host entropy route (gtx_jpeg_enc_collect returns its record)");
+  if (!in_flight_) fail(GTX_ERR_INVALID, "jpeg_enc_collect_jpeg: no frame has been submitted");
+  if (!bytes) fail(GTX_ERR_INVALID, "bytes is NULL");
+  if (!out && capacity) fail(GTX_ERR_INVALID, "jpeg_enc_collect_jpeg: out is NULL with a capacity of %zu", capacity);
+  GTX_HIP(hipSetDevice(ctx_->device));
+  bool fits = false;
+  try {
+    fits = huff_->finish(out, capacity, bytes, nullptr);
+  } catch (...) {
+    in_flight_ = false;                                           // a frame that cannot be coded is given up
+    throw;
+  }
+  if (!fits) return false;
+  GTX_HIP(hipEventElapsedTime(&last_ms_, e0_, e1_));
+  GTX_HIP(hipEventElapsedTime(&entropy_ms_, eh_, e1_));
+  in_flight_ = false;
+  return true;
 }
 
 bool JpegEncoder::collect(void* record, size_t capacity, size_t* bytes) {
+  if (huff_) fail(GTX_ERR_INVALID, "jpeg_enc_collect: the encoder is on the GPU entropy route (gtx_jpeg_enc_collect_jpeg returns its picture)");
   if (!in_flight_) fail(GTX_ERR_INVALID, "jpeg_enc_collect: no frame has been submitted");
   if (!bytes) fail(GTX_ERR_INVALID, "bytes is NULL");
   if (!record && capacity) fail(GTX_ERR_INVALID, "jpeg_enc_collect: record is NULL with a capacity of %zu", capacity);

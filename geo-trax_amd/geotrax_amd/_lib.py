@@ -295,6 +295,12 @@ _SIGNATURES = {
     "gtx_jpeg_enc_last_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "gtx_jpeg_emit": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "gtx_op_jpeg_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gtx_jpeg_enc_set_entropy": (C.c_int, [_P, C.c_int]),
+    "gtx_jpeg_enc_collect_jpeg": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gtx_jpeg_enc_entropy_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "gtx_jpeg_picture_bound": (C.c_size_t, [C.c_int, C.c_int]),
+    "gtx_jpeg_header": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gtx_op_jpeg_huff": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
     "gtx_dev_copy": (C.c_int, [_P, _P, _P, C.c_size_t]),
     "gtx_drawer_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(_P)]),
     "gtx_drawer_destroy": (None, [_P]),

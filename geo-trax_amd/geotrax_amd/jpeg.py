@@ -356,3 +356,182 @@ def encode_dev(ctx: _lib.Context, bgr: np.ndarray, quality: int = 90, subsamplin
         rec = np.zeros((n.value + 3) // 4, np.uint32).view(np.uint8)
     _lib.check(rc)
     return rec[:n.value]
+
+
+# ------------------------------------------------------------------------------------------------- entropy coding on the GPU
+# csrc/jpeg_huff.hip codes the record's blocks on the GPU, byte for byte what record_to_bytes() (the host emitter) writes.
+# block_bits() is the numpy twin of its first kernel; blocks_to_record() builds records no real frame produces, for its tests.
+
+def blocks_to_record(w: int, h: int, ncomp: int, hs: int, vs: int, runs, quant: np.ndarray | None = None) -> np.ndarray:
+    """A record from hand-made blocks: runs[b] is block b's zigzag run (0..64 int16 values, DC first; scan order). ncomp 1
+    (hs = vs = 1) or 3 with luma sampling 1x1, 2x1 or 2x2; quant: uint16 [3][64], default quality 90's tables."""
+    mcus_x, mcus_y = -(-w // (8 * hs)), -(-h // (8 * vs))
+    nb = mcus_x * mcus_y * (1 if ncomp == 1 else hs * vs + 2)
+    if len(runs) != nb:
+        raise ValueError(f"{len(runs)} runs for a frame of {nb} blocks")
+    if quant is None:
+        qt = quality_tables(90)
+        quant = np.stack([qt[0], qt[1], qt[1]])
+    lens = np.array([len(r) for r in runs], np.int64)
+    if lens.max(initial=0) > 64:
+        raise ValueError("a run is longer than 64")
+    offsets = np.zeros(nb + 1, np.uint32)
+    np.cumsum(lens, out=offsets[1:])
+    n_coef = int(offsets[-1])
+    total = OFFSETS_OFFSET + 4 * (nb + 1) + 2 * n_coef
+    rec = np.zeros((total + 3) // 4, np.uint32).view(np.uint8)[:total]
+    bw = [mcus_x * hs, mcus_x, mcus_x][:ncomp] + [0] * (3 - ncomp)
+    bh = [mcus_y * vs, mcus_y, mcus_y][:ncomp] + [0] * (3 - ncomp)
+    rec[:HEADER_BYTES].view(np.uint32)[:17] = [MAGIC, total, w, h, ncomp, hs, vs, mcus_x, mcus_y, nb, n_coef, *bw, *bh]
+    rec[QUANT_OFFSET:OFFSETS_OFFSET].view(np.uint16)[:] = np.asarray(quant, np.uint16).ravel()
+    end = OFFSETS_OFFSET + 4 * (nb + 1)
+    rec[OFFSETS_OFFSET:end].view(np.uint32)[:] = offsets
+    if n_coef:
+        rec[end:].view(np.int16)[:] = np.concatenate([np.asarray(r, np.int16).ravel() for r in runs])
+    return rec
+
+
+def _aligned(rec: np.ndarray) -> np.ndarray:
+    r = np.ascontiguousarray(rec, dtype=np.uint8)
+    if r.ctypes.data & 3:
+        r = np.concatenate([r, np.zeros(3, np.uint8)])[:len(rec)]  # (a fresh allocation is aligned)
+    return r
+
+
+def header_bytes(rec: np.ndarray) -> bytes:
+    """The picture's header for this record (gtx_jpeg_header: SOI .. SOS, the one function both entropy routes call). Host only."""
+    lib = _lib.load()
+    r = _aligned(rec)
+    n = C.c_size_t()
+    out = np.empty(1024, np.uint8)
+    rc = lib.gtx_jpeg_header(_lib.ptr(r), r.nbytes, _lib.ptr(out), out.nbytes, C.byref(n))
+    if rc != 0:
+        raise JpegError(rc, lib.gtx_last_error().decode("utf-8", "replace") if rc < 0 else "the JPEG header did not fit 1024 bytes")
+    return out[:n.value].tobytes()
+
+
+_HUFF_SIZES = None
+
+
+def std_huff_sizes() -> tuple[np.ndarray, np.ndarray]:
+    """Code lengths of the Annex K.3 tables, read out of the DHT segment the library itself writes: dc [2][12] by category,
+    ac [2][256] by run << 4 | size (0: no code); index 0 luma, 1 chroma."""
+    global _HUFF_SIZES
+    if _HUFF_SIZES is None:
+        data = header_bytes(blocks_to_record(8, 8, 3, 1, 1, [[]] * 3))
+        at = 2
+        while data[at + 1] != 0xC4:
+            at += 2 + ((data[at + 2] << 8) | data[at + 3])
+        end = at + 2 + ((data[at + 2] << 8) | data[at + 3])
+        at += 4
+        dc, ac = np.zeros((2, 12), np.int64), np.zeros((2, 256), np.int64)
+        while at < end:
+            cls, t = data[at] >> 4, data[at] & 15
+            counts = data[at + 1:at + 17]
+            at += 17
+            for length, cnt in enumerate(counts, 1):
+                for sym in data[at:at + cnt]:
+                    (ac if cls else dc)[t][sym] = length
+                at += cnt
+        _HUFF_SIZES = (dc, ac)
+    return _HUFF_SIZES
+
+
+def _bit_length(x: np.ndarray) -> np.ndarray:
+    return ((x[..., None] >> np.arange(17)) > 0).sum(-1)
+
+
+def block_bits(rec: np.ndarray) -> np.ndarray:
+    """Numpy twin of jpeg_huff_bits_kernel: the bits the emitter writes for every block, uint32 [n_blocks] -- the DC size code
+    and amplitude (the difference against the block before it of the same component in scan order; a block of length 0 has DC
+    0), per non-zero AC value a run/size code and its amplitude, a ZRL per 16 zeros of a run, and an EOB unless the run is 64
+    long and position 63 is non-zero (zeros at the end of a run inside the record are dropped, as emit() drops them). Raises
+    JpegError (-1) for a value the Annex K.3 tables cannot code."""
+    f, _, offsets, coefs = record_fields(rec)
+    nb = f["n_blocks"]
+    off = offsets.astype(np.int64)
+    lens = off[1:] - off[:-1]
+    z = np.arange(64)
+    inside = z[None, :] < lens[:, None]
+    dense = np.zeros((nb, 64), np.int64)
+    dense[inside] = coefs[:int(off[-1])]
+    luma = f["hs"] * f["vs"]
+    bpm = 1 if f["ncomp"] == 1 else luma + 2
+    b = np.arange(nb)
+    mcu, k = b // bpm, b % bpm
+    if bpm == 1:
+        chroma, before = np.zeros(nb, np.int64), b - 1
+    else:
+        chroma = (k >= luma).astype(np.int64)
+        in_mcu = (k < luma) & (k > 0)
+        before = np.where(in_mcu, b - 1, np.where(k == 0, b - bpm + luma - 1, b - bpm))
+        before[(mcu == 0) & ~in_mcu] = -1
+    dc = dense[:, 0]
+    diff = dc - np.where(before >= 0, dc[np.maximum(before, 0)], 0)
+    s = _bit_length(np.abs(diff))
+    if (s > 11).any():
+        raise JpegError(-1, "JPEG record: a DC difference beyond 11 bits (no Annex K.3 code)")
+    dc_size, ac_size = std_huff_sizes()
+    bits = dc_size[chroma, s] + s
+    run = np.zeros(nb, np.int64)
+    for p in range(1, 64):
+        a = dense[:, p]
+        nz = inside[:, p] & (a != 0)
+        sa = _bit_length(np.abs(a))
+        if (nz & (sa > 10)).any():
+            raise JpegError(-1, "JPEG record: an AC coefficient beyond 10 bits (no Annex K.3 code)")
+        sa = np.minimum(sa, 10)
+        bits += np.where(nz, (run >> 4) * ac_size[chroma, 0xF0] + ac_size[chroma, ((run & 15) << 4) | sa] + sa, 0)
+        run = np.where(nz, 0, np.where(inside[:, p], run + 1, run))
+    eob = ~((lens == 64) & (dense[:, 63] != 0))
+    return (bits + np.where(eob, ac_size[chroma, 0], 0)).astype(np.uint32)
+
+
+def huff_dev(ctx: _lib.Context, rec: np.ndarray, want_bits: bool = False):
+    """One record through gtx_op_jpeg_huff (upload of its dense runs, the GPU entropy coder's launches, the picture at its real
+    length): the bytes, or (bytes, per-block bit counts as uint32 [n_blocks]). Tests, tools."""
+    r = _aligned(rec)
+    lib = ctx.lib
+    n = C.c_size_t()
+    nb = record_fields(r)[0]["n_blocks"]
+    bits = np.zeros(nb, np.uint32) if want_bits else None
+    out = np.empty(r.nbytes + 1024, np.uint8)
+    for _ in range(2):
+        rc = lib.gtx_op_jpeg_huff(ctx.handle, _lib.ptr(r), r.nbytes, _lib.ptr(out), out.nbytes, C.byref(n), _lib.ptr(bits) if want_bits else None)
+        if rc != 1:
+            break
+        out = np.empty(n.value, np.uint8)
+    if rc != 0:
+        raise JpegError(rc, lib.gtx_last_error().decode("utf-8", "replace"))
+    data = out[:n.value].tobytes()
+    return (data, bits) if want_bits else data
+
+
+def encode_jpeg_dev(ctx: _lib.Context, bgr: np.ndarray, quality: int = 90, subsampling: str = "4:2:0") -> bytes:
+    """One host frame through an encoder on the GPU entropy route (gtx_jpeg_enc_set_entropy, _submit_dev, _collect_jpeg): the
+    finished JPEG as it leaves the GPU. Tests, tools."""
+    a = np.ascontiguousarray(bgr, dtype=np.uint8)
+    h, w = a.shape[:2]
+    if subsampling not in SUBSAMPLINGS:
+        raise ValueError(f"JPEG subsampling {subsampling!r}: one of {sorted(SUBSAMPLINGS)}")
+    lib = ctx.lib
+    enc = C.c_void_p()
+    _lib.check(lib.gtx_jpeg_enc_create(ctx.handle, h, w, int(quality), SUBSAMPLINGS[subsampling][2], C.byref(enc)))
+    dptr = None
+    try:
+        _lib.check(lib.gtx_jpeg_enc_set_entropy(enc, 1))
+        dptr = ctx.dev_alloc(a.nbytes)
+        ctx.dev_upload(dptr, a)
+        _lib.check(lib.gtx_jpeg_enc_submit_dev(enc, C.c_void_p(dptr)))
+        n = C.c_size_t()
+        out = np.empty(1 << 16, np.uint8)
+        rc = lib.gtx_jpeg_enc_collect_jpeg(enc, _lib.ptr(out), out.nbytes, C.byref(n))
+        if rc == 1:
+            out = np.empty(n.value, np.uint8)
+            rc = lib.gtx_jpeg_enc_collect_jpeg(enc, _lib.ptr(out), out.nbytes, C.byref(n))
+        _lib.check(rc)
+        return out[:n.value].tobytes()
+    finally:
+        lib.gtx_jpeg_enc_destroy(enc)
+        if dptr is not None:
+            ctx.dev_free(dptr)

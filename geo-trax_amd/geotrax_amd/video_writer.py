@@ -3,7 +3,8 @@ visualisation loop (geotrax/visualize.py:131, :298), for frames that are already
 
 The GPU turns a BGR frame into a packed record of quantised coefficients (csrc/jpeg_enc.hip, a few MB instead of the frame's
 25 MB at 4K), host threads Huffman-code the records into baseline JPEG pictures (csrc/jpeg_emit.cpp; the calls release the
-GIL), and this module stores the pictures: suffix .avi -> RIFF AVI with one `vids` / `MJPG` stream, `00dc` chunks and an
+GIL; with entropy="gpu" the GPU codes the pictures itself, csrc/jpeg_huff.hip, and only the finished picture leaves it), and
+this module stores the pictures: suffix .avi -> RIFF AVI with one `vids` / `MJPG` stream, `00dc` chunks and an
 `idx1` index, continued in `RIFF AVIX` lists before a RIFF would pass `riff_limit` bytes (OpenDML); suffix .mjpeg / .mjpg ->
 the pictures one after the other. frames.AviMjpegReader / MjpegReader read both back.
 """
@@ -132,10 +133,18 @@ class MjpegWriter:
     record is collected when the slot comes round again (or at release()), then Huffman-coded on one of `encode_threads` pool
     threads (a parameter, never the machine's CPU count: the engine has threads of its own). Pictures reach the file strictly
     in submission order. A frame given to write_dev() is read on the context's stream: it must stay unchanged until `ring`
-    further frames have been written or release() has returned, unless what overwrites it is ordered on that stream."""
+    further frames have been written or release() has returned, unless what overwrites it is ordered on that stream.
+
+    entropy="gpu" (default "host") puts the ring's encoders on the GPU entropy route: a collected slot hands over the finished
+    picture, which goes straight to the file; the thread pool is not used. write_record() is host coding on either setting."""
+
+    ENTROPY = ("host", "gpu")
 
     def __init__(self, path, fps: float, size: tuple[int, int], quality: int = 90, subsampling: str = "4:2:0", encode_threads: int = 8,
-                 ctx: _lib.Context | None = None, ring: int = 3, riff_limit: int = 1 << 30):
+                 ctx: _lib.Context | None = None, ring: int = 3, riff_limit: int = 1 << 30, entropy: str = "host"):
+        if entropy not in self.ENTROPY:
+            raise ValueError(f"entropy {entropy!r}: one of {list(self.ENTROPY)}")
+        self.entropy = entropy
         self.path = Path(path)
         self.w, self.h = int(size[0]), int(size[1])
         self.quality = int(quality)
@@ -160,7 +169,7 @@ class MjpegWriter:
         self._max_pending = 2 * int(encode_threads) + self.ring
         self._pending: deque = deque()
         self.frames = 0
-        self.record_bytes = 0                              # of all frames: what left the GPU
+        self.record_bytes = 0                              # of all frames: what left the GPU (records, or pictures with entropy="gpu")
         self._sink = sink(self.path, fps, (self.w, self.h), riff_limit)
 
     def isOpened(self) -> bool:  # noqa: N802 (cv2 naming)
@@ -176,6 +185,8 @@ class MjpegWriter:
                 check(self.lib.gtx_jpeg_enc_create(self._ctx.handle, self.h, self.w, self.quality, jpeg.SUBSAMPLINGS[self.subsampling][2], C.byref(h)))
                 s.enc, s.dbuf, s.busy = h, None, False
                 self._slots.append(s)
+                if self.entropy == "gpu":
+                    check(self.lib.gtx_jpeg_enc_set_entropy(h, 1))
         s = self._slots[self._next]
         self._next = (self._next + 1) % self.ring
         if s.busy:
@@ -184,6 +195,20 @@ class MjpegWriter:
 
     def _collect(self, s: _Slot) -> None:
         n = C.c_size_t()
+        if self.entropy == "gpu":                          # the finished picture: nothing left for the pool
+            pic = np.empty(self._guess, np.uint8)
+            rc = self.lib.gtx_jpeg_enc_collect_jpeg(s.enc, _lib.ptr(pic), pic.nbytes, C.byref(n))
+            if rc == 1:
+                pic = np.empty(n.value, np.uint8)
+                rc = self.lib.gtx_jpeg_enc_collect_jpeg(s.enc, _lib.ptr(pic), pic.nbytes, C.byref(n))
+            check(rc)
+            s.busy = False
+            self._guess = n.value + n.value // 8
+            self.record_bytes += n.value
+            self._drain(True)                              # records given to write_record() before this frame come first
+            self._sink.add(pic[:n.value].tobytes())
+            self.frames += 1
+            return
         rec = np.empty((self._guess + 3) // 4, np.uint32).view(np.uint8)
         rc = self.lib.gtx_jpeg_enc_collect(s.enc, _lib.ptr(rec), rec.nbytes, C.byref(n))
         if rc == 1:                                        # larger than the frame before: its real length is known now

@@ -541,7 +541,7 @@ def visualize_mode(args, viz_mode: int, class_names: dict, viz_config: dict, out
         out.parent.mkdir(parents=True, exist_ok=True)
         nbytes = h * w * 3
         batch, n_written, capacity = 2, 0, 16384
-        writer = MjpegWriter(out, fps, (w, h), quality=quality, ctx=ctx)
+        writer = MjpegWriter(out, fps, (w, h), quality=quality, ctx=ctx, entropy=getattr(args, "entropy", None) or "host")
         keep = writer.ring // batch + 2                    # as geotrax_amd.stabilized_video: a frame stays until the writer's ring has come round
         ring = [ctx.dev_alloc(nbytes) for _ in range(writer.ring)] if viz_mode in (1, 2, 4) else []
         bufs.extend(ring)
@@ -673,6 +673,7 @@ def main(argv=None) -> int:
     add_common_args(opt)
     opt.add_argument("--class-names", "-cn", nargs="+", default=None, metavar="ID=NAME|FILE", help="Class-id -> name mapping.")
     opt.add_argument("--quality", type=int, default=90, help="JPEG quality of the output, 1..100")
+    opt.add_argument("--entropy", choices=["host", "gpu"], default="host", help="Where the output's pictures are Huffman-coded: host threads, or the GPU.")
     add_visualization_args(ap.add_argument_group("Visualization arguments"))
     args = ap.parse_args(argv)
     logger = setup_logger(__name__, getattr(args, "verbose", False), getattr(args, "log_path", None))

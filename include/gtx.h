@@ -72,7 +72,9 @@ extern "C" {
  *     the host) added: the same, the number stays. gtx_drawer_{create, destroy, draw_dev, last_ms}, gtx_op_draw (the visualize stage's
  *     drawing: a primitive list painted into a frame in HBM) and gtx_dev_copy added: new entry points and an opaque handle only, so the
  *     number stays. gtx_op_pool_down added and arch 0 also takes YOLOv9 t / s / m / c tensors (yolov9.yaml: ELAN1 / RepNCSPELAN4, AConv / ADown,
- *     SPPELAN = model.9, Detect = model.22; told by their names like the other families): the same, the number stays. */
+ *     SPPELAN = model.9, Detect = model.22; told by their names like the other families): the same, the number stays.
+ *     gtx_jpeg_enc_{set_entropy, collect_jpeg, entropy_ms}, gtx_jpeg_{picture_bound, header} and gtx_op_jpeg_huff (the JPEG sink's
+ *     entropy coder as HIP kernels, opt-in per encoder) added: new entry points only, so the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -257,6 +259,41 @@ int gtx_jpeg_emit(const void* record, size_t bytes, void* out, size_t capacity, 
  * frame, runs one encoder's chain and returns the record as gtx_jpeg_enc_collect does (0, 1 or a negative status). Sizes,
  * quality and subsampling are checked before the GPU is touched. */
 int gtx_op_jpeg_encode(gtx_ctx* ctx, const uint8_t* bgr, int h, int w, int quality, int subsampling, void* record, size_t capacity, size_t* bytes);
+/* The GPU entropy route: the entropy-coding half of cv2.VideoWriter.write() (geotrax/visualize.py:298) as HIP kernels
+ * (csrc/jpeg_huff.hip) instead of gtx_jpeg_emit on host threads. From the dense zigzag runs the forward DCT leaves in HBM: bits
+ * per block (DC prediction resolved per component in scan order), an exclusive prefix sum of the bit counts, the codes packed
+ * MSB first into a zeroed bit buffer, FF bytes counted, prefix-summed and stuffed, and header + scan + EOI assembled in HBM, so
+ * that one copy of the picture's real length hands over a complete file: byte for byte what gtx_jpeg_emit writes for the
+ * encoder's record. Bit offsets are carried in 64 bits, so every frame size gtx_jpeg_enc_create accepts is accepted here too
+ * (16384 x 16384 in 4:4:4 can need 2.1e10 bits of scan; nothing is refused for its size). */
+/* Replaces cv2.VideoWriter(...), visualize.py:131 (its choice of a codec back-end): gpu != 0 puts the encoder on the GPU entropy
+ * route, 0 leaves it on the host route (the default). Only before the encoder's first submit (GTX_ERR_INVALID afterwards). On
+ * the GPU route gtx_jpeg_enc_submit_dev enqueues the entropy coder behind the forward DCT (the record's offset scan and
+ * compaction are not launched) and still returns without waiting. */
+int gtx_jpeg_enc_set_entropy(gtx_jpeg_enc* enc, int gpu);
+/* Replaces cv2.VideoWriter.write(), visualize.py:298 (the hand-over to the host), on the GPU entropy route: waits for the submitted
+ * frame and copies the finished JPEG at its real length into out[0, capacity). *n receives that length. Returns 0 (filled), 1
+ * (capacity < *n: nothing was copied, the frame stays collectable) or a negative status; GTX_ERR_INVALID on an encoder that is
+ * not on the GPU route (gtx_jpeg_enc_collect is GTX_ERR_INVALID on one that is; either way the frame stays collectable by the
+ * right call), and for a frame with a coefficient the Annex K.3 tables cannot code, as gtx_jpeg_emit. */
+int gtx_jpeg_enc_collect_jpeg(gtx_jpeg_enc* enc, void* out, size_t capacity, size_t* n);
+/* Timing of what replaces cv2.VideoWriter.write(), visualize.py:298: milliseconds of the entropy launches alone of the frame
+ * collected last (gtx_jpeg_enc_last_ms covers the whole chain, these included); 0 on the host route. tools/jpeg_encode_time.py. */
+int gtx_jpeg_enc_entropy_ms(gtx_jpeg_enc* enc, float* ms);
+/* Replaces cv2.VideoWriter.write(), visualize.py:298 (its output buffer): the largest picture the GPU route can produce for an
+ * h x w frame over the accepted samplings -- every block 64 long at the longest codes (22 + 63 * 26 bits), doubled for stuffing,
+ * plus header and EOI. 0 for a size outside 1..16384. */
+size_t gtx_jpeg_picture_bound(int h, int w);
+/* Replaces cv2.VideoWriter.write(), visualize.py:298 (the picture's header; host only, no context): the bytes gtx_jpeg_emit writes
+ * in front of the scan for this record -- SOI, APP0, DQT, SOF0, DHT, SOS -- from the one function both entropy routes call. Only
+ * the record's header and quantisers are read. Returns 0, 1 (capacity < *n) or a negative status, as gtx_jpeg_emit. */
+int gtx_jpeg_header(const void* record, size_t bytes, void* out, size_t capacity, size_t* n);
+/* Replaces cv2.VideoWriter.write(), visualize.py:298 (the entropy-coding half), on host arrays (the operator hook the kernel tests
+ * use): record[0, bytes) as gtx_jpeg_emit takes it (grayscale, 4:4:4, 4:2:2, 4:2:0; from the encoder, the parser or hand-built) is
+ * expanded to dense runs + lengths, uploaded and coded by the GPU route's kernels. out[0, capacity) receives the picture, *n its
+ * length; block_bits (may be NULL) the n_blocks per-block bit counts. Returns 0, 1 (capacity < *n: out untouched) or a negative
+ * status (GTX_ERR_INVALID where gtx_jpeg_emit refuses the record: out untouched). */
+int gtx_op_jpeg_huff(gtx_ctx* ctx, const void* record, size_t bytes, void* out, size_t capacity, size_t* n, uint32_t* block_bits);
 
 /* ------------------------------------------------------------------ operator level
  * Single operators of the detector, exposed so the parity tests can check every kernel

@@ -8,6 +8,9 @@
   * gtx_jpeg_emit: ms per frame on one thread
   * the stage (MjpegWriter.write_dev on frames resident in HBM -> .mjpeg in a temporary directory): frames/s at 4, 8 and 12
     encode threads, three passes each
+  * the GPU entropy route (csrc/jpeg_huff.hip, entropy="gpu") in the same session: GPU time per frame of the whole chain and of
+    the entropy launches alone (gtx_jpeg_enc_entropy_ms), bytes per frame off the GPU on both routes, and the stage's frames/s
+    next to the host route's 4 / 8 / 12-thread figures
   * in the same process, for comparison: the 25 MB download FrameWarper.__call__ does per frame today, and Pillow encoding the
     same frame on one host thread
 """
@@ -88,7 +91,46 @@ def main() -> None:
             t.append(time.perf_counter() - t0)
     say(f"gtx_jpeg_emit: {1e3 * np.median(t):.2f} ms per frame on one thread (median of {len(t)}, min {1e3 * np.min(t):.2f})")
 
+    # the GPU entropy route: the same frames through an encoder that Huffman-codes on the GPU
+    _lib.check(lib.gtx_jpeg_enc_create(ctx.handle, h, w, 90, 2, C.byref(enc)))
+    _lib.check(lib.gtx_jpeg_enc_set_entropy(enc, 1))
+    pic = np.zeros(lib.gtx_jpeg_picture_bound(h, w), np.uint8)
+    ems = C.c_float()
+    pics = []
+    for k in range(4):                                      # pass 0 warms up
+        t_gpu, t_ent, t_collect = [], [], []
+        for p in dptrs * 5:
+            _lib.check(lib.gtx_jpeg_enc_submit_dev(enc, C.c_void_p(p)))
+            t0 = time.perf_counter()
+            _lib.check(lib.gtx_jpeg_enc_collect_jpeg(enc, _lib.ptr(pic), pic.nbytes, C.byref(n)))
+            t_collect.append(time.perf_counter() - t0)
+            _lib.check(lib.gtx_jpeg_enc_last_ms(enc, C.byref(ms)))
+            _lib.check(lib.gtx_jpeg_enc_entropy_ms(enc, C.byref(ems)))
+            t_gpu.append(ms.value)
+            t_ent.append(ems.value)
+            if k == 0 and len(pics) < len(frames):
+                pics.append(pic[:n.value].tobytes())
+        if k:
+            say(f"GPU entropy route, GPU time per frame, pass {k} ({len(t_gpu)} frames): whole chain mean {np.mean(t_gpu):.4f} ms, median {np.median(t_gpu):.4f}, "
+                f"min {np.min(t_gpu):.4f}; the entropy launches alone mean {np.mean(t_ent):.4f} ms, median {np.median(t_ent):.4f}, min {np.min(t_ent):.4f}; "
+                f"submit-to-picture on the host (wait + copy of the picture): median {1e3 * np.median(t_collect):.3f} ms")
+    lib.gtx_jpeg_enc_destroy(enc)
+    assert pics == jpgs, "the GPU route's pictures differ from the emitter's"
+    say(f"bytes per frame off the GPU: host route (the record) {np.mean([r.nbytes for r in recs]):.0f}, GPU route (the picture) {np.mean([len(j) for j in pics]):.0f}, "
+        f"picture bound {lib.gtx_jpeg_picture_bound(h, w)}")
+
     with tempfile.TemporaryDirectory() as d:
+        for k in range(3):
+            path = Path(d) / f"gpu_{k}.mjpeg"
+            t0 = time.perf_counter()
+            wr = MjpegWriter(path, 30.0, (w, h), quality=90, ctx=ctx, entropy="gpu")
+            for i in range(a.frames):
+                wr.write_dev(dptrs[i % len(dptrs)])
+            wr.release()
+            dt = time.perf_counter() - t0
+            say(f"stage (write_dev -> .mjpeg), entropy on the GPU (no encode threads), pass {k}: {a.frames} frames in {dt:.3f} s = {a.frames / dt:.0f} frames/s "
+                f"({path.stat().st_size} bytes, {wr.record_bytes // a.frames} bytes per frame off the GPU)")
+            path.unlink()
         for threads in (4, 8, 12):
             for k in range(3):
                 path = Path(d) / f"t{threads}_{k}.mjpeg"
