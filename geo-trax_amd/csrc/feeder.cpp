@@ -23,6 +23,7 @@
 #include <cerrno>
 #include <condition_variable>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 
@@ -32,6 +33,7 @@
 #include "detector.hpp"
 #include "geometry.hpp"
 #include "jpeg.hpp"
+#include "jpeg_entropy.hpp"
 
 struct gtx_feeder {
   gtx_ctx ctx;                       // device + the copy stream
@@ -52,6 +54,16 @@ struct gtx_feeder {
   std::vector<int32_t> file_index;   // ... which of them holds frame i ...
   std::vector<int64_t> lengths;      // ... and how many compressed bytes it has there (at offsets[i])
   std::vector<uint32_t> slot_len;    // [ring*B] JPEG only: bytes of the record in the pinned slot
+  // JPEG, the GPU entropy route (gtx_feeder_set_jpeg_entropy): a reader thread writes the frame's plan (jpeg::plan(): header walk and
+  // unstuffing) into the slot instead of its record and keeps the compressed bytes; the uploader runs the entropy chain in front of
+  // the pixel kernels and copies the frame's status word back; next() sends a frame whose status is not 0 to the host parser.
+  std::unique_ptr<gtx::JpegEntropy> entropy;
+  gtx::DevBuf dev_plan, fb_rec, fb_planes;   // the plan in HBM; record and planes of a frame next() decodes again on the host
+  std::vector<uint8_t> slot_tag;     // [ring*B] what the pinned slot holds: 0 a record, 1 a plan
+  std::vector<std::vector<uint8_t>> slot_src;   // [ring*B] the compressed bytes of the slot's frame
+  uint32_t* h_status = nullptr;      // pinned [ring*B][2]: the entropy chain's status and rounds used
+  std::atomic<int64_t> stats[3] = {{0}, {0}, {0}};   // frames decoded by the GPU / by the host because plan() said so / by the host after a GPU status
+  int64_t dead_from = -1;            // next(): the batch a frame of which the host parser refused too; nothing from it on is delivered
   std::map<int64_t, std::string> bad;   // JPEG only: frames that could not be decoded; the uploader reports one when it reaches it
   std::vector<int64_t> offsets;      // file mode: payload offset of every frame to deliver, in delivery order
   std::vector<const uint8_t*> mem;   // memory mode: the frames as host pointers (the caller keeps them alive), in delivery order
@@ -84,6 +96,7 @@ struct gtx_feeder {
     if (ctx.stream) (void)hipStreamSynchronize(ctx.stream);
     for (auto e : ev) (void)hipEventDestroy(e);
     if (pinned) (void)hipHostFree(pinned);
+    if (h_status) (void)hipHostFree(h_status);
     if (fd >= 0) ::close(fd);
     if (one_fd >= 0) ::close(one_fd);
     if (!own_stream) ctx.stream = nullptr;   // ~gtx_ctx must not destroy a borrowed stream
@@ -122,6 +135,30 @@ struct gtx_feeder {
     return true;
   }
 
+  // JPEG: frame i's compressed bytes -> its pinned slot, as a plan on the GPU entropy route and as the record otherwise. A frame
+  // plan() hands back (a restart interval), one whose plan does not fit the slot and one whose size is not the feeder's (the host
+  // route words that refusal) are decoded here as on the host route.
+  bool fill_slot(int64_t i, const uint8_t* data, size_t len, std::string& why) {
+    const size_t s = slot_of(i);
+    if (!entropy) return decode_into_slot(i, data, len, why);
+    slot_tag[s] = 0;
+    gtx::jpeg::Info info;
+    size_t needed = 0;
+    char msg[512];
+    const int rc = gtx::jpeg::plan(data, len, (long long)i, &info, pinned + s * src_bytes, src_bytes, &needed, msg, sizeof msg);
+    if (rc < 0) {
+      why = msg;
+      return false;
+    }
+    if (rc != gtx::jpeg::kOk || info.height != h || info.width != w) {
+      return decode_into_slot(i, data, len, why);             // (counted when the frame is delivered: settle_batch)
+    }
+    if (slot_src[s].data() != data) slot_src[s].assign(data, data + len);
+    slot_len[s] = (uint32_t)needed;
+    slot_tag[s] = 1;
+    return true;
+  }
+
   // Frame i is in its slot (why empty) or can never be (the uploader reports it after the batches before it).
   void publish(int64_t i, const std::string& why) {
     {
@@ -134,7 +171,7 @@ struct gtx_feeder {
 
   // reader thread of a JPEG source: pread the compressed bytes, entropy-decode into the pinned slot
   void read_jpeg_loop() {
-    std::vector<uint8_t> buf;
+    std::vector<uint8_t> own;
     for (;;) {
       int64_t i;
       {
@@ -145,6 +182,7 @@ struct gtx_feeder {
         if (stop) return;
       }
       const size_t len = (size_t)lengths[(size_t)i];
+      std::vector<uint8_t>& buf = entropy ? slot_src[slot_of(i)] : own;   // the GPU route keeps the bytes with the slot
       buf.resize(len);
       std::string why;
       size_t got = 0;
@@ -164,7 +202,7 @@ struct gtx_feeder {
         got += (size_t)r;
       }
       if (d >= 0 && d != one_fd) ::close(d);
-      if (why.empty()) decode_into_slot(i, buf.data(), len, why);
+      if (why.empty()) fill_slot(i, buf.data(), len, why);
       publish(i, why);
     }
   }
@@ -203,6 +241,42 @@ struct gtx_feeder {
     }
   }
 
+  // next() on the GPU entropy route, batch j of `count` frames: waits for the batch's event, then has the host parser decode every
+  // frame whose status word is not 0 (not converged and invalid alike) from the bytes kept with its slot: parse() + check_record,
+  // upload, the two pixel kernels, a wait. A frame the parser refuses too throws its message, as the host route reports it.
+  void settle_batch(int64_t j, int count) {
+    GTX_HIP(hipSetDevice(ctx.device));
+    GTX_HIP(hipEventSynchronize(ev[(size_t)(j % ring)]));
+    bool again = false;
+    for (int k = 0; k < count; ++k) {
+      const int64_t i = j * B + k;
+      const size_t s = slot_of(i);
+      if (slot_tag[s] != 1) {                                   // the reader thread decoded it: plan() handed it back
+        ++stats[1];
+        continue;
+      }
+      if (h_status[2 * s] == 0) {
+        ++stats[0];
+        continue;
+      }
+      std::string why;
+      slot_tag[s] = 0;
+      if (!decode_into_slot(i, slot_src[s].data(), slot_src[s].size(), why)) {
+        set_error(why);
+        gtx::fail(GTX_ERR_INTERNAL, "%s", why.c_str());
+      }
+      ++stats[2];
+      if (!fb_rec.p) fb_rec.alloc(src_bytes), fb_planes.alloc(64 * gtx::jpeg::max_blocks(h, w));
+      gtx::jpeg::RecordHeader hd;
+      memcpy(&hd, pinned + s * src_bytes, sizeof hd);
+      GTX_HIP(hipStreamSynchronize(ctx.stream));               // fb_rec may still be read by the frame before
+      GTX_HIP(hipMemcpyAsync(fb_rec.p, pinned + s * src_bytes, slot_len[s], hipMemcpyHostToDevice, ctx.stream));
+      gtx::jpeg_decode_launch(&ctx, fb_rec.p, hd, fb_planes.p, dev.as<uint8_t>() + s * bgr_bytes);
+      again = true;
+    }
+    if (again) GTX_HIP(hipStreamSynchronize(ctx.stream));
+  }
+
   // uploader thread: slots in frame order onto the copy stream, one event per batch (a shorter last batch gets its event
   // when the end of the source is known)
   void upload_loop() {
@@ -229,7 +303,14 @@ struct gtx_feeder {
         if (!end) {
           const size_t s = slot_of(i);
           uint8_t* bgr = dev.as<uint8_t>() + s * bgr_bytes;
-          if (kind == 2) {
+          if (kind == 2 && entropy && slot_tag[s] == 1) {
+            gtx::jpeg::PlanHeader ph;
+            memcpy(&ph, pinned + s * src_bytes, sizeof ph);
+            GTX_HIP(hipMemcpyAsync(dev_plan.p, pinned + s * src_bytes, slot_len[s], hipMemcpyHostToDevice, ctx.stream));   // the plan at its real length
+            entropy->enqueue(dev_plan.as<const uint8_t>(), ph, 0, 0, dev_rec.as<uint8_t>());
+            gtx::jpeg_decode_launch(&ctx, dev_rec.p, gtx::JpegEntropy::record_header(ph), dev_planes.p, bgr);
+            GTX_HIP(hipMemcpyAsync(h_status + 2 * s, entropy->d_result(), 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx.stream));
+          } else if (kind == 2) {
             gtx::jpeg::RecordHeader hd;
             memcpy(&hd, pinned + s * src_bytes, sizeof hd);
             GTX_HIP(hipMemcpyAsync(dev_rec.p, pinned + s * src_bytes, slot_len[s], hipMemcpyHostToDevice, ctx.stream));
@@ -380,6 +461,34 @@ int gtx_feeder_open_jpeg(gtx_feeder* f, const char* const* paths, int n_paths, c
   });
 }
 
+int gtx_feeder_set_jpeg_entropy(gtx_feeder* f, int gpu) {
+  return guarded([&] {
+    if (!f) gtx::fail(GTX_ERR_INVALID, "feeder_set_jpeg_entropy: feeder is NULL");
+    if (f->kind != 2) gtx::fail(GTX_ERR_INVALID, "feeder_set_jpeg_entropy: the feeder was created with kind %d, not 2", f->kind);
+    if (f->fd >= 0 || f->one_fd >= 0 || !f->paths.empty() || f->uploader.joinable()) gtx::fail(GTX_ERR_INVALID, "feeder_set_jpeg_entropy: the feeder already has a source");
+    if (!gpu) {
+      f->entropy.reset();
+      return;
+    }
+    if (f->entropy) return;
+    GTX_HIP(hipSetDevice(f->ctx.device));
+    const size_t slots = (size_t)f->ring * f->B;
+    if (!f->h_status) GTX_HIP(hipHostMalloc((void**)&f->h_status, slots * 2 * sizeof(uint32_t), hipHostMallocDefault));
+    f->dev_plan.alloc(f->src_bytes);
+    f->slot_tag.assign(slots, 0);
+    f->slot_src.assign(slots, std::vector<uint8_t>());
+    f->entropy.reset(new gtx::JpegEntropy(&f->ctx, gtx::jpeg::max_blocks(f->h, f->w), f->src_bytes > gtx::jpeg::kPlanStreamOffset ? f->src_bytes - gtx::jpeg::kPlanStreamOffset : 4,   // (a smaller slot holds no plan)
+                                             gtx::kJpegEntropySubBits));
+  });
+}
+
+int gtx_feeder_jpeg_stats(gtx_feeder* f, int64_t out[3]) {
+  return guarded([&] {
+    if (!f || !out) gtx::fail(GTX_ERR_INVALID, "feeder_jpeg_stats: NULL argument");
+    for (int k = 0; k < 3; ++k) out[k] = f->stats[k].load();
+  });
+}
+
 int gtx_feeder_open_push(gtx_feeder* f) {
   return guarded([&] {
     if (!f) gtx::fail(GTX_ERR_INVALID, "feeder is NULL");
@@ -403,7 +512,7 @@ int gtx_feeder_push(gtx_feeder* f, const void* frame, size_t bytes) {
     }
     if (f->kind == 2) {                                  // a compressed frame: decoded here, on the producer's thread
       std::string why;
-      f->decode_into_slot(i, static_cast<const uint8_t*>(frame), bytes, why);
+      f->fill_slot(i, static_cast<const uint8_t*>(frame), bytes, why);
       f->publish(i, why);
       if (!why.empty()) gtx::fail(GTX_ERR_INVALID, "%s", why.c_str());
       return;
@@ -430,7 +539,7 @@ int gtx_feeder_push_at(gtx_feeder* f, int64_t i, const void* frame, size_t bytes
     }
     if (f->kind == 2) {
       std::string why;
-      f->decode_into_slot(i, static_cast<const uint8_t*>(frame), bytes, why);
+      f->fill_slot(i, static_cast<const uint8_t*>(frame), bytes, why);
       {
         std::lock_guard<std::mutex> lk(f->m);
         if (i + 1 > f->next_read) f->next_read = i + 1;
@@ -477,10 +586,24 @@ int gtx_feeder_next(gtx_feeder* f, void** dptr, int* n, int64_t* batch_index) {
     if (!f || !dptr || !n) gtx::fail(GTX_ERR_INVALID, "feeder_next: NULL argument");
     std::unique_lock<std::mutex> lk(f->m);
     f->cv.wait(lk, [&] { return !f->error.empty() || f->issued > f->handed || (f->n_frames >= 0 && f->handed >= f->n_batches()); });
-    if (f->issued > f->handed) {                       // batches that arrived before a failure are still delivered
-      const int64_t j = f->handed++;
+    if (f->issued > f->handed && (f->dead_from < 0 || f->handed < f->dead_from)) {   // batches that arrived before a failure are still delivered
+      const int64_t j = f->handed;
+      const int count = (int)((f->n_frames >= 0 && (j + 1) * f->B > f->n_frames) ? f->n_frames - j * f->B : f->B);
+      if (f->entropy) {                                // the GPU entropy route: the batch's status words decide who decoded it
+        lk.unlock();
+        try {
+          f->settle_batch(j, count);
+        } catch (const std::exception& e) {               // the parser's refusal or a HIP failure: every later call reports it too
+          f->set_error(e.what());
+          lk.lock();
+          f->dead_from = j;
+          throw;
+        }
+        lk.lock();
+      }
+      f->handed = j + 1;
       *dptr = f->dev.as<uint8_t>() + (size_t)(j % f->ring) * f->B * f->bgr_bytes;
-      *n = (int)((f->n_frames >= 0 && (j + 1) * f->B > f->n_frames) ? f->n_frames - j * f->B : f->B);
+      *n = count;
       if (batch_index) *batch_index = j;
       return;
     }

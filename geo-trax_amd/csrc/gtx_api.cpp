@@ -19,6 +19,7 @@
 #include "gmc_feat.hpp"
 #include "jpeg.hpp"
 #include "jpeg_enc.hpp"
+#include "jpeg_entropy.hpp"
 #include "register.hpp"
 #include "sift.hpp"
 #include "sift_stab.hpp"
@@ -731,6 +732,28 @@ int gtx_jpeg_parse(const void* bytes, size_t n, int64_t frame, int* h, int* w, i
   return st != GTX_OK ? st : rc;
 }
 
+size_t gtx_jpeg_plan_bound(int h, int w) {
+  return (h <= 0 || w <= 0 || h > gtx::jpeg::kMaxDim || w > gtx::jpeg::kMaxDim) ? 0 : gtx::jpeg::plan_bound(h, w);
+}
+
+int gtx_jpeg_plan(const void* bytes, size_t n, int64_t frame, int* h, int* w, int* ncomp, int* hs, int* vs, void* out, size_t capacity, size_t* needed) {
+  int rc = 0;
+  const int st = guarded([&] {
+    need(bytes, "bytes"); need(needed, "needed");
+    if (!out && capacity) gtx::fail(GTX_ERR_INVALID, "jpeg_plan: out is NULL with a capacity of %zu", capacity);
+    gtx::jpeg::Info info;
+    char msg[512];
+    rc = gtx::jpeg::plan(static_cast<const uint8_t*>(bytes), n, (long long)frame, &info, out, capacity, needed, msg, sizeof msg);
+    if (h) *h = info.height;
+    if (w) *w = info.width;
+    if (ncomp) *ncomp = info.ncomp;
+    if (hs) *hs = info.hs;
+    if (vs) *vs = info.vs;
+    if (rc < 0) gtx::fail(rc, "%s", msg);
+  });
+  return st != GTX_OK ? st : rc;
+}
+
 int gtx_jpeg_probe(const void* bytes, size_t n, int64_t frame, int* h, int* w, int* ncomp, int* hs, int* vs) {
   return guarded([&] {
     need(bytes, "bytes");
@@ -799,6 +822,54 @@ int gtx_jpeg_kernel_ms(gtx_ctx* ctx, const void* record, size_t bytes, int h, in
     for (auto x : e) (void)hipEventDestroy(x);
     for (int k = 0; k < 3; ++k) ms[k] = (float)(sum[k] / reps);
     if (!yuv_dptr) ms[2] = 0.f;
+  });
+}
+
+int gtx_jpeg_entropy_ms(gtx_ctx* ctx, const void* plan, size_t bytes, int sub_bits, int rounds, int reps, float ms[2], int* status, int* rounds_used) {
+  return guarded([&] {
+    need(plan, "plan"); need(ms, "ms"); need(status, "status"); need(rounds_used, "rounds_used");
+    char msg[256];
+    if (gtx::jpeg::check_plan(plan, bytes, msg, sizeof msg) != 0) gtx::fail(GTX_ERR_INVALID, "%s", msg);
+    if (sub_bits != 0 && !gtx::jpeg_entropy_sub_bits_ok(sub_bits)) gtx::fail(GTX_ERR_INVALID, "jpeg_entropy_ms: sub_bits %d", sub_bits);
+    if (rounds < 0 || rounds > gtx::kJpegEntropyMaxRounds) gtx::fail(GTX_ERR_INVALID, "jpeg_entropy_ms: %d rounds", rounds);
+    if (reps < 1 || reps > 10000) gtx::fail(GTX_ERR_INVALID, "jpeg_entropy_ms: %d repetitions", reps);
+    gtx::jpeg::PlanHeader ph;
+    memcpy(&ph, plan, sizeof ph);
+    if (ph.stream_bytes > (1u << 28)) gtx::fail(GTX_ERR_INVALID, "jpeg_entropy_ms: more than 256 MB of entropy-coded data");
+    need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t nb = ph.n_blocks;
+    const gtx::jpeg::RecordHeader hd = gtx::JpegEntropy::record_header(ph);
+    gtx::DevBuf d_plan(bytes), d_rec(gtx::jpeg::record_bytes(nb, 64 * nb)), d_planes(gtx::jpeg::planes_bytes(hd)), d_bgr((size_t)ph.height * ph.width * 3);
+    GTX_HIP(hipMemcpyAsync(d_plan.p, plan, bytes, hipMemcpyHostToDevice, ctx->stream));
+    gtx::JpegEntropy dec(ctx, nb, ph.stream_bytes, sub_bits ? sub_bits : gtx::kJpegEntropySubBits);
+    hipEvent_t e[3];
+    for (auto& x : e) GTX_HIP(hipEventCreate(&x));
+    double sum[2] = {0, 0};
+    try {
+      for (int r = -1; r < reps; ++r) {                          // one untimed pass first
+        GTX_HIP(hipEventRecord(e[0], ctx->stream));
+        dec.enqueue(d_plan.as<const uint8_t>(), ph, sub_bits, rounds, d_rec.as<uint8_t>());
+        GTX_HIP(hipEventRecord(e[1], ctx->stream));
+        gtx::jpeg_decode_launch(ctx, d_rec.p, hd, d_planes.p, d_bgr.p);
+        GTX_HIP(hipEventRecord(e[2], ctx->stream));
+        GTX_HIP(hipEventSynchronize(e[2]));
+        if (r < 0) continue;
+        for (int k = 0; k < 2; ++k) {
+          float t = 0;
+          GTX_HIP(hipEventElapsedTime(&t, e[k], e[k + 1]));
+          sum[k] += t;
+        }
+      }
+    } catch (...) {
+      for (auto x : e) (void)hipEventDestroy(x);
+      throw;
+    }
+    for (auto x : e) (void)hipEventDestroy(x);
+    for (int k = 0; k < 2; ++k) ms[k] = (float)(sum[k] / reps);
+    uint32_t res[2];
+    GTX_HIP(hipMemcpy(res, dec.d_result(), sizeof res, hipMemcpyDeviceToHost));
+    *status = (int)res[0], *rounds_used = (int)res[1];
   });
 }
 

@@ -20,6 +20,7 @@
 #include "geometry.hpp"
 #include "gmc.hpp"
 #include "jpeg_enc.hpp"
+#include "jpeg_entropy.hpp"
 #include "match_l2.hpp"
 #include "op_staging.hpp"
 #include "pool_down.hpp"
@@ -1242,6 +1243,46 @@ int gtx_op_jpeg_huff(gtx_ctx* ctx, const void* record, size_t bytes, void* out, 
     gtx::JpegHuff huff(ctx, hd, quant);
     huff.enqueue(d_dense.as<const int16_t>(), d_lens.as<const uint32_t>());
     fits = huff.finish(out, capacity, n, block_bits);
+  });
+  return st != GTX_OK ? st : fits ? 0 : 1;
+}
+
+// ---- the GPU entropy decoder on a host plan (tests/test_jpeg_entropy_ops_gpu.py)
+
+int gtx_op_jpeg_entropy(gtx_ctx* ctx, const void* plan, size_t bytes, int sub_bits, int rounds, void* record, size_t capacity, size_t* record_bytes,
+                        int* status, int* rounds_used) {
+  bool fits = true;
+  const int st = guarded([&] {
+    need(plan, "plan"); need(record_bytes, "record_bytes"); need(status, "status"); need(rounds_used, "rounds_used");
+    *record_bytes = 0, *status = 0, *rounds_used = 0;
+    if (!record && capacity) op_bad("jpeg_entropy", "record is NULL with a capacity");
+    if (record && (reinterpret_cast<uintptr_t>(record) & 3)) op_bad("jpeg_entropy", "the record buffer is not 4-byte aligned");
+    if (sub_bits != 0 && !gtx::jpeg_entropy_sub_bits_ok(sub_bits)) op_bad("jpeg_entropy", "sub_bits is none of 0 (the production choice), 256, 512, 1024, 2048");
+    if (rounds < 0 || rounds > gtx::kJpegEntropyMaxRounds) op_bad("jpeg_entropy", "rounds is outside 0 (the production choice), 1..64");
+    char msg[256];
+    if (gtx::jpeg::check_plan(plan, bytes, msg, sizeof msg) != 0) gtx::fail(GTX_ERR_INVALID, "%s", msg);
+    gtx::jpeg::PlanHeader ph;
+    memcpy(&ph, plan, sizeof ph);
+    if (ph.stream_bytes > (1u << 28)) op_bad("jpeg_entropy", "more than 256 MB of entropy-coded data");
+    need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t nb = ph.n_blocks, bound = gtx::jpeg::record_bytes(nb, 64 * nb);
+    gtx::DevBuf d_plan, d_rec(bound);
+    upload(d_plan, plan, bytes);
+    gtx::JpegEntropy dec(ctx, nb, ph.stream_bytes, sub_bits ? sub_bits : gtx::kJpegEntropySubBits);
+    dec.enqueue(d_plan.as<const uint8_t>(), ph, sub_bits, rounds, d_rec.as<uint8_t>());
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    uint32_t res[2];
+    GTX_HIP(hipMemcpy(res, dec.d_result(), sizeof res, hipMemcpyDeviceToHost));
+    *status = (int)res[0], *rounds_used = (int)res[1];
+    if (res[0] != 0) return;                                      // no record: the host parser says what is wrong with the frame
+    gtx::jpeg::RecordHeader hd;
+    GTX_HIP(hipMemcpy(&hd, d_rec.p, sizeof hd, hipMemcpyDeviceToHost));
+    if (hd.n_blocks != nb || hd.n_coef > 64 * nb || hd.bytes != gtx::jpeg::record_bytes(nb, hd.n_coef))
+      gtx::fail(GTX_ERR_INTERNAL, "jpeg_entropy: the device reports a record of %u bytes for %zu blocks", hd.bytes, nb);
+    *record_bytes = hd.bytes;
+    fits = capacity >= hd.bytes;
+    if (fits) download(record, d_rec, hd.bytes);
   });
   return st != GTX_OK ? st : fits ? 0 : 1;
 }

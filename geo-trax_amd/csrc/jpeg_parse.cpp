@@ -139,7 +139,9 @@ struct Parser {
 
   void segments(Info* info);
   void sof(unsigned m, size_t at, size_t len, Info* info);
+  void geometry(RecordHeader* hd) const;
   int scan(void* record, size_t capacity, size_t* needed);
+  int write_plan(void* out, size_t capacity, size_t* needed);
 };
 
 const char* sof_name(unsigned m) {
@@ -268,18 +270,25 @@ void Parser::segments(Info* info) {
   }
 }
 
-// Decodes the scan into the record. Returns kOk or kTooSmall; *needed is the record's size either way.
-int Parser::scan(void* record, size_t capacity, size_t* needed) {
+// The record header's geometry fields from the frame header (n_coef and bytes stay 0).
+void Parser::geometry(RecordHeader* out) const {
   RecordHeader hd;
   memset(&hd, 0, sizeof hd);
   hd.magic = kMagic;
   hd.width = (uint32_t)width, hd.height = (uint32_t)height, hd.ncomp = (uint32_t)ncomp, hd.hs = (uint32_t)hs, hd.vs = (uint32_t)vs;
   hd.mcus_x = (uint32_t)((width + 8 * hs - 1) / (8 * hs)), hd.mcus_y = (uint32_t)((height + 8 * vs - 1) / (8 * vs));
   const int bpm = ncomp == 1 ? 1 : hs * vs + 2;
-  const size_t n_mcu = (size_t)hd.mcus_x * hd.mcus_y, n_blocks = n_mcu * (size_t)bpm;
-  hd.n_blocks = (uint32_t)n_blocks;
+  hd.n_blocks = (uint32_t)((size_t)hd.mcus_x * hd.mcus_y * (size_t)bpm);
   hd.bw[0] = hd.mcus_x * (uint32_t)hs, hd.bh[0] = hd.mcus_y * (uint32_t)vs;
   for (int c = 1; c < ncomp; ++c) hd.bw[c] = hd.mcus_x, hd.bh[c] = hd.mcus_y;
+  *out = hd;
+}
+
+// Decodes the scan into the record. Returns kOk or kTooSmall; *needed is the record's size either way.
+int Parser::scan(void* record, size_t capacity, size_t* needed) {
+  RecordHeader hd;
+  geometry(&hd);
+  const size_t n_mcu = (size_t)hd.mcus_x * hd.mcus_y, n_blocks = hd.n_blocks;
 
   uint8_t* rec = static_cast<uint8_t*>(record);
   const size_t coef_base = kOffsetsOffset + 4 * (n_blocks + 1);
@@ -359,7 +368,81 @@ int Parser::scan(void* record, size_t capacity, size_t* needed) {
   for (int c = 0; c < 3; ++c) memcpy(rec + kQuantOffset + 128 * (size_t)c, quant[comp_tq[c < ncomp ? c : 0]], 128);
   return kOk;
 }
+
+// The plan of jpeg_parse.hpp for the frame whose header segments() has walked; pos is at the first entropy-coded byte.
+int Parser::write_plan(void* out, size_t capacity, size_t* needed) {
+  uint8_t* dst = static_cast<uint8_t*>(out);
+  // fill()'s walk over the segment, a run of plain bytes at a time: FF 00 is an FF, any other FF (or one the data ends on) ends it.
+  // Once to measure, and only when the plan fits once more to copy: a plan that does not fit leaves `out` untouched.
+  auto walk = [&](uint8_t* to) {
+    size_t len = 0, at = pos;
+    while (at < n) {
+      const uint8_t* ff = static_cast<const uint8_t*>(memchr(p + at, 0xFF, n - at));
+      const size_t run = ff ? (size_t)(ff - (p + at)) : n - at;
+      if (to && run) memcpy(to + len, p + at, run);
+      len += run, at += run;
+      if (!ff || at + 1 >= n || p[at + 1] != 0) break;
+      if (to) to[len] = 0xFF;
+      len += 1, at += 2;
+    }
+    return len;
+  };
+  const size_t len = walk(nullptr);
+  const size_t padded = (len + 3) / 4 * 4, total = kPlanStreamOffset + padded;
+  if (needed) *needed = total;
+  if (!dst || capacity < total) return kTooSmall;
+  walk(dst + kPlanStreamOffset);
+  memset(dst + kPlanStreamOffset + len, 0, padded - len);
+  RecordHeader g;
+  geometry(&g);
+  PlanHeader ph;
+  memset(&ph, 0, sizeof ph);
+  ph.magic = kPlanMagic, ph.bytes = (uint32_t)total;
+  ph.width = g.width, ph.height = g.height, ph.ncomp = g.ncomp, ph.hs = g.hs, ph.vs = g.vs, ph.mcus_x = g.mcus_x, ph.mcus_y = g.mcus_y, ph.n_blocks = g.n_blocks;
+  for (int c = 0; c < 3; ++c) ph.bw[c] = g.bw[c], ph.bh[c] = g.bh[c];
+  ph.restart = (uint32_t)restart;
+  for (int c = 0; c < ncomp; ++c) ph.td[c] = (uint32_t)scan_td[c], ph.ta[c] = (uint32_t)scan_ta[c];
+  ph.stream_bytes = (uint32_t)len, ph.stream_bits = 8 * (uint64_t)len;
+  memcpy(dst, &ph, sizeof ph);
+  for (int c = 0; c < 3; ++c) memcpy(dst + kPlanQuantOffset + 128 * (size_t)c, quant[comp_tq[c < ncomp ? c : 0]], 128);
+  memset(dst + kPlanHuffOffset, 0, 6 * sizeof(PlanHuff));
+  for (int c = 0; c < ncomp; ++c)
+    for (int cls = 0; cls < 2; ++cls) {
+      const Huff& t = cls ? ac[scan_ta[c]] : dc[scan_td[c]];
+      PlanHuff h;
+      memset(&h, 0, sizeof h);
+      memcpy(h.look, t.look, sizeof h.look);
+      for (int l = 1; l <= 16; ++l) h.maxcode[l] = t.maxcode[l], h.valoff[l] = t.valoff[l];
+      h.maxcode[0] = h.maxcode[17] = -1;
+      memcpy(h.vals, t.vals, (size_t)t.nvals);
+      h.nvals = (uint32_t)t.nvals;
+      memcpy(dst + kPlanHuffOffset + sizeof(PlanHuff) * (size_t)(3 * cls + c), &h, sizeof h);
+    }
+  return kOk;
+}
 }  // namespace
+
+size_t plan_bound(int h, int w) {
+  const size_t blocks = max_blocks(h, w);
+  return blocks ? kPlanStreamOffset + ((blocks * kMaxBlockBits + 7) / 8 + 3) / 4 * 4 : 0;
+}
+
+int plan(const uint8_t* bytes, size_t n, long long frame, Info* info, void* out, size_t capacity, size_t* needed, char* msg, size_t msg_cap) {
+  if (msg && msg_cap) msg[0] = 0;
+  if (needed) *needed = 0;
+  Parser ps;
+  ps.p = bytes, ps.n = n, ps.frame = frame, ps.msg = msg, ps.msg_cap = msg_cap;
+  try {
+    if (!bytes) ps.fail(kInvalid, "no data");
+    if (out && (reinterpret_cast<uintptr_t>(out) & 3)) ps.fail(kInvalid, "the plan buffer is not 4-byte aligned");
+    ps.segments(info);
+    if (ps.restart) return kHostRoute;
+    if (n - ps.pos > ((size_t)1 << 31)) return kHostRoute;       // the plan's 32-bit sizes
+    return ps.write_plan(out, capacity, needed);
+  } catch (const Failure& f) {
+    return f.code;
+  }
+}
 
 size_t max_blocks(int h, int w) {
   if (h <= 0 || w <= 0) return 0;
@@ -408,6 +491,33 @@ int probe(const uint8_t* bytes, size_t n, long long frame, Info* info, char* msg
   } catch (const Failure& f) {
     return f.code;
   }
+}
+
+int check_plan(const void* plan, size_t bytes, char* msg, size_t msg_cap) {
+  auto bad = [&](const char* what) {
+    if (msg && msg_cap) snprintf(msg, msg_cap, "JPEG plan: %s", what);
+    return kInvalid;
+  };
+  if (!plan || bytes < kPlanStreamOffset || (reinterpret_cast<uintptr_t>(plan) & 3)) return bad("shorter than its header and tables, or misaligned");
+  PlanHeader ph;
+  memcpy(&ph, plan, sizeof ph);
+  if (ph.magic != kPlanMagic) return bad("wrong magic");
+  if (ph.bytes != bytes) return bad("its length field differs from the bytes handed in");
+  if (ph.restart != 0) return bad("a restart interval");
+  if (ph.stream_bytes > (1u << 31) || kPlanStreamOffset + ((size_t)ph.stream_bytes + 3) / 4 * 4 != bytes || ph.stream_bits != 8 * (uint64_t)ph.stream_bytes)
+    return bad("its sizes do not add up to its length");
+  const int w = (int)ph.width, h = (int)ph.height;
+  if (w <= 0 || h <= 0 || w > kMaxDim || h > kMaxDim) return bad("frame size");
+  if (ph.ncomp != 1 && ph.ncomp != 3) return bad("component count");
+  const bool samp = ph.ncomp == 1 ? (ph.hs == 1 && ph.vs == 1) : ((ph.hs == 1 && ph.vs == 1) || (ph.hs == 2 && ph.vs == 1) || (ph.hs == 2 && ph.vs == 2));
+  if (!samp) return bad("sampling factors");
+  if (ph.mcus_x != ((uint32_t)w + 8 * ph.hs - 1) / (8 * ph.hs) || ph.mcus_y != ((uint32_t)h + 8 * ph.vs - 1) / (8 * ph.vs)) return bad("MCU grid");
+  const uint32_t bpm = ph.ncomp == 1 ? 1 : ph.hs * ph.vs + 2;
+  if (ph.n_blocks != ph.mcus_x * ph.mcus_y * bpm) return bad("block count");
+  if (ph.bw[0] != ph.mcus_x * ph.hs || ph.bh[0] != ph.mcus_y * ph.vs) return bad("luma block grid");
+  for (uint32_t c = 1; c < 3; ++c)
+    if (ph.bw[c] != (c < ph.ncomp ? ph.mcus_x : 0u) || ph.bh[c] != (c < ph.ncomp ? ph.mcus_y : 0u)) return bad("chroma block grid");
+  return kOk;
 }
 
 int check_record(const void* record, size_t bytes, int h, int w, char* msg, size_t msg_cap) {

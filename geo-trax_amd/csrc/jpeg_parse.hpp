@@ -59,6 +59,58 @@ int parse(const uint8_t* bytes, size_t n, long long frame, Info* info, void* rec
 // there (n need not reach the entropy-coded data). kOk: parse() would go on to decode the scan of this variant.
 int probe(const uint8_t* bytes, size_t n, long long frame, Info* info, char* msg, size_t msg_cap);
 
+// ---- the GPU entropy route (csrc/jpeg_entropy.hip): the host only walks the header and removes the byte stuffing
+//
+// Plan (little endian, 4-byte aligned):
+//   PlanHeader                         112 bytes
+//   uint16 quant[3][64]                as the record carries them
+//   PlanHuff huff[6]                   the scan's tables by component: huff[c] decodes component c's DC symbols, huff[3 + c] its AC
+//                                      symbols (a component the frame does not have: zeros)
+//   uint8  stream[stream_bytes]        the entropy-coded segment with the stuffing removed (FF 00 -> FF), ended where the parser's
+//                                      bit reader stops: the first FF that no 00 follows, or the end of the data; zeros up to a
+//                                      multiple of 4 follow
+constexpr uint32_t kPlanMagic = 0x3150474au;  // "JGP1"
+constexpr int kHostRoute = 2;                 // plan(): a frame the GPU route does not take (restart intervals); parse() decodes it
+
+struct PlanHuff {
+  uint16_t look[512];                        // 9 leading bits -> (length << 8 | symbol), 0 = longer than 9 bits or no code
+  int32_t maxcode[18];                       // [l], l = 1..16: largest code of length l, -1 if none
+  int32_t valoff[18];                        // [l]: vals index of the first code of length l, minus that code
+  uint8_t vals[256];
+  uint32_t nvals, reserved;
+};
+static_assert(sizeof(PlanHuff) == 1432, "plan table layout");
+
+struct PlanHeader {
+  uint32_t magic, bytes;                     // bytes: the whole plan
+  uint32_t width, height, ncomp, hs, vs, mcus_x, mcus_y, n_blocks;
+  uint32_t bw[3], bh[3];
+  uint32_t restart;                          // the restart interval: 0 in every plan plan() writes
+  uint32_t td[3], ta[3];                     // the SOS header's table selectors, by component
+  uint32_t stream_bytes, reserved;
+  uint64_t stream_bits;                      // bits of the clean stream: 8 * stream_bytes
+};
+static_assert(sizeof(PlanHeader) == 112, "plan header layout");
+constexpr size_t kPlanQuantOffset = sizeof(PlanHeader);
+constexpr size_t kPlanHuffOffset = kPlanQuantOffset + 3 * 64 * sizeof(uint16_t);
+constexpr size_t kPlanStreamOffset = kPlanHuffOffset + 6 * sizeof(PlanHuff);
+static_assert(kPlanStreamOffset % 16 == 0, "the stream starts 16-byte aligned");
+
+// Most bits one block can take in any baseline scan: 64 symbols of a 16-bit code and a 15-bit amplitude.
+constexpr size_t kMaxBlockBits = 64 * 31;
+// Largest plan a decodable frame of h x w can need (every block kMaxBlockBits long, a padded last byte).
+size_t plan_bound(int h, int w);
+
+// The header half of parse() and the unstuffing: bytes[0, n) -> the plan in out[0, capacity) (4-byte aligned; may be NULL with
+// capacity 0). Every refusal parse() makes up to and including the SOS header is made here with the same message. Returns kOk
+// (plan written), kTooSmall (not written: call again with *needed bytes), kHostRoute (a restart interval: *needed is 0, nothing
+// is written, *info is filled), kUnsupported or kInvalid. No byte outside bytes[0, n) is read, none outside out[0, capacity) written.
+int plan(const uint8_t* bytes, size_t n, long long frame, Info* info, void* out, size_t capacity, size_t* needed, char* msg, size_t msg_cap);
+
+// What the entropy kernels rely on in a plan: its sizes consistent with each other and with its length, a geometry parse() would
+// have produced, no restart interval. (The tables are not trusted: the kernels bound every look-up themselves.) kOk or kInvalid.
+int check_plan(const void* plan, size_t bytes, char* msg, size_t msg_cap);
+
 // What the device code relies on: sizes consistent with each other and with h x w, offsets monotone, every block at most 64
 // long, the closing offset equal to the stream length, the record exactly `bytes` long. kOk or kInvalid with a message.
 int check_record(const void* record, size_t bytes, int h, int w, char* msg, size_t msg_cap);

@@ -288,6 +288,12 @@ _SIGNATURES = {
     "gtx_jpeg_probe": (C.c_int, [_P, C.c_size_t, C.c_int64] + [C.POINTER(C.c_int)] * 5),
     "gtx_jpeg_kernel_ms": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_float)]),
     "gtx_feeder_open_jpeg": (C.c_int, [_P, C.POINTER(C.c_char_p), C.c_int, _P, _P, _P, C.c_int64, C.c_int]),
+    "gtx_jpeg_plan_bound": (C.c_size_t, [C.c_int, C.c_int]),
+    "gtx_jpeg_plan": (C.c_int, [_P, C.c_size_t, C.c_int64] + [C.POINTER(C.c_int)] * 5 + [_P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gtx_op_jpeg_entropy": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gtx_jpeg_entropy_ms": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gtx_feeder_set_jpeg_entropy": (C.c_int, [_P, C.c_int]),
+    "gtx_feeder_jpeg_stats": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "gtx_jpeg_enc_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "gtx_jpeg_enc_destroy": (None, [_P]),
     "gtx_jpeg_enc_submit_dev": (C.c_int, [_P, _P]),

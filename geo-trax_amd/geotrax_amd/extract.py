@@ -305,6 +305,7 @@ def track_with_model_sharded(model: YOLO, config: dict, logger: logging.Logger) 
                 paths, findex, offsets, lengths = reader.jpeg_layout()
 
                 def open_on(fd_, frames, threads):
+                    fd_.set_jpeg_entropy(eng_cfg.get('jpeg_entropy', 'host'))      # `engine: {jpeg_entropy: gpu}`: Huffman decode on the copy stream
                     fd_.open_jpeg((paths, findex[frames], offsets[frames], lengths[frames]), n_threads=threads or int(eng_cfg.get('decode_threads', 8)))
             B, n_dets = engine.B, len(engine.dets)
             mine = [f for start, stop in runs for f in range(start, stop)]
@@ -416,6 +417,7 @@ def _read_ahead_batches(reader, engine, eng_cfg: dict, first: int, last, frame_n
         # compressed JPEG frames (.mjpeg, MJPG .avi, a folder of .jpg): read and entropy-decoded by the feeder's threads
         paths, findex, offsets, lengths = reader.jpeg_layout()
         feeder = FrameFeeder(reader.frame_hw, kind="jpeg", batch=engine.B, ring=ring, device=engine.device, ctx=engine.feeder_ctx)
+        feeder.set_jpeg_entropy(eng_cfg.get('jpeg_entropy', 'host'))      # `engine: {jpeg_entropy: gpu}`: Huffman decode on the copy stream
         feeder.open_jpeg((paths, findex[first:stop], offsets[first:stop], lengths[first:stop]), n_threads=int(eng_cfg.get('decode_threads', 8)))
         frame_nums.extend(range(first, max(stop, first)))
     else:

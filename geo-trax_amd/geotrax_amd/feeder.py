@@ -62,10 +62,20 @@ class FrameFeeder:
         off = np.ascontiguousarray(offsets, dtype=np.int64)
         check(self.lib.gtx_feeder_open_file(self.handle, str(path).encode(), _lib.ptr(off), len(off), int(n_threads)))
 
-    def open_jpeg(self, layout, n_threads: int = 8) -> None:
+    def set_jpeg_entropy(self, entropy: str) -> None:
+        """Where a "jpeg" feeder's Huffman decode runs, before the source is opened: "host" (the reader threads) or "gpu"."""
+        if entropy not in ("host", "gpu"):
+            raise ValueError(f"jpeg entropy route {entropy!r}: 'host' or 'gpu'")
+        check(self.lib.gtx_feeder_set_jpeg_entropy(self.handle, 1 if entropy == "gpu" else 0))
+
+    def open_jpeg(self, layout, n_threads: int = 8, entropy: str | None = None) -> None:
         """`layout`: (paths, file_index, offsets, lengths) of a reader's jpeg_layout(), or a slice of it: frame i is lengths[i]
         bytes at offsets[i] of paths[file_index[i]]. `n_threads` library threads read and entropy-decode the frames (a
-        parameter, never the machine's CPU count: the engine has threads of its own)."""
+        parameter, never the machine's CPU count: the engine has threads of its own). entropy "gpu": the threads only walk
+        the header and remove the byte stuffing, the Huffman decode runs on the copy stream (csrc/jpeg_entropy.hip); a frame
+        the kernels do not vouch for is decoded by the host parser, so frames and error messages are those of "host"."""
+        if entropy is not None:                                   # None: as set_jpeg_entropy() left it ("host" on a new feeder)
+            self.set_jpeg_entropy(entropy)
         paths, file_index, offsets, lengths = layout
         idx = np.ascontiguousarray(file_index, dtype=np.int32)
         off = np.ascontiguousarray(offsets, dtype=np.int64)
@@ -74,6 +84,13 @@ class FrameFeeder:
             raise ValueError("jpeg layout: file_index, offsets and lengths differ in length")
         arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
         check(self.lib.gtx_feeder_open_jpeg(self.handle, arr, len(paths), _lib.ptr(idx), _lib.ptr(off), _lib.ptr(ln), len(off), int(n_threads)))
+
+    def jpeg_stats(self) -> tuple[int, int, int]:
+        """Frames of a "jpeg" feeder whose entropy decode ran on the GPU / on the host because the frame is not for the GPU route
+        (restart intervals) / on the host after a GPU status. All 0 on the host route."""
+        out = (C.c_int64 * 3)()
+        check(self.lib.gtx_feeder_jpeg_stats(self.handle, out))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def open_memory(self, frames, n_threads: int = 3) -> None:
         """`frames`: a sequence of host arrays (BGR ndarrays, or the I420 `data` of Yuv420Frame objects) delivered in order; the

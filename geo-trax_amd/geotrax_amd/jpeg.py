@@ -535,3 +535,329 @@ def encode_jpeg_dev(ctx: _lib.Context, bgr: np.ndarray, quality: int = 90, subsa
         lib.gtx_jpeg_enc_destroy(enc)
         if dptr is not None:
             ctx.dev_free(dptr)
+
+
+# ----------------------------------------------------------------------------------------------- entropy decoding on the GPU
+# csrc/jpeg_entropy.hip decodes the scan on the GPU from a plan (gtx_jpeg_plan: header walk and unstuffing on the host; layout in
+# csrc/jpeg_parse.hpp). entropy_decode_twin() restates its kernels' rule -- the same state word, poison handling, workgroup
+# structure and rounds -- so that the rule can be reasoned about and tested without a GPU.
+
+ENTROPY_SUB_BITS, ENTROPY_ROUNDS, ENTROPY_MAX_ROUNDS = 1024, 8, 64     # the production choices (csrc/jpeg_entropy.hpp)
+ENTROPY_SUB_BITS_SET = (256, 512, 1024, 2048)
+ENTROPY_INVALID, ENTROPY_NOT_CONVERGED = 1, 2                          # status bits
+PLAN_MAGIC = 0x3150474A
+PLAN_QUANT_OFFSET, PLAN_HUFF_OFFSET, PLAN_HUFF_BYTES, PLAN_STREAM_OFFSET = 112, 112 + 384, 1432, 112 + 384 + 6 * 1432
+_POISON = (1 << 64) - 1
+_U32 = 0xFFFFFFFF
+
+
+def entropy_lanes(sub_bits: int) -> int:
+    """Lanes of one workgroup: its span of the stream (lanes * sub_bits / 8 bytes) is at most 32 KB."""
+    return 128 if sub_bits == 2048 else 256
+
+
+def entropy_plan(data, frame: int = 0):
+    """One compressed frame -> its plan (uint8 array), or None for a frame the GPU route hands to the host parser (a restart
+    interval). Raises JpegError where parse() refuses the header, with parse()'s message. Host only."""
+    lib = _lib.load()
+    raw = bytes(data)
+    buf = np.frombuffer(raw or b"\0", dtype=np.uint8)
+    out = [C.c_int() for _ in range(5)]
+    needed = C.c_size_t()
+
+    def call(dst, cap):
+        rc = lib.gtx_jpeg_plan(_lib.ptr(buf), len(raw), int(frame), *[C.byref(v) for v in out], dst, cap, C.byref(needed))
+        if rc < 0:
+            raise JpegError(rc, lib.gtx_last_error().decode("utf-8", "replace"))
+        return rc
+
+    if call(None, 0) == 2:
+        return None
+    plan = np.zeros((needed.value + 3) // 4, dtype=np.uint32).view(np.uint8)[:needed.value]
+    if call(_lib.ptr(plan), plan.nbytes) != 0:
+        raise JpegError(-5, f"JPEG frame {frame}: the plan did not fit the size the parser asked for")
+    return plan
+
+
+def plan_fields(plan: np.ndarray):
+    """The plan's header as a dict, its quantisation tables [3][64], its six Huffman tables (dicts: look, maxcode, valoff, vals,
+    nvals; DC of component 0..2, then AC) and the clean stream (a view)."""
+    hd = plan[:PLAN_QUANT_OFFSET].view(np.uint32)
+    if int(hd[0]) != PLAN_MAGIC or int(hd[1]) != plan.nbytes:
+        raise ValueError("not a JPEG plan")
+    f = dict(w=int(hd[2]), h=int(hd[3]), ncomp=int(hd[4]), hs=int(hd[5]), vs=int(hd[6]), mcus_x=int(hd[7]), mcus_y=int(hd[8]), n_blocks=int(hd[9]),
+             bw=[int(v) for v in hd[10:13]], bh=[int(v) for v in hd[13:16]], restart=int(hd[16]), td=[int(v) for v in hd[17:20]],
+             ta=[int(v) for v in hd[20:23]], stream_bytes=int(hd[23]), stream_bits=int(hd[26]) | int(hd[27]) << 32)
+    quant = plan[PLAN_QUANT_OFFSET:PLAN_HUFF_OFFSET].view(np.uint16).reshape(3, 64)
+    tables = []
+    for k in range(6):
+        t = plan[PLAN_HUFF_OFFSET + k * PLAN_HUFF_BYTES:PLAN_HUFF_OFFSET + (k + 1) * PLAN_HUFF_BYTES]
+        tables.append(dict(look=t[:1024].view(np.uint16).tolist(), maxcode=t[1024:1096].view(np.int32).tolist(), valoff=t[1096:1168].view(np.int32).tolist(),
+                           vals=t[1168:1424].tolist(), nvals=int(t[1424:1428].view(np.uint32)[0])))
+    stream = plan[PLAN_STREAM_OFFSET:PLAN_STREAM_OFFSET + f["stream_bytes"]]
+    return f, quant, tables, stream
+
+
+def _pack_state(p: int, k: int, z: int) -> int:
+    return p | k << 40 | z << 44
+
+
+class _WriteSink:
+    """jpeg_entropy_write_kernel's side of a lane: b the block being decoded (at or past nb: dropped), next_b the next to begin."""
+
+    def __init__(self, dense, aclen, nb, base):
+        self.dense, self.aclen, self.nb, self.b, self.next_b, self.maxz, self.invalid = dense, aclen, nb, (base - 1) & _U32, base, 0, False
+
+    def flush(self):
+        if self.maxz and self.b < self.nb:
+            assert 0 <= self.b < len(self.aclen)
+            self.aclen[self.b] = max(int(self.aclen[self.b]), self.maxz)      # atomicMax
+        self.maxz = 0
+
+    def begin(self):
+        self.flush()
+        self.b, self.next_b = self.next_b, (self.next_b + 1) & _U32
+
+    def dc(self, v):
+        if self.b < self.nb:
+            assert 0 <= self.b < self.dense.shape[0] and -32768 <= v <= 32767
+            self.dense[self.b, 0] = v
+
+    def ac(self, z, v):
+        assert 1 <= z <= 63
+        if self.b < self.nb:
+            assert 0 <= self.b < self.dense.shape[0] and -32768 <= v <= 32767
+            self.dense[self.b, z] = v
+        self.maxz = z + 1
+
+    end = flush
+
+    def poisoned(self, at_dc):
+        if (self.next_b if at_dc else self.b) < self.nb:
+            self.invalid = True
+
+
+def _decode_lane(cx, lane: int, entry: int, sink=None):
+    """f_lane(entry) of csrc/jpeg_entropy.hip (decode_lane): the exit state and the blocks that began. cx: the frame's constants."""
+    if entry >> 50:
+        return _POISON, 0
+    p, k, z = entry & ((1 << 40) - 1), (entry >> 40) & 15, (entry >> 44) & 63
+    sub, bits, bpm, luma, tables, padded = cx["sub"], cx["bits"], cx["bpm"], cx["luma"], cx["tables"], cx["padded"]
+    lo = lane * sub
+    hi = lo + sub
+    if p < lo or p >= hi or p > bits or k >= bpm:
+        return _POISON, 0
+    count = 0
+    steps = 0
+    while p < hi:
+        steps += 1
+        assert steps <= sub                                        # every step consumes at least one bit
+        c = 0 if (bpm == 1 or k < luma) else 1 + (k - luma)
+        assert 0 <= c <= 2
+        t = tables[c if z == 0 else 3 + c]
+        at = p >> 3
+        assert 0 <= at and at + 8 <= len(padded)
+        win = (int.from_bytes(padded[at:at + 8], "big") << (p & 7)) & ((1 << 64) - 1)       # bits past the stream read as zero
+        top = win >> 48
+        left = bits - p
+        ln = sym = 0
+        e = t["look"][top >> 7]
+        if e:
+            ln, sym = e >> 8, e & 255
+        else:
+            for l in range(10, 17):
+                code = top >> (16 - l)
+                if code <= t["maxcode"][l]:
+                    idx = t["valoff"][l] + code
+                    if 0 <= idx < min(t["nvals"], 256):
+                        ln, sym = l, t["vals"][idx]
+                    break
+        if ln == 0 or ln > 16 or ln > left:
+            if sink:
+                sink.poisoned(z == 0)
+            return _POISON, count
+        if z == 0:
+            s = sym
+            if s > 15 or ln + s > left:
+                if sink:
+                    sink.poisoned(True)
+                return _POISON, count
+            v = 0
+            if s:
+                v = (win << ln & ((1 << 64) - 1)) >> (64 - s)
+                v = v - (1 << s) + 1 if v < (1 << (s - 1)) else v
+            if sink:
+                sink.begin()
+                sink.dc(v)
+            count += 1
+            p, z = p + ln + s, 1
+            continue
+        r, s = sym >> 4, sym & 15
+        done = False
+        if s == 0:
+            p += ln
+            if r != 15:
+                done = True
+            else:
+                z += 16
+                done = z >= 64
+        else:
+            z += r
+            if z > 63 or ln + s > left:
+                if sink:
+                    sink.poisoned(False)
+                return _POISON, count
+            v = (win << ln & ((1 << 64) - 1)) >> (64 - s)
+            v = v - (1 << s) + 1 if v < (1 << (s - 1)) else v
+            if sink:
+                sink.ac(z, v)
+            p += ln + s
+            z += 1
+            done = z == 64
+        if done:
+            if sink:
+                sink.end()
+            k, z = (0 if k + 1 == bpm else k + 1), 0
+    return _pack_state(p, k, z), count
+
+
+def entropy_decode_plan_twin(plan: np.ndarray, sub_bits: int = 0, lanes: int = 0, rounds: int = 0):
+    """The kernels of csrc/jpeg_entropy.hip on one plan, in numpy and plain Python: (status, record or None, rounds_used).
+    sub_bits: bits of the clean stream per lane; lanes: lanes per workgroup; rounds: synchronisation rounds across workgroups
+    (round 0 included); 0 = the production choice each."""
+    sub = int(sub_bits) or ENTROPY_SUB_BITS
+    if sub not in ENTROPY_SUB_BITS_SET:
+        raise ValueError(f"sub_bits {sub_bits}: one of {ENTROPY_SUB_BITS_SET}")
+    L = int(lanes) or entropy_lanes(sub)
+    R = int(rounds) or ENTROPY_ROUNDS
+    if L < 1 or not 1 <= R <= ENTROPY_MAX_ROUNDS:
+        raise ValueError(f"lanes {lanes}, rounds {rounds}")
+    f, quant, tables, stream = plan_fields(plan)
+    nb, bits = f["n_blocks"], f["stream_bits"]
+    luma = f["hs"] * f["vs"]
+    bpm = 1 if f["ncomp"] == 1 else luma + 2
+    cx = dict(sub=sub, bits=bits, bpm=bpm, luma=luma, tables=tables, padded=stream.tobytes() + bytes(16 + sub // 8))
+    n_lanes = max(1, -(-bits // sub))
+    n_wgs = -(-n_lanes // L)
+    memo = {}
+
+    def f_lane(lane, entry):
+        key = (lane, entry)
+        if key not in memo:
+            memo[key] = _decode_lane(cx, lane, entry)
+        return memo[key]
+
+    # ---- jpeg_entropy_sync_kernel, `R` launches
+    entry, exit_, count = [_POISON] * n_lanes, [_POISON] * n_lanes, [0] * n_lanes
+    edge = [[_POISON] * n_wgs, [_POISON] * n_wgs]
+    changed = [0] * R
+    for r in range(R):
+        for wg in range(n_wgs):
+            first, last = wg * L, min((wg + 1) * L, n_lanes) - 1
+            wg_entry = 0 if wg == 0 else (_pack_state(first * sub, 0, 0) if r == 0 else edge[(r - 1) & 1][wg - 1])
+            if r > 0 and entry[first] == wg_entry:
+                edge[r & 1][wg] = exit_[last]
+                continue
+            n = last - first + 1
+            if r == 0:
+                cur_entry = [wg_entry] + [_pack_state((first + t) * sub, 0, 0) for t in range(1, n)]
+                got = [f_lane(first + t, cur_entry[t]) for t in range(n)]
+                cur_exit, cur_count = [g[0] for g in got], [g[1] for g in got]
+            else:
+                cur_entry, cur_exit, cur_count = entry[first:last + 1], exit_[first:last + 1], count[first:last + 1]
+            for _ in range(L):                                     # in LDS: until no lane of the workgroup changes
+                want = [wg_entry] + cur_exit[:-1]
+                again = [t for t in range(n) if want[t] != cur_entry[t]]
+                if not again:
+                    break
+                for t in again:
+                    cur_entry[t] = want[t]
+                    cur_exit[t], cur_count[t] = f_lane(first + t, want[t])
+            entry[first:last + 1], exit_[first:last + 1], count[first:last + 1] = cur_entry, cur_exit, cur_count
+            edge[r & 1][wg] = cur_exit[-1]
+            changed[r] = 1
+    rounds_used = 1 + sum(changed[1:])
+    # ---- blocks that begin in every lane -> the first of them (32-bit sums)
+    blockoff = [0] * n_lanes
+    run = 0
+    for i in range(n_lanes):
+        blockoff[i] = run
+        run = (run + count[i]) & _U32
+    # ---- jpeg_entropy_write_kernel
+    status = 0
+    dense = np.zeros((nb, 64), np.int16)
+    aclen = np.zeros(nb, np.int64)
+    for lane in range(n_lanes):
+        if entry[lane] != (0 if lane == 0 else exit_[lane - 1]):
+            status |= ENTROPY_NOT_CONVERGED
+        sink = _WriteSink(dense, aclen, nb, blockoff[lane])
+        x, _ = _decode_lane(cx, lane, entry[lane], sink)
+        sink.flush()
+        if sink.invalid:
+            status |= ENTROPY_INVALID
+        if lane == n_lanes - 1 and x != _POISON and ((sink.next_b - (1 if (x >> 44) & 63 else 0)) & _U32) < nb:
+            status |= ENTROPY_INVALID                              # the data ends before the last block does
+    # ---- the DC prefix sums by component (wrapping 32-bit sums), block lengths
+    b = np.arange(nb)
+    k = b % bpm
+    comp = np.zeros(nb, np.int64) if bpm == 1 else np.where(k < luma, 0, 1 + (k - luma))
+    diff = dense[:, 0].astype(np.int64)
+    pred = np.zeros(nb, np.int64)
+    for c in range(f["ncomp"]):
+        vals = np.where(comp == c, diff, 0)
+        pref = (np.cumsum(vals) - vals) & _U32                     # exclusive
+        s32 = (pref + (diff & _U32)) & _U32
+        s32 = np.where(s32 >= 1 << 31, s32 - (1 << 32), s32)
+        pred = np.where(comp == c, s32, pred)
+    if ((pred < -32768) | (pred > 32767)).any():
+        status |= ENTROPY_INVALID
+    dense[:, 0] = pred.astype(np.int16)                            # (truncated where invalid, as the kernel stores it)
+    lens = np.maximum(np.minimum(aclen, 64), (pred != 0).astype(np.int64))
+    if status:
+        return status, None, rounds_used
+    # ---- offsets, compaction, header
+    offsets = np.zeros(nb + 1, np.uint32)
+    np.cumsum(lens, out=offsets[1:])
+    n_coef = int(offsets[-1])
+    assert n_coef <= 64 * nb
+    total = OFFSETS_OFFSET + 4 * (nb + 1) + 2 * n_coef
+    rec = np.zeros((total + 3) // 4, np.uint32).view(np.uint8)[:total]
+    rec[:HEADER_BYTES].view(np.uint32)[:17] = [MAGIC, total, f["w"], f["h"], f["ncomp"], f["hs"], f["vs"], f["mcus_x"], f["mcus_y"], nb, n_coef, *f["bw"], *f["bh"]]
+    rec[QUANT_OFFSET:OFFSETS_OFFSET].view(np.uint16)[:] = quant.ravel()
+    end = OFFSETS_OFFSET + 4 * (nb + 1)
+    rec[OFFSETS_OFFSET:end].view(np.uint32)[:] = offsets
+    rec[end:].view(np.int16)[:] = dense[np.arange(64)[None, :] < lens[:, None]]
+    return 0, rec, rounds_used
+
+
+def entropy_decode_twin(data, sub_bits: int = 0, lanes: int = 0, rounds: int = 0, frame: int = 0):
+    """One compressed frame through entropy_plan() and the twin of the GPU entropy decoder: (status, record or None,
+    rounds_used). A frame of the host route (entropy_plan() is None) raises ValueError."""
+    plan = entropy_plan(data, frame)
+    if plan is None:
+        raise ValueError(f"JPEG frame {frame}: a frame of the host route (restart interval)")
+    return entropy_decode_plan_twin(plan, sub_bits, lanes, rounds)
+
+
+def entropy_dev(ctx: _lib.Context, data, sub_bits: int = 0, rounds: int = 0, frame: int = 0):
+    """One compressed frame through gtx_jpeg_plan and gtx_op_jpeg_entropy (upload of the plan, the entropy chain, the record at
+    its real length): (status, record or None, rounds_used). Tests, tools."""
+    plan = entropy_plan(data, frame)
+    if plan is None:
+        raise ValueError(f"JPEG frame {frame}: a frame of the host route (restart interval)")
+    return entropy_plan_dev(ctx, plan, sub_bits, rounds)
+
+
+def entropy_plan_dev(ctx: _lib.Context, plan: np.ndarray, sub_bits: int = 0, rounds: int = 0):
+    lib = ctx.lib
+    n, status, used = C.c_size_t(), C.c_int(), C.c_int()
+    rec = np.zeros(1 << 14, np.uint32).view(np.uint8)
+    for _ in range(2):
+        rc = lib.gtx_op_jpeg_entropy(ctx.handle, _lib.ptr(plan), plan.nbytes, int(sub_bits), int(rounds), _lib.ptr(rec), rec.nbytes, C.byref(n),
+                                     C.byref(status), C.byref(used))
+        if rc != 1:
+            break
+        rec = np.zeros((n.value + 3) // 4, np.uint32).view(np.uint8)
+    if rc != 0:
+        raise JpegError(rc, lib.gtx_last_error().decode("utf-8", "replace"))
+    return status.value, (rec[:n.value] if status.value == 0 else None), used.value

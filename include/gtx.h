@@ -74,7 +74,9 @@ extern "C" {
  *     number stays. gtx_op_pool_down added and arch 0 also takes YOLOv9 t / s / m / c tensors (yolov9.yaml: ELAN1 / RepNCSPELAN4, AConv / ADown,
  *     SPPELAN = model.9, Detect = model.22; told by their names like the other families): the same, the number stays.
  *     gtx_jpeg_enc_{set_entropy, collect_jpeg, entropy_ms}, gtx_jpeg_{picture_bound, header} and gtx_op_jpeg_huff (the JPEG sink's
- *     entropy coder as HIP kernels, opt-in per encoder) added: new entry points only, so the number stays. */
+ *     entropy coder as HIP kernels, opt-in per encoder) added: new entry points only, so the number stays.
+ *     gtx_jpeg_{plan_bound, plan, entropy_ms}, gtx_op_jpeg_entropy and gtx_feeder_{set_jpeg_entropy, jpeg_stats} (the JPEG source's entropy decoder as
+ *     HIP kernels, opt-in per feeder) added: new entry points only, so the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -225,6 +227,47 @@ int gtx_jpeg_kernel_ms(gtx_ctx* ctx, const void* record, size_t bytes, int h, in
  * compressed frame of any length. */
 int gtx_feeder_open_jpeg(gtx_feeder* f, const char* const* paths, int n_paths, const int32_t* file_index, const int64_t* offsets,
                          const int64_t* lengths, int64_t n_frames, int n_threads);
+
+/* JPEG frame source, the GPU entropy route (opt-in): the Huffman decode of gtx_jpeg_parse moved from the reader threads to HIP
+ * kernels (csrc/jpeg_entropy.hip). The host keeps the header walk and the removal of the byte stuffing (the "plan",
+ * csrc/jpeg_parse.hpp: header, quantisers, the scan's Huffman tables, the clean entropy-coded segment); the GPU cuts the clean
+ * stream into subsequences of `sub_bits` bits, finds every subsequence's entry state by the self-synchronising decode and writes
+ * the packed record, byte for byte what gtx_jpeg_parse writes for the same picture. A frame the kernels cannot vouch for (damaged
+ * data, or entry states still changing after the enqueued rounds) gets a non-zero status and is decoded by gtx_jpeg_parse, so
+ * which frames decode and what an error says do not depend on the route. Frames with a restart interval stay on the host. */
+/* Replaces cv2.VideoCapture.read(), extract.py:146 (buffer sizing): the largest plan a decodable frame of h x w can need; 0
+ * for a size outside 1..16384. */
+size_t gtx_jpeg_plan_bound(int h, int w);
+/* Replaces cv2.VideoCapture.read(), extract.py:146 (the header walk; host only, no context): bytes[0, n) -> the plan in
+ * out[0, capacity) (4-byte aligned; NULL with capacity 0 asks for the size). *needed receives the plan's size. Returns 0 (plan
+ * written), 1 (capacity < *needed, nothing written), 2 (a frame for the host route: a restart interval; *needed is 0) or the
+ * negative status and message gtx_jpeg_parse gives for the same header. h, w, ncomp, hs, vs as gtx_jpeg_parse. */
+int gtx_jpeg_plan(const void* bytes, size_t n, int64_t frame, int* h, int* w, int* ncomp, int* hs, int* vs, void* out, size_t capacity,
+                  size_t* needed);
+/* Replaces cv2.VideoCapture.read(), extract.py:146 (the entropy decode; operator hook for tests and tools): uploads plan[0, bytes)
+ * (host memory, as gtx_jpeg_plan wrote it), runs the entropy chain and copies the record at its real length into
+ * record[0, capacity). sub_bits: 256, 512, 1024 or 2048, 0 = the production choice; rounds: synchronisation rounds across
+ * workgroups to enqueue, 1..64, 0 = the production choice. *status: 0, or bit 0 = invalid data, bit 1 = not converged (no record is
+ * returned then and *record_bytes is 0); *rounds_used: rounds in which a workgroup's entry state still changed, round 0 included.
+ * Returns 0, 1 (capacity < *record_bytes, nothing copied) or a negative status; a plan shorter than its header and tables or
+ * inconsistent with its length, another sub_bits or rounds and NULL arrays are GTX_ERR_INVALID before anything is launched. */
+int gtx_op_jpeg_entropy(gtx_ctx* ctx, const void* plan, size_t bytes, int sub_bits, int rounds, void* record, size_t capacity,
+                        size_t* record_bytes, int* status, int* rounds_used);
+/* Timing of what replaces cv2.VideoCapture.read(), extract.py:146, on the GPU entropy route: plan[0, bytes) is uploaded once, then the
+ * entropy chain and the two pixel kernels run `reps` times (1..10000) on the context's stream with events around each part, after
+ * one untimed pass. ms[0] = the entropy chain, ms[1] = the two pixel kernels, mean milliseconds per frame; *status and *rounds_used
+ * as gtx_op_jpeg_entropy reports them for the last pass. tools/jpeg_time.py. */
+int gtx_jpeg_entropy_ms(gtx_ctx* ctx, const void* plan, size_t bytes, int sub_bits, int rounds, int reps, float ms[2], int* status, int* rounds_used);
+/* Replaces cv2.VideoCapture.read(), extract.py:146, for a feeder of kind 2: gpu != 0 puts the feeder on the GPU entropy route (its
+ * reader threads write plans, the copy stream runs the entropy chain in front of the two pixel kernels, gtx_feeder_next looks at
+ * the batch's status words and has gtx_jpeg_parse decode every frame whose status is not 0), gpu == 0 back on the host route.
+ * Valid on a feeder of kind 2 that has no source yet; GTX_ERR_INVALID with a message for NULL, another kind or an opened feeder. */
+int gtx_feeder_set_jpeg_entropy(gtx_feeder* f, int gpu);
+/* Replaces cv2.VideoCapture.read(), extract.py:146 (book-keeping): frames of a kind-2 feeder delivered so far (counted when
+ * gtx_feeder_next hands their batch out, so the three add up to the frames delivered) whose entropy decode ran out[0] on the GPU,
+ * out[1] on the host because gtx_jpeg_plan handed them back (or their plan did not fit the slot), out[2] on the host after a GPU
+ * status. On the host route all three stay 0. */
+int gtx_feeder_jpeg_stats(gtx_feeder* f, int64_t out[3]);
 
 /* JPEG frame sink: cv2.VideoWriter.write() (geotrax/visualize.py:298) for Motion-JPEG output, the decode above run backwards.
  * The GPU turns a packed BGR frame in HBM into the same packed record (csrc/jpeg_parse.hpp) with libjpeg's default integer

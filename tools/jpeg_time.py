@@ -12,6 +12,15 @@
     .mjpeg at 4, 8 and 12 decode threads, in one process: `bench.py --workload cli` writes the weights, the config and the .y4m,
     this script adds the .mjpeg of the same frames (--no-loop skips it)
 
+    python tools/jpeg_time.py --entropy [--no-loop | --only-loop] [--entropy-out profiles/jpeg_entropy_time.txt]
+
+  the GPU entropy route (engine.jpeg_entropy: gpu) next to the host route, raw output: profiles/jpeg_entropy_time.txt
+  * bytes uploaded per frame (the plan) and the host's plan() time per frame on one thread, next to parse()'s
+  * the entropy chain's GPU time per frame (events around the chain, gtx_jpeg_entropy_ms) at 512 / 1024 / 2048 bits a lane, the
+    rounds used, and the twin's rounds on the same frame without a GPU (--no-gpu stops after these)
+  * the feeder alone and the product loop on .mjpeg with the host and the gpu route at 2 / 4 / 8 reader threads, interleaved, three
+    passes each, next to the .y4m figure, with the fall-back counts of gtx_feeder_jpeg_stats
+
 Needs Pillow (the encoder) and a GPU for the feeder part (--no-gpu skips it)."""
 import argparse
 import io
@@ -35,7 +44,13 @@ def main() -> None:
     ap.add_argument("--no-gpu", action="store_true")
     ap.add_argument("--no-loop", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--entropy", action="store_true", help="the GPU entropy route's figures instead of the host route's")
+    ap.add_argument("--only-loop", action="store_true", help="--entropy: the product loop alone")
+    ap.add_argument("--twin", action="store_true", help="--entropy: also the numpy twin's rounds on the first 4K frame (minutes of host time)")
+    ap.add_argument("--entropy-out", default=str(ROOT / "profiles" / "jpeg_entropy_time.txt"))
     a = ap.parse_args()
+    if a.entropy:
+        return entropy_route(a)
     from PIL import Image
 
     from geotrax_amd import _lib, jpeg
@@ -122,7 +137,119 @@ def main() -> None:
         product_loop(out / "loop", n)
 
 
-def product_loop(root: Path, n: int) -> None:
+def entropy_route(a) -> None:
+    """The GPU entropy route's figures; every line goes to stdout and is appended to --entropy-out as it is produced."""
+    import ctypes as C
+    import io
+
+    from PIL import Image
+
+    from geotrax_amd import _lib, jpeg
+    from geotrax_amd.frames import bgr_to_i420, open_source, write_y4m
+    from geotrax_amd.synth import make_scene
+
+    log = open(a.entropy_out, "a")
+
+    def say(line):
+        print(line, flush=True)
+        log.write(line + "\n")
+        log.flush()
+
+    h, w, n = a.h, a.w, a.frames
+    out = Path(a.out) if a.out else Path(tempfile.mkdtemp())
+    out.mkdir(parents=True, exist_ok=True)
+    if a.only_loop:
+        return product_loop(out / "loop", n, routes=("host", "gpu"), thread_counts=(2, 4, 8), say=say)
+    sc = make_scene(seed=0, h=h, w=w)
+    frames = [sc.render(5 * t, 150) for t in range(a.distinct)]
+    blobs = []
+    for f in frames:
+        buf = io.BytesIO()
+        Image.fromarray(np.ascontiguousarray(f[..., ::-1]), "RGB").save(buf, "JPEG", quality=90, subsampling=2)
+        blobs.append(buf.getvalue())
+    plans = [jpeg.entropy_plan(b) for b in blobs]
+    say(f"frame {w} x {h}, Pillow quality 90, 4:2:0, {a.distinct} distinct frames of the synthetic scene; production: {jpeg.ENTROPY_SUB_BITS} bits a lane, "
+        f"{jpeg.ENTROPY_ROUNDS} rounds enqueued")
+    say(f"bytes uploaded per frame: plan {np.mean([p.nbytes for p in plans]):.0f} (jpg {np.mean([len(b) for b in blobs]):.0f}; "
+        f"record {np.mean([jpeg.parse(b)[0].nbytes for b in blobs]):.0f} on the host route)")
+    t_plan, t_parse = [], []
+    for _ in range(3):
+        for b in blobs:
+            t0 = time.perf_counter()
+            jpeg.entropy_plan(b)                                   # two passes: the size query and the fill
+            t1 = time.perf_counter()
+            jpeg.parse(b)
+            t_plan.append((t1 - t0) / 2), t_parse.append((time.perf_counter() - t1) / 2)
+    say(f"host work per frame on one thread (median of {len(t_plan)}): plan() {1e3 * np.median(t_plan):.3f} ms, parse() {1e3 * np.median(t_parse):.2f} ms")
+    if a.twin:
+        t0 = time.perf_counter()
+        for sub in (512, 1024, 2048):
+            st, _, used = jpeg.entropy_decode_plan_twin(plans[0], sub, 0, jpeg.ENTROPY_MAX_ROUNDS)
+            say(f"numpy twin, frame 0, {sub} bits a lane: status {st}, {used} round(s) used ({time.perf_counter() - t0:.0f} s of host time so far)")
+    if a.no_gpu:
+        return
+    from geotrax_amd.feeder import FrameFeeder
+
+    ctx = _lib.default_context(0)
+    def chain(pl, sub, rounds, reps):
+        ms, st, used = (C.c_float * 2)(), C.c_int(), C.c_int()
+        _lib.check(ctx.lib.gtx_jpeg_entropy_ms(ctx.handle, _lib.ptr(pl), pl.nbytes, sub, rounds, reps, ms, C.byref(st), C.byref(used)))
+        return ms[0], ms[1], st.value, used.value
+
+    for sub in (512, 1024, 2048):
+        lanes = -(-8 * max(jpeg.plan_fields(pl)[0]["stream_bytes"] for pl in plans) // sub)
+        need = [chain(pl, sub, jpeg.ENTROPY_MAX_ROUNDS, 1) for pl in plans]          # what the frames need, whatever is enqueued in production
+        say(f"{sub} bits a lane: {lanes} lanes, {-(-lanes // jpeg.entropy_lanes(sub))} workgroups; with {jpeg.ENTROPY_MAX_ROUNDS} rounds enqueued: "
+            f"status {sorted({r[2] for r in need})}, rounds used {min(r[3] for r in need)}..{max(r[3] for r in need)}")
+        for rounds, passes, reps in ((jpeg.ENTROPY_ROUNDS, 3, 5), (jpeg.ENTROPY_MAX_ROUNDS, 1, 2)):   # (a chain that does not converge takes 0.1 s and more)
+            for rep in range(passes):
+                got = [chain(pl, sub, rounds, reps) for pl in plans]
+                say(f"GPU time per frame, {sub} bits a lane, {rounds} rounds enqueued, pass {rep} (events, mean of {reps} x {len(plans)} frames): "
+                    f"entropy chain {np.mean([g[0] for g in got]):.4f} ms, the two pixel kernels {np.mean([g[1] for g in got]):.4f} ms; "
+                    f"status {sorted({g[2] for g in got})} (0 ok, 1 invalid, 2 not converged, 3 both), rounds used {min(g[3] for g in got)}..{max(g[3] for g in got)}")
+    clip = out / "clip.mjpeg"
+    clip.write_bytes(b"".join(blobs[k % a.distinct] for k in range(n)))
+    y4m = out / "clip.y4m"
+    planes = [bgr_to_i420(f) for f in frames]
+    write_y4m(y4m, [planes[k % a.distinct] if k else frames[0] for k in range(n)])
+
+    def drain(fd):
+        t0 = time.perf_counter()
+        k = 0
+        for b in fd.batches(in_flight=2):
+            b.wait_on(None)
+            k += b.n
+        dt = time.perf_counter() - t0
+        stats = fd.jpeg_stats() if fd.kind == 2 else None
+        fd.close()
+        return k, dt, stats
+
+    r = open_source(y4m)
+    path, kind, off = r.raw_layout()
+    r.release()
+    for rep in range(3):
+        fd = FrameFeeder((h, w), kind=kind, batch=2, ring=6, ctx=None, device=ctx.device)
+        fd.open_file(path, off, n_threads=3)
+        k, dt, _ = drain(fd)
+        say(f"feeder alone, .y4m (page cache), 3 reader threads, pass {rep}: {k} frames in {dt:.3f} s = {k / dt:.0f} frames/s")
+    r = open_source(clip)
+    layout = r.jpeg_layout()
+    r.release()
+    for rep in range(3):                                          # interleaved: every pass visits every case
+        for threads in (2, 4, 8):
+            for route in ("host", "gpu"):
+                fd = FrameFeeder((h, w), kind="jpeg", batch=2, ring=6, device=ctx.device)
+                fd.open_jpeg(layout, n_threads=threads, entropy=route)
+                k, dt, stats = drain(fd)
+                say(f"feeder alone, .mjpeg, {route} route, {threads} reader threads, pass {rep}: {k} frames in {dt:.3f} s = {k / dt:.0f} frames/s; "
+                    f"frames by GPU / host on request / host after a GPU status: {stats[0]} / {stats[1]} / {stats[2]}")
+    clip.unlink()
+    y4m.unlink()
+    if not a.no_loop:
+        product_loop(out / "loop", n, routes=("host", "gpu"), thread_counts=(2, 4, 8), say=say)
+
+
+def product_loop(root: Path, n: int, routes=("host",), thread_counts=(4, 8, 12), say=print) -> None:
     """The product's loop on the same 150 frames as .y4m and as .mjpeg, one process, warm-up run + two timed runs each."""
     import argparse as ap_
     import io
@@ -165,17 +292,24 @@ def product_loop(root: Path, n: int) -> None:
         assert len(tracks) and lr["frames"] == n, (len(tracks), lr)
         return lr["loop_fps"], len(tracks)
 
-    cases = [("clip.y4m", None)] + [("clip.mjpeg", t) for t in (4, 8, 12)]
-    for name, threads in cases:
+    cases = [("clip.y4m", None, "host")] + [("clip.mjpeg", t, route) for t in thread_counts for route in routes]
+    paths = {}
+    for name, threads, route in cases:
         c = dict(cfg)
         c["engine"] = dict(cfg.get("engine") or {})
         if threads:
             c["engine"]["decode_threads"] = threads
-        cfg_path = root / f"cfg_{threads or 'y4m'}.yaml"
-        cfg_path.write_text(yaml.safe_dump(c))
-        runs = [one_run(root / name, cfg_path) for _ in range(3)]
-        what = f"{name}, {threads} decode threads" if threads else f"{name} (page cache), 3 reader threads"
-        print(f"product loop, {what}: {runs[1][0]:.0f} and {runs[2][0]:.0f} frames/s (warm-up run {runs[0][0]:.0f}); {runs[1][1]} track rows")
+            c["engine"]["jpeg_entropy"] = route
+        paths[(name, threads, route)] = root / f"cfg_{threads or 'y4m'}_{route}.yaml"
+        paths[(name, threads, route)].write_text(yaml.safe_dump(c))
+    runs = {case: [] for case in cases}
+    for _ in range(3):                                            # interleaved: every pass visits every case; the first pass warms up
+        for case in cases:
+            runs[case].append(one_run(root / case[0], paths[case]))
+    for name, threads, route in cases:
+        r = runs[(name, threads, route)]
+        what = f"{name}, {route} route, {threads} decode threads" if threads else f"{name} (page cache), 3 reader threads"
+        say(f"product loop, {what}: {r[1][0]:.0f} and {r[2][0]:.0f} frames/s (warm-up run {r[0][0]:.0f}); {r[1][1]} track rows")
 
 
 if __name__ == "__main__":
