@@ -4,6 +4,7 @@
 
 struct gtx_ctx;
 struct gtx_georef_chain;
+struct gtx_georef_tracks_cfg;
 
 namespace gtx {
 
@@ -19,6 +20,21 @@ void perspective_points(const double H[9], const double* x, const double* y, int
 // (geotrax/georeference.py:173-177, 599-628). Device kernel in georef.hip.
 void georef_points(gtx_ctx* ctx, const gtx_georef_chain& chain, const double* x, const double* y, int n, double* ox, double* oy,
                    double* lat, double* lon, double* east, double* north);
+
+// The stage's per-track columns after that chain, in HBM (gtx_op_georef_tracks, include/gtx.h): visibility, dimensions in metres,
+// gap-filled and smoothed speed / acceleration, road-section quad. The caller (gtx_ops.cpp) has checked the plan against n.
+// exp_off: the plan's offsets, already narrowed to int. out_* as in the header, any may be null.
+struct GeorefTracksArgs {
+  const double *x, *y, *bbox, *dims;
+  const int32_t *frame, *interp, *order, *seg, *n_used, *exp_off;
+  const double *quads, *weights;
+  int n, n_quads, n_weights, symmetric;
+  double *ox, *oy, *lat, *lon, *east, *north, *length_m, *width_m, *speed, *accel;
+  uint8_t* vis;
+  int32_t* quad;
+};
+void georef_tracks(gtx_ctx* ctx, const gtx_georef_chain& chain, const gtx_georef_tracks_cfg& cfg, const GeorefTracksArgs& a);
+void georef_tracks_last_ms(float* ms);
 
 // cv2.warpPerspective(frame, H, (w, h)): dst(x,y) = bilinear src(H^-1 (x,y)), constant 0 border
 // (geotrax/visualize.py:289). Device kernel in warp.hip.

@@ -1176,6 +1176,77 @@ int gtx_op_georef_points(gtx_ctx* ctx, const gtx_georef_chain* chain, const doub
   });
 }
 
+// The georeference stage's per-track columns (tests/test_georef_tracks_gpu.py). Everything that decides an address is checked here:
+// the plan against n (a permutation, bounds that tile it, counts and offsets that fit); what the plan says about the table's
+// values (which rows are used, how long a gap-filled series is) the kernels count again themselves (georef.hip).
+int gtx_op_georef_tracks(gtx_ctx* ctx, const gtx_georef_chain* chain, const gtx_georef_tracks_cfg* cfg, const double* x, const double* y,
+                         const double* bbox_unstab, const double* veh_dim_px, const int32_t* frame_num, const int32_t* is_interpolated, int n,
+                         const int32_t* order, const int32_t* seg, const int32_t* n_used, const int64_t* exp_off, const double* quads,
+                         int n_quads, const double* weights, int n_weights, double* ortho_x, double* ortho_y, double* lat, double* lon,
+                         double* east, double* north, uint8_t* visibility, double* length_m, double* width_m, double* speed, double* accel,
+                         int32_t* quad) {
+  return guarded([&] {
+    const char* op = "georef_tracks";
+    need(chain, "chain"); need(cfg, "cfg");
+    if (n < 0) gtx::fail(GTX_ERR_INVALID, "georef_tracks: n = %d", n);
+    if (n_weights < 1 || n_weights % 2 == 0 || n_weights > 4095)
+      gtx::fail(GTX_ERR_INVALID, "georef_tracks: %d weights: an odd count of at most 4095 is needed (a centre tap and a radius)", n_weights);
+    need(weights, "weights");
+    for (int k = 0; k < n_weights; ++k)
+      if (!std::isfinite(weights[k])) op_bad(op, "a weight is not finite");
+    if (n_quads < 0 || n_quads > 512) gtx::fail(GTX_ERR_INVALID, "georef_tracks: %d quads: 0 .. 512 fit the lane kernel's LDS", n_quads);
+    if (n_quads > 0) need(quads, "quads");
+    if (cfg->boundary != 0 && cfg->boundary != 1) op_bad(op, "boundary must be 0 (reflect) or 1 (nearest)");
+    if (cfg->frame_h <= 0 || cfg->frame_w <= 0 || cfg->visibility_margin < 0) op_bad(op, "frame size / visibility margin");
+    if (!std::isfinite(cfg->fps) || !std::isfinite(cfg->conversion_factor)) op_bad(op, "fps / conversion_factor is not finite");
+    if (!chain->projected) op_bad(op, "the chain must end in a projected system (dimensions and kinematics are in metres)");
+    const int T = cfg->n_tracks;
+    if (T < 0 || T > n || (n > 0 && T == 0)) gtx::fail(GTX_ERR_INVALID, "georef_tracks: plan: %d tracks for %d rows", T, n);
+    std::vector<int32_t> eoff;
+    if (n > 0) {
+      need(x, "x"); need(y, "y"); need(bbox_unstab, "bbox_unstab"); need(veh_dim_px, "veh_dim_px"); need(frame_num, "frame_num");
+      need(order, "order"); need(seg, "seg"); need(n_used, "n_used"); need(exp_off, "exp_off");
+      std::vector<bool> seen((size_t)n, false);
+      for (int i = 0; i < n; ++i) {
+        if (order[i] < 0 || order[i] >= n || seen[(size_t)order[i]]) gtx::fail(GTX_ERR_INVALID, "georef_tracks: plan: order is not a permutation of the %d rows (entry %d)", n, i);
+        seen[(size_t)order[i]] = true;
+      }
+      if (seg[0] != 0 || seg[T] != n) gtx::fail(GTX_ERR_INVALID, "georef_tracks: plan: seg runs %d .. %d, the table has %d rows", seg[0], seg[T], n);
+      if (exp_off[0] != 0) op_bad(op, "plan: exp_off[0] must be 0");
+      eoff.resize((size_t)T + 1);
+      eoff[0] = 0;
+      for (int t = 0; t < T; ++t) {
+        const int rows = seg[t + 1] - seg[t];
+        if (rows < 1 || seg[t + 1] > n) gtx::fail(GTX_ERR_INVALID, "georef_tracks: plan: track %d has the bounds %d .. %d", t, seg[t], seg[t + 1]);
+        if (n_used[t] < 0 || n_used[t] > rows) gtx::fail(GTX_ERR_INVALID, "georef_tracks: plan: track %d uses %d of %d rows", t, n_used[t], rows);
+        const int64_t len = exp_off[t + 1] - exp_off[t];
+        if (n_used[t] < 3 ? len != 0 : len < n_used[t])
+          gtx::fail(GTX_ERR_INVALID, "georef_tracks: plan: track %d with %d used rows has a series of %lld points", t, n_used[t], (long long)len);
+        if (exp_off[t + 1] > (int64_t)1 << 30) op_bad(op, "plan: more than 2^30 points in the gap-filled series");
+        eoff[(size_t)t + 1] = (int32_t)exp_off[t + 1];
+      }
+    }
+    need(ctx, "ctx");
+    gtx::GeorefTracksArgs a{};
+    a.x = x; a.y = y; a.bbox = bbox_unstab; a.dims = veh_dim_px; a.frame = frame_num; a.interp = is_interpolated;
+    a.order = order; a.seg = seg; a.n_used = n_used; a.exp_off = eoff.data();
+    a.quads = quads; a.weights = weights; a.n = n; a.n_quads = n_quads; a.n_weights = n_weights;
+    a.symmetric = 1;                                              // scipy.ndimage.correlate1d's test: |w[r + k] - w[r - k]| <= DBL_EPSILON
+    for (int k = 1; k <= n_weights / 2; ++k)
+      if (std::fabs(weights[n_weights / 2 + k] - weights[n_weights / 2 - k]) > 2.220446049250313e-16) { a.symmetric = 0; break; }
+    a.ox = ortho_x; a.oy = ortho_y; a.lat = lat; a.lon = lon; a.east = east; a.north = north;
+    a.vis = visibility; a.length_m = length_m; a.width_m = width_m; a.speed = speed; a.accel = accel; a.quad = quad;
+    gtx::georef_tracks(ctx, *chain, *cfg, a);
+  });
+}
+
+int gtx_georef_tracks_ms(float ms[GTX_GEOREF_TRACKS_MS]) {
+  return guarded([&] {
+    need(ms, "ms");
+    gtx::georef_tracks_last_ms(ms);
+  });
+}
+
 int gtx_op_clahe(gtx_ctx* ctx, const uint8_t* gray, int h, int w, uint8_t* out) {
   return guarded([&] {
     need(ctx, "ctx"); need(gray, "gray"); need(out, "out");

@@ -66,6 +66,15 @@ class GeorefChain(C.Structure):
                 ("false_northing", C.c_double)]
 
 
+GEOREF_TRACKS_MS = 12      # GTX_GEOREF_TRACKS_MS: the times gtx_georef_tracks_ms returns
+
+
+class GeorefTracksCfg(C.Structure):
+    """gtx_georef_tracks_cfg (include/gtx.h)."""
+    _fields_ = [("frame_h", C.c_int), ("frame_w", C.c_int), ("visibility_margin", C.c_int), ("fps", C.c_double),
+                ("conversion_factor", C.c_double), ("boundary", C.c_int), ("n_tracks", C.c_int)]
+
+
 class SiftStabConfig(C.Structure):
     """gtx_sift_stab_config (include/gtx.h)."""
     _fields_ = [("work_h", C.c_int), ("work_w", C.c_int), ("max_features", C.c_int), ("ref_multiplier", C.c_float), ("root", C.c_int),
@@ -265,6 +274,8 @@ _SIGNATURES = {
     "gtx_perspective_points": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
     "gtx_op_estimate_affine_partial": (C.c_int, [_P, _P, C.c_int, C.c_uint, _P, _P, _P]),
     "gtx_op_georef_points": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "gtx_op_georef_tracks": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int] + [_P] * 12),
+    "gtx_georef_tracks_ms": (C.c_int, [_P]),
     "gtx_warp_frame": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "gtx_warp_frame_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "gtx_op_invert3x3": (C.c_int, [_P, _P]),

@@ -348,11 +348,20 @@ def get_master_to_ortho_homography(master_frame, ortho_folder: Path, master_fold
 # --------------------------------------------------------------------------- the stage
 
 def georeference_tracks(track_id, frame_num, bbox_unstab, x_stab, y_stab, class_id, veh_dim_px, is_interpolated, timestamps, frame_size, fps,
-                        H_ref2ortho, ortho_params, ortho_segmentation, config: dict, logger: logging.Logger, ctx=None):
+                        H_ref2ortho, ortho_params, ortho_segmentation, config: dict, logger: logging.Logger, ctx=None, track_columns: str = "host"):
     """Everything after the homography is known (georeference.py:172-194): the per-row chain on the GPU, then the
-    per-track host arithmetic; -> the formatted DataFrame."""
+    per-track host arithmetic; -> the formatted DataFrame. track_columns="gpu": the chain and the per-track columns in one
+    upload / download (gtx_op_georef_tracks; opt-in)."""
     tr = config["transformation"]
     src_crs, dst_crs = tr["source_crs"], tr["target_crs"]
+    if track_columns != "host":
+        flt = config["filtering"]
+        c = G.track_columns(track_id, frame_num, bbox_unstab, x_stab, y_stab, veh_dim_px, is_interpolated, frame_size, fps, H_ref2ortho, ortho_params,
+                            src_crs, dst_crs, ortho_segmentation, flt["filter_type"], flt["kernel_size"], flt["visibility_margin"],
+                            backend=track_columns, ctx=ctx)
+        return G.create_and_format_georeferenced_df(track_id, timestamps, frame_num, c["ortho_x"], c["ortho_y"], c["x_local"], c["y_local"], c["latitude"],
+                                                    c["longitude"], (c["length_m"], c["width_m"]), class_id, c["speed"], c["accel"], c["section"],
+                                                    c["lane"], c["visibility"], flt["min_traj_length"], is_interpolated, logger=logger)
     out = G.transform_points(x_stab, y_stab, H_ref2ortho, ortho_params, src_crs, dst_crs, ctx=ctx)        # gtx_op_georef_points
     x_o, y_o, lat, lon, x_l, y_l = (out[k] for k in ("ortho_x", "ortho_y", "latitude", "longitude", "x_local", "y_local"))
     dim_real = G.convert_dimensions(track_id, veh_dim_px, frame_size, H_ref2ortho, ortho_params, src_crs, dst_crs)
@@ -401,7 +410,8 @@ def georeference(args: argparse.Namespace, logger: logging.Logger, ctx=None) -> 
         H_ref2ortho = np.dot(H_master2ortho, H_ref2master)
 
     df = georeference_tracks(track_id, frame_num, bbox_unstab, x_stab, y_stab, class_id, veh_dim_px, is_interp, timestamps, frame_size, fps,
-                             H_ref2ortho, ortho_params, segmentation, config, logger, ctx=ctx)
+                             H_ref2ortho, ortho_params, segmentation, config, logger, ctx=ctx,
+                             track_columns=getattr(args, "track_columns", None) or "host")
     G.save_georeferenced_data(build_result_path(source, "georeferenced", out_cfg), df, logger)
     G.save_homography(build_result_path(source, "geo_transformations", out_cfg), H_ref2ortho, logger)
 
@@ -415,6 +425,8 @@ def add_georeferencing_args(group) -> None:
     group.add_argument("--master-folder", "-mf", type=Path, default=None)
     group.add_argument("--recompute", "-r", action="store_const", const=True, default=None)
     group.add_argument("--segmentation-folder", "-osf", type=Path, default=None)
+    group.add_argument("--track-columns", choices=["host", "gpu"], default=None,
+                       help="where visibility, dimensions, speed / acceleration and lanes are computed (default: host)")
 
 
 def parse_cli_args(argv=None) -> argparse.Namespace:

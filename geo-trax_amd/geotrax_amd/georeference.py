@@ -5,7 +5,8 @@ transforms (`apply_homography`, `ortho2geo`, `geo2local`, `ortho2local`, `frame2
 dimensions in metres, in-frame visibility, speed / acceleration with Gaussian or Savitzky-Golay
 smoothing, road-section / lane lookup and the formatting + rounding rules of the georeferenced CSV.
 The heavy step of that stage, image registration, is `geotrax_amd.registration` (GPU); everything here
-is O(rows) work on the track table and stays on the host, like in the reference.
+is O(rows) work on the track table and stays on the host, like in the reference -- by default: `track_columns(..., backend="gpu")`
+computes the same columns in HBM with the row chain (gtx_op_georef_tracks).
 
 `geo2local` in the reference goes through geopandas/pyproj (absent here). This module projects
 WGS 84 / GRS 80 geographic coordinates with its own transverse-Mercator series (Karney-Krueger, 6th
@@ -290,6 +291,111 @@ def assign_road_section_lane(ortho_x, ortho_y, ortho_segmentation) -> tuple:
         section[hit], lane[hit] = row[0], row[1]
         taken |= hit
     return section, lane
+
+
+# --------------------------------------------------------------------------- the same columns on the GPU (opt-in)
+
+def kinematics_weights(filter_type: str, kernel_size: int) -> tuple:
+    """What apply_filter correlates a speed series with -> (weights in correlation order, boundary: 0 reflect / 1 nearest), for
+    gtx_op_georef_tracks. Gaussian: scipy's own recipe (sigma = kernel_size, radius int(3 sigma + 0.5), exp(-0.5 / sigma^2 * k^2)
+    normalised by the sum). Savitzky-Golay: savgol_coeffs(window, 2) reversed (savgol_filter convolves), and, where scipy's
+    correlate1d finds them symmetric to DBL_EPSILON and reads the left half only, the right half mirrored from it: the array is
+    the filter's impulse response, bit for bit."""
+    if filter_type == "gaussian":
+        sigma = float(kernel_size)
+        radius = int(3.0 * sigma + 0.5)
+        k = np.arange(-radius, radius + 1)
+        w = np.exp(-0.5 / (sigma * sigma) * k ** 2)
+        return (w / w.sum())[::-1].copy(), 0
+    if filter_type == "savgol":
+        from scipy.signal import savgol_coeffs
+
+        window = kernel_size if kernel_size % 2 == 1 else kernel_size + 1
+        w = np.ascontiguousarray(savgol_coeffs(window, 2)[::-1], dtype=np.float64)
+        r = window // 2
+        if r and np.all(np.abs(w[r + 1:] - w[:r][::-1]) <= np.finfo(np.float64).eps):
+            w[r + 1:] = w[:r][::-1]
+        return w, 1
+    raise ValueError(f"Invalid filter type: '{filter_type}'. Supported types: 'gaussian', 'savgol'.")
+
+
+def track_plan(track_ids, frame_num, visibility, is_interpolated=None) -> dict:
+    """The grouping compute_kinematics and interpolate_missing_points work out track by track, for the whole table at once
+    (gtx_op_georef_tracks' plan, include/gtx.h): order (stable argsort by track id), seg (bounds of the tracks in it), n_used
+    (visible, really detected rows per track) and exp_off (start of each track's gap-filled series: nothing for fewer than 3 used
+    rows, else 1 + sum(where(gap > 1, gap, 1)) points)."""
+    track_ids, frame_num = np.asarray(track_ids), np.asarray(frame_num)
+    n = len(track_ids)
+    if n == 0:
+        return {"order": np.zeros(0, np.int32), "seg": np.zeros(1, np.int32), "n_used": np.zeros(0, np.int32), "exp_off": np.zeros(1, np.int64)}
+    if n >= 2 ** 31 or np.abs(frame_num.astype(np.int64)).max() >= 2 ** 31:
+        raise ValueError("track_plan: row counts and frame numbers must fit 32 bits")
+    order = np.argsort(track_ids, kind="stable")
+    bounds = np.flatnonzero(track_ids[order][1:] != track_ids[order][:-1]) + 1
+    seg = np.concatenate(([0], bounds, [n]))
+    use = np.asarray(visibility, bool)
+    if is_interpolated is not None:
+        use = use & (np.asarray(is_interpolated) == 0)
+    use = use[order]
+    n_used = np.add.reduceat(use.astype(np.int64), seg[:-1])
+    rows = order[use]                                               # the used rows, track by track
+    track_of = np.repeat(np.arange(len(n_used)), n_used)
+    frames = frame_num[rows].astype(np.int64)
+    gaps = frames[1:] - frames[:-1]
+    per = np.where(gaps > 1, gaps, 1) * (track_of[1:] == track_of[:-1])
+    acc = np.concatenate(([0], np.cumsum(per)))                     # acc[j]: points before used row j, counted across tracks
+    start = np.concatenate(([0], np.cumsum(n_used)))
+    first, last = np.minimum(start[:-1], max(len(rows) - 1, 0)), np.maximum(start[1:] - 1, 0)       # clamped where a track uses no row
+    span = acc[last] - acc[first] if len(rows) else np.zeros(len(n_used), np.int64)
+    length = np.where(n_used >= 3, span + 1, 0)
+    exp_off = np.concatenate(([0], np.cumsum(length))).astype(np.int64)
+    if exp_off[-1] > 2 ** 30:
+        raise ValueError("track_plan: the gap-filled series hold more than 2^30 points")
+    return {"order": order.astype(np.int32), "seg": seg.astype(np.int32), "n_used": n_used.astype(np.int32), "exp_off": exp_off}
+
+
+def track_columns(track_ids, frame_num, bbox_unstab, x_stab, y_stab, veh_dim_px, is_interpolated, frame_size, fps: float, homography,
+                  ortho_params, source_crs: str, target_crs: str, ortho_segmentation, filter_type: str, kernel_size: int,
+                  visibility_margin: int = 4, conversion_factor: float = 3.6, backend: str = "host", ctx=None) -> dict:
+    """Every column the stage derives from the track table -> dict(ortho_x, ortho_y, latitude, longitude, x_local, y_local,
+    visibility, length_m, width_m, speed, accel, section, lane).
+    backend "host": the chain on the GPU (transform_points), then the host functions above, as georef_stage always did.
+    backend "gpu": one upload, the chain and every column in HBM (gtx_op_georef_tracks), one download; the host keeps what needs
+    the integer columns only (the plan) and maps quad indices to the segmentation file's section / lane objects."""
+    if backend == "host":
+        out = transform_points(x_stab, y_stab, homography, ortho_params, source_crs, target_crs, ctx=ctx)
+        out["length_m"], out["width_m"] = convert_dimensions(track_ids, veh_dim_px, frame_size, homography, ortho_params, source_crs, target_crs)
+        out["visibility"] = calculate_visibility(track_ids, bbox_unstab, frame_size, visibility_margin)
+        out["speed"], out["accel"] = compute_kinematics(track_ids, frame_num, out["x_local"], out["y_local"], out["visibility"], fps, filter_type,
+                                                        kernel_size, is_interpolated=is_interpolated, conversion_factor=conversion_factor)
+        out["section"], out["lane"] = assign_road_section_lane(out["ortho_x"], out["ortho_y"], ortho_segmentation)
+        return out
+    if backend != "gpu":
+        raise ValueError(f"track_columns: backend '{backend}' (host or gpu)")
+    from . import ops
+
+    weights, boundary = kinematics_weights(filter_type, kernel_size)
+    vis = calculate_visibility(track_ids, bbox_unstab, frame_size, visibility_margin)      # the plan counts used rows; the kernel's own is returned
+    plan = track_plan(track_ids, frame_num, vis, is_interpolated)
+    have_seg = ortho_segmentation is not None and len(ortho_segmentation) > 0
+    seg = ortho_segmentation.iloc[:, :10] if have_seg else None
+    quads = seg.iloc[:, 2:10].to_numpy(np.float64) if have_seg else np.zeros((0, 8))
+    got = ops.georef_tracks(georef_chain(homography, ortho_params, source_crs, target_crs), x_stab, y_stab, bbox_unstab, veh_dim_px, frame_num,
+                            is_interpolated, plan, quads, weights, frame_size=frame_size, visibility_margin=visibility_margin, fps=fps,
+                            conversion_factor=conversion_factor, boundary=boundary, ctx=ctx)
+    out = {k: got[k] for k in ("ortho_x", "ortho_y", "latitude", "longitude", "x_local", "y_local", "length_m", "width_m", "speed", "accel")}
+    out["visibility"] = got["visibility"].astype(bool)
+    if not np.array_equal(out["visibility"], vis):                  # the plan was counted on the host's: they must be one column
+        raise RuntimeError("track_columns: the visibility kernel and calculate_visibility disagree")
+    out["section"] = out["lane"] = None
+    if have_seg:
+        hit = got["quad"] >= 0
+        out["section"], out["lane"] = np.full(len(hit), np.nan, dtype=object), np.full(len(hit), np.nan, dtype=object)
+        sec_col, lane_col = np.empty(len(seg), dtype=object), np.empty(len(seg), dtype=object)
+        for k, row in enumerate(seg.itertuples(index=False)):       # the objects assign_road_section_lane stores, row by row
+            sec_col[k], lane_col[k] = row[0], row[1]
+        out["section"][hit], out["lane"][hit] = sec_col[got["quad"][hit]], lane_col[got["quad"][hit]]
+    return out
 
 
 # --------------------------------------------------------------------------- output table

@@ -207,6 +207,46 @@ def match_2nn(query: np.ndarray, train: np.ndarray, iters: int = 0, ctx: _lib.Co
     return (i1, i2, d1, d2, ms.value) if iters > 0 else (i1, i2, d1, d2)
 
 
+def georef_tracks(chain, x, y, bbox_unstab, veh_dim_px, frame_num, is_interpolated, plan: dict, quads, weights, *, frame_size,
+                  visibility_margin: int, fps: float, conversion_factor: float = 3.6, boundary: int = 0, want=None, ctx=None) -> dict:
+    """gtx_op_georef_tracks (include/gtx.h): the georeference stage's chain and every per-track column in one upload / download.
+    chain: georeference.georef_chain(...); plan: georeference.track_plan(...) (order, seg, n_used, exp_off); quads [q, 8];
+    weights: georeference.kinematics_weights(...). want: the output names to fetch (default all).
+    -> dict(ortho_x, ortho_y, latitude, longitude, x_local, y_local, visibility, length_m, width_m, speed, accel, quad, ms)."""
+    ctx = ctx or _lib.default_context()
+    f64 = lambda a, shape: np.ascontiguousarray(a, np.float64).reshape(shape)
+    i32 = lambda a: np.ascontiguousarray(a, np.int32).reshape(-1)
+    x, y = f64(x, -1), f64(y, -1)
+    n = len(x)
+    frame_num = np.asarray(frame_num).reshape(-1)
+    if len(frame_num) and (frame_num.dtype.kind not in "iu" or np.abs(frame_num.astype(np.int64)).max() >= 2 ** 31):
+        raise ValueError("frame_num must be integers that fit 32 bits")
+    bbox, dims, frames = f64(bbox_unstab, (-1, 4)), f64(veh_dim_px, (-1, 2)), i32(frame_num)
+    interp = None if is_interpolated is None else i32(is_interpolated)
+    for name, a in (("y", y), ("bbox_unstab", bbox), ("veh_dim_px", dims), ("frame_num", frames), ("is_interpolated", interp), ("order", plan["order"])):
+        if a is not None and len(a) != n:
+            raise ValueError(f"{name} has {len(a)} rows, x has {n}")
+    order, seg, n_used = i32(plan["order"]), i32(plan["seg"]), i32(plan["n_used"])
+    exp_off = np.ascontiguousarray(plan["exp_off"], np.int64).reshape(-1)
+    if len(seg) != len(n_used) + 1 or len(exp_off) != len(seg):
+        raise ValueError("plan: seg and exp_off need one entry more than n_used")
+    quads = f64(quads if quads is not None else [], (-1, 8))
+    weights = f64(weights, -1)
+    cfg = _lib.GeorefTracksCfg(int(frame_size[0]), int(frame_size[1]), int(visibility_margin), float(fps), float(conversion_factor), int(boundary),
+                               len(n_used))
+    kinds = {"ortho_x": np.float64, "ortho_y": np.float64, "latitude": np.float64, "longitude": np.float64, "x_local": np.float64,
+             "y_local": np.float64, "visibility": np.uint8, "length_m": np.float64, "width_m": np.float64, "speed": np.float64,
+             "accel": np.float64, "quad": np.int32}
+    out = {k: np.empty(n, dt) for k, dt in kinds.items() if want is None or k in want}
+    check(ctx.lib.gtx_op_georef_tracks(ctx.handle, C.byref(chain), C.byref(cfg), ptr(x), ptr(y), ptr(bbox), ptr(dims), ptr(frames), ptr(interp), n,
+                                       ptr(order), ptr(seg), ptr(n_used), ptr(exp_off), ptr(quads), len(quads), ptr(weights), len(weights),
+                                       *[ptr(out.get(k)) for k in kinds]))
+    ms = np.zeros(_lib.GEOREF_TRACKS_MS, np.float32)
+    check(ctx.lib.gtx_georef_tracks_ms(ptr(ms)))
+    out["ms"] = ms
+    return out
+
+
 def clahe(gray: np.ndarray, ctx=None) -> np.ndarray:
     """cv2.createCLAHE(clipLimit=2.0, tileGridSize=(8, 8)).apply(gray) on the GPU (the stabilizer's `clahe: true` step)."""
     ctx = ctx or _lib.default_context()

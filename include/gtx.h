@@ -76,7 +76,9 @@ extern "C" {
  *     gtx_jpeg_enc_{set_entropy, collect_jpeg, entropy_ms}, gtx_jpeg_{picture_bound, header} and gtx_op_jpeg_huff (the JPEG sink's
  *     entropy coder as HIP kernels, opt-in per encoder) added: new entry points only, so the number stays.
  *     gtx_jpeg_{plan_bound, plan, entropy_ms}, gtx_op_jpeg_entropy and gtx_feeder_{set_jpeg_entropy, jpeg_stats} (the JPEG source's entropy decoder as
- *     HIP kernels, opt-in per feeder) added: new entry points only, so the number stays. */
+ *     HIP kernels, opt-in per feeder) added: new entry points only, so the number stays.
+ *     gtx_op_georef_tracks, gtx_georef_tracks_ms and gtx_georef_tracks_cfg (the georeference stage's per-track columns as HIP
+ *     kernels, opt-in per run) added: new entry points and a struct of their own only, so the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -1130,6 +1132,51 @@ typedef struct gtx_georef_chain {
 } gtx_georef_chain;
 int gtx_op_georef_points(gtx_ctx* ctx, const gtx_georef_chain* chain, const double* x, const double* y, int n,
                          double* ortho_x, double* ortho_y, double* lat, double* lon, double* east, double* north);
+
+/* Every per-row and per-track column of the georeference stage in HBM (replaces, opt-in, the host functions
+ * geotrax/georeference.py:651-799 and :458-479 run after the chain above): one upload of the track table, the chain of
+ * gtx_op_georef_points on (x, y), then calculate_visibility, convert_dimensions, compute_kinematics (gap filling, speed,
+ * Gaussian / Savitzky-Golay smoothing, acceleration) and the road-section / lane lookup, one download. f64 throughout.
+ *   The table is in file order. The host hands in the grouping it has from the integer columns (the plan):
+ *   order[n]            the rows sorted by track id, stable (np.argsort(track_ids, kind="stable"))
+ *   seg[n_tracks + 1]   the tracks' bounds in `order`: 0 = seg[0] < seg[1] < ... < seg[n_tracks] = n
+ *   n_used[n_tracks]    per track, its rows with visibility && is_interpolated == 0 (the rows the kinematics use)
+ *   exp_off[n_tracks+1] per track, where its gap-filled series starts in the scratch buffers: a track of fewer than 3 used rows
+ *                       takes no room, any other 1 + the sum over its consecutive used rows of (gap > 1 ? gap : 1), gap = the
+ *                       difference of their frame numbers (a repeated frame number adds one point).
+ *   The hook refuses, before any launch, a plan that cannot belong to n rows; the kernels count every track's used rows and
+ *   series length themselves and write nothing for a track whose plan entry differs: the call then fails (GTX_ERR_INVALID).
+ *   bbox_unstab: [n][4] x_c, y_c, w, h of the un-stabilized box; veh_dim_px: [n][2] length, width in pixels (NaN = unknown);
+ *   frame_num: [n]; is_interpolated: [n] or NULL (every row is a detection).
+ *   quads: [n_quads][8] x, y of four corners in any winding (the segmentation file's columns 3..10); n_quads <= 512.
+ *   weights: [n_weights] the smoothing filter in correlation order, n_weights odd, <= 4095; cfg->boundary says how a series is
+ *   continued past its ends: 0 = half-sample symmetric reflection, repeated as often as needed (scipy 'reflect': the Gaussian),
+ *   1 = the end value (scipy 'nearest': Savitzky-Golay). The sum runs in scipy.ndimage.correlate1d's order -- centre tap, then
+ *   for k = radius .. 1 (in[i-k] + in[i+k]) * weights[radius-k] when the weights are symmetric to DBL_EPSILON, else the last tap
+ *   then the others left to right -- one rounding per operation, whatever the launch shape.
+ *   Outputs, host arrays of n, any may be NULL: the six columns of gtx_op_georef_points, visibility (0 / 1), length_m / width_m
+ *   (the track's first row in file order decides; NaN in, NaN out), speed (m/s * conversion_factor) / accel (NaN on rows the
+ *   kinematics do not use, on a track's first used row, and for accel on its second), quad (index of the first quad in file
+ *   order that strictly contains the row's orthophoto point, -1 for none; points on an edge or a vertex are outside).
+ * n == 0 is success. chain->projected must be 1. */
+typedef struct gtx_georef_tracks_cfg {
+  int frame_h, frame_w;            /* frame_size of calculate_visibility / convert_dimensions */
+  int visibility_margin;
+  double fps, conversion_factor;   /* compute_kinematics: speed = |dp| * fps * conversion_factor, accel = dv * fps */
+  int boundary;                    /* 0 reflect, 1 nearest */
+  int n_tracks;
+} gtx_georef_tracks_cfg;
+#define GTX_GEOREF_TRACKS_MS 12
+int gtx_op_georef_tracks(gtx_ctx* ctx, const gtx_georef_chain* chain, const gtx_georef_tracks_cfg* cfg, const double* x,
+                         const double* y, const double* bbox_unstab, const double* veh_dim_px, const int32_t* frame_num,
+                         const int32_t* is_interpolated, int n, const int32_t* order, const int32_t* seg, const int32_t* n_used,
+                         const int64_t* exp_off, const double* quads, int n_quads, const double* weights, int n_weights,
+                         double* ortho_x, double* ortho_y, double* lat, double* lon, double* east, double* north,
+                         uint8_t* visibility, double* length_m, double* width_m, double* speed, double* accel, int32_t* quad);
+/* Event times of this thread's last gtx_op_georef_tracks, milliseconds: [0] the chain, [1] visibility, [2] dimensions,
+ * [3] use-mask + compaction + series positions, [4] gap fill, [5] speed, [6] correlate, [7] acceleration + scatter, [8] lanes,
+ * [9] the uploads, [10] the downloads, [11] the nine kernels together. */
+int gtx_georef_tracks_ms(float ms[GTX_GEOREF_TRACKS_MS]);
 
 /* cv2.warpPerspective(frame, H, (w,h)) with bilinear sampling and constant-0 border
  * (visualize.py:289). BGR u8 in/out, host buffers. */
