@@ -604,9 +604,16 @@ void conv_launch(const ConvGroup& g, const ConvConfig& cfg, hipStream_t stream) 
     const ConvProblem& p = g.p[i];
     if (p.c_split == 0) continue;
     GTX_CHECK(cfg.variant == 2 && cfg.ks == 1, "conv: a second (upsampled) source needs the split-f16x3 1x1 kernel");
-    GTX_CHECK(p.in2 && p.c_split % cfg.kc == 0 && p.c_split < p.Cin && p.H % 2 == 0 && p.W % 2 == 0 && p.in2_cstride % 4 == 0 && p.in2_coff % 4 == 0,
+    // a pair-format slice starts and ends on whole 8-channel groups (split_format.hpp)
+    GTX_CHECK(p.in2 && p.c_split > 0 && p.c_split % cfg.kc == 0 && p.c_split < p.Cin && p.H % 2 == 0 && p.W % 2 == 0 && p.in2_cstride % 8 == 0 &&
+                  p.in2_coff >= 0 && p.in2_coff % 8 == 0 && p.in2_coff + p.c_split <= p.in2_cstride,
               "conv: bad second source (c_split=%d, %dx%d)", p.c_split, p.W, p.H);
   }
+  // the fused stages, the plain output and the saturation flag belong to the split-f16x3 kernels: the fp16 / exact-fp32 kernels
+  // would ignore them in silence
+  for (int i = 0; i < g.count; ++i)
+    GTX_CHECK(cfg.variant != 0 || (g.p[i].post_w == nullptr && g.p[i].front_img == nullptr && g.p[i].out_plain == 0 && g.p[i].sat_flag == nullptr),
+              "conv: a fused post / front stage, out_plain and sat_flag need the split-f16x3 path");
   if (cfg.variant == 3 || cfg.variant == 4) return conv_wino_launch(g, cfg, stream);
   if (cfg.variant == 5) return conv_k32_launch(g, cfg, stream);
   if (cfg.variant == 6) return conv_k32p_launch(g, cfg, stream);

@@ -56,8 +56,9 @@ struct ConvOpState {
   int ho = 0, wo = 0;
 };
 
+// force_kc > 0 pins the K chunk (conv_pick_config); y_plain: the output buffer is plain fp32 whatever d->dtype (ConvProblem::out_plain)
 void conv_setup(gtx_ctx* ctx, const gtx_conv_desc* d, const void* x, const float* w, const float* bias,
-                const void* residual, const void* y_init, ConvOpState& st) {
+                const void* residual, const void* y_init, ConvOpState& st, int force_kc = 0, bool y_plain = false) {
   using namespace gtx;
   need(ctx, "ctx"); need(d, "desc");
   GTX_HIP(hipSetDevice(ctx->device));
@@ -66,7 +67,7 @@ void conv_setup(gtx_ctx* ctx, const gtx_conv_desc* d, const void* x, const float
   const int pad = d->ksize / 2;
   st.ho = (d->h + 2 * pad - d->ksize) / d->stride + 1;
   st.wo = (d->w + 2 * pad - d->ksize) / d->stride + 1;
-  st.cfg = conv_pick_config(d->dtype, d->ksize, d->stride, d->cin, d->cout);
+  st.cfg = conv_pick_config(d->dtype, d->ksize, d->stride, d->cin, d->cout, force_kc);
   const bool pairs = d->dtype == GTX_F32S;       // host arrays are plain fp32; the device buffers hold the pair format (split_format.hpp)
   const int vn = pairs ? 8 : 16 / (int)es;
   GTX_CHECK(d->in_cstride % vn == 0 && d->in_coff % vn == 0 && d->out_cstride % (pairs ? 8 : 4) == 0 && d->out_coff % (pairs ? 8 : 4) == 0 &&
@@ -91,7 +92,7 @@ void conv_setup(gtx_ctx* ctx, const gtx_conv_desc* d, const void* x, const float
     for (auto& v : hx) v = uni();
     upload_fmt(st.x, d->dtype, hx.data(), xin);
   }
-  if (y_init) upload_fmt(st.y, d->dtype, y_init, yout);
+  if (y_init) upload_fmt(st.y, y_plain ? GTX_F32 : d->dtype, y_init, yout);
   else st.y.alloc(yout);
   std::vector<uint8_t> packed;
   float acc_scale = 1.f;
@@ -202,6 +203,131 @@ int gtx_op_conv2d_time(gtx_ctx* ctx, const gtx_conv_desc* d, int iters, float* m
     conv_setup(ctx, d, nullptr, nullptr, nullptr, nullptr, nullptr, st);
     *ms_per_launch = time_launches(ctx->stream, iters, [&] { gtx::conv_launch(st.g, st.cfg, ctx->stream); });
     if (flops) *flops = gtx::conv_flops(st.g.p[0], d->ksize);
+  });
+}
+
+// One launch with the stages and sources gtx_op_conv2d leaves off (tests/test_front_ops_gpu.py). The staging is conv_setup's; what
+// the extras ask of the kernel is checked by the launchers themselves (conv_launch, conv_split_launch and the other forms'),
+// which refuse before anything is launched -- only what a launcher cannot know, the size of a host array, is checked here.
+int gtx_op_conv2d_fused(gtx_ctx* ctx, const gtx_conv_desc* d, const gtx_conv_fused* f, const void* x, const float* w_ohwi, const float* bias,
+                        const void* residual, void* y) {
+  return guarded([&] {
+    need(d, "desc"); need(f, "fused"); need(w_ohwi, "w"); need(y, "y");
+    if (!f->front_img) need(x, "x");                  // a front stage computes its input: `in` is not read
+    if (d->has_residual) need(residual, "residual");
+    const bool pairs = d->dtype == GTX_F32S;
+    if (f->x2) {
+      if (f->c_split < 1 || f->in2_coff < 0 || (long)f->in2_coff + f->c_split > f->in2_cstride || (pairs && (f->in2_cstride % 8 || f->in2_coff % 8)))
+        op_bad("conv2d_fused", "the second source's channel slice does not fit its stride (whole 8-channel groups on the split-f16x3 path)");
+      if (d->n < 1 || d->h < 2 || d->w < 2) op_bad("conv2d_fused", "a second source needs a map of at least 2 x 2");
+    }
+    if (f->post_w && (d->cout < 1 || d->cout > 1024)) op_bad("conv2d_fused", "bad Cout");
+    if (f->front_img) {
+      need(f->front_w27, "front_w27"); need(f->front_bias, "front_bias");
+      if (d->n < 1 || f->front_h < 1 || f->front_w_px < 1 || d->cin < 1 || d->cin > 1024) op_bad("conv2d_fused", "front stage: bad sizes");
+    }
+    if (f->force_kc < 0 || f->members < 0 || f->members > gtx::kMaxGroup) op_bad("conv2d_fused", "bad force_kc / members");
+    // the fused stages belong to the 32x32x16 kernel and its 16-channel chunks (yolo_trunk.cpp: YoloTrunk::conv)
+    const int force_kc = f->force_kc > 0 ? f->force_kc : ((f->post_w || f->front_img) ? 16 : 0);
+    const bool plain = f->out_plain != 0;
+    ConvOpState st;
+    conv_setup(ctx, d, x, w_ohwi, bias, residual, y, st, force_kc, plain);
+    gtx::ConvProblem& p = st.g.p[0];
+    gtx::DevBuf x2, sat, pw, pb, fimg, fw, fb, mid;
+    gtx::ConvGroup g2{};                                // post_separate: the 1x1 layer as a launch of its own
+    gtx::ConvConfig c2{};
+    if (f->x2) {
+      upload_fmt(x2, d->dtype, f->x2, (size_t)d->n * (d->h / 2) * (d->w / 2) * f->in2_cstride * gtx::dtype_size(d->dtype));
+      p.in2 = x2.p; p.in2_cstride = f->in2_cstride; p.in2_coff = f->in2_coff; p.c_split = f->c_split;
+    }
+    p.out_plain = plain ? 1 : 0;
+    if (f->sat) {
+      zeros(sat, 4);
+      p.sat_flag = sat.as<int>();
+    }
+    if (f->post_w) {                                    // as fuse_front() finds model.2.cv1: the 1x1 layer's own packed image, 32-channel chunks
+      c2 = gtx::conv_pick_config(d->dtype, 1, 1, d->cout, d->cout, 32);
+      float sc = 1.f;
+      const std::vector<uint8_t> img = gtx::pack_conv_weights(f->post_w, d->cout, d->cout, c2, &sc);
+      upload(pw, img.data(), img.size());
+      p.post_w = pw.p; p.post_scale = sc; p.post_act = f->post_act;
+      if (f->post_bias) {
+        zeros(pb, (size_t)(d->cout + 63) / 64 * 64 * sizeof(float));
+        GTX_HIP(hipMemcpy(pb.p, f->post_bias, d->cout * sizeof(float), hipMemcpyHostToDevice));
+        p.post_bias = pb.as<float>();
+      }
+    }
+    if (f->front_img) {                                 // as YoloTrunk::stem() keeps them for fuse_stem()
+      upload(fimg, f->front_img, (size_t)d->n * f->front_h * f->front_w_px * 4);
+      float sc = 1.f;
+      const std::vector<uint16_t> img = gtx::pack_front_weights_split(f->front_w27, d->cin, &sc);
+      upload(fw, img.data(), img.size() * 2);
+      zeros(fb, (size_t)(d->cin + 31) / 32 * 32 * sizeof(float));
+      GTX_HIP(hipMemcpy(fb.p, f->front_bias, d->cin * sizeof(float), hipMemcpyHostToDevice));
+      p.front_img = fimg.p; p.front_w = fw.p; p.front_bias = fb.as<float>(); p.front_scale = sc;
+      p.front_h = f->front_h; p.front_w_px = f->front_w_px;
+    }
+    if (f->post_w && f->post_separate) {
+      // What the post stage replaces, as the detector runs it with GTX_FUSE_FRONT=0: the 3x3 launch writes its pair-format output to
+      // HBM and the 1x1 layer reads it there. (Two hook calls would take the map through the host instead, and hi + lo split again
+      // is not always the same two halves: a tie in fp16(hi + lo) may go the other way.)
+      if (f->ty_count || f->members > 1 || d->dtype != GTX_F32S) op_bad("conv2d_fused", "post_separate: one whole split-f16x3 launch");
+      zeros(mid, (size_t)d->n * st.ho * st.wo * d->cout * 4);
+      // q is filled field by field: a member added to ConvProblem that a stand-alone 1x1 launch needs has to be set here too
+      // (conv_setup fills the first launch's; g2{} leaves everything else of q zero = off)
+      gtx::ConvProblem& q = g2.p[0];
+      q.in = mid.p; q.out = p.out; q.wpack = p.post_w; q.bias = p.post_bias;
+      q.N = d->n; q.H = q.Ho = st.ho; q.W = q.Wo = st.wo; q.Cin = q.Cout = d->cout;
+      q.in_cstride = d->cout; q.out_cstride = p.out_cstride; q.out_coff = p.out_coff; q.res_cstride = d->cout;
+      q.act = p.post_act; q.acc_scale = p.post_scale; q.post_scale = 1.f; q.out_plain = p.out_plain; q.sat_flag = p.sat_flag;
+      p.out = mid.p; p.out_cstride = d->cout; p.out_coff = 0; p.out_plain = 0;
+      p.post_w = nullptr; p.post_bias = nullptr; p.post_scale = 1.f; p.post_act = 0;
+      c2.variant = 2;                                   // the 32x32x16 kernel, as fuse_front() requires of the layer it folds in
+      g2.count = 1;
+      gtx::conv_group_finalize(g2, c2);
+    }
+    p.ty_first = f->ty_first; p.ty_count = f->ty_count;
+    for (int i = 1; i < f->members; ++i) st.g.p[i] = p;   // the same problem again: only to meet a launcher's rule on group size
+    st.g.count = f->members > 1 ? f->members : 1;
+    gtx::conv_group_finalize(st.g, st.cfg);
+    gtx::conv_launch(st.g, st.cfg, ctx->stream);
+    if (g2.count) gtx::conv_launch(g2, c2, ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t yb = (size_t)d->n * st.ho * st.wo * d->out_cstride * gtx::dtype_size(d->dtype);
+    download_fmt(y, plain ? GTX_F32 : d->dtype, st.y, yb);
+    if (f->sat) download(f->sat, sat, 4);
+  });
+}
+
+// The stem (model.0: 3x3 stride 2 on RGB0 bytes + bias + SiLU) as launch_stem runs it for the detector and the ReID crops
+// (tests/test_front_ops_gpu.py). packed = 0 with GTX_F16: the VALU kernel; GTX_F32 is always that kernel, GTX_F32S always packed.
+int gtx_op_stem(gtx_ctx* ctx, int dtype, int packed, int n, int h, int w, int c0, const void* img, const float* w27, const float* bias,
+                void* out) {
+  return guarded([&] {
+    if (dtype != GTX_F16 && dtype != GTX_F32 && dtype != GTX_F32S) op_bad("stem", "dtype: GTX_F16, GTX_F32 or GTX_F32S");
+    if (c0 < 16 || c0 > 96 || c0 % 16) op_bad("stem", "c0 must be 16, 32, 48, 64, 80 or 96");
+    if (n < 1 || h < 1 || w < 1 || (double)n * h * w > 1e9) op_bad("stem", "n, h and w must be at least 1");
+    need(ctx, "ctx"); need(img, "img"); need(w27, "w27"); need(bias, "bias"); need(out, "out");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
+    const size_t ob = (size_t)n * ho * wo * c0 * gtx::dtype_size(dtype);
+    gtx::DevBuf dimg, dw, db, dpk, dout;
+    upload(dimg, img, (size_t)n * h * w * 4);
+    upload(dw, w27, (size_t)27 * c0 * 4);
+    zeros(db, (size_t)(c0 + 31) / 32 * 32 * sizeof(float));      // whole 32-channel groups: the MFMA stems read a group's bias unconditionally
+    GTX_HIP(hipMemcpy(db.p, bias, c0 * sizeof(float), hipMemcpyHostToDevice));
+    zeros(dout, ob);
+    float sc = 1.f;
+    if (dtype == GTX_F32S) {
+      const std::vector<uint16_t> pk = gtx::pack_stem_weights_split(w27, c0, &sc);
+      upload(dpk, pk.data(), pk.size() * 2);
+    } else if (dtype == GTX_F16 && packed) {
+      const std::vector<uint16_t> pk = gtx::pack_stem_weights_f16(w27, c0);
+      upload(dpk, pk.data(), pk.size() * 2);
+    }
+    gtx::launch_stem(dtype, dimg.p, n, h, w, dw.as<float>(), db.as<float>(), dpk.p, c0, dout.p, ho, wo, ctx->stream, sc);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download_fmt(out, dtype, dout, ob);
   });
 }
 

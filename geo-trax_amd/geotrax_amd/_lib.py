@@ -27,6 +27,14 @@ class ConvDesc(C.Structure):
         "in_cstride", "in_coff", "out_cstride", "out_coff", "has_residual")]
 
 
+class ConvFused(C.Structure):
+    """gtx_conv_fused (include/gtx.h)."""
+    _fields_ = [("x2", C.c_void_p), ("in2_cstride", C.c_int), ("in2_coff", C.c_int), ("c_split", C.c_int), ("out_plain", C.c_int),
+                ("sat", C.POINTER(C.c_int)), ("post_w", C.c_void_p), ("post_bias", C.c_void_p), ("post_act", C.c_int), ("post_separate", C.c_int),
+                ("front_img", C.c_void_p), ("front_w27", C.c_void_p), ("front_bias", C.c_void_p), ("front_h", C.c_int),
+                ("front_w_px", C.c_int), ("ty_first", C.c_int), ("ty_count", C.c_int), ("force_kc", C.c_int), ("members", C.c_int)]
+
+
 class DetConfig(C.Structure):
     _fields_ = [
         ("imgsz", C.c_int), ("conf", C.c_float), ("iou", C.c_float), ("max_det", C.c_int),
@@ -125,6 +133,8 @@ _SIGNATURES = {
     "gtx_op_conv2d": (C.c_int, [_P, C.POINTER(ConvDesc), _P, _P, _P, _P, _P]),
     "gtx_op_conv2d_group": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gtx_op_conv2d_time": (C.c_int, [_P, C.POINTER(ConvDesc), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
+    "gtx_op_conv2d_fused": (C.c_int, [_P, C.POINTER(ConvDesc), C.POINTER(ConvFused), _P, _P, _P, _P, _P]),
+    "gtx_op_stem": (C.c_int, [_P] + [C.c_int] * 6 + [_P, _P, _P, _P]),
     "gtx_op_conv_xcd_ranges": (C.c_int, [C.c_int, _P, _P, _P, _P]),
     "gtx_op_sppf_pool": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gtx_op_upsample2x": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int]),

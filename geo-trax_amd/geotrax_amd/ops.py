@@ -84,6 +84,80 @@ def conv2d_group(members, *, stride: int = 1, act: bool = True, split: bool = Fa
     return outs
 
 
+def conv2d_fused(x: np.ndarray | None, w_ohwi: np.ndarray, bias: np.ndarray | None = None, *, stride: int = 1, act: bool = True,
+                 residual: np.ndarray | None = None, in_coff: int = 0, cin: int | None = None, out: np.ndarray | None = None, out_coff: int = 0,
+                 split: bool = True, in_shape=None, x2: np.ndarray | None = None, in2_coff: int = 0, c_split: int = 0, out_plain: bool = False,
+                 want_sat: bool = False, post_w: np.ndarray | None = None, post_bias: np.ndarray | None = None, post_act: int = 1, post_separate: bool = False,
+                 front_img: np.ndarray | None = None, front_w27: np.ndarray | None = None, front_bias: np.ndarray | None = None,
+                 front_hw=None, ty_first: int = 0, ty_count: int = 0, force_kc: int = 0, members: int = 0,
+                 ctx: _lib.Context | None = None):
+    """conv2d with the extras of gtx_conv_fused (include/gtx.h), one launch. x2 [n,h/2,w/2,cs2]: the second source, whose channels
+    [in2_coff, in2_coff + c_split) upsampled 2x are the layer's first c_split input channels. post_w [cout,cout] (or [cout,1,1,cout]),
+    post_bias, post_act: the fused 1x1 layer (post_separate: the same two layers as two launches, the intermediate map staying in
+    HBM in the pair format). front_img [n,H,W,4] RGB0 bytes, front_w27 [27,cin], front_bias: the fused stem; x may
+    then be None and the layer's input map is in_shape = (n, h, w) (default: half of front_img's sides); front_hw overrides the image
+    size told to the launcher. Returns the output, or (output, sat) with want_sat."""
+    ctx = ctx or _lib.default_context()
+    w = np.ascontiguousarray(w_ohwi, dtype=np.float32)
+    cout, k, _, wcin = w.shape
+    cin = wcin if cin is None else cin
+    assert cin == wcin
+    dt = np.float32
+    if x is not None:
+        x = np.ascontiguousarray(x)
+        n, h, wd, cs = x.shape
+        dt = x.dtype
+    else:
+        assert front_img is not None, "only a front stage computes its own input"
+        n, h, wd = in_shape if in_shape is not None else (front_img.shape[0], front_img.shape[1] // 2, front_img.shape[2] // 2)
+        cs = cin
+    if split and dt != np.float32:
+        raise TypeError("split=True needs float32 activations")
+    pad = k // 2
+    ho, wo = (h + 2 * pad - k) // stride + 1, (wd + 2 * pad - k) // stride + 1
+    if out is None:
+        out = np.zeros((n, ho, wo, cout), dtype=dt)
+    out = np.array(out, dtype=dt, order="C")
+    assert out.shape[:3] == (n, ho, wo)
+    d = ConvDesc(dtype=GTX_F32S if split else (GTX_F16 if dt == np.float16 else GTX_F32), n=n, h=h, w=wd, cin=cin, cout=cout, ksize=k,
+                 stride=stride, act=int(act), in_cstride=cs, in_coff=in_coff, out_cstride=out.shape[3], out_coff=out_coff,
+                 has_residual=int(residual is not None))
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+    addr = lambda a: None if a is None else a.ctypes.data
+    b, r = f32(bias), (None if residual is None else np.ascontiguousarray(residual, dtype=dt))
+    x2a = None if x2 is None else np.ascontiguousarray(x2, dtype=dt)
+    pw, pb, fw, fb = f32(post_w), f32(post_bias), f32(front_w27), f32(front_bias)
+    fi = None if front_img is None else np.ascontiguousarray(front_img, dtype=np.uint8)
+    assert pw is None or pw.size == cout * cout
+    assert fi is None or (fi.ndim == 4 and fi.shape[3] == 4 and fw is not None and fw.shape == (27, cin) and fb is not None and fb.size == cin)
+    assert x2a is None or x2a.shape[:3] == (n, h // 2, wd // 2)
+    fh, fwp = front_hw if front_hw is not None else ((fi.shape[1], fi.shape[2]) if fi is not None else (0, 0))
+    assert fi is None or fh * fwp <= fi.shape[1] * fi.shape[2]          # the launcher is told no more image than the array holds
+    sat = C.c_int(0)
+    f = _lib.ConvFused(x2=addr(x2a), in2_cstride=0 if x2a is None else x2a.shape[3], in2_coff=in2_coff, c_split=c_split, out_plain=int(out_plain),
+                       sat=C.pointer(sat) if want_sat else None, post_w=addr(pw), post_bias=addr(pb), post_act=int(post_act), post_separate=int(post_separate),
+                       front_img=addr(fi), front_w27=addr(fw), front_bias=addr(fb), front_h=fh, front_w_px=fwp, ty_first=ty_first,
+                       ty_count=ty_count, force_kc=force_kc, members=members)
+    check(ctx.lib.gtx_op_conv2d_fused(ctx.handle, C.byref(d), C.byref(f), ptr(x), ptr(w), ptr(b), ptr(r), ptr(out)))
+    return (out, sat.value) if want_sat else out
+
+
+def stem(img: np.ndarray, w27: np.ndarray, bias: np.ndarray, *, dtype, packed: bool = True, ctx: _lib.Context | None = None) -> np.ndarray:
+    """The stem launch (model.0) on img [n,h,w,4] RGB0 bytes: SiLU(conv 3x3 stride 2 of img / 255 + bias), w27 [27,c0] with row
+    (ky * 3 + kx) * 3 + colour. dtype: GTX_F16 (packed: the matrix-core kernel, else the VALU one; fp16 out), GTX_F32 (the VALU
+    kernel) or GTX_F32S (the split-f16x3 kernel; the values its pair-format output holds, as fp32)."""
+    ctx = ctx or _lib.default_context()
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    w27 = np.ascontiguousarray(w27, dtype=np.float32)
+    bias = np.ascontiguousarray(bias, dtype=np.float32)
+    n, h, w, four = img.shape
+    c0 = w27.shape[1]
+    assert four == 4 and w27.shape == (27, c0) and bias.shape == (c0,)
+    out = np.zeros((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c0), np.float16 if dtype == GTX_F16 else np.float32)
+    check(ctx.lib.gtx_op_stem(ctx.handle, int(dtype), int(packed), n, h, w, c0, ptr(img), ptr(w27), ptr(bias), ptr(out)))
+    return out
+
+
 def conv2d_time(dtype, n, h, w, cin, cout, ksize, stride, iters=20, ctx=None):
     """Mean kernel time (ms) and algorithmic FLOPs of one conv launch on zero-filled data."""
     ctx = ctx or _lib.default_context()

@@ -78,7 +78,9 @@ extern "C" {
  *     gtx_jpeg_{plan_bound, plan, entropy_ms}, gtx_op_jpeg_entropy and gtx_feeder_{set_jpeg_entropy, jpeg_stats} (the JPEG source's entropy decoder as
  *     HIP kernels, opt-in per feeder) added: new entry points only, so the number stays.
  *     gtx_op_georef_tracks, gtx_georef_tracks_ms and gtx_georef_tracks_cfg (the georeference stage's per-track columns as HIP
- *     kernels, opt-in per run) added: new entry points and a struct of their own only, so the number stays. */
+ *     kernels, opt-in per run) added: new entry points and a struct of their own only, so the number stays.
+ *     gtx_op_stem and gtx_op_conv2d_fused (the stem launch, and the convolution launch with its second source, plain output,
+ *     saturation flag and fused post / front stages, on host arrays) added: the same, the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -374,6 +376,35 @@ int gtx_op_conv2d_time(gtx_ctx* ctx, const gtx_conv_desc* d, int iters, float* m
  * Fails when the members do not pick the same kernel. */
 int gtx_op_conv2d_group(gtx_ctx* ctx, int n_members, const gtx_conv_desc* descs, const void* const* xs, const float* const* ws,
                         const float* const* biases, void* const* ys, const int* ty_first, const int* ty_count);
+/* What gtx_op_conv2d leaves off: the second source of the neck's 1x1 layers, the plain-fp32 output and the saturation flag of the
+ * split-f16x3 launches, and the stages fused into the detector's first launch. Every part is off when its pointer is NULL (out_plain,
+ * ty_count, force_kc, members: when 0). The launchers' own checks decide what a kernel form accepts; a refused call launches nothing. */
+typedef struct gtx_conv_fused {
+  const void* x2;          /* second source [n][h/2][w/2][in2_cstride] dtype: input channels [0, c_split) are its channels */
+  int in2_cstride, in2_coff, c_split; /* [in2_coff, in2_coff + c_split) upsampled 2x (nearest); [c_split, cin) come from x */
+  int out_plain;           /* GTX_F32S: y is written (and handed back) as plain fp32, not through the pair format */
+  int* sat;                /* out: 1 when the launch clamped a value to fp16's range on its way into the pair format */
+  const float* post_w;     /* post stage: [cout][cout] OHWI weights of a 1x1 layer applied to the tile before it is stored */
+  const float* post_bias;  /* [cout] or NULL */
+  int post_act;
+  int post_separate;       /* 1: the same two layers as two launches, the 3x3 layer's pair-format output staying in HBM between them */
+  const void* front_img;   /* front stage: [n][front_h][front_w_px][4] RGB0 bytes; the layer's input is the stem applied to it */
+  const float* front_w27;  /* [27][cin] as gtx_op_stem's w27 */
+  const float* front_bias; /* [cin] */
+  int front_h, front_w_px;
+  int ty_first, ty_count;  /* as gtx_op_conv2d_group */
+  int force_kc;            /* > 0: the K chunk (16 or 32) instead of the library's pick; a post or front stage pins 16 by itself */
+  int members;             /* > 1: the problem is put into the group that many times (a launcher's rule on the group size) */
+} gtx_conv_fused;
+/* gtx_op_conv2d with the extras of *f; x may be NULL under a front stage (the kernel does not read it). */
+int gtx_op_conv2d_fused(gtx_ctx* ctx, const gtx_conv_desc* d, const gtx_conv_fused* f, const void* x, const float* w_ohwi,
+                        const float* bias, const void* residual, void* y);
+/* The stem, ultralytics' Conv(3, c0, 3, 2) + SiLU on `im / 255`: img [n][h][w][4] RGB0 bytes, w27 [27][c0] fp32 with row
+ * (ky * 3 + kx) * 3 + colour, bias [c0], out [n][(h-1)/2+1][(w-1)/2+1][c0] (fp16 for GTX_F16, else fp32; GTX_F32S: the values the
+ * pair format holds). GTX_F16 with packed = 0 and GTX_F32: the VALU kernel; GTX_F16 with packed = 1 and GTX_F32S: the matrix-core
+ * kernels on their packed weights. c0 must be 16, 32, 48, 64, 80 or 96; h, w >= 1. */
+int gtx_op_stem(gtx_ctx* ctx, int dtype, int packed, int n, int h, int w, int c0, const void* img, const float* w27,
+                const float* bias, void* out);
 /* Host only (no GPU call): how a grouped convolution launch is cut over the 8 XCDs. n_members problems of
  * blocks[i] workgroups with cin[i] input channels each, in launch order. xcd_begin[0..8]: hardware block b takes
  * logical block xcd_begin[b & 7] + (b >> 3) and exits when that reaches xcd_begin[(b & 7) + 1]; the ranges hold equal

@@ -84,6 +84,54 @@ def test_rtdetr_hooks_refuse_bad_sizes_before_any_launch():
     assert lib.gtx_detector_create(None, C.byref(cfg), C.byref(h)) == -3 and not h.value
 
 
+def test_front_hooks_refuse_null_arguments_and_bad_sizes_before_any_launch():
+    """Host only: gtx_op_stem and gtx_op_conv2d_fused check their arrays and the sizes they allocate by before they touch a context."""
+    from geotrax_amd import _lib
+
+    lib = _lib.load()
+    f = np.zeros(4096, np.float32)
+    img = np.zeros(4 * 8 * 8, np.uint8)
+    p = _lib.ptr
+    stem = lambda dtype, n, h, w, c0, im=img, w27=f, b=f, out=f: lib.gtx_op_stem(None, dtype, 1, n, h, w, c0, p(im) if im is not None else None,
+                                                                               p(w27) if w27 is not None else None, p(b) if b is not None else None,
+                                                                               p(out) if out is not None else None)
+    for c0 in (0, 8, 24, 112, 128):
+        assert stem(2, 1, 8, 8, c0) == -1 and b"c0 must be 16, 32, 48, 64, 80 or 96" in lib.gtx_last_error()
+    assert stem(3, 1, 8, 8, 32) == -1 and b"dtype" in lib.gtx_last_error()
+    for n, h, w in ((0, 8, 8), (1, 0, 8), (1, 8, 0), (1, -2, 8)):
+        assert stem(2, n, h, w, 32) == -1 and b"at least 1" in lib.gtx_last_error()
+    assert stem(2, 1, 8, 8, 32) == -1 and b"ctx is NULL" in lib.gtx_last_error()              # the sizes were fine
+
+    d = _lib.ConvDesc(dtype=2, n=1, h=8, w=8, cin=32, cout=64, ksize=3, stride=2, act=1, in_cstride=32, in_coff=0, out_cstride=64, out_coff=0)
+    fused = lambda ex, x=f, w=f, y=f, res=None, desc=d: lib.gtx_op_conv2d_fused(None, C.byref(desc) if desc is not None else None,
+                                                                                C.byref(ex) if ex is not None else None, p(x) if x is not None else None,
+                                                                                p(w) if w is not None else None, None, p(res) if res is not None else None,
+                                                                                p(y) if y is not None else None)
+    assert fused(_lib.ConvFused(), desc=None) == -1 and b"desc is NULL" in lib.gtx_last_error()
+    assert fused(None) == -1 and b"fused is NULL" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(), w=None) == -1 and b"w is NULL" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(), y=None) == -1 and b"y is NULL" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(), x=None) == -1 and b"x is NULL" in lib.gtx_last_error()     # only a front stage does without x
+    dr = _lib.ConvDesc(dtype=2, n=1, h=8, w=8, cin=32, cout=64, ksize=3, stride=2, act=1, in_cstride=32, in_coff=0, out_cstride=64, out_coff=0,
+                       has_residual=1)
+    assert fused(_lib.ConvFused(), desc=dr) == -1 and b"residual is NULL" in lib.gtx_last_error()
+    a = f.ctypes.data
+    front = dict(front_img=img.ctypes.data, front_w27=a, front_bias=a, front_h=16, front_w_px=16)
+    assert fused(_lib.ConvFused(**{**front, "front_w27": None}), x=None) == -1 and b"front_w27 is NULL" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(**{**front, "front_bias": None}), x=None) == -1 and b"front_bias is NULL" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(**{**front, "front_h": 0}), x=None) == -1 and b"front stage: bad sizes" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(**{**front, "front_w_px": -4}), x=None) == -1 and b"front stage: bad sizes" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(**front), x=None) == -1 and b"ctx is NULL" in lib.gtx_last_error()     # x may be NULL here
+    for bad in (dict(in2_cstride=64, in2_coff=0, c_split=0), dict(in2_cstride=64, in2_coff=48, c_split=32), dict(in2_cstride=64, in2_coff=-8, c_split=32),
+                dict(in2_cstride=68, in2_coff=0, c_split=32), dict(in2_cstride=64, in2_coff=4, c_split=32)):
+        assert fused(_lib.ConvFused(x2=a, **bad)) == -1 and b"second source" in lib.gtx_last_error(), bad
+    d1 = _lib.ConvDesc(dtype=2, n=1, h=1, w=8, cin=64, cout=64, ksize=1, stride=1, act=1, in_cstride=64, in_coff=0, out_cstride=64, out_coff=0)
+    assert fused(_lib.ConvFused(x2=a, in2_cstride=64, in2_coff=0, c_split=32), desc=d1) == -1 and b"at least 2 x 2" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(force_kc=-16)) == -1 and b"force_kc" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(members=9)) == -1 and b"members" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused()) == -1 and b"ctx is NULL" in lib.gtx_last_error()                    # nothing asked for: gtx_op_conv2d
+
+
 def test_head_hooks_refuse_bad_sizes_before_any_launch():
     """Host only: what the post-pass launchers would refuse, or their kernels would mishandle in silence, comes back as an error code
     from the operator hooks with no context given."""
