@@ -656,6 +656,169 @@ int gtx_op_rt_post(gtx_ctx* ctx, int n, int nq, int nc, const float* logits, int
   });
 }
 
+// ---- RT-DETR's map-side kernels, one hook per launcher (tests/test_rtdetr_map_ops_gpu.py). As above: every size is checked before
+// anything touches the GPU. Every map holds n_alloc images of which the first n run: what lies behind them, and beside a channel
+// slice, is uploaded as given and comes back with the output, so a test sees a read or a write outside the launch's own data.
+namespace {
+void rt_map_fmt_check(const char* op, int dtype) {
+  if (dtype != GTX_F16 && dtype != GTX_F32 && dtype != GTX_F32S) op_bad(op, "dtype: GTX_F16, GTX_F32 or GTX_F32S");
+}
+void rt_map_batch_check(const char* op, int n, int n_alloc) {
+  if (n < 1 || n_alloc < n || n_alloc > 4096) op_bad(op, "n >= 1 and n <= n_alloc <= 4096");
+}
+// c channels (whole groups of `group`) at coff of an [n_alloc][h][w][cstride] map: the kernels move 16- and 32-byte groups of 8 channels
+void rt_map_check(const char* op, int n_alloc, int h, int w, int c, int cstride, int coff, int group = 8) {
+  if (h < 1 || w < 1 || h > (1 << 14) || w > (1 << 14)) op_bad(op, "h and w must be 1..16384");
+  if (c < group || c % group) op_bad(op, group == 16 ? "the channel count must be a positive multiple of 16" : "the channel count must be a positive multiple of 8");
+  if (cstride < 8 || cstride % 8 || cstride > (1 << 16) || coff < 0 || coff % 8) op_bad(op, "channel strides and offsets must be multiples of 8");
+  if ((long)coff + c > cstride) op_bad(op, "a channel slice does not fit its stride");
+  if ((double)n_alloc * h * w * cstride > 1e9) op_bad(op, "maps too large");
+}
+size_t rt_map_bytes(int dtype, int n_alloc, int h, int w, int cstride) { return (size_t)n_alloc * h * w * cstride * gtx::dtype_size(dtype); }
+}  // namespace
+
+int gtx_op_rt_stem1(gtx_ctx* ctx, int dtype, int n, int n_alloc, int H, int W, int c0, const void* img, const float* w27, const float* bias, void* out,
+                    int out_cstride, int out_coff, int* saturated) {
+  return guarded([&] {
+    const char* op = "rt_stem1";
+    rt_map_fmt_check(op, dtype);
+    rt_map_batch_check(op, n, n_alloc);
+    if (H < 2 || W < 2 || H % 2 || W % 2) op_bad(op, "H and W must be even and at least 2");
+    if (c0 > 1024) op_bad(op, "at most 1024 channels");
+    rt_map_check(op, n_alloc, H / 2, W / 2, c0, out_cstride, out_coff, 16);
+    need(img, "img"); need(w27, "w27"); need(bias, "bias"); need(out, "out"); need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t ob = rt_map_bytes(dtype, n_alloc, H / 2, W / 2, out_cstride);
+    gtx::DevBuf dimg, dw, db, dout, ds;
+    upload(dimg, img, (size_t)n_alloc * H * W * 4);
+    upload(dw, w27, (size_t)27 * c0 * 4); upload(db, bias, (size_t)c0 * 4);
+    upload_fmt(dout, dtype, out, ob);
+    zeros(ds, 4);
+    const gtx::RtMap o{dout.p, H / 2, W / 2, out_cstride, out_coff, c0};
+    gtx::launch_rt_stem1(dtype, dimg.p, n, H, W, dw.as<float>(), db.as<float>(), o, ds.as<int>(), ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download_fmt(out, dtype, dout, ob);
+    if (saturated) download(saturated, ds, 4);
+  });
+}
+
+int gtx_op_rt_pool2(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int c, const void* in, int in_cstride, int in_coff, void* out,
+                    int out_cstride, int out_coff, int* saturated) {
+  return guarded([&] {
+    const char* op = "rt_pool2";
+    rt_map_fmt_check(op, dtype);
+    rt_map_batch_check(op, n, n_alloc);
+    rt_map_check(op, n_alloc, h, w, c, in_cstride, in_coff);
+    rt_map_check(op, n_alloc, h, w, c, out_cstride, out_coff);
+    need(in, "in"); need(out, "out"); need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t xb = rt_map_bytes(dtype, n_alloc, h, w, in_cstride), yb = rt_map_bytes(dtype, n_alloc, h, w, out_cstride);
+    gtx::DevBuf dx, dy, ds;
+    upload_fmt(dx, dtype, in, xb); upload_fmt(dy, dtype, out, yb);
+    zeros(ds, 4);
+    const gtx::RtMap i{dx.p, h, w, in_cstride, in_coff, c}, o{dy.p, h, w, out_cstride, out_coff, c};
+    gtx::launch_rt_pool2(dtype, i, o, n, ds.as<int>(), ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download_fmt(out, dtype, dy, yb);
+    if (saturated) download(saturated, ds, 4);
+  });
+}
+
+int gtx_op_rt_dwconv(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int c, int k, int stride, const void* x, int in_cstride, int in_coff,
+                     const float* wt, const float* bias, int act, const void* res, int res_cstride, int res_coff, void* out, int out_cstride, int out_coff,
+                     int* saturated) {
+  return guarded([&] {
+    const char* op = "rt_dwconv";
+    rt_map_fmt_check(op, dtype);
+    rt_map_batch_check(op, n, n_alloc);
+    if ((k != 3 && k != 5 && k != 7) || (stride != 1 && stride != 2)) op_bad(op, "k must be 3, 5 or 7 and the stride 1 or 2");
+    if (act < 0 || act > 2) op_bad(op, "act: 0 none, 1 SiLU, 2 ReLU");
+    rt_map_check(op, n_alloc, h, w, c, in_cstride, in_coff);
+    const int ho = (h - 1) / stride + 1, wo = (w - 1) / stride + 1;
+    rt_map_check(op, n_alloc, ho, wo, c, out_cstride, out_coff);
+    if (res) rt_map_check(op, n_alloc, ho, wo, c, res_cstride, res_coff);
+    need(x, "x"); need(wt, "w"); need(out, "out"); need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t xb = rt_map_bytes(dtype, n_alloc, h, w, in_cstride), yb = rt_map_bytes(dtype, n_alloc, ho, wo, out_cstride);
+    gtx::DevBuf dx, dy, dr, dw, db, ds;
+    upload_fmt(dx, dtype, x, xb); upload_fmt(dy, dtype, out, yb);
+    if (res) upload_fmt(dr, dtype, res, rt_map_bytes(dtype, n_alloc, ho, wo, res_cstride));
+    upload(dw, wt, (size_t)k * k * c * 4);
+    if (bias) upload(db, bias, (size_t)c * 4);
+    zeros(ds, 4);
+    const gtx::RtMap i{dx.p, h, w, in_cstride, in_coff, c}, o{dy.p, ho, wo, out_cstride, out_coff, c}, r{dr.p, ho, wo, res_cstride, res_coff, c};
+    gtx::launch_rt_dwconv(dtype, i, o, n, k, stride, dw.as<float>(), bias ? db.as<float>() : nullptr, act, ds.as<int>(), ctx->stream, res ? &r : nullptr);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download_fmt(out, dtype, dy, yb);
+    if (saturated) download(saturated, ds, 4);
+  });
+}
+
+int gtx_op_rt_upsample2x(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int c, const void* x, int in_cstride, int in_coff, void* y,
+                         int out_cstride, int out_coff) {
+  return guarded([&] {
+    const char* op = "rt_upsample2x";
+    rt_map_fmt_check(op, dtype);
+    rt_map_batch_check(op, n, n_alloc);
+    rt_map_check(op, n_alloc, h, w, c, in_cstride, in_coff);
+    rt_map_check(op, n_alloc, 2 * h, 2 * w, c, out_cstride, out_coff);
+    need(x, "x"); need(y, "y"); need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t xb = rt_map_bytes(dtype, n_alloc, h, w, in_cstride), yb = rt_map_bytes(dtype, n_alloc, 2 * h, 2 * w, out_cstride);
+    gtx::DevBuf dx, dy;
+    upload_fmt(dx, dtype, x, xb); upload_fmt(dy, dtype, y, yb);
+    const gtx::RtMap i{dx.p, h, w, in_cstride, in_coff, c}, o{dy.p, 2 * h, 2 * w, out_cstride, out_coff, c};
+    gtx::launch_rt_upsample2x(dtype, i, o, n, ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download_fmt(y, dtype, dy, yb);
+  });
+}
+
+int gtx_op_rt_tokens_in(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int c, const void* in, int in_cstride, int in_coff, const float* pos,
+                        float* src, float* q) {
+  return guarded([&] {
+    const char* op = "rt_tokens_in";
+    rt_map_fmt_check(op, dtype);
+    rt_map_batch_check(op, n, n_alloc);
+    rt_map_check(op, n_alloc, h, w, c, in_cstride, in_coff);
+    if ((pos == nullptr) != (q == nullptr)) op_bad(op, "pos and q are given together or not at all");
+    need(in, "in"); need(src, "src"); need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t tb = (size_t)n_alloc * h * w * c * 4;
+    gtx::DevBuf dx, dp, dsrc, dq;
+    upload_fmt(dx, dtype, in, rt_map_bytes(dtype, n_alloc, h, w, in_cstride));
+    upload(dsrc, src, tb);
+    if (q) {
+      upload(dp, pos, (size_t)h * w * c * 4);
+      upload(dq, q, tb);
+    }
+    const gtx::RtMap i{dx.p, h, w, in_cstride, in_coff, c};
+    gtx::launch_rt_tokens_in(dtype, i, n, q ? dp.as<float>() : nullptr, dsrc.as<float>(), q ? dq.as<float>() : nullptr, ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download(src, dsrc, tb);
+    if (q) download(q, dq, tb);
+  });
+}
+
+int gtx_op_rt_mask_invalid(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int c, void* m, int cstride, int coff, int level) {
+  return guarded([&] {
+    const char* op = "rt_mask_invalid";
+    rt_map_fmt_check(op, dtype);
+    rt_map_batch_check(op, n, n_alloc);
+    rt_map_check(op, n_alloc, h, w, c, cstride, coff);
+    if (level < 0 || level > 5) op_bad(op, "level must be 0..5");
+    need(m, "m"); need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t mb = rt_map_bytes(dtype, n_alloc, h, w, cstride);
+    gtx::DevBuf dm;
+    upload_fmt(dm, dtype, m, mb);
+    const gtx::RtMap mm{dm.p, h, w, cstride, coff, c};
+    gtx::launch_rt_mask_invalid(dtype, mm, n, level, ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download_fmt(m, dtype, dm, mb);
+  });
+}
+
 // ---- the detector's post-pass kernels, one hook per launcher (tests/test_head_ops_gpu.py). As above: every size, and every index a
 // kernel would follow, is checked before anything touches the GPU.
 namespace {

@@ -1245,6 +1245,7 @@ void launch_rt_tokens_in(int fmt, const RtMap& in, int n, const float* pos, floa
 }
 
 void launch_rt_mask_invalid(int fmt, const RtMap& m, int n, int level, hipStream_t s) {
+  GTX_CHECK(m.c % 8 == 0, "rt_mask_invalid: channels");
   const size_t total = (size_t)n * m.h * m.w * (m.c / 8);
   hipLaunchKernelGGL(rt_mask_invalid_kernel, dim3(blocks_for(total)), dim3(256), 0, s, m, n, level, 8 * fmt_size(fmt));
   GTX_HIP(hipGetLastError());

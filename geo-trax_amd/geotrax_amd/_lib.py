@@ -149,6 +149,13 @@ _SIGNATURES = {
     "gtx_op_rt_gather_refer": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "gtx_op_rt_deform": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "gtx_op_rt_post": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_float, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "gtx_op_rt_stem1": (C.c_int, [_P] + [C.c_int] * 6 + [_P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "gtx_op_rt_pool2": (C.c_int, [_P] + [C.c_int] * 6 + [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "gtx_op_rt_dwconv": (C.c_int, [_P] + [C.c_int] * 8 + [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int,
+                                   C.POINTER(C.c_int)]),
+    "gtx_op_rt_upsample2x": (C.c_int, [_P] + [C.c_int] * 6 + [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
+    "gtx_op_rt_tokens_in": (C.c_int, [_P] + [C.c_int] * 6 + [_P, C.c_int, C.c_int, _P, _P, _P]),
+    "gtx_op_rt_mask_invalid": (C.c_int, [_P] + [C.c_int] * 6 + [_P, C.c_int, C.c_int, C.c_int]),
     "gtx_op_head_gate": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gtx_op_head_boxes": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
     "gtx_op_nms": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -480,6 +480,100 @@ def rt_post(logits: np.ndarray, nc: int, refer: np.ndarray, conf: float, frame_w
     return rows, out_n, raw
 
 
+# ---------------------------------------------------------------------------- RT-DETR's map-side kernels (gtx_op_rt_*)
+# Maps are [n_alloc, h, w, cstride] arrays whose channels [coff, coff + c) a launch reads or writes; the first n images run
+# (default all). An output map is given as it is before the launch; a copy comes back with only the launch's slice written.
+def _rt_map(a, split):
+    a = np.array(a, order="C")
+    assert a.ndim == 4
+    return a, _map_fmt(a, split)
+
+
+def rt_stem1(img: np.ndarray, w27: np.ndarray, bias: np.ndarray, out: np.ndarray, *, n: int | None = None, out_coff: int = 0, split: bool = False,
+             ctx=None):
+    """HGStem.stem1 on img [n_alloc, H, W, 4] RGB0 bytes: ReLU(conv 3x3 stride 2 of img / 255 + bias) into out[..., out_coff:out_coff + c0],
+    out [n_alloc, H / 2, W / 2, cstride]; w27 [27, c0] with row (ky * 3 + kx) * 3 + colour. Returns (out, saturated)."""
+    ctx = ctx or _lib.default_context()
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    w27, bias = _f32(w27), _f32(bias)
+    na, h, w, four = img.shape
+    c0 = w27.shape[1]
+    out, fmt = _rt_map(out, split)
+    assert four == 4 and w27.shape == (27, c0) and bias.shape == (c0,) and out.shape[:3] == (na, h // 2, w // 2)
+    sat = C.c_int()
+    check(ctx.lib.gtx_op_rt_stem1(ctx.handle, fmt, na if n is None else n, na, h, w, c0, ptr(img), ptr(w27), ptr(bias), ptr(out), out.shape[3],
+                                  out_coff, C.byref(sat)))
+    return out, bool(sat.value)
+
+
+def rt_pool2(x: np.ndarray, c: int, out: np.ndarray, *, n: int | None = None, in_coff: int = 0, out_coff: int = 0, split: bool = False, ctx=None):
+    """max_pool2d(F.pad(x, [0, 1, 0, 1]), 2, 1) of x[..., in_coff:in_coff + c] into out[..., out_coff:out_coff + c]. Returns (out, saturated)."""
+    ctx = ctx or _lib.default_context()
+    x, fmt = _rt_map(x, split)
+    out, _ = _rt_map(out, split)
+    na, h, w, cs = x.shape
+    assert out.shape[:3] == (na, h, w) and out.dtype == x.dtype
+    sat = C.c_int()
+    check(ctx.lib.gtx_op_rt_pool2(ctx.handle, fmt, na if n is None else n, na, h, w, c, ptr(x), cs, in_coff, ptr(out), out.shape[3], out_coff,
+                                  C.byref(sat)))
+    return out, bool(sat.value)
+
+
+def rt_dwconv(x: np.ndarray, w: np.ndarray, bias, out: np.ndarray, *, stride: int = 1, act: int = 0, residual: np.ndarray | None = None,
+              n: int | None = None, in_coff: int = 0, out_coff: int = 0, res_coff: int = 0, split: bool = False, ctx=None):
+    """dwconv() on channel slices: x[..., in_coff:in_coff + c] -> out[..., out_coff:out_coff + c], the residual read from
+    residual[..., res_coff:res_coff + c]; w [c, 1, k, k], bias [c] or None. Returns (out, saturated)."""
+    ctx = ctx or _lib.default_context()
+    x, fmt = _rt_map(x, split)
+    out, _ = _rt_map(out, split)
+    na, h, wd, cs = x.shape
+    c, k = int(w.shape[0]), int(w.shape[-1])
+    wt = np.ascontiguousarray(np.asarray(w, np.float32).reshape(c, k * k).T)     # tap-major
+    b = _f32(bias)
+    r = None if residual is None else np.ascontiguousarray(residual, dtype=x.dtype)
+    assert out.shape[:3] == (na, (h - 1) // stride + 1, (wd - 1) // stride + 1) and out.dtype == x.dtype and (r is None or r.shape[:3] == out.shape[:3])
+    sat = C.c_int()
+    check(ctx.lib.gtx_op_rt_dwconv(ctx.handle, fmt, na if n is None else n, na, h, wd, c, k, stride, ptr(x), cs, in_coff, ptr(wt), ptr(b), int(act),
+                                   ptr(r), 0 if r is None else r.shape[3], res_coff, ptr(out), out.shape[3], out_coff, C.byref(sat)))
+    return out, bool(sat.value)
+
+
+def rt_upsample2x(x: np.ndarray, c: int, out: np.ndarray, *, n: int | None = None, in_coff: int = 0, out_coff: int = 0, split: bool = False,
+                  ctx=None) -> np.ndarray:
+    """Nearest 2x upsampling of x[..., in_coff:in_coff + c] into out[..., out_coff:out_coff + c] (RT-DETR's kernel: raw 8-channel groups)."""
+    ctx = ctx or _lib.default_context()
+    x, fmt = _rt_map(x, split)
+    out, _ = _rt_map(out, split)
+    na, h, w, cs = x.shape
+    assert out.shape[:3] == (na, 2 * h, 2 * w) and out.dtype == x.dtype
+    check(ctx.lib.gtx_op_rt_upsample2x(ctx.handle, fmt, na if n is None else n, na, h, w, c, ptr(x), cs, in_coff, ptr(out), out.shape[3], out_coff))
+    return out
+
+
+def rt_tokens_in(x: np.ndarray, c: int, pos, src: np.ndarray, q: np.ndarray | None = None, *, n: int | None = None, in_coff: int = 0,
+                 split: bool = False, ctx=None):
+    """Map -> token rows: src [n_alloc * h * w, c] = x[..., in_coff:in_coff + c] as float32 and, with pos [h * w, c] and q given,
+    q = src + pos. src and q are given as they are before the launch. Returns (src, q or None)."""
+    ctx = ctx or _lib.default_context()
+    x, fmt = _rt_map(x, split)
+    na, h, w, cs = x.shape
+    src = np.array(src, dtype=np.float32, order="C")
+    q = None if q is None else np.array(q, dtype=np.float32, order="C")
+    pos = _f32(pos)
+    assert src.shape == (na * h * w, c) and (q is None or q.shape == src.shape) and (pos is None or pos.shape == (h * w, c))
+    check(ctx.lib.gtx_op_rt_tokens_in(ctx.handle, fmt, na if n is None else n, na, h, w, c, ptr(x), cs, in_coff, ptr(pos), ptr(src), ptr(q)))
+    return src, q
+
+
+def rt_mask_invalid(m: np.ndarray, c: int, level: int, *, n: int | None = None, coff: int = 0, split: bool = False, ctx=None) -> np.ndarray:
+    """RTDETRDecoder._generate_anchors' valid_mask applied to m[..., coff:coff + c] of a level's map (a copy comes back)."""
+    ctx = ctx or _lib.default_context()
+    m, fmt = _rt_map(m, split)
+    na, h, w, cs = m.shape
+    check(ctx.lib.gtx_op_rt_mask_invalid(ctx.handle, fmt, na if n is None else n, na, h, w, c, ptr(m), cs, coff, int(level)))
+    return m
+
+
 # ---------------------------------------------------------------------------- the detector's post-pass kernels
 def head_levels(levels):
     """Detect levels for the post-pass hooks. levels: dicts with feat [n, h, w, cstride] (float16 / float32), cb, cc, stride and, as

@@ -80,7 +80,9 @@ extern "C" {
  *     gtx_op_georef_tracks, gtx_georef_tracks_ms and gtx_georef_tracks_cfg (the georeference stage's per-track columns as HIP
  *     kernels, opt-in per run) added: new entry points and a struct of their own only, so the number stays.
  *     gtx_op_stem and gtx_op_conv2d_fused (the stem launch, and the convolution launch with its second source, plain output,
- *     saturation flag and fused post / front stages, on host arrays) added: the same, the number stays. */
+ *     saturation flag and fused post / front stages, on host arrays) added: the same, the number stays.
+ *     gtx_op_rt_{stem1, pool2, dwconv, upsample2x, tokens_in, mask_invalid} (RT-DETR's map-side kernels one launcher at a time)
+ *     added: the same, the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -481,6 +483,37 @@ int gtx_op_rt_deform(gtx_ctx* ctx, int fmt, int n, int n_levels, const void* con
  * class c. nq <= 512, nc <= 128. */
 int gtx_op_rt_post(gtx_ctx* ctx, int n, int nq, int nc, const float* logits, int ldl, const float* refer, float conf, uint64_t class_mask0,
                    uint64_t class_mask1, int frame_w, int frame_h, int max_det, float* out_rows, int* out_n, float* raw);
+
+/* RT-DETR's map-side kernels (csrc/rtdetr_kernels.hpp), one launcher per call, for the operator-level tests
+ * (tests/test_rtdetr_map_ops_gpu.py). Maps are NHWC host arrays [n_alloc][h][w][cstride] of fp16 (GTX_F16) or plain fp32 (GTX_F32; GTX_F32S:
+ * converted to the pair format on the way) whose channels [coff, coff + c) the launch reads or writes; the first n of the n_alloc
+ * images run. An output map is given as it is before the launch and comes back whole: everything outside the launch's own slice
+ * and images as given. Refused with GTX_ERR_INVALID before the GPU is touched: NULL arrays, non-positive sizes, channel counts that
+ * are not multiples of 8 (16 for stem1), strides or offsets that are not multiples of 8 (the kernels move 16- and 32-byte groups), a
+ * slice that does not fit its stride. *saturated: the launch clamped a value to fp16's range (GTX_F32S).
+ *
+ * HGStem.stem1: out [n_alloc][H / 2][W / 2][out_cstride] = ReLU(conv 3x3 stride 2 pad 1 of img / 255 + bias); img [n_alloc][H][W][4]
+ * RGB0 bytes (the fourth is not read), w27 [27][c0] with row (ky * 3 + kx) * 3 + colour, bias [c0]. H and W even, c0 % 16 == 0. */
+int gtx_op_rt_stem1(gtx_ctx* ctx, int dtype, int n, int n_alloc, int H, int W, int c0, const void* img, const float* w27, const float* bias,
+                    void* out, int out_cstride, int out_coff, int* saturated);
+/* max_pool2d(F.pad(x, [0, 1, 0, 1]), 2, 1): out(y, x) = the maximum of the 2 x 2 window at (y, x), zeros past the right and bottom border. */
+int gtx_op_rt_pool2(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int c, const void* in, int in_cstride, int in_coff, void* out,
+                    int out_cstride, int out_coff, int* saturated);
+/* gtx_op_dwconv on channel slices: x at in_coff of in_cstride, res (or NULL) at res_coff of res_cstride, out at out_coff of out_cstride;
+ * bias may be NULL (zero). */
+int gtx_op_rt_dwconv(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int c, int k, int stride, const void* x, int in_cstride, int in_coff,
+                     const float* wt, const float* bias, int act, const void* res, int res_cstride, int res_coff, void* out, int out_cstride,
+                     int out_coff, int* saturated);
+/* Nearest 2x upsampling as RT-DETR's neck runs it (a raw copy of 8-channel groups): y [n_alloc][2 h][2 w][out_cstride]. */
+int gtx_op_rt_upsample2x(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int c, const void* x, int in_cstride, int in_coff, void* y,
+                         int out_cstride, int out_coff);
+/* Map -> token rows: src [n_alloc * h * w][c] plain fp32 = the map's values and q = src + pos[row % (h w)], pos [h * w][c]. pos and q
+ * are NULL together (src alone is written). The rows of the images past n come back as given. */
+int gtx_op_rt_tokens_in(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int c, const void* in, int in_cstride, int in_coff,
+                        const float* pos, float* src, float* q);
+/* RTDETRDecoder._generate_anchors' valid_mask on a level's map, in place: the slice of a cell whose anchor ((x + 0.5) / w, (y + 0.5) / h,
+ * 0.05 * 2^level) is not strictly inside (0.01, 0.99), compared in fp32, becomes zero bits. level 0..5. */
+int gtx_op_rt_mask_invalid(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int c, void* m, int cstride, int coff, int level);
 
 /* The detector's post-pass kernels (csrc/det_kernels.hpp, csrc/v10_select.hip), one launcher per call, for the operator-level tests
  * (tests/test_head_ops_gpu.py). Host arrays in, host arrays out; every size and every index is checked before the GPU is touched: what

@@ -84,6 +84,124 @@ def test_rtdetr_hooks_refuse_bad_sizes_before_any_launch():
     assert lib.gtx_detector_create(None, C.byref(cfg), C.byref(h)) == -3 and not h.value
 
 
+def test_rtdetr_map_hooks_refuse_bad_sizes_before_any_launch():
+    """Host only: the six map-side hooks answer NULL arrays, non-positive sizes, channel counts, strides and offsets that are not whole
+    8-channel groups (16 for stem1), a slice that does not fit its stride, an odd image and a level outside 0..5 with an error code,
+    with no context given."""
+    from geotrax_amd import _lib
+
+    lib = _lib.load()
+    f = np.zeros(8192, np.float32)
+    img = np.zeros(2 * 8 * 8 * 4, np.uint8)
+    p = _lib.ptr
+    sat = C.c_int()
+    opt = lambda a: None if a is None else p(a)
+    err = lib.gtx_last_error
+
+    def stem1(dtype=1, n=1, na=1, H=8, W=8, c0=16, im=img, w27=f, b=f, out=f, cs=16, co=0):
+        return lib.gtx_op_rt_stem1(None, dtype, n, na, H, W, c0, opt(im), opt(w27), opt(b), opt(out), cs, co, C.byref(sat))
+
+    assert stem1() == -1 and b"ctx is NULL" in err()                                                    # the sizes were fine
+    assert stem1(n=2, na=2, H=2, W=4, c0=48, cs=64, co=16) == -1 and b"ctx is NULL" in err()
+    for c0 in (0, 8, 24, -16):
+        assert stem1(c0=c0, cs=32) == -1 and b"multiple of 16" in err(), c0
+    assert stem1(c0=1040, cs=1040) == -1 and b"1024 channels" in err()
+    for H, W in ((7, 8), (8, 7), (0, 8), (8, -2)):
+        assert stem1(H=H, W=W) == -1 and b"even" in err(), (H, W)
+    assert stem1(n=0) == -1 and b"n_alloc" in err()
+    assert stem1(n=2) == -1 and b"n_alloc" in err()                                                     # more images than the arrays hold
+    assert stem1(cs=20) == -1 and b"multiples of 8" in err()
+    assert stem1(cs=32, co=4) == -1 and b"multiples of 8" in err()
+    assert stem1(cs=32, co=-8) == -1 and b"multiples of 8" in err()
+    assert stem1(cs=24, co=16) == -1 and b"does not fit" in err()
+    assert stem1(dtype=3) == -1 and b"dtype" in err()
+    for name in ("im", "w27", "b", "out"):
+        assert stem1(**{name: None}) == -1 and b"is NULL" in err(), name
+
+    def pool2(dtype=1, n=1, na=1, h=3, w=5, c=8, x=f, ics=8, ico=0, out=f, ocs=8, oco=0):
+        return lib.gtx_op_rt_pool2(None, dtype, n, na, h, w, c, opt(x), ics, ico, opt(out), ocs, oco, C.byref(sat))
+
+    assert pool2() == -1 and b"ctx is NULL" in err()
+    assert pool2(h=1, w=1, c=24, ics=40, ico=16, ocs=32, oco=8) == -1 and b"ctx is NULL" in err()
+    for c in (0, 4, 12, -8):
+        assert pool2(c=c, ics=16, ocs=16) == -1 and b"multiple of 8" in err(), c
+    for h, w in ((0, 5), (3, 0), (-1, 5)):
+        assert pool2(h=h, w=w) == -1 and b"h and w" in err()
+    assert pool2(ics=12) == -1 and b"multiples of 8" in err()
+    assert pool2(ocs=16, oco=4) == -1 and b"multiples of 8" in err()
+    assert pool2(ics=16, ico=16) == -1 and b"does not fit" in err()
+    assert pool2(ocs=16, oco=16) == -1 and b"does not fit" in err()
+    assert pool2(n=0) == -1 and b"n_alloc" in err()
+    assert pool2(dtype=-1) == -1 and b"dtype" in err()
+    assert pool2(x=None) == -1 and b"in is NULL" in err()
+    assert pool2(out=None) == -1 and b"out is NULL" in err()
+
+    def dw(dtype=2, n=1, na=1, h=3, w=5, c=8, k=5, stride=1, x=f, ics=8, ico=0, wt=f, b=f, act=0, res=None, rcs=0, rco=0, out=f, ocs=8, oco=0):
+        return lib.gtx_op_rt_dwconv(None, dtype, n, na, h, w, c, k, stride, opt(x), ics, ico, opt(wt), opt(b), act, opt(res), rcs, rco, opt(out), ocs, oco,
+                                    C.byref(sat))
+
+    assert dw() == -1 and b"ctx is NULL" in err()
+    assert dw(b=None) == -1 and b"ctx is NULL" in err()                                                 # a layer without bias is a case
+    assert dw(res=f, rcs=24, rco=16, ics=16, ico=8, ocs=16, oco=8, stride=2, k=7) == -1 and b"ctx is NULL" in err()
+    for k in (1, 4, 9):
+        assert dw(k=k) == -1 and b"3, 5 or 7" in err()
+    for stride in (0, 3):
+        assert dw(stride=stride) == -1 and b"stride" in err()
+    assert dw(act=3) == -1 and b"act" in err()
+    for c in (0, 20):
+        assert dw(c=c, ics=24, ocs=24) == -1 and b"multiple of 8" in err()
+    assert dw(h=0) == -1 and b"h and w" in err()
+    assert dw(ics=16, ico=12) == -1 and b"multiples of 8" in err()
+    assert dw(ocs=16, oco=16) == -1 and b"does not fit" in err()
+    assert dw(res=f, rcs=8, rco=8) == -1 and b"does not fit" in err()
+    assert dw(res=f, rcs=12, rco=0) == -1 and b"multiples of 8" in err()
+    assert dw(res=f, rcs=0, rco=0) == -1 and b"multiples of 8" in err()
+    assert dw(n=3, na=2) == -1 and b"n_alloc" in err()
+    for name in ("x", "wt", "out"):
+        assert dw(**{name: None}) == -1 and b"is NULL" in err(), name
+
+    def up(dtype=0, n=1, na=1, h=3, w=5, c=8, x=f, ics=8, ico=0, y=f, ocs=8, oco=0):
+        return lib.gtx_op_rt_upsample2x(None, dtype, n, na, h, w, c, opt(x), ics, ico, opt(y), ocs, oco)
+
+    assert up() == -1 and b"ctx is NULL" in err()
+    assert up(c=4) == -1 and b"multiple of 8" in err()
+    assert up(w=0) == -1 and b"h and w" in err()
+    assert up(ics=10) == -1 and b"multiples of 8" in err()
+    assert up(ocs=24, oco=20) == -1 and b"multiples of 8" in err()
+    assert up(ocs=24, oco=24) == -1 and b"does not fit" in err()
+    assert up(n=-1) == -1 and b"n_alloc" in err()
+    assert up(x=None) == -1 and b"x is NULL" in err()
+    assert up(y=None) == -1 and b"y is NULL" in err()
+
+    def tok(dtype=1, n=1, na=1, h=3, w=5, c=8, x=f, ics=8, ico=0, pos=f, src=f, q=f):
+        return lib.gtx_op_rt_tokens_in(None, dtype, n, na, h, w, c, opt(x), ics, ico, opt(pos), opt(src), opt(q))
+
+    assert tok() == -1 and b"ctx is NULL" in err()
+    assert tok(pos=None, q=None) == -1 and b"ctx is NULL" in err()                                      # src alone
+    assert tok(pos=None) == -1 and b"together" in err()
+    assert tok(q=None) == -1 and b"together" in err()
+    assert tok(c=12, ics=16) == -1 and b"multiple of 8" in err()
+    assert tok(h=0) == -1 and b"h and w" in err()
+    assert tok(ics=16, ico=4) == -1 and b"multiples of 8" in err()
+    assert tok(ics=16, ico=16) == -1 and b"does not fit" in err()
+    assert tok(x=None) == -1 and b"in is NULL" in err()
+    assert tok(src=None) == -1 and b"src is NULL" in err()
+
+    def mask(dtype=1, n=1, na=1, h=3, w=5, c=8, m=f, cs=8, co=0, level=0):
+        return lib.gtx_op_rt_mask_invalid(None, dtype, n, na, h, w, c, opt(m), cs, co, level)
+
+    assert mask() == -1 and b"ctx is NULL" in err()
+    assert mask(level=5) == -1 and b"ctx is NULL" in err()
+    for level in (-1, 6, 31):
+        assert mask(level=level) == -1 and b"level" in err()
+    assert mask(c=4) == -1 and b"multiple of 8" in err()
+    assert mask(w=-3) == -1 and b"h and w" in err()
+    assert mask(cs=12) == -1 and b"multiples of 8" in err()
+    assert mask(cs=16, co=16) == -1 and b"does not fit" in err()
+    assert mask(n=0) == -1 and b"n_alloc" in err()
+    assert mask(m=None) == -1 and b"m is NULL" in err()
+
+
 def test_front_hooks_refuse_null_arguments_and_bad_sizes_before_any_launch():
     """Host only: gtx_op_stem and gtx_op_conv2d_fused check their arrays and the sizes they allocate by before they touch a context."""
     from geotrax_amd import _lib
