@@ -387,10 +387,29 @@ int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
   return e && *e ? atoi(e) : dflt;
 }
+
+void conv_staged_launch(const ConvGroup& g, const ConvConfig& cfg, hipStream_t stream);   // below, behind its template dispatch
+
+// What the host side needs to know of a kernel form, in one place.
+struct ConvFormInfo {
+  void (*launch)(const ConvGroup&, const ConvConfig&, hipStream_t);
+  const char* kernel;   // symbol name as rocprof shows it; conv_kernel_name() appends a templated kernel's arguments
+  bool split;           // a split-f16x3 form: weights from pack_conv_weights_split; fused stages, out_plain and sat_flag are honoured
+};
+ConvFormInfo conv_form_info(ConvForm f) {
+  switch (f) {
+    case ConvForm::Staged: return {conv_staged_launch, "conv_igemm_kernel", false};
+    case ConvForm::Split:  return {conv_split_launch, "conv_igemm_split_kernel", true};
+    case ConvForm::K32:    return {conv_k32_launch, "conv_k32_split_kernel", true};
+    case ConvForm::K32S2:  return {conv_k32s2_launch, "conv_k32s2_split_kernel", true};
+  }
+  fail(-3, "conv: unknown kernel form %d", (int)f);
+}
 }  // namespace
 
-ConvConfig conv_pick_config(int dtype, int ks, int stride, int cin, int cout, int force_kc, int force_bn, long out_pixels) {
+ConvConfig conv_pick_config(int dtype, int ks, int stride, int cin, int cout, int force_kc, int force_bn) {
   ConvConfig c{};
+  c.variant = ConvForm::Staged;
   c.dtype = dtype;
   c.ks = ks;
   c.stride = stride;
@@ -398,7 +417,7 @@ ConvConfig conv_pick_config(int dtype, int ks, int stride, int cin, int cout, in
             "conv: unsupported kernel %dx%d stride %d", ks, ks, stride);
   if (dtype == DT_F32S) {
     // 3x3: 16-channel chunks (patch 11.5 KB + weight taps 36.9 KB per stage at 64 couts); 1x1: 32-channel chunks
-    c.variant = 2;
+    c.variant = ConvForm::Split;
     c.kc = ks == 1 ? (cin % 32 == 0 ? 32 : 16) : 16;
     if (force_kc > 0) c.kc = force_kc;
     c.bn = (cout % 64 == 0) ? 64 : 32;
@@ -406,42 +425,17 @@ ConvConfig conv_pick_config(int dtype, int ks, int stride, int cin, int cout, in
     c.th = 8; c.tw = 16;
     GTX_CHECK(cin % c.kc == 0, "conv: Cin=%d is not a multiple of the K chunk %d", cin, c.kc);
     GTX_CHECK(cout % 16 == 0, "conv: Cout=%d is not a multiple of 16", cout);   // a last cout tile may be half empty (yolov8 n / m / x widths)
-    // 3x3 stride 1 with whole 64-cout tiles: the Winograd F(2x2, 3x3) form (conv_wino_split.hip) is built, bit-exactness-tested
-    // and OFF: alone it is 1.05-1.35 x faster than the direct kernel on the deep K loops (Cin >= 256) and slower on the others,
-    // and next to the engine's second stream it loses even there (one 512-thread workgroup takes a CU's registers: 962 vs 970
-    // frames/s; profiles/r05_winograd_probe.txt). GTX_WINO=1: every eligible layer, GTX_WINO=2: Cin >= 256 only, GTX_WINO=3: the second
-    // form (16 x 16 pixels, one wave per SIMD: 1.04 x alone, its per-workgroup fixed cost is what is left).
-    if (ks == 3 && stride == 1 && c.bn == 64 && c.kc == 16 && cout % 64 == 0) {
-#ifdef GTX_WITH_WINO
-      const int mode = env_int("GTX_WINO", 0);
-#else
-      const int mode = 0;                     // the default libgtx.so carries only what runs: `make WINO=1` builds conv_wino_split.hip in
-#endif
-      if (mode == 1 || (mode == 2 && cin >= 256)) c.variant = 3;
-      if (mode == 3) { c.variant = 4; c.th = 16; }      // the 16 x 16-pixel form (one wave per SIMD)
-      // 4: the second form only where it used less CU-time than the direct kernel alone: launches that fill the chip for several
-      // rounds of its workgroups (>= 1024 of them: 240 x 240 maps at batch 2) with at least 8 chunks of K
-      if (mode == 4 && cin >= 128 && out_pixels * (cout / 64) >= 1024L * 256) { c.variant = 4; c.th = 16; }
-    }
     // 3x3 stride 1, 64-cout tiles, Cin a multiple of 32: the v_mfma_f32_16x16x32_f16 form (conv_k32_split.hip). GTX_K32=0: off
-    if (ks == 3 && stride == 1 && c.bn == 64 && c.variant == 2 && c.kc == 16 && cin % 32 == 0 && env_int("GTX_K32", 1) != 0) {
-      c.variant = 5;
+    if (ks == 3 && stride == 1 && c.bn == 64 && c.kc == 16 && cin % 32 == 0 && env_int("GTX_K32", 1) != 0) {
+      c.variant = ConvForm::K32;
       c.kc = 32;
     }
     // 3x3 stride 2, whole 64-cout tiles, Cin a multiple of 32: the same instruction shape (conv_k32s2_split.hip). A caller that pins
     // the K chunk keeps the 32x32x16 kernel (YOLOv8's model.1, which carries the fused front / post stages). GTX_K32S2=0: off
-    if (ks == 3 && stride == 2 && c.bn == 64 && c.variant == 2 && force_kc == 0 && cin % 32 == 0 && cout % 64 == 0 && env_int("GTX_K32S2", 1) != 0) {
-      c.variant = 7;
+    if (ks == 3 && stride == 2 && c.bn == 64 && force_kc == 0 && cin % 32 == 0 && cout % 64 == 0 && env_int("GTX_K32S2", 1) != 0) {
+      c.variant = ConvForm::K32S2;
       c.kc = 32;
     }
-    // 1x1 with whole 64-cout tiles and 32-channel chunks: the pointwise v_mfma_f32_16x16x32_f16 forms (conv_k32p_split.hip) are built
-    // by `make K32P=1`, bit-comparison-tested and OFF: 0.97 x / 0.81 x of the 32x32x16 kernel on RT-DETR's 1x1 layers
-    // (profiles/r06_k32p_probe.txt). GTX_K32P=1: pixels staged in LDS, 2: pixels straight into the operand registers. Same weight
-    // image as variant 2, so a caller that needs what only the 32x32x16 kernel has (a second upsampled source, a fused stage) sets
-    // the variant back to 2.
-#ifdef GTX_WITH_K32P
-    if (ks == 1 && c.variant == 2 && c.kc == 32 && c.bn == 64 && cout % 64 == 0 && env_int("GTX_K32P", 0) != 0) c.variant = 6;
-#endif
     return c;
   }
   const int epc = dtype == DT_F16 ? 8 : 4;
@@ -470,23 +464,11 @@ inline uint16_t f32_to_f16_bits(float f) {
 }
 }  // namespace
 
-#ifndef GTX_WITH_K32P
-// conv_k32p_split.hip is not part of this build (closed with numbers, profiles/r06_k32p_probe.txt); conv_pick_config never selects variant 6 here
-void conv_k32p_launch(const ConvGroup&, const ConvConfig&, hipStream_t) { fail(-3, "the pointwise 16x16x32 kernels are not in this build (make -C geo-trax_amd K32P=1)"); }
-#endif
-
-#ifndef GTX_WITH_WINO
-// conv_wino_split.hip is not part of this build (closed with numbers: 1.00-1.04 x of the direct kernel alone, -0.8 % end to end,
-// profiles/r05_winograd_probe.txt); conv_pick_config never selects variants 3 / 4 here
-void conv_wino_launch(const ConvGroup&, const ConvConfig&, hipStream_t) { fail(-3, "the Winograd kernels are not in this build (make -C geo-trax_amd WINO=1)"); }
-std::vector<uint8_t> pack_conv_weights_wino(const float*, int, int, const ConvConfig&, float*) { fail(-3, "the Winograd kernels are not in this build (make -C geo-trax_amd WINO=1)"); }
-#endif
-
 std::vector<uint8_t> pack_conv_weights(const float* w, int cout, int cin, const ConvConfig& cfg, float* acc_scale) {
   if (acc_scale) *acc_scale = 1.f;
-  if (cfg.variant >= 2 && cfg.variant <= 7) {
+  if (conv_form_info(cfg.variant).split) {
     float sc = 1.f;
-    std::vector<uint8_t> r = (cfg.variant == 3 || cfg.variant == 4) ? pack_conv_weights_wino(w, cout, cin, cfg, &sc) : pack_conv_weights_split(w, cout, cin, cfg, &sc);
+    std::vector<uint8_t> r = pack_conv_weights_split(w, cout, cin, cfg, &sc);
     if (acc_scale) *acc_scale = sc;
     return r;
   }
@@ -595,15 +577,21 @@ void launch_dt(const ConvGroup& g, const ConvConfig& c, hipStream_t s) {
 #undef GTX_CASE
   fail(-3, "conv: no kernel for ks=%d stride=%d bn=%d kc=%d", c.ks, c.stride, c.bn, c.kc);
 }
+
+void conv_staged_launch(const ConvGroup& g, const ConvConfig& cfg, hipStream_t stream) {
+  if (cfg.dtype == DT_F16) launch_dt<_Float16>(g, cfg, stream);
+  else launch_dt<float>(g, cfg, stream);
+}
 }  // namespace
 
 void conv_launch(const ConvGroup& g, const ConvConfig& cfg, hipStream_t stream) {
   GTX_CHECK(g.count >= 1 && g.count <= kMaxGroup, "conv: bad group size %d", g.count);
   if (g.total_blocks == 0) return;
+  const ConvFormInfo form = conv_form_info(cfg.variant);
   for (int i = 0; i < g.count; ++i) {
     const ConvProblem& p = g.p[i];
     if (p.c_split == 0) continue;
-    GTX_CHECK(cfg.variant == 2 && cfg.ks == 1, "conv: a second (upsampled) source needs the split-f16x3 1x1 kernel");
+    GTX_CHECK(cfg.variant == ConvForm::Split && cfg.ks == 1, "conv: a second (upsampled) source needs the split-f16x3 1x1 kernel");
     // a pair-format slice starts and ends on whole 8-channel groups (split_format.hpp)
     GTX_CHECK(p.in2 && p.c_split > 0 && p.c_split % cfg.kc == 0 && p.c_split < p.Cin && p.H % 2 == 0 && p.W % 2 == 0 && p.in2_cstride % 8 == 0 &&
                   p.in2_coff >= 0 && p.in2_coff % 8 == 0 && p.in2_coff + p.c_split <= p.in2_cstride,
@@ -612,30 +600,21 @@ void conv_launch(const ConvGroup& g, const ConvConfig& cfg, hipStream_t stream) 
   // the fused stages, the plain output and the saturation flag belong to the split-f16x3 kernels: the fp16 / exact-fp32 kernels
   // would ignore them in silence
   for (int i = 0; i < g.count; ++i)
-    GTX_CHECK(cfg.variant != 0 || (g.p[i].post_w == nullptr && g.p[i].front_img == nullptr && g.p[i].out_plain == 0 && g.p[i].sat_flag == nullptr),
+    GTX_CHECK(form.split || (g.p[i].post_w == nullptr && g.p[i].front_img == nullptr && g.p[i].out_plain == 0 && g.p[i].sat_flag == nullptr),
               "conv: a fused post / front stage, out_plain and sat_flag need the split-f16x3 path");
-  if (cfg.variant == 3 || cfg.variant == 4) return conv_wino_launch(g, cfg, stream);
-  if (cfg.variant == 5) return conv_k32_launch(g, cfg, stream);
-  if (cfg.variant == 6) return conv_k32p_launch(g, cfg, stream);
-  if (cfg.variant == 7) return conv_k32s2_launch(g, cfg, stream);
-  if (cfg.variant == 2) return conv_split_launch(g, cfg, stream);
-  if (cfg.dtype == DT_F16) launch_dt<_Float16>(g, cfg, stream);
-  else launch_dt<float>(g, cfg, stream);
+  form.launch(g, cfg, stream);
 }
 
 const char* conv_kernel_name(const ConvConfig& c) {
   static thread_local char buf[96];
-  if (c.variant == 3) return "conv_wino_split_kernel";
-  if (c.variant == 4) return "conv_wino2_split_kernel";
-  if (c.variant == 5) return "conv_k32_split_kernel";
-  if (c.variant == 6) return "conv_k32p_split_kernel";
-  if (c.variant == 7) return "conv_k32s2_split_kernel";
-  if (c.variant == 2) {
-    snprintf(buf, sizeof buf, "conv_igemm_split_kernel<%d, %d, %d, %d, %d>", c.ks, c.stride, c.bn / 32, c.kc / 8, c.th / 8);
-    return buf;
-  }
-  snprintf(buf, sizeof buf, "conv_igemm_kernel<%s, %d, %d, %d, %d>", c.dtype == DT_F16 ? "_Float16" : "float",
-           c.ks, c.stride, c.bn / 32, c.kc * (int)dtype_size(c.dtype) / 16);
+  const char* kernel = conv_form_info(c.variant).kernel;
+  if (c.variant == ConvForm::Split)
+    snprintf(buf, sizeof buf, "%s<%d, %d, %d, %d, %d>", kernel, c.ks, c.stride, c.bn / 32, c.kc / 8, c.th / 8);
+  else if (c.variant == ConvForm::Staged)
+    snprintf(buf, sizeof buf, "%s<%s, %d, %d, %d, %d>", kernel, c.dtype == DT_F16 ? "_Float16" : "float",
+             c.ks, c.stride, c.bn / 32, c.kc * (int)dtype_size(c.dtype) / 16);
+  else
+    return kernel;
   return buf;
 }
 

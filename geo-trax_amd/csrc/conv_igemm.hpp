@@ -87,6 +87,15 @@ struct ConvGroup {
   int grid_blocks;
 };
 
+// The kernel a convolution runs on. The split-f16x3 forms (DT_F32S: all but Staged) share their device code -- arithmetic, block
+// decode, epilogue, launcher -- in conv_split_device.hpp and their weight image (pack_conv_weights_split).
+enum class ConvForm : int {
+  Staged,  // conv_igemm.hip: the register-staged kernel (fp16, exact fp32)
+  Split,   // conv_igemm_split.hip: split-f16x3 on v_mfma_f32_32x32x16_f16 (1x1, 3x3 stride 1 / 2, the fused stages)
+  K32,     // conv_k32_split.hip: split-f16x3 3x3 stride 1 on v_mfma_f32_16x16x32_f16
+  K32S2,   // conv_k32s2_split.hip: split-f16x3 3x3 stride 2 on v_mfma_f32_16x16x32_f16
+};
+
 // Kernel family selector; every member of a grouped launch shares one config.
 struct ConvConfig {
   int dtype;   // DType
@@ -94,14 +103,13 @@ struct ConvConfig {
   int stride;  // 1 or 2
   int bn;      // cout tile: 32, 64 or 128
   int kc;      // cin elements staged per K chunk
-  int variant; // 0 = register-staged kernel (conv_igemm.hip: fp16, exact fp32), 2 = split-f16x3 (conv_igemm_split.hip, DT_F32S), 3 / 4 = its Winograd forms (conv_wino_split.hip), 5 = its 16x16x32 form for 3x3 stride 1 (conv_k32_split.hip), 6 = its 16x16x32 form for plain 1x1 layers (conv_k32p_split.hip), 7 = its 16x16x32 form for 3x3 stride 2 (conv_k32s2_split.hip); variants 2-7 share their device code (arithmetic, block decode, epilogue, launcher) in conv_split_device.hpp
+  ConvForm variant;  // the kernel form
   int th, tw;  // output pixel tile (rows x cols)
 };
 
 // Picks the tile configuration used for a layer shape.
 // force_kc / force_bn > 0 pin the K chunk / cout tile (grouped launches: every member must use the same kernel instantiation).
-// out_pixels (N x Ho x Wo at the layer's largest batch, 0 = unknown): only read by the GTX_WINO=4 experiment.
-ConvConfig conv_pick_config(int dtype, int ks, int stride, int cin, int cout, int force_kc = 0, int force_bn = 0, long out_pixels = 0);
+ConvConfig conv_pick_config(int dtype, int ks, int stride, int cin, int cout, int force_kc = 0, int force_bn = 0);
 
 // Host-side weight packing: w is [Cout][KS][KS][Cin] fp32 (OHWI). Returns the packed
 // byte image for `cfg` (element type per cfg.dtype). acc_scale (may be null) receives ConvProblem::acc_scale.
@@ -121,18 +129,11 @@ void conv_split_launch(const ConvGroup& g, const ConvConfig& cfg, hipStream_t st
 std::vector<uint8_t> pack_conv_weights_split(const float* w_ohwi, int cout, int cin, const ConvConfig& cfg, float* acc_scale);
 std::vector<uint16_t> pack_front_weights_split(const float* w27, int c0, float* acc_scale);
 
-// conv_wino_split.hip: the Winograd F(2x2, 3x3) form of the split-f16x3 3x3 stride-1 convolution (ConvConfig::variant 3)
-void conv_wino_launch(const ConvGroup& g, const ConvConfig& cfg, hipStream_t stream);
-std::vector<uint8_t> pack_conv_weights_wino(const float* w_ohwi, int cout, int cin, const ConvConfig& cfg, float* acc_scale);
-
-// conv_k32_split.hip: the 3x3 stride-1 split-f16x3 convolution on v_mfma_f32_16x16x32_f16 (ConvConfig::variant 5; weights: pack_conv_weights_split, kc = 32)
+// conv_k32_split.hip: the 3x3 stride-1 split-f16x3 convolution on v_mfma_f32_16x16x32_f16 (ConvForm::K32; weights: pack_conv_weights_split, kc = 32)
 void conv_k32_launch(const ConvGroup& g, const ConvConfig& cfg, hipStream_t stream);
 
-// conv_k32s2_split.hip: the 3x3 stride-2 split-f16x3 convolution on v_mfma_f32_16x16x32_f16 (ConvConfig::variant 7; weights: pack_conv_weights_split, kc = 32)
+// conv_k32s2_split.hip: the 3x3 stride-2 split-f16x3 convolution on v_mfma_f32_16x16x32_f16 (ConvForm::K32S2; weights: pack_conv_weights_split, kc = 32)
 void conv_k32s2_launch(const ConvGroup& g, const ConvConfig& cfg, hipStream_t stream);
-
-// conv_k32p_split.hip: the 1x1 split-f16x3 convolution on v_mfma_f32_16x16x32_f16 (ConvConfig::variant 6; the weight image of variant 2 with kc = 32)
-void conv_k32p_launch(const ConvGroup& g, const ConvConfig& cfg, hipStream_t stream);
 
 // Kernel symbol name as rocprof shows it (for the roofline bookkeeping).
 const char* conv_kernel_name(const ConvConfig& cfg);

@@ -25,7 +25,7 @@
 // 4-wave workgroup, per K chunk the input patch and the KS*KS weight taps staged once, taps read shifted
 // fragments); an LDS row holds the CPR hi chunks of its 8*CPR channels followed by the CPR lo chunks.
 // The arithmetic helpers, the block decode, the epilogue pieces and the launcher are conv_split_device.hpp's, shared with the
-// other split-f16x3 kernels (conv_k32_split.hip, conv_k32p_split.hip, conv_wino_split.hip, head_sparse.hip).
+// other split-f16x3 kernels (conv_k32_split.hip, conv_k32s2_split.hip, head_sparse.hip).
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 

@@ -1,4 +1,4 @@
-// 3x3 stride-1 split-f16x3 convolution on v_mfma_f32_16x16x32_f16 ("K32 form", ConvConfig::variant 5). gfx950 only.
+// 3x3 stride-1 split-f16x3 convolution on v_mfma_f32_16x16x32_f16 ("K32 form", ConvForm::K32). gfx950 only.
 //
 // Same arithmetic contract as conv_igemm_split.hip, kept in conv_split_device.hpp (pair-format activations, every product as three fp16 MFMAs -- small terms
 // first -- with fp32 accumulation, weights scaled by an exact power of two, same packed weight image with 32-channel chunks),
@@ -21,19 +21,7 @@ namespace gtx {
 
 namespace {
 
-// Timing-only builds (`make k32probe`, wrong results): GTXK_PROBE bit 0 = no barriers inside a chunk (rows 1, 2), bit 1 = no weight
-// commits (LDS stores) for rows 1, 2, bit 2 = no MFMAs, bit 3 = no weight loads from global for rows 1, 2, bit 5 = no weight fragment reads from LDS (the first tap's stay in registers),
-// bit 6 = no pixel fragment reads from LDS after a chunk's first tap, bit 7 = the first chunk's global loads skipped (what a workgroup
-// that had requested them under the previous tile's epilogue would see), bit 8 = no epilogue (one store per lane)
-#ifndef GTXK_PROBE
-#define GTXK_PROBE 0
-#endif
-#if GTXK_PROBE & 4
-#define GTXK_MFMA(a, b, c) (c + floatx4{(float)(a)[0], (float)(b)[0], 0.f, 0.f})
-#else
 #define GTXK_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
-#endif
-#define GTXK_SYNC_IN() { if (!(GTXK_PROBE & 1)) __syncthreads(); }
 
 struct K32Tile {
   static constexpr int TH = 8, TW = 16, BN = 64, KC = 32, CPR = 4, NCH = 8, RB = 128;
@@ -126,14 +114,8 @@ void conv_k32_split_kernel(const ConvGroup g) {
     d__[0] = pw0; d__[256] = pw1; d__[512] = pw2; d__[768] = pw3; d__[1024] = pw4; d__[1280] = pw5; \
   }
 
-  if (GTXK_PROBE & 128) {                          // timing-only: the first chunk's loads cost nothing
-#pragma unroll
-    for (int s = 0; s < Tile::PATCH_SLOTS; ++s) pre_a[s] = pre_b[s] = make_uint4(tid, s, 0, 0);
-    pw0 = pw1 = pw2 = pw3 = pw4 = pw5 = make_uint4(tid, 1, 2, 3);
-  } else {
-    GTXK_PREFETCH_PATCH(0)
-    GTXK_PREFETCH_W(0)
-  }
+  GTXK_PREFETCH_PATCH(0)
+  GTXK_PREFETCH_W(0)
 
   // accumulators start at bias / acc_scale: lane (col, kg) of block a holds couts 16 a + 4 kg + 0..3. (The loop is the kernel's own:
   // as a shared function that fills the array it costs conv_k32_split_kernel nine more spilled registers.)
@@ -174,9 +156,8 @@ void conv_k32_split_kernel(const ConvGroup g) {
       constexpr int kx__ = (U) / 4, a__ = (U) % 4;                                             \
       constexpr int bs__ = ((KY) * 3 + kx__) & 1;                                              \
       __builtin_amdgcn_sched_barrier(0);                                                       \
-      if ((U) + 1 < 12 && !(GTXK_PROBE & 32)) GTXK_LOAD_A(((U) + 1) / 4, ((U) + 1) % 4, ((U) + 1) & 1) \
-      if (GTXK_PROBE & 64) {}                                                                  \
-      else if (kx__ < 2) GTXK_LOAD_B(KY, kx__ + 1, bs__ ^ 1, a__)                              \
+      if ((U) + 1 < 12) GTXK_LOAD_A(((U) + 1) / 4, ((U) + 1) % 4, ((U) + 1) & 1)               \
+      if (kx__ < 2) GTXK_LOAD_B(KY, kx__ + 1, bs__ ^ 1, a__)                                   \
       else if (!(LAST_ROW)) GTXK_LOAD_B((KY) + 1, 0, bs__ ^ 1, a__)                            \
       acc[a__][0] = GTXK_MFMA(al[(U) & 1], bh[bs__][0], acc[a__][0]);                          \
       acc[a__][1] = GTXK_MFMA(al[(U) & 1], bh[bs__][1], acc[a__][1]);                          \
@@ -192,7 +173,7 @@ void conv_k32_split_kernel(const ConvGroup g) {
       __builtin_amdgcn_sched_barrier(0);                                                       \
     }
 #define GTXK_ROW(KY, LAST_ROW)                                                                 \
-    GTXK_LOAD_A(0, 0, 0) if (GTXK_PROBE & 32) GTXK_LOAD_A(0, 1, 1) if (GTXK_PROBE & 64) { bh[1][0] = bh[0][0]; bh[1][1] = bh[0][1]; bl[1][0] = bl[0][0]; bl[1][1] = bl[0][1]; }                                                                      \
+    GTXK_LOAD_A(0, 0, 0)                                                                       \
     GTXK_UNIT(KY, 0, LAST_ROW) GTXK_UNIT(KY, 1, LAST_ROW) GTXK_UNIT(KY, 2, LAST_ROW) GTXK_UNIT(KY, 3, LAST_ROW)   \
     GTXK_UNIT(KY, 4, LAST_ROW) GTXK_UNIT(KY, 5, LAST_ROW) GTXK_UNIT(KY, 6, LAST_ROW) GTXK_UNIT(KY, 7, LAST_ROW)   \
     GTXK_UNIT(KY, 8, LAST_ROW) GTXK_UNIT(KY, 9, LAST_ROW) GTXK_UNIT(KY, 10, LAST_ROW) GTXK_UNIT(KY, 11, LAST_ROW)
@@ -203,19 +184,19 @@ void conv_k32_split_kernel(const ConvGroup g) {
     GTXK_COMMIT_PATCH()
     GTXK_COMMIT_W()
     __syncthreads();
-    if (!(GTXK_PROBE & 8)) GTXK_PREFETCH_W(3 * chunk + 1)
+    GTXK_PREFETCH_W(3 * chunk + 1)
     GTXK_LOAD_B(0, 0, 0, 0) GTXK_LOAD_B(0, 0, 0, 1) GTXK_LOAD_B(0, 0, 0, 2) GTXK_LOAD_B(0, 0, 0, 3)
     GTXK_ROW(0, false)
     // ---- kernel row 1 ----
-    GTXK_SYNC_IN()
-    if (!(GTXK_PROBE & 2)) GTXK_COMMIT_W()
-    GTXK_SYNC_IN()
-    if (!(GTXK_PROBE & 8)) GTXK_PREFETCH_W(3 * chunk + 2)
+    __syncthreads();
+    GTXK_COMMIT_W()
+    __syncthreads();
+    GTXK_PREFETCH_W(3 * chunk + 2)
     GTXK_ROW(1, false)
     // ---- kernel row 2: the next chunk's patch and first row are requested here ----
-    GTXK_SYNC_IN()
-    if (!(GTXK_PROBE & 2)) GTXK_COMMIT_W()
-    GTXK_SYNC_IN()
+    __syncthreads();
+    GTXK_COMMIT_W()
+    __syncthreads();
     if (chunk + 1 < nchunks) {
       GTXK_PREFETCH_PATCH(chunk + 1)
       GTXK_PREFETCH_W(3 * chunk + 3)
@@ -228,14 +209,6 @@ void conv_k32_split_kernel(const ConvGroup g) {
 #undef GTXK_LOAD_B
 
   // ---- epilogue: acc * 2^-shift -> activation (+ residual) -> split -> NHWC pair format (conv_split_device.hpp) ----
-  if (GTXK_PROBE & 256) {
-    floatx4 t = acc[0][0];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) { t += acc[a][0]; t += acc[a][1]; }
-    const int oy = oy0 + 2 * wave, ox = ox0 + col;
-    if (oy < P.Ho && ox < P.Wo) *reinterpret_cast<floatx4*>(static_cast<float*>(P.out) + (((size_t)n * P.Ho + oy) * P.Wo + ox) * P.out_cstride + P.out_coff + ct * BN + 4 * kg) = t;
-    return;
-  }
   epilogue_k32(acc, P, smem, ct, n, oy0, ox0, wave, lane);
 }
 

@@ -1,4 +1,4 @@
-// 3x3 stride-2 split-f16x3 convolution on v_mfma_f32_16x16x32_f16 ("K32 stride-2 form", ConvConfig::variant 7). gfx950 only.
+// 3x3 stride-2 split-f16x3 convolution on v_mfma_f32_16x16x32_f16 ("K32 stride-2 form", ConvForm::K32S2). gfx950 only.
 //
 // conv_k32_split.hip's arithmetic contract and workgroup (conv_split_device.hpp: pair-format activations, three fp16 MFMAs per
 // product -- small terms first --, fp32 accumulation, the packed weight image with 32-channel chunks, epilogue_k32,

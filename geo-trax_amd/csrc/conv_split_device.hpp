@@ -1,5 +1,5 @@
-// Device code and launcher shared by the split-f16x3 kernels (conv_igemm_split.hip, conv_k32_split.hip, conv_k32p_split.hip,
-// conv_wino_split.hip, head_sparse.hip): the ONE home of their arithmetic contract. gfx950 only.
+// Device code and launcher shared by the split-f16x3 kernels (conv_igemm_split.hip, conv_k32_split.hip, conv_k32s2_split.hip,
+// head_sparse.hip): the ONE home of their arithmetic contract. gfx950 only.
 // The parity tests (the sparse box branch against the dense one, the fused front against the two launches, every form against
 // the 32x32x16 kernel) hold because every kernel runs the operations below, in this order: change them here or nowhere.
 #pragma once
@@ -172,7 +172,7 @@ __device__ __forceinline__ void store_runs(const char* stg, const ConvProblem& P
 __device__ __forceinline__ void flag_saturation(int* flag, const bool sat, const int lane) {
   if (flag && __builtin_amdgcn_ballot_w64(sat) != 0 && lane == 0) atomicOr(flag, 1);
 }
-// The complete epilogue of the 16x16x32 tile (conv_k32_split.hip, conv_k32p_split.hip): 8 x 16 pixels x 64 couts, wave w owns
+// The complete epilogue of the 16x16x32 tile (conv_k32_split.hip, conv_k32s2_split.hip): 8 x 16 pixels x 64 couts, wave w owns
 // tile rows 2 w, 2 w + 1; lane (col, kg) of acc[a][m] holds couts 16 a + 4 kg + 0..3 of pixel (row 2 w + m, col) -- byte
 // 64 a + 16 kg of the pixel's 256-byte run. Staged per wave in LDS (smem: the workgroup's, free after the barrier), stored as runs.
 __device__ __forceinline__ void epilogue_k32(const floatx4 (&acc)[4][2], const ConvProblem& P, char* smem, const int ct, const int n,

@@ -147,8 +147,7 @@ void Detector::build_graph() {
     h2v.plain = fmt_ == DT_F32S;
     force_kc_ = force_bn_ = 0;
     // move the three freshly built single-problem ops into the grouped stage ops: one grouped launch per stage and kernel
-    // configuration (the levels of a stage share a launch when they share the kernel; the fp32 default path runs its deep
-    // levels -- Cin >= 256 -- on the Winograd kernel and the 240 x 240 level on the direct one: two launches for a stage)
+    // configuration (the levels of a stage share a launch when they share the kernel)
     GTX_CHECK(ops_.size() == mark + 3, "internal: head op count");
     o1 = ops_[mark]; o2 = ops_[mark + 1]; o3 = ops_[mark + 2];
     ops_.resize(mark);
@@ -162,7 +161,7 @@ void Detector::build_graph() {
       sparse_ = SparseBox{};
       dense_box_ops_.clear();
     }
-    sparse_on_ = sparse_on_ && cb == 64 && o1.cfg.variant == 5 && o1.cfg.bn == 64 && o2.cfg.variant == 5 && cin % 32 == 0;
+    sparse_on_ = sparse_on_ && cb == 64 && o1.cfg.variant == ConvForm::K32 && o1.cfg.bn == 64 && o2.cfg.variant == ConvForm::K32 && cin % 32 == 0;
     head_ops_[l][0] = o1; head_ops_[l][1] = o2; head_ops_[l][2] = o3;
 
     HeadLevel& L = head_.lv[l];

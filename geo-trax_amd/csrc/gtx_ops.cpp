@@ -282,7 +282,6 @@ int gtx_op_conv2d_fused(gtx_ctx* ctx, const gtx_conv_desc* d, const gtx_conv_fus
       q.act = p.post_act; q.acc_scale = p.post_scale; q.post_scale = 1.f; q.out_plain = p.out_plain; q.sat_flag = p.sat_flag;
       p.out = mid.p; p.out_cstride = d->cout; p.out_coff = 0; p.out_plain = 0;
       p.post_w = nullptr; p.post_bias = nullptr; p.post_scale = 1.f; p.post_act = 0;
-      c2.variant = 2;                                   // the 32x32x16 kernel, as fuse_front() requires of the layer it folds in
       g2.count = 1;
       gtx::conv_group_finalize(g2, c2);
     }

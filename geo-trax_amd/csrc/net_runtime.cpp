@@ -172,8 +172,7 @@ View NetRuntime::conv_problem(const std::string& name, const float* w, int cout,
     GTX_CHECK(x.cstride % 8 == 0 && x.coff % 8 == 0 && out.cstride % 8 == 0 && out.coff % 8 == 0 &&
                   (!a.residual || (a.residual->cstride % 8 == 0 && a.residual->coff % 8 == 0)),
               "%s: channel strides / offsets of the split-f16x3 path must be multiples of 8", name.c_str());
-  cfg = conv_pick_config(fmt_, ks, a.stride, cin, cout, a.force_kc, a.force_bn, a.out_pixels);
-  conv_config_rule(name, cfg);
+  cfg = conv_pick_config(fmt_, ks, a.stride, cin, cout, a.force_kc, a.force_bn);
   const size_t n = (size_t)cout * cin * ks * ks;
   const auto pw = packed_weights(w, n, cout, cin, cfg, [&] {
     PackedWeights r;

@@ -106,14 +106,13 @@ class NetRuntime {
 
   // ---- one Conv op: OIHW weights (cout x cin x ks x ks), bias (may be null: zeros). Picks the tile configuration, packs the
   // weights (shared packed-image cache), uploads weights and bias and fills the op's ConvProblem; the output is *out_slice or a
-  // new view. plain_out: the split path writes plain fp32. out_pixels: conv_pick_config's. The op is appended to `ops`.
+  // new view. plain_out: the split path writes plain fp32. The op is appended to `ops`.
   struct ConvArgs {
     int stride = 1, act = 1;
     const View* out_slice = nullptr;
     const View* residual = nullptr;
     bool plain_out = false;
     int force_kc = 0, force_bn = 0;
-    long out_pixels = 0;
   };
   template <class OpT>
   View emit_conv(std::vector<OpT>& ops, const std::string& name, const float* w_oihw, int cout, int cin, int ks, const float* bias,
@@ -128,17 +127,14 @@ class NetRuntime {
     layer_views_[name] = out;
     return out;
   }
-  // The same from the tensors "<name>.weight" (OIHW, square kernel) and "<name>.bias" (optional); fills a.out_pixels.
+  // The same from the tensors "<name>.weight" (OIHW, square kernel) and "<name>.bias" (optional).
   template <class OpT>
-  View emit_named_conv(std::vector<OpT>& ops, const std::string& name, const View& x, ConvArgs a) {
+  View emit_named_conv(std::vector<OpT>& ops, const std::string& name, const View& x, const ConvArgs& a) {
     const HostTensor& w = tensor(name + ".weight");
     GTX_CHECK(w.shape.size() == 4 && w.shape[2] == w.shape[3], "%s: expected OIHW square kernel", name.c_str());
     const int cout = (int)w.shape[0], cin = (int)w.shape[1], ks = (int)w.shape[2];
-    a.out_pixels = (long)x.n * ((x.h + 2 * (ks / 2) - ks) / a.stride + 1) * ((x.w + 2 * (ks / 2) - ks) / a.stride + 1);
     return emit_conv(ops, name, w.data.data(), cout, cin, ks, bias_of(name, cout), x, a);
   }
-  // a family's rule on the configuration conv_pick_config chose, applied before the weights are packed
-  virtual void conv_config_rule(const std::string& name, ConvConfig& cfg) const { (void)name; (void)cfg; }
 
   // ---- the layers layer_output() can read, by module path
   void set_layer_view(const std::string& name, const View& v) { layer_views_[name] = v; }

@@ -111,12 +111,6 @@ std::unique_ptr<NetRuntime> Embedder::make_exact() const {
   return std::unique_ptr<NetRuntime>(new Embedder(ctx_, S_, max_batch_, false));
 }
 
-// GTX_WINO: the direct split kernel here (same kc / bn)
-void Embedder::conv_config_rule(const std::string& name, ConvConfig& cfg) const {
-  (void)name;
-  if (cfg.variant == 3 || cfg.variant == 4) { cfg.variant = 2; cfg.th = 8; }
-}
-
 // model.0-8 (yolov8-cls) or model.0-9 (yolo11-cls) through the trunk's walk (no fusion: fuse() is never called, so the stem gets no
 // front-packed weights)
 void Embedder::build_graph() {

@@ -41,7 +41,6 @@ class Embedder : public NetRuntime {
   void launch_op(size_t i, int nb, hipStream_t s) override { trunk_.run_op(ops_[i], nb, s); }
   std::unique_ptr<NetRuntime> make_exact() const override;
   void release_graph() override { ops_.clear(); }
-  void conv_config_rule(const std::string& name, ConvConfig& cfg) const override;
   void build_graph();
   void set_batch(int nb) override;
   void enqueue(int n_total);

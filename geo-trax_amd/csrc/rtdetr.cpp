@@ -32,11 +32,6 @@ std::unique_ptr<NetRuntime> RtDetr::make_exact() const {
   return std::unique_ptr<NetRuntime>(new RtDetr(ctx_, c));
 }
 
-void RtDetr::conv_config_rule(const std::string& name, ConvConfig& cfg) const {
-  (void)name;
-  GTX_CHECK(cfg.variant != 3 && cfg.variant != 4, "RT-DETR does not run on the Winograd kernels (unset GTX_WINO)");
-}
-
 // Token rows are fp32 on every path, whatever a map element takes (2 bytes under half for the YOLOv8 trunk's maps).
 float* RtDetr::new_tokens(int rows_per_image, int ld, const std::string& name) {
   View v{alloc((size_t)max_batch_ * rows_per_image * ld * sizeof(float)), max_batch_, 1, rows_per_image, ld, 0, ld, true};

@@ -56,7 +56,6 @@ class RtDetr : public DetectorBase {
   }
   std::unique_ptr<NetRuntime> make_exact() const override;
   void release_graph() override { ops_.clear(); trunk_ops_.clear(); trunk_.clear(); }
-  void conv_config_rule(const std::string& name, ConvConfig& cfg) const override;
   float* new_tokens(int rows_per_image, int ld, const std::string& name);
   // graph building
   View conv_raw(const std::string& name, const std::vector<float>& w_oihw, int cout, int cin, int ks, const float* bias_host, const View& x, int stride,

@@ -53,8 +53,7 @@ View YoloTrunk::conv(const std::string& name, const View& x, int stride, const V
   const View out = net_.emit_named_conv(ops_, name, x, a);
   if (up_src) {
     Op& op = ops_.back();
-    if (op.cfg.variant == 6) op.cfg.variant = 2;     // the second source is read by the 32x32x16 kernel only (same weight image)
-    GTX_CHECK(op.cfg.ks == 1 && stride == 1 && op.cfg.variant == 2 && up_src->h * 2 == x.h && up_src->w * 2 == x.w && up_src->c < x.c,
+    GTX_CHECK(op.cfg.ks == 1 && stride == 1 && op.cfg.variant == ConvForm::Split && up_src->h * 2 == x.h && up_src->w * 2 == x.w && up_src->c < x.c,
               "%s: upsampled source does not fit", name.c_str());
     ConvProblem& p = op.grp.p[0];
     p.in2 = up_src->ptr; p.in2_cstride = up_src->cstride; p.in2_coff = up_src->coff; p.c_split = up_src->c;
@@ -114,7 +113,6 @@ View YoloTrunk::conv_act(const std::string& name, const View& x, int act, const 
       for (int t = 0; t < taps; ++t) wp[((size_t)o * cin_p + ip) * taps + t] = w.data[((size_t)o * cin + i) * taps + t];
     }
   if (const float* b = net_.bias_of(name, cout)) std::copy(b, b + cout, bp.begin());
-  a.out_pixels = (long)x.n * x.h * x.w;
   return net_.emit_conv(ops_, name, wp.data(), cout_p, cin_p, ks, bp.data(), x, a);
 }
 
@@ -492,8 +490,8 @@ void YoloTrunk::fuse_front() {
     const Op &a = ops_[i], &b = ops_[i + 1];
     if (a.kind != Op::CONV || b.kind != Op::CONV || a.grp.count != 1 || b.grp.count != 1) return;
     const ConvProblem &pa = a.grp.p[0], &pb = b.grp.p[0];
-    const bool ok = a.cfg.variant == 2 && a.cfg.ks == 3 && a.cfg.stride == 2 && pa.Cout == a.cfg.bn && !pa.res &&
-                    (b.cfg.variant == 2 || b.cfg.variant == 6) && b.cfg.ks == 1 && b.cfg.kc == 32 && b.cfg.bn == pb.Cout && pb.Cin == pa.Cout && pb.Cout == pa.Cout &&
+    const bool ok = a.cfg.variant == ConvForm::Split && a.cfg.ks == 3 && a.cfg.stride == 2 && pa.Cout == a.cfg.bn && !pa.res &&
+                    b.cfg.variant == ConvForm::Split && b.cfg.ks == 1 && b.cfg.kc == 32 && b.cfg.bn == pb.Cout && pb.Cin == pa.Cout && pb.Cout == pa.Cout &&
                     pb.in == pa.out && pb.in_cstride == pa.out_cstride && pb.in_coff == pa.out_coff && !pb.res && !pb.in2;
     if (!ok) return;
     unfused_ = {a, b};
@@ -519,7 +517,7 @@ void YoloTrunk::fuse_stem() {
   Op& cv = ops_[1];
   if (st.kind != Op::STEM || cv.kind != Op::CONV || cv.grp.count != 1 || !st.front_wpk) return;
   ConvProblem& p = cv.grp.p[0];
-  const bool ok = cv.cfg.variant == 2 && cv.cfg.ks == 3 && cv.cfg.stride == 2 && cv.cfg.kc == 16 && cv.cfg.th == 8 && ((cv.cfg.bn == 32 && p.Cin == 16) || (cv.cfg.bn == 64 && p.Cin == 32)) &&
+  const bool ok = cv.cfg.variant == ConvForm::Split && cv.cfg.ks == 3 && cv.cfg.stride == 2 && cv.cfg.kc == 16 && cv.cfg.th == 8 && ((cv.cfg.bn == 32 && p.Cin == 16) || (cv.cfg.bn == 64 && p.Cin == 32)) &&
                   p.Cout <= cv.cfg.bn && !p.res && p.in == st.out.ptr && p.in_cstride == st.out.c && p.in_coff == 0 && p.Cin == st.out.c &&
                   st.in.h == 2 * st.out.h && st.in.w == 2 * st.out.w && p.H == st.out.h && p.W == st.out.w;
   if (!ok) return;

@@ -1,4 +1,4 @@
-"""The v_mfma_f32_16x16x32_f16 form of the split-f16x3 3x3 stride-2 convolution (csrc/conv_k32s2_split.hip, ConvConfig::variant 7,
+"""The v_mfma_f32_16x16x32_f16 form of the split-f16x3 3x3 stride-2 convolution (csrc/conv_k32s2_split.hip, ConvForm::K32S2,
 GTX_K32S2=0 falls back to the 32x32x16 kernel), on the smallest shapes that reach each of its paths.
 
 Bars. Between the two kernel forms: 1e-5 of the layer's largest value, the project's bar for a re-ordered sum

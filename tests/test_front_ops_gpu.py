@@ -300,8 +300,7 @@ def test_second_source_refusals(gtx_ctx, monkeypatch):
     _refused(lambda: ops.conv2d_fused(xo, wt, b, in_coff=8, cin=96, x2=np.zeros((2, 4, 9, 88), np.float32), in2_coff=16, c_split=64, ctx=gtx_ctx), bad)   # odd H
     xw = np.zeros((2, 10, 17, 112), np.float32)
     _refused(lambda: ops.conv2d_fused(xw, wt, b, in_coff=8, cin=96, x2=np.zeros((2, 5, 8, 88), np.float32), in2_coff=16, c_split=64, ctx=gtx_ctx), bad)   # odd W
-    # the 3x3 kernels of the default library: the 32x32x16 ones (stride 1 and 2) and the 16x16x32 ones (the Winograd and the
-    # pointwise 16x16x32 forms: the two tests below, which skip on a library built without them)
+    # the 3x3 kernels: the 32x32x16 ones (stride 1 and 2) and the 16x16x32 ones
     w3, b3 = fc.conv_weights(1, 64, 3, 96)
     needs_1x1 = "needs the split-f16x3 1x1 kernel"
     for stride in (1, 2):
@@ -312,39 +311,6 @@ def test_second_source_refusals(gtx_ctx, monkeypatch):
     xh = x.astype(np.float16)                           # the fp16 and exact-fp32 kernels
     _refused(lambda: ops.conv2d_fused(xh, wt, b, split=False, in_coff=8, cin=96, x2=x2.astype(np.float16), in2_coff=16, c_split=64, ctx=gtx_ctx), needs_1x1)
     _refused(lambda: ops.conv2d_fused(x, wt, b, split=False, c_split=64, **kw), needs_1x1)
-
-
-def test_second_source_refused_by_the_pointwise_k32_form(gtx_ctx, monkeypatch):
-    """GTX_K32P=1 on a library built with conv_k32p_split.hip: that form has no second source and must say so. Whether the library
-    carries the form is decided first, on a plain 1x1 launch (as tests/test_ops_gpu.py does); the refusal is then asserted."""
-    from geotrax_amd import ops
-
-    x, x2, wt, b, explicit = _two_source_data(10, 18, 64, 32, 64)
-    monkeypatch.setenv("GTX_K32P", "0")
-    direct = ops.conv2d(explicit, wt, b, in_coff=8, cin=96, split=True, ctx=gtx_ctx)
-    monkeypatch.setenv("GTX_K32P", "1")
-    if np.array_equal(ops.conv2d(explicit, wt, b, in_coff=8, cin=96, split=True, ctx=gtx_ctx), direct):
-        pytest.skip("libgtx.so was built without conv_k32p_split.hip (make -C geo-trax_amd clean && make -C geo-trax_amd K32P=1)")
-    for form in ("1", "2"):
-        monkeypatch.setenv("GTX_K32P", form)
-        _refused(lambda: ops.conv2d_fused(x, wt, b, in_coff=8, cin=96, x2=x2, in2_coff=16, c_split=64, ctx=gtx_ctx), "needs the split-f16x3 1x1 kernel")
-
-
-@pytest.mark.parametrize("mode", ["1", "3"])
-def test_second_source_refused_by_the_winograd_forms(gtx_ctx, monkeypatch, mode):
-    """GTX_WINO=1 / 3 on a library built with conv_wino_split.hip (3x3 stride 1, whole 64-cout tiles): no second source there
-    either. The build is probed first on a plain launch; on the default library the switch is compiled out and the case skips."""
-    from geotrax_amd import ops
-
-    x, x2, _, _, _ = _two_source_data(10, 18, 64, 32, 64)
-    w3, b3 = fc.conv_weights(1, 64, 3, 96)
-    monkeypatch.setenv("GTX_K32", "0")
-    monkeypatch.setenv("GTX_WINO", "0")
-    direct = ops.conv2d(x, w3, b3, in_coff=8, cin=96, split=True, ctx=gtx_ctx)
-    monkeypatch.setenv("GTX_WINO", mode)
-    if np.array_equal(ops.conv2d(x, w3, b3, in_coff=8, cin=96, split=True, ctx=gtx_ctx), direct):
-        pytest.skip("libgtx.so was built without conv_wino_split.hip (make -C geo-trax_amd clean && make -C geo-trax_amd WINO=1)")
-    _refused(lambda: ops.conv2d_fused(x, w3, b3, in_coff=8, cin=96, x2=x2, in2_coff=16, c_split=64, ctx=gtx_ctx), "needs the split-f16x3 1x1 kernel")
 
 
 # ---------------------------------------------------------------------------------------------------- out_plain and sat_flag

@@ -83,42 +83,6 @@ def test_conv2d_split_f16x3_meets_the_fp32_bar(gtx_ctx, case):
     np.testing.assert_allclose(got, conv2d_nhwc(x, wt, b, stride=stride, act=True), rtol=2e-4, atol=2e-4)
 
 
-@pytest.mark.parametrize("shape", [(1, 8, 16, 16, 64, False), (2, 20, 30, 64, 64, True), (1, 60, 60, 32, 128, False), (2, 37, 53, 128, 192, True),
-                                   (1, 16, 32, 256, 64, False)])
-@pytest.mark.parametrize("mode", ["1", "3"])
-def test_conv2d_winograd_split_meets_the_fp32_bar(gtx_ctx, monkeypatch, shape, mode):
-    """The Winograd F(2x2, 3x3) form of the split-f16x3 3x3 convolution (csrc/conv_wino_split.hip; opt-in, GTX_WINO=1): same
-    bar as the direct kernel against a float64 convolution of the values the pair format holds, on partial tiles, several
-    cout tiles, with residual and SiLU; and within 2e-6 of the direct kernel."""
-    import torch
-    from geotrax_amd import ops
-
-    n, h, w, cin, cout, use_res = shape
-    rng = np.random.default_rng(11)
-    x = (rng.standard_normal((n, h, w, cin)) * np.exp(rng.uniform(-3, 3, (n, h, w, cin)))).astype(np.float32)
-    wt = (rng.standard_normal((cout, 3, 3, cin)) / np.sqrt(9 * cin)).astype(np.float32)
-    b = rng.standard_normal(cout).astype(np.float32)
-    res = rng.standard_normal((n, h, w, cout)).astype(np.float32) if use_res else None
-
-    def pairs(a):                                     # what the pair format keeps: hi + lo
-        hi = a.astype(np.float16).astype(np.float32)
-        return hi.astype(np.float64) + (a - hi).astype(np.float16).astype(np.float64)
-
-    y = torch.nn.functional.conv2d(torch.from_numpy(pairs(x)).permute(0, 3, 1, 2), torch.from_numpy(wt.astype(np.float64)).permute(0, 3, 1, 2),
-                                   torch.from_numpy(b.astype(np.float64)), padding=1)
-    y = torch.nn.functional.silu(y).permute(0, 2, 3, 1).numpy()
-    if res is not None:
-        y = y + pairs(res)
-    monkeypatch.setenv("GTX_WINO", "0")
-    direct = ops.conv2d(x, wt, b, act=True, residual=res, split=True, ctx=gtx_ctx)
-    monkeypatch.setenv("GTX_WINO", mode)              # 1: 8 x 16 pixels, 8 waves; 3: 16 x 16 pixels, one wave per SIMD
-    wino = ops.conv2d(x, wt, b, act=True, residual=res, split=True, ctx=gtx_ctx)
-    scale = np.abs(y).max()
-    if np.array_equal(wino, direct):                  # the default libgtx.so does not carry the Winograd kernels (round 6)
-        pytest.skip("libgtx.so was built without conv_wino_split.hip (make -C geo-trax_amd clean && make -C geo-trax_amd WINO=1)")
-    assert np.abs(wino - y).max() / scale < 2e-6 and np.abs(wino - direct).max() / scale < 2e-6
-
-
 @pytest.mark.parametrize("shape", [(1, 8, 16, 32, 64, False), (2, 20, 30, 64, 64, True), (1, 60, 60, 32, 128, False), (2, 37, 53, 128, 192, True),
                                    (1, 16, 32, 256, 64, False), (1, 9, 17, 96, 80, True)])
 def test_conv2d_k32_split_meets_the_fp32_bar(gtx_ctx, monkeypatch, shape):
@@ -152,50 +116,6 @@ def test_conv2d_k32_split_meets_the_fp32_bar(gtx_ctx, monkeypatch, shape):
     if cout % 64 == 0:
         assert not np.array_equal(k32, direct)        # the other kernel did run (cout % 64 != 0: 32-cout tiles, not eligible)
     assert np.abs(k32 - y).max() / scale < 2e-6 and np.abs(k32 - direct).max() / scale < 2e-6
-
-
-@pytest.mark.parametrize("shape", [(1, 8, 16, 64, 64, False), (2, 20, 30, 96, 64, True), (1, 60, 60, 32, 128, False), (2, 37, 53, 160, 192, True),
-                                   (1, 16, 32, 704, 256, False), (1, 9, 17, 96, 80, True)])
-def test_conv2d_k32_pointwise_split_meets_the_fp32_bar(gtx_ctx, monkeypatch, shape):
-    """The v_mfma_f32_16x16x32_f16 forms of the split-f16x3 1x1 convolution (csrc/conv_k32p_split.hip; `make K32P=1`, GTX_K32P=1 / 2;
-    green on a K32P=1 library on MI355X, skipped on the default one): two 32-channel
-    chunks per stage -- an odd chunk count (96, 160 channels), a single chunk (32) and RT-DETR's deep concatenations (704) --,
-    partial tiles, several cout tiles, residual and SiLU: the direct kernel's bar against a float64 convolution of the values
-    the pair format holds, and within 2e-6 of the 32x32x16 kernel."""
-    import torch
-    from geotrax_amd import ops
-
-    n, h, w, cin, cout, use_res = shape
-    rng = np.random.default_rng(13)
-    x = (rng.standard_normal((n, h, w, cin)) * np.exp(rng.uniform(-3, 3, (n, h, w, cin)))).astype(np.float32)
-    wt = (rng.standard_normal((cout, 1, 1, cin)) / np.sqrt(cin)).astype(np.float32)
-    b = rng.standard_normal(cout).astype(np.float32)
-    res = rng.standard_normal((n, h, w, cout)).astype(np.float32) if use_res else None
-
-    def pairs(a):
-        hi = a.astype(np.float16).astype(np.float32)
-        return hi.astype(np.float64) + (a - hi).astype(np.float16).astype(np.float64)
-
-    y = torch.nn.functional.conv2d(torch.from_numpy(pairs(x)).permute(0, 3, 1, 2), torch.from_numpy(wt.astype(np.float64)).permute(0, 3, 1, 2),
-                                   torch.from_numpy(b.astype(np.float64)))
-    y = torch.nn.functional.silu(y).permute(0, 2, 3, 1).numpy()
-    if res is not None:
-        y = y + pairs(res)
-    monkeypatch.setenv("GTX_K32P", "0")
-    direct = ops.conv2d(x, wt, b, act=True, residual=res, split=True, ctx=gtx_ctx)
-    scale = np.abs(y).max()
-    forms = []
-    for form in ("1", "2"):                           # 1: pixels staged in LDS, 2: pixels straight into the MFMA operand registers
-        monkeypatch.setenv("GTX_K32P", form)
-        k32 = ops.conv2d(x, wt, b, act=True, residual=res, split=True, ctx=gtx_ctx)
-        if cout % 64 == 0:
-            if np.array_equal(k32, direct):           # the default libgtx.so does not carry these kernels (closed with numbers, round 6)
-                pytest.skip("libgtx.so was built without conv_k32p_split.hip (make -C geo-trax_amd clean && make -C geo-trax_amd K32P=1)")
-        else:
-            np.testing.assert_array_equal(k32, direct)
-        assert np.abs(k32 - y).max() / scale < 2e-6 and np.abs(k32 - direct).max() / scale < 2e-6
-        forms.append(k32)
-    np.testing.assert_array_equal(forms[0], forms[1])  # same MFMAs in the same order
 
 
 def test_conv2d_split_slices_residual_and_exact_integers(gtx_ctx):

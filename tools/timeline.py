@@ -12,7 +12,7 @@ f = sorted(glob.glob(d + "/**/*_kernel_trace.csv", recursive=True))[-1]
 ev = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r["Queue_Id"]) for r in csv.DictReader(open(f)))
 def is_conv(n):
     """Every convolution family of the detector: conv_igemm[_split], conv_k32_split (the dominant one since round 5 -- the round-5
-    digest's filter missed it and reported 62 % where this prints ~90 %), conv_front_split, conv_wino*, the stems."""
+    digest's filter missed it and reported 62 % where this prints ~90 %), conv_front_split, the stems."""
     return "conv_" in n or "stem" in n
 
 
