@@ -341,6 +341,15 @@ _SIGNATURES = {
     "gtx_drawer_draw_dev": (C.c_int, [_P, _P, _P, C.c_int]),
     "gtx_drawer_last_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "gtx_op_draw": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_size_t]),
+    "gtx_plot_canvas_create": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "gtx_plot_canvas_destroy": (None, [_P]),
+    "gtx_plot_canvas_size": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gtx_plot_canvas_draw": (C.c_int, [_P, _P, C.c_int]),
+    "gtx_plot_canvas_read": (C.c_int, [_P, _P]),
+    "gtx_plot_canvas_dptr": (C.c_int, [_P, C.POINTER(_P)]),
+    "gtx_plot_canvas_stats": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "gtx_op_plot_draw": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_int, C.c_size_t, _P, C.c_int]),
+    "gtx_op_plot_reduce": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
 }
 
 _lib = None

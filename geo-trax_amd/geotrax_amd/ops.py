@@ -896,3 +896,19 @@ def sift_select(oriented, max_features: int, rects=None, *, ctx=None):
                                      ptr(fin), ptr(xy), ptr(kp5), ptr(octv)))
     k = n.value
     return dict(n=k, final=fin[:k].copy(), xy=xy[:k].copy(), kp5=kp5[:k].copy(), octave=octv[:k].copy())
+
+
+# ---- the plot stage's trajectory maps (csrc/plot_draw.hip; the rule and the PlotCanvas class live in geotrax_amd/plot_draw.py)
+
+def plot_draw(ctx, canvas, prims):
+    """gtx_op_plot_draw: a host BGR canvas [h][w][3] with the strokes / discs of `prims` blended in (plot_draw.PRIM_DTYPE records)."""
+    from . import plot_draw as PD
+
+    return PD.draw_dev(ctx, canvas, prims)
+
+
+def plot_reduce(ctx, image, k: int):
+    """gtx_op_plot_reduce: the exact box average of a gray / RGB / RGBA u8 image by the integer factor k, as BGR."""
+    from . import plot_draw as PD
+
+    return PD.reduce_dev(ctx, image, k)

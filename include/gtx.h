@@ -82,7 +82,10 @@ extern "C" {
  *     gtx_op_stem and gtx_op_conv2d_fused (the stem launch, and the convolution launch with its second source, plain output,
  *     saturation flag and fused post / front stages, on host arrays) added: the same, the number stays.
  *     gtx_op_rt_{stem1, pool2, dwconv, upsample2x, tokens_in, mask_invalid} (RT-DETR's map-side kernels one launcher at a time)
- *     added: the same, the number stays. */
+ *     added: the same, the number stays.
+ *     gtx_plot_canvas_{create, destroy, size, draw, read, dptr, stats}, gtx_op_plot_draw and gtx_op_plot_reduce (the plot stage's
+ *     trajectory maps: an image reduced into a canvas in HBM, strokes and discs blended into it) added: new entry points and an
+ *     opaque handle only, so the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -1283,6 +1286,42 @@ int gtx_drawer_last_ms(gtx_drawer* drawer, float* ms);
 /* Operator hook (tests/test_draw_ops_gpu.py): a host frame, painted in place through one drawer. Sizes and records are checked
  * before the GPU is touched. */
 int gtx_op_draw(gtx_ctx* ctx, uint8_t* bgr, int h, int w, const int32_t* prims, int n, const void* atlas, size_t atlas_bytes);
+
+/* ------------------------------------------------------------------ trajectory maps (for the plot stage)
+ *
+ * Replaces plt.imshow(ortho) + plt.plot / plt.scatter per vehicle + plt.savefig of plot_trajectories_in_given_coordinates
+ * (plot.py:419-488, :740-756) for the pictures that have a pixel hot path: the orthophoto (or a white page) becomes a BGR u8
+ * canvas in HBM, semi-transparent strokes and discs are blended into it through per-tile lists, and the canvas goes to the JPEG
+ * encoder where it lies. A primitive is 32 bytes: float x0, y0, x1, y1, width; int32 bgr (b | g << 8 | r << 16), alpha (1..256,
+ * in 1/256 steps), poly. Coordinates are canvas pixels (a pixel's centre is at its integer coordinates), finite, in
+ * [-32768, 32767], a record spanning at most 2048 pixels per axis; width 0.25..64 pixels; a zero-length record is the disc of
+ * diameter `width`. A run of consecutive records with one `poly` is a polyline (same width, bgr and alpha throughout): a pixel
+ * takes the maximum coverage over its records and is blended once, polylines in list order. The pixel rule is specified in
+ * geotrax_amd/plot_draw.py, whose numpy twin the kernels (csrc/plot_draw.hip) equal byte for byte. Every bad size, count, width,
+ * alpha or coordinate is GTX_ERR_INVALID with the record's index in the message, before anything is uploaded; no primitive is
+ * ever dropped (the tile lists are sized exactly from a counting pass). */
+typedef struct gtx_plot_canvas gtx_plot_canvas;
+/* image: h x w x channels u8 on the host (1 = gray, 3 = RGB, 4 = RGBA, alpha ignored), reduced by the exact box average of
+ * factor k (1..256; round half up; edge blocks over the pixels they have) into a BGR canvas of ceil(h / k) x ceil(w / k), which
+ * must be within 1..16384 per side: what gtx_jpeg_enc_create accepts. Waits for the upload and the reduce launch. */
+int gtx_plot_canvas_create(gtx_ctx* ctx, const uint8_t* image, int h, int w, int channels, int k, gtx_plot_canvas** out);
+void gtx_plot_canvas_destroy(gtx_plot_canvas* canvas);
+int gtx_plot_canvas_size(gtx_plot_canvas* canvas, int* h, int* w);
+/* Blends n records (up to 2^22) into the canvas: count -> prefix sum -> fill -> per-tile sort -> paint on the context's stream. */
+int gtx_plot_canvas_draw(gtx_plot_canvas* canvas, const void* prims, int n);
+/* The canvas, h x w x 3 BGR, to the host. */
+int gtx_plot_canvas_read(gtx_plot_canvas* canvas, uint8_t* bgr);
+/* The canvas's device pointer (packed BGR, pitch 3 w), for gtx_jpeg_enc_submit_dev on the same context. Owned by the canvas. */
+int gtx_plot_canvas_dptr(gtx_plot_canvas* canvas, void** dptr);
+/* out[0..8): milliseconds between events of the creation's upload and reduce and of the last draw's binning launches and paint
+ * launch; that draw's tile count, list entries in all, longest list, primitive count. tools/plot_time.py. */
+int gtx_plot_canvas_stats(gtx_plot_canvas* canvas, double out[8]);
+/* Operator hook (tests/test_plot_draw_gpu.py): buf holds a canvas of h rows of `pitch` bytes (pitch >= 3 w; the first 3 w bytes
+ * of a row are its pixels) within buf_bytes >= (h - 1) pitch + 3 w bytes; the whole buffer is uploaded, painted and downloaded,
+ * and every byte that is not a pixel comes back as it went in. Sizes and records are checked before the GPU is touched. */
+int gtx_op_plot_draw(gtx_ctx* ctx, uint8_t* buf, size_t buf_bytes, int h, int w, size_t pitch, const void* prims, int n);
+/* Operator hook: the reduce launch alone on a host image; bgr_out: ceil(h / k) x ceil(w / k) x 3. */
+int gtx_op_plot_reduce(gtx_ctx* ctx, const uint8_t* image, int h, int w, int channels, int k, uint8_t* bgr_out);
 
 /* ------------------------------------------------------------------ result files (host code, no GPU work)
  *
