@@ -9,6 +9,7 @@
 #include <cmath>
 
 #include "det_kernels.hpp"
+#include "head_reg1.hpp"
 
 namespace gtx {
 
@@ -1030,6 +1031,51 @@ __global__ __launch_bounds__(256) void head_raw_kernel(const HeadParams hp, floa
   }
 }
 
+// ---- reg_max = 1 (yolo26.yaml's Detect): the box branch's last 1x1 has four outputs, the signed distances themselves; no DFL.
+// Four lanes per candidate, lane j forming side j (head_reg1.hpp: the sparse form's arithmetic); 64 candidates per workgroup and
+// step. Every lane of a group of four follows the same candidate, so the shuffles below stay inside active groups.
+template <typename T>
+__global__ __launch_bounds__(256) void head_boxes_r1_kernel(const HeadParams hp, const NmsBuffers nb) {
+  const int n = blockIdx.y;
+  const int cnt = min(nb.count[n], nb.cap);
+  const int lane = threadIdx.x & 63, j = lane & 3, base = lane & ~3;
+  for (int i0 = blockIdx.x * 64; i0 < cnt; i0 += gridDim.x * 64) {
+    const int i = i0 + (threadIdx.x >> 2);
+    const size_t o = (size_t)n * nb.cap + min(i, cnt - 1);
+    int a = nb.cand_anchor[o];
+    const bool ok = i < cnt && a >= 0 && a < hp.n_anchors;   // an index outside the level set is followed nowhere
+    if (!ok) a = 0;
+    const HeadLevel& L = hp.lv[find_level(hp, a)];
+    const int la = a - L.anchor_begin;
+    const T* f = static_cast<const T*>(L.feat) + ((size_t)n * L.h * L.w + la) * L.cstride;
+    const float d = reg1_side([&](int k) { return ldf(f + k); }, L.cb, L.wb, L.bb, j);
+    const float d0 = __shfl(d, base, 64), d1 = __shfl(d, base + 1, 64), d2 = __shfl(d, base + 2, 64), d3 = __shfl(d, base + 3, 64);
+    if (ok && j == 0) reinterpret_cast<float4*>(nb.cand_box)[o] = reg1_xyxy(d0, d1, d2, d3, la, L.w, L.stride);
+  }
+}
+
+// Debug / parity, reg_max = 1: every anchor -> [A][4+nc], the box as xywh like head_raw_kernel's. One wave per anchor.
+template <typename T>
+__global__ __launch_bounds__(256) void head_raw_r1_kernel(const HeadParams hp, float* __restrict__ out, int logits) {
+  const int n = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  const int a = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (a >= hp.n_anchors) return;
+  const HeadLevel& L = hp.lv[find_level(hp, a)];
+  const int la = a - L.anchor_begin;
+  const T* f = static_cast<const T*>(L.feat) + ((size_t)n * L.h * L.w + la) * L.cstride;
+  const float d = reg1_side([&](int k) { return ldf(f + k); }, L.cb, L.wb, L.bb, lane & 3);
+  const float4 b = reg1_xyxy(__shfl(d, 0, 64), __shfl(d, 1, 64), __shfl(d, 2, 64), __shfl(d, 3, 64), la, L.w, L.stride);
+  float* o = out + ((size_t)n * hp.n_anchors + a) * (4 + hp.nc);
+  if (lane == 0) { o[0] = (b.x + b.z) * 0.5f; o[1] = (b.y + b.w) * 0.5f; o[2] = b.z - b.x; o[3] = b.w - b.y; }
+  const T* fc = f + L.cb;
+  for (int c = lane; c < hp.nc; c += 64) {
+    float acc = L.bc[c];
+    for (int k = 0; k < L.cc; ++k) acc = fmaf(ldf(fc + k), L.wc[c * L.cc + k], acc);
+    o[4 + c] = logits ? acc : 1.f / (1.f + expf(-acc));
+  }
+}
+
 void launch_head_candidates(int dtype, const HeadParams& hp, int n, const NmsBuffers& nb, hipStream_t s) {
   launch_head_gate(dtype, hp, n, nb, s);
   launch_head_boxes(dtype, hp, n, nb, s);
@@ -1045,6 +1091,14 @@ void launch_head_gate(int dtype, const HeadParams& hp, int n, const NmsBuffers& 
 }
 
 void launch_head_boxes(int dtype, const HeadParams& hp, int n, const NmsBuffers& nb, hipStream_t s) {
+  if (hp.reg_max == 1) {                           // yolo26.yaml: four distances per anchor, no DFL, no weights in LDS
+    GTX_CHECK(hp.n_levels <= kMaxLevels, "head: %d levels", hp.n_levels);
+    dim3 grid(64, n), blk(256);
+    if (dtype == DT_F16) hipLaunchKernelGGL(head_boxes_r1_kernel<_Float16>, grid, blk, 0, s, hp, nb);
+    else hipLaunchKernelGGL(head_boxes_r1_kernel<float>, grid, blk, 0, s, hp, nb);
+    GTX_HIP(hipGetLastError());
+    return;
+  }
   dim3 grid2(64, n), block(256);
   const size_t lds = (size_t)hp.n_levels * hp.lv[0].cb * 64 * sizeof(float);
   GTX_CHECK(hp.n_levels <= kMaxLevels && hp.lv[0].cb <= 128, "head: %d levels of %d box channels", hp.n_levels, hp.lv[0].cb);
@@ -1063,6 +1117,12 @@ void launch_head_boxes(int dtype, const HeadParams& hp, int n, const NmsBuffers&
 
 void launch_head_raw(int dtype, const HeadParams& hp, int n, float* out, bool logits, hipStream_t s) {
   dim3 grid(cdiv(hp.n_anchors * 64, 256), n), block(256);
+  if (hp.reg_max == 1) {
+    if (dtype == DT_F16) hipLaunchKernelGGL(head_raw_r1_kernel<_Float16>, grid, block, 0, s, hp, out, logits ? 1 : 0);
+    else hipLaunchKernelGGL(head_raw_r1_kernel<float>, grid, block, 0, s, hp, out, logits ? 1 : 0);
+    GTX_HIP(hipGetLastError());
+    return;
+  }
   if (dtype == DT_F16) hipLaunchKernelGGL(head_raw_kernel<_Float16>, grid, block, 0, s, hp, out, logits ? 1 : 0);
   else hipLaunchKernelGGL(head_raw_kernel<float>, grid, block, 0, s, hp, out, logits ? 1 : 0);
   GTX_HIP(hipGetLastError());

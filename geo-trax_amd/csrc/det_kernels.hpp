@@ -45,8 +45,8 @@ struct HeadLevel {
   const void* feat;     // [N][h][w][cstride] T: channels [0,cb) box branch, [cb, cb+cc) cls branch
   int h, w, cstride;
   int cb, cc;           // box / cls feature channels (64 / 128 for YOLOv8s)
-  const float* wb;      // [cb][64] fp32  final box 1x1 conv (4*reg_max outputs), transposed
-  const float* bb;      // [64]
+  const float* wb;      // [cb][64] fp32  final box 1x1 conv (4*reg_max outputs), transposed; HeadParams::reg_max = 1: [cb][4]
+  const float* bb;      // [64]; reg_max = 1: [4]
   const float* wc;      // [nc][cc] fp32  final cls 1x1 conv
   const float* bc;      // [nc]
   float stride;         // 4 / 8 / 16 / 32
@@ -59,6 +59,7 @@ struct HeadParams {
   int nc;
   float conf;           // score threshold (strict >)
   unsigned long long class_mask[2];  // bit c set = class c kept (ultralytics `classes`); 128 classes
+  int reg_max;          // 1: yolo26.yaml's Detect, the box branch ends in four signed distances (the *_r1_kernel forms); else 16 DFL bins per side
 };
 
 struct NmsBuffers {
@@ -117,13 +118,14 @@ struct SparseBoxLevel {
   const void* w1; const float* b1; float sc1;
   const void* w2; const float* b2; float sc2;
   int anchor_begin;
-  const float* wb; const float* bb; float stride;   // the level's final box 1x1 convolution ([64][64] transposed, bias) and its stride: HeadLevel
+  const float* wb; const float* bb; float stride;   // the level's final box 1x1 convolution ([64][64] transposed, bias; reg_max = 1: [64][4]) and its stride: HeadLevel
 };
 struct SparseBox {
   SparseBoxLevel lv[kMaxLevels];
   int n_levels;
   int cap;              // candidates per image the buffer holds (more: the caller runs the dense layers)
   int* sat_flag;
+  int reg_max;          // 1: wb [64][4], bb [4], no DFL (HeadParams::reg_max)
 };
 void launch_head_sparse_box(const SparseBox& sb, int n, const NmsBuffers& nb, hipStream_t s);
 // ---- the YOLOv10 tail (v10_select.hip): v10Detect's one-to-one head needs no NMS

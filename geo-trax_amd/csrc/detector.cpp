@@ -1,7 +1,7 @@
-// YOLOv8 / YOLO11 / YOLOv10 (detect) graph builder + executor: the trunk (yolo_trunk.cpp walks the layer table of ultralytics' cfg/models/v8/yolov8.yaml,
+// YOLOv8 / YOLO11 / YOLOv10 / YOLO26 (detect) graph builder + executor: the trunk (yolo_trunk.cpp walks the layer table of ultralytics' cfg/models/v8/yolov8.yaml,
 // yolov8-p2.yaml or cfg/models/11/yolo11.yaml, whichever the tensor names tell) and the Detect layer on the levels, strides and prefix the
 // table's Detect row gives (model.22, model.28 of the P2 graph: a fourth level at stride 4, or model.23 of YOLO11 and YOLOv10: a class branch of
-// depthwise + pointwise pairs; YOLOv10's one-to-one pair of branches ends in the top-300 cut of v10_select.hip instead of the NMS); channel widths and bottleneck counts are read off the tensor shapes, so every scale (n/s/m/l/x) loads unchanged.
+// depthwise + pointwise pairs; YOLOv10's and YOLO26's one-to-one pair of branches ends in the top-300 cut of v10_select.hip instead of the NMS; YOLO26's box branch has reg_max = 1, four signed distances instead of 4 x 16 DFL bins, read off its last 1x1's row count); channel widths and bottleneck counts are read off the tensor shapes, so every scale (n/s/m/l/x) loads unchanged.
 #include "detector.hpp"
 #include "split_format.hpp"
 
@@ -54,11 +54,11 @@ void Detector::build_graph() {
   // top-300 cut, v10_select.hip). gtx_det_config.end2end picks the pair; the other pair's tensors are not read.
   const bool has_o2o = has(det_pfx_ + ".one2one_cv2.0.0.conv.weight");
   end2end_ = cfg_.end2end != 0;
-  GTX_CHECK(!end2end_ || has_o2o, "end2end: the checkpoint has no one-to-one head (%s.one2one_cv2 / one2one_cv3): only a YOLOv10 file has", det_pfx_.c_str());
+  GTX_CHECK(!end2end_ || has_o2o, "end2end: the checkpoint has no one-to-one head (%s.one2one_cv2 / one2one_cv3): only a YOLOv10 or YOLO26 file has", det_pfx_.c_str());
   GTX_CHECK(!end2end_ || !cfg_.obj_feats, "end2end: obj_feats (ReID `model: auto`) is not implemented for the one-to-one head");
   const std::string box_br = end2end_ ? ".one2one_cv2." : ".cv2.", cls_br = end2end_ ? ".one2one_cv3." : ".cv3.";
   GTX_CHECK(has(det_pfx_ + box_br + "0.0.conv.weight") && has(det_pfx_ + cls_br + "0.2.weight"),
-            "%s: the checkpoint holds no %s / %s tensors (a fused YOLOv10 export keeps the one-to-one head only: run it with end2end)", det_pfx_.c_str(),
+            "%s: the checkpoint holds no %s / %s tensors (a fused YOLOv10 / YOLO26 export keeps the one-to-one head only: run it with end2end)", det_pfx_.c_str(),
             box_br.substr(1, box_br.size() - 2).c_str(), cls_br.substr(1, cls_br.size() - 2).c_str());
 
   // ---- Detect (model.22, or model.28 of the P2 graph) ----
@@ -175,14 +175,18 @@ void Detector::build_graph() {
       return d;
     };
     const HostTensor &wb = tensor(b2 + ".2.weight"), &wc = tensor(b3 + ".2.weight");
-    GTX_CHECK(wb.shape[0] == 64 && (int)wb.shape[1] == cb, "Detect box head must have 4*16 outputs");
+    // reg_max off the last box convolution's rows: 4 x 16 DFL bins, or yolo26.yaml's four distances (reg_max = 1)
+    const int box_out = (int)wb.shape[0];
+    GTX_CHECK((box_out == 64 || box_out == 4) && (int)wb.shape[1] == cb, "Detect box head must have 4*16 outputs, or 4 (reg_max = 1); it has %d", box_out);
+    GTX_CHECK(l == 0 || head_.reg_max == box_out / 4, "Detect box branch: reg_max differs between levels");
+    head_.reg_max = box_out / 4;
     GTX_CHECK(cb <= 128 && cc % 8 == 0, "Detect head widths cb=%d cc=%d are outside what the decode kernels support", cb, cc);
     GTX_CHECK(l == 0 || cb == head_.lv[0].cb, "Detect box branch width differs between levels");
     GTX_CHECK((int)wc.shape[0] == cfg_.nc && (int)wc.shape[1] == cc, "Detect cls head has %d outputs, nc=%d", (int)wc.shape[0], cfg_.nc);
     {
-      std::vector<float> wbt((size_t)cb * 64);  // [cb][64]: the decode wave reads one output per lane
-      for (int o = 0; o < 64; ++o)
-        for (int k = 0; k < cb; ++k) wbt[(size_t)k * 64 + o] = wb.data[(size_t)o * cb + k];
+      std::vector<float> wbt((size_t)cb * box_out);  // [cb][64]: the decode wave reads one output per lane; reg_max = 1: [cb][4]
+      for (int o = 0; o < box_out; ++o)
+        for (int k = 0; k < cb; ++k) wbt[(size_t)k * box_out + o] = wb.data[(size_t)o * cb + k];
       L.wb = upload(wbt);
     }
     L.bb = upload(tensor(b2 + ".2.bias").data);
@@ -247,6 +251,7 @@ void Detector::build_graph() {
     }
     if (sparse_on_) {
       sparse_.n_levels = nl;
+      sparse_.reg_max = head_.reg_max;
       for (std::vector<Op>* stage : {&d1, &d2})
         for (Op& g : *stage) { g.family = conv_kernel_name(g.cfg); dense_box_ops_.push_back(g); }
     }

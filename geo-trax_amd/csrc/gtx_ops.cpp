@@ -855,7 +855,7 @@ long head_check(const char* op, int dtype, int n, int n_levels, const gtx_head_l
   if (A > (1l << 22)) op_bad(op, "too many anchors");
   return A;
 }
-void head_upload(HeadSet& s, int dtype, int n, int n_levels, const gtx_head_level* lv, int nc, bool gate, bool boxes) {
+void head_upload(HeadSet& s, int dtype, int n, int n_levels, const gtx_head_level* lv, int nc, bool gate, bool boxes, int box_out = 64) {
   s.hp.n_levels = n_levels;
   s.hp.nc = nc;
   int anchor = 0;
@@ -872,8 +872,8 @@ void head_upload(HeadSet& s, int dtype, int n, int n_levels, const gtx_head_leve
       H.wc = s.wc[l].as<float>(); H.bc = s.bc[l].as<float>();
     }
     if (boxes) {
-      upload(s.wb[l], L.wb, (size_t)L.cb * 64 * 4);
-      upload(s.bb[l], L.bb, 64 * 4);
+      upload(s.wb[l], L.wb, (size_t)L.cb * box_out * 4);
+      upload(s.bb[l], L.bb, (size_t)box_out * 4);
       H.wb = s.wb[l].as<float>(); H.bb = s.bb[l].as<float>();
     }
   }
@@ -932,27 +932,38 @@ int gtx_op_head_gate(gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx_hea
   });
 }
 
+namespace {
+// box_out: 64 (4 x 16 DFL bins) or 4 (reg_max = 1)
+void head_boxes_op(const char* op, int box_out, gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx_head_level* lv, int cap, const int* count,
+                   const int* cand_anchor, float* cand_box) {
+  const long A = head_check(op, dtype, n, n_levels, lv, 0, false, true);
+  if (cap < 1 || cap > (1 << 22)) op_bad(op, "cap >= 1");
+  cand_check(op, n, cap, count, cand_anchor, A);
+  need(cand_box, "cand_box"); need(ctx, "ctx");
+  GTX_HIP(hipSetDevice(ctx->device));
+  HeadSet hs;
+  head_upload(hs, dtype, n, n_levels, lv, 0, false, true, box_out);
+  hs.hp.reg_max = box_out / 4;
+  const size_t m = (size_t)n * cap;
+  gtx::DevBuf dc, da, db;
+  upload(dc, count, (size_t)n * 4); upload(da, cand_anchor, m * 4); fill_ff(db, m * 16);
+  gtx::NmsBuffers nb{};
+  nb.cap = cap;
+  nb.count = dc.as<int>(); nb.cand_anchor = da.as<int>(); nb.cand_box = db.as<float>();
+  gtx::launch_head_boxes(dtype, hs.hp, n, nb, ctx->stream);
+  GTX_HIP(hipStreamSynchronize(ctx->stream));
+  download(cand_box, db, m * 16);
+}
+}  // namespace
+
 int gtx_op_head_boxes(gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx_head_level* lv, int cap, const int* count, const int* cand_anchor,
                       float* cand_box) {
-  return guarded([&] {
-    const char* op = "head_boxes";
-    const long A = head_check(op, dtype, n, n_levels, lv, 0, false, true);
-    if (cap < 1 || cap > (1 << 22)) op_bad(op, "cap >= 1");
-    cand_check(op, n, cap, count, cand_anchor, A);
-    need(cand_box, "cand_box"); need(ctx, "ctx");
-    GTX_HIP(hipSetDevice(ctx->device));
-    HeadSet hs;
-    head_upload(hs, dtype, n, n_levels, lv, 0, false, true);
-    const size_t m = (size_t)n * cap;
-    gtx::DevBuf dc, da, db;
-    upload(dc, count, (size_t)n * 4); upload(da, cand_anchor, m * 4); fill_ff(db, m * 16);
-    gtx::NmsBuffers nb{};
-    nb.cap = cap;
-    nb.count = dc.as<int>(); nb.cand_anchor = da.as<int>(); nb.cand_box = db.as<float>();
-    gtx::launch_head_boxes(dtype, hs.hp, n, nb, ctx->stream);
-    GTX_HIP(hipStreamSynchronize(ctx->stream));
-    download(cand_box, db, m * 16);
-  });
+  return guarded([&] { head_boxes_op("head_boxes", 64, ctx, dtype, n, n_levels, lv, cap, count, cand_anchor, cand_box); });
+}
+
+int gtx_op_head_boxes_r1(gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx_head_level* lv, int cap, const int* count, const int* cand_anchor,
+                         float* cand_box) {
+  return guarded([&] { head_boxes_op("head_boxes_r1", 4, ctx, dtype, n, n_levels, lv, cap, count, cand_anchor, cand_box); });
 }
 
 int gtx_op_nms(gtx_ctx* ctx, int n, int cap, const int* count, const float* cand_score, const int* cand_anchor, const int* cand_cls,

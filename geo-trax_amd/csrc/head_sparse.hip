@@ -11,11 +11,14 @@
 // The wave then decodes its candidates' boxes (the final 1x1 convolution + DFL of head_boxes_kernel, same operations in the same
 // order), so the sparse path is one launch between the score gate and the NMS.
 // The dense convolutions stay available (Detector: GTX_SPARSE_BOX=0, the debug read-backs, more candidates than the buffer holds).
+// kReg1 (yolo26.yaml's Detect, reg_max = 1): the same two layers, then the four-output 1x1 of head_boxes_r1_kernel straight to xyxy
+// (head_reg1.hpp) -- no 64-bin stage. The 16-bin instantiation is the kernel as it was.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
 #include "conv_split_device.hpp"
 #include "det_kernels.hpp"
+#include "head_reg1.hpp"
 
 namespace gtx {
 
@@ -35,6 +38,7 @@ __device__ __forceinline__ const char* wrow(const void* w, int step /* chunk * 9
 // grid.x = levels x groups: workgroup g of level l takes candidates [16 g, 16 g + 16) of the level's list (head_candidates_kernel
 // files every candidate under its level), four per wave. A wave's candidates share the weights: 8 fragment loads per K step feed
 // 48 MFMAs, and the four independent accumulator sets hide the loads' latency.
+template <bool kReg1>
 __global__ __launch_bounds__(256) void head_sparse_box_kernel(const SparseBox sb, const NmsBuffers nb, int groups) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int n = blockIdx.y;
@@ -188,6 +192,20 @@ __global__ __launch_bounds__(256) void head_sparse_box_kernel(const SparseBox sb
       *reinterpret_cast<float4*>(fl + col * 64 + 16 * q + 4 * kg) = make_float4(v0.x, v0.y, v1.x, v1.y);
     }
   }
+  if constexpr (kReg1) {
+    // ---- reg_max = 1: lane 4 c + j forms side j of candidate c (head_boxes_r1_kernel's arithmetic, head_reg1.hpp), lane 4 c stores the
+    // box. A short last group's repeated candidates and an entry or anchor outside its buffer / level are not stored.
+    const int c = (lane >> 2) & 3, j = lane & 3, base = lane & 12;
+    const int mine_ci = c == 0 ? ci[0] : (c == 1 ? ci[1] : (c == 2 ? ci[2] : ci[3]));
+    const bool live = lane < 4 * kCandPerWave && first + c < cnt && mine_ci >= 0 && mine_ci < nb.cap;
+    const int la = (live ? nb.cand_anchor[(size_t)n * nb.cap + mine_ci] : L.anchor_begin) - L.anchor_begin;
+    const float d = reg1_side([&](int k) { return fl[c * 64 + k]; }, 64, L.wb, L.bb, j);
+    const float d0 = __shfl(d, base, 64), d1 = __shfl(d, base + 1, 64), d2 = __shfl(d, base + 2, 64), d3 = __shfl(d, base + 3, 64);
+    if (live && j == 0 && la >= 0 && la < L.H * L.W)
+      reinterpret_cast<float4*>(nb.cand_box)[(size_t)n * nb.cap + mine_ci] = reg1_xyxy(d0, d1, d2, d3, la, L.W, L.stride);
+    flag_saturation(sb.sat_flag, sat, lane);
+    return;
+  }
   // ---- box decode of the wave's candidates (head_boxes_kernel's arithmetic: the 64 x 64 final 1x1 convolution as one fmaf chain
   // per output in feature order, DFL softmax expectation per side, dist2bbox, xywh -> xyxy) ----
 #pragma unroll 1
@@ -228,7 +246,8 @@ __global__ __launch_bounds__(256) void head_sparse_box_kernel(const SparseBox sb
 void launch_head_sparse_box(const SparseBox& sb, int n, const NmsBuffers& nb, hipStream_t s) {
   GTX_CHECK(sb.cap > 0 && nb.lvl_count != nullptr && nb.lvl_list != nullptr && nb.lvl_cap == sb.cap, "sparse box branch: no buffers");
   const int groups = (nb.lvl_cap + 4 * kCandPerWave - 1) / (4 * kCandPerWave);
-  hipLaunchKernelGGL(head_sparse_box_kernel, dim3(sb.n_levels * groups, n), dim3(256), 4 * kWaveLds, s, sb, nb, groups);
+  if (sb.reg_max == 1) hipLaunchKernelGGL(head_sparse_box_kernel<true>, dim3(sb.n_levels * groups, n), dim3(256), 4 * kWaveLds, s, sb, nb, groups);
+  else hipLaunchKernelGGL(head_sparse_box_kernel<false>, dim3(sb.n_levels * groups, n), dim3(256), 4 * kWaveLds, s, sb, nb, groups);
   GTX_HIP(hipGetLastError());
 }
 

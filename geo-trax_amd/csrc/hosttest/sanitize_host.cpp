@@ -172,19 +172,23 @@ bool run_writers(unsigned seed) {
   return anchor[0] == 0 && anchor[1] <= 1;
 }
 
-// The YOLO trunks' layer tables are walkable (yolov10.yaml's among them), a broken one is caught at its row, and the depthwise
+// The YOLO trunks' layer tables are walkable (yolov10.yaml's and yolo26.yaml's among them), a broken one is caught at its row, and the depthwise
 // weight transposition touches exactly its taps x channels values (odd sizes: 7x7 on 24 channels, 3x3 on 8)
 static bool run_trunk_tables() {
   using namespace gtx;
   using namespace gtx::tables;
   const struct { const TrunkRow* rows; int n; } all[] = {{kYolov8, (int)(sizeof(kYolov8) / sizeof(TrunkRow))}, {kYolov8P2, (int)(sizeof(kYolov8P2) / sizeof(TrunkRow))},
                                                           {kYolo11, (int)(sizeof(kYolo11) / sizeof(TrunkRow))}, {kYolo10, (int)(sizeof(kYolo10) / sizeof(TrunkRow))},
-                                                          {kYolo11Cls, (int)(sizeof(kYolo11Cls) / sizeof(TrunkRow))}, {kYolov8, kClsBackboneRows}};
+                                                          {kYolo11Cls, (int)(sizeof(kYolo11Cls) / sizeof(TrunkRow))}, {kYolov8, kClsBackboneRows},
+                                                          {kYolo26, (int)(sizeof(kYolo26) / sizeof(TrunkRow))}};
   for (const auto& t : all)
     if (trunk_table_error(t.rows, t.n) >= 0) return false;
   int scdown = 0, psa = 0;
   for (const TrunkRow& r : kYolo10) { scdown += r.mod == TrunkRow::SCDOWN; psa += r.mod == TrunkRow::PSA; }
   if (scdown != 3 || psa != 1 || kYolo10[23].mod != TrunkRow::DETECT) return false;
+  // yolo26.yaml: kYolo11's modules row for row; its SPPF row alone carries the linear-cv1 + residual flag
+  for (int i = 0; i < 24; ++i)
+    if (kYolo26[i].mod != kYolo11[i].mod || (kYolo26[i].mod == TrunkRow::SPPF) != (i == 9) || (i == 9 && (!kYolo26[i].shortcut || kYolo11[i].shortcut))) return false;
   std::vector<TrunkRow> bad(kYolo10, kYolo10 + 24);
   bad[12].from[1] = 13;                               // a Concat that reads a later layer
   if (trunk_table_error(bad.data(), 24) != 12) return false;

@@ -14,7 +14,7 @@ struct TrunkRow {
                     // SCDOWN: 1x1 Conv + depthwise 3x3 stride 2 without activation; PSA: C2PSA's one block directly under the layer (yolov10.yaml);
                     // ELAN: ELAN1 / RepNCSPELAN4, ADOWN: AConv / ADown (which one, the tensors tell), SPPELAN: SPPF's pools closed by cv5 (yolov9.yaml)
   int from[4];      // the yaml's `from`: -1 = the row above (row 0: the image), else a layer index; 0 ends the list
-  bool shortcut;    // BLOCK: the bottlenecks add their input
+  bool shortcut;    // BLOCK: the bottlenecks add their input; SPPF: yolo26.yaml's form (cv1 without activation, the input added to cv2's output)
 };
 struct TrunkGraph {
   const TrunkRow* rows;
@@ -91,6 +91,20 @@ inline constexpr R kYolo10[] = {
     {12, R::CONCAT, {-1, 6}, false}, {13, R::BLOCK, {-1}, false},     {14, R::UPSAMPLE, {-1}, false},  {15, R::CONCAT, {-1, 4}, false},
     {16, R::BLOCK, {-1}, false},    {17, R::CONV, {-1}, false},       {18, R::CONCAT, {-1, 13}, false}, {19, R::BLOCK, {-1}, false},
     {20, R::SCDOWN, {-1}, false},   {21, R::CONCAT, {-1, 10}, false}, {22, R::BLOCK, {-1}, true},      {23, R::DETECT, {16, 19, 22}, false}};
+// 26/yolo26.yaml: kYolo11's rows; SPPF(shortcut) = model.9 and, told by its tensors, the C3k2 with attention (m.{k} = Bottleneck + PSABlock)
+// = model.22; Detect = model.23 with reg_max = 1 and a one-to-one pair (the 4-row last box convolution tells). What no tensor tells,
+// tests/yolo26_ref.py lists as doubts: the neck's shortcuts (kNeckShortcut, as for YOLO11), model.22's Bottleneck shortcut (taken as on)
+// and whether SPPF's residual follows cv2's activation (taken as so: the epilogue form proj / ffn.1 use; the other order is not built).
+inline constexpr bool kAttnBlockShortcut = true;
+inline constexpr bool kSppfResidualAfterAct = true;
+static_assert(kSppfResidualAfterAct, "SPPF's residual in front of the activation is not built");
+inline constexpr R kYolo26[] = {
+    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},
+    {4, R::BLOCK, {-1}, true},      {5, R::CONV, {-1}, false},        {6, R::BLOCK, {-1}, true},       {7, R::CONV, {-1}, false},
+    {8, R::BLOCK, {-1}, true},      {9, R::SPPF, {-1}, true},         {10, R::C2PSA, {-1}, false},     {11, R::UPSAMPLE, {-1}, false},
+    {12, R::CONCAT, {-1, 6}, false}, {13, R::BLOCK, {-1}, kNeckShortcut}, {14, R::UPSAMPLE, {-1}, false}, {15, R::CONCAT, {-1, 4}, false},
+    {16, R::BLOCK, {-1}, kNeckShortcut}, {17, R::CONV, {-1}, false},  {18, R::CONCAT, {-1, 13}, false}, {19, R::BLOCK, {-1}, kNeckShortcut},
+    {20, R::CONV, {-1}, false},     {21, R::CONCAT, {-1, 10}, false}, {22, R::BLOCK, {-1}, kAttnBlockShortcut}, {23, R::DETECT, {16, 19, 22}, false}};
 // v9/yolov9{t,s,m,c}.yaml: ELAN1 or RepNCSPELAN4 where the others have C2f, AConv (t / s / m) or ADown (c) where they have the
 // stride-2 Convs, SPPELAN = model.9, YOLOv8's Detect = model.22
 inline constexpr R kYolo9[] = {

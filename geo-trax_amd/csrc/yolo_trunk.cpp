@@ -6,6 +6,7 @@
 // more rule in choose_graph(); a new module is one more case in build(). v10/yolov10.yaml is kYolo10 (SCDown, PSA = model.10, C2fCIB, v10Detect = model.23),
 // v9/yolov9{t,s,m,c}.yaml kYolo9 (ELAN1 / RepNCSPELAN4, AConv / ADown behind pool_down.hip's launch, SPPELAN = model.9, Detect = model.22). The two classification graphs of the ReID embedder are
 // prefixes of these tables: yolov8-cls.yaml = kYolov8's rows 0-8, 11/yolo11-cls.yaml = kYolo11's rows 0-8 + C2PSA as model.9 (kYolo11Cls).
+// 26/yolo26.yaml is kYolo26: kYolo11's rows with SPPF's linear cv1 + residual at model.9 and the C3k2 with attention at model.22.
 #include "yolo_trunk.hpp"
 #include "pool_down.hpp"
 #include "rtdetr_kernels.hpp"
@@ -32,6 +33,9 @@ TrunkGraph YoloTrunk::choose_graph() const {
   // yolov10.yaml: PSA's attention directly under model.10, SCDown's depthwise model.5.cv2 and a one-to-one head at model.23
   if (net_.has("model.10.attn.qkv.conv.weight") && net_.has("model.5.cv2.conv.weight") && net_.has("model.23.one2one_cv2.0.0.conv.weight"))
     return graph_of(kYolo10, true);
+  // yolo26.yaml: yolo11.yaml's names plus the attention inside model.22's C3k2 and a one-to-one head at model.23
+  if (net_.has("model.10.m.0.attn.qkv.conv.weight") && net_.has("model.22.m.0.1.attn.qkv.conv.weight") && net_.has("model.23.one2one_cv2.0.0.conv.weight"))
+    return graph_of(kYolo26, true);
   // yolo11.yaml: C2PSA at model.10 and Detect (depthwise class branch) at model.23 -- names no YOLOv8 file has
   if (net_.has("model.10.m.0.attn.qkv.conv.weight") && net_.has("model.23.cv3.0.0.0.conv.weight")) return graph_of(kYolo11, true);
   // yolov9.yaml: a RepNCSPELAN4's RepCSP (a Sequential inside the block) and SPPELAN's cv5 at model.9, Detect = model.22
@@ -73,11 +77,13 @@ void YoloTrunk::upsample(const std::string& name, const View& src, const View& d
 }
 
 // ---- SPPF: cv1 -> 3 cascaded pools -> cv2, written into `out` (its slice of the Concat that lists it, or a view of its own)
-void YoloTrunk::sppf(const std::string& pfx, const View& x, const View& out, const char* last) {
+// linear_res (yolo26.yaml's SPPF(shortcut)): cv1 has no activation, and x joins cv2's output in its epilogue, after the activation
+void YoloTrunk::sppf(const std::string& pfx, const View& x, const View& out, const char* last, bool linear_res) {
   const int cm = (int)net_.tensor(pfx + ".cv1.conv.weight").shape[0];
   View sp = net_.new_view(x.h, x.w, 4 * cm);
   View sp0 = sp.slice(0, cm);
-  conv(pfx + ".cv1.conv", x, 1, &sp0, nullptr);
+  if (linear_res) conv_act(pfx + ".cv1.conv", x, 0, &sp0, nullptr);
+  else conv(pfx + ".cv1.conv", x, 1, &sp0, nullptr);
   Op op;
   op.kind = Op::POOL;
   op.name = pfx + ".m";
@@ -85,7 +91,8 @@ void YoloTrunk::sppf(const std::string& pfx, const View& x, const View& out, con
   op.in = sp0;
   op.out = sp;
   ops_.push_back(op);
-  conv(pfx + last, sp, 1, &out, nullptr);
+  GTX_CHECK(!linear_res || x.c == out.c, "%s: the residual has %d channels, the output %d", pfx.c_str(), x.c, out.c);
+  conv(pfx + last, sp, 1, &out, linear_res ? &x : nullptr);
   net_.set_layer_view(pfx, out);
 }
 
@@ -205,18 +212,26 @@ View YoloTrunk::adown(const std::string& pfx, const View& x, const View* out_sli
 }
 
 // C2f / C3k2: cv1 -> a | b, n blocks m.{k} chained from b with every output appended, cv2 on the concatenation. m.{k} is a Bottleneck
-// (C2f: full hidden width; C3k2 with c3k = False: half of it) or a C3k (C3k2 with c3k = True: the block has a cv3).
+// (C2f: full hidden width; C3k2 with c3k = False: half of it), a C3k (C3k2 with c3k = True: the block has a cv3) or, in yolo26.yaml's
+// C3k2 with attention, Sequential(Bottleneck of half width, PSABlock): m.{k}.0.cv1 / cv2, then C2PSA's block on m.{k}.1.*.
 View YoloTrunk::c2f(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src) {
   const int c = (int)net_.tensor(pfx + ".cv1.conv.weight").shape[0] / 2;
   int n = 0;
-  while (net_.has(pfx + ".m." + std::to_string(n) + ".cv1.conv.weight") || net_.has(pfx + ".m." + std::to_string(n) + ".cv1.0.conv.weight")) ++n;
+  while (net_.has(pfx + ".m." + std::to_string(n) + ".cv1.conv.weight") || net_.has(pfx + ".m." + std::to_string(n) + ".cv1.0.conv.weight") ||
+         net_.has(pfx + ".m." + std::to_string(n) + ".0.cv1.conv.weight"))
+    ++n;
   View cat = net_.new_view(x.h, x.w, (2 + n) * c);
   View first = cat.slice(0, 2 * c);
   conv(pfx + ".cv1.conv", x, 1, &first, nullptr, up_src);
   for (int k = 0; k < n; ++k) {
     const std::string m = pfx + ".m." + std::to_string(k);
     View src = cat.slice((1 + k) * c, c), dst = cat.slice((2 + k) * c, c);
-    if (net_.has(m + ".cv1.0.conv.weight")) cib(m, src, dst, shortcut);                       // C2fCIB (yolov10.yaml)
+    if (net_.has(m + ".0.cv1.conv.weight") && net_.has(m + ".1.attn.qkv.conv.weight")) {        // C3k2 with attention (yolo26.yaml): Bottleneck, then PSABlock
+      GTX_CHECK(c % 64 == 0, "%s: %d hidden channels are not whole 64-wide attention heads", m.c_str(), c);
+      const View mid = net_.new_view(x.h, x.w, c);
+      bottleneck(m + ".0", src, mid, shortcut);
+      psa_block(m + ".1", mid, dst);
+    } else if (net_.has(m + ".cv1.0.conv.weight")) cib(m, src, dst, shortcut);                // C2fCIB (yolov10.yaml)
     else if (net_.has(m + ".cv3.conv.weight")) c3k(m, src, dst, shortcut);
     else bottleneck(m, src, dst, shortcut);
   }
@@ -225,47 +240,52 @@ View YoloTrunk::c2f(const std::string& pfx, const View& x, bool shortcut, const 
   return out;
 }
 
+// PSABlock on b (c channels, c / 64 heads of key depth 32 and value width 64) -> dst: b1 = b + proj(attention(qkv(b)) + pe(v)), dst = b1 +
+// ffn.1(ffn.0(b1)). The convolutions without activation take the residual in their epilogue. dst may be b's own buffer.
+void YoloTrunk::psa_block(const std::string& m, const View& b, const View& dst) {
+  const int c = b.c, heads = c / 64;
+  const HostTensor &wq = net_.tensor(m + ".attn.qkv.conv.weight"), &wp = net_.tensor(m + ".attn.pe.conv.weight");
+  GTX_CHECK(c % 64 == 0 && (int)wq.shape[0] == heads * 128 && wp.shape.size() == 4 && (int)wp.shape[0] == c && wp.shape[1] == 1 && wp.shape[2] == 3,
+            "%s: attention of %d heads with key_dim 32 / head_dim 64 expected", m.c_str(), heads);
+  const View qkv = conv_act(m + ".attn.qkv.conv", b, 0, nullptr, nullptr);
+  View att = net_.new_view(b.h, b.w, c);
+  {
+    std::vector<float> wt((size_t)9 * c);
+    for (int ch = 0; ch < c; ++ch)
+      for (int t = 0; t < 9; ++t) wt[(size_t)t * c + ch] = wp.data[(size_t)ch * 9 + t];
+    std::vector<float> bias(c, 0.f);
+    if (const float* pb = net_.bias_of(m + ".attn.pe.conv", c)) std::copy(pb, pb + c, bias.begin());
+    Op op;
+    op.kind = Op::ATTN;
+    op.name = m + ".attn";
+    op.family = psa_attention_small(b.h, b.w) ? "psa_attn_small_kernel" : "psa_attn_kernel";     // launch_psa_attention's rule
+    op.in = qkv; op.out = att;
+    op.heads = heads;
+    op.dw_w = net_.upload(wt); op.dw_bias = net_.upload(bias);
+    op.sat = net_.sat_flag();
+    ops_.push_back(op);
+    net_.set_layer_view(m + ".attn.out", att);       // softmax(q^T k) v + pe(v): what proj reads
+  }
+  View b1 = net_.new_view(b.h, b.w, c);
+  conv_act(m + ".attn.proj.conv", att, 0, &b1, &b);
+  const View f0 = conv_act(m + ".ffn.0.conv", b1, 1, nullptr, nullptr);
+  conv_act(m + ".ffn.1.conv", f0, 0, &dst, &b1);
+}
+
 // C2PSA: cv1 -> a | b; per PSABlock b += proj(attention(qkv(b)) + pe(v)), b += ffn.1(ffn.0(b)); cv2 on cat(a, b). The convolutions
 // without activation take the residual in their epilogue (activation first, then the residual: x + conv(x)). The last block
 // writes b back into cv1's buffer, which cv2 then reads whole.
 View YoloTrunk::c2psa(const std::string& pfx, const View& x, const View* out_slice, bool bare) {
   const int c = (int)net_.tensor(pfx + ".cv1.conv.weight").shape[0] / 2;
   GTX_CHECK(c % 64 == 0, "%s: %d hidden channels are not whole 64-wide attention heads", pfx.c_str(), c);
-  const int heads = c / 64;
   int n = bare ? 1 : 0;
   while (!bare && net_.has(pfx + ".m." + std::to_string(n) + ".attn.qkv.conv.weight")) ++n;
   GTX_CHECK(n > 0, "%s: no PSABlock", pfx.c_str());
   View ab = conv(pfx + ".cv1.conv", x, 1, nullptr, nullptr);
   View b = ab.slice(c, c);
   for (int k = 0; k < n; ++k) {
-    const std::string m = bare ? pfx : pfx + ".m." + std::to_string(k);
-    const HostTensor &wq = net_.tensor(m + ".attn.qkv.conv.weight"), &wp = net_.tensor(m + ".attn.pe.conv.weight");
-    GTX_CHECK((int)wq.shape[0] == heads * 128 && wp.shape.size() == 4 && (int)wp.shape[0] == c && wp.shape[1] == 1 && wp.shape[2] == 3,
-              "%s: attention of %d heads with key_dim 32 / head_dim 64 expected", m.c_str(), heads);
-    const View qkv = conv_act(m + ".attn.qkv.conv", b, 0, nullptr, nullptr);
-    View att = net_.new_view(x.h, x.w, c);
-    {
-      std::vector<float> wt((size_t)9 * c);
-      for (int ch = 0; ch < c; ++ch)
-        for (int t = 0; t < 9; ++t) wt[(size_t)t * c + ch] = wp.data[(size_t)ch * 9 + t];
-      std::vector<float> bias(c, 0.f);
-      if (const float* pb = net_.bias_of(m + ".attn.pe.conv", c)) std::copy(pb, pb + c, bias.begin());
-      Op op;
-      op.kind = Op::ATTN;
-      op.name = m + ".attn";
-      op.family = psa_attention_small(x.h, x.w) ? "psa_attn_small_kernel" : "psa_attn_kernel";     // launch_psa_attention's rule
-      op.in = qkv; op.out = att;
-      op.heads = heads;
-      op.dw_w = net_.upload(wt); op.dw_bias = net_.upload(bias);
-      op.sat = net_.sat_flag();
-      ops_.push_back(op);
-      net_.set_layer_view(m + ".attn.out", att);       // softmax(q^T k) v + pe(v): what proj reads
-    }
-    View b1 = net_.new_view(x.h, x.w, c);
-    conv_act(m + ".attn.proj.conv", att, 0, &b1, &b);
-    const View f0 = conv_act(m + ".ffn.0.conv", b1, 1, nullptr, nullptr);
-    View b2 = k + 1 == n ? ab.slice(c, c) : net_.new_view(x.h, x.w, c);
-    conv_act(m + ".ffn.1.conv", f0, 0, &b2, &b1);
+    const View b2 = k + 1 == n ? ab.slice(c, c) : net_.new_view(x.h, x.w, c);
+    psa_block(bare ? pfx : pfx + ".m." + std::to_string(k), b, b2);
     b = b2;
   }
   View out = conv(pfx + ".cv2.conv", ab, 1, out_slice, nullptr);
@@ -435,7 +455,7 @@ YoloTrunk::Levels YoloTrunk::build(const View& img, const TrunkGraph& g, bool fr
       case TrunkRow::SPPF: {
         const View* s = place(i, x.h, x.w);
         out[i] = s ? *s : net_.new_view(x.h, x.w, width[i]);
-        sppf(name(i), x, out[i]);
+        sppf(name(i), x, out[i], ".cv2.conv", r.shortcut);
         break;
       }
       case TrunkRow::C2PSA: out[i] = c2psa(name(i), x, place(i, x.h, x.w)); break;

@@ -1,5 +1,5 @@
 // The YOLO trunk: everything in front of the Detect layer of ultralytics' yolov8.yaml (model.0-21), yolov8-p2.yaml (model.0-27) and
-// yolo11.yaml / yolov10.yaml (model.0-22), and the YOLOv8-cls (model.0-8) and YOLO11-cls (model.0-9) backbones. Each graph is a constant table with one row per yaml layer
+// yolo11.yaml / yolov10.yaml / yolo26.yaml (model.0-22), and the YOLOv8-cls (model.0-8) and YOLO11-cls (model.0-9) backbones. Each graph is a constant table with one row per yaml layer
 // (yolo_trunk.cpp); one walk over a table emits its launches into the caller's op list. Every family that runs a trunk builds
 // through it: the YOLOv8 / P2 / YOLO11 detector (Detect on its outputs, detector.cpp), YOLOv8-RTDETR (an RTDETRDecoder on model.15 /
 // 18 / 21, rtdetr.cpp) and the ReID embedder (reid.cpp). It also owns the fused front (stem + model.1 + model.2.cv1 in one launch on
@@ -49,10 +49,10 @@ class YoloTrunk {
   struct Levels {
     std::vector<View> in;        // the Detect row's inputs, finest level first (a table without one: its last layer's output)
     std::vector<float> strides;  // net height / level height
-    std::string det_pfx;         // the Detect row: model.22 (yolov8.yaml), model.28 (yolov8-p2.yaml) or model.23 (yolo11.yaml, yolov10.yaml)
+    std::string det_pfx;         // the Detect row: model.22 (yolov8.yaml), model.28 (yolov8-p2.yaml) or model.23 (yolo11.yaml, yolov10.yaml, yolo26.yaml)
     bool dw_cls = false;         // TrunkGraph::dw_cls
   };
-  // The graph the tensors were built from, by their names: yolov10.yaml, yolo11.yaml, yolov9.yaml, yolov8-p2.yaml, else yolov8.yaml
+  // The graph the tensors were built from, by their names: yolov10.yaml, yolo26.yaml, yolo11.yaml, yolov9.yaml, yolov8-p2.yaml, else yolov8.yaml
   TrunkGraph choose_graph() const;
   static TrunkGraph cls_backbone();   // model.0-8 of yolov8.yaml = yolov8-cls.yaml's backbone
   // The classification graph the tensors were built from: yolo11-cls.yaml (model.0-8 of yolo11.yaml + C2PSA = model.9), else cls_backbone()
@@ -88,12 +88,14 @@ class YoloTrunk {
   View bottleneck(const std::string& m, const View& src, const View& dst, bool shortcut);
   View c3k(const std::string& m, const View& src, const View& dst, bool shortcut);
   View c2psa(const std::string& pfx, const View& x, const View* out_slice, bool bare = false);   // bare: PSA, the one block's tensors directly under pfx
+  void psa_block(const std::string& m, const View& b, const View& dst);                         // one PSABlock (C2PSA's, PSA's, the C3k2 with attention's)
   View cib(const std::string& m, const View& src, const View& dst, bool shortcut);
   View scdown(const std::string& pfx, const View& x, const View* out_slice);
   View elan(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src);   // ELAN1 and RepNCSPELAN4
   View adown(const std::string& pfx, const View& x, const View* out_slice);                                     // AConv and ADown
   void upsample(const std::string& name, const View& src, const View& dst);
-  void sppf(const std::string& pfx, const View& x, const View& out, const char* last = ".cv2.conv");   // SPPELAN: last = ".cv5.conv"
+  // SPPELAN: last = ".cv5.conv"; linear_res: yolo26.yaml's SPPF (cv1 without activation, x added to the output)
+  void sppf(const std::string& pfx, const View& x, const View& out, const char* last = ".cv2.conv", bool linear_res = false);
   void fuse_front();         // model.1 (3x3 stride 2) + model.2.cv1 (1x1) as one launch on the split-f16x3 path
   void fuse_stem();          // model.0 (the stem) computed inside model.1's launch: its output never reaches HBM
   void release_hidden_layers();

@@ -158,6 +158,7 @@ _SIGNATURES = {
     "gtx_op_rt_mask_invalid": (C.c_int, [_P] + [C.c_int] * 6 + [_P, C.c_int, C.c_int, C.c_int]),
     "gtx_op_head_gate": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gtx_op_head_boxes": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "gtx_op_head_boxes_r1": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
     "gtx_op_nms": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                              C.c_double, C.c_int, _P, _P, _P]),
     "gtx_op_v10_select": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -42,21 +42,24 @@ class Detections:
             if len(b) else np.zeros((0, 4), np.float32)
 
 
+END2END_GRAPHS = {"yolov10": "YOLOv10", "yolo26": "YOLO26"}   # detector_topology's graphs that carry a one-to-one head at model.23
+
+
 def resolve_end2end(graph: str, tensors: dict, end2end: bool | None) -> bool:
-    """Which head a detector of `graph` runs under `ultralytics.end2end` (null = the checkpoint's own): True = YOLOv10's one-to-one
-    head + top-300 cut, False = Detect + NMS. Raises for end2end: true with a family that has no such head, and for end2end: false
-    with a YOLOv10 file that no longer holds its one-to-many branches."""
+    """Which head a detector of `graph` runs under `ultralytics.end2end` (null = the checkpoint's own): True = YOLOv10's / YOLO26's
+    one-to-one head + top-300 cut, False = Detect + NMS. Raises for end2end: true with a family that has no such head, and for
+    end2end: false with a YOLOv10 / YOLO26 file that no longer holds its one-to-many branches."""
     from .weights import yolov10_has_one2many
 
-    if graph != "yolov10":
+    if graph not in END2END_GRAPHS:
         if end2end:
             raise ValueError(f"end2end: true needs a checkpoint with an end-to-end (one-to-one) head; this one is {graph}, of the implemented "
-                             f"families only YOLOv10 has one (leave end2end empty)")
+                             f"families only YOLOv10 and YOLO26 have one (leave end2end empty)")
         return False
     if end2end is None or end2end:
         return True
     if not yolov10_has_one2many(tensors):
-        raise ValueError("end2end: false runs YOLOv10's one-to-many branches (model.23.cv2 / cv3) through NMS, but this file holds only the "
+        raise ValueError(f"end2end: false runs {END2END_GRAPHS[graph]}'s one-to-many branches (model.23.cv2 / cv3) through NMS, but this file holds only the "
                          "one-to-one head (a fused ultralytics export drops them; tools/convert_weights.py keeps them)")
     return False
 
@@ -66,9 +69,9 @@ class Detector:
                  conf: float = 0.25, iou: float = 0.7, max_det: int = 1000, classes=None,
                  agnostic_nms: bool = True, half: bool = False, rect: bool = False, max_batch: int = 1,
                  fp32_split: bool | None = None, obj_feats: bool = False, end2end: bool | None = None, ctx: _lib.Context | None = None):
-        """end2end (ultralytics.end2end, default.yaml:250): None = the checkpoint's own head -- YOLOv10's one-to-one head without NMS
-        (the 300 best (anchor, class) scores; iou / agnostic_nms are not read), Detect + NMS for every other family; False runs a
-        YOLOv10 file's one-to-many branches (cv2 / cv3) through Detect + NMS; True with another family raises.
+        """end2end (ultralytics.end2end, default.yaml:250): None = the checkpoint's own head -- YOLOv10's / YOLO26's one-to-one head
+        without NMS (the 300 best (anchor, class) scores; iou / agnostic_nms are not read), Detect + NMS for every other family; False
+        runs a YOLOv10 / YOLO26 file's one-to-many branches (cv2 / cv3) through Detect + NMS; True with another family raises.
         obj_feats: keep one appearance vector per box (Detections.feats; include/gtx.h gtx_det_config.obj_feats).
         half=False (the reference default, default.yaml:245) computes at fp32 grade: fp32 activations in HBM and
         either the exact-fp32 MFMA (fp32_split=False) or the split-f16x3 convolutions (fp32_split=True: hi + lo fp16
@@ -99,7 +102,7 @@ class Detector:
             tensors, self._layout = pad_yolov9_channels(tensors, scale)
         self.end2end = resolve_end2end(self.graph, tensors, end2end)
         if self.end2end and obj_feats:
-            raise NotImplementedError("with_reid: true, model: auto reads the Detect layer's inputs at the boxes NMS keeps; not implemented for YOLOv10's "
+            raise NotImplementedError(f"with_reid: true, model: auto reads the Detect layer's inputs at the boxes NMS keeps; not implemented for {END2END_GRAPHS[self.graph]}'s "
                                       "end-to-end head (a separate network works: `model: yolo11n-cls.safetensors`, or run the file with end2end: false)")
         nc = int(tensors[head + (".enc_score_head.weight" if self.rtdetr else ".one2one_cv3.0.2.weight" if self.end2end else ".cv3.0.2.weight")].shape[0])
         self.ctx = ctx or _lib.default_context()

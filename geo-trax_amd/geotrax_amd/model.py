@@ -125,11 +125,16 @@ class YOLO:
         self.is_rtdetr = graph in ("rtdetr-l", "yolov8-rtdetr")
         self.is_p2 = graph == "yolov8-p2"
         self.is_yolov10 = graph == "yolov10"
-        nc = int(self.tensors[head + (".enc_score_head.weight" if self.is_rtdetr else ".one2one_cv3.0.2.weight" if self.is_yolov10 else ".cv3.0.2.weight")].shape[0])
+        self.is_end2end = graph in ("yolov10", "yolo26")  # the families whose own head is the one-to-one pair at model.23
+        nc = int(self.tensors[head + (".enc_score_head.weight" if self.is_rtdetr else ".one2one_cv3.0.2.weight" if self.is_end2end else ".cv3.0.2.weight")].shape[0])
         if self.is_yolov10:                               # ultralytics names the file by its scale: yolov10n.yaml / yolov10s.yaml
             from .weights import check_yolov10
 
             graph += check_yolov10(self.tensors)
+        if graph == "yolo26":                             # yolo26n.yaml ... yolo26x.yaml
+            from .weights import check_yolo26
+
+            graph += check_yolo26(self.tensors)
         if graph == "yolov9":                             # yolov9t.yaml / yolov9s.yaml / yolov9m.yaml / yolov9c.yaml
             from .weights import check_yolov9
 
@@ -252,8 +257,8 @@ class YOLO:
         if self._obj_feats and self.is_rtdetr:
             raise NotImplementedError("with_reid: true, model: auto needs the YOLOv8 Detect layer's inputs; not implemented for RT-DETR "
                                       "(a separate network works: `model: yolo11n-cls.safetensors`)")
-        if self._obj_feats and self.is_yolov10 and kwargs.get("end2end") in (None, True):
-            raise NotImplementedError("with_reid: true, model: auto needs the boxes NMS keeps and the Detect layer's inputs; not implemented for YOLOv10's "
+        if self._obj_feats and self.is_end2end and kwargs.get("end2end") in (None, True):
+            raise NotImplementedError("with_reid: true, model: auto needs the boxes NMS keeps and the Detect layer's inputs; not implemented for YOLOv10's / YOLO26's "
                                       "end-to-end head (a separate network works: `model: yolo11n-cls.safetensors`)")
         frame = np.ascontiguousarray(source, dtype=np.uint8)
         d = self._detector(frame.shape[:2], kwargs).detect(frame)

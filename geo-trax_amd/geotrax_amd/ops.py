@@ -624,6 +624,20 @@ def head_boxes(levels, count, cand_anchor, ctx=None) -> np.ndarray:
     return box
 
 
+def head_boxes_r1(levels, count, cand_anchor, ctx=None) -> np.ndarray:
+    """head_boxes for a Detect layer with reg_max = 1 (yolo26.yaml): the levels' wb are [cb, 4] and bb [4], the four signed distances
+    in strides; boxes [n, cap, 4] = the cell centre -/+ them, times the stride (NaN where nothing was decoded)."""
+    ctx = ctx or _lib.default_context()
+    keep, dt, n, L, arr = head_levels(levels)
+    count, cand_anchor = _i32(count), _i32(cand_anchor)
+    cap = cand_anchor.shape[1]
+    assert count.shape == (n,) and cand_anchor.shape == (n, cap)
+    assert all(np.shape(lv["wb"]) == (int(lv["cb"]), 4) and np.shape(lv["bb"]) == (4,) for lv in levels)
+    box = np.zeros((n, cap, 4), np.float32)
+    check(ctx.lib.gtx_op_head_boxes_r1(ctx.handle, dt, n, L, arr, cap, ptr(count), ptr(cand_anchor), ptr(box)))
+    return box
+
+
 def _rows_io(n, max_det, out_rows, out_n, out_anchor):
     rows = np.zeros((n, max_det, 6), np.float32) if out_rows is None else np.array(out_rows, dtype=np.float32, order="C")
     on = np.full(n, -1, np.int32) if out_n is None else np.array(out_n, dtype=np.int32, order="C")

@@ -179,6 +179,12 @@ YOLOV10_YAML = [                                           # v10/yolov10s.yaml; 
     (-1, 3, "C2fCIB", (1024, True, True)),                 # 22
     ((16, 19, 22), 1, "v10Detect", ("nc",)),               # 23: YOLO11's Detect layers twice (cv2 / cv3, one2one_cv2 / one2one_cv3)
 ]
+YOLO26_YAML = YOLO11_YAML[:9] + [                          # 26/yolo26.yaml (end2end: True, reg_max: 1): yolo11.yaml's rows but for 9, 22 and 23
+    (-1, 1, "SPPF", (1024, 5, 3, True)),                   # 9: (c2, k, n, shortcut): cv1 without activation, the input added to cv2's output
+] + YOLO11_YAML[10:22] + [
+    (-1, 1, "C3k2", (1024, True, 0.5, True)),              # 22: (c2, c3k, e, attn): every m.{k} is Sequential(Bottleneck, PSABlock)
+    ((16, 19, 22), 1, "Detect26", ("nc",)),                # 23: Detect with reg_max = 1 (a 4-output box 1x1) and a one-to-one copy of both branches
+]
 YOLOV8_CLS_YAML = _V8_BACKBONE + [(-1, 1, "Classify", ("nc",))]
 YOLO11_CLS_YAML = YOLO11_YAML[:9] + [                      # model.0-8 of yolo11.yaml; no SPPF
     (-1, 2, "C2PSA", (1024,)),                             # 9
@@ -208,14 +214,26 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False) -> list[tuple[
         conv(p + ".cv1.conv", c, int(c * e), 3)
         conv(p + ".cv2.conv", int(c * e), c, 3)
 
-    def c2f(pfx, cin, cout, n, c3k=None, e=0.5, cib=None):
+    def psablock(m, c):
+        """PSABlock(c, attn_ratio 0.5, num_heads = c / 64): key_dim 32, head_dim 64"""
+        conv(m + ".attn.qkv.conv", c, c + 2 * (c // 64) * 32, 1, act=False)
+        conv(m + ".attn.proj.conv", c, c, 1, act=False)
+        dwconv(m + ".attn.pe.conv", c, False)
+        conv(m + ".ffn.0.conv", c, 2 * c, 1)
+        conv(m + ".ffn.1.conv", 2 * c, c, 1, act=False)
+
+    def c2f(pfx, cin, cout, n, c3k=None, e=0.5, cib=None, attn=False):
         """C2f (c3k None: full-width Bottlenecks) or C3k2 (half-width Bottlenecks, or C3k blocks of two Bottlenecks when c3k) or
-        C2fCIB (cib = lk: CIB blocks of full hidden width; lk: the middle depthwise layer is the fused RepVGGDW, one 7x7)."""
+        C2fCIB (cib = lk: CIB blocks of full hidden width; lk: the middle depthwise layer is the fused RepVGGDW, one 7x7) or
+        yolo26.yaml's C3k2 with attn: every m.{k} is Sequential(Bottleneck(c, c, e = 0.5), PSABlock(c))."""
         c = int(cout * e)
         conv(f"{pfx}.cv1.conv", cin, 2 * c, 1)
         for k in range(n):
             m = f"{pfx}.m.{k}"
-            if cib is not None:                            # CIB(c, c, shortcut, e=1.0, lk): dw3 -> 1x1 c->2c -> dw3 / dw7 -> 1x1 2c->c -> dw3, SiLU after each
+            if attn:
+                bottleneck(m + ".0", c, 0.5)
+                psablock(m + ".1", c)
+            elif cib is not None:                            # CIB(c, c, shortcut, e=1.0, lk): dw3 -> 1x1 c->2c -> dw3 / dw7 -> 1x1 2c->c -> dw3, SiLU after each
                 dwconv(m + ".cv1.0.conv", c, True)
                 conv(m + ".cv1.1.conv", c, 2 * c, 1)
                 dwconv(m + ".cv1.2.conv", 2 * c, True, 7 if cib else 3)
@@ -241,13 +259,13 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False) -> list[tuple[
         for k in range(n):
             bottleneck(f"{p}.m.{k}", h, 1.0)
 
-    def detect(d, chans, box="cv2", cls="cv3"):
-        cb = max(16, chans[0] // 4, 64)
+    def detect(d, chans, box="cv2", cls="cv3", reg_max=16):
+        cb = max(16, chans[0] // 4, YOLO26_BOX_FLOOR if reg_max == 1 else 4 * reg_max)
         cc = max(chans[0], min(nc, 100))
         for l, cin in enumerate(chans):
             conv(f"{d}.{box}.{l}.0.conv", cin, cb, 3)
             conv(f"{d}.{box}.{l}.1.conv", cb, cb, 3)
-            specs.append((f"{d}.{box}.{l}.2", (64, cb, 1, 1), False))
+            specs.append((f"{d}.{box}.{l}.2", (4 * reg_max, cb, 1, 1), False))
             if dw_cls:
                 dwconv(f"{d}.{cls}.{l}.0.0.conv", cin, True)
                 conv(f"{d}.{cls}.{l}.0.1.conv", cin, cc, 1)
@@ -269,22 +287,17 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False) -> list[tuple[
             c2f(pfx, cin, out[i], n)
         elif mod == "C3k2":
             out.append(ch(args[0]))
-            c2f(pfx, cin, out[i], n, c3k_all or args[1], *args[2:])
+            c2f(pfx, cin, out[i], n, c3k_all or args[1], *args[2:3], attn=len(args) > 3 and bool(args[3]))
         elif mod == "SPPF":
             out.append(ch(args[0]))
-            conv(pfx + ".cv1.conv", cin, cin // 2, 1)
+            conv(pfx + ".cv1.conv", cin, cin // 2, 1, act=not (len(args) > 3 and args[3]))   # yolo26.yaml's SPPF(c2, k, n, shortcut): a linear cv1
             conv(pfx + ".cv2.conv", cin // 2 * 4, out[i], 1)
         elif mod == "C2PSA":                               # heads = c / 64, key_dim 32, head_dim 64
             out.append(ch(args[0]))
             c = cin // 2
             conv(pfx + ".cv1.conv", cin, 2 * c, 1)
             for k in range(n):
-                m = f"{pfx}.m.{k}"
-                conv(m + ".attn.qkv.conv", c, c + 2 * (c // 64) * 32, 1, act=False)
-                conv(m + ".attn.proj.conv", c, c, 1, act=False)
-                dwconv(m + ".attn.pe.conv", c, False)
-                conv(m + ".ffn.0.conv", c, 2 * c, 1)
-                conv(m + ".ffn.1.conv", 2 * c, c, 1, act=False)
+                psablock(f"{pfx}.m.{k}", c)
             conv(pfx + ".cv2.conv", 2 * c, out[i], 1)
         elif mod == "C2fCIB":
             out.append(ch(args[0]))
@@ -338,6 +351,10 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False) -> list[tuple[
             out.append(0)
             detect(pfx, src)
             detect(pfx, src, "one2one_cv2", "one2one_cv3")
+        elif mod == "Detect26":                            # reg_max = 1; the one-to-many pair, then its one-to-one copy
+            out.append(0)
+            detect(pfx, src, reg_max=1)
+            detect(pfx, src, "one2one_cv2", "one2one_cv3", reg_max=1)
         elif mod == "Classify":
             out.append(nc)
             conv(pfx + ".conv.conv", cin, 1280, 1)
@@ -404,7 +421,10 @@ def _draw_yolov8(rng, specs, cls_bias: float = -4.0, gain: float = 1.7, box_deca
             b = b + cls_bias + float(level_bias[int(last.group(2))])
         if last and last.group(1) == "2":
             t[name + ".weight"] *= np.float32(box_weight_scale)
-            b = b - np.repeat(decay, 16) * np.tile(np.arange(16), 4)
+            if shape[0] == 4:                              # reg_max = 1 (YOLO26): the four outputs are the distances themselves, in strides
+                b = b + np.asarray(YOLO26_BOX_BIAS)
+            else:
+                b = b - np.repeat(decay, 16) * np.tile(np.arange(16), 4)
         t[name + ".bias"] = b.astype(np.float32)
     return t
 
@@ -458,7 +478,7 @@ def has_yolo11_blocks(tensors: dict) -> bool:
 
 def check_yolo11(tensors: dict) -> None:
     """Raises NotImplementedError unless the names and shapes are those of a fused yolo11.yaml detect model. Other graphs built from
-    the same blocks (YOLO12's A2C2f, YOLO26's end-to-end Detect, yolo11-cls with C2PSA at model.9 -- the ReID embedder's, is_yolo11_cls --, -seg / -obb / -pose heads with a
+    the same blocks (YOLO12's A2C2f, yolo11-cls with C2PSA at model.9 -- the ReID embedder's, is_yolo11_cls --, -seg / -obb / -pose heads with a
     cv4 or proto branch) are never built into the wrong network."""
     no = NotImplementedError(f"checkpoint with attention / depthwise-Detect blocks in another arrangement than yolo11.yaml's: of that "
                              f"family only {YOLO11_TOPOLOGY} is implemented")
@@ -609,6 +629,116 @@ def synthetic_yolov10(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: fl
     yolov10_layer_specs). Both head pairs are emitted, cv2 / cv3 first, each with draws of its own, so the two heads detect
     different things; the knobs shape both alike."""
     return _draw_yolov8(np.random.default_rng(seed), yolov10_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias, box_weight_scale)
+
+# --------------------------------------------------------------------------- YOLO26 (cfg/models/26/yolo26.yaml)
+# What `YOLO("yolo26s.pt")` fine-tunes to: yolo11.yaml's rows with three changes. SPPF = model.9 has a cv1 WITHOUT activation and adds
+# its input to cv2's output (after cv2's SiLU); the last neck block, model.22, is a C3k2 whose m.{k} are Sequential(Bottleneck, PSABlock)
+# (`model.22.m.0.0.cv1.conv`, `model.22.m.0.1.attn.qkv.conv`); Detect = model.23 has reg_max = 1 -- the box branch ends in a 1x1 to FOUR
+# channels, the signed distances l, t, r, b in strides, no DFL -- and, like v10Detect, carries one2one_cv2 / one2one_cv3 next to cv2 /
+# cv3 and ends in the same two-stage top-300 cut. Restated from memory of ultralytics' public source; not checked against the package
+# (it is not installed). The doubts are listed in tests/yolo26_ref.py; the constants below and their twins in csrc/yolo_tables.hpp hold them.
+
+YOLO26_TOPOLOGY = ("yolo26 detect (yolo26{n,s,m,l,x}: yolo11.yaml's rows with SPPF(shortcut) = model.9, C3k2(attn) = model.22 and Detect = "
+                   "model.23 on model.16 / 19 / 22 with reg_max = 1 and a one2one_cv2 / one2one_cv3 head)")
+YOLO26_BOX_FLOOR = 64        # doubt: Detect's box-branch width is max(16, ch[0] // 4, this). Every other family here has 4 * reg_max = 64 as the third
+                             # term; with reg_max = 1 the package may give 16 / 32 channels at scales n / s. Taken as 64; such a file is refused by shape.
+YOLO26_BOX_BIAS = (2.0, 2.5, 2.0, -0.5)   # synthetic_yolo26: the means of l, t, r, b (strides): boxes four strides wide and two high whose lower
+                             # side lies ABOVE the cell centre -- a negative distance at every anchor of a calm seeded stack
+
+
+def is_yolo26(tensors: dict) -> bool:
+    """True when the names hold what only a YOLO26 file has, all of: YOLO11's blocks, the attention inside model.22's C3k2
+    (`model.22.m.0.1.attn.qkv`), a last box convolution of 4 rows (reg_max = 1) and a one-to-one class branch. Which graph it is, and
+    whether this build runs it: check_yolo26()."""
+    if not has_yolo11_blocks(tensors) or "model.22.m.0.1.attn.qkv.conv.weight" not in tensors:
+        return False
+    w = tensors.get("model.23.one2one_cv2.0.2.weight")
+    if w is None:
+        w = tensors.get("model.23.cv2.0.2.weight")
+    return w is not None and np.ndim(w) == 4 and np.shape(w)[0] == 4 and any(k.startswith("model.23.one2one_cv3.") for k in tensors)
+
+
+def _yolo26_marks(tensors: dict) -> bool:
+    """A file with YOLO11's blocks and one of YOLO26's own marks, the attention inside model.22 or a 4-row last box convolution, but
+    not all that is_yolo26() demands: check_yolo26() refuses it with YOLO26's message. A YOLO11 file with stray one2one_* tensors has
+    neither mark and goes to check_yolo11()."""
+    if not has_yolo11_blocks(tensors):
+        return False
+    rows = [np.shape(tensors[k])[0] for k in ("model.23.one2one_cv2.0.2.weight", "model.23.cv2.0.2.weight") if k in tensors and np.ndim(tensors[k]) == 4]
+    return "model.22.m.0.1.attn.qkv.conv.weight" in tensors or 4 in rows
+
+
+def check_yolo26(tensors: dict) -> str:
+    """The scale ("n" / "s" / "m" / "l" / "x") of a fused yolo26.yaml detect model; raises NotImplementedError for every other
+    arrangement of its blocks (a cv4 / proto branch, attention elsewhere, Detect elsewhere, reg_max other than 1, anything past
+    model.23, another width). Strict like check_yolov10(): the table is rebuilt from what the tensors tell (c3k or not per C3k2) and
+    every shape is compared. The one-to-many pair cv2 / cv3 may be missing as a whole (ultralytics' fuse() drops it)."""
+    no = NotImplementedError(f"checkpoint with YOLO26's blocks (attention inside model.22's C3k2, a 4-output box branch, a one-to-one head) in "
+                             f"another arrangement than yolo26.yaml's: of that family only {YOLO26_TOPOLOGY} is implemented")
+    shape = lambda n: tuple(np.shape(tensors[n])) if n in tensors else None
+    c0, c1 = shape("model.0.conv.weight"), shape("model.1.conv.weight")
+    nc_w = shape("model.23.one2one_cv3.0.2.weight")
+    if c0 is None or c1 is None or nc_w is None:
+        raise no
+    for k in ("model.23.one2one_cv2.0.2.weight", "model.23.cv2.0.2.weight"):
+        if shape(k) is not None and shape(k)[0] != 4:
+            raise NotImplementedError(f"{k} has {shape(k)[0]} rows (reg_max = {shape(k)[0] // 4}) in a graph with YOLO26's attention inside model.22: "
+                                      f"only reg_max = 1, a 4-row box convolution, is implemented there ({YOLO26_TOPOLOGY})")
+    # model.0's width tells n / s / x apart; m and l share every width and differ in the repeats (model.2: 1 or 2 blocks)
+    scale = {16: "n", 32: "s", 96: "x"}.get(c0[0]) or ({64: "l" if "model.2.m.1.cv1.conv.weight" in tensors else "m"}.get(c0[0]))
+    if scale is None:
+        raise no
+    layer = lambda k: int(k.split(".")[1]) if k.startswith("model.") and k.split(".")[1].isdigit() else -1
+    table = []
+    for i, (frm, n, mod, args) in enumerate(YOLO26_YAML):
+        if mod == "C3k2" and len(args) < 4:                # c3k or not: off the tensors, not off a remembered flag
+            table.append((frm, n, mod, (args[0], f"model.{i}.m.0.cv3.conv.weight" in tensors) + tuple(args[2:])))
+        else:
+            table.append((frm, n, mod, args))
+    depth, width, maxc = YOLO11_SCALES[scale]
+    n22 = 0                                                # model.22's repeats (the yaml writes 1, which no scale multiplies): off the tensors, 1 or 2
+    while f"model.22.m.{n22}.0.cv1.conv.weight" in tensors:
+        n22 += 1
+    if n22 not in (1, 2):
+        raise no
+    want = _parse_model(table, nc_w[0], lambda c: _make_divisible(min(c, maxc) * width),
+                        lambda i, n: n22 if i == 22 else (max(round(n * depth), 1) if n > 1 else n), dw_cls=True)
+    many = [n for n, _, _ in want if n.startswith(("model.23.cv2.", "model.23.cv3."))]
+    have_many = [n + ".weight" in tensors for n in many]
+    if any(have_many) and not all(have_many):
+        raise no
+    names = set()
+    for name, shp, _ in want:
+        if name in many and not have_many[0]:
+            continue
+        names.add(name)
+        if shape(name + ".weight") != shp:
+            raise no
+    for k in tensors:
+        i = layer(k)
+        if i < 0:
+            continue
+        if i > 23 or (".attn." in k and i not in (10, 22)):
+            raise no
+        if i == 23 and k.split(".")[2] == "dfl":
+            continue
+        if k.endswith(".weight") and k[: -len(".weight")] not in names:
+            raise no
+    return scale
+
+
+def yolo26_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
+    """(tensor name, OIHW shape, has_act) for every conv of a fused YOLO26 detect model, both head pairs included (the last box
+    convolutions: (4, cb, 1, 1))."""
+    return _scaled_specs(YOLO26_YAML, YOLO11_SCALES, scale, nc, c3k_all=scale in "mlx", dw_cls=True)
+
+
+def synthetic_yolo26(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0, gain: float = 1.7,
+                     box_weight_scale: float = 0.3) -> dict[str, np.ndarray]:
+    """Seeded random fused weights of the YOLO26 architecture, drawn like synthetic_yolov10's (same knobs, the draws in the order of
+    yolo26_layer_specs; both head pairs, each with draws of its own). The last box convolutions give the four distances directly:
+    damped weights (box_weight_scale) around the biases YOLO26_BOX_BIAS, one of which is negative."""
+    return _draw_yolov8(np.random.default_rng(seed), yolo26_layer_specs(scale, nc), cls_bias, gain, 0.3, (0.0, 0.0, 0.0), box_weight_scale)
 
 # --------------------------------------------------------------------------- YOLOv9 (cfg/models/v9/yolov9{t,s,m,c}.yaml)
 # The GELAN networks: ELAN1 / RepNCSPELAN4 blocks (cv1 1x1 -> two chunks; cv2 and cv3 are Sequential(RepCSP, Conv3x3) -- plain Conv3x3
@@ -798,13 +928,13 @@ def pad_yolov9_channels(tensors: dict, scale: str) -> tuple[dict, dict]:
 
 
 def detector_meta(tensors: dict) -> dict | None:
-    """The optional `detector.meta` tensor tools/convert_weights.py writes for a YOLOv10 file: [family 10, one-to-many pair kept,
+    """The optional `detector.meta` tensor tools/convert_weights.py writes for a YOLOv10 / YOLO26 file: [family 10 / 26, one-to-many pair kept,
     end-to-end head, the head's row count]; None when the file has none."""
     m = tensors.get("detector.meta")
     if m is None or np.size(m) < 4:
         return None
     m = np.asarray(m).ravel()
-    return dict(family={10: "yolov10"}.get(int(m[0]), str(int(m[0]))), one2many=bool(m[1]), end2end=bool(m[2]), max_det=int(m[3]))
+    return dict(family={10: "yolov10", 26: "yolo26"}.get(int(m[0]), str(int(m[0]))), one2many=bool(m[1]), end2end=bool(m[2]), max_det=int(m[3]))
 
 
 def fold_repvggdw(t: dict[str, np.ndarray]) -> dict[str, np.ndarray]:
@@ -864,17 +994,20 @@ RTDETR_TOPOLOGIES = ("rtdetr-l (HGNetv2 + AIFI + CCFM, RTDETRDecoder = model.28)
 
 def detector_topology(tensors: dict) -> tuple[str, str]:
     """(graph, head prefix) of a detector checkpoint, read off the tensor names the way the reference reads its model yaml:
-    ("yolov8", "model.22"), ("yolov8-p2", "model.28"), ("yolo11", "model.23"), ("yolov10", "model.23"), ("yolov9", "model.22"), ("rtdetr-l", "model.28") or
+    ("yolov8", "model.22"), ("yolov8-p2", "model.28"), ("yolo11", "model.23"), ("yolov10", "model.23"), ("yolo26", "model.23"), ("yolov9", "model.22"), ("rtdetr-l", "model.28") or
     ("yolov8-rtdetr", "model.22").
     An RT-DETR layout other than those two (rtdetr-x with its decoder at model.32, ResNet backbones, ...) raises NotImplementedError,
-    and so does a file with YOLO11's or YOLOv10's blocks (attention, a depthwise Detect class branch, SCDown + a one-to-one head) in
-    another arrangement than their yaml's."""
+    and so does a file with YOLO11's, YOLOv10's or YOLO26's blocks (attention, a depthwise Detect class branch, SCDown + a one-to-one head,
+    attention inside model.22 + a 4-output box branch) in another arrangement than their yaml's."""
     if not is_rtdetr(tensors):
         if is_yolov10(tensors):
             check_yolov10(tensors)                         # raises for another arrangement, and for the scales that are not implemented
             return "yolov10", "model.23"
+        if is_yolo26(tensors) or _yolo26_marks(tensors):
+            check_yolo26(tensors)                          # raises for another arrangement, reg_max other than 1, -seg / -obb / -pose heads
+            return "yolo26", "model.23"
         if has_yolo11_blocks(tensors):
-            check_yolo11(tensors)                          # raises for YOLO12 / YOLO26 / yolo11-cls, -seg, -obb, -pose ...
+            check_yolo11(tensors)                          # raises for YOLO12 / yolo11-cls, -seg, -obb, -pose ...
             return "yolo11", "model.23"
         if _has_gelan(tensors):                            # is_yolov9, or GELAN blocks without model.9.cv5: yolov9e, which check_yolov9 refuses by name
             check_yolov9(tensors)

@@ -85,7 +85,10 @@ extern "C" {
  *     added: the same, the number stays.
  *     gtx_plot_canvas_{create, destroy, size, draw, read, dptr, stats}, gtx_op_plot_draw and gtx_op_plot_reduce (the plot stage's
  *     trajectory maps: an image reduced into a canvas in HBM, strokes and discs blended into it) added: new entry points and an
- *     opaque handle only, so the number stays. */
+ *     opaque handle only, so the number stays.
+ *     gtx_op_head_boxes_r1 added and arch 0 also takes YOLO26 tensors (yolo26.yaml: SPPF with a residual, attention inside model.22, a
+ *     Detect of reg_max = 1 read off its last box convolution's four rows, the one-to-one head under gtx_det_config.end2end): a new
+ *     entry point only, so the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -546,6 +549,10 @@ int gtx_op_head_gate(gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx_hea
  * them: all bits set). cb <= 128 and no level's cb above level 0's. */
 int gtx_op_head_boxes(gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx_head_level* lv, int cap, const int* count, const int* cand_anchor,
                       float* cand_box);
+/* The same for a Detect layer with reg_max = 1 (yolo26.yaml): wb [cb][4] and bb [4], the four outputs are the signed distances l, t,
+ * r, b from the cell centre in strides; cand_box = ((x + 0.5 - l), (y + 0.5 - t), (x + 0.5 + r), (y + 0.5 + b)) * stride, no clamp. */
+int gtx_op_head_boxes_r1(gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx_head_level* lv, int cap, const int* count, const int* cand_anchor,
+                         float* cand_box);
 /* NMS of given candidates (count [n], cand_* [n][cap]; anchors in [0, 2^20)): order score descending then anchor ascending, greedy
  * suppression at IoU > iou_thr (boxes offset by 7680 * class unless agnostic), the max_nms best only, max_det rows, scale_boxes +
  * clip to the frame. which: 0 both paths, 1 the single-workgroup kernel only (an image beyond 4096 candidates or max_det beyond 2048

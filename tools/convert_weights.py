@@ -27,6 +27,11 @@ branches (`model.23.cv2 / cv3`): convert_state_dict() folds every Conv + BN pair
 one2one_cv3 -- `end2end: false` runs them through NMS -- and writes `detector.meta` = [family 10, one-to-many kept, end-to-end head,
 the head's 300].
 
+A YOLO26 detect checkpoint (yolo26{n,s,m,l,x}.yaml: `model.22.m.0.1.attn.qkv.*`, 4-row `model.23.*cv2.<l>.2`) takes the same branch: every
+Conv + BN pair is folded under its own name (model.22's `m.<k>.0.cv1` Bottleneck and `m.<k>.1.attn.*` / `ffn.*` PSABlock convolutions
+included; it has no RepVGGDW), cv2 / cv3 stay next to one2one_cv2 / one2one_cv3, and `detector.meta` = [family 26, one-to-many kept,
+end-to-end head, the head's 300].
+
 A YOLOv9 detect checkpoint (yolov9{t,s,m,c}.yaml) goes through `model.fuse()` like YOLOv8: RepConv.fuse_convs leaves one 3x3 under
 `...cv2.0.m.<k>.cv1.conv.*`, and the fused state_dict ends in `model.22.cv3.2.2.bias`. Where a version leaves a RepConv's two branches
 (`...m.<k>.cv1.conv1` / `conv2`) unfused, geotrax_amd.weights.load_weights folds each branch's BN first and then sums the 1x1 into the
@@ -42,7 +47,7 @@ import yaml
 
 
 def convert_state_dict(sd: dict) -> dict:
-    """An unfused YOLOv10 state_dict (numpy arrays under ultralytics' names) -> the flat fused tensors the library reads, plus
+    """An unfused YOLOv10 or YOLO26 state_dict (numpy arrays under ultralytics' names) -> the flat fused tensors the library reads, plus
     `detector.meta` (geotrax_amd.weights.detector_meta). Needs no ultralytics."""
     import numpy as np
 
@@ -54,9 +59,9 @@ def convert_state_dict(sd: dict) -> dict:
     t = {k: np.asarray(v, np.float32) for k, v in sd.items() if "dfl" not in k and "num_batches_tracked" not in k}
     t = fold_repvggdw(fold_bn(t))
     graph, _ = detector_topology(t)
-    if graph != "yolov10":
-        raise ValueError(f"convert_state_dict folds YOLOv10 checkpoints; this one is {graph}")
-    t["detector.meta"] = np.asarray([10, float(yolov10_has_one2many(t)), 1, V10_MAX_DET], np.float32)
+    if graph not in ("yolov10", "yolo26"):
+        raise ValueError(f"convert_state_dict folds YOLOv10 and YOLO26 checkpoints; this one is {graph}")
+    t["detector.meta"] = np.asarray([10 if graph == "yolov10" else 26, float(yolov10_has_one2many(t)), 1, V10_MAX_DET], np.float32)
     return t
 
 
@@ -71,13 +76,13 @@ def main():
         from ultralytics import RTDETR
 
         yolo = RTDETR(str(src))                       # what the reference itself does (extract.py:223-225)
-    if any(".one2one_cv2." in k for k in yolo.model.state_dict()):   # YOLOv10: folded here, so that cv2 / cv3 survive
+    if any(".one2one_cv2." in k for k in yolo.model.state_dict()):   # YOLOv10 / YOLO26: folded here, so that cv2 / cv3 survive
         from safetensors.numpy import save_file as save_np
 
         sd = convert_state_dict({k: v.detach().float().numpy() for k, v in yolo.model.float().eval().state_dict().items() if v.dtype.is_floating_point})
         save_np(sd, str(dst))
         dst.with_suffix(".names.yaml").write_text(yaml.safe_dump({int(k): str(v) for k, v in yolo.names.items()}))
-        print(f"wrote {dst} ({len(sd)} tensors, YOLOv10 with both head pairs) and {dst.with_suffix('.names.yaml')}")
+        print(f"wrote {dst} ({len(sd)} tensors, both head pairs) and {dst.with_suffix('.names.yaml')}")
         return
     net = yolo.model.float().fuse().eval()
     sd = {k: v.detach().float().contiguous() for k, v in net.state_dict().items()
