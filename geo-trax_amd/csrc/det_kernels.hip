@@ -843,9 +843,10 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const uint4* __restrict
   y[((size_t)(n * ho + oy) * wo + ox) * out_vstride + out_voff + v] = val;
 }
 
-void launch_upsample2x(int dtype, const void* x, int n, int h, int w, int c, int in_cstride,
+void launch_upsample2x(size_t es, const void* x, int n, int h, int w, int c, int in_cstride,
                        int in_coff, void* y, int out_cstride, int out_coff, hipStream_t s) {
-  const int vn = dtype == DT_F16 ? 8 : 4;
+  GTX_CHECK(es == 2 || es == 4, "upsample: %zu bytes per element", es);
+  const int vn = 16 / (int)es;
   GTX_CHECK(c % vn == 0 && in_cstride % vn == 0 && in_coff % vn == 0 && out_cstride % vn == 0 &&
                 out_coff % vn == 0, "upsample: channel layout must be 16-byte aligned");
   const long work = (long)4 * h * w * (c / vn);

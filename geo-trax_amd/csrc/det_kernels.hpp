@@ -36,7 +36,10 @@ std::vector<uint16_t> pack_stem_weights_split(const float* w27, int c0, float* a
 // SPPF pools: channels [0,c) -> 5x5 / 9x9 / 13x13 clipped-window maxima at [c,2c) [2c,3c) [3c,4c).
 void launch_sppf_pool(int dtype, void* x, int n, int h, int w, int c, hipStream_t s);
 
-void launch_upsample2x(int dtype, const void* x, int n, int h, int w, int c, int in_cstride,
+// Nearest 2x upsampling of channels [in_coff, in_coff + c) of x [n][h][w][in_cstride] into y [n][2h][2w][out_cstride] at out_coff: a raw
+// copy of 16-byte groups, whatever the values mean. es: bytes per element as the maps are stored (2: fp16; 4: fp32 and the pair
+// format) -- the caller says it, no format code is interpreted here; channel counts, strides and offsets are whole 16-byte groups.
+void launch_upsample2x(size_t es, const void* x, int n, int h, int w, int c, int in_cstride,
                        int in_coff, void* y, int out_cstride, int out_coff, hipStream_t s);
 
 // ---- head decode + NMS ----

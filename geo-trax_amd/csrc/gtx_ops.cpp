@@ -352,7 +352,7 @@ int gtx_op_upsample2x(gtx_ctx* ctx, int dtype, int n, int h, int w, int c, const
     const size_t xb = (size_t)n * h * w * in_cstride * es, yb = (size_t)n * 4 * h * w * out_cstride * es;
     gtx::DevBuf dx, dy;
     upload(dx, x, xb); upload(dy, y, yb);
-    gtx::launch_upsample2x(dtype, dx.p, n, h, w, c, in_cstride, in_coff, dy.p, out_cstride, out_coff, ctx->stream);
+    gtx::launch_upsample2x(es, dx.p, n, h, w, c, in_cstride, in_coff, dy.p, out_cstride, out_coff, ctx->stream);
     GTX_HIP(hipStreamSynchronize(ctx->stream));
     download(y, dy, yb);
   });
@@ -766,8 +766,7 @@ int gtx_op_rt_upsample2x(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int
     const size_t xb = rt_map_bytes(dtype, n_alloc, h, w, in_cstride), yb = rt_map_bytes(dtype, n_alloc, 2 * h, 2 * w, out_cstride);
     gtx::DevBuf dx, dy;
     upload_fmt(dx, dtype, x, xb); upload_fmt(dy, dtype, y, yb);
-    const gtx::RtMap i{dx.p, h, w, in_cstride, in_coff, c}, o{dy.p, 2 * h, 2 * w, out_cstride, out_coff, c};
-    gtx::launch_rt_upsample2x(dtype, i, o, n, ctx->stream);
+    gtx::launch_upsample2x(gtx::dtype_size(dtype), dx.p, n, h, w, c, in_cstride, in_coff, dy.p, out_cstride, out_coff, ctx->stream);
     GTX_HIP(hipStreamSynchronize(ctx->stream));
     download_fmt(y, dtype, dy, yb);
   });

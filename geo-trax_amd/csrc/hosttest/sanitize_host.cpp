@@ -173,7 +173,8 @@ bool run_writers(unsigned seed) {
 }
 
 // The YOLO trunks' layer tables are walkable (yolov10.yaml's and yolo26.yaml's among them), a broken one is caught at its row, and the depthwise
-// weight transposition touches exactly its taps x channels values (odd sizes: 7x7 on 24 channels, 3x3 on 8)
+// weight transposition touches exactly its taps x channels values (odd sizes: 7x7 on 24 channels, 3x3 on 8, 5x5 on 40); the depthwise and
+// attention launchers' kernel names follow their dispatch predicates
 static bool run_trunk_tables() {
   using namespace gtx;
   using namespace gtx::tables;
@@ -195,7 +196,20 @@ static bool run_trunk_tables() {
   bad.assign(kYolo10, kYolo10 + 24);
   bad[21].from[1] = 6;                                // model.6 in two Concats
   if (trunk_table_error(bad.data(), 24) != 21) return false;
-  const int sizes[2][2] = {{24, 49}, {8, 9}};
+  // the kernel names the graph builders label their ops with: <3>, <5> and <7> forms, tiled exactly at stride 1 on whole 32-channel groups
+  for (int k : {3, 5, 7})
+    for (int stride : {1, 2})
+      for (int c : {8, 24, 32, 40, 64, 96}) {
+        const bool tiled = stride == 1 && c % 32 == 0;
+        const std::string want = std::string(tiled ? "rt_dwconv_tile_kernel<" : "rt_dwconv_kernel<") + std::to_string(k) + ">";
+        if (rt_dwconv_tiled(stride, c) != tiled || want != rt_dwconv_kernel_name(k, stride, c)) return false;
+      }
+  for (int h = 1; h <= 12; ++h)
+    for (int w = 1; w <= 12; ++w) {
+      if (psa_attention_small(h, w) != (h * w <= 64)) return false;
+      if (std::string(psa_attention_kernel_name(h, w)) != (psa_attention_small(h, w) ? "psa_attn_small_kernel" : "psa_attn_kernel")) return false;
+    }
+  const int sizes[3][2] = {{24, 49}, {8, 9}, {40, 25}};   // {40, 25}: rtdetr-l's LightConv 5x5
   for (const auto& ck : sizes) {
     const int c = ck[0], taps = ck[1];
     std::vector<float> w((size_t)c * taps);

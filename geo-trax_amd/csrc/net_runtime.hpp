@@ -12,6 +12,7 @@
 #include "common.hpp"
 #include "conv_igemm.hpp"
 #include "det_kernels.hpp"
+#include "rtdetr_kernels.hpp"
 
 struct gtx_ctx {
   int device = 0;
@@ -43,6 +44,8 @@ struct View {
     v.c = cnt;
     return v;
   }
+  // what the map-side kernels take by value (rtdetr_kernels.hpp); the one place that orders the fields
+  RtMap map() const { return RtMap{ptr, h, w, cstride, coff, c}; }
 };
 
 // What the timing helpers read of an op of a forward graph. flops / bytes are algorithmic (2 * MAC; inputs read once + outputs

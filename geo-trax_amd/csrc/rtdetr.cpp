@@ -8,10 +8,6 @@
 
 namespace gtx {
 
-namespace {
-RtMap rt_map(const View& v) { return RtMap{v.ptr, v.h, v.w, v.cstride, v.coff, v.c}; }
-}  // namespace
-
 // half: fp16 maps and weights on the fp16 MFMA convolutions (fp32 accumulate); the token side (AIFI, the decoder's queries) stays fp32.
 // rtdetr-l allocates every map at 4 bytes per element; the YOLOv8 trunk's maps take its activation type's size (build_graph).
 RtDetr::RtDetr(gtx_ctx* ctx, const gtx_det_config& cfg)
@@ -45,7 +41,16 @@ View RtDetr::conv_raw(const std::string& name, const std::vector<float>& w, int 
   GTX_CHECK((int)w.size() == cout * cin * ks * ks, "%s: weight size", name.c_str());
   ConvArgs a;
   a.stride = stride; a.act = act; a.out_slice = out_slice; a.residual = residual; a.plain_out = plain_out;
-  return emit_conv(ops_, name, w.data(), cout, cin, ks, bias_host, x, a);
+  const View out = emit_conv(trunk_ops_, name, w.data(), cout, cin, ks, bias_host, x, a);
+  adopt_map_ops();
+  return out;
+}
+
+void RtDetr::adopt_map_ops(size_t first, size_t at) {
+  std::vector<Op> m(trunk_ops_.size() - first);
+  for (size_t i = 0; i < m.size(); ++i) m[i].map = trunk_ops_[first + i];
+  ops_.insert(ops_.begin() + (long)at, m.begin(), m.end());
+  trunk_ops_.resize(first);
 }
 
 View RtDetr::conv(const std::string& name, const View& x, int stride, int act, const View* out_slice, const View* residual) {
@@ -67,38 +72,6 @@ View RtDetr::conv2x2(const std::string& name, const View& x, const View* out_sli
       for (int dy = 0; dy < 2; ++dy)
         for (int dx = 0; dx < 2; ++dx) w3[(((size_t)o * cin + i) * 3 + 1 + dy) * 3 + 1 + dx] = w.data[(((size_t)o * cin + i) * 2 + dy) * 2 + dx];
   return conv_raw(name, w3, cout, cin, 3, bias_of(name, cout), x, 1, 2, out_slice, nullptr);
-}
-
-void RtDetr::dwconv(const std::string& name, const View& x, const View& out, int stride, int act) {
-  const HostTensor& w = tensor(name + ".weight");
-  GTX_CHECK(w.shape.size() == 4 && w.shape[1] == 1 && w.shape[2] == w.shape[3] && (int)w.shape[0] == x.c && out.c == x.c, "%s: expected a depthwise kernel on %d channels", name.c_str(), x.c);
-  const int k = (int)w.shape[2], C = x.c;
-  std::vector<float> wt((size_t)k * k * C);
-  for (int c = 0; c < C; ++c)
-    for (int t = 0; t < k * k; ++t) wt[(size_t)t * C + c] = w.data[(size_t)c * k * k + t];
-  Op op;
-  op.kind = Op::DWCONV;
-  op.name = name;
-  const bool tiled = stride == 1 && C % 32 == 0;               // launch_rt_dwconv's rule (GTX_RT_DW_TILE=0 aside)
-  op.family = std::string(tiled ? "rt_dwconv_tile_kernel<" : "rt_dwconv_kernel<") + (k == 3 ? "3>" : "5>");
-  op.a = rt_map(x); op.b = rt_map(out);
-  op.w = upload(wt);
-  op.bias = has(name + ".bias") ? upload(tensor(name + ".bias").data) : nullptr;
-  op.k = k; op.stride = stride; op.act = act;
-  op.img_flops = 2.0 * out.h * out.w * C * k * k;
-  op.img_bytes = ((double)x.h * x.w + (double)out.h * out.w) * C * 4;
-  ops_.push_back(op);
-  layer_views_[name] = out;
-}
-
-void RtDetr::upsample(const std::string& name, const View& src, const View& dst) {
-  Op op;
-  op.kind = Op::UPSAMPLE;
-  op.name = name;
-  op.family = "rt_upsample2x_kernel";
-  op.a = rt_map(src); op.b = rt_map(dst);
-  op.img_bytes = (double)src.h * src.w * src.c * 4 * 5;
-  ops_.push_back(op);
 }
 
 // The HGBlock's concat buffer [x | m.0 .. m.(n-1)]: allocated before x's producer so that x is written in place.
@@ -124,7 +97,8 @@ View RtDetr::hgblock(const std::string& pfx, const View& cat, int c1, bool short
     if (light) {                                              // LightConv: 1x1 without activation, depthwise k x k + ReLU
       View tmp = new_view(cat.h, cat.w, cm);
       conv(m + ".conv1.conv", src, 1, 0, &tmp);
-      dwconv(m + ".conv2.conv", tmp, dst, 1, 2);
+      trunk_.dwconv(m + ".conv2.conv", tmp, 2, 1, &dst);
+      adopt_map_ops();
     } else {
       conv(m + ".conv", src, 1, 2, &dst);
     }
@@ -223,6 +197,7 @@ void RtDetr::build_graph() {
   View feats[3];
   if (yolo_) {
     const YoloTrunk::Levels lv = trunk_.build(img_);
+    n_trunk_ = trunk_ops_.size();
     GTX_CHECK(lv.in.size() == 3 && lv.det_pfx == "model.22" && has("model.22.enc_score_head.weight"),
               "YOLOv8-RTDETR: the decoder must be model.22 on model.15 / 18 / 21 (yolov8-rtdetr.yaml)");
     for (int l = 0; l < 3; ++l) feats[l] = lv.in[l];
@@ -250,7 +225,7 @@ void RtDetr::build_hgnet(View feats[3]) {
     op.kind = Op::STEM1;
     op.name = "model.0.stem1.conv";
     op.family = "rt_stem1_kernel";
-    op.a = rt_map(img_); op.b = rt_map(s1);
+    op.a = img_.map(); op.b = s1.map();
     op.w = upload(w27);
     op.bias = upload(has("model.0.stem1.conv.bias") ? tensor("model.0.stem1.conv.bias").data : std::vector<float>(cm0, 0.f));
     op.img_flops = 2.0 * s1.h * s1.w * cm0 * 27;
@@ -266,7 +241,7 @@ void RtDetr::build_hgnet(View feats[3]) {
     op.name = "model.0.pool";
     op.family = "rt_pool2_kernel";
     View dst = cat_s.slice(0, cm0);
-    op.a = rt_map(s1); op.b = rt_map(dst);
+    op.a = s1.map(); op.b = dst.map();
     op.img_bytes = (double)s1.h * s1.w * cm0 * 8;
     ops_.push_back(op);
   }
@@ -283,14 +258,18 @@ void RtDetr::build_hgnet(View feats[3]) {
     layer_views_["model.0"] = s4;
   }
   // ---- backbone
+  auto down = [&](const std::string& name, const View& x, const View& dst) {   // DWConv(c, c, 3, 2) without activation
+    trunk_.dwconv(name, x, 0, 2, &dst);
+    adopt_map_ops();
+  };
   View x1 = hgblock("model.1", cat1, c1, false, nullptr);
   int c3 = 0;
   View cat3 = hg_cat("model.3", S / 8, S / 8, &c3);
-  dwconv("model.2.conv", x1, cat3.slice(0, c3), 2, 0);
+  down("model.2.conv", x1, cat3.slice(0, c3));
   View x3 = hgblock("model.3", cat3, c3, false, nullptr);
   int c5 = 0, c6 = 0, c7 = 0, c9 = 0;
   View cat5 = hg_cat("model.5", S / 16, S / 16, &c5);
-  dwconv("model.4.conv", x3, cat5.slice(0, c5), 2, 0);
+  down("model.4.conv", x3, cat5.slice(0, c5));
   View cat6 = hg_cat("model.6", S / 16, S / 16, &c6);
   View cat7 = hg_cat("model.7", S / 16, S / 16, &c7);
   {
@@ -300,7 +279,7 @@ void RtDetr::build_hgnet(View feats[3]) {
   }
   View x7 = hgblock("model.7", cat7, c7, true, nullptr);
   View cat9 = hg_cat("model.9", S / 32, S / 32, &c9);
-  dwconv("model.8.conv", x7, cat9.slice(0, c9), 2, 0);
+  down("model.8.conv", x7, cat9.slice(0, c9));
   View x9 = hgblock("model.9", cat9, c9, false, nullptr);
   // ---- encoder: AIFI on P5 (model.10-11)
   View x10 = conv("model.10.conv", x9, 1, 0);
@@ -330,7 +309,7 @@ void RtDetr::build_hgnet(View feats[3]) {
     op.kind = Op::TOKENS_IN;
     op.name = A + ".tokens";
     op.family = "rt_tokens_in_kernel";
-    op.a = rt_map(x10);
+    op.a = x10.map();
     op.p0 = upload(pos);
     float* src = new_tokens(T5, E, A + ".src");
     float* q = new_tokens(T5, E, A + ".q");
@@ -369,7 +348,8 @@ void RtDetr::build_hgnet(View feats[3]) {
   }
   const View x12 = cat27.slice(E, E);
   View cat16 = new_view(S / 16, S / 16, 2 * E);
-  upsample("model.13", x12, cat16.slice(0, E));
+  trunk_.upsample("model.13", x12, cat16.slice(0, E));
+  adopt_map_ops();
   {
     View d = cat16.slice(E, E);
     conv("model.14.conv", x7, 1, 0, &d);
@@ -382,7 +362,8 @@ void RtDetr::build_hgnet(View feats[3]) {
   }
   const View x17 = cat24.slice(E, E);
   View cat21 = new_view(S / 8, S / 8, 2 * E);
-  upsample("model.18", x17, cat21.slice(0, E));
+  trunk_.upsample("model.18", x17, cat21.slice(0, E));
+  adopt_map_ops();
   {
     View d = cat21.slice(E, E);
     conv("model.19.conv", x3, 1, 0, &d);
@@ -435,7 +416,7 @@ void RtDetr::build_decoder(const std::string& D, const View feats[3]) {
     op.kind = Op::MASK;
     op.name = D + ".valid_mask." + std::to_string(l);
     op.family = "rt_mask_invalid_kernel";
-    op.a = rt_map(proj[l]);
+    op.a = proj[l].map();
     op.level = l;
     ops_.push_back(op);
   }
@@ -582,18 +563,13 @@ void RtDetr::build_decoder(const std::string& D, const View feats[3]) {
 
 void RtDetr::set_batch(int nb) {
   if (nb == cur_nb_) return;
-  set_batch_ops(trunk_ops_, nb, view_es_, false);
   for (Op& op : ops_) {
-    if (op.kind != Op::CONV) {
+    if (op.kind == Op::MAP) {
+      set_batch_op(op.map, nb, view_es_, false);
+    } else {
       op.flops = op.img_flops * nb;
       op.bytes = op.img_bytes * nb;
-      continue;
     }
-    for (int i = 0; i < op.grp.count; ++i) op.grp.p[i].N = nb;
-    conv_group_finalize(op.grp, op.cfg);
-    const ConvProblem& p = op.grp.p[0];
-    op.flops = conv_flops(p, op.cfg.ks);
-    op.bytes = ((double)p.H * p.W * p.Cin + (double)p.Ho * p.Wo * p.Cout) * 4 * nb + (double)p.Cout * p.Cin * op.cfg.ks * op.cfg.ks * 4;
   }
   cur_nb_ = nb;
 }
@@ -602,7 +578,11 @@ void RtDetr::finalize() {
   GTX_CHECK(!finalized_, "finalize called twice");
   GTX_HIP(hipSetDevice(ctx_->device));
   build_graph();
-  if (yolo_) trunk_.fuse();
+  GTX_CHECK(trunk_ops_.size() == n_trunk_, "internal: %zu map layers were built and not adopted (they would never launch)", trunk_ops_.size() - n_trunk_);
+  if (yolo_) {
+    trunk_.fuse();
+    adopt_map_ops(0, 0);
+  }
   const int N = cfg_.max_batch;
   alloc_outputs();
   class_mask_[0] = class_mask_[1] = cfg_.n_classes == 0 ? ~0ull : 0ull;
@@ -619,11 +599,9 @@ void RtDetr::finalize() {
 
 void RtDetr::run_op(const Op& op, int nb, hipStream_t s) {
   switch (op.kind) {
-    case Op::CONV: conv_launch(op.grp, op.cfg, s); break;
+    case Op::MAP: trunk_.run_op(op.map, nb, s); break;
     case Op::STEM1: launch_rt_stem1(fmt_, op.a.ptr, nb, op.a.h, op.a.w, op.w, op.bias, op.b, sat_dev_, s); break;
     case Op::POOL2: launch_rt_pool2(fmt_, op.a, op.b, nb, sat_dev_, s); break;
-    case Op::DWCONV: launch_rt_dwconv(fmt_, op.a, op.b, nb, op.k, op.stride, op.w, op.bias, op.act, sat_dev_, s); break;
-    case Op::UPSAMPLE: launch_rt_upsample2x(fmt_, op.a, op.b, nb, s); break;
     case Op::TOKENS_IN: launch_rt_tokens_in(fmt_, op.a, nb, op.p0, op.p1, op.p2, s); break;
     case Op::LINEAR: {
       RtLinear L = op.lin;

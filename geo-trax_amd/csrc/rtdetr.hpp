@@ -28,14 +28,15 @@ class RtDetr : public DetectorBase {
   void sparse_box(int* on, int* overflows) const override { if (on) *on = 0; if (overflows) *overflows = 0; }
 
  private:
+  // MAP: a plain map-side layer (convolution, depthwise convolution, 2x upsampling): the trunk's op, built by its builders, launched by
+  // its run_op and accounted for by set_batch_op. The other kinds are the family's own.
   struct Op : OpInfo {
-    enum Kind { CONV, STEM1, POOL2, DWCONV, UPSAMPLE, TOKENS_IN, LINEAR, LAYERNORM, MHA, MASK, TOPK, GATHER, REFER, DEFORM } kind = CONV;
-    ConvGroup grp{};
-    ConvConfig cfg{};
+    enum Kind { MAP, STEM1, POOL2, TOKENS_IN, LINEAR, LAYERNORM, MHA, MASK, TOPK, GATHER, REFER, DEFORM } kind = MAP;
+    gtx::Op map;                     // MAP (its OpInfo is the op's)
     RtMap a{}, b{};                  // map in / out
-    const float* w = nullptr;        // STEM1 / DWCONV weights
+    const float* w = nullptr;        // STEM1 weights; LAYERNORM gamma
     const float* bias = nullptr;
-    int k = 0, stride = 1, act = 0, level = 0, mode = 0;
+    int level = 0, mode = 0;
     RtLinear lin{};                  // LINEAR (M = rows per image; scaled by the batch at launch)
     RtRows r_in{}, r_out{};          // LAYERNORM
     long rows = 0;                   // LAYERNORM: rows per image
@@ -45,15 +46,12 @@ class RtDetr : public DetectorBase {
     float* p2 = nullptr;             // TOKENS_IN q; REFER refer; DEFORM refer; GATHER anchors
     int ld0 = 0, ld1 = 0;
     RtLevels lv{};                   // TOPK scores / GATHER enc / DEFORM values
-    double img_flops = 0, img_bytes = 0;   // ops other than CONV: per image (set_batch scales them to the pass)
+    double img_flops = 0, img_bytes = 0;   // per image (set_batch scales them to the pass)
   };
 
-  // the YOLOv8 trunk's launches (yolov8-rtdetr) come first, then the family's own
-  size_t op_count() const override { return trunk_ops_.size() + ops_.size(); }
-  const OpInfo& op_info(size_t i) const override { return i < trunk_ops_.size() ? (const OpInfo&)trunk_ops_[i] : ops_[i - trunk_ops_.size()]; }
-  void launch_op(size_t i, int nb, hipStream_t s) override {
-    if (i < trunk_ops_.size()) trunk_.run_op(trunk_ops_[i], nb, s); else run_op(ops_[i - trunk_ops_.size()], nb, s);
-  }
+  size_t op_count() const override { return ops_.size(); }
+  const OpInfo& op_info(size_t i) const override { return ops_[i].kind == Op::MAP ? (const OpInfo&)ops_[i].map : ops_[i]; }
+  void launch_op(size_t i, int nb, hipStream_t s) override { run_op(ops_[i], nb, s); }
   std::unique_ptr<NetRuntime> make_exact() const override;
   void release_graph() override { ops_.clear(); trunk_ops_.clear(); trunk_.clear(); }
   float* new_tokens(int rows_per_image, int ld, const std::string& name);
@@ -62,11 +60,9 @@ class RtDetr : public DetectorBase {
                 int act, const View* out_slice, const View* residual, bool plain_out = false);
   View conv(const std::string& name, const View& x, int stride, int act, const View* out_slice = nullptr, const View* residual = nullptr);
   View conv2x2(const std::string& name, const View& x, const View* out_slice);
-  void dwconv(const std::string& name, const View& x, const View& out, int stride, int act);
   View hg_cat(const std::string& pfx, int h, int w, int* c1);
   View hgblock(const std::string& pfx, const View& cat, int c1, bool shortcut, const View* out_slice);
   View repc3(const std::string& pfx, const View& x);
-  void upsample(const std::string& name, const View& src, const View& dst);
   float* linear(const std::string& name, const std::vector<float>& w, const std::vector<float>& bias, int nout, int k, const float* x, int ldx, const float* x2,
                 int rows, int act, const float* res, int ldr, float* y, int ldy, const std::string& out_name);
   float* layernorm_tokens(const std::string& name, const float* x, int rows, int C, const std::string& out_name, const View* map_out = nullptr);
@@ -77,9 +73,16 @@ class RtDetr : public DetectorBase {
   void run_post(int nb, hipStream_t s) override;
   void set_batch(int nb) override;
 
+  // The trunk's builders (and emit_conv) append to trunk_ops_; what stands there from `first` on moves into ops_ at position `at`
+  // as MAP ops. A layer of the family's own goes behind the ops before it at once (first = n_trunk_); the YOLOv8 trunk's n_trunk_ ops
+  // stay until YoloTrunk::fuse() has rewritten them and then go in front.
+  void adopt_map_ops(size_t first, size_t at);
+  void adopt_map_ops() { adopt_map_ops(n_trunk_, ops_.size()); }
+
   std::vector<Op> ops_;
   bool yolo_ = false;                // yolov8-rtdetr.yaml: the YOLOv8 trunk
   std::vector<gtx::Op> trunk_ops_;
+  size_t n_trunk_ = 0;
   YoloTrunk trunk_;
   int nh_ = 8, npts_ = 4, nq_ = 300, enc_heads_ = 8, hd_ = 256, nc_ = 0, ncp_ = 0, ndl_ = 0;
 

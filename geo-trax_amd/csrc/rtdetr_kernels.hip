@@ -1,7 +1,7 @@
 // RT-DETR's non-convolution kernels (see rtdetr_kernels.hpp). gfx950 only.
 //
 // What bounds them at the reference configuration (one 3840x2160 frame stretched to 1920 x 1920, rtdetr-l):
-//   rt_stem1 / rt_pool2 / rt_dwconv / rt_upsample2x / rt_tokens_in / rt_layernorm / rt_mask_invalid   HBM (each tensor read and written once)
+//   rt_stem1 / rt_pool2 / rt_dwconv / rt_tokens_in / rt_layernorm / rt_mask_invalid   HBM (each tensor read and written once)
 //   rt_linear                     the fp32 matrix pipe (v_mfma_f32_16x16x4_f32, 157 TFLOP/s dense); tiny M: launch latency
 //   rt_mha                        vector fp32 (2 d FMAs per query-key pair from LDS broadcasts)
 //   rt_topk / rt_gather / rt_refer / rt_deform / rt_post   latency (a few hundred queries per image)
@@ -285,24 +285,6 @@ __global__ __launch_bounds__(256) void rt_dwconv_tile_kernel(RtMap in, RtMap out
   bool s = false;
   store8<FMT>(out.ptr, (((size_t)n * out.h + oy) * out.w + ox) * out.cstride + out.coff + c0 + g * 8, acc, s);
   flag_sat(sat, s);
-}
-
-// ============================================================================ nearest 2x upsampling (raw 8-channel groups)
-__global__ __launch_bounds__(256) void rt_upsample2x_kernel(RtMap in, RtMap out, int N, int gbytes) {
-  const int groups = in.c / 8;
-  const size_t total = (size_t)N * out.h * out.w * groups;
-  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= total) return;
-  const int g = (int)(t % groups);
-  const size_t pix = t / groups;
-  const int ox = (int)(pix % out.w), oy = (int)((pix / out.w) % out.h), n = (int)(pix / ((size_t)out.w * out.h));
-  const size_t src = (((size_t)n * in.h + oy / 2) * in.w + ox / 2) * in.cstride + in.coff + g * 8;
-  const size_t dst = pix * out.cstride + out.coff + g * 8;
-  const int es = gbytes / 8;
-  const uint4* sp = reinterpret_cast<const uint4*>(static_cast<const char*>(in.ptr) + src * es);
-  uint4* dp = reinterpret_cast<uint4*>(static_cast<char*>(out.ptr) + dst * es);
-  dp[0] = sp[0];
-  if (gbytes == 32) dp[1] = sp[1];
 }
 
 // ============================================================================ map -> token rows (+ positional embedding)
@@ -840,7 +822,6 @@ __global__ __launch_bounds__(256) void psa_attn_kernel(RtMap qkv, RtMap out, con
 // neither read nor stored. pe(v) reads the staged V: at these sizes most of its 3 x 3 window is padding.
 // LDS: 64 * (36 + 68) floats = 26 624 bytes, six workgroups per CU. (Two pairs per workgroup measured slower at every crop count
 // from 100 to 600: DESIGN section 7a.)
-constexpr int kPsaSmallT = 64;
 template <int FMT>
 __global__ __launch_bounds__(256) void psa_attn_small_kernel(RtMap qkv, RtMap out, int heads, const float* __restrict__ pe_w,
                                                              const float* __restrict__ pe_b, int* sat) {
@@ -1215,11 +1196,11 @@ void launch_rt_dwconv(int fmt, const RtMap& in, const RtMap& out, int n, int k, 
                       const RtMap* residual) {
   GTX_CHECK(in.c % 8 == 0 && in.c == out.c && (k == 3 || k == 5 || k == 7) && (stride == 1 || stride == 2), "rt_dwconv: unsupported %dx%d stride %d on %d channels", k, k, stride, in.c);
   GTX_CHECK(out.h == (in.h + 2 * (k / 2) - k) / stride + 1 && out.w == (in.w + 2 * (k / 2) - k) / stride + 1, "rt_dwconv: output size");
-  const RtMap res = residual ? *residual : RtMap{nullptr, 0, 0, 0, 0, 0};
+  const RtMap res = residual ? *residual : RtMap();
   GTX_CHECK(!res.ptr || (res.h == out.h && res.w == out.w && res.c == out.c && res.coff % 8 == 0 && res.cstride % 8 == 0), "rt_dwconv: the residual does not have the output's shape");
   const size_t total = (size_t)n * out.h * out.w * (in.c / 8);
   static const bool tiled = [] { const char* e = getenv("GTX_RT_DW_TILE"); return !(e && e[0] == '0'); }();
-  if (stride == 1 && in.c % 32 == 0 && tiled) {
+  if (rt_dwconv_tiled(stride, in.c) && tiled) {
     const dim3 grid(cdiv(out.w, 8) * cdiv(out.h, 8), in.c / 32, n);
     if (k == 3) RT_FMT(fmt, hipLaunchKernelGGL((rt_dwconv_tile_kernel<F, 3>), grid, dim3(256), 0, s, in, out, w, bias, act, sat, res));
     else if (k == 5) RT_FMT(fmt, hipLaunchKernelGGL((rt_dwconv_tile_kernel<F, 5>), grid, dim3(256), 0, s, in, out, w, bias, act, sat, res));
@@ -1229,13 +1210,6 @@ void launch_rt_dwconv(int fmt, const RtMap& in, const RtMap& out, int n, int k, 
   if (k == 3) RT_FMT(fmt, hipLaunchKernelGGL((rt_dwconv_kernel<F, 3>), dim3(blocks_for(total)), dim3(256), 0, s, in, out, n, stride, w, bias, act, sat, res));
   else if (k == 5) RT_FMT(fmt, hipLaunchKernelGGL((rt_dwconv_kernel<F, 5>), dim3(blocks_for(total)), dim3(256), 0, s, in, out, n, stride, w, bias, act, sat, res));
   else RT_FMT(fmt, hipLaunchKernelGGL((rt_dwconv_kernel<F, 7>), dim3(blocks_for(total)), dim3(256), 0, s, in, out, n, stride, w, bias, act, sat, res));
-}
-
-void launch_rt_upsample2x(int fmt, const RtMap& in, const RtMap& out, int n, hipStream_t s) {
-  GTX_CHECK(in.c % 8 == 0 && in.c == out.c && out.h == 2 * in.h && out.w == 2 * in.w, "rt_upsample2x: bad shapes");
-  const size_t total = (size_t)n * out.h * out.w * (in.c / 8);
-  hipLaunchKernelGGL(rt_upsample2x_kernel, dim3(blocks_for(total)), dim3(256), 0, s, in, out, n, 8 * fmt_size(fmt));
-  GTX_HIP(hipGetLastError());
 }
 
 void launch_rt_tokens_in(int fmt, const RtMap& in, int n, const float* pos, float* src, float* q, hipStream_t s) {
@@ -1285,8 +1259,6 @@ void launch_rt_mha(const float* qkv, int ld, int n, int T, int C, int heads, flo
   else fail(-3, "rt_mha: head dimension %d is not built (8, 16, 32)", d);
   GTX_HIP(hipGetLastError());
 }
-
-bool psa_attention_small(int h, int w) { return h * w <= kPsaSmallT; }
 
 void launch_psa_attention(int fmt, const RtMap& qkv, const RtMap& out, int n, int heads, const float* pe_w, const float* pe_b, int* sat, hipStream_t s,
                           int form) {

@@ -11,6 +11,7 @@
 #pragma once
 #include "common.hpp"
 #include "conv_igemm.hpp"
+#include "yolo_tables.hpp"
 
 namespace gtx {
 
@@ -25,11 +26,10 @@ void launch_rt_stem1(int fmt, const void* img, int n, int H, int W, const float*
 // MaxPool2d(2, 1, ceil_mode) on F.pad(x, [0, 1, 0, 1]): out(y, x) = max over the 2 x 2 window at (y, x), zeros past the border
 void launch_rt_pool2(int fmt, const RtMap& in, const RtMap& out, int n, int* sat, hipStream_t s);
 // depthwise k x k (3, 5 or 7), stride 1 or 2, pad k / 2; w [k * k][C] tap-major, bias [C]; act: 0 none, 1 SiLU (YOLO11's DWConv), 2 ReLU;
-// residual (optional, the output's shape): added after the activation (YOLOv10's CIB: x + cv1(x))
+// residual (optional, the output's shape): added after the activation (YOLOv10's CIB: x + cv1(x)). Runs rt_dwconv_kernel_name(k, stride, c)
+// (yolo_tables.hpp): the tiled form when rt_dwconv_tiled(stride, c)
 void launch_rt_dwconv(int fmt, const RtMap& in, const RtMap& out, int n, int k, int stride, const float* w, const float* bias, int act, int* sat, hipStream_t s,
                       const RtMap* residual = nullptr);
-// nearest 2x upsampling into a channel slice (raw copy of 8-channel groups)
-void launch_rt_upsample2x(int fmt, const RtMap& in, const RtMap& out, int n, hipStream_t s);
 // map -> tokens: src [N * h * w][C] plain fp32 and, when q != null, q = src + pos (pos [h * w][C])
 void launch_rt_tokens_in(int fmt, const RtMap& in, int n, const float* pos, float* src, float* q, hipStream_t s);
 // zero the rows of anchors outside (eps, 1 - eps) (RTDETRDecoder._generate_anchors' valid_mask) of a level's map
@@ -60,11 +60,10 @@ void launch_rt_mha(const float* qkv, int ld, int n, int T, int C, int heads, flo
 // channels, out [N][h][w][heads * 64] = softmax(q^T k * 32^-0.5) v over the h w positions + pe(v), pe a depthwise 3x3
 // convolution without activation (pe_w [9][heads * 64] tap-major, pe_b [heads * 64]). Scores and softmax in fp32.
 // Maps of at most 64 positions (the ReID embedder's crops) run psa_attn_small_kernel: one workgroup per (crop, head) pair, its K
-// and V staged once; larger ones psa_attn_kernel. form: 0 = that rule, 1 / 2 = the large- / small-map kernel whatever the size (the
-// operator-level hook's, for tests and timing; 2 needs h w <= 64).
+// and V staged once; larger ones psa_attn_kernel. form: 0 = that rule (psa_attention_small / psa_attention_kernel_name, yolo_tables.hpp),
+// 1 / 2 = the large- / small-map kernel whatever the size (the operator-level hook's, for tests and timing; 2 needs h w <= 64).
 void launch_psa_attention(int fmt, const RtMap& qkv, const RtMap& out, int n, int heads, const float* pe_w, const float* pe_b, int* sat, hipStream_t s,
                           int form = 0);
-bool psa_attention_small(int h, int w);   // the rule of form 0
 
 // query selection: per image, the nq anchors with the largest max-over-classes score, descending (ties: lower anchor index
 // first). scores: per level maps [N][h][w][cs] with the classes in channels [0, nc): plain fp32 (fmt DT_F32, both fp32-grade

@@ -53,6 +53,21 @@ inline std::vector<float> dw_tap_major(const float* w, int c, int taps) {
   return wt;
 }
 
+// Which kernel a launcher of rtdetr_kernels.hpp runs. The launcher dispatches on the predicate, the graph builders label their ops
+// (OpInfo::family, what the profile tables are keyed by) with the name.
+// launch_rt_dwconv: the LDS-tiled form at stride 1 on whole 32-channel groups (GTX_RT_DW_TILE=0, a debugging switch, aside)
+inline bool rt_dwconv_tiled(int stride, int c) { return stride == 1 && c % 32 == 0; }
+inline const char* rt_dwconv_kernel_name(int k, int stride, int c) {
+  const bool t = rt_dwconv_tiled(stride, c);
+  if (k == 3) return t ? "rt_dwconv_tile_kernel<3>" : "rt_dwconv_kernel<3>";
+  if (k == 5) return t ? "rt_dwconv_tile_kernel<5>" : "rt_dwconv_kernel<5>";
+  return t ? "rt_dwconv_tile_kernel<7>" : "rt_dwconv_kernel<7>";
+}
+// launch_psa_attention (form 0): maps of at most kPsaSmallT positions run the one-workgroup-per-(image, head) kernel
+inline constexpr int kPsaSmallT = 64;
+inline bool psa_attention_small(int h, int w) { return h * w <= kPsaSmallT; }
+inline const char* psa_attention_kernel_name(int h, int w) { return psa_attention_small(h, w) ? "psa_attn_small_kernel" : "psa_attn_kernel"; }
+
 namespace tables {
 using R = TrunkRow;
 inline constexpr R kYolov8[] = {

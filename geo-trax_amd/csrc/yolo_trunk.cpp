@@ -67,6 +67,7 @@ View YoloTrunk::conv(const std::string& name, const View& x, int stride, const V
 }
 
 void YoloTrunk::upsample(const std::string& name, const View& src, const View& dst) {
+  GTX_CHECK(dst.h == 2 * src.h && dst.w == 2 * src.w && dst.c == src.c, "%s: a %dx%dx%d map does not upsample into %dx%dx%d", name.c_str(), src.w, src.h, src.c, dst.w, dst.h, dst.c);
   Op op;
   op.kind = Op::UPSAMPLE;
   op.name = name;
@@ -250,18 +251,15 @@ void YoloTrunk::psa_block(const std::string& m, const View& b, const View& dst) 
   const View qkv = conv_act(m + ".attn.qkv.conv", b, 0, nullptr, nullptr);
   View att = net_.new_view(b.h, b.w, c);
   {
-    std::vector<float> wt((size_t)9 * c);
-    for (int ch = 0; ch < c; ++ch)
-      for (int t = 0; t < 9; ++t) wt[(size_t)t * c + ch] = wp.data[(size_t)ch * 9 + t];
     std::vector<float> bias(c, 0.f);
     if (const float* pb = net_.bias_of(m + ".attn.pe.conv", c)) std::copy(pb, pb + c, bias.begin());
     Op op;
     op.kind = Op::ATTN;
     op.name = m + ".attn";
-    op.family = psa_attention_small(b.h, b.w) ? "psa_attn_small_kernel" : "psa_attn_kernel";     // launch_psa_attention's rule
+    op.family = psa_attention_kernel_name(b.h, b.w);
     op.in = qkv; op.out = att;
     op.heads = heads;
-    op.dw_w = net_.upload(wt); op.dw_bias = net_.upload(bias);
+    op.dw_w = net_.upload(dw_tap_major(wp.data.data(), c, 9)); op.dw_bias = net_.upload(bias);
     op.sat = net_.sat_flag();
     ops_.push_back(op);
     net_.set_layer_view(m + ".attn.out", att);       // softmax(q^T k) v + pe(v): what proj reads
@@ -296,17 +294,17 @@ View YoloTrunk::c2psa(const std::string& pfx, const View& x, const View* out_sli
 View YoloTrunk::dwconv(const std::string& name, const View& x, int act, int stride, const View* out_slice, const View* residual) {
   const HostTensor& w = net_.tensor(name + ".weight");
   const int c = x.c;
-  GTX_CHECK(w.shape.size() == 4 && (int)w.shape[0] == c && w.shape[1] == 1 && (w.shape[2] == 3 || w.shape[2] == 7) && w.shape[3] == w.shape[2] && c % 8 == 0,
-            "%s: expected a depthwise 3x3 or 7x7 convolution on %d channels", name.c_str(), c);
+  GTX_CHECK(w.shape.size() == 4 && (int)w.shape[0] == c && w.shape[1] == 1 && (w.shape[2] == 3 || w.shape[2] == 5 || w.shape[2] == 7) && w.shape[3] == w.shape[2] && c % 8 == 0,
+            "%s: expected a depthwise 3x3, 5x5 or 7x7 convolution on %d channels", name.c_str(), c);
   const int k = (int)w.shape[2], taps = k * k;
   GTX_CHECK(stride == 1 || (stride == 2 && k == 3), "%s: stride %d", name.c_str(), stride);
-  std::vector<float> wt = dw_tap_major(w.data.data(), c, taps), bias(c, 0.f);
+  std::vector<float> wt = dw_tap_major(w.data.data(), c, taps), bias(c, 0.f);   // no bias tensor: zeros, the same sum
   if (const float* pb = net_.bias_of(name, c)) std::copy(pb, pb + c, bias.begin());
   const int ho = (x.h - 1) / stride + 1, wo = (x.w - 1) / stride + 1;
   Op op;
   op.kind = Op::DWCONV;
   op.name = name;
-  op.family = std::string(stride == 1 && c % 32 == 0 ? "rt_dwconv_tile_kernel<" : "rt_dwconv_kernel<") + (k == 3 ? "3>" : "7>");     // launch_rt_dwconv's rule
+  op.family = rt_dwconv_kernel_name(k, stride, c);
   op.in = x;
   op.out = out_slice ? *out_slice : net_.new_view(ho, wo, c);
   GTX_CHECK(op.out.h == ho && op.out.w == wo && op.out.c == c, "%s: the output slice does not fit", name.c_str());
@@ -650,31 +648,23 @@ void YoloTrunk::run_op(const Op& op, int nb, hipStream_t s) const {
       break;
     case Op::POOL: launch_sppf_pool(fmt == DT_F32S ? DT_F32S : dtype_, op.out.ptr, nb, op.in.h, op.in.w, op.in.c, s); break;
     case Op::UPSAMPLE:
-      launch_upsample2x(dtype_, op.in.ptr, nb, op.in.h, op.in.w, op.in.c, op.in.cstride, op.in.coff, op.out.ptr,
+      // a raw copy: all it needs is what a stored element takes -- 2 bytes under half, 4 in fp32 and in the pair format (dtype_ is
+      // DT_F32 there), also where the net allocates more per element than it stores (rtdetr-l's fp16 maps in 4-byte slots)
+      launch_upsample2x(dtype_size(dtype_), op.in.ptr, nb, op.in.h, op.in.w, op.in.c, op.in.cstride, op.in.coff, op.out.ptr,
                         op.out.cstride, op.out.coff, s);
       break;
     case Op::DWCONV: {
-      const RtMap res{op.dw_res.ptr, op.dw_res.h, op.dw_res.w, op.dw_res.cstride, op.dw_res.coff, op.dw_res.c};
-      launch_rt_dwconv(fmt, RtMap{op.in.ptr, op.in.h, op.in.w, op.in.cstride, op.in.coff, op.in.c},
-                       RtMap{op.out.ptr, op.out.h, op.out.w, op.out.cstride, op.out.coff, op.out.c}, nb, op.dw_k, op.dw_stride, op.dw_w, op.dw_bias, op.dw_act,
-                       op.sat, s, op.dw_res.ptr ? &res : nullptr);
+      const RtMap res = op.dw_res.map();
+      launch_rt_dwconv(fmt, op.in.map(), op.out.map(), nb, op.dw_k, op.dw_stride, op.dw_w, op.dw_bias, op.dw_act, op.sat, s, res.ptr ? &res : nullptr);
       break;
     }
-    case Op::POOLDOWN:
-      launch_pool_down(fmt, RtMap{op.in.ptr, op.in.h, op.in.w, op.in.cstride, op.in.coff, op.in.c},
-                       RtMap{op.out.ptr, op.out.h, op.out.w, op.out.cstride, op.out.coff, op.out.c},
-                       RtMap{op.out2.ptr, op.out2.h, op.out2.w, op.out2.cstride, op.out2.coff, op.out2.c}, nb, s);
-      break;
-    case Op::ATTN:
-      launch_psa_attention(fmt, RtMap{op.in.ptr, op.in.h, op.in.w, op.in.cstride, op.in.coff, op.in.c},
-                           RtMap{op.out.ptr, op.out.h, op.out.w, op.out.cstride, op.out.coff, op.out.c}, nb, op.heads, op.dw_w, op.dw_bias, op.sat, s);
-      break;
+    case Op::POOLDOWN: launch_pool_down(fmt, op.in.map(), op.out.map(), op.out2.map(), nb, s); break;
+    case Op::ATTN: launch_psa_attention(fmt, op.in.map(), op.out.map(), nb, op.heads, op.dw_w, op.dw_bias, op.sat, s); break;
   }
 }
 
-void set_batch_ops(std::vector<Op>& ops, int nb, size_t es, bool pad_skip_on) {
-  for (Op& op : ops) {
-    if (op.kind != Op::CONV) continue;
+void set_batch_op(Op& op, int nb, size_t es, bool pad_skip_on) {
+  if (op.kind == Op::CONV) {
     for (int i = 0; i < op.grp.count; ++i) {
       op.grp.p[i].N = nb;
       op.grp.p[i].ty_first = pad_skip_on ? op.ty_first[i] : 0;
@@ -699,29 +689,30 @@ void set_batch_ops(std::vector<Op>& ops, int nb, size_t es, bool pad_skip_on) {
         op.bytes += part * ((double)p.N * p.front_h * p.front_w_px * 4 - (double)p.N * p.H * p.W * p.Cin * es);
       }
     }
+  } else if (op.kind == Op::STEM) {
+    op.flops = 2.0 * nb * op.out.h * op.out.w * op.out.c * 27;
+    op.bytes = (double)nb * ((double)op.in.h * op.in.w * 4 + (double)op.out.h * op.out.w * op.out.c * es);   // RGB0 bytes in
+  } else if (op.kind == Op::POOL) {
+    op.flops = 0;
+    op.bytes = (double)nb * op.in.h * op.in.w * op.in.c * 4 * es;
+  } else if (op.kind == Op::UPSAMPLE) {
+    op.flops = 0;
+    op.bytes = (double)nb * op.in.h * op.in.w * op.in.c * 5 * es;
+  } else if (op.kind == Op::DWCONV) {
+    op.flops = 2.0 * op.dw_k * op.dw_k * nb * op.out.h * op.out.w * op.in.c;
+    op.bytes = (double)nb * ((double)op.in.h * op.in.w + (double)op.out.h * op.out.w * (op.dw_res.ptr ? 2 : 1)) * op.in.c * es;
+  } else if (op.kind == Op::POOLDOWN) {             // three additions per averaged element, eight maxima per maximum; every map once
+    op.flops = (double)nb * op.in.h * op.in.w * (3.0 * op.out.c + 3.0 * op.out2.c) + 8.0 * nb * op.out2.h * op.out2.w * op.out2.c;
+    op.bytes = (double)nb * ((double)op.in.h * op.in.w * (op.in.c + op.out.c) + (double)op.out2.h * op.out2.w * op.out2.c) * es;
+  } else if (op.kind == Op::ATTN) {                 // q.k (depth 32) + p.v (width 64) per query-key pair and head, + pe; the qkv map in, the output map out
+    const double T = (double)op.in.h * op.in.w;
+    op.flops = nb * (op.heads * T * T * 2.0 * (32 + 64) + 2.0 * 9 * T * op.out.c);
+    op.bytes = nb * T * (op.in.c + op.out.c) * es;
   }
-  for (Op& op : ops) {
-    if (op.kind == Op::STEM) {
-      op.flops = 2.0 * nb * op.out.h * op.out.w * op.out.c * 27;
-      op.bytes = (double)nb * ((double)op.in.h * op.in.w * 4 + (double)op.out.h * op.out.w * op.out.c * es);   // RGB0 bytes in
-    } else if (op.kind == Op::POOL) {
-      op.flops = 0;
-      op.bytes = (double)nb * op.in.h * op.in.w * op.in.c * 4 * es;
-    } else if (op.kind == Op::UPSAMPLE) {
-      op.flops = 0;
-      op.bytes = (double)nb * op.in.h * op.in.w * op.in.c * 5 * es;
-    } else if (op.kind == Op::DWCONV) {
-      op.flops = 2.0 * op.dw_k * op.dw_k * nb * op.out.h * op.out.w * op.in.c;
-      op.bytes = (double)nb * ((double)op.in.h * op.in.w + (double)op.out.h * op.out.w * (op.dw_res.ptr ? 2 : 1)) * op.in.c * es;
-    } else if (op.kind == Op::POOLDOWN) {           // three additions per averaged element, eight maxima per maximum; every map once
-      op.flops = (double)nb * op.in.h * op.in.w * (3.0 * op.out.c + 3.0 * op.out2.c) + 8.0 * nb * op.out2.h * op.out2.w * op.out2.c;
-      op.bytes = (double)nb * ((double)op.in.h * op.in.w * (op.in.c + op.out.c) + (double)op.out2.h * op.out2.w * op.out2.c) * es;
-    } else if (op.kind == Op::ATTN) {               // q.k (depth 32) + p.v (width 64) per query-key pair and head, + pe; the qkv map in, the output map out
-      const double T = (double)op.in.h * op.in.w;
-      op.flops = nb * (op.heads * T * T * 2.0 * (32 + 64) + 2.0 * 9 * T * op.out.c);
-      op.bytes = nb * T * (op.in.c + op.out.c) * es;
-    }
-  }
+}
+
+void set_batch_ops(std::vector<Op>& ops, int nb, size_t es, bool pad_skip_on) {
+  for (Op& op : ops) set_batch_op(op, nb, es, pad_skip_on);
 }
 
 }  // namespace gtx

@@ -25,7 +25,7 @@ struct Op : OpInfo {
   float stem_scale = 1.f;      // split-f16x3 stem: inverse of the weights' power-of-two scaling
   const void* front_wpk = nullptr;   // the same weights packed for the front stage of model.1 (ConvProblem::front_w)
   float front_scale = 1.f;
-  // DWCONV (depthwise dw_k x dw_k, stride dw_stride, on `in` -> `out`; act 0 none, 1 SiLU; dw_res: added after the activation when it
+  // DWCONV (depthwise dw_k x dw_k, stride dw_stride, on `in` -> `out`; act 0 none, 1 SiLU, 2 ReLU; dw_res: added after the activation when it
   // has a buffer) / ATTN (C2PSA's attention on the qkv map `in`, dw_w / dw_bias = its pe)
   const float* dw_w = nullptr;       // [k * k][C] tap-major
   const float* dw_bias = nullptr;
@@ -38,7 +38,8 @@ struct Op : OpInfo {
   int ty_first[kMaxGroup] = {0}, ty_count[kMaxGroup] = {0};
 };
 
-// N of every conv op (and the rows it computes) and every op's flops / bytes for a pass at batch nb (es: bytes per activation)
+// N of a conv op (and the rows it computes) and the op's flops / bytes for a pass at batch nb (es: bytes per activation); every op of a list
+void set_batch_op(Op& op, int nb, size_t es, bool pad_skip_on);
 void set_batch_ops(std::vector<Op>& ops, int nb, size_t es, bool pad_skip_on);
 
 class YoloTrunk {
@@ -74,10 +75,11 @@ class YoloTrunk {
   // p is the placeholder of a released buffer that no layer_output() has re-created yet (no device address)
   bool hidden(const void* p) const;
   void clear() { unfused_.clear(); hidden_.clear(); }
-  // Depthwise convolution "<name>.weight" [C][1][k][k] (+ bias), k = 3 or 7 read off the tensor, stride 1 or 2, SiLU or no activation
-  // (YOLO11's DWConv, used by its Detect; YOLOv10's SCDown and CIB). out_slice: where it writes (null: a view of its own);
-  // residual: added after the activation
+  // Depthwise convolution "<name>.weight" [C][1][k][k] (+ bias), k = 3, 5 or 7 read off the tensor, stride 1 or 2 (2: k = 3), act 0 none, 1 SiLU,
+  // 2 ReLU (YOLO11's DWConv, used by its Detect; YOLOv10's SCDown and CIB; rtdetr-l's DWConv and LightConv). out_slice: where it writes
+  // (null: a view of its own); residual: added after the activation
   View dwconv(const std::string& name, const View& x, int act, int stride = 1, const View* out_slice = nullptr, const View* residual = nullptr);
+  void upsample(const std::string& name, const View& src, const View& dst);   // nearest 2x of src into dst, a channel slice
 
  private:
   View stem(const View& img, bool front);
@@ -93,7 +95,6 @@ class YoloTrunk {
   View scdown(const std::string& pfx, const View& x, const View* out_slice);
   View elan(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src);   // ELAN1 and RepNCSPELAN4
   View adown(const std::string& pfx, const View& x, const View* out_slice);                                     // AConv and ADown
-  void upsample(const std::string& name, const View& src, const View& dst);
   // SPPELAN: last = ".cv5.conv"; linear_res: yolo26.yaml's SPPF (cv1 without activation, x added to the output)
   void sppf(const std::string& pfx, const View& x, const View& out, const char* last = ".cv2.conv", bool linear_res = false);
   void fuse_front();         // model.1 (3x3 stride 2) + model.2.cv1 (1x1) as one launch on the split-f16x3 path

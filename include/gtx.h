@@ -510,7 +510,8 @@ int gtx_op_rt_pool2(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, i
 int gtx_op_rt_dwconv(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int c, int k, int stride, const void* x, int in_cstride, int in_coff,
                      const float* wt, const float* bias, int act, const void* res, int res_cstride, int res_coff, void* out, int out_cstride,
                      int out_coff, int* saturated);
-/* Nearest 2x upsampling as RT-DETR's neck runs it (a raw copy of 8-channel groups): y [n_alloc][2 h][2 w][out_cstride]. */
+/* Nearest 2x upsampling as RT-DETR's neck runs it: gtx_op_upsample2x's launch behind the map hooks' argument checks, on the first n of
+ * n_alloc images; y [n_alloc][2 h][2 w][out_cstride]. */
 int gtx_op_rt_upsample2x(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int c, const void* x, int in_cstride, int in_coff, void* y,
                          int out_cstride, int out_coff);
 /* Map -> token rows: src [n_alloc * h * w][c] plain fp32 = the map's values and q = src + pos[row % (h w)], pos [h * w][c]. pos and q
