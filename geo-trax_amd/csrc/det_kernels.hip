@@ -9,11 +9,10 @@
 #include <cmath>
 
 #include "det_kernels.hpp"
-#include "head_reg1.hpp"
+#include "head_device.hpp"
 
 namespace gtx {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
 // ============================================================================ letterbox
@@ -857,31 +856,10 @@ void launch_upsample2x(size_t es, const void* x, int n, int h, int w, int c, int
 }
 
 // ============================================================================ head decode
-template <typename T> __device__ __forceinline__ float ldf(const T* p) { return (float)*p; }
+// The arithmetic of every kernel of this section is head_device.hpp's; what stays here is which lane takes which anchor.
 
-__device__ __forceinline__ int find_level(const HeadParams& hp, int a) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < kMaxLevels; ++i)
-    if (i < hp.n_levels && a >= hp.lv[i].anchor_begin) l = i;
-  return l;
-}
-
-template <typename T> __device__ __forceinline__ void load8(const T* p, float (&v)[8]);
-template <> __device__ __forceinline__ void load8<_Float16>(const _Float16* p, float (&v)[8]) {
-  const half8 h = *reinterpret_cast<const half8*>(p);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) v[i] = (float)h[i];
-}
-template <> __device__ __forceinline__ void load8<float>(const float* p, float (&v)[8]) {
-  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-
-// Class branch of Detect folded into the score gate: final 1x1 conv (nc x cc) + sigmoid + max
-// over classes + threshold + compaction. 16 lanes share an anchor, each owning 8-channel chunks of
-// its cls features (one fully coalesced 16-B load per lane per 128 channels), partial dot products
-// are combined with 4 xor-shuffles.
+// Class branch of Detect folded into the score gate: final 1x1 conv (nc x cc) + sigmoid (cls_scores4: 16 lanes share an anchor) + max
+// over classes + threshold + compaction.
 template <typename T>
 __global__ __launch_bounds__(256) void head_candidates_kernel(const HeadParams hp, const NmsBuffers nb) {
   const int sub = threadIdx.x & 15;
@@ -892,33 +870,15 @@ __global__ __launch_bounds__(256) void head_candidates_kernel(const HeadParams h
   const HeadLevel& L = hp.lv[l];
   const int la = (valid ? a : 0) - L.anchor_begin;
   const T* fc = static_cast<const T*>(L.feat) + ((size_t)n * L.h * L.w + la) * L.cstride + L.cb;
-  const int chunks = L.cc >> 3;
+  const int nc = hp.nc;
   float best = -1.f;
   int best_c = 0;
-  for (int c0 = 0; c0 < hp.nc; c0 += 4) {
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int ch = sub; ch < chunks; ch += 16) {
-      float f[8];
-      load8<T>(fc + ch * 8, f);
+  for (int c0 = 0; c0 < nc; c0 += 4) {
+    float sc[4];
+    cls_scores4<T>(L, fc, sub, c0, nc, sc);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (c0 + j < hp.nc) {
-          float w[8];
-          load8<float>(L.wc + (size_t)(c0 + j) * L.cc + ch * 8, w);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc[j] = fmaf(f[e], w[e], acc[j]);
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-      for (int o = 8; o >= 1; o >>= 1) acc[j] += __shfl_xor(acc[j], o, 64);
-      if (c0 + j < hp.nc) {
-        const float sc = 1.f / (1.f + expf(-(acc[j] + L.bc[c0 + j])));
-        if (sc > best) { best = sc; best_c = c0 + j; }
-      }
-    }
+    for (int j = 0; j < 4; ++j)
+      if (sc[j] > best) { best = sc[j]; best_c = c0 + j; }   // -1 past the last class: never above best
   }
   if (valid && sub == 0 && best > hp.conf && ((hp.class_mask[best_c >> 6] >> (best_c & 63)) & 1ull)) {
     const int idx = atomicAdd(&nb.count[n], 1);
@@ -933,44 +893,6 @@ __global__ __launch_bounds__(256) void head_candidates_kernel(const HeadParams h
       }
     }
   }
-}
-
-// DFL tail shared by the decode kernels: lane = side*16 + bin holds one box logit; softmax
-// expectation per side, dist2bbox(xywh) * stride. Returns xywh in network pixels on every lane.
-__device__ __forceinline__ float4 dfl_box(const HeadLevel& L, float acc, int la, int lane) {
-  // softmax over the 16 lanes of a side
-  float m = acc;
-#pragma unroll
-  for (int o = 8; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  const float e = expf(acc - m);
-  float se = e, sw = e * (float)(lane & 15);
-#pragma unroll
-  for (int o = 8; o >= 1; o >>= 1) {
-    se += __shfl_xor(se, o, 64);
-    sw += __shfl_xor(sw, o, 64);
-  }
-  const float d = sw / se;
-  const float d0 = __shfl(d, 0, 64), d1 = __shfl(d, 16, 64), d2 = __shfl(d, 32, 64), d3 = __shfl(d, 48, 64);
-  const float ax = (float)(la % L.w) + 0.5f, ay = (float)(la / L.w) + 0.5f;
-  const float x1 = ax - d0, y1 = ay - d1, x2 = ax + d2, y2 = ay + d3;
-  return make_float4((x1 + x2) * 0.5f * L.stride, (y1 + y2) * 0.5f * L.stride, (x2 - x1) * L.stride,
-                     (y2 - y1) * L.stride);
-}
-
-// Box branch for one anchor by one wave: 64 box logits (lane = side*16 + bin), DFL softmax
-// expectation per side, dist2bbox(xywh) * stride. Returns xywh in network pixels on every lane.
-template <typename T>
-__device__ __forceinline__ float4 anchor_box(const HeadLevel& L, const T* f, int la, int lane) {
-  // lane k holds box feature k (and k+64); the 64x cb mat-vec then takes each feature by shuffle and
-  // one coalesced 256-B line of the transposed weights [cb][64] per feature.
-  const float f0 = lane < L.cb ? ldf(f + lane) : 0.f;
-  const float f1 = lane + 64 < L.cb ? ldf(f + lane + 64) : 0.f;
-  float acc = L.bb[lane];
-  const float* wr = L.wb + lane;
-  const int k0 = min(L.cb, 64);
-  for (int k = 0; k < k0; ++k) acc = fmaf(__shfl(f0, k, 64), wr[(size_t)k * 64], acc);
-  for (int k = 64; k < L.cb; ++k) acc = fmaf(__shfl(f1, k - 64, 64), wr[(size_t)k * 64], acc);
-  return dfl_box(L, acc, la, lane);
 }
 
 // One wave per candidate; the transposed box weights of every level ([cb][64] each) are staged in
@@ -995,6 +917,7 @@ __global__ __launch_bounds__(256) void head_boxes_kernel(const HeadParams hp, co
     const HeadLevel& L = hp.lv[l];
     const int la = a - L.anchor_begin;
     const T* f = static_cast<const T*>(L.feat) + ((size_t)n * L.h * L.w + la) * L.cstride;
+    // head_raw_kernel's two box_chain calls written out (weights in LDS): through the accessors this kernel's code comes out 2 % slower
     const float f0 = lane < L.cb ? ldf(f + lane) : 0.f;
     const float f1 = lane + 64 < L.cb ? ldf(f + lane + 64) : 0.f;
     float acc = L.bb[lane];
@@ -1002,39 +925,14 @@ __global__ __launch_bounds__(256) void head_boxes_kernel(const HeadParams hp, co
     const int k0 = min(L.cb, 64);
     for (int k = 0; k < k0; ++k) acc = fmaf(__shfl(f0, k, 64), wr[k * 64], acc);
     for (int k = 64; k < L.cb; ++k) acc = fmaf(__shfl(f1, k - 64, 64), wr[k * 64], acc);
-    const float4 b = dfl_box(L, acc, la, lane);
-    if (lane == 0) {
-      const float hw = b.z / 2.f, hh = b.w / 2.f;   // xywh2xyxy
-      reinterpret_cast<float4*>(nb.cand_box)[o] = make_float4(b.x - hw, b.y - hh, b.x + hw, b.y + hh);
-    }
-  }
-}
-
-// Debug / parity: full decode of every anchor -> [A][4+nc].
-template <typename T>
-__global__ __launch_bounds__(256) void head_raw_kernel(const HeadParams hp, float* __restrict__ out, int logits) {
-  const int n = blockIdx.y;
-  const int lane = threadIdx.x & 63;
-  const int a = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (a >= hp.n_anchors) return;
-  const int l = find_level(hp, a);
-  const HeadLevel& L = hp.lv[l];
-  const int la = a - L.anchor_begin;
-  const T* f = static_cast<const T*>(L.feat) + ((size_t)n * L.h * L.w + la) * L.cstride;
-  const float4 b = anchor_box<T>(L, f, la, lane);
-  float* o = out + ((size_t)n * hp.n_anchors + a) * (4 + hp.nc);
-  if (lane == 0) { o[0] = b.x; o[1] = b.y; o[2] = b.z; o[3] = b.w; }
-  const T* fc = f + L.cb;
-  for (int c = lane; c < hp.nc; c += 64) {
-    float acc = L.bc[c];
-    for (int k = 0; k < L.cc; ++k) acc = fmaf(ldf(fc + k), L.wc[c * L.cc + k], acc);
-    o[4 + c] = logits ? acc : 1.f / (1.f + expf(-acc));
+    const float4 b = dfl_xywh(acc, la, L.w, L.stride, lane);
+    if (lane == 0) reinterpret_cast<float4*>(nb.cand_box)[o] = xywh_to_xyxy(b);
   }
 }
 
 // ---- reg_max = 1 (yolo26.yaml's Detect): the box branch's last 1x1 has four outputs, the signed distances themselves; no DFL.
-// Four lanes per candidate, lane j forming side j (head_reg1.hpp: the sparse form's arithmetic); 64 candidates per workgroup and
-// step. Every lane of a group of four follows the same candidate, so the shuffles below stay inside active groups.
+// Four lanes per candidate, lane j forming side j (reg1_side); 64 candidates per workgroup and step. Every lane of a group of four
+// follows the same candidate, so the shuffles below stay inside active groups.
 template <typename T>
 __global__ __launch_bounds__(256) void head_boxes_r1_kernel(const HeadParams hp, const NmsBuffers nb) {
   const int n = blockIdx.y;
@@ -1055,9 +953,9 @@ __global__ __launch_bounds__(256) void head_boxes_r1_kernel(const HeadParams hp,
   }
 }
 
-// Debug / parity, reg_max = 1: every anchor -> [A][4+nc], the box as xywh like head_raw_kernel's. One wave per anchor.
-template <typename T>
-__global__ __launch_bounds__(256) void head_raw_r1_kernel(const HeadParams hp, float* __restrict__ out, int logits) {
+// Debug / parity: full decode of every anchor -> [A][4+nc], the box as xywh. One wave per anchor; kReg1: lanes 0..3 form the sides.
+template <typename T, bool kReg1>
+__global__ __launch_bounds__(256) void head_raw_kernel(const HeadParams hp, float* __restrict__ out, int logits) {
   const int n = blockIdx.y;
   const int lane = threadIdx.x & 63;
   const int a = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -1065,16 +963,24 @@ __global__ __launch_bounds__(256) void head_raw_r1_kernel(const HeadParams hp, f
   const HeadLevel& L = hp.lv[find_level(hp, a)];
   const int la = a - L.anchor_begin;
   const T* f = static_cast<const T*>(L.feat) + ((size_t)n * L.h * L.w + la) * L.cstride;
-  const float d = reg1_side([&](int k) { return ldf(f + k); }, L.cb, L.wb, L.bb, lane & 3);
-  const float4 b = reg1_xyxy(__shfl(d, 0, 64), __shfl(d, 1, 64), __shfl(d, 2, 64), __shfl(d, 3, 64), la, L.w, L.stride);
-  float* o = out + ((size_t)n * hp.n_anchors + a) * (4 + hp.nc);
-  if (lane == 0) { o[0] = (b.x + b.z) * 0.5f; o[1] = (b.y + b.w) * 0.5f; o[2] = b.z - b.x; o[3] = b.w - b.y; }
-  const T* fc = f + L.cb;
-  for (int c = lane; c < hp.nc; c += 64) {
-    float acc = L.bc[c];
-    for (int k = 0; k < L.cc; ++k) acc = fmaf(ldf(fc + k), L.wc[c * L.cc + k], acc);
-    o[4 + c] = logits ? acc : 1.f / (1.f + expf(-acc));
+  float4 b;
+  if constexpr (kReg1) {
+    const float d = reg1_side([&](int k) { return ldf(f + k); }, L.cb, L.wb, L.bb, lane & 3);
+    const float4 c = reg1_xyxy(__shfl(d, 0, 64), __shfl(d, 1, 64), __shfl(d, 2, 64), __shfl(d, 3, 64), la, L.w, L.stride);
+    b = make_float4((c.x + c.z) * 0.5f, (c.y + c.w) * 0.5f, c.z - c.x, c.w - c.y);
+  } else {
+    // lane k holds box feature k (and k + 64); the 64 x cb mat-vec takes each feature by shuffle and one coalesced 256-B line of the
+    // transposed weights [cb][64] per feature
+    const float f0 = lane < L.cb ? ldf(f + lane) : 0.f;
+    const float f1 = lane + 64 < L.cb ? ldf(f + lane + 64) : 0.f;
+    const float* wr = L.wb + lane;
+    const auto weight = [&](int k) { return wr[(size_t)k * 64]; };
+    const float acc = box_chain(L.bb[lane], 0, min(L.cb, 64), [&](int k) { return __shfl(f0, k, 64); }, weight);
+    b = dfl_xywh(box_chain(acc, 64, L.cb, [&](int k) { return __shfl(f1, k - 64, 64); }, weight), la, L.w, L.stride, lane);
   }
+  float* o = out + ((size_t)n * hp.n_anchors + a) * (4 + hp.nc);
+  if (lane == 0) { o[0] = b.x; o[1] = b.y; o[2] = b.z; o[3] = b.w; }
+  raw_class_row(L, f + L.cb, hp.nc, lane, logits, o);
 }
 
 void launch_head_candidates(int dtype, const HeadParams& hp, int n, const NmsBuffers& nb, hipStream_t s) {
@@ -1116,17 +1022,17 @@ void launch_head_boxes(int dtype, const HeadParams& hp, int n, const NmsBuffers&
   GTX_HIP(hipGetLastError());
 }
 
-void launch_head_raw(int dtype, const HeadParams& hp, int n, float* out, bool logits, hipStream_t s) {
+template <typename T>
+static void launch_head_raw_t(const HeadParams& hp, int n, float* out, int logits, hipStream_t s) {
   dim3 grid(cdiv(hp.n_anchors * 64, 256), n), block(256);
-  if (hp.reg_max == 1) {
-    if (dtype == DT_F16) hipLaunchKernelGGL(head_raw_r1_kernel<_Float16>, grid, block, 0, s, hp, out, logits ? 1 : 0);
-    else hipLaunchKernelGGL(head_raw_r1_kernel<float>, grid, block, 0, s, hp, out, logits ? 1 : 0);
-    GTX_HIP(hipGetLastError());
-    return;
-  }
-  if (dtype == DT_F16) hipLaunchKernelGGL(head_raw_kernel<_Float16>, grid, block, 0, s, hp, out, logits ? 1 : 0);
-  else hipLaunchKernelGGL(head_raw_kernel<float>, grid, block, 0, s, hp, out, logits ? 1 : 0);
+  if (hp.reg_max == 1) hipLaunchKernelGGL((head_raw_kernel<T, true>), grid, block, 0, s, hp, out, logits);
+  else hipLaunchKernelGGL((head_raw_kernel<T, false>), grid, block, 0, s, hp, out, logits);
   GTX_HIP(hipGetLastError());
+}
+
+void launch_head_raw(int dtype, const HeadParams& hp, int n, float* out, bool logits, hipStream_t s) {
+  if (dtype == DT_F16) launch_head_raw_t<_Float16>(hp, n, out, logits ? 1 : 0, s);
+  else launch_head_raw_t<float>(hp, n, out, logits ? 1 : 0, s);
 }
 
 // ============================================================================ NMS
@@ -1304,10 +1210,7 @@ __global__ __launch_bounds__(1024) void nms_resolve_kernel(const NmsBuffers nb, 
     const int slot = s_prefix[wl] + __popcll(s_keep[wl] & (bit - 1ull));
     if (slot >= nb.max_det) continue;
     float4 b = boxes[i];
-    b.x = (b.x - padx) / gain; b.y = (b.y - pady) / gain;
-    b.z = (b.z - padx) / gain; b.w = (b.w - pady) / gain;
-    b.x = fminf(fmaxf(b.x, 0.f), fw); b.z = fminf(fmaxf(b.z, 0.f), fw);
-    b.y = fminf(fmaxf(b.y, 0.f), fh); b.w = fminf(fmaxf(b.w, 0.f), fh);
+    undo_letterbox(b, gain, padx, pady, fw, fh);
     float* r = rows + (size_t)slot * 6;
     r[0] = b.x; r[1] = b.y; r[2] = b.z; r[3] = b.w;
     r[4] = nb.s_score[(size_t)n * nb.nms_cap + i];
@@ -1423,10 +1326,7 @@ __global__ __launch_bounds__(1024) void nms_small_kernel(const NmsBuffers nb, fl
       s_kbox[my_slot] = bi;
       const int slot = (int)(s_key[i] & 0xFFFu);
       float4 o = reinterpret_cast<const float4*>(nb.cand_box)[base + slot];
-      o.x = (o.x - padx) / gain; o.y = (o.y - pady) / gain;
-      o.z = (o.z - padx) / gain; o.w = (o.w - pady) / gain;
-      o.x = fminf(fmaxf(o.x, 0.f), fw); o.z = fminf(fmaxf(o.z, 0.f), fw);
-      o.y = fminf(fmaxf(o.y, 0.f), fh); o.w = fminf(fmaxf(o.w, 0.f), fh);
+      undo_letterbox(o, gain, padx, pady, fw, fh);
       float* r = rows + (size_t)my_slot * 6;
       r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = o.w;
       r[4] = nb.cand_score[base + slot];
@@ -1495,13 +1395,9 @@ void launch_nms(const NmsBuffers& nb, int n, float iou_thr, bool agnostic, int m
   GTX_CHECK(which == 2 || (unsigned)nb.cap <= kSmallAnchors, "nms: %d anchors, the single-workgroup kernel orders at most %u", nb.cap, kSmallAnchors);
   const int limit = std::min(max_nms, nb.nms_cap);
   const float cls_offset = agnostic ? 0.f : 7680.f;  // ultralytics max_wh
-  // ultralytics scale_boxes: gain = min ratio, pad = round((net - src*gain)/2 - 0.1)
-  const double gain = lb.gain;
-  const float padx = (float)std::nearbyint((lb.net_w - lb.src_w * gain) / 2 - 0.1);
-  const float pady = (float)std::nearbyint((lb.net_h - lb.src_h * gain) / 2 - 0.1);
+  const LetterboxUndo lu = letterbox_undo(lb);
   if (which != 2) {
-    hipLaunchKernelGGL(nms_small_kernel, dim3(n), dim3(1024), 0, s, nb, iou_thr, cls_offset, (float)gain, padx, pady,
-                       (float)lb.src_w, (float)lb.src_h);
+    hipLaunchKernelGGL(nms_small_kernel, dim3(n), dim3(1024), 0, s, nb, iou_thr, cls_offset, lu.gain, lu.padx, lu.pady, lu.fw, lu.fh);
     GTX_HIP(hipGetLastError());
   }
   if (which == 1) return;
@@ -1509,8 +1405,7 @@ void launch_nms(const NmsBuffers& nb, int n, float iou_thr, bool agnostic, int m
   GTX_HIP(hipGetLastError());
   hipLaunchKernelGGL(nms_mask_kernel, dim3(256, n), dim3(256), 0, s, nb, iou_thr, cls_offset);
   GTX_HIP(hipGetLastError());
-  hipLaunchKernelGGL(nms_resolve_kernel, dim3(n), dim3(1024), 0, s, nb, (float)gain, padx, pady,
-                     (float)lb.src_w, (float)lb.src_h);
+  hipLaunchKernelGGL(nms_resolve_kernel, dim3(n), dim3(1024), 0, s, nb, lu.gain, lu.padx, lu.pady, lu.fw, lu.fh);
   GTX_HIP(hipGetLastError());
 }
 

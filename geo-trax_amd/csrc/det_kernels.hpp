@@ -62,7 +62,7 @@ struct HeadParams {
   int nc;
   float conf;           // score threshold (strict >)
   unsigned long long class_mask[2];  // bit c set = class c kept (ultralytics `classes`); 128 classes
-  int reg_max;          // 1: yolo26.yaml's Detect, the box branch ends in four signed distances (the *_r1_kernel forms); else 16 DFL bins per side
+  int reg_max;          // 1: yolo26.yaml's Detect, the box branch ends in four signed distances (head_boxes_r1_kernel, the kReg1 forms); else 16 DFL bins per side
 };
 
 struct NmsBuffers {

@@ -8,17 +8,17 @@
 // kernels it replaces (conv_k32_split.hip, through conv_split_device.hpp: same packed weight images and power-of-two scales, same v_mfma_f32_16x16x32_f16
 // sequence per output pixel -- chunk, kernel row, kernel column, small terms first -- same bias start, SiLU and hi / lo split,
 // zero padding at the image border for both layers), so a candidate's 64 box features are the dense path's bit for bit.
-// The wave then decodes its candidates' boxes (the final 1x1 convolution + DFL of head_boxes_kernel, same operations in the same
-// order), so the sparse path is one launch between the score gate and the NMS.
+// The wave then decodes its candidates' boxes (the final 1x1 convolution + DFL of head_boxes_kernel: head_device.hpp), so the
+// sparse path is one launch between the score gate and the NMS.
 // The dense convolutions stay available (Detector: GTX_SPARSE_BOX=0, the debug read-backs, more candidates than the buffer holds).
 // kReg1 (yolo26.yaml's Detect, reg_max = 1): the same two layers, then the four-output 1x1 of head_boxes_r1_kernel straight to xyxy
-// (head_reg1.hpp) -- no 64-bin stage. The 16-bin instantiation is the kernel as it was.
+// (head_device.hpp: reg1_side, reg1_xyxy) -- no 64-bin stage.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
 #include "conv_split_device.hpp"
 #include "det_kernels.hpp"
-#include "head_reg1.hpp"
+#include "head_device.hpp"
 
 namespace gtx {
 
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void head_sparse_box_kernel(const SparseBox sb
     }
   }
   if constexpr (kReg1) {
-    // ---- reg_max = 1: lane 4 c + j forms side j of candidate c (head_boxes_r1_kernel's arithmetic, head_reg1.hpp), lane 4 c stores the
+    // ---- reg_max = 1: lane 4 c + j forms side j of candidate c (reg1_side, as head_boxes_r1_kernel), lane 4 c stores the
     // box. A short last group's repeated candidates and an entry or anchor outside its buffer / level are not stored.
     const int c = (lane >> 2) & 3, j = lane & 3, base = lane & 12;
     const int mine_ci = c == 0 ? ci[0] : (c == 1 ? ci[1] : (c == 2 ? ci[2] : ci[3]));
@@ -206,37 +206,16 @@ __global__ __launch_bounds__(256) void head_sparse_box_kernel(const SparseBox sb
     flag_saturation(sb.sat_flag, sat, lane);
     return;
   }
-  // ---- box decode of the wave's candidates (head_boxes_kernel's arithmetic: the 64 x 64 final 1x1 convolution as one fmaf chain
-  // per output in feature order, DFL softmax expectation per side, dist2bbox, xywh -> xyxy) ----
+  // ---- box decode of the wave's candidates: lane = side * 16 + bin forms its output of the 64 x 64 final 1x1 convolution from the
+  // LDS row (box_chain), then the wave the box (dfl_xywh, xywh_to_xyxy): head_device.hpp, as head_boxes_kernel ----
 #pragma unroll 1
   for (int c = 0; c < kCandPerWave; ++c) {
     if (first + c >= cnt) break;                   // wave-uniform
-    float a = L.bb[lane];
     const float* wr = L.wb + lane;
-#pragma unroll 8
-    for (int k = 0; k < 64; ++k) a = fmaf(fl[c * 64 + k], wr[(size_t)k * 64], a);
+    const float a = box_chain<8>(L.bb[lane], 0, 64, [&](int k) { return fl[c * 64 + k]; }, [&](int k) { return wr[(size_t)k * 64]; });
     const int anchor = __builtin_amdgcn_readfirstlane(nb.cand_anchor[(size_t)n * nb.cap + ci[c]]);
-    const int la = anchor - L.anchor_begin;
-    // softmax over the 16 lanes of a side
-    float m = a;
-#pragma unroll
-    for (int o = 8; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    const float e = expf(a - m);
-    float se = e, sw = e * (float)(lane & 15);
-#pragma unroll
-    for (int o = 8; o >= 1; o >>= 1) {
-      se += __shfl_xor(se, o, 64);
-      sw += __shfl_xor(sw, o, 64);
-    }
-    const float d = sw / se;
-    const float d0 = __shfl(d, 0, 64), d1 = __shfl(d, 16, 64), d2 = __shfl(d, 32, 64), d3 = __shfl(d, 48, 64);
-    const float ax = (float)(la % L.W) + 0.5f, ay = (float)(la / L.W) + 0.5f;
-    const float bx1 = ax - d0, by1 = ay - d1, bx2 = ax + d2, by2 = ay + d3;
-    const float4 b = make_float4((bx1 + bx2) * 0.5f * L.stride, (by1 + by2) * 0.5f * L.stride, (bx2 - bx1) * L.stride, (by2 - by1) * L.stride);
-    if (lane == 0) {
-      const float hw = b.z / 2.f, hh = b.w / 2.f;   // xywh2xyxy
-      reinterpret_cast<float4*>(nb.cand_box)[(size_t)n * nb.cap + ci[c]] = make_float4(b.x - hw, b.y - hh, b.x + hw, b.y + hh);
-    }
+    const float4 b = dfl_xywh(a, anchor - L.anchor_begin, L.W, L.stride, lane);
+    if (lane == 0) reinterpret_cast<float4*>(nb.cand_box)[(size_t)n * nb.cap + ci[c]] = xywh_to_xyxy(b);
   }
   flag_saturation(sb.sat_flag, sat, lane);
 }

@@ -5,8 +5,8 @@
 // `classes`, cuts to `max_det` and scales the boxes to the frame. Gating at conf first changes nothing (what the cut keeps of the
 // gated entries is what the gate keeps of the cut), so the tail here is
 //   head_candidates_kernel (every class kept)   anchors whose best score clears conf -> the candidate arrays, at most one per anchor
-//   v10_select_kernel                          stage 1 over the candidates, the nc scores of the anchors kept (the gate's arithmetic
-//                                              again, operation for operation), stage 2 over them; the rows sorted by score
+//   v10_select_kernel                          stage 1 over the candidates, the nc scores of the anchors kept (the gate's own
+//                                              cls_scores4, head_device.hpp), stage 2 over them; the rows sorted by score
 //   head_sparse_box_kernel / head_boxes_kernel the one-to-one box branch at the at most 300 entries kept
 //   v10_rows_kernel                            `classes`, the max_det cut, scale_boxes + clip, the result rows
 // in place of head_candidates -> head_sparse_box -> nms_small. Without ties the two stages equal one global top-300 over all
@@ -17,61 +17,12 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
-#include <cmath>
-
 #include "det_kernels.hpp"
+#include "head_device.hpp"
 
 namespace gtx {
 
 namespace {
-
-typedef _Float16 half8v __attribute__((ext_vector_type(8)));
-
-template <typename T> __device__ __forceinline__ void ld8(const T* p, float (&v)[8]);
-template <> __device__ __forceinline__ void ld8<_Float16>(const _Float16* p, float (&v)[8]) {
-  const half8v h = *reinterpret_cast<const half8v*>(p);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) v[i] = (float)h[i];
-}
-template <> __device__ __forceinline__ void ld8<float>(const float* p, float (&v)[8]) {
-  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-
-__device__ __forceinline__ int level_of_anchor(const HeadParams& hp, int a) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < kMaxLevels; ++i)
-    if (i < hp.n_levels && a >= hp.lv[i].anchor_begin) l = i;
-  return l;
-}
-
-// Scores of classes c0 .. c0 + 3 of one anchor by the 16 lanes that share it: head_candidates_kernel's operations in its order
-// (8-channel chunks strided over the lanes, one fmaf chain per class, four xor-shuffles, bias, sigmoid). -1 past the last class.
-template <typename T>
-__device__ __forceinline__ void cls_scores4(const HeadLevel& L, const T* fc, int sub, int c0, int nc, float (&sc)[4]) {
-  const int chunks = L.cc >> 3;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int ch = sub; ch < chunks; ch += 16) {
-    float f[8];
-    ld8<T>(fc + ch * 8, f);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (c0 + j < nc) {
-        float w[8];
-        ld8<float>(L.wc + (size_t)(c0 + j) * L.cc + ch * 8, w);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[j] = fmaf(f[e], w[e], acc[j]);
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-#pragma unroll
-    for (int o = 8; o >= 1; o >>= 1) acc[j] += __shfl_xor(acc[j], o, 64);
-    sc[j] = c0 + j < nc ? 1.f / (1.f + expf(-(acc[j] + L.bc[c0 + j]))) : -1.f;
-  }
-}
 
 __device__ __forceinline__ unsigned long long entry_key(float score, unsigned index) {   // larger score first, then the lower index
   return ((unsigned long long)__float_as_uint(score) << 32) | (unsigned long long)(0xFFFFFFFFu - index);   // scores are positive: their bits are monotone
@@ -160,7 +111,7 @@ __global__ __launch_bounds__(kSelThreads) void v10_select_kernel(const HeadParam
     for (int k0 = 0; k0 < K; k0 += kSelThreads / 16) {
       const int k = k0 + grp;
       const int a = s_anchor[min(k, K - 1)];
-      const HeadLevel& L = hp.lv[level_of_anchor(hp, a)];
+      const HeadLevel& L = hp.lv[find_level(hp, a)];
       const T* fc = static_cast<const T*>(L.feat) + ((size_t)n * L.h * L.w + (a - L.anchor_begin)) * L.cstride + L.cb;
       for (int c0 = 0; c0 < nc; c0 += 4) {
         float sc[4];
@@ -215,7 +166,7 @@ __global__ __launch_bounds__(kSelThreads) void v10_select_kernel(const HeadParam
     sel.cand_anchor[o] = a;
     sel.cand_cls[o] = c;
     if (sel.lvl_count) {                              // filed under its level for the sparse box branch (kept <= kV10Keep <= lvl_cap)
-      const int l = level_of_anchor(hp, a);
+      const int l = find_level(hp, a);
       const int q = atomicAdd(&sel.lvl_count[n * kMaxLevels + l], 1);
       sel.lvl_list[((size_t)n * kMaxLevels + l) * sel.lvl_cap + q] = tid;
     }
@@ -223,7 +174,7 @@ __global__ __launch_bounds__(kSelThreads) void v10_select_kernel(const HeadParam
   if (tid == 0) sel.count[n] = kept;
 }
 
-// The rows of image n in score order: `classes`, the max_det cut, ultralytics' scale_boxes + clip_boxes (nms_small_kernel's sequence)
+// The rows of image n in score order: `classes`, the max_det cut, ultralytics' scale_boxes + clip_boxes (undo_letterbox)
 __global__ __launch_bounds__(kSortCap) void v10_rows_kernel(const NmsBuffers sel, unsigned long long mask0, unsigned long long mask1, float gain, float padx,
                                                             float pady, float fw, float fh) {
   __shared__ int wave_cnt[kSortCap / 64];
@@ -246,10 +197,7 @@ __global__ __launch_bounds__(kSortCap) void v10_rows_kernel(const NmsBuffers sel
   }
   if (keep && slot < sel.max_det) {
     float4 b = reinterpret_cast<const float4*>(sel.cand_box)[o];
-    b.x = (b.x - padx) / gain; b.y = (b.y - pady) / gain;
-    b.z = (b.z - padx) / gain; b.w = (b.w - pady) / gain;
-    b.x = fminf(fmaxf(b.x, 0.f), fw); b.z = fminf(fmaxf(b.z, 0.f), fw);
-    b.y = fminf(fmaxf(b.y, 0.f), fh); b.w = fminf(fmaxf(b.w, 0.f), fh);
+    undo_letterbox(b, gain, padx, pady, fw, fh);
     float* r = sel.out_rows + ((size_t)n * sel.max_det + slot) * 6;
     r[0] = b.x; r[1] = b.y; r[2] = b.z; r[3] = b.w;
     r[4] = sel.cand_score[o];
@@ -270,11 +218,8 @@ void launch_v10_select(int dtype, const HeadParams& hp, int n, const NmsBuffers&
 }
 
 void launch_v10_rows(const NmsBuffers& sel, const unsigned long long class_mask[2], int n, const Letterbox& lb, hipStream_t s) {
-  const double gain = lb.gain;                        // ultralytics scale_boxes: gain = min ratio, pad = round((net - src * gain) / 2 - 0.1)
-  const float padx = (float)std::nearbyint((lb.net_w - lb.src_w * gain) / 2 - 0.1);
-  const float pady = (float)std::nearbyint((lb.net_h - lb.src_h * gain) / 2 - 0.1);
-  hipLaunchKernelGGL(v10_rows_kernel, dim3(n), dim3(kSortCap), 0, s, sel, class_mask[0], class_mask[1], (float)gain, padx, pady, (float)lb.src_w,
-                     (float)lb.src_h);
+  const LetterboxUndo lu = letterbox_undo(lb);
+  hipLaunchKernelGGL(v10_rows_kernel, dim3(n), dim3(kSortCap), 0, s, sel, class_mask[0], class_mask[1], lu.gain, lu.padx, lu.pady, lu.fw, lu.fh);
   GTX_HIP(hipGetLastError());
 }
 
