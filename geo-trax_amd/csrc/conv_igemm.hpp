@@ -107,6 +107,12 @@ struct ConvConfig {
   int th, tw;  // output pixel tile (rows x cols)
 };
 
+// Both configurations name one kernel instantiation: what two problems need to share a grouped launch.
+inline bool same_kernel(const ConvConfig& a, const ConvConfig& b) {
+  return a.dtype == b.dtype && a.ks == b.ks && a.stride == b.stride && a.bn == b.bn && a.kc == b.kc && a.variant == b.variant &&
+         a.th == b.th && a.tw == b.tw;
+}
+
 // Picks the tile configuration used for a layer shape.
 // force_kc / force_bn > 0 pin the K chunk / cout tile (grouped launches: every member must use the same kernel instantiation).
 ConvConfig conv_pick_config(int dtype, int ks, int stride, int cin, int cout, int force_kc = 0, int force_bn = 0);

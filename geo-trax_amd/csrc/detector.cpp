@@ -1,12 +1,10 @@
-// YOLOv8 / YOLO11 / YOLOv10 / YOLO26 (detect) graph builder + executor: the trunk (yolo_trunk.cpp walks the layer table of ultralytics' cfg/models/v8/yolov8.yaml,
-// yolov8-p2.yaml or cfg/models/11/yolo11.yaml, whichever the tensor names tell) and the Detect layer on the levels, strides and prefix the
-// table's Detect row gives (model.22, model.28 of the P2 graph: a fourth level at stride 4, or model.23 of YOLO11 and YOLOv10: a class branch of
-// depthwise + pointwise pairs; YOLOv10's and YOLO26's one-to-one pair of branches ends in the top-300 cut of v10_select.hip instead of the NMS; YOLO26's box branch has reg_max = 1, four signed distances instead of 4 x 16 DFL bins, read off its last 1x1's row count); channel widths and bottleneck counts are read off the tensor shapes, so every scale (n/s/m/l/x) loads unchanged.
+// The YOLO detector's runtime around its graph (YOLOv8 / P2, YOLOv9, YOLOv10, YOLO11, YOLO26 `detect` checkpoints): the plan that
+// computes the letterbox's padding rows once, finalize() with the post-pass workspaces, the post-pass itself (score gate, box
+// branch, NMS or the one-to-one head's top-300 cut, result copies), what collect() finishes for a batch the pass left short, and
+// the debug read-backs. The graph is built in detect_head.cpp: the trunk through yolo_trunk.cpp, then the Detect head.
 #include "detector.hpp"
-#include "split_format.hpp"
 
 #include <algorithm>
-#include <cmath>
 
 namespace gtx {
 
@@ -29,252 +27,6 @@ std::unique_ptr<NetRuntime> Detector::make_exact() const {
   gtx_det_config c = cfg_;
   c.fp32_split = 0;
   return std::unique_ptr<NetRuntime>(new Detector(ctx_, c));
-}
-
-// One Conv op of the Detect head, with the grouped stages' K chunk / cout tile / plain output in force
-View Detector::head_conv(const std::string& name, const View& x, const View* out_slice) {
-  ConvArgs a;
-  a.out_slice = out_slice;
-  a.plain_out = fmt_ == DT_F32S && plain_out_;
-  a.force_kc = force_kc_; a.force_bn = force_bn_;
-  return emit_named_conv(ops_, name, x, a);
-}
-
-void Detector::build_graph() {
-  const int H = lb_.net_h, W = lb_.net_w;
-  img_ = new_view(H, W, 4);
-  alloc_sat_flag();
-  const YoloTrunk::Levels trunk = trunk_.build(img_);
-  const std::vector<View>& lvl_in = trunk.in;     // the Detect layer's inputs, finest level first
-  const std::vector<float>& strides = trunk.strides;
-  det_pfx_ = trunk.det_pfx;
-  const int nl = (int)lvl_in.size();
-  GTX_CHECK(nl <= kMaxLevels, "internal: %d Detect levels", nl);
-  // v10Detect holds Detect's layers twice: cv2 / cv3 (one-to-many, followed by NMS) and one2one_cv2 / one2one_cv3 (followed by the
-  // top-300 cut, v10_select.hip). gtx_det_config.end2end picks the pair; the other pair's tensors are not read.
-  const bool has_o2o = has(det_pfx_ + ".one2one_cv2.0.0.conv.weight");
-  end2end_ = cfg_.end2end != 0;
-  GTX_CHECK(!end2end_ || has_o2o, "end2end: the checkpoint has no one-to-one head (%s.one2one_cv2 / one2one_cv3): only a YOLOv10 or YOLO26 file has", det_pfx_.c_str());
-  GTX_CHECK(!end2end_ || !cfg_.obj_feats, "end2end: obj_feats (ReID `model: auto`) is not implemented for the one-to-one head");
-  const std::string box_br = end2end_ ? ".one2one_cv2." : ".cv2.", cls_br = end2end_ ? ".one2one_cv3." : ".cv3.";
-  GTX_CHECK(has(det_pfx_ + box_br + "0.0.conv.weight") && has(det_pfx_ + cls_br + "0.2.weight"),
-            "%s: the checkpoint holds no %s / %s tensors (a fused YOLOv10 / YOLO26 export keeps the one-to-one head only: run it with end2end)", det_pfx_.c_str(),
-            box_br.substr(1, box_br.size() - 2).c_str(), cls_br.substr(1, cls_br.size() - 2).c_str());
-
-  // ---- Detect (model.22, or model.28 of the P2 graph) ----
-  // Stage 1 fuses the sibling convs cv2[l][0] and cv3[l][0] (same input) into one conv by
-  // stacking their output channels; stage 2 runs cv2[l][1] and cv3[l][1] on channel slices.
-  // The levels (three, four with P2) go out as one grouped launch per stage. The final 1x1 convs are folded
-  // into the decode kernels (the box one only runs for anchors that pass the score gate).
-  std::vector<Op> st1, st2;
-  const bool dw_cls = trunk.dw_cls;
-  std::vector<Op> dw_a, pw_a, dw_b;                // yolo11.yaml: per level, the class branch's DWConv / 1x1 Conv / DWConv in front of its last 1x1
-  head_ = HeadParams{};
-  head_.n_levels = nl;
-  head_.nc = cfg_.nc;
-  head_.conf = cfg_.conf;
-  head_.class_mask[0] = head_.class_mask[1] = cfg_.n_classes == 0 ? ~0ull : 0ull;
-  for (int i = 0; i < cfg_.n_classes; ++i)
-    if (cfg_.classes[i] >= 0 && cfg_.classes[i] < 128) head_.class_mask[cfg_.classes[i] >> 6] |= 1ull << (cfg_.classes[i] & 63);
-  int anchor = 0;
-  for (int l = 0; l < nl; ++l) {
-    const std::string b2 = det_pfx_ + box_br + std::to_string(l), b3 = det_pfx_ + cls_br + std::to_string(l);
-    const HostTensor &w20 = tensor(b2 + ".0.conv.weight"), &w30 = tensor(b3 + (dw_cls ? ".1.1.conv.weight" : ".0.conv.weight"));
-    const int cb = (int)w20.shape[0], cc = (int)w30.shape[0], cin = (int)w20.shape[1];
-    GTX_CHECK(cin == lvl_in[l].c && (dw_cls || (int)w30.shape[1] == cin), "Detect level %d input channels", l);
-    Op o1, o2, o3;
-    View h2;
-    if (dw_cls) {
-      // yolo11.yaml's Detect: the box branch as above on its own (cv2[l][0] is a launch of one 64-cout tile, the sparse box branch's
-      // image); the class branch is DWConv 3x3 + Conv 1x1 twice. Six ops per level, regrouped by stage below.
-      const size_t mark = ops_.size();
-      bool k32 = true;
-      for (int q = 0; q < nl; ++q) k32 = k32 && lvl_in[q].c % 32 == 0;
-      h2 = new_view(lvl_in[l].h, lvl_in[l].w, cb + cc);
-      View h2b = h2.slice(0, cb), h2c = h2.slice(cb, cc);
-      force_kc_ = fmt_ == DT_F16 ? (k32 ? 32 : 16) : 0;
-      force_bn_ = cb % 64 == 0 ? 64 : 32;
-      const View h1b = head_conv(b2 + ".0.conv", lvl_in[l], nullptr);
-      force_kc_ = fmt_ == DT_F16 ? (cb % 32 == 0 ? 32 : 16) : 0;
-      plain_out_ = true;
-      head_conv(b2 + ".1.conv", h1b, &h2b);
-      plain_out_ = false;
-      const View d0 = trunk_.dwconv(b3 + ".0.0.conv", lvl_in[l], 1);
-      force_kc_ = fmt_ == DT_F16 ? (k32 ? 32 : 16) : 0;
-      force_bn_ = cc % 64 == 0 ? 64 : 32;
-      const View p0 = head_conv(b3 + ".0.1.conv", d0, nullptr);
-      const View d1v = trunk_.dwconv(b3 + ".1.0.conv", p0, 1);
-      force_kc_ = fmt_ == DT_F16 ? (cc % 32 == 0 ? 32 : 16) : 0;
-      plain_out_ = true;
-      head_conv(b3 + ".1.1.conv", d1v, &h2c);
-      plain_out_ = false;
-      h2.plain = fmt_ == DT_F32S;
-      force_kc_ = force_bn_ = 0;
-      GTX_CHECK(ops_.size() == mark + 6, "internal: head op count");
-      o1 = ops_[mark]; o2 = ops_[mark + 1]; o3 = ops_[mark + 5];
-      dw_a.push_back(ops_[mark + 2]); pw_a.push_back(ops_[mark + 3]); dw_b.push_back(ops_[mark + 4]);
-      ops_.resize(mark);
-    } else {
-    // stacked stage-1 weights / bias
-    HostTensor ws;
-    ws.shape = {cb + cc, cin, 3, 3};
-    ws.data = w20.data;
-    ws.data.insert(ws.data.end(), w30.data.begin(), w30.data.end());
-    tensors_["__head" + std::to_string(l) + ".s1.weight"] = ws;
-    HostTensor bs;
-    bs.shape = {cb + cc};
-    bs.data = tensor(b2 + ".0.conv.bias").data;
-    const auto& b30 = tensor(b3 + ".0.conv.bias").data;
-    bs.data.insert(bs.data.end(), b30.begin(), b30.end());
-    tensors_["__head" + std::to_string(l) + ".s1.bias"] = bs;
-    const size_t mark = ops_.size();
-    // The levels run as grouped launches: one K chunk and one cout tile for all members of a stage. Widths that
-    // are multiples of 16 only (yolov8 n / m / x) take the 16-channel chunk; a stage with a member whose Cout is not a
-    // multiple of 64 takes the 32-cout tile.
-    bool k32 = true;
-    for (int q = 0; q < nl; ++q) k32 = k32 && lvl_in[q].c % 32 == 0;
-    force_kc_ = fmt_ == DT_F16 ? (k32 ? 32 : 16) : 0;
-    force_bn_ = (cb + cc) % 64 == 0 ? 64 : 32;
-    View h1 = head_conv("__head" + std::to_string(l) + ".s1", lvl_in[l], nullptr);
-    View h2v = new_view(h1.h, h1.w, cb + cc);
-    View h1b = h1.slice(0, cb), h1c = h1.slice(cb, cc), h2b = h2v.slice(0, cb), h2c = h2v.slice(cb, cc);
-    force_kc_ = fmt_ == DT_F16 ? ((cb % 32 == 0 && cc % 32 == 0) ? 32 : 16) : 0;
-    force_bn_ = (cb % 64 == 0 && cc % 64 == 0) ? 64 : 32;
-    plain_out_ = true;            // the decode kernels read these two as plain fp32
-    head_conv(b2 + ".1.conv", h1b, &h2b);
-    head_conv(b3 + ".1.conv", h1c, &h2c);
-    plain_out_ = false;
-    h2v.plain = fmt_ == DT_F32S;
-    force_kc_ = force_bn_ = 0;
-    // move the three freshly built single-problem ops into the grouped stage ops: one grouped launch per stage and kernel
-    // configuration (the levels of a stage share a launch when they share the kernel)
-    GTX_CHECK(ops_.size() == mark + 3, "internal: head op count");
-    o1 = ops_[mark]; o2 = ops_[mark + 1]; o3 = ops_[mark + 2];
-    ops_.resize(mark);
-    h2 = h2v;
-    }
-    // Sparse box branch (head_sparse.hip): the box half of stage 1 (cout tile 0 of the stacked image) and cv2[l][1] are evaluated
-    // at the candidate anchors only, after the score gate; stage 1 keeps its class half (cout tiles 1..), same packed image,
-    // same scale. Needs the 16x16x32 kernel's image (32-channel chunks, one 64-cout box tile); decided for all levels at once.
-    if (l == 0) {
-      sparse_on_ = fmt_ == DT_F32S && env_flag("GTX_SPARSE_BOX", true);
-      sparse_ = SparseBox{};
-      dense_box_ops_.clear();
-    }
-    sparse_on_ = sparse_on_ && cb == 64 && o1.cfg.variant == ConvForm::K32 && o1.cfg.bn == 64 && o2.cfg.variant == ConvForm::K32 && cin % 32 == 0;
-    head_ops_[l][0] = o1; head_ops_[l][1] = o2; head_ops_[l][2] = o3;
-
-    HeadLevel& L = head_.lv[l];
-    L.feat = h2.ptr; L.h = h2.h; L.w = h2.w; L.cstride = h2.cstride; L.cb = cb; L.cc = cc;
-    L.stride = strides[l];
-    L.anchor_begin = anchor;
-    anchor += h2.h * h2.w;
-    auto upload = [&](const std::vector<float>& v) {
-      float* d = (float*)alloc(v.size() * sizeof(float));
-      GTX_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-      return d;
-    };
-    const HostTensor &wb = tensor(b2 + ".2.weight"), &wc = tensor(b3 + ".2.weight");
-    // reg_max off the last box convolution's rows: 4 x 16 DFL bins, or yolo26.yaml's four distances (reg_max = 1)
-    const int box_out = (int)wb.shape[0];
-    GTX_CHECK((box_out == 64 || box_out == 4) && (int)wb.shape[1] == cb, "Detect box head must have 4*16 outputs, or 4 (reg_max = 1); it has %d", box_out);
-    GTX_CHECK(l == 0 || head_.reg_max == box_out / 4, "Detect box branch: reg_max differs between levels");
-    head_.reg_max = box_out / 4;
-    GTX_CHECK(cb <= 128 && cc % 8 == 0, "Detect head widths cb=%d cc=%d are outside what the decode kernels support", cb, cc);
-    GTX_CHECK(l == 0 || cb == head_.lv[0].cb, "Detect box branch width differs between levels");
-    GTX_CHECK((int)wc.shape[0] == cfg_.nc && (int)wc.shape[1] == cc, "Detect cls head has %d outputs, nc=%d", (int)wc.shape[0], cfg_.nc);
-    {
-      std::vector<float> wbt((size_t)cb * box_out);  // [cb][64]: the decode wave reads one output per lane; reg_max = 1: [cb][4]
-      for (int o = 0; o < box_out; ++o)
-        for (int k = 0; k < cb; ++k) wbt[(size_t)k * box_out + o] = wb.data[(size_t)o * cb + k];
-      L.wb = upload(wbt);
-    }
-    L.bb = upload(tensor(b2 + ".2.bias").data);
-    L.wc = upload(wc.data); L.bc = upload(tensor(b3 + ".2.bias").data);
-    layer_views_[det_pfx_ + ".feat" + std::to_string(l)] = h2;
-  }
-  head_.n_anchors = anchor;
-  GTX_CHECK(end2end_ || anchor <= nms_max_anchors(), "%d anchors per image: the NMS kernels order at most %d (ties between candidates go to the lower anchor)", anchor,
-            nms_max_anchors());
-  {
-    auto same = [](const ConvConfig& a, const ConvConfig& b) {
-      return a.dtype == b.dtype && a.ks == b.ks && a.stride == b.stride && a.bn == b.bn && a.kc == b.kc &&
-             a.variant == b.variant && a.th == b.th && a.tw == b.tw;
-    };
-    auto add = [&](std::vector<Op>& stage, const char* name, const Op& o) {
-      for (Op& g : stage)
-        if (same(g.cfg, o.cfg) && g.grp.count < kMaxGroup) { g.grp.p[g.grp.count++] = o.grp.p[0]; return; }
-      Op g;
-      g.kind = Op::CONV;
-      g.name = stage.empty() ? std::string(name) : std::string(name) + "." + std::to_string(stage.size());
-      g.cfg = o.cfg;
-      g.grp.p[g.grp.count++] = o.grp.p[0];
-      stage.push_back(g);
-    };
-    std::vector<Op> d1, d2;                          // the dense box layers, kept for the debug read-backs and the overflow case
-    for (int l = 0; l < nl; ++l) {
-      Op o1 = head_ops_[l][0];
-      const Op &o2 = head_ops_[l][1], &o3 = head_ops_[l][2];
-      if (sparse_on_) {
-        const ConvProblem full = o1.grp.p[0];
-        const int cb = head_.lv[l].cb, cc = head_.lv[l].cc;
-        const size_t tile_bytes = (size_t)(full.Cin / o1.cfg.kc) * 9 * 64 * 128;   // one 64-cout tile of the packed image
-        SparseBoxLevel& S = sparse_.lv[l];
-        S.in = full.in; S.H = full.H; S.W = full.W; S.cstride = full.in_cstride; S.coff = full.in_coff; S.cin = full.Cin;
-        S.w1 = full.wpack; S.b1 = full.bias; S.sc1 = full.acc_scale;
-        S.w2 = o2.grp.p[0].wpack; S.b2 = o2.grp.p[0].bias; S.sc2 = o2.grp.p[0].acc_scale;
-        S.anchor_begin = head_.lv[l].anchor_begin;
-        S.wb = head_.lv[l].wb; S.bb = head_.lv[l].bb; S.stride = head_.lv[l].stride;
-        GTX_CHECK(full.bias && o2.grp.p[0].bias && o2.grp.p[0].Cin == 64 && o2.grp.p[0].Cout == 64, "sparse box branch: unexpected Detect box layers");
-        Op box1 = o1;                                // the box tile alone
-        box1.grp.p[0].Cout = cb;
-        add(d1, (det_pfx_ + ".box1").c_str(), box1);
-        add(d2, (det_pfx_ + ".box2").c_str(), o2);
-        if (dw_cls) {                                // stage 1 holds no class tile: the class branch's own 1x1 layers
-          add(st1, (det_pfx_ + ".stage1").c_str(), pw_a[l]);
-          add(st2, (det_pfx_ + ".stage2").c_str(), o3);
-          continue;
-        }
-        ConvProblem& p = o1.grp.p[0];                // the class tiles alone
-        p.wpack = static_cast<const char*>(full.wpack) + tile_bytes;
-        p.bias = full.bias + 64;
-        p.Cout = cc;
-        p.out_coff = full.out_coff + cb;
-        add(st1, (det_pfx_ + ".stage1").c_str(), o1);
-        add(st2, (det_pfx_ + ".stage2").c_str(), o3);
-      } else {
-        if (dw_cls) add(st1, (det_pfx_ + ".stage1").c_str(), pw_a[l]);
-        add(st1, (det_pfx_ + ".stage1").c_str(), o1);
-        add(st2, (det_pfx_ + ".stage2").c_str(), o2);
-        add(st2, (det_pfx_ + ".stage2").c_str(), o3);
-      }
-    }
-    if (sparse_on_) {
-      sparse_.n_levels = nl;
-      sparse_.reg_max = head_.reg_max;
-      for (std::vector<Op>* stage : {&d1, &d2})
-        for (Op& g : *stage) { g.family = conv_kernel_name(g.cfg); dense_box_ops_.push_back(g); }
-    }
-  }
-  feat_levels_ = FeatLevels{};
-  if (cfg_.obj_feats) {                           // `with_reid: true, model: auto`: the Detect layer's inputs, read after NMS
-    feat_levels_.n_levels = nl;
-    feat_levels_.dim = lvl_in[0].c;
-    for (int l = 1; l < nl; ++l) feat_levels_.dim = std::min(feat_levels_.dim, lvl_in[l].c);
-    for (int l = 0; l < nl; ++l) {
-      feat_levels_.feat[l] = lvl_in[l].ptr; feat_levels_.h[l] = lvl_in[l].h; feat_levels_.w[l] = lvl_in[l].w;
-      feat_levels_.cstride[l] = lvl_in[l].cstride; feat_levels_.coff[l] = lvl_in[l].coff; feat_levels_.c[l] = lvl_in[l].c;
-      feat_levels_.anchor_begin[l] = head_.lv[l].anchor_begin;
-      GTX_CHECK(lvl_in[l].c % feat_levels_.dim == 0, "obj_feats: Detect input %d has %d channels, not a multiple of %d", l, lvl_in[l].c, feat_levels_.dim);
-    }
-  }
-  for (std::vector<Op>* stage : {&st1, &st2}) {
-    for (const Op& d : stage == &st1 ? dw_a : dw_b) ops_.push_back(d);   // the depthwise layers a stage's 1x1 launches read
-    for (Op& g : *stage) {
-      g.family = conv_kernel_name(g.cfg);
-      ops_.push_back(g);
-    }
-  }
 }
 
 void Detector::set_batch(int nb) {
@@ -406,6 +158,15 @@ void Detector::prime_pad_skip() {
   pad_skip_on_ = true;
 }
 
+// The sparse box branch files its candidates by level: the lists in b, `cap` entries per level and image
+void Detector::alloc_level_lists(NmsBuffers& b, int cap) {
+  sparse_.cap = cap;
+  sparse_.sat_flag = sat_dev_;
+  b.lvl_cap = cap;
+  b.lvl_count = (int*)alloc(sizeof(int) * cfg_.max_batch * kMaxLevels);
+  b.lvl_list = (int*)alloc(sizeof(int) * cfg_.max_batch * kMaxLevels * cap);
+}
+
 void Detector::finalize() {
   GTX_CHECK(!finalized_, "finalize called twice");
   GTX_HIP(hipSetDevice(ctx_->device));
@@ -439,13 +200,7 @@ void Detector::finalize() {
     d_feats_ = (float*)alloc(sizeof(float) * N * cfg_.max_det * feat_levels_.dim);
     GTX_HIP(hipHostMalloc((void**)&h_feats_, sizeof(float) * N * cfg_.max_det * feat_levels_.dim));
   }
-  if (sparse_on_ && !end2end_) {
-    sparse_.cap = kSparseCap;
-    sparse_.sat_flag = sat_dev_;
-    nms_.lvl_cap = kSparseCap;
-    nms_.lvl_count = (int*)alloc(sizeof(int) * N * kMaxLevels);
-    nms_.lvl_list = (int*)alloc(sizeof(int) * N * kMaxLevels * kSparseCap);
-  }
+  if (sparse_on_ && !end2end_) alloc_level_lists(nms_, kSparseCap);
   if (end2end_) {
     // the one-to-one head: nms_ holds the gate's candidates (one per anchor at most); sel_ the entries v10_select keeps, with the
     // result buffers; the box branch runs on sel_'s entries only
@@ -456,15 +211,7 @@ void Detector::finalize() {
     sel_.cand_anchor = (int*)alloc(sizeof(int) * N * kSelCap);
     sel_.cand_cls = (int*)alloc(sizeof(int) * N * kSelCap);
     sel_.cand_box = (float*)alloc(sizeof(float) * 4 * N * kSelCap);
-    sel_.lvl_count = sel_.lvl_list = nullptr;
-    sel_.lvl_cap = 0;
-    if (sparse_on_) {
-      sparse_.cap = kSelCap;
-      sparse_.sat_flag = sat_dev_;
-      sel_.lvl_cap = kSelCap;
-      sel_.lvl_count = (int*)alloc(sizeof(int) * N * kMaxLevels);
-      sel_.lvl_list = (int*)alloc(sizeof(int) * N * kMaxLevels * kSelCap);
-    }
+    if (sparse_on_) alloc_level_lists(sel_, kSelCap);   // nms_, the gate's buffer, keeps none
     v10_scores_ = (float*)alloc(sizeof(float) * N * kV10Keep * cfg_.nc);
   }
   GTX_HIP(hipHostMalloc((void**)&h_count_, sizeof(int) * N));
@@ -493,15 +240,9 @@ void Detector::run_post(int nb, hipStream_t s) {
       launch_head_boxes(dtype_, head_, nb, sel_, s);
     }
     launch_v10_rows(sel_, head_.class_mask, nb, lb_, s);
-    GTX_HIP(hipMemcpyAsync(h_count_, nms_.count, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
-    GTX_HIP(hipMemcpyAsync(h_out_n_, sel_.out_n, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
-    GTX_HIP(hipMemcpyAsync(h_out_rows_, sel_.out_rows, sizeof(float) * 6 * nb * cfg_.max_det, hipMemcpyDeviceToHost, s));
-    if (sat_dev_) GTX_HIP(hipMemcpyAsync(h_sat_, sat_dev_, sizeof(int), hipMemcpyDeviceToHost, s));
-    return;
-  }
-  if (sparse_on_) {                                // score gate -> the box branch at the candidates -> their boxes
+  } else if (sparse_on_) {                         // score gate -> the box branch at the candidates -> their boxes
     launch_head_gate(dtype_, head_, nb, nms_, s);
-    launch_head_sparse_box(sparse_, nb, nms_, s);    // the box branch at the candidates and their boxes
+    launch_head_sparse_box(sparse_, nb, nms_, s);
     dense_head_valid_ = false;
   } else {
     launch_head_candidates(dtype_, head_, nb, nms_, s);
@@ -509,14 +250,17 @@ void Detector::run_post(int nb, hipStream_t s) {
   // the candidate counts come back with the results: collect() runs what this pass leaves out for a batch that needs it (the
   // general NMS kernels for > 4096 candidates in an image, the dense box layers for > kSparseCap)
   GTX_HIP(hipMemcpyAsync(h_count_, nms_.count, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
-  launch_nms(nms_, nb, cfg_.iou, cfg_.agnostic_nms != 0, 30000, lb_, s, 1);
-  GTX_HIP(hipMemcpyAsync(h_out_n_, nms_.out_n, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
-  GTX_HIP(hipMemcpyAsync(h_out_rows_, nms_.out_rows, sizeof(float) * 6 * nb * cfg_.max_det, hipMemcpyDeviceToHost, s));
-  if (sat_dev_) GTX_HIP(hipMemcpyAsync(h_sat_, sat_dev_, sizeof(int), hipMemcpyDeviceToHost, s));
-  if (cfg_.obj_feats) {
-    launch_obj_feats(fmt_, feat_levels_, nb, nms_, d_feats_, s);
-    GTX_HIP(hipMemcpyAsync(h_feats_, d_feats_, sizeof(float) * nb * cfg_.max_det * feat_levels_.dim, hipMemcpyDeviceToHost, s));
-  }
+  if (!end2end_) launch_nms(nms_, nb, cfg_.iou, cfg_.agnostic_nms != 0, 30000, lb_, s, 1);
+  read_back(end2end_ ? sel_ : nms_, nb, true, s);
+}
+
+void Detector::read_back(const NmsBuffers& r, int nb, bool sat, hipStream_t s) {
+  GTX_HIP(hipMemcpyAsync(h_out_n_, r.out_n, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
+  GTX_HIP(hipMemcpyAsync(h_out_rows_, r.out_rows, sizeof(float) * 6 * nb * cfg_.max_det, hipMemcpyDeviceToHost, s));
+  if (sat && sat_dev_) GTX_HIP(hipMemcpyAsync(h_sat_, sat_dev_, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (!cfg_.obj_feats) return;                     // never with the one-to-one head (choose_head_pair)
+  launch_obj_feats(fmt_, feat_levels_, nb, r, d_feats_, s);
+  GTX_HIP(hipMemcpyAsync(h_feats_, d_feats_, sizeof(float) * nb * cfg_.max_det * feat_levels_.dim, hipMemcpyDeviceToHost, s));
 }
 
 // The dense box layers of the Detect head on the activations of the pass that ran last (sparse mode leaves them out of the
@@ -547,19 +291,13 @@ void Detector::after_pass(int nb) {
   }
   if (over || big) {
     hipStream_t s = ctx_->stream;
-    NmsBuffers dense = nms_;
     if (over) {                                      // the dense box layers, then every candidate's box again
       run_dense_box(s);
-      launch_head_boxes(dtype_, head_, nb, dense, s);
+      launch_head_boxes(dtype_, head_, nb, nms_, s);
       ++sparse_overflows_;
     }
-    launch_nms(dense, nb, cfg_.iou, cfg_.agnostic_nms != 0, 30000, lb_, s, over ? 0 : 2);
-    GTX_HIP(hipMemcpyAsync(h_out_n_, nms_.out_n, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
-    GTX_HIP(hipMemcpyAsync(h_out_rows_, nms_.out_rows, sizeof(float) * 6 * nb * cfg_.max_det, hipMemcpyDeviceToHost, s));
-    if (cfg_.obj_feats) {
-      launch_obj_feats(fmt_, feat_levels_, nb, nms_, d_feats_, s);
-      GTX_HIP(hipMemcpyAsync(h_feats_, d_feats_, sizeof(float) * nb * cfg_.max_det * feat_levels_.dim, hipMemcpyDeviceToHost, s));
-    }
+    launch_nms(nms_, nb, cfg_.iou, cfg_.agnostic_nms != 0, 30000, lb_, s, over ? 0 : 2);
+    read_back(nms_, nb, false, s);                   // the flag has come back with the pass
     record_post_end(s);                              // the postprocess figure now includes the re-run
     GTX_HIP(hipStreamSynchronize(s));
   }

@@ -158,8 +158,7 @@ int gtx_op_conv2d_group(gtx_ctx* ctx, int n_members, const gtx_conv_desc* descs,
       need(xs[i], "x"); need(ws[i], "w"); need(ys[i], "y");
       if (descs[i].has_residual) gtx::fail(GTX_ERR_INVALID, "grouped op: no residual");
       conv_setup(ctx, &descs[i], xs[i], ws[i], biases ? biases[i] : nullptr, nullptr, ys[i], st[i]);
-      const gtx::ConvConfig &a = st[0].cfg, &b = st[i].cfg;
-      if (a.dtype != b.dtype || a.ks != b.ks || a.stride != b.stride || a.bn != b.bn || a.kc != b.kc || a.variant != b.variant || a.th != b.th)
+      if (!gtx::same_kernel(st[0].cfg, st[i].cfg))
         gtx::fail(GTX_ERR_INVALID, "grouped op: member %d picks another kernel than member 0", i);
       g.p[i] = st[i].g.p[0];
       g.p[i].ty_first = ty_first ? ty_first[i] : 0;

@@ -1,7 +1,7 @@
 // The YOLO trunk: everything in front of the Detect layer of ultralytics' yolov8.yaml (model.0-21), yolov8-p2.yaml (model.0-27) and
 // yolo11.yaml / yolov10.yaml / yolo26.yaml (model.0-22), and the YOLOv8-cls (model.0-8) and YOLO11-cls (model.0-9) backbones. Each graph is a constant table with one row per yaml layer
 // (yolo_trunk.cpp); one walk over a table emits its launches into the caller's op list. Every family that runs a trunk builds
-// through it: the YOLOv8 / P2 / YOLO11 detector (Detect on its outputs, detector.cpp), YOLOv8-RTDETR (an RTDETRDecoder on model.15 /
+// through it: the YOLOv8 / P2 / YOLO11 detector (Detect on its outputs, detect_head.cpp), YOLOv8-RTDETR (an RTDETRDecoder on model.15 /
 // 18 / 21, rtdetr.cpp) and the ReID embedder (reid.cpp). It also owns the fused front (stem + model.1 + model.2.cv1 in one launch on
 // the split-f16x3 path) with the stand-alone forms it hides, and launches its op kinds.
 #pragma once
