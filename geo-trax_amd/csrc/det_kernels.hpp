@@ -115,6 +115,9 @@ void launch_head_boxes(int dtype, const HeadParams& hp, int n, const NmsBuffers&
 // The Detect box branch (cv2[l][0]: Cin -> 64 and cv2[l][1]: 64 -> 64, both 3x3 + SiLU) evaluated at the candidate anchors only
 // (head_sparse.hip; split-f16x3 path). Per level: the Detect input (pair format), the packed weight image of the first layer's
 // 64-cout tile and of the second layer (pack_conv_weights_split with 32-channel chunks), their biases and power-of-two scales.
+// w1 may be tile 0 of a stacked image (the plain head packs cv2[l][0] and cv3[l][0] as one layer: box tile first, class tiles
+// behind it); b1 is then the stack's bias, of which the first 64 are read, and sc1 the STACK's acc_scale -- the power of two is
+// set by the largest weight of the whole stack, the class tiles' included, not by the box tile's own.
 struct SparseBoxLevel {
   const void* in;
   int H, W, cstride, coff, cin;

@@ -964,6 +964,86 @@ int gtx_op_head_boxes_r1(gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx
   return guarded([&] { head_boxes_op("head_boxes_r1", 4, ctx, dtype, n, n_levels, lv, cap, count, cand_anchor, cand_box); });
 }
 
+// The sparse box launch (head_sparse.hip; tests/test_head_sparse_ops_gpu.py): the levels' maps go up in the pair format, the first
+// layer's whole stack is packed as the detector packs it and the kernel gets its tile 0 with the stack's scale (Detector::plan_sparse_box).
+int gtx_op_head_sparse_box(gtx_ctx* ctx, int n, int n_levels, const gtx_sparse_level* lv, int reg_max, int cap, int lvl_cap, const int* count,
+                           const int* cand_anchor, const int* lvl_count, const int* lvl_list, float* cand_box, int* sat) {
+  return guarded([&] {
+    const char* op = "head_sparse_box";
+    if (n_levels > gtx::kMaxLevels) op_bad(op, "at most 4 levels");
+    if (n < 1 || n > 64 || n_levels < 1) op_bad(op, "bad sizes");
+    if (reg_max != 16 && reg_max != 1) op_bad(op, "reg_max is 16 or 1");
+    if (cap < 1 || cap > (1 << 22)) op_bad(op, "cap >= 1");
+    if (lvl_cap < 1 || lvl_cap > (1 << 22)) op_bad(op, "lvl_cap >= 1");
+    need(lv, "lv");
+    long begin[gtx::kMaxLevels + 1] = {0};
+    for (int l = 0; l < n_levels; ++l) {
+      const gtx_sparse_level& L = lv[l];
+      need(L.feat, "lv[l].feat"); need(L.w1, "lv[l].w1"); need(L.b1, "lv[l].b1"); need(L.w2, "lv[l].w2"); need(L.b2, "lv[l].b2");
+      need(L.wb, "lv[l].wb"); need(L.bb, "lv[l].bb");
+      if (L.h < 1 || L.w < 1 || L.cstride < 1 || L.cstride > (1 << 16) || L.cstride % 8) op_bad(op, "a level's map: h, w >= 1, cstride a multiple of 8");
+      if (L.cin < 32 || L.cin % 32) op_bad(op, "cin must be a positive multiple of 32 (the kernel's K chunk)");
+      if (L.coff < 0 || L.coff % 8) op_bad(op, "coff must be a multiple of 8 (whole pair-format groups)");
+      if ((long)L.coff + L.cin > L.cstride) op_bad(op, "a level's channels do not fit its stride");
+      if (L.c1out < 64 || L.c1out % 64 || L.c1out > 1024) op_bad(op, "c1out must be a multiple of 64 in [64, 1024]");
+      if ((double)n * L.h * L.w * L.cstride > 2.5e8) op_bad(op, "maps too large");
+      begin[l + 1] = begin[l] + (long)L.h * L.w;
+    }
+    if (begin[n_levels] > (1l << 22)) op_bad(op, "too many anchors");
+    need(count, "count"); need(cand_anchor, "cand_anchor"); need(lvl_count, "lvl_count"); need(lvl_list, "lvl_list");
+    // every entry the kernel follows: lvl_list -> cand_anchor -> a cell of the level it is filed under
+    for (int b = 0; b < n; ++b)
+      for (int l = 0; l < n_levels; ++l) {
+        const int c = lvl_count[b * gtx::kMaxLevels + l];
+        if (c < 0) op_bad(op, "a negative lvl_count");
+        const int* list = lvl_list + ((size_t)b * gtx::kMaxLevels + l) * lvl_cap;
+        for (int k = 0; k < std::min(c, lvl_cap); ++k) {
+          if (list[k] < 0 || list[k] >= cap) op_bad(op, "a lvl_list entry is outside [0, cap)");
+          const int a = cand_anchor[(size_t)b * cap + list[k]];
+          if (a < begin[l] || a >= begin[l + 1]) op_bad(op, "an entry's anchor is not inside the level it is filed under");
+        }
+      }
+    need(cand_box, "cand_box"); need(sat, "sat"); need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    // What conv_pick_config gives the K32 form (32-channel chunks, 64-cout tiles), written out: the pick follows GTX_K32, and
+    // pack_conv_weights_split reads kc, ks and bn only. A copy: if the K32 form's packing parameters change, change them here too --
+    // the detector feeds the kernel the pick's image (Detector::plan_sparse_box), and only the dense-route case of
+    // tests/test_head_sparse_ops_gpu.py would notice a difference.
+    gtx::ConvConfig k32{};
+    k32.variant = gtx::ConvForm::K32; k32.dtype = GTX_F32S; k32.ks = 3; k32.stride = 1; k32.kc = 32; k32.bn = 64; k32.th = 8; k32.tw = 16;
+    const int box_out = 4 * reg_max;
+    gtx::DevBuf feat[gtx::kMaxLevels], w1[gtx::kMaxLevels], b1[gtx::kMaxLevels], w2[gtx::kMaxLevels], b2[gtx::kMaxLevels], wb[gtx::kMaxLevels],
+        bb[gtx::kMaxLevels], dc, da, dlc, dll, db, dsat;
+    gtx::SparseBox sb{};
+    for (int l = 0; l < n_levels; ++l) {
+      const gtx_sparse_level& L = lv[l];
+      gtx::SparseBoxLevel& S = sb.lv[l];
+      upload_fmt(feat[l], GTX_F32S, L.feat, (size_t)n * L.h * L.w * L.cstride * 4);
+      const std::vector<uint8_t> i1 = gtx::pack_conv_weights_split(L.w1, L.c1out, L.cin, k32, &S.sc1);
+      const std::vector<uint8_t> i2 = gtx::pack_conv_weights_split(L.w2, 64, 64, k32, &S.sc2);
+      upload(w1[l], i1.data(), i1.size()); upload(b1[l], L.b1, (size_t)L.c1out * 4);
+      upload(w2[l], i2.data(), i2.size()); upload(b2[l], L.b2, 64 * 4);
+      upload(wb[l], L.wb, (size_t)64 * box_out * 4); upload(bb[l], L.bb, (size_t)box_out * 4);
+      S.in = feat[l].p; S.H = L.h; S.W = L.w; S.cstride = L.cstride; S.coff = L.coff; S.cin = L.cin;
+      S.w1 = w1[l].p; S.b1 = b1[l].as<float>();          // tile 0 of the stack is the image's first 64-cout tile
+      S.w2 = w2[l].p; S.b2 = b2[l].as<float>();
+      S.wb = wb[l].as<float>(); S.bb = bb[l].as<float>(); S.stride = L.stride; S.anchor_begin = (int)begin[l];
+    }
+    const size_t m = (size_t)n * cap, lb = (size_t)n * gtx::kMaxLevels * lvl_cap * 4;
+    upload(dc, count, (size_t)n * 4); upload(da, cand_anchor, m * 4);
+    upload(dlc, lvl_count, (size_t)n * gtx::kMaxLevels * 4); upload(dll, lvl_list, lb);
+    fill_ff(db, m * 16); zeros(dsat, 4);
+    sb.n_levels = n_levels; sb.cap = lvl_cap; sb.sat_flag = dsat.as<int>(); sb.reg_max = reg_max;
+    gtx::NmsBuffers nb{};
+    nb.cap = cap;
+    nb.count = dc.as<int>(); nb.cand_anchor = da.as<int>(); nb.cand_box = db.as<float>();
+    nb.lvl_count = dlc.as<int>(); nb.lvl_list = dll.as<int>(); nb.lvl_cap = lvl_cap;
+    gtx::launch_head_sparse_box(sb, n, nb, ctx->stream);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download(cand_box, db, m * 16); download(sat, dsat, 4);
+  });
+}
+
 int gtx_op_nms(gtx_ctx* ctx, int n, int cap, const int* count, const float* cand_score, const int* cand_anchor, const int* cand_cls,
                const float* cand_box, float iou_thr, int agnostic, int max_nms, int nms_cap, int max_det, int src_h, int src_w, int net_h, int net_w,
                double gain, int which, float* out_rows, int* out_n, int* out_anchor) {

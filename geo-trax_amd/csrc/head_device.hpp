@@ -7,9 +7,11 @@
 //   16-bin box     head_boxes_kernel == head_sparse_box_kernel<false> == head_raw_kernel<T, false>: box_chain from the bias in feature
 //                  order (head_boxes_kernel writes that chain out itself: through the accessors its code came out 2 % slower),
 //                  dfl_xywh, xywh_to_xyxy -- tests/test_detector_gpu.py (test_sparse_box_branch_is_the_dense_one_bit_for_bit),
-//                  tests/test_head_ops_gpu.py (boxes), raw_output == the rows
+//                  tests/test_head_ops_gpu.py (boxes), tests/test_head_sparse_ops_gpu.py (the sparse launch on its own: float64,
+//                  and the dense route's hooks bit for bit), raw_output == the rows
 //   reg_max = 1    head_boxes_r1_kernel == head_sparse_box_kernel<true> == head_raw_kernel<T, true>: reg1_side, reg1_xyxy
-//                  -- tests/test_yolo26_gpu.py (test_sparse_box_form_equals_the_dense_one, ..._on_every_map_corner)
+//                  -- tests/test_yolo26_gpu.py (test_sparse_box_form_equals_the_dense_one, ..._on_every_map_corner),
+//                  tests/test_head_sparse_ops_gpu.py (the same two checks for the sparse launch on its own)
 //   class logits   head_raw_kernel, both forms: raw_class_row (a serial chain: the scores of raw_output are not the gate's bits)
 //   frame boxes    nms_resolve_kernel == nms_small_kernel == v10_rows_kernel: undo_letterbox with letterbox_undo()'s figures
 //                  -- tests/test_head_ops_gpu.py (NMS, v10_rows)

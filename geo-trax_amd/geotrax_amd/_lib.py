@@ -107,6 +107,13 @@ class HeadLevel(C.Structure):
                 ("wb", C.c_void_p), ("bb", C.c_void_p), ("wc", C.c_void_p), ("bc", C.c_void_p), ("stride", C.c_float)]
 
 
+class SparseLevel(C.Structure):
+    """gtx_sparse_level: one Detect level of the sparse box launch's operator hook."""
+    _fields_ = [("feat", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("cstride", C.c_int), ("coff", C.c_int), ("cin", C.c_int), ("c1out", C.c_int),
+                ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("wb", C.c_void_p), ("bb", C.c_void_p),
+                ("stride", C.c_float)]
+
+
 # name -> (restype, argtypes); kept in one table so tests can check the export list against
 # include/gtx.h.
 ABI_VERSION = 14       # GTX_ABI_VERSION of include/gtx.h
@@ -159,6 +166,7 @@ _SIGNATURES = {
     "gtx_op_head_gate": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gtx_op_head_boxes": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
     "gtx_op_head_boxes_r1": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "gtx_op_head_sparse_box": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.POINTER(C.c_int)]),
     "gtx_op_nms": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                              C.c_double, C.c_int, _P, _P, _P]),
     "gtx_op_v10_select": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -638,6 +638,43 @@ def head_boxes_r1(levels, count, cand_anchor, ctx=None) -> np.ndarray:
     return box
 
 
+def sparse_levels(levels):
+    """Detect levels for the sparse box hook. levels: dicts with feat [n, h, w, cstride] float32, coff, cin, w1 [c1out, 3, 3, cin], b1
+    [c1out], w2 [64, 3, 3, 64], b2 [64], wb [64, 4 * reg_max], bb [4 * reg_max], stride. -> (kept arrays, n, L, gtx_sparse_level array)."""
+    L = len(levels)
+    arr = (_lib.SparseLevel * max(L, 1))()
+    keep = []
+    n = np.shape(levels[0]["feat"])[0]
+    for i, lv in enumerate(levels):
+        f = _f32(lv["feat"])
+        w = {k: _f32(lv[k]) for k in ("w1", "b1", "w2", "b2", "wb", "bb")}
+        cin = int(lv.get("cin", w["w1"].shape[3]))
+        assert f.ndim == 4 and f.shape[0] == n and w["w1"].shape[1:] == (3, 3, cin) and w["b1"].shape == (w["w1"].shape[0],)
+        assert w["w2"].shape == (64, 3, 3, 64) and w["b2"].shape == (64,) and w["wb"].shape[0] == 64 and w["bb"].shape == (w["wb"].shape[1],)
+        keep += [f, w]
+        arr[i] = _lib.SparseLevel(f.ctypes.data, f.shape[1], f.shape[2], f.shape[3], int(lv.get("coff", 0)), cin, w["w1"].shape[0], w["w1"].ctypes.data,
+                                  w["b1"].ctypes.data, w["w2"].ctypes.data, w["b2"].ctypes.data, w["wb"].ctypes.data, w["bb"].ctypes.data,
+                                  float(lv.get("stride", 8.0)))
+    return keep, n, L, arr
+
+
+def head_sparse_box(levels, count, cand_anchor, lvl_count, lvl_list, *, reg_max: int = 16, ctx=None):
+    """The sparse Detect box launch (head_sparse.hip) on given candidates: cand_anchor [n, cap], lvl_count [n, 4], lvl_list
+    [n, 4, lvl_cap] (entry indices filed by level). -> (boxes [n, cap, 4] xyxy in network pixels, NaN where no list names the entry;
+    sat: 1 when a first-layer value a candidate reads left the fp16 range)."""
+    ctx = ctx or _lib.default_context()
+    keep, n, L, arr = sparse_levels(levels)
+    count, cand_anchor, lvl_count, lvl_list = _i32(count), _i32(cand_anchor), _i32(lvl_count), _i32(lvl_list)
+    cap, lvl_cap = cand_anchor.shape[1], lvl_list.shape[2]
+    assert count.shape == (n,) and cand_anchor.shape == (n, cap) and lvl_count.shape == (n, 4) and lvl_list.shape == (n, 4, lvl_cap)
+    assert all(np.shape(lv["wb"]) == (64, 4 * reg_max) for lv in levels)
+    box = np.zeros((n, cap, 4), np.float32)
+    sat = C.c_int(-1)
+    check(ctx.lib.gtx_op_head_sparse_box(ctx.handle, n, L, arr, int(reg_max), cap, lvl_cap, ptr(count), ptr(cand_anchor), ptr(lvl_count), ptr(lvl_list),
+                                         ptr(box), C.byref(sat)))
+    return box, sat.value
+
+
 def _rows_io(n, max_det, out_rows, out_n, out_anchor):
     rows = np.zeros((n, max_det, 6), np.float32) if out_rows is None else np.array(out_rows, dtype=np.float32, order="C")
     on = np.full(n, -1, np.int32) if out_n is None else np.array(out_n, dtype=np.int32, order="C")

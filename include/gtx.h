@@ -88,7 +88,9 @@ extern "C" {
  *     opaque handle only, so the number stays.
  *     gtx_op_head_boxes_r1 added and arch 0 also takes YOLO26 tensors (yolo26.yaml: SPPF with a residual, attention inside model.22, a
  *     Detect of reg_max = 1 read off its last box convolution's four rows, the one-to-one head under gtx_det_config.end2end): a new
- *     entry point only, so the number stays. */
+ *     entry point only, so the number stays.
+ *     gtx_op_head_sparse_box and gtx_sparse_level (the sparse Detect box launch on host arrays) added: a new entry point and a
+ *     struct of its own only, so the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -554,6 +556,31 @@ int gtx_op_head_boxes(gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx_he
  * r, b from the cell centre in strides; cand_box = ((x + 0.5 - l), (y + 0.5 - t), (x + 0.5 + r), (y + 0.5 + b)) * stride, no clamp. */
 int gtx_op_head_boxes_r1(gtx_ctx* ctx, int dtype, int n, int n_levels, const gtx_head_level* lv, int cap, const int* count, const int* cand_anchor,
                          float* cand_box);
+/* One Detect level of the sparse box launch (csrc/head_sparse.hip; tests/test_head_sparse_ops_gpu.py): the Detect input map feat
+ * [n][h][w][cstride] plain fp32 (converted to the pair format on the way) with the layer's cin channels at coff; w1 [c1out][3][3][cin]
+ * OHWI and b1 [c1out]: cv2[l][0], alone (c1out = 64) or as the first 64 outputs of a stacked box + class layer (c1out a multiple of
+ * 64: the whole stack is packed, the kernel reads its first 64-cout tile under the stack's power-of-two scale); w2 [64][3][3][64]
+ * and b2 [64]: cv2[l][1]; wb [64][4 * reg_max] (the final box 1x1 convolution, transposed) and bb [4 * reg_max]. cin a multiple of
+ * 32; coff and cstride multiples of 8. */
+typedef struct gtx_sparse_level {
+  const float* feat;
+  int h, w, cstride, coff, cin, c1out;
+  const float* w1;
+  const float* b1;
+  const float* w2;
+  const float* b2;
+  const float* wb;
+  const float* bb;
+  float stride;
+} gtx_sparse_level;
+/* The Detect box branch at given candidates, one launch: the two 3x3 layers + SiLU at the candidates' anchors and the box decode
+ * (reg_max 16: DFL; 1: the four signed distances of gtx_op_head_boxes_r1). cand_anchor [n][cap]; lvl_count [n][4] and lvl_list
+ * [n][4][lvl_cap] file entry indices under their level, as the gate does; the first min(lvl_count, lvl_cap) entries of a list are
+ * computed, each must lie in [0, cap) and its anchor inside the level it is filed under. count [n] is uploaded as the launch's
+ * candidate count (the kernel does not read it). cand_box [n][cap][4] xyxy in network pixels (entries no list names: all bits set);
+ * *sat: 1 when a first-layer value that a candidate reads left the fp16 range. At most 4 levels. */
+int gtx_op_head_sparse_box(gtx_ctx* ctx, int n, int n_levels, const gtx_sparse_level* lv, int reg_max, int cap, int lvl_cap, const int* count,
+                           const int* cand_anchor, const int* lvl_count, const int* lvl_list, float* cand_box, int* sat);
 /* NMS of given candidates (count [n], cand_* [n][cap]; anchors in [0, 2^20)): order score descending then anchor ascending, greedy
  * suppression at IoU > iou_thr (boxes offset by 7680 * class unless agnostic), the max_nms best only, max_det rows, scale_boxes +
  * clip to the frame. which: 0 both paths, 1 the single-workgroup kernel only (an image beyond 4096 candidates or max_det beyond 2048

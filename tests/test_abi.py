@@ -293,6 +293,47 @@ def test_head_hooks_refuse_bad_sizes_before_any_launch():
     assert boxes(levels(cb=136, cstride=160)) == -1 and b"128 box channels" in lib.gtx_last_error()
     assert boxes(levels(), anchor=4) == -1 and b"outside the level set" in lib.gtx_last_error()           # 2 x 2 anchors
 
+    def sparse(n_levels=1, h=2, w=2, cstride=40, coff=8, cin=32, c1out=64, reg_max=16, cap=16, lvl_cap=4, lvl_count=1, entry=0, anchor=0):
+        arr = (_lib.SparseLevel * n_levels)()
+        for l in range(n_levels):
+            arr[l] = _lib.SparseLevel(f.ctypes.data, h, w, cstride, coff, cin, c1out, *([f.ctypes.data] * 6), 8.0)
+        c = np.array([1], np.int32)
+        a = np.full(cap if cap > 0 else 1, anchor, np.int32)
+        lc = np.zeros((1, 4), np.int32)
+        lc[0, :min(n_levels, 4)] = lvl_count
+        ll = np.full((1, 4, max(lvl_cap, 1)), entry, np.int32)
+        sat = C.c_int(0)
+        return lib.gtx_op_head_sparse_box(None, 1, n_levels, arr, reg_max, cap, lvl_cap, p(c), p(a), p(lc), p(ll), p(f), C.byref(sat))
+
+    assert sparse() == -1 and b"ctx is NULL" in lib.gtx_last_error()                                      # the sizes were fine
+    assert sparse(cin=96, cstride=104) == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert sparse(lvl_count=9) == -1 and b"ctx is NULL" in lib.gtx_last_error()                           # lvl_count > lvl_cap: the kernel clamps
+    assert sparse(cin=48, cstride=56) == -1 and b"multiple of 32" in lib.gtx_last_error()                 # the K chunk would run past the slice
+    assert sparse(cin=16) == -1 and b"multiple of 32" in lib.gtx_last_error()
+    assert sparse(cin=0) == -1 and b"multiple of 32" in lib.gtx_last_error()
+    assert sparse(coff=4) == -1 and b"coff" in lib.gtx_last_error()                                       # half a pair-format group
+    assert sparse(coff=-8) == -1 and b"coff" in lib.gtx_last_error()
+    assert sparse(coff=16) == -1 and b"do not fit" in lib.gtx_last_error()                                # coff + cin > cstride
+    assert sparse(cstride=44) == -1 and b"cstride" in lib.gtx_last_error()
+    assert sparse(5) == -1 and b"4 levels" in lib.gtx_last_error()
+    assert sparse(lvl_cap=0) == -1 and b"lvl_cap" in lib.gtx_last_error()
+    assert sparse(lvl_count=-1) == -1 and b"negative lvl_count" in lib.gtx_last_error()
+    assert sparse(entry=16) == -1 and b"outside [0, cap)" in lib.gtx_last_error()
+    assert sparse(entry=-1) == -1 and b"outside [0, cap)" in lib.gtx_last_error()
+    assert sparse(lvl_count=2, entry=16) == -1 and b"outside [0, cap)" in lib.gtx_last_error()
+    assert sparse(lvl_count=0, entry=16) == -1 and b"ctx is NULL" in lib.gtx_last_error()                 # past the count: never followed
+    assert sparse(anchor=4) == -1 and b"not inside the level" in lib.gtx_last_error()                     # 2 x 2 anchors
+    assert sparse(anchor=-1) == -1 and b"not inside the level" in lib.gtx_last_error()
+    assert sparse(2, anchor=0) == -1 and b"not inside the level" in lib.gtx_last_error()                  # level 1's list names an anchor of level 0
+    assert sparse(c1out=96) == -1 and b"c1out" in lib.gtx_last_error()
+    assert sparse(c1out=0) == -1 and b"c1out" in lib.gtx_last_error()
+    assert sparse(reg_max=8) == -1 and b"reg_max" in lib.gtx_last_error()
+    assert sparse(cap=0) == -1 and b"cap >= 1" in lib.gtx_last_error()
+    assert sparse(cap=2**22 + 1) == -1 and b"cap >= 1" in lib.gtx_last_error()
+    assert sparse(h=0) == -1 and b"a level's map" in lib.gtx_last_error()
+    assert sparse(cstride=2**16 + 8, cin=32) == -1 and b"a level's map" in lib.gtx_last_error()
+    assert sparse(h=2100, w=2100) == -1 and b"too many anchors" in lib.gtx_last_error()                   # > 2^22 (the check reads no array)
+
     def nms(anchor=0, nms_cap=64, which=0, score=0.5, count=1, max_det=4):
         c = np.array([count], np.int32)
         s = np.full(16, score, np.float32)
