@@ -6,7 +6,8 @@
 
 #include <algorithm>
 
-#include "stabilizer.hpp"
+#include "clahe.hpp"
+#include "net_runtime.hpp"   // gtx_ctx
 
 namespace gtx {
 
@@ -84,6 +85,20 @@ void clahe_dev(const uint8_t* src, int h, int w, uint8_t* luts, uint8_t* dst, hi
                      255.0f / (float)area, luts);
   hipLaunchKernelGGL(clahe_apply_kernel, dim3((w + 255) / 256, h), dim3(256), 0, s, src, w, h, 1.0f / (float)tw, 1.0f / (float)th, luts, dst);
   GTX_HIP(hipGetLastError());
+}
+
+// The same for a host image (a host copy around clahe_dev: no float arithmetic of its own).
+void clahe_image(gtx_ctx* ctx, const uint8_t* gray, int h, int w, uint8_t* out) {
+  GTX_HIP(hipSetDevice(ctx->device));
+  GTX_CHECK(h >= 8 && w >= 8, "clahe: image %dx%d is smaller than the tile grid", w, h);
+  const size_t bytes = (size_t)h * w;
+  DevBuf d_src(bytes), d_dst(bytes), d_lut(kClaheLutBytes);
+  hipStream_t s = ctx->stream;
+  GTX_HIP(hipMemcpyAsync(d_src.p, gray, bytes, hipMemcpyHostToDevice, s));
+  clahe_dev(d_src.as<uint8_t>(), h, w, d_lut.as<uint8_t>(), d_dst.as<uint8_t>(), s);
+  GTX_HIP(hipGetLastError());
+  GTX_HIP(hipMemcpyAsync(out, d_dst.p, bytes, hipMemcpyDeviceToHost, s));
+  GTX_HIP(hipStreamSynchronize(s));
 }
 
 }  // namespace gtx

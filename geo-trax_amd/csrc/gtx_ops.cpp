@@ -2,7 +2,7 @@
 // The float64 tests drive them, and the package calls a few itself (the registration matcher, the georeference chain, CLAHE).
 // A hook checks every size, and every index a kernel would turn into an address, before it touches the GPU; then it stages its
 // arrays with op_staging.hpp, launches as the product launches, and copies the results back. The hooks of file-local kernels
-// (op_gmc_* in gmc.hip, op_ecc_* in ecc.hip, op_orb_* in stabilizer.hip, op_sift_* in sift.hip) keep their staging beside the kernels and have only their checks here.
+// (op_gmc_* in gmc.hip, op_ecc_* in ecc.hip, op_orb_match in stabilizer.hip, op_orb_ransac in homography.hip, op_sift_* in sift.hip) keep their staging beside the kernels and have only their checks here.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -11,6 +11,7 @@
 
 #include "../../include/gtx.h"
 #include "api_guard.hpp"
+#include "clahe.hpp"
 #include "common.hpp"
 #include "conv_igemm.hpp"
 #include "det_kernels.hpp"
@@ -19,6 +20,7 @@
 #include "ecc.hpp"
 #include "geometry.hpp"
 #include "gmc.hpp"
+#include "homography.hpp"
 #include "jpeg_enc.hpp"
 #include "jpeg_entropy.hpp"
 #include "match_l2.hpp"
@@ -1533,6 +1535,18 @@ int gtx_op_estimate_affine_partial(const float* p_xy, const float* q_xy, int n, 
     if (n > 0) { need(p_xy, "p_xy"); need(q_xy, "q_xy"); }
     if (n < 0) gtx::fail(GTX_ERR_INVALID, "estimate_affine_partial: n = %d", n);
     *valid = gtx::estimate_affine_partial(p_xy, q_xy, n, seed, A, n_inliers) ? 1 : 0;
+  });
+}
+
+int gtx_op_homography_refit(const float* pairs, int n, int frame_w, int frame_h, double thr, int affine, const double H0[9], double H[9],
+                            int* valid, int* n_inliers) {
+  return guarded([&] {
+    need(H0, "H0"); need(H, "H"); need(valid, "valid"); need(n_inliers, "n_inliers");
+    if (n > 0) need(pairs, "pairs");
+    if (n < 0) gtx::fail(GTX_ERR_INVALID, "homography_refit: n = %d", n);
+    if (frame_w < 1 || frame_h < 1) gtx::fail(GTX_ERR_INVALID, "homography_refit: frame %d x %d", frame_w, frame_h);
+    *n_inliers = 0;
+    *valid = gtx::refine_homography(pairs, n, frame_w, frame_h, thr, affine != 0, H0, H, n_inliers) ? 1 : 0;
   });
 }
 

@@ -18,6 +18,7 @@
 
 #include "../../../include/gtx.h"
 #include "../geometry.hpp"
+#include "../homography.hpp"
 #include "../tracker.hpp"
 #include "../vec_acos.hpp"
 #include "../yolo_tables.hpp"
@@ -138,6 +139,55 @@ bool run_affine_fit(unsigned seed) {
   }
   return true;
 }
+
+// The robust homography's host refit (homography_refit.cpp) on seeded pairs of a 1920x1080 frame: every size around the minimal
+// sets, projective and affine, about 30 % gross outliers, a winner nowhere near the pairs (no support: false) and n identical
+// pairs (a singular normal matrix: the Cholesky step must bail out). Only what must hold is asserted: false leaves H alone, true
+// gives finite entries with h33 = 1. (h33 leaves the refit as x * (1 / x): exactly 1 for every case of the seed main() passes, one
+// ulp below 1 for some cases of other seeds -- 1, 2, 4, 5, 6, 8, 11 of the first twelve. Change the seed and that comparison with it.)
+bool run_homography_refit(unsigned seed) {
+  std::mt19937 rng(seed);
+  std::uniform_real_distribution<float> U(0.f, 1.f);
+  std::normal_distribution<float> N(0.f, 0.3f);
+  const int w = 1920, h = 1080;
+  auto check = [&](const std::vector<float>& pairs, int n, bool affine, const double* H0, int want) {   // want: 1 true, 0 false, -1 either
+    double H[9];
+    for (double& v : H) v = 7.0;
+    int inl = -1;
+    const bool ok = gtx::refine_homography(pairs.data(), n, w, h, 2.0, affine, H0, H, &inl);
+    if (want >= 0 && ok != (want == 1)) return false;
+    for (double v : H)
+      if (ok ? !std::isfinite(v) : v != 7.0) return false;
+    return !ok || (H[8] == 1.0 && inl >= (affine ? 3 : 4) && inl <= n);
+  };
+  for (int affine = 0; affine < 2; ++affine) {
+    const double p6 = affine ? 0.0 : 2e-6, p7 = affine ? 0.0 : -1e-6;
+    const double Ht[9] = {1.002, -0.01, 12.5, 0.01, 1.002, -7.25, p6, p7, 1.0};
+    double H0[9], Hfar[9];                              // the winner as a kernel leaves it: close to the truth, any scale
+    for (int k = 0; k < 9; ++k) { H0[k] = 2.0 * Ht[k]; Hfar[k] = Ht[k]; }
+    H0[2] += 1.0; Hfar[2] += 500.0;
+    for (int n : {0, 3, 4, 5, 60, 800}) {
+      std::vector<float> pairs((size_t)4 * n);
+      for (int i = 0; i < n; ++i) {
+        const double x = U(rng) * w, y = U(rng) * h, d = Ht[6] * x + Ht[7] * y + 1.0;
+        pairs[4 * i] = (float)x; pairs[4 * i + 1] = (float)y;
+        pairs[4 * i + 2] = (float)((Ht[0] * x + Ht[1] * y + Ht[2]) / d) + N(rng);
+        pairs[4 * i + 3] = (float)((Ht[3] * x + Ht[4] * y + Ht[5]) / d) + N(rng);
+        if (n >= 60 && U(rng) < 0.3f) { pairs[4 * i + 2] += (U(rng) - 0.5f) * 400.f; pairs[4 * i + 3] += (U(rng) - 0.5f) * 400.f; }
+      }
+      if (!check(pairs, n, affine != 0, H0, n < (affine ? 3 : 4) ? 0 : (n >= 60 ? 1 : -1))) return false;
+      if (n == 60 && !check(pairs, n, affine != 0, Hfar, 0)) return false;                    // under-supported
+      if (n == 60) {                                                                           // n identical pairs, on the model
+        const double x = 700.0, y = 400.0, d = Ht[6] * x + Ht[7] * y + 1.0;
+        const float one[4] = {(float)x, (float)y, (float)((Ht[0] * x + Ht[1] * y + Ht[2]) / d), (float)((Ht[3] * x + Ht[4] * y + Ht[5]) / d)};
+        for (int i = 0; i < n; ++i)
+          for (int k = 0; k < 4; ++k) pairs[4 * i + k] = one[k];
+        if (!check(pairs, n, affine != 0, H0, 1)) return false;                               // the winner comes back, normalised
+      }
+    }
+  }
+  return true;
+}
 }  // namespace
 
 // The result-file writers (table_writer.cpp): several chunks per call so that their own threads hand the file to each other in
@@ -235,12 +285,16 @@ int main(int argc, char** argv) {
       th.emplace_back([&r, i] {
         r[i] = i < 4 ? run_tracker(i & 1, 100 + i) : (i == 4 ? run_reid_tracker<gtx::OcSortTracker>(3, 104) : run_reid_tracker<gtx::TrackTrackTracker>(5, 105));
       });
+    bool refit[2] = {false, false};                    // the refit shares nothing between calls: two at once
+    for (int i = 0; i < 2; ++i) th.emplace_back([&refit, i] { refit[i] = run_homography_refit(7); });
     for (auto& t : th) t.join();
     for (long v : r) rows += v;
+    if (!refit[0] || !refit[1]) { std::fprintf(stderr, "homography refit wrong\n"); return 7; }
   } else {
     rows = run_tracker(0, 1) + run_tracker(1, 2);
     rows += run_reid_tracker<gtx::OcSortTracker>(3, 3) + run_reid_tracker<gtx::TrackTrackTracker>(5, 4);
     if (!run_affine_fit(5)) { std::fprintf(stderr, "partial-affine fit wrong\n"); return 4; }
+    if (!run_homography_refit(7)) { std::fprintf(stderr, "homography refit wrong\n"); return 7; }
     if (!run_acos_check(6)) { std::fprintf(stderr, "vector acos differs from libm\n"); return 5; }
     // geometry helpers on edge inputs: zero boxes, a point on the line at infinity, a degenerate matrix
     const double H[9] = {1.01, 0.002, 3.0, -0.001, 0.99, -6.0, 1e-7, -1e-7, 1.0};

@@ -18,9 +18,12 @@ struct gtx_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   hipDeviceProp_t prop{};
-  void* orb_op_state = nullptr;      // device words of gtx_op_orb_match / gtx_op_orb_ransac (stabilizer.hip), allocated by their first call
+  // device words of the two operator hooks, each allocated and initialised by its hook's first call and never written by the host again
+  void* orb_match_ticket = nullptr;  // gtx_op_orb_match (stabilizer.hip): match_kernel's ticket
+  void* orb_ransac_state = nullptr;  // gtx_op_orb_ransac (homography.hip): ransac_kernel's two state words
   ~gtx_ctx() {
-    if (orb_op_state) (void)hipFree(orb_op_state);
+    if (orb_match_ticket) (void)hipFree(orb_match_ticket);
+    if (orb_ransac_state) (void)hipFree(orb_ransac_state);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };

@@ -1,5 +1,5 @@
-// What the operator hooks (gtx_op_*: gtx_ops.cpp, and the hooks that sit beside their file-local kernels in gmc.hip and
-// stabilizer.hip) share: refusing an argument, staging host arrays into fresh device buffers and back, the step between plain fp32
+// What the operator hooks (gtx_op_*: gtx_ops.cpp, and the hooks that sit beside their file-local kernels in gmc.hip,
+// stabilizer.hip and homography.hip) share: refusing an argument, staging host arrays into fresh device buffers and back, the step between plain fp32
 // host arrays and the pair format (split_format.hpp), and the event-timed launch loop. Host only, synchronous copies: none of
 // this is on the product's path.
 #pragma once

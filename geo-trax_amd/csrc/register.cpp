@@ -7,9 +7,9 @@
 #include <vector>
 
 #include "detector.hpp"
+#include "homography.hpp"
 #include "match_l2.hpp"
 #include "sift.hpp"
-#include "stabilizer.hpp"
 
 namespace gtx {
 

@@ -1,5 +1,5 @@
 // Image-to-image registration: RootSIFT keypoints (sift.hip) -> MFMA 2-NN matching (match_l2.hip)
-// -> Lowe ratio -> robust homography (stabilizer.hip). Mirrors what
+// -> Lowe ratio -> robust homography (homography.hip, homography_refit.cpp). Mirrors what
 // geotrax/utils/registration.py:59-85 asks stabilo for.
 #pragma once
 #include "../../include/gtx.h"

@@ -5,10 +5,10 @@
 #include <cstring>
 #include <vector>
 
+#include "homography.hpp"
 #include "match_l2.hpp"
 #include "net_runtime.hpp"   // gtx_ctx
 #include "sift.hpp"
-#include "stabilizer.hpp"
 
 namespace gtx {
 
@@ -167,7 +167,7 @@ void SiftStab::submit_gray_dev(const void* gray, int gh, int gw, const float* bo
   } else {
     GTX_HIP(hipMemsetAsync(S.n_pairs.p, 0, sizeof(int), s));
   }
-  ransac_submit(s, S.pts.as<float4>(), S.n_pairs.as<int>(), n_cur_dev, S.cfg.seed, S.n_hyp, S.gw, S.gh, S.cfg.ransac_threshold,
+  ransac_submit(s, S.pts.as<float4>(), S.n_pairs.as<int>(), n_cur_dev, S.cfg.seed, S.n_hyp, S.gw, S.gh, S.cfg.ransac_threshold, 0,
                 S.rstate.as<unsigned long long>(), S.record.p);
   GTX_HIP(hipMemcpyAsync(S.h_out, S.record.p, ransac_record_bytes(), hipMemcpyDeviceToHost, s));
   GTX_HIP(hipMemcpyAsync(S.h_out + kRecordRoom, S.sift->counters_dev(), 16, hipMemcpyDeviceToHost, s));
@@ -195,7 +195,7 @@ void SiftStab::collect(double H[9], int* valid, int stats[4]) {
   S.last_pairs.assign(S.h_pts(), S.h_pts() + n_pairs);
   double Hc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   int n_inl = 0, ok = 0;
-  if (n_cur >= 1 && S.n_ref >= 2 && n_pairs >= 4 && ransac_finish(S.h_out, S.h_pts(), S.gw, S.gh, S.cfg.ransac_threshold, Hc, &n_inl)) ok = 1;
+  if (n_cur >= 1 && S.n_ref >= 2 && n_pairs >= 4 && ransac_finish(S.h_out, S.h_pts(), S.gw, S.gh, S.cfg.ransac_threshold, false, Hc, &n_inl)) ok = 1;
   if (!ok) n_inl = 0;
   if (H) std::memcpy(H, Hc, sizeof Hc);
   if (valid) *valid = ok;

@@ -1,6 +1,6 @@
 // GPU homography stabilizer for gfx950: ORB-style keypoints (integer-exact pyramid, FAST-9/16,
 // Harris ranking, intensity-centroid orientation, steered BRIEF), brute-force Hamming 2-NN with
-// Lowe's ratio test, and a massively parallel RANSAC homography with an f64 refit on the host.
+// Lowe's ratio test; the matches go to the shared robust homography solver (homography.hpp: RANSAC on the GPU, f64 refit on the host).
 //
 // Stands in for stabilo.Stabilizer as the reference drives it (geotrax/extract.py:139,177-187;
 // parameters geotrax/cfg/default.yaml:100-145): detector 'orb', matcher 'bf', filter 'ratio',
@@ -19,8 +19,10 @@
 #include <cstring>
 #include <vector>
 
+#include "clahe.hpp"
 #include "detector.hpp"   // gtx_ctx
 #include "geometry.hpp"
+#include "homography.hpp"
 #include "op_staging.hpp"
 #include "stabilizer.hpp"
 
@@ -872,200 +874,6 @@ __global__ __launch_bounds__(256) void match_kernel(const unsigned long long* __
     }
 }
 
-// ------------------------------------------------------------------ RANSAC
-__device__ __forceinline__ unsigned hash_u32(unsigned x) {
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return x;
-}
-
-// Homography from 4 correspondences by the projective-basis construction: A maps the canonical
-// basis (e1, e2, e3, e1+e2+e3) to the four source points, B to the four destination points,
-// H = B * adj(A). Closed form, static indexing only (stays in registers), f64.
-__device__ __forceinline__ bool basis_matrix(const double* px, const double* py, double* M) {
-  // solve [p0 p1 p2] (l0,l1,l2)^T = p3 by Cramer's rule; columns then scaled by l
-  const double x0 = px[0], y0 = py[0], x1 = px[1], y1 = py[1], x2 = px[2], y2 = py[2], x3 = px[3], y3 = py[3];
-  const double det = x0 * (y1 - y2) - x1 * (y0 - y2) + x2 * (y0 - y1);
-  if (!(fabs(det) > 1e-9)) return false;
-  const double l0 = (x3 * (y1 - y2) - x1 * (y3 - y2) + x2 * (y3 - y1)) / det;
-  const double l1 = (x0 * (y3 - y2) - x3 * (y0 - y2) + x2 * (y0 - y3)) / det;
-  const double l2 = (x0 * (y1 - y3) - x1 * (y0 - y3) + x3 * (y0 - y1)) / det;
-  if (!(fabs(l0) > 1e-9 && fabs(l1) > 1e-9 && fabs(l2) > 1e-9)) return false;   // three points collinear
-  M[0] = l0 * x0; M[1] = l1 * x1; M[2] = l2 * x2;
-  M[3] = l0 * y0; M[4] = l1 * y1; M[5] = l2 * y2;
-  M[6] = l0;      M[7] = l1;      M[8] = l2;
-  return true;
-}
-__device__ bool homography4(const double* px, const double* py, const double* qx, const double* qy, double* H) {
-  double A[9], B[9];
-  if (!basis_matrix(px, py, A) || !basis_matrix(qx, qy, B)) return false;
-  const double adj[9] = {A[4] * A[8] - A[5] * A[7], A[2] * A[7] - A[1] * A[8], A[1] * A[5] - A[2] * A[4],
-                         A[5] * A[6] - A[3] * A[8], A[0] * A[8] - A[2] * A[6], A[2] * A[3] - A[0] * A[5],
-                         A[3] * A[7] - A[4] * A[6], A[1] * A[6] - A[0] * A[7], A[0] * A[4] - A[1] * A[3]};
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) H[r * 3 + c] = B[r * 3] * adj[c] + B[r * 3 + 1] * adj[3 + c] + B[r * 3 + 2] * adj[6 + c];
-  if (!(fabs(H[8]) > 1e-12)) return false;
-  const double inv = 1.0 / H[8];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) H[i] *= inv;
-  return true;
-}
-
-// Affine map from 3 correspondences (Cramer's rule), as a 3x3 matrix with last row (0, 0, 1).
-__device__ bool affine3(const double* px, const double* py, const double* qx, const double* qy, double* H) {
-  const double x0 = px[0], y0 = py[0], x1 = px[1], y1 = py[1], x2 = px[2], y2 = py[2];
-  const double det = x0 * (y1 - y2) - y0 * (x1 - x2) + (x1 * y2 - x2 * y1);
-  if (!(fabs(det) > 1e-9)) return false;           // the three source points are collinear
-  const double id = 1.0 / det;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const double* q = r == 0 ? qx : qy;
-    const double u0 = q[0], u1 = q[1], u2 = q[2];
-    H[r * 3 + 0] = (u0 * (y1 - y2) - y0 * (u1 - u2) + (u1 * y2 - u2 * y1)) * id;
-    H[r * 3 + 1] = (x0 * (u1 - u2) - u0 * (x1 - x2) + (x1 * u2 - x2 * u1)) * id;
-    H[r * 3 + 2] = (x0 * (y1 * u2 - y2 * u1) - y0 * (x1 * u2 - x2 * u1) + u0 * (x1 * y2 - x2 * y1)) * id;
-  }
-  H[6] = 0.0; H[7] = 0.0; H[8] = 1.0;
-  return true;
-}
-
-// One hypothesis: 4 (projective) or 3 (affine) distinct matches drawn by a counter-based hash of (seed, hypothesis, draw),
-// exact minimal solve in normalised coordinates, de-normalised H. Straight-line f64 code without LDS: every lane of a wave
-// runs it on the same inputs and gets the same bits, which is how the scoring wave below obtains its hypothesis.
-__device__ __forceinline__ bool make_hypothesis(const float4* __restrict__ pts, int n, unsigned seed, int hyp, double cx, double cy, double sc, int affine, double H[9]) {
-  // inlined, and every small array indexed by unrolled constants: as a call with H behind a pointer and idx[] indexed by a
-  // run-time k the kernel kept 80 bytes of scratch per lane -- 9.2 MB of HBM writes per launch for a one-record result
-  // (profiles/r05_pmc_traffic.json)
-  const int ns = affine ? 3 : 4;
-  if (n < ns) return false;
-  int idx[4] = {0, 0, 0, 0};
-  unsigned ctr = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (k >= ns) break;
-    for (;;) {
-      const int cand = (int)(hash_u32(seed ^ hash_u32((unsigned)hyp * 977u + ctr)) % (unsigned)n);
-      ++ctr;
-      bool dup = false;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) dup |= (j < k) && idx[j] == cand;
-      if (!dup) { idx[k] = cand; break; }
-    }
-  }
-  double px[4], py[4], qx[4], qy[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float4 p = pts[idx[k]];
-    px[k] = ((double)p.x - cx) * sc; py[k] = ((double)p.y - cy) * sc;
-    qx[k] = ((double)p.z - cx) * sc; qy[k] = ((double)p.w - cy) * sc;
-  }
-  double Hn[9];
-  if (!(affine ? affine3(px, py, qx, qy, Hn) : homography4(px, py, qx, qy, Hn))) return false;
-  // de-normalise: H = T^-1 Hn T with T = [[sc,0,-sc*cx],[0,sc,-sc*cy],[0,0,1]]
-  const double is = 1.0 / sc;
-  double M[9];
-  for (int r = 0; r < 3; ++r) {   // M = Hn T
-    M[r * 3 + 0] = Hn[r * 3 + 0] * sc;
-    M[r * 3 + 1] = Hn[r * 3 + 1] * sc;
-    M[r * 3 + 2] = Hn[r * 3 + 2] - sc * (Hn[r * 3 + 0] * cx + Hn[r * 3 + 1] * cy);
-  }
-  for (int k = 0; k < 3; ++k) {   // H = T^-1 M, T^-1 = [[is,0,cx],[0,is,cy],[0,0,1]]
-    H[0 + k] = is * M[0 + k] + cx * M[6 + k];
-    H[3 + k] = is * M[3 + k] + cy * M[6 + k];
-    H[6 + k] = M[6 + k];
-  }
-  return fabs(H[8]) > 1e-12;
-}
-
-// Device-side result record of one stabilize pass, fetched with a single D2H copy (the match points follow it in the same
-// buffer: StabOut).
-struct StabResult {
-  int n_match, best, n_cur, pad;
-  double H[9];
-  long cost;        // the winner's MSAC cost in 1/1024 px^2 (0 when there is none); the record stays 96 bytes with its padding
-};
-
-// Hypothesise, score and pick the winner in ONE launch (round 4; three launches before: solve, score, argmin).
-// A wave makes hypothesis `hyp` (every lane the same solve) and scores it: truncated squared reprojection error (MSAC) over
-// all matches, quantised to 1/1024 px^2 so that the sum is an exact integer regardless of the reduction order. The
-// workgroup's 8 costs are reduced in LDS to one key (cost << 16 | hyp: the lowest cost, then the lowest hypothesis index,
-// exactly the order of the former argmin) and folded into `state[0]` with one device-scope atomic minimum; `state[1]` is a
-// ticket: the workgroup that draws the last one knows every minimum has been applied (each workgroup's ticket add depends on
-// the value its minimum returned), reads the winner back with another atomic, re-derives its H from the index, writes the
-// result record and re-arms state for the next pass. Device-scope atomics are performed beyond the per-XCD L2s, so no
-// fence and no other cross-workgroup visibility is involved.
-constexpr unsigned long long kNoHyp = ~0ull;
-__global__ __launch_bounds__(512) void ransac_kernel(const float4* __restrict__ pts, const int* __restrict__ n_p, const int* __restrict__ n_cur_p,
-                                                      unsigned seed, int n_hyp, double cx, double cy, double sc, int affine, float thr2,
-                                                      unsigned long long* __restrict__ state /*[2]: best key (armed: all ones), tickets (0)*/,
-                                                      StabResult* __restrict__ res) {
-  constexpr int kHypPerWg = 8;
-  __shared__ unsigned long long s_key[kHypPerWg];
-  __shared__ int s_last;
-  const int n = *n_p;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int hyp = blockIdx.x * kHypPerWg + wv;
-  unsigned long long key = kNoHyp;
-  if (hyp < n_hyp) {
-    double H[9];
-    if (make_hypothesis(pts, n, seed, hyp, cx, cy, sc, affine, H)) {
-      long acc = 0;
-      for (int i = lane; i < n; i += 64) {
-        const float4 p = pts[i];
-        const double x = p.x, y = p.y;
-        const double w = H[6] * x + H[7] * y + H[8];
-        double e = (double)thr2;
-        if (fabs(w) > 1e-12) {
-          const double iw = 1.0 / w;
-          const double dx = (H[0] * x + H[1] * y + H[2]) * iw - p.z;
-          const double dy = (H[3] * x + H[4] * y + H[5]) * iw - p.w;
-          e = fmin(dx * dx + dy * dy, (double)thr2);
-        }
-        acc += (long)(e * 1024.0 + 0.5);
-      }
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-      key = ((unsigned long long)acc << 16) | (unsigned long long)hyp;     // cost < 2^47 (4096 per match at most), hyp < 2^16
-    }
-  }
-  if (lane == 0) s_key[wv] = key;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long k = s_key[0];
-#pragma unroll
-    for (int i = 1; i < kHypPerWg; ++i) k = min(k, s_key[i]);
-    // The ordering is the memory model's: the minimum is published by the RELEASE half of the ticket's acq_rel read-modify-write
-    // (agent scope), and the workgroup that draws the last ticket ACQUIRES every earlier workgroup's release through the
-    // ticket word's modification order (a release sequence of RMWs), so its read of state[0] below sees every minimum.
-    // The s_waitcnt between the two is not part of that argument: cdna_hip_programming.md (section 6, Guideline 16, Pitfall 12)
-    // records that ROCm 7.2 can drop the wait a release implies, and prescribes keeping an explicit one in front of the ticket.
-    (void)__hip_atomic_fetch_min(&state[0], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long ticket = __hip_atomic_fetch_add(&state[1], 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = ticket == (unsigned long long)gridDim.x - 1 ? 1 : 0;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  // ---- the last workgroup: every minimum has been applied
-  if (wv != 0) return;
-  unsigned long long best_key = 0;
-  if (lane == 0) best_key = __hip_atomic_fetch_min(&state[0], kNoHyp, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);   // acquire read-back, in L2
-  best_key = __shfl(best_key, 0, 64);
-  const int b = best_key == kNoHyp ? -1 : (int)(best_key & 0xffffull);
-  double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (b >= 0) make_hypothesis(pts, n, seed, b, cx, cy, sc, affine, H);
-  if (lane == 0) {
-    res->n_match = n;
-    res->n_cur = *n_cur_p;
-    res->best = b;
-    for (int k = 0; k < 9; ++k) res->H[k] = H[k];
-    res->cost = b >= 0 ? (long)(best_key >> 16) : 0;
-    atomicExch(&state[0], kNoHyp);                                         // re-arm for the next pass on this stream
-    atomicExch(&state[1], 0ull);
-  }
-}
-
 }  // namespace
 
 // =========================================================================== host side
@@ -1135,12 +943,10 @@ struct Stabilizer::Impl {
     int host_n = 0;
   } ref, cur;
   DevBuf d_bidx, d_bd, d_sd, d_mq, d_mt, d_md, d_nmatch, d_best, d_pidx, d_pd1, d_pd2, d_rstate, d_mticket;
-  DevBuf d_out;                  // StabResult, then the match points (float4 x slots): one D2H copy per pass
+  DevBuf d_out;                  // the solver's record, then the match points (float4 x slots): one D2H copy per pass
   uint8_t* h_out = nullptr;      // pinned image of d_out
-  StabResult* h_res = nullptr;   // = h_out
   float4* h_pts = nullptr;       // = h_out + kOutPts
-  static constexpr size_t kOutPts = (sizeof(StabResult) + 15) / 16 * 16;
-  StabResult* d_res() const { return d_out.as<StabResult>(); }
+  static constexpr size_t kOutPts = 96;   // room for ransac_record_bytes() (checked at construction), a multiple of 16
   float4* d_mpts() const { return reinterpret_cast<float4*>(d_out.as<uint8_t>() + kOutPts); }
   hipEvent_t done_ev = nullptr;
   hipEvent_t t0_ev = nullptr, t1_ev = nullptr;   // GPU time of the last submitted pass (timing events)
@@ -1300,17 +1106,14 @@ Stabilizer::Stabilizer(gtx_ctx* ctx, const gtx_stab_config& cfg) : impl_(new Imp
   S.d_nmatch.alloc(sizeof(int));
   S.n_hyp = std::max(64, std::min(cfg.ransac_max_iter, 2048));
   S.d_best.alloc(sizeof(int));
+  GTX_CHECK(ransac_record_bytes() <= Impl::kOutPts, "stabilizer: the RANSAC record grew beyond %zu bytes", Impl::kOutPts);
   S.d_out.alloc(Impl::kOutPts + sizeof(float4) * slots);
   GTX_HIP(hipHostMalloc((void**)&S.h_out, Impl::kOutPts + sizeof(float4) * slots));
-  S.h_res = reinterpret_cast<StabResult*>(S.h_out);
   S.h_pts = reinterpret_cast<float4*>(S.h_out + Impl::kOutPts);
   S.d_mticket.alloc(sizeof(unsigned));
   GTX_HIP(hipMemset(S.d_mticket.p, 0, sizeof(unsigned)));
   S.d_rstate.alloc(2 * sizeof(unsigned long long));
-  {
-    const unsigned long long armed[2] = {kNoHyp, 0ull};
-    GTX_HIP(hipMemcpy(S.d_rstate.p, armed, sizeof armed, hipMemcpyHostToDevice));
-  }
+  ransac_arm(S.d_rstate.as<unsigned long long>(), ctx->stream);
   GTX_HIP(hipEventCreateWithFlags(&S.done_ev, wait_event_flags(false)));
   GTX_HIP(hipEventCreate(&S.t0_ev));
   GTX_HIP(hipEventCreate(&S.t1_ev));
@@ -1432,146 +1235,6 @@ void Stabilizer::Impl::extract(const uint8_t* gray_dev, const float* boxes, int 
 }
 
 namespace {
-
-// Robust refinement of the RANSAC winner. Keypoints sit on integer pixels of their pyramid level,
-// so matches carry 1-2 px of localisation noise in full-resolution pixels -- comparable to the
-// RANSAC threshold. A hard inlier cut at the threshold throws away (and biases) much of the
-// evidence. Instead: keep every match within 3x the threshold of the winner and minimise the
-// geometric transfer error with iteratively re-weighted Gauss-Newton (Tukey biweight, scale from
-// the median residual), h33 = 1, in normalised coordinates.
-bool refine_homography(const std::vector<float4>& pts, double cx, double cy, double sc,
-                       double thr, double H[9], int* n_inliers, bool affine = false) {
-  const size_t n = pts.size();
-  const int np = affine ? 6 : 8;                     // affine: h31 = h32 = 0 stay as they are, six parameters move
-  const size_t min_pts = affine ? 3 : 4;
-  // to normalised coordinates: Hn = T H T^-1
-  auto to_norm = [&](const double* Hp, double* Hn) {
-    const double is = 1.0 / sc;
-    double M[9];  // M = H T^-1, T^-1 = [[is,0,cx],[0,is,cy],[0,0,1]]
-    for (int r = 0; r < 3; ++r) {
-      M[r * 3 + 0] = Hp[r * 3 + 0] * is;
-      M[r * 3 + 1] = Hp[r * 3 + 1] * is;
-      M[r * 3 + 2] = Hp[r * 3 + 0] * cx + Hp[r * 3 + 1] * cy + Hp[r * 3 + 2];
-    }
-    for (int k = 0; k < 3; ++k) {  // Hn = T M, T = [[sc,0,-sc cx],[0,sc,-sc cy],[0,0,1]]
-      Hn[0 + k] = sc * M[0 + k] - sc * cx * M[6 + k];
-      Hn[3 + k] = sc * M[3 + k] - sc * cy * M[6 + k];
-      Hn[6 + k] = M[6 + k];
-    }
-    const double inv = 1.0 / Hn[8];
-    for (int i = 0; i < 9; ++i) Hn[i] *= inv;
-  };
-  auto from_norm = [&](const double* Hn, double* Hp) {
-    const double is = 1.0 / sc;
-    double M[9];  // M = Hn T
-    for (int r = 0; r < 3; ++r) {
-      M[r * 3 + 0] = Hn[r * 3 + 0] * sc;
-      M[r * 3 + 1] = Hn[r * 3 + 1] * sc;
-      M[r * 3 + 2] = Hn[r * 3 + 2] - sc * (Hn[r * 3 + 0] * cx + Hn[r * 3 + 1] * cy);
-    }
-    for (int k = 0; k < 3; ++k) {
-      Hp[0 + k] = is * M[0 + k] + cx * M[6 + k];
-      Hp[3 + k] = is * M[3 + k] + cy * M[6 + k];
-      Hp[6 + k] = M[6 + k];
-    }
-    const double inv = 1.0 / Hp[8];
-    for (int i = 0; i < 9; ++i) Hp[i] *= inv;
-  };
-  std::vector<double> x(n), y(n), u(n), v(n);
-  for (size_t i = 0; i < n; ++i) {
-    x[i] = (pts[i].x - cx) * sc; y[i] = (pts[i].y - cy) * sc;
-    u[i] = (pts[i].z - cx) * sc; v[i] = (pts[i].w - cy) * sc;
-  }
-  double h[9];
-  to_norm(H, h);
-  auto residual = [&](size_t i, double& rx, double& ry, double& w) {
-    w = h[6] * x[i] + h[7] * y[i] + 1.0;
-    rx = (h[0] * x[i] + h[1] * y[i] + h[2]) / w - u[i];
-    ry = (h[3] * x[i] + h[4] * y[i] + h[5]) / w - v[i];
-  };
-  // support set: within 3 thresholds of the winner (fixed over the iterations)
-  std::vector<int> sup;
-  const double lim = 3.0 * thr * sc;
-  for (size_t i = 0; i < n; ++i) {
-    double rx, ry, w;
-    residual(i, rx, ry, w);
-    if (std::fabs(w) > 1e-9 && rx * rx + ry * ry <= lim * lim) sup.push_back((int)i);
-  }
-  if (sup.size() < min_pts) return false;
-  std::vector<double> un(sup.size());
-  for (int iter = 0; iter < 8; ++iter) {
-    for (size_t k = 0; k < sup.size(); ++k) {
-      double rx, ry, w;
-      residual(sup[k], rx, ry, w);
-      un[k] = std::sqrt(rx * rx + ry * ry) / sc;   // pixels
-    }
-    std::vector<double> tmp = un;
-    std::nth_element(tmp.begin(), tmp.begin() + tmp.size() / 2, tmp.end());
-    const double sigma = std::max(1.4826 * tmp[tmp.size() / 2], 0.05);
-    const double c = 4.685 * sigma;
-    double A[64] = {0}, g[8] = {0};
-    for (size_t k = 0; k < sup.size(); ++k) {
-      const int i = sup[k];
-      if (un[k] >= c) continue;
-      const double t = 1.0 - (un[k] / c) * (un[k] / c);
-      const double wt = t * t;
-      double rx, ry, w;
-      residual(i, rx, ry, w);
-      const double iw = 1.0 / w, px = rx + u[i], py = ry + v[i];
-      const double Jx[8] = {x[i] * iw, y[i] * iw, iw, 0, 0, 0, -px * x[i] * iw, -px * y[i] * iw};
-      const double Jy[8] = {0, 0, 0, x[i] * iw, y[i] * iw, iw, -py * x[i] * iw, -py * y[i] * iw};
-      for (int a = 0; a < np; ++a) {
-        g[a] += wt * (Jx[a] * rx + Jy[a] * ry);
-        for (int b = a; b < np; ++b) A[a * 8 + b] += wt * (Jx[a] * Jx[b] + Jy[a] * Jy[b]);
-      }
-    }
-    for (int a = 0; a < np; ++a)
-      for (int b = 0; b < a; ++b) A[a * 8 + b] = A[b * 8 + a];
-    // Cholesky solve A d = g
-    double Lc[64] = {0};
-    bool ok = true;
-    for (int i = 0; i < np && ok; ++i)
-      for (int j = 0; j <= i; ++j) {
-        double s = A[i * 8 + j];
-        for (int k = 0; k < j; ++k) s -= Lc[i * 8 + k] * Lc[j * 8 + k];
-        if (i == j) {
-          if (!(s > 0)) { ok = false; break; }
-          Lc[i * 8 + i] = std::sqrt(s);
-        } else {
-          Lc[i * 8 + j] = s / Lc[j * 8 + j];
-        }
-      }
-    if (!ok) break;
-    double yv[8], d[8];
-    for (int i = 0; i < np; ++i) {
-      double s = g[i];
-      for (int k = 0; k < i; ++k) s -= Lc[i * 8 + k] * yv[k];
-      yv[i] = s / Lc[i * 8 + i];
-    }
-    for (int i = np - 1; i >= 0; --i) {
-      double s = yv[i];
-      for (int k = i + 1; k < np; ++k) s -= Lc[k * 8 + i] * d[k];
-      d[i] = s / Lc[i * 8 + i];
-    }
-    double step = 0;
-    for (int a = 0; a < np; ++a) { h[a] -= d[a]; step = std::max(step, std::fabs(d[a])); }
-    if (step < 1e-14) break;
-  }
-  from_norm(h, H);
-  int cnt = 0;
-  const double t2 = thr * sc * thr * sc;
-  for (size_t i = 0; i < n; ++i) {
-    double rx, ry, w;
-    residual(i, rx, ry, w);
-    if (rx * rx + ry * ry <= t2) ++cnt;
-  }
-  if (n_inliers) *n_inliers = cnt;
-  return cnt >= (int)min_pts;
-}
-
-}  // namespace
-
-namespace {
 // The match launch: a grid over the keypoint SLOTS of both sets (their counts are read on the device). Buffers: query / train
 // descriptors and counts, the per-chunk partials [cdiv(slots_t, 256)][slots_q], the ticket (0 between launches), the outputs.
 struct MatchBufs {
@@ -1589,12 +1252,6 @@ void launch_match_kernel(hipStream_t s, int slots_q, int slots_t, const MatchBuf
                      B.part_d1, B.part_d2, B.ticket, ratio, keep_all, B.q_xy, B.t_xy, B.best_idx, B.best_d, B.second_d, B.m_q, B.m_t, B.m_d, B.m_pts,
                      B.n_match);
 }
-// The RANSAC launch: n_hyp hypotheses, 8 per workgroup, on a state that is armed ({all ones, 0}) between launches.
-void launch_ransac_kernel(hipStream_t s, const float4* pts, const int* n_p, const int* n_cur_p, unsigned seed, int n_hyp, int frame_w, int frame_h,
-                          int affine, float thr, unsigned long long* state, StabResult* res) {
-  const double cx = frame_w / 2.0, cy = frame_h / 2.0, sc = 2.0 / frame_w;
-  hipLaunchKernelGGL(ransac_kernel, dim3(cdiv(n_hyp, 8)), dim3(512), 0, s, pts, n_p, n_cur_p, seed, n_hyp, cx, cy, sc, affine, thr * thr, state, res);
-}
 }  // namespace
 
 void Stabilizer::Impl::launch_match() {
@@ -1609,9 +1266,8 @@ void Stabilizer::Impl::launch_match() {
 void Stabilizer::Impl::submit_match() {
   hipStream_t s = ctx->stream;
   launch_match();
-  launch_ransac_kernel(s, d_mpts(), d_nmatch.as<int>(), cur.n.as<int>(), cfg.seed, n_hyp, fw, fh, cfg.affine ? 1 : 0, cfg.ransac_threshold,
-                       d_rstate.as<unsigned long long>(), d_res());
-  GTX_HIP(hipGetLastError());
+  ransac_submit(s, d_mpts(), d_nmatch.as<int>(), cur.n.as<int>(), cfg.seed, n_hyp, fw, fh, cfg.ransac_threshold, cfg.affine ? 1 : 0,
+                d_rstate.as<unsigned long long>(), d_out.p);
   GTX_HIP(hipMemcpyAsync(h_out, d_out.p, kOutPts + sizeof(float4) * slots_cur, hipMemcpyDeviceToHost, s));
   GTX_HIP(hipEventRecord(t1_ev, s));
   GTX_HIP(hipEventRecord(done_ev, s));
@@ -1626,24 +1282,11 @@ void Stabilizer::Impl::collect(double Hout[9], int* valid_out, int st[4]) {
   last_ms = 0.f;
   if (timed) GTX_HIP(hipEventElapsedTime(&last_ms, t0_ev, t1_ev));
   timed = false;
-  const StabResult& R = *h_res;
-  const double cx = fw / 2.0, cy = fh / 2.0, sc = 2.0 / fw;
-  cur.host_n = R.n_cur;
-  stats[0] = ref.host_n; stats[1] = R.n_cur; stats[2] = R.n_match; stats[3] = 0;
-  valid = false;
-  if (R.n_match >= (cfg.affine ? 3 : 4) && R.best >= 0) {
-    std::vector<float4> pts(h_pts, h_pts + R.n_match);
-    double Hc[9];
-    std::memcpy(Hc, R.H, sizeof Hc);
-    const double inv = 1.0 / Hc[8];
-    for (double& v : Hc) v *= inv;
-    int n_inl = 0;
-    if (refine_homography(pts, cx, cy, sc, (double)cfg.ransac_threshold, Hc, &n_inl, cfg.affine != 0)) {
-      std::memcpy(H, Hc, sizeof H);
-      valid = true;
-      stats[3] = n_inl;
-    }
-  }
+  int n_match = 0, n_cur = 0, n_inl = 0;
+  ransac_record_counts(h_out, &n_match, &n_cur);
+  cur.host_n = n_cur;
+  valid = ransac_finish(h_out, h_pts, fw, fh, cfg.ransac_threshold, cfg.affine != 0, H, &n_inl);    // H stays as it was when there is no model
+  stats[0] = ref.host_n; stats[1] = n_cur; stats[2] = n_match; stats[3] = valid ? n_inl : 0;
   if (Hout) std::memcpy(Hout, H, sizeof H);
   if (valid_out) *valid_out = valid ? 1 : 0;
   if (st) std::memcpy(st, stats, sizeof stats);
@@ -1823,114 +1466,18 @@ void Stabilizer::candidates(int which, int i, int cap, int* n, int* pix, int* sc
 
 void Stabilizer::pattern(int8_t* out) const { std::memcpy(out, impl_->pattern.data(), impl_->pattern.size()); }
 
-// Blocking robust homography from matched point pairs already in HBM (registration path): the same
-// hypothesis / MSAC-score / argmin kernels as the per-frame stabilizer, then the host IRLS refit.
-// cv2.createCLAHE(2.0, (8, 8)).apply(gray) for a host image (the stabilizer's own pre-processing step, exposed for tests / tools).
-void clahe_image(gtx_ctx* ctx, const uint8_t* gray, int h, int w, uint8_t* out) {
-  GTX_HIP(hipSetDevice(ctx->device));
-  GTX_CHECK(h >= 8 && w >= 8, "clahe: image %dx%d is smaller than the tile grid", w, h);
-  const size_t bytes = (size_t)h * w;
-  DevBuf d_src(bytes), d_dst(bytes), d_lut(kClaheLutBytes);
-  hipStream_t s = ctx->stream;
-  GTX_HIP(hipMemcpyAsync(d_src.p, gray, bytes, hipMemcpyHostToDevice, s));
-  clahe_dev(d_src.as<uint8_t>(), h, w, d_lut.as<uint8_t>(), d_dst.as<uint8_t>(), s);
-  GTX_HIP(hipGetLastError());
-  GTX_HIP(hipMemcpyAsync(out, d_dst.p, bytes, hipMemcpyDeviceToHost, s));
-  GTX_HIP(hipStreamSynchronize(s));
-}
-
-bool ransac_homography(int device, hipStream_t s, const float4* d_pts, int n_match, unsigned seed, int n_hyp, int frame_w, int frame_h,
-                       float threshold, double H[9], int* n_inliers) {
-  *n_inliers = 0;
-  if (n_match < 4) return false;
-  GTX_HIP(hipSetDevice(device));
-  DevBuf d_n(sizeof(int) * 2), d_state(2 * sizeof(unsigned long long)), d_res(sizeof(StabResult));
-  const int two[2] = {n_match, n_match};
-  const unsigned long long armed[2] = {kNoHyp, 0ull};
-  GTX_HIP(hipMemcpyAsync(d_n.p, two, sizeof two, hipMemcpyHostToDevice, s));
-  GTX_HIP(hipMemcpyAsync(d_state.p, armed, sizeof armed, hipMemcpyHostToDevice, s));
-  const double cx = frame_w / 2.0, cy = frame_h / 2.0, sc = 2.0 / frame_w;
-  GTX_CHECK(n_hyp <= 65536, "ransac: at most 65536 hypotheses (got %d)", n_hyp);
-  launch_ransac_kernel(s, d_pts, d_n.as<int>(), d_n.as<int>() + 1, seed, n_hyp, frame_w, frame_h, 0, threshold, d_state.as<unsigned long long>(),
-                       d_res.as<StabResult>());
-  GTX_HIP(hipGetLastError());
-  StabResult R;
-  std::vector<float4> pts(n_match);
-  GTX_HIP(hipMemcpyAsync(&R, d_res.p, sizeof R, hipMemcpyDeviceToHost, s));
-  GTX_HIP(hipMemcpyAsync(pts.data(), d_pts, sizeof(float4) * n_match, hipMemcpyDeviceToHost, s));
-  GTX_HIP(hipStreamSynchronize(s));
-  if (R.best < 0) return false;
-  double Hc[9];
-  std::memcpy(Hc, R.H, sizeof Hc);
-  const double inv = 1.0 / Hc[8];
-  for (double& v : Hc) v *= inv;
-  if (!refine_homography(pts, cx, cy, sc, (double)threshold, Hc, n_inliers)) return false;
-  std::memcpy(H, Hc, sizeof Hc);
-  return true;
-}
-
-// The two halves of ransac_homography for a chain that keeps the pair count in HBM and must not wait (sift_stab.cpp): ransac_submit
-// enqueues the one launch on a state that ransac_arm initialised once (the kernel re-arms it), ransac_finish is the host half on the
-// record and the pairs the caller copied back.
-size_t ransac_record_bytes() { return sizeof(StabResult); }
-
-void ransac_arm(unsigned long long* state_dev, hipStream_t s) {
-  const unsigned long long armed[2] = {kNoHyp, 0ull};
-  GTX_HIP(hipMemcpyAsync(state_dev, armed, sizeof armed, hipMemcpyHostToDevice, s));
-  GTX_HIP(hipStreamSynchronize(s));
-}
-
-void ransac_submit(hipStream_t s, const float4* d_pts, const int* n_pairs_dev, const int* n_cur_dev, unsigned seed, int n_hyp, int frame_w, int frame_h,
-                   float threshold, unsigned long long* state_dev, void* record_dev) {
-  GTX_CHECK(n_hyp <= 65536, "ransac: at most 65536 hypotheses (got %d)", n_hyp);
-  launch_ransac_kernel(s, d_pts, n_pairs_dev, n_cur_dev, seed, n_hyp, frame_w, frame_h, 0, threshold, state_dev, static_cast<StabResult*>(record_dev));
-  GTX_HIP(hipGetLastError());
-}
-
-void ransac_record_counts(const void* record_host, int* n_pairs, int* n_cur) {
-  const StabResult& R = *static_cast<const StabResult*>(record_host);
-  *n_pairs = R.n_match;
-  *n_cur = R.n_cur;
-}
-
-bool ransac_finish(const void* record_host, const float4* pts_host, int frame_w, int frame_h, float threshold, double H[9], int* n_inliers) {
-  const StabResult& R = *static_cast<const StabResult*>(record_host);
-  *n_inliers = 0;
-  if (R.n_match < 4 || R.best < 0) return false;
-  const double cx = frame_w / 2.0, cy = frame_h / 2.0, sc = 2.0 / frame_w;
-  std::vector<float4> pts(pts_host, pts_host + R.n_match);
-  double Hc[9];
-  std::memcpy(Hc, R.H, sizeof Hc);
-  const double inv = 1.0 / Hc[8];
-  for (double& v : Hc) v *= inv;
-  if (!refine_homography(pts, cx, cy, sc, (double)threshold, Hc, n_inliers)) return false;
-  std::memcpy(H, Hc, sizeof Hc);
-  return true;
-}
-
-// ---- operator hooks (gtx_op_orb_match / gtx_op_orb_ransac): one launch of match_kernel / ransac_kernel on host arrays. The ticket
-// and the RANSAC state live with the context and are initialised once, when the first hook call allocates them: every later call
-// finds them as the launch before it left them, which is how the kernels' re-arming is exercised. The caller has validated all sizes.
-namespace {
-struct OrbOpState {
-  unsigned long long ransac[2];
-  unsigned ticket, pad;
-};
-OrbOpState* orb_op_state(gtx_ctx* ctx) {
-  if (!ctx->orb_op_state) {
-    const OrbOpState armed{{kNoHyp, 0ull}, 0u, 0u};
-    GTX_HIP(hipMalloc(&ctx->orb_op_state, sizeof armed));
-    GTX_HIP(hipMemcpy(ctx->orb_op_state, &armed, sizeof armed, hipMemcpyHostToDevice));
-  }
-  return static_cast<OrbOpState*>(ctx->orb_op_state);
-}
-}  // namespace
+// ---- operator hook (gtx_op_orb_match): one launch of match_kernel on host arrays. The ticket lives with the context and is zeroed
+// once, when the first hook call allocates it: every later call finds it as the launch before it left it, which is how the kernel's
+// re-arming is exercised. The caller has validated all sizes.
 
 void op_orb_match(gtx_ctx* ctx, const uint8_t* desc_q, int nq, int slots_q, const uint8_t* desc_t, int nt, int slots_t, float ratio, int keep_all,
                   const float* xy_q, const float* xy_t, int* best_idx, int* best_d, int* second_d, int* m_q, int* m_t, int* m_d, float* m_pts,
                   int* n_match) {
   GTX_HIP(hipSetDevice(ctx->device));
-  OrbOpState* st = orb_op_state(ctx);
+  if (!ctx->orb_match_ticket) {
+    GTX_HIP(hipMalloc(&ctx->orb_match_ticket, sizeof(unsigned)));
+    GTX_HIP(hipMemset(ctx->orb_match_ticket, 0, sizeof(unsigned)));
+  }
   DevBuf dq, dt, dqxy, dtxy, dn, pi, p1, p2, bi, bd, sd, mq, mt, md, mp, nm;
   upload(dq, desc_q, 32 * (size_t)nq, 32 * (size_t)slots_q);
   upload(dt, desc_t, 32 * (size_t)nt, 32 * (size_t)slots_t);
@@ -1943,7 +1490,7 @@ void op_orb_match(gtx_ctx* ctx, const uint8_t* desc_q, int nq, int slots_q, cons
   fill_ff(bi, per_q); fill_ff(bd, per_q); fill_ff(sd, per_q); fill_ff(mq, per_q); fill_ff(mt, per_q); fill_ff(md, per_q); fill_ff(mp, 4 * per_q);
   fill_ff(nm, sizeof(int));
   MatchBufs B{dq.as<unsigned long long>(), dt.as<unsigned long long>(), dn.as<int>(), dn.as<int>() + 1, dqxy.as<float2>(), dtxy.as<float2>(),
-              pi.as<int>(), p1.as<int>(), p2.as<int>(), &st->ticket, bi.as<int>(), bd.as<int>(), sd.as<int>(), mq.as<int>(), mt.as<int>(), md.as<int>(),
+              pi.as<int>(), p1.as<int>(), p2.as<int>(), static_cast<unsigned*>(ctx->orb_match_ticket), bi.as<int>(), bd.as<int>(), sd.as<int>(), mq.as<int>(), mt.as<int>(), md.as<int>(),
               mp.as<float4>(), nm.as<int>()};
   launch_match_kernel(ctx->stream, slots_q, slots_t, B, ratio, keep_all);
   GTX_HIP(hipGetLastError());
@@ -1958,26 +1505,6 @@ void op_orb_match(gtx_ctx* ctx, const uint8_t* desc_q, int nq, int slots_q, cons
   download(m_t, mt, out_q);
   download(m_d, md, out_q);
   download(m_pts, mp, 4 * out_q);
-}
-
-void op_orb_ransac(gtx_ctx* ctx, const float* pts, int n, unsigned seed, int n_hyp, int frame_w, int frame_h, float thr, int affine, int* best,
-                   long long* cost, double H[9]) {
-  GTX_HIP(hipSetDevice(ctx->device));
-  OrbOpState* st = orb_op_state(ctx);
-  DevBuf dp, dn, dr;
-  upload(dp, pts, sizeof(float4) * (size_t)n, sizeof(float4));
-  const int counts[2] = {n, n};
-  upload(dn, counts, sizeof counts, sizeof counts);
-  fill_ff(dr, sizeof(StabResult));
-  launch_ransac_kernel(ctx->stream, dp.as<float4>(), dn.as<int>(), dn.as<int>() + 1, seed, n_hyp, frame_w, frame_h, affine, thr, st->ransac,
-                       dr.as<StabResult>());
-  GTX_HIP(hipGetLastError());
-  GTX_HIP(hipStreamSynchronize(ctx->stream));
-  StabResult R;
-  download(&R, dr, sizeof R);
-  *best = R.best;
-  *cost = R.cost;
-  std::memcpy(H, R.H, sizeof R.H);
 }
 
 }  // namespace gtx

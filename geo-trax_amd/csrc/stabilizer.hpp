@@ -1,4 +1,4 @@
-// GPU homography stabilizer (ORB-style keypoints + Hamming matching + RANSAC homography).
+// GPU homography stabilizer (ORB-style keypoints + Hamming matching; the robust homography is homography.hpp's).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -57,34 +57,11 @@ class Stabilizer {
 // The steered-BRIEF sampling table [256 bins][256 tests][ax, ay, bx, by] (host only, no device needed).
 void stabilizer_pattern_table(std::vector<int8_t>& out);
 
-// clahe.hip: cv2.createCLAHE(2.0, (8, 8)).apply on a u8 image in HBM (src == dst allowed); luts: kClaheLutBytes of scratch.
-constexpr int kClaheLutBytes = 8 * 8 * 256;
-void clahe_dev(const uint8_t* src, int h, int w, uint8_t* luts, uint8_t* dst, hipStream_t s);
-// cv2.createCLAHE(2.0, (8, 8)).apply(gray), host image in / out (what `clahe: true` runs on the working gray image).
-void clahe_image(gtx_ctx* ctx, const uint8_t* gray, int h, int w, uint8_t* out);
-
-// Robust homography (MSAC hypotheses on the GPU + IRLS refit on the host, f64) from n_match point pairs
-// (x, y) -> (z, w) in HBM; threshold in pixels of the destination. false: no model.
-bool ransac_homography(int device, hipStream_t s, const float4* d_pts, int n_match, unsigned seed, int n_hyp, int frame_w, int frame_h,
-                       float threshold, double H[9], int* n_inliers);
-
-// The same in two halves, for a caller whose pair count is in HBM and who must not wait between them: state_dev is two words that
-// ransac_arm sets once (the kernel leaves them armed), record_dev ransac_record_bytes() of HBM. n_cur_dev is copied into the record.
-// After the stream has run: copy the record and the pairs to the host, read the counts, and ransac_finish does the refit.
-size_t ransac_record_bytes();
-void ransac_arm(unsigned long long* state_dev, hipStream_t s);
-void ransac_submit(hipStream_t s, const float4* d_pts, const int* n_pairs_dev, const int* n_cur_dev, unsigned seed, int n_hyp, int frame_w, int frame_h,
-                   float threshold, unsigned long long* state_dev, void* record_dev);
-void ransac_record_counts(const void* record_host, int* n_pairs, int* n_cur);
-bool ransac_finish(const void* record_host, const float4* pts_host, int frame_w, int frame_h, float threshold, double H[9], int* n_inliers);
-
-// Operator hooks: one launch of the matcher / of the RANSAC kernel on host arrays, exactly as the stabilizer launches them (sizes are
-// validated by the caller, gtx_ops.cpp). Their ticket / state words live with the context and are never re-initialised by the host.
+// Operator hook: one launch of the matcher on host arrays, exactly as the stabilizer launches it (sizes are validated by the caller,
+// gtx_ops.cpp). Its ticket word lives with the context (gtx_ctx::orb_match_ticket) and is never re-initialised by the host.
 void op_orb_match(gtx_ctx* ctx, const uint8_t* desc_q, int nq, int slots_q, const uint8_t* desc_t, int nt, int slots_t, float ratio, int keep_all,
                   const float* xy_q, const float* xy_t, int* best_idx, int* best_d, int* second_d, int* m_q, int* m_t, int* m_d, float* m_pts,
                   int* n_match);
-void op_orb_ransac(gtx_ctx* ctx, const float* pts, int n, unsigned seed, int n_hyp, int frame_w, int frame_h, float thr, int affine, int* best,
-                   long long* cost, double H[9]);
 }  // namespace gtx
 
 struct gtx_stabilizer {

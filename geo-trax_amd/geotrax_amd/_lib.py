@@ -299,6 +299,7 @@ _SIGNATURES = {
     "gtx_warp_boxes": (C.c_int, [_P, _P, C.c_int, _P]),
     "gtx_perspective_points": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
     "gtx_op_estimate_affine_partial": (C.c_int, [_P, _P, C.c_int, C.c_uint, _P, _P, _P]),
+    "gtx_op_homography_refit": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gtx_op_georef_points": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gtx_op_georef_tracks": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int] + [_P] * 12),
     "gtx_georef_tracks_ms": (C.c_int, [_P]),

@@ -115,8 +115,8 @@ class FeatureGMC:
     descriptors of the half-resolution gray image, brute-force 2-NN matching against the previous frame's with Lowe's ratio 0.9,
     the two spatial filters of apply_features, then the RANSAC partial-affine fit. Built from what the path already has:
 
-    * orb: gtx_fgmc_* (csrc/gmc_feat.hip) -- the stabilizer's detector / descriptor / Hamming matcher kernels (csrc/stabilizer.hip:
-      FAST 20 on an 8-level pyramid, Harris ranking, 256-bit rotated BRIEF; 1000 keypoints per frame), the filters and the RANSAC
+    * orb: gtx_fgmc_* (csrc/gmc_feat.hip) -- the stabilizer's detector / descriptor / Hamming matcher kernels (csrc/stabilizer.hip, without its
+      homography solver, csrc/homography.hip: FAST 20 on an 8-level pyramid, Harris ranking, 256-bit rotated BRIEF; 1000 keypoints per frame), the filters and the RANSAC
       hypotheses as one chain on the object's stream per submitted frame. submit_gray_dev / submit_gray / submit_frame_dev only
       enqueue (frames may be submitted ahead, as with GMC); collect() waits for the oldest frame and refits on the host;
     * sift: csrc/sift.hip's SIFT (plain, not RootSIFT) + the L2 2-NN kernel (csrc/match_l2.hip), the filters in numpy and the fit

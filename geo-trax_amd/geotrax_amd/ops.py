@@ -791,6 +791,17 @@ def orb_ransac(pts, seed: int, n_hyp: int, frame_wh, thr: float, *, affine: bool
     return best.value, cost.value, H.reshape(3, 3)
 
 
+def homography_refit(pts, H0, frame_wh, thr: float, *, affine: bool = False):
+    """The host refit that ends every robust homography (csrc/homography_refit.cpp; no device): pts [n, 4] f32 = (x, y) -> (z, w), H0
+    [3, 3] f64 the RANSAC winner as sampled. -> (H [3, 3] f64 with h33 = 1, the pairs within thr of it), or (None, 0): no model."""
+    p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 4)
+    h0 = np.ascontiguousarray(H0, dtype=np.float64).reshape(9)
+    H, valid, inl = np.full(9, np.nan, np.float64), C.c_int(-1), C.c_int(-1)
+    check(_lib.load().gtx_op_homography_refit(ptr(p) if len(p) else None, len(p), int(frame_wh[0]), int(frame_wh[1]), float(thr), int(affine), ptr(h0),
+                                              ptr(H), C.byref(valid), C.byref(inl)))
+    return (H.reshape(3, 3), inl.value) if valid.value else (None, 0)
+
+
 def gmc_corners(gray, *, ctx=None):
     """The sparse-optical-flow GMC's corner step (response + nms + select kernels, one launch each) on a gray image [h, w] u8.
     -> (corners [n, 2] f32 (x, y), n <= 1000, strongest first, equal responses by larger pixel index first;

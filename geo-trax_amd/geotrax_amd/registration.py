@@ -4,7 +4,7 @@ Reference behaviour replaced: geotrax/utils/registration.py:21-95 (`estimate_hom
 georeference stage registers a video frame / master frame / orthophoto cut-out pair through a stabilo
 Stabilizer configured for RootSIFT + brute-force matching + ratio filter + USAC_MAGSAC, and retries
 with half the features when no model comes back. Same function name, keywords, return tuple and
-retry rule here; the arithmetic runs on the GPU (csrc/sift.hip, match_l2.hip, stabilizer.hip).
+retry rule here; the arithmetic runs on the GPU (csrc/sift.hip, match_l2.hip, homography.hip).
 """
 from __future__ import annotations
 

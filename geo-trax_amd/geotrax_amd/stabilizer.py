@@ -95,7 +95,7 @@ class Stabilizer:
         return b, len(b)
 
     # ---- detector_name sift / rsift (default.yaml:109): the registration stage's kernels (csrc/sift.hip, match_l2.hip, the RANSAC of
-    # stabilizer.hip behind gtx_register_images) on the working-resolution frames; one blocking call per frame, host frames only
+    # homography.hip behind gtx_register_images) on the working-resolution frames; one blocking call per frame, host frames only
     def _working(self, frame):
         f = np.ascontiguousarray(frame, dtype=np.uint8)
         r = float(self._kw["downsample_ratio"])

@@ -90,7 +90,9 @@ extern "C" {
  *     Detect of reg_max = 1 read off its last box convolution's four rows, the one-to-one head under gtx_det_config.end2end): a new
  *     entry point only, so the number stays.
  *     gtx_op_head_sparse_box and gtx_sparse_level (the sparse Detect box launch on host arrays) added: a new entry point and a
- *     struct of its own only, so the number stays. */
+ *     struct of its own only, so the number stays.
+ *     gtx_op_homography_refit (the host refit that ends every robust homography, on host arrays) added: a new entry point only, so
+ *     the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -1219,6 +1221,13 @@ int gtx_perspective_points(const double H[9], const double* x, const double* y, 
  * the 4-parameter similarity p -> q of n matched points ([n][2] float32 each), A row-major 2x3 f64; *valid = 0 when no model
  * exists (fewer than two distinct points). Host code (a few hundred matches); no device needed. */
 int gtx_op_estimate_affine_partial(const float* p_xy, const float* q_xy, int n, unsigned seed, double A[6], int* valid, int* n_inliers);
+
+/* The host half of every robust homography here (the ORB and SIFT stabilizers, gtx_register_images): the IRLS refit of a RANSAC
+ * winner H0 (row-major 3x3 f64 as gtx_op_orb_ransac returns it, any scale) on n point pairs (x, y) -> (z, w), [n][4] float32, of a
+ * frame_w x frame_h frame; thr in pixels; affine = 1 keeps h31 = h32 = 0. *valid = 1: H (h33 = 1) and *n_inliers, the pairs within
+ * thr of it. *valid = 0: no model (too few pairs near H0, or too few inliers), H untouched. Host code; no device needed. */
+int gtx_op_homography_refit(const float* pairs, int n, int frame_w, int frame_h, double thr, int affine, const double H0[9], double H[9],
+                            int* valid, int* n_inliers);
 
 /* The georeference stage's per-row transform chain in one HIP pass (replaces
  * geotrax/georeference.py:173-177 = apply_homography :599-605 -> ortho2geo :608-615 -> geo2local :618-628, where the

@@ -13,7 +13,7 @@ memory bit for bit. This file therefore restates the *published algorithms* (Rub
 scale pyramid, FAST-9/16 with 3x3 non-maximum suppression, FAST-score pre-selection then Harris ranking, intensity-centroid
 orientation, steered BRIEF on a Gaussian-smoothed patch; Lowe's ratio test; RANSAC with an
 MSAC score and a robust iteratively re-weighted Gauss-Newton refit) in the integer-exact form the HIP kernels implement
-(geo-trax_amd/csrc/stabilizer.hip), so that every stage can be compared bit for bit. The BRIEF
+(geo-trax_amd/csrc/stabilizer.hip, homography.hip, homography_refit.cpp), so that every stage can be compared bit for bit. The BRIEF
 sampling table is generated HERE (`brief_pattern`: 256 pairs from an isotropic Gaussian, sigma = patch/5,
 BRIEF "G II" of Calonder et al., seeded splitmix64, rotated to 256 orientation bins) and the tests compare
 the library's table (gtx_stabilizer_pattern) with it, not the other way round.
@@ -312,7 +312,7 @@ def _denorm(Hn, cx, cy, sc):
 def refine_homography(H0, p, q, cx, cy, sc, thr, affine=False):
     """Iteratively re-weighted Gauss-Newton on the transfer error (Tukey biweight, scale from the
     median residual, support = matches within 3 thresholds of H0), h33 = 1, normalised
-    coordinates. Mirrors refine_homography() in csrc/stabilizer.hip. affine: h31 = h32 = 0 stay, six
+    coordinates. Mirrors refine_homography() in csrc/homography_refit.cpp (tests/test_geometry.py compares the two). affine: h31 = h32 = 0 stay, six
     parameters move, three matches suffice (stabilo transformation_type: affine, default.yaml:121)."""
     npar, min_pts = (6, 3) if affine else (8, 4)
     T = np.array([[sc, 0, -sc * cx], [0, sc, -sc * cy], [0, 0, 1.0]])
@@ -365,7 +365,7 @@ def _errors(H, p, q):
 
 
 def _basis_ok(x, y):
-    """The kernel's test of a 4-point sample (csrc/stabilizer.hip basis_matrix): the first three points are not collinear, and the
+    """The kernel's test of a 4-point sample (csrc/homography.hip basis_matrix): the first three points are not collinear, and the
     fourth is on none of the lines through two of them -- |det| and the three barycentric-like weights above 1e-9 in normalised units."""
     det = x[0] * (y[1] - y[2]) - x[1] * (y[0] - y[2]) + x[2] * (y[0] - y[1])
     if not abs(det) > 1e-9:

@@ -427,6 +427,30 @@ def test_orb_hooks_refuse_bad_sizes_before_any_launch():
     assert lib.gtx_stabilizer_candidates(None, 0, 0, 0, C.byref(n), None, None, None, None, None) == -1 and b"st is NULL" in lib.gtx_last_error()
 
 
+def test_homography_refit_hook_refuses_bad_arguments():
+    """Host only: negative n, no pairs with n > 0, a frame without a size and missing outputs get an error code; n = 0 is a case (no model)."""
+    from geotrax_amd import _lib
+
+    lib = _lib.load()
+    f = np.zeros((8, 4), np.float32)
+    H0, H = np.eye(3).ravel(), np.full(9, 7.0)
+    valid, inl = C.c_int(-1), C.c_int(-1)
+    p = _lib.ptr
+
+    def refit(n=8, w=640, h=480, pts=f, h0=H0, out=H):
+        return lib.gtx_op_homography_refit(p(pts), n, w, h, 2.0, 0, p(h0), p(out), C.byref(valid), C.byref(inl))
+
+    assert refit(n=-1) == -1 and b"homography_refit: n" in lib.gtx_last_error()
+    assert refit(pts=None) == -1 and b"pairs is NULL" in lib.gtx_last_error()
+    assert refit(w=0) == -1 and b"frame" in lib.gtx_last_error()
+    assert refit(h=-480) == -1 and b"frame" in lib.gtx_last_error()
+    assert refit(h0=None) == -1 and b"H0 is NULL" in lib.gtx_last_error()
+    assert refit(out=None) == -1 and b"H is NULL" in lib.gtx_last_error()
+    assert valid.value == -1 and inl.value == -1                                                       # nothing was written on the way out
+    assert refit(n=0, pts=None) == 0 and valid.value == 0 and inl.value == 0
+    np.testing.assert_array_equal(H, np.full(9, 7.0))
+
+
 def test_gmc_hooks_refuse_bad_sizes_before_any_launch():
     """Host only: the sparse-optical-flow GMC's operator hooks and its counts read-back answer bad sizes, points outside the image
     and missing arrays with an error code, with no context or object given."""

@@ -105,6 +105,73 @@ def test_estimate_affine_partial_equals_the_oracle_and_recovers_a_similarity():
     assert got is None and inl == 0
 
 
+_REFIT_FRAME, _REFIT_THR = (1920, 1080), 2.0
+_REFIT_CASES = [(False, 4), (False, 5), (False, 60), (False, 800), (True, 3), (True, 60)]      # (affine, n)
+_REFIT_BAR = 2.73e-5   # px: ten times the worst distance measured, see the test's docstring
+
+
+def _refit_pairs(affine, n):
+    """n pairs of a 1920x1080 frame under a known map (a mild perspective term unless affine), 0.3 px Gaussian noise, 30 % outliers."""
+    w, h = _REFIT_FRAME
+    rng = np.random.default_rng(100 * n + affine)
+    a, s = 0.01, 1.002
+    Ht = np.array([[s * np.cos(a), -s * np.sin(a), 12.5], [s * np.sin(a), s * np.cos(a), -7.25], [0.0, 0.0, 1.0] if affine else [2e-6, -1e-6, 1.0]])
+    p = rng.uniform((0, 0), (w, h), (n, 2)).astype(np.float32)
+    g = np.concatenate([p.astype(np.float64), np.ones((n, 1))], 1) @ Ht.T
+    q = (g[:, :2] / g[:, 2:] + 0.3 * rng.standard_normal((n, 2))).astype(np.float32)
+    bad = rng.random(n) < 0.3
+    q[bad] += rng.uniform(-200, 200, (int(bad.sum()), 2)).astype(np.float32)
+    return p, q, Ht
+
+
+def _refit_both(p, q, H0, affine):
+    from geotrax_amd.ops import homography_refit
+    from oracle import stabilo_ref
+
+    w, h = _REFIT_FRAME
+    thr = float(np.float32(_REFIT_THR))
+    want = stabilo_ref.refine_homography(H0 / H0[2, 2], p.astype(np.float64), q.astype(np.float64), w / 2.0, h / 2.0, 2.0 / w, thr, affine)
+    return homography_refit(np.concatenate([p, q], 1), H0, _REFIT_FRAME, thr, affine=affine), want
+
+
+def test_homography_refit_equals_the_oracle():
+    """gtx_op_homography_refit (csrc/homography_refit.cpp, the host tail of every robust homography) == oracle.stabilo_ref.refine_homography
+    on the same pairs and the same RANSAC winner (the oracle's, 64 hypotheses): both give a model or both none, the same inlier count,
+    and H within the 9 x 16 grid reprojection distance of tests/test_stabilizer_gpu.py. The counts can only be compared exactly when no
+    residual sits on the threshold: the oracle's final residuals are first shown to keep 1e-6 px away from it for these seeds.
+    The two sides differ in the linear solve (Cholesky here, LU there) and in summation order only. Measured on the CPU this was
+    written on: 2.73e-6 px for the five projective pairs (four inliers: the normal matrix is close to singular), at most 9.1e-13 px for
+    the other five cases. The bar is ten times the worst, for another libm or BLAS build: 2.73e-5 px, far inside the 1e-3 px that
+    test_stabilizer_gpu.py allows end to end for this very pair."""
+    from oracle import stabilo_ref
+    from test_stabilizer_gpu import _grid_err
+
+    w, h = _REFIT_FRAME
+    worst = 0.0
+    for affine, n in _REFIT_CASES:
+        p, q, _ = _refit_pairs(affine, n)
+        _, _, H0 = stabilo_ref.ransac_hypotheses(p, q, _REFIT_FRAME, _REFIT_THR, 64, 0, affine)
+        assert H0 is not None, (affine, n)
+        (got, got_inl), (want, want_inl) = _refit_both(p, q, H0, affine)
+        assert want is not None, (affine, n)
+        res = np.sqrt(stabilo_ref._errors(want, p.astype(np.float64), q.astype(np.float64)))
+        margin = np.abs(res - float(np.float32(_REFIT_THR))).min()
+        assert margin > 1e-6, (affine, n, margin)                     # the oracle alone: no pair on the threshold
+        assert got is not None, (affine, n)
+        err = _grid_err(got, want, (h, w))
+        worst = max(worst, err)
+        print(f"homography_refit affine={affine} n={n}: inliers {got_inl} / {want_inl}, nearest residual {margin:.3g} px from the threshold, grid distance {err:.3g} px")
+        assert got_inl == want_inl, (affine, n)
+        assert err <= _REFIT_BAR, (affine, n, err)
+    print(f"homography_refit: worst grid distance {worst:.3g} px, bar {_REFIT_BAR:.3g} px")
+    # under-supported: a winner 500 px away from every pair leaves fewer than four pairs within three thresholds
+    p, q, Ht = _refit_pairs(False, 60)
+    far = Ht.copy()
+    far[0, 2] += 500.0
+    (got, got_inl), (want, want_inl) = _refit_both(p, q, far, False)
+    assert got is None and want is None and got_inl == 0 and want_inl == 0
+
+
 def _adjugate_inverse_longdouble(H):
     m = np.asarray(H, np.longdouble).ravel()
     a, b, c, d, e, f, g, h, i = m

@@ -1,4 +1,4 @@
-"""The ORB stabilizer's kernels at the edges its one synthetic scene never reaches (csrc/stabilizer.hip).
+"""The ORB stabilizer's kernels at the edges its one synthetic scene never reaches (csrc/stabilizer.hip; the RANSAC kernel: csrc/homography.hip).
 
 Extract: the pyramid levels, the candidate sets after FAST + 3x3 maximum test + mask, the per-level counts and the keypoints of a
 pass are read back (Stabilizer.keep_pass / level / candidates) and compared with oracle.stabilo_ref.extract bit for bit, on images
