@@ -11,6 +11,7 @@
 
 #include "../../include/gtx.h"
 #include "api_guard.hpp"
+#include "area_attn.hpp"
 #include "clahe.hpp"
 #include "common.hpp"
 #include "conv_igemm.hpp"
@@ -376,6 +377,31 @@ int gtx_op_psa_attention(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int
     zeros(ds, 4);
     const gtx::RtMap in{dx.p, h, w, in_cstride, in_coff, heads * 128}, o{dy.p, h, w, out_cstride, out_coff, heads * 64};
     auto once = [&] { gtx::launch_psa_attention(dtype, in, o, n, heads, dw.as<float>(), db.as<float>(), ds.as<int>(), ctx->stream, form); };
+    once();
+    if (iters > 0 && ms_per_launch) *ms_per_launch = time_launches(ctx->stream, iters, once);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download_fmt(out, dtype, dy, yb);
+    if (saturated) download(saturated, ds, 4);
+  });
+}
+
+int gtx_op_area_attention(gtx_ctx* ctx, int dtype, int n, int h, int w, int heads, int area, int planar, const void* qkv, int in_cstride, int in_coff,
+                          void* out, int out_cstride, int out_coff, int iters, float* ms_per_launch, int* saturated) {
+  return guarded([&] {
+    need(ctx, "ctx"); need(qkv, "qkv"); need(out, "out");
+    if (n < 1 || h < 1 || w < 1 || heads < 1 || area < 1 || iters < 0) gtx::fail(GTX_ERR_INVALID, "area_attention: bad sizes");
+    if (in_coff < 0 || in_coff + heads * 96 > in_cstride || out_coff < 0 || out_coff + heads * 32 > out_cstride)
+      gtx::fail(GTX_ERR_INVALID, "area_attention: the channel slices do not fit their strides");
+    if (!gtx::area_attention_fits(h, w, area))
+      gtx::fail(GTX_ERR_UNSUPPORTED, "area_attention: a %d x %d map (%d positions) does not cut into %d equal areas", w, h, h * w, area);
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t es = gtx::dtype_size(dtype);
+    const size_t xb = (size_t)n * h * w * in_cstride * es, yb = (size_t)n * h * w * out_cstride * es;
+    gtx::DevBuf dx, dy, ds;
+    upload_fmt(dx, dtype, qkv, xb); upload_fmt(dy, dtype, out, yb);
+    zeros(ds, 4);
+    const gtx::RtMap in{dx.p, h, w, in_cstride, in_coff, heads * 96}, o{dy.p, h, w, out_cstride, out_coff, heads * 32};
+    auto once = [&] { gtx::launch_area_attention(dtype, in, o, n, heads, area, planar != 0, ds.as<int>(), ctx->stream); };
     once();
     if (iters > 0 && ms_per_launch) *ms_per_launch = time_launches(ctx->stream, iters, once);
     GTX_HIP(hipStreamSynchronize(ctx->stream));

@@ -222,7 +222,7 @@ bool run_writers(unsigned seed) {
   return anchor[0] == 0 && anchor[1] <= 1;
 }
 
-// The YOLO trunks' layer tables are walkable (yolov10.yaml's and yolo26.yaml's among them), a broken one is caught at its row, and the depthwise
+// The YOLO trunks' layer tables are walkable (yolov10.yaml's, yolo26.yaml's and yolo12.yaml's among them), a broken one is caught at its row, and the depthwise
 // weight transposition touches exactly its taps x channels values (odd sizes: 7x7 on 24 channels, 3x3 on 8, 5x5 on 40); the depthwise and
 // attention launchers' kernel names follow their dispatch predicates
 static bool run_trunk_tables() {
@@ -231,7 +231,7 @@ static bool run_trunk_tables() {
   const struct { const TrunkRow* rows; int n; } all[] = {{kYolov8, (int)(sizeof(kYolov8) / sizeof(TrunkRow))}, {kYolov8P2, (int)(sizeof(kYolov8P2) / sizeof(TrunkRow))},
                                                           {kYolo11, (int)(sizeof(kYolo11) / sizeof(TrunkRow))}, {kYolo10, (int)(sizeof(kYolo10) / sizeof(TrunkRow))},
                                                           {kYolo11Cls, (int)(sizeof(kYolo11Cls) / sizeof(TrunkRow))}, {kYolov8, kClsBackboneRows},
-                                                          {kYolo26, (int)(sizeof(kYolo26) / sizeof(TrunkRow))}};
+                                                          {kYolo26, (int)(sizeof(kYolo26) / sizeof(TrunkRow))}, {kYolo12, (int)(sizeof(kYolo12) / sizeof(TrunkRow))}};
   for (const auto& t : all)
     if (trunk_table_error(t.rows, t.n) >= 0) return false;
   int scdown = 0, psa = 0;
@@ -240,6 +240,21 @@ static bool run_trunk_tables() {
   // yolo26.yaml: kYolo11's modules row for row; its SPPF row alone carries the linear-cv1 + residual flag
   for (int i = 0; i < 24; ++i)
     if (kYolo26[i].mod != kYolo11[i].mod || (kYolo26[i].mod == TrunkRow::SPPF) != (i == 9) || (i == 9 && (!kYolo26[i].shortcut || kYolo11[i].shortcut))) return false;
+  // yolo12.yaml: 22 rows, five A2C2f blocks of which the two in the backbone carry an area (4 at stride 16, 1 at stride 32), Detect last;
+  // a map cuts into its areas exactly when its positions are a multiple of them
+  int a2 = 0;
+  for (const TrunkRow& r : kYolo12) a2 += r.mod == TrunkRow::A2C2F;
+  if (sizeof(kYolo12) / sizeof(TrunkRow) != 22 || a2 != 5 || kYolo12[6].area != 4 || kYolo12[8].area != 1 || kYolo12[11].area != 0 || kYolo12[21].mod != TrunkRow::DETECT) return false;
+  for (const auto& t : all)
+    for (int i = 0; i < t.n; ++i)
+      if (t.rows != kYolo12 && t.rows[i].area != 0) return false;
+  for (int h = 1; h <= 12; ++h)
+    for (int w = 1; w <= 12; ++w)
+      for (int area = 0; area <= 5; ++area)
+        if (area_attention_fits(h, w, area) != (area > 0 && h * w % area == 0)) return false;
+  std::vector<TrunkRow> bad12(kYolo12, kYolo12 + 22);
+  bad12[10].from[1] = 11;                             // yolo12.yaml's first Concat reading a later layer
+  if (trunk_table_error(bad12.data(), 22) != 10) return false;
   std::vector<TrunkRow> bad(kYolo10, kYolo10 + 24);
   bad[12].from[1] = 13;                               // a Concat that reads a later layer
   if (trunk_table_error(bad.data(), 24) != 12) return false;

@@ -6,80 +6,15 @@
 //   rt_mha                        vector fp32 (2 d FMAs per query-key pair from LDS broadcasts)
 //   rt_topk / rt_gather / rt_refer / rt_deform / rt_post   latency (a few hundred queries per image)
 #include "rtdetr_kernels.hpp"
+#include "map_format_device.hpp"
 
 #include <cfloat>
 
 namespace gtx {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-// ---- 8-channel groups in the three activation formats; e = element index of the group's first channel (a multiple of 8)
-template <int FMT> __device__ __forceinline__ void load8(const void* base, size_t e, float v[8]) {
-  const char* b = static_cast<const char*>(base);
-  if constexpr (FMT == DT_F16) {
-    const half8 h = *reinterpret_cast<const half8*>(b + e * 2);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (float)h[i];
-  } else if constexpr (FMT == DT_F32) {
-    const float4 a = *reinterpret_cast<const float4*>(b + e * 4), c = *reinterpret_cast<const float4*>(b + e * 4 + 16);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = c.x; v[5] = c.y; v[6] = c.z; v[7] = c.w;
-  } else {                                                       // pair format: 8 hi halves then 8 lo halves (split_format.hpp)
-    const half8 hi = *reinterpret_cast<const half8*>(b + e * 4), lo = *reinterpret_cast<const half8*>(b + e * 4 + 16);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (float)hi[i] + (float)lo[i];
-  }
-}
-template <int FMT> __device__ __forceinline__ void store8(void* base, size_t e, const float v[8], bool& sat) {
-  char* b = static_cast<char*>(base);
-  if constexpr (FMT == DT_F16) {
-    half8 h;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) h[i] = (_Float16)v[i];
-    *reinterpret_cast<half8*>(b + e * 2) = h;
-  } else if constexpr (FMT == DT_F32) {
-    *reinterpret_cast<float4*>(b + e * 4) = make_float4(v[0], v[1], v[2], v[3]);
-    *reinterpret_cast<float4*>(b + e * 4 + 16) = make_float4(v[4], v[5], v[6], v[7]);
-  } else {
-    half8 hi, lo;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const float x = __builtin_amdgcn_fmed3f(v[i], -65504.f, 65504.f);   // a NaN comes out as -65504, like the convolutions' split
-      sat |= x != v[i];
-      hi[i] = (_Float16)x;
-      lo[i] = (_Float16)(x - (float)hi[i]);                                // x - hi is exact in fp32
-    }
-    *reinterpret_cast<half8*>(b + e * 4) = hi;
-    *reinterpret_cast<half8*>(b + e * 4 + 16) = lo;
-  }
-}
-template <int FMT> __device__ __forceinline__ float load1(const void* base, size_t e) {
-  const char* b = static_cast<const char*>(base);
-  if constexpr (FMT == DT_F16) return (float)*reinterpret_cast<const _Float16*>(b + e * 2);
-  else if constexpr (FMT == DT_F32) return *reinterpret_cast<const float*>(b + e * 4);
-  else {
-    const char* g = b + (e & ~(size_t)7) * 4 + 2 * (e & 7);
-    return (float)*reinterpret_cast<const _Float16*>(g) + (float)*reinterpret_cast<const _Float16*>(g + 16);
-  }
-}
 constexpr __host__ __device__ int fmt_size(int fmt) { return fmt == DT_F16 ? 2 : 4; }
 
-#define RT_FMT(fmt, ...)                                                           \
-  do {                                                                             \
-    switch (fmt) {                                                                 \
-      case DT_F16: { constexpr int F = DT_F16; __VA_ARGS__; } break;               \
-      case DT_F32: { constexpr int F = DT_F32; __VA_ARGS__; } break;               \
-      case DT_F32S: { constexpr int F = DT_F32S; __VA_ARGS__; } break;             \
-      default: fail(-3, "rtdetr: unknown activation format %d", (int)(fmt));       \
-    }                                                                              \
-    GTX_HIP(hipGetLastError());                                                    \
-  } while (0)
-
-__device__ __forceinline__ void flag_sat(int* sat, bool s) {
-  if (sat && s) *sat = 1;
-}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -650,47 +585,6 @@ __global__ __launch_bounds__(256) void rt_mha32_kernel(const float* __restrict__
 }
 
 // ============================================================================ position-sensitive attention on a qkv map (YOLO11's C2PSA)
-// Four consecutive channels (e a multiple of 4) in the three activation formats: half a group of the pair format
-template <int FMT> __device__ __forceinline__ void load4(const void* base, size_t e, float v[4]) {
-  const char* b = static_cast<const char*>(base);
-  if constexpr (FMT == DT_F16) {
-    const half4 h = *reinterpret_cast<const half4*>(b + e * 2);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (float)h[i];
-  } else if constexpr (FMT == DT_F32) {
-    const float4 a = *reinterpret_cast<const float4*>(b + e * 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  } else {
-    const char* g = b + (e & ~(size_t)7) * 4 + 2 * (e & 7);
-    const half4 hi = *reinterpret_cast<const half4*>(g), lo = *reinterpret_cast<const half4*>(g + 16);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (float)hi[i] + (float)lo[i];
-  }
-}
-template <int FMT> __device__ __forceinline__ void store4(void* base, size_t e, const float v[4], bool& sat) {
-  char* b = static_cast<char*>(base);
-  if constexpr (FMT == DT_F16) {
-    half4 h;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) h[i] = (_Float16)v[i];
-    *reinterpret_cast<half4*>(b + e * 2) = h;
-  } else if constexpr (FMT == DT_F32) {
-    *reinterpret_cast<float4*>(b + e * 4) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    half4 hi, lo;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float x = __builtin_amdgcn_fmed3f(v[i], -65504.f, 65504.f);
-      sat |= x != v[i];
-      hi[i] = (_Float16)x;
-      lo[i] = (_Float16)(x - (float)hi[i]);
-    }
-    char* g = b + (e & ~(size_t)7) * 4 + 2 * (e & 7);
-    *reinterpret_cast<half4*>(g) = hi;
-    *reinterpret_cast<half4*>(g + 16) = lo;
-  }
-}
-
 // rt_mha32_kernel's scheme (a wave owns 16 queries, walks the keys 16 at a time on v_mfma_f32_16x16x4_f32, the probabilities stay
 // in the lanes that computed them, K / V tiles of 64 keys shared through LDS with the next stage prefetched into registers) for
 // ultralytics' Attention block: the positions of a map are the tokens, a head's 128 channels of the qkv map are [q 32 | k 32 | v 64],

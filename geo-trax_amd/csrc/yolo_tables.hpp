@@ -8,13 +8,15 @@ namespace gtx {
 
 // One row of a trunk's layer table: a layer of the model yaml, as the yaml writes it
 struct TrunkRow {
-  enum Module { CONV, BLOCK, SPPF, C2PSA, UPSAMPLE, CONCAT, DETECT, SCDOWN, PSA, ELAN, ADOWN, SPPELAN };
+  enum Module { CONV, BLOCK, SPPF, C2PSA, UPSAMPLE, CONCAT, DETECT, SCDOWN, PSA, ELAN, ADOWN, SPPELAN, A2C2F };
   int i;            // the layer index: its tensors are "model.<i>.*"
   Module mod;       // CONV: Conv 3x3 stride 2 (row 0: the stem); BLOCK: C2f / C3k2 / C2fCIB (which one, the tensors tell);
                     // SCDOWN: 1x1 Conv + depthwise 3x3 stride 2 without activation; PSA: C2PSA's one block directly under the layer (yolov10.yaml);
-                    // ELAN: ELAN1 / RepNCSPELAN4, ADOWN: AConv / ADown (which one, the tensors tell), SPPELAN: SPPF's pools closed by cv5 (yolov9.yaml)
+                    // ELAN: ELAN1 / RepNCSPELAN4, ADOWN: AConv / ADown (which one, the tensors tell), SPPELAN: SPPF's pools closed by cv5 (yolov9.yaml);
+                    // A2C2F: yolo12.yaml's block, members of two ABlocks (area attention) or one C3k each (which, the tensors tell)
   int from[4];      // the yaml's `from`: -1 = the row above (row 0: the image), else a layer index; 0 ends the list
   bool shortcut;    // BLOCK: the bottlenecks add their input; SPPF: yolo26.yaml's form (cv1 without activation, the input added to cv2's output)
+  int area = 0;     // A2C2F with ABlocks: the yaml's `area` (bands the attention is cut into; 1 = the whole map). No tensor tells it.
 };
 struct TrunkGraph {
   const TrunkRow* rows;
@@ -67,6 +69,9 @@ inline const char* rt_dwconv_kernel_name(int k, int stride, int c) {
 inline constexpr int kPsaSmallT = 64;
 inline bool psa_attention_small(int h, int w) { return h * w <= kPsaSmallT; }
 inline const char* psa_attention_kernel_name(int h, int w) { return psa_attention_small(h, w) ? "psa_attn_small_kernel" : "psa_attn_kernel"; }
+// launch_area_attention (area_attn.hpp): keys per LDS stage of area_attn_kernel; a map runs when its positions cut into `area` equal runs
+inline constexpr int kAreaAttnKeyTile = 64;
+inline bool area_attention_fits(int h, int w, int area) { return area >= 1 && h >= 1 && w >= 1 && (h * w) % area == 0; }
 
 namespace tables {
 using R = TrunkRow;
@@ -129,6 +134,17 @@ inline constexpr R kYolo9[] = {
     {12, R::ELAN, {-1}, true},      {13, R::UPSAMPLE, {-1}, false},   {14, R::CONCAT, {-1, 4}, false}, {15, R::ELAN, {-1}, true},
     {16, R::ADOWN, {-1}, false},    {17, R::CONCAT, {-1, 12}, false}, {18, R::ELAN, {-1}, true},       {19, R::ADOWN, {-1}, false},
     {20, R::CONCAT, {-1, 9}, false}, {21, R::ELAN, {-1}, true},       {22, R::DETECT, {15, 18, 21}, false}};
+// 12/yolo12.yaml: 22 layers, no SPPF and no C2PSA; A2C2f with area attention at strides 16 (area 4) and 32 (area 1) of the backbone,
+// A2C2f with C3k members in the neck, a C3k2 as the neck's last block, YOLO11's Detect = model.21. The C3k members of A2C2f take the
+// module's default shortcut (on); tests/yolo12_ref.py lists the doubts.
+inline constexpr bool kA2C2fC3kShortcut = true;
+inline constexpr R kYolo12[] = {
+    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},
+    {4, R::BLOCK, {-1}, true},      {5, R::CONV, {-1}, false},        {6, R::A2C2F, {-1}, false, 4},   {7, R::CONV, {-1}, false},
+    {8, R::A2C2F, {-1}, false, 1},  {9, R::UPSAMPLE, {-1}, false},    {10, R::CONCAT, {-1, 6}, false}, {11, R::A2C2F, {-1}, kA2C2fC3kShortcut},
+    {12, R::UPSAMPLE, {-1}, false}, {13, R::CONCAT, {-1, 4}, false},  {14, R::A2C2F, {-1}, kA2C2fC3kShortcut}, {15, R::CONV, {-1}, false},
+    {16, R::CONCAT, {-1, 11}, false}, {17, R::A2C2F, {-1}, kA2C2fC3kShortcut}, {18, R::CONV, {-1}, false}, {19, R::CONCAT, {-1, 8}, false},
+    {20, R::BLOCK, {-1}, kNeckShortcut}, {21, R::DETECT, {14, 17, 20}, false}};
 // yolo11-cls.yaml: model.0-8 are yolo11.yaml's, C2PSA follows them directly (no SPPF) and is the embedded layer; Classify = model.10
 inline constexpr R kYolo11Cls[] = {
     {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},

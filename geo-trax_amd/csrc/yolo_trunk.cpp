@@ -7,7 +7,9 @@
 // v9/yolov9{t,s,m,c}.yaml kYolo9 (ELAN1 / RepNCSPELAN4, AConv / ADown behind pool_down.hip's launch, SPPELAN = model.9, Detect = model.22). The two classification graphs of the ReID embedder are
 // prefixes of these tables: yolov8-cls.yaml = kYolov8's rows 0-8, 11/yolo11-cls.yaml = kYolo11's rows 0-8 + C2PSA as model.9 (kYolo11Cls).
 // 26/yolo26.yaml is kYolo26: kYolo11's rows with SPPF's linear cv1 + residual at model.9 and the C3k2 with attention at model.22.
+// 12/yolo12.yaml is kYolo12: A2C2f blocks (area attention in the backbone, C3k members in the neck), no SPPF, Detect = model.21.
 #include "yolo_trunk.hpp"
+#include "area_attn.hpp"
 #include "pool_down.hpp"
 #include "rtdetr_kernels.hpp"
 #include "split_format.hpp"
@@ -30,6 +32,8 @@ TrunkGraph YoloTrunk::choose_cls_graph() const {
 
 // Which yaml the tensors were built from, told apart by their names like the reference's model yaml does
 TrunkGraph YoloTrunk::choose_graph() const {
+  // yolo12.yaml: an A2C2f's ABlocks (a Sequential of two inside m.{k}) at model.6 and YOLO11's Detect at model.21 -- no other yaml has either
+  if (net_.has("model.6.m.0.0.attn.qkv.conv.weight") && net_.has("model.21.cv3.0.0.0.conv.weight")) return graph_of(kYolo12, true);
   // yolov10.yaml: PSA's attention directly under model.10, SCDown's depthwise model.5.cv2 and a one-to-one head at model.23
   if (net_.has("model.10.attn.qkv.conv.weight") && net_.has("model.5.cv2.conv.weight") && net_.has("model.23.one2one_cv2.0.0.conv.weight"))
     return graph_of(kYolo10, true);
@@ -291,6 +295,96 @@ View YoloTrunk::c2psa(const std::string& pfx, const View& x, const View* out_sli
   return out;
 }
 
+// ABlock(c, heads = c / 32, mlp_ratio, area) on x -> dst: x1 = x + proj(attention(qkv(x)) + pe(v)), dst = x1 + mlp.1(mlp.0(x1)). AAttn's qkv
+// convolution writes per head [q 32 | k 32 | v 32]; its rows are emitted in the order [q of every head | k of every head | v of every
+// head] instead (the same sums, other channel positions), so that v is a channel slice of the qkv map: the attention launch reads the
+// planar layout, and `pe` -- a depthwise 7x7 without activation -- is the existing depthwise launch on that slice with the attention's
+// output as its residual. mlp.0's width int(c * mlp_ratio) need not be a multiple of 16 (307 at scale l): conv_act pads it with zeros.
+void YoloTrunk::ablock(const std::string& m, const View& x, const View& dst, int area) {
+  const int c = x.c, heads = c / 32;
+  const std::string q = m + ".attn.qkv.conv";
+  const HostTensor &wq = net_.tensor(q + ".weight"), &wp = net_.tensor(m + ".attn.pe.conv.weight");
+  GTX_CHECK(c % 32 == 0 && heads > 0 && wq.shape.size() == 4 && (int)wq.shape[0] == 3 * c && (int)wq.shape[1] == c && wq.shape[2] == 1 && wq.shape[3] == 1 &&
+                wp.shape.size() == 4 && (int)wp.shape[0] == c && wp.shape[1] == 1 && wp.shape[2] == 7,
+            "%s: area attention of %d heads of width 32 with a 7x7 pe expected", m.c_str(), heads);
+  GTX_CHECK(area_attention_fits(x.h, x.w, area), "%s: a %d x %d map (%d positions) does not cut into %d equal areas", m.c_str(), x.w, x.h, x.h * x.w, area);
+  std::vector<float> wpl((size_t)3 * c * c), bpl(3 * c, 0.f);
+  const float* bq = net_.bias_of(q, 3 * c);
+  for (int part = 0; part < 3; ++part)
+    for (int h = 0; h < heads; ++h)
+      for (int d = 0; d < 32; ++d) {
+        const int src = h * 96 + part * 32 + d, dstrow = part * c + h * 32 + d;
+        std::copy(wq.data.begin() + (size_t)src * c, wq.data.begin() + (size_t)(src + 1) * c, wpl.begin() + (size_t)dstrow * c);
+        if (bq) bpl[dstrow] = bq[src];
+      }
+  NetRuntime::ConvArgs a;
+  a.act = 0;
+  const View qkv = net_.emit_conv(ops_, q, wpl.data(), 3 * c, c, 1, bpl.data(), x, a);
+  View att = net_.new_view(x.h, x.w, c);
+  {
+    Op op;
+    op.kind = Op::AREAATTN;
+    op.name = m + ".attn";
+    op.family = "area_attn_kernel";
+    op.in = qkv; op.out = att;
+    op.heads = heads; op.area = area;
+    op.sat = net_.sat_flag();
+    ops_.push_back(op);
+    net_.set_layer_view(m + ".attn.out", att);       // softmax(q^T k) v, bands back in map order
+  }
+  const View v = qkv.slice(2 * c, c);
+  const View sum = dwconv(m + ".attn.pe.conv", v, 0, 1, nullptr, &att);   // attention + pe(v): what proj reads
+  View x1 = net_.new_view(x.h, x.w, c);
+  conv_act(m + ".attn.proj.conv", sum, 0, &x1, &x);
+  const View f0 = conv_act(m + ".mlp.0.conv", x1, 1, nullptr, nullptr);
+  conv_act(m + ".mlp.1.conv", f0, 0, &dst, &x1);
+}
+
+// A2C2f(c1, c2, n, a2, area, residual, mlp_ratio, e = 0.5): cv1 -> y0 (c_ = c2 / 2 channels); member k maps y_k to y_{k+1} -- with a2 two
+// ABlocks in sequence, without it a C3k(c_, c_, 2) --; cv2 on the concatenation of all of them. The concat is channel offsets into one
+// buffer, as in C2f. With a `gamma` tensor (scales l / x: residual = True) the output is x + gamma[c] * cv2(...), one scale-add launch.
+View YoloTrunk::a2c2f(const std::string& pfx, const View& x, int area, bool c3k_shortcut, const View* out_slice, const View* up_src) {
+  const int c = (int)net_.tensor(pfx + ".cv1.conv.weight").shape[0];
+  const bool a2 = net_.has(pfx + ".m.0.0.attn.qkv.conv.weight");
+  int n = 0;
+  while (net_.has(pfx + ".m." + std::to_string(n) + (a2 ? ".0.attn.qkv.conv.weight" : ".cv1.conv.weight"))) ++n;
+  GTX_CHECK(n > 0 && c % 16 == 0 && (!a2 || (c % 32 == 0 && area >= 1)), "%s: %d members on %d hidden channels, area %d", pfx.c_str(), n, c, area);
+  View cat = net_.new_view(x.h, x.w, (1 + n) * c);
+  View first = cat.slice(0, c);
+  conv(pfx + ".cv1.conv", x, 1, &first, nullptr, up_src);
+  for (int k = 0; k < n; ++k) {
+    const std::string m = pfx + ".m." + std::to_string(k);
+    const View src = cat.slice(k * c, c), dst = cat.slice((k + 1) * c, c);
+    if (a2) {
+      const View mid = net_.new_view(x.h, x.w, c);
+      ablock(m + ".0", src, mid, area);
+      ablock(m + ".1", mid, dst, area);
+      net_.set_layer_view(m, dst);
+    } else {
+      c3k(m, src, dst, c3k_shortcut);
+    }
+  }
+  if (!(a2 && net_.has(pfx + ".gamma"))) {
+    const View out = conv(pfx + ".cv2.conv", cat, 1, out_slice, nullptr);
+    net_.set_layer_view(pfx, out);
+    return out;
+  }
+  const HostTensor& gm = net_.tensor(pfx + ".gamma");
+  const View y = conv(pfx + ".cv2.conv", cat, 1, nullptr, nullptr);
+  GTX_CHECK((int)gm.data.size() == y.c && x.c == y.c && y.c % 8 == 0, "%s: gamma of %d values on %d -> %d channels", pfx.c_str(), (int)gm.data.size(), x.c, y.c);
+  Op op;
+  op.kind = Op::SCALEADD;
+  op.name = pfx + ".gamma";
+  op.family = "scale_add_kernel";
+  op.in = y; op.dw_res = x;
+  op.out = out_slice ? *out_slice : net_.new_view(x.h, x.w, y.c);
+  op.dw_w = net_.upload(gm.data);
+  op.sat = net_.sat_flag();
+  ops_.push_back(op);
+  net_.set_layer_view(pfx, op.out);
+  return op.out;
+}
+
 View YoloTrunk::dwconv(const std::string& name, const View& x, int act, int stride, const View* out_slice, const View* residual) {
   const HostTensor& w = net_.tensor(name + ".weight");
   const int c = x.c;
@@ -398,7 +492,7 @@ YoloTrunk::Levels YoloTrunk::build(const View& img, const TrunkGraph& g, bool fr
     const TrunkRow& r = g.rows[i];
     switch (r.mod) {
       case TrunkRow::CONV: width[i] = cout_of(name(i) + ".conv"); break;
-      case TrunkRow::BLOCK: case TrunkRow::SPPF: case TrunkRow::C2PSA: case TrunkRow::SCDOWN: case TrunkRow::PSA: width[i] = cout_of(name(i) + ".cv2.conv"); break;
+      case TrunkRow::BLOCK: case TrunkRow::SPPF: case TrunkRow::C2PSA: case TrunkRow::SCDOWN: case TrunkRow::PSA: case TrunkRow::A2C2F: width[i] = cout_of(name(i) + ".cv2.conv"); break;
       case TrunkRow::ELAN: width[i] = cout_of(name(i) + ".cv4.conv"); break;
       case TrunkRow::ADOWN: width[i] = cout_of(name(i) + ".cv1.conv") + (net_.has(name(i) + ".cv2.conv.weight") ? cout_of(name(i) + ".cv2.conv") : 0); break;
       case TrunkRow::SPPELAN: width[i] = cout_of(name(i) + ".cv5.conv"); break;
@@ -441,7 +535,7 @@ YoloTrunk::Levels YoloTrunk::build(const View& img, const TrunkGraph& g, bool fr
     const int f = from(r, 0);
     const View& x = i == 0 ? img : out[f];
     GTX_CHECK(i == 0 || r.mod == TrunkRow::DETECT || r.mod == TrunkRow::CONCAT || x.ptr, "internal: model.%d reads model.%d, which has no output", i, f);
-    GTX_CHECK(i == 0 || up_src[f] < 0 || r.mod == TrunkRow::BLOCK || r.mod == TrunkRow::ELAN, "internal: only a C2f / C3k2 / ELAN block reads an upsampled source in place (model.%d)", i);
+    GTX_CHECK(i == 0 || up_src[f] < 0 || r.mod == TrunkRow::BLOCK || r.mod == TrunkRow::ELAN || r.mod == TrunkRow::A2C2F, "internal: only a C2f / C3k2 / ELAN / A2C2f block reads an upsampled source in place (model.%d)", i);
     switch (r.mod) {
       case TrunkRow::CONV:
         if (i == 0) { out[i] = stem(img, front); break; }
@@ -457,6 +551,9 @@ YoloTrunk::Levels YoloTrunk::build(const View& img, const TrunkGraph& g, bool fr
         break;
       }
       case TrunkRow::C2PSA: out[i] = c2psa(name(i), x, place(i, x.h, x.w)); break;
+      case TrunkRow::A2C2F:
+        out[i] = a2c2f(name(i), x, r.area, r.shortcut, place(i, x.h, x.w), up_src[f] >= 0 ? &out[up_src[f]] : nullptr);
+        break;
       case TrunkRow::PSA: out[i] = c2psa(name(i), x, place(i, x.h, x.w), true); break;
       case TrunkRow::ELAN:
         out[i] = elan(name(i), x, r.shortcut, place(i, x.h, x.w), up_src[f] >= 0 ? &out[up_src[f]] : nullptr);
@@ -660,6 +757,8 @@ void YoloTrunk::run_op(const Op& op, int nb, hipStream_t s) const {
     }
     case Op::POOLDOWN: launch_pool_down(fmt, op.in.map(), op.out.map(), op.out2.map(), nb, s); break;
     case Op::ATTN: launch_psa_attention(fmt, op.in.map(), op.out.map(), nb, op.heads, op.dw_w, op.dw_bias, op.sat, s); break;
+    case Op::AREAATTN: launch_area_attention(fmt, op.in.map(), op.out.map(), nb, op.heads, op.area, true, op.sat, s); break;
+    case Op::SCALEADD: launch_scale_add(fmt, op.in.map(), op.dw_res.map(), op.out.map(), nb, op.dw_w, op.sat, s); break;
   }
 }
 
@@ -708,6 +807,13 @@ void set_batch_op(Op& op, int nb, size_t es, bool pad_skip_on) {
     const double T = (double)op.in.h * op.in.w;
     op.flops = nb * (op.heads * T * T * 2.0 * (32 + 64) + 2.0 * 9 * T * op.out.c);
     op.bytes = nb * T * (op.in.c + op.out.c) * es;
+  } else if (op.kind == Op::AREAATTN) {             // q.k and p.v (width 32 each) per query-key pair of a band and head; the qkv map in, the output map out
+    const double T = (double)op.in.h * op.in.w;
+    op.flops = nb * op.heads * T * (T / op.area) * 2.0 * (32 + 32);
+    op.bytes = nb * T * (op.in.c + op.out.c) * es;
+  } else if (op.kind == Op::SCALEADD) {
+    op.flops = 2.0 * nb * op.out.h * op.out.w * op.out.c;
+    op.bytes = 3.0 * nb * op.out.h * op.out.w * op.out.c * es;
   }
 }
 

@@ -14,7 +14,7 @@
 namespace gtx {
 
 struct Op : OpInfo {
-  enum Kind { CONV, STEM, POOL, UPSAMPLE, DWCONV, ATTN, POOLDOWN } kind = CONV;
+  enum Kind { CONV, STEM, POOL, UPSAMPLE, DWCONV, ATTN, POOLDOWN, AREAATTN, SCALEADD } kind = CONV;
   ConvGroup grp{};       // CONV
   ConvConfig cfg{};
   // STEM / POOL / UPSAMPLE parameters
@@ -26,10 +26,11 @@ struct Op : OpInfo {
   const void* front_wpk = nullptr;   // the same weights packed for the front stage of model.1 (ConvProblem::front_w)
   float front_scale = 1.f;
   // DWCONV (depthwise dw_k x dw_k, stride dw_stride, on `in` -> `out`; act 0 none, 1 SiLU, 2 ReLU; dw_res: added after the activation when it
-  // has a buffer) / ATTN (C2PSA's attention on the qkv map `in`, dw_w / dw_bias = its pe)
+  // has a buffer) / ATTN (C2PSA's attention on the qkv map `in`, dw_w / dw_bias = its pe) / AREAATTN (AAttn's attention on the planar qkv
+  // map `in`, cut into `area` bands; area_attn.hpp) / SCALEADD (A2C2f's residual: out = dw_res + dw_w[c] * in)
   const float* dw_w = nullptr;       // [k * k][C] tap-major
   const float* dw_bias = nullptr;
-  int dw_act = 0, heads = 0;
+  int dw_act = 0, heads = 0, area = 0;
   int dw_k = 3, dw_stride = 1;
   View dw_res;
   View out2;                         // POOLDOWN (pool_down.hpp): `in` -> `out` (the 2x2 average) and, ADown, out2 (its 3x3 stride-2 maximum)
@@ -50,10 +51,10 @@ class YoloTrunk {
   struct Levels {
     std::vector<View> in;        // the Detect row's inputs, finest level first (a table without one: its last layer's output)
     std::vector<float> strides;  // net height / level height
-    std::string det_pfx;         // the Detect row: model.22 (yolov8.yaml), model.28 (yolov8-p2.yaml) or model.23 (yolo11.yaml, yolov10.yaml, yolo26.yaml)
+    std::string det_pfx;         // the Detect row: model.22 (yolov8.yaml), model.28 (yolov8-p2.yaml) or model.23 (yolo11.yaml, yolov10.yaml, yolo26.yaml) or model.21 (yolo12.yaml)
     bool dw_cls = false;         // TrunkGraph::dw_cls
   };
-  // The graph the tensors were built from, by their names: yolov10.yaml, yolo26.yaml, yolo11.yaml, yolov9.yaml, yolov8-p2.yaml, else yolov8.yaml
+  // The graph the tensors were built from, by their names: yolo12.yaml, yolov10.yaml, yolo26.yaml, yolo11.yaml, yolov9.yaml, yolov8-p2.yaml, else yolov8.yaml
   TrunkGraph choose_graph() const;
   static TrunkGraph cls_backbone();   // model.0-8 of yolov8.yaml = yolov8-cls.yaml's backbone
   // The classification graph the tensors were built from: yolo11-cls.yaml (model.0-8 of yolo11.yaml + C2PSA = model.9), else cls_backbone()
@@ -90,6 +91,9 @@ class YoloTrunk {
   View bottleneck(const std::string& m, const View& src, const View& dst, bool shortcut);
   View c3k(const std::string& m, const View& src, const View& dst, bool shortcut);
   View c2psa(const std::string& pfx, const View& x, const View* out_slice, bool bare = false);   // bare: PSA, the one block's tensors directly under pfx
+  // A2C2f (yolo12.yaml): members of two ABlocks cut into `area` bands, or of one C3k (c3k_shortcut) each -- the tensors tell which
+  View a2c2f(const std::string& pfx, const View& x, int area, bool c3k_shortcut, const View* out_slice, const View* up_src);
+  void ablock(const std::string& m, const View& x, const View& dst, int area);                  // one ABlock: x + AAttn(x), then + mlp
   void psa_block(const std::string& m, const View& b, const View& dst);                         // one PSABlock (C2PSA's, PSA's, the C3k2 with attention's)
   View cib(const std::string& m, const View& src, const View& dst, bool shortcut);
   View scdown(const std::string& pfx, const View& x, const View* out_slice);

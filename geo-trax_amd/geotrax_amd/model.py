@@ -135,6 +135,10 @@ class YOLO:
             from .weights import check_yolo26
 
             graph += check_yolo26(self.tensors)
+        if graph == "yolo12":                             # yolo12n.yaml ... yolo12x.yaml
+            from .weights import check_yolo12
+
+            graph += check_yolo12(self.tensors)
         if graph == "yolov9":                             # yolov9t.yaml / yolov9s.yaml / yolov9m.yaml / yolov9c.yaml
             from .weights import check_yolov9
 

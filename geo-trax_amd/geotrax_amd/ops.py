@@ -210,6 +210,25 @@ def psa_attention(qkv: np.ndarray, pe_w: np.ndarray, pe_b: np.ndarray, heads: in
     return out, bool(sat.value), (ms.value if iters > 0 else None)
 
 
+def area_attention(qkv: np.ndarray, heads: int, area: int, *, planar: bool = False, in_coff: int = 0, out: np.ndarray | None = None,
+                   out_coff: int = 0, split: bool = False, iters: int = 0, ctx=None):
+    """YOLO12's area attention (AAttn) on maps: qkv [n, h, w, cs] with 96 heads channels from in_coff -- per head [q 32 | k 32 | v 32],
+    or with planar [q of every head | k of every head | v of every head]. The h w positions, row-major, are cut into `area` equal runs
+    and a position attends to its own run only. Returns (out [n, h, w, cs_out] with 32 heads channels written from out_coff, saturated,
+    ms per launch or None). A map whose h w is no multiple of area is refused."""
+    ctx = ctx or _lib.default_context()
+    qkv = np.ascontiguousarray(qkv)
+    n, h, w, cs = qkv.shape
+    if out is None:
+        out = np.zeros((n, h, w, heads * 32), qkv.dtype)
+    out = np.ascontiguousarray(out).copy()
+    assert out.shape[:3] == (n, h, w) and out.dtype == qkv.dtype and (not split or qkv.dtype == np.float32)
+    ms, sat = C.c_float(), C.c_int()
+    check(ctx.lib.gtx_op_area_attention(ctx.handle, GTX_F32S if split else _dt(qkv), n, h, w, heads, area, int(planar), ptr(qkv), cs, in_coff,
+                                        ptr(out), out.shape[3], out_coff, iters, C.byref(ms), C.byref(sat)))
+    return out, bool(sat.value), (ms.value if iters > 0 else None)
+
+
 def dwconv(x: np.ndarray, w: np.ndarray, bias: np.ndarray, *, stride: int = 1, act: int = 1, residual: np.ndarray | None = None,
            split: bool = False, ctx=None):
     """Depthwise k x k convolution (k = 3, 5, 7; pad k / 2) + bias + activation (0 none, 1 SiLU, 2 ReLU) + residual after the

@@ -185,6 +185,24 @@ YOLO26_YAML = YOLO11_YAML[:9] + [                          # 26/yolo26.yaml (end
     (-1, 1, "C3k2", (1024, True, 0.5, True)),              # 22: (c2, c3k, e, attn): every m.{k} is Sequential(Bottleneck, PSABlock)
     ((16, 19, 22), 1, "Detect26", ("nc",)),                # 23: Detect with reg_max = 1 (a 4-output box 1x1) and a one-to-one copy of both branches
 ]
+YOLO12_YAML = YOLO11_YAML[:6] + [                          # 12/yolo12.yaml: 22 layers, no SPPF, no C2PSA
+    (-1, 4, "A2C2f", (512, True, 4)),                      # 6: (c2, a2, area): members of two ABlocks, attention cut into 4 horizontal bands
+    (-1, 1, "Conv", (1024, 3, 2)),
+    (-1, 4, "A2C2f", (1024, True, 1)),                     # 8: attention over the whole map
+    _UP,
+    ((-1, 6), 1, "Concat", (1,)),
+    (-1, 2, "A2C2f", (512, False, -1)),                    # 11: a2 off: every member is a C3k
+    _UP,
+    ((-1, 4), 1, "Concat", (1,)),
+    (-1, 2, "A2C2f", (256, False, -1)),                    # 14
+    (-1, 1, "Conv", (256, 3, 2)),
+    ((-1, 11), 1, "Concat", (1,)),
+    (-1, 2, "A2C2f", (512, False, -1)),                    # 17
+    (-1, 1, "Conv", (512, 3, 2)),
+    ((-1, 8), 1, "Concat", (1,)),
+    (-1, 2, "C3k2", (1024, True)),                         # 20
+    ((14, 17, 20), 1, "Detect", ("nc",)),                  # 21: YOLO11's Detect
+]
 YOLOV8_CLS_YAML = _V8_BACKBONE + [(-1, 1, "Classify", ("nc",))]
 YOLO11_CLS_YAML = YOLO11_YAML[:9] + [                      # model.0-8 of yolo11.yaml; no SPPF
     (-1, 2, "C2PSA", (1024,)),                             # 9
@@ -197,10 +215,11 @@ def _rows(table, *modules) -> tuple[int, ...]:
     return tuple(i for i, r in enumerate(table) if r[2] in modules)
 
 
-def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False) -> list[tuple[str, tuple[int, ...], bool]]:
+def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False, a2_residual=False, gammas=None) -> list[tuple[str, tuple[int, ...], bool]]:
     """ultralytics' parse_model over one table: (tensor name, shape, has_act) of every conv of the fused model, in module order.
     ch(c): a yaml width as built; rep(i, n): the repeats of layer i as built; c3k_all: every C3k2 holds C3k blocks (yolo11 m / l / x);
-    dw_cls: Detect's class branch is DWConv + Conv(1x1) twice (yolo11.yaml)."""
+    dw_cls: Detect's class branch is DWConv + Conv(1x1) twice (yolo11.yaml); a2_residual: parse_model's extra A2C2f arguments of
+    yolo12 l / x (residual = True, mlp_ratio = 1.2), the `gamma` vectors of which -- no convs -- are appended to `gammas` as (name, (c2,))."""
     specs: list[tuple[str, tuple[int, ...], bool]] = []
     out: list[int] = []                                    # output channels per layer
 
@@ -249,6 +268,23 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False) -> list[tuple[
             else:
                 bottleneck(m, c, 1.0 if c3k is None else 0.5)
         conv(f"{pfx}.cv2.conv", (2 + n) * c, cout, 1)
+
+    def c3k_block(m, c, n=2):
+        """C3k(c, c, n): cv1 / cv2 to half the width, n full-width Bottlenecks behind cv1, cv3 on the two"""
+        h = int(c * 0.5)
+        conv(m + ".cv1.conv", c, h, 1)
+        conv(m + ".cv2.conv", c, h, 1)
+        conv(m + ".cv3.conv", 2 * h, c, 1)
+        for j in range(n):
+            bottleneck(f"{m}.m.{j}", h, 1.0)
+
+    def ablock(m, c, mlp_ratio):
+        """ABlock(c, heads = c / 32, mlp_ratio, area): AAttn's qkv / proj / pe (depthwise 7x7), none with an activation, then the two-conv mlp"""
+        conv(m + ".attn.qkv.conv", c, 3 * c, 1, act=False)
+        conv(m + ".attn.proj.conv", c, c, 1, act=False)
+        dwconv(m + ".attn.pe.conv", c, False, 7)
+        conv(m + ".mlp.0.conv", c, int(c * mlp_ratio), 1)
+        conv(m + ".mlp.1.conv", int(c * mlp_ratio), c, 1, act=False)
 
     def repcsp(p, c1, c2, n):
         """RepCSP(c1, c2, n) = C3 whose m.{k} are RepBottlenecks of e = 1.0: the fused RepConv (one 3x3) then a Conv3x3"""
@@ -299,6 +335,19 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False) -> list[tuple[
             for k in range(n):
                 psablock(f"{pfx}.m.{k}", c)
             conv(pfx + ".cv2.conv", 2 * c, out[i], 1)
+        elif mod == "A2C2f":                               # (c2, a2, area): c_ = c2 / 2; cv1 -> c_, n members chained, cv2 on all 1 + n
+            out.append(ch(args[0]))
+            c = int(out[i] * 0.5)
+            conv(pfx + ".cv1.conv", cin, c, 1)
+            for k in range(n):
+                if args[1]:
+                    for j in range(2):
+                        ablock(f"{pfx}.m.{k}.{j}", c, 1.2 if a2_residual else 2.0)
+                else:
+                    c3k_block(f"{pfx}.m.{k}", c)
+            conv(pfx + ".cv2.conv", (1 + n) * c, out[i], 1)
+            if args[1] and a2_residual and gammas is not None:
+                gammas.append((pfx + ".gamma", (out[i],)))
         elif mod == "C2fCIB":
             out.append(ch(args[0]))
             c2f(pfx, cin, out[i], n, cib=bool(args[2]) if len(args) > 2 else False)
@@ -478,7 +527,7 @@ def has_yolo11_blocks(tensors: dict) -> bool:
 
 def check_yolo11(tensors: dict) -> None:
     """Raises NotImplementedError unless the names and shapes are those of a fused yolo11.yaml detect model. Other graphs built from
-    the same blocks (YOLO12's A2C2f, yolo11-cls with C2PSA at model.9 -- the ReID embedder's, is_yolo11_cls --, -seg / -obb / -pose heads with a
+    the same blocks (YOLO12's A2C2f when is_yolo12() does not claim the file, yolo11-cls with C2PSA at model.9 -- the ReID embedder's, is_yolo11_cls --, -seg / -obb / -pose heads with a
     cv4 or proto branch) are never built into the wrong network."""
     no = NotImplementedError(f"checkpoint with attention / depthwise-Detect blocks in another arrangement than yolo11.yaml's: of that "
                              f"family only {YOLO11_TOPOLOGY} is implemented")
@@ -740,6 +789,102 @@ def synthetic_yolo26(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: flo
     damped weights (box_weight_scale) around the biases YOLO26_BOX_BIAS, one of which is negative."""
     return _draw_yolov8(np.random.default_rng(seed), yolo26_layer_specs(scale, nc), cls_bias, gain, 0.3, (0.0, 0.0, 0.0), box_weight_scale)
 
+# --------------------------------------------------------------------------- YOLO12 (cfg/models/12/yolo12.yaml)
+# What `YOLO("yolo12s.pt")` fine-tunes to: yolo11.yaml's first six rows, then A2C2f blocks in place of its C3k2 / SPPF / C2PSA: with
+# area attention in the backbone (model.6: 4 horizontal bands, model.8: the whole map; each member two ABlocks of heads = c_ / 32, head
+# width 32 for q, k and v, a depthwise 7x7 `pe`, an mlp of ratio 2.0 -- 1.2 at scales l / x, which also scale the block's output by a
+# learned per-channel `gamma` and add its input) and with C3k members in the neck (model.11 / 14 / 17); a C3k2 closes the neck (model.20)
+# and YOLO11's Detect = model.21 reads [14, 17, 20]. 22 layers. Restated from memory of ultralytics' public source; not checked against
+# the package (it is not installed). The doubts are listed in tests/yolo12_ref.py.
+
+YOLO12_TOPOLOGY = ("yolo12 detect (yolo12{n,s,m,l,x}: A2C2f with area attention = model.6 / 8, A2C2f with C3k members = model.11 / 14 / 17, "
+                   "C3k2 = model.2 / 4 / 20, Detect = model.21 on model.14 / 17 / 20)")
+YOLO12_AREAS = {6: 4, 8: 1}   # the yaml's `area` per attention row; no tensor tells it (csrc/yolo_tables.hpp kYolo12 holds the same)
+
+
+def is_yolo12(tensors: dict) -> bool:
+    """True when the names hold what only a YOLO12 file has: an A2C2f's ABlocks, a Sequential of two inside `m.{k}`, at model.6 or
+    model.8 (`model.6.m.0.0.attn.qkv`; YOLO11 and YOLO26 have no attention there, and a stray `model.6.m.0.attn` is YOLO11's to
+    refuse). Which graph it is, and whether this build runs it: check_yolo12()."""
+    return "model.6.m.0.0.attn.qkv.conv.weight" in tensors or "model.8.m.0.0.attn.qkv.conv.weight" in tensors
+
+
+def _yolo12_want(tensors_or_none, scale: str, nc: int):
+    """(conv specs, gamma specs) of yolo12<scale>.yaml; c3k per C3k2 row off the tensors when some are given, else parse_model's rule"""
+    table = []
+    for i, (frm, n, mod, args) in enumerate(YOLO12_YAML):
+        if mod == "C3k2" and tensors_or_none is not None:
+            table.append((frm, n, mod, (args[0], f"model.{i}.m.0.cv3.conv.weight" in tensors_or_none) + tuple(args[2:])))
+        else:
+            table.append((frm, n, mod, args))
+    gammas: list = []
+    specs = _scaled_specs(table, YOLO11_SCALES, scale, nc, c3k_all=tensors_or_none is None and scale in "mlx", dw_cls=True,
+                          a2_residual=scale in "lx", gammas=gammas)
+    return specs, gammas
+
+
+def check_yolo12(tensors: dict) -> str:
+    """The scale ("n" / "s" / "m" / "l" / "x") of a fused yolo12.yaml detect model; raises NotImplementedError, with a message that
+    names yolo12, for every other arrangement of its blocks (attention elsewhere, Detect elsewhere, a cv4 / proto branch, anything past
+    model.21, another width or repeat count, a gamma where the scale has none). Strict like check_yolo26(): the table is rebuilt from
+    model.0's width and the repeats, and every shape is compared. yolo12.yaml's scales are yolo11.yaml's."""
+    no = NotImplementedError(f"checkpoint with YOLO12's blocks (A2C2f with area attention at model.6 / 8) in another arrangement than yolo12.yaml's: "
+                             f"of that family only {YOLO12_TOPOLOGY} is implemented")
+    shape = lambda n: tuple(np.shape(tensors[n])) if n in tensors else None
+    c0, nc_w = shape("model.0.conv.weight"), shape("model.21.cv3.0.2.weight")
+    if c0 is None or nc_w is None:
+        raise no
+    # model.0's width tells n / s / x apart; m and l share every width and differ in the repeats (model.2: 1 or 2 blocks)
+    scale = {16: "n", 32: "s", 96: "x"}.get(c0[0]) or ({64: "l" if "model.2.m.1.cv1.conv.weight" in tensors else "m"}.get(c0[0]))
+    if scale is None:
+        raise no
+    want, gammas = _yolo12_want(tensors, scale, nc_w[0])
+    names = set()
+    for name, shp, _ in want:
+        names.add(name)
+        if shape(name + ".weight") != shp:
+            raise no
+    for name, shp in gammas:
+        if shape(name) != shp:
+            raise no
+    layer = lambda k: int(k.split(".")[1]) if k.startswith("model.") and k.split(".")[1].isdigit() else -1
+    for k in tensors:
+        i = layer(k)
+        if i < 0:
+            continue
+        if i > 21 or (".attn." in k and i not in YOLO12_AREAS):
+            raise no
+        if i == 21 and k.split(".")[2] == "dfl":
+            continue
+        if k.endswith(".gamma") and (k, shape(k)) not in gammas:
+            raise no
+        if k.endswith(".weight") and k[: -len(".weight")] not in names:
+            raise no
+    return scale
+
+
+def yolo12_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
+    """(tensor name, OIHW shape, has_act) for every conv of a fused YOLO12 detect model (depthwise convs: (C, 1, k, k); AAttn's pe is
+    7x7). The `gamma` vectors of scales l / x are no convs: yolo12_gamma_specs()."""
+    return _yolo12_want(None, scale, nc)[0]
+
+
+def yolo12_gamma_specs(scale: str = "s") -> list[tuple[str, tuple[int]]]:
+    """(tensor name, (c2,)) of A2C2f's learned residual scales: model.6.gamma and model.8.gamma at scales l / x, none below."""
+    return _yolo12_want(None, scale, 4)[1]
+
+
+def synthetic_yolo12(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0, gain: float = 1.7, box_decay: float | tuple = 0.3,
+                     level_bias: tuple = (0.0, 0.0, 0.0), box_weight_scale: float = 0.3, gamma: float = 0.5) -> dict[str, np.ndarray]:
+    """Seeded random fused weights of the YOLO12 architecture, drawn like synthetic_yolo11's (same knobs, the draws in the order of
+    yolo12_layer_specs), then the gammas of scales l / x ~ N(gamma, (gamma / 4)^2) from the same generator: ultralytics starts them at
+    0.01, which would hide the block behind its own input; the default lets both terms of x + gamma * y count."""
+    rng = np.random.default_rng(seed)
+    t = _draw_yolov8(rng, yolo12_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias, box_weight_scale)
+    for name, shp in yolo12_gamma_specs(scale):
+        t[name] = (gamma + 0.25 * gamma * rng.standard_normal(shp)).astype(np.float32)
+    return t
+
 # --------------------------------------------------------------------------- YOLOv9 (cfg/models/v9/yolov9{t,s,m,c}.yaml)
 # The GELAN networks: ELAN1 / RepNCSPELAN4 blocks (cv1 1x1 -> two chunks; cv2 and cv3 are Sequential(RepCSP, Conv3x3) -- plain Conv3x3
 # in ELAN1 -- each on the output before it; cv4 1x1 on the four pieces), AConv (avg_pool2d(2, 1) then a 3x3 stride-2 Conv; scales t / s /
@@ -994,20 +1139,23 @@ RTDETR_TOPOLOGIES = ("rtdetr-l (HGNetv2 + AIFI + CCFM, RTDETRDecoder = model.28)
 
 def detector_topology(tensors: dict) -> tuple[str, str]:
     """(graph, head prefix) of a detector checkpoint, read off the tensor names the way the reference reads its model yaml:
-    ("yolov8", "model.22"), ("yolov8-p2", "model.28"), ("yolo11", "model.23"), ("yolov10", "model.23"), ("yolo26", "model.23"), ("yolov9", "model.22"), ("rtdetr-l", "model.28") or
+    ("yolov8", "model.22"), ("yolov8-p2", "model.28"), ("yolo11", "model.23"), ("yolov10", "model.23"), ("yolo26", "model.23"), ("yolo12", "model.21"), ("yolov9", "model.22"), ("rtdetr-l", "model.28") or
     ("yolov8-rtdetr", "model.22").
     An RT-DETR layout other than those two (rtdetr-x with its decoder at model.32, ResNet backbones, ...) raises NotImplementedError,
-    and so does a file with YOLO11's, YOLOv10's or YOLO26's blocks (attention, a depthwise Detect class branch, SCDown + a one-to-one head,
+    and so does a file with YOLO11's, YOLOv10's, YOLO12's or YOLO26's blocks (attention, a depthwise Detect class branch, SCDown + a one-to-one head,
     attention inside model.22 + a 4-output box branch) in another arrangement than their yaml's."""
     if not is_rtdetr(tensors):
         if is_yolov10(tensors):
             check_yolov10(tensors)                         # raises for another arrangement, and for the scales that are not implemented
             return "yolov10", "model.23"
+        if is_yolo12(tensors):                             # asked before YOLO11's check, so that a YOLO12 file gets its own messages
+            check_yolo12(tensors)                          # raises for another arrangement of A2C2f's blocks
+            return "yolo12", "model.21"
         if is_yolo26(tensors) or _yolo26_marks(tensors):
             check_yolo26(tensors)                          # raises for another arrangement, reg_max other than 1, -seg / -obb / -pose heads
             return "yolo26", "model.23"
         if has_yolo11_blocks(tensors):
-            check_yolo11(tensors)                          # raises for YOLO12 / yolo11-cls, -seg, -obb, -pose ...
+            check_yolo11(tensors)                          # raises for yolo11-cls, -seg, -obb, -pose, stray attention ...
             return "yolo11", "model.23"
         if _has_gelan(tensors):                            # is_yolov9, or GELAN blocks without model.9.cv5: yolov9e, which check_yolov9 refuses by name
             check_yolov9(tensors)

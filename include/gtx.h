@@ -92,7 +92,9 @@ extern "C" {
  *     gtx_op_head_sparse_box and gtx_sparse_level (the sparse Detect box launch on host arrays) added: a new entry point and a
  *     struct of its own only, so the number stays.
  *     gtx_op_homography_refit (the host refit that ends every robust homography, on host arrays) added: a new entry point only, so
- *     the number stays. */
+ *     the number stays.
+ *     gtx_op_area_attention added and arch 0 also takes YOLO12 tensors (yolo12.yaml: A2C2f blocks with area attention, Detect =
+ *     model.21; the tensors tell the graph, gtx_det_config is unchanged): a new entry point only, so the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -439,6 +441,14 @@ int gtx_op_upsample2x(gtx_ctx* ctx, int dtype, int n, int h, int w, int c, const
 int gtx_op_psa_attention(gtx_ctx* ctx, int dtype, int n, int n_alloc, int h, int w, int heads, const void* qkv, int in_cstride,
                          int in_coff, const float* pe_w, const float* pe_b, void* out, int out_cstride, int out_coff, int form,
                          int iters, float* ms_per_launch, int* saturated);
+/* ultralytics' AAttn attention (YOLO12's A2C2f) on n maps: the h w positions, row-major, are the tokens, cut into `area` contiguous
+ * runs of h w / area (GTX_ERR_UNSUPPORTED when h w % area != 0); a token attends to its own run only. qkv [n][h][w][in_cstride] holds
+ * 96 heads channels from in_coff -- planar = 0: per head [q 32 | k 32 | v 32], heads consecutive; planar = 1: [q of every head | k of
+ * every head | v of every head] --; out [n][h][w][out_cstride] gets softmax(q^T k * 32^-0.5) v in its channels [out_coff, out_coff +
+ * 32 heads), head-major, and keeps the rest. Host arrays as for gtx_op_psa_attention; iters, *ms_per_launch and *saturated likewise. */
+int gtx_op_area_attention(gtx_ctx* ctx, int dtype, int n, int h, int w, int heads, int area, int planar, const void* qkv,
+                          int in_cstride, int in_coff, void* out, int out_cstride, int out_coff, int iters, float* ms_per_launch,
+                          int* saturated);
 
 /* Depthwise k x k convolution (k = 3, 5 or 7; stride 1 or 2; pad k / 2) + bias + activation (0 none, 1 SiLU, 2 ReLU) + optional residual
  * added after the activation: x [n][h][w][c], w [k * k][c] tap-major, bias [c], res (or NULL) and out [n][ho][wo][c], c % 8 == 0. Host

@@ -27,6 +27,10 @@ branches (`model.23.cv2 / cv3`): convert_state_dict() folds every Conv + BN pair
 one2one_cv3 -- `end2end: false` runs them through NMS -- and writes `detector.meta` = [family 10, one-to-many kept, end-to-end head,
 the head's 300].
 
+A YOLO12 detect checkpoint (yolo12{n,s,m,l,x}.yaml: `model.6.m.0.0.attn.qkv.conv.*`, Detect = model.21) goes through the plain branch:
+every Conv + BatchNorm pair of its A2C2f blocks (qkv, proj, the depthwise 7x7 pe, the mlp pair, the C3k members) is folded by fold_bn
+like any other, and the `model.6.gamma` / `model.8.gamma` vectors of scales l / x are written as they are.
+
 A YOLO26 detect checkpoint (yolo26{n,s,m,l,x}.yaml: `model.22.m.0.1.attn.qkv.*`, 4-row `model.23.*cv2.<l>.2`) takes the same branch: every
 Conv + BN pair is folded under its own name (model.22's `m.<k>.0.cv1` Bottleneck and `m.<k>.1.attn.*` / `ffn.*` PSABlock convolutions
 included; it has no RepVGGDW), cv2 / cv3 stay next to one2one_cv2 / one2one_cv3, and `detector.meta` = [family 26, one-to-many kept,
