@@ -66,8 +66,8 @@ void Detector::plan_pad_skip() {
     return hit;
   };
   dep[img_.ptr] = Rows{lb_.top, lb_.top + lb_.new_h};
-  auto through = [](Rows r, int k, int s, int h_out) {   // rows of a k x k / stride s / pad k/2 layer's output that see input rows [lo, hi)
-    const int p = k / 2;
+  auto through = [](Rows r, int k, int s, int h_out, int pad = -1) {   // rows of a k x k / stride s / pad k/2 (or `pad`) layer's output that see input rows [lo, hi)
+    const int p = pad < 0 ? k / 2 : pad;
     const int num = r.lo + p - k + 1;                      // y >= num / s
     const int lo = num <= 0 ? 0 : (num + s - 1) / s;
     const int hi = (r.hi - 1 + p) / s + 1;
@@ -90,7 +90,8 @@ void Detector::plan_pad_skip() {
     if (op.kind == Op::STEM) {
       Rows in{0, 0};
       const bool known = get(op.in.ptr, in);
-      put(op.out.ptr, known, through(in, 3, 2, op.out.h));
+      // yolov5.yaml's 6x6 / 2 / pad 2 stem: output row y reads image rows 2 y - 2 .. 2 y + 3
+      put(op.out.ptr, known, op.stem_k == 6 ? through(in, 6, 2, op.out.h, 2) : through(in, 3, 2, op.out.h));
       continue;
     }
     if (op.kind != Op::CONV) { put(op.out.ptr, false, Rows{0, 0}); continue; }   // pools / upsampling: deep in the network

@@ -31,6 +31,7 @@
 #include "rtdetr_kernels.hpp"
 #include "sift.hpp"
 #include "stabilizer.hpp"
+#include "stem6.hpp"
 #include "tracker.hpp"
 
 namespace {
@@ -327,6 +328,38 @@ int gtx_op_stem(gtx_ctx* ctx, int dtype, int packed, int n, int h, int w, int c0
       upload(dpk, pk.data(), pk.size() * 2);
     }
     gtx::launch_stem(dtype, dimg.p, n, h, w, dw.as<float>(), db.as<float>(), dpk.p, c0, dout.p, ho, wo, ctx->stream, sc);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    download_fmt(out, dtype, dout, ob);
+  });
+}
+
+// yolov5.yaml's stem (model.0: 6x6 stride 2 pad 2 on RGB0 bytes + bias + SiLU) as launch_stem6 runs it for the detector
+// (tests/test_yolov5u_gpu.py). GTX_F16 and GTX_F32S: the matrix-core kernels on their packed weights; GTX_F32: the exact kernel.
+// iters > 0: *ms_per_launch = mean time of that many further launches.
+int gtx_op_stem6(gtx_ctx* ctx, int dtype, int n, int h, int w, int c0, const void* img, const float* w108, const float* bias, void* out,
+                 int iters, float* ms_per_launch) {
+  return guarded([&] {
+    if (dtype != GTX_F16 && dtype != GTX_F32 && dtype != GTX_F32S) op_bad("stem6", "dtype: GTX_F16, GTX_F32 or GTX_F32S");
+    if (c0 < 16 || c0 > 96 || c0 % 16) op_bad("stem6", "c0 must be 16, 32, 48, 64, 80 or 96");
+    if (n < 1 || h < 2 || w < 2 || (double)n * h * w > 1e9) op_bad("stem6", "n must be at least 1, h and w at least 2");
+    need(ctx, "ctx"); need(img, "img"); need(w108, "w108"); need(bias, "bias"); need(out, "out");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const int ho = gtx::stem6_out(h), wo = gtx::stem6_out(w);
+    const size_t ob = (size_t)n * ho * wo * c0 * gtx::dtype_size(dtype);
+    gtx::DevBuf dimg, dw, db, dpk, dout;
+    upload(dimg, img, (size_t)n * h * w * 4);
+    upload(dw, w108, (size_t)108 * c0 * 4);
+    zeros(db, (size_t)(c0 + 31) / 32 * 32 * sizeof(float));      // whole 32-channel groups: the matrix-core kernels read a group's bias unconditionally
+    GTX_HIP(hipMemcpy(db.p, bias, c0 * sizeof(float), hipMemcpyHostToDevice));
+    zeros(dout, ob);
+    float sc = 1.f;
+    if (dtype != GTX_F32) {
+      const std::vector<uint16_t> pk = dtype == GTX_F32S ? gtx::pack_stem6_weights_split(w108, c0, &sc) : gtx::pack_stem6_weights_f16(w108, c0);
+      upload(dpk, pk.data(), pk.size() * 2);
+    }
+    auto once = [&] { gtx::launch_stem6(dtype, dimg.p, n, h, w, dw.as<float>(), db.as<float>(), dpk.p, c0, dout.p, ho, wo, ctx->stream, sc); };
+    once();
+    if (iters > 0 && ms_per_launch) *ms_per_launch = time_launches(ctx->stream, iters, once);
     GTX_HIP(hipStreamSynchronize(ctx->stream));
     download_fmt(out, dtype, dout, ob);
   });

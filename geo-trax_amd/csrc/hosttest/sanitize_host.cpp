@@ -255,6 +255,19 @@ static bool run_trunk_tables() {
   std::vector<TrunkRow> bad12(kYolo12, kYolo12 + 22);
   bad12[10].from[1] = 11;                             // yolo12.yaml's first Concat reading a later layer
   if (trunk_table_error(bad12.data(), 22) != 10) return false;
+  // yolov5.yaml: 25 rows, eight C3 blocks (shortcut on in the backbone only), the neck's 1x1 Convs at 10 / 14 each feed one Concat (22 / 19)
+  // besides their Upsample, Detect last on 17 / 20 / 23; the 6x6 / 2 / pad 2 stem's output side, odd sides and the smallest one included
+  constexpr int n5 = (int)(sizeof(kYolov5u) / sizeof(TrunkRow));
+  int c3 = 0;
+  for (const TrunkRow& r : kYolov5u) c3 += r.mod == TrunkRow::C3 && r.shortcut == (r.i < 9) && r.area == 0;
+  if (n5 != 25 || trunk_table_error(kYolov5u, n5) >= 0 || c3 != 8 || kYolov5u[24].mod != TrunkRow::DETECT || kYolov5u[24].from[0] != 17 ||
+      kYolov5u[24].from[1] != 20 || kYolov5u[24].from[2] != 23 || kYolov5u[22].from[1] != 10 || kYolov5u[19].from[1] != 14)
+    return false;
+  std::vector<TrunkRow> bad5(kYolov5u, kYolov5u + n5);
+  bad5[19].from[1] = 10;                              // model.10 in two Concats
+  if (trunk_table_error(bad5.data(), n5) != 22) return false;
+  for (int n = 2; n <= 40; ++n)
+    if (stem6_out(n) != (n + 2 * 2 - 6) / 2 + 1 || 2 * (stem6_out(n) - 1) - 2 + 5 > n + 1 || 2 * stem6_out(n) - 2 + 5 <= n + 1) return false;
   std::vector<TrunkRow> bad(kYolo10, kYolo10 + 24);
   bad[12].from[1] = 13;                               // a Concat that reads a later layer
   if (trunk_table_error(bad.data(), 24) != 12) return false;

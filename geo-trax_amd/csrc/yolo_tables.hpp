@@ -8,14 +8,16 @@ namespace gtx {
 
 // One row of a trunk's layer table: a layer of the model yaml, as the yaml writes it
 struct TrunkRow {
-  enum Module { CONV, BLOCK, SPPF, C2PSA, UPSAMPLE, CONCAT, DETECT, SCDOWN, PSA, ELAN, ADOWN, SPPELAN, A2C2F };
+  enum Module { CONV, BLOCK, SPPF, C2PSA, UPSAMPLE, CONCAT, DETECT, SCDOWN, PSA, ELAN, ADOWN, SPPELAN, A2C2F, C3 };
   int i;            // the layer index: its tensors are "model.<i>.*"
-  Module mod;       // CONV: Conv 3x3 stride 2 (row 0: the stem); BLOCK: C2f / C3k2 / C2fCIB (which one, the tensors tell);
+  Module mod;       // CONV: Conv 3x3 stride 2, or 1x1 stride 1 (yolov5.yaml's neck; the tensor tells), row 0: the stem (3x3, or yolov5.yaml's
+                    // 6x6 / 2 / pad 2; the tensor tells); BLOCK: C2f / C3k2 / C2fCIB (which one, the tensors tell);
                     // SCDOWN: 1x1 Conv + depthwise 3x3 stride 2 without activation; PSA: C2PSA's one block directly under the layer (yolov10.yaml);
                     // ELAN: ELAN1 / RepNCSPELAN4, ADOWN: AConv / ADown (which one, the tensors tell), SPPELAN: SPPF's pools closed by cv5 (yolov9.yaml);
                     // A2C2F: yolo12.yaml's block, members of two ABlocks (area attention) or one C3k each (which, the tensors tell)
+                    // C3: yolov5.yaml's block, cv3(cat(m(cv1 x), cv2 x)) with m = Bottlenecks (1x1, 3x3) of full hidden width
   int from[4];      // the yaml's `from`: -1 = the row above (row 0: the image), else a layer index; 0 ends the list
-  bool shortcut;    // BLOCK: the bottlenecks add their input; SPPF: yolo26.yaml's form (cv1 without activation, the input added to cv2's output)
+  bool shortcut;    // BLOCK / C3: the bottlenecks add their input; SPPF: yolo26.yaml's form (cv1 without activation, the input added to cv2's output)
   int area = 0;     // A2C2F with ABlocks: the yaml's `area` (bands the attention is cut into; 1 = the whole map). No tensor tells it.
 };
 struct TrunkGraph {
@@ -72,6 +74,10 @@ inline const char* psa_attention_kernel_name(int h, int w) { return psa_attentio
 // launch_area_attention (area_attn.hpp): keys per LDS stage of area_attn_kernel; a map runs when its positions cut into `area` equal runs
 inline constexpr int kAreaAttnKeyTile = 64;
 inline bool area_attention_fits(int h, int w, int area) { return area >= 1 && h >= 1 && w >= 1 && (h * w) % area == 0; }
+// launch_stem6 (stem6.hpp): the output side of Conv(k = 6, s = 2, p = 2) on a side of `n` pixels (n >= 2), and the workgroup's tile of
+// output pixels: rows x columns on the matrix-core kernels (one row per wave), rows x columns on the exact-fp32 kernel
+inline int stem6_out(int n) { return (n - 2) / 2 + 1; }
+inline constexpr int kStem6Cols = 32, kStem6Rows = 4, kStem6RowsF32 = 8;
 
 namespace tables {
 using R = TrunkRow;
@@ -145,6 +151,17 @@ inline constexpr R kYolo12[] = {
     {12, R::UPSAMPLE, {-1}, false}, {13, R::CONCAT, {-1, 4}, false},  {14, R::A2C2F, {-1}, kA2C2fC3kShortcut}, {15, R::CONV, {-1}, false},
     {16, R::CONCAT, {-1, 11}, false}, {17, R::A2C2F, {-1}, kA2C2fC3kShortcut}, {18, R::CONV, {-1}, false}, {19, R::CONCAT, {-1, 8}, false},
     {20, R::BLOCK, {-1}, kNeckShortcut}, {21, R::DETECT, {14, 17, 20}, false}};
+// v5/yolov5.yaml with the anchor-free Detect (the yolov5{n,s,m,l,x}u files): a 6x6 stem, C3 blocks (shortcut on in the backbone, off in the
+// neck, as the yaml writes it), SPPF = model.9, 1x1 Convs at model.10 / 14 that feed both an Upsample and the Concats 22 / 19 of the way
+// back down, YOLOv8's Detect = model.24. 25 layers. tests/yolov5u_ref.py lists the doubts.
+inline constexpr R kYolov5u[] = {
+    {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::C3, {-1}, true},          {3, R::CONV, {-1}, false},
+    {4, R::C3, {-1}, true},         {5, R::CONV, {-1}, false},        {6, R::C3, {-1}, true},          {7, R::CONV, {-1}, false},
+    {8, R::C3, {-1}, true},         {9, R::SPPF, {-1}, false},        {10, R::CONV, {-1}, false},      {11, R::UPSAMPLE, {-1}, false},
+    {12, R::CONCAT, {-1, 6}, false}, {13, R::C3, {-1}, false},        {14, R::CONV, {-1}, false},      {15, R::UPSAMPLE, {-1}, false},
+    {16, R::CONCAT, {-1, 4}, false}, {17, R::C3, {-1}, false},        {18, R::CONV, {-1}, false},      {19, R::CONCAT, {-1, 14}, false},
+    {20, R::C3, {-1}, false},       {21, R::CONV, {-1}, false},       {22, R::CONCAT, {-1, 10}, false}, {23, R::C3, {-1}, false},
+    {24, R::DETECT, {17, 20, 23}, false}};
 // yolo11-cls.yaml: model.0-8 are yolo11.yaml's, C2PSA follows them directly (no SPPF) and is the embedded layer; Classify = model.10
 inline constexpr R kYolo11Cls[] = {
     {0, R::CONV, {-1}, false},      {1, R::CONV, {-1}, false},        {2, R::BLOCK, {-1}, true},       {3, R::CONV, {-1}, false},

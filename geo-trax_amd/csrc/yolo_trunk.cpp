@@ -8,11 +8,13 @@
 // prefixes of these tables: yolov8-cls.yaml = kYolov8's rows 0-8, 11/yolo11-cls.yaml = kYolo11's rows 0-8 + C2PSA as model.9 (kYolo11Cls).
 // 26/yolo26.yaml is kYolo26: kYolo11's rows with SPPF's linear cv1 + residual at model.9 and the C3k2 with attention at model.22.
 // 12/yolo12.yaml is kYolo12: A2C2f blocks (area attention in the backbone, C3k members in the neck), no SPPF, Detect = model.21.
+// v5/yolov5.yaml with the anchor-free Detect (the yolov5*u files) is kYolov5u: a 6x6 stem (stem6.hip), C3 blocks, 1x1 Convs in the neck, Detect = model.24.
 #include "yolo_trunk.hpp"
 #include "area_attn.hpp"
 #include "pool_down.hpp"
 #include "rtdetr_kernels.hpp"
 #include "split_format.hpp"
+#include "stem6.hpp"
 
 #include <algorithm>
 
@@ -32,6 +34,10 @@ TrunkGraph YoloTrunk::choose_cls_graph() const {
 
 // Which yaml the tensors were built from, told apart by their names like the reference's model yaml does
 TrunkGraph YoloTrunk::choose_graph() const {
+  // yolov5.yaml: a 6x6 stem and YOLOv8's Detect at model.24 -- no other yaml has either
+  if (net_.has("model.0.conv.weight") && net_.tensor("model.0.conv.weight").shape.size() == 4 && net_.tensor("model.0.conv.weight").shape[2] == 6 &&
+      net_.has("model.24.cv2.0.0.conv.weight"))
+    return graph_of(kYolov5u, false);
   // yolo12.yaml: an A2C2f's ABlocks (a Sequential of two inside m.{k}) at model.6 and YOLO11's Detect at model.21 -- no other yaml has either
   if (net_.has("model.6.m.0.0.attn.qkv.conv.weight") && net_.has("model.21.cv3.0.0.0.conv.weight")) return graph_of(kYolo12, true);
   // yolov10.yaml: PSA's attention directly under model.10, SCDown's depthwise model.5.cv2 and a one-to-one head at model.23
@@ -59,15 +65,17 @@ View YoloTrunk::conv(const std::string& name, const View& x, int stride, const V
       (env_flag("GTX_FUSE_FRONT", true) || env_flag("GTX_FUSE_STEM", true)))
     a.force_kc = 16;
   const View out = net_.emit_named_conv(ops_, name, x, a);
-  if (up_src) {
-    Op& op = ops_.back();
-    GTX_CHECK(op.cfg.ks == 1 && stride == 1 && op.cfg.variant == ConvForm::Split && up_src->h * 2 == x.h && up_src->w * 2 == x.w && up_src->c < x.c,
-              "%s: upsampled source does not fit", name.c_str());
-    ConvProblem& p = op.grp.p[0];
-    p.in2 = up_src->ptr; p.in2_cstride = up_src->cstride; p.in2_coff = up_src->coff; p.c_split = up_src->c;
-    op.family = conv_kernel_name(op.cfg);
-  }
+  if (up_src) read_upsampled(ops_.back(), x, *up_src);
   return out;
+}
+
+// The conv op just emitted on x reads x's leading up_src.c channels from up_src, upsampled 2x, instead (ConvProblem::in2)
+void YoloTrunk::read_upsampled(Op& op, const View& x, const View& up_src) {
+  GTX_CHECK(op.cfg.ks == 1 && op.cfg.stride == 1 && op.cfg.variant == ConvForm::Split && up_src.h * 2 == x.h && up_src.w * 2 == x.w && up_src.c < x.c,
+            "%s: upsampled source does not fit", op.name.c_str());
+  ConvProblem& p = op.grp.p[0];
+  p.in2 = up_src.ptr; p.in2_cstride = up_src.cstride; p.in2_coff = up_src.coff; p.c_split = up_src.c;
+  op.family = conv_kernel_name(op.cfg);
 }
 
 void YoloTrunk::upsample(const std::string& name, const View& src, const View& dst) {
@@ -152,6 +160,41 @@ View YoloTrunk::c3k(const std::string& m, const View& src, const View& dst, bool
   }
   conv_act(m + ".cv2.conv", src, 1, &right, nullptr);
   return conv_act(m + ".cv3.conv", cat, 1, &dst, nullptr, chp != ch ? ch : 0);
+}
+
+// C3(c1, c2, n, shortcut, e = 0.5) of yolov5.yaml: cv3(cat(m(cv1 x), cv2 x)), cv1 and cv2 both 1x1 on the block's input, m = n
+// Bottleneck(c_, c_, shortcut, k = (1x1, 3x3), e = 1.0). cv1 and cv2 run as ONE 1x1 launch over their weights stacked [cv2 | cv1] into
+// channels [c_, 3 c_) of a 3 c_-wide buffer; the bottlenecks chain from cv1's slice and the last one writes channels [0, c_), so that
+// cv3 reads its concat [m | cv2 x] in place as the buffer's first 2 c_ channels and no slice has two writers (plan_pad_skip).
+View YoloTrunk::c3(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src) {
+  const HostTensor &w1 = net_.tensor(pfx + ".cv1.conv.weight"), &w2 = net_.tensor(pfx + ".cv2.conv.weight");
+  const int c = (int)w1.shape[0], cin = (int)w1.shape[1];
+  int n = 0;
+  while (net_.has(pfx + ".m." + std::to_string(n) + ".cv1.conv.weight")) ++n;
+  GTX_CHECK(n > 0 && c % 16 == 0 && w1.shape.size() == 4 && w1.shape == w2.shape && w1.shape[2] == 1 && w1.shape[3] == 1 && cin == x.c,
+            "%s: cv1 / cv2 must be 1x1 convolutions of one shape on %d channels, with bottlenecks behind cv1", pfx.c_str(), x.c);
+  std::vector<float> ws((size_t)2 * c * cin), bs(2 * c, 0.f);
+  std::copy(w2.data.begin(), w2.data.end(), ws.begin());
+  std::copy(w1.data.begin(), w1.data.end(), ws.begin() + (size_t)c * cin);
+  if (const float* b = net_.bias_of(pfx + ".cv2.conv", c)) std::copy(b, b + c, bs.begin());
+  if (const float* b = net_.bias_of(pfx + ".cv1.conv", c)) std::copy(b, b + c, bs.begin() + c);
+  View buf = net_.new_view(x.h, x.w, 3 * c);
+  const View both = buf.slice(c, 2 * c), left = buf.slice(0, c);
+  NetRuntime::ConvArgs a;
+  a.act = 1; a.out_slice = &both;
+  net_.emit_conv(ops_, pfx + ".cv2|cv1.conv", ws.data(), 2 * c, cin, 1, bs.data(), x, a);
+  if (up_src) read_upsampled(ops_.back(), x, *up_src);
+  net_.set_layer_view(pfx + ".cv1.conv", buf.slice(2 * c, c));
+  net_.set_layer_view(pfx + ".cv2.conv", buf.slice(c, c));
+  View y = buf.slice(2 * c, c);
+  for (int j = 0; j < n; ++j) {
+    const View nxt = j + 1 == n ? left : net_.new_view(x.h, x.w, c);
+    bottleneck(pfx + ".m." + std::to_string(j), y, nxt, shortcut);
+    y = nxt;
+  }
+  const View out = conv(pfx + ".cv3.conv", buf.slice(0, 2 * c), 1, out_slice, nullptr);
+  net_.set_layer_view(pfx, out);
+  return out;
 }
 
 // ELAN1 / RepNCSPELAN4(c1, c2, c3, c4, n): cv1 -> two chunks of c3 / 2; cv2 on the second chunk, cv3 on cv2's output, each a
@@ -436,7 +479,9 @@ View YoloTrunk::scdown(const std::string& pfx, const View& x, const View* out_sl
 View YoloTrunk::stem(const View& img, bool front) {
   const int fmt = net_.format();
   const HostTensor& w0 = net_.tensor("model.0.conv.weight");
-  GTX_CHECK(w0.shape.size() == 4 && w0.shape[1] == 3 && w0.shape[2] == 3 && w0.shape[3] == 3, "model.0 must be a 3x3 conv on 3 channels");
+  GTX_CHECK(w0.shape.size() == 4 && w0.shape[1] == 3 && (w0.shape[2] == 3 || w0.shape[2] == 6) && w0.shape[3] == w0.shape[2],
+            "model.0 must be a 3x3 conv, or yolov5.yaml's 6x6, on 3 channels");
+  if (w0.shape[2] == 6) return stem6(img);
   const int c0 = (int)w0.shape[0];
   View a0 = net_.new_view(img.h / 2, img.w / 2, c0);
   std::vector<float> w27((size_t)27 * c0);
@@ -475,6 +520,42 @@ View YoloTrunk::stem(const View& img, bool front) {
   return a0;
 }
 
+// yolov5.yaml's layer 0: Conv(3, c0, 6, 2, 2), its own kernels (stem6.hip) on weights in tap-major order [108][c0]. Nothing is packed
+// for fuse_stem(): the fused front launch is built on the 27-tap stem.
+View YoloTrunk::stem6(const View& img) {
+  const int fmt = net_.format();
+  const HostTensor& w0 = net_.tensor("model.0.conv.weight");
+  const int c0 = (int)w0.shape[0];
+  GTX_CHECK(c0 % 16 == 0 && c0 <= 96 && img.h >= 2 && img.w >= 2, "model.0: a 6x6 stem of %d channels on a %d x %d image", c0, img.w, img.h);
+  View a0 = net_.new_view(stem6_out(img.h), stem6_out(img.w), c0);
+  std::vector<float> w108((size_t)108 * c0);
+  for (int o = 0; o < c0; ++o)
+    for (int i = 0; i < 3; ++i)
+      for (int y = 0; y < 6; ++y)
+        for (int x = 0; x < 6; ++x) w108[(size_t)((y * 6 + x) * 3 + i) * c0 + o] = w0.data[(((size_t)o * 3 + i) * 6 + y) * 6 + x];
+  std::vector<float> b((size_t)(c0 + 31) / 32 * 32, 0.f);     // whole 32-channel groups: the matrix-core kernels read a group's bias unconditionally
+  if (const float* pb = net_.bias_of("model.0.conv", c0)) std::copy(pb, pb + c0, b.begin());
+  auto upload_u16 = [&](const std::vector<uint16_t>& pk) {
+    void* dp = net_.alloc(pk.size() * 2);
+    GTX_HIP(hipMemcpy(dp, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
+    return dp;
+  };
+  Op op;
+  op.kind = Op::STEM;
+  op.stem_k = 6;
+  op.name = "model.0.conv";
+  op.family = dtype_ == DT_F16 ? "stem6_mfma_kernel" : (fmt == DT_F32S ? "stem6_split_kernel" : "stem6_kernel");
+  op.in = img;
+  op.out = a0;
+  op.w27 = net_.upload(w108);
+  op.bias = net_.upload(b);
+  if (dtype_ == DT_F16) op.wpk = upload_u16(pack_stem6_weights_f16(w108.data(), c0));
+  else if (fmt == DT_F32S) op.wpk = upload_u16(pack_stem6_weights_split(w108.data(), c0, &op.stem_scale));
+  ops_.push_back(op);
+  net_.set_layer_view("model.0.conv", a0);
+  return a0;
+}
+
 // The walk over a layer table, in yaml order. No Concat op exists: a row that a Concat lists writes straight into its slice of that
 // Concat's buffer (members in the yaml's `from` order, widths off the tensor shapes), which the Concat's consumer reads whole.
 YoloTrunk::Levels YoloTrunk::build(const View& img, const TrunkGraph& g, bool front) {
@@ -494,6 +575,7 @@ YoloTrunk::Levels YoloTrunk::build(const View& img, const TrunkGraph& g, bool fr
       case TrunkRow::CONV: width[i] = cout_of(name(i) + ".conv"); break;
       case TrunkRow::BLOCK: case TrunkRow::SPPF: case TrunkRow::C2PSA: case TrunkRow::SCDOWN: case TrunkRow::PSA: case TrunkRow::A2C2F: width[i] = cout_of(name(i) + ".cv2.conv"); break;
       case TrunkRow::ELAN: width[i] = cout_of(name(i) + ".cv4.conv"); break;
+      case TrunkRow::C3: width[i] = cout_of(name(i) + ".cv3.conv"); break;
       case TrunkRow::ADOWN: width[i] = cout_of(name(i) + ".cv1.conv") + (net_.has(name(i) + ".cv2.conv.weight") ? cout_of(name(i) + ".cv2.conv") : 0); break;
       case TrunkRow::SPPELAN: width[i] = cout_of(name(i) + ".cv5.conv"); break;
       case TrunkRow::UPSAMPLE:
@@ -535,11 +617,18 @@ YoloTrunk::Levels YoloTrunk::build(const View& img, const TrunkGraph& g, bool fr
     const int f = from(r, 0);
     const View& x = i == 0 ? img : out[f];
     GTX_CHECK(i == 0 || r.mod == TrunkRow::DETECT || r.mod == TrunkRow::CONCAT || x.ptr, "internal: model.%d reads model.%d, which has no output", i, f);
-    GTX_CHECK(i == 0 || up_src[f] < 0 || r.mod == TrunkRow::BLOCK || r.mod == TrunkRow::ELAN || r.mod == TrunkRow::A2C2F, "internal: only a C2f / C3k2 / ELAN / A2C2f block reads an upsampled source in place (model.%d)", i);
+    GTX_CHECK(i == 0 || up_src[f] < 0 || r.mod == TrunkRow::BLOCK || r.mod == TrunkRow::ELAN || r.mod == TrunkRow::A2C2F || r.mod == TrunkRow::C3, "internal: only a C2f / C3k2 / ELAN / A2C2f / C3 block reads an upsampled source in place (model.%d)", i);
     switch (r.mod) {
       case TrunkRow::CONV:
         if (i == 0) { out[i] = stem(img, front); break; }
+        if (net_.tensor(name(i) + ".conv.weight").shape.size() == 4 && net_.tensor(name(i) + ".conv.weight").shape[2] == 1) {   // yolov5.yaml's Conv(c, 1, 1)
+          out[i] = conv(name(i) + ".conv", x, 1, place(i, x.h, x.w), nullptr);
+          break;
+        }
         out[i] = conv(name(i) + ".conv", x, 2, place(i, (x.h - 1) / 2 + 1, (x.w - 1) / 2 + 1), nullptr);
+        break;
+      case TrunkRow::C3:
+        out[i] = c3(name(i), x, r.shortcut, place(i, x.h, x.w), up_src[f] >= 0 ? &out[up_src[f]] : nullptr);
         break;
       case TrunkRow::BLOCK:
         out[i] = c2f(name(i), x, r.shortcut, place(i, x.h, x.w), up_src[f] >= 0 ? &out[up_src[f]] : nullptr);
@@ -740,6 +829,11 @@ void YoloTrunk::run_op(const Op& op, int nb, hipStream_t s) const {
       conv_launch(op.grp, op.cfg, s);
       break;
     case Op::STEM:
+      if (op.stem_k == 6) {
+        launch_stem6(dtype_ == DT_F32 ? fmt : dtype_, op.in.ptr, nb, op.in.h, op.in.w, op.w27, op.bias, op.wpk, op.out.c, op.out.ptr, op.out.h, op.out.w, s,
+                     op.stem_scale);
+        break;
+      }
       launch_stem(dtype_ == DT_F32 ? fmt : dtype_, op.in.ptr, nb, op.in.h, op.in.w, op.w27, op.bias, op.wpk, op.out.c, op.out.ptr, op.out.h,
                   op.out.w, s, op.stem_scale);
       break;
@@ -789,7 +883,7 @@ void set_batch_op(Op& op, int nb, size_t es, bool pad_skip_on) {
       }
     }
   } else if (op.kind == Op::STEM) {
-    op.flops = 2.0 * nb * op.out.h * op.out.w * op.out.c * 27;
+    op.flops = 2.0 * nb * op.out.h * op.out.w * op.out.c * 3 * op.stem_k * op.stem_k;
     op.bytes = (double)nb * ((double)op.in.h * op.in.w * 4 + (double)op.out.h * op.out.w * op.out.c * es);   // RGB0 bytes in
   } else if (op.kind == Op::POOL) {
     op.flops = 0;

@@ -19,7 +19,8 @@ struct Op : OpInfo {
   ConvConfig cfg{};
   // STEM / POOL / UPSAMPLE parameters
   View in, out;
-  const float* w27 = nullptr;
+  const float* w27 = nullptr;        // the stem's weights, tap-major: [27][c0], or [108][c0] for stem_k = 6
+  int stem_k = 3;                    // STEM: 3 (Conv 3x3 / 2 / pad 1) or 6 (yolov5.yaml's Conv 6x6 / 2 / pad 2, stem6.hpp)
   const float* bias = nullptr;
   const void* wpk = nullptr;   // fp16 MFMA / split-f16x3 stem weights
   float stem_scale = 1.f;      // split-f16x3 stem: inverse of the weights' power-of-two scaling
@@ -51,10 +52,10 @@ class YoloTrunk {
   struct Levels {
     std::vector<View> in;        // the Detect row's inputs, finest level first (a table without one: its last layer's output)
     std::vector<float> strides;  // net height / level height
-    std::string det_pfx;         // the Detect row: model.22 (yolov8.yaml), model.28 (yolov8-p2.yaml) or model.23 (yolo11.yaml, yolov10.yaml, yolo26.yaml) or model.21 (yolo12.yaml)
+    std::string det_pfx;         // the Detect row: model.22 (yolov8.yaml), model.28 (yolov8-p2.yaml) or model.23 (yolo11.yaml, yolov10.yaml, yolo26.yaml) or model.21 (yolo12.yaml) or model.24 (yolov5.yaml)
     bool dw_cls = false;         // TrunkGraph::dw_cls
   };
-  // The graph the tensors were built from, by their names: yolo12.yaml, yolov10.yaml, yolo26.yaml, yolo11.yaml, yolov9.yaml, yolov8-p2.yaml, else yolov8.yaml
+  // The graph the tensors were built from, by their names: yolov5.yaml, yolo12.yaml, yolov10.yaml, yolo26.yaml, yolo11.yaml, yolov9.yaml, yolov8-p2.yaml, else yolov8.yaml
   TrunkGraph choose_graph() const;
   static TrunkGraph cls_backbone();   // model.0-8 of yolov8.yaml = yolov8-cls.yaml's backbone
   // The classification graph the tensors were built from: yolo11-cls.yaml (model.0-8 of yolo11.yaml + C2PSA = model.9), else cls_backbone()
@@ -84,6 +85,9 @@ class YoloTrunk {
 
  private:
   View stem(const View& img, bool front);
+  View stem6(const View& img);                                                                                   // yolov5.yaml's 6x6 stem
+  void read_upsampled(Op& op, const View& x, const View& up_src);
+  View c3(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src);    // yolov5.yaml's C3
   View c2f(const std::string& pfx, const View& x, bool shortcut, const View* out_slice, const View* up_src);   // C2f and C3k2
   // one stride-1 Conv op with activation `act`; channel counts that are no multiple of 16 are zero-padded (YOLO11-n's 8-channel hidden layer).
   // in_seg > 0: x is segments of in_seg channels, each followed by its zero padding up to a multiple of 16 (a concat of padded maps)

@@ -142,6 +142,7 @@ _SIGNATURES = {
     "gtx_op_conv2d_time": (C.c_int, [_P, C.POINTER(ConvDesc), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
     "gtx_op_conv2d_fused": (C.c_int, [_P, C.POINTER(ConvDesc), C.POINTER(ConvFused), _P, _P, _P, _P, _P]),
     "gtx_op_stem": (C.c_int, [_P] + [C.c_int] * 6 + [_P, _P, _P, _P]),
+    "gtx_op_stem6": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P, _P, _P, C.c_int, C.POINTER(C.c_float)]),
     "gtx_op_conv_xcd_ranges": (C.c_int, [C.c_int, _P, _P, _P, _P]),
     "gtx_op_sppf_pool": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gtx_op_upsample2x": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int]),

@@ -139,6 +139,10 @@ class YOLO:
             from .weights import check_yolo12
 
             graph += check_yolo12(self.tensors)
+        if graph == "yolov5u":                            # ultralytics builds the *u files from yolov5n.yaml ... yolov5x.yaml
+            from .weights import check_yolov5u
+
+            graph = "yolov5" + check_yolov5u(self.tensors)
         if graph == "yolov9":                             # yolov9t.yaml / yolov9s.yaml / yolov9m.yaml / yolov9c.yaml
             from .weights import check_yolov9
 

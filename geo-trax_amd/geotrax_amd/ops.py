@@ -158,6 +158,24 @@ def stem(img: np.ndarray, w27: np.ndarray, bias: np.ndarray, *, dtype, packed: b
     return out
 
 
+def stem6(img: np.ndarray, w108: np.ndarray, bias: np.ndarray, *, dtype, iters: int = 0, ctx: _lib.Context | None = None):
+    """yolov5.yaml's stem launch (model.0) on img [n,h,w,4] RGB0 bytes: SiLU(conv 6x6 stride 2 pad 2 of img / 255 + bias), w108 [108,c0]
+    with row (ky * 6 + kx) * 3 + colour. dtype: GTX_F16 (the fp16 matrix-core kernel; fp16 out), GTX_F32 (the exact-fp32 kernel) or
+    GTX_F32S (the split-f16x3 kernel; the values its pair-format output holds, as fp32). Returns the output [n,(h-2)//2+1,(w-2)//2+1,c0],
+    or (output, milliseconds per launch over `iters` further launches) with iters > 0."""
+    ctx = ctx or _lib.default_context()
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    w108 = np.ascontiguousarray(w108, dtype=np.float32)
+    bias = np.ascontiguousarray(bias, dtype=np.float32)
+    n, h, w, four = img.shape
+    c0 = w108.shape[1]
+    assert four == 4 and w108.shape == (108, c0) and bias.shape == (c0,)
+    out = np.zeros((n, max((h - 2) // 2 + 1, 0), max((w - 2) // 2 + 1, 0), c0), np.float16 if dtype == GTX_F16 else np.float32)
+    ms = C.c_float(0.0)
+    check(ctx.lib.gtx_op_stem6(ctx.handle, int(dtype), n, h, w, c0, ptr(img), ptr(w108), ptr(bias), ptr(out), int(iters), C.byref(ms)))
+    return (out, ms.value) if iters > 0 else out
+
+
 def conv2d_time(dtype, n, h, w, cin, cout, ksize, stride, iters=20, ctx=None):
     """Mean kernel time (ms) and algorithmic FLOPs of one conv launch on zero-filled data."""
     ctx = ctx or _lib.default_context()

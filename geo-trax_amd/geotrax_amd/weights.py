@@ -203,6 +203,33 @@ YOLO12_YAML = YOLO11_YAML[:6] + [                          # 12/yolo12.yaml: 22 
     (-1, 2, "C3k2", (1024, True)),                         # 20
     ((14, 17, 20), 1, "Detect", ("nc",)),                  # 21: YOLO11's Detect
 ]
+YOLOV5_YAML = [                                            # v5/yolov5.yaml, what the yolov5{n,s,m,l,x}u files are built from: 25 layers
+    (-1, 1, "Conv", (64, 6, 2, 2)),                        # 0: (c2, k, s, p): the 6x6 stem
+    (-1, 1, "Conv", (128, 3, 2)),
+    (-1, 3, "C3", (128,)),
+    (-1, 1, "Conv", (256, 3, 2)),
+    (-1, 6, "C3", (256,)),
+    (-1, 1, "Conv", (512, 3, 2)),
+    (-1, 9, "C3", (512,)),
+    (-1, 1, "Conv", (1024, 3, 2)),
+    (-1, 3, "C3", (1024,)),
+    (-1, 1, "SPPF", (1024, 5)),                            # 9
+    (-1, 1, "Conv", (512, 1, 1)),                          # 10: 1x1, stride 1
+    _UP,
+    ((-1, 6), 1, "Concat", (1,)),
+    (-1, 3, "C3", (512, False)),                           # 13
+    (-1, 1, "Conv", (256, 1, 1)),                          # 14
+    _UP,
+    ((-1, 4), 1, "Concat", (1,)),
+    (-1, 3, "C3", (256, False)),                           # 17
+    (-1, 1, "Conv", (256, 3, 2)),
+    ((-1, 14), 1, "Concat", (1,)),
+    (-1, 3, "C3", (512, False)),                           # 20
+    (-1, 1, "Conv", (512, 3, 2)),
+    ((-1, 10), 1, "Concat", (1,)),
+    (-1, 3, "C3", (1024, False)),                          # 23
+    ((17, 20, 23), 1, "Detect", ("nc",)),                  # 24: YOLOv8's Detect
+]
 YOLOV8_CLS_YAML = _V8_BACKBONE + [(-1, 1, "Classify", ("nc",))]
 YOLO11_CLS_YAML = YOLO11_YAML[:9] + [                      # model.0-8 of yolo11.yaml; no SPPF
     (-1, 2, "C2PSA", (1024,)),                             # 9
@@ -278,6 +305,17 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False, a2_residual=Fa
         for j in range(n):
             bottleneck(f"{m}.m.{j}", h, 1.0)
 
+    def c3_block(pfx, cin, cout, n):
+        """C3(c1, c2, n, shortcut, e = 0.5) of yolov5.yaml: cv1 / cv2 1x1 to c_ = c2 / 2, both on the input, cv3 1x1 on the two, then n
+        Bottleneck(c_, c_, k = (1x1, 3x3), e = 1.0) behind cv1 -- in the module's own order"""
+        c = int(cout * 0.5)
+        conv(pfx + ".cv1.conv", cin, c, 1)
+        conv(pfx + ".cv2.conv", cin, c, 1)
+        conv(pfx + ".cv3.conv", 2 * c, cout, 1)
+        for k in range(n):
+            conv(f"{pfx}.m.{k}.cv1.conv", c, c, 1)
+            conv(f"{pfx}.m.{k}.cv2.conv", c, c, 3)
+
     def ablock(m, c, mlp_ratio):
         """ABlock(c, heads = c / 32, mlp_ratio, area): AAttn's qkv / proj / pe (depthwise 7x7), none with an activation, then the two-conv mlp"""
         conv(m + ".attn.qkv.conv", c, 3 * c, 1, act=False)
@@ -321,6 +359,9 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False, a2_residual=Fa
         elif mod == "C2f":
             out.append(ch(args[0]))
             c2f(pfx, cin, out[i], n)
+        elif mod == "C3":
+            out.append(ch(args[0]))
+            c3_block(pfx, cin, out[i], n)
         elif mod == "C3k2":
             out.append(ch(args[0]))
             c2f(pfx, cin, out[i], n, c3k_all or args[1], *args[2:3], attn=len(args) > 3 and bool(args[3]))
@@ -885,6 +926,116 @@ def synthetic_yolo12(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: flo
         t[name] = (gamma + 0.25 * gamma * rng.standard_normal(shp)).astype(np.float32)
     return t
 
+# --------------------------------------------------------------------------- YOLOv5u (cfg/models/v5/yolov5.yaml)
+# What `YOLO("yolov5su.pt")` is: yolov5.yaml -- a 6x6 stride-2 stem (Conv(64, 6, 2, 2)), C3 blocks (cv1 and cv2 1x1 on the block's
+# input, Bottlenecks of a 1x1 and a 3x3 behind cv1, cv3 on the two; shortcut on in the backbone, off in the neck), SPPF = model.9, a neck
+# whose 1x1 Convs (model.10 / 14) feed the Upsamples and the Concats of the way back down -- with YOLOv8's anchor-free Detect = model.24 on
+# [17, 20, 23]. 25 layers. Restated from memory of ultralytics' public source; not checked against the package (it is not installed).
+# The doubts are listed in tests/yolov5u_ref.py. Not implemented and refused by name: the P6 files (yolov5{n,s,m,l,x}6u: four Detect
+# levels, Detect = model.33), an anchor-based export of the original YOLOv5 (model.24.m.* / anchors), YOLOv3u (yolov3.yaml's Darknet
+# with the same Detect) and the -seg / -cls heads.
+
+YOLOV5_SCALES = {"n": (0.33, 0.25, 1024), "s": (0.33, 0.50, 1024), "m": (0.67, 0.75, 1024),
+                 "l": (1.00, 1.00, 1024), "x": (1.33, 1.25, 1024)}   # yolov5.yaml: depth, width, max_channels
+
+YOLOV5U_TOPOLOGY = ("yolov5u detect (yolov5{n,s,m,l,x}u from yolov5.yaml: 6x6 stem = model.0, C3 blocks, SPPF = model.9, 1x1 Convs = model.10 / 14, "
+                    "Detect = model.24 on model.17 / 20 / 23)")
+
+
+def _stem_kernel(tensors: dict) -> int:
+    """model.0's kernel side (6: yolov5.yaml's stem), 0 when there is no 4-d `model.0.conv.weight`"""
+    w = tensors.get("model.0.conv.weight")
+    return int(np.shape(w)[2]) if w is not None and np.ndim(w) == 4 and np.shape(w)[2] == np.shape(w)[3] else 0
+
+
+def is_yolov5u(tensors: dict) -> bool:
+    """True when model.0 is a 6x6 convolution and an anchor-free Detect (cv2 branch and DFL) stands at model.24: a yolov5{n,s,m,l,x}u
+    file. Which scale it is, and whether every shape is yolov5.yaml's: check_yolov5u()."""
+    return _stem_kernel(tensors) == 6 and "model.24.cv2.0.0.conv.weight" in tensors and "model.24.dfl.conv.weight" in tensors
+
+
+def _is_yolov3u(tensors: dict) -> bool:
+    """yolov3.yaml / yolov3-spp.yaml / yolov3-tiny.yaml with the anchor-free Detect: a 3x3 stem, a bare Darknet Bottleneck at model.2
+    (`model.2.cv2.conv` 3x3 and no `model.2.m.*`; tiny: no `model.2.*` convolution at all, a MaxPool at model.1) and a Detect with a DFL
+    that is neither model.22 (yolov8.yaml) nor model.24 (yolov5.yaml)"""
+    if _stem_kernel(tensors) != 3:
+        return False
+    dfl = {k.split(".")[1] for k in tensors if k.startswith("model.") and k.endswith(".dfl.conv.weight") and len(k.split(".")) == 5}
+    if not dfl or dfl & {"22", "24"}:
+        return False
+    w = tensors.get("model.2.cv2.conv.weight")
+    darknet = w is not None and np.ndim(w) == 4 and np.shape(w)[2] == 3 and "model.2.m.0.cv1.conv.weight" not in tensors
+    tiny = "model.1.conv.weight" not in tensors and "model.2.conv.weight" in tensors
+    return darknet or tiny
+
+
+def _yolov5_lookalike(tensors: dict) -> bool:
+    """A file of YOLOv5's wider family that is not a yolov5*u detect file: any other 6x6 stem (the P6 files, -seg, -cls, other Detect
+    rows), an anchor-based export (`model.<k>.anchors` / `model.24.m.0.weight`), YOLOv3u. check_yolov5u() refuses each by name."""
+    return (_stem_kernel(tensors) == 6 or "model.24.m.0.weight" in tensors or "model.24.anchors" in tensors or "model.33.m.0.weight" in tensors or
+            _is_yolov3u(tensors))
+
+
+def check_yolov5u(tensors: dict) -> str:
+    """The scale ("n" / "s" / "m" / "l" / "x") of a fused yolov5.yaml detect model with the anchor-free head; raises NotImplementedError,
+    with a message that names yolov5.yaml and what is implemented, for everything else of the family: the P6 files, an anchor-based
+    export, YOLOv3u, -seg / -cls heads, and any tensor whose shape is not what model.0's width (16 / 32 / 48 / 64 / 80 = n / s / m / l /
+    x) gives through yolov5.yaml's width, depth and max_channels. Strict like check_yolo12(): every shape is compared."""
+    only = f"of that family only {YOLOV5U_TOPOLOGY} is implemented"
+    no = lambda what: NotImplementedError(f"{what}: {only}")
+    shape = lambda n: tuple(np.shape(tensors[n])) if n in tensors else None
+    if "model.24.m.0.weight" in tensors or "model.33.m.0.weight" in tensors or any(k.startswith("model.") and k.endswith(".anchors") for k in tensors):
+        raise no("an anchor-based export of the original YOLOv5 (Detect with `anchors` and `m.{l}` output convolutions, not yolov5.yaml's "
+                 "anchor-free yolov5*u head)")
+    if _is_yolov3u(tensors):
+        raise no("a YOLOv3u checkpoint (yolov3.yaml's Darknet-53 with the anchor-free Detect; of the files that share yolov5.yaml's head)")
+    if _stem_kernel(tensors) != 6:
+        raise no("a checkpoint without yolov5.yaml's 6x6 stem")
+    if any(re.match(r"model\.\d+\.(cv4|proto)\.", k) for k in tensors):
+        raise no("a yolov5*u-seg checkpoint (yolov5.yaml with a Segment head: `cv4` / `proto` branches)")
+    if any(re.match(r"model\.\d+\.linear\.", k) for k in tensors):
+        raise no("a yolov5*u-cls checkpoint (yolov5.yaml's backbone with a Classify head)")
+    if "model.33.cv2.0.0.conv.weight" in tensors or "model.33.dfl.conv.weight" in tensors:
+        raise no("a yolov5*6u checkpoint (yolov5-p6.yaml: four Detect levels, Detect = model.33)")
+    bad = no("checkpoint with yolov5.yaml's 6x6 stem in another arrangement than yolov5.yaml's")
+    c0, nc_w = shape("model.0.conv.weight"), shape("model.24.cv3.0.2.weight")
+    if not is_yolov5u(tensors) or nc_w is None:
+        raise bad
+    scale = {16: "n", 32: "s", 48: "m", 64: "l", 80: "x"}.get(c0[0])
+    if scale is None:
+        raise bad
+    want = {n: s for n, s, _ in yolov5u_layer_specs(scale, nc_w[0])}
+    for name, shp in want.items():
+        if shape(name + ".weight") != shp:
+            raise bad
+    for k in tensors:
+        p = k.split(".")
+        if p[0] != "model" or len(p) < 2 or not p[1].isdigit():
+            continue
+        if int(p[1]) > 24:
+            raise bad
+        if p[1] == "24" and p[2] == "dfl":
+            continue
+        if k.endswith(".weight") and k[: -len(".weight")] not in want:
+            raise bad
+    return scale
+
+
+def yolov5u_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
+    """(tensor name, OIHW shape, has_act) for every conv of a fused YOLOv5u detect model (model.0 is 6x6, model.10 / 14 are 1x1)"""
+    return _scaled_specs(YOLOV5_YAML, YOLOV5_SCALES, scale, nc)
+
+
+def synthetic_yolov5u(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0, gain: float = 1.7,
+                      box_decay: float | tuple = 0.3, level_bias: tuple = (0.0, 0.0, 0.0), box_weight_scale: float = 0.3) -> dict[str, np.ndarray]:
+    """Seeded random fused weights of the YOLOv5u architecture, drawn like synthetic_yolov8's (same knobs, the draws in the order of
+    yolov5u_layer_specs), plus Detect's constant DFL convolution `model.24.dfl.conv.weight` (0 .. 15), which every real file carries and
+    is_yolov5u() asks for."""
+    t = _draw_yolov8(np.random.default_rng(seed), yolov5u_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias, box_weight_scale)
+    t["model.24.dfl.conv.weight"] = np.arange(16, dtype=np.float32).reshape(1, 16, 1, 1)
+    return t
+
+
 # --------------------------------------------------------------------------- YOLOv9 (cfg/models/v9/yolov9{t,s,m,c}.yaml)
 # The GELAN networks: ELAN1 / RepNCSPELAN4 blocks (cv1 1x1 -> two chunks; cv2 and cv3 are Sequential(RepCSP, Conv3x3) -- plain Conv3x3
 # in ELAN1 -- each on the output before it; cv4 1x1 on the four pieces), AConv (avg_pool2d(2, 1) then a 3x3 stride-2 Conv; scales t / s /
@@ -1139,7 +1290,7 @@ RTDETR_TOPOLOGIES = ("rtdetr-l (HGNetv2 + AIFI + CCFM, RTDETRDecoder = model.28)
 
 def detector_topology(tensors: dict) -> tuple[str, str]:
     """(graph, head prefix) of a detector checkpoint, read off the tensor names the way the reference reads its model yaml:
-    ("yolov8", "model.22"), ("yolov8-p2", "model.28"), ("yolo11", "model.23"), ("yolov10", "model.23"), ("yolo26", "model.23"), ("yolo12", "model.21"), ("yolov9", "model.22"), ("rtdetr-l", "model.28") or
+    ("yolov8", "model.22"), ("yolov8-p2", "model.28"), ("yolo11", "model.23"), ("yolov10", "model.23"), ("yolo26", "model.23"), ("yolo12", "model.21"), ("yolov9", "model.22"), ("yolov5u", "model.24"), ("rtdetr-l", "model.28") or
     ("yolov8-rtdetr", "model.22").
     An RT-DETR layout other than those two (rtdetr-x with its decoder at model.32, ResNet backbones, ...) raises NotImplementedError,
     and so does a file with YOLO11's, YOLOv10's, YOLO12's or YOLO26's blocks (attention, a depthwise Detect class branch, SCDown + a one-to-one head,
@@ -1160,6 +1311,9 @@ def detector_topology(tensors: dict) -> tuple[str, str]:
         if _has_gelan(tensors):                            # is_yolov9, or GELAN blocks without model.9.cv5: yolov9e, which check_yolov9 refuses by name
             check_yolov9(tensors)
             return "yolov9", "model.22"
+        if is_yolov5u(tensors) or _yolov5_lookalike(tensors):   # asked last, in front of the YOLOv8 default only: no other family's route changes
+            check_yolov5u(tensors)                         # raises for the P6 files, an anchor-based export, YOLOv3u, -seg / -cls, a wrong shape
+            return "yolov5u", "model.24"
         return ("yolov8-p2", "model.28") if is_yolov8_p2(tensors) else ("yolov8", "model.22")
     decs = sorted({k.split(".")[1] for k in tensors if k.startswith("model.") and ".decoder.layers." in k and k.split(".")[2] == "decoder"})
     has = lambda pfx: any(k.startswith(pfx) for k in tensors)

@@ -94,7 +94,9 @@ extern "C" {
  *     gtx_op_homography_refit (the host refit that ends every robust homography, on host arrays) added: a new entry point only, so
  *     the number stays.
  *     gtx_op_area_attention added and arch 0 also takes YOLO12 tensors (yolo12.yaml: A2C2f blocks with area attention, Detect =
- *     model.21; the tensors tell the graph, gtx_det_config is unchanged): a new entry point only, so the number stays. */
+ *     model.21; the tensors tell the graph, gtx_det_config is unchanged): a new entry point only, so the number stays.
+ *     gtx_op_stem6 added and arch 0 also takes YOLOv5u tensors (yolov5.yaml with the anchor-free Detect = model.24: a 6x6 stem, C3
+ *     blocks; the tensors tell the graph, gtx_det_config is unchanged): a new entry point only, so the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -419,6 +421,13 @@ int gtx_op_conv2d_fused(gtx_ctx* ctx, const gtx_conv_desc* d, const gtx_conv_fus
  * kernels on their packed weights. c0 must be 16, 32, 48, 64, 80 or 96; h, w >= 1. */
 int gtx_op_stem(gtx_ctx* ctx, int dtype, int packed, int n, int h, int w, int c0, const void* img, const float* w27,
                 const float* bias, void* out);
+/* yolov5.yaml's stem, ultralytics' Conv(3, c0, 6, 2, 2) + SiLU on `im / 255` (F.conv2d(x, w, b, stride=2, padding=2)): img [n][h][w][4]
+ * RGB0 bytes, w108 [108][c0] fp32 with row (ky * 6 + kx) * 3 + colour, bias [c0], out [n][(h-2)/2+1][(w-2)/2+1][c0] (fp16 for GTX_F16,
+ * else fp32; GTX_F32S: the values the pair format holds). GTX_F16 and GTX_F32S: the matrix-core kernels on their packed weights (K = 108
+ * padded with zero taps to 112); GTX_F32: the exact-fp32 kernel. c0 must be 16, 32, 48, 64, 80 or 96; h, w >= 2. iters > 0:
+ * *ms_per_launch = mean time of that many further launches (may be NULL). */
+int gtx_op_stem6(gtx_ctx* ctx, int dtype, int n, int h, int w, int c0, const void* img, const float* w108, const float* bias, void* out,
+                 int iters, float* ms_per_launch);
 /* Host only (no GPU call): how a grouped convolution launch is cut over the 8 XCDs. n_members problems of
  * blocks[i] workgroups with cin[i] input channels each, in launch order. xcd_begin[0..8]: hardware block b takes
  * logical block xcd_begin[b & 7] + (b >> 3) and exits when that reaches xcd_begin[(b & 7) + 1]; the ranges hold equal

@@ -31,6 +31,11 @@ A YOLO12 detect checkpoint (yolo12{n,s,m,l,x}.yaml: `model.6.m.0.0.attn.qkv.conv
 every Conv + BatchNorm pair of its A2C2f blocks (qkv, proj, the depthwise 7x7 pe, the mlp pair, the C3k members) is folded by fold_bn
 like any other, and the `model.6.gamma` / `model.8.gamma` vectors of scales l / x are written as they are.
 
+A YOLOv5u detect checkpoint (yolov5{n,s,m,l,x}u.pt, built from yolov5{n,s,m,l,x}.yaml: a 6x6 `model.0.conv`, Detect = model.24 with its
+`dfl`) goes through the plain branch too: the 6x6 stem, the C3 blocks' cv1 / cv2 / cv3 and 1x1 + 3x3 Bottlenecks and the neck's 1x1
+Convs are Conv + BatchNorm pairs folded by fold_bn like any other. The P6 files (yolov5*6u), an anchor-based export of the original
+YOLOv5, YOLOv3u and the -seg / -cls heads are refused by name when the file is loaded (geotrax_amd.weights.check_yolov5u).
+
 A YOLO26 detect checkpoint (yolo26{n,s,m,l,x}.yaml: `model.22.m.0.1.attn.qkv.*`, 4-row `model.23.*cv2.<l>.2`) takes the same branch: every
 Conv + BN pair is folded under its own name (model.22's `m.<k>.0.cv1` Bottleneck and `m.<k>.1.attn.*` / `ffn.*` PSABlock convolutions
 included; it has no RepVGGDW), cv2 / cv3 stay next to one2one_cv2 / one2one_cv3, and `detector.meta` = [family 26, one-to-many kept,
