@@ -4,6 +4,7 @@
 // arrays with op_staging.hpp, launches as the product launches, and copies the results back. The hooks of file-local kernels
 // (op_gmc_* in gmc.hip, op_ecc_* in ecc.hip, op_orb_match in stabilizer.hip, op_orb_ransac in homography.hip, op_sift_* in sift.hip) keep their staging beside the kernels and have only their checks here.
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -60,9 +61,13 @@ struct ConvOpState {
   int ho = 0, wo = 0;
 };
 
-// force_kc > 0 pins the K chunk (conv_pick_config); y_plain: the output buffer is plain fp32 whatever d->dtype (ConvProblem::out_plain)
+// force_kc > 0 pins the K chunk (conv_pick_config); y_plain: the output buffer is plain fp32 whatever d->dtype (ConvProblem::out_plain).
+// res_cstride > 0: the residual array has that many channels per pixel and the launch adds the slice at res_coff (0: [..][cout]).
+// in_place: y_init is the one array behind input, residual and output; it is uploaded once and all three pointers are that buffer
+// (gtx_op_conv2d_fused has checked the slices).
 void conv_setup(gtx_ctx* ctx, const gtx_conv_desc* d, const void* x, const float* w, const float* bias,
-                const void* residual, const void* y_init, ConvOpState& st, int force_kc = 0, bool y_plain = false) {
+                const void* residual, const void* y_init, ConvOpState& st, int force_kc = 0, bool y_plain = false,
+                int res_cstride = 0, int res_coff = 0, bool in_place = false) {
   using namespace gtx;
   need(ctx, "ctx"); need(d, "desc");
   GTX_HIP(hipSetDevice(ctx->device));
@@ -85,7 +90,9 @@ void conv_setup(gtx_ctx* ctx, const gtx_conv_desc* d, const void* x, const float
   unsigned long long lcg = 0x2545F4914F6CDD1Dull;
   const bool all_zero = std::getenv("GTX_TIME_ZEROS") != nullptr;   // the old behaviour, to show the difference
   auto uni = [&]() { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; return all_zero ? 0.f : (float)((lcg >> 40) * (1.0 / 8388608.0) - 1.0); };
-  if (x) {
+  if (in_place) {
+    need(y_init, "y");                               // st.x stays empty: `in` is the output buffer
+  } else if (x) {
     upload_fmt(st.x, d->dtype, x, xin);
   } else if (es == 2) {
     std::vector<_Float16> hx(xin / 2);
@@ -114,19 +121,20 @@ void conv_setup(gtx_ctx* ctx, const gtx_conv_desc* d, const void* x, const float
     zeros(st.b, padded);
     GTX_HIP(hipMemcpy(st.b.p, bias, d->cout * sizeof(float), hipMemcpyHostToDevice));
   }
-  if (d->has_residual) {
-    const size_t rb = (size_t)d->n * st.ho * st.wo * d->cout * es;
+  const int rcs = res_cstride > 0 ? res_cstride : d->cout;
+  if (d->has_residual && !in_place) {
+    const size_t rb = (size_t)d->n * st.ho * st.wo * rcs * es;
     if (residual) upload_fmt(st.r, d->dtype, residual, rb);
     else zeros(st.r, rb);
   }
   ConvProblem& p = st.g.p[0];
-  p.in = st.x.p; p.out = st.y.p; p.wpack = st.w.p;
+  p.in = in_place ? st.y.p : st.x.p; p.out = st.y.p; p.wpack = st.w.p;
   p.bias = bias ? st.b.as<float>() : nullptr;
-  p.res = d->has_residual ? st.r.p : nullptr;
+  p.res = d->has_residual ? (in_place ? st.y.p : st.r.p) : nullptr;
   p.N = d->n; p.H = d->h; p.W = d->w; p.Ho = st.ho; p.Wo = st.wo; p.Cin = d->cin; p.Cout = d->cout;
   p.in_cstride = d->in_cstride; p.in_coff = d->in_coff;
   p.out_cstride = d->out_cstride; p.out_coff = d->out_coff;
-  p.res_cstride = d->cout; p.res_coff = 0;
+  p.res_cstride = rcs; p.res_coff = res_cstride > 0 ? res_coff : 0;
   p.act = d->act;
   p.acc_scale = acc_scale;
   p.in2 = nullptr; p.in2_cstride = p.in2_coff = p.c_split = 0;
@@ -198,6 +206,17 @@ int gtx_op_conv_xcd_ranges(int n_members, const int* blocks, const int* cin, int
   });
 }
 
+int gtx_op_conv_config(int dtype, int ksize, int stride, int cin, int cout, int force_kc, int* form, int* bn, int* kc, char* name, int name_cap) {
+  return guarded([&] {
+    need(form, "form"); need(bn, "bn"); need(kc, "kc");
+    if (dtype != GTX_F16 && dtype != GTX_F32 && dtype != GTX_F32S) op_bad("conv_config", "dtype: GTX_F16, GTX_F32 or GTX_F32S");
+    if (cin < 1 || cout < 1 || force_kc < 0 || (name && name_cap < 1)) op_bad("conv_config", "cin, cout and name_cap must be positive, force_kc not negative");
+    const gtx::ConvConfig c = gtx::conv_pick_config(dtype, ksize, stride, cin, cout, force_kc);
+    *form = (int)c.variant; *bn = c.bn; *kc = c.kc;
+    if (name) std::snprintf(name, (size_t)name_cap, "%s", gtx::conv_kernel_name(c));
+  });
+}
+
 int gtx_op_conv2d_time(gtx_ctx* ctx, const gtx_conv_desc* d, int iters, float* ms_per_launch, double* flops) {
   return guarded([&] {
     need(ms_per_launch, "ms_per_launch");
@@ -230,11 +249,28 @@ int gtx_op_conv2d_fused(gtx_ctx* ctx, const gtx_conv_desc* d, const gtx_conv_fus
       if (d->n < 1 || f->front_h < 1 || f->front_w_px < 1 || d->cin < 1 || d->cin > 1024) op_bad("conv2d_fused", "front stage: bad sizes");
     }
     if (f->force_kc < 0 || f->members < 0 || f->members > gtx::kMaxGroup) op_bad("conv2d_fused", "bad force_kc / members");
+    // a residual slice as the kernels address it: 4 elements per load (whole 8-channel groups in the pair format), inside its stride
+    const int rvn = pairs ? 8 : 4;
+    if (f->res_cstride < 0 || f->res_coff < 0 || (f->res_cstride == 0 && f->res_coff != 0) || (f->res_cstride > 0 && !d->has_residual))
+      op_bad("conv2d_fused", "residual slice: res_cstride / res_coff must not be negative and need a residual");
+    if (f->res_cstride > 0 && (d->cout < 1 || (long)f->res_coff + d->cout > f->res_cstride || f->res_cstride % rvn || f->res_coff % rvn))
+      op_bad("conv2d_fused", "the residual's channel slice does not fit its stride (4-element alignment, whole 8-channel groups on the split-f16x3 path)");
+    if (f->in_place) {
+      if (f->in_place != 1 || d->stride != 1 || (d->ksize != 1 && d->ksize != 3) || f->x2 || f->front_img || f->post_w || f->out_plain)
+        op_bad("conv2d_fused", "in_place: a plain stride-1 launch (no second source, fused stage or plain output)");
+      if (x != y || (d->has_residual && residual != y)) op_bad("conv2d_fused", "in_place: x, residual and y must be the same array");
+      if (d->cin < 1 || d->cout < 1 || d->in_coff < 0 || d->out_coff < 0 || d->in_cstride != d->out_cstride ||
+          (d->has_residual && f->res_cstride != d->out_cstride))
+        op_bad("conv2d_fused", "in_place: input, residual and output share one channel stride");
+      const auto meets = [&](long a, long na) { return a < (long)d->out_coff + d->cout && (long)d->out_coff < a + na; };
+      if (meets(d->in_coff, d->cin) || (d->has_residual && meets(f->res_coff, d->cout)))
+        op_bad("conv2d_fused", "in_place: the input and residual channels must not overlap the output's");
+    }
     // the fused stages belong to the 32x32x16 kernel and its 16-channel chunks (yolo_trunk.cpp: YoloTrunk::conv)
     const int force_kc = f->force_kc > 0 ? f->force_kc : ((f->post_w || f->front_img) ? 16 : 0);
     const bool plain = f->out_plain != 0;
     ConvOpState st;
-    conv_setup(ctx, d, x, w_ohwi, bias, residual, y, st, force_kc, plain);
+    conv_setup(ctx, d, x, w_ohwi, bias, residual, y, st, force_kc, plain, f->res_cstride, f->res_coff, f->in_place != 0);
     gtx::ConvProblem& p = st.g.p[0];
     gtx::DevBuf x2, sat, pw, pb, fimg, fw, fb, mid;
     gtx::ConvGroup g2{};                                // post_separate: the 1x1 layer as a launch of its own

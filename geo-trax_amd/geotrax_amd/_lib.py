@@ -32,7 +32,8 @@ class ConvFused(C.Structure):
     _fields_ = [("x2", C.c_void_p), ("in2_cstride", C.c_int), ("in2_coff", C.c_int), ("c_split", C.c_int), ("out_plain", C.c_int),
                 ("sat", C.POINTER(C.c_int)), ("post_w", C.c_void_p), ("post_bias", C.c_void_p), ("post_act", C.c_int), ("post_separate", C.c_int),
                 ("front_img", C.c_void_p), ("front_w27", C.c_void_p), ("front_bias", C.c_void_p), ("front_h", C.c_int),
-                ("front_w_px", C.c_int), ("ty_first", C.c_int), ("ty_count", C.c_int), ("force_kc", C.c_int), ("members", C.c_int)]
+                ("front_w_px", C.c_int), ("ty_first", C.c_int), ("ty_count", C.c_int), ("force_kc", C.c_int), ("members", C.c_int),
+                ("res_cstride", C.c_int), ("res_coff", C.c_int), ("in_place", C.c_int)]
 
 
 class DetConfig(C.Structure):
@@ -144,6 +145,7 @@ _SIGNATURES = {
     "gtx_op_stem": (C.c_int, [_P] + [C.c_int] * 6 + [_P, _P, _P, _P]),
     "gtx_op_stem6": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P, _P, _P, C.c_int, C.POINTER(C.c_float)]),
     "gtx_op_conv_xcd_ranges": (C.c_int, [C.c_int, _P, _P, _P, _P]),
+    "gtx_op_conv_config": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int)] * 3 + [C.c_char_p, C.c_int]),
     "gtx_op_sppf_pool": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gtx_op_upsample2x": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
     "gtx_op_dwconv": (C.c_int, [_P] + [C.c_int] * 7 + [_P, _P, _P, C.c_int, _P, _P, _P]),

@@ -90,13 +90,16 @@ def conv2d_fused(x: np.ndarray | None, w_ohwi: np.ndarray, bias: np.ndarray | No
                  want_sat: bool = False, post_w: np.ndarray | None = None, post_bias: np.ndarray | None = None, post_act: int = 1, post_separate: bool = False,
                  front_img: np.ndarray | None = None, front_w27: np.ndarray | None = None, front_bias: np.ndarray | None = None,
                  front_hw=None, ty_first: int = 0, ty_count: int = 0, force_kc: int = 0, members: int = 0,
-                 ctx: _lib.Context | None = None):
+                 res_coff: int | None = None, in_place: bool = False, ctx: _lib.Context | None = None):
     """conv2d with the extras of gtx_conv_fused (include/gtx.h), one launch. x2 [n,h/2,w/2,cs2]: the second source, whose channels
     [in2_coff, in2_coff + c_split) upsampled 2x are the layer's first c_split input channels. post_w [cout,cout] (or [cout,1,1,cout]),
     post_bias, post_act: the fused 1x1 layer (post_separate: the same two layers as two launches, the intermediate map staying in
     HBM in the pair format). front_img [n,H,W,4] RGB0 bytes, front_w27 [27,cin], front_bias: the fused stem; x may
     then be None and the layer's input map is in_shape = (n, h, w) (default: half of front_img's sides); front_hw overrides the image
-    size told to the launcher. Returns the output, or (output, sat) with want_sat."""
+    size told to the launcher. res_coff (not None): residual is [n,ho,wo,rcs] and the launch adds its channels [res_coff, res_coff + cout).
+    in_place (stride 1): x is the one buffer [n,h,w,cs] behind input, residual (channels from res_coff, when given) and output (channels
+    from out_coff); a copy of it is handed over once and comes back with the output slice written. Returns the output, or (output, sat)
+    with want_sat."""
     ctx = ctx or _lib.default_context()
     w = np.ascontiguousarray(w_ohwi, dtype=np.float32)
     cout, k, _, wcin = w.shape
@@ -115,16 +118,25 @@ def conv2d_fused(x: np.ndarray | None, w_ohwi: np.ndarray, bias: np.ndarray | No
         raise TypeError("split=True needs float32 activations")
     pad = k // 2
     ho, wo = (h + 2 * pad - k) // stride + 1, (wd + 2 * pad - k) // stride + 1
-    if out is None:
+    if in_place:
+        assert x is not None and out is None and residual is None, "in_place: x is the one buffer"
+        x = out = np.array(x, order="C")                                   # the caller's array stays as it is
+    elif out is None:
         out = np.zeros((n, ho, wo, cout), dtype=dt)
-    out = np.array(out, dtype=dt, order="C")
+    else:
+        out = np.array(out, dtype=dt, order="C")
     assert out.shape[:3] == (n, ho, wo)
+    has_res = residual is not None or (in_place and res_coff is not None)
     d = ConvDesc(dtype=GTX_F32S if split else (GTX_F16 if dt == np.float16 else GTX_F32), n=n, h=h, w=wd, cin=cin, cout=cout, ksize=k,
                  stride=stride, act=int(act), in_cstride=cs, in_coff=in_coff, out_cstride=out.shape[3], out_coff=out_coff,
-                 has_residual=int(residual is not None))
+                 has_residual=int(has_res))
     f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
     addr = lambda a: None if a is None else a.ctypes.data
     b, r = f32(bias), (None if residual is None else np.ascontiguousarray(residual, dtype=dt))
+    if in_place and has_res:
+        r = out
+    assert r is None or r.shape[:3] == (n, ho, wo)
+    assert res_coff is None or has_res, "res_coff needs a residual"
     x2a = None if x2 is None else np.ascontiguousarray(x2, dtype=dt)
     pw, pb, fw, fb = f32(post_w), f32(post_bias), f32(front_w27), f32(front_bias)
     fi = None if front_img is None else np.ascontiguousarray(front_img, dtype=np.uint8)
@@ -137,7 +149,8 @@ def conv2d_fused(x: np.ndarray | None, w_ohwi: np.ndarray, bias: np.ndarray | No
     f = _lib.ConvFused(x2=addr(x2a), in2_cstride=0 if x2a is None else x2a.shape[3], in2_coff=in2_coff, c_split=c_split, out_plain=int(out_plain),
                        sat=C.pointer(sat) if want_sat else None, post_w=addr(pw), post_bias=addr(pb), post_act=int(post_act), post_separate=int(post_separate),
                        front_img=addr(fi), front_w27=addr(fw), front_bias=addr(fb), front_h=fh, front_w_px=fwp, ty_first=ty_first,
-                       ty_count=ty_count, force_kc=force_kc, members=members)
+                       ty_count=ty_count, force_kc=force_kc, members=members, res_cstride=0 if res_coff is None else r.shape[3],
+                       res_coff=res_coff or 0, in_place=int(in_place))
     check(ctx.lib.gtx_op_conv2d_fused(ctx.handle, C.byref(d), C.byref(f), ptr(x), ptr(w), ptr(b), ptr(r), ptr(out)))
     return (out, sat.value) if want_sat else out
 
@@ -365,6 +378,19 @@ def clahe(gray: np.ndarray, ctx=None) -> np.ndarray:
     out = np.empty_like(g)
     check(ctx.lib.gtx_op_clahe(ctx.handle, ptr(g), g.shape[0], g.shape[1], ptr(out)))
     return out
+
+
+CONV_FORMS = ("Staged", "Split", "K32", "K32S2")      # gtx_op_conv_config's *form
+
+
+def conv_config(dtype: int, ksize: int, stride: int, cin: int, cout: int, force_kc: int = 0):
+    """The kernel a convolution of this shape is given (host only; the GTX_K32 / GTX_K32S2 switches as every launch reads them).
+    dtype: GTX_F16, GTX_F32 or GTX_F32S. -> (form, one of CONV_FORMS; cout tile; K chunk; kernel name)."""
+    lib = _lib.load()
+    form, bn, kc = C.c_int(-1), C.c_int(), C.c_int()
+    name = C.create_string_buffer(128)
+    check(lib.gtx_op_conv_config(int(dtype), ksize, stride, cin, cout, force_kc, C.byref(form), C.byref(bn), C.byref(kc), name, len(name)))
+    return CONV_FORMS[form.value], bn.value, kc.value, name.value.decode()
 
 
 def conv_xcd_ranges(blocks, cin):

@@ -96,7 +96,10 @@ extern "C" {
  *     gtx_op_area_attention added and arch 0 also takes YOLO12 tensors (yolo12.yaml: A2C2f blocks with area attention, Detect =
  *     model.21; the tensors tell the graph, gtx_det_config is unchanged): a new entry point only, so the number stays.
  *     gtx_op_stem6 added and arch 0 also takes YOLOv5u tensors (yolov5.yaml with the anchor-free Detect = model.24: a 6x6 stem, C3
- *     blocks; the tensors tell the graph, gtx_det_config is unchanged): a new entry point only, so the number stays. */
+ *     blocks; the tensors tell the graph, gtx_det_config is unchanged): a new entry point only, so the number stays.
+ *     gtx_op_conv_config added (host only: the kernel a convolution shape is given) and gtx_conv_fused.{res_cstride, res_coff,
+ *     in_place} appended at the struct's end (a residual read as a channel slice, and one buffer behind x, residual and y; 0 =
+ *     every earlier behaviour), as gtx_det_config.end2end was: the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -411,6 +414,10 @@ typedef struct gtx_conv_fused {
   int ty_first, ty_count;  /* as gtx_op_conv2d_group */
   int force_kc;            /* > 0: the K chunk (16 or 32) instead of the library's pick; a post or front stage pins 16 by itself */
   int members;             /* > 1: the problem is put into the group that many times (a launcher's rule on the group size) */
+  int res_cstride, res_coff; /* res_cstride > 0: residual is [n][ho][wo][res_cstride] and the launch adds its channels [res_coff, res_coff + cout),
+                              as the trunk's bottlenecks read a chunk of their concat buffer; 0 (with res_coff 0): residual is [n][ho][wo][cout] */
+  int in_place;            /* 1 (stride 1, no other extra): x, residual (if any) and y are ONE host array [n][h][w][cs], uploaded once; the launch
+                              reads, adds and writes channel slices of that one device buffer. Input and residual slices must not meet the output's */
 } gtx_conv_fused;
 /* gtx_op_conv2d with the extras of *f; x may be NULL under a front stage (the kernel does not read it). */
 int gtx_op_conv2d_fused(gtx_ctx* ctx, const gtx_conv_desc* d, const gtx_conv_fused* f, const void* x, const float* w_ohwi,
@@ -433,6 +440,11 @@ int gtx_op_stem6(gtx_ctx* ctx, int dtype, int n, int h, int w, int c0, const voi
  * logical block xcd_begin[b & 7] + (b >> 3) and exits when that reaches xcd_begin[(b & 7) + 1]; the ranges hold equal
  * work (blocks weighted by their K depth), not equal counts. grid_blocks = 8 x the longest range. */
 int gtx_op_conv_xcd_ranges(int n_members, const int* blocks, const int* cin, int xcd_begin[9], int* grid_blocks);
+/* Host only (no GPU call): the kernel a convolution of this shape is given (force_kc as gtx_conv_fused's; the GTX_K32 / GTX_K32S2 switches
+ * are read as every launch reads them). *form: 0 the register-staged kernel (fp16, exact fp32), 1 split-f16x3 on 32x32x16, 2 its 3x3
+ * stride-1 form on 16x16x32, 3 its 3x3 stride-2 form on 16x16x32; *bn: the cout tile; *kc: the input channels per K chunk; name (may be
+ * NULL): the kernel's symbol with its template arguments, cut to name_cap bytes. A shape no kernel takes is an error. */
+int gtx_op_conv_config(int dtype, int ksize, int stride, int cin, int cout, int force_kc, int* form, int* bn, int* kc, char* name, int name_cap);
 
 /* SPPF max-pool cascade (three 5x5/s1/p2 pools of ultralytics SPPF.forward): reads channels
  * [0,c) of x and writes the 5x5, 9x9 and 13x13 window maxima to channels [c,2c), [2c,3c),

@@ -248,6 +248,55 @@ def test_front_hooks_refuse_null_arguments_and_bad_sizes_before_any_launch():
     assert fused(_lib.ConvFused(force_kc=-16)) == -1 and b"force_kc" in lib.gtx_last_error()
     assert fused(_lib.ConvFused(members=9)) == -1 and b"members" in lib.gtx_last_error()
     assert fused(_lib.ConvFused()) == -1 and b"ctx is NULL" in lib.gtx_last_error()                    # nothing asked for: gtx_op_conv2d
+    # the residual as a channel slice: it needs a residual, fits its stride, and starts on 4 elements (whole 8-channel groups in the pair format)
+    assert fused(_lib.ConvFused(res_cstride=192, res_coff=64)) == -1 and b"residual slice" in lib.gtx_last_error()
+    for bad in (dict(res_cstride=0, res_coff=8), dict(res_cstride=-64), dict(res_cstride=64, res_coff=-8)):
+        assert fused(_lib.ConvFused(**bad), res=f, desc=dr) == -1 and b"residual slice" in lib.gtx_last_error(), bad
+    for bad in (dict(res_cstride=64, res_coff=8), dict(res_cstride=32, res_coff=0), dict(res_cstride=196, res_coff=64), dict(res_cstride=192, res_coff=4)):
+        assert fused(_lib.ConvFused(**bad), res=f, desc=dr) == -1 and b"does not fit its stride" in lib.gtx_last_error(), bad
+    assert fused(_lib.ConvFused(res_cstride=192, res_coff=64), res=f, desc=dr) == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    d16 = _lib.ConvDesc(dtype=0, n=1, h=8, w=8, cin=32, cout=64, ksize=3, stride=2, act=1, in_cstride=32, in_coff=0, out_cstride=64, out_coff=0, has_residual=1)
+    assert fused(_lib.ConvFused(res_cstride=72, res_coff=4), res=f, desc=d16) == -1 and b"ctx is NULL" in lib.gtx_last_error()   # fp16: 4 elements do
+    assert fused(_lib.ConvFused(res_cstride=72, res_coff=2), res=f, desc=d16) == -1 and b"does not fit its stride" in lib.gtx_last_error()
+    # in place: one array behind x, residual and y, a plain stride-1 launch, one stride, input and residual clear of the output's channels
+    ip = lambda res=0, **kw: _lib.ConvDesc(**{**dict(dtype=2, n=1, h=8, w=8, cin=32, cout=32, ksize=3, stride=1, act=0, in_cstride=96, in_coff=0,
+                                                     out_cstride=96, out_coff=64, has_residual=res), **kw})
+    slice1 = dict(in_place=1, res_cstride=96, res_coff=32)
+    assert fused(_lib.ConvFused(in_place=1), desc=ip()) == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(**slice1), res=f, desc=ip(1)) == -1 and b"ctx is NULL" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(in_place=1), desc=ip(stride=2)) == -1 and b"in_place: a plain stride-1 launch" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(in_place=2), desc=ip()) == -1 and b"in_place: a plain stride-1 launch" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(in_place=1, out_plain=1), desc=ip()) == -1 and b"in_place: a plain stride-1 launch" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(in_place=1), y=img, desc=ip()) == -1 and b"same array" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(**slice1), res=img, desc=ip(1)) == -1 and b"same array" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(in_place=1), desc=ip(out_cstride=128)) == -1 and b"one channel stride" in lib.gtx_last_error()
+    assert fused(_lib.ConvFused(in_place=1), res=f, desc=ip(1)) == -1 and b"one channel stride" in lib.gtx_last_error()      # a [..][cout] residual
+    for bad in (dict(in_coff=32, cin=64), dict(in_coff=64), dict(out_coff=24), dict(out_coff=0)):
+        assert fused(_lib.ConvFused(in_place=1), desc=ip(**bad)) == -1 and b"must not overlap" in lib.gtx_last_error(), bad
+    assert fused(_lib.ConvFused(in_place=1, res_cstride=96, res_coff=40), res=f, desc=ip(1)) == -1 and b"must not overlap" in lib.gtx_last_error()
+
+
+def test_conv_config_hook_is_host_only_and_refuses_bad_arguments():
+    """Host only: gtx_op_conv_config takes no context; it answers a class with its kernel's name, and NULL outputs, a dtype or sizes out
+    of range and a shape no kernel takes with an error code."""
+    from geotrax_amd import _lib
+
+    lib = _lib.load()
+    form, bn, kc = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    name = C.create_string_buffer(96)
+    cfg = lambda dtype=2, ks=3, stride=1, cin=48, cout=64, force_kc=0, fo=form, nm=name, cap=96: lib.gtx_op_conv_config(
+        dtype, ks, stride, cin, cout, force_kc, C.byref(fo) if fo is not None else None, C.byref(bn), C.byref(kc), nm, cap)
+    assert cfg() == 0 and (form.value, bn.value, kc.value) == (1, 64, 16) and name.value == b"conv_igemm_split_kernel<3, 1, 2, 2, 1>"
+    assert cfg(dtype=0, ks=1, cin=64) == 0 and (form.value, bn.value, kc.value) == (0, 64, 64) and name.value == b"conv_igemm_kernel<_Float16, 1, 1, 2, 8>"
+    assert cfg(nm=None, cap=0) == 0
+    assert cfg(cap=8) == 0 and name.value == b"conv_ig"                                                 # cut, and terminated
+    assert cfg(fo=None) == -1 and b"form is NULL" in lib.gtx_last_error()
+    assert cfg(dtype=3) == -1 and b"dtype" in lib.gtx_last_error()
+    assert cfg(cin=0) == -1 and cfg(cout=-16) == -1 and cfg(force_kc=-1) == -1 and cfg(cap=0) == -1
+    assert cfg(ks=5) < 0 and b"unsupported kernel" in lib.gtx_last_error()
+    assert cfg(ks=1, stride=2) < 0 and b"unsupported kernel" in lib.gtx_last_error()
+    assert cfg(cin=24) < 0 and b"K chunk" in lib.gtx_last_error()
+    assert cfg(cout=24) < 0 and b"multiple of 16" in lib.gtx_last_error()
 
 
 def test_head_hooks_refuse_bad_sizes_before_any_launch():
