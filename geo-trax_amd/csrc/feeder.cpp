@@ -34,6 +34,7 @@
 #include "geometry.hpp"
 #include "jpeg.hpp"
 #include "jpeg_entropy.hpp"
+#include "jpeg_restart.hpp"
 
 struct gtx_feeder {
   gtx_ctx ctx;                       // device + the copy stream
@@ -59,10 +60,17 @@ struct gtx_feeder {
   // the pixel kernels and copies the frame's status word back; next() sends a frame whose status is not 0 to the host parser.
   std::unique_ptr<gtx::JpegEntropy> entropy;
   gtx::DevBuf dev_plan, fb_rec, fb_planes;   // the plan in HBM; record and planes of a frame next() decodes again on the host
-  std::vector<uint8_t> slot_tag;     // [ring*B] what the pinned slot holds: 0 a record, 1 a plan
+  std::vector<uint8_t> slot_tag;     // [ring*B] what the pinned slot holds: 0 a record, 1 a plan, 2 an interval plan, 3 a record the restart route handed back
   std::vector<std::vector<uint8_t>> slot_src;   // [ring*B] the compressed bytes of the slot's frame
   uint32_t* h_status = nullptr;      // pinned [ring*B][2]: the entropy chain's status and rounds used
   std::atomic<int64_t> stats[3] = {{0}, {0}, {0}};   // frames decoded by the GPU / by the host because plan() said so / by the host after a GPU status
+  // JPEG, the restart-interval route (gtx_feeder_set_jpeg_restart): a frame that has a restart interval gets an interval plan
+  // (jpeg::plan_intervals()) in its slot, whichever way the other frames go. The uploader copies the plans of a batch side by
+  // side into HBM and, when the batch is complete, decodes all their intervals in one launch (csrc/jpeg_restart.hip).
+  std::unique_ptr<gtx::JpegRestart> restart;
+  gtx::DevBuf rs_plan, rs_rec;       // [B][src_bytes] each: the batch's interval plans and their records
+  uint32_t* h_rstatus = nullptr;     // pinned [ring*B]: the restart chain's status
+  std::atomic<int64_t> rstats[3] = {{0}, {0}, {0}};   // frames decoded by the interval route / handed back to the reader thread / decoded again after a GPU status
   int64_t dead_from = -1;            // next(): the batch a frame of which the host parser refused too; nothing from it on is delivered
   std::map<int64_t, std::string> bad;   // JPEG only: frames that could not be decoded; the uploader reports one when it reaches it
   std::vector<int64_t> offsets;      // file mode: payload offset of every frame to deliver, in delivery order
@@ -97,6 +105,7 @@ struct gtx_feeder {
     for (auto e : ev) (void)hipEventDestroy(e);
     if (pinned) (void)hipHostFree(pinned);
     if (h_status) (void)hipHostFree(h_status);
+    if (h_rstatus) (void)hipHostFree(h_rstatus);
     if (fd >= 0) ::close(fd);
     if (one_fd >= 0) ::close(one_fd);
     if (!own_stream) ctx.stream = nullptr;   // ~gtx_ctx must not destroy a borrowed stream
@@ -140,11 +149,29 @@ struct gtx_feeder {
   // route words that refusal) are decoded here as on the host route.
   bool fill_slot(int64_t i, const uint8_t* data, size_t len, std::string& why) {
     const size_t s = slot_of(i);
-    if (!entropy) return decode_into_slot(i, data, len, why);
+    if (!entropy && !restart) return decode_into_slot(i, data, len, why);
     slot_tag[s] = 0;
     gtx::jpeg::Info info;
     size_t needed = 0;
     char msg[512];
+    if (restart) {
+      // Only bad or odd frames pay twice here, and harmlessly: where a marker is out of place plan_intervals() has already run the
+      // parser's scan to word its refusal and decode_into_slot() below runs parse() once more, so that the message is the host
+      // route's whatever the cause; a frame of another size had its plan written into the slot before parse() writes over it.
+      const int rc = gtx::jpeg::plan_intervals(data, len, (long long)i, &info, pinned + s * src_bytes, src_bytes, &needed, msg, sizeof msg);
+      if (rc == gtx::jpeg::kOk && info.height == h && info.width == w) {
+        if (slot_src[s].data() != data) slot_src[s].assign(data, data + len);
+        slot_len[s] = (uint32_t)needed;
+        slot_tag[s] = 2;
+        return true;
+      }
+      if (rc != gtx::jpeg::kNoRestart) {                       // refused, too large for the slot or of another size: the host route decodes it or words the refusal
+        const bool ok = decode_into_slot(i, data, len, why);
+        if (ok) slot_tag[s] = 3;
+        return ok;
+      }
+      if (!entropy) return decode_into_slot(i, data, len, why);
+    }
     const int rc = gtx::jpeg::plan(data, len, (long long)i, &info, pinned + s * src_bytes, src_bytes, &needed, msg, sizeof msg);
     if (rc < 0) {
       why = msg;
@@ -182,7 +209,7 @@ struct gtx_feeder {
         if (stop) return;
       }
       const size_t len = (size_t)lengths[(size_t)i];
-      std::vector<uint8_t>& buf = entropy ? slot_src[slot_of(i)] : own;   // the GPU route keeps the bytes with the slot
+      std::vector<uint8_t>& buf = (entropy || restart) ? slot_src[slot_of(i)] : own;   // the GPU route keeps the bytes with the slot
       buf.resize(len);
       std::string why;
       size_t got = 0;
@@ -251,12 +278,17 @@ struct gtx_feeder {
     for (int k = 0; k < count; ++k) {
       const int64_t i = j * B + k;
       const size_t s = slot_of(i);
-      if (slot_tag[s] != 1) {                                   // the reader thread decoded it: plan() handed it back
-        ++stats[1];
+      const int tag = slot_tag[s];
+      if (tag == 3) {                                           // the restart route handed it back to its reader thread
+        ++rstats[1];
         continue;
       }
-      if (h_status[2 * s] == 0) {
-        ++stats[0];
+      if (tag == 0) {                                           // the reader thread decoded it: plan() handed it back (or the host route is on)
+        if (entropy) ++stats[1];
+        continue;
+      }
+      if ((tag == 2 ? h_rstatus[s] : h_status[2 * s]) == 0) {
+        ++(tag == 2 ? rstats[0] : stats[0]);
         continue;
       }
       std::string why;
@@ -265,7 +297,7 @@ struct gtx_feeder {
         set_error(why);
         gtx::fail(GTX_ERR_INTERNAL, "%s", why.c_str());
       }
-      ++stats[2];
+      ++(tag == 2 ? rstats[2] : stats[2]);
       if (!fb_rec.p) fb_rec.alloc(src_bytes), fb_planes.alloc(64 * gtx::jpeg::max_blocks(h, w));
       gtx::jpeg::RecordHeader hd;
       memcpy(&hd, pinned + s * src_bytes, sizeof hd);
@@ -281,6 +313,10 @@ struct gtx_feeder {
   // when the end of the source is known)
   void upload_loop() {
     if (hipSetDevice(ctx.device) != hipSuccess) return set_error("hipSetDevice failed on the feeder's upload thread");
+    std::vector<int64_t> pending;                               // the batch's frames on the restart-interval route
+    std::vector<const uint8_t*> rs_plans;
+    std::vector<uint8_t*> rs_recs;
+    std::vector<gtx::jpeg::PlanHeader> rs_phs;
     try {
       for (int64_t i = 0;; ++i) {
         bool end;
@@ -303,7 +339,11 @@ struct gtx_feeder {
         if (!end) {
           const size_t s = slot_of(i);
           uint8_t* bgr = dev.as<uint8_t>() + s * bgr_bytes;
-          if (kind == 2 && entropy && slot_tag[s] == 1) {
+          if (kind == 2 && restart && slot_tag[s] == 2) {       // decoded with the rest of its batch, below
+            const size_t k = (size_t)(i % B);
+            GTX_HIP(hipMemcpyAsync(rs_plan.as<uint8_t>() + k * src_bytes, pinned + s * src_bytes, slot_len[s], hipMemcpyHostToDevice, ctx.stream));
+            pending.push_back(i);
+          } else if (kind == 2 && entropy && slot_tag[s] == 1) {
             gtx::jpeg::PlanHeader ph;
             memcpy(&ph, pinned + s * src_bytes, sizeof ph);
             GTX_HIP(hipMemcpyAsync(dev_plan.p, pinned + s * src_bytes, slot_len[s], hipMemcpyHostToDevice, ctx.stream));   // the plan at its real length
@@ -325,6 +365,22 @@ struct gtx_feeder {
         }
         if (end || i % B == B - 1) {
           const int64_t j = end ? (i - 1) / B : i / B;
+          if (!pending.empty()) {                                // every interval of the batch's restart frames in one launch
+            rs_plans.clear(), rs_recs.clear(), rs_phs.clear();
+            for (const int64_t fi : pending) {
+              const size_t k = (size_t)(fi % B);
+              gtx::jpeg::PlanHeader ph;
+              memcpy(&ph, pinned + slot_of(fi) * src_bytes, sizeof ph);
+              rs_plans.push_back(rs_plan.as<const uint8_t>() + k * src_bytes), rs_recs.push_back(rs_rec.as<uint8_t>() + k * src_bytes), rs_phs.push_back(ph);
+            }
+            restart->enqueue((int)pending.size(), rs_plans.data(), rs_phs.data(), rs_recs.data());
+            for (size_t q = 0; q < pending.size(); ++q) {
+              const size_t fs = slot_of(pending[q]);
+              gtx::jpeg_decode_launch(&ctx, rs_recs[q], gtx::JpegEntropy::record_header(rs_phs[q]), dev_planes.p, dev.as<uint8_t>() + fs * bgr_bytes);
+              GTX_HIP(hipMemcpyAsync(h_rstatus + fs, restart->d_result((int)q), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx.stream));
+            }
+            pending.clear();
+          }
           GTX_HIP(hipEventRecord(ev[(size_t)(j % ring)], ctx.stream));
           {
             std::lock_guard<std::mutex> lk(m);
@@ -482,6 +538,34 @@ int gtx_feeder_set_jpeg_entropy(gtx_feeder* f, int gpu) {
   });
 }
 
+int gtx_feeder_set_jpeg_restart(gtx_feeder* f, int on) {
+  return guarded([&] {
+    if (!f) gtx::fail(GTX_ERR_INVALID, "feeder_set_jpeg_restart: feeder is NULL");
+    if (f->kind != 2) gtx::fail(GTX_ERR_INVALID, "feeder_set_jpeg_restart: the feeder was created with kind %d, not 2", f->kind);
+    if (f->fd >= 0 || f->one_fd >= 0 || !f->paths.empty() || f->uploader.joinable()) gtx::fail(GTX_ERR_INVALID, "feeder_set_jpeg_restart: the feeder already has a source");
+    if (!on) {
+      f->restart.reset();
+      return;
+    }
+    if (f->restart) return;
+    GTX_HIP(hipSetDevice(f->ctx.device));
+    const size_t slots = (size_t)f->ring * f->B;
+    if (!f->h_rstatus) GTX_HIP(hipHostMalloc((void**)&f->h_rstatus, slots * sizeof(uint32_t), hipHostMallocDefault));
+    f->rs_plan.alloc((size_t)f->B * f->src_bytes);
+    f->rs_rec.alloc((size_t)f->B * f->src_bytes);
+    if (f->slot_tag.size() != slots) f->slot_tag.assign(slots, 0);
+    if (f->slot_src.size() != slots) f->slot_src.assign(slots, std::vector<uint8_t>());
+    f->restart.reset(new gtx::JpegRestart(&f->ctx, f->B, gtx::jpeg::max_blocks(f->h, f->w)));
+  });
+}
+
+int gtx_feeder_jpeg_restart_stats(gtx_feeder* f, int64_t out[3]) {
+  return guarded([&] {
+    if (!f || !out) gtx::fail(GTX_ERR_INVALID, "feeder_jpeg_restart_stats: NULL argument");
+    for (int k = 0; k < 3; ++k) out[k] = f->rstats[k].load();
+  });
+}
+
 int gtx_feeder_jpeg_stats(gtx_feeder* f, int64_t out[3]) {
   return guarded([&] {
     if (!f || !out) gtx::fail(GTX_ERR_INVALID, "feeder_jpeg_stats: NULL argument");
@@ -589,7 +673,7 @@ int gtx_feeder_next(gtx_feeder* f, void** dptr, int* n, int64_t* batch_index) {
     if (f->issued > f->handed && (f->dead_from < 0 || f->handed < f->dead_from)) {   // batches that arrived before a failure are still delivered
       const int64_t j = f->handed;
       const int count = (int)((f->n_frames >= 0 && (j + 1) * f->B > f->n_frames) ? f->n_frames - j * f->B : f->B);
-      if (f->entropy) {                                // the GPU entropy route: the batch's status words decide who decoded it
+      if (f->entropy || f->restart) {                  // a GPU entropy route: the batch's status words decide who decoded it
         lk.unlock();
         try {
           f->settle_batch(j, count);

@@ -20,6 +20,7 @@
 #include "jpeg.hpp"
 #include "jpeg_enc.hpp"
 #include "jpeg_entropy.hpp"
+#include "jpeg_restart.hpp"
 #include "register.hpp"
 #include "sift.hpp"
 #include "sift_stab.hpp"
@@ -871,6 +872,96 @@ int gtx_jpeg_entropy_ms(gtx_ctx* ctx, const void* plan, size_t bytes, int sub_bi
     GTX_HIP(hipMemcpy(res, dec.d_result(), sizeof res, hipMemcpyDeviceToHost));
     *status = (int)res[0], *rounds_used = (int)res[1];
   });
+}
+
+size_t gtx_jpeg_plan_intervals_bound(int h, int w) {
+  return (h <= 0 || w <= 0 || h > gtx::jpeg::kMaxDim || w > gtx::jpeg::kMaxDim) ? 0 : gtx::jpeg::plan_intervals_bound(h, w);
+}
+
+int gtx_jpeg_plan_intervals(const void* bytes, size_t n, int64_t frame, int* h, int* w, int* ncomp, int* hs, int* vs, void* out, size_t capacity,
+                            size_t* needed) {
+  int rc = 0;
+  const int st = guarded([&] {
+    need(bytes, "bytes"); need(needed, "needed");
+    if (!out && capacity) gtx::fail(GTX_ERR_INVALID, "jpeg_plan_intervals: out is NULL with a capacity of %zu", capacity);
+    gtx::jpeg::Info info;
+    char msg[512];
+    rc = gtx::jpeg::plan_intervals(static_cast<const uint8_t*>(bytes), n, (long long)frame, &info, out, capacity, needed, msg, sizeof msg);
+    if (h) *h = info.height;
+    if (w) *w = info.width;
+    if (ncomp) *ncomp = info.ncomp;
+    if (hs) *hs = info.hs;
+    if (vs) *vs = info.vs;
+    if (rc < 0) gtx::fail(rc, "%s", msg);
+  });
+  return st != GTX_OK ? st : rc;
+}
+
+int gtx_jpeg_restart_ms(gtx_ctx* ctx, const void* plan, size_t bytes, int copies, int reps, float ms[2], int* status) {
+  return guarded([&] {
+    need(plan, "plan"); need(ms, "ms"); need(status, "status");
+    char msg[256];
+    if (gtx::jpeg::check_plan_intervals(plan, bytes, msg, sizeof msg) != 0) gtx::fail(GTX_ERR_INVALID, "%s", msg);
+    if (copies < 1 || copies > 64) gtx::fail(GTX_ERR_INVALID, "jpeg_restart_ms: %d copies", copies);
+    if (reps < 1 || reps > 10000) gtx::fail(GTX_ERR_INVALID, "jpeg_restart_ms: %d repetitions", reps);
+    gtx::jpeg::PlanHeader ph;
+    memcpy(&ph, plan, sizeof ph);
+    if (ph.stream_bytes > (1u << 28)) gtx::fail(GTX_ERR_INVALID, "jpeg_restart_ms: more than 256 MB of entropy-coded data");
+    need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t nb = ph.n_blocks, rec_bytes = (gtx::jpeg::record_bytes(nb, 64 * nb) + 255) / 256 * 256, plan_bytes = (bytes + 255) / 256 * 256;
+    const gtx::jpeg::RecordHeader hd = gtx::JpegEntropy::record_header(ph);
+    gtx::DevBuf d_plan((size_t)copies * plan_bytes), d_rec((size_t)copies * rec_bytes), d_planes(gtx::jpeg::planes_bytes(hd)), d_bgr((size_t)ph.height * ph.width * 3);
+    std::vector<const uint8_t*> plans((size_t)copies);
+    std::vector<uint8_t*> recs((size_t)copies);
+    std::vector<gtx::jpeg::PlanHeader> phs((size_t)copies, ph);
+    for (int k = 0; k < copies; ++k) {
+      plans[(size_t)k] = d_plan.as<const uint8_t>() + (size_t)k * plan_bytes, recs[(size_t)k] = d_rec.as<uint8_t>() + (size_t)k * rec_bytes;
+      GTX_HIP(hipMemcpyAsync(d_plan.as<uint8_t>() + (size_t)k * plan_bytes, plan, bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    gtx::JpegRestart dec(ctx, copies, nb);
+    hipEvent_t e[3];
+    for (auto& x : e) GTX_HIP(hipEventCreate(&x));
+    double sum[2] = {0, 0};
+    try {
+      for (int r = -1; r < reps; ++r) {                          // one untimed pass first
+        GTX_HIP(hipEventRecord(e[0], ctx->stream));
+        dec.enqueue(copies, plans.data(), phs.data(), recs.data());
+        GTX_HIP(hipEventRecord(e[1], ctx->stream));
+        for (int k = 0; k < copies; ++k) gtx::jpeg_decode_launch(ctx, recs[(size_t)k], hd, d_planes.p, d_bgr.p);
+        GTX_HIP(hipEventRecord(e[2], ctx->stream));
+        GTX_HIP(hipEventSynchronize(e[2]));
+        if (r < 0) continue;
+        for (int k = 0; k < 2; ++k) {
+          float t = 0;
+          GTX_HIP(hipEventElapsedTime(&t, e[k], e[k + 1]));
+          sum[k] += t;
+        }
+      }
+    } catch (...) {
+      for (auto x : e) (void)hipEventDestroy(x);
+      throw;
+    }
+    for (auto x : e) (void)hipEventDestroy(x);
+    for (int k = 0; k < 2; ++k) ms[k] = (float)(sum[k] / reps / copies);
+    uint32_t res = 0;
+    GTX_HIP(hipMemcpy(&res, dec.d_result(0), sizeof res, hipMemcpyDeviceToHost));
+    *status = (int)res;
+  });
+}
+
+int gtx_jpeg_emit_restart(const void* record, size_t bytes, int restart_mcus, void* out, size_t capacity, size_t* n) {
+  int rc = 0;
+  const int st = guarded([&] {
+    need(record, "record"); need(n, "n");
+    if (!out && capacity) gtx::fail(GTX_ERR_INVALID, "jpeg_emit_restart: out is NULL with a capacity of %zu", capacity);
+    if (reinterpret_cast<uintptr_t>(record) & 3) gtx::fail(GTX_ERR_INVALID, "jpeg_emit_restart: the record is not 4-byte aligned");
+    if (restart_mcus < 0 || restart_mcus > 65535) gtx::fail(GTX_ERR_INVALID, "jpeg_emit_restart: a restart interval of %d MCUs (0..65535)", restart_mcus);
+    char msg[256];
+    rc = gtx::jpeg::emit_restart(record, bytes, (unsigned)restart_mcus, static_cast<uint8_t*>(out), capacity, n, msg, sizeof msg);
+    if (rc < 0) gtx::fail(rc, "%s", msg);
+  });
+  return st != GTX_OK ? st : rc;
 }
 
 int gtx_jpeg_enc_create(gtx_ctx* ctx, int h, int w, int quality, int subsampling, gtx_jpeg_enc** out) {

@@ -25,6 +25,7 @@
 #include "homography.hpp"
 #include "jpeg_enc.hpp"
 #include "jpeg_entropy.hpp"
+#include "jpeg_restart.hpp"
 #include "match_l2.hpp"
 #include "op_staging.hpp"
 #include "pool_down.hpp"
@@ -1837,6 +1838,45 @@ int gtx_op_jpeg_entropy(gtx_ctx* ctx, const void* plan, size_t bytes, int sub_bi
     GTX_HIP(hipMemcpy(&hd, d_rec.p, sizeof hd, hipMemcpyDeviceToHost));
     if (hd.n_blocks != nb || hd.n_coef > 64 * nb || hd.bytes != gtx::jpeg::record_bytes(nb, hd.n_coef))
       gtx::fail(GTX_ERR_INTERNAL, "jpeg_entropy: the device reports a record of %u bytes for %zu blocks", hd.bytes, nb);
+    *record_bytes = hd.bytes;
+    fits = capacity >= hd.bytes;
+    if (fits) download(record, d_rec, hd.bytes);
+  });
+  return st != GTX_OK ? st : fits ? 0 : 1;
+}
+
+// ---- the restart-interval decoder on a host interval plan (tests/test_jpeg_restart_gpu.py)
+
+int gtx_op_jpeg_restart(gtx_ctx* ctx, const void* plan, size_t bytes, void* record, size_t capacity, size_t* record_bytes, int* status) {
+  bool fits = true;
+  const int st = guarded([&] {
+    need(plan, "plan"); need(record_bytes, "record_bytes"); need(status, "status");
+    *record_bytes = 0, *status = 0;
+    if (!record && capacity) op_bad("jpeg_restart", "record is NULL with a capacity");
+    if (record && (reinterpret_cast<uintptr_t>(record) & 3)) op_bad("jpeg_restart", "the record buffer is not 4-byte aligned");
+    char msg[256];
+    if (gtx::jpeg::check_plan_intervals(plan, bytes, msg, sizeof msg) != 0) gtx::fail(GTX_ERR_INVALID, "%s", msg);
+    gtx::jpeg::PlanHeader ph;
+    memcpy(&ph, plan, sizeof ph);
+    if (ph.stream_bytes > (1u << 28)) op_bad("jpeg_restart", "more than 256 MB of entropy-coded data");
+    need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    const size_t nb = ph.n_blocks, bound = gtx::jpeg::record_bytes(nb, 64 * nb);
+    gtx::DevBuf d_plan, d_rec(bound);
+    upload(d_plan, plan, bytes);
+    gtx::JpegRestart dec(ctx, 1, nb);
+    const uint8_t* plans[1] = {d_plan.as<const uint8_t>()};
+    uint8_t* recs[1] = {d_rec.as<uint8_t>()};
+    dec.enqueue(1, plans, &ph, recs);
+    GTX_HIP(hipStreamSynchronize(ctx->stream));
+    uint32_t res = 0;
+    GTX_HIP(hipMemcpy(&res, dec.d_result(0), sizeof res, hipMemcpyDeviceToHost));
+    *status = (int)res;
+    if (res != 0) return;                                         // no record: the host parser says what is wrong with the frame
+    gtx::jpeg::RecordHeader hd;
+    GTX_HIP(hipMemcpy(&hd, d_rec.p, sizeof hd, hipMemcpyDeviceToHost));
+    if (hd.n_blocks != nb || hd.n_coef > 64 * nb || hd.bytes != gtx::jpeg::record_bytes(nb, hd.n_coef))
+      gtx::fail(GTX_ERR_INTERNAL, "jpeg_restart: the device reports a record of %u bytes for %zu blocks", hd.bytes, nb);
     *record_bytes = hd.bytes;
     fits = capacity >= hd.bytes;
     if (fits) download(record, d_rec, hd.bytes);

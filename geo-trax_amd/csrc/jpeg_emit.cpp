@@ -90,7 +90,8 @@ void dht(Writer& w, int cls_id, const uint8_t bits[16], const uint8_t* vals, int
 }
 
 // SOI, APP0, DQT, SOF0, DHT, SOS: everything in front of the scan (jpeg_emit.hpp: header())
-void write_header(Writer& w, const RecordHeader& hd, const uint16_t* quant) {
+// restart > 0: a DRI segment in front of SOS
+void write_header(Writer& w, const RecordHeader& hd, const uint16_t* quant, unsigned restart = 0) {
   const int ncomp = (int)hd.ncomp;
   // Cr shares Cb's table when the two are equal (what libjpeg writes), else it gets a third
   const bool third = ncomp == 3 && memcmp(quant + 64, quant + 128, 128) != 0;
@@ -117,6 +118,7 @@ void write_header(Writer& w, const RecordHeader& hd, const uint16_t* quant) {
     dht(w, 0x01, kStdDcChromaBits, kStdDcChromaVals, 12);
     dht(w, 0x11, kStdAcChromaBits, kStdAcChromaVals, 162);
   }
+  if (restart) w.u16(0xFFDD), w.u16(4), w.u16(restart);
   w.u16(0xFFDA), w.u16(6 + 2 * (unsigned)ncomp), w.byte((unsigned)ncomp);
   for (int c = 0; c < ncomp; ++c) w.byte((unsigned)c + 1), w.byte(c == 0 ? 0x00 : 0x11);
   w.byte(0), w.byte(63), w.byte(0);
@@ -164,6 +166,10 @@ void std_huff_codes(HuffCodes* out) {
 }
 
 int emit(const void* record, size_t bytes, uint8_t* out, size_t capacity, size_t* n, char* msg, size_t msg_cap) {
+  return emit_restart(record, bytes, 0, out, capacity, n, msg, msg_cap);
+}
+
+int emit_restart(const void* record, size_t bytes, unsigned restart_mcus, uint8_t* out, size_t capacity, size_t* n, char* msg, size_t msg_cap) {
   static const Tables tables;
   if (msg && msg_cap) msg[0] = 0;
   if (n) *n = 0;
@@ -171,6 +177,10 @@ int emit(const void* record, size_t bytes, uint8_t* out, size_t capacity, size_t
     if (msg && msg_cap) snprintf(msg, msg_cap, "JPEG record: %s", what);
     return kInvalid;
   };
+  if (restart_mcus > 65535u) {
+    if (msg && msg_cap) snprintf(msg, msg_cap, "JPEG emit: a restart interval of %u MCUs (DRI holds 0..65535)", restart_mcus);
+    return kInvalid;
+  }
   if (!record || bytes < sizeof(RecordHeader)) return bad("too short or misaligned");
   if (!out && capacity) return bad("no output buffer for the capacity given");
   RecordHeader hd;
@@ -186,12 +196,20 @@ int emit(const void* record, size_t bytes, uint8_t* out, size_t capacity, size_t
     if (quant[i] > 255) return bad("a quantiser above 255 (baseline tables have 8-bit entries)");
 
   Writer w{out, out ? capacity : 0};
-  write_header(w, hd, quant);
+  write_header(w, hd, quant, restart_mcus);
 
   const uint32_t luma = hd.hs * hd.vs, bpm = ncomp == 1 ? 1u : luma + 2u;
   int pred[3] = {0, 0, 0};
   uint32_t k = 0;                                                  // position inside the MCU
+  uint32_t mcu = 0;
+  unsigned next_rst = 0;
   for (uint32_t b = 0; b < hd.n_blocks; ++b) {
+    if (restart_mcus && k == 0 && mcu && mcu % restart_mcus == 0) {   // the interval's last byte padded with 1-bits, RSTn, predictors reset
+      w.flush();
+      w.u16(0xFFD0 + next_rst);
+      next_rst = (next_rst + 1) & 7;
+      pred[0] = pred[1] = pred[2] = 0;
+    }
     const int c = (ncomp == 1 || k < luma) ? 0 : 1 + (int)(k - luma);
     const EncTable &td = tables.dc[c ? 1 : 0], &ta = tables.ac[c ? 1 : 0];
     const int16_t* v = coef + off[b];
@@ -223,7 +241,7 @@ int emit(const void* record, size_t bytes, uint8_t* out, size_t capacity, size_t
     int last = len;
     while (last > 1 && v[last - 1] == 0) --last;
     if (last < 64) w.bits(ta.code[0], ta.size[0]);
-    if (++k == bpm) k = 0;
+    if (++k == bpm) k = 0, ++mcu;
   }
   w.flush();
   w.u16(0xFFD9);

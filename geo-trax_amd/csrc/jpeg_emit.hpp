@@ -27,6 +27,12 @@ bool make_header(int h, int w, int ncomp, int hs, int vs, RecordHeader* hd);
 // yields one). Every record the parser produces from 8-bit pictures is accepted: grayscale, 4:4:4, 4:2:2, 4:2:0.
 int emit(const void* record, size_t bytes, uint8_t* out, size_t capacity, size_t* n, char* msg, size_t msg_cap);
 
+// emit() with restart intervals of `restart_mcus` MCUs, so that the file decodes one lane per interval (csrc/jpeg_restart.hip): a
+// DRI segment in front of SOS and, before every MCU whose index is a multiple of restart_mcus (but the first), the pending byte
+// padded with 1-bits, RSTn (n counts 0..7 and wraps) and the DC predictors back at 0. restart_mcus = 0: emit()'s bytes exactly.
+// Above 65535 (what DRI holds): kInvalid. Everything else as emit().
+int emit_restart(const void* record, size_t bytes, unsigned restart_mcus, uint8_t* out, size_t capacity, size_t* n, char* msg, size_t msg_cap);
+
 // The picture's header alone, the bytes emit() writes in front of the scan: SOI, APP0, DQT (one table per component; Cr shares
 // Cb's when the two are equal), SOF0, DHT, SOS. It depends on the frame's size, sampling and quantisers only (hd's width, height,
 // ncomp, hs, vs; quant[3][64] in natural order), so both entropy routes call it: emit() per picture, the GPU coder

@@ -32,6 +32,7 @@
 #include "detector.hpp"
 #include "jpeg_entropy.hpp"
 #include "jpeg_scan.hpp"
+#include "jpeg_symbol.hpp"
 
 namespace gtx {
 namespace {
@@ -96,8 +97,6 @@ struct WriteSink {
   }
 };
 
-__device__ __forceinline__ int extend(uint32_t v, uint32_t s) { return v < (1u << (s - 1)) ? (int)v - (1 << s) + 1 : (int)v; }   // s in 1..15
-
 // f_lane(entry). span: the workgroup's staged words, whose first bit is stream bit span_bit0. *count: blocks that began.
 template <class Sink>
 __device__ __forceinline__ uint64_t decode_lane(const uint32_t* span, uint64_t span_bit0, const PlanHuff* tabs, const Geom& g, uint64_t lane, uint64_t entry,
@@ -113,58 +112,13 @@ __device__ __forceinline__ uint64_t decode_lane(const uint32_t* span, uint64_t s
     const PlanHuff& t = tabs[z == 0 ? c : 3u + c];
     const uint32_t q = (uint32_t)(p - span_bit0), w = q >> 5;      // w + 1 <= span_words: staged
     const uint64_t win = ((uint64_t)__builtin_bswap32(span[span_at(w)]) << 32 | __builtin_bswap32(span[span_at(w + 1)])) << (q & 31u);
-    const uint32_t top = (uint32_t)(win >> 48);
-    const uint64_t left = g.bits - p;
-    uint32_t len = 0, sym = 0;
-    const uint32_t e = t.look[top >> 7];
-    if (e) {
-      len = e >> 8, sym = e & 255u;
-    } else {
-      for (uint32_t l = 10; l <= 16; ++l) {
-        const int code = (int)(top >> (16 - l));
-        if (code <= t.maxcode[l]) {
-          const int idx = t.valoff[l] + code;
-          if (idx >= 0 && idx < (int)min(t.nvals, 256u)) len = l, sym = t.vals[idx];
-          break;
-        }
-      }
-    }
-    if (len == 0 || len > 16 || len > left) {                     // no such code, or it ends past the data
-      sink.poisoned(z == 0);
-      return kPoison;
-    }
-    if (z == 0) {                                                 // DC: the category, then that many bits
-      const uint32_t s = sym;
-      if (s > 15 || len + s > left) {
-        sink.poisoned(true);
-        return kPoison;
-      }
-      sink.begin();
-      sink.dc(s ? extend((uint32_t)((win << len) >> (64 - s)), s) : 0);
-      ++*count;
-      p += len + s, z = 1;
-      continue;
-    }
-    const uint32_t r = sym >> 4, s = sym & 15u;
-    bool done = false;
-    if (s == 0) {
-      p += len;
-      if (r != 15) done = true;                                   // EOB
-      else if ((z += 16) >= 64) done = true;                      // ZRL; the parser's loop ends without a word when it leaves the block
-    } else {
-      z += r;
-      if (z > 63 || len + s > left) {
-        sink.poisoned(false);
-        return kPoison;
-      }
-      sink.ac(z, extend((uint32_t)((win << len) >> (64 - s)), s));
-      p += len + s;
-      if (++z == 64) done = true;
-    }
-    if (done) {
-      sink.end();
-      k = k + 1 == g.bpm ? 0u : k + 1, z = 0;
-    }
+    const bool at_dc = z == 0;
+    uint32_t used;
+    const uint32_t r = jpegsym::step(t, win, g.bits - p, z, &used, sink);
+    if (r == jpegsym::kBad) return kPoison;
+    if (at_dc) ++*count;
+    p += used;
+    if (r == jpegsym::kBlockEnd) k = k + 1 == g.bpm ? 0u : k + 1, z = 0;
   }
   return pack_state(p, k, z);
 }
@@ -305,6 +259,10 @@ jpeg::RecordHeader JpegEntropy::record_header(const jpeg::PlanHeader& ph) {
   return hd;
 }
 
+void JpegEntropy::pack_launch(hipStream_t s, const uint8_t* d_plan, const jpeg::RecordHeader& hd, const int16_t* d_dense, uint8_t* d_rec, int rounds, uint32_t* d_state) {
+  hipLaunchKernelGGL(jpeg_entropy_pack_kernel, dim3((unsigned)(((size_t)hd.n_blocks * 64 + 255) / 256)), dim3(256), 0, s, d_plan, hd, d_dense, d_rec, rounds, d_state);
+}
+
 JpegEntropy::JpegEntropy(gtx_ctx* ctx, size_t max_blocks, size_t max_stream_bytes, int min_sub_bits)
     : ctx_(ctx), max_blocks_(max_blocks), max_stream_bytes_(max_stream_bytes), min_sub_bits_(min_sub_bits) {
   if (!ctx) fail(GTX_ERR_INVALID, "ctx is NULL");
@@ -367,8 +325,7 @@ void JpegEntropy::enqueue(const uint8_t* d_plan, const jpeg::PlanHeader& ph, int
                      d_lens_.as<uint32_t>(), state + kStStatus);
   uint32_t* offsets = reinterpret_cast<uint32_t*>(d_rec + jpeg::kOffsetsOffset);
   jpegscan::scan_launch<uint32_t>(s, d_lens_.as<const uint32_t>(), nb, nullptr, 64u, d_block_tiles_.as<uint32_t>(), offsets, offsets + nb);
-  hipLaunchKernelGGL(jpeg_entropy_pack_kernel, dim3((unsigned)(((size_t)nb * 64 + 255) / 256)), dim3(256), 0, s, d_plan, hd, d_dense_.as<const int16_t>(), d_rec, rounds,
-                     state);
+  pack_launch(s, d_plan, hd, d_dense_.as<const int16_t>(), d_rec, rounds, state);
   GTX_HIP(hipGetLastError());
 }
 

@@ -32,6 +32,9 @@ class JpegEntropy {
   const uint32_t* d_result() const { return d_state_.as<const uint32_t>(); }
   // The header the two pixel kernels take by value for a plan's record: n_coef is the buffer's bound, not the real count.
   static jpeg::RecordHeader record_header(const jpeg::PlanHeader& ph);
+  // jpeg_entropy_pack_kernel alone, the closing launch of both GPU entropy routes: dense runs + the record's offsets -> coef[],
+  // header and quantisers (d_plan: a plan of either format). d_state: 2 words or more, [1] receives the rounds used.
+  static void pack_launch(hipStream_t s, const uint8_t* d_plan, const jpeg::RecordHeader& hd, const int16_t* d_dense, uint8_t* d_rec, int rounds, uint32_t* d_state);
 
  private:
   gtx_ctx* ctx_;

@@ -142,6 +142,8 @@ struct Parser {
   void geometry(RecordHeader* hd) const;
   int scan(void* record, size_t capacity, size_t* needed);
   int write_plan(void* out, size_t capacity, size_t* needed);
+  void write_plan_head(uint8_t* dst, uint32_t magic, size_t total, size_t len, uint32_t n_intervals) const;
+  int write_interval_plan(void* out, size_t capacity, size_t* needed);
 };
 
 const char* sof_name(unsigned m) {
@@ -393,16 +395,22 @@ int Parser::write_plan(void* out, size_t capacity, size_t* needed) {
   if (!dst || capacity < total) return kTooSmall;
   walk(dst + kPlanStreamOffset);
   memset(dst + kPlanStreamOffset + len, 0, padded - len);
+  write_plan_head(dst, kPlanMagic, total, len, 0);
+  return kOk;
+}
+
+// The header, quantisers and tables both plan formats share, for the frame whose header segments() has walked.
+void Parser::write_plan_head(uint8_t* dst, uint32_t magic, size_t total, size_t len, uint32_t n_intervals) const {
   RecordHeader g;
   geometry(&g);
   PlanHeader ph;
   memset(&ph, 0, sizeof ph);
-  ph.magic = kPlanMagic, ph.bytes = (uint32_t)total;
+  ph.magic = magic, ph.bytes = (uint32_t)total;
   ph.width = g.width, ph.height = g.height, ph.ncomp = g.ncomp, ph.hs = g.hs, ph.vs = g.vs, ph.mcus_x = g.mcus_x, ph.mcus_y = g.mcus_y, ph.n_blocks = g.n_blocks;
   for (int c = 0; c < 3; ++c) ph.bw[c] = g.bw[c], ph.bh[c] = g.bh[c];
   ph.restart = (uint32_t)restart;
   for (int c = 0; c < ncomp; ++c) ph.td[c] = (uint32_t)scan_td[c], ph.ta[c] = (uint32_t)scan_ta[c];
-  ph.stream_bytes = (uint32_t)len, ph.stream_bits = 8 * (uint64_t)len;
+  ph.stream_bytes = (uint32_t)len, ph.stream_bits = 8 * (uint64_t)len, ph.reserved = n_intervals;
   memcpy(dst, &ph, sizeof ph);
   for (int c = 0; c < 3; ++c) memcpy(dst + kPlanQuantOffset + 128 * (size_t)c, quant[comp_tq[c < ncomp ? c : 0]], 128);
   memset(dst + kPlanHuffOffset, 0, 6 * sizeof(PlanHuff));
@@ -418,7 +426,73 @@ int Parser::write_plan(void* out, size_t capacity, size_t* needed) {
       h.nvals = (uint32_t)t.nvals;
       memcpy(dst + kPlanHuffOffset + sizeof(PlanHuff) * (size_t)(3 * cls + c), &h, sizeof h);
     }
+}
+
+// The interval plan of jpeg_parse.hpp; pos is at the first entropy-coded byte and restart > 0.
+int Parser::write_interval_plan(void* out, size_t capacity, size_t* needed) {
+  uint8_t* dst = static_cast<uint8_t*>(out);
+  RecordHeader g;
+  geometry(&g);
+  const size_t n_mcu = (size_t)g.mcus_x * g.mcus_y, n_int = interval_count(n_mcu, (size_t)restart), stream_at = interval_stream_offset(n_int);
+  // One pass measures, and only when the plan fits a second one copies. An interval is fill()'s walk, a run of plain bytes at a
+  // time: FF 00 is an FF, any other FF (or one the data ends on) ends it. Behind every interval but the last, scan()'s marker
+  // rules: at least two bytes left, FF fill bytes, then RSTn in sequence. false: scan() refuses this frame at that marker or before.
+  auto walk = [&](uint8_t* to, uint32_t* start, size_t* total) {
+    size_t len = 0, at = pos;
+    unsigned next_rst = 0;
+    for (size_t i = 0; i < n_int; ++i) {
+      if (start) start[i] = (uint32_t)len;
+      while (at < n) {
+        const uint8_t* ff = static_cast<const uint8_t*>(memchr(p + at, 0xFF, n - at));
+        const size_t run = ff ? (size_t)(ff - (p + at)) : n - at;
+        if (to && run) memcpy(to + len, p + at, run);
+        len += run, at += run;
+        if (!ff || at + 1 >= n || p[at + 1] != 0) break;
+        if (to) to[len] = 0xFF;
+        len += 1, at += 2;
+      }
+      if (i + 1 == n_int) break;
+      if (at + 1 >= n) return false;                              // "restart marker RSTn missing"
+      while (at < n && p[at] == 0xFF) ++at;
+      if (at >= n || p[at] != 0xD0 + next_rst) return false;      // missing, or out of sequence
+      ++at;
+      next_rst = (next_rst + 1) & 7;
+    }
+    if (start) start[n_int] = (uint32_t)len;
+    *total = len;
+    return true;
+  };
+  size_t len = 0;
+  if (n - pos > ((size_t)1 << 31)) fail(kUnsupported, "more than 2 GB of entropy-coded data (the interval plan's 32-bit sizes)");
+  if (!walk(nullptr, nullptr, &len)) {                            // a marker is not where the walk needs it: the parser words the refusal
+    size_t rec_needed = 0;
+    (void)scan(nullptr, 0, &rec_needed);                          // throws what parse() reports
+    fail(kInvalid, "restart markers are not where the intervals end");   // not reached: the walk applies scan()'s own marker rules
+  }
+  const size_t padded = (len + 3) / 4 * 4, total = stream_at + padded;
+  if (needed) *needed = total;
+  if (!dst || capacity < total) return kTooSmall;
+  memset(dst + kPlanStreamOffset, 0, stream_at - kPlanStreamOffset);
+  walk(dst + stream_at, reinterpret_cast<uint32_t*>(dst + kPlanStreamOffset), &len);
+  memset(dst + stream_at + len, 0, padded - len);
+  write_plan_head(dst, kIntervalPlanMagic, total, len, (uint32_t)n_int);
   return kOk;
+}
+
+// The geometry rules a plan header of either format must meet (what parse() would have produced); NULL: it does.
+const char* plan_geometry_fault(const PlanHeader& ph) {
+  const int w = (int)ph.width, h = (int)ph.height;
+  if (w <= 0 || h <= 0 || w > kMaxDim || h > kMaxDim) return "frame size";
+  if (ph.ncomp != 1 && ph.ncomp != 3) return "component count";
+  const bool samp = ph.ncomp == 1 ? (ph.hs == 1 && ph.vs == 1) : ((ph.hs == 1 && ph.vs == 1) || (ph.hs == 2 && ph.vs == 1) || (ph.hs == 2 && ph.vs == 2));
+  if (!samp) return "sampling factors";
+  if (ph.mcus_x != ((uint32_t)w + 8 * ph.hs - 1) / (8 * ph.hs) || ph.mcus_y != ((uint32_t)h + 8 * ph.vs - 1) / (8 * ph.vs)) return "MCU grid";
+  const uint32_t bpm = ph.ncomp == 1 ? 1 : ph.hs * ph.vs + 2;
+  if (ph.n_blocks != ph.mcus_x * ph.mcus_y * bpm) return "block count";
+  if (ph.bw[0] != ph.mcus_x * ph.hs || ph.bh[0] != ph.mcus_y * ph.vs) return "luma block grid";
+  for (uint32_t c = 1; c < 3; ++c)
+    if (ph.bw[c] != (c < ph.ncomp ? ph.mcus_x : 0u) || ph.bh[c] != (c < ph.ncomp ? ph.mcus_y : 0u)) return "chroma block grid";
+  return nullptr;
 }
 }  // namespace
 
@@ -506,17 +580,52 @@ int check_plan(const void* plan, size_t bytes, char* msg, size_t msg_cap) {
   if (ph.restart != 0) return bad("a restart interval");
   if (ph.stream_bytes > (1u << 31) || kPlanStreamOffset + ((size_t)ph.stream_bytes + 3) / 4 * 4 != bytes || ph.stream_bits != 8 * (uint64_t)ph.stream_bytes)
     return bad("its sizes do not add up to its length");
-  const int w = (int)ph.width, h = (int)ph.height;
-  if (w <= 0 || h <= 0 || w > kMaxDim || h > kMaxDim) return bad("frame size");
-  if (ph.ncomp != 1 && ph.ncomp != 3) return bad("component count");
-  const bool samp = ph.ncomp == 1 ? (ph.hs == 1 && ph.vs == 1) : ((ph.hs == 1 && ph.vs == 1) || (ph.hs == 2 && ph.vs == 1) || (ph.hs == 2 && ph.vs == 2));
-  if (!samp) return bad("sampling factors");
-  if (ph.mcus_x != ((uint32_t)w + 8 * ph.hs - 1) / (8 * ph.hs) || ph.mcus_y != ((uint32_t)h + 8 * ph.vs - 1) / (8 * ph.vs)) return bad("MCU grid");
-  const uint32_t bpm = ph.ncomp == 1 ? 1 : ph.hs * ph.vs + 2;
-  if (ph.n_blocks != ph.mcus_x * ph.mcus_y * bpm) return bad("block count");
-  if (ph.bw[0] != ph.mcus_x * ph.hs || ph.bh[0] != ph.mcus_y * ph.vs) return bad("luma block grid");
-  for (uint32_t c = 1; c < 3; ++c)
-    if (ph.bw[c] != (c < ph.ncomp ? ph.mcus_x : 0u) || ph.bh[c] != (c < ph.ncomp ? ph.mcus_y : 0u)) return bad("chroma block grid");
+  if (const char* what = plan_geometry_fault(ph)) return bad(what);
+  return kOk;
+}
+
+size_t plan_intervals_bound(int h, int w) {
+  const size_t blocks = max_blocks(h, w);                         // at most one interval per MCU, so at most one per block
+  return blocks ? interval_stream_offset(blocks) + ((blocks * kMaxBlockBits + 7) / 8 + blocks + 3) / 4 * 4 : 0;
+}
+
+int plan_intervals(const uint8_t* bytes, size_t n, long long frame, Info* info, void* out, size_t capacity, size_t* needed, char* msg, size_t msg_cap) {
+  if (msg && msg_cap) msg[0] = 0;
+  if (needed) *needed = 0;
+  Parser ps;
+  ps.p = bytes, ps.n = n, ps.frame = frame, ps.msg = msg, ps.msg_cap = msg_cap;
+  try {
+    if (!bytes) ps.fail(kInvalid, "no data");
+    if (out && (reinterpret_cast<uintptr_t>(out) & 3)) ps.fail(kInvalid, "the plan buffer is not 4-byte aligned");
+    ps.segments(info);
+    if (!ps.restart) return kNoRestart;
+    return ps.write_interval_plan(out, capacity, needed);
+  } catch (const Failure& f) {
+    return f.code;
+  }
+}
+
+int check_plan_intervals(const void* plan, size_t bytes, char* msg, size_t msg_cap) {
+  auto bad = [&](const char* what) {
+    if (msg && msg_cap) snprintf(msg, msg_cap, "JPEG interval plan: %s", what);
+    return kInvalid;
+  };
+  if (!plan || bytes < interval_stream_offset(1) || (reinterpret_cast<uintptr_t>(plan) & 3)) return bad("shorter than its header and tables, or misaligned");
+  PlanHeader ph;
+  memcpy(&ph, plan, sizeof ph);
+  if (ph.magic != kIntervalPlanMagic) return bad("wrong magic");
+  if (ph.bytes != bytes) return bad("its length field differs from the bytes handed in");
+  if (const char* what = plan_geometry_fault(ph)) return bad(what);
+  if (ph.restart == 0 || ph.restart > 65535u) return bad("a restart interval outside 1..65535");
+  const size_t n_int = interval_count((size_t)ph.mcus_x * ph.mcus_y, ph.restart), stream_at = interval_stream_offset(n_int);
+  if (ph.reserved != n_int) return bad("its interval count is not ceil(MCUs / restart interval)");
+  if (ph.stream_bytes > (1u << 31) || stream_at > bytes || stream_at + ((size_t)ph.stream_bytes + 3) / 4 * 4 != bytes || ph.stream_bits != 8 * (uint64_t)ph.stream_bytes)
+    return bad("its sizes do not add up to its length");
+  const uint32_t* start = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(plan) + kPlanStreamOffset);
+  if (start[0] != 0) return bad("the first interval does not start at byte 0");
+  for (size_t i = 0; i < n_int; ++i)
+    if (start[i + 1] < start[i]) return bad("interval starts are not monotone");
+  if (start[n_int] != ph.stream_bytes) return bad("the closing interval start differs from the stream length");
   return kOk;
 }
 

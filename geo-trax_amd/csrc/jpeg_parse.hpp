@@ -87,7 +87,7 @@ struct PlanHeader {
   uint32_t bw[3], bh[3];
   uint32_t restart;                          // the restart interval: 0 in every plan plan() writes
   uint32_t td[3], ta[3];                     // the SOS header's table selectors, by component
-  uint32_t stream_bytes, reserved;
+  uint32_t stream_bytes, reserved;           // reserved: 0 in a plan; the number of intervals in an interval plan (below)
   uint64_t stream_bits;                      // bits of the clean stream: 8 * stream_bytes
 };
 static_assert(sizeof(PlanHeader) == 112, "plan header layout");
@@ -110,6 +110,45 @@ int plan(const uint8_t* bytes, size_t n, long long frame, Info* info, void* out,
 // What the entropy kernels rely on in a plan: its sizes consistent with each other and with its length, a geometry parse() would
 // have produced, no restart interval. (The tables are not trusted: the kernels bound every look-up themselves.) kOk or kInvalid.
 int check_plan(const void* plan, size_t bytes, char* msg, size_t msg_cap);
+
+// ---- the restart-interval route (csrc/jpeg_restart.hip): a frame with a DRI segment, one lane per restart interval
+//
+// At every RSTn the stream is byte aligned, the DC predictors are zero and the MCU index is known, so every interval decodes on
+// its own. The host walks the header, removes the byte stuffing and the RSTn markers and notes where every interval starts.
+//
+// Interval plan (little endian, 4-byte aligned):
+//   PlanHeader                         magic kIntervalPlanMagic, restart = Ri (MCUs per interval, > 0), reserved = n_intervals;
+//                                      stream_bytes, stream_bits of the whole clean stream
+//   uint16 quant[3][64], PlanHuff huff[6]   as in the plan above
+//   uint32 start[n_intervals + 1]      byte offset of every interval in the clean stream; start[n_intervals] = stream_bytes.
+//                                      n_intervals = ceil(mcus_x * mcus_y / Ri)
+//   zeros up to a multiple of 16
+//   uint8  stream[stream_bytes]        the intervals back to back: stuffing removed, markers and their fill bytes removed;
+//                                      zeros up to a multiple of 4 follow
+constexpr uint32_t kIntervalPlanMagic = 0x3249474au;   // "JGI2": check_plan() refuses it, check_plan_intervals() refuses a "JGP1"
+constexpr int kNoRestart = 3;                 // plan_intervals(): the frame has no restart interval; nothing is written
+
+inline size_t interval_count(size_t n_mcus, size_t restart) { return restart ? (n_mcus + restart - 1) / restart : 0; }
+// Offset of the clean stream in an interval plan of n_intervals intervals (16-byte aligned).
+inline size_t interval_stream_offset(size_t n_intervals) { return (kPlanStreamOffset + 4 * (n_intervals + 1) + 15) / 16 * 16; }
+// Largest interval plan a decodable frame of h x w can need (one interval per MCU, every block kMaxBlockBits long and every
+// interval's last byte padded).
+size_t plan_intervals_bound(int h, int w);
+
+// plan() for a frame that has a restart interval. The header walk and every refusal up to and including the SOS header are
+// parse()'s, with the same status and message. The entropy-coded segment is then walked with memchr: an interval ends at the
+// first FF that no 00 follows, where RSTn (after any FF fill bytes) must stand in sequence, RST7 followed by RST0; the last
+// interval ends at the first marker or with the data, as the parser's bit reader does. Where a marker is missing, out of
+// sequence or the data ends early, the Huffman decode of parse() runs to word the refusal: the status and message are
+// parse()'s by construction. Returns kOk (plan written), kTooSmall (not written: call again with *needed bytes), kNoRestart
+// (*needed is 0, nothing is written, *info is filled), kUnsupported or kInvalid. No byte outside bytes[0, n) is read, none
+// outside out[0, capacity) written.
+int plan_intervals(const uint8_t* bytes, size_t n, long long frame, Info* info, void* out, size_t capacity, size_t* needed, char* msg, size_t msg_cap);
+
+// What the restart kernel relies on in an interval plan: the geometry rules of check_plan(), restart in 1..65535,
+// n_intervals = ceil(n_mcus / restart), start[0] = 0, start[] monotone, start[n_intervals] = stream_bytes, and sizes that add up
+// to the length. (The tables are not trusted: the kernel bounds every look-up itself.) kOk or kInvalid.
+int check_plan_intervals(const void* plan, size_t bytes, char* msg, size_t msg_cap);
 
 // What the device code relies on: sizes consistent with each other and with h x w, offsets monotone, every block at most 64
 // long, the closing offset equal to the stream length, the record exactly `bytes` long. kOk or kInvalid with a message.

@@ -336,6 +336,13 @@ _SIGNATURES = {
     "gtx_jpeg_entropy_ms": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gtx_feeder_set_jpeg_entropy": (C.c_int, [_P, C.c_int]),
     "gtx_feeder_jpeg_stats": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "gtx_jpeg_plan_intervals_bound": (C.c_size_t, [C.c_int, C.c_int]),
+    "gtx_jpeg_plan_intervals": (C.c_int, [_P, C.c_size_t, C.c_int64] + [C.POINTER(C.c_int)] * 5 + [_P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gtx_op_jpeg_restart": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "gtx_jpeg_restart_ms": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "gtx_feeder_set_jpeg_restart": (C.c_int, [_P, C.c_int]),
+    "gtx_feeder_jpeg_restart_stats": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "gtx_jpeg_emit_restart": (C.c_int, [_P, C.c_size_t, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "gtx_jpeg_enc_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "gtx_jpeg_enc_destroy": (None, [_P]),
     "gtx_jpeg_enc_submit_dev": (C.c_int, [_P, _P]),

@@ -306,6 +306,7 @@ def track_with_model_sharded(model: YOLO, config: dict, logger: logging.Logger) 
 
                 def open_on(fd_, frames, threads):
                     fd_.set_jpeg_entropy(eng_cfg.get('jpeg_entropy', 'host'))      # `engine: {jpeg_entropy: gpu}`: Huffman decode on the copy stream
+                    fd_.set_jpeg_restart(eng_cfg.get('jpeg_restart', 'host'))      # `engine: {jpeg_restart: gpu}`: restart-interval frames, one lane per interval
                     fd_.open_jpeg((paths, findex[frames], offsets[frames], lengths[frames]), n_threads=threads or int(eng_cfg.get('decode_threads', 8)))
             B, n_dets = engine.B, len(engine.dets)
             mine = [f for start, stop in runs for f in range(start, stop)]
@@ -418,6 +419,7 @@ def _read_ahead_batches(reader, engine, eng_cfg: dict, first: int, last, frame_n
         paths, findex, offsets, lengths = reader.jpeg_layout()
         feeder = FrameFeeder(reader.frame_hw, kind="jpeg", batch=engine.B, ring=ring, device=engine.device, ctx=engine.feeder_ctx)
         feeder.set_jpeg_entropy(eng_cfg.get('jpeg_entropy', 'host'))      # `engine: {jpeg_entropy: gpu}`: Huffman decode on the copy stream
+        feeder.set_jpeg_restart(eng_cfg.get('jpeg_restart', 'host'))      # `engine: {jpeg_restart: gpu}`: restart-interval frames, one lane per interval
         feeder.open_jpeg((paths, findex[first:stop], offsets[first:stop], lengths[first:stop]), n_threads=int(eng_cfg.get('decode_threads', 8)))
         frame_nums.extend(range(first, max(stop, first)))
     else:

@@ -68,6 +68,14 @@ class FrameFeeder:
             raise ValueError(f"jpeg entropy route {entropy!r}: 'host' or 'gpu'")
         check(self.lib.gtx_feeder_set_jpeg_entropy(self.handle, 1 if entropy == "gpu" else 0))
 
+    def set_jpeg_restart(self, route: str) -> None:
+        """Where the frames of a "jpeg" feeder that have a restart interval are Huffman-decoded, before the source is opened:
+        "host" (as every other frame goes) or "gpu" (one lane per restart interval, csrc/jpeg_restart.hip). Independent of
+        set_jpeg_entropy(); frames without a restart interval are not affected."""
+        if route not in ("host", "gpu"):
+            raise ValueError(f"jpeg restart route {route!r}: 'host' or 'gpu'")
+        check(self.lib.gtx_feeder_set_jpeg_restart(self.handle, 1 if route == "gpu" else 0))
+
     def open_jpeg(self, layout, n_threads: int = 8, entropy: str | None = None) -> None:
         """`layout`: (paths, file_index, offsets, lengths) of a reader's jpeg_layout(), or a slice of it: frame i is lengths[i]
         bytes at offsets[i] of paths[file_index[i]]. `n_threads` library threads read and entropy-decode the frames (a
@@ -84,6 +92,13 @@ class FrameFeeder:
             raise ValueError("jpeg layout: file_index, offsets and lengths differ in length")
         arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
         check(self.lib.gtx_feeder_open_jpeg(self.handle, arr, len(paths), _lib.ptr(idx), _lib.ptr(off), _lib.ptr(ln), len(off), int(n_threads)))
+
+    def jpeg_restart_stats(self) -> tuple[int, int, int]:
+        """Frames of a "jpeg" feeder the restart-interval route decoded / handed back to a reader thread / had the host parser
+        decode again after a GPU status. jpeg_stats() counts none of them. All 0 with set_jpeg_restart("host")."""
+        out = (C.c_int64 * 3)()
+        check(self.lib.gtx_feeder_jpeg_restart_stats(self.handle, out))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def jpeg_stats(self) -> tuple[int, int, int]:
         """Frames of a "jpeg" feeder whose entropy decode ran on the GPU / on the host because the frame is not for the GPU route

@@ -861,3 +861,255 @@ def entropy_plan_dev(ctx: _lib.Context, plan: np.ndarray, sub_bits: int = 0, rou
     if rc != 0:
         raise JpegError(rc, lib.gtx_last_error().decode("utf-8", "replace"))
     return status.value, (rec[:n.value] if status.value == 0 else None), used.value
+
+
+# ------------------------------------------------------------------------------------- restart intervals, one lane per interval
+# csrc/jpeg_restart.hip decodes a frame that has a restart interval from an interval plan (gtx_jpeg_plan_intervals: header walk,
+# stuffing and RSTn markers removed, the start of every interval noted; layout in csrc/jpeg_parse.hpp). At every RSTn the stream is
+# byte aligned, the DC predictors are zero and the MCU index is known, so a lane needs nothing from the others.
+# restart_decode_twin() restates the kernel's rule with every index asserted; emit() is the host emitter with restart markers.
+
+INTERVAL_PLAN_MAGIC = 0x3249474A
+RESTART_INVALID = 1                                                    # status bit
+NO_RESTART = 3                                                         # gtx_jpeg_plan_intervals: the frame has no restart interval
+
+
+def interval_stream_offset(n_intervals: int) -> int:
+    return (PLAN_STREAM_OFFSET + 4 * (n_intervals + 1) + 15) // 16 * 16
+
+
+def restart_plan(data, frame: int = 0):
+    """One compressed frame -> its interval plan (uint8 array), or None for a frame without a restart interval. Raises JpegError
+    with parse()'s status and message where parse() refuses the header, or where a restart marker is missing or out of
+    sequence. Host only."""
+    lib = _lib.load()
+    raw = bytes(data)
+    buf = np.frombuffer(raw or b"\0", dtype=np.uint8)
+    out = [C.c_int() for _ in range(5)]
+    needed = C.c_size_t()
+
+    def call(dst, cap):
+        rc = lib.gtx_jpeg_plan_intervals(_lib.ptr(buf), len(raw), int(frame), *[C.byref(v) for v in out], dst, cap, C.byref(needed))
+        if rc < 0:
+            raise JpegError(rc, lib.gtx_last_error().decode("utf-8", "replace"))
+        return rc
+
+    if call(None, 0) == NO_RESTART:
+        return None
+    plan = np.zeros((needed.value + 3) // 4, dtype=np.uint32).view(np.uint8)[:needed.value]
+    if call(_lib.ptr(plan), plan.nbytes) != 0:
+        raise JpegError(-5, f"JPEG frame {frame}: the interval plan did not fit the size the parser asked for")
+    return plan
+
+
+def restart_plan_fields(plan: np.ndarray):
+    """The interval plan's header as a dict (with n_intervals), its quantisation tables, its six Huffman tables (as plan_fields),
+    start[n_intervals + 1] and the clean stream (views)."""
+    hd = plan[:PLAN_QUANT_OFFSET].view(np.uint32)
+    if int(hd[0]) != INTERVAL_PLAN_MAGIC or int(hd[1]) != plan.nbytes:
+        raise ValueError("not a JPEG interval plan")
+    f = dict(w=int(hd[2]), h=int(hd[3]), ncomp=int(hd[4]), hs=int(hd[5]), vs=int(hd[6]), mcus_x=int(hd[7]), mcus_y=int(hd[8]), n_blocks=int(hd[9]),
+             bw=[int(v) for v in hd[10:13]], bh=[int(v) for v in hd[13:16]], restart=int(hd[16]), td=[int(v) for v in hd[17:20]],
+             ta=[int(v) for v in hd[20:23]], stream_bytes=int(hd[23]), n_intervals=int(hd[24]), stream_bits=int(hd[26]) | int(hd[27]) << 32)
+    quant = plan[PLAN_QUANT_OFFSET:PLAN_HUFF_OFFSET].view(np.uint16).reshape(3, 64)
+    tables = []
+    for k in range(6):
+        t = plan[PLAN_HUFF_OFFSET + k * PLAN_HUFF_BYTES:PLAN_HUFF_OFFSET + (k + 1) * PLAN_HUFF_BYTES]
+        tables.append(dict(look=t[:1024].view(np.uint16).tolist(), maxcode=t[1024:1096].view(np.int32).tolist(), valoff=t[1096:1168].view(np.int32).tolist(),
+                           vals=t[1168:1424].tolist(), nvals=int(t[1424:1428].view(np.uint32)[0])))
+    n_int = f["n_intervals"]
+    start = plan[PLAN_STREAM_OFFSET:PLAN_STREAM_OFFSET + 4 * (n_int + 1)].view(np.uint32)
+    at = interval_stream_offset(n_int)
+    stream = plan[at:at + f["stream_bytes"]]
+    return f, quant, tables, start, stream
+
+
+def _symbol_step(t, win: int, left: int, z: int):
+    """jpegsym::step of csrc/jpeg_symbol.hpp: (result, used bits, new z, event). result 0 bad, 1 the block goes on, 2 the block
+    ends; event: None, ("dc", difference) or ("ac", z, value)."""
+    top = win >> 48
+    assert 0 <= top < 1 << 16
+    ln = sym = 0
+    e = t["look"][top >> 7]
+    if e:
+        ln, sym = e >> 8, e & 255
+    else:
+        for l in range(10, 17):
+            code = top >> (16 - l)
+            if code <= t["maxcode"][l]:
+                idx = t["valoff"][l] + code
+                if 0 <= idx < min(t["nvals"], 256):
+                    ln, sym = l, t["vals"][idx]
+                break
+    if ln == 0 or ln > 16 or ln > left:
+        return 0, 0, z, None
+    m64 = (1 << 64) - 1
+
+    def amplitude(s):
+        v = ((win << ln) & m64) >> (64 - s)
+        return v - (1 << s) + 1 if v < (1 << (s - 1)) else v
+
+    if z == 0:
+        s = sym
+        if s > 15 or ln + s > left:
+            return 0, 0, z, None
+        return 1, ln + s, 1, ("dc", amplitude(s) if s else 0)
+    r, s = sym >> 4, sym & 15
+    if s == 0:
+        if r != 15:
+            return 2, ln, z, None
+        z += 16
+        return (2 if z >= 64 else 1), ln, z, None
+    z += r
+    if z > 63 or ln + s > left:
+        return 0, 0, z, None
+    ev = ("ac", z, amplitude(s))
+    z += 1
+    return (2 if z == 64 else 1), ln + s, z, ev
+
+
+def restart_lane_twin(plan: np.ndarray, i: int):
+    """Lane i of jpeg_restart_kernel alone: (bad, first block, dense int16 [blocks][64], lens [blocks]) for the blocks of
+    interval i. It reads start[i], start[i + 1], the tables and its own bytes of the stream, nothing else."""
+    f, _, tables, start, stream = restart_plan_fields(plan)
+    n_int, nb = f["n_intervals"], f["n_blocks"]
+    assert 0 <= i < n_int and i + 1 < len(start)
+    luma = f["hs"] * f["vs"]
+    bpm = 1 if f["ncomp"] == 1 else luma + 2
+    n_mcus = f["mcus_x"] * f["mcus_y"]
+    sb = f["stream_bytes"]
+    byte1 = min(int(start[i + 1]), sb)
+    byte0 = min(int(start[i]), byte1)
+    bits = 8 * (byte1 - byte0)
+    mcu0 = i * f["restart"]
+    mcu1 = min(mcu0 + f["restart"], n_mcus)
+    b0, b_end = min(mcu0 * bpm, nb), min(mcu1 * bpm, nb)
+    own = stream[byte0:byte1].tobytes() + bytes(8)                 # bits at or past start[i + 1] read as zero
+    dense = np.zeros((max(b_end - b0, 0), 64), np.int16)
+    lens = np.zeros(max(b_end - b0, 0), np.int64)
+    pred = [0, 0, 0]
+    b, k, z, p, ln, bad = b0, 0, 0, 0, 0, False
+    steps = 0
+    while b < b_end:
+        steps += 1
+        assert steps <= bits + 1                                   # every step consumes at least one bit
+        c = 0 if (bpm == 1 or k < luma) else min(1 + (k - luma), 2)
+        at = p >> 3
+        assert 0 <= at and at + 8 <= len(own)
+        win = (int.from_bytes(own[at:at + 8], "big") << (p & 7)) & ((1 << 64) - 1)
+        left = bits - p
+        assert left >= 0
+        if left < 64:
+            assert win & ((1 << (64 - left)) - 1) == 0 or left == 0    # the zero padding is the mask the kernel applies
+            win = win & ~((1 << (64 - left)) - 1) if left else 0
+        r, used, z, ev = _symbol_step(tables[c if z == 0 else 3 + c], win, left, z)
+        if r == 0:
+            bad = True
+            break
+        assert 1 <= used <= left and b0 <= b < b_end and b < nb
+        if ev and ev[0] == "dc":
+            pred[c] += ev[1]
+            if not -32768 <= pred[c] <= 32767:
+                bad = True
+                break
+            dense[b - b0, 0] = pred[c]
+            ln = 1 if pred[c] else 0
+        elif ev:
+            assert 1 <= ev[1] <= 63 and -32768 <= ev[2] <= 32767
+            dense[b - b0, ev[1]] = ev[2]
+            ln = ev[1] + 1
+        p += used
+        if r == 2:
+            lens[b - b0] = ln
+            b, k, z = b + 1, (0 if k + 1 == bpm else k + 1), 0
+    if not bad and i + 1 < n_int and bits - p >= 8:                # a marker follows: one byte's pad bits at most stand before it
+        bad = True
+    return bad, b0, dense, lens
+
+
+def restart_decode_twin(plan: np.ndarray):
+    """jpeg_restart_kernel, the offset scan and the compaction on one interval plan, in numpy and plain Python with every index
+    asserted: (status, record or None)."""
+    f, quant, _, start, _ = restart_plan_fields(plan)
+    nb, n_int = f["n_blocks"], f["n_intervals"]
+    assert n_int == -(-(f["mcus_x"] * f["mcus_y"]) // f["restart"]) and int(start[0]) == 0 and int(start[n_int]) == f["stream_bytes"]
+    assert (np.diff(start.astype(np.int64)) >= 0).all()
+    dense = np.zeros((nb, 64), np.int16)
+    lens = np.zeros(nb, np.int64)
+    status = 0
+    for i in range(n_int):
+        bad, b0, d, l = restart_lane_twin(plan, i)
+        assert b0 + len(l) <= nb
+        dense[b0:b0 + len(l)], lens[b0:b0 + len(l)] = d, l
+        if bad:
+            status |= RESTART_INVALID
+    if status:
+        return status, None
+    lens = np.minimum(lens, 64)
+    offsets = np.zeros(nb + 1, np.uint32)
+    np.cumsum(lens, out=offsets[1:])
+    n_coef = int(offsets[-1])
+    assert n_coef <= 64 * nb
+    total = OFFSETS_OFFSET + 4 * (nb + 1) + 2 * n_coef
+    rec = np.zeros((total + 3) // 4, np.uint32).view(np.uint8)[:total]
+    rec[:HEADER_BYTES].view(np.uint32)[:17] = [MAGIC, total, f["w"], f["h"], f["ncomp"], f["hs"], f["vs"], f["mcus_x"], f["mcus_y"], nb, n_coef, *f["bw"], *f["bh"]]
+    rec[QUANT_OFFSET:OFFSETS_OFFSET].view(np.uint16)[:] = quant.ravel()
+    end = OFFSETS_OFFSET + 4 * (nb + 1)
+    rec[OFFSETS_OFFSET:end].view(np.uint32)[:] = offsets
+    rec[end:].view(np.int16)[:] = dense[np.arange(64)[None, :] < lens[:, None]]
+    return 0, rec
+
+
+def restart_plan_dev(ctx: _lib.Context, plan: np.ndarray):
+    """One interval plan through gtx_op_jpeg_restart (upload, the interval launch, scan and compaction, the record at its real
+    length): (status, record or None). Tests, tools."""
+    lib = ctx.lib
+    n, status = C.c_size_t(), C.c_int()
+    p = _aligned(plan)
+    rec = np.zeros(1 << 14, np.uint32).view(np.uint8)
+    for _ in range(2):
+        rc = lib.gtx_op_jpeg_restart(ctx.handle, _lib.ptr(p), p.nbytes, _lib.ptr(rec), rec.nbytes, C.byref(n), C.byref(status))
+        if rc != 1:
+            break
+        rec = np.zeros((n.value + 3) // 4, np.uint32).view(np.uint8)
+    if rc != 0:
+        raise JpegError(rc, lib.gtx_last_error().decode("utf-8", "replace"))
+    return status.value, (rec[:n.value] if status.value == 0 else None)
+
+
+def emit(rec: np.ndarray, restart: int = 0) -> bytes:
+    """Record -> baseline JFIF JPEG with a restart interval of `restart` MCUs (gtx_jpeg_emit_restart: record_to_bytes() plus a
+    DRI segment, predictor resets, 1-bit padding and RSTn every `restart` MCUs). restart 0: record_to_bytes()'s bytes exactly.
+    Raises JpegError where record_to_bytes() does, and for a restart outside 0..65535. Host only; the call releases the GIL."""
+    lib = _lib.load()
+    r = _aligned(rec)
+    n = C.c_size_t()
+    out = np.empty(r.nbytes + 1024, np.uint8)
+    for _ in range(2):
+        rc = lib.gtx_jpeg_emit_restart(_lib.ptr(r), r.nbytes, int(restart), _lib.ptr(out), out.nbytes, C.byref(n))
+        if rc != 1:
+            break
+        out = np.empty(n.value, np.uint8)
+    if rc != 0:
+        raise JpegError(rc, lib.gtx_last_error().decode("utf-8", "replace"))
+    return out[:n.value].tobytes()
+
+
+def recode_with_restarts(data, restart: int, frame: int = 0) -> bytes:
+    """One compressed frame -> the same coefficients coded again with a restart interval of `restart` MCUs (parse(), then emit()):
+    lossless on coefficients, with the Annex K.3 tables. Refuses what parse() refuses and what gtx_jpeg_emit refuses."""
+    rec, _ = parse(data, frame)
+    return emit(rec, restart)
+
+
+def mcus_per_row(data, frame: int = 0) -> int:
+    """MCUs in one MCU row of the frame (the restart interval that gives one interval per row)."""
+    lib = _lib.load()
+    raw = bytes(data)
+    buf = np.frombuffer(raw or b"\0", dtype=np.uint8)
+    out = [C.c_int() for _ in range(5)]
+    rc = lib.gtx_jpeg_probe(_lib.ptr(buf), len(raw), int(frame), *[C.byref(v) for v in out])
+    if rc < 0:
+        raise JpegError(rc, lib.gtx_last_error().decode("utf-8", "replace"))
+    h, w, ncomp, hs, vs = (v.value for v in out)
+    return -(-w // (8 * (hs if ncomp == 3 else 1)))

@@ -6,7 +6,7 @@ an unregistered frame -- passes through unchanged, :285) and written as Motion-J
 read-ahead feeder puts them into HBM, gtx_warp_frame_dev and the JPEG encoder (geotrax_amd.video_writer) run there, and only
 the packed coefficient records come back for Huffman coding.
 
-    python -m geotrax_amd.stabilized_video <clip> [--quality Q] [--entropy host|gpu] [--cut-frame-left N] [--cut-frame-right N] [-o PATH]
+    python -m geotrax_amd.stabilized_video <clip> [--quality Q] [--entropy host|gpu] [--restart-interval N] [--cut-frame-left N] [--cut-frame-right N] [-o PATH]
 """
 from __future__ import annotations
 
@@ -23,7 +23,7 @@ from .extract import get_output_dir
 from .feeder import FrameFeeder
 from .frames import Y4mReader, open_source
 from .georef_stage import DEFAULT_FPS, build_result_path, detect_delimiter
-from .video_writer import MjpegWriter
+from .video_writer import MjpegWriter, check_restart_interval
 
 
 def visualized_path(source: Path, out_cfg: dict | None = None, viz_mode: int = 1, ext: str = "avi") -> Path:
@@ -74,9 +74,11 @@ def _open_feeder(reader, first: int, stop: int, batch: int, ring: int, ctx: _lib
 
 def write_stabilized(source, out_path=None, transforms_path=None, quality: int = 90, subsampling: str = "4:2:0", cut_frame_left: int = 0,
                      cut_frame_right: int | None = None, out_cfg: dict | None = None, encode_threads: int = 8, ctx: _lib.Context | None = None,
-                     logger: logging.Logger | None = None, entropy: str = "host") -> tuple[Path, int]:
+                     logger: logging.Logger | None = None, entropy: str = "host", restart_interval: int = 0) -> tuple[Path, int]:
     """Writes the stabilized clip; returns (path, frames written). Frames cut_frame_left .. cut_frame_right - 1 are written
-    (visualize.py:272-279: the loop breaks when it reaches cut_frame_right)."""
+    (visualize.py:272-279: the loop breaks when it reaches cut_frame_right). restart_interval > 0: a restart marker every that
+    many MCUs (host emitter only), so that the clip reads back one GPU lane per interval (`engine: {jpeg_restart: gpu}`)."""
+    check_restart_interval(entropy, restart_interval)
     log = logger or logging.getLogger(__name__)
     source = Path(source)
     ctx = ctx or _lib.default_context()
@@ -92,7 +94,8 @@ def write_stabilized(source, out_path=None, transforms_path=None, quality: int =
         fps = getattr(reader, "fps", 0.0) or DEFAULT_FPS
         out.parent.mkdir(parents=True, exist_ok=True)
         batch, n_written = 2, 0
-        writer = MjpegWriter(out, fps, (w, h), quality=quality, subsampling=subsampling, encode_threads=encode_threads, ctx=ctx, entropy=entropy)
+        writer = MjpegWriter(out, fps, (w, h), quality=quality, subsampling=subsampling, encode_threads=encode_threads, ctx=ctx, entropy=entropy,
+                             restart_interval=restart_interval)
         # a frame is read by its encoder's launches until the writer's ring has come round: that many batches stay with us
         keep = writer.ring // batch + 2
         warped = [ctx.dev_alloc(h * w * 3) for _ in range(writer.ring)]
@@ -133,12 +136,15 @@ def main(argv=None) -> int:
     ap.add_argument("--transforms", type=Path, default=None, help="another transforms file")
     ap.add_argument("--encode-threads", type=int, default=8)
     ap.add_argument("--entropy", choices=["host", "gpu"], default="host", help="where the pictures are Huffman-coded: host threads, or the GPU")
+    ap.add_argument("--restart-interval", type=int, default=0, metavar="N",
+                    help="a restart marker every N MCUs (0: none), so that the clip is read back one GPU lane per interval; needs --entropy host")
     ap.add_argument("-o", "--output", type=Path, default=None, help="the file to write (.avi, .mjpeg); default <output folder>/<stem>_mode_1.avi")
     args = ap.parse_args(argv)
+    check_restart_interval(args.entropy, args.restart_interval)   # ValueError: the GPU coder and restart markers do not go together
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     try:
         write_stabilized(args.source, args.output, args.transforms, args.quality, args.subsampling, args.cut_frame_left, args.cut_frame_right,
-                         encode_threads=args.encode_threads, entropy=args.entropy)
+                         encode_threads=args.encode_threads, entropy=args.entropy, restart_interval=args.restart_interval)
     except (OSError, ValueError, _lib.GtxError) as e:
         logging.getLogger(__name__).error(str(e))
         return 1

@@ -126,6 +126,18 @@ class _Slot:
     __slots__ = ("enc", "dbuf", "busy")
 
 
+def check_restart_interval(entropy: str, restart_interval: int) -> int:
+    """The restart interval a writer may use with this entropy route, or ValueError: 0..65535 MCUs (what a DRI segment holds), and
+    above 0 only with the host emitter (the GPU Huffman coder writes one unbroken scan). The stages' command lines call it as
+    soon as their arguments are parsed, before any file or GPU is touched."""
+    n = int(restart_interval)
+    if not 0 <= n <= 65535:
+        raise ValueError(f"restart interval {restart_interval} is outside 0..65535 MCUs")
+    if entropy == "gpu" and n > 0:
+        raise ValueError(f"a restart interval ({n} MCUs) needs the host emitter (--entropy host, entropy='host'): the GPU Huffman coder writes one unbroken scan")
+    return n
+
+
 class MjpegWriter:
     """cv2.VideoWriter's shape: MjpegWriter(path, fps, (w, h)); write(frame) / write_dev(dptr); release().
 
@@ -136,14 +148,20 @@ class MjpegWriter:
     further frames have been written or release() has returned, unless what overwrites it is ordered on that stream.
 
     entropy="gpu" (default "host") puts the ring's encoders on the GPU entropy route: a collected slot hands over the finished
-    picture, which goes straight to the file; the thread pool is not used. write_record() is host coding on either setting."""
+    picture, which goes straight to the file; the thread pool is not used. write_record() is host coding on either setting.
+
+    restart_interval=N (default 0: none) has the host emitter put a restart marker after every N MCUs (jpeg.emit), so that the
+    file reads back one GPU lane per interval (`engine: {jpeg_restart: gpu}`); the same coefficients either way. It needs
+    entropy="host": the GPU Huffman coder writes one unbroken scan."""
 
     ENTROPY = ("host", "gpu")
 
     def __init__(self, path, fps: float, size: tuple[int, int], quality: int = 90, subsampling: str = "4:2:0", encode_threads: int = 8,
-                 ctx: _lib.Context | None = None, ring: int = 3, riff_limit: int = 1 << 30, entropy: str = "host"):
+                 ctx: _lib.Context | None = None, ring: int = 3, riff_limit: int = 1 << 30, entropy: str = "host", restart_interval: int = 0):
         if entropy not in self.ENTROPY:
             raise ValueError(f"entropy {entropy!r}: one of {list(self.ENTROPY)}")
+        check_restart_interval(entropy, restart_interval)
+        self.restart_interval = int(restart_interval)
         self.entropy = entropy
         self.path = Path(path)
         self.w, self.h = int(size[0]), int(size[1])
@@ -252,7 +270,7 @@ class MjpegWriter:
         if (f["w"], f["h"]) != (self.w, self.h):
             raise ValueError(f"the record is of a {f['w']} x {f['h']} frame, the writer was opened for {self.w} x {self.h}")
         self.record_bytes += rec.nbytes
-        self._pending.append(self._pool.submit(jpeg.record_to_bytes, rec))
+        self._pending.append(self._pool.submit(jpeg.emit, rec, self.restart_interval) if self.restart_interval else self._pool.submit(jpeg.record_to_bytes, rec))
         self._drain(False)
 
     def _drain(self, everything: bool) -> None:

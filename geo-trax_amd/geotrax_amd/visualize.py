@@ -541,7 +541,8 @@ def visualize_mode(args, viz_mode: int, class_names: dict, viz_config: dict, out
         out.parent.mkdir(parents=True, exist_ok=True)
         nbytes = h * w * 3
         batch, n_written, capacity = 2, 0, 16384
-        writer = MjpegWriter(out, fps, (w, h), quality=quality, ctx=ctx, entropy=getattr(args, "entropy", None) or "host")
+        writer = MjpegWriter(out, fps, (w, h), quality=quality, ctx=ctx, entropy=getattr(args, "entropy", None) or "host",
+                             restart_interval=getattr(args, "restart_interval", None) or 0)
         keep = writer.ring // batch + 2                    # as geotrax_amd.stabilized_video: a frame stays until the writer's ring has come round
         ring = [ctx.dev_alloc(nbytes) for _ in range(writer.ring)] if viz_mode in (1, 2, 4) else []
         bufs.extend(ring)
@@ -666,6 +667,7 @@ def visualize_results(args: argparse.Namespace, logger: logging.Logger) -> int:
 
 def main(argv=None) -> int:
     from .extract import add_common_args, setup_logger
+    from .video_writer import check_restart_interval
 
     ap = argparse.ArgumentParser(prog="python -m geotrax_amd.visualize", description="Tracking results visualization")
     ap.add_argument("source", type=Path, help="Path to the input video file.")
@@ -674,8 +676,11 @@ def main(argv=None) -> int:
     opt.add_argument("--class-names", "-cn", nargs="+", default=None, metavar="ID=NAME|FILE", help="Class-id -> name mapping.")
     opt.add_argument("--quality", type=int, default=90, help="JPEG quality of the output, 1..100")
     opt.add_argument("--entropy", choices=["host", "gpu"], default="host", help="Where the output's pictures are Huffman-coded: host threads, or the GPU.")
+    opt.add_argument("--restart-interval", type=int, default=0, metavar="N",
+                     help="A restart marker every N MCUs in the output (0: none), so that it is read back one GPU lane per interval; needs --entropy host.")
     add_visualization_args(ap.add_argument_group("Visualization arguments"))
     args = ap.parse_args(argv)
+    check_restart_interval(args.entropy, args.restart_interval)   # ValueError: the GPU coder and restart markers do not go together
     logger = setup_logger(__name__, getattr(args, "verbose", False), getattr(args, "log_path", None))
     return visualize_results(args, logger)
 

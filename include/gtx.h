@@ -77,6 +77,9 @@ extern "C" {
  *     entropy coder as HIP kernels, opt-in per encoder) added: new entry points only, so the number stays.
  *     gtx_jpeg_{plan_bound, plan, entropy_ms}, gtx_op_jpeg_entropy and gtx_feeder_{set_jpeg_entropy, jpeg_stats} (the JPEG source's entropy decoder as
  *     HIP kernels, opt-in per feeder) added: new entry points only, so the number stays.
+ *     gtx_jpeg_{plan_intervals_bound, plan_intervals, restart_ms, emit_restart}, gtx_op_jpeg_restart and gtx_feeder_{set_jpeg_restart,
+ *     jpeg_restart_stats} (JPEG frames with restart intervals decoded one lane per interval, opt-in per feeder; the host emitter
+ *     writes such frames) added: new entry points only, so the number stays.
  *     gtx_op_georef_tracks, gtx_georef_tracks_ms and gtx_georef_tracks_cfg (the georeference stage's per-track columns as HIP
  *     kernels, opt-in per run) added: new entry points and a struct of their own only, so the number stays.
  *     gtx_op_stem and gtx_op_conv2d_fused (the stem launch, and the convolution launch with its second source, plain output,
@@ -292,6 +295,47 @@ int gtx_feeder_set_jpeg_entropy(gtx_feeder* f, int gpu);
  * status. On the host route all three stay 0. */
 int gtx_feeder_jpeg_stats(gtx_feeder* f, int64_t out[3]);
 
+/* JPEG frame source, the restart-interval route (opt-in): frames that carry a DRI segment, decoded one lane per restart interval
+ * (csrc/jpeg_restart.hip). At every RSTn the stream is byte aligned, the DC predictors are zero and the MCU index is known, so
+ * the intervals need nothing from each other. The host keeps the header walk and removes the byte stuffing and the markers (the
+ * "interval plan", csrc/jpeg_parse.hpp: header, quantisers, tables, the start of every interval, the clean stream); the GPU
+ * produces the packed record, byte for byte what gtx_jpeg_parse writes for the same picture. A frame the kernel cannot vouch
+ * for gets a non-zero status and is decoded by gtx_jpeg_parse, so which frames decode and what an error says does not depend on
+ * the route. */
+/* Replaces cv2.VideoCapture.read(), extract.py:146 (sizing): bytes of the largest interval plan a decodable h x w frame can need;
+ * 0 for a size outside 1..16384. */
+size_t gtx_jpeg_plan_intervals_bound(int h, int w);
+/* Replaces cv2.VideoCapture.read(), extract.py:146 (the host half of the restart-interval route): bytes[0, n) -> the interval plan
+ * in out[0, capacity) (4-byte aligned; NULL with capacity 0 asks for the size). Returns 0 (written), 1 (capacity < *needed), 3 (the
+ * frame has no restart interval: *needed is 0, nothing is written) or the negative status and message gtx_jpeg_parse gives for the
+ * same frame: its header rules, and where a restart marker is missing or out of sequence its scan's. h, w, ncomp, hs, vs as
+ * gtx_jpeg_parse. */
+int gtx_jpeg_plan_intervals(const void* bytes, size_t n, int64_t frame, int* h, int* w, int* ncomp, int* hs, int* vs, void* out, size_t capacity,
+                            size_t* needed);
+/* Kernel hook of the restart-interval decoder (tests/test_jpeg_restart_gpu.py; no product use): uploads one interval plan (host
+ * memory, as gtx_jpeg_plan_intervals wrote it), runs the chain and copies the record at its real length into record[0, capacity)
+ * (4-byte aligned). *status: 0 or 1 (invalid: *record_bytes is 0 and nothing is copied; gtx_jpeg_parse says what is wrong with
+ * the frame). Returns 0, 1 (capacity < *record_bytes: nothing copied) or a negative status; a plan jpeg::check_plan_intervals
+ * refuses is GTX_ERR_INVALID before any launch. */
+int gtx_op_jpeg_restart(gtx_ctx* ctx, const void* plan, size_t bytes, void* record, size_t capacity, size_t* record_bytes, int* status);
+/* Timing of what replaces cv2.VideoCapture.read(), extract.py:146, on the restart-interval route: `copies` copies of one interval
+ * plan (1..64, a feeder batch) decoded `reps` times, two events around each part. ms[0] = the entropy chain (the interval launch, the
+ * offset scans and the compactions), ms[1] = the two pixel kernels, mean milliseconds per frame. *status: the first copy's.
+ * tools/jpeg_time.py. */
+int gtx_jpeg_restart_ms(gtx_ctx* ctx, const void* plan, size_t bytes, int copies, int reps, float ms[2], int* status);
+/* Replaces cv2.VideoCapture.read(), extract.py:146, for a feeder of kind 2: on != 0 sends every frame that has a restart interval
+ * down the restart-interval route, whichever way gtx_feeder_set_jpeg_entropy sends the others (the two switches are independent; a
+ * frame without a restart interval goes where it goes without this switch). The restart frames of a batch share one interval
+ * launch. A frame whose status is not 0 is decoded again by gtx_jpeg_parse when gtx_feeder_next hands its batch out; one whose
+ * plan does not fit its slot, or that gtx_jpeg_plan_intervals refuses, is decoded by gtx_jpeg_parse on its reader thread. Valid on a
+ * feeder of kind 2 that has no source yet; GTX_ERR_INVALID with a message for NULL, another kind or an opened feeder. */
+int gtx_feeder_set_jpeg_restart(gtx_feeder* f, int on);
+/* Replaces cv2.VideoCapture.read(), extract.py:146 (book-keeping): frames of a kind-2 feeder delivered so far that out[0] the
+ * restart-interval route decoded, out[1] it handed back to a reader thread (the plan did not fit the slot, or was refused),
+ * out[2] gtx_jpeg_parse decoded again after a GPU status. None of them is counted by gtx_feeder_jpeg_stats. All 0 with the
+ * switch off. */
+int gtx_feeder_jpeg_restart_stats(gtx_feeder* f, int64_t out[3]);
+
 /* JPEG frame sink: cv2.VideoWriter.write() (geotrax/visualize.py:298) for Motion-JPEG output, the decode above run backwards.
  * The GPU turns a packed BGR frame in HBM into the same packed record (csrc/jpeg_parse.hpp) with libjpeg's default integer
  * arithmetic (jccolor.c's 16-bit tables, h2v2 downsampling with its alternating bias, the slow-integer forward DCT, jcdctmgr.c's
@@ -321,6 +365,11 @@ int gtx_jpeg_enc_last_ms(gtx_jpeg_enc* enc, float* ms);
  * quantiser above 255 or a coefficient the Annex K.3 tables cannot code is GTX_ERR_INVALID). *n receives the file's size.
  * Returns 0 (written), 1 (capacity < *n: nothing outside out[0, capacity) was touched) or a negative status. */
 int gtx_jpeg_emit(const void* record, size_t bytes, void* out, size_t capacity, size_t* n);
+/* Replaces cv2.VideoWriter.write(), visualize.py:298 (host only): gtx_jpeg_emit with restart intervals of `restart_mcus` MCUs, so
+ * that the file reads back one lane per interval (gtx_feeder_set_jpeg_restart): a DRI segment and, every restart_mcus MCUs, the
+ * pending byte padded with 1-bits, RSTn (0..7, wrapping) and the DC predictors reset. restart_mcus 0: gtx_jpeg_emit's bytes
+ * exactly; above 65535 (what DRI holds): GTX_ERR_INVALID. Everything else as gtx_jpeg_emit. */
+int gtx_jpeg_emit_restart(const void* record, size_t bytes, int restart_mcus, void* out, size_t capacity, size_t* n);
 /* Replaces cv2.VideoWriter.write(), visualize.py:298, on host arrays (the operator hook the kernel tests use): uploads the BGR
  * frame, runs one encoder's chain and returns the record as gtx_jpeg_enc_collect does (0, 1 or a negative status). Sizes,
  * quality and subsampling are checked before the GPU is touched. */

@@ -45,12 +45,16 @@ def main() -> None:
     ap.add_argument("--no-loop", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--entropy", action="store_true", help="the GPU entropy route's figures instead of the host route's")
-    ap.add_argument("--only-loop", action="store_true", help="--entropy: the product loop alone")
+    ap.add_argument("--only-loop", action="store_true", help="--entropy, --restart: the product loop alone")
     ap.add_argument("--twin", action="store_true", help="--entropy: also the numpy twin's rounds on the first 4K frame (minutes of host time)")
+    ap.add_argument("--restart", action="store_true", help="the restart-interval route's figures (engine.jpeg_restart: gpu) next to the host route's")
+    ap.add_argument("--restart-out", default=str(ROOT / "profiles" / "jpeg_restart_time.txt"))
     ap.add_argument("--entropy-out", default=str(ROOT / "profiles" / "jpeg_entropy_time.txt"))
     a = ap.parse_args()
     if a.entropy:
         return entropy_route(a)
+    if a.restart:
+        return restart_route(a)
     from PIL import Image
 
     from geotrax_amd import _lib, jpeg
@@ -249,7 +253,105 @@ def entropy_route(a) -> None:
         product_loop(out / "loop", n, routes=("host", "gpu"), thread_counts=(2, 4, 8), say=say)
 
 
-def product_loop(root: Path, n: int, routes=("host",), thread_counts=(4, 8, 12), say=print) -> None:
+def restart_route(a) -> None:
+    """The restart-interval route's figures on the clip of the other legs, recoded at one MCU row per interval and at 8 MCUs per
+    interval; every line goes to stdout and is appended to --restart-out as it is produced. The host route (parse() on the
+    reader threads) is measured on the same files in the same passes. The product loop comes last (--no-loop leaves it out)."""
+    import ctypes as C
+    import io
+
+    from PIL import Image
+
+    from geotrax_amd import _lib, jpeg
+    from geotrax_amd.frames import open_source
+    from geotrax_amd.synth import make_scene
+
+    log = open(a.restart_out, "a")
+
+    def say(line):
+        print(line, flush=True)
+        log.write(line + "\n")
+        log.flush()
+
+    h, w, n = a.h, a.w, a.frames
+    out = Path(a.out) if a.out else Path(tempfile.mkdtemp())
+    out.mkdir(parents=True, exist_ok=True)
+    if a.only_loop:                                               # (the product loop plays bench.py's 4K clip: 240 MCUs per MCU row)
+        for r in (240, 8):
+            product_loop(out / f"loop_{r}", n, routes=("host", "gpu"), thread_counts=(2, 4, 8), say=say, key="jpeg_restart", restart=r)
+        return
+    sc = make_scene(seed=0, h=h, w=w)
+    frames = [sc.render(5 * t, 150) for t in range(a.distinct)]
+    plain = []
+    for f in frames:
+        buf = io.BytesIO()
+        Image.fromarray(np.ascontiguousarray(f[..., ::-1]), "RGB").save(buf, "JPEG", quality=90, subsampling=2)
+        plain.append(jpeg.recode_with_restarts(buf.getvalue(), 0))   # the Annex K.3 tables, no markers: what the sizes are compared with
+    row = jpeg.mcus_per_row(plain[0])
+    say(f"frame {w} x {h}, Pillow quality 90, 4:2:0, {a.distinct} distinct frames of the synthetic scene, recoded by the host emitter; {row} MCUs per MCU row")
+    ctx = None if a.no_gpu else _lib.default_context(0)
+    for name, r in (("one MCU row per interval", row), ("8 MCUs per interval", 8)):
+        blobs = [jpeg.recode_with_restarts(b, r) for b in plain]
+        plans = [jpeg.restart_plan(b) for b in blobs]
+        n_int = jpeg.restart_plan_fields(plans[0])[0]["n_intervals"]
+        size, size0 = np.mean([len(b) for b in blobs]), np.mean([len(b) for b in plain])
+        say(f"{name} (Ri = {r}, {n_int} intervals = lanes per frame): file {size:.0f} bytes against {size0:.0f} without markers (+{100 * (size / size0 - 1):.3f} %); "
+            f"plan {np.mean([p.nbytes for p in plans]):.0f} bytes uploaded per frame")
+        t_plan, t_parse = [], []
+        lib = _lib.load()
+        room = np.zeros(lib.gtx_jpeg_plan_intervals_bound(h, w) // 4 + 1, np.uint32).view(np.uint8)   # one call into a slot-sized buffer, as the feeder makes it
+        needed = C.c_size_t()
+        for _ in range(3):
+            for b in blobs:
+                src = np.frombuffer(b, np.uint8)
+                t0 = time.perf_counter()
+                rc = lib.gtx_jpeg_plan_intervals(_lib.ptr(src), len(b), 0, None, None, None, None, None, _lib.ptr(room), room.nbytes, C.byref(needed))
+                t1 = time.perf_counter()
+                assert rc == 0, rc
+                jpeg.parse(b)                                      # two calls, each with the full scan
+                t_plan.append(t1 - t0), t_parse.append((time.perf_counter() - t1) / 2)
+        say(f"{name}: host work per frame on one thread (median of {len(t_plan)}): plan_intervals() {1e3 * np.median(t_plan):.3f} ms, parse() {1e3 * np.median(t_parse):.2f} ms")
+        if ctx is None:
+            continue
+        from geotrax_amd.feeder import FrameFeeder
+
+        for copies in (1, 2, 8):
+            for rep in range(3):
+                got = []
+                for pl in plans:
+                    ms, st = (C.c_float * 2)(), C.c_int()
+                    _lib.check(ctx.lib.gtx_jpeg_restart_ms(ctx.handle, _lib.ptr(pl), pl.nbytes, copies, 5, ms, C.byref(st)))
+                    got.append((ms[0], ms[1], st.value))
+                say(f"{name}: GPU time per frame, {copies} frame(s) a launch, pass {rep} (events, mean of 5 x {len(plans)} frames): entropy chain "
+                    f"{np.mean([g[0] for g in got]):.4f} ms, the two pixel kernels {np.mean([g[1] for g in got]):.4f} ms; status {sorted({g[2] for g in got})}")
+        clip = out / "clip_restart.mjpeg"
+        clip.write_bytes(b"".join(blobs[k % a.distinct] for k in range(n)))
+        rd = open_source(clip)
+        layout = rd.jpeg_layout()
+        rd.release()
+        for rep in range(3):                                      # interleaved: every pass visits every case
+            for threads in (2, 4, 8):
+                for route in ("host", "gpu"):
+                    fd = FrameFeeder((h, w), kind="jpeg", batch=2, ring=6, device=ctx.device)
+                    fd.set_jpeg_restart(route)
+                    fd.open_jpeg(layout, n_threads=threads, entropy="host")
+                    t0 = time.perf_counter()
+                    k = 0
+                    for b in fd.batches(in_flight=2):
+                        b.wait_on(None)
+                        k += b.n
+                    dt = time.perf_counter() - t0
+                    stats = fd.jpeg_restart_stats()
+                    fd.close()
+                    say(f"{name}: feeder alone, jpeg_restart {route}, {threads} reader threads, pass {rep}: {k} frames in {dt:.3f} s = {k / dt:.0f} frames/s; "
+                        f"frames by the interval route / handed back / host after a GPU status: {stats[0]} / {stats[1]} / {stats[2]}")
+        clip.unlink()
+    if ctx is not None and not a.no_loop:
+        for r in (row, 8):
+            product_loop(out / f"loop_{r}", n, routes=("host", "gpu"), thread_counts=(2, 4, 8), say=say, key="jpeg_restart", restart=r)
+
+
+def product_loop(root: Path, n: int, routes=("host",), thread_counts=(4, 8, 12), say=print, key: str = "jpeg_entropy", restart: int = 0) -> None:
     """The product's loop on the same 150 frames as .y4m and as .mjpeg, one process, warm-up run + two timed runs each."""
     import argparse as ap_
     import io
@@ -276,6 +378,10 @@ def product_loop(root: Path, n: int, routes=("host",), thread_counts=(4, 8, 12),
         buf = io.BytesIO()
         Image.fromarray(np.ascontiguousarray(sc.render(t, 150)[..., ::-1]), "RGB").save(buf, "JPEG", quality=90, subsampling=2)
         blobs.append(buf.getvalue())
+    if restart:                                                  # the same coefficients with a restart marker every `restart` MCUs (host emitter)
+        from geotrax_amd import jpeg
+
+        blobs = [jpeg.recode_with_restarts(b, restart) for b in blobs]
     order = list(range(pool)) + list(range(pool - 2, 0, -1))
     (root / "clip.mjpeg").write_bytes(b"".join(blobs[order[i % len(order)]] for i in range(n)))
     cfg = yaml.safe_load((root / "cfg.yaml").read_text())
@@ -299,7 +405,7 @@ def product_loop(root: Path, n: int, routes=("host",), thread_counts=(4, 8, 12),
         c["engine"] = dict(cfg.get("engine") or {})
         if threads:
             c["engine"]["decode_threads"] = threads
-            c["engine"]["jpeg_entropy"] = route
+            c["engine"][key] = route
         paths[(name, threads, route)] = root / f"cfg_{threads or 'y4m'}_{route}.yaml"
         paths[(name, threads, route)].write_text(yaml.safe_dump(c))
     runs = {case: [] for case in cases}
@@ -308,7 +414,7 @@ def product_loop(root: Path, n: int, routes=("host",), thread_counts=(4, 8, 12),
             runs[case].append(one_run(root / case[0], paths[case]))
     for name, threads, route in cases:
         r = runs[(name, threads, route)]
-        what = f"{name}, {route} route, {threads} decode threads" if threads else f"{name} (page cache), 3 reader threads"
+        what = f"{name}{f' at {restart} MCUs per interval' if restart else ''}, {key} {route}, {threads} decode threads" if threads else f"{name} (page cache), 3 reader threads"
         say(f"product loop, {what}: {r[1][0]:.0f} and {r[2][0]:.0f} frames/s (warm-up run {r[0][0]:.0f}); {r[1][1]} track rows")
 
 
