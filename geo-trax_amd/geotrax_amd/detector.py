@@ -42,16 +42,18 @@ class Detections:
             if len(b) else np.zeros((0, 4), np.float32)
 
 
-END2END_GRAPHS = {"yolov10": "YOLOv10", "yolo26": "YOLO26"}   # detector_topology's graphs that carry a one-to-one head at model.23
+def _family_name(graph: str) -> str:
+    """A YOLO family's name as its authors write it: "yolov10" -> "YOLOv10", "yolo26" -> "YOLO26" """
+    return "YOLO" + graph[4:]
 
 
 def resolve_end2end(graph: str, tensors: dict, end2end: bool | None) -> bool:
     """Which head a detector of `graph` runs under `ultralytics.end2end` (null = the checkpoint's own): True = YOLOv10's / YOLO26's
     one-to-one head + top-300 cut, False = Detect + NMS. Raises for end2end: true with a family that has no such head, and for
     end2end: false with a YOLOv10 / YOLO26 file that no longer holds its one-to-many branches."""
-    from .weights import yolov10_has_one2many
+    from .weights import family_row, yolov10_has_one2many
 
-    if graph not in END2END_GRAPHS:
+    if not family_row(graph).end2end:
         if end2end:
             raise ValueError(f"end2end: true needs a checkpoint with an end-to-end (one-to-one) head; this one is {graph}, of the implemented "
                              f"families only YOLOv10 and YOLO26 have one (leave end2end empty)")
@@ -59,7 +61,7 @@ def resolve_end2end(graph: str, tensors: dict, end2end: bool | None) -> bool:
     if end2end is None or end2end:
         return True
     if not yolov10_has_one2many(tensors):
-        raise ValueError(f"end2end: false runs {END2END_GRAPHS[graph]}'s one-to-many branches (model.23.cv2 / cv3) through NMS, but this file holds only the "
+        raise ValueError(f"end2end: false runs {_family_name(graph)}'s one-to-many branches (model.23.cv2 / cv3) through NMS, but this file holds only the "
                          "one-to-one head (a fused ultralytics export drops them; tools/convert_weights.py keeps them)")
     return False
 
@@ -80,20 +82,20 @@ class Detector:
         if fp32_split is None:
             fp32_split = os.environ.get("GTX_FP32_SPLIT", "1" if FP32_SPLIT_DEFAULT else "0") == "1"
         self.fp32_split = bool(fp32_split) and not half
-        from .weights import detector_topology
+        from .weights import detector_family
 
         # the graph the tensors describe picks the detector family (reference: the model's yaml, extract.py:222-225): the RTDETR
         # predictor for rtdetr-l and yolov8-rtdetr (gtx_det_config.arch = 1; the library tells the two trunks apart by the names)
-        self.graph, head = detector_topology(tensors)
-        self.rtdetr = self.graph in ("rtdetr-l", "yolov8-rtdetr")
+        fam = detector_family(tensors)                    # the family's check runs here, once
+        self.graph, self.rtdetr = fam.graph, fam.rtdetr
         if self.rtdetr and obj_feats:
             raise NotImplementedError("RT-DETR: obj_feats (ReID `model: auto`) is not implemented")
         self.p2 = self.graph == "yolov8-p2"   # yolov8-p2.yaml: a fourth Detect level at stride 4, Detect = model.28
         self._layout: dict[str, np.ndarray] = {}
         if self.graph == "yolov9":
-            from .weights import check_yolov9, pad_yolov9_channels
+            from .weights import pad_yolov9_channels
 
-            scale = check_yolov9(tensors)
+            scale = fam.scale
             if obj_feats and scale != "c":                # ultralytics' own reshape of the Detect inputs fails on these widths too
                 raise NotImplementedError(f"yolov9{scale}: with_reid: true, model: auto needs Detect inputs whose channel counts are multiples of the "
                                           f"narrowest (yolov9t 64 / 96 / 128, yolov9s 128 / 192 / 256, yolov9m 240 / 360 / 480 are not); of the YOLOv9 "
@@ -102,9 +104,9 @@ class Detector:
             tensors, self._layout = pad_yolov9_channels(tensors, scale)
         self.end2end = resolve_end2end(self.graph, tensors, end2end)
         if self.end2end and obj_feats:
-            raise NotImplementedError(f"with_reid: true, model: auto reads the Detect layer's inputs at the boxes NMS keeps; not implemented for {END2END_GRAPHS[self.graph]}'s "
+            raise NotImplementedError(f"with_reid: true, model: auto reads the Detect layer's inputs at the boxes NMS keeps; not implemented for {_family_name(self.graph)}'s "
                                       "end-to-end head (a separate network works: `model: yolo11n-cls.safetensors`, or run the file with end2end: false)")
-        nc = int(tensors[head + (".enc_score_head.weight" if self.rtdetr else ".one2one_cv3.0.2.weight" if self.end2end else ".cv3.0.2.weight")].shape[0])
+        nc = int(tensors[fam.nc_key].shape[0])            # an end-to-end file run with end2end: false has the same nc in both pairs (checked)
         self.ctx = ctx or _lib.default_context()
         lib = self.ctx.lib
         cfg = DetConfig(imgsz=imgsz, conf=conf, iou=iou, max_det=max_det, agnostic_nms=int(agnostic_nms),

@@ -119,34 +119,17 @@ class YOLO:
             side = p.with_suffix(".names.yaml")
             if side.is_file():
                 self.names = {int(k): str(v) for k, v in yaml.safe_load(side.read_text()).items()}
-        from .weights import detector_topology
+        from .weights import detector_family, family_row
 
-        graph, head = detector_topology(self.tensors)     # refuses an RT-DETR layout this build does not run
-        self.is_rtdetr = graph in ("rtdetr-l", "yolov8-rtdetr")
-        self.is_p2 = graph == "yolov8-p2"
-        self.is_yolov10 = graph == "yolov10"
-        self.is_end2end = graph in ("yolov10", "yolo26")  # the families whose own head is the one-to-one pair at model.23
-        nc = int(self.tensors[head + (".enc_score_head.weight" if self.is_rtdetr else ".one2one_cv3.0.2.weight" if self.is_end2end else ".cv3.0.2.weight")].shape[0])
-        if self.is_yolov10:                               # ultralytics names the file by its scale: yolov10n.yaml / yolov10s.yaml
-            from .weights import check_yolov10
-
-            graph += check_yolov10(self.tensors)
-        if graph == "yolo26":                             # yolo26n.yaml ... yolo26x.yaml
-            from .weights import check_yolo26
-
-            graph += check_yolo26(self.tensors)
-        if graph == "yolo12":                             # yolo12n.yaml ... yolo12x.yaml
-            from .weights import check_yolo12
-
-            graph += check_yolo12(self.tensors)
-        if graph == "yolov5u":                            # ultralytics builds the *u files from yolov5n.yaml ... yolov5x.yaml
-            from .weights import check_yolov5u
-
-            graph = "yolov5" + check_yolov5u(self.tensors)
-        if graph == "yolov9":                             # yolov9t.yaml / yolov9s.yaml / yolov9m.yaml / yolov9c.yaml
-            from .weights import check_yolov9
-
-            graph += check_yolov9(self.tensors)
+        fam = detector_family(self.tensors)               # refuses a layout this build does not run; the family's check runs here, once
+        self.is_rtdetr = fam.rtdetr
+        self.is_p2 = fam.graph == "yolov8-p2"
+        self.is_yolov10 = fam.graph == "yolov10"
+        self.is_end2end = fam.end2end                     # the families whose own head is the one-to-one pair at model.23
+        # ultralytics names the file by its scale where the check tells one: yolov10n.yaml, yolo26x.yaml, yolov9t.yaml; the *u files are
+        # built from yolov5n.yaml ... yolov5x.yaml
+        graph = (family_row(fam.graph).stem or fam.graph) + (fam.scale or "")
+        nc = int(self.tensors[fam.nc_key].shape[0])
         if not self.names:
             self.names = {i: str(i) for i in range(nc)}
         self.model = self            # ultralytics exposes .model.yaml_file; keep attribute access harmless

@@ -11,7 +11,9 @@ ultralytics' ``fuse_conv_and_bn``.
 from __future__ import annotations
 
 import re
+from dataclasses import dataclass
 from pathlib import Path
+from typing import Callable, NamedTuple
 
 import numpy as np
 
@@ -286,21 +288,17 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False, a2_residual=Fa
                 conv(m + ".cv1.3.conv", 2 * c, c, 1)
                 dwconv(m + ".cv1.4.conv", c, True)
             elif c3k:
-                h = int(c * 0.5)
-                conv(m + ".cv1.conv", c, h, 1)
-                conv(m + ".cv2.conv", c, h, 1)
-                conv(m + ".cv3.conv", 2 * h, c, 1)
-                for j in range(2):
-                    bottleneck(f"{m}.m.{j}", h, 1.0)
+                c3k_block(m, c, c)
             else:
                 bottleneck(m, c, 1.0 if c3k is None else 0.5)
         conv(f"{pfx}.cv2.conv", (2 + n) * c, cout, 1)
 
-    def c3k_block(m, c, n=2):
-        """C3k(c, c, n): cv1 / cv2 to half the width, n full-width Bottlenecks behind cv1, cv3 on the two"""
+    def c3k_block(m, cin, c, n=2):
+        """C3k(cin, c, n): cv1 / cv2 to half the width, n full-width Bottlenecks behind cv1, cv3 on the two. RepCSP(cin, c, n) is the same
+        list: its RepBottlenecks of e = 1.0 are the fused RepConv (one 3x3), then a Conv3x3"""
         h = int(c * 0.5)
-        conv(m + ".cv1.conv", c, h, 1)
-        conv(m + ".cv2.conv", c, h, 1)
+        conv(m + ".cv1.conv", cin, h, 1)
+        conv(m + ".cv2.conv", cin, h, 1)
         conv(m + ".cv3.conv", 2 * h, c, 1)
         for j in range(n):
             bottleneck(f"{m}.m.{j}", h, 1.0)
@@ -323,15 +321,6 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False, a2_residual=Fa
         dwconv(m + ".attn.pe.conv", c, False, 7)
         conv(m + ".mlp.0.conv", c, int(c * mlp_ratio), 1)
         conv(m + ".mlp.1.conv", int(c * mlp_ratio), c, 1, act=False)
-
-    def repcsp(p, c1, c2, n):
-        """RepCSP(c1, c2, n) = C3 whose m.{k} are RepBottlenecks of e = 1.0: the fused RepConv (one 3x3) then a Conv3x3"""
-        h = int(c2 * 0.5)
-        conv(p + ".cv1.conv", c1, h, 1)
-        conv(p + ".cv2.conv", c1, h, 1)
-        conv(p + ".cv3.conv", 2 * h, c2, 1)
-        for k in range(n):
-            bottleneck(f"{p}.m.{k}", h, 1.0)
 
     def detect(d, chans, box="cv2", cls="cv3", reg_max=16):
         cb = max(16, chans[0] // 4, YOLO26_BOX_FLOOR if reg_max == 1 else 4 * reg_max)
@@ -385,7 +374,7 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False, a2_residual=Fa
                     for j in range(2):
                         ablock(f"{pfx}.m.{k}.{j}", c, 1.2 if a2_residual else 2.0)
                 else:
-                    c3k_block(f"{pfx}.m.{k}", c)
+                    c3k_block(f"{pfx}.m.{k}", c, c)
             conv(pfx + ".cv2.conv", (1 + n) * c, out[i], 1)
             if args[1] and a2_residual and gammas is not None:
                 gammas.append((pfx + ".gamma", (out[i],)))
@@ -400,11 +389,7 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False, a2_residual=Fa
             out.append(ch(args[0]))
             c = cin // 2
             conv(pfx + ".cv1.conv", cin, 2 * c, 1)
-            conv(pfx + ".attn.qkv.conv", c, c + 2 * (c // 64) * 32, 1, act=False)
-            conv(pfx + ".attn.proj.conv", c, c, 1, act=False)
-            dwconv(pfx + ".attn.pe.conv", c, False)
-            conv(pfx + ".ffn.0.conv", c, 2 * c, 1)
-            conv(pfx + ".ffn.1.conv", 2 * c, c, 1, act=False)
+            psablock(pfx, c)
             conv(pfx + ".cv2.conv", 2 * c, out[i], 1)
         elif mod in ("ELAN1", "RepNCSPELAN4"):            # (c2, c3, c4[, n]): cv1 -> two chunks; cv2 on the second, cv3 on cv2's; cv4 on all four
             c2, c3, c4 = args[:3]
@@ -414,9 +399,9 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False, a2_residual=Fa
                 conv(pfx + ".cv2.conv", c3 // 2, c4, 3)
                 conv(pfx + ".cv3.conv", c4, c4, 3)
             else:
-                repcsp(pfx + ".cv2.0", c3 // 2, c4, args[3])
+                c3k_block(pfx + ".cv2.0", c3 // 2, c4, args[3])
                 conv(pfx + ".cv2.1.conv", c4, c4, 3)
-                repcsp(pfx + ".cv3.0", c4, c4, args[3])
+                c3k_block(pfx + ".cv3.0", c4, c4, args[3])
                 conv(pfx + ".cv3.1.conv", c4, c4, 3)
             conv(pfx + ".cv4.conv", c3 + 2 * c4, c2, 1)
         elif mod == "AConv":                               # avg_pool2d(2, 1), then Conv 3x3 stride 2
@@ -454,15 +439,33 @@ def _parse_model(table, nc, ch, rep, c3k_all=False, dw_cls=False, a2_residual=Fa
     return specs
 
 
-def _scaled_specs(table, scales, scale, nc, **kw):
-    """_parse_model at one of the yaml's scales (depth, width, max_channels)."""
+def _scaled_specs(table, scales, scale, nc, reps={}, **kw):
+    """_parse_model at one of the yaml's scales (depth, width, max_channels); reps: layer -> its repeats as built, where a file tells them."""
     depth, width, maxc = scales[scale]
-    return _parse_model(table, nc, lambda c: _make_divisible(min(c, maxc) * width), lambda i, n: max(round(n * depth), 1) if n > 1 else n, **kw)
+    return _parse_model(table, nc, lambda c: _make_divisible(min(c, maxc) * width),
+                        lambda i, n: reps[i] if i in reps else (max(round(n * depth), 1) if n > 1 else n), **kw)
+
+
+def family_specs(graph: str, scale: str, nc: int = 4, table=None, **kw) -> list[tuple[str, tuple[int, ...], bool]]:
+    """(tensor name, OIHW shape, has_act) for every conv of a fused detect model of FAMILIES' row `graph`, in module order. table: the
+    family's yaml table as a check rebuilt it from a file; kw: _parse_model / _scaled_specs keywords that replace the row's own."""
+    f = family_row(graph)
+    if table is None:
+        table = f.table(scale) if callable(f.table) else f.table
+    if f.scales is None:                                   # YOLOv9: the tables carry their widths and repeats
+        return _parse_model(table, nc, lambda c: c, lambda i, n: n)
+    return _scaled_specs(table, f.scales, scale, nc, **(f.kw(scale) | kw))
+
+
+def family_synthetic(graph: str, seed=0, nc: int = 4, scale: str = "s", **knobs) -> dict[str, np.ndarray]:
+    """Seeded random fused weights of FAMILIES' row `graph`: synthetic_yolov8's draws (its docstring explains the knobs) in the order of
+    family_specs. seed: an int, or the generator to go on drawing from."""
+    return _draw_yolov8(np.random.default_rng(seed), family_specs(graph, scale, nc), **knobs)
 
 
 def yolov8_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
     """(tensor name, OIHW shape, has_act) for every conv of a fused YOLOv8 detect model."""
-    return _scaled_specs(YOLOV8_YAML, SCALES, scale, nc)
+    return family_specs("yolov8", scale, nc)
 
 
 def synthetic_yolov8(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0,
@@ -488,8 +491,8 @@ def synthetic_yolov8(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: flo
     then vary smoothly over neighbouring anchors, so the
     anchors that clear the confidence threshold come in clusters of several per object and NMS has boxes to
     suppress -- the load SURVEY.md 8d.2 asks for (1-3 k candidates in ~132 clusters) instead of isolated ones."""
-    return _draw_yolov8(np.random.default_rng(seed), yolov8_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias,
-                        box_weight_scale, smooth_cls)
+    return family_synthetic("yolov8", seed, nc, scale, cls_bias=cls_bias, gain=gain, box_decay=box_decay, level_bias=level_bias,
+                            box_weight_scale=box_weight_scale, smooth_cls=smooth_cls)
 
 
 def _draw_yolov8(rng, specs, cls_bias: float = -4.0, gain: float = 1.7, box_decay: float | tuple = 0.3, level_bias: tuple = (0.0, 0.0, 0.0),
@@ -519,6 +522,63 @@ def _draw_yolov8(rng, specs, cls_bias: float = -4.0, gain: float = 1.7, box_deca
     return t
 
 
+# --------------------------------------------------------------------------- what every family's check shares
+def _layer(k: str) -> int:
+    """The N of a `model.N.*` name, -1 for any other"""
+    p = k.split(".")
+    return int(p[1]) if p[0] == "model" and len(p) > 1 and p[1].isdigit() else -1
+
+
+def _shape(tensors: dict, name: str) -> tuple | None:
+    return tuple(np.shape(tensors[name])) if name in tensors else None
+
+
+_ONE2MANY = ("model.23.cv2.", "model.23.cv3.")             # v10Detect's / Detect26's one-to-many pair: ultralytics' fuse() drops it as a whole
+
+
+def _strict_compare(want, tensors: dict, head: int, exc: Exception, ignore=("dfl",), group=(), extra=(), attn=()) -> None:
+    """The strict comparison of a file with a family's specs; raises `exc` unless all of this holds. Every name of `want` ((name, shape,
+    ...) per conv) is there as `name.weight` with exactly that shape, and so is every (name, shape) of `extra` (YOLO12's gammas); no
+    other `.weight` or `.gamma` stands at layers 0 .. head; nothing at all stands past the head row; `.attn.` stands at the layers
+    `attn` only. The head row's modules `ignore` (Detect's constant `dfl`; None: the whole row, a classifier's unread Classify) are not
+    looked at, and the wanted names that start with one of `group` are there as a whole or missing as a whole."""
+    want = [(n, s) for n, s, *_ in want]
+    if group:
+        have = [n + ".weight" in tensors for n, _ in want if n.startswith(group)]
+        if any(have) and not all(have):
+            raise exc
+        if not any(have):
+            want = [(n, s) for n, s in want if not n.startswith(group)]
+    specs = {n + ".weight": s for n, s in want} | dict(extra)
+    if any(_shape(tensors, n) != s for n, s in specs.items()):
+        raise exc
+    for k in tensors:
+        i = _layer(k)
+        if i < 0 or (i == head and (ignore is None or k.split(".")[2] in ignore)):
+            continue
+        if i > head or (".attn." in k and i not in attn) or (k.endswith((".weight", ".gamma")) and k not in specs):
+            raise exc
+
+
+def _compare_family(graph: str, want, tensors: dict, exc: Exception, **kw) -> None:
+    """_strict_compare with the head row and the attention layers of FAMILIES' row `graph`"""
+    f = family_row(graph)
+    _strict_compare(want, tensors, _layer(f.head + "."), exc, attn=f.attn, **kw)
+
+
+def _scale_of_yolo11_widths(tensors: dict) -> str | None:
+    """The scale letter of a file built on yolo11.yaml's scales (YOLO26 and YOLO12 share them), None for another width: model.0's width
+    tells n / s / x apart; m and l share every width and differ in the repeats (model.2: 1 or 2 blocks)"""
+    c0 = _shape(tensors, "model.0.conv.weight")
+    return {16: "n", 32: "s", 96: "x", 64: "l" if "model.2.m.1.cv1.conv.weight" in tensors else "m"}.get(c0[0]) if c0 else None
+
+
+def _c3k_off_tensors(table, tensors: dict):
+    """The table with every plain C3k2 row's c3k flag read off the tensors (a C3k has `m.0.cv3`), not off a remembered rule"""
+    return [(f, n, m, (a[0], f"model.{i}.m.0.cv3.conv.weight" in tensors) + tuple(a[2:])) if m == "C3k2" and len(a) < 4 else (f, n, m, a)
+            for i, (f, n, m, a) in enumerate(table)]
+
+
 # --------------------------------------------------------------------------- YOLOv8-P2 (yolov8-p2.yaml)
 # geo-trax's train.sh `-p`: the backbone of yolov8.yaml, a neck that goes one Upsample + Concat(model.2) + C2f further down to
 # stride 4 (model.16-18) and back up (model.19-27), and Detect = model.28 on [18, 21, 24, 27] (strides 4 / 8 / 16 / 32). The Detect
@@ -530,7 +590,7 @@ def is_yolov8_p2(tensors: dict) -> bool:
 
 def yolov8_p2_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
     """(tensor name, OIHW shape, has_act) for every conv of a fused YOLOv8-P2 detect model."""
-    return _scaled_specs(YOLOV8_P2_YAML, SCALES, scale, nc)
+    return family_specs("yolov8-p2", scale, nc)
 
 
 def synthetic_yolov8_p2(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0, gain: float = 1.7,
@@ -539,7 +599,7 @@ def synthetic_yolov8_p2(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: 
     """Seeded random fused weights of the YOLOv8-P2 architecture, drawn like synthetic_yolov8's (same knobs, same order of draws
     over yolov8_p2_layer_specs). ``level_bias`` is added to the class logits of the stride-4/8/16/32 heads; the default silences the
     two coarse heads, whose random logits otherwise dominate, so that the stride-4 and stride-8 anchors are the ones that fire."""
-    return _draw_yolov8(np.random.default_rng(seed), yolov8_p2_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias, box_weight_scale)
+    return family_synthetic("yolov8-p2", seed, nc, scale, cls_bias=cls_bias, gain=gain, box_decay=box_decay, level_bias=level_bias, box_weight_scale=box_weight_scale)
 
 
 # --------------------------------------------------------------------------- YOLO11 (cfg/models/11/yolo11.yaml)
@@ -570,6 +630,8 @@ def check_yolo11(tensors: dict) -> None:
     """Raises NotImplementedError unless the names and shapes are those of a fused yolo11.yaml detect model. Other graphs built from
     the same blocks (YOLO12's A2C2f when is_yolo12() does not claim the file, yolo11-cls with C2PSA at model.9 -- the ReID embedder's, is_yolo11_cls --, -seg / -obb / -pose heads with a
     cv4 or proto branch) are never built into the wrong network."""
+    # Not _strict_compare: this test is weaker -- a hand-listed subset of the names, a few shapes -- and stays as it is, because the strict
+    # one would refuse files that load today (tests/test_families.py pins one: a model.22 without C3k members).
     no = NotImplementedError(f"checkpoint with attention / depthwise-Detect blocks in another arrangement than yolo11.yaml's: of that "
                              f"family only {YOLO11_TOPOLOGY} is implemented")
     shape = lambda n: tuple(np.shape(tensors[n])) if n in tensors else None
@@ -601,7 +663,7 @@ def check_yolo11(tensors: dict) -> None:
 
 def yolo11_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
     """(tensor name, OIHW shape, has_act) for every conv of a fused YOLO11 detect model (depthwise convs: (C, 1, 3, 3))."""
-    return _scaled_specs(YOLO11_YAML, YOLO11_SCALES, scale, nc, c3k_all=scale in "mlx", dw_cls=True)   # parse_model: c3k=True in every C3k2 of the larger scales
+    return family_specs("yolo11", scale, nc)
 
 
 def synthetic_yolo11(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0, gain: float = 1.7,
@@ -609,7 +671,7 @@ def synthetic_yolo11(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: flo
     """Seeded random fused weights of the YOLO11 architecture, drawn like synthetic_yolov8's (same knobs, the draws in the order of
     yolo11_layer_specs): weights ~ N(0, g^2 / fan_in) with g = gain in front of a SiLU and 1 for the activation-free layers (qkv,
     proj, pe, ffn.1, Detect's last 1x1s); a depthwise layer's fan-in is its 9 taps."""
-    return _draw_yolov8(np.random.default_rng(seed), yolo11_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias, box_weight_scale)
+    return family_synthetic("yolo11", seed, nc, scale, cls_bias=cls_bias, gain=gain, box_decay=box_decay, level_bias=level_bias, box_weight_scale=box_weight_scale)
 
 # --------------------------------------------------------------------------- YOLOv10 (cfg/models/v10/yolov10{n,s}.yaml)
 # What `YOLO("yolov10s.pt")` fine-tunes to: the YOLOv8 backbone and neck with SCDown (1x1 Conv, then a depthwise 3x3 stride 2 without
@@ -648,57 +710,28 @@ def is_yolov10(tensors: dict) -> bool:
 
 def check_yolov10(tensors: dict) -> str:
     """The scale ("n" / "s") of a fused yolov10.yaml detect model; raises NotImplementedError for every other arrangement of its blocks
-    (a cv4 / proto branch, attention elsewhere, Detect elsewhere, anything past model.23, another width). Strict like check_yolo11():
-    the table is rebuilt from what the tensors tell (repeats, C2f or C2fCIB per block row, large-kernel or not) and every shape is
-    compared. The one-to-many pair cv2 / cv3 may be missing as a whole (ultralytics' fuse() drops it)."""
+    (a cv4 / proto branch, attention elsewhere, Detect elsewhere, anything past model.23, another width). The table is rebuilt from what
+    the tensors tell (C2f or C2fCIB per block row, large-kernel or not) and compared strictly (_strict_compare). The one-to-many pair
+    cv2 / cv3 may be missing as a whole (ultralytics' fuse() drops it)."""
     no = NotImplementedError(f"checkpoint with YOLOv10's blocks (PSA, SCDown, a one-to-one head) in another arrangement than yolov10.yaml's: of that "
                              f"family only {YOLOV10_TOPOLOGY} is implemented")
-    shape = lambda n: tuple(np.shape(tensors[n])) if n in tensors else None
-    c0 = shape("model.0.conv.weight")
-    if c0 is None:
-        raise no
-    if c0[0] in _V10_BIGGER:
+    c0, nc_w = _shape(tensors, "model.0.conv.weight"), _shape(tensors, "model.23.one2one_cv3.0.2.weight")
+    if c0 is not None and c0[0] in _V10_BIGGER:
         raise NotImplementedError(f"{_V10_BIGGER[c0[0]]} (model.0 has {c0[0]} channels): of the YOLOv10 scales only n and s are implemented ({YOLOV10_TOPOLOGY})")
-    scale = {16: "n", 32: "s"}.get(c0[0])
-    if scale is None:
+    scale = {16: "n", 32: "s"}.get(c0[0]) if c0 else None
+    if scale is None or nc_w is None:
         raise no
-    layer = lambda k: int(k.split(".")[1]) if k.startswith("model.") and k.split(".")[1].isdigit() else -1
     table = []
     for i, (frm, n, mod, args) in enumerate(YOLOV10_YAML):
         if mod in ("C2f", "C2fCIB"):
             cib = f"model.{i}.m.0.cv1.0.conv.weight" in tensors
-            first = f"model.{i}.m.0." + ("cv1.0.conv.weight" if cib else "cv1.conv.weight")
-            if first not in tensors:
+            if f"model.{i}.m.0." + ("cv1.0.conv.weight" if cib else "cv1.conv.weight") not in tensors:
                 raise no
-            lk = cib and (shape(f"model.{i}.m.0.cv1.2.conv.weight") or (0, 0, 0))[2] == 7
+            lk = cib and (_shape(tensors, f"model.{i}.m.0.cv1.2.conv.weight") or (0, 0, 0))[2] == 7
             table.append((frm, n, "C2fCIB", (args[0], args[1] if len(args) > 1 else False, lk)) if cib else (frm, n, "C2f", args[:2]))
         else:
             table.append((frm, n, mod, args))
-    nc_w = shape("model.23.one2one_cv3.0.2.weight")
-    if nc_w is None:
-        raise no
-    want = _scaled_specs(table, YOLOV10_SCALES, scale, nc_w[0], dw_cls=True)
-    many = [n for n, _, _ in want if n.startswith(("model.23.cv2.", "model.23.cv3."))]
-    have_many = [n + ".weight" in tensors for n in many]
-    if any(have_many) and not all(have_many):
-        raise no
-    names = set()
-    for name, shp, _ in want:
-        if name in many and not have_many[0]:
-            continue
-        names.add(name)
-        if shape(name + ".weight") != shp:
-            raise no
-    for k in tensors:
-        i = layer(k)
-        if i < 0:
-            continue
-        if i > 23 or (".attn." in k and i != 10):
-            raise no
-        if i == 23 and k.split(".")[2] == "dfl":
-            continue
-        if k.endswith(".weight") and k[: -len(".weight")] not in names:
-            raise no
+    _compare_family("yolov10", family_specs("yolov10", scale, nc_w[0], table=table), tensors, no, group=_ONE2MANY)
     return scale
 
 
@@ -710,7 +743,7 @@ def yolov10_has_one2many(tensors: dict) -> bool:
 def yolov10_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
     """(tensor name, OIHW shape, has_act) for every conv of a fused YOLOv10 detect model (depthwise convs: (C, 1, k, k); the fused
     RepVGGDW of a large-kernel CIB: (C, 1, 7, 7) at m.{k}.cv1.2.conv), both head pairs included."""
-    return _scaled_specs(_yolov10_table(scale), YOLOV10_SCALES, scale, nc, dw_cls=True)
+    return family_specs("yolov10", scale, nc)
 
 
 def synthetic_yolov10(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0, gain: float = 1.7,
@@ -718,7 +751,7 @@ def synthetic_yolov10(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: fl
     """Seeded random fused weights of the YOLOv10 architecture, drawn like synthetic_yolo11's (same knobs, the draws in the order of
     yolov10_layer_specs). Both head pairs are emitted, cv2 / cv3 first, each with draws of its own, so the two heads detect
     different things; the knobs shape both alike."""
-    return _draw_yolov8(np.random.default_rng(seed), yolov10_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias, box_weight_scale)
+    return family_synthetic("yolov10", seed, nc, scale, cls_bias=cls_bias, gain=gain, box_decay=box_decay, level_bias=level_bias, box_weight_scale=box_weight_scale)
 
 # --------------------------------------------------------------------------- YOLO26 (cfg/models/26/yolo26.yaml)
 # What `YOLO("yolo26s.pt")` fine-tunes to: yolo11.yaml's rows with three changes. SPPF = model.9 has a cv1 WITHOUT activation and adds
@@ -761,66 +794,33 @@ def _yolo26_marks(tensors: dict) -> bool:
 def check_yolo26(tensors: dict) -> str:
     """The scale ("n" / "s" / "m" / "l" / "x") of a fused yolo26.yaml detect model; raises NotImplementedError for every other
     arrangement of its blocks (a cv4 / proto branch, attention elsewhere, Detect elsewhere, reg_max other than 1, anything past
-    model.23, another width). Strict like check_yolov10(): the table is rebuilt from what the tensors tell (c3k or not per C3k2) and
-    every shape is compared. The one-to-many pair cv2 / cv3 may be missing as a whole (ultralytics' fuse() drops it)."""
+    model.23, another width). The table is rebuilt from what the tensors tell (c3k or not per C3k2, model.22's repeats) and compared
+    strictly (_strict_compare). The one-to-many pair cv2 / cv3 may be missing as a whole (ultralytics' fuse() drops it)."""
     no = NotImplementedError(f"checkpoint with YOLO26's blocks (attention inside model.22's C3k2, a 4-output box branch, a one-to-one head) in "
                              f"another arrangement than yolo26.yaml's: of that family only {YOLO26_TOPOLOGY} is implemented")
-    shape = lambda n: tuple(np.shape(tensors[n])) if n in tensors else None
-    c0, c1 = shape("model.0.conv.weight"), shape("model.1.conv.weight")
-    nc_w = shape("model.23.one2one_cv3.0.2.weight")
-    if c0 is None or c1 is None or nc_w is None:
+    nc_w = _shape(tensors, "model.23.one2one_cv3.0.2.weight")
+    if "model.0.conv.weight" not in tensors or "model.1.conv.weight" not in tensors or nc_w is None:
         raise no
     for k in ("model.23.one2one_cv2.0.2.weight", "model.23.cv2.0.2.weight"):
-        if shape(k) is not None and shape(k)[0] != 4:
-            raise NotImplementedError(f"{k} has {shape(k)[0]} rows (reg_max = {shape(k)[0] // 4}) in a graph with YOLO26's attention inside model.22: "
+        rows = (_shape(tensors, k) or (4,))[0]
+        if rows != 4:
+            raise NotImplementedError(f"{k} has {rows} rows (reg_max = {rows // 4}) in a graph with YOLO26's attention inside model.22: "
                                       f"only reg_max = 1, a 4-row box convolution, is implemented there ({YOLO26_TOPOLOGY})")
-    # model.0's width tells n / s / x apart; m and l share every width and differ in the repeats (model.2: 1 or 2 blocks)
-    scale = {16: "n", 32: "s", 96: "x"}.get(c0[0]) or ({64: "l" if "model.2.m.1.cv1.conv.weight" in tensors else "m"}.get(c0[0]))
-    if scale is None:
-        raise no
-    layer = lambda k: int(k.split(".")[1]) if k.startswith("model.") and k.split(".")[1].isdigit() else -1
-    table = []
-    for i, (frm, n, mod, args) in enumerate(YOLO26_YAML):
-        if mod == "C3k2" and len(args) < 4:                # c3k or not: off the tensors, not off a remembered flag
-            table.append((frm, n, mod, (args[0], f"model.{i}.m.0.cv3.conv.weight" in tensors) + tuple(args[2:])))
-        else:
-            table.append((frm, n, mod, args))
-    depth, width, maxc = YOLO11_SCALES[scale]
+    scale = _scale_of_yolo11_widths(tensors)
     n22 = 0                                                # model.22's repeats (the yaml writes 1, which no scale multiplies): off the tensors, 1 or 2
     while f"model.22.m.{n22}.0.cv1.conv.weight" in tensors:
         n22 += 1
-    if n22 not in (1, 2):
+    if scale is None or n22 not in (1, 2):
         raise no
-    want = _parse_model(table, nc_w[0], lambda c: _make_divisible(min(c, maxc) * width),
-                        lambda i, n: n22 if i == 22 else (max(round(n * depth), 1) if n > 1 else n), dw_cls=True)
-    many = [n for n, _, _ in want if n.startswith(("model.23.cv2.", "model.23.cv3."))]
-    have_many = [n + ".weight" in tensors for n in many]
-    if any(have_many) and not all(have_many):
-        raise no
-    names = set()
-    for name, shp, _ in want:
-        if name in many and not have_many[0]:
-            continue
-        names.add(name)
-        if shape(name + ".weight") != shp:
-            raise no
-    for k in tensors:
-        i = layer(k)
-        if i < 0:
-            continue
-        if i > 23 or (".attn." in k and i not in (10, 22)):
-            raise no
-        if i == 23 and k.split(".")[2] == "dfl":
-            continue
-        if k.endswith(".weight") and k[: -len(".weight")] not in names:
-            raise no
+    want = family_specs("yolo26", scale, nc_w[0], table=_c3k_off_tensors(YOLO26_YAML, tensors), reps={22: n22}, c3k_all=False)
+    _compare_family("yolo26", want, tensors, no, group=_ONE2MANY)
     return scale
 
 
 def yolo26_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
     """(tensor name, OIHW shape, has_act) for every conv of a fused YOLO26 detect model, both head pairs included (the last box
     convolutions: (4, cb, 1, 1))."""
-    return _scaled_specs(YOLO26_YAML, YOLO11_SCALES, scale, nc, c3k_all=scale in "mlx", dw_cls=True)
+    return family_specs("yolo26", scale, nc)
 
 
 def synthetic_yolo26(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0, gain: float = 1.7,
@@ -828,7 +828,7 @@ def synthetic_yolo26(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: flo
     """Seeded random fused weights of the YOLO26 architecture, drawn like synthetic_yolov10's (same knobs, the draws in the order of
     yolo26_layer_specs; both head pairs, each with draws of its own). The last box convolutions give the four distances directly:
     damped weights (box_weight_scale) around the biases YOLO26_BOX_BIAS, one of which is negative."""
-    return _draw_yolov8(np.random.default_rng(seed), yolo26_layer_specs(scale, nc), cls_bias, gain, 0.3, (0.0, 0.0, 0.0), box_weight_scale)
+    return family_synthetic("yolo26", seed, nc, scale, cls_bias=cls_bias, gain=gain, box_weight_scale=box_weight_scale)   # box_decay / level_bias: fixed
 
 # --------------------------------------------------------------------------- YOLO12 (cfg/models/12/yolo12.yaml)
 # What `YOLO("yolo12s.pt")` fine-tunes to: yolo11.yaml's first six rows, then A2C2f blocks in place of its C3k2 / SPPF / C2PSA: with
@@ -852,55 +852,24 @@ def is_yolo12(tensors: dict) -> bool:
 
 def _yolo12_want(tensors_or_none, scale: str, nc: int):
     """(conv specs, gamma specs) of yolo12<scale>.yaml; c3k per C3k2 row off the tensors when some are given, else parse_model's rule"""
-    table = []
-    for i, (frm, n, mod, args) in enumerate(YOLO12_YAML):
-        if mod == "C3k2" and tensors_or_none is not None:
-            table.append((frm, n, mod, (args[0], f"model.{i}.m.0.cv3.conv.weight" in tensors_or_none) + tuple(args[2:])))
-        else:
-            table.append((frm, n, mod, args))
     gammas: list = []
-    specs = _scaled_specs(table, YOLO11_SCALES, scale, nc, c3k_all=tensors_or_none is None and scale in "mlx", dw_cls=True,
-                          a2_residual=scale in "lx", gammas=gammas)
-    return specs, gammas
+    if tensors_or_none is None:
+        return family_specs("yolo12", scale, nc, gammas=gammas), gammas
+    return family_specs("yolo12", scale, nc, table=_c3k_off_tensors(YOLO12_YAML, tensors_or_none), c3k_all=False, gammas=gammas), gammas
 
 
 def check_yolo12(tensors: dict) -> str:
     """The scale ("n" / "s" / "m" / "l" / "x") of a fused yolo12.yaml detect model; raises NotImplementedError, with a message that
     names yolo12, for every other arrangement of its blocks (attention elsewhere, Detect elsewhere, a cv4 / proto branch, anything past
-    model.21, another width or repeat count, a gamma where the scale has none). Strict like check_yolo26(): the table is rebuilt from
-    model.0's width and the repeats, and every shape is compared. yolo12.yaml's scales are yolo11.yaml's."""
+    model.21, another width or repeat count, a gamma where the scale has none). The table is rebuilt from model.0's width and the
+    repeats and compared strictly (_strict_compare), the gammas with it. yolo12.yaml's scales are yolo11.yaml's."""
     no = NotImplementedError(f"checkpoint with YOLO12's blocks (A2C2f with area attention at model.6 / 8) in another arrangement than yolo12.yaml's: "
                              f"of that family only {YOLO12_TOPOLOGY} is implemented")
-    shape = lambda n: tuple(np.shape(tensors[n])) if n in tensors else None
-    c0, nc_w = shape("model.0.conv.weight"), shape("model.21.cv3.0.2.weight")
-    if c0 is None or nc_w is None:
-        raise no
-    # model.0's width tells n / s / x apart; m and l share every width and differ in the repeats (model.2: 1 or 2 blocks)
-    scale = {16: "n", 32: "s", 96: "x"}.get(c0[0]) or ({64: "l" if "model.2.m.1.cv1.conv.weight" in tensors else "m"}.get(c0[0]))
-    if scale is None:
+    scale, nc_w = _scale_of_yolo11_widths(tensors), _shape(tensors, "model.21.cv3.0.2.weight")
+    if scale is None or nc_w is None:
         raise no
     want, gammas = _yolo12_want(tensors, scale, nc_w[0])
-    names = set()
-    for name, shp, _ in want:
-        names.add(name)
-        if shape(name + ".weight") != shp:
-            raise no
-    for name, shp in gammas:
-        if shape(name) != shp:
-            raise no
-    layer = lambda k: int(k.split(".")[1]) if k.startswith("model.") and k.split(".")[1].isdigit() else -1
-    for k in tensors:
-        i = layer(k)
-        if i < 0:
-            continue
-        if i > 21 or (".attn." in k and i not in YOLO12_AREAS):
-            raise no
-        if i == 21 and k.split(".")[2] == "dfl":
-            continue
-        if k.endswith(".gamma") and (k, shape(k)) not in gammas:
-            raise no
-        if k.endswith(".weight") and k[: -len(".weight")] not in names:
-            raise no
+    _compare_family("yolo12", want, tensors, no, extra=gammas)
     return scale
 
 
@@ -921,7 +890,7 @@ def synthetic_yolo12(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: flo
     yolo12_layer_specs), then the gammas of scales l / x ~ N(gamma, (gamma / 4)^2) from the same generator: ultralytics starts them at
     0.01, which would hide the block behind its own input; the default lets both terms of x + gamma * y count."""
     rng = np.random.default_rng(seed)
-    t = _draw_yolov8(rng, yolo12_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias, box_weight_scale)
+    t = family_synthetic("yolo12", rng, nc, scale, cls_bias=cls_bias, gain=gain, box_decay=box_decay, level_bias=level_bias, box_weight_scale=box_weight_scale)
     for name, shp in yolo12_gamma_specs(scale):
         t[name] = (gamma + 0.25 * gamma * rng.standard_normal(shp)).astype(np.float32)
     return t
@@ -980,10 +949,9 @@ def check_yolov5u(tensors: dict) -> str:
     """The scale ("n" / "s" / "m" / "l" / "x") of a fused yolov5.yaml detect model with the anchor-free head; raises NotImplementedError,
     with a message that names yolov5.yaml and what is implemented, for everything else of the family: the P6 files, an anchor-based
     export, YOLOv3u, -seg / -cls heads, and any tensor whose shape is not what model.0's width (16 / 32 / 48 / 64 / 80 = n / s / m / l /
-    x) gives through yolov5.yaml's width, depth and max_channels. Strict like check_yolo12(): every shape is compared."""
+    x) gives through yolov5.yaml's width, depth and max_channels (_strict_compare)."""
     only = f"of that family only {YOLOV5U_TOPOLOGY} is implemented"
     no = lambda what: NotImplementedError(f"{what}: {only}")
-    shape = lambda n: tuple(np.shape(tensors[n])) if n in tensors else None
     if "model.24.m.0.weight" in tensors or "model.33.m.0.weight" in tensors or any(k.startswith("model.") and k.endswith(".anchors") for k in tensors):
         raise no("an anchor-based export of the original YOLOv5 (Detect with `anchors` and `m.{l}` output convolutions, not yolov5.yaml's "
                  "anchor-free yolov5*u head)")
@@ -998,32 +966,17 @@ def check_yolov5u(tensors: dict) -> str:
     if "model.33.cv2.0.0.conv.weight" in tensors or "model.33.dfl.conv.weight" in tensors:
         raise no("a yolov5*6u checkpoint (yolov5-p6.yaml: four Detect levels, Detect = model.33)")
     bad = no("checkpoint with yolov5.yaml's 6x6 stem in another arrangement than yolov5.yaml's")
-    c0, nc_w = shape("model.0.conv.weight"), shape("model.24.cv3.0.2.weight")
-    if not is_yolov5u(tensors) or nc_w is None:
+    nc_w = _shape(tensors, "model.24.cv3.0.2.weight")
+    scale = {16: "n", 32: "s", 48: "m", 64: "l", 80: "x"}.get(_shape(tensors, "model.0.conv.weight")[0])
+    if not is_yolov5u(tensors) or nc_w is None or scale is None:
         raise bad
-    scale = {16: "n", 32: "s", 48: "m", 64: "l", 80: "x"}.get(c0[0])
-    if scale is None:
-        raise bad
-    want = {n: s for n, s, _ in yolov5u_layer_specs(scale, nc_w[0])}
-    for name, shp in want.items():
-        if shape(name + ".weight") != shp:
-            raise bad
-    for k in tensors:
-        p = k.split(".")
-        if p[0] != "model" or len(p) < 2 or not p[1].isdigit():
-            continue
-        if int(p[1]) > 24:
-            raise bad
-        if p[1] == "24" and p[2] == "dfl":
-            continue
-        if k.endswith(".weight") and k[: -len(".weight")] not in want:
-            raise bad
+    _compare_family("yolov5u", family_specs("yolov5u", scale, nc_w[0]), tensors, bad)
     return scale
 
 
 def yolov5u_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
     """(tensor name, OIHW shape, has_act) for every conv of a fused YOLOv5u detect model (model.0 is 6x6, model.10 / 14 are 1x1)"""
-    return _scaled_specs(YOLOV5_YAML, YOLOV5_SCALES, scale, nc)
+    return family_specs("yolov5u", scale, nc)
 
 
 def synthetic_yolov5u(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0, gain: float = 1.7,
@@ -1031,7 +984,7 @@ def synthetic_yolov5u(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: fl
     """Seeded random fused weights of the YOLOv5u architecture, drawn like synthetic_yolov8's (same knobs, the draws in the order of
     yolov5u_layer_specs), plus Detect's constant DFL convolution `model.24.dfl.conv.weight` (0 .. 15), which every real file carries and
     is_yolov5u() asks for."""
-    t = _draw_yolov8(np.random.default_rng(seed), yolov5u_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias, box_weight_scale)
+    t = family_synthetic("yolov5u", seed, nc, scale, cls_bias=cls_bias, gain=gain, box_decay=box_decay, level_bias=level_bias, box_weight_scale=box_weight_scale)
     t["model.24.dfl.conv.weight"] = np.arange(16, dtype=np.float32).reshape(1, 16, 1, 1)
     return t
 
@@ -1106,35 +1059,28 @@ def is_yolov9(tensors: dict) -> bool:
 
 def check_yolov9(tensors: dict) -> str:
     """The scale ("t" / "s" / "m" / "c") of a fused yolov9.yaml detect model; raises NotImplementedError for every other arrangement of
-    its blocks (yolov9e's second backbone, anything past model.22, Detect elsewhere, another width or repeat count). Strict like
-    check_yolov10(): model.0's width names the candidate scales, and every tensor name and shape must be the candidate table's."""
+    its blocks (yolov9e's second backbone, anything past model.22, Detect elsewhere, another width or repeat count). The widths of
+    model.0 and of model.2's cv1 name the one candidate scale (s and m share model.0's), whose table is compared strictly (_strict_compare)."""
     no = NotImplementedError(f"checkpoint with YOLOv9's blocks (RepNCSPELAN4, ADown / AConv, SPPELAN) in another arrangement than yolov9{{t,s,m,c}}.yaml's "
                              f"(yolov9e with its CBLinear / CBFuse second backbone included): of that family only {YOLOV9_TOPOLOGY} is implemented")
-    shape = lambda n: tuple(np.shape(tensors[n])) if n in tensors else None
-    c0, nc_w = shape("model.0.conv.weight"), shape("model.22.cv3.0.2.weight")
-    if c0 is None or nc_w is None:
+    c0, c2, nc_w = (_shape(tensors, n) for n in ("model.0.conv.weight", "model.2.cv1.conv.weight", "model.22.cv3.0.2.weight"))
+    scale = next((s for s, w in _YOLOV9_WIDTHS.items() if c0 and c2 and (w[0], w[2][0][1]) == (c0[0], c2[0])), None)
+    if scale is None or nc_w is None:
         raise no
-    have = {k[: -len(".weight")]: tuple(np.shape(v)) for k, v in tensors.items()
-            if k.startswith("model.") and k.endswith(".weight") and ".dfl." not in k}
-    for scale, w in _YOLOV9_WIDTHS.items():
-        if w[0] != c0[0]:
-            continue
-        want = {n: s for n, s, _ in yolov9_layer_specs(scale, nc_w[0])}
-        if want == have:
-            return scale
-    raise no
+    _compare_family("yolov9", family_specs("yolov9", scale, nc_w[0]), tensors, no)
+    return scale
 
 
 def yolov9_layer_specs(scale: str = "s", nc: int = 4) -> list[tuple[str, tuple[int, ...], bool]]:
     """(tensor name, OIHW shape, has_act) for every conv of a fused YOLOv9 detect model (RepConv fused: `...m.{k}.cv1.conv` is one 3x3)"""
-    return _parse_model(_yolov9_table(scale), nc, lambda c: c, lambda i, n: n)
+    return family_specs("yolov9", scale, nc)
 
 
 def synthetic_yolov9(seed: int = 0, nc: int = 4, scale: str = "s", cls_bias: float = -4.0, gain: float = 1.7,
                      box_decay: float | tuple = 0.3, level_bias: tuple = (0.0, 0.0, 0.0), box_weight_scale: float = 0.3) -> dict[str, np.ndarray]:
     """Seeded random fused weights of the YOLOv9 architecture, drawn like synthetic_yolov8's (same knobs, the draws in the order of
     yolov9_layer_specs)."""
-    return _draw_yolov8(np.random.default_rng(seed), yolov9_layer_specs(scale, nc), cls_bias, gain, box_decay, level_bias, box_weight_scale)
+    return family_synthetic("yolov9", seed, nc, scale, cls_bias=cls_bias, gain=gain, box_decay=box_decay, level_bias=level_bias, box_weight_scale=box_weight_scale)
 
 
 def pad_yolov9_channels(tensors: dict, scale: str) -> tuple[dict, dict]:
@@ -1230,7 +1176,7 @@ def detector_meta(tensors: dict) -> dict | None:
     if m is None or np.size(m) < 4:
         return None
     m = np.asarray(m).ravel()
-    return dict(family={10: "yolov10", 26: "yolo26"}.get(int(m[0]), str(int(m[0]))), one2many=bool(m[1]), end2end=bool(m[2]), max_det=int(m[3]))
+    return dict(family={f.meta: f.graph for f in FAMILIES if f.meta}.get(int(m[0]), str(int(m[0]))), one2many=bool(m[1]), end2end=bool(m[2]), max_det=int(m[3]))
 
 
 def fold_repvggdw(t: dict[str, np.ndarray]) -> dict[str, np.ndarray]:
@@ -1288,42 +1234,100 @@ RTDETR_TOPOLOGIES = ("rtdetr-l (HGNetv2 + AIFI + CCFM, RTDETRDecoder = model.28)
                      "yolov8-rtdetr (the YOLOv8 backbone + neck model.0-21, RTDETRDecoder = model.22)")
 
 
+def _rtdetr_decoders(tensors: dict) -> list[str]:
+    """The layer numbers that hold an RTDETRDecoder, sorted"""
+    return sorted({k.split(".")[1] for k in tensors if k.startswith("model.") and ".decoder.layers." in k and k.split(".")[2] == "decoder"})
+
+
+def _has(tensors: dict, *prefixes: str) -> bool:
+    return all(any(k.startswith(p) for k in tensors) for p in prefixes)
+
+
+# --------------------------------------------------------------------------- the family table
+@dataclass(frozen=True)
+class Family:
+    """One detector graph this build runs: how its files are recognised, checked, spec'd and named."""
+    graph: str                      # detector_topology's name for it
+    head: str                       # the head's prefix: Detect / v10Detect / RTDETRDecoder
+    topology: str                   # the sentence the refusals quote
+    claims: Callable[[dict], bool]  # asked in FAMILIES' order; the first row that says yes takes the file, for its check to accept or refuse
+    check: Callable[[dict], str | None] | None = None   # raises NotImplementedError for a file that is not the family's; the scale letter where there is one
+    table: list | Callable[[str], list] | None = None   # the yaml table, or scale -> table where the scales differ in rows
+    scales: dict | None = None      # the yaml's scales; None: the tables carry their widths (YOLOv9)
+    kw: Callable[[str], dict] = lambda scale: {}        # _parse_model's keywords at a scale
+    end2end: bool = False           # the family's own head is a one-to-one pair (one2one_cv2 / one2one_cv3) with the top-300 cut, no NMS
+    attn: tuple = ()                # the layers that may hold `.attn.` tensors
+    stem: str | None = None         # ultralytics' yaml file is <stem><scale>.yaml; None: the graph's name
+    meta: int = 0                   # the family number tools/convert_weights.py writes into `detector.meta`
+    rtdetr: bool = False            # the RTDETR predictor family: stretch to the square, no NMS, the 300-query score stage
+
+
+_YOLO11_KW = lambda s: dict(c3k_all=s in "mlx", dw_cls=True)   # parse_model: c3k = True in every C3k2 of the larger scales; Detect's class branch is DWConv + Conv
+_V8_TOPOLOGY = "yolov8 detect (yolov8{n,s,m,l,x}: Conv / C2f backbone + neck, SPPF = model.9, Detect = model.22 on model.15 / 18 / 21)"
+_P2_TOPOLOGY = "yolov8-p2 detect (yolov8{n,s,m,l,x}-p2: yolov8.yaml's backbone, a neck down to stride 4, Detect = model.28 on model.18 / 21 / 24 / 27)"
+
+# The order is the order of asking. Every `claims` is a cheap look at the names; what a row claims, its `check` then accepts or refuses
+# in the family's own words, so a near miss of one family never falls through to the next.
+FAMILIES: tuple[Family, ...] = (
+    # RT-DETR first: a decoder anywhere makes the file the RTDETR predictor's, whatever its trunk (yolov8-rtdetr has YOLOv8's)
+    Family("rtdetr-l", "model.28", RTDETR_TOPOLOGIES[0], lambda t: _rtdetr_decoders(t) == ["28"] and _has(t, "model.0.stem1."), rtdetr=True),
+    Family("yolov8-rtdetr", "model.22", RTDETR_TOPOLOGIES[1],
+           lambda t: _rtdetr_decoders(t) == ["22"] and "model.0.conv.weight" in t and _has(t, "model.9.cv1.", "model.21.cv2."), rtdetr=True),
+    # YOLOv10 before the YOLO11 relatives: its PSA has `.attn.` too. check: another arrangement, and the scales that are not implemented
+    Family("yolov10", "model.23", YOLOV10_TOPOLOGY, is_yolov10, check_yolov10, _yolov10_table, YOLOV10_SCALES, lambda s: dict(dw_cls=True),
+           end2end=True, attn=(10,), meta=10),
+    # asked before YOLO11's check, so that a YOLO12 file gets its own messages
+    Family("yolo12", "model.21", YOLO12_TOPOLOGY, is_yolo12, check_yolo12, YOLO12_YAML, YOLO11_SCALES,
+           lambda s: dict(c3k_all=s in "mlx", dw_cls=True, a2_residual=s in "lx"), attn=tuple(YOLO12_AREAS)),
+    # is_yolo26, or one of its marks only: check refuses that in YOLO26's words (reg_max other than 1, -seg / -obb / -pose heads)
+    Family("yolo26", "model.23", YOLO26_TOPOLOGY, lambda t: is_yolo26(t) or _yolo26_marks(t), check_yolo26, YOLO26_YAML, YOLO11_SCALES, _YOLO11_KW,
+           end2end=True, attn=(10, 22), meta=26),
+    # whatever else has attention or a depthwise Detect class branch. check: yolo11-cls, -seg, -obb, -pose, stray attention ...
+    Family("yolo11", "model.23", YOLO11_TOPOLOGY, has_yolo11_blocks, check_yolo11, YOLO11_YAML, YOLO11_SCALES, _YOLO11_KW, attn=(10,)),
+    # is_yolov9, or GELAN blocks without model.9.cv5: yolov9e, which check refuses by name
+    Family("yolov9", "model.22", YOLOV9_TOPOLOGY, _has_gelan, check_yolov9, _yolov9_table),
+    # asked last, in front of the YOLOv8 rows only: no other family's route changes. check: the P6 files, an anchor-based export,
+    # YOLOv3u, -seg / -cls, a wrong shape
+    Family("yolov5u", "model.24", YOLOV5U_TOPOLOGY, lambda t: is_yolov5u(t) or _yolov5_lookalike(t), check_yolov5u, YOLOV5_YAML, YOLOV5_SCALES, stem="yolov5"),
+    # the YOLOv8 pair has no check: what nothing above claims is built as YOLOv8, and the library refuses what it cannot build
+    Family("yolov8-p2", "model.28", _P2_TOPOLOGY, is_yolov8_p2, None, YOLOV8_P2_YAML, SCALES),
+    Family("yolov8", "model.22", _V8_TOPOLOGY, lambda t: True, None, YOLOV8_YAML, SCALES),
+)
+
+
+def family_row(graph: str) -> Family:
+    return next(f for f in FAMILIES if f.graph == graph)
+
+
+class DetectorFamily(NamedTuple):
+    """detector_family's answer"""
+    graph: str
+    head: str
+    scale: str | None               # where the family's files differ by scale and its check tells it
+    end2end: bool                   # the family has a one-to-one head
+    rtdetr: bool
+    nc_key: str                     # the tensor whose row count is nc
+
+
+def detector_family(tensors: dict) -> DetectorFamily:
+    """Which of FAMILIES a detector checkpoint belongs to, read off the tensor names the way the reference reads its model yaml; the
+    family's check runs here, once. An RT-DETR layout other than the two rows' (rtdetr-x with its decoder at model.32, ResNet
+    backbones, ...) raises NotImplementedError, and so does a file with a family's blocks in another arrangement than its yaml's."""
+    f = next(f for f in FAMILIES if f.claims(tensors))
+    if is_rtdetr(tensors) and not f.rtdetr:
+        where = ", ".join(f"model.{d}" for d in _rtdetr_decoders(tensors))
+        raise NotImplementedError(f"RT-DETR checkpoint with its decoder at {where}: only {RTDETR_TOPOLOGIES[0]} and "
+                                  f"{RTDETR_TOPOLOGIES[1]} are implemented")
+    scale = f.check(tensors) if f.check else None
+    last = ".enc_score_head.weight" if f.rtdetr else ".one2one_cv3.0.2.weight" if f.end2end else ".cv3.0.2.weight"
+    return DetectorFamily(f.graph, f.head, scale, f.end2end, f.rtdetr, f.head + last)
+
+
 def detector_topology(tensors: dict) -> tuple[str, str]:
-    """(graph, head prefix) of a detector checkpoint, read off the tensor names the way the reference reads its model yaml:
-    ("yolov8", "model.22"), ("yolov8-p2", "model.28"), ("yolo11", "model.23"), ("yolov10", "model.23"), ("yolo26", "model.23"), ("yolo12", "model.21"), ("yolov9", "model.22"), ("yolov5u", "model.24"), ("rtdetr-l", "model.28") or
-    ("yolov8-rtdetr", "model.22").
-    An RT-DETR layout other than those two (rtdetr-x with its decoder at model.32, ResNet backbones, ...) raises NotImplementedError,
-    and so does a file with YOLO11's, YOLOv10's, YOLO12's or YOLO26's blocks (attention, a depthwise Detect class branch, SCDown + a one-to-one head,
-    attention inside model.22 + a 4-output box branch) in another arrangement than their yaml's."""
-    if not is_rtdetr(tensors):
-        if is_yolov10(tensors):
-            check_yolov10(tensors)                         # raises for another arrangement, and for the scales that are not implemented
-            return "yolov10", "model.23"
-        if is_yolo12(tensors):                             # asked before YOLO11's check, so that a YOLO12 file gets its own messages
-            check_yolo12(tensors)                          # raises for another arrangement of A2C2f's blocks
-            return "yolo12", "model.21"
-        if is_yolo26(tensors) or _yolo26_marks(tensors):
-            check_yolo26(tensors)                          # raises for another arrangement, reg_max other than 1, -seg / -obb / -pose heads
-            return "yolo26", "model.23"
-        if has_yolo11_blocks(tensors):
-            check_yolo11(tensors)                          # raises for yolo11-cls, -seg, -obb, -pose, stray attention ...
-            return "yolo11", "model.23"
-        if _has_gelan(tensors):                            # is_yolov9, or GELAN blocks without model.9.cv5: yolov9e, which check_yolov9 refuses by name
-            check_yolov9(tensors)
-            return "yolov9", "model.22"
-        if is_yolov5u(tensors) or _yolov5_lookalike(tensors):   # asked last, in front of the YOLOv8 default only: no other family's route changes
-            check_yolov5u(tensors)                         # raises for the P6 files, an anchor-based export, YOLOv3u, -seg / -cls, a wrong shape
-            return "yolov5u", "model.24"
-        return ("yolov8-p2", "model.28") if is_yolov8_p2(tensors) else ("yolov8", "model.22")
-    decs = sorted({k.split(".")[1] for k in tensors if k.startswith("model.") and ".decoder.layers." in k and k.split(".")[2] == "decoder"})
-    has = lambda pfx: any(k.startswith(pfx) for k in tensors)
-    if decs == ["28"] and has("model.0.stem1."):
-        return "rtdetr-l", "model.28"
-    if decs == ["22"] and "model.0.conv.weight" in tensors and has("model.9.cv1.") and has("model.21.cv2."):
-        return "yolov8-rtdetr", "model.22"
-    where = ", ".join(f"model.{d}" for d in decs)
-    raise NotImplementedError(f"RT-DETR checkpoint with its decoder at {where}: only {RTDETR_TOPOLOGIES[0]} and "
-                              f"{RTDETR_TOPOLOGIES[1]} are implemented")
+    """(graph, head prefix) of a detector checkpoint, detector_family's first two entries: ("yolov8", "model.22"), ("yolov8-p2", "model.28"),
+    ("yolo11", "model.23"), ("yolov10", "model.23"), ("yolo26", "model.23"), ("yolo12", "model.21"), ("yolov9", "model.22"), ("yolov5u",
+    "model.24"), ("rtdetr-l", "model.28") or ("yolov8-rtdetr", "model.22"); it raises what detector_family raises."""
+    return tuple(detector_family(tensors)[:2])
 
 
 def fuse_repconv(t: dict[str, np.ndarray]) -> dict[str, np.ndarray]:
@@ -1588,16 +1592,7 @@ def is_yolov8_cls(tensors: dict) -> bool:
         reps.append(n)
     if min(reps) < 1:
         raise unsupported
-    want = _cls_backbone_specs(c1, 2 * c1, 4 * c1, 8 * c1, 16 * c1, tuple(reps))
-    names = {n for n, _ in want}
-    for name, shape in want:
-        w = tensors.get(name + ".weight")
-        if w is None or tuple(np.shape(w)) != shape:
-            raise unsupported
-    extra = {k.rsplit(".", 1)[0] for k in tensors if k.startswith(("model.1.", "model.2.", "model.3.", "model.4.", "model.5.", "model.6.",
-                                                                  "model.7.", "model.8.")) and k.endswith(".weight")} - names
-    if extra:
-        raise unsupported
+    _strict_compare(_cls_backbone_specs(c1, 2 * c1, 4 * c1, 8 * c1, 16 * c1, tuple(reps)), tensors, 9, unsupported, ignore=None)
     return True
 
 
@@ -1630,23 +1625,16 @@ def is_yolo11_cls(tensors: dict) -> bool:
     the repeat counts and c3k-or-not imply, so such a file is never built into the wrong network."""
     if "model.0.conv.weight" not in tensors or is_rtdetr(tensors):
         return False
-    layer = lambda k: int(k.split(".")[1]) if k.startswith("model.") and k.split(".")[1].isdigit() else -1
-    if any(layer(k) > 10 for k in tensors):                # a neck or a Detect head: no classifier
+    if any(_layer(k) > 10 for k in tensors):               # a neck or a Detect head: no classifier
         return False
     if not any(".attn." in k for k in tensors):            # no attention anywhere: YOLOv8-cls or something else, not ours to judge
         return False
     unsupported = NotImplementedError(f"ReID model: of the classifiers with attention blocks only {YOLO11_CLS_TOPOLOGY} is implemented "
                                       f"(next to YOLOv8-cls); this file has another topology")
-    shape = lambda n: tuple(np.shape(tensors[n + ".weight"])) if n + ".weight" in tensors else None
     c0 = int(np.shape(tensors["model.0.conv.weight"])[0])
-    if c0 % 16 or any(".attn." in k and layer(k) != 9 for k in tensors):
-        raise unsupported
     width = 4 * c0 / 64                                    # model.0 is ch(64): the scale's width factor, max_channels aside
-    c8 = shape("model.8.cv2.conv")
-    if c8 is None:
-        raise unsupported
     maxc = {0.25: 1024, 0.5: 1024, 1.0: 512, 1.5: 512}.get(width / 4)
-    if maxc is None:
+    if c0 % 16 or "model.8.cv2.conv.weight" not in tensors or maxc is None:
         raise unsupported
     reps, c3k = {}, {}
     for i in (2, 4, 6, 8):
@@ -1660,15 +1648,8 @@ def is_yolo11_cls(tensors: dict) -> bool:
     reps[9] = n9
     if min(reps.values()) < 1 or len(set(reps.values())) != 1 or not (c3k[6] and c3k[8]) or c3k[2] != c3k[4] or c3k[2] != (width / 4 >= 1.0):
         raise unsupported
-    table = [(f, n, m, (a[0], c3k[i]) + tuple(a[2:]) if m == "C3k2" else a) for i, (f, n, m, a) in enumerate(YOLO11_CLS_YAML[:10])]
-    want = _parse_model(table, 0, lambda c: _make_divisible(min(c, maxc) * width / 4), lambda i, n: reps[i] if n > 1 else n)
-    names = {n for n, _, _ in want}
-    for name, shp, _ in want:
-        if shape(name) != shp:
-            raise unsupported
-    extra = {k.rsplit(".", 1)[0] for k in tensors if 0 <= layer(k) <= 9 and k.endswith(".weight")} - names
-    if extra:
-        raise unsupported
+    want = _parse_model(_c3k_off_tensors(YOLO11_CLS_YAML[:10], tensors), 0,lambda c: _make_divisible(min(c, maxc) * width / 4), lambda i, n: reps[i] if n > 1 else n)
+    _strict_compare(want, tensors, 10, unsupported, ignore=None, attn=(9,))
     return True
 
 

@@ -63,14 +63,14 @@ def convert_state_dict(sd: dict) -> dict:
     root = Path(__file__).resolve().parent.parent / "geo-trax_amd"
     if str(root) not in sys.path:
         sys.path.insert(0, str(root))
-    from geotrax_amd.weights import V10_MAX_DET, detector_topology, fold_bn, fold_repvggdw, yolov10_has_one2many
+    from geotrax_amd.weights import V10_MAX_DET, detector_family, family_row, fold_bn, fold_repvggdw, yolov10_has_one2many
 
     t = {k: np.asarray(v, np.float32) for k, v in sd.items() if "dfl" not in k and "num_batches_tracked" not in k}
     t = fold_repvggdw(fold_bn(t))
-    graph, _ = detector_topology(t)
-    if graph not in ("yolov10", "yolo26"):
-        raise ValueError(f"convert_state_dict folds YOLOv10 and YOLO26 checkpoints; this one is {graph}")
-    t["detector.meta"] = np.asarray([10 if graph == "yolov10" else 26, float(yolov10_has_one2many(t)), 1, V10_MAX_DET], np.float32)
+    fam = detector_family(t)
+    if not fam.end2end:
+        raise ValueError(f"convert_state_dict folds YOLOv10 and YOLO26 checkpoints; this one is {fam.graph}")
+    t["detector.meta"] = np.asarray([family_row(fam.graph).meta, float(yolov10_has_one2many(t)), 1, V10_MAX_DET], np.float32)
     return t
 
 
