@@ -1396,6 +1396,54 @@ int gtx_op_orb_match(gtx_ctx* ctx, const uint8_t* desc_q, int nq, int slots_q, c
   });
 }
 
+// ---- the stabilizer's working-resolution gray image (tests/test_stab_ratio_gpu.py; the engine's "frame" route calls the _dev entry
+// per frame). One check for both entries: the frame, the ratio and the working size the caller believes in.
+static void gray_resize_check(const char* op, int h, int w, float ratio, int gh, int gw) {
+  if (h < 1 || w < 1 || h > 0xffff || w > 0xffff) op_bad(op, "frames of 1..65535 pixels a side");
+  if (!(ratio > 0.f && ratio <= 1.f)) op_bad(op, "downsample_ratio must be in (0, 1]");
+  int eh = 0, ew = 0;
+  gtx::gray_working_size(h, w, ratio, &eh, &ew);
+  if (eh < 1 || ew < 1) op_bad(op, "the working image would be empty");
+  if (gh != eh || gw != ew) gtx::fail(GTX_ERR_INVALID, "%s: gray image is %dx%d, the working size of a %dx%d frame at ratio %g is %dx%d", op, gw, gh, w, h, ratio, ew, eh);
+}
+
+int gtx_op_gray_working_size(int h, int w, float ratio, int* gh, int* gw) {
+  return guarded([&] {
+    const char* op = "gray_working_size";
+    need(gh, "gh"); need(gw, "gw");
+    if (h < 1 || w < 1 || h > 0xffff || w > 0xffff) op_bad(op, "frames of 1..65535 pixels a side");
+    if (!(ratio > 0.f && ratio <= 1.f)) op_bad(op, "downsample_ratio must be in (0, 1]");
+    gtx::gray_working_size(h, w, ratio, gh, gw);
+  });
+}
+
+int gtx_op_gray_resize_dev(gtx_ctx* ctx, const void* bgr_dptr, int h, int w, float ratio, void* gray_dptr, int gh, int gw) {
+  return guarded([&] {
+    gray_resize_check("gray_resize_dev", h, w, ratio, gh, gw);
+    need(bgr_dptr, "bgr"); need(gray_dptr, "gray"); need(ctx, "ctx");
+    gtx::gray_resize_dev(ctx, bgr_dptr, h, w, ratio, gray_dptr);
+  });
+}
+
+int gtx_op_gray_resize_ms(gtx_ctx* ctx, const void* bgr_dptr, int h, int w, float ratio, void* gray_dptr, int gh, int gw, int reps, float* ms) {
+  return guarded([&] {
+    const char* op = "gray_resize_ms";
+    gray_resize_check(op, h, w, ratio, gh, gw);
+    if (reps < 1 || reps > 100000) op_bad(op, "1..100000 repetitions");
+    need(bgr_dptr, "bgr"); need(gray_dptr, "gray"); need(ms, "ms"); need(ctx, "ctx");
+    GTX_HIP(hipSetDevice(ctx->device));
+    *ms = time_launches(ctx->stream, reps, [&] { gtx::gray_resize_dev(ctx, bgr_dptr, h, w, ratio, gray_dptr); });
+  });
+}
+
+int gtx_op_gray_resize(gtx_ctx* ctx, const uint8_t* bgr, int h, int w, float ratio, uint8_t* gray, int gh, int gw) {
+  return guarded([&] {
+    gray_resize_check("gray_resize", h, w, ratio, gh, gw);
+    need(bgr, "bgr"); need(gray, "gray"); need(ctx, "ctx");
+    gtx::op_gray_resize(ctx, bgr, h, w, ratio, gray);
+  });
+}
+
 int gtx_op_orb_ransac(gtx_ctx* ctx, const float* pts, int n, uint32_t seed, int n_hyp, int frame_w, int frame_h, float thr, int affine, int* best,
                       int64_t* cost, double H[9]) {
   return guarded([&] {

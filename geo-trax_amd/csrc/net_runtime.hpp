@@ -21,7 +21,13 @@ struct gtx_ctx {
   // device words of the two operator hooks, each allocated and initialised by its hook's first call and never written by the host again
   void* orb_match_ticket = nullptr;  // gtx_op_orb_match (stabilizer.hip): match_kernel's ticket
   void* orb_ransac_state = nullptr;  // gtx_op_orb_ransac (homography.hip): ransac_kernel's two state words
+  // gtx_op_gray_resize(_dev) (stabilizer.hip): the column / row tap tables of every (frame, working size) pair the context was asked
+  // for, uploaded once each and never written again (a run asks for one pair)
+  struct GrayTab { int fh, fw, gh, gw; void* tab; };
+  std::vector<GrayTab> gray_tabs;
   ~gtx_ctx() {
+    for (auto& t : gray_tabs)
+      if (t.tab) (void)hipFree(t.tab);
     if (orb_match_ticket) (void)hipFree(orb_match_ticket);
     if (orb_ransac_state) (void)hipFree(orb_ransac_state);
     if (stream) (void)hipStreamDestroy(stream);
@@ -233,7 +239,7 @@ class DetectorBase : public NetRuntime {
 
   // gray images of the last batches: a batch's image lives until kGrayRing - 2 more batches have been submitted after the one
   // that follows it (engine.py sizes its queues from this)
-  static constexpr int kGrayRing = 16;
+  static constexpr int kGrayRing = GTX_GRAY_RING;
 
  protected:
   void alloc_outputs();                   // the gray ring and the pinned result rows / counts (at finalize)

@@ -87,6 +87,85 @@ __global__ __launch_bounds__(256) void gray_kernel(const uint8_t* __restrict__ b
   }
 }
 
+// BGR frame -> working-resolution gray at any downsample_ratio other than 0.5 and 1.0, in one launch: what stabilo computes as
+// cv2.cvtColor(BGR2GRAY) followed by cv2.resize(gray, None, fx=r, fy=r) (INTER_LINEAR), restated as
+// oracle/yolov8_ref.py::resize_linear_u8 over oracle/stabilo_ref.py::bgr2gray(frame, half=False): every tap is rounded to its
+// u8 gray value first, the horizontal pass is a0 * g0 + a1 * g1 with 11-bit weights, the vertical pass
+// (((ay0 * (r0 >> 4)) >> 16) + ((ay1 * (r1 >> 4)) >> 16) + 2) >> 2 -- the rule of the detector's letterbox kernel
+// (det_kernels.hip). The weights sum to 2048, so the result is at most 255 and needs no clamp. The working size is
+// gw = rint(fw * r), gh = rint(fh * r) (gray_working_size) and the source step is n_src / n_dst (OpenCV's dsize form); where
+// fw * r and fh * r are integers that step equals 1 / r, the step of OpenCV's fx form, and the two forms agree. What OpenCV does
+// when fw * r is not an integer is recalled, not verified: the rule here is the oracle function's.
+// Source index, second-tap step and both weights of every destination column / row are made on the host in float32
+// (gray_resize_tabs: the oracle's operation sequence) and read from a table, so no float rounding happens on the device.
+// A lane produces 4 consecutive pixels of a row from at most 2 x 2 BGR pixels each and stores them as one dword when the address
+// allows (the working width need not be a multiple of 4, and the caller's buffer need not be aligned); a scalar tail otherwise.
+// Table entry: x = source index | (1 << 16 when the second tap is the next pixel), y = weight 0 | weight 1 << 16.
+__global__ __launch_bounds__(256) void gray_resize_kernel(const uint8_t* __restrict__ bgr, int fw, uint8_t* __restrict__ out, int gw,
+                                                          const uint2* __restrict__ tab_x, const uint2* __restrict__ tab_y) {
+  const int x = 4 * (blockIdx.x * blockDim.x + threadIdx.x), y = blockIdx.y;
+  if (x >= gw) return;
+  const uint2 ty = tab_y[y];
+  const int ay0 = (int)(ty.y & 0xffff), ay1 = (int)(ty.y >> 16);
+  const size_t pitch = (size_t)fw * 3;
+  const uint8_t* r0 = bgr + (size_t)(ty.x & 0xffff) * pitch;
+  const uint8_t* r1 = r0 + ((ty.x >> 16) ? pitch : 0);
+  unsigned o = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint2 tx = tab_x[min(x + k, gw - 1)];
+    const unsigned xa = (tx.x & 0xffff) * 3, xb = xa + (tx.x >> 16) * 3;
+    const int ax0 = (int)(tx.y & 0xffff), ax1 = (int)(tx.y >> 16);
+    const int top = bgr2gray_u8(r0[xa], r0[xa + 1], r0[xa + 2]) * ax0 + bgr2gray_u8(r0[xb], r0[xb + 1], r0[xb + 2]) * ax1;
+    const int bot = bgr2gray_u8(r1[xa], r1[xa + 1], r1[xa + 2]) * ax0 + bgr2gray_u8(r1[xb], r1[xb + 1], r1[xb + 2]) * ax1;
+    o |= (unsigned)((((ay0 * (top >> 4)) >> 16) + ((ay1 * (bot >> 4)) >> 16) + 2) >> 2) << (8 * k);   // <= 255 * 2048 * 128: exact in 32 bits
+  }
+  uint8_t* d = out + (size_t)y * gw + x;
+  if (x + 4 <= gw && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+    *reinterpret_cast<unsigned*>(d) = o;
+  } else {
+    for (int k = 0; k < 4 && x + k < gw; ++k) d[k] = (uint8_t)(o >> (8 * k));
+  }
+}
+
+// The taps of one axis, as resize_linear_u8's coeffs(): float32 operation by operation (no contraction), rint = round half to even.
+void gray_resize_axis(int n_dst, int n_src, uint2* out) {
+#pragma clang fp contract(off)
+  const float scale = (float)((double)n_src / (double)n_dst);
+  for (int d = 0; d < n_dst; ++d) {
+    float f = (float)d + 0.5f;
+    f = f * scale;
+    f = f - 0.5f;
+    int i0 = (int)std::floor(f);
+    f = f - (float)i0;
+    if (i0 < 0) { f = 0.f; i0 = 0; }
+    if (i0 >= n_src - 1) { f = 0.f; i0 = n_src - 1; }
+    const int i1 = std::min(i0 + 1, n_src - 1);
+    const unsigned a1 = (unsigned)std::nearbyint(f * 2048.f);
+    const float g = 1.f - f;
+    const unsigned a0 = (unsigned)std::nearbyint(g * 2048.f);
+    out[d] = make_uint2((unsigned)i0 | ((unsigned)(i1 - i0) << 16), a0 | (a1 << 16));
+  }
+}
+
+// [gw column entries][gh row entries]
+std::vector<uint2> gray_resize_tabs(int fh, int fw, int gh, int gw) {
+  std::vector<uint2> tab((size_t)gw + gh);
+  gray_resize_axis(gw, fw, tab.data());
+  gray_resize_axis(gh, fh, tab.data() + gw);
+  return tab;
+}
+
+// frame -> working gray on s: ratio 0.5 and 1.0 keep gray_kernel (2x2 mean of gray values / gray alone), every other ratio
+// gray_resize_kernel with `tab` (gray_resize_tabs of the same sizes, in HBM)
+void launch_working_gray(hipStream_t s, const uint8_t* bgr, int fh, int fw, float ratio, uint8_t* out, int gh, int gw, const uint2* tab) {
+  if (ratio == 0.5f || ratio == 1.0f)
+    hipLaunchKernelGGL(gray_kernel, dim3(cdiv(gw, 256), gh), dim3(256), 0, s, bgr, fh, fw, ratio == 0.5f ? 1 : 0, out, gh, gw);
+  else
+    hipLaunchKernelGGL(gray_resize_kernel, dim3(cdiv(gw, 1024), gh), dim3(256), 0, s, bgr, fw, out, gw, tab, tab + gw);
+  GTX_HIP(hipGetLastError());
+}
+
 // Integer bilinear resize of one pyramid level from the one above it (16.16 source coordinates at pixel centres, 11-bit
 // weights, round to nearest): bit-exact on any machine. The source column / row and weight of every destination column /
 // row depend on the level sizes only, so they are tabulated once when the stabilizer is created (pyr_src; the table entry
@@ -926,12 +1005,22 @@ void stabilizer_pattern_table(std::vector<int8_t>& out) {
   }
 }
 
+// The working size of a frame: fh / 2 x fw / 2 at ratio 0.5 and the frame's own at 1.0 (as ever), else rint(fh * r) x rint(fw * r)
+// in double from the float ratio, halves to even (geotrax_amd.stabilizer.working_size states the same rule).
+void gray_working_size(int fh, int fw, float ratio, int* gh, int* gw) {
+  if (ratio == 0.5f) { *gh = fh / 2; *gw = fw / 2; return; }
+  if (ratio == 1.0f) { *gh = fh; *gw = fw; return; }
+  *gh = (int)std::nearbyint((double)fh * (double)ratio);
+  *gw = (int)std::nearbyint((double)fw * (double)ratio);
+}
+
 struct Stabilizer::Impl {
   gtx_ctx* ctx;
   gtx_stab_config cfg;
   int fh, fw;            // frame
   int gh, gw;            // level-0 gray (frame * downsample_ratio)
   int half;              // 1 when downsample_ratio == 0.5
+  DevBuf d_gray_tab;     // gray_resize_kernel's column / row taps (ratios other than 0.5 and 1.0)
   Levels lev_ref{}, lev_cur{};
   int pyr_bytes = 0, cand_total = 0, slots_ref = 0, slots_cur = 0;
   int n_hyp = 0;
@@ -1066,15 +1155,15 @@ Stabilizer::Stabilizer(gtx_ctx* ctx, const gtx_stab_config& cfg) : impl_(new Imp
   S.ctx = ctx;
   S.cfg = cfg;
   GTX_CHECK(cfg.frame_h > 0 && cfg.frame_w > 0, "stabilizer: frame size must be given");
-  GTX_CHECK(cfg.downsample_ratio == 0.5f || cfg.downsample_ratio == 1.0f, "stabilizer: downsample_ratio must be 0.5 or 1.0 (got %g)", cfg.downsample_ratio);
+  GTX_CHECK(cfg.downsample_ratio > 0.f && cfg.downsample_ratio <= 1.0f, "stabilizer: downsample_ratio must be in (0, 1] (got %g)", cfg.downsample_ratio);
+  GTX_CHECK(cfg.frame_h <= 0xffff && cfg.frame_w <= 0xffff, "stabilizer: frames of at most 65535 x 65535 pixels");
   GTX_CHECK(cfg.n_levels >= 1 && cfg.n_levels <= kPyrLevels, "stabilizer: n_levels must be in [1,%d]", kPyrLevels);
   GTX_CHECK(cfg.scale_factor > 1.0f, "stabilizer: scale_factor must be > 1");
   GTX_CHECK(cfg.max_features >= 8, "stabilizer: max_features too small");
   S.fh = cfg.frame_h;
   S.fw = cfg.frame_w;
   S.half = cfg.downsample_ratio == 0.5f ? 1 : 0;
-  S.gh = S.half ? S.fh / 2 : S.fh;
-  S.gw = S.half ? S.fw / 2 : S.fw;
+  gray_working_size(S.fh, S.fw, cfg.downsample_ratio, &S.gh, &S.gw);
   GTX_HIP(hipSetDevice(ctx->device));
   const int ref_features = (int)std::lround(cfg.max_features * (double)cfg.ref_multiplier);
   S.plan(S.lev_cur, cfg.max_features, S.slots_cur);
@@ -1135,6 +1224,11 @@ Stabilizer::Stabilizer(gtx_ctx* ctx, const gtx_stab_config& cfg) : impl_(new Imp
     S.d_pyr_tab.alloc(sizeof(unsigned) * std::max<size_t>(tab.size(), 1));
     if (!tab.empty()) GTX_HIP(hipMemcpy(S.d_pyr_tab.p, tab.data(), sizeof(unsigned) * tab.size(), hipMemcpyHostToDevice));
   }
+  if (cfg.downsample_ratio != 0.5f && cfg.downsample_ratio != 1.0f) {
+    const std::vector<uint2> tab = gray_resize_tabs(S.fh, S.fw, S.gh, S.gw);
+    S.d_gray_tab.alloc(sizeof(uint2) * tab.size());
+    GTX_HIP(hipMemcpy(S.d_gray_tab.p, tab.data(), sizeof(uint2) * tab.size(), hipMemcpyHostToDevice));
+  }
   long tans[32];
   for (int j = 0; j < 32; ++j) tans[j] = std::lround(std::tan((j + 0.5) * 2.0 * M_PI / kAngleBins) * 16777216.0);
   GTX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_tan), tans, sizeof tans));
@@ -1166,9 +1260,7 @@ void Stabilizer::Impl::gray_from_frame(const uint8_t* frame, int h, int w) {
   const size_t bytes = (size_t)h * w * 3;
   if (d_frame.bytes < bytes) d_frame.alloc(bytes);
   GTX_HIP(hipMemcpyAsync(d_frame.p, frame, bytes, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(gray_kernel, dim3(cdiv(gw, 256), gh), dim3(256), 0, ctx->stream, d_frame.as<uint8_t>(), h, w, half,
-                     d_pyr.as<uint8_t>(), gh, gw);
-  GTX_HIP(hipGetLastError());
+  launch_working_gray(ctx->stream, d_frame.as<uint8_t>(), h, w, cfg.downsample_ratio, d_pyr.as<uint8_t>(), gh, gw, d_gray_tab.as<uint2>());
 }
 
 // gray_dev == nullptr: level 0 is already in d_pyr.
@@ -1505,6 +1597,44 @@ void op_orb_match(gtx_ctx* ctx, const uint8_t* desc_q, int nq, int slots_q, cons
   download(m_t, mt, out_q);
   download(m_d, md, out_q);
   download(m_pts, mp, 4 * out_q);
+}
+
+// ---- gtx_op_gray_resize_dev / gtx_op_gray_resize: the working-resolution gray of a BGR frame in HBM, enqueued on the context's
+// stream into the caller's buffer -- gray_from_frame's launch with the same host-made tables, which live with the context (one
+// upload per frame and working size, never written again). The caller has validated the sizes.
+void gray_resize_dev(gtx_ctx* ctx, const void* bgr, int fh, int fw, float ratio, void* gray) {
+  GTX_HIP(hipSetDevice(ctx->device));
+  int gh, gw;
+  gray_working_size(fh, fw, ratio, &gh, &gw);
+  const uint2* tab = nullptr;
+  if (ratio != 0.5f && ratio != 1.0f) {
+    for (const auto& t : ctx->gray_tabs)
+      if (t.fh == fh && t.fw == fw && t.gh == gh && t.gw == gw) tab = static_cast<const uint2*>(t.tab);
+    if (!tab) {
+      // a table enters the cache only once it is filled; a context that is asked for ever new sizes is refused, not grown without end
+      GTX_CHECK(ctx->gray_tabs.size() < 16, "gray_resize: this context already holds the tables of 16 frame / working sizes");
+      const std::vector<uint2> host = gray_resize_tabs(fh, fw, gh, gw);
+      DevBuf d(sizeof(uint2) * host.size());
+      GTX_HIP(hipMemcpy(d.p, host.data(), sizeof(uint2) * host.size(), hipMemcpyHostToDevice));
+      ctx->gray_tabs.reserve(16);
+      ctx->gray_tabs.push_back({fh, fw, gh, gw, d.p});
+      tab = static_cast<const uint2*>(d.p);
+      d.p = nullptr;                                      // the context owns it now (freed with the context)
+    }
+  }
+  launch_working_gray(ctx->stream, static_cast<const uint8_t*>(bgr), fh, fw, ratio, static_cast<uint8_t*>(gray), gh, gw, tab);
+}
+
+void op_gray_resize(gtx_ctx* ctx, const uint8_t* bgr, int fh, int fw, float ratio, uint8_t* gray) {
+  GTX_HIP(hipSetDevice(ctx->device));
+  int gh, gw;
+  gray_working_size(fh, fw, ratio, &gh, &gw);
+  DevBuf d_bgr, d_gray;
+  upload(d_bgr, bgr, (size_t)fh * fw * 3);
+  fill_ff(d_gray, (size_t)gh * gw);
+  gray_resize_dev(ctx, d_bgr.p, fh, fw, ratio, d_gray.p);
+  GTX_HIP(hipStreamSynchronize(ctx->stream));
+  download(gray, d_gray, (size_t)gh * gw);
 }
 
 }  // namespace gtx

@@ -57,6 +57,14 @@ class Stabilizer {
 // The steered-BRIEF sampling table [256 bins][256 tests][ax, ay, bx, by] (host only, no device needed).
 void stabilizer_pattern_table(std::vector<int8_t>& out);
 
+// frame pixels -> working pixels: fh / 2 x fw / 2 at ratio 0.5, the frame's size at 1.0, else rint(fh * r) x rint(fw * r)
+void gray_working_size(int fh, int fw, float ratio, int* gh, int* gw);
+// The stabilizer's working-resolution gray image of a BGR u8 frame in HBM, into the caller's buffer (gh * gw bytes, any alignment),
+// enqueued on the context's stream: the launch Stabilizer::set_ref_frame / stabilize make for a host frame. op_gray_resize: the same
+// on host arrays (staged, synchronous). The caller has validated the sizes (gtx_ops.cpp).
+void gray_resize_dev(gtx_ctx* ctx, const void* bgr, int fh, int fw, float ratio, void* gray);
+void op_gray_resize(gtx_ctx* ctx, const uint8_t* bgr, int fh, int fw, float ratio, uint8_t* gray);
+
 // Operator hook: one launch of the matcher on host arrays, exactly as the stabilizer launches it (sizes are validated by the caller,
 // gtx_ops.cpp). Its ticket word lives with the context (gtx_ctx::orb_match_ticket) and is never re-initialised by the host.
 void op_orb_match(gtx_ctx* ctx, const uint8_t* desc_q, int nq, int slots_q, const uint8_t* desc_t, int nt, int slots_t, float ratio, int keep_all,

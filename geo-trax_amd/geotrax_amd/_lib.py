@@ -118,6 +118,7 @@ class SparseLevel(C.Structure):
 # name -> (restype, argtypes); kept in one table so tests can check the export list against
 # include/gtx.h.
 ABI_VERSION = 14       # GTX_ABI_VERSION of include/gtx.h
+GRAY_RING = 16         # GTX_GRAY_RING of include/gtx.h: batches whose gray images a detector keeps (tests/test_stab_ratio.py compares the two)
 _P = C.c_void_p
 _SIGNATURES = {
     "gtx_abi_version": (C.c_int, []),
@@ -300,6 +301,10 @@ _SIGNATURES = {
     "gtx_op_orb_match": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gtx_op_orb_ransac": (C.c_int, [_P, _P, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int),
                                     C.POINTER(C.c_int64), _P]),
+    "gtx_op_gray_working_size": (C.c_int, [C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gtx_op_gray_resize_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P, C.c_int, C.c_int]),
+    "gtx_op_gray_resize": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P, C.c_int, C.c_int]),
+    "gtx_op_gray_resize_ms": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "gtx_warp_boxes": (C.c_int, [_P, _P, C.c_int, _P]),
     "gtx_perspective_points": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
     "gtx_op_estimate_affine_partial": (C.c_int, [_P, _P, C.c_int, C.c_uint, _P, _P, _P]),

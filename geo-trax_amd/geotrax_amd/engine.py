@@ -36,7 +36,7 @@ from . import _lib
 from .detector import Detector
 from .geometry import warp_boxes
 from .sift_stabilizer import SiftStabilizer, resident
-from .stabilizer import Stabilizer
+from .stabilizer import Stabilizer, working_size
 from .tracker import Tracker
 
 
@@ -265,6 +265,19 @@ def stabilizer_class(stab_kw: dict | None):
     return SiftStabilizer if resident(stab_kw) else Stabilizer
 
 
+def gray_route(stab_kw: dict | None) -> str | None:
+    """Where the stabilizers of an engine built with this `stabilo:` block get their working image from (None: no stabilizer):
+    "detector": downsample_ratio 0.5 -- the half-resolution gray image the detector's preprocess leaves in HBM;
+    "frame":    detector_name orb at any other ratio -- the working gray of every frame of a batch is made from the BGR frame in HBM
+                (gtx_op_gray_resize_dev) on the detector's stream when the batch goes to the detector;
+    "host":     detector_name sift / rsift at other ratios, which Stabilizer registers on host frames, one blocking call each."""
+    if stab_kw is None:
+        return None
+    if float(stab_kw.get("downsample_ratio", 0.5)) == 0.5:
+        return "detector"
+    return "frame" if str(stab_kw.get("detector_name", "orb")) == "orb" else "host"
+
+
 class ExtractEngine:
     def __init__(self, weights: dict, frame_hw: tuple[int, int], det_kw: dict, tracker: Tracker | None, stab_kw: dict | None, *,
                  device: int | None = None, batch: int = 2, det_streams: int = 2, stab_streams: int = 4, gmc: bool | str = False,
@@ -323,6 +336,13 @@ class ExtractEngine:
             self.gmc = make_gmc(self.frame_hw, method=gmc if isinstance(gmc, str) else "sparseOptFlow", ctx=take("g"),
                                 **(gmc_kw or {}))    # gmc_kw: the GMC object's own keywords (`engine: {gmc: {...}}`, e.g. ecc's max_iters)
         self.use_dev_gray = bool(self.stabs) and float(stab_kw.get("downsample_ratio", 0.5)) == 0.5
+        # gray_route(): "frame" = the stabilizers' working image is made from each BGR frame in HBM, at the stabilizer's own ratio
+        self.gray_route = gray_route(stab_kw) if self.stabs else None
+        self.stab_dev_gray = self.gray_route in ("detector", "frame")   # the stabilizers read gray images in HBM (no host frames kept)
+        self._work_hw = working_size(self.frame_hw, stab_kw["downsample_ratio"]) if self.gray_route == "frame" else None
+        self._work_ratio = float(stab_kw["downsample_ratio"]) if self.gray_route == "frame" else None
+        self._work_ring = {}             # per detector: [device pointer of _GRAY_RING x B working gray images, slot of the newest batch]
+        self._work_grays = {}            # per detector: (pointer, gh, gw) of every frame of its batch in flight
         self._stage = {}                 # per detector: device staging buffer for host frames
         self._host_frames = {}           # frames kept for the host-gray fallback of the stabilizer
         self._frames_of = {}             # per detector: device pointer of the frames of its batch in flight (the ReID crops read them)
@@ -345,11 +365,25 @@ class ExtractEngine:
         registered against it. The foreground mask is the frame's raw detections."""
         if hasattr(frame, "bgr"):                               # a Yuv420Frame of a .y4m source
             frame = frame.bgr()
-        d = self.dets[0].detect(np.ascontiguousarray(frame, np.uint8))
-        g = self.dets[0].gray_dptr(0)
+        frame = np.ascontiguousarray(frame, np.uint8)
+        det = self.dets[0]
+        d = det.detect(frame)
+        g = det.gray_dptr(0)
+        if self.gray_route == "frame" and self.stabs:           # the frame's working gray, made in HBM as for every later frame
+            if tuple(frame.shape[:2]) != self.frame_hw:
+                raise ValueError(f"frame is {frame.shape[1]}x{frame.shape[0]}, engine was built for {self.frame_hw[1]}x{self.frame_hw[0]}")
+            key = id(det)
+            ref = det.ctx.dev_alloc(frame.nbytes)               # one frame, for this call only (a run on device batches never stages host frames)
+            try:
+                det.ctx.dev_upload(ref, frame)
+                self._frame_grays(det, ref, 1)
+                det.ctx.synchronize()
+            finally:
+                det.ctx.dev_free(ref)
+            g = self._work_grays.pop(key)[0]
         boxes = d.xywh if len(d) else None
         for st in self.stabs:                                   # same reference image -> identical reference keypoints
-            if self.use_dev_gray:
+            if self.stab_dev_gray:
                 st.set_ref_gray_dev(g[0], g[1], g[2], boxes)
             else:
                 st.set_ref_frame(frame, boxes)
@@ -370,7 +404,7 @@ class ExtractEngine:
 
     def close(self) -> None:
         for d in self.dets:
-            for p in [self._stage.pop(id(d), None), self._stage.pop(("yuv", id(d)), None)]:
+            for p in [self._stage.pop(id(d), None), self._stage.pop(("yuv", id(d)), None), (self._work_ring.pop(id(d), None) or [None])[0]]:
                 if p:
                     d.ctx.dev_free(p)
             d.close()
@@ -390,6 +424,7 @@ class ExtractEngine:
     def _submit(self, det: Detector, batch) -> int:
         if isinstance(batch, (int, np.integer)):                # device pointer to B contiguous frames
             self._gmc_frames(det, int(batch), self.B)
+            self._frame_grays(det, int(batch), self.B)
             det.submit_dev(int(batch), self.B)
             self._last_frames = int(batch)
             return self.B
@@ -399,10 +434,12 @@ class ExtractEngine:
         if isinstance(batch, DeviceBatch):                      # frames a read-ahead feeder is bringing into HBM: the detector's
             if not 1 <= batch.n <= self.B:                      # stream waits for their upload, this thread does not
                 raise ValueError(f"a batch holds 1..{self.B} frames, got {batch.n}")
-            if self.stabs and not self.use_dev_gray:
-                raise ValueError("device batches need the stabilizer to work on the detector's gray image (downsample_ratio 0.5)")
+            if self.stabs and not self.stab_dev_gray:
+                raise ValueError("device batches need a stabilizer that works on gray images in HBM (detector_name orb at any downsample_ratio, "
+                                 "sift / rsift at 0.5)")
             batch.wait_on(det.ctx)
             self._gmc_frames(det, batch.ptr, batch.n)
+            self._frame_grays(det, batch.ptr, batch.n)
             det.submit_dev(batch.ptr, batch.n)
             self._last_frames = batch.ptr
             return batch.n
@@ -427,9 +464,10 @@ class ExtractEngine:
             else:
                 det.ctx.dev_upload(self._stage[key] + i * nbytes, f)
         self._gmc_frames(det, self._stage[key], len(frames))
+        self._frame_grays(det, self._stage[key], len(frames))
         det.submit_dev(self._stage[key], len(frames))
         self._last_frames = self._stage[key]
-        if self.stabs and not self.use_dev_gray:
+        if self.stabs and not self.stab_dev_gray:
             self._host_frames[key] = [f.bgr() if isinstance(f, Yuv420Frame) else f for f in frames]
         return len(frames)
 
@@ -444,6 +482,36 @@ class ExtractEngine:
         for i in range(n):
             self.gmc.submit_frame_dev(ptr + i * nbytes, self.frame_hw[0], self.frame_hw[1], producer=det.ctx)
             self._gmc_sub += 1
+
+    #: batches whose working gray images a detector keeps on the "frame" route: the depth of the detector's own gray ring
+    #: (GTX_GRAY_RING of include/gtx.h = DetectorBase::kGrayRing, through _lib.GRAY_RING), whose lifetime rule these buffers share;
+    #: the queue-depth assert of _tracked_frames_threaded is written in the same number
+    _GRAY_RING = _lib.GRAY_RING
+
+    def _frame_grays(self, det: Detector, ptr: int, n: int) -> None:
+        """The "frame" route (gray_route): the stabilizers' working gray image of every frame of a batch, made from the BGR frame in
+        HBM by gtx_op_gray_resize_dev on the detector's stream when the batch goes to its detector -- as _gmc_frames does for ECC:
+        behind whatever brought the frame into HBM and ahead of the detector pass, so collect() of that pass covers it and the next
+        batch may overwrite the frame buffer. The images go to the next slot of a per-detector ring as deep as the detector's own
+        gray ring, advanced once per batch like it: a frame's image stays until that detector has taken _GRAY_RING - 1 more batches,
+        which the queue depths of _tracked_frames_threaded keep beyond the stabilizers' reads."""
+        if self.gray_route != "frame" or not self.stabs:
+            return
+        gh, gw = self._work_hw
+        stride = -(-gh * gw // 256) * 256                       # every image starts on a 256-byte boundary (dword stores)
+        key = id(det)
+        if key not in self._work_ring:
+            self._work_ring[key] = [det.ctx.dev_alloc(self._GRAY_RING * self.B * stride), 0]
+        ring = self._work_ring[key]
+        ring[1] = (ring[1] + 1) % self._GRAY_RING
+        nbytes = self.frame_hw[0] * self.frame_hw[1] * 3
+        out = []
+        for i in range(n):
+            g = ring[0] + (ring[1] * self.B + i) * stride
+            _lib.check(det.ctx.lib.gtx_op_gray_resize_dev(det.ctx.handle, C.c_void_p(ptr + i * nbytes), self.frame_hw[0], self.frame_hw[1],
+                                                          self._work_ratio, C.c_void_p(g), gh, gw))
+            out.append((g, gh, gw))
+        self._work_grays[key] = out
 
     def run(self, batches, paced: bool | None = None):
         """paced: the source is a live stream (see PacedSource); None = what the source declares (`batches.paced`, default False).
@@ -497,7 +565,7 @@ class ExtractEngine:
             inflight.append((det, self._submit(det, b), prev, n_skip))
             self._frames_of[id(det)] = self._last_frames
 
-        host_gray = bool(self.stabs) and not self.use_dev_gray
+        host_gray = bool(self.stabs) and not self.stab_dev_gray
         try:
             def fill():                                             # a pass in flight on every detector stream -- unless the source is a stream
                 while not exhausted and not paced and len(inflight) < len(self.dets):
@@ -525,6 +593,7 @@ class ExtractEngine:
                         self._prof["reid"] += time.perf_counter() - t0
                 grays = [det.gray_dptr(b) for b in range(nb)]
                 hosts = self._host_frames.pop(id(det), None)
+                work = self._work_grays.pop(id(det), None)          # the "frame" route: the stabilizers' own images of this batch
                 det_ms = float(sum(dets[0].speed.values())) / nb if dets else 0.0
                 late = host_gray or paced                           # paced source: the batch's results leave before the stage blocks on the next one
                 if not late:
@@ -541,7 +610,7 @@ class ExtractEngine:
                             restart = False
                         self.gmc.submit_gray_dev(*g)
                         self._gmc_sub += 1
-                yield det, dets, grays, hosts, det_ms, n_skip
+                yield det, dets, grays, hosts, det_ms, n_skip, work
                 if host_gray:
                     submit_next()
                 elif late and not inflight and not exhausted:       # a stream: everything in flight has been handed on; now wait for the next batch
@@ -553,10 +622,13 @@ class ExtractEngine:
                 except Exception:
                     pass
             self._host_frames.clear()
+            self._work_grays.clear()
 
     # ---- stage 2: camera-motion compensation + tracker, strictly in clip order
-    def _track_batch(self, det, dets, grays, hosts, det_ms, n_skip=0):
+    def _track_batch(self, det, dets, grays, hosts, det_ms, n_skip=0, work=None):
         # a generator: a frame goes on to the stabilizer stage while the tracker works on the next one of its batch
+        if work is not None:                                    # the stabilizer stage reads its own working images, not the detector's
+            grays = work
         for _ in range(n_skip):                                 # warp of the frame that only primed the GMC (identity)
             self._gmc_collect()
         for b, (d, g) in enumerate(zip(dets, grays)):
@@ -591,7 +663,7 @@ class ExtractEngine:
         n_batches = 2
         n_frames = 2 * self.B * len(self.dets)
         in_flight = (n_batches + 1) * self.B + n_frames + len(self.stabs) + 1
-        assert in_flight <= 14 * len(self.dets) * self.B, "engine queues outlive the detector's gray ring"
+        assert in_flight <= (self._GRAY_RING - 2) * len(self.dets) * self.B, "engine queues outlive the detector's gray ring"
         assert self.gmc is None or (n_batches + 2) * self.B <= 63, "engine queues outrun the GMC's 64-deep result ring"
         # ECC frames are queued when a batch goes to its detector: one batch in flight per detector stream, the batches of the stage
         # queue, the one the detector stage holds and the one the tracker stage holds, plus a shard rank's template frame
@@ -700,7 +772,7 @@ class ExtractEngine:
                 if not self._have_ref:                              # reference frame: boxes pass through, no transform row
                     det.ctx.synchronize()
                     for st in self.stabs:
-                        if self.use_dev_gray:
+                        if self.stab_dev_gray:
                             st.set_ref_gray_dev(g[0], g[1], g[2], r.xywh)
                         else:
                             st.set_ref_frame(host, r.xywh)
@@ -711,7 +783,7 @@ class ExtractEngine:
                 if len(pending) == len(self.stabs):                 # results are taken in frame order
                     yield finish()
                 st = self.stabs[r.index % len(self.stabs)]
-                if self.use_dev_gray:
+                if self.stab_dev_gray:
                     t0 = time.perf_counter() if prof is not None else 0.0
                     st.submit_gray_dev(g[0], g[1], g[2], r.xywh)
                     if prof is not None:
@@ -719,7 +791,7 @@ class ExtractEngine:
                         self.marks.append(("sub", r.index, time.perf_counter() - self._t_run))
                         prof["frames"] += 1
                     pending.append((st, r))
-                else:                                               # other downsample ratios: the stabilizer makes its own gray
+                else:                                               # the "host" route (sift / rsift on host frames): one blocking call
                     st.stabilize(host, r.xywh)
                     r.H = st.get_cur_trans_matrix(raw=True)
                     last_known(r)

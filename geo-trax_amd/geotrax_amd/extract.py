@@ -339,7 +339,7 @@ def track_with_model_sharded(model: YOLO, config: dict, logger: logging.Logger) 
                      or (hasattr(reader, 'jpeg_layout') and reader.jpeg_layout() is not None))
         lengths_ok = all((stop - start) % engine.B == 0 for start, stop in runs[:-1])       # batches must not span two runs
         use_feeder = (layout_ok and lengths_ok and fail_at is None and os.environ.get("GTX_FEEDER", "1") != "0" and eng_cfg.get('read_ahead', True) is not False
-                      and (not engine.stabs or engine.use_dev_gray))
+                      and (not engine.stabs or engine.stab_dev_gray))
         for r in engine.run(fed_batches() if use_feeder else batches()):
             yield D.pack_frame_record(max_det, r.xyxy, r.conf, r.cls, None if r.H_fallback else r.H, r.gmc, with_gmc=with_gmc)
 
@@ -399,11 +399,12 @@ def _frames_in_range(reader, first: int, last):
 def _read_ahead_batches(reader, engine, eng_cfg: dict, first: int, last, frame_nums: list, logger: logging.Logger):
     """The frames of `reader` as feeder.DeviceBatch objects: read, uploaded (and colour-converted) beside the pipeline by
     geotrax_amd.feeder instead of on the detector stage thread. Returns (batches iterable, feeder) or (None, None) when the
-    run needs host frames (a stabilizer that makes its own gray image) or `engine: {read_ahead: false}` / GTX_FEEDER=0."""
+    run needs host frames (sift / rsift stabilization on host frames, engine.gray_route "host") or `engine: {read_ahead: false}` /
+    GTX_FEEDER=0. ORB stabilization reads gray images in HBM at every downsample_ratio (engine.stab_dev_gray)."""
     from .feeder import FrameFeeder
 
     off = os.environ.get("GTX_FEEDER", "1") == "0" or eng_cfg.get('read_ahead', True) is False
-    if off or (engine.stabs and not engine.use_dev_gray):
+    if off or (engine.stabs and not engine.stab_dev_gray):
         return None, None
     layout = reader.raw_layout() if hasattr(reader, 'raw_layout') else None
     n_dets = len(engine.dets)
@@ -541,6 +542,8 @@ def track_with_model_blocking(model: YOLO, config: dict, logger: logging.Logger)
                 continue
             if not success:
                 break
+            if hasattr(frame, "bgr"):                             # a .y4m source hands out I420 planes: the host conversion (= the device's, bit for bit)
+                frame = frame.bgr()
             results = model.track(frame, **config['ultralytics'], persist=True)
             boxes = results[0].boxes
             yolo_time.append(sum(results[0].speed.values()))

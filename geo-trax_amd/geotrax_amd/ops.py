@@ -380,6 +380,23 @@ def clahe(gray: np.ndarray, ctx=None) -> np.ndarray:
     return out
 
 
+def gray_resize(frame_bgr: np.ndarray, ratio: float, ctx=None) -> np.ndarray:
+    """The ORB stabilizer's working-resolution gray image of a BGR frame (cv2.cvtColor(BGR2GRAY), then cv2.resize(fx = fy = ratio,
+    INTER_LINEAR)) [gh, gw] u8, gh, gw = stabilizer.working_size: gtx_op_gray_resize, one launch of the kernel the stabilizer and the
+    engine's "frame" route run."""
+    from .stabilizer import working_size
+
+    ctx = ctx or _lib.default_context()
+    f = np.ascontiguousarray(frame_bgr, dtype=np.uint8)
+    if f.ndim != 3 or f.shape[2] != 3:
+        raise ValueError("frame_bgr is [h, w, 3] u8")
+    h, w = f.shape[:2]
+    gh, gw = working_size((h, w), ratio)
+    out = np.empty((gh, gw), np.uint8)
+    check(ctx.lib.gtx_op_gray_resize(ctx.handle, ptr(f), h, w, float(ratio), ptr(out), gh, gw))
+    return out
+
+
 CONV_FORMS = ("Staged", "Split", "K32", "K32S2")      # gtx_op_conv_config's *form
 
 

@@ -18,6 +18,23 @@ from ._lib import StabConfig, check, ptr
 logger = logging.getLogger(__name__)
 
 
+def working_size(frame_hw: tuple[int, int], ratio: float) -> tuple[int, int]:
+    """(gh, gw) of the gray image the ORB stabilizer works on for frames of (h, w) at `downsample_ratio` ratio -- the size the
+    library's `_gray_dev` entries expect and gtx_op_gray_working_size returns. 0.5 keeps the detector's half-resolution image
+    (h // 2, w // 2) and 1.0 the frame's own size; every other ratio in (0, 1]: rint(h * r), rint(w * r), computed in double from the
+    float32 ratio the config struct carries, halves to even. Where h * r and w * r are integers this is cv2.resize(fx=r, fy=r)'s
+    size and its source step; elsewhere the rule is oracle/yolov8_ref.py::resize_linear_u8's for this size."""
+    h, w = int(frame_hw[0]), int(frame_hw[1])
+    r = float(np.float32(ratio))
+    if not 0.0 < r <= 1.0:
+        raise ValueError(f"downsample_ratio must be in (0, 1] (got {ratio})")
+    if r == 0.5:
+        return h // 2, w // 2
+    if r == 1.0:
+        return h, w
+    return int(np.rint(h * r)), int(np.rint(w * r))
+
+
 class Stabilizer:
     def __init__(self, frame_hw: tuple[int, int] | None = None, *, detector_name: str = "orb", matcher_name: str = "bf",
                  filter_type: str = "ratio", transformation_type: str = "projective", clahe: bool = False,

@@ -102,7 +102,10 @@ extern "C" {
  *     blocks; the tensors tell the graph, gtx_det_config is unchanged): a new entry point only, so the number stays.
  *     gtx_op_conv_config added (host only: the kernel a convolution shape is given) and gtx_conv_fused.{res_cstride, res_coff,
  *     in_place} appended at the struct's end (a residual read as a channel slice, and one buffer behind x, residual and y; 0 =
- *     every earlier behaviour), as gtx_det_config.end2end was: the number stays. */
+ *     every earlier behaviour), as gtx_det_config.end2end was: the number stays.
+ *     gtx_op_gray_resize_dev, gtx_op_gray_resize, gtx_op_gray_resize_ms and gtx_op_gray_working_size (the ORB stabilizer's working-resolution gray image at
+ *     any downsample_ratio in (0, 1]) added, and gtx_stab_config.downsample_ratio takes every value of that range instead of 0.5
+ *     and 1.0 alone: new entry points and a wider accepted range only, so the number stays. */
 #define GTX_ABI_VERSION 14
 
 typedef enum gtx_status {
@@ -780,7 +783,10 @@ int gtx_detector_collect(gtx_detector* det, int* n_out, float* xyxy, float* conf
                          float speed_ms[3]);
 /* Device pointer of the half-resolution gray image the preprocess pass wrote for batch slot b of
  * the most recently *collected* batch (the images live in a 16-deep ring: an image stays valid until
- * fourteen more batches have been submitted after the one that follows it), or NULL. The stabilizer consumes it so the frame is read from HBM once. */
+ * fourteen more batches have been submitted after the one that follows it), or NULL. The stabilizer consumes it so the frame is read from HBM once.
+ * GTX_GRAY_RING is that depth: a caller that keeps images of its own per batch beside the detector's (the engine's working gray
+ * images at other downsample ratios) sizes its ring by it, so that both follow one lifetime rule. */
+#define GTX_GRAY_RING 16
 const void* gtx_detector_gray(gtx_detector* det, int b, int* gray_h, int* gray_w);
 /* Raw head output of the last forward for parity tests: [anchors][4+nc] fp32 (xywh in network
  * pixels + sigmoid class scores), like the tensor ultralytics' Detect returns. */
@@ -957,7 +963,7 @@ int gtx_op_linear_assignment(const float* cost, int rows, int cols, double cost_
  * geotrax/utils/registration.py:59-85. */
 
 typedef struct gtx_stab_config {
-  float downsample_ratio;      /* stabilo downsample_ratio (default.yaml:106) */
+  float downsample_ratio;      /* stabilo downsample_ratio (default.yaml:106): any value in (0, 1] */
   int max_features;            /* per frame; the reference frame gets ref_multiplier x */
   float ref_multiplier;
   float filter_ratio;          /* Lowe ratio */
@@ -986,7 +992,25 @@ void gtx_stabilizer_destroy(gtx_stabilizer* st);
 /* Stabilizer.set_ref_frame(frame, boxes): boxes xywh [n,4] in frame pixels or NULL. */
 int gtx_stabilizer_set_ref_frame(gtx_stabilizer* st, const uint8_t* frame_bgr, int h, int w,
                                  const float* boxes_xywh, int n);
-/* Same, from a half-resolution gray image already in HBM (gtx_detector_gray). */
+/* The stabilizer's working-resolution gray image of a BGR u8 frame [h][w][3] in HBM, written to gray_dptr (gh * gw bytes, any
+ * alignment) by one launch on the context's stream: cv2.cvtColor(BGR2GRAY) then cv2.resize(fx = fy = downsample_ratio,
+ * INTER_LINEAR), as stabilo makes it and as gtx_stabilizer_set_ref_frame / _stabilize make it of a host frame. Any ratio in
+ * (0, 1]; gh, gw must be the working size gtx_op_gray_working_size gives (h / 2, w / 2 at 0.5; h, w at 1.0; else rint(h * ratio),
+ * rint(w * ratio), halves to even), anything else is GTX_ERR_INVALID. The image feeds the _gray_dev entries below of a stabilizer
+ * created with the same frame size and ratio. The tap tables are made on the host once per context, frame size and working size,
+ * and stay with the context: at most 16 such pairs per context (a 17th is GTX_ERR_INVALID), and the gray_resize entries of ONE
+ * context must not be called from two threads at once (contexts are independent; the engine calls them from its detector stage).
+ * gh, gw are passed although the library can compute them: the caller sized gray_dptr by them, and a caller whose idea of the
+ * working size differs from the library's is refused here instead of having its buffer overrun. */
+int gtx_op_gray_working_size(int h, int w, float ratio, int* gh, int* gw);
+int gtx_op_gray_resize_dev(gtx_ctx* ctx, const void* bgr_dptr, int h, int w, float ratio, void* gray_dptr, int gh, int gw);
+/* Mean milliseconds of that launch over `reps` launches between two events on the context's stream, after 3 untimed ones
+ * (tools/stab_ratio_time.py). */
+int gtx_op_gray_resize_ms(gtx_ctx* ctx, const void* bgr_dptr, int h, int w, float ratio, void* gray_dptr, int gh, int gw, int reps, float* ms);
+/* The same on host arrays (staged, synchronous): the kernel on its own, for tests. */
+int gtx_op_gray_resize(gtx_ctx* ctx, const uint8_t* bgr, int h, int w, float ratio, uint8_t* gray, int gh, int gw);
+/* Same as _set_ref_frame, from a gray image of the stabilizer's working size already in HBM (gtx_detector_gray at downsample_ratio 0.5,
+ * gtx_op_gray_resize_dev at any ratio). Another size is GTX_ERR_INVALID; so for the _gray_dev entries below. */
 int gtx_stabilizer_set_ref_gray_dev(gtx_stabilizer* st, const void* gray_dptr, int gh, int gw,
                                     const float* boxes_xywh, int n);
 /* Stabilizer.stabilize(frame, boxes) + get_cur_trans_matrix(): H maps current-frame pixels
