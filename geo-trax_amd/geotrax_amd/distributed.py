@@ -22,6 +22,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from .geometry import LastKnown, xyxy_to_xywh
+
 
 def shard_range(n_frames: int, rank: int, world: int, first: int = 0) -> tuple[int, int]:
     """Contiguous [start, stop) of rank `rank` over frames [first, n_frames)."""
@@ -339,11 +341,7 @@ class Replayer:
     def __init__(self, first: int, tracker, warp_boxes, max_det: int, with_gmc: bool = False):
         self.first, self.tracker, self.warp_boxes, self.max_det, self.with_gmc = first, tracker, warp_boxes, max_det, with_gmc
         self.lists = ([], [], [], [], [], [], [])            # frame_arr, track_id, bbox, bbox_stab, class_id, conf, transforms
-        self.last_H = None
-
-    @staticmethod
-    def _xywh(b):
-        return np.stack([(b[:, 0] + b[:, 2]) / 2, (b[:, 1] + b[:, 3]) / 2, b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1).astype(np.float32)
+        self.last = LastKnown(copy=False)                    # in clip order, as engine._stabilized keeps it
 
     def feed(self, frames, recs) -> None:
         """frames: frame numbers (clip order, continuing the previous feed); recs: their packed records."""
@@ -357,10 +355,7 @@ class Replayer:
             a, b = int(starts[i]), int(starts[i + 1])
             bx, ids, sc, cl = t_xyxy[a:b], t_ids[a:b], t_score[a:b], t_cls[a:b]
             if f != self.first:
-                if H is None:
-                    H = self.last_H                              # stabilo's last known transform (see engine._stabilized)
-                else:
-                    self.last_H = H
+                H, _ = self.last.update(H)
                 if H is not None:
                     transforms.append(np.hstack((np.array([[f]]), H.reshape(1, -1))))
             if len(conf) == 0:
@@ -368,7 +363,7 @@ class Replayer:
             if len(ids) == 0:
                 bx, ids, sc, cl = xyxy, np.full(len(conf), -1), conf, cls
             n = len(ids)
-            xywh = self._xywh(bx)
+            xywh = xyxy_to_xywh(bx)
             frame_arr.append(np.full((n, 1), f, dtype=np.uint32))
             track_id.append(np.asarray(ids).reshape(-1, 1).astype(np.uint16) if (np.asarray(ids) >= 0).all() else np.full((n, 1), -1))
             bbox.append(xywh)

@@ -22,6 +22,7 @@ Ordering rules kept from the reference loop:
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes as C
 import os
 import queue
@@ -34,7 +35,8 @@ import numpy as np
 
 from . import _lib
 from .detector import Detector
-from .geometry import warp_boxes
+from .frames import Yuv420Frame
+from .geometry import LastKnown, stabilized_boxes, xyxy_to_xywh  # noqa: F401  (xyxy_to_xywh: also imported from here)
 from .sift_stabilizer import SiftStabilizer, resident
 from .stabilizer import Stabilizer, working_size
 from .tracker import Tracker
@@ -55,12 +57,6 @@ class FrameResult:
     gmc: np.ndarray | None = None    # 2x3 camera-motion warp the GMC found for the frame (engines built with gmc=True)
     stab_ms: float = 0.0             # GPU time of the frame's stabilizer pass (0 for the reference frame / no stabilizer)
     H_fallback: bool = False         # True when registration failed and H is the last known transform
-
-
-def xyxy_to_xywh(b: np.ndarray) -> np.ndarray | None:
-    if len(b) == 0:
-        return None
-    return np.stack([(b[:, 0] + b[:, 2]) / 2, (b[:, 1] + b[:, 3]) / 2, b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1).astype(np.float32)
 
 
 def parse_prio(text: str | None) -> tuple[int, int]:
@@ -278,6 +274,74 @@ def gray_route(stab_kw: dict | None) -> str | None:
     return "frame" if str(stab_kw.get("detector_name", "orb")) == "orb" else "host"
 
 
+def queue_depths(n_dets: int, B: int, n_stabs: int, gmc: bool, gmc_frames: bool) -> tuple[int, int]:
+    """(batches the stage 1 -> 2 queue holds, frames the stage 2 -> 3 queue holds) of an engine with n_dets detector streams,
+    batches of B frames and n_stabs stabilizers; `gmc`: it has a GMC, `gmc_frames`: one that is handed the BGR frames (ecc).
+
+    A frame's gray image -- the detector's half-resolution one, or the working image of the "frame" route, whose ring follows the
+    same rule -- lives in a ring of GTX_GRAY_RING batches per detector (include/gtx.h; _lib.GRAY_RING): it stays until that
+    detector has started GTX_GRAY_RING - 1 more passes. By then stage 1 has handed on at least (GTX_GRAY_RING - 2) * n_dets * B
+    later frames, so the frames between stage 1 and the stabilizers' collect must stay below that. The GMC's results wait in a
+    64-deep ring, the ECC GMC's prepared frames in a 32-deep one."""
+    n_batches = 2
+    n_frames = 2 * B * n_dets
+    in_flight = (n_batches + 1) * B + n_frames + n_stabs + 1
+    assert in_flight <= (_lib.GRAY_RING - 2) * n_dets * B, "engine queues outlive the detector's gray ring"
+    assert not gmc or (n_batches + 2) * B <= 63, "engine queues outrun the GMC's 64-deep result ring"
+    # ECC frames are queued when a batch goes to its detector: one batch in flight per detector stream, the batches of the stage
+    # queue, the one the detector stage holds and the one the tracker stage holds, plus a shard rank's template frame
+    assert not (gmc and gmc_frames) or (n_dets + n_batches + 2) * B + 1 <= 31, "engine queues outrun the ECC GMC's 32-deep frame ring"
+    return n_batches, n_frames
+
+
+class _Lane:
+    """One detector stream of the engine and what belongs to it alone: the detector, its ReID encoder (or None), the device
+    buffers host frames are staged in, the ring of working gray images of the "frame" route, and what stage 1 knows of the
+    lane's one batch in flight. The buffers are allocated on first use, on the detector's context; close() frees them."""
+
+    def __init__(self, det: Detector, enc=None):
+        self.det, self.enc = det, enc
+        self.stage = self.yuv = 0        # device staging: B BGR frames / the I420 planes of one frame
+        self.ring, self.slot = 0, 0      # _GRAY_RING x B working gray images; slot of the newest batch
+        self.frames = 0                  # the batch in flight: device pointer of its frames (the ReID crops read them),
+        self.work = None                 # (pointer, gh, gw) of its working gray images ("frame" route),
+        self.hosts = None                # its frames on the host ("host" route: the stabilizers register host frames)
+
+    def stage_buffer(self, nbytes: int) -> int:
+        self.stage = self.stage or self.det.ctx.dev_alloc(nbytes)
+        return self.stage
+
+    def yuv_buffer(self, nbytes: int) -> int:
+        self.yuv = self.yuv or self.det.ctx.dev_alloc(nbytes)
+        return self.yuv
+
+    def gray_ring(self, nbytes: int) -> int:
+        self.ring = self.ring or self.det.ctx.dev_alloc(nbytes)
+        return self.ring
+
+    def close(self) -> None:
+        for p in (self.stage, self.yuv, self.ring):
+            if p:
+                self.det.ctx.dev_free(p)
+        self.stage = self.yuv = self.ring = 0
+        self.det.close()
+
+
+@dataclass
+class _Batch:
+    """A batch on its way through the host stages: made when it goes to its lane's detector, filled in when the pass is
+    collected, read by the tracker stage."""
+    lane: _Lane
+    n: int                           # frames
+    n_skip: int = 0                  # GMC warps queued ahead of the batch's own that nobody reads (the frame that primed it)
+    prime: int | None = None         # a shard rank's batch: device pointer of the frame the GMC is primed with
+    restart: bool = False            # the batch does not continue the previous one: the GMC starts a new sequence
+    dets: list | None = None         # detections per frame
+    grays: list | None = None        # (pointer, gh, gw) per frame of the image the stabilizers read: the detector's or the lane's
+    hosts: list | None = None        # the frames on the host ("host" route)
+    det_ms: float = 0.0
+
+
 class ExtractEngine:
     def __init__(self, weights: dict, frame_hw: tuple[int, int], det_kw: dict, tracker: Tracker | None, stab_kw: dict | None, *,
                  device: int | None = None, batch: int = 2, det_streams: int = 2, stab_streams: int = 4, gmc: bool | str = False,
@@ -296,7 +360,6 @@ class ExtractEngine:
         n_stab = max(1, min(int(stab_streams), 4 * n_dets * self.B - 2)) if stab_kw is not None else 0   # frames in flight < gray ring lifetime
         self.tracker = tracker
         self.reid_tensors = getattr(tracker, "reid_tensors", None) if tracker is not None and getattr(tracker, "with_reid", False) else None
-        self.encoders = {}               # id(detector) -> ReIDEncoder on that detector's context (`model: <cls checkpoint>`)
         if tracker is not None and getattr(tracker, "with_reid", False) and self.reid_tensors is None:   # `with_reid: true, model: auto`: a vector per box
             det_kw = dict(det_kw, obj_feats=True)
             if any(not getattr(d, "obj_feats", False) for d in self.dets):
@@ -321,38 +384,62 @@ class ExtractEngine:
         stab_cls = stab_cls or stabilizer_class(stab_kw)
         while len(self.stabs) < n_stab:
             self.stabs.append(stab_cls(self.frame_hw, ctx=take("s"), **stab_kw))
+        self._lanes = [_Lane(d) for d in self.dets]
         if self.reid_tensors is not None:
-            # the separate ReID network runs on each detector's own stream (no stream of its own: the StreamPlan is the one runs
-            # without ReID get), in stream order behind the detector pass that read the same frames
+            # the separate ReID network (`model: <cls checkpoint>`) runs on each detector's own stream (no stream of its own: the
+            # StreamPlan is the one runs without ReID get), in stream order behind the detector pass that read the same frames
             from .reid import ReIDEncoder
 
-            for d in self.dets:
-                self.encoders[id(d)] = ReIDEncoder(self.reid_tensors, ctx=d.ctx, max_crops=min(d.max_det * self.B, 256),
-                                                     fp32_split=det_kw.get("fp32_split"))   # `engine: {fp32_split}` as YOLO.track gets it; None: the library default (also under half)
+            for lane in self._lanes:
+                lane.enc = ReIDEncoder(self.reid_tensors, ctx=lane.det.ctx, max_crops=min(lane.det.max_det * self.B, 256),
+                                       fp32_split=det_kw.get("fp32_split"))   # `engine: {fp32_split}` as YOLO.track gets it; None: the library default (also under half)
         self.feeder_ctx = take("f") if feeder_stream else None   # the context a read-ahead feeder's transfers run on
         if gmc:                          # True / "sparseOptFlow": the GPU Lucas-Kanade GMC; "orb" / "sift": the feature-based ones (gmc.FeatureGMC); "ecc": gmc.EccGMC
             from .gmc import make_gmc
 
             self.gmc = make_gmc(self.frame_hw, method=gmc if isinstance(gmc, str) else "sparseOptFlow", ctx=take("g"),
                                 **(gmc_kw or {}))    # gmc_kw: the GMC object's own keywords (`engine: {gmc: {...}}`, e.g. ecc's max_iters)
-        self.use_dev_gray = bool(self.stabs) and float(stab_kw.get("downsample_ratio", 0.5)) == 0.5
+        self._gmc_frames_route = self.gmc is not None and self.gmc.wants_frames   # ecc: the GMC is handed the BGR frames, not gray images
         # gray_route(): "frame" = the stabilizers' working image is made from each BGR frame in HBM, at the stabilizer's own ratio
         self.gray_route = gray_route(stab_kw) if self.stabs else None
         self.stab_dev_gray = self.gray_route in ("detector", "frame")   # the stabilizers read gray images in HBM (no host frames kept)
-        self._work_hw = working_size(self.frame_hw, stab_kw["downsample_ratio"]) if self.gray_route == "frame" else None
-        self._work_ratio = float(stab_kw["downsample_ratio"]) if self.gray_route == "frame" else None
-        self._work_ring = {}             # per detector: [device pointer of _GRAY_RING x B working gray images, slot of the newest batch]
-        self._work_grays = {}            # per detector: (pointer, gh, gw) of every frame of its batch in flight
-        self._stage = {}                 # per detector: device staging buffer for host frames
-        self._host_frames = {}           # frames kept for the host-gray fallback of the stabilizer
-        self._frames_of = {}             # per detector: device pointer of the frames of its batch in flight (the ReID crops read them)
-        self._last_frames = 0
+        # the "frame" route's working image: (gh, gw, downsample_ratio)
+        self._work = (*working_size(self.frame_hw, stab_kw["downsample_ratio"]), float(stab_kw["downsample_ratio"])) if self.gray_route == "frame" else None
+        self._frame_bytes = self.frame_hw[0] * self.frame_hw[1] * 3
         self._index, self._have_ref = 0, False
-        self._last_H = None              # last valid current->reference transform, in frame order
+        self._last = LastKnown()         # last valid current->reference transform, in frame order
         self._prof = self.prof = None    # GTX_ENGINE_PROF=1: see run()
         self._gmc_sub = self._gmc_col = 0   # frames queued on the GMC stream / warps taken (one writer thread each)
 
     _IDLE = object()                 # drain() -> _stabilized(): no frame arrived for a few milliseconds
+    _NO_TIMER = contextlib.nullcontext()
+
+    @property
+    def encoders(self) -> dict:
+        """lane index -> the ReIDEncoder on that lane's detector context; empty without a separate ReID network. Read-only, built
+        on every access; the keys used to be id(detector)."""
+        return {i: lane.enc for i, lane in enumerate(self._lanes) if lane.enc is not None}
+
+    @property
+    def _host_frames(self) -> list:
+        """The host frames the lanes keep for the stabilizers (only the "host" route keeps any, and only while a batch is in flight)."""
+        return [lane.hosts for lane in self._lanes if lane.hosts is not None]
+
+    # ---- GTX_ENGINE_PROF=1 (see run()): seconds spent in a block of a host stage, and the moment it ended
+    def _timed(self, key: str, what: str | None = None, index: int = 0):
+        return self._NO_TIMER if self._prof is None else self._timer(key, what, index)
+
+    @contextlib.contextmanager
+    def _timer(self, key, what, index):
+        t0 = time.perf_counter()
+        yield
+        self._prof[key] += time.perf_counter() - t0
+        if what is not None:
+            self.marks.append((what, index, time.perf_counter() - self._t_run))
+
+    def _check_frame(self, f) -> None:
+        if tuple(f.shape[:2]) != self.frame_hw:
+            raise ValueError(f"frame is {f.shape[1]}x{f.shape[0]}, engine was built for {self.frame_hw[1]}x{self.frame_hw[0]}")
 
     #: host threads the engine adds to the caller's: the detector stage and the GMC + tracker stage (the stabilizer stage runs on
     #: the thread that iterates run()). All three wait on HIP events with hipEventBlockingSync, i.e. asleep while the GPU works:
@@ -366,21 +453,20 @@ class ExtractEngine:
         if hasattr(frame, "bgr"):                               # a Yuv420Frame of a .y4m source
             frame = frame.bgr()
         frame = np.ascontiguousarray(frame, np.uint8)
-        det = self.dets[0]
+        lane = self._lanes[0]
+        det = lane.det
         d = det.detect(frame)
         g = det.gray_dptr(0)
-        if self.gray_route == "frame" and self.stabs:           # the frame's working gray, made in HBM as for every later frame
-            if tuple(frame.shape[:2]) != self.frame_hw:
-                raise ValueError(f"frame is {frame.shape[1]}x{frame.shape[0]}, engine was built for {self.frame_hw[1]}x{self.frame_hw[0]}")
-            key = id(det)
+        if self.gray_route == "frame":                          # the frame's working gray, made in HBM as for every later frame
+            self._check_frame(frame)
             ref = det.ctx.dev_alloc(frame.nbytes)               # one frame, for this call only (a run on device batches never stages host frames)
             try:
                 det.ctx.dev_upload(ref, frame)
-                self._frame_grays(det, ref, 1)
+                self._frame_grays(lane, ref, 1)
                 det.ctx.synchronize()
             finally:
                 det.ctx.dev_free(ref)
-            g = self._work_grays.pop(key)[0]
+            g, lane.work = lane.work[0], None
         boxes = d.xywh if len(d) else None
         for st in self.stabs:                                   # same reference image -> identical reference keypoints
             if self.stab_dev_gray:
@@ -392,25 +478,26 @@ class ExtractEngine:
     def reset(self, keep_reference: bool = False) -> None:
         """Forget the tracks and the camera-motion state (and, unless told otherwise, the reference frame)."""
         self._index = 0
-        self._last_H = None
+        self._last.reset()
         if not keep_reference:
             self._have_ref = False
         if self.tracker is not None:
             self.tracker.reset()
-        if self.gmc is not None:
-            while self._gmc_sub > self._gmc_col:                # a run that was abandoned half way
-                self._gmc_collect()
+        if self.gmc is not None:                                # a run that was abandoned half way leaves warps nobody took
+            if self._gmc_frames_route:
+                # gtx_ecc_reset (Ecc::reset, csrc/ecc.hip) drops the frames that were submitted and never collected by itself;
+                # collecting them here would run every one's fit, up to max_iters iterations each
+                self._gmc_col = self._gmc_sub
+            else:
+                while self._gmc_sub > self._gmc_col:
+                    self._gmc_collect()
             self.gmc.reset_params()
 
     def close(self) -> None:
-        for d in self.dets:
-            for p in [self._stage.pop(id(d), None), self._stage.pop(("yuv", id(d)), None), (self._work_ring.pop(id(d), None) or [None])[0]]:
-                if p:
-                    d.ctx.dev_free(p)
-            d.close()
-        for e in self.encoders.values():
+        for lane in self._lanes:
+            lane.close()
+        for e in self.encoders.values():                        # after every detector, as always
             e.close()
-        self.encoders = {}
         for s in self.stabs:
             s.close()
         if self.gmc is not None:
@@ -418,100 +505,88 @@ class ExtractEngine:
         for c in self._taken:                                   # the streams stay alive for the next engine of the process
             self.plan.give_back(c)
         self.feeder_ctx = None
-        self.dets, self.stabs, self.gmc, self._taken = [], [], None, []
+        self.dets, self._lanes, self.stabs, self.gmc, self._taken = [], [], [], None, []
 
     # ---- feeding
-    def _submit(self, det: Detector, batch) -> int:
+    def _submit(self, lane: _Lane, batch) -> int:
+        """A batch of any of run()'s three kinds goes to the lane's detector -> the number of its frames. The kinds differ only in
+        how the batch becomes (device pointer of n contiguous frames, n); what is queued on the detector's stream then is the same."""
+        det, hosts = lane.det, None
         if isinstance(batch, (int, np.integer)):                # device pointer to B contiguous frames
-            self._gmc_frames(det, int(batch), self.B)
-            self._frame_grays(det, int(batch), self.B)
-            det.submit_dev(int(batch), self.B)
-            self._last_frames = int(batch)
-            return self.B
-        from .feeder import DeviceBatch
-        from .frames import Yuv420Frame
+            ptr, n = int(batch), self.B
+        else:
+            from .feeder import DeviceBatch
 
-        if isinstance(batch, DeviceBatch):                      # frames a read-ahead feeder is bringing into HBM: the detector's
-            if not 1 <= batch.n <= self.B:                      # stream waits for their upload, this thread does not
-                raise ValueError(f"a batch holds 1..{self.B} frames, got {batch.n}")
-            if self.stabs and not self.stab_dev_gray:
-                raise ValueError("device batches need a stabilizer that works on gray images in HBM (detector_name orb at any downsample_ratio, "
-                                 "sift / rsift at 0.5)")
-            batch.wait_on(det.ctx)
-            self._gmc_frames(det, batch.ptr, batch.n)
-            self._frame_grays(det, batch.ptr, batch.n)
-            det.submit_dev(batch.ptr, batch.n)
-            self._last_frames = batch.ptr
-            return batch.n
-
-        frames = [f if isinstance(f, Yuv420Frame) else np.ascontiguousarray(f, dtype=np.uint8) for f in batch]
-        if not 1 <= len(frames) <= self.B:
-            raise ValueError(f"a batch holds 1..{self.B} frames, got {len(frames)}")
-        nbytes = self.frame_hw[0] * self.frame_hw[1] * 3
-        key = id(det)
-        if key not in self._stage:
-            self._stage[key] = det.ctx.dev_alloc(nbytes * self.B)
-        for i, f in enumerate(frames):
-            if tuple(f.shape[:2]) != self.frame_hw:
-                raise ValueError(f"frame is {f.shape[1]}x{f.shape[0]}, engine was built for {self.frame_hw[1]}x{self.frame_hw[0]}")
-            if isinstance(f, Yuv420Frame):                      # I420 planes cross PCIe (half the bytes), BGR is made on the GPU
-                ykey = ("yuv", key)
-                if ykey not in self._stage:
-                    self._stage[ykey] = det.ctx.dev_alloc(len(f.data))
-                det.ctx.dev_upload(self._stage[ykey], f.data)
-                _lib.check(det.ctx.lib.gtx_yuv420_to_bgr_dev(det.ctx.handle, C.c_void_p(self._stage[ykey]), f.h, f.w,
-                                                             C.c_void_p(self._stage[key] + i * nbytes)))
+            hosts = None if isinstance(batch, DeviceBatch) else [f if isinstance(f, Yuv420Frame) else np.ascontiguousarray(f, dtype=np.uint8) for f in batch]
+            n = batch.n if hosts is None else len(hosts)
+            if not 1 <= n <= self.B:
+                raise ValueError(f"a batch holds 1..{self.B} frames, got {n}")
+            if hosts is None:                                   # frames a read-ahead feeder is bringing into HBM: the detector's
+                if self.gray_route == "host":                   # stream waits for their upload, this thread does not
+                    raise ValueError("device batches need a stabilizer that works on gray images in HBM (detector_name orb at any downsample_ratio, "
+                                     "sift / rsift at 0.5)")
+                batch.wait_on(det.ctx)
+                ptr = batch.ptr
             else:
-                det.ctx.dev_upload(self._stage[key] + i * nbytes, f)
-        self._gmc_frames(det, self._stage[key], len(frames))
-        self._frame_grays(det, self._stage[key], len(frames))
-        det.submit_dev(self._stage[key], len(frames))
-        self._last_frames = self._stage[key]
-        if self.stabs and not self.stab_dev_gray:
-            self._host_frames[key] = [f.bgr() if isinstance(f, Yuv420Frame) else f for f in frames]
-        return len(frames)
+                ptr = self._stage_frames(lane, hosts)
+        self._gmc_frames(det, ptr, n)
+        self._frame_grays(lane, ptr, n)
+        det.submit_dev(ptr, n)
+        lane.frames = ptr
+        if hosts is not None and self.gray_route == "host":
+            lane.hosts = [f.bgr() if isinstance(f, Yuv420Frame) else f for f in hosts]
+        return n
+
+    def _stage_frames(self, lane: _Lane, frames: list) -> int:
+        """Host frames (BGR arrays, or the Yuv420Frame objects of a .y4m source) into the lane's staging buffer -> its pointer."""
+        ctx, nbytes = lane.det.ctx, self._frame_bytes
+        stage = lane.stage_buffer(nbytes * self.B)
+        for i, f in enumerate(frames):
+            self._check_frame(f)
+            if isinstance(f, Yuv420Frame):                      # I420 planes cross PCIe (half the bytes), BGR is made on the GPU
+                yuv = lane.yuv_buffer(len(f.data))
+                ctx.dev_upload(yuv, f.data)
+                _lib.check(ctx.lib.gtx_yuv420_to_bgr_dev(ctx.handle, C.c_void_p(yuv), f.h, f.w, C.c_void_p(stage + i * nbytes)))
+            else:
+                ctx.dev_upload(stage + i * nbytes, f)
+        return stage
 
     def _gmc_frames(self, det: Detector, ptr: int, n: int) -> None:
         """A GMC that works on the BGR frames (gmc_method ecc) gets every frame of a batch here, when the batch goes to its
         detector: the frame's image is prepared on the detector's stream, behind whatever brought the frame into HBM and AHEAD of
         the detector pass -- collect() of that pass therefore also covers it, and the next batch may overwrite the frame buffer.
         Submission order = clip order (batches go to the detectors in clip order)."""
-        if self.gmc is None or not getattr(self.gmc, "wants_frames", False):
+        if not self._gmc_frames_route:
             return
-        nbytes = self.frame_hw[0] * self.frame_hw[1] * 3
         for i in range(n):
-            self.gmc.submit_frame_dev(ptr + i * nbytes, self.frame_hw[0], self.frame_hw[1], producer=det.ctx)
+            self.gmc.submit_frame_dev(ptr + i * self._frame_bytes, self.frame_hw[0], self.frame_hw[1], producer=det.ctx)
             self._gmc_sub += 1
 
     #: batches whose working gray images a detector keeps on the "frame" route: the depth of the detector's own gray ring
     #: (GTX_GRAY_RING of include/gtx.h = DetectorBase::kGrayRing, through _lib.GRAY_RING), whose lifetime rule these buffers share;
-    #: the queue-depth assert of _tracked_frames_threaded is written in the same number
+    #: queue_depths() is written in the same number
     _GRAY_RING = _lib.GRAY_RING
 
-    def _frame_grays(self, det: Detector, ptr: int, n: int) -> None:
+    def _frame_grays(self, lane: _Lane, ptr: int, n: int) -> None:
         """The "frame" route (gray_route): the stabilizers' working gray image of every frame of a batch, made from the BGR frame in
         HBM by gtx_op_gray_resize_dev on the detector's stream when the batch goes to its detector -- as _gmc_frames does for ECC:
         behind whatever brought the frame into HBM and ahead of the detector pass, so collect() of that pass covers it and the next
         batch may overwrite the frame buffer. The images go to the next slot of a per-detector ring as deep as the detector's own
         gray ring, advanced once per batch like it: a frame's image stays until that detector has taken _GRAY_RING - 1 more batches,
-        which the queue depths of _tracked_frames_threaded keep beyond the stabilizers' reads."""
-        if self.gray_route != "frame" or not self.stabs:
+        which queue_depths() keeps beyond the stabilizers' reads."""
+        if self._work is None:
             return
-        gh, gw = self._work_hw
+        gh, gw, ratio = self._work
         stride = -(-gh * gw // 256) * 256                       # every image starts on a 256-byte boundary (dword stores)
-        key = id(det)
-        if key not in self._work_ring:
-            self._work_ring[key] = [det.ctx.dev_alloc(self._GRAY_RING * self.B * stride), 0]
-        ring = self._work_ring[key]
-        ring[1] = (ring[1] + 1) % self._GRAY_RING
-        nbytes = self.frame_hw[0] * self.frame_hw[1] * 3
-        out = []
+        ctx = lane.det.ctx
+        ring = lane.gray_ring(self._GRAY_RING * self.B * stride)
+        lane.slot = (lane.slot + 1) % self._GRAY_RING
+        lane.work = []
         for i in range(n):
-            g = ring[0] + (ring[1] * self.B + i) * stride
-            _lib.check(det.ctx.lib.gtx_op_gray_resize_dev(det.ctx.handle, C.c_void_p(ptr + i * nbytes), self.frame_hw[0], self.frame_hw[1],
-                                                          self._work_ratio, C.c_void_p(g), gh, gw))
-            out.append((g, gh, gw))
-        self._work_grays[key] = out
+            g = ring + (lane.slot * self.B + i) * stride
+            _lib.check(ctx.lib.gtx_op_gray_resize_dev(ctx.handle, C.c_void_p(ptr + i * self._frame_bytes), self.frame_hw[0], self.frame_hw[1],
+                                                      ratio, C.c_void_p(g), gh, gw))
+            lane.work.append((g, gh, gw))
 
     def run(self, batches, paced: bool | None = None):
         """paced: the source is a live stream (see PacedSource); None = what the source declares (`batches.paced`, default False).
@@ -538,8 +613,9 @@ class ExtractEngine:
     # ---- stage 1: detector batches (submit keeps every detector stream busy; collect blocks on the oldest pass)
     def _detected_batches(self, batches):
         it = iter(batches)
-        inflight = collections.deque()                          # (detector, frames in the batch)
+        inflight = collections.deque()                          # the _Batch of every pass in flight, oldest first
         k = 0
+        h, w = self.frame_hw
 
         paced = self._paced                                      # a live stream (PacedSource): work for latency, not for throughput
         exhausted = False
@@ -550,22 +626,21 @@ class ExtractEngine:
             if b is None:
                 exhausted = True
                 return
-            prev = None
-            if isinstance(b, tuple):                            # (batch, device pointer of the frame before it | None | False)
-                b, prev = b
-                prev = False if prev is None else prev          # None: the batch opens the clip -> restart without a frame
-            det = self.dets[k % len(self.dets)]
+            restart, prime = False, None
+            if isinstance(b, tuple):                            # (batch, prev): the batch does not continue the previous one; prev is the
+                b, prev = b                                     # device pointer of the frame before it, or None (False): it opens the clip
+                restart, prime = True, None if prev is None or prev is False else int(prev)
+            lane = self._lanes[k % len(self._lanes)]
             k += 1
             n_skip = 0
-            if prev is not None and prev is not False and self.gmc is not None and getattr(self.gmc, "wants_frames", False):
+            if prime is not None and self._gmc_frames_route:
                 # gmc_method ecc registers every frame against the clip's FIRST frame: a shard rank that does not hold that frame
                 # hands it over here (`prev`), once, ahead of its first batch -- it becomes the template, its identity warp is dropped
-                n_skip = self.gmc.submit_frame_dev(int(prev), self.frame_hw[0], self.frame_hw[1])
+                n_skip = self.gmc.submit_frame_dev(prime, h, w)
                 self._gmc_sub += n_skip
-            inflight.append((det, self._submit(det, b), prev, n_skip))
-            self._frames_of[id(det)] = self._last_frames
+            inflight.append(_Batch(lane, self._submit(lane, b), n_skip, prime, restart))
 
-        host_gray = bool(self.stabs) and not self.stab_dev_gray
+        host_gray = self.gray_route == "host"
         try:
             def fill():                                             # a pass in flight on every detector stream -- unless the source is a stream
                 while not exhausted and not paced and len(inflight) < len(self.dets):
@@ -574,78 +649,70 @@ class ExtractEngine:
             submit_next()
             fill()
             while inflight:
-                det, nb, prev, n_skip = inflight.popleft()
-                t0 = time.perf_counter() if self._prof is not None else 0.0
-                dets = det.collect()
-                if self._prof is not None:
-                    self._prof["det_collect"] += time.perf_counter() - t0
-                    self.marks.append(("det", k - len(inflight) - 1, time.perf_counter() - self._t_run))
-                enc = self.encoders.get(id(det))
-                if enc is not None:
+                bt = inflight.popleft()
+                lane, det = bt.lane, bt.lane.det
+                with self._timed("det_collect", "det", k - len(inflight) - 1):
+                    bt.dets = det.collect()
+                if lane.enc is not None:
                     # the crops are cut now, before anything can refill this batch's frames: the next batch for this detector
                     # (its staging buffer), the feeder's slot release and the re-run of a saturated pass all come after this
                     # collect. The vectors ride on the detections to the tracker stage.
-                    t0 = time.perf_counter() if self._prof is not None else 0.0
-                    enc.submit_dev(self._frames_of.pop(id(det)), self.frame_hw[0], self.frame_hw[1], [d.xyxy for d in dets])
-                    for d, f in zip(dets, enc.collect()):
-                        d.feats = f
-                    if self._prof is not None:
-                        self._prof["reid"] += time.perf_counter() - t0
-                grays = [det.gray_dptr(b) for b in range(nb)]
-                hosts = self._host_frames.pop(id(det), None)
-                work = self._work_grays.pop(id(det), None)          # the "frame" route: the stabilizers' own images of this batch
-                det_ms = float(sum(dets[0].speed.values())) / nb if dets else 0.0
+                    with self._timed("reid"):
+                        lane.enc.submit_dev(lane.frames, h, w, [d.xyxy for d in bt.dets])
+                        for d, f in zip(bt.dets, lane.enc.collect()):
+                            d.feats = f
+                det_grays = [det.gray_dptr(b) for b in range(bt.n)]
+                # what the lane holds of this batch leaves with it now: fill() below may give the lane its next batch. The stabilizers
+                # read their own working images where the lane made them ("frame" route), else the detector's half-resolution ones
+                bt.grays = det_grays if lane.work is None else lane.work
+                bt.hosts, lane.hosts, lane.work = lane.hosts, None, None
+                bt.det_ms = float(sum(bt.dets[0].speed.values())) / bt.n if bt.dets else 0.0
                 late = host_gray or paced                           # paced source: the batch's results leave before the stage blocks on the next one
                 if not late:
                     fill()                                      # keep the detectors busy while the host works on the batch
-                if self.gmc is not None and not getattr(self.gmc, "wants_frames", False):   # the batch queues on the GMC stream now, results in order
-                    restart = prev is not None                  # a shard rank's batch: it does not continue the previous one
-                    if restart and prev is not False:           # the frame that precedes the batch in the clip, from HBM
-                        self.gmc.submit_frame_dev(int(prev), self.frame_hw[0], self.frame_hw[1], restart=True)
+                if self.gmc is not None and not self._gmc_frames_route:   # the batch queues on the GMC stream now, results in order
+                    restart = bt.restart                        # a shard rank's batch: it does not continue the previous one
+                    if bt.prime is not None:                    # the frame that precedes the batch in the clip, from HBM
+                        self.gmc.submit_frame_dev(bt.prime, h, w, restart=True)
                         self._gmc_sub += 1
-                        n_skip, restart = 1, False
-                    for g in grays:                             # every frame, detections or not (BOTSORT.update -> gmc.apply)
+                        bt.n_skip, restart = 1, False
+                    for g in det_grays:                         # every frame, detections or not (BOTSORT.update -> gmc.apply)
                         if restart:                             # no frame before it: the batch's first frame opens the sequence
                             self.gmc.reset_sequence()
                             restart = False
                         self.gmc.submit_gray_dev(*g)
                         self._gmc_sub += 1
-                yield det, dets, grays, hosts, det_ms, n_skip, work
+                yield bt
                 if host_gray:
                     submit_next()
                 elif late and not inflight and not exhausted:       # a stream: everything in flight has been handed on; now wait for the next batch
                     submit_next()
         finally:                                                # consumer stopped early or a stage failed: leave no pass in flight
-            for det, *_ in inflight:
+            for bt in inflight:
                 try:
-                    det.collect()
+                    bt.lane.det.collect()
                 except Exception:
                     pass
-            self._host_frames.clear()
-            self._work_grays.clear()
+            for lane in self._lanes:
+                lane.hosts = lane.work = None
 
     # ---- stage 2: camera-motion compensation + tracker, strictly in clip order
-    def _track_batch(self, det, dets, grays, hosts, det_ms, n_skip=0, work=None):
+    def _track_batch(self, bt: _Batch):
         # a generator: a frame goes on to the stabilizer stage while the tracker works on the next one of its batch
-        if work is not None:                                    # the stabilizer stage reads its own working images, not the detector's
-            grays = work
-        for _ in range(n_skip):                                 # warp of the frame that only primed the GMC (identity)
+        for _ in range(bt.n_skip):                              # warp of the frame that only primed the GMC (identity)
             self._gmc_collect()
-        for b, (d, g) in enumerate(zip(dets, grays)):
+        for b, (d, g) in enumerate(zip(bt.dets, bt.grays)):
             ids = None
             xyxy, conf, cls = d.xyxy, d.conf, d.cls
             warp = self._gmc_collect() if self.gmc is not None else None
             if self.tracker is not None:                        # also on frames without detections (frame counter, lost/removed ageing)
-                t0 = time.perf_counter() if self._prof is not None else 0.0
-                t_xyxy, t_ids, t_score, t_cls, _ = self.tracker.update(d.xyxy, d.conf, d.cls, gmc=warp, feats=d.feats)
-                if self._prof is not None:
-                    self._prof["tracker"] += time.perf_counter() - t0
-                    self.marks.append(("trk", self._index, time.perf_counter() - self._t_run))
+                with self._timed("tracker", "trk", self._index):
+                    t_xyxy, t_ids, t_score, t_cls, _ = self.tracker.update(d.xyxy, d.conf, d.cls, gmc=warp, feats=d.feats)
                 if len(t_ids):
                     xyxy, conf, cls, ids = t_xyxy, t_score, t_cls, t_ids
-            r = FrameResult(self._index, xyxy, conf, cls, ids, xyxy_to_xywh(xyxy), None, None, len(d), det_ms, warp)
+            r = FrameResult(self._index, xyxy, conf, cls, ids, xyxy_to_xywh(xyxy), None, None, len(d), bt.det_ms, warp)
             self._index += 1
-            yield r, det, g, hosts[b] if hosts is not None else None
+            yield r, bt.lane.det, g, bt.hosts[b] if bt.hosts is not None else None
 
     def _gmc_collect(self):
         warp = self.gmc.collect()
@@ -654,21 +721,10 @@ class ExtractEngine:
 
     def _tracked_frames(self, batches):
         for item in self._detected_batches(batches):
-            yield from self._track_batch(*item)
+            yield from self._track_batch(item)
 
     def _tracked_frames_threaded(self, batches):
-        # Queue depths. A frame's gray image lives in its detector's 16-deep ring (net_runtime.hpp DetectorBase::kGrayRing) until that
-        # detector has started 15 more passes; by then stage 1 has handed on at least 14 * n_dets * B later frames, so
-        # the frames between stage 1 and the stabilizer's collect must stay below that.
-        n_batches = 2
-        n_frames = 2 * self.B * len(self.dets)
-        in_flight = (n_batches + 1) * self.B + n_frames + len(self.stabs) + 1
-        assert in_flight <= (self._GRAY_RING - 2) * len(self.dets) * self.B, "engine queues outlive the detector's gray ring"
-        assert self.gmc is None or (n_batches + 2) * self.B <= 63, "engine queues outrun the GMC's 64-deep result ring"
-        # ECC frames are queued when a batch goes to its detector: one batch in flight per detector stream, the batches of the stage
-        # queue, the one the detector stage holds and the one the tracker stage holds, plus a shard rank's template frame
-        assert self.gmc is None or not getattr(self.gmc, "wants_frames", False) or (len(self.dets) + n_batches + 2) * self.B + 1 <= 31, \
-            "engine queues outrun the ECC GMC's 32-deep frame ring"
+        n_batches, n_frames = queue_depths(len(self.dets), self.B, len(self.stabs), self.gmc is not None, self._gmc_frames_route)
         q_det = queue.Queue(maxsize=n_batches)                  # detected batches
         q_trk = queue.Queue(maxsize=n_frames)                   # tracked frames
         stop = threading.Event()
@@ -713,7 +769,7 @@ class ExtractEngine:
                 yield item
 
         t1 = threading.Thread(target=stage, args=(self._detected_batches(batches), q_det, lambda item: (item,)), daemon=True)
-        t2 = threading.Thread(target=stage, args=(drain(q_det), q_trk, lambda item: self._track_batch(*item)), daemon=True)
+        t2 = threading.Thread(target=stage, args=(drain(q_det), q_trk, self._track_batch), daemon=True)
         t1.start()
         t2.start()
         try:
@@ -733,31 +789,21 @@ class ExtractEngine:
     def _stabilized(self, frames):
         pending = collections.deque()                           # (stabilizer, partial FrameResult) awaiting collect
 
-        def last_known(r):
+        def registered(r, st):
             # stabilo keeps `trans_matrix_last_known`: when a frame cannot be registered (too few matches, no model)
             # the previous valid transform is used for its boxes and reported as its matrix. Results leave here in
             # frame order, so "last" is the previous frame's, whichever stabilizer object produced it.
-            if r.H is None:
-                if self._last_H is not None:
-                    r.H, r.H_fallback = self._last_H.copy(), True
-            else:
-                self._last_H = r.H.copy()
-
-        prof = self._prof
+            r.H, r.H_fallback = self._last.update(st.get_cur_trans_matrix(raw=True))
+            if r.xywh is not None:
+                r.xywh_stab = stabilized_boxes(r.H, r.xywh)
+            return r
 
         def finish():
             st, r = pending.popleft()
-            t0 = time.perf_counter() if prof is not None else 0.0
-            st.collect()
-            if prof is not None:
-                prof["stab_collect"] += time.perf_counter() - t0
-                self.marks.append(("stab", r.index, time.perf_counter() - self._t_run))
-            r.H = st.get_cur_trans_matrix(raw=True)
+            with self._timed("stab_collect", "stab", r.index):
+                st.collect()
             r.stab_ms = st.last_ms()
-            last_known(r)
-            if r.xywh is not None:
-                r.xywh_stab = warp_boxes(r.H, r.xywh) if r.H is not None else r.xywh.copy()
-            return r
+            return registered(r, st)
 
         try:
             for item in frames:
@@ -784,20 +830,14 @@ class ExtractEngine:
                     yield finish()
                 st = self.stabs[r.index % len(self.stabs)]
                 if self.stab_dev_gray:
-                    t0 = time.perf_counter() if prof is not None else 0.0
-                    st.submit_gray_dev(g[0], g[1], g[2], r.xywh)
-                    if prof is not None:
-                        prof["stab_submit"] += time.perf_counter() - t0
-                        self.marks.append(("sub", r.index, time.perf_counter() - self._t_run))
-                        prof["frames"] += 1
+                    with self._timed("stab_submit", "sub", r.index):
+                        st.submit_gray_dev(g[0], g[1], g[2], r.xywh)
+                    if self._prof is not None:
+                        self._prof["frames"] += 1
                     pending.append((st, r))
                 else:                                               # the "host" route (sift / rsift on host frames): one blocking call
                     st.stabilize(host, r.xywh)
-                    r.H = st.get_cur_trans_matrix(raw=True)
-                    last_known(r)
-                    if r.xywh is not None:
-                        r.xywh_stab = warp_boxes(r.H, r.xywh) if r.H is not None else r.xywh.copy()
-                    yield r
+                    yield registered(r, st)
             while pending:
                 yield finish()
         finally:                                                # abandoned run: take what the stabilizers still owe

@@ -1,5 +1,6 @@
 """Projective helpers over the C ABI (host, f64): box warp of the stabilizer and the point
-transform of the georeference stage.
+transform of the georeference stage; and the transform bookkeeping the stabilizer classes, the
+engine and the sharded replay share (last known transform, box warp, working -> frame pixels).
 
 Reference calls replaced: stabilo ``Stabilizer.transform_cur_boxes()`` (geotrax/extract.py:183)
 and ``cv2.perspectiveTransform`` inside ``apply_homography`` (geotrax/georeference.py:599-605);
@@ -21,6 +22,47 @@ def warp_boxes(H: np.ndarray, xywh: np.ndarray) -> np.ndarray:
     out = np.empty_like(b)
     check(lib.gtx_warp_boxes(ptr(Hm), ptr(b), len(b), ptr(out)))
     return out
+
+
+def xyxy_to_xywh(b: np.ndarray) -> np.ndarray | None:
+    """Corner boxes -> centre/size float32; None for a frame without boxes."""
+    if len(b) == 0:
+        return None
+    return np.stack([(b[:, 0] + b[:, 2]) / 2, (b[:, 1] + b[:, 3]) / 2, b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1).astype(np.float32)
+
+
+def stabilized_boxes(H: np.ndarray | None, xywh: np.ndarray) -> np.ndarray:
+    """The boxes of a frame in the reference frame: warped through H, or a copy while no transform is known."""
+    return warp_boxes(H, xywh) if H is not None else xywh.copy()
+
+
+def work_to_frame(Hw: np.ndarray, ratio: float) -> np.ndarray:
+    """A transform between working-resolution images (downsample_ratio `ratio`) as one between the frames: working pixels ->
+    frame pixels on both sides, D^-1 Hw D with D = diag(ratio, ratio, 1), normalised by its [2, 2]."""
+    D = np.diag([ratio, ratio, 1.0])
+    Hf = np.linalg.inv(D) @ Hw @ D
+    return Hf / Hf[2, 2]
+
+
+class LastKnown:
+    """stabilo's `trans_matrix_last_known`: a frame that cannot be registered (too few matches, no model) takes the previous
+    valid transform for its boxes and reports it as its matrix; before the first valid one there is none. `copy`: keep a copy
+    of every valid transform and hand out copies of it (False: the caller's own array is kept and handed out)."""
+
+    def __init__(self, copy: bool = True):
+        self.H, self._copy = None, copy
+
+    def reset(self) -> None:
+        self.H = None
+
+    def update(self, H: np.ndarray | None) -> tuple[np.ndarray | None, bool]:
+        """H: this frame's own transform or None -> (the transform the frame takes, whether it is the last known one)."""
+        if H is not None:
+            self.H = H.copy() if self._copy else H
+            return H, False
+        if self.H is None:
+            return None, False
+        return (self.H.copy() if self._copy else self.H), True
 
 
 def apply_homography(input_x: np.ndarray, input_y: np.ndarray, homography: np.ndarray) -> tuple[np.ndarray, np.ndarray]:

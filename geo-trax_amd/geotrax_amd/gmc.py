@@ -16,6 +16,8 @@ from ._lib import check, ptr
 
 
 class GMC:
+    wants_frames = False             # works on the detector's half-resolution gray image (EccGMC: on the BGR frames)
+
     def __init__(self, frame_hw: tuple[int, int], method: str = "sparseOptFlow", downscale: int = 2, seed: int = 0,
                  ctx: _lib.Context | None = None):
         if method in (None, "none", "None"):
@@ -126,6 +128,8 @@ class FeatureGMC:
     Stated differences from the OpenCV calls upstream makes: the matcher's query is the CURRENT frame (stabilo's rule; upstream
     queries with the previous one), no detection-box mask, SIFT with OpenCV's default thresholds (upstream: contrast 0.02, edge 20).
     Interface of GMC above."""
+
+    wants_frames = False
 
     def __init__(self, frame_hw: tuple[int, int], method: str = "orb", downscale: int = 2, seed: int = 0, ctx: _lib.Context | None = None,
                  max_features: int = 1000):

@@ -266,7 +266,7 @@ class YOLO:
 
                 self._gmc = make_gmc(frame.shape[:2], method=self._gmc_method, ctx=self.ctx)
             g = self._det.gray_dptr(0) if self._det is not None else (0, 0, 0)
-            if getattr(self._gmc, "wants_frames", False):   # ecc: the blur comes before the reduction, it works on the frame itself
+            if self._gmc.wants_frames:                      # ecc: the blur comes before the reduction, it works on the frame itself
                 warp = self._gmc.apply(frame)
             elif g[0] and (g[1], g[2]) == (frame.shape[0] // 2, frame.shape[1] // 2):
                 self._gmc.submit_gray_dev(g[0], g[1], g[2])  # the half-resolution gray the detector left in HBM

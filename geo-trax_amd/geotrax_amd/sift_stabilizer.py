@@ -24,6 +24,7 @@ import numpy as np
 
 from . import _lib, geometry
 from ._lib import SiftStabConfig, check, ptr
+from .stabilizer_base import _StabilizerBase, check_options
 
 logger = logging.getLogger(__name__)
 
@@ -38,7 +39,9 @@ def resident(stab_kw: dict | None) -> bool:
             and not kw.get("clahe", False) and str(kw.get("matcher_name", "bf")) in ("bf", "flann"))
 
 
-class SiftStabilizer:
+class SiftStabilizer(_StabilizerBase):
+    _destroy, _log = "gtx_sift_stab_destroy", logger
+
     def __init__(self, frame_hw: tuple[int, int], *, detector_name: str = "rsift", matcher_name: str = "bf", filter_type: str = "ratio",
                  transformation_type: str = "projective", clahe: bool = False, downsample_ratio: float = 0.5, max_features: int = 2000,
                  ref_multiplier: float = 2.0, filter_ratio: float = 0.9, ransac_method: int = 38, ransac_epipolar_threshold: float = 2.0,
@@ -47,63 +50,28 @@ class SiftStabilizer:
                  ctx: _lib.Context | None = None, **unused):
         if detector_name not in ("sift", "rsift"):
             raise NotImplementedError(f"detector_name='{detector_name}': SiftStabilizer runs 'sift' and 'rsift' (Stabilizer runs 'orb')")
-        if not unused.get("sift_enable_precise_upscale", False):
-            logger.warning(f"detector_name='{detector_name}': this build's SIFT doubles the base image with OpenCV's precise (half-pixel aligned) "
-                           "upscaling; `sift_enable_precise_upscale: false` (default.yaml:112) is not implemented -- keypoints sit ~0.25 px from where "
-                           "stabilo's default would put them, on both frames alike")
-        if filter_type != "ratio" or transformation_type != "projective" or clahe:
-            raise NotImplementedError(f"detector_name='{detector_name}' is built with filter_type 'ratio', transformation_type 'projective' and clahe off")
-        if float(downsample_ratio) != 0.5:
-            raise NotImplementedError(f"detector_name='{detector_name}' on the gray image in HBM needs downsample_ratio 0.5 (got {downsample_ratio}): "
-                                      "Stabilizer runs other ratios on host frames")
-        if matcher_name == "flann":
-            logger.warning("matcher_name='flann': matched with the exact brute-force kernel (what FLANN approximates); a stabilo run with FLANN "
-                           "may keep slightly different matches")
-        elif matcher_name != "bf":
-            raise NotImplementedError(f"matcher_name='{matcher_name}': 'bf' (exact brute force) and 'flann' (served by the same exact kernel) are implemented")
+        check_options(logger, detector_name, matcher_name, filter_type, transformation_type, clahe, unused.get("sift_enable_precise_upscale", False),
+                      hbm_ratio=downsample_ratio)
+        super().__init__(min_good_match_count_warning, min_inliers_match_count_warning)
         self.ctx = ctx or _lib.default_context()
         self.frame_hw = (int(frame_hw[0]), int(frame_hw[1]))
         self.work_hw = (self.frame_hw[0] // 2, self.frame_hw[1] // 2)
         self._ratio = float(downsample_ratio)
-        self.min_good, self.min_inl = min_good_match_count_warning, min_inliers_match_count_warning
         cfg = SiftStabConfig(work_h=self.work_hw[0], work_w=self.work_hw[1], max_features=max(int(max_features), 4), ref_multiplier=ref_multiplier,
                              root=int(detector_name == "rsift"), rsift_eps=rsift_eps, filter_ratio=filter_ratio,
                              ransac_threshold=ransac_epipolar_threshold, ransac_max_iter=ransac_max_iter, ransac_confidence=ransac_confidence,
                              mask_use=int(bool(mask_use)), mask_margin_ratio=mask_margin_ratio, downsample_ratio=self._ratio, seed=int(seed))
-        self.handle = None
         h = C.c_void_p()
         check(self.ctx.lib.gtx_sift_stab_create(self.ctx.handle, C.byref(cfg), C.byref(h)))
         self.handle = h
-        self._H = None                   # what get_cur_trans_matrix() returns: this frame's transform, else the last known one
-        self._H_raw = None               # this frame's own transform, None when the frame could not be registered
-        self._H_last_known = None
         self._H_work = None              # this frame's own transform in working-resolution pixels, as the library returned it
-        self._stats = np.zeros(4, np.int32)
-        self._cur_boxes = None
-        self._pending_boxes = None
         self._mask_use = bool(mask_use)
         self._rects_warned = False
 
-    # ---- lifecycle
-    def close(self):
-        if getattr(self, "handle", None):
-            self.ctx.lib.gtx_sift_stab_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _boxes(self, boxes):
-        if boxes is None or len(boxes) == 0:
-            return None, 0
-        b = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 4)
+    def _check_mask(self, b):
         if len(b) > MAX_MASK_RECTS and self._mask_use and not self._rects_warned:
             self._rects_warned = True
             logger.warning(f"{len(b)} boxes: the vehicle mask holds {MAX_MASK_RECTS} rectangles, keypoints on the boxes beyond them reach the matcher")
-        return b, len(b)
 
     # ---- stabilo interface, on the gray image in HBM
     def set_ref_frame(self, frame, boxes=None) -> None:
@@ -112,33 +80,20 @@ class SiftStabilizer:
     def set_ref_gray_dev(self, gray_dptr: int, gh: int, gw: int, boxes=None) -> None:
         b, n = self._boxes(boxes)
         check(self.ctx.lib.gtx_sift_stab_set_ref_gray_dev(self.handle, C.c_void_p(gray_dptr), gh, gw, ptr(b), n))
-        self._H = self._H_raw = self._H_last_known = self._H_work = None
-        self._cur_boxes = None
+        self._H_work = None
+        self._new_reference()
 
-    def _finish(self, Hw, valid, boxes):
-        # stabilo keeps `trans_matrix_last_known`: a frame that cannot be registered (too few matches, no model) takes the
-        # previous valid transform for its boxes and reports it as its matrix; before the first valid one there is none.
-        self._H_work = self._H_raw = None
-        if valid.value:
-            self._H_work = Hw.reshape(3, 3).copy()
-            r = self._ratio
-            D = np.diag([r, r, 1.0])
-            Hf = np.linalg.inv(D) @ self._H_work @ D                         # working-resolution pixels -> frame pixels on both sides
-            self._H_raw = Hf / Hf[2, 2]
-            self._H_last_known = self._H_raw
-        self._H = self._H_last_known
-        self._cur_boxes = boxes
-        if self._stats[2] < self.min_good:
-            logger.warning(f"Only {int(self._stats[2])} good matches found.")
-        elif self._H is not None and self._stats[3] < self.min_inl:
-            logger.warning(f"Only {int(self._stats[3])} inliers found.")
+    def _result(self, Hw, valid, boxes):
+        """What the library wrote for a frame: Hw[9] in working-resolution pixels, valid 0 when the frame could not be registered."""
+        self._H_work = Hw.reshape(3, 3).copy() if valid.value else None
+        self._finish(None if self._H_work is None else geometry.work_to_frame(self._H_work, self._ratio), boxes)
 
     def stabilize_gray_dev(self, gray_dptr: int, gh: int, gw: int, boxes=None) -> None:
         b, n = self._boxes(boxes)
         H, valid = np.zeros(9, np.float64), C.c_int()
         check(self.ctx.lib.gtx_sift_stab_stabilize_gray_dev(self.handle, C.c_void_p(gray_dptr), gh, gw, ptr(b), n, ptr(H), C.byref(valid),
                                                             ptr(self._stats)))
-        self._finish(H, valid, b)
+        self._result(H, valid, b)
 
     def submit_gray_dev(self, gray_dptr: int, gh: int, gw: int, boxes=None) -> None:
         """Asynchronous stabilize: enqueue on the object's stream; pair with collect()."""
@@ -149,7 +104,7 @@ class SiftStabilizer:
     def collect(self) -> None:
         H, valid = np.zeros(9, np.float64), C.c_int()
         check(self.ctx.lib.gtx_sift_stab_collect(self.handle, ptr(H), C.byref(valid), ptr(self._stats)))
-        self._finish(H, valid, self._pending_boxes)
+        self._result(H, valid, self._pending_boxes)
 
     def last_ms(self) -> float:
         """GPU time (ms) of the last collected pass."""
@@ -157,37 +112,9 @@ class SiftStabilizer:
         check(self.ctx.lib.gtx_sift_stab_last_ms(self.handle, C.byref(ms)))
         return float(ms.value)
 
-    def get_cur_trans_matrix(self, raw: bool = False) -> np.ndarray | None:
-        """3x3 float64 mapping current-frame pixels to reference-frame pixels, or None. raw=True: None also when this
-        frame itself could not be registered."""
-        H = self._H_raw if raw else self._H
-        return None if H is None else H.copy()
-
     def working_matrix(self) -> np.ndarray | None:
         """This frame's own transform in working-resolution pixels, exactly as the library returned it (None: not registered)."""
         return None if self._H_work is None else self._H_work.copy()
-
-    @property
-    def registered(self) -> bool:
-        """False when the last frame took the last known transform (or none) instead of one of its own."""
-        return self._H_raw is not None
-
-    def transform_cur_boxes(self) -> np.ndarray:
-        """The boxes given with the last frame, mapped into the reference frame (xywh)."""
-        if self._cur_boxes is None:
-            return np.zeros((0, 4), np.float32)
-        if self._H is None:
-            return self._cur_boxes.copy()
-        return geometry.warp_boxes(self._H, self._cur_boxes)
-
-    def get_cur_num_keypoints(self) -> tuple[int, int]:
-        return int(self._stats[0]), int(self._stats[1])  # (reference, current)
-
-    def get_cur_num_matches(self) -> int:
-        return int(self._stats[2])
-
-    def get_cur_inliers_count(self) -> int:
-        return int(self._stats[3])
 
     # ---- introspection for the parity tests
     def keypoints(self, which: str = "cur") -> dict:

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _lib, geometry
 from ._lib import StabConfig, check, ptr
+from .stabilizer_base import _StabilizerBase, check_options
 
 logger = logging.getLogger(__name__)
 
@@ -35,7 +36,9 @@ def working_size(frame_hw: tuple[int, int], ratio: float) -> tuple[int, int]:
     return int(np.rint(h * r)), int(np.rint(w * r))
 
 
-class Stabilizer:
+class Stabilizer(_StabilizerBase):
+    _destroy, _log = "gtx_stabilizer_destroy", logger
+
     def __init__(self, frame_hw: tuple[int, int] | None = None, *, detector_name: str = "orb", matcher_name: str = "bf",
                  filter_type: str = "ratio", transformation_type: str = "projective", clahe: bool = False,
                  downsample_ratio: float = 0.5, max_features: int = 2000, ref_multiplier: float = 2.0,
@@ -48,19 +51,7 @@ class Stabilizer:
         if detector_name not in ("orb", "sift", "rsift"):
             raise NotImplementedError(f"detector_name='{detector_name}': 'orb', 'sift' and 'rsift' are implemented (not brisk / kaze / akaze)")
         self._sift = detector_name if detector_name != "orb" else None
-        if self._sift and not unused.get("sift_enable_precise_upscale", False):
-            logger.warning(f"detector_name='{detector_name}': this build's SIFT doubles the base image with OpenCV's precise (half-pixel aligned) "
-                           "upscaling; `sift_enable_precise_upscale: false` (default.yaml:112) is not implemented -- keypoints sit ~0.25 px from where "
-                           "stabilo's default would put them, on both frames alike")
-        if self._sift and (filter_type != "ratio" or transformation_type != "projective" or clahe):
-            raise NotImplementedError(f"detector_name='{detector_name}' is built with filter_type 'ratio', transformation_type 'projective' and clahe off")
-        if matcher_name == "flann":
-            # FLANN returns APPROXIMATE nearest neighbours (LSH for binary descriptors, kd-trees for SIFT); the GPU matcher is exact
-            # and faster than either here, so the option runs on it: the matches are the ones FLANN approximates, not FLANN's own
-            logger.warning("matcher_name='flann': matched with the exact brute-force kernel (what FLANN approximates); a stabilo run with FLANN "
-                           "may keep slightly different matches")
-        elif matcher_name != "bf":
-            raise NotImplementedError(f"matcher_name='{matcher_name}': 'bf' (exact brute force) and 'flann' (served by the same exact kernel) are implemented")
+        check_options(logger, detector_name, matcher_name, filter_type, transformation_type, clahe, unused.get("sift_enable_precise_upscale", False))
         if filter_type not in ("ratio", "none"):
             raise NotImplementedError(f"filter_type='{filter_type}': only 'ratio' and 'none' are implemented")
         if transformation_type not in ("projective", "affine"):
@@ -71,8 +62,7 @@ class Stabilizer:
                         ransac_confidence=ransac_confidence, mask_use=int(mask_use), mask_margin_ratio=mask_margin_ratio,
                         fast_threshold=fast_threshold, n_levels=n_levels, scale_factor=scale_factor, seed=seed, clahe=int(bool(clahe)),
                         affine=int(transformation_type == "affine"), filter_type=int(filter_type == "none"))
-        self.min_good, self.min_inl = min_good_match_count_warning, min_inliers_match_count_warning
-        self.handle = None
+        super().__init__(min_good_match_count_warning, min_inliers_match_count_warning)
         self.frame_hw = None
         self._ref_img = None
         self._mask_warned = False
@@ -80,11 +70,6 @@ class Stabilizer:
             self._create(frame_hw)
         elif frame_hw is not None:
             self.frame_hw = (int(frame_hw[0]), int(frame_hw[1]))
-        self._H = None                   # what get_cur_trans_matrix() returns: this frame's transform, else the last known one
-        self._H_raw = None               # this frame's own transform, None when the frame could not be registered
-        self._H_last_known = None
-        self._stats = np.zeros(4, np.int32)
-        self._cur_boxes = None
 
     # ---- lifecycle
     def _create(self, frame_hw):
@@ -92,24 +77,6 @@ class Stabilizer:
         h = C.c_void_p()
         check(self.ctx.lib.gtx_stabilizer_create(self.ctx.handle, C.byref(cfg), C.byref(h)))
         self.handle, self.frame_hw = h, (int(frame_hw[0]), int(frame_hw[1]))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.ctx.lib.gtx_stabilizer_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @staticmethod
-    def _boxes(boxes):
-        if boxes is None or len(boxes) == 0:
-            return None, 0
-        b = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 4)
-        return b, len(b)
 
     # ---- detector_name sift / rsift (default.yaml:109): the registration stage's kernels (csrc/sift.hip, match_l2.hip, the RANSAC of
     # homography.hip behind gtx_register_images) on the working-resolution frames; one blocking call per frame, host frames only
@@ -137,53 +104,33 @@ class Stabilizer:
                                      ransac_confidence=self._kw["ransac_confidence"], rsift_eps=1e-8 if self._sift == "rsift" else -1.0,
                                      seed=self._kw["seed"], ctx=self.ctx)
         self._stats[:] = (stats[1], stats[0], stats[2], stats[3])          # (reference, current, matches, inliers)
-        H = np.zeros(9, np.float64)
-        valid = C.c_int(0)
-        if Hh is not None:
-            r = float(self._kw["downsample_ratio"])
-            D = np.diag([r, r, 1.0])
-            Hf = np.linalg.inv(D) @ Hh @ D                                   # working-resolution pixels -> frame pixels on both sides
-            H[:] = (Hf / Hf[2, 2]).ravel()
-            valid = C.c_int(1)
         b, _ = self._boxes(boxes)
-        self._finish(H, valid, b)
+        self._finish(None if Hh is None else geometry.work_to_frame(Hh, float(self._kw["downsample_ratio"])), b)
 
     # ---- stabilo interface
     def set_ref_frame(self, frame: np.ndarray, boxes: np.ndarray | None = None) -> None:
         if self._sift:
             self._ref_img = self._working(frame)
             self.frame_hw = tuple(np.asarray(frame).shape[:2])
-            self._H = self._H_raw = self._H_last_known = None
-            self._cur_boxes = None
+            self._new_reference()
             return
         f = np.ascontiguousarray(frame, dtype=np.uint8)
         if self.handle is None:
             self._create(f.shape[:2])
         b, n = self._boxes(boxes)
         check(self.ctx.lib.gtx_stabilizer_set_ref_frame(self.handle, ptr(f), f.shape[0], f.shape[1], ptr(b), n))
-        self._H = self._H_raw = self._H_last_known = None
-        self._cur_boxes = None
+        self._new_reference()
 
     def set_ref_gray_dev(self, gray_dptr: int, gh: int, gw: int, boxes=None) -> None:
         if self._sift:
             raise NotImplementedError(f"detector_name='{self._sift}' takes host frames (set_ref_frame / stabilize): run with engine: {{pipelined: false}}")
         b, n = self._boxes(boxes)
         check(self.ctx.lib.gtx_stabilizer_set_ref_gray_dev(self.handle, C.c_void_p(gray_dptr), gh, gw, ptr(b), n))
-        self._H = self._H_raw = self._H_last_known = None
-        self._cur_boxes = None
+        self._new_reference()
 
-    def _finish(self, H, valid, boxes):
-        # stabilo keeps `trans_matrix_last_known`: a frame that cannot be registered (too few matches, no model) takes the
-        # previous valid transform for its boxes and reports it as its matrix; before the first valid one there is none.
-        self._H_raw = H.reshape(3, 3).copy() if valid.value else None
-        if self._H_raw is not None:
-            self._H_last_known = self._H_raw
-        self._H = self._H_last_known
-        self._cur_boxes = boxes
-        if self._stats[2] < self.min_good:
-            logger.warning(f"Only {int(self._stats[2])} good matches found.")
-        elif self._H is not None and self._stats[3] < self.min_inl:
-            logger.warning(f"Only {int(self._stats[3])} inliers found.")
+    def _result(self, H, valid, boxes):
+        """What the library wrote for a frame: H[9] in frame pixels, valid 0 when the frame could not be registered."""
+        self._finish(H.reshape(3, 3).copy() if valid.value else None, boxes)
 
     def stabilize(self, frame: np.ndarray, boxes: np.ndarray | None = None) -> None:
         if self._sift:
@@ -195,14 +142,14 @@ class Stabilizer:
         H, valid = np.zeros(9, np.float64), C.c_int()
         check(self.ctx.lib.gtx_stabilizer_stabilize(self.handle, ptr(f), f.shape[0], f.shape[1], ptr(b), n, ptr(H),
                                                     C.byref(valid), ptr(self._stats)))
-        self._finish(H, valid, b)
+        self._result(H, valid, b)
 
     def stabilize_gray_dev(self, gray_dptr: int, gh: int, gw: int, boxes=None) -> None:
         b, n = self._boxes(boxes)
         H, valid = np.zeros(9, np.float64), C.c_int()
         check(self.ctx.lib.gtx_stabilizer_stabilize_gray_dev(self.handle, C.c_void_p(gray_dptr), gh, gw, ptr(b), n, ptr(H),
                                                              C.byref(valid), ptr(self._stats)))
-        self._finish(H, valid, b)
+        self._result(H, valid, b)
 
     def submit_gray_dev(self, gray_dptr: int, gh: int, gw: int, boxes=None) -> None:
         """Asynchronous stabilize: enqueue on the stabilizer's stream; pair with collect()."""
@@ -213,42 +160,13 @@ class Stabilizer:
     def collect(self) -> None:
         H, valid = np.zeros(9, np.float64), C.c_int()
         check(self.ctx.lib.gtx_stabilizer_collect(self.handle, ptr(H), C.byref(valid), ptr(self._stats)))
-        self._finish(H, valid, self._pending_boxes)
+        self._result(H, valid, self._pending_boxes)
 
     def last_ms(self) -> float:
         """GPU time (ms) of the last collected asynchronous pass."""
         ms = C.c_float()
         check(self.ctx.lib.gtx_stabilizer_last_ms(self.handle, C.byref(ms)))
         return float(ms.value)
-
-    def get_cur_trans_matrix(self, raw: bool = False) -> np.ndarray | None:
-        """3x3 float64 mapping current-frame pixels to reference-frame pixels, or None. raw=True: None also when this
-        frame itself could not be registered (the engine, whose stabilizer objects take turns, keeps the last known
-        transform in frame order itself)."""
-        H = self._H_raw if raw else self._H
-        return None if H is None else H.copy()
-
-    @property
-    def registered(self) -> bool:
-        """False when the last frame took the last known transform (or none) instead of one of its own."""
-        return self._H_raw is not None
-
-    def transform_cur_boxes(self) -> np.ndarray:
-        """The boxes given to the last stabilize() call, mapped into the reference frame (xywh)."""
-        if self._cur_boxes is None:
-            return np.zeros((0, 4), np.float32)
-        if self._H is None:
-            return self._cur_boxes.copy()
-        return geometry.warp_boxes(self._H, self._cur_boxes)
-
-    def get_cur_num_keypoints(self) -> tuple[int, int]:
-        return int(self._stats[0]), int(self._stats[1])  # (reference, current)
-
-    def get_cur_num_matches(self) -> int:
-        return int(self._stats[2])
-
-    def get_cur_inliers_count(self) -> int:
-        return int(self._stats[3])
 
     # ---- introspection for the parity tests
     def promote_cur(self) -> None:

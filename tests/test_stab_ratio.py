@@ -60,7 +60,7 @@ def test_gray_route():
     assert gray_route(dict(detector_name="rsift", downsample_ratio=1.0)) == "host"
     assert gray_route(dict(detector_name="sift", downsample_ratio=0.25)) == "host"      # Stabilizer refuses it at the first frame, as before
     assert gray_route(dict(detector_name="rsift", downsample_ratio=0.5)) == "detector"  # the resident SiftStabilizer chain
-    assert gray_route(None) is None                                             # no stabilizer: ExtractEngine.use_dev_gray is False, nothing to route
+    assert gray_route(None) is None                                             # no stabilizer: ExtractEngine.stab_dev_gray is False, nothing to route
 
 
 def _config(**stab):

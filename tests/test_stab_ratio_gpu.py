@@ -267,7 +267,7 @@ def test_engine_device_batches_equal_blocking_calls(gtx_ctx, tmp_path, ratio, co
     path, kind, off = reader.raw_layout()
     fd = FrameFeeder((H, W), kind=kind, batch=2, ring=6, device=eng.device, ctx=eng.feeder_ctx)
     try:
-        assert eng.gray_route == "frame" and eng.stab_dev_gray and not eng.use_dev_gray
+        assert eng.gray_route == "frame" and eng.stab_dev_gray
         fd.open_file(path, off, n_threads=2)
         got = list(eng.run(fd.batches(len(eng.dets))))
         assert not eng._host_frames                              # no host copies of frames were kept
